@@ -4,6 +4,7 @@
     python bench.py [--gpus N] [--steps K] [--warmup W] [--reps R]
                     [--workload config3|flat|flat10k|config2|config4|config5|10k|64k|256k|512k]
                     [--fast] [--full] [--budget-s S] [--no-cpu] [--no-abi] [--configs1] [--batch B]
+                    [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one raw IQ frame (250 ms of signal: 384 000 cf32 at
 1.536 MS/s), already resident in HBM, through every VFO of the workload.
@@ -20,7 +21,8 @@ overrides the default (with `--workload config5` the roles swap: side object `we
 Timing.  W untimed warm-up steps (plus enough extra to reach ~50 ms of GPU time: the clock ramps),
 then the timed region -- EXACTLY K steps between barrier + torch.cuda.synchronize() on both sides,
 max over ranks -- is repeated R times (default 11); `ms_per_step` and `value` are the MEDIAN
-repetition, min / max are in `ms_per_step_min/max`.
+repetition, min / max are in `ms_per_step_min/max`.  `--dump-outputs DIR` writes what the last timed step delivered
+(the payloads of the workload's leaves, float32 .npy files, at most 64 MB) for a comparison of two builds.
 
 Prints ONE JSON line of at most 8 KB (rank 0): the contract keys, `roofline`, `cpu_baseline`, `verified` and one compact
 row per side workload.  Everything else that is measured (the counters' VALU sub-objects, the instruction mix, the
@@ -217,6 +219,45 @@ class Verifier:
         if bad:
             out["mismatches"] = [{"after_frames": a, "vfo": b} for a, b in bad[:8]]
         return out
+
+
+DUMP_LIMIT = 64 << 20  # bytes: what --dump-outputs writes at most, over all ranks
+DUMP_SEED = 20261015
+
+
+def dump_outputs(job, out_dir, rank=0, world=1):
+    """--dump-outputs: what the last timed step delivered -- the payloads a caller fetches for the frame it handed over last
+    (int16 audio / int8 IQ, written as float32) -- one array per publishing leaf, `out_dir`/vfo<index>.npy (at N > 1
+    rank<r>_vfo<index>.npy, indices of the rank's shard).  Every leaf while they fit in 64 MB (shared by the ranks), else the
+    seeded sample of topology.sample_leaves, cut at that limit.  The same arguments hand the receiver the same frames in the
+    same order, so the files of two builds can be compared one for one.  Returns (arrays, bytes)."""
+    import numpy as np
+    from sdrreceiver_amd import topology as tp
+    rx, topo = job.rx, job.topo
+    if rx is None:
+        return 0, 0
+    rx.set_publish(False)
+    rx.fetch()  # completes the frame pipeline and copies the payloads of the last frame to the host
+    rx.set_publish(True)
+    limit = DUMP_LIMIT // world
+
+    def take(ids):
+        arrays, total = {}, 0
+        for i in ids:
+            a = rx.output(i).astype(np.float32)
+            if total + a.nbytes > limit:
+                return arrays, False
+            arrays[i], total = a, total + a.nbytes
+        return arrays, True
+
+    arrays, whole = take([i for i in range(len(topo.vfos)) if not topo.children(i)])
+    if not whole:
+        arrays, _ = take(tp.sample_leaves(topo, 64, DUMP_SEED))
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for i, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{prefix}vfo{i:05d}.npy"), a)
+    return len(arrays), sum(a.nbytes for a in arrays.values())
 
 
 def pmc_for(workload, exact):
@@ -470,6 +511,9 @@ def main():
     ap.add_argument("--configs1", action="store_true",
                     help="also time BASELINE configs[1] (32 sub VFOs) and report it as a side reading (off by default: the "
                          "profiled default command must launch the kernels of ONE workload only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the payloads the last one delivered to DIR/<name>.npy (float32, <= 64 MB: "
+                         "every leaf of the workload, or a seeded sample of them)")
     args = ap.parse_args()
     arith = args.arith if args.arith is not None else (0 if args.fast else 1)  # option "exact" of the line's own workload
     args.fast = arith != 1                                                      # (the side readings in the other arithmetics ride along with the exact line only)
@@ -661,7 +705,7 @@ def main():
             barrier()
             return allmax(time.perf_counter() - t0)
 
-        def measure(self, steps, warmup, reps, verifier=None):
+        def measure(self, steps, warmup, reps, verifier=None, after_timed=None):
             for k in range(warmup):
                 self.step(k)
             self.realign(warmup)
@@ -674,8 +718,10 @@ def main():
                     self.step(k)
                 self.realign(extra)
             out = []
-            for _ in range(reps):
+            for r in range(reps):
                 out.append(self.timed(steps))
+                if after_timed and r == reps - 1:
+                    after_timed(self)       # outside the region, before anything else is handed to the receiver
                 self.realign(steps)
                 if verifier:
                     verifier.checkpoint()  # outside the timed region: payloads of the frame the region ended on
@@ -770,8 +816,16 @@ def main():
         job = Job(workload)
     topo, rx, st, full, descr = job.topo, job.rx, job.st, job.full, job.descr
     ver = Verifier(job, n_random=64 if args.full else 32) if (rx and not args.no_verify) else None
+    dumped = None
+
+    def dump(j):
+        nonlocal dumped
+        n, nbytes = dump_outputs(j, args.dump_outputs, rank, world)
+        dumped = {"dir": args.dump_outputs, "arrays": n, "bytes": nbytes}
+        print(f"bench: rank {rank}: {n} output arrays ({nbytes / 1e6:.1f} MB) written to {args.dump_outputs}", file=sys.stderr)
+
     with leg("main_measure"):
-        reps = job.measure(args.steps, args.warmup, max(1, n_reps), ver)
+        reps = job.measure(args.steps, args.warmup, max(1, n_reps), ver, dump if args.dump_outputs else None)
     dt = statistics.median(reps)
     vfo_samples, alg_bytes, n_leaves = allsum([st["vfo_samples_per_frame"], st["algorithmic_bytes_per_frame"], st["n_leaves"]])
 
@@ -1038,6 +1092,8 @@ def main():
                 out["configs1_32_sub_vfos"] = {"error": f"{type(e).__name__}: {e}"}
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if dumped:
+            out["dumped_outputs"] = dumped
         out["legs_s"] = legs
         out["wall_s"] = round(time.perf_counter() - t_start, 1)
         write_full(out)

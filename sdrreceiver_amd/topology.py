@@ -269,7 +269,7 @@ def topology_from_ini(text: str, name: str = "") -> Topology:
 
 # ----------------------------------------------------------------------------- BASELINE configs
 # Derived parameters of sample_ini/sdr_25E.ini (reproduced from the INI by
-# tests/test_topology.py where /root/reference is present).
+# tests/test_topology.py, on its copy in tests/golden/sample_ini).
 _25E_MAIN = [(484000, 2), (-496000, 3)]
 _25E_SUBS_MAIN0 = [  # (topic, mixer, d, filter_bw)
     ("VFO01", 110854, 5, 4000), ("VFO02", -98573, 5, 0), ("VFO03", -103706, 5, 0),

@@ -7,7 +7,8 @@ import os
 import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REFERENCE_ROOT = "/root/reference"
+# the reference's shipped INI profiles (its sample_ini/ folder), kept as data fixtures
+SAMPLE_INI = os.path.join(GOLDEN, "sample_ini")
 
 
 def sha(a) -> str:

@@ -143,6 +143,56 @@ def test_printed_line_stays_under_8_kb():
     assert len(json.dumps(slim)) <= 8192 and "roofline" in slim and "cpu_baseline" in slim and "value" in slim
 
 
+def test_dump_outputs_writes_what_a_caller_fetches_within_64_mb(tmp_path):
+    """`--dump-outputs DIR` (bench.dump_outputs), here over a stand-in receiver: the payloads come from a fetch after the last
+    step, one float32 file per publishing leaf -- every leaf of config 3 (31 MB), the seeded sample of the 10 240-sub tree
+    whose leaves would not fit -- never more than 64 MB, the same files every time, rank-prefixed at N > 1."""
+    import numpy as np
+    from sdrreceiver_amd import topology as tp
+    b = _bench()
+
+    class Rx:
+        def __init__(self, topo):
+            self.topo, self.fetched, self.publish = topo, 0, True
+
+        def set_publish(self, on):
+            self.publish = on
+
+        def fetch(self):
+            assert not self.publish  # (the payloads are read below, not handed to a publish callback per leaf)
+            self.fetched += 1
+
+        def output(self, i):
+            assert self.fetched, "payloads read before the fetch that completes the last frame"
+            v = self.topo.vfos[i]
+            n = (v.samples_per_buffer >> v.decimate_count) // (v.late_decimate or 1)
+            return ((np.arange(n) * (i + 1)) % 601 - 300).astype(np.int16 if v.demod_usb else np.int8)
+
+    class Job:
+        def __init__(self, topo):
+            self.topo, self.rx = topo, Rx(topo)
+
+    topo = tp.config3(1024)
+    leaves = [i for i in range(len(topo.vfos)) if not topo.children(i)]
+    n, nbytes = b.dump_outputs(Job(topo), str(tmp_path / "a"))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert n == len(leaves) == len(files) == 1024 and files[0] == f"vfo{leaves[0]:05d}.npy" and nbytes <= b.DUMP_LIMIT
+    a = np.load(tmp_path / "a" / files[-1])
+    rx = Rx(topo)
+    rx.fetched = 1
+    assert a.dtype == np.float32 and np.array_equal(a, rx.output(leaves[-1]).astype(np.float32))
+
+    big = tp.config3(10240)
+    n, nbytes = b.dump_outputs(Job(big), str(tmp_path / "b"))
+    want = tp.sample_leaves(big, 64, b.DUMP_SEED)
+    assert n == len(want) and sorted(os.listdir(tmp_path / "b")) == [f"vfo{i:05d}.npy" for i in want] and nbytes <= b.DUMP_LIMIT
+    assert b.dump_outputs(Job(big), str(tmp_path / "c")) == (n, nbytes)
+    assert all(np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)) for f in os.listdir(tmp_path / "b"))
+
+    n, nbytes = b.dump_outputs(Job(topo), str(tmp_path / "d"), rank=3, world=4)  # 16 MB per rank: 31 MB of leaves are cut
+    assert 0 < n < 1024 and nbytes <= b.DUMP_LIMIT // 4 and all(f.startswith("rank3_vfo") for f in os.listdir(tmp_path / "d"))
+
+
 DRIVER_COMMAND = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"]
 
 

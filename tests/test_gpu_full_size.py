@@ -252,15 +252,8 @@ def test_all_10240_vfos_of_the_north_star_workload_bit_exact():
 
 def test_all_65536_vfos_of_config5_bit_exact():
     """The same for config 5's whole tree: every one of its 65 536 sub VFOs against the oracle, 2 frames, payloads
-    and final cf32 streams (64 oracle batches of 1 024 sub VFOs: 90-113 s on the 64-core host of the MI355X boxes).  On
-    request only (SDRX_EXHAUSTIVE=1) since round 6 -- the GPU suite has a time limit, and what this test adds to the
-    default suite's coverage of that size (the seeded sample with the first and last sub of every shard block, the all-VFO
-    properties, the sha256 over all 65 536 payloads of the sharded form, below) is the 65 000 VFOs in between, whose code path
-    is the one every sub VFO of config 3 and of the 10 240-sub workload is checked on in full.  Logs of exhaustive runs:
-    profiles/r03/exhaustive_config5.txt, profiles/r06/exhaustive_config5.txt."""
-    import os
-    if os.environ.get("SDRX_EXHAUSTIVE") != "1":
-        pytest.skip("64 oracle batches of 1 024 sub VFOs (~100 s): set SDRX_EXHAUSTIVE=1 to run it")
+    and final cf32 streams (64 oracle batches of 1 024 sub VFOs: 90-113 s on the 64-core host of the MI355X boxes).  Logs of
+    earlier exhaustive runs: profiles/r03/exhaustive_config5.txt, profiles/r06/exhaustive_config5.txt."""
     assert _every_sub_vfo_against_the_oracle(tp.config5(65536), 2) == 2 * 65536
 
 

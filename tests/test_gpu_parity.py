@@ -103,17 +103,9 @@ def test_designed_taps_bit_exact(Receiver):
 # two-kernel form of rounds 1-3.  Results must not differ by one bit.
 # Option "fuse_demod" (off by default: measured slower, include/sdrx.h): a d = 2 USB leaf below a parent -- the reference's
 # 48 kS/s sub VFOs -- demodulates inside its mix wave and writes only its int16 payload; with keep_streams also decimate[2].
+# On a tree without such leaves a launch form is the default one, and setting its option must change nothing either.
 LATE_MODES = {"fused": dict(), "fused+streams": dict(keep_streams=True), "two kernels": dict(fuse_late=False),
               "demodulation in the wave": dict(fuse_demod=True), "demodulation in the wave+streams": dict(fuse_demod=True, keep_streams=True)}
-
-
-def _mode_applies(topo, late):
-    """does launch form `late` differ from the default on this tree?"""
-    if late == "fused":
-        return True
-    if late.startswith("demodulation"):
-        return any(v.demod_usb and v.parent >= 0 and not v.late_decimate and v.decimate_count == 2 for v in topo.vfos)
-    return any(v.late_decimate for v in topo.vfos)
 
 
 @pytest.mark.parametrize("late", sorted(LATE_MODES))
@@ -123,8 +115,6 @@ def test_exact_mode_against_reference_fixtures(Receiver, fixture, late):
     payload and stream on every VFO and frame (crosses the NCO table wrap, > 1 s of signal)."""
     key, frames = GOLDEN_TREES[fixture]
     topo = golden_topology(key)
-    if not _mode_applies(topo, late):
-        pytest.skip("this launch form is the default one on this tree")
     g = golden(fixture)
     rx = Receiver.from_topology(topo, exact=True, **LATE_MODES[late])
     for f, iq in _frames(topo, frames):
@@ -141,8 +131,6 @@ def test_exact_mode_against_reference_fixtures(Receiver, fixture, late):
 @pytest.mark.parametrize("key,frames", [("config1", 5), ("profile_25e", 5), ("54w", 3), ("288k", 6), ("compress", 2)])
 def test_exact_mode_against_live_oracle(Receiver, key, frames, late):
     topo = golden_topology(key)
-    if not _mode_applies(topo, late):
-        pytest.skip("this launch form is the default one on this tree")
     rx = Receiver.from_topology(topo, exact=True, **LATE_MODES[late])
     nodes, roots = ob.build_tree("port", topo)
     for f, iq in _frames(topo, frames, seed=11, tones=[(-377000.0, 25.0), (251000.0, 11.0)]):
@@ -291,8 +279,6 @@ def test_config4_256_vfos_vs_cpu(Receiver, late):
     """BASELINE config 4: 1.92 MS/s, 3 mains, 256 late-decimate subs with the 10 kHz low-pass: every payload (and, where
     decimate[0] is kept, every stream) of all 256 bit-identical to the oracle."""
     topo = tp.config4(256)
-    if not _mode_applies(topo, late):
-        pytest.skip("this launch form is the default one on this tree")
     rx = Receiver.from_topology(topo, exact=True, **LATE_MODES[late])
     nodes, roots = ob.build_tree("port", topo)
     for f, iq in _frames(topo, 2, seed=2):
@@ -679,14 +665,20 @@ def test_group_of_contexts_in_one_process(members, key):
 
 
 def test_group_over_distinct_devices():
-    """The same, over DISTINCT device ordinals: runs by itself wherever the box has two or more GPUs (the
-    1-GPU test box skips it) -- the branches no same-device run reaches: hipMemcpyPeerAsync between two
-    devices, peer-access enabling, the cross-device hipStreamWaitEvent on the first device's frame event.
-    A host-staged fallback of the peer copies is not an error but must be visible (sdrx_group_peer_access)."""
+    """The same, over DISTINCT device ordinals, wherever the box has two or more GPUs -- the branches no same-device
+    run reaches: hipMemcpyPeerAsync between two devices, peer-access enabling, the cross-device hipStreamWaitEvent on
+    the first device's frame event.  A host-staged fallback of the peer copies is not an error but must be visible
+    (sdrx_group_peer_access).  On a box with one GPU the ordinal of a second device does not exist: the group must
+    refuse it before it touches any device (SdrxError naming the ordinal), and a group of two shards on the one device
+    still works after that refusal."""
     import torch
+    from sdrreceiver_amd.receiver import Group, SdrxError
     n = torch.cuda.device_count()
     if n < 2:
-        pytest.skip(f"{n} GPU(s) here: the distinct-device group needs >= 2")
+        with pytest.raises(SdrxError, match=f"device {n} out of range"):
+            Group([0, n])
+        _group_body([0, 0], "profile_25e")
+        return
     for key in ("profile_25e", "config3-64"):
         g = _group_body(list(range(min(n, 8))), key)
         print(f"group over {min(n, 8)} devices, {key}: peer access {'direct' if g else 'HOST-STAGED'}")

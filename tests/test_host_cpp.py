@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import REFERENCE_ROOT
+from helpers import SAMPLE_INI
 from sdrreceiver_amd import synth, topology as tp
 from test_topology import INI_25E_LIKE
 
@@ -82,9 +82,8 @@ def test_cpp_ini_front_door_matches_python_rules(ini, tmp_path):
     _check_dump(_dump(ini, tmp_path), tp.topology_from_ini(ini))
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_ROOT), reason="needs the reference's sample INIs")
 def test_cpp_ini_front_door_on_shipped_profiles(tmp_path):
-    d = os.path.join(REFERENCE_ROOT, "sample_ini")
+    d = SAMPLE_INI
     for name in sorted(os.listdir(d)):
         text = open(os.path.join(d, name), encoding="utf-8", errors="replace").read()
         _check_dump(_dump(text, tmp_path), tp.topology_from_ini(text))
@@ -92,7 +91,7 @@ def test_cpp_ini_front_door_on_shipped_profiles(tmp_path):
 
 def test_cpp_ini_front_door_under_sanitizers(tmp_path):
     """host/sdrx_host.hpp's parser and tree builder under ASan + UBSan (leak check on), on the INIs of
-    this file and -- where present -- every shipped sample profile."""
+    this file and every shipped sample profile (tests/golden/sample_ini)."""
     exe = tmp_path / "demo_san"
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", str(exe),
                            os.path.join(ROOT, "host", "demo.cpp"), "-L" + os.path.join(ROOT, "sdrreceiver_amd"), "-lsdrx",
@@ -102,9 +101,7 @@ def test_cpp_ini_front_door_under_sanitizers(tmp_path):
         p = tmp_path / f"p{k}.ini"
         p.write_text(text)
         inis.append(str(p))
-    d = os.path.join(REFERENCE_ROOT, "sample_ini")
-    if os.path.isdir(d):
-        inis += [os.path.join(d, n) for n in sorted(os.listdir(d))]
+    inis += [os.path.join(SAMPLE_INI, n) for n in sorted(os.listdir(SAMPLE_INI))]
     for ini in inis:
         r = subprocess.run([str(exe), ini, "--dump"], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
         assert r.returncode == 0 and r.stderr == "", (ini, r.stderr[-1500:])

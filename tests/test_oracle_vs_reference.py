@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import REFERENCE_ROOT, bits, golden_topology, sha
+from helpers import SAMPLE_INI, bits, golden_topology, sha
 from oracle import binding as ob
 from sdrreceiver_amd import synth, topology as tp
 
@@ -99,13 +99,12 @@ def test_fir_newest_sample_excluded():
     assert list(y) == [0, 100, 210, 321, 432]
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_ROOT), reason="needs the reference's sample INIs")
 def test_ini_parser_matches_qsettings():
     _try_reference()
     R = ob.load("reference")
     fn = R.fn("qsettings_dump")
     fn.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
-    ini_dir = os.path.join(REFERENCE_ROOT, "sample_ini")
+    ini_dir = SAMPLE_INI
     for name in sorted(os.listdir(ini_dir)):
         path = os.path.join(ini_dir, name)
         buf = C.create_string_buffer(1 << 20)

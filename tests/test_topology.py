@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import REFERENCE_ROOT
+from helpers import SAMPLE_INI
 from sdrreceiver_amd import synth, topology as tp
 
 INI_25E_LIKE = """
@@ -107,14 +107,13 @@ size=2
         tp.topology_from_ini("sample_rate=1000000\n")
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_ROOT), reason="needs the reference's sample INIs")
 def test_shipped_profiles_reproduce_embedded_tables():
-    ini = open(os.path.join(REFERENCE_ROOT, "sample_ini", "sdr_25E.ini"), encoding="utf-8", errors="replace").read()
+    ini = open(os.path.join(SAMPLE_INI, "sdr_25E.ini"), encoding="utf-8", errors="replace").read()
     t, e = tp.topology_from_ini(ini), tp.profile_25e()
     assert len(t.vfos) == len(e.vfos) == 29
     for a, b in zip(t.vfos, e.vfos):
         assert a == b, (a, b)
-    ini = open(os.path.join(REFERENCE_ROOT, "sample_ini", "sdr_54W_all.ini"), encoding="utf-8", errors="replace").read()
+    ini = open(os.path.join(SAMPLE_INI, "sdr_54W_all.ini"), encoding="utf-8", errors="replace").read()
     t = tp.topology_from_ini(ini)
     # SURVEY.md appendix A
     assert [(v.mixer_freq, v.decimate_count) for v in t.vfos[:3]] == [(819000.0, 3), (-181000.0, 3), (-911000.0, 3)]
