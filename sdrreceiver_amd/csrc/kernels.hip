@@ -154,36 +154,6 @@ __device__ __forceinline__ v4f gldv4(const float4 *p) { return *(const SDRX_AS1 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ v4u gldv4u(const v4u *p) { return *(const SDRX_AS1 v4u *)p; }
 __device__ __forceinline__ void gstv2(float2 *p, v2f v) { *(SDRX_AS1 v2f *)p = v; }
-// Experiment switch -DSDRX_NT=1 (profiles/README.md, round 3): the leaf streams -- written by the mix/decimate launch,
-// read exactly once by the demodulation ~40 us later -- with the non-temporal hint on both sides.
-#ifndef SDRX_NT
-#define SDRX_NT 0
-#endif
-__device__ __forceinline__ void gstv2_leaf(float2 *p, v2f v)
-{
-#if SDRX_NT
-    __builtin_nontemporal_store(v, (SDRX_AS1 v2f *)p);
-#else
-    *(SDRX_AS1 v2f *)p = v;
-#endif
-}
-__device__ __forceinline__ void gstv4_leaf(float4 *p, v4f v)
-{
-#if SDRX_NT
-    __builtin_nontemporal_store(v, (SDRX_AS1 v4f *)p);
-#else
-    *(SDRX_AS1 v4f *)p = v;
-#endif
-}
-__device__ __forceinline__ float2 gld2_once(const float2 *p)
-{
-#if SDRX_NT
-    const v2f v = __builtin_nontemporal_load((const SDRX_AS1 v2f *)p);
-#else
-    const v2f v = *(const SDRX_AS1 v2f *)p;
-#endif
-    return make_float2(v.x, v.y);
-}
 __device__ __forceinline__ void gstv4(float4 *p, v4f v) { *(SDRX_AS1 v4f *)p = v; }
 // Stores that are ALWAYS issued, lanes that have nothing to store included: a buffer store whose offset lies beyond the
 // resource's num_records is dropped by the hardware, so "this lane does not store" is an offset, not a branch -- and a
@@ -364,21 +334,6 @@ __device__ __forceinline__ size_t tile_pos(int g)
 {
     const int c = g >> 10, r = g & 1023, ln = r >> 4, i = r & 15;
     return (size_t)c * 1024 + (i >> 1) * 128 + ln * 2 + (i & 1);
-}
-
-// 16-byte units from one buffer to another, either of which may be pinned HOST memory reached over PCIe: the payloads' way
-// out (sdrx.hip, enqueue_frame).  Grid-stride with four units per thread in flight; the launch decides how much of the chip it
-// may occupy -- a PCIe-bound copy needs bytes in flight, not CUs.
-__global__ __launch_bounds__(256) void k_copy16(const uint4 *__restrict__ src, uint4 *__restrict__ dst, size_t n16)
-{
-    const size_t stride = (size_t)gridDim.x * 256;
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    for (; i + 3 * stride < n16; i += 4 * stride) {
-        const uint4 a = src[i], b = src[i + stride], c = src[i + 2 * stride], d = src[i + 3 * stride];
-        dst[i] = a, dst[i + stride] = b, dst[i + 2 * stride] = c, dst[i + 3 * stride] = d;
-    }
-    for (; i < n16; i += stride)
-        dst[i] = src[i];
 }
 
 // natural cf32 frame -> tile layout (host-fed / broadcast raw frames enter the pipeline here)
@@ -1056,7 +1011,7 @@ __device__ __forceinline__ void hb_stage_lds(v2f *__restrict__ A, v2f *__restric
             if (tiled)
                 gstv2(gout + tile_pos(gbase + j), y);
             else
-                gstv2_leaf(gout + (size_t)(gbase + j), y);
+                gstv2(gout + (size_t)(gbase + j), y);
         }
     }
     wave_sync(); // all window reads done before the carry is overwritten
@@ -1075,13 +1030,10 @@ __device__ __forceinline__ void hb_stage_lds(v2f *__restrict__ A, v2f *__restric
 // that does not hold the frame's last sample -- with the depth as a compile-time constant: every count, LDS offset
 // and trip count folds, the per-stage loop, the tiled / natural and last / not-last selects and the save branch
 // disappear (the generic routine spends about as many VALU instructions on them as on the 11-operation dot product).
-// Same arithmetic, same order, same LDS contents afterwards.  -DSDRX_FIXED_STAGES=0 switches it off (A/B).
-#ifndef SDRX_FIXED_STAGES
-#define SDRX_FIXED_STAGES 1
-#endif
+// Same arithmetic, same order, same LDS contents afterwards.
 constexpr int kFixedDepth = 5; // 1.536 MS/s / 384 kS/s -> 48 / 12 kS/s: the depth of the reference's sub VFOs below a 384 k main
 // Stage S of a full chunk: A_S = [16 carry | M * (1024 >> S) inputs] -> outputs into B's data from entry `boff` on, or -- the last stage --
-// to the leaf's stream.  M = 2: the stage runs every SECOND chunk on two chunks' worth of input (SDRX_PAIR_STAGES: stages >= 3
+// to the leaf's stream.  M = 2: the stage runs every SECOND chunk on two chunks' worth of input (paired stages: stages >= 3
 // of a d = 5 leaf, whose last stage otherwise fills 32 of the 64 lanes; one carry hand-over and one set of phase fences per
 // two chunks).  Same arithmetic on the same values in the same order: an output does not know how many of its neighbours
 // were computed in the same pass.
@@ -1147,9 +1099,6 @@ __device__ __forceinline__ void hb_stage_fixed(v2f *__restrict__ lds, HeldStores
     if constexpr (S + 1 < D)
         hb_stage_fixed<EXACT, S + 1, D, M>(lds, held, gbase, jmin, lane);
 }
-#ifndef SDRX_PAIR_STAGES
-#define SDRX_PAIR_STAGES 1
-#endif
 
 // NOUT outputs of a register-resident stage.  ext[k] holds input sample k-10 of this lane's run
 // (k = 0..9: the halo, only the needed ones set).
@@ -1324,28 +1273,18 @@ __device__ __forceinline__ short to_short(double d)
 // an fp32 form with identical results -- the exact difference of two floats rounded to 53 and then to 24
 // bits is the fp32 subtraction (double rounding is innocuous for + - * / when the wide format has
 // >= 2*24 + 2 significand bits), and `float * 2^15` is exact in either format with v_cvt_i32_f32
-// saturating like v_cvt_i32_f64 -- which -DSDRX_DEMOD_F32 selects: all 115 GPU parity tests pass with it,
-// and it is not faster (k_usb_demod 35.8-37.0 vs 35.7-36.6 us on config 3), so the literal form stays.
+// saturating like v_cvt_i32_f64: all 115 GPU parity tests passed with that form, and it was not faster (k_usb_demod
+// 35.8-37.0 vs 35.7-36.6 us on config 3), so the literal form stays.
 __device__ __forceinline__ float usb_difference(float delayed_i, float hilbert)
 {
-#ifndef SDRX_DEMOD_F32
     return (float)((double)delayed_i - (double)hilbert);
-#else
-    return delayed_i - hilbert;
-#endif
 }
 __device__ __forceinline__ float quantise(float scaled, short &out)
 {
-#ifndef SDRX_DEMOD_F32
     const double pre = (double)scaled * 32768.0;
     // |pre| < 2^31 <=> |scaled| < 2^16 (the product is exact): the range test of to_short() as ONE fp32 compare
     out = fabsf(scaled) < 65536.0f ? (short)(unsigned short)(unsigned)(int)pre : (short)0;
     return (float)pre; // exact: float * 2^15
-#else
-    const float pre = scaled * 32768.0f;
-    out = (short)(unsigned short)(unsigned)((pre >= -2147483648.0f && pre < 2147483648.0f) ? (int)pre : (int)0x80000000);
-    return pre;
-#endif
 }
 
 
@@ -1547,9 +1486,9 @@ __device__ __forceinline__ void demod_chunk(float *dm, const DemodCtx &C, const 
 }
 
 // Fused NCO + mixer + half-band cascade.
-#ifndef SDRX_K1_MIN_WAVES
-#define SDRX_K1_MIN_WAVES 5 // waves per SIMD the register allocator must leave room for
-#endif
+// Waves per SIMD the register allocator must leave room for: 5 (at 6, 80 VGPRs, the tolerance arithmetic spills inside its
+// chunk loop: k_mix_levels 102 vs 60 us on config 3; profiles/README.md round 6).
+constexpr int kK1MinWaves = 5;
 // The body of one work item, run by ONE wave on LDS of its own (`smem`: k1_lds_bytes()); `level0`: the
 // item's VFO is fed by the raw frame (`raw`, `raw_mode`), otherwise by its parent's tile-layout stream.
 // DM: the leaf demodulates its stream in this very wave (demod_chunk; DEPTH == 2 only) -- decimate[2] itself is then written only
@@ -1629,7 +1568,7 @@ __device__ __forceinline__ void mix_item(const K1Vfo *__restrict__ vfos, const K
         if constexpr (DM) { // (nothing is ever held: the payload leaves where it arises, 8 bytes per lane and chunk)
         } else if constexpr (!kShape) { // (the any-VFO body stores at once: an ordinary conditional store)
             if (held.units == 1 && lane >= held.jmin && lane < held.nout)
-                gstv2_leaf(out + (size_t)(held.gbase + lane), held.one);
+                gstv2(out + (size_t)(held.gbase + lane), held.one);
         } else if constexpr (DEPTH == 2) {
             const __amdgpu_buffer_rsrc_t out_rsrc = stream_rsrc(out);
             // (a lane reads back what it wrote itself: no fence needed; before the first chunk the LDS holds anything -- and
@@ -1647,7 +1586,7 @@ __device__ __forceinline__ void mix_item(const K1Vfo *__restrict__ vfos, const K
         }
         held.units = 0;
     };
-    int pair_base = -1; // >= 0: the stage-2 outputs of the chunk at this position wait in A_3 for the next chunk's (SDRX_PAIR_STAGES)
+    int pair_base = -1; // >= 0: the stage-2 outputs of the chunk at this position wait in A_3 for the next chunk's (paired stages)
     for (int base = W.s_begin; base < W.s_end; base += kChunk) {
         const int valid = min(kChunk, D.n_in - base);
         const int p16 = (base >> 4) + lane;               // this lane's run, in units of 16 samples
@@ -1709,7 +1648,7 @@ __device__ __forceinline__ void mix_item(const K1Vfo *__restrict__ vfos, const K
 #pragma unroll
                     for (int i = 0; i < 8; ++i)
                         if (128 * i + 2 * lane < valid && base + 128 * i + 2 * lane >= first_out)
-                            gstv4_leaf(reinterpret_cast<float4 *>(out + (at + 128u * i)), *reinterpret_cast<const v4f *>(src + 144 * i));
+                            gstv4(reinterpret_cast<float4 *>(out + (at + 128u * i)), *reinterpret_cast<const v4f *>(src + 144 * i));
                 }
             }
             continue;
@@ -1776,8 +1715,8 @@ __device__ __forceinline__ void mix_item(const K1Vfo *__restrict__ vfos, const K
                 held.units = 2, held.base = base, held.lv = lv;
             } else if (!otiled && emit_l && active) {
                 const int g = (base >> 2) + lane * 4;
-                gstv4_leaf(reinterpret_cast<float4 *>(out + (size_t)g), cat2(z[0], z[1]));
-                gstv4_leaf(reinterpret_cast<float4 *>(out + (size_t)(g + 2)), cat2(z[2], z[3]));
+                gstv4(reinterpret_cast<float4 *>(out + (size_t)g), cat2(z[0], z[1]));
+                gstv4(reinterpret_cast<float4 *>(out + (size_t)(g + 2)), cat2(z[2], z[3]));
             }
             continue;
         }
@@ -1788,9 +1727,7 @@ __device__ __forceinline__ void mix_item(const K1Vfo *__restrict__ vfos, const K
             *reinterpret_cast<v4f *>(A2) = cat2(z[0], z[1]);
             *reinterpret_cast<v4f *>(A2 + 2) = cat2(z[2], z[3]);
         }
-#if SDRX_FIXED_STAGES
         if (kShape && valid == kChunk && !save && dd == kFixedDepth) { // (uniform) a full chunk, not the frame's last (the shaped body of a d = 5 leaf only)
-#if SDRX_PAIR_STAGES
             // stage 2 every chunk; stages 3 and 4 every second chunk on both chunks' stage-2 outputs -- when the NEXT chunk
             // of this item is such a chunk too (otherwise this one is finished alone: nothing pending ever meets another path)
             if (pair_base < 0 && base + kChunk < W.s_end && base + 2 * kChunk < D.n_in) {
@@ -1807,14 +1744,12 @@ __device__ __forceinline__ void mix_item(const K1Vfo *__restrict__ vfos, const K
                     flush_held();
                 continue;
             }
-#endif
             const int jmin = max(0, (first_out - base) >> dd), gbase = base >> dd;
             hb_stage_fixed<EXACT, 2, kFixedDepth, 1>(lds, held, gbase, jmin, lane);
             if constexpr (!kShape)
                 flush_held();
             continue;
         }
-#endif
         for (int s = kRegStages; s < dd; ++s) {
             hb_stage_lds<EXACT>(lds + stage_offset(s), lds + stage_offset(s + 1), out, base >> dd, otiled != 0, s + 1 == dd,
                                 max(0, (first_out - base) >> dd), valid >> s, lane, save, hb_save + s * kHbHist);
@@ -1982,7 +1917,7 @@ __device__ __forceinline__ void late_item(const K1Vfo *__restrict__ vfos, const 
 #pragma unroll
             for (int r = 0; r < 3; ++r)
                 if (pos + LD * r >= W.s_first_out && kRow * lane + LD * r < valid)
-                    gstv2_leaf(zout + (size_t)(kb + 3 * lane + r), acc[r]);
+                    gstv2(zout + (size_t)(kb + 3 * lane + r), acc[r]);
         }
         wave_sync();
         if (base + valid == D.n_in) {
@@ -2038,7 +1973,7 @@ __device__ __forceinline__ void run_item(const K1Vfo *__restrict__ vfos, const K
 // One wave per workgroup, one workgroup per K1Work.  LEVEL only gives the root launch and the sub
 // launches distinct kernel names in profiles.
 template <bool EXACT, int LEVEL, bool ROT = !EXACT>
-__global__ __launch_bounds__(64, SDRX_K1_MIN_WAVES) void k_mix_decimate(const K1Vfo *__restrict__ vfos, const K1Work *__restrict__ work,
+__global__ __launch_bounds__(64, kK1MinWaves) void k_mix_decimate(const K1Vfo *__restrict__ vfos, const K1Work *__restrict__ work,
                                                      unsigned long long frame_no, const void *__restrict__ raw, int raw_mode)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -2105,27 +2040,32 @@ __global__ __launch_bounds__(256) void k_late_decimate(const K2aVfo *__restrict_
 }
 
 // The same for L in {5,6} (all the reference configures, mainwindow.cpp:196-216) and Nd <= 96: ONE
-// wave per 64 R outputs, R consecutive outputs per lane.  The R windows of a lane overlap
+// wave per 64 R outputs, R = 2 consecutive outputs per lane.  The R windows of a lane overlap
 // (Nd + (R-1) L samples instead of R Nd), so a lane streams ITS window once (two ds_read_b128 per
 // 4 samples) and feeds R accumulator pairs; output r uses tap j - L r for window sample j, read
 // as aligned ds_read_b128 from a copy of the taps shifted by L r (zero outside [0, Nd): adding
 // 0*x never changes a float sum).  The lane stride in LDS is padded to an odd multiple of 16
 // bytes so that 8 lanes' b128 reads cover all 32 banks.  Same summation order as the reference:
 // one accumulator per output and component, taps in ascending order.
+// R = 2 (8 KB of LDS per wave, ~20 waves per CU) measured 38 us on config 4, R = 4 (fewer LDS reads, 16 KB, 10 waves per CU)
+// 48 us, the one-output-per-thread kernel 54 us.
 constexpr int kLateMaxTaps = 96;
+constexpr int kLate4R = 2;
 constexpr int kLateTapRow = 124; // shifted tap copies: u = i + L r < Nd + 3 L = 114 (+ b128 overrun), a multiple of 4
-__host__ __device__ constexpr int late4_pad(int R, int L) { return (2 * R * L) % 8 == 4 ? 0 : 2; } // float2 per R L samples
-__host__ __device__ constexpr int late4_lds_bytes(int R, int L, int ndec) // for the launch's largest L and Nd
+__host__ __device__ constexpr int late4_pad(int L) { return (2 * kLate4R * L) % 8 == 4 ? 0 : 2; } // float2 per R L samples
+__host__ __device__ constexpr int late4_lds_bytes(int L, int ndec) // for the launch's largest L and Nd
 {
+    constexpr int R = kLate4R;
     const int span = L * (64 * R - 1) + ndec + (R - 1) * L;
     return 4 * R * kLateTapRow + 8 * (span + 2 * (span / (R * L)) + 16);
 }
 
-template <bool EXACT, int L, int R>
+template <bool EXACT, int L>
 __device__ __forceinline__ void late4_body(const float2 *__restrict__ x, float2 *__restrict__ zout, const float *__restrict__ taps, int n, int ndec,
                                            int n_out, int k0, int lane, v2f *__restrict__ sx, float *__restrict__ sh)
 {
-    constexpr int kPad = late4_pad(R, L);
+    constexpr int R = kLate4R;
+    constexpr int kPad = late4_pad(L);
     constexpr int kStride = R * L + kPad;                                          // float2 per lane
     constexpr int kIters = (L * (64 * R - 1) + kLateMaxTaps + (R - 1) * L + 8 + 63) / 64; // window loads per lane (+8: zero tail)
     constexpr int kTapIters = (R * kLateTapRow + 63) / 64;
@@ -2197,13 +2137,12 @@ __device__ __forceinline__ void late4_body(const float2 *__restrict__ x, float2 
     }
 }
 
-#ifndef SDRX_LATE4_WAVES
-#define SDRX_LATE4_WAVES 6 // 76 VGPRs; measured 34.0 us vs 35.4 (5 waves) and 35.5 (8 waves) on config 4
-#endif
-template <bool EXACT, int R>
-__global__ __launch_bounds__(64, SDRX_LATE4_WAVES) void k_late_decimate4(const K2aVfo *__restrict__ vfos, const BlockWork *__restrict__ work,
+constexpr int kLate4Waves = 6; // 76 VGPRs; measured 34.0 us vs 35.4 (5 waves) and 35.5 (8 waves) on config 4
+template <bool EXACT>
+__global__ __launch_bounds__(64, kLate4Waves) void k_late_decimate4(const K2aVfo *__restrict__ vfos, const BlockWork *__restrict__ work,
                                                        unsigned long long frame_no)
 {
+    constexpr int R = kLate4R;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *sh = reinterpret_cast<float *>(smem);
     v2f *sx = reinterpret_cast<v2f *>(smem + 4 * R * kLateTapRow);
@@ -2224,9 +2163,9 @@ __global__ __launch_bounds__(64, SDRX_LATE4_WAVES) void k_late_decimate4(const K
         for (int j = lane; j < D.Hx; j += 64)
             gst2(xnext + j, gld2(xbase + D.n + j));
     if (D.L == 5)
-        late4_body<EXACT, 5, R>(xbase + D.Hx, Dp->z[par], D.taps, D.n, D.ndec, D.n_out, k0, lane, sx, sh);
+        late4_body<EXACT, 5>(xbase + D.Hx, Dp->z[par], D.taps, D.n, D.ndec, D.n_out, k0, lane, sx, sh);
     else
-        late4_body<EXACT, 6, R>(xbase + D.Hx, Dp->z[par], D.taps, D.n, D.ndec, D.n_out, k0, lane, sx, sh);
+        late4_body<EXACT, 6>(xbase + D.Hx, Dp->z[par], D.taps, D.n, D.ndec, D.n_out, k0, lane, sx, sh);
 }
 
 // USB demodulation + optional audio low-pass + int16 (vfo.cpp:300-332):
@@ -2278,14 +2217,6 @@ __device__ __forceinline__ void pk_mac2_s(v2f &A, v2f &B, v2f pa, v2f pb, v2f vv
         : "+v"(A), "+v"(B), "=&v"(ta), "=&v"(tb)
         : "s"(pa), "s"(pb), "v"(vv), "n"(H));
 }
-template <int H>
-__device__ __forceinline__ void pk_fma2_v(v2f &A, v2f &B, v2f pa, v2f pb, v2f vv) // taps: vector register pairs
-{
-    asm("v_pk_fma_f32 %0, %2, %4, %0 op_sel:[1,%5,0] op_sel_hi:[0,%5,1]\n\t"
-        "v_pk_fma_f32 %1, %3, %4, %1 op_sel:[1,%5,0] op_sel_hi:[0,%5,1]"
-        : "+v"(A), "+v"(B)
-        : "v"(pa), "v"(pb), "v"(vv), "n"(H));
-}
 // pair i (0..8) of the 18 floats (x16, x2) a pass has loaded
 template <int I>
 __device__ __forceinline__ v2f pair_of(v16f a, v2f b)
@@ -2333,19 +2264,12 @@ __device__ __forceinline__ void hilbert4_packed(const float *plane, const float 
     acc[0] = A.x, acc[1] = A.y, acc[2] = B.x, acc[3] = B.y;
 }
 
-#ifndef SDRX_PACKED_EXACT_HILBERT
-#define SDRX_PACKED_EXACT_HILBERT 0 // (A/B: 1 = the exact arithmetic's Hilbert sum as packed v_pk_mul / v_pk_add on output pairs as well)
-#endif
-#ifndef SDRX_PACKED_LPF
-#define SDRX_PACKED_LPF 0 // (A/B: 1 = the audio low-pass of the non-exact arithmetics as packed FMAs too -- measured slower on config 4, profiles/README.md round 6)
-#endif
 struct DemodLds { // LDS of one 256-thread demodulation block
     alignas(16) float sP0[kPlaneLen + 4]; // even offsets from `lo`, stored shifted by +3
     alignas(16) float sP1[kPlaneLen + 4]; // odd offsets
     alignas(16) float sI[kDemodTile + kMaxFir + 8];
     alignas(16) float sU[kDemodTile + kMaxFir + 16];
-    alignas(16) float sH[kMaxFir + 16];  // sH[m] = hu[m - 3]: the E pairs of the packed form, (hu[2j'-3], hu[2j'-2])
-    alignas(16) float sH1[SDRX_PACKED_LPF ? kMaxFir + 16 : 4]; // sH1[m] = sH[m + 1] = hu[m - 2]: the O pairs (the packed low-pass only)
+    alignas(16) float sH[kMaxFir + 16];  // sH[m] = hu[m - 3]
 };
 static_assert(sizeof(DemodLds) % 16 == 0, "DemodLds is a whole number of 16-byte units");
 
@@ -2353,7 +2277,7 @@ template <bool EXACT>
 __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, const BlockWork bw, unsigned long long frame_no, DemodLds &S,
                                             int tid)
 {
-    float *sP0 = S.sP0, *sP1 = S.sP1, *sI = S.sI, *sU = S.sU, *sH = S.sH, *sH1 = S.sH1;
+    float *sP0 = S.sP0, *sP1 = S.sP1, *sI = S.sI, *sU = S.sU, *sH = S.sH;
     const K2Vfo *Dp = vfos + bw.vfo;
     const int blk = bw.blk;
     const int par = (int)(frame_no & 1ull);
@@ -2373,8 +2297,9 @@ __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, cons
         return;
     // The 62 Hilbert taps, read before this kernel has stored anything so the compiler can use
     // wave-uniform scalar loads and keep them in SGPRs for the whole block.  (The non-exact arithmetics take them pass by
-    // pass as register PAIRS instead: hilbert4_packed.)
-    constexpr bool kPackedHilbert = !EXACT || SDRX_PACKED_EXACT_HILBERT;
+    // pass as register PAIRS instead: hilbert4_packed.  The exact arithmetic's sum packed -- v_pk_mul / v_pk_add -- was
+    // 1-3 % slower on all three workloads.)
+    constexpr bool kPackedHilbert = !EXACT;
     float hnz[kHilbertNz];
     if constexpr (!kPackedHilbert) {
 #pragma unroll
@@ -2382,11 +2307,8 @@ __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, cons
             hnz[s] = ldc(D.hnz + s);
     }
     if (D.nlpf > 0)
-        for (int j = tid; j < D.nlpf + 15; j += 256) {
+        for (int j = tid; j < D.nlpf + 15; j += 256)
             sH[j] = gld(D.lpf + j);
-            if constexpr (!EXACT && SDRX_PACKED_LPF)
-                sH1[j] = j + 1 < D.nlpf + 15 ? gld(D.lpf + j + 1) : 0.f;
-        }
     if (blk == 0) // history for the next frame: the last H entries of [hist | data]
         for (int j = tid; j < D.H; j += 256)
             gst2(snext + j, gld2(sbase + D.n + j));
@@ -2403,7 +2325,7 @@ __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, cons
 #pragma unroll
     for (int it = 0; it < kStageIters; ++it) {
         const int r = tid + 256 * it, idx = lo + r;
-        stage[it] = (r < nr && idx < D.n) ? gld2_once(z + idx) : make_float2(0.f, 0.f);
+        stage[it] = (r < nr && idx < D.n) ? gld2(z + idx) : make_float2(0.f, 0.f);
     }
 #pragma unroll
     for (int it = 0; it < kStageIters; ++it) {
@@ -2468,38 +2390,22 @@ __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, cons
         const float *w = sU + soff + (E - N) + j0; // 16-byte aligned by the choice of soff
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         const int groups = (N + 6) / 4;
-        if constexpr (EXACT || !SDRX_PACKED_LPF) {
-            for (int g = 0; g < groups; ++g) {
-                const float4 v4 = *reinterpret_cast<const float4 *>(w + 4 * g);
-                const float v[4] = {v4.x, v4.y, v4.z, v4.w};
-                const float4 ha = *reinterpret_cast<const float4 *>(sH + 4 * g), hb4 = *reinterpret_cast<const float4 *>(sH + 4 * g + 4);
-                const float h[8] = {ha.x, ha.y, ha.z, ha.w, hb4.x, hb4.y, hb4.z, hb4.w}; // h[k] = hu[4g + k - 3]
+        // (scalar in every arithmetic: packed like hilbert4_packed, the low-pass has two accumulator chains per thread instead
+        // of four and cost config 4 2-3 %; profiles/README.md round 6)
+        for (int g = 0; g < groups; ++g) {
+            const float4 v4 = *reinterpret_cast<const float4 *>(w + 4 * g);
+            const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+            const float4 ha = *reinterpret_cast<const float4 *>(sH + 4 * g), hb4 = *reinterpret_cast<const float4 *>(sH + 4 * g + 4);
+            const float h[8] = {ha.x, ha.y, ha.z, ha.w, hb4.x, hb4.y, hb4.z, hb4.w}; // h[k] = hu[4g + k - 3]
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
+            for (int e = 0; e < 4; ++e)
 #pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) {
-                        if (EXACT)
-                            acc[rr] = acc[rr] + h[e - rr + 3] * v[e];
-                        else
-                            acc[rr] = fmaf(h[e - rr + 3], v[e], acc[rr]);
-                    }
-            }
-        } else {
-            // the packed form (see hilbert4_packed): window entry q = 4 g + e gives out_r the tap hu[q - r]; quad t of sH holds
-            // the E pairs 2 t, 2 t + 1 -- (hu[4t-3], hu[4t-2]), (hu[4t-1], hu[4t]) --, of sH1 the O pairs (hu[4t-2], hu[4t-1]),
-            // (hu[4t], hu[4t+1]); a group needs the pairs 2 g, 2 g + 1 (the quad before) and 2 g + 2 (this one's low half)
-            v2f A = {0.f, 0.f}, B = {0.f, 0.f};
-            v4f ep = *reinterpret_cast<const v4f *>(sH), op = *reinterpret_cast<const v4f *>(sH1);
-            for (int g = 0; g < groups; ++g) {
-                const v4f w4 = *reinterpret_cast<const v4f *>(w + 4 * g);
-                const v4f ec = *reinterpret_cast<const v4f *>(sH + 4 * g + 4), oc = *reinterpret_cast<const v4f *>(sH1 + 4 * g + 4);
-                pk_fma2_v<0>(A, B, hi2(ep), lo2(ep), lo2(w4)); // q = 4g:     (hu[4g-1], hu[4g])   | (hu[4g-3], hu[4g-2])
-                pk_fma2_v<1>(A, B, hi2(op), lo2(op), lo2(w4)); // q = 4g + 1: (hu[4g],   hu[4g+1]) | (hu[4g-2], hu[4g-1])
-                pk_fma2_v<0>(A, B, lo2(ec), hi2(ep), hi2(w4)); // q = 4g + 2: (hu[4g+1], hu[4g+2]) | (hu[4g-1], hu[4g])
-                pk_fma2_v<1>(A, B, lo2(oc), hi2(op), hi2(w4)); // q = 4g + 3: (hu[4g+2], hu[4g+3]) | (hu[4g],   hu[4g+1])
-                ep = ec, op = oc;
-            }
-            acc[0] = A.x, acc[1] = A.y, acc[2] = B.x, acc[3] = B.y;
+                for (int rr = 0; rr < 4; ++rr) {
+                    if (EXACT)
+                        acc[rr] = acc[rr] + h[e - rr + 3] * v[e];
+                    else
+                        acc[rr] = fmaf(h[e - rr + 3], v[e], acc[rr]);
+                }
         }
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr)
@@ -2534,11 +2440,10 @@ __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, cons
     }
 }
 
-#ifndef SDRX_DEMOD_MIN_WAVES
-#define SDRX_DEMOD_MIN_WAVES 1 // (A/B: 8 = at most 64 VGPRs, eight 256-thread blocks per CU)
-#endif
+// (no occupancy demand: __launch_bounds__(256, 8) -- at most 64 VGPRs, eight 256-thread blocks per CU -- measured 92 us
+// against 47 us; profiles/README.md)
 template <bool EXACT>
-__global__ __launch_bounds__(256, SDRX_DEMOD_MIN_WAVES) void k_usb_demod(const K2Vfo *__restrict__ vfos, const BlockWork *__restrict__ work,
+__global__ __launch_bounds__(256, 1) void k_usb_demod(const K2Vfo *__restrict__ vfos, const BlockWork *__restrict__ work,
                                                    unsigned long long frame_no)
 {
     __shared__ __attribute__((aligned(16))) DemodLds S;
@@ -2562,7 +2467,7 @@ struct LevelArgs {
     int pad_;
 };
 template <bool EXACT, bool ROT = !EXACT>
-__global__ __launch_bounds__(64, SDRX_K1_MIN_WAVES) void k_mix_levels(const K1Vfo *__restrict__ k1, const K1Work *__restrict__ items,
+__global__ __launch_bounds__(64, kK1MinWaves) void k_mix_levels(const K1Vfo *__restrict__ k1, const K1Work *__restrict__ items,
                                                    const int *__restrict__ item_level, const int *__restrict__ list, LevelArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

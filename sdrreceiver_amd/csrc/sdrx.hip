@@ -140,12 +140,9 @@ struct sdrx_ctx {
     // `copy_stream` for frames that came in through sdrx_submit*.  Cross-stream order is by the
     // per-parity events below (measured on this runtime, tools/event_probe.hip: a record costs its
     // stream ~3-5 us, a wait on an event that completed long ago ~2.5 us, a tight hop ~11 us).
-    hipStream_t own_stream = nullptr, stream = nullptr, tail_stream = nullptr, copy_stream = nullptr, copy_stream2 = nullptr;
-    int late_copy = -1;                    // payload copy issued by sdrx_wait instead of queued behind the frame: -1 = for frames that carry the DC recurrence, 0 never, 1 always (SDRX_LATE_COPY)
-    bool copy_owed[2] = {false, false};    //   ... and not issued yet
-    bool upload_kernel = false; // SDRX_UPLOAD_KERNEL=1: host frames go up with k_copy16 instead of hipMemcpyAsync (A/B switch; slower)
-    int download_blocks = 0;    // workgroups of a payload copy KERNEL for the frames that carry the recurrence (SDRX_DOWNLOAD_BLOCKS with SDRX_LATE_COPY=0; 0: hipMemcpyAsync) ...
-    bool long_frame = false;    // ... which carries the payloads of frames whose kernels outlast the copy (the DC-bias recurrence)
+    hipStream_t own_stream = nullptr, stream = nullptr, tail_stream = nullptr, copy_stream = nullptr, copy_stream2 = nullptr; // copy_stream2: odd frames
+    bool long_frame = false;             // the frame's kernels outlast its payload copy (the DC-bias recurrence): the copy is issued by sdrx_wait
+    bool copy_owed[2] = {false, false};  //   ... and not issued yet
     hipEvent_t ev_levels[2] = {nullptr, nullptr}; // levels of frame f done (recorded on `stream`)
     hipEvent_t ev_tail[2] = {nullptr, nullptr};   // tail of frame f done (recorded on the tail's stream)
     hipEvent_t ev_copied[2] = {nullptr, nullptr}; // payloads of frame f are in h_pay[f & 1]
@@ -175,14 +172,12 @@ struct sdrx_ctx {
     float2 *d_raw_tiled = nullptr; // the raw frame in tile layout: input of the parent-less VFOs
     int last_raw = -1;             // how the last frame reached level 0 (kRaw*; -1: caller-owned device memory)
     bool late4 = false;            // k_late_decimate4 serves the late-decimation launch
-    int late4_r = 4;               // outputs per lane of that kernel
     bool root_direct = false;      // level 0 reads the caller's natural-order frame itself (few VFOs)
     unsigned char *d_raw_u8[2] = {nullptr, nullptr}; // the same for dongle bytes
     float *d_dc_state = nullptr;   // DC-bias accumulator (exact: [2]; fast: [parity][2])
     float *d_dc_work = nullptr;    // exact DC-bias removal: products P[2][stride] and estimates A[2][stride] of one frame
     unsigned long long *d_dc_counters = nullptr; // k_dc_chain_spec: [0] blocks walked, [1] blocks redone with the sequential operations, [2] blocks taken again on their own
-    int dc_waves = 8;                            // k_dc_chain_spec: blocks per step = waves per workgroup (SDRX_DC_WAVES: 1, 2, 4, 8)
-    int dc_rounds = 0;                           //   ... its limit of rounds per step (SDRX_DC_ROUNDS; 0 = kDcMaxIter)
+    int dc_waves = 8;                            // k_dc_chain_spec: blocks per step = waves per workgroup (option dc_blocks_per_step: 1, 2, 4, 8)
     int dc_work_stride = 0;
     double *d_dc_tab = nullptr;    // fast DC scan: powers of the decay + per-chunk sums behind them
     unsigned long long dc_frames = 0; // frames the fast scan has run on (its state ping-pongs)
@@ -402,21 +397,14 @@ int enqueue_frame_as(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
     // A frame that carries the DC-bias recurrence did not get to run beside a copy queued that way (0.59-0.82 ms per frame,
     // about the SUM of its parts), nor beside a copy kernel of ours (a kernel cannot retire beside one): for those frames the copy
     // is issued by sdrx_wait, when the host has seen the frame's last kernel end -- 0.34 ms per frame.  (The float path would lose
-    // by that, 0.38 vs 0.30: between two waits the copy engine idles.)  SDRX_LATE_COPY=0 / 1: never / always.
-    if (egress && (c->late_copy == 1 || (c->late_copy < 0 && c->long_frame))) {
+    // by that, 0.38 vs 0.30: between two waits the copy engine idles.)
+    if (egress && c->long_frame) {
         c->copy_owed[p] = true;
         c->in_flight++;
     } else if (egress) {
-        hipStream_t cs = (p && c->copy_stream2) ? c->copy_stream2 : c->copy_stream;
+        hipStream_t cs = p ? c->copy_stream2 : c->copy_stream;
         HIPCHK(c, hipStreamWaitEvent(cs, c->ev_tail[p], 0));
-        // (SDRX_DOWNLOAD_BLOCKS=n with SDRX_LATE_COPY=0: a copy kernel of ours on n workgroups for the frames that carry the recurrence -- A/B switch)
-        if (c->download_blocks > 0 && c->long_frame) {
-            const size_t n16 = (c->pay_bytes + 15) / 16; // (both buffers are allocated in whole 16-byte units)
-            hipLaunchKernelGGL(k_copy16, dim3(c->download_blocks), dim3(256), 0, cs, reinterpret_cast<const uint4 *>(c->d_pay[p]),
-                               reinterpret_cast<uint4 *>(c->h_pay[p]), n16);
-        } else {
-            HIPCHK(c, hipMemcpyAsync(c->h_pay[p], c->d_pay[p], c->pay_bytes, hipMemcpyDeviceToHost, cs));
-        }
+        HIPCHK(c, hipMemcpyAsync(c->h_pay[p], c->d_pay[p], c->pay_bytes, hipMemcpyDeviceToHost, cs));
         HIPCHK(c, hipEventRecord(c->ev_copied[p], cs));
         c->in_flight++;
     }
@@ -439,17 +427,10 @@ void launch_block_kernel(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned
     const BlockWork *w = reinterpret_cast<const BlockWork *>(c->arena + L.off_work);
     const K2aVfo *k2a = reinterpret_cast<const K2aVfo *>(c->arena + L.off_desc);
     if (L.kind == KIND_LATE_DEC && c->late4) {
-        if (c->late4_r == 2) {
-            if (exact)
-                hipLaunchKernelGGL((k_late_decimate4<true, 2>), grid, dim3(64), L.lds_bytes, ts, k2a, w, frame);
-            else
-                hipLaunchKernelGGL((k_late_decimate4<false, 2>), grid, dim3(64), L.lds_bytes, ts, k2a, w, frame);
-        } else {
-            if (exact)
-                hipLaunchKernelGGL((k_late_decimate4<true, 4>), grid, dim3(64), L.lds_bytes, ts, k2a, w, frame);
-            else
-                hipLaunchKernelGGL((k_late_decimate4<false, 4>), grid, dim3(64), L.lds_bytes, ts, k2a, w, frame);
-        }
+        if (exact)
+            hipLaunchKernelGGL(k_late_decimate4<true>, grid, dim3(64), L.lds_bytes, ts, k2a, w, frame);
+        else
+            hipLaunchKernelGGL(k_late_decimate4<false>, grid, dim3(64), L.lds_bytes, ts, k2a, w, frame);
     } else if (L.kind == KIND_LATE_DEC) {
         if (exact)
             hipLaunchKernelGGL(k_late_decimate<true>, grid, dim3(256), L.lds_bytes, ts, k2a, w, frame);
@@ -544,8 +525,7 @@ int drain(sdrx_ctx *c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipStreamSynchronize(c->tail_stream));
     HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-    if (c->copy_stream2)
-        HIPCHK(c, hipStreamSynchronize(c->copy_stream2));
+    HIPCHK(c, hipStreamSynchronize(c->copy_stream2));
     drain_events(c);
     return SDRX_OK;
 }
@@ -665,35 +645,11 @@ int sdrx_create(sdrx_ctx **out, int device)
         return fail(nullptr, SDRX_EHIP, "hipStreamCreate: %s", hipGetErrorString(e));
     }
     c->stream = c->own_stream;
-    bool ok = hipStreamCreateWithFlags(&c->tail_stream, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) == hipSuccess;
-    if (getenv("SDRX_LATE_COPY"))
-        c->late_copy = atoi(getenv("SDRX_LATE_COPY")) != 0;
-    c->upload_kernel = getenv("SDRX_UPLOAD_KERNEL") && atoi(getenv("SDRX_UPLOAD_KERNEL")) != 0;
-    // experiment switches of the exact DC-bias removal, read ONCE, here, and validated like the option they shadow
-    if (const char *e = getenv("SDRX_DC_WAVES")) {
-        const int v = atoi(e);
-        if (v != 1 && v != 2 && v != 4 && v != 8) {
-            sdrx_destroy(c);
-            return fail(nullptr, SDRX_EINVAL, "SDRX_DC_WAVES=%s: 1, 2, 4 or 8 (option dc_blocks_per_step)", e);
-        }
-        c->dc_waves = v;
-    }
-    if (const char *e = getenv("SDRX_DC_ROUNDS")) {
-        const int v = atoi(e);
-        if (v < 1 || v > 1000) {
-            sdrx_destroy(c);
-            return fail(nullptr, SDRX_EINVAL, "SDRX_DC_ROUNDS=%s: 1 .. 1000 rounds per step of k_dc_chain_spec", e);
-        }
-        c->dc_rounds = v;
-    }
-    if (getenv("SDRX_DOWNLOAD_BLOCKS"))
-        c->download_blocks = std::max(0, std::min(4096, atoi(getenv("SDRX_DOWNLOAD_BLOCKS"))));
     // odd frames' payloads leave on a copy stream of their own: the next copy's set-up then overlaps the
-    // current copy's tail (measured through the ABI on config 3: 0.296 vs 0.306 ms per frame;
-    // SDRX_TWO_COPY_STREAMS=0 for A/B runs)
-    if (ok && !(getenv("SDRX_TWO_COPY_STREAMS") && atoi(getenv("SDRX_TWO_COPY_STREAMS")) == 0))
-        ok = hipStreamCreateWithFlags(&c->copy_stream2, hipStreamNonBlocking) == hipSuccess;
+    // current copy's tail (measured through the ABI on config 3: 0.296 vs 0.306 ms per frame)
+    bool ok = hipStreamCreateWithFlags(&c->tail_stream, hipStreamNonBlocking) == hipSuccess &&
+              hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) == hipSuccess &&
+              hipStreamCreateWithFlags(&c->copy_stream2, hipStreamNonBlocking) == hipSuccess;
     for (int p = 0; p < 2 && ok; ++p)
         ok = hipEventCreateWithFlags(&c->ev_levels[p], hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&c->ev_tail[p], hipEventDisableTiming) == hipSuccess &&
@@ -1099,12 +1055,12 @@ int build_mix_work(sdrx_ctx *c, Built &B)
             ncu = prop.multiProcessorCount;
     }
     std::vector<int> level_nseg((size_t)c->n_levels, 1);
-    // (experiment switches, read here: SDRX_ITEMS_PER_CU = work items per CU a level is cut into, default 32; SDRX_MIN_SEG = the
-    // fewest chunks of useful work a segment of a many-VFO level may have, default 4)
-    const int items_per_cu = getenv("SDRX_ITEMS_PER_CU") ? std::max(1, atoi(getenv("SDRX_ITEMS_PER_CU"))) : 32;
-    const int min_seg_chunks = getenv("SDRX_MIN_SEG") ? std::max(1, atoi(getenv("SDRX_MIN_SEG"))) : 4;
-    for (int lv = 0; lv < c->n_levels; ++lv) // 32 work items per CU (= the hardware's wave slots per CU)
-        level_nseg[(size_t)lv] = std::max(1, (ncu * items_per_cu + B.level_count[(size_t)lv] - 1) / B.level_count[(size_t)lv]);
+    constexpr int kItemsPerCu = 32;  // work items per CU a level is cut into (= the hardware's wave slots per CU)
+    constexpr int kMinSegChunks = 4; // the fewest chunks of useful work a segment of a many-VFO level may have
+    constexpr int kLateMinSeg = 4;   // the same for a fused late decimation (measured on config 4, interleaved: 2 / 3 / 4 / 6 / 8
+                                     //   chunks per segment = 0.0481 / 0.0484 / 0.0471 / 0.0482 / 0.0509 ms per step)
+    for (int lv = 0; lv < c->n_levels; ++lv)
+        level_nseg[(size_t)lv] = std::max(1, (ncu * kItemsPerCu + B.level_count[(size_t)lv] - 1) / B.level_count[(size_t)lv]);
     c->mix_chunks = 0;
     for (int i = 0; i < N; ++i) {
         const Node &n = c->nodes[(size_t)i];
@@ -1122,10 +1078,7 @@ int build_mix_work(sdrx_ctx *c, Built &B)
         // few VFOs in the level (the 2-3 mains): segments as short as the warm-up allows;
         // otherwise at least 4 chunks of useful work per segment
         const bool few = (long long)B.level_count[(size_t)n.level] * nchunks < (long long)ncu * 16;
-        // (a fused late decimation: measured on config 4, interleaved: 2 / 3 / 4 / 6 / 8 chunks per segment = 0.0481 / 0.0484 /
-        // 0.0471 / 0.0482 / 0.0509 ms per step; SDRX_LATE_MINSEG for A/B runs)
-        const int late_min_seg = getenv("SDRX_LATE_MINSEG") ? std::max(1, atoi(getenv("SDRX_LATE_MINSEG"))) : 4;
-        const int min_seg = few ? std::max(1, wch) : n.fused_late ? late_min_seg : std::max(min_seg_chunks, min_seg_chunks * wch);
+        const int min_seg = few ? std::max(1, wch) : n.fused_late ? kLateMinSeg : std::max(kMinSegChunks, kMinSegChunks * wch);
         int nseg = c->opt_segments > 0 ? c->opt_segments : std::min(level_nseg[(size_t)n.level], std::max(1, nchunks / min_seg));
         nseg = std::max(1, std::min(nseg, nchunks / std::max(1, wch)));
         // Segment s > 0 starts `warm` samples before its first emitted output and ends on a chunk
@@ -1172,14 +1125,8 @@ int build_mix_work(sdrx_ctx *c, Built &B)
             first_out = w.s_end;
         }
     }
-    // Order of the work items inside a launch (experiment switch SDRX_ORDER, default = VFO-major,
-    // i.e. creation order; measured: spreading d=5 and d=2 items evenly through the list is 12 %
-    // SLOWER than keeping each VFO's -- and each parent's -- items together).
-    if (const char *e = getenv("SDRX_ORDER")) {
-        if (atoi(e) == 1) // segment-major: all first segments, then all second segments, ...
-            for (auto &wl : B.works)
-                std::stable_sort(wl.begin(), wl.end(), [](const K1Work &a, const K1Work &b) { return a.s_first_out < b.s_first_out; });
-    }
+    // The work items of a launch stay in VFO-major order, i.e. creation order (measured: spreading d=5 and d=2 items evenly
+    // through the list is 12 % SLOWER than keeping each VFO's -- and each parent's -- items together).
     c->l1.clear();
     for (int lv = 0; lv < c->n_levels; ++lv) {
         Launch1 L;
@@ -1213,8 +1160,9 @@ void build_tail_work(sdrx_ctx *c, Built &B)
     int64_t b2 = 0, b3 = 0;
     int lds2a = 0;
     auto two_kernel_late = [](const Node &n) { return n.leaf && n.d.demod_usb && n.d.late_decimate > 0 && !n.fused_late; };
-    // every late-decimating VFO left to a kernel of its own has L in {5,6} and <= 96 taps: one-wave tiles, R outputs per lane
-    bool late4 = !getenv("SDRX_NO_LATE4");
+    // every late-decimating VFO left to a kernel of its own has L in {5,6} and <= 96 taps: one-wave tiles of k_late_decimate4,
+    // 2 outputs per lane; anything else goes to the generic k_late_decimate
+    bool late4 = true;
     int late_lmax = 5, late_ndec = 0;
     for (const Node &n : c->nodes)
         if (two_kernel_late(n)) {
@@ -1223,12 +1171,7 @@ void build_tail_work(sdrx_ctx *c, Built &B)
             late_ndec = std::max(late_ndec, (int)n.dec.size());
         }
     c->late4 = late4;
-    // 2 outputs per lane (8 KB of LDS per wave, ~20 waves per CU) measured 38 us on config 4, 4 outputs
-    // per lane (fewer LDS reads, 16 KB, 10 waves per CU) 48 us, the one-output-per-thread kernel 54 us
-    c->late4_r = getenv("SDRX_LATE4_R") ? atoi(getenv("SDRX_LATE4_R")) : 2;
-    if (c->late4_r != 4)
-        c->late4_r = 2;
-    const int late_tile = late4 ? 64 * c->late4_r : 256;
+    const int late_tile = late4 ? 64 * kLate4R : 256;
     for (int i = 0; i < N; ++i) {
         Node &n = c->nodes[(size_t)i];
         if (!n.leaf)
@@ -1246,7 +1189,7 @@ void build_tail_work(sdrx_ctx *c, Built &B)
                 // its tile is shortened by E so that usb stays ONE pass of <= 1024 values (a second pass would
                 // keep two of the four waves busy for a whole Hilbert loop on ~50 values)
                 const int nl = n.long_lpf ? 0 : (int)n.lpf.size();
-                n.demod_tile = (nl > 0 && !getenv("SDRX_DEMOD_FULL_TILE")) ? ((kDemodTile - (nl + (nl & 1))) & ~3) : kDemodTile;
+                n.demod_tile = nl > 0 ? ((kDemodTile - (nl + (nl & 1))) & ~3) : kDemodTile;
             }
             // (a leaf that demodulates in its mix wave has a descriptor -- the wave reads it -- but no blocks in this launch)
             for (int b = 0; !n.fused_demod && b < (n.n_out + n.demod_tile - 1) / n.demod_tile; ++b)
@@ -1275,9 +1218,9 @@ void build_tail_work(sdrx_ctx *c, Built &B)
     if (!B.d2a.empty()) {
         B.o2a = plan.take(sizeof(K2aVfo) * B.d2a.size());
         B.ow2a = plan.take(sizeof(BlockWork) * B.w2a.size());
-        c->lb.push_back({KIND_LATE_DEC, (int)B.w2a.size(), B.o2a, B.ow2a, c->late4 ? late4_lds_bytes(c->late4_r, late_lmax, late_ndec) : lds2a, 0});
+        c->lb.push_back({KIND_LATE_DEC, (int)B.w2a.size(), B.o2a, B.ow2a, c->late4 ? late4_lds_bytes(late_lmax, late_ndec) : lds2a, 0});
     }
-    if (!B.d2.empty() && !getenv("SDRX_NO_LPT")) {
+    if (!B.d2.empty()) {
         // Blocks are independent and the launch is a few resident rounds deep, so its tail is set by
         // what is dispatched last: longest blocks first (a block with the audio low-pass does about
         // twice the work; the last block of a VFO-frame may be nearly empty).
@@ -1327,13 +1270,11 @@ void build_level_plan(sdrx_ctx *c, Built &B)
         return;
     // deepest level first: in the steady state of the reference's two-level trees the long sub-VFO
     // items are dispatched first and the short level-0 items fill the launch's tail
-    // (SDRX_LEVEL_ORDER=1: level 0 first, for A/B runs)
-    const bool root_first = getenv("SDRX_LEVEL_ORDER") && atoi(getenv("SDRX_LEVEL_ORDER")) == 1;
     P.part_begin.assign((size_t)c->n_levels, 0);
     P.part_end.assign((size_t)c->n_levels, 0);
     P.part_bytes.assign((size_t)c->n_levels, 0);
     for (int q = 0; q < c->n_levels; ++q) {
-        const int lv = root_first ? q : c->n_levels - 1 - q;
+        const int lv = c->n_levels - 1 - q;
         while (B.llist.size() % 8)
             B.llist.push_back(-1);
         P.part_begin[(size_t)lv] = (int)B.llist.size();
@@ -1361,7 +1302,7 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
     HIPCHK(c, hipMemsetAsync(c->arena, 0, c->arena_bytes, c->stream));
     c->pay_bytes = std::max<size_t>(B.pay, 64);
     for (int p = 0; p < 2; ++p) {
-        HIPCHK(c, hipMalloc(&c->d_pay[p], align_up(c->pay_bytes, 16))); // (whole 16-byte units: k_copy16)
+        HIPCHK(c, hipMalloc(&c->d_pay[p], align_up(c->pay_bytes, 16))); // (whole 16-byte units)
         HIPCHK(c, hipMemsetAsync(c->d_pay[p], 0, c->pay_bytes, c->stream));
         HIPCHK(c, hipHostMalloc(&c->h_pay[p], align_up(c->pay_bytes, 16), hipHostMallocDefault));
         memset(c->h_pay[p], 0, c->pay_bytes);
@@ -1370,7 +1311,7 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
         const size_t raw_tiles = align_up((size_t)c->root_frame, kChunk) + kChunk; // (+1 tile, as for the parents' streams)
         HIPCHK(c, hipMalloc(&c->d_raw_tiled, raw_tiles * sizeof(float2)));
         HIPCHK(c, hipMemsetAsync(c->d_raw_tiled, 0, raw_tiles * sizeof(float2), c->stream));
-        c->root_direct = B.level_count[0] <= 4 && !getenv("SDRX_NO_ROOT_DIRECT"); // the reference allows 3 mains (mainwindow.h:82)
+        c->root_direct = B.level_count[0] <= 4; // the reference allows 3 mains (mainwindow.h:82)
     }
     auto P = [&](size_t off) { return c->arena + off; };
     std::vector<K1Vfo> k1((size_t)N);
@@ -1695,16 +1636,10 @@ int stage_host_frame(sdrx_ctx *c, const void *src, size_t bytes, void *dst_dev)
             HIPCHK(c, hipStreamWaitEvent(c->stream, r.ev, 0));
             r.pending = false;
         }
-    // (the runtime moves host-to-device copies with the DMA engine: concurrent with kernels.  SDRX_UPLOAD_KERNEL=1: a copy kernel
-    // reading the pinned buffer over PCIe instead -- measured slower, 0.353 vs 0.302 ms per pipelined frame on config 3: it sits
-    // in the compute stream's way)
-    if (!c->upload_kernel) {
-        HIPCHK(c, hipMemcpyAsync(dst_dev, c->h_in[p], bytes, hipMemcpyHostToDevice, c->stream));
-    } else {
-        const size_t n16 = (bytes + 15) / 16; // (both buffers are whole 16-byte units long: frames are multiples of 16 samples)
-        hipLaunchKernelGGL(k_copy16, dim3(64), dim3(256), 0, c->stream, reinterpret_cast<const uint4 *>(c->h_in[p]),
-                           reinterpret_cast<uint4 *>(dst_dev), n16);
-    }
+    // (the runtime moves host-to-device copies with the DMA engine: concurrent with kernels.  A copy kernel reading the pinned
+    // buffer over PCIe instead measured slower, 0.353 vs 0.302 ms per pipelined frame on config 3: it sits in the compute
+    // stream's way)
+    HIPCHK(c, hipMemcpyAsync(dst_dev, c->h_in[p], bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(c->ev_staged[p], c->stream)); // (for a context that shares this frame: sdrx_submit_shared)
     return SDRX_OK;
 }
@@ -1773,7 +1708,7 @@ int enqueue_u8_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, int cor
             auto chain = c->dc_waves >= 8 ? k_dc_chain_spec<8> : c->dc_waves >= 4 ? k_dc_chain_spec<4> : c->dc_waves >= 2 ? k_dc_chain_spec<2> : k_dc_chain_spec<1>;
             const int waves = c->dc_waves >= 8 ? 8 : c->dc_waves >= 4 ? 4 : c->dc_waves >= 2 ? 2 : 1;
             hipLaunchKernelGGL(chain, dim3(2), dim3(64 * waves), 0, c->stream, Pp, Ap, n_complex, c->dc_work_stride, c->d_dc_state, c->d_dc_counters,
-                               c->dc_rounds > 0 ? c->dc_rounds : kDcMaxIter);
+                               kDcMaxIter);
         } else {
             hipLaunchKernelGGL(k_dc_chain, dim3(2), dim3(64), 0, c->stream, Pp, Ap, n_complex, c->dc_work_stride, c->d_dc_state);
         }
@@ -1935,7 +1870,7 @@ int start_owed_copy(sdrx_ctx *c)
     if (!c->copy_owed[p])
         return SDRX_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t cs = (p && c->copy_stream2) ? c->copy_stream2 : c->copy_stream;
+    hipStream_t cs = p ? c->copy_stream2 : c->copy_stream;
     HIPCHK(c, hipEventSynchronize(c->ev_tail[p]));
     HIPCHK(c, hipMemcpyAsync(c->h_pay[p], c->d_pay[p], c->pay_bytes, hipMemcpyDeviceToHost, cs));
     HIPCHK(c, hipEventRecord(c->ev_copied[p], cs));

@@ -55,6 +55,23 @@ def test_product_never_touches_the_oracle():
                         and "from oracle" not in txt, os.path.join(dirpath, f)
 
 
+def test_library_has_no_experiment_switches():
+    """The shipped library behaves the same whatever environment it starts in and whatever macros a build passes: no getenv
+    under csrc/ but the fault injection's SDRX_FAULT_WAIT, no #if on an SDRX_ macro but the Makefile's SDRX_SOURCE_HASH and
+    tapdesign.h's SDRX_PI constant."""
+    csrc = os.path.join(ROOT, "sdrreceiver_amd", "csrc")
+    allowed_macros = {"SDRX_SOURCE_HASH", "SDRX_PI"}
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h", ".cpp", ".c")):
+            continue
+        txt = open(os.path.join(csrc, f), errors="replace").read()
+        for m in re.finditer(r"getenv\s*\(([^)]*)\)", txt):
+            assert m.group(1).strip() == '"SDRX_FAULT_WAIT"', (f, m.group(0))
+        for m in re.finditer(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)$", txt, re.M):
+            macros = set(re.findall(r"\bSDRX_\w+", m.group(1)))
+            assert macros <= allowed_macros, (f, m.group(0).strip())
+
+
 def test_compiled_kernels_use_no_scratch_memory():
     """`make asm` + tools/check_asm.py: every kernel of the gfx950 build at 0 bytes of scratch (a spill reload in a chunk loop
     is a vector-memory operation behind an s_waitcnt), and k_dc_chain without an SGPR spill next to its scalar prefetch

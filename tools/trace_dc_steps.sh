@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/trace_dc_steps.sh -- per-kernel durations (rocprofv3 --kernel-trace --stats) of tools/dc_steps_probe.py: k_dc_products,
-# k_dc_chain_spec<NW>, k_dc_apply on its four byte streams.  PER_STEP / SDRX_DC_ROUNDS as for the probe.
+# k_dc_chain_spec<NW>, k_dc_apply on its four byte streams.  PER_STEP as for the probe.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/trace_dc_steps; rm -rf $OUT; mkdir -p $OUT
 rocprofv3 --kernel-trace --stats -d $OUT -o t --output-format csv -- python3 tools/dc_steps_probe.py 16 > $OUT/probe.txt 2> $OUT/err.txt
