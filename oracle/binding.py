@@ -16,6 +16,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 PORT_SO = os.path.join(_HERE, "liborc.so")
 REF_SO = os.path.join(_HERE, "_ref", "libsdrref.so")
 REF_OFAST_SO = os.path.join(_HERE, "_ref", "libsdrref_ofast.so")  # the reference as shipped: -Ofast (SDRReceiver.pro:74-75)
+# the real sdrj + sdr (byte LUT, DC-bias IIR, raw spectrum signal) with the vfo sources behind them (oracle/ref/sdrj_harness.cpp)
+SDRJ_SO = os.path.join(_HERE, "_ref", "libsdrjref.so")
+SDRJ_OFAST_SO = os.path.join(_HERE, "_ref", "libsdrjref_ofast.so")
+_SDRJ_WORKER = os.path.join(os.path.dirname(_HERE), "tests", "sdrj_ref_worker.py")
 
 _vp, _i, _d, _f, _l = C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_long
 
@@ -46,8 +50,8 @@ class _Lib:
             build_port()
             self.lib = C.CDLL(PORT_SO)
             self.p = "orc_"
-        elif kind in ("reference", "reference_ofast"):
-            so = REF_SO if kind == "reference" else REF_OFAST_SO
+        elif kind in ("reference", "reference_ofast", "sdrj", "sdrj_ofast"):
+            so = {"reference": REF_SO, "reference_ofast": REF_OFAST_SO, "sdrj": SDRJ_SO, "sdrj_ofast": SDRJ_OFAST_SO}[kind]
             if not os.path.exists(so):
                 raise FileNotFoundError(so)
             self.lib = C.CDLL(so)
@@ -111,6 +115,20 @@ class _Lib:
             s("fir_run").argtypes = [_vp, _i, _vp, _vp, _i, _vp]
             s("hilbert_run").argtypes = [_i, _i, _vp, _i, _vp]
             s("delay_run").argtypes = [_i, _vp, _i, _vp]
+        if self.kind.startswith("sdrj"):
+            L = self.lib
+            L.sdrjh_new.restype = _vp
+            L.sdrjh_new.argtypes = []
+            L.sdrjh_add_root.argtypes = [_vp, _vp]
+            L.sdrjh_set_dc_correction.argtypes = [_vp, _i]
+            L.sdrjh_fft_vfo_slot.argtypes = [_vp, C.c_char_p]
+            L.sdrjh_bytes_to_floats.argtypes = [_vp, _vp, _l, _vp]
+            L.sdrjh_demod.argtypes = [_vp, _vp, _i]
+            L.sdrjh_get_samples.argtypes = [_vp, _vp, _i]
+            L.sdrjh_fft_count.argtypes = [_vp]
+            L.sdrjh_fft_call.argtypes = [_vp, _i]
+            L.sdrjh_fft_call.restype = _l
+            L.sdrjh_fft_get.argtypes = [_vp, _i, _vp, _i]
 
 
 _cache: dict[str, _Lib] = {}
@@ -128,6 +146,38 @@ def have_reference() -> bool:
 
 def have_reference_ofast() -> bool:
     return os.path.exists(REF_OFAST_SO)
+
+
+def have_sdrj_reference() -> bool:
+    """Both builds of the real sdrj.cpp / jonti/sdr.cpp (-O2 and -Ofast) exist."""
+    return os.path.exists(SDRJ_SO) and os.path.exists(SDRJ_OFAST_SO)
+
+
+def sdrj_run(frames, u8=None, f32=None, dc=True, topic="Main", topo=None, ofast=False, timeout=600):
+    """One stream through the REAL sdrj in a fresh process (tests/sdrj_ref_worker.py): its DC estimate is a
+    function-static (sdrj.cpp:280), so a stream from the zero state needs a process that has not run one yet.
+    `frames` are the complex lengths of the successive demodData calls over the bytes `u8` (through the real LUT)
+    or the interleaved floats `f32`.  Returns the worker's arrays (see its docstring) as a dict."""
+    import sys
+    import tempfile
+    so = SDRJ_OFAST_SO if ofast else SDRJ_SO
+    if not os.path.exists(so):
+        raise FileNotFoundError(so)
+    inp = {"frames": np.asarray(frames, np.int64), "dc": np.int64(bool(dc)), "topic": np.array(topic)}
+    if u8 is not None:
+        inp["u8"] = np.ascontiguousarray(u8, np.uint8).reshape(-1)
+    else:
+        inp["f32"] = _f32(f32).reshape(-1)
+    if topo is not None:
+        inp["topo"] = np.array(topo)
+    with tempfile.TemporaryDirectory(prefix="sdrjref") as d:
+        a, b = os.path.join(d, "in.npz"), os.path.join(d, "out.npz")
+        np.savez(a, **inp)
+        r = subprocess.run([sys.executable, _SDRJ_WORKER, so, a, b], capture_output=True, text=True, timeout=timeout)
+        if r.returncode != 0:
+            raise RuntimeError(f"sdrj worker failed ({r.returncode}): {r.stdout[-2000:]} {r.stderr[-2000:]}")
+        with np.load(b) as z:
+            return {k: z[k] for k in z.files}
 
 
 def _f32(a):

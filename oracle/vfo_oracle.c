@@ -23,6 +23,9 @@
 #include "vfo_oracle.h"
 
 #include <math.h>
+#ifdef _OPENMP
+#include <omp.h>
+#endif
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -136,8 +139,8 @@ void orc_hilbert_taps(int len, int fs, float *taps)
 
 /* DC-bias removal on the shared raw stream, sdrj.cpp:277-283: a first-order IIR whose
  * accumulator is function-static there (lives for the whole process); here the caller
- * keeps state[2] = {re, im}, zero at start.  (sdrj.cpp is not buildable in this image --
- * it needs librtlsdr's header -- so these four lines are restated from the text only.) */
+ * keeps state[2] = {re, im}, zero at start.  Pinned bit for bit to the real sdrj::demodData
+ * (oracle/_ref/libsdrjref*.so, tests/test_oracle_vs_reference.py; tests/golden/dc_reference.npz). */
 void orc_dc_correct(float *iq, int n, float state[2])
 {
     const float keep = 1.0f - 0.000001f, k = 0.000001f;
@@ -152,7 +155,8 @@ void orc_dc_correct(float *iq, int n, float state[2])
     state[1] = ai;
 }
 
-/* Dongle bytes -> float, jonti/sdr.cpp:43-49,122-129 and sdrj.cpp:155-160: b - 127. */
+/* Dongle bytes -> float, jonti/sdr.cpp:43-49,122-129 and sdrj.cpp:155-160: b - 127 (pinned to the
+ * real sdr::floats for all 256 bytes). */
 void orc_u8_to_float(const unsigned char *b, int n, float *out)
 {
     for (int i = 0; i < n; ++i)
@@ -573,6 +577,13 @@ void orc_vfo_process(orc_vfo *v, const float *iq, int n)
  * another VFO's state (vfo.cpp:253-264) -- as the "all host cores" CPU baseline. */
 void orc_process_roots(orc_vfo **roots, int n_roots, const float *iq, int n, int frames, int threads)
 {
+    /* Never more threads than the OpenMP environment grants (OMP_NUM_THREADS, else the CPUs of the affinity mask).
+     * num_threads() overrides that limit, and a CPU quota narrower than the affinity mask is invisible to libgomp: the
+     * surplus threads spin at every barrier on CPUs the process does not get, which slows the run by whole multiples. */
+#ifdef _OPENMP
+    if (threads > omp_get_max_threads())
+        threads = omp_get_max_threads();
+#endif
     if (threads <= 1) {
         for (int f = 0; f < frames; ++f)
             for (int r = 0; r < n_roots; ++r)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/*.npz from the REAL reference build (oracle/_ref/libsdrref.so).
+"""Generate tests/golden/*.npz from the REAL reference build (oracle/_ref/libsdrref.so, libsdrjref.so).
 
 Run in the build container only (needs /root/reference to have been compiled by
 `make -C oracle/ref`):   python tests/golden/make_golden.py
@@ -198,34 +198,38 @@ def gen_capture():
     """Row "recorded IQ" (BASELINE.json north_star; SURVEY.md 8c: the reference holds no recording): the capture-like byte
     stream of sdrreceiver_amd/synth.py (capture_like_u8: tuner noise, strong carriers past +-100, an ADC offset, 600 / 1200 Bd
     BPSK and 10 500 Bd OQPSK bursts on sdr_25E VFO frequencies) through the shipped sdr_25E profile as the reference runs
-    it: bytes -> b - 127 (jonti/sdr.cpp:43-49) -> DC-bias removal (sdrj.cpp:271-286, correct_dc_bias=1; restated in
-    oracle/vfo_oracle.c -- sdrj.cpp itself cannot be compiled here) -> the REAL reference's vfo tree, -O2 and, as a
-    patch against it, the -Ofast build the project ships.  Per VFO and frame: sha256 + head + max|z| of the final complex
-    stream, sha256 + head of the int16 payload; for -Ofast the stream's every 128th sample and the payload patch."""
+    it, all in the REAL code (oracle/_ref/libsdrjref.so, one process): bytes -> sdr::floats (jonti/sdr.cpp:43-49) ->
+    sdrj::demodData with the DC-bias removal on (sdrj.cpp:266-305, correct_dc_bias=1) -> the vfo tree attached to that
+    sdrj; and, as a patch against it, the -Ofast vfo build the project ships fed with the same frames.  Per VFO and frame:
+    sha256 + head + max|z| of the final complex stream, sha256 + head of the int16 payload; for -Ofast the stream's every
+    128th sample and the payload patch.  f<k>_dc_state is the plain-C oracle's accumulator after frame k (the real one is
+    a function-static nobody can read): the real DC-corrected frames are asserted identical to the oracle's here."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     topo = tp.profile_25e()
     u8 = synth.capture_like_u8(CAPTURE_FRAMES, topo.frame, topo.fs)
-    d = {"frames": np.int64(CAPTURE_FRAMES), "input_sha256": np.array(hashlib.sha256(u8.tobytes()).hexdigest())}
-    ref = ob.build_tree("reference", topo)
+    d = {"frames": np.int64(CAPTURE_FRAMES), "input_sha256": np.array(hashlib.sha256(u8.tobytes()).hexdigest()),
+         "provenance": np.array("real sdrj::demodData (DC on) over real sdr::floats, real vfo tree (oracle/_ref/libsdrjref.so)")}
+    real = ob.sdrj_run([topo.frame] * CAPTURE_FRAMES, u8=u8, dc=True, topic="", topo="profile_25e")
     fast = ob.build_tree("reference_ofast", topo) if ob.have_reference_ofast() else None
     state = np.zeros(2, np.float32)
     ndiff = total = 0
     peak = 0
     for f in range(CAPTURE_FRAMES):
-        iq = ob.u8_to_float(u8[2 * topo.frame * f: 2 * topo.frame * (f + 1)])
-        ob.dc_correct(iq, state)
+        iq = real["samples"][topo.frame * f: topo.frame * (f + 1)].view(np.float32).copy()
+        port = ob.u8_to_float(u8[2 * topo.frame * f: 2 * topo.frame * (f + 1)])
+        ob.dc_correct(port, state)
+        assert np.array_equal(port.view(np.uint32), iq.view(np.uint32)), f"frame {f}: oracle DC removal differs from sdrj"
         d[f"f{f}_dc_state"] = state.copy()
         d[f"f{f}_raw_sha"] = np.array(sha(iq))
-        ob.process_roots(ref[1], iq)
         if fast:
             ob.process_roots(fast[1], iq)
         for i, v in enumerate(topo.vfos):
-            z = ref[0][i].stream()
+            z = real[f"f{f}_v{i}_stream"]
             d[f"f{f}_v{i}_stream_sha"] = np.array(sha(z))
             d[f"f{f}_v{i}_stream_head"] = z[:64].copy()
             d[f"f{f}_v{i}_stream_absmax"] = np.float32(np.abs(z).max())
             if not topo.children(i):
-                a = ref[0][i].usb()
+                a = real[f"f{f}_v{i}_usb"]
                 peak = max(peak, int(np.abs(a.astype(np.int32)).max()))
                 d[f"f{f}_v{i}_pay_sha"] = np.array(sha(a))
                 d[f"f{f}_v{i}_pay_head"] = a[:64].copy()
@@ -243,6 +247,44 @@ def gen_capture():
                 d[f"f{f}_v{i}_ofast_stream_absmax"] = np.float32(np.abs(zf).max())
     np.savez_compressed(os.path.join(OUT, "capture_25e.npz"), **d)
     print(f"capture_25e.npz: {CAPTURE_FRAMES} frames, int16 peak {peak}; -Ofast: {ndiff} of {total} int16 samples differ from the -O2 build")
+
+
+def gen_dc_reference():
+    """tests/golden/dc_reference.npz: the real sdrj::demodData with the DC-bias removal on (sdrj.cpp:266-305, -O2 build;
+    the -Ofast build must give the same bits) over the byte regimes of tests/helpers.py DC_REFERENCE_REGIMES, each a
+    fresh process from the zero state, through the real sdr::floats LUT.  No streams are stored: per regime and frame the
+    sha256 of the DC-corrected cf32 bits, the first 64 samples and every 4096th; per regime the demodData calls on which
+    the raw spectrum (fftVFOSlot("Main")) was emitted; for the "lcg" regime the FNV-1a 64 of those spectra (what
+    host/demo.cpp prints)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from helpers import DC_REFERENCE_REGIMES, dc_reference_bytes, fnv1a64
+    d = {"regimes": np.array(sorted(DC_REFERENCE_REGIMES)), "lut": None}
+    for rid in sorted(DC_REFERENCE_REGIMES):
+        n, frames, _, _, label = DC_REFERENCE_REGIMES[rid]
+        u8 = np.concatenate(dc_reference_bytes(rid))
+        real = ob.sdrj_run([n] * frames, u8=u8, dc=True, topic="Main")
+        fast = ob.sdrj_run([n] * frames, u8=u8, dc=True, topic="Main", ofast=True)
+        assert np.array_equal(real["samples"].view(np.uint64), fast["samples"].view(np.uint64)), f"{rid}: -O2 and -Ofast differ"
+        assert np.array_equal(real["fft_calls"], fast["fft_calls"])
+        d["lut"] = real["lut"]
+        d[f"{rid}_label"] = np.array(label)
+        d[f"{rid}_frame"] = np.int64(n)
+        d[f"{rid}_frames"] = np.int64(frames)
+        d[f"{rid}_fft_calls"] = real["fft_calls"]
+        for k in range(frames):
+            z = real["samples"][n * k: n * (k + 1)]
+            d[f"{rid}_f{k}_sha"] = np.array(sha(z))
+            d[f"{rid}_f{k}_head"] = z[:64].copy()
+            d[f"{rid}_f{k}_every4096"] = z[::4096].copy()
+        if rid == "lcg":
+            p = 0
+            fnv = []
+            for ln in real["fft_len"]:
+                fnv.append(fnv1a64(real["fft_data"][p: p + ln]))
+                p += ln
+            d[f"{rid}_fft_fnv1a"] = np.array(fnv, np.uint64)
+        print(f"dc_reference {rid}: {frames} x {n}, spectra on calls {list(real['fft_calls'])}")
+    np.savez_compressed(os.path.join(OUT, "dc_reference.npz"), **d)
 
 
 def gen_zmq():
@@ -290,9 +332,14 @@ if __name__ == "__main__":
         gen_dropin()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "capture":
-        if not ob.have_reference():
-            sys.exit("oracle/_ref/libsdrref.so missing: run `make -C oracle/ref` first (needs /root/reference)")
+        if not ob.have_sdrj_reference():
+            sys.exit("oracle/_ref/libsdrjref.so missing: run `make -C oracle/ref` first (needs /root/reference)")
         gen_capture()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "dc":
+        if not ob.have_sdrj_reference():
+            sys.exit("oracle/_ref/libsdrjref*.so missing: run `make -C oracle/ref` first (needs /root/reference)")
+        gen_dc_reference()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "ofast":
         if not (ob.have_reference() and ob.have_reference_ofast()):
@@ -304,6 +351,7 @@ if __name__ == "__main__":
     gen_primitives()
     gen_chains()
     gen_capture()
+    gen_dc_reference()
     gen_zmq()
     gen_dropin()
     if ob.have_reference_ofast():

@@ -197,3 +197,77 @@ def adversarial_frames(topo, case, n_frames=5, seed=606):
     rng = np.random.default_rng(seed)
     for f in range(n_frames):
         yield f, synth.tone_frame(topo.frame, topo.fs, [(f_c, a_c)], f * topo.frame) + rng.integers(-1, 2, 2 * topo.frame).astype(np.float32)
+
+
+# ---- tests/golden/dc_reference.npz: the DC-bias removal of the REAL sdrj::demodData (sdrj.cpp:266-305) ---------------------------
+# Byte streams from the integer generator synth.Lcg (no numpy RNG: the fixture does not depend on its version).  A regime is
+# (frame length, frames, kind, parameters); "noise" is an offset (di, dq) plus Lcg noise of standard deviation sigma per
+# component, "pattern" a sequence of per-frame byte patterns, "step" two noise regimes, the second from half way through.
+DC_REFERENCE_REGIMES = {
+    # the DC_STREAMS regimes of test_gpu_parity.py, 14 frames of 384 000 samples from the zero state
+    "capture": (384000, 14, "noise", (1.3, -0.7, 7.0), "offsets of the capture-like stream"),
+    "binade": (384000, 14, "noise", (0.25, 4.94, 7.0), "next to a binade boundary and a rounding threshold"),
+    "opposite": (384000, 14, "noise", (100.0, -120.0, 10.0), "large, opposite signs (one estimate pinned to its threshold)"),
+    "pinned": (384000, 14, "noise", (30.0, -2.0, 3.0), "an offset ten times the noise (pinned)"),
+    "nooffset": (384000, 14, "noise", (0.0, 0.02, 7.0), "no offset at all (the estimate wanders through zero)"),
+    "quiet": (384000, 14, "noise", (1.3, -0.7, 2.0), "quiet front end"),
+    "strong": (384000, 14, "noise", (1.3, -0.7, 50.0), "strong carriers"),
+    # constant and extreme bytes; 480 000 = 468.75 blocks of 1 024 (a partial last block)
+    "const0": (480000, 3, "pattern", ("0",), "constant 0"),
+    "const127": (480000, 3, "pattern", ("127",), "constant 127"),
+    "const255": (480000, 3, "pattern", ("255",), "constant 255"),
+    "alt": (480000, 3, "pattern", ("alt",), "alternating 0 / 255 samples"),
+    "extremes": (57600, 8, "pattern", ("255", "255", "0", "0", "127", "127", "alt", "alt"), "extremes in turn, short frames"),
+    "step": (384000, 8, "step", ((20.0, -10.0, 5.0), (-30.0, 15.0, 5.0)), "an offset step half way through"),
+    "capture480": (480000, 6, "noise", (1.3, -0.7, 7.0), "capture-like offsets, partial last block"),
+    "lcg": (384000, 9, "lcg", (), "the synthetic LCG frames of host/demo.cpp (components -8 ... 8)"),
+}
+
+
+def _lcg_noise(lcg, n, sigma):
+    """n values of mean 0 and standard deviation sigma: the sum of four 24-bit uniforms on [-1/2, 1/2) (exact in float64),
+    scaled by sigma * sqrt(3)."""
+    u = (lcg.draw(4 * n) >> np.uint32(8)).astype(np.float64) / float(1 << 24) - 0.5
+    return u.reshape(n, 4).sum(axis=1) * (sigma * np.sqrt(3.0))
+
+
+def _noise_bytes(lcg, n_complex, di, dq, sigma):
+    z = _lcg_noise(lcg, 2 * n_complex, sigma)
+    z[0::2] += di
+    z[1::2] += dq
+    return np.clip(np.rint(z) + 127, 0, 255).astype(np.uint8)
+
+
+def dc_reference_bytes(rid):
+    """The dongle bytes of regime `rid`, one array per frame (2 * frame bytes each)."""
+    from sdrreceiver_amd import synth
+    n, frames, kind, par, _ = DC_REFERENCE_REGIMES[rid]
+    lcg = synth.Lcg(1000 + sorted(DC_REFERENCE_REGIMES).index(rid))
+    out = []
+    for f in range(frames):
+        if kind == "noise":
+            out.append(_noise_bytes(lcg, n, *par))
+        elif kind == "step":
+            out.append(_noise_bytes(lcg, n, *par[0 if f < frames // 2 else 1]))
+        elif kind == "lcg":
+            if f == 0:
+                lcg = synth.Lcg(1)  # host/demo.cpp's stream: x = 1 at the start
+            out.append(synth.lcg_frame_u8(n, lcg))
+        else:
+            p = par[f % len(par)]
+            if p == "alt":
+                b = np.zeros(2 * n, np.uint8)
+                b[0::4] = 255
+                b[1::4] = 255
+            else:
+                b = np.full(2 * n, int(p), np.uint8)
+            out.append(b)
+    return out
+
+
+def fnv1a64(a) -> int:
+    """FNV-1a 64 of the bytes of `a` (host/demo.cpp prints it for every message and spectrum)."""
+    h = 1469598103934665603
+    for b in np.ascontiguousarray(a).tobytes():
+        h = ((h ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    return h

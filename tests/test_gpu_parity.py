@@ -12,7 +12,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import ADVERSARIAL_CARRIERS, GOLDEN_TREES, REFERENCE_BUILDS_DIFFER, adversarial_frames, bits, golden, golden_topology, random_topology, sha
+from helpers import ADVERSARIAL_CARRIERS, DC_REFERENCE_REGIMES, GOLDEN_TREES, REFERENCE_BUILDS_DIFFER, adversarial_frames, bits, golden, golden_topology, random_topology, sha, dc_reference_bytes
 from oracle import binding as ob
 from sdrreceiver_amd import synth, topology as tp
 
@@ -1192,6 +1192,153 @@ def test_speculative_dc_chain_on_constant_and_extreme_bytes(Receiver, per_step):
             ob.dc_correct(iq, state)
             assert np.array_equal(bits(rx.raw()), bits(iq.view(np.complex64))), (n, f)
         rx.close()
+
+
+# ------------------------------------------------------------------------------ DC-bias removal against the real sdrj
+# tests/golden/dc_reference.npz: the real sdrj::demodData (sdrj.cpp:266-305, built untouched with the real sdr::floats LUT)
+# over the byte regimes of helpers.DC_REFERENCE_REGIMES, from the zero state.  These tests read only the fixture.
+_DC_BYTES: dict = {}
+
+
+def _dc_regime(rid):
+    if rid not in _DC_BYTES:
+        _DC_BYTES[rid] = dc_reference_bytes(rid)
+    n, frames, _, _, _ = DC_REFERENCE_REGIMES[rid]
+    return n, _DC_BYTES[rid]
+
+
+def _check_dc_fixture(g, rid, k, z, ctx):
+    """Frame k of regime rid, DC-corrected, against the real build: first 64 samples, every 4096th, sha256 of all bits."""
+    n = int(g[f"{rid}_frame"])
+    assert z.size == n, ctx
+    assert np.array_equal(bits(z[:64]), bits(g[f"{rid}_f{k}_head"])), (ctx, "first 64 samples")
+    assert np.array_equal(bits(z[::4096]), bits(g[f"{rid}_f{k}_every4096"])), (ctx, "every 4096th sample")
+    assert sha(z) == str(g[f"{rid}_f{k}_sha"]), (ctx, "sha256 of the DC-corrected frame")
+
+
+def _dc_topology(n, subs=0):
+    """One main VFO on frames of n samples (fs = 4n): alone, /4; with `subs` USB leaves under it, undecimated (the leaves
+    then take whole frames: n / 4 would leave a last chunk under 256 samples for n = 480 000 and 57 600)."""
+    t = tp.Topology(fs=4 * n, frame=n, name=f"dcref{n}")
+    t.vfos.append(tp.VfoDesc(topic="M", parent=-1, fs=4 * n, decimate_count=0 if subs else 2, mixer_freq=float(n // 7), demod_usb=False,
+                             cstyle=1, samples_per_buffer=n))
+    for j in range(subs):
+        t.vfos.append(tp.VfoDesc(topic=f"S{j}", parent=0, fs=4 * n, decimate_count=2, mixer_freq=float(n // 11) * (j + 1), filter_bw=0,
+                                 gain=tp._g(0.05), cstyle=1, samples_per_buffer=n))
+    return t
+
+
+@pytest.mark.parametrize("config", ["sequential", "1 per step", "2 per step", "4 per step", "8 per step"])
+def test_dc_bias_removal_is_the_real_sdrj(Receiver, config):
+    """sdrx_process_u8 with correct_dc=1 -- the LUT and k_dc_products / k_dc_chain(_spec) / k_dc_apply -- on every regime of
+    the fixture, a fresh context per regime: every DC-corrected frame bit for bit what the real demodData produced.
+    dc_speculative=0 (every sample in turn) and the speculative chain with 1, 2, 4 and 8 blocks per step.  The fixture must
+    drive the speculative chain through verified blocks and through blocks redone sequentially, and (several blocks per
+    step) through blocks taken again on their own: otherwise one of its code paths would go unpinned."""
+    g = golden("dc_reference.npz")
+    kw = {"dc_speculative": False} if config == "sequential" else {"dc_blocks_per_step": int(config.split()[0])}
+    blocks = fallback = retried = frames_fb = frames_retried = 0
+    for rid in sorted(DC_REFERENCE_REGIMES):
+        n, u8 = _dc_regime(rid)
+        rx = Receiver.from_topology(_dc_topology(n), exact=True, **kw)
+        prev = (0, 0, 0)
+        for k, b in enumerate(u8):
+            rx.process_u8(b, correct_dc=True)
+            _check_dc_fixture(g, rid, k, rx.raw(), (config, rid, k))
+            st = rx.stats()
+            cur = (st["dc_blocks"], st["dc_fallback_blocks"], st["dc_retried_blocks"])
+            d = [c - p for c, p in zip(cur, prev)]
+            prev = cur
+            blocks, fallback, retried = blocks + d[0], fallback + d[1], retried + d[2]
+            frames_fb += d[1] > 0
+            frames_retried += d[2] > 0
+        rx.close()
+    print(f"{config}: {blocks} blocks, {fallback} redone sequentially ({frames_fb} frames), {retried} taken again on their own "
+          f"({frames_retried} frames)")
+    if config != "sequential":
+        assert blocks > 0 and fallback > 0 and blocks - fallback > 0, (blocks, fallback)
+        assert frames_fb > 0
+        if kw["dc_blocks_per_step"] > 1:
+            assert retried > 0 and frames_retried > 0, retried
+
+
+def test_pipelined_dc_bias_removal_is_the_real_sdrj(Receiver):
+    """sdrx_submit_u8 / sdrx_wait with correct_dc=1, two frames in flight (the accumulator carries from one in-flight frame
+    to the next): after each pair is delivered the context is idle and its raw frame -- the second of the pair -- must be
+    the real build's; a last odd frame goes through sdrx_process_u8."""
+    g = golden("dc_reference.npz")
+    for rid in sorted(DC_REFERENCE_REGIMES):
+        n, u8 = _dc_regime(rid)
+        rx = Receiver.from_topology(_dc_topology(n, subs=2), exact=True)
+        k = 0
+        while k < len(u8):
+            if k + 1 < len(u8):
+                rx.submit_u8(u8[k], correct_dc=True)
+                rx.submit_u8(u8[k + 1], correct_dc=True)
+                rx.wait()
+                rx.wait()
+                k += 2
+            else:
+                rx.process_u8(u8[k], correct_dc=True)
+                k += 1
+            _check_dc_fixture(g, rid, k - 1, rx.raw(), ("pipelined", rid, k - 1))
+        rx.close()
+
+
+def test_group_dc_bias_removal_is_the_real_sdrj():
+    """A 2-member sdrx_group fed with bytes and correct_dc=1: every member runs the recurrence on the whole frame with an
+    accumulator of its own; the raw frame of every member that holds VFOs is the real build's, frame after frame."""
+    import ctypes as C
+    from sdrreceiver_amd.receiver import Group
+    g = golden("dc_reference.npz")
+    for rid in sorted(DC_REFERENCE_REGIMES):
+        n, u8 = _dc_regime(rid)
+        grp = Group.from_topology(_dc_topology(n, subs=2), [0, 0])
+        ctxs = [c for c in (grp.member_context(m)[0] for m in range(2)) if c.value]
+        assert len(ctxs) == 2
+        for k, b in enumerate(u8):
+            grp.process_u8(b, correct_dc=True)
+            for m, ctx in enumerate(ctxs):
+                out = np.zeros(2 * n, np.float32)
+                got = C.c_int()
+                assert grp.L.sdrx_get_raw(ctx, out.ctypes.data, n, C.byref(got)) == 0
+                assert got.value == n
+                _check_dc_fixture(g, rid, k, out.view(np.complex64), ("group", rid, k, m))
+        grp.close()
+
+
+def test_mirror_sdrj_dc_removal_is_the_real_sdrj(Receiver):
+    """The mirror class sdrj (receiver.py) with setDCCorrection(true) and fftVFOSlot("Main"), fed with demodBytes: the raw
+    frame of every call, and the raw spectrum emitted on exactly the calls the real build emitted it on (5, 9, 13, ...)
+    with that call's DC-corrected contents."""
+    from sdrreceiver_amd.receiver import sdrj, vfo
+    g = golden("dc_reference.npz")
+    for rid in sorted(DC_REFERENCE_REGIMES):
+        n, u8 = _dc_regime(rid)
+        t = _dc_topology(n, subs=1)
+        nodes = []
+        for d in t.vfos:
+            v = vfo()
+            v.setFs(d.fs); v.setDecimationCount(d.decimate_count); v.setMixerFreq(d.mixer_freq)
+            v.setFilterBandwidth(d.filter_bw); v.setGain(d.gain); v.setDemodUSB(d.demod_usb)
+            v.setCompressonStyle(d.cstyle); v.setScaleComp(d.scalecomp); v.setZmqTopic(d.topic)
+            v.init(d.samples_per_buffer, False, d.late_decimate)
+            nodes.append(v)
+        nodes[0].setVFOs([nodes[1]])
+        radio = sdrj()
+        radio.setVFOs([nodes[0]])
+        radio.setDCCorrection(True)
+        emitted = []
+        radio.fftData = lambda a: emitted.append((call, a.copy()))
+        radio.fftVFOSlot("Main")
+        for k, b in enumerate(u8):
+            call = k + 1
+            radio.demodBytes(b)
+            _check_dc_fixture(g, rid, k, radio.rx.raw(), ("mirror", rid, k))
+        assert [c for c, _ in emitted] == list(g[f"{rid}_fft_calls"]), rid
+        for c, a in emitted:
+            _check_dc_fixture(g, rid, c - 1, a, ("mirror spectrum", rid, c))
+        radio.rx.close()
 
 
 # ------------------------------------------------------------------------------ edge geometry

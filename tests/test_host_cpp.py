@@ -235,6 +235,27 @@ def test_cpp_host_fft_taps(tmp_path):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("u8", [False, True])
+def test_cpp_host_dc_removal_is_the_real_sdrj(u8, tmp_path):
+    """sdrj of host/sdrx_host.hpp with correct_dc_bias=1 and fftVFOSlot("Main"): the float path (host-side DC removal,
+    compiled at -O2 without -march: no FMA contraction) and the byte path (LUT + DC removal on the device) emit the raw
+    spectrum on the calls the REAL sdrj::demodData emitted it on, with the real DC-corrected contents (FNV-1a 64 from
+    tests/golden/dc_reference.npz, regime "lcg": the demo's own LCG frames through the real build)."""
+    from helpers import golden
+    _build()
+    g = golden("dc_reference.npz")
+    p = tmp_path / "profile.ini"
+    p.write_text(INI_25E_LIKE)
+    topo = tp.topology_from_ini(INI_25E_LIKE)
+    assert topo.frame == int(g["lcg_frame"]) and topo.correct_dc
+    frames = int(g["lcg_frames"])
+    out = subprocess.check_output([DEMO, str(p), "--frames", str(frames), "--fft", "Main"] + (["--u8"] if u8 else []), text=True)
+    got = [l.split() for l in out.splitlines() if l.startswith("fft ")]
+    want = [["fft", str(int(c) - 1), "Main", str(topo.frame), f"{int(h):016x}"] for c, h in zip(g["lcg_fft_calls"], g["lcg_fft_fnv1a"])]
+    assert len(want) == 2 and got == want
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("devices", [None, "0,0"])
 def test_cpp_host_fft_tap_on_a_fused_late_decimation(devices, tmp_path):
     """The 54W-like profile: VFO51 / VFO52 are /5 leaves with decimate_count 0 -- their low-pass runs inside the mix wave

@@ -3,7 +3,7 @@ outputs of the real reference build (tests/golden/make_golden.py).  Bit-exact ev
 import numpy as np
 import pytest
 
-from helpers import GOLDEN_TREES, bits, golden, golden_topology, sha
+from helpers import DC_REFERENCE_REGIMES, GOLDEN_TREES, bits, dc_reference_bytes, golden, golden_topology, sha
 from oracle import binding as ob
 from sdrreceiver_amd import synth
 
@@ -161,3 +161,24 @@ def test_capture_like_stream_through_the_shipped_profile():
                 shipped[g[f"f{f}_v{i}_ofast_pay_idx"]] = g[f"f{f}_v{i}_ofast_pay_val"]
                 assert sha(shipped) == str(g[f"f{f}_v{i}_ofast_pay_sha"]) and np.abs(shipped.astype(np.int32) - a).max() <= 1, (f, i)
     assert 26000 < peak < 32768  # near full scale, never past it (a wrapped sample would make "+-1 LSB" meaningless)
+
+
+@pytest.mark.parametrize("rid", sorted(DC_REFERENCE_REGIMES))
+def test_dc_correct_against_the_real_sdrj_fixture(rid):
+    """orc_u8_to_float + orc_dc_correct (the restatement every GPU DC test compares with) against
+    tests/golden/dc_reference.npz, the real sdrj::demodData's output on the same regenerated bytes: the LUT, and every
+    DC-corrected frame's sha256, head and every 4096th sample."""
+    g = golden("dc_reference.npz")
+    assert np.array_equal(bits(ob.u8_to_float(np.arange(256))), bits(g["lut"]))
+    n = int(g[f"{rid}_frame"])
+    u8 = dc_reference_bytes(rid)
+    assert len(u8) == int(g[f"{rid}_frames"])
+    state = np.zeros(2, np.float32)
+    for k, b in enumerate(u8):
+        x = ob.u8_to_float(b)
+        ob.dc_correct(x, state)
+        z = x.view(np.complex64)
+        assert z.size == n
+        assert np.array_equal(bits(z[:64]), bits(g[f"{rid}_f{k}_head"])), (rid, k)
+        assert np.array_equal(bits(z[::4096]), bits(g[f"{rid}_f{k}_every4096"])), (rid, k)
+        assert sha(z) == str(g[f"{rid}_f{k}_sha"]), (rid, k)

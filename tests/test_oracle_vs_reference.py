@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import SAMPLE_INI, bits, golden_topology, sha
+from helpers import DC_REFERENCE_REGIMES, SAMPLE_INI, bits, dc_reference_bytes, golden, golden_topology, sha
 from oracle import binding as ob
 from sdrreceiver_amd import synth, topology as tp
 
@@ -190,3 +190,96 @@ def test_reference_builds_under_a_strong_carrier(case):
                 lsb = max(lsb, int(np.abs(a_nodes[i].usb().astype(np.int32) - b_nodes[i].usb().astype(np.int32)).max()))
     print(f"{case}: -O2 vs -Ofast build of the reference: worst stream difference {worst:.3g} of max|stream|, int16 within {lsb} LSB")
     assert lsb == 1 and abs(worst / REFERENCE_BUILDS_DIFFER[case] - 1.0) < 0.15, worst
+
+
+# ---- the byte LUT and the DC-bias removal of the REAL sdrj / sdr (oracle/_ref/libsdrjref*.so; one stream per process) --------
+needs_sdrj = pytest.mark.skipif(not ob.have_sdrj_reference(), reason="oracle/_ref/libsdrjref.so / libsdrjref_ofast.so not built "
+                                "(make -C oracle/ref needs the reference sources)")
+SDRJ_BUILDS = [pytest.param(False, id="O2"), pytest.param(True, id="Ofast")]
+
+
+def _port_dc(u8_frames):
+    """bytes -> orc_u8_to_float -> orc_dc_correct from the zero state, frame by frame: the restatement under test."""
+    state = np.zeros(2, np.float32)
+    out = []
+    for b in u8_frames:
+        x = ob.u8_to_float(b)
+        ob.dc_correct(x, state)
+        out.append(x.view(np.complex64))
+    return np.concatenate(out)
+
+
+@needs_sdrj
+@pytest.mark.parametrize("ofast", SDRJ_BUILDS)
+def test_u8_lut_is_the_real_one(ofast):
+    """orc_u8_to_float for all 256 byte values against sdr::floats.at() of a real sdr object (jonti/sdr.cpp:43-49,125;
+    sdrj.cpp:158), and the fixture tests/golden/dc_reference.npz carries the same table."""
+    b = np.arange(256, dtype=np.uint8)
+    real = ob.sdrj_run([128], u8=b, dc=False, ofast=ofast)
+    assert np.array_equal(bits(real["lut"]), bits(ob.u8_to_float(b)))
+    assert np.array_equal(bits(real["samples"].view(np.float32)), bits(ob.u8_to_float(b)))  # demodData without DC: untouched
+    assert np.array_equal(bits(golden("dc_reference.npz")["lut"]), bits(real["lut"]))
+
+
+@needs_sdrj
+@pytest.mark.parametrize("ofast", SDRJ_BUILDS)
+@pytest.mark.parametrize("rid", sorted(DC_REFERENCE_REGIMES))
+def test_dc_correct_is_the_real_demod_data(rid, ofast):
+    """orc_dc_correct (oracle/vfo_oracle.c) against the real sdrj::demodData with setDCCorrection(true), bit for bit, on every
+    regime of DC_REFERENCE_REGIMES: the DC_STREAMS regimes of test_gpu_parity.py over 14 x 384 000 samples from the zero
+    state (the estimate climbs through its binades and settles), constant 0 / 127 / 255 and alternating 0 / 255 bytes,
+    partial last blocks, an offset step half way.  The raw spectrum goes out on calls 5, 9, 13, ... after
+    fftVFOSlot("Main") (sdrj.cpp:296-303) and holds that call's DC-corrected samples.  The live build also reproduces the
+    committed fixture, so the GPU tests that read only the fixture stay pinned to the real code."""
+    n, frames, _, _, _ = DC_REFERENCE_REGIMES[rid]
+    u8 = dc_reference_bytes(rid)
+    real = ob.sdrj_run([n] * frames, u8=np.concatenate(u8), dc=True, topic="Main", ofast=ofast)
+    want = _port_dc(u8)
+    assert real["samples"].size == want.size
+    bad = np.flatnonzero(bits(real["samples"]) != bits(want))
+    assert bad.size == 0, (rid, "first difference at sample", int(bad[0]) if bad.size else None)
+    assert list(real["fft_calls"]) == list(range(5, frames + 1, 4)), real["fft_calls"]
+    p = 0
+    for call, ln in zip(real["fft_calls"], real["fft_len"]):
+        assert ln == n
+        assert np.array_equal(bits(real["fft_data"][p: p + ln]), bits(want[n * (call - 1): n * call])), (rid, call)
+        p += ln
+    g = golden("dc_reference.npz")
+    for k in range(frames):
+        assert sha(real["samples"][n * k: n * (k + 1)]) == str(g[f"{rid}_f{k}_sha"]), (rid, k, "fixture is stale")
+
+
+@needs_sdrj
+@pytest.mark.parametrize("ofast", SDRJ_BUILDS)
+def test_real_dc_removal_does_not_depend_on_the_frame_split(ofast):
+    """The accumulator carries across demodData calls: frames of unequal lengths that are not multiples of 16 samples
+    give the bits of one whole-stream call (and of the oracle)."""
+    rid = "capture"
+    u8 = np.concatenate(dc_reference_bytes(rid)[:3])
+    total = u8.size // 2
+    cuts = [1, 15, 1023, 1025, 77777, 4099, 250001, 17, 300000 - 3]
+    frames = cuts + [total - sum(cuts)]
+    assert frames[-1] > 0 and all(c % 16 for c in cuts)
+    whole = ob.sdrj_run([total], u8=u8, dc=True, topic="", ofast=ofast)
+    split = ob.sdrj_run(frames, u8=u8, dc=True, topic="", ofast=ofast)
+    assert np.array_equal(bits(whole["samples"]), bits(split["samples"]))
+    assert np.array_equal(bits(whole["samples"]), bits(_port_dc([u8])))
+
+
+@needs_sdrj
+def test_python_host_dc_correct_is_the_real_one():
+    """receiver._dc_correct (the mirror sdrj's float path) against the real demodData: from the zero state, and from the
+    oracle's state after 12 frames of the dongle-like and pinned regimes (a settled estimate), on frames of 40 000 samples."""
+    from sdrreceiver_amd.receiver import _dc_correct
+    for rid in ("capture", "opposite", "step"):
+        n, frames, _, _, _ = DC_REFERENCE_REGIMES[rid]
+        u8 = dc_reference_bytes(rid)
+        real = ob.sdrj_run([n] * frames, u8=np.concatenate(u8), dc=True, topic="")["samples"]
+        state = np.zeros(2, np.float32)
+        for k in range(frames):
+            if k in (0, frames - 2):
+                x = ob.u8_to_float(u8[k][: 2 * 40000])
+                s = state.copy()
+                _dc_correct(x, s)
+                assert np.array_equal(bits(x.view(np.complex64)), bits(real[n * k: n * k + 40000])), (rid, k)
+            ob.dc_correct(ob.u8_to_float(u8[k]), state)
