@@ -260,6 +260,40 @@ int sdrx_get_taps(sdrx_ctx *ctx, int id, int which, float *out, int max, int *n)
 /* NCO table entries [first, first+count) of node `id` as the device generated them. */
 int sdrx_get_nco(sdrx_ctx *ctx, int id, long first, long count, float *out_iq);
 
+/* ---- spectrum display ( = MainWindow::fftHandlerSlot, mainwindow.cpp:411-478, on the device) -------------------
+ * One display state per enabled spectrum: VFO `id` (its decimate[decimateCount], what vfo.cpp:290-293 emits as fftData)
+ * or SDRX_SPECTRUM_RAW (the raw frame exactly as sdrx_get_raw would return it -- for sdrx_process_device /
+ * sdrx_submit_device frames the caller's device frame, read inside that frame's own launch sequence).  Per update: the
+ * first n_in = min(stream length, 8192) samples times the Hann window (a shorter stream is zero-padded), a kiss_fft of 8192
+ * points in kiss_fft's own butterfly order (bins bit-identical to kiss_fft on the same input, whatever option "exact" is),
+ * then pwr[(i + 4096) mod 8192] = pwr*0.95 + 0.5*log10(fmax(100000*|bin_i|/8192, 1)) in double, maxval / aveval of pwr and
+ * the "maxval - aveval < 10 -> maxval = aveval + 10" rule.
+ * Cadence: a VFO spectrum is updated after every frame whose stream exists (a leaf whose late decimation or demodulation
+ * is fused into the mix wave keeps its stream only while it is tapped, sdrx_set_tap: otherwise `updates` does not move);
+ * the raw spectrum follows sdrj's counter (sdrj.cpp:296-303): the 5th frame after enabling, then every 4th.
+ * Deliberately not reproduced: the reference's ONE shared display when a GUI topic names several VFOs (their updates and
+ * stale tails mixed in tree order) -- here every VFO has its own state, which equals the reference whenever one VFO is
+ * selected.  No spectrum enabled: no launch, no allocation, no event -- payloads and streams are identical either way. */
+#define SDRX_SPECTRUM_BINS 8192 /* nFFT, mainwindow.cpp:243 */
+#define SDRX_SPECTRUM_RAW (-2)  /* sdrj's own fftData: the raw frame, at sdrj's every-4th-call cadence */
+typedef struct sdrx_spectrum_info {
+    int64_t updates;        /* fftHandlerSlot calls since the spectrum was enabled */
+    int32_t n_in;           /* samples each update windows: min(stream length, 8192) */
+    int32_t reserved;
+    double maxval, aveval;  /* of the last update, after the "< 10 dB" rule */
+} sdrx_spectrum_info;
+/* enable = 1: allocate (if needed) and ZERO the state and, for SDRX_SPECTRUM_RAW, the cadence counter (the GUI's combo-box
+ * reset, mainwindow.cpp:539-549); 0: release it.  After sdrx_finalize, not while submitted frames are in flight. */
+int sdrx_set_spectrum(sdrx_ctx *ctx, int id, int enable);
+/* The state after the last frame: `pwr` 8192 doubles (display order), `smooth` 8182 doubles (the 5-point mean of
+ * mainwindow.cpp:454-458), `bins_iq` 2*8192 floats (the last update's FFT output, natural order); each may be NULL.
+ * SDRX_ESTATE before sdrx_finalize, while frames are in flight, or for a spectrum that is not enabled; SDRX_EINVAL for a bad
+ * id.  Runs what the software pipeline of sdrx_process_device still holds first. */
+int sdrx_get_spectrum(sdrx_ctx *ctx, int id, sdrx_spectrum_info *info, double *pwr, double *smooth, float *bins_iq);
+/* The many-channel monitor: maxval / aveval / updates of n enabled spectra `ids` in one small device-to-host copy (each
+ * output array may be NULL). */
+int sdrx_get_spectrum_levels(sdrx_ctx *ctx, const int *ids, int n, double *maxval, double *aveval, int64_t *updates);
+
 /* ---- one tree on several GPUs, one host process ---------------------------------------------------
  * The fan-out the reference does on one thread -- sdrj::demodData over the main VFOs (sdrj.cpp:288-294),
  * each main over its sub VFOs (vfo.cpp:253-264) -- sharded over the devices of one node:

@@ -13,6 +13,7 @@ CSRC = os.path.join(_HERE, "csrc")
 NKERNELS = 8
 SDRX_EINVAL, SDRX_ESTATE, SDRX_EFILTER, SDRX_EHIP, SDRX_EUNSUPPORTED, SDRX_ENOMEM, SDRX_ENOSTREAM = -1, -2, -3, -4, -5, -6, -7  # include/sdrx.h
 SDRX_DIFFERENT = 1  # sdrx_*_if_same: the frame is not the one the source context staged
+SPECTRUM_BINS, SPECTRUM_RAW = 8192, -2  # SDRX_SPECTRUM_BINS, SDRX_SPECTRUM_RAW
 
 
 class VfoDescC(C.Structure):
@@ -41,6 +42,12 @@ class StatsC(C.Structure):
         ("device_bytes", C.c_int64), ("frames", C.c_int64), ("mix_chunks_per_frame", C.c_int64),
         ("dc_blocks", C.c_int64), ("dc_fallback_blocks", C.c_int64), ("dc_retried_blocks", C.c_int64),
     ]
+
+
+class SpectrumInfoC(C.Structure):
+    """struct sdrx_spectrum_info"""
+    _fields_ = [("updates", C.c_int64), ("n_in", C.c_int32), ("reserved", C.c_int32),
+                ("maxval", C.c_double), ("aveval", C.c_double)]
 
 
 PUBLISH_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
@@ -77,6 +84,9 @@ SYMBOLS = {
     "sdrx_get_prequant": (_i, [_vp, _i, _vp, _i, C.POINTER(_i)]),
     "sdrx_get_taps": (_i, [_vp, _i, _i, _vp, _i, C.POINTER(_i)]),
     "sdrx_get_nco": (_i, [_vp, _i, C.c_long, C.c_long, _vp]),
+    "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
+    "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
+    "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "sdrx_submit_shared": (_i, [_vp, _vp]),
     "sdrx_process_shared": (_i, [_vp, _vp]),
     "sdrx_submit_if_same": (_i, [_vp, _vp, _vp, _i]),

@@ -27,12 +27,16 @@
 
 #include "../../include/sdrx.h"
 #include "kernels.hip"
+#include "spectrum.hip"
 #include "tapdesign.h"
 
 using namespace sdrx;
 
 static_assert(sizeof(sdrx_vfo_desc) == 56 && offsetof(sdrx_vfo_desc, topic) == 48, "sdrx_vfo_desc ABI layout");
 static_assert(sizeof(sdrx_stats) == 80, "sdrx_stats ABI layout");
+static_assert(sizeof(sdrx_spectrum_info) == sizeof(SpecRecord) && offsetof(sdrx_spectrum_info, maxval) == offsetof(SpecRecord, maxval) &&
+                  SDRX_SPECTRUM_BINS == kSpecN,
+              "sdrx_spectrum_info ABI layout");
 
 namespace {
 
@@ -199,6 +203,21 @@ struct sdrx_ctx {
     double t_ms[SDRX_NKERNELS] = {0};
     int64_t t_n[SDRX_NKERNELS] = {0};
     int64_t t_bytes[SDRX_NKERNELS] = {0};
+
+    // spectrum display (sdrx_set_spectrum): state slot id of a VFO, nodes.size() of the raw frame.  All of it is allocated by
+    // sdrx_set_spectrum; with nothing enabled the frame sequence launches nothing more.
+    struct SpecState {
+        double *pwr = nullptr; // kSpecN doubles, then kSpecN cf32 bins (one allocation)
+        bool on = false;
+    };
+    std::vector<SpecState> spec;     // per slot
+    SpecRecord *d_spec_rec = nullptr; // per slot (one array: sdrx_get_spectrum_levels is one copy)
+    float2 *d_spec_tw = nullptr;      // kiss_fft's twiddles, then the Hann window (kSpecN floats)
+    SpecDesc *d_spec_desc = nullptr;  // the VFO spectra that have a stream, by tree level; then the raw one
+    int spec_n_desc = 0;              // VFO descriptors in d_spec_desc
+    std::vector<int> spec_level_begin; // first descriptor of every level (n_levels + 1 entries)
+    bool spec_raw_on = false;
+    int spec_raw_count = 0;           // sdrj's `count` (sdrj.cpp:84-101, 296-303)
 };
 
 namespace {
@@ -310,6 +329,45 @@ struct Bracket { // RAII: event pair around one launch when timing is on, on the
 
 int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode);
 int pipeline_flush(sdrx_ctx *c);
+
+// The VFO spectra of tree levels lo..hi, whose streams hold frame frames[l] (frames == nullptr: all hold frame f): behind the
+// launch that wrote those streams, before anything can overwrite them (frame f + 2 -- the next writer of that parity -- is
+// queued behind this launch on the same stream, or waits for ev_tail).  Nothing enabled: nothing is launched.
+void spectrum_launch(sdrx_ctx *c, hipStream_t st, int lo, int hi, unsigned long long f, const unsigned long long *frames)
+{
+    if (c->spec_n_desc == 0)
+        return;
+    const int first = c->spec_level_begin[(size_t)lo], last = c->spec_level_begin[(size_t)hi + 1];
+    if (last <= first)
+        return;
+    SpecArgs A;
+    memset(&A, 0, sizeof A);
+    for (int l = 0; l < kMaxLevels; ++l)
+        A.frame_level[l] = frames ? frames[l] : f;
+    const float *hann = reinterpret_cast<const float *>(c->d_spec_tw + kSpecN);
+    hipLaunchKernelGGL(k_spectrum, dim3(last - first), dim3(kSpecThreads), 0, st, c->d_spec_desc + first, A, c->d_spec_tw, hann);
+}
+
+// The raw spectrum at sdrj's cadence: `if (count == 4) {emit fftData(samples); count = 0;} count++` once per frame, on the
+// frame as the parent-less VFOs get it -- queued first in the frame's own sequence, so that a caller's device frame or the
+// tile-layout copy of a DC-corrected one is read before anything else may overwrite it.
+void spectrum_raw_step(sdrx_ctx *c, const void *raw, int raw_mode)
+{
+    if (!c->spec_raw_on)
+        return;
+    const bool due = c->spec_raw_count == 4;
+    if (due)
+        c->spec_raw_count = 0;
+    c->spec_raw_count++;
+    if (!due)
+        return;
+    SpecArgs A;
+    memset(&A, 0, sizeof A);
+    A.raw = raw_mode == kRawTiled ? static_cast<const void *>(c->d_raw_tiled) : raw;
+    A.raw_mode = raw_mode;
+    const float *hann = reinterpret_cast<const float *>(c->d_spec_tw + kSpecN);
+    hipLaunchKernelGGL(k_spectrum, dim3(1), dim3(kSpecThreads), 0, c->stream, c->d_spec_desc + c->spec_n_desc, A, c->d_spec_tw, hann);
+}
 inline int pipeline_flush_unless(sdrx_ctx *c, bool keep) { return keep ? SDRX_OK : pipeline_flush(c); }
 void launch_block_kernel(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned long long frame, bool exact);
 
@@ -337,6 +395,7 @@ int enqueue_frame_as(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
     const bool pipe = c->opt_pipeline != 0;
     if (pipe && c->tail_recorded[p])
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_tail[p], 0));
+    spectrum_raw_step(c, raw, raw_mode);
     // A few parent-less VFOs (the reference's 2-3 mains) read the caller's frame as it is; a wide
     // level 0 (the flat workloads) is bandwidth bound and wants coalesced reads: one layout pass
     // natural order -> tile layout first.
@@ -384,6 +443,7 @@ int enqueue_frame_as(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
     }
     for (const LaunchB &L : c->lb)
         launch_block_kernel(c, L, ts, c->frame_no, EXACT);
+    spectrum_launch(c, ts, 0, c->n_levels - 1, c->frame_no, nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return fail(c, SDRX_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
@@ -492,6 +552,7 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
         else
             hipLaunchKernelGGL((k_mix_levels<false, true>), dim3(last - first), dim3(64), P.lds_bytes, c->stream, k1, items, item_level, list, A);
     }
+    spectrum_launch(c, c->stream, lo, hi, 0, A.frame_level);
     for (InFlight &q : c->pipe)
         q.next++;
     if (c->pipe.front().next >= n_levels) { // the oldest frame has passed its last level: its leaf tail, now
@@ -586,6 +647,14 @@ void free_device_state(sdrx_ctx *c)
     c->dc_work_stride = 0;
     dfree(c->d_dc_tab);
     c->raw_cap = 0;
+    for (auto &s : c->spec)
+        dfree(s.pwr);
+    c->spec.clear();
+    dfree(c->d_spec_rec);
+    dfree(c->d_spec_tw);
+    dfree(c->d_spec_desc);
+    c->spec_n_desc = 0;
+    c->spec_raw_on = false;
 }
 
 int ensure_raw(sdrx_ctx *c, size_t n_complex)
@@ -1516,12 +1585,75 @@ int sdrx_finalize(sdrx_ctx *c)
     return rc;
 }
 
+namespace {
+// The descriptors of the enabled spectra, uploaded whenever what they point at changes (sdrx_set_spectrum, the taps): the VFO
+// spectra whose stream exists -- where sdrx_get_stream finds it, by tree level -- then the raw one.  Synchronous: never inside
+// a frame call.
+int spectrum_rebuild(sdrx_ctx *c)
+{
+    if (c->spec.empty())
+        return SDRX_OK;
+    const int N = (int)c->nodes.size();
+    std::vector<SpecDesc> d;
+    c->spec_level_begin.assign((size_t)c->n_levels + 1, 0);
+    for (int lv = 0; lv < c->n_levels; ++lv) {
+        c->spec_level_begin[(size_t)lv] = (int)d.size();
+        for (int id = 0; id < N; ++id) {
+            const Node &n = c->nodes[(size_t)id];
+            const auto tap = c->taps.find(id);
+            if (n.level != lv || !c->spec[(size_t)id].on || (!n.has_stream && tap == c->taps.end()))
+                continue;
+            SpecDesc e;
+            memset(&e, 0, sizeof e);
+            for (int p = 0; p < 2; ++p) {
+                if (!n.has_stream)
+                    e.src[p] = tap->second.buf[p];
+                else if (n.leaf)
+                    e.src[p] = reinterpret_cast<const float2 *>(c->arena + n.off_stream[p]) + n.Hx;
+                else
+                    e.src[p] = reinterpret_cast<const float2 *>(c->arena + n.off_stream[p]);
+            }
+            e.kind = n.has_stream && !n.leaf ? kSpecTiled : kSpecNatural;
+            e.n_in = std::min(n.n_f, kSpecN);
+            e.level = std::min(lv, kMaxLevels - 1); // (only the frame pipeline, at most kMaxLevels deep, has frames per level)
+            e.pwr = c->spec[(size_t)id].pwr;
+            e.bins = reinterpret_cast<float2 *>(e.pwr + kSpecN);
+            e.rec = c->d_spec_rec + id;
+            d.push_back(e);
+        }
+    }
+    c->spec_level_begin[(size_t)c->n_levels] = (int)d.size();
+    c->spec_n_desc = (int)d.size();
+    c->spec_raw_on = c->spec[(size_t)N].on;
+    if (c->spec_raw_on) {
+        SpecDesc e;
+        memset(&e, 0, sizeof e);
+        e.kind = kSpecRaw;
+        e.n_in = std::min(c->root_frame, kSpecN);
+        e.pwr = c->spec[(size_t)N].pwr;
+        e.bins = reinterpret_cast<float2 *>(e.pwr + kSpecN);
+        e.rec = c->d_spec_rec + N;
+        d.push_back(e);
+    }
+    if (!d.empty())
+        HIPCHK(c, hipMemcpy(c->d_spec_desc, d.data(), sizeof(SpecDesc) * d.size(), hipMemcpyHostToDevice));
+    return SDRX_OK;
+}
+} // namespace
+
 // The reference's fftVFOSlot(topic) (vfo.cpp:492-509): from the next frame on, decimate[decimateCount] of node `id` is what
 // sdrx_get_stream serves.  Every VFO keeps that stream in HBM anyway -- except a leaf whose late decimation runs inside the
 // mix wave (it writes only the decimated stream): for such a leaf this call makes the wave keep decimate[0] as well.
 // sdrx_set_tap REPLACES the selection (id = -1: none), sdrx_add_tap adds to it: fftVFOSlot sets emitFFT on every VFO whose
 // topic equals the selected string, so two VFOs with one topic are two taps.
+static int tap_change_impl(sdrx_ctx *c, int id, bool replace, const char *what);
 static int tap_change(sdrx_ctx *c, int id, bool replace, const char *what)
+{
+    const int rc = tap_change_impl(c, id, replace, what);
+    const int rc2 = c && c->finalized ? spectrum_rebuild(c) : SDRX_OK; // a fused leaf's spectrum follows its tap buffer
+    return rc ? rc : rc2;
+}
+static int tap_change_impl(sdrx_ctx *c, int id, bool replace, const char *what)
 {
     if (!c)
         return SDRX_EINVAL;
@@ -2085,6 +2217,133 @@ int sdrx_get_stream(sdrx_ctx *c, int id, float *out, int max_complex, int *n_ret
     }
     if (n_ret)
         *n_ret = n.n_f;
+    return SDRX_OK;
+}
+
+int sdrx_set_spectrum(sdrx_ctx *c, int id, int enable)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_set_spectrum before sdrx_finalize");
+    const int N = (int)c->nodes.size();
+    if (id != SDRX_SPECTRUM_RAW && (id < 0 || id >= N))
+        return fail(c, SDRX_EINVAL, "sdrx_set_spectrum: bad vfo id %d", id);
+    if (c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "sdrx_set_spectrum: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c)) // frames inside the software pipeline finish under the spectra they were queued with
+        return rc;
+    const int slot = id < 0 ? N : id;
+    if (c->spec.empty()) { // the first spectrum: tables (the reference's own double expressions) and per-slot records
+        std::vector<float2> tab((size_t)kSpecN + kSpecN / 2);
+        const double pi = 3.141592653589793238462643383279502884197169399375105820974944; // kiss_fft.c:355-363
+        for (int i = 0; i < kSpecN; ++i) {
+            const double phase = -2 * pi * i / kSpecN;
+            tab[(size_t)i] = make_float2((float)cos(phase), (float)sin(phase));
+        }
+        float *hann = reinterpret_cast<float *>(tab.data() + kSpecN); // mainwindow.cpp:284-287
+        for (int i = 0; i < kSpecN; ++i)
+            hann[i] = (float)(0.5 * (1.0 - cos(2 * SDRX_PI * ((float)i) / (kSpecN - 1.0))));
+        HIPCHK(c, hipMalloc(&c->d_spec_tw, sizeof(float2) * tab.size()));
+        HIPCHK(c, hipMemcpy(c->d_spec_tw, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMalloc(&c->d_spec_rec, sizeof(SpecRecord) * (size_t)(N + 1)));
+        HIPCHK(c, hipMemsetAsync(c->d_spec_rec, 0, sizeof(SpecRecord) * (size_t)(N + 1), c->stream));
+        HIPCHK(c, hipMalloc(&c->d_spec_desc, sizeof(SpecDesc) * (size_t)(N + 1)));
+        c->spec.assign((size_t)N + 1, sdrx_ctx::SpecState());
+    }
+    sdrx_ctx::SpecState &S = c->spec[(size_t)slot];
+    if (enable) {
+        if (!S.pwr && hipMalloc(&S.pwr, (sizeof(double) + sizeof(float2)) * kSpecN) != hipSuccess) {
+            S.pwr = nullptr;
+            return fail(c, SDRX_ENOMEM, "sdrx_set_spectrum: no device memory for the spectrum of vfo %d", id);
+        }
+        // the combo-box reset (mainwindow.cpp:539-549): pwr and the window input zeroed, sdrj's count = 0
+        HIPCHK(c, hipMemsetAsync(S.pwr, 0, (sizeof(double) + sizeof(float2)) * kSpecN, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // (the context's streams do not synchronise with the null stream)
+        SpecRecord r;
+        memset(&r, 0, sizeof r);
+        r.n_in = std::min(id < 0 ? c->root_frame : c->nodes[(size_t)id].n_f, kSpecN);
+        HIPCHK(c, hipMemcpy(c->d_spec_rec + slot, &r, sizeof r, hipMemcpyHostToDevice));
+        S.on = true;
+        if (id < 0)
+            c->spec_raw_count = 0;
+    } else {
+        if (S.pwr)
+            (void)hipFree(S.pwr);
+        S.pwr = nullptr;
+        S.on = false;
+    }
+    return spectrum_rebuild(c);
+}
+
+static int spectrum_call(sdrx_ctx *c, const char *what, const int *ids, int n)
+{
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "%s before sdrx_finalize", what);
+    const int N = (int)c->nodes.size();
+    for (int k = 0; k < n; ++k) {
+        const int id = ids[k];
+        if (id != SDRX_SPECTRUM_RAW && (id < 0 || id >= N))
+            return fail(c, SDRX_EINVAL, "%s: bad vfo id %d", what, id);
+        if (c->spec.empty() || !c->spec[(size_t)(id < 0 ? N : id)].on)
+            return fail(c, SDRX_ESTATE, "%s: the spectrum of vfo %d is not enabled (sdrx_set_spectrum)", what, id);
+    }
+    if (c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "%s: %d submitted frame(s) not yet delivered -- call sdrx_wait first", what, c->in_flight);
+    HIPCHK(c, hipSetDevice(c->device));
+    return drain(c);
+}
+
+int sdrx_get_spectrum(sdrx_ctx *c, int id, sdrx_spectrum_info *info, double *pwr, double *smooth, float *bins_iq)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (int rc = spectrum_call(c, "sdrx_get_spectrum", &id, 1))
+        return rc;
+    const int slot = id < 0 ? (int)c->nodes.size() : id;
+    const double *d_pwr = c->spec[(size_t)slot].pwr;
+    if (info)
+        HIPCHK(c, hipMemcpy(info, c->d_spec_rec + slot, sizeof *info, hipMemcpyDeviceToHost));
+    if (bins_iq)
+        HIPCHK(c, hipMemcpy(bins_iq, d_pwr + kSpecN, sizeof(float2) * kSpecN, hipMemcpyDeviceToHost));
+    if (pwr || smooth) {
+        std::vector<double> tmp;
+        double *p = pwr;
+        if (!p) {
+            tmp.resize(kSpecN);
+            p = tmp.data();
+        }
+        HIPCHK(c, hipMemcpy(p, d_pwr, sizeof(double) * kSpecN, hipMemcpyDeviceToHost));
+        if (smooth) // mainwindow.cpp:454-458
+            for (int i = 0; i < kSpecN - 10; ++i)
+                smooth[i] = (p[i + 4] + p[i + 3] + p[i + 2] + p[i + 1] + p[i]) / 5;
+    }
+    return SDRX_OK;
+}
+
+int sdrx_get_spectrum_levels(sdrx_ctx *c, const int *ids, int n, double *maxval, double *aveval, int64_t *updates)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (n < 0 || (n > 0 && !ids))
+        return fail(c, SDRX_EINVAL, "sdrx_get_spectrum_levels: bad id list");
+    if (int rc = spectrum_call(c, "sdrx_get_spectrum_levels", ids, n))
+        return rc;
+    if (n == 0)
+        return SDRX_OK;
+    const int N = (int)c->nodes.size();
+    std::vector<SpecRecord> r((size_t)N + 1);
+    HIPCHK(c, hipMemcpy(r.data(), c->d_spec_rec, sizeof(SpecRecord) * r.size(), hipMemcpyDeviceToHost));
+    for (int k = 0; k < n; ++k) {
+        const SpecRecord &e = r[(size_t)(ids[k] < 0 ? N : ids[k])];
+        if (maxval)
+            maxval[k] = e.maxval;
+        if (aveval)
+            aveval[k] = e.aveval;
+        if (updates)
+            updates[k] = e.updates;
+    }
     return SDRX_OK;
 }
 

@@ -34,6 +34,9 @@ def arithmetic(exact) -> int:
     return 2 if (exact is not True and exact == 2) else int(bool(exact))
 
 
+SPECTRUM_RAW = _lib.SPECTRUM_RAW  # the raw frame's spectrum (sdrj's own fftData, every 4th frame)
+
+
 class Receiver:
     """One libsdrx context: a VFO tree on one GPU."""
 
@@ -255,6 +258,33 @@ class Receiver:
         out = np.zeros(2 * max(count, 1), np.float32)
         self._chk(self.L.sdrx_get_nco(self.h, vid, first, count, out.ctypes.data))
         return out[: 2 * count].view(np.complex64).copy()
+
+    # -- spectrum display (MainWindow::fftHandlerSlot on the device) ---------------------------------------------
+    def set_spectrum(self, vid: int, on: bool = True) -> None:
+        """Enable (and zero: the GUI's combo-box reset) or release the spectrum of VFO `vid`, or of the raw frame with
+        ``SPECTRUM_RAW``."""
+        self._chk(self.L.sdrx_set_spectrum(self.h, int(vid), int(bool(on))))
+
+    def spectrum(self, vid: int) -> dict:
+        """The display state after the last frame: ``pwr`` (8192 float64), ``smooth`` (8182), ``bins`` (the last update's
+        FFT output, complex64, natural order), ``maxval``, ``aveval``, ``updates``, ``n_in``."""
+        info = _lib.SpectrumInfoC()
+        pwr = np.zeros(_lib.SPECTRUM_BINS, np.float64)
+        smooth = np.zeros(_lib.SPECTRUM_BINS - 10, np.float64)
+        bins = np.zeros(2 * _lib.SPECTRUM_BINS, np.float32)
+        self._chk(self.L.sdrx_get_spectrum(self.h, int(vid), C.byref(info), pwr.ctypes.data, smooth.ctypes.data,
+                                           bins.ctypes.data))
+        return {"pwr": pwr, "smooth": smooth, "bins": bins.view(np.complex64), "maxval": info.maxval,
+                "aveval": info.aveval, "updates": info.updates, "n_in": info.n_in}
+
+    def spectrum_levels(self, vids) -> dict:
+        """maxval / aveval / updates of many spectra in one small copy: arrays in the order of `vids`."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        mx, av = np.zeros(ids.size, np.float64), np.zeros(ids.size, np.float64)
+        up = np.zeros(ids.size, np.int64)
+        self._chk(self.L.sdrx_get_spectrum_levels(self.h, ids.ctypes.data, ids.size, mx.ctypes.data, av.ctypes.data,
+                                                  up.ctypes.data))
+        return {"maxval": mx, "aveval": av, "updates": up}
 
     # -- measurement -----------------------------------------------------------------------
     def stats(self) -> dict:
