@@ -130,6 +130,13 @@ int sdrx_add_vfo(sdrx_ctx *ctx, const sdrx_vfo_desc *desc, int *id_out);
  *            0.091 tolerance: the frame is bound by VALU issue, not by HBM, and the demodulation's plain fp32 MACs issue in
  *            pairs only beside other waves doing the same (k_usb_demod: 80 % paired at 7 waves per SIMD) -- inside the mix
  *            wave, five waves per SIMD most of which are in packed-fp32 phases, they do not.  Off by default; an A/B switch.
+ *   "tail_in_levels" 1 (default) | 0: with "fuse" and "frame_pipeline", the USB demodulation of the frame that left the last
+ *            tree level runs inside the NEXT k_mix_levels launch (k_levels_tail: one launch per step instead of two) -- where
+ *            the planner finds it safe and faster: every demodulated leaf on the last tree level (frame parity of the leaf
+ *            streams), four mix waves' LDS fitting as many waves on a CU as before, and at most 64 demodulation blocks per CU
+ *            in the exact arithmetic, 16 in the others.  A frame is then complete one call later still;
+ *            sdrx_sync / sdrx_fetch / sdrx_get_* run what is outstanding as before.  0 = the demodulation in a k_usb_demod
+ *            launch behind the frame's last level (A/B switch).  Composes with "fuse_demod".  Results are bit-identical.
  *   "keep_streams" 0 (default) | 1: every such leaf also keeps decimate[d] of every frame (parity tests that
  *            compare every stream of the tree).
  *   "dc_blocked_scan" 0|1 (default 0): how sdrx_process_u8 removes the DC bias.  0 = the

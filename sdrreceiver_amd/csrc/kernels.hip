@@ -2479,6 +2479,53 @@ __global__ __launch_bounds__(64, kK1MinWaves) void k_mix_levels(const K1Vfo *__r
                     A.frame_level[lv], A.raw, A.raw_mode, lv == 0, smem, (int)threadIdx.x);
 }
 
+// ------------------------------------------------------------------------------------ k_levels_tail
+// k_mix_levels with the USB demodulation of the frame that left the last level in the PREVIOUS launch inside the same grid
+// (option tail_in_levels): one launch per step where k_mix_levels + k_usb_demod were two, and the second launch's ramp and
+// tail go.  Nothing in the grid depends on anything else in it: level l works on frame k - l, the demodulation
+// on frame k - n_levels, whose leaf streams (parity (k - n_levels) & 1) no item of this launch writes -- the planner fuses only
+// trees whose demodulated leaves all sit on the last level (sdrx.hip, build_level_plan).
+// Workgroups of 256 threads, each one of two things (TailWg):
+//   * four mix items, one per wave, every wave on LDS of its own (lds_wave bytes apart) -- exactly k_mix_levels' item body;
+//   * one demodulation block (demod_block, unchanged: same taps, same order, one accumulator per output) on all four waves.
+// Every part of the list starts at a multiple of 8 workgroups, and inside a part workgroup 8 b + x takes the items
+// 32 b + 8 w + x (w = wave): item j still runs on XCD j mod 8, as it does in k_mix_levels.
+struct TailWg {
+    int item[4]; // mix items of the four waves (-1: none); item[0] <= -2: demodulation block -2 - item[0] of the BlockWork list
+};
+struct LevelTailArgs {
+    LevelArgs L;
+    unsigned long long frame_tail; // frame the demodulation blocks work on
+    int active;                    // bit l: tree level l has a frame in this launch; bit kMaxLevels: the demodulation has one
+    int lds_wave;                  // LDS bytes of one mix wave
+};
+template <bool EXACT, bool ROT = !EXACT>
+__global__ __launch_bounds__(256, kK1MinWaves) void k_levels_tail(const K1Vfo *__restrict__ k1, const K1Work *__restrict__ items,
+                                                                  const int *__restrict__ item_level, const TailWg *__restrict__ wgs,
+                                                                  const K2Vfo *__restrict__ k2, const BlockWork *__restrict__ dwork,
+                                                                  LevelTailArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int first = ldc(&wgs[blockIdx.x].item[0]);
+    if (first <= -2) {
+        if (A.active & (1 << kMaxLevels)) {
+            const int b = -2 - first;
+            demod_block<EXACT>(k2, BlockWork{ldc(&dwork[b].vfo), ldc(&dwork[b].blk)}, A.frame_tail, *reinterpret_cast<DemodLds *>(smem),
+                               (int)threadIdx.x);
+        }
+        return;
+    }
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int it = ldc(&wgs[blockIdx.x].item[wave]);
+    if (it < 0)
+        return;
+    const int lv = ldc(item_level + it);
+    if (!((A.active >> lv) & 1)) // (a level without a frame: only while the pipeline drains)
+        return;
+    run_item<EXACT, ROT>(k1, K1Work{ldc(&items[it].vfo), ldc(&items[it].s_begin), ldc(&items[it].s_first_out), ldc(&items[it].s_end)},
+                         A.L.frame_level[lv], A.L.raw, A.L.raw_mode, lv == 0, smem + wave * A.lds_wave, (int)threadIdx.x & 63);
+}
+
 // An audio low-pass of more than kMaxFir taps (the reference accepts any filter_bandwidth: 500 Hz at
 // 48 kS/s is 925 taps, firfilter.cpp:108-119): usb'[m] = sum_{i<N} hu[i] usb[m-N+i], newest sample
 // excluded (FIR::FIRUpdateAndProcess, dsp.cpp:59-71), one accumulator per output in tap order, then the

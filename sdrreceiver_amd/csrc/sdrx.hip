@@ -102,8 +102,18 @@ struct LevelPlan {
     std::vector<int> part_begin, part_end;                   // list range of every level
     std::vector<int64_t> part_bytes;                         // SURVEY 8d share of every level
     int lds_bytes = 0;
+    // Option tail_in_levels: k_levels_tail's workgroup list [level n-1 | ... | level 0 | demodulation blocks], each part from a
+    // multiple of 8 workgroups (TailWg, kernels.hip); the demodulation of a frame then rides in the launch after the one that
+    // finished its last level.  tail = false: k_mix_levels, and k_usb_demod behind the launch that finished the frame.
+    bool tail = false;
+    size_t off_wgs = 0;
+    std::vector<int> wg_begin, wg_end; // workgroup range of every level
+    int dm_begin = 0, dm_end = 0;      // ... and of the demodulation blocks
+    int lds_wave = 0, tail_lds = 0;    // LDS of one mix wave; of a workgroup
+    int64_t dm_bytes = 0;              // SURVEY 8d share of the demodulation
 };
-struct InFlight { // a frame inside the software pipeline: `next` = the level that runs it in the next launch
+struct InFlight { // a frame inside the software pipeline: `next` = the level that runs it in the next launch (n_levels: its
+                  // demodulation, with LevelPlan::tail)
     unsigned long long f;
     int next;
 };
@@ -123,6 +133,7 @@ struct sdrx_ctx {
     bool finalized = false;
     int opt_exact = 1, opt_prequant = 0, opt_segments = 0, opt_dc_blocked = 0, opt_pipeline = 0, opt_dc_speculative = 1;
     int opt_fuse = 1, opt_frame_pipeline = 1, opt_fuse_late = 1, opt_keep_streams = 0, opt_fuse_demod = 0;
+    int opt_tail_in_levels = 1;
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first
     // frame that fills them.  The first such leaf uses the arena's buffer, further ones buffers of their own (hipMalloc).
@@ -517,6 +528,9 @@ void launch_block_kernel(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned
 // the tree level it has reached -- ONE k_mix_levels launch over the contiguous range of those levels --
 // and the frame that thereby leaves the last level gets its leaf tail (late decimation, demodulation,
 // compress) right behind that launch.
+// With LevelPlan::tail the demodulation of that frame is one more stage instead: it runs inside the NEXT step's launch
+// (k_levels_tail), its long audio low-pass (k_lpf_long) right behind that launch; the late decimation and compress stay
+// behind the launch that finished the frame's levels.
 int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
 {
     const LevelPlan &P = c->fp;
@@ -530,20 +544,27 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
     A.raw = raw;
     A.raw_mode = raw_mode;
     int lo = n_levels, hi = -1;
+    bool dm = false;             // the oldest frame is due for its demodulation (P.tail only)
+    unsigned long long f_dm = 0;
     for (const InFlight &q : c->pipe) {
+        if (q.next == n_levels) {
+            dm = true;
+            f_dm = q.f;
+            continue;
+        }
         lo = std::min(lo, q.next);
         hi = std::max(hi, q.next);
         A.frame_level[q.next] = q.f;
     }
-    const int first = std::min(P.part_begin[(size_t)lo], P.part_begin[(size_t)hi]), last = std::max(P.part_end[(size_t)lo], P.part_end[(size_t)hi]);
-    {
-        int64_t bytes = 0;
-        for (int j = lo; j <= hi; ++j)
-            bytes += P.part_bytes[(size_t)j];
+    const K1Vfo *k1 = reinterpret_cast<const K1Vfo *>(c->arena + c->off_k1vfo);
+    const K1Work *items = reinterpret_cast<const K1Work *>(c->arena + P.off_items);
+    const int *item_level = reinterpret_cast<const int *>(c->arena + P.off_item_level);
+    int64_t bytes = dm ? P.dm_bytes : 0;
+    for (int j = lo; j <= hi; ++j)
+        bytes += P.part_bytes[(size_t)j];
+    if (!P.tail) {
+        const int first = std::min(P.part_begin[(size_t)lo], P.part_begin[(size_t)hi]), last = std::max(P.part_end[(size_t)lo], P.part_end[(size_t)hi]);
         Bracket b(c, c->stream, lo != hi ? KIND_LEVELS : lo == 0 ? KIND_MIX_ROOT : KIND_MIX_SUB, bytes);
-        const K1Vfo *k1 = reinterpret_cast<const K1Vfo *>(c->arena + c->off_k1vfo);
-        const K1Work *items = reinterpret_cast<const K1Work *>(c->arena + P.off_items);
-        const int *item_level = reinterpret_cast<const int *>(c->arena + P.off_item_level);
         const int *list = reinterpret_cast<const int *>(c->arena + P.off_list) + first;
         if (c->opt_exact == 1)
             hipLaunchKernelGGL((k_mix_levels<true, false>), dim3(last - first), dim3(64), P.lds_bytes, c->stream, k1, items, item_level, list, A);
@@ -551,15 +572,48 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
             hipLaunchKernelGGL((k_mix_levels<false, false>), dim3(last - first), dim3(64), P.lds_bytes, c->stream, k1, items, item_level, list, A);
         else
             hipLaunchKernelGGL((k_mix_levels<false, true>), dim3(last - first), dim3(64), P.lds_bytes, c->stream, k1, items, item_level, list, A);
+    } else {
+        // the list is [level n-1 | ... | level 0 | demodulation]: the range runs from the deepest level with a frame to the
+        // demodulation (or to the shallowest level with a frame); levels inside it without a frame (the pipeline draining)
+        // are masked out by `active`
+        LevelTailArgs T;
+        memset(&T, 0, sizeof T);
+        T.L = A;
+        T.frame_tail = f_dm;
+        T.lds_wave = P.lds_wave;
+        T.active = dm ? 1 << kMaxLevels : 0;
+        for (int j = lo; j <= hi; ++j)
+            T.active |= 1 << j;
+        const int first = hi >= 0 ? P.wg_begin[(size_t)hi] : P.dm_begin, last = dm ? P.dm_end : P.wg_end[(size_t)lo];
+        Bracket b(c, c->stream, hi < 0 || lo != hi || dm ? KIND_LEVELS : lo == 0 ? KIND_MIX_ROOT : KIND_MIX_SUB, bytes);
+        const TailWg *wgs = reinterpret_cast<const TailWg *>(c->arena + P.off_wgs) + first;
+        const LaunchB &D = *std::find_if(c->lb.begin(), c->lb.end(), [](const LaunchB &L) { return L.kind == KIND_DEMOD; });
+        const K2Vfo *k2 = reinterpret_cast<const K2Vfo *>(c->arena + D.off_desc);
+        const BlockWork *dwork = reinterpret_cast<const BlockWork *>(c->arena + D.off_work);
+        if (c->opt_exact == 1)
+            hipLaunchKernelGGL((k_levels_tail<true, false>), dim3(last - first), dim3(256), P.tail_lds, c->stream, k1, items, item_level, wgs, k2, dwork, T);
+        else if (c->opt_exact == 2)
+            hipLaunchKernelGGL((k_levels_tail<false, false>), dim3(last - first), dim3(256), P.tail_lds, c->stream, k1, items, item_level, wgs, k2, dwork, T);
+        else
+            hipLaunchKernelGGL((k_levels_tail<false, true>), dim3(last - first), dim3(256), P.tail_lds, c->stream, k1, items, item_level, wgs, k2, dwork, T);
     }
-    spectrum_launch(c, c->stream, lo, hi, 0, A.frame_level);
+    if (dm)
+        for (const LaunchB &L : c->lb)
+            if (L.kind == KIND_LPF_LONG)
+                launch_block_kernel(c, L, c->stream, f_dm, c->opt_exact == 1);
+    if (hi >= 0)
+        spectrum_launch(c, c->stream, lo, hi, 0, A.frame_level);
+    if (dm)
+        c->pipe.erase(c->pipe.begin());
     for (InFlight &q : c->pipe)
         q.next++;
-    if (c->pipe.front().next >= n_levels) { // the oldest frame has passed its last level: its leaf tail, now
+    if (!c->pipe.empty() && c->pipe.front().next == n_levels) { // the oldest frame has passed its last level: its leaf tail, now
         const unsigned long long f = c->pipe.front().f;
         for (const LaunchB &L : c->lb)
-            launch_block_kernel(c, L, c->stream, f, c->opt_exact == 1);
-        c->pipe.erase(c->pipe.begin());
+            if (!P.tail || (L.kind != KIND_DEMOD && L.kind != KIND_LPF_LONG))
+                launch_block_kernel(c, L, c->stream, f, c->opt_exact == 1);
+        if (!P.tail)
+            c->pipe.erase(c->pipe.begin());
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
@@ -796,6 +850,8 @@ int sdrx_set_option(sdrx_ctx *c, const char *name, int value)
         c->opt_keep_streams = value != 0;
     else if (!strcmp(name, "fuse_demod"))
         c->opt_fuse_demod = value != 0;
+    else if (!strcmp(name, "tail_in_levels"))
+        c->opt_tail_in_levels = value != 0;
     else
         return fail(c, SDRX_EINVAL, "unknown option '%s'", name);
     return SDRX_OK;
@@ -899,6 +955,7 @@ struct Built { // host copies of what goes to the arena, and where
     size_t o2a = 0, o2 = 0, o3 = 0, o4 = 0, ow2a = 0, ow2 = 0, ow3 = 0, ow4 = 0;
     std::vector<K1Work> all_items; // k_mix_levels: every level's items in one array ...
     std::vector<int> all_item_level, llist; // ... their levels, and the launch list over them
+    std::vector<TailWg> tail_wgs;           // k_levels_tail's workgroup list (LevelPlan::tail)
     size_t off_nco_jobs = 0;
 
     size_t place_taps(const std::vector<float> &t)
@@ -1101,6 +1158,14 @@ void plan_buffers(sdrx_ctx *c, Built &B)
         c->off_tapbuf[p] = tap_len ? plan.take(sizeof(float2) * tap_len) : 0;
 }
 
+int cu_count(const sdrx_ctx *c)
+{
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0)
+        return prop.multiProcessorCount;
+    return 256;
+}
+
 // ---- work lists for the mix/decimate launches, one launch per tree level
 // A work item is one wave walking a run of chunks of one VFO-frame (+ a warm-up when it starts mid-frame).  Measured on
 // config 3 (profiles/README.md): the same NUMBER of segments for every VFO of a level, 32 work items per CU in total, in
@@ -1117,12 +1182,7 @@ int build_mix_work(sdrx_ctx *c, Built &B)
         B.level_count[(size_t)n.level]++;
         B.level_maxd[(size_t)n.level] = std::max(B.level_maxd[(size_t)n.level], n.d.decimate_count);
     }
-    int ncu = 256;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0)
-            ncu = prop.multiProcessorCount;
-    }
+    const int ncu = cu_count(c);
     std::vector<int> level_nseg((size_t)c->n_levels, 1);
     constexpr int kItemsPerCu = 32;  // work items per CU a level is cut into (= the hardware's wave slots per CU)
     constexpr int kMinSegChunks = 4; // the fewest chunks of useful work a segment of a many-VFO level may have
@@ -1359,6 +1419,71 @@ void build_level_plan(sdrx_ctx *c, Built &B)
     P.off_items = B.plan.take(sizeof(K1Work) * B.all_items.size());
     P.off_item_level = B.plan.take(sizeof(int) * B.all_item_level.size());
     P.off_list = B.plan.take(sizeof(int) * B.llist.size());
+
+    // Option tail_in_levels: the demodulation of frame k - n_levels inside the launch of frame k (k_levels_tail).  A leaf at
+    // level l writes frame f in launch f + l and frame f + 2 -- the same parity buffer -- in launch f + l + 2; the demodulation
+    // of f reads it in launch f + n_levels, so l + 2 > n_levels: every leaf that k_usb_demod serves must sit on the last
+    // level (the reference's trees: the sub VFOs).  Its history prefix goes to the other parity's buffer, of which the same
+    // launch writes only the data part (frame f + 1 on the last level).  A late decimation left to k_late_decimate writes
+    // the demodulation's input behind the launch that finished the frame (next writer: frame f + 2, behind launch
+    // f + n_levels + 1); compress reads its streams there too, as without the option.  Leaves that demodulate in their mix
+    // wave (fuse_demod) have no blocks here.  One-level trees have no k_mix_levels launch to ride in (see above).
+    const auto dm_launch = std::find_if(c->lb.begin(), c->lb.end(), [](const LaunchB &L) { return L.kind == KIND_DEMOD; });
+    bool tail = c->opt_tail_in_levels && dm_launch != c->lb.end();
+    for (const Node &n : c->nodes)
+        if (n.leaf && n.d.demod_usb && !n.fused_demod && n.level != c->n_levels - 1)
+            tail = false;
+    // LDS: four mix waves or one demodulation block per workgroup.  Where four waves' LDS would fit fewer mix waves on a CU
+    // than k_mix_levels does (the fused /5 and /6 leaves: 9 KB a wave), the two-launch form stays.
+    constexpr int kLdsPerCu = 160 * 1024;
+    const int lds_wave = (int)align_up((size_t)P.lds_bytes, 16);
+    const int tail_lds = std::max(4 * lds_wave, (int)sizeof(DemodLds));
+    if (4 * (kLdsPerCu / tail_lds) < std::min(4 * kK1MinWaves, kLdsPerCu / std::max(1, lds_wave)))
+        tail = false;
+    // What the fusion buys is fixed per frame (the second launch's ramp and tail, ~6 us); what it costs grows with the
+    // demodulation blocks (they run at the mix code's 96 registers, 5 waves per SIMD, instead of k_usb_demod's 7 -- or 9 in the
+    // packed arithmetics, which lose more).  Measured: config 4 (13 blocks per CU) gains in every arithmetic,
+    // config 3 (31 per CU) gains in the exact one and breaks even in the others, 10 240 subs (310 per CU) loses in all.
+    const int dm_per_cu_max = c->opt_exact == 1 ? 64 : 16;
+    if ((long long)B.w2.size() > (long long)dm_per_cu_max * cu_count(c))
+        tail = false;
+    if (!tail)
+        return;
+    P.tail = true;
+    P.lds_wave = lds_wave;
+    P.tail_lds = tail_lds;
+    P.dm_bytes = dm_launch->alg_bytes;
+    P.wg_begin.assign((size_t)c->n_levels, 0);
+    P.wg_end.assign((size_t)c->n_levels, 0);
+    const TailWg none = {{-1, -1, -1, -1}};
+    for (int q = 0; q < c->n_levels; ++q) {
+        const int lv = c->n_levels - 1 - q;
+        while (B.tail_wgs.size() % 8)
+            B.tail_wgs.push_back(none);
+        P.wg_begin[(size_t)lv] = (int)B.tail_wgs.size();
+        const int b0 = P.part_begin[(size_t)lv], cnt = P.part_end[(size_t)lv] - b0;
+        // workgroup 8 b + x of the part takes the items 32 b + 8 w + x (w = its wave): item j on XCD j mod 8, as in k_mix_levels
+        for (int blk = 0; 32 * blk < cnt; ++blk)
+            for (int x = 0; x < 8; ++x) {
+                TailWg g = none;
+                for (int w = 0; w < 4; ++w) {
+                    const int j = 32 * blk + 8 * w + x;
+                    g.item[w] = j < cnt ? B.llist[(size_t)(b0 + j)] : -1;
+                }
+                B.tail_wgs.push_back(g);
+            }
+        while ((int)B.tail_wgs.size() > P.wg_begin[(size_t)lv] && B.tail_wgs.back().item[0] < 0) // (no empty workgroups at the end)
+            B.tail_wgs.pop_back();
+        P.wg_end[(size_t)lv] = (int)B.tail_wgs.size();
+    }
+    // the demodulation blocks behind the mix items, longest first (build_tail_work sorted them): they fill the mix tail
+    while (B.tail_wgs.size() % 8)
+        B.tail_wgs.push_back(none);
+    P.dm_begin = (int)B.tail_wgs.size();
+    for (size_t i = 0; i < B.w2.size(); ++i)
+        B.tail_wgs.push_back(TailWg{{-2 - (int)i, -1, -1, -1}});
+    P.dm_end = (int)B.tail_wgs.size();
+    P.off_wgs = B.plan.take(sizeof(TailWg) * B.tail_wgs.size());
 }
 
 // ---- allocate, zero (= the reference's zero-initialised filter state, dsp.cpp:40-49), fill the descriptors, build the NCO tables
@@ -1511,6 +1636,8 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
         HIPCHK(c, up(c->fp.off_items, B.all_items.data(), sizeof(K1Work) * B.all_items.size()));
         HIPCHK(c, up(c->fp.off_item_level, B.all_item_level.data(), sizeof(int) * B.all_item_level.size()));
         HIPCHK(c, up(c->fp.off_list, B.llist.data(), sizeof(int) * B.llist.size()));
+        if (c->fp.tail)
+            HIPCHK(c, up(c->fp.off_wgs, B.tail_wgs.data(), sizeof(TailWg) * B.tail_wgs.size()));
     }
     for (auto &kv : B.tap_offsets)
         HIPCHK(c, up(kv.second, kv.first.data(), kv.first.size() * sizeof(float)));
