@@ -267,6 +267,24 @@ int sdrx_get_taps(sdrx_ctx *ctx, int id, int which, float *out, int max, int *n)
 /* NCO table entries [first, first+count) of node `id` as the device generated them. */
 int sdrx_get_nco(sdrx_ctx *ctx, int id, long first, long count, float *out_iq);
 
+/* ---- retuning a running tree ---------------------------------------------------------------------------------
+ * sdrx_set_mixer_freqs: VFO ids[k] gets the mixer frequency mixer_freq_hz[k] (vfo::setMixerFreq) from the next frame
+ * submitted on.  A retune is the reference's own primitive between two frames, `delete osc_mix; osc_mix = new
+ * Oscillator(Fs, f)`: the NCO restarts as a fresh oscillator does (sample 0 of that frame takes the new table's entry L-1,
+ * then entries 1, 2, ...: oscillator.cpp:20-50), and everything else is carried over -- half-band histories, the late
+ * decimation's FIR, delay line, Hilbert and audio low-pass, the children (they receive the new stream) and an enabled
+ * spectrum's state.  sdrx_get_nco reports the new table.  Used for a dongle's drift: a change of mix_offset by D moves the
+ * mixer of every sub VFO by -D (mainwindow.cpp:141-225).
+ * sdrx_set_gains: vfo::setGain between two vfo::process calls (the reference reads `gain` on every sample, vfo.cpp:328,364):
+ * from the next frame on.  The gain of a VFO that does not demodulate USB is stored and has no effect, as in the reference.
+ * Both are batched (the drift case retunes thousands of VFOs) and atomic: the whole list is checked first, and a bad or
+ * duplicate id, a value that is not finite or n < 0 is SDRX_EINVAL with nothing changed; n == 0 does nothing.  SDRX_ESTATE
+ * before sdrx_finalize and while submitted frames are undelivered (as sdrx_set_tap); frames the software pipeline of
+ * sdrx_process_device still holds run to their end with the old values first.  One small upload and one launch per call; the
+ * call returns when the device has applied it (a retune replays the new table once: a serial chain of Fs steps). */
+int sdrx_set_mixer_freqs(sdrx_ctx *ctx, const int *ids, const double *mixer_freq_hz, int n);
+int sdrx_set_gains(sdrx_ctx *ctx, const int *ids, const float *gains, int n);
+
 /* ---- spectrum display ( = MainWindow::fftHandlerSlot, mainwindow.cpp:411-478, on the device) -------------------
  * One display state per enabled spectrum: VFO `id` (its decimate[decimateCount], what vfo.cpp:290-293 emits as fftData)
  * or SDRX_SPECTRUM_RAW (the raw frame exactly as sdrx_get_raw would return it -- for sdrx_process_device /
@@ -352,6 +370,10 @@ int sdrx_group_get_output(sdrx_group *grp, int id, const void **buf, uint32_t *l
  * timing. */
 int sdrx_group_locate(sdrx_group *grp, int id, int *member, int *local_id);
 int sdrx_group_member(sdrx_group *grp, int k, sdrx_ctx **ctx, int *device_ordinal);
+/* sdrx_set_mixer_freqs / sdrx_set_gains with ids of the whole tree: applied on every member that holds the VFO (a VFO with
+ * children is replicated on each member that holds part of its subtree); a member with nothing listed makes no launch. */
+int sdrx_group_set_mixer_freqs(sdrx_group *grp, const int *ids, const double *mixer_freq_hz, int n);
+int sdrx_group_set_gains(sdrx_group *grp, const int *ids, const float *gains, int n);
 
 /* ---- introspection / measurement ------------------------------------------------------------- */
 typedef struct sdrx_stats {

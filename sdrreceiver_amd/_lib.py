@@ -84,6 +84,8 @@ SYMBOLS = {
     "sdrx_get_prequant": (_i, [_vp, _i, _vp, _i, C.POINTER(_i)]),
     "sdrx_get_taps": (_i, [_vp, _i, _i, _vp, _i, C.POINTER(_i)]),
     "sdrx_get_nco": (_i, [_vp, _i, C.c_long, C.c_long, _vp]),
+    "sdrx_set_mixer_freqs": (_i, [_vp, _vp, _vp, _i]),
+    "sdrx_set_gains": (_i, [_vp, _vp, _vp, _i]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
@@ -112,6 +114,8 @@ SYMBOLS = {
     "sdrx_group_get_output": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "sdrx_group_locate": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i)]),
     "sdrx_group_member": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
+    "sdrx_group_set_mixer_freqs": (_i, [_vp, _vp, _vp, _i]),
+    "sdrx_group_set_gains": (_i, [_vp, _vp, _vp, _i]),
     "sdrx_get_stats": (_i, [_vp, C.POINTER(StatsC)]),
     "sdrx_enable_kernel_timing": (_i, [_vp, _i]),
     "sdrx_get_kernel_times": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -29,9 +29,9 @@ namespace sdrx {
 // all point into HBM: these helpers say so, so that accesses become global_load/global_store
 // (or s_load for wave-uniform read-only data) instead of flat_* instructions.
 #define SDRX_AS1 __attribute__((address_space(1)))
-// Descriptors, work lists and filter taps are written once at sdrx_finalize and never by a kernel:
-// reading them through the CONSTANT address space tells the compiler so (no store of the kernel can
-// alias them), and a wave-uniform address then becomes a scalar load into SGPRs whatever else the
+// Descriptors, work lists and filter taps are written at sdrx_finalize and never by a kernel that reads them
+// (k_vfo_retune patches NCO fields and gains between frames, in a launch of its own): reading them through the
+// CONSTANT address space tells the compiler so (no store of the kernel can alias them), and a wave-uniform address then becomes a scalar load into SGPRs whatever else the
 // kernel does.  (Without it the 62 Hilbert taps of the demodulation turn into 62 VGPRs -- and spill --
 // as soon as the same kernel also contains the mix/decimate code: k_frame.)
 #define SDRX_AS4 __attribute__((address_space(4)))
@@ -256,21 +256,49 @@ __device__ __forceinline__ void nco_mix_fast16(v2f c, const float2 *__restrict__
 
 // Replays the whole table once per VFO and keeps every 16th entry: cp[j] = table[16j-1]
 // (cp[0] = the initial (1,0)), so any aligned run of 16 entries can be regenerated in
-// registers, bit-exact by construction.  One thread per VFO; init-time only.
+// registers, bit-exact by construction.
+__device__ __forceinline__ void nco_fill(float2 *__restrict__ cp, float rot_re, float rot_im, int L)
+{
+    float2 v = make_float2(1.0f, 0.0f);
+    cp[0] = v;
+    for (int k = 0; k < L; k += kRun) {
+#pragma unroll
+        for (int t = 0; t < kRun; ++t)
+            v = nco_step(v, rot_re, rot_im);
+        cp[(k >> 4) + 1] = v;
+    }
+}
+// One thread per VFO, at finalize.
 __global__ void k_nco_init(const NcoInit *__restrict__ jobs, int n)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
         return;
-    NcoInit J = jobs[i];
-    float2 v = make_float2(1.0f, 0.0f);
-    J.cp[0] = v;
-    for (int k = 0; k < J.L; k += kRun) {
-#pragma unroll
-        for (int t = 0; t < kRun; ++t)
-            v = nco_step(v, J.rot_re, J.rot_im);
-        J.cp[(k >> 4) + 1] = v;
+    const NcoInit J = jobs[i];
+    nco_fill(J.cp, J.rot_re, J.rot_im, J.L);
+}
+
+// sdrx_set_mixer_freqs / sdrx_set_gains between two frames: one thread per job.  A retune is `delete osc_mix; osc_mix = new
+// Oscillator(Fs, f)` (the checkpoints regenerated in place by the same recurrence as k_nco_init, exact in every arithmetic)
+// plus the new rotation and the frame the oscillator starts at; a gain job patches one float of a demodulation descriptor.
+// The host drained the context first: no launch reads these records while this one runs.
+__global__ void k_vfo_retune(const RetuneJob *__restrict__ jobs, int n)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const RetuneJob J = jobs[i];
+    if (J.kind == kJobGain) {
+        *J.gain = J.value;
+        return;
     }
+    K1Vfo *v = J.vfo;
+    nco_fill(const_cast<float2 *>(v->cp), J.rot_re, J.rot_im, v->L);
+    v->rot_re = J.rot_re;
+    v->rot_im = J.rot_im;
+    for (int t = 0; t < 4; ++t)
+        v->rk[t] = J.rk[t];
+    v->origin = J.origin;
 }
 
 // Debug/parity helper: regenerate table[first .. first+count) from the checkpoints.
@@ -1540,7 +1568,8 @@ __device__ __forceinline__ void mix_item(const K1Vfo *__restrict__ vfos, const K
     DemodCtx dmc;
     if constexpr (DM)
         demod_prologue(dm, ldc(&Dp->dm), par, from_state, lane, dmc);
-    const int phase_frame = (int)((frame_no * (unsigned long long)D.n_in) % (unsigned long long)D.L);
+    const unsigned long long origin = ldc(&Dp->origin); // (frame_no >= origin: set between frames)
+    const int phase_frame = (int)(((frame_no - origin) * (unsigned long long)D.n_in) % (unsigned long long)D.L);
 
     // The item walks 1024-sample chunks from sample s_begin (any multiple of 16: a chunk need not
     // coincide with a tile of the input) and emits the outputs whose input position is >= s_first_out.
@@ -1620,7 +1649,7 @@ __device__ __forceinline__ void mix_item(const K1Vfo *__restrict__ vfos, const K
         {
             int i0 = phase_frame + base;
             i0 -= i0 >= D.L ? D.L : 0;
-            nco_mix<EXACT, ROT>(o, rot, Dp->rk, D.cp + (D.L >> 4), frame_no == 0 && base == 0 && lane == 0, i0, kChunk, D.L, x);
+            nco_mix<EXACT, ROT>(o, rot, Dp->rk, D.cp + (D.L >> 4), frame_no == origin && base == 0 && lane == 0, i0, kChunk, D.L, x);
         }
 
         if (dd == 0) {
@@ -1809,7 +1838,8 @@ __device__ __forceinline__ void late_item(const K1Vfo *__restrict__ vfos, const 
     const int wr_lo = (G::kCarryRows + q0) * kStride + r0;
     int wr_T = kRow - r0;
     const v2f *rd = buf + lane * kStride; // window sample u of this lane: rd[(kCarryRows + floor(u / kRow)) * kStride + u mod kRow]
-    const int phase_frame = (int)((frame_no * (unsigned long long)D.n_in) % (unsigned long long)D.L);
+    const unsigned long long origin = ldc(&Dp->origin); // (frame_no >= origin: set between frames)
+    const int phase_frame = (int)(((frame_no - origin) * (unsigned long long)D.n_in) % (unsigned long long)D.L);
     // As in mix_item: the checkpoint the whole NCO hangs on is requested a chunk ahead (always issued: a load the compiler can
     // count).  (Holding the chunk's outputs back behind the next chunk's loads, as mix_item's shaped bodies do, measured
     // +2 % on config 4 here -- the parking in the window rows' padding and the three buffer stores cost more than the
@@ -1838,7 +1868,7 @@ __device__ __forceinline__ void late_item(const K1Vfo *__restrict__ vfos, const 
             int i0 = phase_frame + base;
             i0 -= i0 >= D.L ? D.L : 0;
             // (kChunk, not kChunkLen: the lanes past the chunk replay entries nobody uses -- up to 64 x 16 of them must not wrap either)
-            nco_mix<EXACT, ROT>(o, rot, Dp->rk, D.cp + (D.L >> 4), frame_no == 0 && base == 0 && lane == 0, i0, kChunk, D.L, x);
+            nco_mix<EXACT, ROT>(o, rot, Dp->rk, D.cp + (D.L >> 4), frame_no == origin && base == 0 && lane == 0, i0, kChunk, D.L, x);
         }
         if (tap && lane < G::kMixLanes && 16 * lane < valid && base + 16 * lane >= W.s_first_out) {
             // decimate[0] is wanted (the GUI's spectrum tap, parity tests)

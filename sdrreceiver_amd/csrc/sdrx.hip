@@ -74,6 +74,7 @@ struct Node {
     bool fused_demod = false; // the USB demodulation runs inside the mix wave (demod_chunk): the leaf writes its payload itself
     size_t off_dstate[2] = {0, 0}; //   ... its demodulation history per frame parity (kDemodStateFloats floats)
     int d2_index = -1;      // its K2Vfo in the demodulation descriptor array
+    int d4_index = -1;      // its K4Vfo (long_lpf): k_lpf_long applies the gain
     bool has_stream = true; // decimate[d] of every frame is kept in HBM (false: a fused late decimation writes only z', a fused demodulation only the payload)
 };
 
@@ -200,6 +201,9 @@ struct sdrx_ctx {
     size_t raw_cap = 0;
     int root_frame = 0; // samples_per_buffer of the parent-less VFOs
     size_t off_k1vfo = 0;
+    size_t off_k2 = 0, off_k4 = 0; // the K2Vfo / K4Vfo arrays (sdrx_set_gains patches their gain)
+    RetuneJob *d_jobs = nullptr;   // k_vfo_retune's job list (sdrx_set_mixer_freqs, sdrx_set_gains), grown on demand
+    size_t jobs_cap = 0;
     std::vector<Launch1> l1;
     std::vector<LaunchB> lb;
     std::vector<int> publish_order;
@@ -707,6 +711,8 @@ void free_device_state(sdrx_ctx *c)
     dfree(c->d_spec_rec);
     dfree(c->d_spec_tw);
     dfree(c->d_spec_desc);
+    dfree(c->d_jobs);
+    c->jobs_cap = 0;
     c->spec_n_desc = 0;
     c->spec_raw_on = false;
 }
@@ -1331,6 +1337,7 @@ void build_tail_work(sdrx_ctx *c, Built &B)
             if (n.long_lpf) {
                 for (int b = 0; b < (n.n_out + 255) / 256; ++b)
                     B.w4.push_back({(int)B.d4.size(), b});
+                n.d4_index = (int)B.d4.size();
                 B.n4.push_back(i);
                 B.d4.push_back(K4Vfo{});
             }
@@ -1362,6 +1369,7 @@ void build_tail_work(sdrx_ctx *c, Built &B)
     }
     if (!B.d2.empty()) {
         B.o2 = plan.take(sizeof(K2Vfo) * B.d2.size());
+        c->off_k2 = B.o2;
         B.ow2 = plan.take(sizeof(BlockWork) * std::max<size_t>(1, B.w2.size()));
         if (!B.w2.empty()) // (every USB leaf may demodulate in its own mix wave: no k_usb_demod launch at all then)
             c->lb.push_back({KIND_DEMOD, (int)B.w2.size(), B.o2, B.ow2, 0, b2});
@@ -1371,6 +1379,7 @@ void build_tail_work(sdrx_ctx *c, Built &B)
         for (int i : B.n4)
             lds4 = std::max(lds4, (int)sizeof(float) * ((int)c->nodes[(size_t)i].lpf.size() + 256));
         B.o4 = plan.take(sizeof(K4Vfo) * B.d4.size());
+        c->off_k4 = B.o4;
         B.ow4 = plan.take(sizeof(BlockWork) * B.w4.size());
         c->lb.push_back({KIND_LPF_LONG, (int)B.w4.size(), B.o4, B.ow4, lds4, 0});
     }
@@ -1487,6 +1496,15 @@ void build_level_plan(sdrx_ctx *c, Built &B)
 }
 
 // ---- allocate, zero (= the reference's zero-initialised filter state, dsp.cpp:40-49), fill the descriptors, build the NCO tables
+// the tolerance arithmetic's NCO: 1 .. 4 steps of the recurrence as ONE rotation (the stabiliser holds |v|, so a step is the
+// rotation by arg(rot) at unit modulus: oscillator.cpp:20-28), in double, stored as floats
+void nco_powers(float rot_re, float rot_im, float2 rk[4])
+{
+    const double ang = std::atan2((double)rot_im, (double)rot_re);
+    for (int t = 0; t < 4; ++t)
+        rk[t] = make_float2((float)std::cos(ang * (t + 1)), (float)std::sin(ang * (t + 1)));
+}
+
 int allocate_and_upload(sdrx_ctx *c, Built &B)
 {
     const int N = (int)c->nodes.size();
@@ -1535,13 +1553,7 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
         k.cp = reinterpret_cast<const float2 *>(P(n.off_cp));
         k.rot_re = n.rot_re;
         k.rot_im = n.rot_im;
-        {
-            // the tolerance arithmetic's NCO: 1 .. 4 steps of the recurrence as ONE rotation (the stabiliser holds |v|, so a
-            // step is the rotation by arg(rot) at unit modulus: oscillator.cpp:20-28), in double, stored as floats
-            const double ang = std::atan2((double)n.rot_im, (double)n.rot_re);
-            for (int t = 0; t < 4; ++t)
-                k.rk[t] = make_float2((float)std::cos(ang * (t + 1)), (float)std::sin(ang * (t + 1)));
-        }
+        nco_powers(n.rot_re, n.rot_im, k.rk);
         k.n_in = n.d.samples_per_buffer;
         k.d = n.d.decimate_count;
         k.L = n.d.fs;
@@ -1836,6 +1848,130 @@ static int tap_change_impl(sdrx_ctx *c, int id, bool replace, const char *what)
 
 int sdrx_set_tap(sdrx_ctx *c, int id) { return tap_change(c, id, true, "sdrx_set_tap"); }
 int sdrx_add_tap(sdrx_ctx *c, int id) { return tap_change(c, id, false, "sdrx_add_tap"); }
+
+} // extern "C"
+
+namespace {
+
+// The checks of sdrx_set_mixer_freqs / sdrx_set_gains (and their group forms): the whole list before anything changes.
+// Returns SDRX_OK or SDRX_EINVAL with the reason in `msg`.
+int check_vfo_list(int n_nodes, const int *ids, const void *vals, bool dbl, int n, std::string &msg)
+{
+    char buf[160];
+    if (n < 0 || (n > 0 && (!ids || !vals))) {
+        snprintf(buf, sizeof buf, "bad list (n = %d)", n);
+        msg = buf;
+        return SDRX_EINVAL;
+    }
+    std::vector<char> seen((size_t)n_nodes, 0);
+    for (int k = 0; k < n; ++k) {
+        const int id = ids[k];
+        const double v = dbl ? static_cast<const double *>(vals)[k] : (double)static_cast<const float *>(vals)[k];
+        buf[0] = 0;
+        if (id < 0 || id >= n_nodes)
+            snprintf(buf, sizeof buf, "bad vfo id %d (entry %d)", id, k);
+        else if (seen[(size_t)id]++)
+            snprintf(buf, sizeof buf, "vfo %d listed twice", id);
+        else if (!std::isfinite(v))
+            snprintf(buf, sizeof buf, "vfo %d: value is not finite", id);
+        if (buf[0]) {
+            msg = buf;
+            return SDRX_EINVAL;
+        }
+    }
+    return SDRX_OK;
+}
+
+// Applies a checked list: drain the software pipeline (frames queued earlier finish with the old values), then one upload of
+// the job list and one k_vfo_retune launch.  The host copies of every node follow.
+int apply_vfo_jobs(sdrx_ctx *c, const int *ids, const double *freqs, const float *gains, int n)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c))
+        return rc;
+    std::vector<RetuneJob> jobs;
+    jobs.reserve((size_t)n * 2);
+    K1Vfo *k1 = reinterpret_cast<K1Vfo *>(c->arena + c->off_k1vfo);
+    for (int k = 0; k < n; ++k) {
+        const Node &nd = c->nodes[(size_t)ids[k]];
+        RetuneJob J;
+        memset(&J, 0, sizeof J);
+        if (freqs) {
+            J.kind = kJobRetune;
+            J.vfo = k1 + ids[k];
+            nco_rotation((double)nd.d.fs, freqs[k], J.rot_re, J.rot_im);
+            nco_powers(J.rot_re, J.rot_im, J.rk);
+            J.origin = c->frame_no;
+            jobs.push_back(J);
+            continue;
+        }
+        J.kind = kJobGain;
+        J.value = gains[k];
+        if (nd.d2_index >= 0) {
+            J.gain = &(reinterpret_cast<K2Vfo *>(c->arena + c->off_k2) + nd.d2_index)->gain;
+            jobs.push_back(J);
+        }
+        if (nd.d4_index >= 0) {
+            J.gain = &(reinterpret_cast<K4Vfo *>(c->arena + c->off_k4) + nd.d4_index)->gain;
+            jobs.push_back(J);
+        }
+    }
+    if (!jobs.empty()) {
+        if (jobs.size() > c->jobs_cap) {
+            if (c->d_jobs)
+                (void)hipFree(c->d_jobs);
+            c->d_jobs = nullptr;
+            c->jobs_cap = 0;
+            HIPCHK(c, hipMalloc(&c->d_jobs, sizeof(RetuneJob) * jobs.size()));
+            c->jobs_cap = jobs.size();
+        }
+        HIPCHK(c, hipMemcpyAsync(c->d_jobs, jobs.data(), sizeof(RetuneJob) * jobs.size(), hipMemcpyHostToDevice, c->stream));
+        const int nj = (int)jobs.size();
+        hipLaunchKernelGGL(k_vfo_retune, dim3((nj + 63) / 64), dim3(64), 0, c->stream, c->d_jobs, nj);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // (`jobs` lives on this stack)
+    }
+    for (int k = 0; k < n; ++k) {
+        Node &nd = c->nodes[(size_t)ids[k]];
+        if (freqs) {
+            nd.d.mixer_freq_hz = freqs[k];
+            nco_rotation((double)nd.d.fs, freqs[k], nd.rot_re, nd.rot_im);
+        } else {
+            nd.d.gain = gains[k];
+        }
+    }
+    return SDRX_OK;
+}
+
+int set_vfo_values(sdrx_ctx *c, const int *ids, const double *freqs, const float *gains, int n, const char *what)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "%s before sdrx_finalize", what);
+    std::string msg;
+    if (check_vfo_list((int)c->nodes.size(), ids, freqs ? (const void *)freqs : (const void *)gains, freqs != nullptr, n, msg))
+        return fail(c, SDRX_EINVAL, "%s: %s", what, msg.c_str());
+    if (c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "%s: %d submitted frame(s) not yet delivered -- call sdrx_wait first", what, c->in_flight);
+    if (n == 0)
+        return SDRX_OK;
+    return apply_vfo_jobs(c, ids, freqs, gains, n);
+}
+
+} // namespace
+
+extern "C" {
+
+int sdrx_set_mixer_freqs(sdrx_ctx *c, const int *ids, const double *mixer_freq_hz, int n)
+{
+    return set_vfo_values(c, ids, mixer_freq_hz, nullptr, n, "sdrx_set_mixer_freqs");
+}
+
+int sdrx_set_gains(sdrx_ctx *c, const int *ids, const float *gains, int n)
+{
+    return set_vfo_values(c, ids, nullptr, gains, n, "sdrx_set_gains");
+}
 
 int sdrx_set_stream(sdrx_ctx *c, void *s)
 {

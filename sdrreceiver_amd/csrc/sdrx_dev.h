@@ -47,6 +47,10 @@ struct K1Vfo {
     // A USB leaf that demodulates in the mix wave itself (demod_chunk, kernels.hip; option fuse_demod): its demodulation
     // descriptor.  `out` is then unused -- decimate[d] of such a leaf goes to HBM only through `tap`.
     const K2Vfo *dm;
+    // The frame at which this VFO's oscillator started: 0 at finalize, the next frame after sdrx_set_mixer_freqs.  The table
+    // phase of frame f is ((f - origin) n_in) mod L, and sample 0 of frame `origin` takes the table's last entry -- a fresh
+    // Oscillator (oscillator.cpp:20-50) from that frame on.  (A frame number: as wide as the one the kernels are given.)
+    unsigned long long origin;
 };
 static_assert(sizeof(K1Vfo) % 8 == 0, "K1Vfo array stride");
 constexpr int kNcoSettle = 512; // table entries below this still carry the start-up ringing of the amplitude stabiliser (oscillator.cpp:20-28): always replayed exactly
@@ -159,5 +163,19 @@ struct NcoInit {
     int L;
     int pad_;
 };
+
+// One entry of k_vfo_retune's job list (sdrx_set_mixer_freqs, sdrx_set_gains).
+constexpr int kJobRetune = 0; // a new oscillator: regenerate vfo->cp, then write rot, rk and origin into *vfo
+constexpr int kJobGain = 1;   // *gain = value (K2Vfo::gain or K4Vfo::gain)
+struct RetuneJob {
+    K1Vfo *vfo;
+    float *gain;
+    float rot_re, rot_im;
+    float2 rk[4];
+    unsigned long long origin;
+    int kind;
+    float value;
+};
+static_assert(sizeof(RetuneJob) % 8 == 0, "RetuneJob array stride");
 
 } // namespace sdrx

@@ -29,6 +29,7 @@ struct sdrx_group {
     std::vector<sdrx_vfo_desc> descs;
     std::vector<std::pair<std::string, int>> options;
     std::vector<std::pair<int, int>> where; // global id -> (member, local id): the owner of a leaf, the FIRST replica of a VFO with children
+    std::vector<std::vector<std::pair<int, int>>> replicas; // global id -> every (member, local id) that holds it
     std::vector<int> publish_order;         // global ids of the leaves, reference order
     sdrx_publish_fn cb = nullptr;
     void *cb_user = nullptr;
@@ -172,6 +173,7 @@ void group_drop_members(sdrx_group *g)
         (void)hipStreamDestroy(g->stage_stream);
     g->stage_stream = nullptr;
     g->where.clear();
+    g->replicas.clear();
     g->publish_order.clear();
 }
 
@@ -339,6 +341,7 @@ static int group_finalize_impl(sdrx_group *g)
     if (g->root_frame <= 0)
         return gfail(g, SDRX_EINVAL, "vfo %d: samples_per_buffer must be positive", roots[0]);
     g->where.assign((size_t)N, std::make_pair(-1, -1));
+    g->replicas.assign((size_t)N, {});
     for (int k = 0; k < W; ++k) {
         std::vector<char> keep((size_t)N, 0);
         std::vector<int> stack;
@@ -389,6 +392,7 @@ static int group_finalize_impl(sdrx_group *g)
             M.global_of.push_back(i);
             if (g->where[(size_t)i].first < 0)
                 g->where[(size_t)i] = std::make_pair(k, lid);
+            g->replicas[(size_t)i].push_back(std::make_pair(k, lid));
         }
         if ((rc = sdrx_finalize(M.c)) != SDRX_OK)
             return member_fail(g, k, rc);
@@ -565,6 +569,62 @@ int sdrx_group_locate(sdrx_group *g, int id, int *member, int *local_id)
     if (local_id)
         *local_id = g->where[(size_t)id].second;
     return SDRX_OK;
+}
+
+// sdrx_set_mixer_freqs / sdrx_set_gains over the whole tree: the list is checked as a whole, then every member that holds a
+// listed VFO -- a VFO with children may be replicated on several -- applies its part (one launch per such member, none on the
+// others).
+static int group_set_values(sdrx_group *g, const int *ids, const double *freqs, const float *gains, int n, const char *what)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "%s before sdrx_group_finalize", what);
+    std::string msg;
+    if (check_vfo_list((int)g->descs.size(), ids, freqs ? (const void *)freqs : (const void *)gains, freqs != nullptr, n, msg))
+        return gfail(g, SDRX_EINVAL, "%s: %s", what, msg.c_str());
+    if (g->broken)
+        return gfail(g, SDRX_ESTATE, "%s: an earlier frame failed on one member", what);
+    if (g->in_flight > 0)
+        return gfail(g, SDRX_ESTATE, "%s: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", what, g->in_flight);
+    const size_t W = g->m.size();
+    std::vector<std::vector<int>> lids(W);
+    std::vector<std::vector<double>> fv(W);
+    std::vector<std::vector<float>> gv(W);
+    for (int k = 0; k < n; ++k)
+        for (const auto &r : g->replicas[(size_t)ids[k]]) {
+            lids[(size_t)r.first].push_back(r.second);
+            if (freqs)
+                fv[(size_t)r.first].push_back(freqs[k]);
+            else
+                gv[(size_t)r.first].push_back(gains[k]);
+        }
+    for (size_t k = 0; k < W; ++k) {
+        if (lids[k].empty())
+            continue;
+        const int cnt = (int)lids[k].size();
+        const int rc = freqs ? sdrx_set_mixer_freqs(g->m[k].c, lids[k].data(), fv[k].data(), cnt)
+                             : sdrx_set_gains(g->m[k].c, lids[k].data(), gv[k].data(), cnt);
+        if (rc)
+            return member_fail(g, (int)k, rc);
+    }
+    for (int k = 0; k < n; ++k) {
+        if (freqs)
+            g->descs[(size_t)ids[k]].mixer_freq_hz = freqs[k];
+        else
+            g->descs[(size_t)ids[k]].gain = gains[k];
+    }
+    return SDRX_OK;
+}
+
+int sdrx_group_set_mixer_freqs(sdrx_group *g, const int *ids, const double *mixer_freq_hz, int n)
+{
+    return group_set_values(g, ids, mixer_freq_hz, nullptr, n, "sdrx_group_set_mixer_freqs");
+}
+
+int sdrx_group_set_gains(sdrx_group *g, const int *ids, const float *gains, int n)
+{
+    return group_set_values(g, ids, nullptr, gains, n, "sdrx_group_set_gains");
 }
 
 int sdrx_group_member(sdrx_group *g, int k, sdrx_ctx **ctx, int *device)

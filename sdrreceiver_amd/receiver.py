@@ -13,6 +13,7 @@ Everything here is plumbing; the arithmetic runs in the HIP kernels of libsdrx.s
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
@@ -35,6 +36,14 @@ def arithmetic(exact) -> int:
 
 
 SPECTRUM_RAW = _lib.SPECTRUM_RAW  # the raw frame's spectrum (sdrj's own fftData, every 4th frame)
+
+
+def _value_list(vids, values, dtype) -> tuple[np.ndarray, np.ndarray]:
+    ids = np.ascontiguousarray(np.atleast_1d(np.asarray(vids)), dtype=np.int32).reshape(-1)
+    vals = np.ascontiguousarray(np.atleast_1d(np.asarray(values, dtype=dtype)), dtype=dtype).reshape(-1)
+    if ids.size != vals.size:
+        raise ValueError(f"{ids.size} ids but {vals.size} values")
+    return ids, vals
 
 
 class Receiver:
@@ -261,6 +270,21 @@ class Receiver:
         self._chk(self.L.sdrx_get_nco(self.h, vid, first, count, out.ctypes.data))
         return out[: 2 * count].view(np.complex64).copy()
 
+    # -- retuning between frames (sdrx_set_mixer_freqs / sdrx_set_gains) ------------------------------------------
+    def set_mixer_freqs(self, vids, freqs) -> None:
+        """VFO vids[k] mixes with a fresh oscillator at freqs[k] Hz from the next frame on; every filter state is kept."""
+        ids, vals = _value_list(vids, freqs, np.float64)
+        self._chk(self.L.sdrx_set_mixer_freqs(self.h, ids.ctypes.data, vals.ctypes.data, ids.size))
+        for i, f in zip(ids.tolist(), vals.tolist()):
+            self.descs[i] = dataclasses.replace(self.descs[i], mixer_freq=f)
+
+    def set_gains(self, vids, gains) -> None:
+        """vfo::setGain of VFO vids[k] between two frames: from the next frame on."""
+        ids, vals = _value_list(vids, gains, np.float32)
+        self._chk(self.L.sdrx_set_gains(self.h, ids.ctypes.data, vals.ctypes.data, ids.size))
+        for i, g in zip(ids.tolist(), vals.tolist()):
+            self.descs[i] = dataclasses.replace(self.descs[i], gain=g)
+
     # -- spectrum display (MainWindow::fftHandlerSlot on the device) ---------------------------------------------
     def set_spectrum(self, vid: int, on: bool = True) -> None:
         """Enable (and zero: the GUI's combo-box reset) or release the spectrum of VFO `vid`, or of the raw frame with
@@ -414,6 +438,20 @@ class Group:
         m, l = C.c_int(), C.c_int()
         self._chk(self.L.sdrx_group_locate(self.h, vid, C.byref(m), C.byref(l)))
         return m.value, l.value
+
+    def set_mixer_freqs(self, vids, freqs) -> None:
+        """:meth:`Receiver.set_mixer_freqs` with ids of the whole tree, on every member that holds the VFO."""
+        ids, vals = _value_list(vids, freqs, np.float64)
+        self._chk(self.L.sdrx_group_set_mixer_freqs(self.h, ids.ctypes.data, vals.ctypes.data, ids.size))
+        for i, f in zip(ids.tolist(), vals.tolist()):
+            self.descs[i] = dataclasses.replace(self.descs[i], mixer_freq=f)
+
+    def set_gains(self, vids, gains) -> None:
+        """:meth:`Receiver.set_gains` with ids of the whole tree."""
+        ids, vals = _value_list(vids, gains, np.float32)
+        self._chk(self.L.sdrx_group_set_gains(self.h, ids.ctypes.data, vals.ctypes.data, ids.size))
+        for i, g in zip(ids.tolist(), vals.tolist()):
+            self.descs[i] = dataclasses.replace(self.descs[i], gain=g)
 
     def member_stats(self) -> list[dict | None]:
         out = []

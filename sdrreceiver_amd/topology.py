@@ -195,8 +195,8 @@ def _ilog2(x) -> int:
     return int(math.log2(x))
 
 
-def topology_from_ini(text: str, name: str = "") -> Topology:
-    """mainwindow.cpp:27-233 on an INI text."""
+def topology_from_ini(text: str, name: str = "", mix_offset: int | None = None) -> Topology:
+    """mainwindow.cpp:27-233 on an INI text (`mix_offset`: in place of the INI's own key)."""
     kv = parse_ini(text)
     fs = _to_int(kv.get("sample_rate"))
     if fs == 0:
@@ -204,7 +204,9 @@ def topology_from_ini(text: str, name: str = "") -> Topology:
     if fs not in SUPPORTED_RATES:
         raise ValueError(f"sample_rate {fs} not supported, only {SUPPORTED_RATES}")  # 39-47
     center = _to_int(kv.get("center_frequency"))
-    mix_offset = _to_int(kv.get("mix_offset"))
+    if mix_offset is None:
+        mix_offset = _to_int(kv.get("mix_offset"))
+    mix_offset = int(mix_offset)
     # "usually 4 buffers per Fs but in some cases 5 due to multiple of 512", 65-80
     if ((2 * fs) // 4) % 512 > 0:
         buflen, bufsplit = (2 * fs) // 5, 5
@@ -265,6 +267,31 @@ def topology_from_ini(text: str, name: str = "") -> Topology:
             mixer_freq=float((center - main_vfo_freq) - vfo_freq), demod_usb=True, late_decimate=late,
             filter_bw=filterbw, gain=gain, cstyle=1, samples_per_buffer=main_out // bufsplit))
     return topo
+
+
+def mix_offset_retune(topo: Topology, ini_text: str, new_offset: int) -> tuple[list[int], list[float]]:
+    """A live change of the INI's `mix_offset` (the dongle's drift) as a retune of the running tree `topo`, which
+    topology_from_ini built from `ini_text`: the ids of the sub VFOs and their new mixers by mainwindow.cpp:141-225 (a change
+    of the offset by D moves every sub's mixer by -D and leaves the mains alone), for Receiver.set_mixer_freqs.  ValueError when
+    the new offset would move a sub VFO to another main or change its decimation or late-decimation geometry: that takes a
+    new tree."""
+    new = topology_from_ini(ini_text, mix_offset=new_offset)
+    if len(new.vfos) != len(topo.vfos) or new.frame != topo.frame or new.fs != topo.fs:
+        raise ValueError("the running tree was not built from this INI")
+    ids, freqs = [], []
+    for i, (a, b) in enumerate(zip(topo.vfos, new.vfos)):
+        geometry = ("parent", "fs", "decimate_count", "late_decimate", "samples_per_buffer", "demod_usb")
+        if any(getattr(a, k) != getattr(b, k) for k in geometry):
+            what = ", ".join(f"{k} {getattr(a, k)} -> {getattr(b, k)}" for k in geometry if getattr(a, k) != getattr(b, k))
+            raise ValueError(f"mix_offset {new_offset}: vfo {i} ({a.topic or 'main'}) changes its place in the tree ({what}): "
+                             "that needs a new tree, not a retune")
+        if a.parent < 0:
+            if a.mixer_freq != b.mixer_freq:
+                raise ValueError("the running tree was not built from this INI")
+            continue
+        ids.append(i)
+        freqs.append(float(b.mixer_freq))
+    return ids, freqs
 
 
 # ----------------------------------------------------------------------------- BASELINE configs
