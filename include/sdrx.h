@@ -139,6 +139,8 @@ int sdrx_add_vfo(sdrx_ctx *ctx, const sdrx_vfo_desc *desc, int *id_out);
  *            launch behind the frame's last level (A/B switch).  Composes with "fuse_demod".  Results are bit-identical.
  *   "keep_streams" 0 (default) | 1: every such leaf also keeps decimate[d] of every frame (parity tests that
  *            compare every stream of the tree).
+ *   "meter" 0 (default) | 1: with 1 every leaf also reports an output meter per frame (sdrx_get_meters).  0 changes
+ *            nothing: same kernels, same launches, same device_bytes.  Payloads are bit-identical either way.
  *   "dc_blocked_scan" 0|1 (default 0): how sdrx_process_u8 removes the DC bias.  0 = the
  *                 reference's sequentially rounded fp32 recurrence, bit for bit (below).  1 = the same linear filter as a
  *                 blocked parallel scan (~15 us): the true IIR response.  The reference's recurrence
@@ -242,6 +244,27 @@ int sdrx_in_flight(sdrx_ctx *ctx); /* >= 0: frames submitted and not yet deliver
 /* Payload of leaf `id` after the last frame: int16 audio (USB leaf) or packed int8 IQ
  * (compress(), vfo.cpp:389-424).  *rate = outputRate (vfo.cpp:102). */
 int sdrx_get_output(sdrx_ctx *ctx, int id, const void **buf, uint32_t *len_bytes, uint32_t *rate);
+/* Output meters (option "meter" = 1): what leaf ids[k]'s payload of the last DELIVERED frame -- the one sdrx_get_output
+ * serves -- holds, computed on the device where the payload is produced and copied out with it (readable while the next
+ * frame is in flight; for sdrx_process_device frames this runs what is outstanding first, as sdrx_get_output does).
+ *   USB leaf (int16):      pre = usb' * gain * 32768.0 as the reference computes it (vfo.cpp:328,364), v = the int16 sent;
+ *                          n_values = n_out; a sample wrapped when !(pre > -32769.0 && pre < 32768.0) (NaN included):
+ *                          exactly where the truncating conversion to short differs from trunc(pre).
+ *   compress() leaf (int8): per component pre = re * 128 (cstyle 0) or (re / scalecomp) * 128 (cstyle 1), v = its int8
+ *                          value before cstyle 1's nibble masking; n_values = 2 n; a sample wrapped when either component
+ *                          has !(pre > -129 && pre < 128).
+ * sum_sq = sum of v * v (exact), peak = max |pre| in LSB of the payload type (NaN if any pre was NaN).
+ * SDRX_ESTATE with the option off, before sdrx_finalize or before any frame was delivered; SDRX_EINVAL for a bad id, a
+ * VFO with children (it publishes nothing) or n < 0; n == 0 does nothing. */
+typedef struct sdrx_meter {
+    int64_t frame;     /* index of the frame these figures belong to (0 = first frame after finalize) */
+    uint64_t sum_sq;   /* sum of v*v over the payload values v of that frame (exact integer) */
+    uint32_t n_values; /* how many values were summed */
+    uint32_t clipped;  /* samples whose conversion left the payload type's range (i.e. wrapped) */
+    float peak;        /* max |pre-quantisation value|, in LSB of the payload type; NaN if any was NaN */
+    uint32_t reserved;
+} sdrx_meter;
+int sdrx_get_meters(sdrx_ctx *ctx, const int *ids, int n, sdrx_meter *out);
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);
@@ -374,6 +397,9 @@ int sdrx_group_member(sdrx_group *grp, int k, sdrx_ctx **ctx, int *device_ordina
  * children is replicated on each member that holds part of its subtree); a member with nothing listed makes no launch. */
 int sdrx_group_set_mixer_freqs(sdrx_group *grp, const int *ids, const double *mixer_freq_hz, int n);
 int sdrx_group_set_gains(sdrx_group *grp, const int *ids, const float *gains, int n);
+/* sdrx_get_meters with ids of the whole tree (group option "meter" = 1): each id is answered by the member that owns the
+ * leaf (sdrx_group_locate); `frame` counts the group's frames. */
+int sdrx_group_get_meters(sdrx_group *grp, const int *ids, int n, sdrx_meter *out);
 
 /* ---- introspection / measurement ------------------------------------------------------------- */
 typedef struct sdrx_stats {

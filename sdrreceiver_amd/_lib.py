@@ -50,6 +50,12 @@ class SpectrumInfoC(C.Structure):
                 ("maxval", C.c_double), ("aveval", C.c_double)]
 
 
+class MeterC(C.Structure):
+    """struct sdrx_meter"""
+    _fields_ = [("frame", C.c_int64), ("sum_sq", C.c_uint64), ("n_values", C.c_uint32), ("clipped", C.c_uint32),
+                ("peak", C.c_float), ("reserved", C.c_uint32)]
+
+
 PUBLISH_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
 
 # every symbol include/sdrx.h declares: (restype, argtypes)
@@ -86,6 +92,7 @@ SYMBOLS = {
     "sdrx_get_nco": (_i, [_vp, _i, C.c_long, C.c_long, _vp]),
     "sdrx_set_mixer_freqs": (_i, [_vp, _vp, _vp, _i]),
     "sdrx_set_gains": (_i, [_vp, _vp, _vp, _i]),
+    "sdrx_get_meters": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
@@ -116,6 +123,7 @@ SYMBOLS = {
     "sdrx_group_member": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
     "sdrx_group_set_mixer_freqs": (_i, [_vp, _vp, _vp, _i]),
     "sdrx_group_set_gains": (_i, [_vp, _vp, _vp, _i]),
+    "sdrx_group_get_meters": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_get_stats": (_i, [_vp, C.POINTER(StatsC)]),
     "sdrx_enable_kernel_timing": (_i, [_vp, _i]),
     "sdrx_get_kernel_times": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

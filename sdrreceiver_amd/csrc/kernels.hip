@@ -1315,6 +1315,65 @@ __device__ __forceinline__ float quantise(float scaled, short &out)
     return (float)pre; // exact: float * 2^15
 }
 
+// ---- output meters (option "meter") --------------------------------------------------------------------------
+// A work unit (a demodulation / low-pass / compress block, or a fused-demodulation mix item) folds the payload values it
+// emits into ONE 16-byte record {sum of v*v (u64), samples that wrapped, max |pre| as the bits of a non-negative float} and
+// writes it to a slot of its own behind the payloads (the host sums a leaf's slots).  Every slot is written every frame:
+// no zeroing, no atomics.  A lane's sum is 64-bit: four int16 -32768 squared already make 2^32.  The max of the bit
+// patterns is the max of the magnitudes, and a NaN (bits above +inf) wins.
+struct MeterAcc {
+    unsigned long long sum_sq;
+    unsigned clipped, peak;
+};
+__device__ __forceinline__ MeterAcc meter_zero() { return MeterAcc{0ull, 0u, 0u}; }
+// an int16 value v = the short of quantise(), pre = its return value (exact): wrapped unless -32769 < pre < 32768
+__device__ __forceinline__ void meter_usb(MeterAcc &m, float pre, short v)
+{
+    const int iv = v;
+    m.sum_sq += (unsigned long long)(unsigned)(iv * iv);
+    m.clipped += !(pre > -32769.0f && pre < 32768.0f);
+    m.peak = max(m.peak, __float_as_uint(fabsf(pre)));
+}
+__device__ __forceinline__ void meter_wave_reduce(MeterAcc &m)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        m.sum_sq += __shfl_xor(m.sum_sq, o, 64);
+        m.clipped += (unsigned)__shfl_xor((int)m.clipped, o, 64);
+        m.peak = max(m.peak, (unsigned)__shfl_xor((int)m.peak, o, 64));
+    }
+}
+__device__ __forceinline__ void meter_put(unsigned char *slot, const MeterAcc &m)
+{
+    const v4u r = {(unsigned)m.sum_sq, (unsigned)(m.sum_sq >> 32), m.clipped, m.peak};
+    *(SDRX_AS1 v4u *)slot = r;
+}
+// one wave's record (every lane of the wave calls it)
+__device__ __forceinline__ void meter_wave_store(MeterAcc m, unsigned char *slot, int lane)
+{
+    meter_wave_reduce(m);
+    if (lane == 0)
+        meter_put(slot, m);
+}
+// one 256-thread block's record: every thread of the block calls it (a barrier inside); `red`: 64 bytes of LDS nothing else
+// uses from here on (a static array would move the dynamic LDS of k_levels_tail's mix waves, and cost its exact form a spill)
+__device__ __forceinline__ void meter_block_store(MeterAcc m, unsigned char *slot, int tid, MeterAcc *red)
+{
+    meter_wave_reduce(m);
+    if ((tid & 63) == 0)
+        red[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            m.sum_sq += red[w].sum_sq;
+            m.clipped += red[w].clipped;
+            m.peak = max(m.peak, red[w].peak);
+        }
+        meter_put(slot, m);
+    }
+}
+
 
 // ---- the USB demodulation INSIDE the leaf's wave (vfo::usb_demod, vfo.cpp:300-332) -----------------------------------------
 // A d = 2 leaf below a parent (the reference's 48 kS/s sub VFOs: 83 % of BASELINE config 3's demodulation work) turns every
@@ -1381,8 +1440,10 @@ __device__ __forceinline__ void demod_prologue(float *dm, const K2Vfo *Kp, int p
 }
 // One chunk: z[0..3] = the lane's stream samples 4 lane .. 4 lane + 3 of the chunk (stream index g0 + ...), nv = how many of
 // the chunk's 256 are real (a multiple of 4), fo = first stream index this item emits, `last` = the chunk holds the frame's end.
-template <bool EXACT>
-__device__ __forceinline__ void demod_chunk(float *dm, const DemodCtx &C, const v2f *z, int lane, int nv, int g0, int fo, bool last)
+// METER: the emitted values are folded into `macc` (the item's record, written by mix_item at its end).
+template <bool EXACT, bool METER>
+__device__ __forceinline__ void demod_chunk(float *dm, const DemodCtx &C, const v2f *z, int lane, int nv, int g0, int fo, bool last,
+                                            MeterAcc &macc)
 {
     const K2Vfo *Kp = C.Kp;
     asm volatile("" : "+s"(Kp)); // (what is read through it below is read in THIS chunk, not once in front of the chunk loop)
@@ -1485,6 +1546,10 @@ __device__ __forceinline__ void demod_chunk(float *dm, const DemodCtx &C, const 
             float *prequant = ldc(&Kp->prequant);
             if (prequant)
                 gst4(reinterpret_cast<float4 *>(prequant + g), make_float4(pq[0], pq[1], pq[2], pq[3]));
+            if constexpr (METER)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr)
+                    meter_usb(macc, pq[rr], o4[rr]);
         }
     }
     wave_sync();
@@ -1521,7 +1586,9 @@ constexpr int kK1MinWaves = 5;
 // item's VFO is fed by the raw frame (`raw`, `raw_mode`), otherwise by its parent's tile-layout stream.
 // DM: the leaf demodulates its stream in this very wave (demod_chunk; DEPTH == 2 only) -- decimate[2] itself is then written only
 // where it is wanted (K1Vfo::tap: the spectrum tap, option keep_streams).
-template <bool EXACT, int DEPTH, bool ROT, bool DM = false>
+// METER (with DM): the item's output meter goes to the leaf's record s_first_out >> s (K2Vfo::meter_rel).  (Only the
+// descriptor the chunks use anyway is read: the exact k_levels_tail has no SGPR to spare for another pointer.)
+template <bool EXACT, int DEPTH, bool ROT, bool DM = false, bool METER = false>
 __device__ __forceinline__ void mix_item(const K1Vfo *__restrict__ vfos, const K1Work W, unsigned long long frame_no,
                                          const void *__restrict__ raw, int raw_mode, bool level0_arg, unsigned char *smem, int lane)
 {
@@ -1568,6 +1635,7 @@ __device__ __forceinline__ void mix_item(const K1Vfo *__restrict__ vfos, const K
     DemodCtx dmc;
     if constexpr (DM)
         demod_prologue(dm, ldc(&Dp->dm), par, from_state, lane, dmc);
+    MeterAcc macc = meter_zero();
     const unsigned long long origin = ldc(&Dp->origin); // (frame_no >= origin: set between frames)
     const int phase_frame = (int)(((frame_no - origin) * (unsigned long long)D.n_in) % (unsigned long long)D.L);
 
@@ -1736,7 +1804,7 @@ __device__ __forceinline__ void mix_item(const K1Vfo *__restrict__ vfos, const K
                     gstv4(reinterpret_cast<float4 *>(dm_tap + (size_t)g), cat2(z[0], z[1]));
                     gstv4(reinterpret_cast<float4 *>(dm_tap + (size_t)(g + 2)), cat2(z[2], z[3]));
                 }
-                demod_chunk<EXACT>(dm, dmc, z, lane, valid >> 2, base >> 2, first_out >> 2, save);
+                demod_chunk<EXACT, METER>(dm, dmc, z, lane, valid >> 2, base >> 2, first_out >> 2, save, macc);
             } else if constexpr (kShape) { // its four outputs wait (in LDS) for the next chunk's loads to be on their way
                 v4f *park = reinterpret_cast<v4f *>(lds) + 2 * lane;
                 park[0] = cat2(z[0], z[1]);
@@ -1785,6 +1853,10 @@ __device__ __forceinline__ void mix_item(const K1Vfo *__restrict__ vfos, const K
         }
     }
     flush_held(); // the last chunk's outputs
+    if constexpr (DM && METER) {
+        const int rel = ldc(&dmc.Kp->meter_rel);
+        meter_wave_store(macc, reinterpret_cast<unsigned char *>(ldc(&dmc.Kp->pay[par])) + (rel & ~15) + 16 * (first_out >> (rel & 15)), lane);
+    }
 }
 
 // ------------------------------------------------------------------------------------ late_item
@@ -1975,7 +2047,7 @@ __device__ __forceinline__ void late_item(const K1Vfo *__restrict__ vfos, const 
 }
 
 // which body a work item runs: the fused late decimation for the leaves marked so at finalize, the half-band cascade otherwise
-template <bool EXACT, bool ROT>
+template <bool EXACT, bool ROT, bool METER>
 __device__ __forceinline__ void run_item(const K1Vfo *__restrict__ vfos, const K1Work W, unsigned long long frame_no,
                                          const void *__restrict__ raw, int raw_mode, bool level0, unsigned char *smem, int lane)
 {
@@ -1990,7 +2062,7 @@ __device__ __forceinline__ void run_item(const K1Vfo *__restrict__ vfos, const K
         const int d = ldc(&vfos[W.vfo].d);
         const int shape = leaf_on_tiles && d == kFixedDepth ? kFixedDepth : leaf_on_tiles && d == 2 ? 2 : 0;
         if (shape == 2 && ldc(&vfos[W.vfo].dm) != nullptr) // (set at finalize for exactly such leaves: option fuse_demod)
-            mix_item<EXACT, 2, ROT, true>(vfos, W, frame_no, raw, raw_mode, false, smem, lane);
+            mix_item<EXACT, 2, ROT, true, METER>(vfos, W, frame_no, raw, raw_mode, false, smem, lane);
         else if (shape == kFixedDepth)
             mix_item<EXACT, kFixedDepth, ROT>(vfos, W, frame_no, raw, raw_mode, false, smem, lane);
         else if (shape == 2)
@@ -2002,12 +2074,13 @@ __device__ __forceinline__ void run_item(const K1Vfo *__restrict__ vfos, const K
 
 // One wave per workgroup, one workgroup per K1Work.  LEVEL only gives the root launch and the sub
 // launches distinct kernel names in profiles.
-template <bool EXACT, int LEVEL, bool ROT = !EXACT>
+// METER: option "meter" (the fused-demodulation items write output meters).
+template <bool EXACT, int LEVEL, bool ROT = !EXACT, bool METER = false>
 __global__ __launch_bounds__(64, kK1MinWaves) void k_mix_decimate(const K1Vfo *__restrict__ vfos, const K1Work *__restrict__ work,
                                                      unsigned long long frame_no, const void *__restrict__ raw, int raw_mode)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    run_item<EXACT, ROT>(vfos, work[blockIdx.x], frame_no, raw, raw_mode, LEVEL == 0, smem, (int)threadIdx.x);
+    run_item<EXACT, ROT, METER>(vfos, work[blockIdx.x], frame_no, raw, raw_mode, LEVEL == 0, smem, (int)threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------ demod tail (kernels of its own)
@@ -2303,7 +2376,9 @@ struct DemodLds { // LDS of one 256-thread demodulation block
 };
 static_assert(sizeof(DemodLds) % 16 == 0, "DemodLds is a whole number of 16-byte units");
 
-template <bool EXACT>
+// METER: the block's output meter goes to the leaf's record blk (K2Vfo::meter_rel; not for a leaf with a long low-pass:
+// k_lpf_long meters that one).
+template <bool EXACT, bool METER>
 __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, const BlockWork bw, unsigned long long frame_no, DemodLds &S,
                                             int tid)
 {
@@ -2323,8 +2398,12 @@ __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, cons
     const float2 *sbase = ldc(&Dp->s[par]);
     float2 *snext = ldc(&Dp->s_next[par]);
     const int m0 = blk * D.tile;
-    if (m0 >= D.n && blk != 0)
+    if (m0 >= D.n && blk != 0) {
+        if constexpr (METER) // (the whole block: no value, an empty record)
+            if (!usb_out && tid == 0)
+                meter_put(reinterpret_cast<unsigned char *>(D.pay) + ldc(&Dp->meter_rel) + 16 * blk, meter_zero());
         return;
+    }
     // The 62 Hilbert taps, read before this kernel has stored anything so the compiler can use
     // wave-uniform scalar loads and keep them in SGPRs for the whole block.  (The non-exact arithmetics take them pass by
     // pass as register PAIRS instead: hilbert4_packed.  The exact arithmetic's sum packed -- v_pk_mul / v_pk_add -- was
@@ -2412,8 +2491,12 @@ __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, cons
     // ---- audio low-pass (newest sample excluded) on 4 consecutive outputs, then int16
     const int j0 = 4 * tid;
     const int m = m0 + j0;
-    if (j0 >= D.tile || m >= D.n)
+    const bool emits = j0 < D.tile && m < D.n;
+    if (!emits && (!METER || usb_out)) // (usb_out: the same for the whole block -- none of its threads reaches the record)
         return;
+    // (METER: every thread goes on to the block's record)
+    MeterAcc macc = meter_zero();
+    if (emits) {
     float u4[4];
     if (N > 0) {
         // output j0+rr, tap i reads usb t = j0 + rr + (E-N) + i; sH[i+3] = hu[i], zeros around
@@ -2461,23 +2544,33 @@ __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, cons
         *(SDRX_AS1 v4s *)(D.pay + m) = o;
         if (D.prequant)
             gst4(reinterpret_cast<float4 *>(D.prequant + m), make_float4(pq[0], pq[1], pq[2], pq[3]));
+        if constexpr (METER)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr)
+                meter_usb(macc, pq[rr], o4[rr]);
     } else {
         for (int rr = 0; rr < 4 && m + rr < D.n; ++rr) {
             *(SDRX_AS1 short *)(D.pay + m + rr) = o4[rr];
             if (D.prequant)
                 *(SDRX_AS1 float *)(D.prequant + m + rr) = pq[rr];
+            if constexpr (METER)
+                meter_usb(macc, pq[rr], o4[rr]);
         }
     }
+    }
+    if constexpr (METER)
+        meter_block_store(macc, reinterpret_cast<unsigned char *>(D.pay) + ldc(&Dp->meter_rel) + 16 * blk, tid,
+                          reinterpret_cast<MeterAcc *>(sP0)); // (the Hilbert planes are done with)
 }
 
 // (no occupancy demand: __launch_bounds__(256, 8) -- at most 64 VGPRs, eight 256-thread blocks per CU -- measured 92 us
 // against 47 us; profiles/README.md)
-template <bool EXACT>
+template <bool EXACT, bool METER = false>
 __global__ __launch_bounds__(256, 1) void k_usb_demod(const K2Vfo *__restrict__ vfos, const BlockWork *__restrict__ work,
                                                    unsigned long long frame_no)
 {
     __shared__ __attribute__((aligned(16))) DemodLds S;
-    demod_block<EXACT>(vfos, work[blockIdx.x], frame_no, S, (int)threadIdx.x);
+    demod_block<EXACT, METER>(vfos, work[blockIdx.x], frame_no, S, (int)threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------ k_mix_levels
@@ -2496,7 +2589,7 @@ struct LevelArgs {
     int raw_mode;                               // ... and its form (kRaw*)
     int pad_;
 };
-template <bool EXACT, bool ROT = !EXACT>
+template <bool EXACT, bool ROT = !EXACT, bool METER = false>
 __global__ __launch_bounds__(64, kK1MinWaves) void k_mix_levels(const K1Vfo *__restrict__ k1, const K1Work *__restrict__ items,
                                                    const int *__restrict__ item_level, const int *__restrict__ list, LevelArgs A)
 {
@@ -2505,7 +2598,7 @@ __global__ __launch_bounds__(64, kK1MinWaves) void k_mix_levels(const K1Vfo *__r
     if (it < 0)
         return;
     const int lv = ldc(item_level + it);
-    run_item<EXACT, ROT>(k1, K1Work{ldc(&items[it].vfo), ldc(&items[it].s_begin), ldc(&items[it].s_first_out), ldc(&items[it].s_end)},
+    run_item<EXACT, ROT, METER>(k1, K1Work{ldc(&items[it].vfo), ldc(&items[it].s_begin), ldc(&items[it].s_first_out), ldc(&items[it].s_end)},
                     A.frame_level[lv], A.raw, A.raw_mode, lv == 0, smem, (int)threadIdx.x);
 }
 
@@ -2529,7 +2622,7 @@ struct LevelTailArgs {
     int active;                    // bit l: tree level l has a frame in this launch; bit kMaxLevels: the demodulation has one
     int lds_wave;                  // LDS bytes of one mix wave
 };
-template <bool EXACT, bool ROT = !EXACT>
+template <bool EXACT, bool ROT = !EXACT, bool METER = false>
 __global__ __launch_bounds__(256, kK1MinWaves) void k_levels_tail(const K1Vfo *__restrict__ k1, const K1Work *__restrict__ items,
                                                                   const int *__restrict__ item_level, const TailWg *__restrict__ wgs,
                                                                   const K2Vfo *__restrict__ k2, const BlockWork *__restrict__ dwork,
@@ -2540,8 +2633,8 @@ __global__ __launch_bounds__(256, kK1MinWaves) void k_levels_tail(const K1Vfo *_
     if (first <= -2) {
         if (A.active & (1 << kMaxLevels)) {
             const int b = -2 - first;
-            demod_block<EXACT>(k2, BlockWork{ldc(&dwork[b].vfo), ldc(&dwork[b].blk)}, A.frame_tail, *reinterpret_cast<DemodLds *>(smem),
-                               (int)threadIdx.x);
+            demod_block<EXACT, METER>(k2, BlockWork{ldc(&dwork[b].vfo), ldc(&dwork[b].blk)}, A.frame_tail, *reinterpret_cast<DemodLds *>(smem),
+                                      (int)threadIdx.x);
         }
         return;
     }
@@ -2552,8 +2645,10 @@ __global__ __launch_bounds__(256, kK1MinWaves) void k_levels_tail(const K1Vfo *_
     const int lv = ldc(item_level + it);
     if (!((A.active >> lv) & 1)) // (a level without a frame: only while the pipeline drains)
         return;
-    run_item<EXACT, ROT>(k1, K1Work{ldc(&items[it].vfo), ldc(&items[it].s_begin), ldc(&items[it].s_first_out), ldc(&items[it].s_end)},
-                         A.L.frame_level[lv], A.L.raw, A.L.raw_mode, lv == 0, smem + wave * A.lds_wave, (int)threadIdx.x & 63);
+    // (METER && EXACT: the fused-demodulation items' meters would cost this kernel a spill -- 4 VGPRs of accumulators beside
+    // the demodulation blocks' SGPRs; the planner keeps such trees in k_mix_levels + k_usb_demod instead: build_level_plan)
+    run_item<EXACT, ROT, METER && !EXACT>(k1, K1Work{ldc(&items[it].vfo), ldc(&items[it].s_begin), ldc(&items[it].s_first_out), ldc(&items[it].s_end)},
+                                A.L.frame_level[lv], A.L.raw, A.L.raw_mode, lv == 0, smem + wave * A.lds_wave, (int)threadIdx.x & 63);
 }
 
 // An audio low-pass of more than kMaxFir taps (the reference accepts any filter_bandwidth: 500 Hz at
@@ -2561,8 +2656,9 @@ __global__ __launch_bounds__(256, kK1MinWaves) void k_levels_tail(const K1Vfo *_
 // excluded (FIR::FIRUpdateAndProcess, dsp.cpp:59-71), one accumulator per output in tap order, then the
 // same quantisation as k_usb_demod.  256 outputs per block; the block's window of N + 256 usb values sits
 // in LDS, the taps are wave-uniform scalar loads.  A rare configuration: correctness first.
-template <bool EXACT>
-__global__ __launch_bounds__(256) void k_lpf_long(const K4Vfo *__restrict__ vfos, const BlockWork *__restrict__ work, unsigned long long frame_no)
+template <bool EXACT, bool METER = false>
+__global__ __launch_bounds__(256) void k_lpf_long(const K4Vfo *__restrict__ vfos, const BlockWork *__restrict__ work, unsigned long long frame_no,
+                                                  const int *__restrict__ mrel)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *sw = reinterpret_cast<float *>(smem);
@@ -2588,8 +2684,10 @@ __global__ __launch_bounds__(256) void k_lpf_long(const K4Vfo *__restrict__ vfos
     }
     __syncthreads();
     const int m = m0 + tid;
-    if (m >= n)
+    if (!METER && m >= n)
         return;
+    MeterAcc macc = meter_zero();
+    if (m < n) { // (METER: every thread goes on to the block's record)
     const float *w = sw + tid; // w[i] = usb[m - N + i]
     float acc = 0.f;
     for (int i = 0; i < N; ++i) {
@@ -2604,6 +2702,13 @@ __global__ __launch_bounds__(256) void k_lpf_long(const K4Vfo *__restrict__ vfos
     *(SDRX_AS1 short *)(pay + m) = q;
     if (prequant)
         *(SDRX_AS1 float *)(prequant + m) = pre;
+    if constexpr (METER)
+        meter_usb(macc, pre, q);
+    }
+    if constexpr (METER) {
+        __shared__ MeterAcc red[4];
+        meter_block_store(macc, reinterpret_cast<unsigned char *>(pay) + ldc(mrel + blockIdx.x), tid, red);
+    }
 }
 
 // vfo::compress (vfo.cpp:389-424): cstyle 1 packs the high nibbles of (re/scalecomp)*128 and
@@ -2613,6 +2718,15 @@ __device__ __forceinline__ int to_schar(float f) // cvttss2si + the low 8 bits: 
     const int t = (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : (int)0x80000000;
     return (int)(signed char)(unsigned char)(unsigned)t;
 }
+// METER: n_values 2 n; v = each component's to_schar value (before cstyle 1's nibble masking), pre = what it converts; a
+// sample wrapped when either component left -129 < pre < 128.
+__device__ __forceinline__ void meter_iq(MeterAcc &m, float pre_re, float pre_im, int re, int im)
+{
+    m.sum_sq += (unsigned long long)(unsigned)(re * re + im * im);
+    m.clipped += !(pre_re > -129.0f && pre_re < 128.0f && pre_im > -129.0f && pre_im < 128.0f);
+    m.peak = max(m.peak, max(__float_as_uint(fabsf(pre_re)), __float_as_uint(fabsf(pre_im))));
+}
+template <bool METER = false>
 __global__ __launch_bounds__(256) void k_compress(const K3Vfo *__restrict__ vfos, const BlockWork *__restrict__ work,
                                                   unsigned long long frame_no)
 {
@@ -2625,17 +2739,29 @@ __global__ __launch_bounds__(256) void k_compress(const K3Vfo *__restrict__ vfos
         int n, cstyle, scalecomp;
     } D = {Dp->pay[par], Dp->n, Dp->cstyle, Dp->scalecomp};
     const float2 *z = Dp->s[par];
+    MeterAcc macc = meter_zero();
     for (int i = blk * 4096 + threadIdx.x; i < min(D.n, (blk + 1) * 4096); i += 256) {
         const float2 v = gld2(z + i);
         if (D.cstyle == 1) {
             const float sc = (float)D.scalecomp;
-            const int re = to_schar((v.x / sc) * 128.0f);
-            const int im = to_schar((v.y / sc) * 128.0f);
+            const float pre_re = (v.x / sc) * 128.0f, pre_im = (v.y / sc) * 128.0f;
+            const int re = to_schar(pre_re);
+            const int im = to_schar(pre_im);
             D.pay[i] = (signed char)((re & 0xF0) | ((im & 0xF0) >> 4));
+            if constexpr (METER)
+                meter_iq(macc, pre_re, pre_im, re, im);
         } else {
-            D.pay[2 * i] = (signed char)to_schar(v.x * 128.0f);
-            D.pay[2 * i + 1] = (signed char)to_schar(v.y * 128.0f);
+            const float pre_re = v.x * 128.0f, pre_im = v.y * 128.0f;
+            const int re = to_schar(pre_re), im = to_schar(pre_im);
+            D.pay[2 * i] = (signed char)re;
+            D.pay[2 * i + 1] = (signed char)im;
+            if constexpr (METER)
+                meter_iq(macc, pre_re, pre_im, re, im);
         }
+    }
+    if constexpr (METER) {
+        __shared__ MeterAcc red[4];
+        meter_block_store(macc, reinterpret_cast<unsigned char *>(D.pay) + Dp->meter_rel + 16 * blk, (int)threadIdx.x, red);
     }
 }
 

@@ -76,6 +76,8 @@ struct Node {
     int d2_index = -1;      // its K2Vfo in the demodulation descriptor array
     int d4_index = -1;      // its K4Vfo (long_lpf): k_lpf_long applies the gain
     bool has_stream = true; // decimate[d] of every frame is kept in HBM (false: a fused late decimation writes only z', a fused demodulation only the payload)
+    int meter_first = 0, meter_n = 0; // option meter: this leaf's records, slots [meter_first, meter_first + meter_n) behind the payloads
+    int meter_shift = 0;              //   ... fuse_demod: the record of a mix item is s_first_out >> meter_shift
 };
 
 struct Launch1 { // one k_mix_decimate launch (a tree level)
@@ -92,6 +94,7 @@ struct LaunchB { // block-per-tile launches (late decimate / demod / compress): 
     size_t off_desc, off_work;
     int lds_bytes;
     int64_t alg_bytes;
+    size_t off_mrel = 0; // option meter, k_lpf_long: arena offset of the blocks' record offsets (int[n_blocks])
 };
 
 // The one-launch levels (k_mix_levels): the list is [level 0 items | level 1 items | ...], every part
@@ -135,6 +138,11 @@ struct sdrx_ctx {
     int opt_exact = 1, opt_prequant = 0, opt_segments = 0, opt_dc_blocked = 0, opt_pipeline = 0, opt_dc_speculative = 1;
     int opt_fuse = 1, opt_frame_pipeline = 1, opt_fuse_late = 1, opt_keep_streams = 0, opt_fuse_demod = 0;
     int opt_tail_in_levels = 1;
+    int opt_meter = 0;
+    // option meter: per frame parity, behind the payloads in d_pay / h_pay (at meter_off), one 16-byte MeterAcc record per work
+    // unit that emits payload values (kernels.hip "output meters"); the records travel in the payload copy
+    size_t meter_off = 0;
+    int meter_slots = 0;
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first
     // frame that fills them.  The first such leaf uses the arena's buffer, further ones buffers of their own (hipMalloc).
@@ -172,6 +180,7 @@ struct sdrx_ctx {
     int in_flight = 0;               // frames submitted (sdrx_submit*) and not yet delivered (sdrx_wait)
     bool broken = false;             // fault injection (SDRX_FAULT_WAIT): every frame call fails from here on, like after a HIP error
     int host_slot = -1;              // which h_pay holds the payloads sdrx_get_output serves
+    unsigned long long host_frame = 0; // ... and which frame they are
     float2 *d_raw[2] = {nullptr, nullptr}; // host-fed frames on the device (natural order), per frame parity: frame f's
                                            //   buffer stays untouched until f+2 is staged (another context on this device may
                                            //   be working on it: sdrx_submit_shared)
@@ -445,11 +454,16 @@ int enqueue_frame_as(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
     for (const Launch1 &L : c->l1) {
         Bracket b(c, c->stream, L.kind, L.alg_bytes);
         const K1Work *w = reinterpret_cast<const K1Work *>(c->arena + L.off_work);
-        if (L.level == 0)
-            hipLaunchKernelGGL((k_mix_decimate<EXACT, 0, ROT>), dim3(L.n_work), dim3(64), L.lds_bytes, c->stream, k1, w, c->frame_no, raw, raw_mode);
+        const void *lraw = L.level == 0 ? raw : nullptr;
+        const int lmode = L.level == 0 ? raw_mode : kRawTiled;
+        if (c->opt_meter && L.level == 0)
+            hipLaunchKernelGGL((k_mix_decimate<EXACT, 0, ROT, true>), dim3(L.n_work), dim3(64), L.lds_bytes, c->stream, k1, w, c->frame_no, lraw, lmode);
+        else if (c->opt_meter)
+            hipLaunchKernelGGL((k_mix_decimate<EXACT, 1, ROT, true>), dim3(L.n_work), dim3(64), L.lds_bytes, c->stream, k1, w, c->frame_no, lraw, lmode);
+        else if (L.level == 0)
+            hipLaunchKernelGGL((k_mix_decimate<EXACT, 0, ROT>), dim3(L.n_work), dim3(64), L.lds_bytes, c->stream, k1, w, c->frame_no, lraw, lmode);
         else
-            hipLaunchKernelGGL((k_mix_decimate<EXACT, 1, ROT>), dim3(L.n_work), dim3(64), L.lds_bytes, c->stream, k1, w, c->frame_no,
-                               (const void *)nullptr, kRawTiled);
+            hipLaunchKernelGGL((k_mix_decimate<EXACT, 1, ROT>), dim3(L.n_work), dim3(64), L.lds_bytes, c->stream, k1, w, c->frame_no, lraw, lmode);
     }
     hipStream_t ts = pipe ? c->tail_stream : c->stream;
     if (pipe) {
@@ -500,6 +514,8 @@ void launch_block_kernel(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned
     Bracket b(c, ts, L.kind, L.alg_bytes);
     const dim3 grid(L.n_blocks);
     const BlockWork *w = reinterpret_cast<const BlockWork *>(c->arena + L.off_work);
+    const bool meter = c->opt_meter != 0;
+    const int *mrel = meter ? reinterpret_cast<const int *>(c->arena + L.off_mrel) : nullptr;
     const K2aVfo *k2a = reinterpret_cast<const K2aVfo *>(c->arena + L.off_desc);
     if (L.kind == KIND_LATE_DEC && c->late4) {
         if (exact)
@@ -513,18 +529,30 @@ void launch_block_kernel(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned
             hipLaunchKernelGGL(k_late_decimate<false>, grid, dim3(256), L.lds_bytes, ts, k2a, w, frame);
     } else if (L.kind == KIND_DEMOD) {
         const K2Vfo *k2 = reinterpret_cast<const K2Vfo *>(c->arena + L.off_desc);
-        if (exact)
-            hipLaunchKernelGGL(k_usb_demod<true>, grid, dim3(256), 0, ts, k2, w, frame);
+        if (exact && meter)
+            hipLaunchKernelGGL((k_usb_demod<true, true>), grid, dim3(256), 0, ts, k2, w, frame);
+        else if (exact)
+            hipLaunchKernelGGL((k_usb_demod<true>), grid, dim3(256), 0, ts, k2, w, frame);
+        else if (meter)
+            hipLaunchKernelGGL((k_usb_demod<false, true>), grid, dim3(256), 0, ts, k2, w, frame);
         else
-            hipLaunchKernelGGL(k_usb_demod<false>, grid, dim3(256), 0, ts, k2, w, frame);
+            hipLaunchKernelGGL((k_usb_demod<false>), grid, dim3(256), 0, ts, k2, w, frame);
     } else if (L.kind == KIND_LPF_LONG) {
         const K4Vfo *k4 = reinterpret_cast<const K4Vfo *>(c->arena + L.off_desc);
-        if (exact)
-            hipLaunchKernelGGL(k_lpf_long<true>, grid, dim3(256), L.lds_bytes, ts, k4, w, frame);
+        if (exact && meter)
+            hipLaunchKernelGGL((k_lpf_long<true, true>), grid, dim3(256), L.lds_bytes, ts, k4, w, frame, mrel);
+        else if (exact)
+            hipLaunchKernelGGL((k_lpf_long<true>), grid, dim3(256), L.lds_bytes, ts, k4, w, frame, mrel);
+        else if (meter)
+            hipLaunchKernelGGL((k_lpf_long<false, true>), grid, dim3(256), L.lds_bytes, ts, k4, w, frame, mrel);
         else
-            hipLaunchKernelGGL(k_lpf_long<false>, grid, dim3(256), L.lds_bytes, ts, k4, w, frame);
+            hipLaunchKernelGGL((k_lpf_long<false>), grid, dim3(256), L.lds_bytes, ts, k4, w, frame, mrel);
     } else {
-        hipLaunchKernelGGL(k_compress, grid, dim3(256), 0, ts, reinterpret_cast<const K3Vfo *>(c->arena + L.off_desc), w, frame);
+        const K3Vfo *k3 = reinterpret_cast<const K3Vfo *>(c->arena + L.off_desc);
+        if (meter)
+            hipLaunchKernelGGL(k_compress<true>, grid, dim3(256), 0, ts, k3, w, frame);
+        else
+            hipLaunchKernelGGL(k_compress<>, grid, dim3(256), 0, ts, k3, w, frame);
     }
 }
 
@@ -570,12 +598,21 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
         const int first = std::min(P.part_begin[(size_t)lo], P.part_begin[(size_t)hi]), last = std::max(P.part_end[(size_t)lo], P.part_end[(size_t)hi]);
         Bracket b(c, c->stream, lo != hi ? KIND_LEVELS : lo == 0 ? KIND_MIX_ROOT : KIND_MIX_SUB, bytes);
         const int *list = reinterpret_cast<const int *>(c->arena + P.off_list) + first;
-        if (c->opt_exact == 1)
-            hipLaunchKernelGGL((k_mix_levels<true, false>), dim3(last - first), dim3(64), P.lds_bytes, c->stream, k1, items, item_level, list, A);
-        else if (c->opt_exact == 2)
-            hipLaunchKernelGGL((k_mix_levels<false, false>), dim3(last - first), dim3(64), P.lds_bytes, c->stream, k1, items, item_level, list, A);
-        else
-            hipLaunchKernelGGL((k_mix_levels<false, true>), dim3(last - first), dim3(64), P.lds_bytes, c->stream, k1, items, item_level, list, A);
+        const dim3 grid(last - first);
+        if (c->opt_meter) {
+            if (c->opt_exact == 1)
+                hipLaunchKernelGGL((k_mix_levels<true, false, true>), grid, dim3(64), P.lds_bytes, c->stream, k1, items, item_level, list, A);
+            else if (c->opt_exact == 2)
+                hipLaunchKernelGGL((k_mix_levels<false, false, true>), grid, dim3(64), P.lds_bytes, c->stream, k1, items, item_level, list, A);
+            else
+                hipLaunchKernelGGL((k_mix_levels<false, true, true>), grid, dim3(64), P.lds_bytes, c->stream, k1, items, item_level, list, A);
+        } else if (c->opt_exact == 1) {
+            hipLaunchKernelGGL((k_mix_levels<true, false>), grid, dim3(64), P.lds_bytes, c->stream, k1, items, item_level, list, A);
+        } else if (c->opt_exact == 2) {
+            hipLaunchKernelGGL((k_mix_levels<false, false>), grid, dim3(64), P.lds_bytes, c->stream, k1, items, item_level, list, A);
+        } else {
+            hipLaunchKernelGGL((k_mix_levels<false, true>), grid, dim3(64), P.lds_bytes, c->stream, k1, items, item_level, list, A);
+        }
     } else {
         // the list is [level n-1 | ... | level 0 | demodulation]: the range runs from the deepest level with a frame to the
         // demodulation (or to the shallowest level with a frame); levels inside it without a frame (the pipeline draining)
@@ -594,12 +631,21 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
         const LaunchB &D = *std::find_if(c->lb.begin(), c->lb.end(), [](const LaunchB &L) { return L.kind == KIND_DEMOD; });
         const K2Vfo *k2 = reinterpret_cast<const K2Vfo *>(c->arena + D.off_desc);
         const BlockWork *dwork = reinterpret_cast<const BlockWork *>(c->arena + D.off_work);
-        if (c->opt_exact == 1)
-            hipLaunchKernelGGL((k_levels_tail<true, false>), dim3(last - first), dim3(256), P.tail_lds, c->stream, k1, items, item_level, wgs, k2, dwork, T);
-        else if (c->opt_exact == 2)
-            hipLaunchKernelGGL((k_levels_tail<false, false>), dim3(last - first), dim3(256), P.tail_lds, c->stream, k1, items, item_level, wgs, k2, dwork, T);
-        else
-            hipLaunchKernelGGL((k_levels_tail<false, true>), dim3(last - first), dim3(256), P.tail_lds, c->stream, k1, items, item_level, wgs, k2, dwork, T);
+        const dim3 grid(last - first);
+        if (c->opt_meter) {
+            if (c->opt_exact == 1)
+                hipLaunchKernelGGL((k_levels_tail<true, false, true>), grid, dim3(256), P.tail_lds, c->stream, k1, items, item_level, wgs, k2, dwork, T);
+            else if (c->opt_exact == 2)
+                hipLaunchKernelGGL((k_levels_tail<false, false, true>), grid, dim3(256), P.tail_lds, c->stream, k1, items, item_level, wgs, k2, dwork, T);
+            else
+                hipLaunchKernelGGL((k_levels_tail<false, true, true>), grid, dim3(256), P.tail_lds, c->stream, k1, items, item_level, wgs, k2, dwork, T);
+        } else if (c->opt_exact == 1) {
+            hipLaunchKernelGGL((k_levels_tail<true, false>), grid, dim3(256), P.tail_lds, c->stream, k1, items, item_level, wgs, k2, dwork, T);
+        } else if (c->opt_exact == 2) {
+            hipLaunchKernelGGL((k_levels_tail<false, false>), grid, dim3(256), P.tail_lds, c->stream, k1, items, item_level, wgs, k2, dwork, T);
+        } else {
+            hipLaunchKernelGGL((k_levels_tail<false, true>), grid, dim3(256), P.tail_lds, c->stream, k1, items, item_level, wgs, k2, dwork, T);
+        }
     }
     if (dm)
         for (const LaunchB &L : c->lb)
@@ -858,6 +904,8 @@ int sdrx_set_option(sdrx_ctx *c, const char *name, int value)
         c->opt_fuse_demod = value != 0;
     else if (!strcmp(name, "tail_in_levels"))
         c->opt_tail_in_levels = value != 0;
+    else if (!strcmp(name, "meter"))
+        c->opt_meter = value != 0;
     else
         return fail(c, SDRX_EINVAL, "unknown option '%s'", name);
     return SDRX_OK;
@@ -962,6 +1010,7 @@ struct Built { // host copies of what goes to the arena, and where
     std::vector<K1Work> all_items; // k_mix_levels: every level's items in one array ...
     std::vector<int> all_item_level, llist; // ... their levels, and the launch list over them
     std::vector<TailWg> tail_wgs;           // k_levels_tail's workgroup list (LevelPlan::tail)
+    std::vector<int> mrel4; // option meter: byte offset from the leaf's payload to the record of each k_lpf_long block (w4)
     size_t off_nco_jobs = 0;
 
     size_t place_taps(const std::vector<float> &t)
@@ -1439,9 +1488,12 @@ void build_level_plan(sdrx_ctx *c, Built &B)
     // wave (fuse_demod) have no blocks here.  One-level trees have no k_mix_levels launch to ride in (see above).
     const auto dm_launch = std::find_if(c->lb.begin(), c->lb.end(), [](const LaunchB &L) { return L.kind == KIND_DEMOD; });
     bool tail = c->opt_tail_in_levels && dm_launch != c->lb.end();
-    for (const Node &n : c->nodes)
+    for (const Node &n : c->nodes) {
         if (n.leaf && n.d.demod_usb && !n.fused_demod && n.level != c->n_levels - 1)
             tail = false;
+        if (n.fused_demod && c->opt_meter && c->opt_exact == 1) // (k_levels_tail's exact form does not meter mix items: kernels.hip)
+            tail = false;
+    }
     // LDS: four mix waves or one demodulation block per workgroup.  Where four waves' LDS would fit fewer mix waves on a CU
     // than k_mix_levels does (the fused /5 and /6 leaves: 9 KB a wave), the two-launch form stays.
     constexpr int kLdsPerCu = 160 * 1024;
@@ -1495,6 +1547,59 @@ void build_level_plan(sdrx_ctx *c, Built &B)
     P.off_wgs = B.plan.take(sizeof(TailWg) * B.tail_wgs.size());
 }
 
+// ---- option meter: the record slots behind the payloads, leaf by leaf.  A leaf's records come from exactly one kind of work
+// unit: its demodulation blocks (k_usb_demod / k_levels_tail; record = block), its k_lpf_long blocks (long low-pass; record =
+// block, placed through a table: K4Vfo has no spare field), its fused-demodulation mix items (fuse_demod) or its k_compress
+// blocks (record = block).  A mix item's record is s_first_out >> meter_shift, the shift chosen so that no two items of the
+// leaf share one; records no item writes stay zero (d_pay is zeroed at finalize), which the fold ignores.
+// byte offset from a leaf's payload to its first record
+int meter_rel(const sdrx_ctx *c, const Node &n) { return (int)(c->meter_off + 16 * (size_t)n.meter_first - n.pay_off); }
+
+void build_meter_plan(sdrx_ctx *c, Built &B)
+{
+    c->meter_off = 0;
+    c->meter_slots = 0;
+    if (!c->opt_meter)
+        return;
+    c->meter_off = align_up(B.pay, 16);
+    const int N = (int)c->nodes.size();
+    for (int i = 0; i < N; ++i) {
+        Node &n = c->nodes[(size_t)i];
+        n.meter_first = c->meter_slots;
+        n.meter_n = 0;
+        n.meter_shift = 0;
+        if (!n.leaf)
+            continue;
+        if (n.fused_demod) {
+            std::vector<int> fo;
+            for (const K1Work &w : B.works[(size_t)n.level])
+                if (w.vfo == i)
+                    fo.push_back(w.s_first_out);
+            std::sort(fo.begin(), fo.end());
+            int gap = n.d.samples_per_buffer;
+            for (size_t k = 1; k < fo.size(); ++k)
+                gap = std::min(gap, fo[k] - fo[k - 1]);
+            while (n.meter_shift < 15 && (2 << n.meter_shift) <= gap) // (15: what K2Vfo::meter_rel has room for)
+                n.meter_shift++;
+            n.meter_n = (fo.back() >> n.meter_shift) + 1;
+        } else if (!n.d.demod_usb) {
+            n.meter_n = (n.n_f + 4095) / 4096;
+        } else if (n.long_lpf) {
+            n.meter_n = (n.n_out + 255) / 256;
+        } else {
+            n.meter_n = (n.n_out + n.demod_tile - 1) / n.demod_tile;
+        }
+        c->meter_slots += n.meter_n;
+    }
+    for (const BlockWork &w : B.w4) {
+        const Node &n = c->nodes[(size_t)B.n4[(size_t)w.vfo]];
+        B.mrel4.push_back(meter_rel(c, n) + 16 * w.blk);
+    }
+    for (LaunchB &L : c->lb)
+        if (L.kind == KIND_LPF_LONG)
+            L.off_mrel = B.plan.take(sizeof(int) * B.mrel4.size());
+}
+
 // ---- allocate, zero (= the reference's zero-initialised filter state, dsp.cpp:40-49), fill the descriptors, build the NCO tables
 // the tolerance arithmetic's NCO: 1 .. 4 steps of the recurrence as ONE rotation (the stabiliser holds |v|, so a step is the
 // rotation by arg(rot) at unit modulus: oscillator.cpp:20-28), in double, stored as floats
@@ -1512,7 +1617,8 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
     c->arena_bytes = align_up(B.plan.size, 256);
     HIPCHK(c, hipMalloc(&c->arena, c->arena_bytes));
     HIPCHK(c, hipMemsetAsync(c->arena, 0, c->arena_bytes, c->stream));
-    c->pay_bytes = std::max<size_t>(B.pay, 64);
+    // (the copy length stays a multiple of 64 bytes, as the packed payloads are)
+    c->pay_bytes = std::max<size_t>(c->opt_meter ? align_up(c->meter_off + 16 * (size_t)c->meter_slots, 64) : B.pay, 64);
     for (int p = 0; p < 2; ++p) {
         HIPCHK(c, hipMalloc(&c->d_pay[p], align_up(c->pay_bytes, 16))); // (whole 16-byte units)
         HIPCHK(c, hipMemsetAsync(c->d_pay[p], 0, c->pay_bytes, c->stream));
@@ -1602,6 +1708,7 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
         k.n = n.n_out;
         k.nlpf = n.long_lpf ? 0 : (int)n.lpf.size();
         k.tile = n.demod_tile;
+        k.meter_rel = c->opt_meter ? meter_rel(c, n) | n.meter_shift : 0;
     }
     for (size_t q = 0; q < B.d4.size(); ++q) {
         Node &n = c->nodes[(size_t)B.n4[q]];
@@ -1628,6 +1735,7 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
         k.n = n.n_f;
         k.cstyle = n.d.cstyle;
         k.scalecomp = n.d.scalecomp;
+        k.meter_rel = c->opt_meter ? meter_rel(c, n) : 0;
     }
     auto up = [&](size_t off, const void *src, size_t bytes) -> hipError_t {
         return bytes ? hipMemcpyAsync(P(off), src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
@@ -1653,6 +1761,9 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
     }
     for (auto &kv : B.tap_offsets)
         HIPCHK(c, up(kv.second, kv.first.data(), kv.first.size() * sizeof(float)));
+    for (const LaunchB &L : c->lb)
+        if (c->opt_meter && L.kind == KIND_LPF_LONG)
+            HIPCHK(c, up(L.off_mrel, B.mrel4.data(), sizeof(int) * B.mrel4.size()));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // the host vectors above go out of scope
 
     // NCO tables: Oscillator::Oscillator for every node, on the device
@@ -1692,6 +1803,7 @@ int finalize_impl(sdrx_ctx *c)
         return rc;
     build_tail_work(c, B);
     build_level_plan(c, B);
+    build_meter_plan(c, B);
     if (int rc = allocate_and_upload(c, B))
         return rc;
     build_publish_order(c);
@@ -2303,6 +2415,7 @@ int wait_frame(sdrx_ctx *c, int *slot)
     HIPCHK(c, hipEventSynchronize(c->ev_copied[p]));
     c->in_flight--;
     c->host_slot = p;
+    c->host_frame = f;
     if (c->in_flight == 0)
         drain_events(c);
     *slot = p;
@@ -2353,6 +2466,7 @@ int sdrx_fetch(sdrx_ctx *c)
     if (rc)
         return rc;
     c->pending_fetch = false;
+    c->host_frame = c->frame_no - 1;
     publish_all(c, p);
     return SDRX_OK;
 }
@@ -2400,6 +2514,58 @@ int sdrx_get_output(sdrx_ctx *c, int id, const void **buf, uint32_t *len, uint32
         *len = n.pay_len;
     if (rate)
         *rate = n.rate;
+    return SDRX_OK;
+}
+
+int sdrx_get_meters(sdrx_ctx *c, const int *ids, int n, sdrx_meter *out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_meters before sdrx_finalize");
+    if (!c->opt_meter)
+        return fail(c, SDRX_ESTATE, "sdrx_get_meters: option \"meter\" is off");
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return fail(c, SDRX_EINVAL, "sdrx_get_meters: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
+    for (int k = 0; k < n; ++k) {
+        if (ids[k] < 0 || ids[k] >= (int)c->nodes.size())
+            return fail(c, SDRX_EINVAL, "bad vfo id %d", ids[k]);
+        if (!c->nodes[(size_t)ids[k]].leaf)
+            return fail(c, SDRX_EINVAL, "vfo %d has children and publishes nothing: it has no meter", ids[k]);
+    }
+    if (n == 0)
+        return SDRX_OK;
+    if (c->in_flight > 0 && c->host_slot < 0)
+        return fail(c, SDRX_ESTATE, "sdrx_get_meters: %d submitted frame(s), none delivered yet -- call sdrx_wait first", c->in_flight);
+    if (c->pending_fetch) { // frames queued with sdrx_process_device: bring the last one's payloads (and records) over
+        int rc = sdrx_fetch(c);
+        if (rc)
+            return rc;
+    }
+    if (c->host_slot < 0)
+        return fail(c, SDRX_ESTATE, "sdrx_get_meters: no frame has been delivered yet");
+    const unsigned char *rec = c->h_pay[c->host_slot] + c->meter_off;
+    for (int k = 0; k < n; ++k) {
+        const Node &nd = c->nodes[(size_t)ids[k]];
+        sdrx_meter m;
+        memset(&m, 0, sizeof m);
+        m.frame = (int64_t)c->host_frame;
+        m.n_values = (uint32_t)(nd.d.demod_usb ? nd.n_out : 2 * nd.n_f);
+        uint32_t peak = 0;
+        for (int j = 0; j < nd.meter_n; ++j) { // {sum_sq u64, clipped u32, peak u32} per slot
+            const unsigned char *r = rec + 16 * (size_t)(nd.meter_first + j);
+            uint64_t sum;
+            uint32_t clipped, pk;
+            memcpy(&sum, r, 8);
+            memcpy(&clipped, r + 8, 4);
+            memcpy(&pk, r + 12, 4);
+            m.sum_sq += sum;
+            m.clipped += clipped;
+            peak = std::max(peak, pk); // magnitudes as bits: the max of the bits is the max, a NaN wins
+        }
+        memcpy(&m.peak, &peak, 4);
+        out[k] = m;
+    }
     return SDRX_OK;
 }
 

@@ -128,7 +128,9 @@ struct K2Vfo {
     float gain;
     int H, n, nlpf;
     int tile;               // outputs per block: 1024, or 1024 - E with the low-pass (E = nlpf rounded up to even)
-    int pad_;
+    int meter_rel;          // option meter: byte offset from pay[par] to this leaf's first output-meter record (a multiple of 16); a
+                            //   leaf that demodulates in its mix wave keeps s in the low 4 bits: its item from input sample
+                            //   s_first_out writes record s_first_out >> s
     float *usb_out[2];      // a low-pass longer than kMaxFir: the unfiltered usb floats go here per frame parity
                             //   (behind that stream's history) and k_lpf_long does the rest; else null
     const float *hnz_e, *hnz_o; // the same taps for the packed MACs of the non-exact arithmetics (hilbert4_packed): hnz_e[m] = h[m-3],
@@ -143,7 +145,7 @@ struct K3Vfo {
     const float2 *s[2];
     signed char *pay[2];    // per frame parity
     int n, cstyle, scalecomp;
-    int pad_;
+    int meter_rel;          // option meter: byte offset from pay[par] to this leaf's first output-meter record (one per block)
 };
 
 // ---- audio low-pass of more than kMaxFir taps (FIR::FIRUpdateAndProcess, dsp.cpp:59-71) + int16 --------

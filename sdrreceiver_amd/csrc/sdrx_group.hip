@@ -557,6 +557,26 @@ int sdrx_group_get_output(sdrx_group *g, int id, const void **buf, uint32_t *len
     return rc ? member_fail(g, w.first, rc) : SDRX_OK;
 }
 
+int sdrx_group_get_meters(sdrx_group *g, const int *ids, int n, sdrx_meter *out)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_meters before sdrx_group_finalize");
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return gfail(g, SDRX_EINVAL, "sdrx_group_get_meters: n = %d", n);
+    for (int k = 0; k < n; ++k) // the whole list first: nothing is written for a bad one
+        if (ids[k] < 0 || ids[k] >= (int)g->descs.size() || g->where[(size_t)ids[k]].first < 0)
+            return gfail(g, SDRX_EINVAL, "bad vfo id %d", ids[k]);
+    for (int k = 0; k < n; ++k) {
+        const auto w = g->where[(size_t)ids[k]];
+        const int rc = sdrx_get_meters(g->m[(size_t)w.first].c, &w.second, 1, out + k);
+        if (rc)
+            return member_fail(g, w.first, rc);
+    }
+    return SDRX_OK;
+}
+
 // Which member holds VFO `id` -- the owner of a leaf or sub VFO, the first replica of a VFO with
 // children -- and its LOCAL id inside that member's context (sdrx_group_member), for sdrx_get_stream,
 // sdrx_get_stats, kernel timing ...

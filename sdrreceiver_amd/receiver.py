@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib
+from . import _lib, meter
 from .topology import Topology, VfoDesc
 
 
@@ -53,7 +53,7 @@ class Receiver:
                  dc_blocked_scan: bool = False, pipeline: bool = False, fuse: bool = True, frame_pipeline: bool = True,
                  fuse_late: bool = True, keep_streams: bool = False, dc_speculative: bool = True,
                  dc_blocks_per_step: int | None = None, fuse_demod: bool = False,
-                 tail_in_levels: bool = True):
+                 tail_in_levels: bool = True, meter: bool = False):
         self.L = _lib.lib()
         h = C.c_void_p()
         rc = self.L.sdrx_create(C.byref(h), int(device))
@@ -75,6 +75,7 @@ class Receiver:
         self._chk(self.L.sdrx_set_option(self.h, b"keep_streams", int(bool(keep_streams))))
         self._chk(self.L.sdrx_set_option(self.h, b"fuse_demod", int(bool(fuse_demod))))
         self._chk(self.L.sdrx_set_option(self.h, b"tail_in_levels", int(bool(tail_in_levels))))
+        self._chk(self.L.sdrx_set_option(self.h, b"meter", int(bool(meter))))
         self._chk(self.L.sdrx_set_option(self.h, b"dc_speculative", int(bool(dc_speculative))))
         if dc_blocks_per_step is not None:
             self._chk(self.L.sdrx_set_option(self.h, b"dc_blocks_per_step", int(dc_blocks_per_step)))
@@ -206,6 +207,14 @@ class Receiver:
         self._chk(self.L.sdrx_get_output(self.h, vid, C.byref(buf), C.byref(ln), C.byref(rate)))
         raw = C.string_at(buf.value, ln.value)
         return np.frombuffer(raw, dtype=np.int16 if self.descs[vid].demod_usb else np.int8).copy()
+
+    def meters(self, vids) -> dict:
+        """Output meters of the leaves `vids` for the last delivered frame (option ``meter``): arrays in the order of
+        `vids` -- see :func:`sdrreceiver_amd.meter.meters_dict`."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        out = (_lib.MeterC * max(1, ids.size))()
+        self._chk(self.L.sdrx_get_meters(self.h, ids.ctypes.data, ids.size, out))
+        return meter.meters_dict(out[:ids.size], [self.descs[i].demod_usb for i in ids.tolist()])
 
     def output_rate(self, vid: int) -> int:
         rate = C.c_uint32()
@@ -433,6 +442,13 @@ class Group:
         self._chk(self.L.sdrx_group_get_output(self.h, vid, C.byref(buf), C.byref(ln), C.byref(rate)))
         raw = C.string_at(buf.value, ln.value)
         return np.frombuffer(raw, dtype=np.int16 if self.descs[vid].demod_usb else np.int8).copy()
+
+    def meters(self, vids) -> dict:
+        """:meth:`Receiver.meters` with ids of the whole tree (group option ``meter=1``)."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        out = (_lib.MeterC * max(1, ids.size))()
+        self._chk(self.L.sdrx_group_get_meters(self.h, ids.ctypes.data, ids.size, out))
+        return meter.meters_dict(out[:ids.size], [self.descs[i].demod_usb for i in ids.tolist()])
 
     def locate(self, vid: int) -> tuple[int, int]:
         m, l = C.c_int(), C.c_int()
