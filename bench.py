@@ -3,7 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--reps R]
                     [--workload config3|flat|flat10k|config2|config4|config5|10k|64k|256k|512k]
-                    [--fast] [--full] [--budget-s S] [--no-cpu] [--no-abi] [--configs1] [--batch B]
+                    [--fast] [--full] [--no-cpu] [--no-abi] [--configs1] [--batch B]
                     [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one raw IQ frame (250 ms of signal: 384 000 cf32 at
@@ -24,16 +24,20 @@ max over ranks -- is repeated R times (default 11); `ms_per_step` and `value` ar
 repetition, min / max are in `ms_per_step_min/max`.  `--dump-outputs DIR` writes what the last timed step delivered
 (the payloads of the workload's leaves, float32 .npy files, at most 64 MB) for a comparison of two builds.
 
-Prints ONE JSON line of at most 8 KB (rank 0): the contract keys, `roofline`, `cpu_baseline`, `verified` and one compact
-row per side workload.  Everything else that is measured (the counters' VALU sub-objects, the instruction mix, the
-through-the-ABI details, the prose) goes to `bench_full.json` beside this file (and to `gpurun_out/` where that exists) and
-to stderr.  `value` = IQ MSamples/s ingested, summed over every VFO chain of every rank (the unit that scales with the
+Prints ONE JSON line of at most 8 KB (rank 0): the contract keys and, with `--full`, `roofline`, `cpu_baseline`, `verified`
+and one compact row per side workload.  Everything else that is measured (the counters' VALU sub-objects, the instruction
+mix, the through-the-ABI details, the prose) goes to `bench_full.json` beside this file and to stderr.
+`value` = IQ MSamples/s ingested, summed over every VFO chain of every rank (the unit that scales with the
 number of VFOs); `raw_iq_msps` and `vfos_at_realtime` are the other two readings of BASELINE.json's metric.
 
-Time.  The default command is held to ~30 s of wall time (`--budget-s`): the clock is warmed on a throw-away receiver, so
-the oracle that verifies the timed launch sequence replays a few hundred frames, not a thousand; the side workloads run in
-order of importance while the budget lasts (a side that did not fit says so in its row); `--full` lifts the budget and
-adds the Qt drop-in legs.
+Plain and full runs.  A plain run measures the headline and nothing else: it sets up, warms up, times the K steps R times,
+writes the outputs if `--dump-outputs` is given and prints the line.  `--full` adds everything else, after the timed
+repetitions: the oracle check of the timed launch sequence (`verified`), the event-timed kernel pass (`kernels`, `roofline`),
+the CPU baseline, the through-the-ABI and Qt drop-in legs and the side workloads (other sizes, configurations and
+arithmetics, each verified); its default is 25 repetitions, with larger oracle samples.  The fetch and the refill frame after
+every repetition (see Verifier) are done in both, so with the same `--reps` a plain and a full run hand the measured receiver
+the same frames in the same order (`--no-verify` drops them from both).  The clock is warmed on a throw-away receiver, so the
+oracle of a full run replays a few hundred frames, not a thousand.
 """
 from __future__ import annotations
 
@@ -140,10 +144,10 @@ def cpu_baseline(workload):
 class Verifier:
     """Checks WHAT WAS TIMED: the launch sequence of the timed region (sdrx_process_device back to back on the torch stream:
     one k_mix_levels launch per step, level l on frame k - l, + the leaf tail of the frame that left the last level) at the
-    benchmarked size.  After every timed repetition -- outside the region -- `checkpoint()` fetches the payloads of the frame
-    processed last (sdrx_fetch: completes what is queued, copies the payloads out) and keeps those of a seeded sample of
-    leaves (topology.sample_leaves: first / last leaf of every shard block of every main + >= 64 random ones), then queues
-    one untimed frame so that the next region starts from the same steady pipeline state.  `finish()` runs the plain-C
+    benchmarked size (--full).  After every timed repetition -- outside the region -- Job.drain fetches the payloads of the
+    frame processed last (sdrx_fetch: completes what is queued, copies the payloads out) and `keep()` takes those of a seeded
+    sample of leaves (topology.sample_leaves: first / last leaf of every shard block of every main + >= 64 random ones); then
+    Job.drain queues one untimed frame so that the next region starts from the same steady pipeline state.  `finish()` runs the plain-C
     oracle (oracle/vfo_oracle.c, the checker -- never the thing measured) over EVERY frame this receiver was handed since
     its creation, warm-up and timed frames alike, and compares at every checkpoint: exact arithmetic bit for bit, --fast
     within 1 LSB int16 / 1e-5 of max|ref| on the final cf32 stream (north_star's tolerance).  sdrj.cpp:288-294."""
@@ -155,16 +159,12 @@ class Verifier:
         self.sub, self.remap = tp.subset(job.topo, self.sample)
         self.points = []   # (frames handed over so far, {leaf: payload}, {leaf: stream} | None)
 
-    def checkpoint(self, with_streams=False):
+    def keep(self, with_streams=False):
+        """The sample's payloads of the frame Job.drain has just fetched (and their final streams)."""
         j = self.job
-        j.rx.set_publish(False)  # (a ctypes callback per leaf costs microseconds: the payloads are read through sdrx_get_output)
-        j.rx.fetch()
-        j.rx.set_publish(True)
         pay = {i: j.rx.output(i) for i in self.sample}
         st = {i: j.rx.stream(i, missing_ok=True) for i in self.sample} if with_streams else None
         self.points.append((len(j.hist), pay, st))
-        j.step(len(j.hist))     # refill the frame pipeline: untimed, and part of the history like every other frame
-        j.realign(len(j.hist))
 
     def finish(self, exact, rel_tol=1e-5):
         import numpy as np
@@ -489,17 +489,18 @@ def main():
     ap.add_argument("--arith", type=int, default=None, choices=[0, 1, 2],
                     help="option \"exact\" of the library: 1 exact (default), 0 tolerance (= --fast), 2 robust (exact NCO, FMA mixer and filters)")
     ap.add_argument("--full", action="store_true",
-                    help="no time budget: every side workload, 25 repetitions, a larger oracle sample, the Qt drop-in legs")
-    ap.add_argument("--budget-s", type=float, default=32.0,
-                    help="wall-time budget of the default command: side workloads are started only while it lasts")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-abi", action="store_true", help="skip the through-the-ABI (host buffers, PCIe both ways) leg")
+                    help="everything beyond the headline: the oracle check of the timed launch sequence, the kernel pass and roofline, "
+                         "the CPU baseline, the through-the-ABI and Qt drop-in legs, every side workload; 25 repetitions, larger "
+                         "oracle samples")
+    ap.add_argument("--no-cpu", action="store_true", help="(--full) skip the cpu_baseline leg")
+    ap.add_argument("--no-abi", action="store_true", help="(--full) skip the through-the-ABI (host buffers, PCIe both ways) leg")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the oracle check of the timed launch sequence (`verified` in the line; a profiled command skips it: "
-                         "the checkpoints add fetches and single-level launches to the kernel statistics)")
+                    help="no fetch + refill frame after each timed repetition, and (--full) no oracle check of the timed launch "
+                         "sequence (`verified` in the line; a profiled command skips it: the checkpoints add fetches and "
+                         "single-level launches to the kernel statistics)")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the side readings of the N = 1 line (north-star 10 240 subs, flat, config 4, ...): a profiled "
-                         "command must launch the kernels of ONE workload only")
+                    help="(--full) skip the side readings (north-star 10 240 subs, flat, config 4, ...; config 5 at N > 1): a "
+                         "profiled command must launch the kernels of ONE workload only")
     ap.add_argument("--no-clock-warmup", action="store_true", help="no throw-away receiver spinning the clock up before the timed regions")
     ap.add_argument("--pipeline", action="store_true", help="leaf tail on a second stream beside the next frame's levels (A/B switch; slower)")
     ap.add_argument("--no-fuse", action="store_true", help="one k_mix_decimate launch per tree level instead of k_mix_levels (A/B switch)")
@@ -519,11 +520,7 @@ def main():
     args.fast = arith != 1                                                      # (the side readings in the other arithmetics ride along with the exact line only)
     n_reps = args.reps or (25 if args.full else 11)
     user_options = {k: int(v) for k, v in (o.split("=", 1) for o in args.option)}
-    budget = float("inf") if args.full else args.budget_s
     legs = {}  # wall seconds per leg of the run (bench_full.json): where the command's time goes
-
-    def left():
-        return budget - (time.perf_counter() - t_start)
 
     class leg:
         def __init__(self, name):
@@ -705,7 +702,7 @@ def main():
             barrier()
             return allmax(time.perf_counter() - t0)
 
-        def measure(self, steps, warmup, reps, verifier=None, after_timed=None):
+        def measure(self, steps, warmup, reps, drain=False, verifier=None, after_timed=None):
             for k in range(warmup):
                 self.step(k)
             self.realign(warmup)
@@ -723,9 +720,20 @@ def main():
                 if after_timed and r == reps - 1:
                     after_timed(self)       # outside the region, before anything else is handed to the receiver
                 self.realign(steps)
-                if verifier:
-                    verifier.checkpoint()  # outside the timed region: payloads of the frame the region ended on
+                if drain and self.rx:
+                    self.drain(verifier)  # outside the timed region: payloads of the frame the region ended on
             return out
+
+        def drain(self, verifier=None, with_streams=False):
+            """Completes what is queued and copies the payloads of the frame processed last out (sdrx_fetch), lets `verifier`
+            keep its sample of them, then queues one untimed frame: the next region starts from the same steady pipeline state."""
+            self.rx.set_publish(False)  # (a ctypes callback per leaf costs microseconds: the payloads are read through sdrx_get_output)
+            self.rx.fetch()
+            self.rx.set_publish(True)
+            if verifier:
+                verifier.keep(with_streams)
+            self.step(len(self.hist))   # refill the frame pipeline: untimed, and part of the history like every other frame
+            self.realign(len(self.hist))
 
         def realign(self, steps_done):
             """Finish a partly used batch so that the next region starts at a batch boundary."""
@@ -769,23 +777,21 @@ def main():
                 dom, dom_ms = name, per_frame
         return kt, kernels, dom, frame_kernel_ms
 
-    def side_reading(key, name, exact=None, need_s=3.0, options=None):
+    def side_reading(key, name, exact=None, options=None):
         """Another workload of BASELINE.json / SURVEY.md 8d on this GPU (or the default one in the other arithmetic),
         measured the same way (clock warm-up, K steps between synchronisations, median of a few repetitions, event-timed
-        kernel pass, oracle check of the timed launch sequence): a side object of the N = 1 line.  `value` and
-        `ms_per_step` of the line stay those of the default workload.  Started only while the command's time budget lasts."""
-        if left() < need_s:
-            return {"skipped": f"time budget ({budget:g} s; --full runs it)"}
+        kernel pass, oracle check of the timed launch sequence): a side object of the N = 1 line of a --full run.  `value`
+        and `ms_per_step` of the line stay those of the default workload."""
         t_side = time.perf_counter()
         try:
             j = Job(name, exact, options)
-            sv = Verifier(j, n_random=32 if args.full else 0) if (j.rx and not args.no_verify) else None
-            sreps = j.measure(args.steps, args.warmup, 5 if args.full else 3, sv)
+            sv = Verifier(j, n_random=32) if (j.rx and not args.no_verify) else None
+            sreps = j.measure(args.steps, args.warmup, 5, not args.no_verify, sv)
             sdt = statistics.median(sreps)
             ks = min(args.steps, 12)
             skt, skern, sdom, sfk = kernel_pass(j, ks)
             if sv:
-                sv.checkpoint(with_streams=True)
+                j.drain(sv, with_streams=True)
             fsec = j.full.frame / j.full.fs
             o = {"workload": j.descr, "arithmetic": ARITH[j.exact], "sub_vfos": int(j.st["n_leaves"]), "ms_per_step": round(sdt / args.steps * 1e3, 4),
                  "ms_per_step_min": round(min(sreps) / args.steps * 1e3, 4), "ms_per_step_max": round(max(sreps) / args.steps * 1e3, 4),
@@ -815,7 +821,7 @@ def main():
     with leg("main_job_create"):
         job = Job(workload)
     topo, rx, st, full, descr = job.topo, job.rx, job.st, job.full, job.descr
-    ver = Verifier(job, n_random=64 if args.full else 32) if (rx and not args.no_verify) else None
+    ver = Verifier(job, n_random=64) if (args.full and rx and not args.no_verify) else None
     dumped = None
 
     def dump(j):
@@ -825,22 +831,25 @@ def main():
         print(f"bench: rank {rank}: {n} output arrays ({nbytes / 1e6:.1f} MB) written to {args.dump_outputs}", file=sys.stderr)
 
     with leg("main_measure"):
-        reps = job.measure(args.steps, args.warmup, max(1, n_reps), ver, dump if args.dump_outputs else None)
+        reps = job.measure(args.steps, args.warmup, max(1, n_reps), not args.no_verify, ver, dump if args.dump_outputs else None)
     dt = statistics.median(reps)
     vfo_samples, alg_bytes, n_leaves = allsum([st["vfo_samples_per_frame"], st["algorithmic_bytes_per_frame"], st["n_leaves"]])
 
+    # everything below up to the line is --full: the headline is measured
     kt_steps = min(args.steps, 20)
-    with leg("kernel_pass"):
-        kt, kernels, dom, frame_kernel_ms = kernel_pass(job, kt_steps)
+    kt, kernels, dom, frame_kernel_ms = {}, {}, None, 0.0
+    if args.full:
+        with leg("kernel_pass"):
+            kt, kernels, dom, frame_kernel_ms = kernel_pass(job, kt_steps)
     verified = None
     if ver:
         with leg("main_verify"):
-            ver.checkpoint(with_streams=True)
+            job.drain(ver, with_streams=True)
             try:  # (the oracle runs here, on the host, before the legs below put other frames through this receiver)
                 verified = ver.finish(exact=arith == 1)
             except Exception as e:
                 verified = {"ok": None, "error": f"{type(e).__name__}: {e}"}
-    if use_dist:  # every rank checks its own shard; the line reports the worst
+    if use_dist and args.full:  # every rank checks its own shard; the line reports the worst
         nbad = allsum([0.0 if (verified is None or verified.get("ok")) else 1.0])[0]
         if verified is not None and nbad:
             verified["ok"] = False
@@ -849,7 +858,7 @@ def main():
     # the reference's CPU path on this box's host cores, rank 0 at N = 1 (before the side workloads: it is part of the contract,
     # they are not)
     cpu = None
-    if world == 1 and not args.no_cpu:
+    if world == 1 and args.full and not args.no_cpu:
         with leg("cpu_baseline"):
             try:
                 cpu = cpu_baseline(workload)
@@ -858,7 +867,7 @@ def main():
 
     # third (N = 1): through the C ABI from HOST buffers -- what a Qt / C++ host sees, PCIe both ways.
     abi = None
-    if world == 1 and not args.no_abi and rx:
+    if world == 1 and args.full and not args.no_abi and rx:
         t_abi = time.perf_counter()
         n_abi = max(8, min(args.steps, 24))
         pay_mb = sum(topo.vfos[i].n_out * 2 if topo.vfos[i].demod_usb else topo.vfos[i].n_stage_out
@@ -958,34 +967,30 @@ def main():
         legs["through_abi"] = round(time.perf_counter() - t_abi, 2)
 
     side = {}
-    if world == 1 and workload == "config3" and not args.no_side:
-        # In order of importance (the time budget may cut the list short): BASELINE.json's north-star target, the same workload in
+    if world == 1 and workload == "config3" and args.full and not args.no_side:
+        # In order of importance: BASELINE.json's north-star target, the same workload in
         # the TOLERANCE arithmetic north_star allows ("within 1e-5 relative float tolerance"; option exact = 0; each checked against
         # the oracle at that tolerance), config 4, the north-star sentence read literally (10 240 flat leaves at 1.536 MS/s),
         # SURVEY.md 8d's flat variant of config 3, and BASELINE config 5's whole tree (65 536 sub VFOs) on this ONE GPU: the N = 1
-        # origin of the strong-scaling curve the N > 1 lines carry as `config5_strong`.  (key, workload, exact, seconds it needs)
-        plan = [("north_star_10k", "10k", None, 4.0)]
+        # origin of the strong-scaling curve the N > 1 lines carry as `config5_strong`.  (key, workload, exact)
+        plan = [("north_star_10k", "10k", None)]
         if not args.fast:
-            plan += [("fast_config3", "config3", 0, 2.5), ("robust_config3", "config3", 2, 2.5)]
-        plan += [("config4_256", "config4", None, 2.5), ("flat_10k", "flat10k", None, 6.0)]
+            plan += [("fast_config3", "config3", 0), ("robust_config3", "config3", 2)]
+        plan += [("config4_256", "config4", None), ("flat_10k", "flat10k", None)]
         if not args.fast:
-            plan += [("fast_10k", "10k", 0, 4.0), ("fast_config4", "config4", 0, 2.5), ("robust_10k", "10k", 2, 4.0), ("robust_config4", "config4", 2, 2.5)]
-        plan += [("flat_1024", "flat", None, 3.0), ("config5_64k_one_gpu", "64k", None, 9.0)]
-        for key, name, ex, need in plan:
-            side[key] = side_reading(key, name, exact=ex, need_s=need)
+            plan += [("fast_10k", "10k", 0), ("fast_config4", "config4", 0), ("robust_10k", "10k", 2), ("robust_config4", "config4", 2)]
+        plan += [("flat_1024", "flat", None), ("config5_64k_one_gpu", "64k", None)]
+        for key, name, ex in plan:
+            side[key] = side_reading(key, name, exact=ex)
 
     # fourth (N = 1, --full): the Qt drop-in -- `class vfo` of the reference's unmodified vfo.h over the adapter
     # (host/qt/vfo_adapter.cpp), driven like sdrj::demodData drives it, transmitData / ZmqPublisher::publish included
     if abi is not None and workload == "config3" and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libdropin_sdrx.so")):
         import subprocess
         qt = {}
-        modes = (("sync", {}), ("sync_shared_upload", {"SDRX_SHARE_UPLOAD": "1"}), ("pipelined", {"SDRX_PIPELINE": "1"})) if args.full else \
-                (("pipelined", {"SDRX_PIPELINE": "1"}), ("sync", {}))
+        modes = (("sync", {}), ("sync_shared_upload", {"SDRX_SHARE_UPLOAD": "1"}), ("pipelined", {"SDRX_PIPELINE": "1"}))
         with leg("qt_adapter"):
             for label, env in modes:
-                if left() < 4.0:
-                    qt[label + "_ms"] = None
-                    continue
                 try:
                     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "dropin_run.py"), "time", "sdrx", "1024", "12"],
                                        capture_output=True, text=True, timeout=300, env=dict(os.environ, SDRX_DEVICE=str(local), **env))
@@ -993,11 +998,11 @@ def main():
                 except Exception as e:
                     qt[label + "_ms"] = {"error": f"{type(e).__name__}: {e}"}
         qt["note"] = ("per frame: process() on both main VFOs of config 3 through the public interface of vfo.h, 1024 x (payload copy into "
-                      "transmit_usb + ZmqPublisher::publish) included; one context per main VFO; null = did not fit the time budget (--full)")
+                      "transmit_usb + ZmqPublisher::publish) included; one context per main VFO")
         abi["qt_adapter"] = qt
 
     weak, other_key = None, None
-    if world > 1 and workload in ("config3", "config5") and not args.no_side:
+    if world > 1 and workload in ("config3", "config5") and args.full and not args.no_side:
         # side reading at N > 1: the other of the two multi-GPU workloads -- BASELINE config 5 (65 536 sub VFOs in total, strong
         # scaling) next to the weak-scaled default, or the other way round with --workload config5
         other, other_key, other_scaling = (("config5", "config5_strong", "strong") if workload == "config3" else
@@ -1007,7 +1012,7 @@ def main():
         with leg("side:" + other_key):
             try:
                 wj = Job(other)
-                wreps = wj.measure(args.steps, args.warmup, 7 if args.full else 5)
+                wreps = wj.measure(args.steps, args.warmup, 7)
                 wdt = statistics.median(wreps)
                 ws, wa, wl = allsum([wj.st["vfo_samples_per_frame"], wj.st["algorithmic_bytes_per_frame"], wj.st["n_leaves"]])
                 weak = {"workload": wj.descr, "scaling": other_scaling, "ms_per_step": round(wdt / args.steps * 1e3, 4),
@@ -1054,7 +1059,8 @@ def main():
             pm = pmc_for(workload, arith)
             out["roofline"] = roofline_object(dom, kt[dom], kt_steps, frame_kernel_ms, alg_bytes, world, pm, st["mix_chunks_per_frame"],
                                               demanded_valu_per_launch(topo, arith) if world == 1 else None)
-        out["kernels"] = kernels
+        if args.full:
+            out["kernels"] = kernels
         if abi:
             out["through_abi"] = abi
             ch = abi.get("c_host") if isinstance(abi.get("c_host"), dict) else {}

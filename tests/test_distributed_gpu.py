@@ -61,9 +61,9 @@ def test_two_ranks_config5_shaped_tree():
 
 @pytest.mark.gpu
 def test_bench_four_ranks_dry_run_on_one_gpu():
-    """What the driver's SCALE run launches at N > 1 -- `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`:
-    the weak-scaled config 3 (1 024 sub VFOs per rank, mains replicated, 4 frames per broadcast) as the line's own workload and
-    the FULL config 5 (65 536 sub VFOs, 16 384 per rank: strong scaling) as its side object -- with four ranks on the one GPU of
+    """What the driver's SCALE run launches at N > 1 -- `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`,
+    here with `--full`: the weak-scaled config 3 (1 024 sub VFOs per rank, mains replicated, 4 frames per broadcast) as the line's
+    own workload and the FULL config 5 (65 536 sub VFOs, 16 384 per rank: strong scaling) as its side object -- with four ranks on the one GPU of
     the test box (SDRX_BENCH_SHARE_GPU=1: gloo instead of RCCL, numbers meaningless).  Four, not eight: together with this
     process, which has the GPU open too, eight ranks would be more processes on one shared GPU than it may serve at once.  The
     shapes, the sharding, the broadcast batching, the weak / strong bookkeeping, the self-diagnosis fields and the JSON line are
@@ -75,7 +75,7 @@ def test_bench_four_ranks_dry_run_on_one_gpu():
         port = s.getsockname()[1]
     env = dict(os.environ, SDRX_BENCH_SHARE_GPU="1", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "8", "--warmup", "2", "--reps", "2"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "8", "--warmup", "2", "--reps", "2", "--full"]
     import time
     t0 = time.perf_counter()
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
