@@ -219,6 +219,10 @@ int sdrx_set_stream(sdrx_ctx *ctx, void *hip_stream);
 #define SDRX_MAX_IN_FLIGHT 2
 int sdrx_submit(sdrx_ctx *ctx, const float *iq, int n_complex);
 int sdrx_submit_u8(sdrx_ctx *ctx, const uint8_t *iq_bytes, int n_complex, int correct_dc);
+/* sdrx_submit_device: `dev_iq` is a DEVICE pointer to n_complex cf32 on this context's device.  No host staging: the frame
+ * is read where it lies, so it must be complete in the order of the context's stream (sdrx_set_stream; the context's own
+ * stream by default: then complete already at the time of the call) and stay untouched until sdrx_wait has delivered
+ * this frame.  sdrx_get_raw returns SDRX_ESTATE after such a frame (caller-owned device memory). */
 int sdrx_submit_device(sdrx_ctx *ctx, const void *dev_iq, int n_complex);
 /* Two contexts on ONE device fed the same raw frame -- sdrj::demodData hands every main VFO the same `samples`
  * (sdrj.cpp:288-294), and a binding that keeps one context per main VFO (host/qt/vfo_adapter.cpp) would otherwise

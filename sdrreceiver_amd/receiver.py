@@ -157,6 +157,9 @@ class Receiver:
         self._chk(self.L.sdrx_submit_u8(self.h, b.ctypes.data, b.size // 2, int(bool(correct_dc))))
 
     def submit_device(self, dev_ptr: int, n_complex: int) -> None:
+        """One frame of cf32 already in this context's device memory, pipelined like :meth:`submit`.  The frame must be
+        complete in the order of the context's stream (:meth:`set_stream`; by default: complete already) and stay untouched
+        until :meth:`wait` has delivered it."""
         self._chk(self.L.sdrx_submit_device(self.h, C.c_void_p(dev_ptr), int(n_complex)))
 
     def process_shared(self, src: "Receiver") -> None:
@@ -422,6 +425,9 @@ class Group:
         return out[: 2 * n.value].view(np.complex64).copy()
 
     def submit_device(self, dev_ptr: int, n_complex: int, producer_stream: int | None = None) -> None:
+        """One frame of cf32 already on the first device, pipelined like :meth:`submit`.  The frame must be complete in the
+        order of `producer_stream` (a hipStream_t of that device, e.g. ``torch.cuda.Stream().cuda_stream``; None: complete
+        already) and stay untouched until :meth:`wait` has delivered it."""
         self._chk(self.L.sdrx_group_submit_device(self.h, C.c_void_p(dev_ptr), int(n_complex), C.c_void_p(producer_stream or 0)))
 
     def process_device(self, dev_ptr: int, n_complex: int, producer_stream: int | None = None) -> None:

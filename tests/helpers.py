@@ -73,6 +73,38 @@ def golden_topology(key):
             "compress": topo_compress_golden, "288k": topo_288k_golden}[key]()
 
 
+# ---- the sdr_25E shapes of the retune, meter and device-frame tests ------------------------------------------------------------
+def tree_1536():
+    """The sdr_25E shapes: two mains; d=5 12 k subs on main 1 (one with the 4 kHz low-pass), d=2 48 k subs on main 2 (10 kHz
+    low-pass, none, and a 1 kHz low-pass of more than 256 taps: k_lpf_long)."""
+    from sdrreceiver_amd.topology import Topology, VfoDesc
+    t = Topology(fs=1536000, frame=384000, bufsplit=4, center_frequency=1545600000, name="retune-1536")
+    m = dict(parent=-1, fs=1536000, demod_usb=False, cstyle=1, samples_per_buffer=384000)
+    t.vfos.append(VfoDesc(decimate_count=2, mixer_freq=484000.0, **m))
+    t.vfos.append(VfoDesc(decimate_count=3, mixer_freq=-496000.0, **m))
+    a = dict(parent=0, fs=384000, decimate_count=5, gain=float(np.float32(0.05)), cstyle=1, samples_per_buffer=96000)
+    t.vfos.append(VfoDesc(topic="VFO01", mixer_freq=110854.0, filter_bw=4000, **a))
+    t.vfos.append(VfoDesc(topic="VFO06", mixer_freq=-3063.0, **a))
+    b = dict(parent=1, fs=192000, decimate_count=2, gain=float(np.float32(0.03)), cstyle=1, samples_per_buffer=48000)
+    t.vfos.append(VfoDesc(topic="VFO19", mixer_freq=-41300.0, filter_bw=10000, **b))
+    t.vfos.append(VfoDesc(topic="VFO16", mixer_freq=11400.0, **b))
+    t.vfos.append(VfoDesc(topic="VFO25", mixer_freq=-61500.0, filter_bw=1000, **b))
+    return t
+
+
+def tree_mixed():
+    """tree_1536 (d=5 and d=2 USB subs, the 10 kHz low-pass, a 1 kHz low-pass of more than 256 taps:
+    k_lpf_long) plus two childless mains: compress() with cstyle 0 / scalecomp 1 and cstyle 1 / scalecomp 4."""
+    from sdrreceiver_amd.topology import VfoDesc
+    t = tree_1536()
+    t.name = "meter-1536"
+    t.vfos.append(VfoDesc(topic="IQ0", parent=-1, fs=1536000, decimate_count=4, mixer_freq=200000.0, demod_usb=False,
+                          cstyle=0, scalecomp=1, samples_per_buffer=384000))
+    t.vfos.append(VfoDesc(topic="IQ1", parent=-1, fs=1536000, decimate_count=3, mixer_freq=-300000.0, demod_usb=False,
+                          cstyle=1, scalecomp=4, samples_per_buffer=384000))
+    return t
+
+
 # ---- the reference AS SHIPPED (-Ofast, SDRReceiver.pro:74-75): tests/golden/ofast_*.npz ------------------------------
 OFAST_FIXTURES = {"ofast_config1.npz": "config1", "ofast_profile_25e.npz": "profile_25e", "ofast_54w.npz": "54w"}
 OFAST_REL_TOL = 1e-5  # north_star: "within 1e-5 relative float tolerance"

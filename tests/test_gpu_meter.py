@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from sdrreceiver_amd import _lib, meter, synth, topology as tp
-from sdrreceiver_amd.topology import Topology, VfoDesc
+from helpers import tree_mixed
 
 pytestmark = pytest.mark.gpu
 
@@ -16,27 +16,6 @@ N_FRAMES = 3
 def R():
     from sdrreceiver_amd.receiver import Receiver
     return Receiver
-
-
-def tree_mixed() -> Topology:
-    """tree_1536 of test_gpu_retune.py (d=5 and d=2 USB subs, the 10 kHz low-pass, a 1 kHz low-pass of more than 256 taps:
-    k_lpf_long) plus two childless mains: compress() with cstyle 0 / scalecomp 1 and cstyle 1 / scalecomp 4."""
-    t = Topology(fs=1536000, frame=384000, bufsplit=4, center_frequency=1545600000, name="meter-1536")
-    m = dict(parent=-1, fs=1536000, demod_usb=False, cstyle=1, samples_per_buffer=384000)
-    t.vfos.append(VfoDesc(decimate_count=2, mixer_freq=484000.0, **m))
-    t.vfos.append(VfoDesc(decimate_count=3, mixer_freq=-496000.0, **m))
-    a = dict(parent=0, fs=384000, decimate_count=5, gain=float(np.float32(0.05)), cstyle=1, samples_per_buffer=96000)
-    t.vfos.append(VfoDesc(topic="VFO01", mixer_freq=110854.0, filter_bw=4000, **a))
-    t.vfos.append(VfoDesc(topic="VFO06", mixer_freq=-3063.0, **a))
-    b = dict(parent=1, fs=192000, decimate_count=2, gain=float(np.float32(0.03)), cstyle=1, samples_per_buffer=48000)
-    t.vfos.append(VfoDesc(topic="VFO19", mixer_freq=-41300.0, filter_bw=10000, **b))
-    t.vfos.append(VfoDesc(topic="VFO16", mixer_freq=11400.0, **b))
-    t.vfos.append(VfoDesc(topic="VFO25", mixer_freq=-61500.0, filter_bw=1000, **b))
-    t.vfos.append(VfoDesc(topic="IQ0", parent=-1, fs=1536000, decimate_count=4, mixer_freq=200000.0, demod_usb=False,
-                          cstyle=0, scalecomp=1, samples_per_buffer=384000))
-    t.vfos.append(VfoDesc(topic="IQ1", parent=-1, fs=1536000, decimate_count=3, mixer_freq=-300000.0, demod_usb=False,
-                          cstyle=1, scalecomp=4, samples_per_buffer=384000))
-    return t
 
 
 TREES = {"config3": lambda: tp.config3(1024), "config4": lambda: tp.config4(256), "mixed": tree_mixed}

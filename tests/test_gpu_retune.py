@@ -14,6 +14,7 @@ import retune_ref as rr
 from oracle import binding as ob
 from sdrreceiver_amd import _lib, synth, topology as tp
 from sdrreceiver_amd.topology import Topology, VfoDesc
+from helpers import tree_1536
 
 pytestmark = pytest.mark.gpu
 
@@ -22,23 +23,6 @@ N_FRAMES = 6
 
 def _bits(a):
     return np.ascontiguousarray(a).view(np.uint8)
-
-
-def tree_1536() -> Topology:
-    """The sdr_25E shapes: two mains; d=5 12 k subs on main 1 (one with the 4 kHz low-pass), d=2 48 k subs on main 2 (10 kHz
-    low-pass, none, and a 1 kHz low-pass of more than 256 taps: k_lpf_long)."""
-    t = Topology(fs=1536000, frame=384000, bufsplit=4, center_frequency=1545600000, name="retune-1536")
-    m = dict(parent=-1, fs=1536000, demod_usb=False, cstyle=1, samples_per_buffer=384000)
-    t.vfos.append(VfoDesc(decimate_count=2, mixer_freq=484000.0, **m))
-    t.vfos.append(VfoDesc(decimate_count=3, mixer_freq=-496000.0, **m))
-    a = dict(parent=0, fs=384000, decimate_count=5, gain=float(np.float32(0.05)), cstyle=1, samples_per_buffer=96000)
-    t.vfos.append(VfoDesc(topic="VFO01", mixer_freq=110854.0, filter_bw=4000, **a))
-    t.vfos.append(VfoDesc(topic="VFO06", mixer_freq=-3063.0, **a))
-    b = dict(parent=1, fs=192000, decimate_count=2, gain=float(np.float32(0.03)), cstyle=1, samples_per_buffer=48000)
-    t.vfos.append(VfoDesc(topic="VFO19", mixer_freq=-41300.0, filter_bw=10000, **b))
-    t.vfos.append(VfoDesc(topic="VFO16", mixer_freq=11400.0, **b))
-    t.vfos.append(VfoDesc(topic="VFO25", mixer_freq=-61500.0, filter_bw=1000, **b))
-    return t
 
 
 def tree_1920() -> Topology:
