@@ -179,6 +179,17 @@ public:
     }
     sdrx_ctx *context() { return ctx_; }
     sdrx_group *group() { return grp_; }
+    // Squelch-gated egress (library option "squelch" = 1, no counterpart in the reference): leaf ids[k] -- vfo::id after
+    // start() -- opens when its meter sum_sq reaches thr_sum_sq[k] and stays open hang_frames[k] frames; between two frames.
+    void set_squelch(const std::vector<int> &ids, const std::vector<uint64_t> &thr_sum_sq, const std::vector<uint32_t> &hang_frames)
+    {
+        if (ids.size() != thr_sum_sq.size() || ids.size() != hang_frames.size())
+            throw std::invalid_argument("set_squelch: lists of different length");
+        if (grp_)
+            check(sdrx_group_set_squelch(grp_, ids.data(), thr_sum_sq.data(), hang_frames.data(), (int)ids.size()), "sdrx_group_set_squelch");
+        else
+            check(sdrx_set_squelch(ctx_, ids.data(), thr_sum_sq.data(), hang_frames.data(), (int)ids.size()), "sdrx_set_squelch");
+    }
 
 private:
     bool started() const { return ctx_ || grp_; }

@@ -141,6 +141,10 @@ int sdrx_add_vfo(sdrx_ctx *ctx, const sdrx_vfo_desc *desc, int *id_out);
  *            compare every stream of the tree).
  *   "meter" 0 (default) | 1: with 1 every leaf also reports an output meter per frame (sdrx_get_meters).  0 changes
  *            nothing: same kernels, same launches, same device_bytes.  Payloads are bit-identical either way.
+ *   "squelch" 0 (default) | 1: squelch-gated egress (sdrx_set_squelch below); 1 implies "meter".  0 changes nothing.  With 1
+ *            and every threshold 0 (the start) every payload and callback is what it is with 0; sdrx_get_output of a leaf that
+ *            was closed in the delivered frame gives SDRX_OK, *len_bytes = 0, *rate as always and a non-NULL *buf that is not to
+ *            be read, and the publish callback is not invoked for it (the rule for an empty payload).
  *   "dc_blocked_scan" 0|1 (default 0): how sdrx_process_u8 removes the DC bias.  0 = the
  *                 reference's sequentially rounded fp32 recurrence, bit for bit (below).  1 = the same linear filter as a
  *                 blocked parallel scan (~15 us): the true IIR response.  The reference's recurrence
@@ -269,6 +273,31 @@ typedef struct sdrx_meter {
     uint32_t reserved;
 } sdrx_meter;
 int sdrx_get_meters(sdrx_ctx *ctx, const int *ids, int n, sdrx_meter *out);
+/* Squelch-gated egress (option "squelch" = 1): every leaf has a threshold thr_sum_sq in units of its meter's sum_sq (0 = always
+ * open: the default), a hang time in frames and a state hang_left (0 after sdrx_finalize).  For every frame the context
+ * processes, on whichever path, with s = the leaf's meter sum_sq of that frame, decided on the device in integers:
+ *     if s >= thr: open, hang_left = hang_frames;  else if hang_left > 0: open, hang_left -= 1;  else closed.
+ * The open leaves' payloads are packed into one dense device buffer, and only those bytes are copied to the host (plus a part
+ * of fixed size: the meter records of EVERY leaf -- sdrx_get_meters answers for closed leaves too, which is how a threshold is
+ * chosen -- and the gate's directory).  The reference has no squelch (vfo.cpp:426-453 publishes every leaf every frame).
+ * sdrx_set_squelch: batched and atomic like sdrx_set_gains -- the whole list is checked first; a bad, duplicate or non-leaf id
+ * or n < 0 is SDRX_EINVAL with nothing changed; n == 0 does nothing; SDRX_ESTATE before sdrx_finalize, with the option off and
+ * while submitted frames are undelivered; frames the software pipeline of sdrx_process_device still holds run to their end with
+ * the old values first.  It resets hang_left of the named leaves to 0.  One small upload and one small launch per call.
+ * sdrx_get_squelch: the state after the last DELIVERED frame (the one sdrx_get_output serves); calling rules of
+ * sdrx_get_meters.
+ * sdrx_get_egress: what the payload copy of the last delivered frame moved -- payload bytes only; the part of fixed size is
+ * not counted.  Host bookkeeping (with the option off: every leaf, the whole payload region).  Each pointer may be NULL. */
+typedef struct sdrx_squelch_state {
+    int64_t frame;       /* the frame this state follows */
+    uint64_t thr_sum_sq; /* as set */
+    uint32_t hang_frames, hang_left;
+    int32_t open;        /* 1: the leaf's payload of that frame was copied out and published */
+    uint32_t reserved;
+} sdrx_squelch_state;
+int sdrx_set_squelch(sdrx_ctx *ctx, const int *ids, const uint64_t *thr_sum_sq, const uint32_t *hang_frames, int n);
+int sdrx_get_squelch(sdrx_ctx *ctx, const int *ids, int n, sdrx_squelch_state *out);
+int sdrx_get_egress(sdrx_ctx *ctx, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied);
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);
@@ -404,6 +433,11 @@ int sdrx_group_set_gains(sdrx_group *grp, const int *ids, const float *gains, in
 /* sdrx_get_meters with ids of the whole tree (group option "meter" = 1): each id is answered by the member that owns the
  * leaf (sdrx_group_locate); `frame` counts the group's frames. */
 int sdrx_group_get_meters(sdrx_group *grp, const int *ids, int n, sdrx_meter *out);
+/* sdrx_set_squelch / sdrx_get_squelch with ids of the whole tree (group option "squelch" = 1), each id routed to the member
+ * that owns the leaf; sdrx_group_get_egress sums n_open, n_leaves and payload_bytes_copied over the members. */
+int sdrx_group_set_squelch(sdrx_group *grp, const int *ids, const uint64_t *thr_sum_sq, const uint32_t *hang_frames, int n);
+int sdrx_group_get_squelch(sdrx_group *grp, const int *ids, int n, sdrx_squelch_state *out);
+int sdrx_group_get_egress(sdrx_group *grp, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied);
 
 /* ---- introspection / measurement ------------------------------------------------------------- */
 typedef struct sdrx_stats {

@@ -56,7 +56,13 @@ class MeterC(C.Structure):
                 ("peak", C.c_float), ("reserved", C.c_uint32)]
 
 
-PUBLISH_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
+class SquelchStateC(C.Structure):
+    """struct sdrx_squelch_state"""
+    _fields_ = [("frame", C.c_int64), ("thr_sum_sq", C.c_uint64), ("hang_frames", C.c_uint32), ("hang_left", C.c_uint32),
+                ("open", C.c_int32), ("reserved", C.c_uint32)]
+
+
+PUBLISH_FN =C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
 
 # every symbol include/sdrx.h declares: (restype, argtypes)
 _vp, _i = C.c_void_p, C.c_int
@@ -93,6 +99,12 @@ SYMBOLS = {
     "sdrx_set_mixer_freqs": (_i, [_vp, _vp, _vp, _i]),
     "sdrx_set_gains": (_i, [_vp, _vp, _vp, _i]),
     "sdrx_get_meters": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_set_squelch": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "sdrx_get_squelch": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_get_egress": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "sdrx_group_set_squelch": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "sdrx_group_get_squelch": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_group_get_egress": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

@@ -28,6 +28,7 @@
 #include "../../include/sdrx.h"
 #include "kernels.hip"
 #include "spectrum.hip"
+#include "squelch.hip"
 #include "tapdesign.h"
 
 using namespace sdrx;
@@ -143,6 +144,26 @@ struct sdrx_ctx {
     // unit that emits payload values (kernels.hip "output meters"); the records travel in the payload copy
     size_t meter_off = 0;
     int meter_slots = 0;
+    // option squelch (squelch.hip): per frame parity the gate's directory sits behind the meter records in d_pay /
+    // h_pay (at dir_off: SqHeader | offset per leaf | hang_left per leaf, leaves in publish order) -- [meter_off, pay_bytes) is the
+    // fixed-size part that always travels -- and the open leaves' payloads are packed into d_pack[p]; the host receives them at
+    // the start of h_pay[p], whose payload region they can never outgrow.
+    int opt_squelch = 0;
+    size_t dir_off = 0, pack_bytes = 0, sq_bytes = 0; // sq_bytes: what the option allocates besides the directory
+    unsigned char *d_pack[2] = {nullptr, nullptr};
+    SqLeaf *d_sq_leaves = nullptr;
+    SqCfg *d_sq_cfg = nullptr;
+    unsigned *d_sq_hang = nullptr; // hang_left per leaf: one array, every gate runs in frame order on one stream
+    SqJob *d_sq_jobs = nullptr;
+    size_t sq_jobs_cap = 0;
+    int sq_tiles = 1;                           // k_squelch_gather's grid.y: 16 KiB tiles of the longest payload
+    std::vector<int> sq_index;                  // node -> its place in publish order (-1: not a leaf)
+    std::vector<SqCfg> sq_cfg;                  // host copy of the thresholds
+    std::vector<unsigned> sq_offs, sq_hang;     // the directory of the last DELIVERED frame
+    unsigned sq_n_open = 0;                     //   ... its header
+    unsigned long long sq_copied = 0;           //   ... and the payload bytes its copy moved
+    unsigned long long sq_copied_slot[2] = {0, 0};
+    hipEvent_t ev_dir[2] = {nullptr, nullptr};  // the fixed-size part of frame f is in h_pay[f & 1]
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first
     // frame that fills them.  The first such leaf uses the arena's buffer, further ones buffers of their own (hipMalloc).
@@ -395,6 +416,20 @@ void spectrum_raw_step(sdrx_ctx *c, const void *raw, int raw_mode)
 inline int pipeline_flush_unless(sdrx_ctx *c, bool keep) { return keep ? SDRX_OK : pipeline_flush(c); }
 void launch_block_kernel(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned long long frame, bool exact);
 
+// Option squelch: the gate of frame `frame`, on the stream -- and behind the launch -- that completed its payloads and meter
+// records: decide + scan (one workgroup), then the gather of the open leaves into d_pack[p] (squelch.hip).  Not bracketed:
+// sdrx_get_kernel_times keeps its SDRX_NKERNELS kinds.
+void squelch_gate(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
+{
+    const int n = (int)c->publish_order.size();
+    if (!c->opt_squelch || n == 0)
+        return;
+    const int p = (int)(frame & 1ull);
+    unsigned char *dir = c->d_pay[p] + c->dir_off;
+    hipLaunchKernelGGL(k_squelch_scan, dim3(1), dim3(kSqThreads), 0, ts, c->d_sq_leaves, c->d_sq_cfg, c->d_sq_hang, c->d_pay[p], dir, n, (long long)frame);
+    hipLaunchKernelGGL(k_squelch_gather, dim3(n, c->sq_tiles), dim3(256), 0, ts, c->d_sq_leaves, c->d_pay[p], dir, c->d_pack[p]);
+}
+
 // One frame: [wait for the tail of frame f-2] -> ingest -> one k_mix_decimate launch per tree level on
 // `stream`; then the leaf tail (late decimation, demodulation, compress) -- on `tail_stream` behind an
 // event when the pipeline option is on, so that it runs beside the NEXT frame's levels -- and, for a
@@ -408,6 +443,9 @@ void launch_block_kernel(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned
 //   * half-band state, NCO tables and the parents' streams are touched by the levels only;
 //   * d_pay[p] is written by the tail of f and read by the copy of f; its next writer is the tail of
 //     f+2, which the host does not submit before frame f was delivered (SDRX_MAX_IN_FLIGHT = 2).
+//   * option squelch: d_pack[p] and the directory (inside d_pay[p]) are written by the gate of f, behind its tail on the
+//     tail's stream, and read by the two copies of f (fixed part at submit, packed payloads from sdrx_wait): the same
+//     argument -- their next writer is the gate of f+2.  hang_left is one array: gates run in frame order on one stream.
 // ARITH = option "exact": 1 the exact arithmetic, 0 the tolerance arithmetic (NCO as rotations), 2 the robust one (exact NCO,
 // FMA mixer and filters) -- kernels.hip, nco_mix.
 template <int ARITH>
@@ -472,6 +510,7 @@ int enqueue_frame_as(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
     }
     for (const LaunchB &L : c->lb)
         launch_block_kernel(c, L, ts, c->frame_no, EXACT);
+    squelch_gate(c, ts, c->frame_no);
     spectrum_launch(c, ts, 0, c->n_levels - 1, c->frame_no, nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
@@ -487,7 +526,17 @@ int enqueue_frame_as(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
     // about the SUM of its parts), nor beside a copy kernel of ours (a kernel cannot retire beside one): for those frames the copy
     // is issued by sdrx_wait, when the host has seen the frame's last kernel end -- 0.34 ms per frame.  (The float path would lose
     // by that, 0.38 vs 0.30: between two waits the copy engine idles.)
-    if (egress && c->long_frame) {
+    // Option squelch: how much leaves is a device result.  Here only the fixed-size part -- meter records and directory -- is
+    // queued behind the gate; sdrx_wait reads packed_bytes from it and issues the one copy of the packed payloads (the owed-copy
+    // form, whatever kind of frame this is).
+    if (egress && c->opt_squelch) {
+        hipStream_t cs = p ? c->copy_stream2 : c->copy_stream;
+        HIPCHK(c, hipStreamWaitEvent(cs, c->ev_tail[p], 0));
+        HIPCHK(c, hipMemcpyAsync(c->h_pay[p] + c->meter_off, c->d_pay[p] + c->meter_off, c->pay_bytes - c->meter_off, hipMemcpyDeviceToHost, cs));
+        HIPCHK(c, hipEventRecord(c->ev_dir[p], cs));
+        c->copy_owed[p] = true;
+        c->in_flight++;
+    } else if (egress && c->long_frame) {
         c->copy_owed[p] = true;
         c->in_flight++;
     } else if (egress) {
@@ -651,6 +700,8 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
         for (const LaunchB &L : c->lb)
             if (L.kind == KIND_LPF_LONG)
                 launch_block_kernel(c, L, c->stream, f_dm, c->opt_exact == 1);
+    if (dm) // that launch completed frame f_dm's payloads and records: its gate
+        squelch_gate(c, c->stream, f_dm);
     if (hi >= 0)
         spectrum_launch(c, c->stream, lo, hi, 0, A.frame_level);
     if (dm)
@@ -662,8 +713,10 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
         for (const LaunchB &L : c->lb)
             if (!P.tail || (L.kind != KIND_DEMOD && L.kind != KIND_LPF_LONG))
                 launch_block_kernel(c, L, c->stream, f, c->opt_exact == 1);
-        if (!P.tail)
+        if (!P.tail) {
+            squelch_gate(c, c->stream, f);
             c->pipe.erase(c->pipe.begin());
+        }
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
@@ -695,6 +748,22 @@ int drain(sdrx_ctx *c)
     return SDRX_OK;
 }
 
+// Leaf `id`'s payload of the delivered frame in host slot `slot`.  Option squelch: through the delivered directory -- a closed
+// leaf has *len = 0 (the pointer is valid and not to be read).
+const unsigned char *leaf_payload(const sdrx_ctx *c, int id, int slot, uint32_t *len)
+{
+    const Node &n = c->nodes[(size_t)id];
+    *len = n.pay_len;
+    if (!c->opt_squelch)
+        return c->h_pay[slot] + n.pay_off;
+    const unsigned off = c->sq_offs[(size_t)c->sq_index[(size_t)id]];
+    if (off == kSqClosed) {
+        *len = 0;
+        return c->h_pay[slot];
+    }
+    return c->h_pay[slot] + 64 * (size_t)off;
+}
+
 // vfo::transmitData for every leaf, in the reference's order (vfo.cpp:426-453, sdrj.cpp:288-294)
 void publish_all(sdrx_ctx *c, int slot)
 {
@@ -704,15 +773,17 @@ void publish_all(sdrx_ctx *c, int slot)
     for (int i : c->publish_order) {
         const Node &n = c->nodes[(size_t)i];
         // USB leaves always publish; an IQ leaf only with a topic; ZmqPublisher::publish sends
-        // nothing for len 0 (zmqpublisher.cpp:88).
-        if (n.pay_len == 0)
+        // nothing for len 0 (zmqpublisher.cpp:88) -- which is also what a leaf closed by option squelch has.
+        uint32_t len = 0;
+        const unsigned char *pay = leaf_payload(c, i, slot, &len);
+        if (len == 0)
             continue;
         if (!n.d.demod_usb && n.d.topic[0] == 0)
             continue;
         char topic[5] = {0, 0, 0, 0, 0};
         for (int k = 0; k < 5 && n.d.topic[k]; ++k)
             topic[k] = n.d.topic[k];
-        c->cb(c->cb_user, topic, n.rate, c->h_pay[slot] + n.pay_off, n.pay_len);
+        c->cb(c->cb_user, topic, n.rate, pay, len);
     }
 }
 
@@ -759,6 +830,14 @@ void free_device_state(sdrx_ctx *c)
     dfree(c->d_spec_desc);
     dfree(c->d_jobs);
     c->jobs_cap = 0;
+    for (int p = 0; p < 2; ++p)
+        dfree(c->d_pack[p]);
+    dfree(c->d_sq_leaves);
+    dfree(c->d_sq_cfg);
+    dfree(c->d_sq_hang);
+    dfree(c->d_sq_jobs);
+    c->sq_jobs_cap = 0;
+    c->sq_bytes = 0;
     c->spec_n_desc = 0;
     c->spec_raw_on = false;
 }
@@ -858,7 +937,7 @@ int sdrx_destroy(sdrx_ctx *c)
         for (const auto &r : *v)
             (void)hipEventDestroy(r.ev);
     for (int p = 0; p < 2; ++p)
-        for (hipEvent_t e : {c->ev_levels[p], c->ev_tail[p], c->ev_copied[p], c->ev_staged[p]})
+        for (hipEvent_t e : {c->ev_levels[p], c->ev_tail[p], c->ev_copied[p], c->ev_staged[p], c->ev_dir[p]})
             if (e)
                 (void)hipEventDestroy(e);
     free_device_state(c);
@@ -906,6 +985,8 @@ int sdrx_set_option(sdrx_ctx *c, const char *name, int value)
         c->opt_tail_in_levels = value != 0;
     else if (!strcmp(name, "meter"))
         c->opt_meter = value != 0;
+    else if (!strcmp(name, "squelch"))
+        c->opt_squelch = value != 0;
     else
         return fail(c, SDRX_EINVAL, "unknown option '%s'", name);
     return SDRX_OK;
@@ -1619,6 +1700,14 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
     HIPCHK(c, hipMemsetAsync(c->arena, 0, c->arena_bytes, c->stream));
     // (the copy length stays a multiple of 64 bytes, as the packed payloads are)
     c->pay_bytes = std::max<size_t>(c->opt_meter ? align_up(c->meter_off + 16 * (size_t)c->meter_slots, 64) : B.pay, 64);
+    if (c->opt_squelch) { // the directory behind the records: one fixed-size copy brings both
+        size_t n_leaves = 0;
+        for (const Node &n : c->nodes)
+            n_leaves += n.leaf;
+        c->dir_off = c->pay_bytes;
+        c->pay_bytes = align_up(c->dir_off + sizeof(SqHeader) + 8 * n_leaves, 64);
+        c->pack_bytes = std::max<size_t>(align_up(B.pay, 64), 64);
+    }
     for (int p = 0; p < 2; ++p) {
         HIPCHK(c, hipMalloc(&c->d_pay[p], align_up(c->pay_bytes, 16))); // (whole 16-byte units)
         HIPCHK(c, hipMemsetAsync(c->d_pay[p], 0, c->pay_bytes, c->stream));
@@ -1793,6 +1882,49 @@ void build_publish_order(sdrx_ctx *c)
     }
 }
 
+// ---- option squelch: the per-leaf descriptors in publish order, thresholds 0 (always open), hang_left 0, the packed buffers
+int squelch_setup(sdrx_ctx *c)
+{
+    if (!c->opt_squelch)
+        return SDRX_OK;
+    const size_t n = c->publish_order.size();
+    if (n > (size_t)kSqMaxLeaves)
+        return fail(c, SDRX_EUNSUPPORTED, "option squelch: %zu leaves, the gate handles %d", n, kSqMaxLeaves);
+    c->sq_index.assign(c->nodes.size(), -1);
+    std::vector<SqLeaf> leaves(n);
+    size_t longest = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const Node &nd = c->nodes[(size_t)c->publish_order[k]];
+        c->sq_index[(size_t)c->publish_order[k]] = (int)k;
+        SqLeaf &L = leaves[k];
+        L.pay_off = (unsigned)nd.pay_off;
+        L.pay_units = (unsigned)(align_up(nd.pay_len, 64) / 64);
+        L.meter_off = (unsigned)(c->meter_off + 16 * (size_t)nd.meter_first);
+        L.meter_n = (unsigned)nd.meter_n;
+        longest = std::max(longest, align_up(nd.pay_len, 64));
+    }
+    c->sq_tiles = (int)std::max<size_t>((longest + kSqTile - 1) / kSqTile, 1);
+    c->sq_cfg.assign(n, SqCfg{0, 0, 0});
+    c->sq_offs.assign(n, 0);
+    c->sq_hang.assign(n, 0);
+    const size_t n1 = std::max<size_t>(n, 1);
+    HIPCHK(c, hipMalloc(&c->d_sq_leaves, sizeof(SqLeaf) * n1));
+    HIPCHK(c, hipMalloc(&c->d_sq_cfg, sizeof(SqCfg) * n1));
+    HIPCHK(c, hipMalloc(&c->d_sq_hang, sizeof(unsigned) * n1));
+    c->sq_bytes = (sizeof(SqLeaf) + sizeof(SqCfg) + sizeof(unsigned)) * n1 + 2 * c->pack_bytes;
+    HIPCHK(c, hipMemcpyAsync(c->d_sq_leaves, leaves.data(), sizeof(SqLeaf) * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_sq_cfg, 0, sizeof(SqCfg) * n1, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_sq_hang, 0, sizeof(unsigned) * n1, c->stream));
+    for (int p = 0; p < 2; ++p) {
+        HIPCHK(c, hipMalloc(&c->d_pack[p], c->pack_bytes));
+        HIPCHK(c, hipMemsetAsync(c->d_pack[p], 0, c->pack_bytes, c->stream));
+        if (!c->ev_dir[p])
+            HIPCHK(c, hipEventCreateWithFlags(&c->ev_dir[p], hipEventDisableTiming));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (`leaves` lives on this stack)
+    return SDRX_OK;
+}
+
 int finalize_impl(sdrx_ctx *c)
 {
     if (int rc = derive_nodes(c))
@@ -1807,6 +1939,8 @@ int finalize_impl(sdrx_ctx *c)
     if (int rc = allocate_and_upload(c, B))
         return rc;
     build_publish_order(c);
+    if (int rc = squelch_setup(c))
+        return rc;
     c->taps.clear();
     c->finalized = true;
     return SDRX_OK;
@@ -1825,6 +1959,8 @@ int sdrx_finalize(sdrx_ctx *c)
     if (c->nodes.empty())
         return fail(c, SDRX_ESTATE, "sdrx_finalize: no VFOs");
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->opt_squelch) // the gate reads the meter records
+        c->opt_meter = 1;
     const int rc = finalize_impl(c);
     if (rc != SDRX_OK) { // nothing of a half-built tree stays behind: a later call starts clean
         (void)hipStreamSynchronize(c->stream);
@@ -2369,6 +2505,35 @@ int sdrx_in_flight(sdrx_ctx *c) { return c ? c->in_flight : SDRX_EINVAL; }
 namespace {
 // the oldest undelivered frame's payload copy, if sdrx_wait is the one to issue it (enqueue_frame: frames that carry the DC
 // recurrence): the host waits for the frame's last kernel, then the copy goes out with nothing to wait for
+// option squelch: packed_bytes of the directory that arrived in h_pay[p]
+int squelch_packed_bytes(sdrx_ctx *c, int p, size_t *bytes)
+{
+    SqHeader H;
+    memcpy(&H, c->h_pay[p] + c->dir_off, sizeof H);
+    if (H.packed_bytes > c->pack_bytes || H.packed_bytes % 64)
+        return fail(c, SDRX_EHIP, "squelch: the directory of frame %lld names %llu packed bytes, the buffer holds %zu", H.frame,
+                    H.packed_bytes, c->pack_bytes);
+    *bytes = (size_t)H.packed_bytes;
+    return SDRX_OK;
+}
+// ... and, once its payloads are there too, the host's copy of that directory: what sdrx_get_output, the callbacks,
+// sdrx_get_squelch and sdrx_get_egress serve until the next delivery
+void squelch_delivered(sdrx_ctx *c, int p)
+{
+    if (!c->opt_squelch)
+        return;
+    SqHeader H;
+    const unsigned char *dir = c->h_pay[p] + c->dir_off;
+    memcpy(&H, dir, sizeof H);
+    const size_t n = c->sq_offs.size();
+    if (n) {
+        memcpy(c->sq_offs.data(), dir + sizeof H, 4 * n);
+        memcpy(c->sq_hang.data(), dir + sizeof H + 4 * n, 4 * n);
+    }
+    c->sq_n_open = H.n_open;
+    c->sq_copied = c->sq_copied_slot[p];
+}
+
 int start_owed_copy(sdrx_ctx *c)
 {
     if (c->in_flight <= 0)
@@ -2378,8 +2543,18 @@ int start_owed_copy(sdrx_ctx *c)
         return SDRX_OK;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t cs = p ? c->copy_stream2 : c->copy_stream;
-    HIPCHK(c, hipEventSynchronize(c->ev_tail[p]));
-    HIPCHK(c, hipMemcpyAsync(c->h_pay[p], c->d_pay[p], c->pay_bytes, hipMemcpyDeviceToHost, cs));
+    if (c->opt_squelch) { // the directory has arrived: ONE copy of the packed payloads (none if every leaf is closed)
+        HIPCHK(c, hipEventSynchronize(c->ev_dir[p]));
+        size_t bytes = 0;
+        if (int rc = squelch_packed_bytes(c, p, &bytes))
+            return rc;
+        if (bytes)
+            HIPCHK(c, hipMemcpyAsync(c->h_pay[p], c->d_pack[p], bytes, hipMemcpyDeviceToHost, cs));
+        c->sq_copied_slot[p] = bytes;
+    } else {
+        HIPCHK(c, hipEventSynchronize(c->ev_tail[p]));
+        HIPCHK(c, hipMemcpyAsync(c->h_pay[p], c->d_pay[p], c->pay_bytes, hipMemcpyDeviceToHost, cs));
+    }
     HIPCHK(c, hipEventRecord(c->ev_copied[p], cs));
     // only now: a wait retried after one of the calls above failed must find the copy still owed -- ev_copied[p] is still the
     // event of frame f - 2, which completed long ago, and h_pay[p] still holds THAT frame's payloads
@@ -2416,6 +2591,7 @@ int wait_frame(sdrx_ctx *c, int *slot)
     c->in_flight--;
     c->host_slot = p;
     c->host_frame = f;
+    squelch_delivered(c, p);
     if (c->in_flight == 0)
         drain_events(c);
     *slot = p;
@@ -2460,11 +2636,23 @@ int sdrx_fetch(sdrx_ctx *c)
     hipStream_t ts = c->opt_pipeline ? c->tail_stream : c->stream;
     if (int rc = pipeline_flush(c)) // frames still inside the software pipeline run to their end first
         return rc;
-    if (c->pending_fetch)
+    if (c->pending_fetch && c->opt_squelch) { // the same two steps as sdrx_submit / sdrx_wait: fixed part, then the packed payloads
+        HIPCHK(c, hipMemcpyAsync(c->h_pay[p] + c->meter_off, c->d_pay[p] + c->meter_off, c->pay_bytes - c->meter_off, hipMemcpyDeviceToHost, ts));
+        HIPCHK(c, hipStreamSynchronize(ts));
+        size_t bytes = 0;
+        if (int rc = squelch_packed_bytes(c, p, &bytes))
+            return rc;
+        if (bytes)
+            HIPCHK(c, hipMemcpyAsync(c->h_pay[p], c->d_pack[p], bytes, hipMemcpyDeviceToHost, ts));
+        c->sq_copied_slot[p] = bytes;
+    } else if (c->pending_fetch) {
         HIPCHK(c, hipMemcpyAsync(c->h_pay[p], c->d_pay[p], c->pay_bytes, hipMemcpyDeviceToHost, ts));
+    }
     int rc = drain(c);
     if (rc)
         return rc;
+    if (c->pending_fetch)
+        squelch_delivered(c, p);
     c->pending_fetch = false;
     c->host_frame = c->frame_no - 1;
     publish_all(c, p);
@@ -2505,13 +2693,16 @@ int sdrx_get_output(sdrx_ctx *c, int id, const void **buf, uint32_t *len, uint32
         if (rc)
             return rc;
     }
+    uint32_t pay_len = n.pay_len;
     if (buf) {
         if (c->host_slot < 0)
             return fail(c, SDRX_ESTATE, "sdrx_get_output: no frame has been delivered yet");
-        *buf = c->h_pay[c->host_slot] + n.pay_off;
+        *buf = leaf_payload(c, id, c->host_slot, &pay_len);
+    } else if (c->opt_squelch && c->host_slot >= 0) {
+        (void)leaf_payload(c, id, c->host_slot, &pay_len);
     }
     if (len)
-        *len = n.pay_len;
+        *len = pay_len;
     if (rate)
         *rate = n.rate;
     return SDRX_OK;
@@ -2566,6 +2757,118 @@ int sdrx_get_meters(sdrx_ctx *c, const int *ids, int n, sdrx_meter *out)
         memcpy(&m.peak, &peak, 4);
         out[k] = m;
     }
+    return SDRX_OK;
+}
+
+// The whole list is checked before anything changes; then the software pipeline runs out with the old values, one upload of
+// the job list, one k_squelch_set launch.
+int sdrx_set_squelch(sdrx_ctx *c, const int *ids, const uint64_t *thr, const uint32_t *hang_frames, int n)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_set_squelch before sdrx_finalize");
+    if (!c->opt_squelch)
+        return fail(c, SDRX_ESTATE, "sdrx_set_squelch: option \"squelch\" is off");
+    if (n < 0 || (n > 0 && (!ids || !thr || !hang_frames)))
+        return fail(c, SDRX_EINVAL, "sdrx_set_squelch: n = %d, ids %p, thresholds %p, hang times %p", n, (const void *)ids, (const void *)thr,
+                    (const void *)hang_frames);
+    std::vector<char> seen(c->nodes.size(), 0);
+    for (int k = 0; k < n; ++k) {
+        if (ids[k] < 0 || ids[k] >= (int)c->nodes.size())
+            return fail(c, SDRX_EINVAL, "sdrx_set_squelch: bad vfo id %d", ids[k]);
+        if (!c->nodes[(size_t)ids[k]].leaf)
+            return fail(c, SDRX_EINVAL, "sdrx_set_squelch: vfo %d has children and publishes nothing", ids[k]);
+        if (seen[(size_t)ids[k]]++)
+            return fail(c, SDRX_EINVAL, "sdrx_set_squelch: vfo %d listed twice", ids[k]);
+    }
+    if (c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "sdrx_set_squelch: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+    if (n == 0)
+        return SDRX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c))
+        return rc;
+    std::vector<SqJob> jobs((size_t)n);
+    for (int k = 0; k < n; ++k)
+        jobs[(size_t)k] = SqJob{thr[k], hang_frames[k], (unsigned)c->sq_index[(size_t)ids[k]]};
+    if (jobs.size() > c->sq_jobs_cap) {
+        if (c->d_sq_jobs)
+            (void)hipFree(c->d_sq_jobs);
+        c->d_sq_jobs = nullptr;
+        c->sq_jobs_cap = 0;
+        HIPCHK(c, hipMalloc(&c->d_sq_jobs, sizeof(SqJob) * jobs.size()));
+        c->sq_jobs_cap = jobs.size();
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_sq_jobs, jobs.data(), sizeof(SqJob) * jobs.size(), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_squelch_set, dim3((n + 63) / 64), dim3(64), 0, c->stream, c->d_sq_jobs, n, c->d_sq_cfg, c->d_sq_hang);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (`jobs` lives on this stack)
+    for (const SqJob &J : jobs) {
+        c->sq_cfg[J.index] = SqCfg{J.thr, J.hang_frames, 0};
+        c->sq_hang[J.index] = 0;
+    }
+    return SDRX_OK;
+}
+
+int sdrx_get_squelch(sdrx_ctx *c, const int *ids, int n, sdrx_squelch_state *out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_squelch before sdrx_finalize");
+    if (!c->opt_squelch)
+        return fail(c, SDRX_ESTATE, "sdrx_get_squelch: option \"squelch\" is off");
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return fail(c, SDRX_EINVAL, "sdrx_get_squelch: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
+    for (int k = 0; k < n; ++k) {
+        if (ids[k] < 0 || ids[k] >= (int)c->nodes.size())
+            return fail(c, SDRX_EINVAL, "bad vfo id %d", ids[k]);
+        if (!c->nodes[(size_t)ids[k]].leaf)
+            return fail(c, SDRX_EINVAL, "vfo %d has children and publishes nothing: it has no squelch", ids[k]);
+    }
+    if (n == 0)
+        return SDRX_OK;
+    if (c->in_flight > 0 && c->host_slot < 0)
+        return fail(c, SDRX_ESTATE, "sdrx_get_squelch: %d submitted frame(s), none delivered yet -- call sdrx_wait first", c->in_flight);
+    if (c->pending_fetch) {
+        int rc = sdrx_fetch(c);
+        if (rc)
+            return rc;
+    }
+    if (c->host_slot < 0)
+        return fail(c, SDRX_ESTATE, "sdrx_get_squelch: no frame has been delivered yet");
+    for (int k = 0; k < n; ++k) {
+        const size_t i = (size_t)c->sq_index[(size_t)ids[k]];
+        sdrx_squelch_state s;
+        memset(&s, 0, sizeof s);
+        s.frame = (int64_t)c->host_frame;
+        s.thr_sum_sq = c->sq_cfg[i].thr;
+        s.hang_frames = c->sq_cfg[i].hang_frames;
+        s.hang_left = c->sq_hang[i];
+        s.open = c->sq_offs[i] != kSqClosed;
+        out[k] = s;
+    }
+    return SDRX_OK;
+}
+
+int sdrx_get_egress(sdrx_ctx *c, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_egress before sdrx_finalize");
+    if (c->host_slot < 0 || c->pending_fetch)
+        return fail(c, SDRX_ESTATE, "sdrx_get_egress: no frame has been delivered yet (sdrx_wait / sdrx_fetch first)");
+    const uint32_t leaves = (uint32_t)c->publish_order.size();
+    if (frame)
+        *frame = (int64_t)c->host_frame;
+    if (n_leaves)
+        *n_leaves = leaves;
+    if (n_open)
+        *n_open = c->opt_squelch ? c->sq_n_open : leaves;
+    if (payload_bytes_copied)
+        *payload_bytes_copied = c->opt_squelch ? c->sq_copied : (uint64_t)(c->meter_off ? c->meter_off : c->pay_bytes);
     return SDRX_OK;
 }
 
@@ -2854,7 +3157,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->exact = c->opt_exact;
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10);
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq_bytes);
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->d_dc_counters) { // (waits for what is queued: a measurement call)

@@ -189,12 +189,16 @@ void group_publish(sdrx_group *g)
         const Node &n = c->nodes[(size_t)w.second];
         if (n.pay_len == 0 || c->host_slot < 0)
             continue;
+        uint32_t len = 0; // (option squelch: 0 for a leaf closed in this frame)
+        const unsigned char *pay = leaf_payload(c, w.second, c->host_slot, &len);
+        if (len == 0)
+            continue;
         if (!n.d.demod_usb && n.d.topic[0] == 0) // vfo::transmitData: an IQ leaf publishes only with a topic
             continue;
         char topic[5] = {0, 0, 0, 0, 0};
         for (int k = 0; k < 5 && n.d.topic[k]; ++k)
             topic[k] = n.d.topic[k];
-        g->cb(g->cb_user, topic, n.rate, c->h_pay[c->host_slot] + n.pay_off, n.pay_len);
+        g->cb(g->cb_user, topic, n.rate, pay, len);
     }
 }
 
@@ -574,6 +578,105 @@ int sdrx_group_get_meters(sdrx_group *g, const int *ids, int n, sdrx_meter *out)
         if (rc)
             return member_fail(g, w.first, rc);
     }
+    return SDRX_OK;
+}
+
+// sdrx_set_squelch over the whole tree: the list is checked as a whole (a leaf has exactly one owner), then every member that
+// owns a listed leaf applies its part.
+int sdrx_group_set_squelch(sdrx_group *g, const int *ids, const uint64_t *thr, const uint32_t *hang_frames, int n)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch before sdrx_group_finalize");
+    if (n < 0 || (n > 0 && (!ids || !thr || !hang_frames)))
+        return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch: n = %d", n);
+    const size_t W = g->m.size();
+    std::vector<char> seen(g->descs.size(), 0);
+    for (int k = 0; k < n; ++k) {
+        if (ids[k] < 0 || ids[k] >= (int)g->descs.size() || g->where[(size_t)ids[k]].first < 0)
+            return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch: bad vfo id %d", ids[k]);
+        const auto w = g->where[(size_t)ids[k]];
+        if (!g->m[(size_t)w.first].c->nodes[(size_t)w.second].leaf)
+            return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch: vfo %d has children and publishes nothing", ids[k]);
+        if (seen[(size_t)ids[k]]++)
+            return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch: vfo %d listed twice", ids[k]);
+    }
+    for (size_t k = 0; k < W; ++k)
+        if (g->m[k].c && !g->m[k].c->opt_squelch)
+            return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch: option \"squelch\" is off");
+    if (g->broken)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch: an earlier frame failed on one member");
+    if (g->in_flight > 0)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
+    std::vector<std::vector<int>> lids(W);
+    std::vector<std::vector<uint64_t>> tv(W);
+    std::vector<std::vector<uint32_t>> hv(W);
+    for (int k = 0; k < n; ++k) {
+        const auto w = g->where[(size_t)ids[k]];
+        lids[(size_t)w.first].push_back(w.second);
+        tv[(size_t)w.first].push_back(thr[k]);
+        hv[(size_t)w.first].push_back(hang_frames[k]);
+    }
+    for (size_t k = 0; k < W; ++k) {
+        if (lids[k].empty())
+            continue;
+        const int rc = sdrx_set_squelch(g->m[k].c, lids[k].data(), tv[k].data(), hv[k].data(), (int)lids[k].size());
+        if (rc)
+            return member_fail(g, (int)k, rc);
+    }
+    return SDRX_OK;
+}
+
+int sdrx_group_get_squelch(sdrx_group *g, const int *ids, int n, sdrx_squelch_state *out)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_squelch before sdrx_group_finalize");
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return gfail(g, SDRX_EINVAL, "sdrx_group_get_squelch: n = %d", n);
+    for (int k = 0; k < n; ++k) // the whole list first: nothing is written for a bad one
+        if (ids[k] < 0 || ids[k] >= (int)g->descs.size() || g->where[(size_t)ids[k]].first < 0)
+            return gfail(g, SDRX_EINVAL, "bad vfo id %d", ids[k]);
+    for (int k = 0; k < n; ++k) {
+        const auto w = g->where[(size_t)ids[k]];
+        const int rc = sdrx_get_squelch(g->m[(size_t)w.first].c, &w.second, 1, out + k);
+        if (rc)
+            return member_fail(g, w.first, rc);
+    }
+    return SDRX_OK;
+}
+
+int sdrx_group_get_egress(sdrx_group *g, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_egress before sdrx_group_finalize");
+    int64_t f = 0;
+    uint32_t open = 0, leaves = 0;
+    uint64_t bytes = 0;
+    for (size_t k = 0; k < g->m.size(); ++k) {
+        if (!g->m[k].c)
+            continue;
+        uint32_t o = 0, l = 0;
+        uint64_t b = 0;
+        const int rc = sdrx_get_egress(g->m[k].c, &f, &o, &l, &b);
+        if (rc)
+            return member_fail(g, (int)k, rc);
+        open += o;
+        leaves += l;
+        bytes += b;
+    }
+    if (frame)
+        *frame = f;
+    if (n_open)
+        *n_open = open;
+    if (n_leaves)
+        *n_leaves = leaves;
+    if (payload_bytes_copied)
+        *payload_bytes_copied = bytes;
     return SDRX_OK;
 }
 

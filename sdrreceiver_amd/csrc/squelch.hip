@@ -1,0 +1,150 @@
+// squelch.hip -- option "squelch": the per-leaf gate behind a frame's last payload-producing launch (included from sdrx.hip,
+// launched by its frame sequence).  Two launches on one stream:
+//
+//   k_squelch_scan   ONE workgroup.  Per leaf, in publish order: fold sum_sq of its meter records (what sdrx_get_meters folds
+//                    on the host), apply the rule
+//                        s >= thr: open, hang_left = hang_frames | hang_left > 0: open, hang_left -= 1 | else closed
+//                    on the per-leaf device state, and take the exclusive prefix sum of `open ? pay_len / 64 : 0` (payloads
+//                    are padded to 64 bytes).  Integers only: exact and independent of any order.  Writes the directory
+//                    {frame, n_open, packed_bytes | offset per leaf in 64-byte units, all ones = closed | hang_left per leaf}.
+//   k_squelch_gather reads the directory (a launch later on the same stream: no inter-workgroup protocol) and copies the open
+//                    leaves' payloads to their packed place, 16 bytes per lane and step.  The grid is sized for the worst
+//                    case (every leaf open): workgroups of closed leaves, and of tiles behind a leaf's end, return at once.
+//
+// No atomics, no grid-wide barrier; plain vector loads and stores.
+#pragma once
+
+namespace sdrx {
+
+constexpr int kSqThreads = 1024;    // k_squelch_scan: 16 waves, passes of 1 024 consecutive leaves, one per lane
+constexpr int kSqMaxLeaves = 65536; //   ... at most 64 passes
+constexpr int kSqTile = 16384;      // k_squelch_gather: bytes per workgroup (256 lanes x 4 x 16 bytes)
+constexpr unsigned kSqClosed = 0xffffffffu;
+
+struct SqLeaf { // static, per leaf in publish order (byte offsets into d_pay[p]; every one a multiple of 16)
+    unsigned pay_off, pay_units; // payload: offset, length in 64-byte units (padding included)
+    unsigned meter_off, meter_n; // its MeterAcc records
+};
+struct SqCfg { // sdrx_set_squelch
+    unsigned long long thr;
+    unsigned hang_frames, pad;
+};
+struct SqHeader { // 64 bytes in front of the directory's per-leaf arrays
+    long long frame;
+    unsigned n_open, n_leaves;
+    unsigned long long packed_bytes;
+    unsigned long long pad[5];
+};
+struct SqJob { // sdrx_set_squelch: leaf `index` (publish order) gets thr / hang_frames, its hang_left restarts at 0
+    unsigned long long thr;
+    unsigned hang_frames, index;
+};
+
+__global__ __launch_bounds__(64) void k_squelch_set(const SqJob *__restrict__ jobs, int n, SqCfg *__restrict__ cfg, unsigned *__restrict__ hang_left)
+{
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= n)
+        return;
+    const SqJob J = jobs[j];
+    SqCfg c;
+    c.thr = J.thr;
+    c.hang_frames = J.hang_frames;
+    c.pad = 0;
+    cfg[J.index] = c;
+    hang_left[J.index] = 0;
+}
+
+// dir: SqHeader | unsigned offs[n] | unsigned hang[n]
+__global__ __launch_bounds__(kSqThreads) void k_squelch_scan(const SqLeaf *__restrict__ leaves, const SqCfg *__restrict__ cfg,
+                                                             unsigned *__restrict__ hang_left, const unsigned char *__restrict__ pay,
+                                                             unsigned char *__restrict__ dir, int n, long long frame)
+{
+    __shared__ unsigned s_units[kSqThreads / 64], s_open[kSqThreads / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    unsigned *offs = reinterpret_cast<unsigned *>(dir + sizeof(SqHeader));
+    unsigned *hang = offs + n;
+    unsigned run_u = 0, run_o = 0; // units and open leaves of the passes so far (the same in every lane)
+    for (int i0 = 0; i0 < n; i0 += kSqThreads) { // pass: leaves i0 .. i0 + 1023, leaf i0 + t in lane t (coalesced loads)
+        const int i = i0 + t;
+        unsigned units = 0, is_open = 0;
+        if (i < n) {
+            const SqLeaf L = leaves[i];
+            const SqCfg C = cfg[i];
+            unsigned long long s = 0;
+            const uint4 *rec = reinterpret_cast<const uint4 *>(pay + L.meter_off);
+            for (unsigned j = 0; j < L.meter_n; ++j) { // {sum_sq u64, clipped u32, peak u32}
+                const uint4 r = rec[j];
+                s += ((unsigned long long)r.y << 32) | r.x;
+            }
+            unsigned h = hang_left[i];
+            is_open = 1;
+            if (s >= C.thr)
+                h = C.hang_frames;
+            else if (h > 0)
+                h -= 1;
+            else
+                is_open = 0;
+            hang_left[i] = h;
+            hang[i] = h;
+            units = is_open ? L.pay_units : 0u;
+        }
+        // inclusive scan over the wave, the waves' totals through LDS
+        unsigned su = units, so = is_open;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned u = __shfl_up(su, d, 64), o = __shfl_up(so, d, 64);
+            if (lane >= d) {
+                su += u;
+                so += o;
+            }
+        }
+        if (lane == 63) {
+            s_units[wave] = su;
+            s_open[wave] = so;
+        }
+        __syncthreads();
+        unsigned base = run_u + su - units;
+#pragma unroll
+        for (int w = 0; w < kSqThreads / 64; ++w) {
+            if (w < wave)
+                base += s_units[w];
+            run_u += s_units[w];
+            run_o += s_open[w];
+        }
+        if (i < n)
+            offs[i] = is_open ? base : kSqClosed;
+        __syncthreads(); // (the next pass overwrites the totals)
+    }
+    if (t == 0) {
+        SqHeader H;
+        H.frame = frame;
+        H.n_open = run_o;
+        H.n_leaves = (unsigned)n;
+        H.packed_bytes = 64ull * run_u;
+        for (int k = 0; k < 5; ++k)
+            H.pad[k] = 0;
+        *reinterpret_cast<SqHeader *>(dir) = H;
+    }
+}
+
+// grid (n leaves, tiles of the longest payload), 256 lanes
+__global__ __launch_bounds__(256) void k_squelch_gather(const SqLeaf *__restrict__ leaves, const unsigned char *__restrict__ pay,
+                                                        const unsigned char *__restrict__ dir, unsigned char *__restrict__ pack)
+{
+    const int i = blockIdx.x;
+    const unsigned off = reinterpret_cast<const unsigned *>(dir + sizeof(SqHeader))[i];
+    if (off == kSqClosed)
+        return;
+    const SqLeaf L = leaves[i];
+    const unsigned n16 = L.pay_units * 4u; // 16-byte units of this payload
+    const unsigned tile = blockIdx.y * (unsigned)(kSqTile / 16);
+    if (tile >= n16)
+        return;
+    const uint4 *src = reinterpret_cast<const uint4 *>(pay + L.pay_off) + tile;
+    uint4 *dst = reinterpret_cast<uint4 *>(pack + 64ull * off) + tile;
+    const unsigned m = min(n16 - tile, (unsigned)(kSqTile / 16));
+    for (unsigned k = threadIdx.x; k < m; k += 256)
+        dst[k] = src[k];
+}
+
+} // namespace sdrx

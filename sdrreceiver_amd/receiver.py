@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, meter
+from . import _lib, meter, squelch as _squelch
 from .topology import Topology, VfoDesc
 
 
@@ -53,7 +53,7 @@ class Receiver:
                  dc_blocked_scan: bool = False, pipeline: bool = False, fuse: bool = True, frame_pipeline: bool = True,
                  fuse_late: bool = True, keep_streams: bool = False, dc_speculative: bool = True,
                  dc_blocks_per_step: int | None = None, fuse_demod: bool = False,
-                 tail_in_levels: bool = True, meter: bool = False):
+                 tail_in_levels: bool = True, meter: bool = False, squelch: bool = False):
         self.L = _lib.lib()
         h = C.c_void_p()
         rc = self.L.sdrx_create(C.byref(h), int(device))
@@ -76,6 +76,8 @@ class Receiver:
         self._chk(self.L.sdrx_set_option(self.h, b"fuse_demod", int(bool(fuse_demod))))
         self._chk(self.L.sdrx_set_option(self.h, b"tail_in_levels", int(bool(tail_in_levels))))
         self._chk(self.L.sdrx_set_option(self.h, b"meter", int(bool(meter))))
+        if squelch:  # (off is the library's default: a library without the option is never asked)
+            self._chk(self.L.sdrx_set_option(self.h, b"squelch", 1))
         self._chk(self.L.sdrx_set_option(self.h, b"dc_speculative", int(bool(dc_speculative))))
         if dc_blocks_per_step is not None:
             self._chk(self.L.sdrx_set_option(self.h, b"dc_blocks_per_step", int(dc_blocks_per_step)))
@@ -218,6 +220,29 @@ class Receiver:
         out = (_lib.MeterC * max(1, ids.size))()
         self._chk(self.L.sdrx_get_meters(self.h, ids.ctypes.data, ids.size, out))
         return meter.meters_dict(out[:ids.size], [self.descs[i].demod_usb for i in ids.tolist()])
+
+    # -- squelch-gated egress (option ``squelch``; sdrreceiver_amd.squelch has the definition) ---------------------
+    def set_squelch(self, vids, thr_sum_sq, hang_frames) -> None:
+        """Leaf vids[k] opens when its meter ``sum_sq`` reaches thr_sum_sq[k] and stays open hang_frames[k] frames
+        after it last did; from the next frame on.  Resets the named leaves' ``hang_left``."""
+        ids, thr = _value_list(vids, thr_sum_sq, np.uint64)
+        _, hang = _value_list(vids, hang_frames, np.uint32)
+        self._chk(self.L.sdrx_set_squelch(self.h, ids.ctypes.data, thr.ctypes.data, hang.ctypes.data, ids.size))
+
+    def squelch(self, vids) -> dict:
+        """Squelch state of the leaves `vids` after the last delivered frame: ``frame``, ``thr_sum_sq``,
+        ``hang_frames``, ``hang_left``, ``open`` as arrays in the order of `vids`."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        out = (_lib.SquelchStateC * max(1, ids.size))()
+        self._chk(self.L.sdrx_get_squelch(self.h, ids.ctypes.data, ids.size, out))
+        return _squelch.squelch_dict(out[:ids.size])
+
+    def egress(self) -> dict:
+        """What the last delivered frame's payload copy moved: ``frame``, ``n_open``, ``n_leaves``,
+        ``payload_bytes_copied``."""
+        f, o, n, b = C.c_int64(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._chk(self.L.sdrx_get_egress(self.h, C.byref(f), C.byref(o), C.byref(n), C.byref(b)))
+        return {"frame": f.value, "n_open": o.value, "n_leaves": n.value, "payload_bytes_copied": b.value}
 
     def output_rate(self, vid: int) -> int:
         rate = C.c_uint32()
@@ -455,6 +480,25 @@ class Group:
         out = (_lib.MeterC * max(1, ids.size))()
         self._chk(self.L.sdrx_group_get_meters(self.h, ids.ctypes.data, ids.size, out))
         return meter.meters_dict(out[:ids.size], [self.descs[i].demod_usb for i in ids.tolist()])
+
+    def set_squelch(self, vids, thr_sum_sq, hang_frames) -> None:
+        """:meth:`Receiver.set_squelch` with ids of the whole tree (group option ``squelch=1``)."""
+        ids, thr = _value_list(vids, thr_sum_sq, np.uint64)
+        _, hang = _value_list(vids, hang_frames, np.uint32)
+        self._chk(self.L.sdrx_group_set_squelch(self.h, ids.ctypes.data, thr.ctypes.data, hang.ctypes.data, ids.size))
+
+    def squelch(self, vids) -> dict:
+        """:meth:`Receiver.squelch` with ids of the whole tree."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        out = (_lib.SquelchStateC * max(1, ids.size))()
+        self._chk(self.L.sdrx_group_get_squelch(self.h, ids.ctypes.data, ids.size, out))
+        return _squelch.squelch_dict(out[:ids.size])
+
+    def egress(self) -> dict:
+        """:meth:`Receiver.egress`, summed over the members."""
+        f, o, n, b = C.c_int64(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._chk(self.L.sdrx_group_get_egress(self.h, C.byref(f), C.byref(o), C.byref(n), C.byref(b)))
+        return {"frame": f.value, "n_open": o.value, "n_leaves": n.value, "payload_bytes_copied": b.value}
 
     def locate(self, vid: int) -> tuple[int, int]:
         m, l = C.c_int(), C.c_int()

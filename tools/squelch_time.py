@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""tools/squelch_time.py -- what squelch-gated egress costs and saves per streamed frame.
+
+    python3 tools/squelch_time.py [--steps K] [--warmup W] [--reps R] [--skip-10k] [--parent-lib FILE] [--out FILE]
+
+BASELINE config 3 (1 024 subs) and the north-star tree of 10 240 subs in the streaming host's form submit(f+1); wait() (kernels
+plus the payload copy), publish callback off.  Receivers, timed in turn (R rounds, the median per-frame time reported with
+min and max): meter=1 squelch=0 (baseline b), and squelch=1 with 100 %, 50 %, 10 % and 1 % of the leaves open (threshold 0
+for the open ones, 2^63 for the others, spread evenly over the tree).  --parent-lib FILE adds baseline (a): a library built
+from the parent commit, loaded in a child process through SDRX_LIB (it lacks the squelch entry points, so the child asks for
+none of them), plain options, timed in the same run.  Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+NEW = ("sdrx_set_squelch", "sdrx_get_squelch", "sdrx_get_egress", "sdrx_group_set_squelch", "sdrx_group_get_squelch", "sdrx_group_get_egress")
+FRACTIONS = (1.0, 0.5, 0.1, 0.01)
+
+
+def timed(rx, host, steps, warmup):
+    rx.submit(host)
+    for _ in range(warmup):
+        rx.submit(host)
+        rx.wait()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        rx.submit(host)
+        rx.wait()
+    ms = (time.perf_counter() - t0) * 1e3 / steps
+    rx.wait()
+    return ms
+
+
+def summary(v):
+    return {"ms_per_frame": round(statistics.median(v), 5), "min": round(min(v), 5), "max": round(max(v), 5)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--skip-10k", action="store_true")
+    ap.add_argument("--parent-lib", default="")
+    ap.add_argument("--child", default="", help=argparse.SUPPRESS)  # tree name: time the loaded library once, plain options
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    import numpy as np
+    from sdrreceiver_amd import _lib, synth, topology as tp
+    if a.child:
+        import ctypes
+        probe = ctypes.CDLL(_lib.LIB_PATH)
+        for name in NEW:
+            if not hasattr(probe, name):
+                _lib.SYMBOLS.pop(name, None)
+    from sdrreceiver_amd.receiver import Receiver
+
+    trees = {"config3": lambda: tp.config3(1024), "10k": lambda: tp.config3(10240)}
+    if a.child:
+        topo = trees[a.child]()
+        host = synth.lcg_frame(topo.frame, synth.Lcg(1))
+        rx = Receiver.from_topology(topo, device=0)
+        rx.set_publish(False)
+        print(json.dumps([timed(rx, host, a.steps, a.warmup) for _ in range(a.reps)]))
+        rx.close()
+        return
+    result = {}
+    for name in ["config3"] + ([] if a.skip_10k else ["10k"]):
+        topo = trees[name]()
+        lv = topo.leaves_in_publish_order()
+        host = synth.lcg_frame(topo.frame, synth.Lcg(1))
+        rxs = {"meter1_squelch0": Receiver.from_topology(topo, device=0, meter=True)}
+        for frac in FRACTIONS:
+            rx = Receiver.from_topology(topo, device=0, squelch=True)
+            n_open = max(1, round(frac * len(lv)))
+            is_open = np.zeros(len(lv), bool)
+            is_open[np.unique(np.linspace(0, len(lv) - 1, n_open).round().astype(int))] = True
+            rx.set_squelch(lv, [0 if x else 1 << 63 for x in is_open], [0] * len(lv))
+            rxs[f"open_{round(100 * frac)}pct"] = rx
+        for rx in rxs.values():
+            rx.set_publish(False)
+        times = {k: [] for k in rxs}
+        parent = []
+        for r in range(a.reps):
+            for k, rx in rxs.items():
+                times[k].append(timed(rx, host, a.steps, a.warmup))
+            if a.parent_lib:  # one round of the parent's library between ours, in a process of its own
+                out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--steps", str(a.steps), "--warmup",
+                                      str(a.warmup), "--reps", "1"], env={**os.environ, "SDRX_LIB": os.path.abspath(a.parent_lib)},
+                                     capture_output=True, text=True, check=True, timeout=300)
+                parent += json.loads(out.stdout.strip().splitlines()[-1])
+        for k, v in times.items():
+            result[f"{name}_{k}"] = summary(v)
+            if k != "meter1_squelch0":
+                eg = rxs[k].egress()
+                result[f"{name}_{k}"].update(n_open=eg["n_open"], payload_bytes_copied=eg["payload_bytes_copied"])
+        if parent:
+            result[f"{name}_parent_lib"] = summary(parent)
+        result[f"{name}_device_bytes"] = {"meter1_squelch0": rxs["meter1_squelch0"].stats()["device_bytes"],
+                                          "squelch1": rxs["open_100pct"].stats()["device_bytes"]}
+        for rx in rxs.values():
+            rx.close()
+    print(json.dumps(result))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
