@@ -66,7 +66,10 @@ typedef struct sdrx_vfo_desc {
  * (sdrj.cpp:288-294, vfo.cpp:257-263).  `buf` is owned by the library and valid until the next
  * sdrx_process*() / sdrx_wait() / sdrx_fetch() / sdrx_destroy() -- libzmq copies on zmq_send
  * (zmqpublisher.cpp:91-93), so the reference's publisher needs it no longer than the callback.
- * Not invoked for an empty payload (zmqpublisher.cpp:88). */
+ * Not invoked for an empty payload (zmqpublisher.cpp:88).
+ * With option "preroll" = 1, and only then, "once per leaf per frame" becomes "at most twice": a leaf that opens in the
+ * delivered frame f after its squelch was closed in f-1 gets two invocations at its place in that order, its payload of frame
+ * f-1 first, then that of f (same topic, same rate). */
 typedef void (*sdrx_publish_fn)(void *user, const char topic[5], uint32_t sample_rate, const void *buf,
                                 uint32_t len_bytes);
 
@@ -125,7 +128,10 @@ int sdrx_add_vfo(sdrx_ctx *ctx, const sdrx_vfo_desc *desc, int *id_out);
  *            taps (the reference's 48 kS/s sub VFOs, vfo::usb_demod, vfo.cpp:300-332) demodulates inside its mix wave: 256
  *            stream samples per 1024-sample chunk go from registers through the wave's LDS to int16 and the leaf's cf32
  *            stream never reaches HBM (decimate[2] of such a leaf is kept only while it is the tap, sdrx_set_tap, or with
- *            "keep_streams").  Results are bit-identical.  Measured on MI355X (round 6, profiles/README.md): it removes
+ *            "keep_streams").  Results are bit-identical with "exact" = 1 and 2; with "exact" = 0 they keep the same tolerance
+ *            against the reference but are not bit-identical to the k_usb_demod form (the fused form cuts VFO-frames into
+ *            other segments and chunks, which changes which chunks replay the NCO table exactly).  Measured on MI355X
+ *            (round 6, profiles/README.md): it removes
  *            138 MB of HBM traffic per frame of BASELINE config 3 and is SLOWER -- 0.123 vs 0.112 ms per frame exact, 0.102 vs
  *            0.091 tolerance: the frame is bound by VALU issue, not by HBM, and the demodulation's plain fp32 MACs issue in
  *            pairs only beside other waves doing the same (k_usb_demod: 80 % paired at 7 waves per SIMD) -- inside the mix
@@ -145,6 +151,11 @@ int sdrx_add_vfo(sdrx_ctx *ctx, const sdrx_vfo_desc *desc, int *id_out);
  *            and every threshold 0 (the start) every payload and callback is what it is with 0; sdrx_get_output of a leaf that
  *            was closed in the delivered frame gives SDRX_OK, *len_bytes = 0, *rate as always and a non-NULL *buf that is not to
  *            be read, and the publish callback is not invoked for it (the rule for an empty payload).
+ *   "preroll" 0 (default) | 1: squelch pre-roll (sdrx_get_preroll below); 1 implies "squelch".  0 changes nothing.  With 1 a
+ *            leaf that is open in frame f and was closed by the gate in frame f-1 is delivered with its payload of f-1 as
+ *            well, ahead of that of f: one frame, which is what the device still holds.  With "fuse_demod" leaves the tree
+ *            keeps k_mix_levels + k_usb_demod in every arithmetic ("tail_in_levels" is not used), and "pipeline" = 1 loses its
+ *            overlap.
  *   "dc_blocked_scan" 0|1 (default 0): how sdrx_process_u8 removes the DC bias.  0 = the
  *                 reference's sequentially rounded fp32 recurrence, bit for bit (below).  1 = the same linear filter as a
  *                 blocked parallel scan (~15 us): the true IIR response.  The reference's recurrence
@@ -298,6 +309,25 @@ typedef struct sdrx_squelch_state {
 int sdrx_set_squelch(sdrx_ctx *ctx, const int *ids, const uint64_t *thr_sum_sq, const uint32_t *hang_frames, int n);
 int sdrx_get_squelch(sdrx_ctx *ctx, const int *ids, int n, sdrx_squelch_state *out);
 int sdrx_get_egress(sdrx_ctx *ctx, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied);
+/* Squelch pre-roll (option "preroll" = 1).  Per leaf one more bit of device state, prev_open: 1 after sdrx_finalize (frame 0 has
+ * no predecessor), and after every gate that gate's `open`; sdrx_set_squelch does not touch it.  With open(f) as above:
+ *     pre(f) = open(f) && !prev_open;   prev_open = open(f)
+ * A frame delivered with pre(f) = 1 for a leaf carries that leaf's payload of frame f-1 too; the callback sees it first
+ * (sdrx_publish_fn).  The rule follows the gate, not the host: after several sdrx_process_device calls sdrx_fetch delivers the
+ * last frame and, where due, the pre-roll of the one before it, which was never delivered itself.
+ * sdrx_get_output is unchanged (frame f's payload).  sdrx_get_preroll: the leaf's pre-rolled payload in the delivered frame and
+ * *frame = f-1, or SDRX_OK with *len_bytes = 0 (and a non-NULL *buf that is not to be read); calling rules and buffer lifetime
+ * of sdrx_get_output; SDRX_ESTATE with the option off.  Each pointer may be NULL.
+ * sdrx_get_preroll_count: for the delivered frame, how many leaves are pre-rolled and how many bytes (payloads padded to 64)
+ * that added to the copy; calling rules of sdrx_get_egress, whose payload_bytes_copied includes them (it reports what the copy
+ * moved) and whose n_open stays the number of open leaves.
+ * The two calls differ after sdrx_process_device, as sdrx_get_squelch and sdrx_get_egress do: sdrx_get_preroll brings the last
+ * queued frame over itself (an implicit sdrx_fetch, callbacks included), sdrx_get_preroll_count refuses with SDRX_ESTATE until
+ * sdrx_fetch or another sdrx_get_* has delivered it.
+ * A sdrx_finalize that fails (memory: the packed buffers double) leaves the options as they were set, so "preroll" can be
+ * switched off and sdrx_finalize called again. */
+int sdrx_get_preroll(sdrx_ctx *ctx, int id, const void **buf, uint32_t *len_bytes, int64_t *frame);
+int sdrx_get_preroll_count(sdrx_ctx *ctx, uint32_t *n_preroll, uint64_t *preroll_bytes);
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);
@@ -438,6 +468,10 @@ int sdrx_group_get_meters(sdrx_group *grp, const int *ids, int n, sdrx_meter *ou
 int sdrx_group_set_squelch(sdrx_group *grp, const int *ids, const uint64_t *thr_sum_sq, const uint32_t *hang_frames, int n);
 int sdrx_group_get_squelch(sdrx_group *grp, const int *ids, int n, sdrx_squelch_state *out);
 int sdrx_group_get_egress(sdrx_group *grp, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied);
+/* sdrx_get_preroll routed to the member that owns the leaf; sdrx_get_preroll_count summed over the members (group option
+ * "preroll" = 1). */
+int sdrx_group_get_preroll(sdrx_group *grp, int id, const void **buf, uint32_t *len_bytes, int64_t *frame);
+int sdrx_group_get_preroll_count(sdrx_group *grp, uint32_t *n_preroll, uint64_t *preroll_bytes);
 
 /* ---- introspection / measurement ------------------------------------------------------------- */
 typedef struct sdrx_stats {

@@ -105,6 +105,10 @@ SYMBOLS = {
     "sdrx_group_set_squelch": (_i, [_vp, _vp, _vp, _vp, _i]),
     "sdrx_group_get_squelch": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_group_get_egress": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "sdrx_get_preroll": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int64)]),
+    "sdrx_get_preroll_count": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "sdrx_group_get_preroll": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int64)]),
+    "sdrx_group_get_preroll_count": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

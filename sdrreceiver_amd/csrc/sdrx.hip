@@ -163,6 +163,17 @@ struct sdrx_ctx {
     unsigned sq_n_open = 0;                     //   ... its header
     unsigned long long sq_copied = 0;           //   ... and the payload bytes its copy moved
     unsigned long long sq_copied_slot[2] = {0, 0};
+    // option preroll: a leaf that opens in frame f after the gate closed it in f-1 is delivered with its payload
+    // of f-1 in front of that of f.  prev_open per leaf on the device; the directory gains pre[n] behind hang[n]; d_pack[p] holds
+    // the worst case (every leaf re-opens: twice the payload region), and so does its host side, which then lies BEHIND the
+    // fixed part of h_pay[p] (at hpack_off; 0 with the option off: the start of h_pay[p], as before).
+    int opt_preroll = 0;
+    unsigned *d_sq_prev = nullptr;
+    size_t hpack_off = 0;
+    bool preroll_fused = false;                 // a leaf demodulates in its mix wave: the levels write d_pay (enqueue_frame_as)
+    std::vector<unsigned> sq_pre, sq_units;     // the delivered directory's pre-roll flags; 64-byte units of every leaf's payload
+    unsigned sq_n_pre = 0;                      // pre-rolled leaves of the delivered frame
+    unsigned long long sq_pre_bytes = 0;        //   ... and the packed bytes their pre-roll added to the copy
     hipEvent_t ev_dir[2] = {nullptr, nullptr};  // the fixed-size part of frame f is in h_pay[f & 1]
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first
@@ -426,8 +437,16 @@ void squelch_gate(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
         return;
     const int p = (int)(frame & 1ull);
     unsigned char *dir = c->d_pay[p] + c->dir_off;
-    hipLaunchKernelGGL(k_squelch_scan, dim3(1), dim3(kSqThreads), 0, ts, c->d_sq_leaves, c->d_sq_cfg, c->d_sq_hang, c->d_pay[p], dir, n, (long long)frame);
-    hipLaunchKernelGGL(k_squelch_gather, dim3(n, c->sq_tiles), dim3(256), 0, ts, c->d_sq_leaves, c->d_pay[p], dir, c->d_pack[p]);
+    if (c->opt_preroll) { // the same two launches in their second form: the gather also reads frame - 1's payloads in d_pay[p ^ 1]
+        const SqPre<true> X = {c->d_sq_prev, c->d_pay[p ^ 1]};
+        hipLaunchKernelGGL(k_squelch_scan<true>, dim3(1), dim3(kSqThreads), 0, ts, c->d_sq_leaves, c->d_sq_cfg, c->d_sq_hang, c->d_pay[p], dir, n,
+                           (long long)frame, X);
+        hipLaunchKernelGGL(k_squelch_gather<true>, dim3(n, c->sq_tiles, 2), dim3(256), 0, ts, c->d_sq_leaves, c->d_pay[p], dir, c->d_pack[p], X);
+        return;
+    }
+    hipLaunchKernelGGL(k_squelch_scan<>, dim3(1), dim3(kSqThreads), 0, ts, c->d_sq_leaves, c->d_sq_cfg, c->d_sq_hang, c->d_pay[p], dir, n, (long long)frame,
+                       SqPre<false>());
+    hipLaunchKernelGGL(k_squelch_gather<>, dim3(n, c->sq_tiles), dim3(256), 0, ts, c->d_sq_leaves, c->d_pay[p], dir, c->d_pack[p], SqPre<false>());
 }
 
 // One frame: [wait for the tail of frame f-2] -> ingest -> one k_mix_decimate launch per tree level on
@@ -446,6 +465,25 @@ void squelch_gate(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
 //   * option squelch: d_pack[p] and the directory (inside d_pay[p]) are written by the gate of f, behind its tail on the
 //     tail's stream, and read by the two copies of f (fixed part at submit, packed payloads from sdrx_wait): the same
 //     argument -- their next writer is the gate of f+2.  hang_left is one array: gates run in frame order on one stream.
+//   * option preroll: the gate of f also READS the payloads of f-1 in d_pay[p ^ 1], whose next writer is frame f+1 -- every
+//     launch that writes a payload of f+1 must come behind the gate of f.  prev_open is one array, as hang_left.  Path by path:
+//       - one launch per level, one stream (below, !pipe): tail(f), gate(f), levels(f+1), tail(f+1) in order, whichever kernel
+//         writes the payloads (fuse_demod leaves write theirs in the levels);
+//       - two streams (pipe): the tails and gates of all frames are in order on tail_stream, and without fuse_demod only the
+//         tail writes d_pay.  With fuse_demod leaves the levels of f+1 on `stream` write it, and they wait only for ev_tail of
+//         f-1: with preroll they also wait for ev_tail[p ^ 1], recorded behind the gate of f (preroll_fused below) -- which
+//         takes the overlap away for exactly that combination;
+//       - pipeline_step with k_mix_levels: the launch of step k runs level l of frame k-l, then the block kernels and the gate
+//         of the frame g that left the last level.  Block kernels of g+1 come in step k+1: behind gate(g).  A fuse_demod leaf
+//         on level n-1 writes g's payload in step k and g+1's in step k+1: behind gate(g).  One on level n-2 writes g+1's payload
+//         in step k's launch, BEFORE gate(g): with preroll such a tree does not use the software pipeline (build_level_plan);
+//       - pipeline_step with k_levels_tail: the demodulation blocks of f ride in the launch of the step after f's last level,
+//         then k_lpf_long(f), gate(f), and only then the compress / late-decimation launches of f+1 in the same step; the
+//         demodulation of f+1 is in the next step's launch.  fuse_demod leaves of f+1 would write their payload inside the
+//         launch that carries f's demodulation, before gate(f): with preroll a tree with such leaves keeps k_mix_levels +
+//         k_usb_demod in every arithmetic (build_level_plan; the rule option meter has for the exact one);
+//       - paths mix only through pipeline_flush, which runs every gate still outstanding, in frame order, on `stream`; the
+//         two-stream form never enters pipeline_step.  sdrx_fetch and the copies read d_pack and the directory only.
 // ARITH = option "exact": 1 the exact arithmetic, 0 the tolerance arithmetic (NCO as rotations), 2 the robust one (exact NCO,
 // FMA mixer and filters) -- kernels.hip, nco_mix.
 template <int ARITH>
@@ -457,6 +495,8 @@ int enqueue_frame_as(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
     const bool pipe = c->opt_pipeline != 0;
     if (pipe && c->tail_recorded[p])
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_tail[p], 0));
+    if (pipe && c->opt_preroll && c->preroll_fused && c->tail_recorded[p ^ 1]) // the levels write d_pay[p], which the previous gate reads
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_tail[p ^ 1], 0));
     spectrum_raw_step(c, raw, raw_mode);
     // A few parent-less VFOs (the reference's 2-3 mains) read the caller's frame as it is; a wide
     // level 0 (the flat workloads) is bandwidth bound and wants coalesced reads: one layout pass
@@ -756,12 +796,27 @@ const unsigned char *leaf_payload(const sdrx_ctx *c, int id, int slot, uint32_t 
     *len = n.pay_len;
     if (!c->opt_squelch)
         return c->h_pay[slot] + n.pay_off;
-    const unsigned off = c->sq_offs[(size_t)c->sq_index[(size_t)id]];
+    const size_t k = (size_t)c->sq_index[(size_t)id];
+    const unsigned off = c->sq_offs[k];
     if (off == kSqClosed) {
         *len = 0;
         return c->h_pay[slot];
     }
-    return c->h_pay[slot] + 64 * (size_t)off;
+    if (c->opt_preroll && c->sq_pre[k]) // the pre-rolled payload lies in front
+        return c->h_pay[slot] + c->hpack_off + 64 * ((size_t)off + c->sq_units[k]);
+    return c->h_pay[slot] + c->hpack_off + 64 * (size_t)off;
+}
+// Option preroll: leaf `id`'s payload of the frame BEFORE the delivered one, if the delivered frame carries it (else *len = 0)
+const unsigned char *leaf_preroll(const sdrx_ctx *c, int id, int slot, uint32_t *len)
+{
+    *len = 0;
+    if (!c->opt_preroll)
+        return c->h_pay[slot];
+    const size_t k = (size_t)c->sq_index[(size_t)id];
+    if (c->sq_offs[k] == kSqClosed || !c->sq_pre[k])
+        return c->h_pay[slot];
+    *len = c->nodes[(size_t)id].pay_len;
+    return c->h_pay[slot] + c->hpack_off + 64 * (size_t)c->sq_offs[k];
 }
 
 // vfo::transmitData for every leaf, in the reference's order (vfo.cpp:426-453, sdrj.cpp:288-294)
@@ -783,6 +838,12 @@ void publish_all(sdrx_ctx *c, int slot)
         char topic[5] = {0, 0, 0, 0, 0};
         for (int k = 0; k < 5 && n.d.topic[k]; ++k)
             topic[k] = n.d.topic[k];
+        if (c->opt_preroll) { // a leaf that has just opened: the frame before, first
+            uint32_t plen = 0;
+            const unsigned char *pre = leaf_preroll(c, i, slot, &plen);
+            if (plen)
+                c->cb(c->cb_user, topic, n.rate, pre, plen);
+        }
         c->cb(c->cb_user, topic, n.rate, pay, len);
     }
 }
@@ -835,9 +896,11 @@ void free_device_state(sdrx_ctx *c)
     dfree(c->d_sq_leaves);
     dfree(c->d_sq_cfg);
     dfree(c->d_sq_hang);
+    dfree(c->d_sq_prev);
     dfree(c->d_sq_jobs);
     c->sq_jobs_cap = 0;
     c->sq_bytes = 0;
+    c->dir_off = c->pack_bytes = c->hpack_off = 0; // (they describe the buffers that have just gone)
     c->spec_n_desc = 0;
     c->spec_raw_on = false;
 }
@@ -987,6 +1050,8 @@ int sdrx_set_option(sdrx_ctx *c, const char *name, int value)
         c->opt_meter = value != 0;
     else if (!strcmp(name, "squelch"))
         c->opt_squelch = value != 0;
+    else if (!strcmp(name, "preroll"))
+        c->opt_preroll = value != 0;
     else
         return fail(c, SDRX_EINVAL, "unknown option '%s'", name);
     return SDRX_OK;
@@ -1534,6 +1599,12 @@ void build_level_plan(sdrx_ctx *c, Built &B)
     for (const Node &n : c->nodes)
         if (n.leaf && n.level < c->n_levels - 2)
             P.usable = false;
+    // Option preroll: the gate of frame g, behind launch g + n_levels - 1, reads the payloads of g - 1 in the parity that g + 1
+    // writes.  A leaf that demodulates in its mix wave on level n_levels - 2 writes g + 1's payload in that very launch: only
+    // on the last level is its next write behind the gate (the argument above enqueue_frame_as).
+    for (const Node &n : c->nodes)
+        if (c->opt_preroll && n.fused_demod && n.level != c->n_levels - 1)
+            P.usable = false;
     if (!P.usable)
         return;
     // deepest level first: in the steady state of the reference's two-level trees the long sub-VFO
@@ -1573,6 +1644,8 @@ void build_level_plan(sdrx_ctx *c, Built &B)
         if (n.leaf && n.d.demod_usb && !n.fused_demod && n.level != c->n_levels - 1)
             tail = false;
         if (n.fused_demod && c->opt_meter && c->opt_exact == 1) // (k_levels_tail's exact form does not meter mix items: kernels.hip)
+            tail = false;
+        if (n.fused_demod && c->opt_preroll) // (its payload of f+1 would be written in the launch in front of the gate of f)
             tail = false;
     }
     // LDS: four mix waves or one demodulation block per workgroup.  Where four waves' LDS would fit fewer mix waves on a CU
@@ -1700,19 +1773,25 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
     HIPCHK(c, hipMemsetAsync(c->arena, 0, c->arena_bytes, c->stream));
     // (the copy length stays a multiple of 64 bytes, as the packed payloads are)
     c->pay_bytes = std::max<size_t>(c->opt_meter ? align_up(c->meter_off + 16 * (size_t)c->meter_slots, 64) : B.pay, 64);
+    c->dir_off = c->pack_bytes = c->hpack_off = 0; // (a finalize that was refused may have left another tree's values)
     if (c->opt_squelch) { // the directory behind the records: one fixed-size copy brings both
         size_t n_leaves = 0;
         for (const Node &n : c->nodes)
             n_leaves += n.leaf;
         c->dir_off = c->pay_bytes;
-        c->pay_bytes = align_up(c->dir_off + sizeof(SqHeader) + 8 * n_leaves, 64);
+        c->pay_bytes = align_up(c->dir_off + sizeof(SqHeader) + (c->opt_preroll ? 12 : 8) * n_leaves, 64);
         c->pack_bytes = std::max<size_t>(align_up(B.pay, 64), 64);
+        if (c->opt_preroll) { // every leaf re-opens: two payloads each; on the host behind the fixed part, which they could overrun
+            c->pack_bytes *= 2;
+            c->hpack_off = c->pay_bytes;
+        }
     }
+    const size_t h_bytes = align_up(c->pay_bytes, 16) + (c->opt_preroll ? c->pack_bytes : 0);
     for (int p = 0; p < 2; ++p) {
         HIPCHK(c, hipMalloc(&c->d_pay[p], align_up(c->pay_bytes, 16))); // (whole 16-byte units)
         HIPCHK(c, hipMemsetAsync(c->d_pay[p], 0, c->pay_bytes, c->stream));
-        HIPCHK(c, hipHostMalloc(&c->h_pay[p], align_up(c->pay_bytes, 16), hipHostMallocDefault));
-        memset(c->h_pay[p], 0, c->pay_bytes);
+        HIPCHK(c, hipHostMalloc(&c->h_pay[p], h_bytes, hipHostMallocDefault));
+        memset(c->h_pay[p], 0, h_bytes);
     }
     {
         const size_t raw_tiles = align_up((size_t)c->root_frame, kChunk) + kChunk; // (+1 tile, as for the parents' streams)
@@ -1907,11 +1986,20 @@ int squelch_setup(sdrx_ctx *c)
     c->sq_cfg.assign(n, SqCfg{0, 0, 0});
     c->sq_offs.assign(n, 0);
     c->sq_hang.assign(n, 0);
+    c->sq_pre.assign(n, 0);
+    c->sq_units.resize(n);
+    for (size_t k = 0; k < n; ++k)
+        c->sq_units[k] = leaves[k].pay_units;
     const size_t n1 = std::max<size_t>(n, 1);
     HIPCHK(c, hipMalloc(&c->d_sq_leaves, sizeof(SqLeaf) * n1));
     HIPCHK(c, hipMalloc(&c->d_sq_cfg, sizeof(SqCfg) * n1));
     HIPCHK(c, hipMalloc(&c->d_sq_hang, sizeof(unsigned) * n1));
     c->sq_bytes = (sizeof(SqLeaf) + sizeof(SqCfg) + sizeof(unsigned)) * n1 + 2 * c->pack_bytes;
+    if (c->opt_preroll) { // prev_open = 1: frame 0 has no predecessor
+        HIPCHK(c, hipMalloc(&c->d_sq_prev, sizeof(unsigned) * n1));
+        HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_sq_prev), 1, n1, c->stream));
+        c->sq_bytes += sizeof(unsigned) * n1;
+    }
     HIPCHK(c, hipMemcpyAsync(c->d_sq_leaves, leaves.data(), sizeof(SqLeaf) * n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_sq_cfg, 0, sizeof(SqCfg) * n1, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_sq_hang, 0, sizeof(unsigned) * n1, c->stream));
@@ -1941,6 +2029,9 @@ int finalize_impl(sdrx_ctx *c)
     build_publish_order(c);
     if (int rc = squelch_setup(c))
         return rc;
+    c->preroll_fused = false;
+    for (const Node &n : c->nodes)
+        c->preroll_fused |= n.fused_demod;
     c->taps.clear();
     c->finalized = true;
     return SDRX_OK;
@@ -1959,15 +2050,21 @@ int sdrx_finalize(sdrx_ctx *c)
     if (c->nodes.empty())
         return fail(c, SDRX_ESTATE, "sdrx_finalize: no VFOs");
     HIPCHK(c, hipSetDevice(c->device));
+    const int asked_squelch = c->opt_squelch, asked_meter = c->opt_meter;
+    if (c->opt_preroll) // the pre-roll is the gate's
+        c->opt_squelch = 1;
     if (c->opt_squelch) // the gate reads the meter records
         c->opt_meter = 1;
     const int rc = finalize_impl(c);
-    if (rc != SDRX_OK) { // nothing of a half-built tree stays behind: a later call starts clean
+    if (rc != SDRX_OK) { // nothing of a half-built tree stays behind: a later call starts clean -- with the options as they
+                         // were SET, not as this attempt implied them (the caller may switch "preroll" off and try again)
         (void)hipStreamSynchronize(c->stream);
         free_device_state(c);
         c->l1.clear();
         c->lb.clear();
         c->publish_order.clear();
+        c->opt_squelch = asked_squelch;
+        c->opt_meter = asked_meter;
     }
     return rc;
 }
@@ -2532,6 +2629,15 @@ void squelch_delivered(sdrx_ctx *c, int p)
     }
     c->sq_n_open = H.n_open;
     c->sq_copied = c->sq_copied_slot[p];
+    if (c->opt_preroll) {
+        if (n)
+            memcpy(c->sq_pre.data(), dir + sizeof H + 8 * n, 4 * n);
+        c->sq_n_pre = (unsigned)H.pad[0];
+        c->sq_pre_bytes = 0;
+        for (size_t k = 0; k < n; ++k)
+            if (c->sq_pre[k])
+                c->sq_pre_bytes += 64ull * c->sq_units[k];
+    }
 }
 
 int start_owed_copy(sdrx_ctx *c)
@@ -2549,7 +2655,7 @@ int start_owed_copy(sdrx_ctx *c)
         if (int rc = squelch_packed_bytes(c, p, &bytes))
             return rc;
         if (bytes)
-            HIPCHK(c, hipMemcpyAsync(c->h_pay[p], c->d_pack[p], bytes, hipMemcpyDeviceToHost, cs));
+            HIPCHK(c, hipMemcpyAsync(c->h_pay[p] + c->hpack_off, c->d_pack[p], bytes, hipMemcpyDeviceToHost, cs));
         c->sq_copied_slot[p] = bytes;
     } else {
         HIPCHK(c, hipEventSynchronize(c->ev_tail[p]));
@@ -2643,7 +2749,7 @@ int sdrx_fetch(sdrx_ctx *c)
         if (int rc = squelch_packed_bytes(c, p, &bytes))
             return rc;
         if (bytes)
-            HIPCHK(c, hipMemcpyAsync(c->h_pay[p], c->d_pack[p], bytes, hipMemcpyDeviceToHost, ts));
+            HIPCHK(c, hipMemcpyAsync(c->h_pay[p] + c->hpack_off, c->d_pack[p], bytes, hipMemcpyDeviceToHost, ts));
         c->sq_copied_slot[p] = bytes;
     } else if (c->pending_fetch) {
         HIPCHK(c, hipMemcpyAsync(c->h_pay[p], c->d_pay[p], c->pay_bytes, hipMemcpyDeviceToHost, ts));
@@ -2869,6 +2975,53 @@ int sdrx_get_egress(sdrx_ctx *c, int64_t *frame, uint32_t *n_open, uint32_t *n_l
         *n_open = c->opt_squelch ? c->sq_n_open : leaves;
     if (payload_bytes_copied)
         *payload_bytes_copied = c->opt_squelch ? c->sq_copied : (uint64_t)(c->meter_off ? c->meter_off : c->pay_bytes);
+    return SDRX_OK;
+}
+
+int sdrx_get_preroll(sdrx_ctx *c, int id, const void **buf, uint32_t *len, int64_t *frame)
+{
+    if (!c || id < 0 || id >= (int)c->nodes.size())
+        return fail(c, SDRX_EINVAL, "bad vfo id %d", id);
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_preroll before sdrx_finalize");
+    if (!c->opt_preroll)
+        return fail(c, SDRX_ESTATE, "sdrx_get_preroll: option \"preroll\" is off");
+    if (!c->nodes[(size_t)id].leaf)
+        return fail(c, SDRX_EINVAL, "vfo %d has children and publishes nothing (vfo.cpp:253-266)", id);
+    if (c->in_flight > 0 && c->host_slot < 0)
+        return fail(c, SDRX_ESTATE, "sdrx_get_preroll: %d submitted frame(s), none delivered yet -- call sdrx_wait first", c->in_flight);
+    if (c->pending_fetch) {
+        int rc = sdrx_fetch(c);
+        if (rc)
+            return rc;
+    }
+    if (c->host_slot < 0)
+        return fail(c, SDRX_ESTATE, "sdrx_get_preroll: no frame has been delivered yet");
+    uint32_t plen = 0;
+    const unsigned char *pre = leaf_preroll(c, id, c->host_slot, &plen);
+    if (buf)
+        *buf = pre;
+    if (len)
+        *len = plen;
+    if (frame)
+        *frame = (int64_t)c->host_frame - 1;
+    return SDRX_OK;
+}
+
+int sdrx_get_preroll_count(sdrx_ctx *c, uint32_t *n_preroll, uint64_t *preroll_bytes)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_preroll_count before sdrx_finalize");
+    if (!c->opt_preroll)
+        return fail(c, SDRX_ESTATE, "sdrx_get_preroll_count: option \"preroll\" is off");
+    if (c->host_slot < 0 || c->pending_fetch)
+        return fail(c, SDRX_ESTATE, "sdrx_get_preroll_count: no frame has been delivered yet (sdrx_wait / sdrx_fetch first)");
+    if (n_preroll)
+        *n_preroll = c->sq_n_pre;
+    if (preroll_bytes)
+        *preroll_bytes = c->sq_pre_bytes;
     return SDRX_OK;
 }
 

@@ -198,6 +198,12 @@ void group_publish(sdrx_group *g)
         char topic[5] = {0, 0, 0, 0, 0};
         for (int k = 0; k < 5 && n.d.topic[k]; ++k)
             topic[k] = n.d.topic[k];
+        if (c->opt_preroll) { // a leaf that has just opened: the frame before, first
+            uint32_t plen = 0;
+            const unsigned char *pre = leaf_preroll(c, w.second, c->host_slot, &plen);
+            if (plen)
+                g->cb(g->cb_user, topic, n.rate, pre, plen);
+        }
         g->cb(g->cb_user, topic, n.rate, pay, len);
     }
 }
@@ -677,6 +683,45 @@ int sdrx_group_get_egress(sdrx_group *g, int64_t *frame, uint32_t *n_open, uint3
         *n_leaves = leaves;
     if (payload_bytes_copied)
         *payload_bytes_copied = bytes;
+    return SDRX_OK;
+}
+
+int sdrx_group_get_preroll(sdrx_group *g, int id, const void **buf, uint32_t *len, int64_t *frame)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_preroll before sdrx_group_finalize");
+    if (id < 0 || id >= (int)g->descs.size() || g->where[(size_t)id].first < 0)
+        return gfail(g, SDRX_EINVAL, "bad vfo id %d", id);
+    const auto w = g->where[(size_t)id];
+    const int rc = sdrx_get_preroll(g->m[(size_t)w.first].c, w.second, buf, len, frame);
+    return rc ? member_fail(g, w.first, rc) : SDRX_OK;
+}
+
+int sdrx_group_get_preroll_count(sdrx_group *g, uint32_t *n_preroll, uint64_t *preroll_bytes)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_preroll_count before sdrx_group_finalize");
+    uint32_t count = 0;
+    uint64_t bytes = 0;
+    for (size_t k = 0; k < g->m.size(); ++k) {
+        if (!g->m[k].c)
+            continue;
+        uint32_t n = 0;
+        uint64_t b = 0;
+        const int rc = sdrx_get_preroll_count(g->m[k].c, &n, &b);
+        if (rc)
+            return member_fail(g, (int)k, rc);
+        count += n;
+        bytes += b;
+    }
+    if (n_preroll)
+        *n_preroll = count;
+    if (preroll_bytes)
+        *preroll_bytes = bytes;
     return SDRX_OK;
 }
 

@@ -12,6 +12,15 @@
 //                    case (every leaf open): workgroups of closed leaves, and of tiles behind a leaf's end, return at once.
 //
 // No atomics, no grid-wide barrier; plain vector loads and stores.
+//
+// Option "preroll"  launches the second form of both kernels (template parameter PRE, and what it needs
+// besides in a trailing argument that is empty for the first form: the option off runs the kernels above as they were).
+// One more bit of per-leaf state, prev_open (1 after finalize, then the previous gate's `open`):
+//     pre = open && !prev_open;  prev_open = open
+// A pre-rolled leaf takes 2 * pay_units in the prefix sum -- its payload of frame f-1 (still in the other parity of d_pay) at
+// its offset, that of frame f directly behind -- and the directory gains pre[n] behind hang[n], the header the count of
+// pre-rolled leaves.  The gather's grid gets a third dimension: z = 0 copies from d_pay[p] as before, z = 1 from d_pay[p ^ 1]
+// and returns after one 4-byte load unless the leaf is pre-rolled.
 #pragma once
 
 namespace sdrx {
@@ -33,11 +42,20 @@ struct SqHeader { // 64 bytes in front of the directory's per-leaf arrays
     long long frame;
     unsigned n_open, n_leaves;
     unsigned long long packed_bytes;
-    unsigned long long pad[5];
+    unsigned long long pad[5]; // option preroll: pad[0] = pre-rolled leaves of this frame; zero otherwise
 };
 struct SqJob { // sdrx_set_squelch: leaf `index` (publish order) gets thr / hang_frames, its hang_left restarts at 0
     unsigned long long thr;
     unsigned hang_frames, index;
+};
+
+template <bool PRE>
+struct SqPre { // what the second form of the gate's kernels is given besides (option preroll); empty for the first
+};
+template <>
+struct SqPre<true> {
+    unsigned *prev_open;           // k_squelch_scan: per leaf, 1 = the previous gate left it open
+    const unsigned char *pay_prev; // k_squelch_gather: d_pay[p ^ 1], the payloads of the frame before
 };
 
 __global__ __launch_bounds__(64) void k_squelch_set(const SqJob *__restrict__ jobs, int n, SqCfg *__restrict__ cfg, unsigned *__restrict__ hang_left)
@@ -54,19 +72,23 @@ __global__ __launch_bounds__(64) void k_squelch_set(const SqJob *__restrict__ jo
     hang_left[J.index] = 0;
 }
 
-// dir: SqHeader | unsigned offs[n] | unsigned hang[n]
+// dir: SqHeader | unsigned offs[n] | unsigned hang[n] | PRE: unsigned pre[n]
+template <bool PRE = false>
 __global__ __launch_bounds__(kSqThreads) void k_squelch_scan(const SqLeaf *__restrict__ leaves, const SqCfg *__restrict__ cfg,
                                                              unsigned *__restrict__ hang_left, const unsigned char *__restrict__ pay,
-                                                             unsigned char *__restrict__ dir, int n, long long frame)
+                                                             unsigned char *__restrict__ dir, int n, long long frame, SqPre<PRE> X)
 {
     __shared__ unsigned s_units[kSqThreads / 64], s_open[kSqThreads / 64];
+    __shared__ unsigned s_pre[PRE ? kSqThreads / 64 : 1]; // (PRE = false never touches it and the compiler drops it: 128 bytes
+                                                          //   of LDS as before; a declaration cannot sit under `if constexpr`)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     unsigned *offs = reinterpret_cast<unsigned *>(dir + sizeof(SqHeader));
     unsigned *hang = offs + n;
     unsigned run_u = 0, run_o = 0; // units and open leaves of the passes so far (the same in every lane)
+    unsigned run_p = 0;            // PRE: pre-rolled leaves
     for (int i0 = 0; i0 < n; i0 += kSqThreads) { // pass: leaves i0 .. i0 + 1023, leaf i0 + t in lane t (coalesced loads)
         const int i = i0 + t;
-        unsigned units = 0, is_open = 0;
+        unsigned units = 0, is_open = 0, pre = 0;
         if (i < n) {
             const SqLeaf L = leaves[i];
             const SqCfg C = cfg[i];
@@ -87,6 +109,12 @@ __global__ __launch_bounds__(kSqThreads) void k_squelch_scan(const SqLeaf *__res
             hang_left[i] = h;
             hang[i] = h;
             units = is_open ? L.pay_units : 0u;
+            if constexpr (PRE) {
+                pre = is_open & (X.prev_open[i] == 0u);
+                X.prev_open[i] = is_open;
+                hang[n + i] = pre; // (pre[] lies behind hang[])
+                units += pre ? L.pay_units : 0u; // frame f-1's payload in front of frame f's
+            }
         }
         // inclusive scan over the wave, the waves' totals through LDS
         unsigned su = units, so = is_open;
@@ -102,6 +130,11 @@ __global__ __launch_bounds__(kSqThreads) void k_squelch_scan(const SqLeaf *__res
             s_units[wave] = su;
             s_open[wave] = so;
         }
+        if constexpr (PRE) { // (only the total is wanted)
+            const unsigned long long m = __ballot(pre != 0);
+            if (lane == 0)
+                s_pre[wave] = (unsigned)__popcll(m);
+        }
         __syncthreads();
         unsigned base = run_u + su - units;
 #pragma unroll
@@ -110,6 +143,11 @@ __global__ __launch_bounds__(kSqThreads) void k_squelch_scan(const SqLeaf *__res
                 base += s_units[w];
             run_u += s_units[w];
             run_o += s_open[w];
+        }
+        if constexpr (PRE) {
+#pragma unroll
+            for (int w = 0; w < kSqThreads / 64; ++w)
+                run_p += s_pre[w];
         }
         if (i < n)
             offs[i] = is_open ? base : kSqClosed;
@@ -123,16 +161,26 @@ __global__ __launch_bounds__(kSqThreads) void k_squelch_scan(const SqLeaf *__res
         H.packed_bytes = 64ull * run_u;
         for (int k = 0; k < 5; ++k)
             H.pad[k] = 0;
+        if constexpr (PRE)
+            H.pad[0] = run_p;
         *reinterpret_cast<SqHeader *>(dir) = H;
     }
 }
 
-// grid (n leaves, tiles of the longest payload), 256 lanes
+// grid (n leaves, tiles of the longest payload[, PRE: source 0 = this frame's parity | 1 = the other one]), 256 lanes
+template <bool PRE = false>
 __global__ __launch_bounds__(256) void k_squelch_gather(const SqLeaf *__restrict__ leaves, const unsigned char *__restrict__ pay,
-                                                        const unsigned char *__restrict__ dir, unsigned char *__restrict__ pack)
+                                                        const unsigned char *__restrict__ dir, unsigned char *__restrict__ pack, SqPre<PRE> X)
 {
     const int i = blockIdx.x;
-    const unsigned off = reinterpret_cast<const unsigned *>(dir + sizeof(SqHeader))[i];
+    const unsigned *offs = reinterpret_cast<const unsigned *>(dir + sizeof(SqHeader));
+    unsigned pre = 0;
+    if constexpr (PRE) {
+        pre = offs[2 * gridDim.x + i]; // (pre[] behind offs[] and hang[]: one entry per leaf = per blockIdx.x)
+        if (blockIdx.z == 1 && pre == 0)
+            return;
+    }
+    unsigned off = offs[i];
     if (off == kSqClosed)
         return;
     const SqLeaf L = leaves[i];
@@ -140,11 +188,16 @@ __global__ __launch_bounds__(256) void k_squelch_gather(const SqLeaf *__restrict
     const unsigned tile = blockIdx.y * (unsigned)(kSqTile / 16);
     if (tile >= n16)
         return;
+    if constexpr (PRE) {
+        if (blockIdx.z == 1)
+            pay = X.pay_prev; // the pre-rolled payload at the leaf's offset ...
+        else if (pre)
+            off += L.pay_units; // ... this frame's behind it
+    }
     const uint4 *src = reinterpret_cast<const uint4 *>(pay + L.pay_off) + tile;
     uint4 *dst = reinterpret_cast<uint4 *>(pack + 64ull * off) + tile;
     const unsigned m = min(n16 - tile, (unsigned)(kSqTile / 16));
     for (unsigned k = threadIdx.x; k < m; k += 256)
         dst[k] = src[k];
 }
-
 } // namespace sdrx

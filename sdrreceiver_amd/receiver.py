@@ -53,7 +53,7 @@ class Receiver:
                  dc_blocked_scan: bool = False, pipeline: bool = False, fuse: bool = True, frame_pipeline: bool = True,
                  fuse_late: bool = True, keep_streams: bool = False, dc_speculative: bool = True,
                  dc_blocks_per_step: int | None = None, fuse_demod: bool = False,
-                 tail_in_levels: bool = True, meter: bool = False, squelch: bool = False):
+                 tail_in_levels: bool = True, meter: bool = False, squelch: bool = False, preroll: bool = False):
         self.L = _lib.lib()
         h = C.c_void_p()
         rc = self.L.sdrx_create(C.byref(h), int(device))
@@ -78,6 +78,8 @@ class Receiver:
         self._chk(self.L.sdrx_set_option(self.h, b"meter", int(bool(meter))))
         if squelch:  # (off is the library's default: a library without the option is never asked)
             self._chk(self.L.sdrx_set_option(self.h, b"squelch", 1))
+        if preroll:
+            self._chk(self.L.sdrx_set_option(self.h, b"preroll", 1))
         self._chk(self.L.sdrx_set_option(self.h, b"dc_speculative", int(bool(dc_speculative))))
         if dc_blocks_per_step is not None:
             self._chk(self.L.sdrx_set_option(self.h, b"dc_blocks_per_step", int(dc_blocks_per_step)))
@@ -243,6 +245,21 @@ class Receiver:
         f, o, n, b = C.c_int64(), C.c_uint32(), C.c_uint32(), C.c_uint64()
         self._chk(self.L.sdrx_get_egress(self.h, C.byref(f), C.byref(o), C.byref(n), C.byref(b)))
         return {"frame": f.value, "n_open": o.value, "n_leaves": n.value, "payload_bytes_copied": b.value}
+
+    def preroll(self, vid: int) -> np.ndarray:
+        """Option ``preroll``: leaf `vid`'s payload of the frame before the delivered one, if the leaf has just opened (what
+        the callback saw first); an empty array of the leaf's dtype otherwise."""
+        buf, ln, f = C.c_void_p(), C.c_uint32(), C.c_int64()
+        self._chk(self.L.sdrx_get_preroll(self.h, vid, C.byref(buf), C.byref(ln), C.byref(f)))
+        raw = C.string_at(buf.value, ln.value) if ln.value else b""
+        return np.frombuffer(raw, dtype=np.int16 if self.descs[vid].demod_usb else np.int8).copy()
+
+    def preroll_count(self) -> dict:
+        """Pre-rolled leaves of the last delivered frame and the bytes that added to its copy: ``n_preroll``,
+        ``preroll_bytes``."""
+        n, b = C.c_uint32(), C.c_uint64()
+        self._chk(self.L.sdrx_get_preroll_count(self.h, C.byref(n), C.byref(b)))
+        return {"n_preroll": n.value, "preroll_bytes": b.value}
 
     def output_rate(self, vid: int) -> int:
         rate = C.c_uint32()
@@ -499,6 +516,19 @@ class Group:
         f, o, n, b = C.c_int64(), C.c_uint32(), C.c_uint32(), C.c_uint64()
         self._chk(self.L.sdrx_group_get_egress(self.h, C.byref(f), C.byref(o), C.byref(n), C.byref(b)))
         return {"frame": f.value, "n_open": o.value, "n_leaves": n.value, "payload_bytes_copied": b.value}
+
+    def preroll(self, vid: int) -> np.ndarray:
+        """:meth:`Receiver.preroll` with an id of the whole tree (group option ``preroll=1``)."""
+        buf, ln, f = C.c_void_p(), C.c_uint32(), C.c_int64()
+        self._chk(self.L.sdrx_group_get_preroll(self.h, vid, C.byref(buf), C.byref(ln), C.byref(f)))
+        raw = C.string_at(buf.value, ln.value) if ln.value else b""
+        return np.frombuffer(raw, dtype=np.int16 if self.descs[vid].demod_usb else np.int8).copy()
+
+    def preroll_count(self) -> dict:
+        """:meth:`Receiver.preroll_count`, summed over the members."""
+        n, b = C.c_uint32(), C.c_uint64()
+        self._chk(self.L.sdrx_group_get_preroll_count(self.h, C.byref(n), C.byref(b)))
+        return {"n_preroll": n.value, "preroll_bytes": b.value}
 
     def locate(self, vid: int) -> tuple[int, int]:
         m, l = C.c_int(), C.c_int()

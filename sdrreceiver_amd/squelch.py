@@ -11,6 +11,14 @@ For every frame, with ``s`` the leaf's meter ``sum_sq`` of that frame (:mod:`sdr
 Integers only, so the decision is exact.  The library decides on the device (``k_squelch_scan``), packs the open
 leaves' payloads and copies only those to the host; :func:`decide` restates the rule for the tests.
 
+Option ``preroll`` adds one bit of state per leaf, ``prev_open``: 1 after finalize (frame 0 has no predecessor), and after
+every frame that frame's ``open``; ``set_squelch`` does not touch it.  With ``open(f)`` as above::
+
+    pre(f) = open(f) and not prev_open;   prev_open = open(f)
+
+A frame with ``pre(f) = 1`` for a leaf is delivered with the leaf's payload of frame ``f-1`` ahead of that of ``f``
+(:func:`preroll_flags`).  One frame and no more: it is what the device still holds.
+
 There is deliberately no default threshold: what level separates a live channel from an idle one on a real front end
 has not been measured.  Read ``meters()`` of the closed leaves (they are always reported) and choose.
 """
@@ -46,6 +54,17 @@ def decide(sum_sq_per_frame, thr, hang_frames, hang_left: int = 0, return_state:
     if return_state:
         return flags, np.array(lefts, np.int64).reshape(len(lefts))
     return flags
+
+
+def preroll_flags(open_flags, prev_open: int = 1):
+    """The pre-roll flag of one leaf for each frame of `open_flags` (what :func:`decide` returns), starting from
+    `prev_open` (1 after finalize)."""
+    prev, out = int(bool(prev_open)), []
+    for o in open_flags:
+        o = int(bool(o))
+        out.append(int(o and not prev))
+        prev = o
+    return np.array(out, np.int32).reshape(len(out))
 
 
 def threshold(rms_dbfs: float, n_values: int, full_scale: float) -> int:

@@ -9,6 +9,12 @@ min and max): meter=1 squelch=0 (baseline b), and squelch=1 with 100 %, 50 %, 10
 for the open ones, 2^63 for the others, spread evenly over the tree).  --parent-lib FILE adds baseline (a): a library built
 from the parent commit, loaded in a child process through SDRX_LIB (it lacks the squelch entry points, so the child asks for
 none of them), plain options, timed in the same run.  Prints one JSON line.
+
+Option preroll, at 10 % open: `preroll_10pct` is the `open_10pct` receiver's twin with preroll=1 and the same
+static open set -- no leaf ever re-opens, so the difference to `open_10pct` is the gate's second form alone.  `rot_squelch_10pct`
+and `rot_preroll_10pct` rotate the open set EVERY frame (set_squelch; submit; wait -- a set needs an empty queue, so these two
+rows have no frame of look-ahead and compare with each other only): with preroll every open leaf is then pre-rolled and the
+copy doubles.
 """
 import argparse
 import json
@@ -20,7 +26,8 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-NEW = ("sdrx_set_squelch", "sdrx_get_squelch", "sdrx_get_egress", "sdrx_group_set_squelch", "sdrx_group_get_squelch", "sdrx_group_get_egress")
+NEW = ("sdrx_set_squelch", "sdrx_get_squelch", "sdrx_get_egress", "sdrx_group_set_squelch", "sdrx_group_get_squelch", "sdrx_group_get_egress",
+       "sdrx_get_preroll", "sdrx_get_preroll_count", "sdrx_group_get_preroll", "sdrx_group_get_preroll_count")
 FRACTIONS = (1.0, 0.5, 0.1, 0.01)
 
 
@@ -36,6 +43,20 @@ def timed(rx, host, steps, warmup):
     ms = (time.perf_counter() - t0) * 1e3 / steps
     rx.wait()
     return ms
+
+
+def timed_rotating(rx, host, steps, warmup, lv, sets):
+    def one(i):
+        thr, hang = sets[i % len(sets)]
+        rx.set_squelch(lv, thr, hang)
+        rx.submit(host)
+        rx.wait()
+    for i in range(warmup):
+        one(i)
+    t0 = time.perf_counter()
+    for i in range(steps):
+        one(warmup + i)
+    return (time.perf_counter() - t0) * 1e3 / steps
 
 
 def summary(v):
@@ -84,13 +105,23 @@ def main():
             is_open[np.unique(np.linspace(0, len(lv) - 1, n_open).round().astype(int))] = True
             rx.set_squelch(lv, [0 if x else 1 << 63 for x in is_open], [0] * len(lv))
             rxs[f"open_{round(100 * frac)}pct"] = rx
-        for rx in rxs.values():
+        static10 = np.zeros(len(lv), bool)
+        static10[np.unique(np.linspace(0, len(lv) - 1, max(1, round(0.1 * len(lv)))).round().astype(int))] = True
+        rxs["preroll_10pct"] = Receiver.from_topology(topo, device=0, preroll=True)
+        rxs["preroll_10pct"].set_squelch(lv, [0 if x else 1 << 63 for x in static10], [0] * len(lv))
+        rot = {"rot_squelch_10pct": Receiver.from_topology(topo, device=0, squelch=True),
+               "rot_preroll_10pct": Receiver.from_topology(topo, device=0, preroll=True)}
+        hang0 = np.zeros(len(lv), np.uint32)
+        sets = [(np.where(np.arange(len(lv)) % 10 == j, np.uint64(0), np.uint64(1 << 63)), hang0) for j in range(10)]  # disjoint tenths
+        for rx in list(rxs.values()) + list(rot.values()):
             rx.set_publish(False)
-        times = {k: [] for k in rxs}
+        times = {k: [] for k in list(rxs) + list(rot)}
         parent = []
         for r in range(a.reps):
             for k, rx in rxs.items():
                 times[k].append(timed(rx, host, a.steps, a.warmup))
+            for k, rx in rot.items():
+                times[k].append(timed_rotating(rx, host, a.steps, a.warmup, lv, sets))
             if a.parent_lib:  # one round of the parent's library between ours, in a process of its own
                 out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--steps", str(a.steps), "--warmup",
                                       str(a.warmup), "--reps", "1"], env={**os.environ, "SDRX_LIB": os.path.abspath(a.parent_lib)},
@@ -99,13 +130,16 @@ def main():
         for k, v in times.items():
             result[f"{name}_{k}"] = summary(v)
             if k != "meter1_squelch0":
-                eg = rxs[k].egress()
+                eg = {**rxs, **rot}[k].egress()
                 result[f"{name}_{k}"].update(n_open=eg["n_open"], payload_bytes_copied=eg["payload_bytes_copied"])
+            if "preroll" in k:
+                result[f"{name}_{k}"].update({**rxs, **rot}[k].preroll_count())
         if parent:
             result[f"{name}_parent_lib"] = summary(parent)
         result[f"{name}_device_bytes"] = {"meter1_squelch0": rxs["meter1_squelch0"].stats()["device_bytes"],
-                                          "squelch1": rxs["open_100pct"].stats()["device_bytes"]}
-        for rx in rxs.values():
+                                          "squelch1": rxs["open_100pct"].stats()["device_bytes"],
+                                          "preroll1": rxs["preroll_10pct"].stats()["device_bytes"]}
+        for rx in list(rxs.values()) + list(rot.values()):
             rx.close()
     print(json.dumps(result))
     if a.out:
