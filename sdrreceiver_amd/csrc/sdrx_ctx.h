@@ -1,0 +1,288 @@
+// sdrx_ctx.h -- what a context IS: the VFO tree's nodes, the launch plans finalize leaves behind, and sdrx_ctx itself with its
+// state grouped by concern; plus the error helpers every part of the host side uses.  A fragment of the one translation unit
+// (sdrx.hip includes it behind the kernels); it is not a public header.
+#pragma once
+
+namespace {
+
+thread_local std::string g_create_error;
+
+enum Kind { KIND_MIX_ROOT = 0, KIND_MIX_SUB = 1, KIND_LATE_DEC = 2, KIND_DEMOD = 3, KIND_COMPRESS = 4, KIND_INGEST = 5, KIND_LEVELS = 6, KIND_LPF_LONG = 7 };
+const char *kKindNames[SDRX_NKERNELS] = {"k_mix_decimate(level0)", "k_mix_decimate(sub)", "k_late_decimate", "k_usb_demod",
+                                         "k_compress",             "k_ingest",            "k_mix_levels",    "k_lpf_long"};
+
+struct Node {
+    sdrx_vfo_desc d;
+    std::vector<int> children;
+    int level = 0;
+    int n_f = 0;       // samples of decimate[d] per frame
+    int n_out = 0;     // after late decimation
+    unsigned rate = 0; // outputRate
+    bool leaf = false;
+    // designed taps (host copies for sdrx_get_taps)
+    std::vector<float> lpf, dec, hilbert;
+    std::vector<float> lpf_pad, hnz; // device forms: zero-padded low-pass, compacted Hilbert
+    std::vector<float> hnz_e, hnz_o; //   ... and the compacted Hilbert taps shifted by 3 / 2 in 96 zero-padded floats (hilbert4_packed)
+    size_t off_hnz_e = 0, off_hnz_o = 0;
+    int demod_tile = 1024;           // outputs per k_usb_demod block
+    bool long_lpf = false;           // audio low-pass of more than kMaxFir taps: applied by k_lpf_long
+    int Hu = 0;                      // its history length (usb floats of the previous frame)
+    size_t off_u[2] = {0, 0};        // its input: [hist Hu | data n_out] usb floats per frame parity
+    // device placement (byte offsets into the arena)
+    size_t off_cp = 0, off_hb[2] = {0, 0}, off_stream[2] = {0, 0}, off_z[2] = {0, 0}, off_preq = 0;
+    size_t off_lpf = 0, off_dec = 0, off_hilbert = 0, off_hnz = 0;
+    int H = 0, Hx = 0;
+    size_t pay_off = 0; // into the payload buffer
+    uint32_t pay_len = 0;
+    float rot_re = 0, rot_im = 0;
+    int fused_late = 0;     // 5 | 6: the late decimation runs inside the mix wave (late_item); 0: not
+    bool fused_demod = false; // the USB demodulation runs inside the mix wave (demod_chunk): the leaf writes its payload itself
+    size_t off_dstate[2] = {0, 0}; //   ... its demodulation history per frame parity (kDemodStateFloats floats)
+    int d2_index = -1;      // its K2Vfo in the demodulation descriptor array
+    int d4_index = -1;      // its K4Vfo (long_lpf): k_lpf_long applies the gain
+    bool has_stream = true; // decimate[d] of every frame is kept in HBM (false: a fused late decimation writes only z', a fused demodulation only the payload)
+    int meter_first = 0, meter_n = 0; // option meter: this leaf's records, slots [meter_first, meter_first + meter_n) behind the payloads
+    int meter_shift = 0;              //   ... fuse_demod: the record of a mix item is s_first_out >> meter_shift
+};
+
+struct Launch1 { // one k_mix_decimate launch (a tree level)
+    int kind;
+    int level;
+    int n_work;
+    int lds_bytes;
+    size_t off_work; // arena offset of K1Work[]
+    int64_t alg_bytes;
+};
+struct LaunchB { // block-per-tile launches (late decimate / demod / compress): one launch per kernel
+    int kind;
+    int n_blocks;
+    size_t off_desc, off_work;
+    int lds_bytes;
+    int64_t alg_bytes;
+    size_t off_mrel = 0; // option meter, k_lpf_long: arena offset of the blocks' record offsets (int[n_blocks])
+};
+
+// The one-launch levels (k_mix_levels): the list is [level 0 items | level 1 items | ...], every part
+// starting at a multiple of 8 entries.  A launch covers the contiguous range of the levels that have a
+// frame to work on.
+struct LevelPlan {
+    bool usable = false;
+    size_t off_items = 0, off_item_level = 0, off_list = 0; // arena offsets
+    std::vector<int> part_begin, part_end;                   // list range of every level
+    std::vector<int64_t> part_bytes;                         // SURVEY 8d share of every level
+    int lds_bytes = 0;
+    // Option tail_in_levels: k_levels_tail's workgroup list [level n-1 | ... | level 0 | demodulation blocks], each part from a
+    // multiple of 8 workgroups (TailWg, kernels.hip); the demodulation of a frame then rides in the launch after the one that
+    // finished its last level.  tail = false: k_mix_levels, and k_usb_demod behind the launch that finished the frame.
+    bool tail = false;
+    size_t off_wgs = 0;
+    std::vector<int> wg_begin, wg_end; // workgroup range of every level
+    int dm_begin = 0, dm_end = 0;      // ... and of the demodulation blocks
+    int lds_wave = 0, tail_lds = 0;    // LDS of one mix wave; of a workgroup
+    int64_t dm_bytes = 0;              // SURVEY 8d share of the demodulation
+};
+struct InFlight { // a frame inside the software pipeline: `next` = the level that runs it in the next launch (n_levels: its
+                  // demodulation, with LevelPlan::tail)
+    unsigned long long f;
+    int next;
+};
+
+struct TimedEvent {
+    hipEvent_t a, b;
+    int kind;
+    int64_t bytes;
+};
+
+} // namespace
+
+struct sdrx_ctx {
+    int device = 0;
+    std::string err;
+    std::vector<Node> nodes;
+    bool finalized = false;
+    int opt_exact = 1, opt_prequant = 0, opt_segments = 0, opt_dc_blocked = 0, opt_pipeline = 0, opt_dc_speculative = 1;
+    int opt_fuse = 1, opt_frame_pipeline = 1, opt_fuse_late = 1, opt_keep_streams = 0, opt_fuse_demod = 0;
+    int opt_tail_in_levels = 1;
+    int opt_meter = 0, opt_squelch = 0, opt_preroll = 0;
+    // option meter: per frame parity, behind the payloads in d_pay / h_pay (at meter_off), one 16-byte MeterAcc record per work
+    // unit that emits payload values (kernels.hip "output meters"); the records travel in the payload copy
+    size_t meter_off = 0;
+    int meter_slots = 0;
+
+    // Option squelch (squelch.hip): per frame parity the gate's directory sits behind the meter records in d_pay /
+    // h_pay (at dir_off: SqHeader | offset per leaf | hang_left per leaf, leaves in publish order) -- [meter_off, pay_bytes) is the
+    // fixed-size part that always travels -- and the open leaves' payloads are packed into d_pack[p]; the host receives them at
+    // the start of h_pay[p], whose payload region they can never outgrow.
+    // Option preroll: a leaf that opens in frame f after the gate closed it in f-1 is delivered with its payload
+    // of f-1 in front of that of f.  prev_open per leaf on the device; the directory gains pre[n] behind hang[n]; d_pack[p] holds
+    // the worst case (every leaf re-opens: twice the payload region), and so does its host side, which then lies BEHIND the
+    // fixed part of h_pay[p] (at hpack_off; 0 with the option off: the start of h_pay[p], as before).
+    struct Squelch {
+        size_t dir_off = 0, pack_bytes = 0, bytes = 0; // bytes: what the option allocates besides the directory
+        unsigned char *d_pack[2] = {nullptr, nullptr};
+        SqLeaf *d_leaves = nullptr;
+        SqCfg *d_cfg = nullptr;
+        unsigned *d_hang = nullptr; // hang_left per leaf: one array, every gate runs in frame order on one stream
+        unsigned *d_prev = nullptr; // prev_open per leaf (preroll)
+        SqJob *d_jobs = nullptr;
+        size_t jobs_cap = 0;
+        int tiles = 1;                        // k_squelch_gather's grid.y: 16 KiB tiles of the longest payload
+        std::vector<int> index;               // node -> its place in publish order (-1: not a leaf)
+        std::vector<SqCfg> cfg;               // host copy of the thresholds
+        std::vector<unsigned> offs, hang;     // the directory of the last DELIVERED frame
+        unsigned n_open = 0;                  //   ... its header
+        unsigned long long copied = 0;        //   ... and the payload bytes its copy moved
+        unsigned long long copied_slot[2] = {0, 0};
+        size_t hpack_off = 0;
+        bool preroll_fused = false;           // a leaf demodulates in its mix wave: the levels write d_pay (enqueue_frame)
+        std::vector<unsigned> pre, units;     // the delivered directory's pre-roll flags; 64-byte units of every leaf's payload
+        unsigned n_pre = 0;                   // pre-rolled leaves of the delivered frame
+        unsigned long long pre_bytes = 0;     //   ... and the packed bytes their pre-roll added to the copy
+        hipEvent_t ev_dir[2] = {nullptr, nullptr}; // the fixed-size part of frame f is in h_pay[f & 1]
+    } sq;
+
+    // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
+    // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first
+    // frame that fills them.  The first such leaf uses the arena's buffer, further ones buffers of their own (hipMalloc).
+    struct TapBuf {
+        float2 *buf[2] = {nullptr, nullptr};
+        unsigned long long since = 0;
+        bool own = false;
+    };
+    std::map<int, TapBuf> taps;
+    size_t tap_len = 0, off_tapbuf[2] = {0, 0}; // the arena's tap buffer (sized for the longest fused leaf), per frame parity
+    LevelPlan fp;
+    std::vector<InFlight> pipe; // oldest first
+    sdrx_publish_fn cb = nullptr;
+    void *cb_user = nullptr;
+
+    // Streams.  `stream` (the context's own or the caller's) carries the ingest and the
+    // mix/decimate launches of every tree level; the leaf tail of a frame runs on `tail_stream`
+    // when option "pipeline" is on (off by default: measured slower, profiles/README.md); payloads leave on
+    // `copy_stream` for frames that came in through sdrx_submit*.  Cross-stream order is by the
+    // per-parity events below (measured on this runtime, tools/event_probe.hip: a record costs its
+    // stream ~3-5 us, a wait on an event that completed long ago ~2.5 us, a tight hop ~11 us).
+    struct Streams {
+        hipStream_t own_stream = nullptr, stream = nullptr, tail_stream = nullptr, copy_stream = nullptr, copy_stream2 = nullptr; // copy_stream2: odd frames
+        hipEvent_t ev_levels[2] = {nullptr, nullptr}; // levels of frame f done (recorded on `stream`)
+        hipEvent_t ev_tail[2] = {nullptr, nullptr};   // tail of frame f done (recorded on the tail's stream)
+        hipEvent_t ev_copied[2] = {nullptr, nullptr}; // payloads of frame f are in h_pay[f & 1]
+        hipEvent_t ev_staged[2] = {nullptr, nullptr}; // the host frame of parity p is complete on the device
+        bool tail_recorded[2] = {false, false};
+    } st;
+    bool long_frame = false;             // the frame's kernels outlast its payload copy (the DC-bias recurrence): the copy is issued by sdrx_wait
+    bool copy_owed[2] = {false, false};  //   ... and not issued yet
+    unsigned char *arena = nullptr;
+    size_t arena_bytes = 0;
+    unsigned char *d_pay[2] = {nullptr, nullptr}, *h_pay[2] = {nullptr, nullptr}; // per frame parity
+    size_t pay_bytes = 0;
+    unsigned char *h_in[2] = {nullptr, nullptr}; // pinned staging of host-fed frames, per frame parity
+    size_t h_in_bytes = 0;
+    int in_flight = 0;               // frames submitted (sdrx_submit*) and not yet delivered (sdrx_wait)
+    bool broken = false;             // fault injection (SDRX_FAULT_WAIT): every frame call fails from here on, like after a HIP error
+    int host_slot = -1;              // which h_pay holds the payloads sdrx_get_output serves
+    unsigned long long host_frame = 0; // ... and which frame they are
+    float2 *d_raw[2] = {nullptr, nullptr}; // host-fed frames on the device (natural order), per frame parity: frame f's
+                                           //   buffer stays untouched until f+2 is staged (another context on this device may
+                                           //   be working on it: sdrx_submit_shared)
+    // other contexts that ran on this context's uploaded frame of parity p (sdrx_submit_shared): each left an event behind its
+    // kernels, and this context's next upload into that buffer waits for them (events owned, and reused, by this context).
+    // No lock: `ctx` and `src` of a sharing call must be driven from ONE thread (sdrx.h).
+    struct SharedReader {
+        const sdrx_ctx *who; // (identity only: never dereferenced)
+        hipEvent_t ev;       // behind who's kernels on this context's frame of that parity; owned by THIS context
+        bool pending;        // recorded since this context last waited for it
+    };
+    std::vector<SharedReader> shared_readers[2]; // at most one entry per (reader, parity): re-recorded, never piled up
+    float2 *d_raw_tiled = nullptr; // the raw frame in tile layout: input of the parent-less VFOs
+    int last_raw = -1;             // how the last frame reached level 0 (kRaw*; -1: caller-owned device memory)
+    bool late4 = false;            // k_late_decimate4 serves the late-decimation launch
+    bool root_direct = false;      // level 0 reads the caller's natural-order frame itself (few VFOs)
+    unsigned char *d_raw_u8[2] = {nullptr, nullptr}; // the same for dongle bytes
+    struct DcBias { // DC-bias removal of dongle bytes (sdrx_*_u8 with correct_dc), allocated by the first such frame
+        float *d_state = nullptr;   // accumulator (exact: [2]; fast: [parity][2])
+        float *d_work = nullptr;    // exact removal: products P[2][stride] and estimates A[2][stride] of one frame
+        unsigned long long *d_counters = nullptr; // k_dc_chain_spec: [0] blocks walked, [1] blocks redone with the sequential operations, [2] blocks taken again on their own
+        int waves = 8;              // k_dc_chain_spec: blocks per step = waves per workgroup (option dc_blocks_per_step: 1, 2, 4, 8)
+        int work_stride = 0;
+        double *d_tab = nullptr;    // fast scan: powers of the decay + per-chunk sums behind them
+        unsigned long long frames = 0; // frames the fast scan has run on (its state ping-pongs)
+        size_t tab_sums = 0;        // offset (in doubles) of the double2 sums[] inside d_tab
+    } dc;
+    size_t raw_cap = 0;
+    int root_frame = 0; // samples_per_buffer of the parent-less VFOs
+    size_t off_k1vfo = 0;
+    size_t off_k2 = 0, off_k4 = 0; // the K2Vfo / K4Vfo arrays (sdrx_set_gains patches their gain)
+    RetuneJob *d_jobs = nullptr;   // k_vfo_retune's job list (sdrx_set_mixer_freqs, sdrx_set_gains), grown on demand
+    size_t jobs_cap = 0;
+    std::vector<Launch1> l1;
+    std::vector<LaunchB> lb;
+    std::vector<int> publish_order;
+    unsigned long long frame_no = 0;
+    bool pending_fetch = false;
+    int64_t alg_bytes = 0, vfo_samples = 0, mix_chunks = 0;
+    int n_levels = 0;
+
+    struct Timing { // sdrx_enable_kernel_timing: an event pair around every launch (Bracket, sdrx_frame.hip)
+        bool on = false;
+        std::vector<TimedEvent> pending;
+        std::vector<hipEvent_t> pool;
+        double ms[SDRX_NKERNELS] = {0};
+        int64_t n[SDRX_NKERNELS] = {0};
+        int64_t bytes[SDRX_NKERNELS] = {0};
+    } tm;
+
+    // spectrum display (sdrx_set_spectrum): state slot id of a VFO, nodes.size() of the raw frame.  All of it is allocated by
+    // sdrx_set_spectrum; with nothing enabled the frame sequence launches nothing more.
+    struct SpecState {
+        double *pwr = nullptr; // kSpecN doubles, then kSpecN cf32 bins (one allocation)
+        bool on = false;
+    };
+    struct Spectrum {
+        std::vector<SpecState> slots;  // per slot
+        SpecRecord *d_rec = nullptr;   // per slot (one array: sdrx_get_spectrum_levels is one copy)
+        float2 *d_tw = nullptr;        // kiss_fft's twiddles, then the Hann window (kSpecN floats)
+        SpecDesc *d_desc = nullptr;    // the VFO spectra that have a stream, by tree level; then the raw one
+        int n_desc = 0;                // VFO descriptors in d_desc
+        std::vector<int> level_begin;  // first descriptor of every level (n_levels + 1 entries)
+        bool raw_on = false;
+        int raw_count = 0;             // sdrj's `count` (sdrj.cpp:84-101, 296-303)
+    } spec;
+};
+
+namespace {
+
+int fail(sdrx_ctx *c, int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (c)
+        c->err = buf;
+    else
+        g_create_error = buf;
+    return code;
+}
+
+#define HIPCHK(c, expr)                                                                         \
+    do {                                                                                        \
+        hipError_t e_ = (expr);                                                                 \
+        if (e_ != hipSuccess)                                                                   \
+            return fail((c), SDRX_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+struct ArenaPlan {
+    size_t size = 0;
+    size_t take(size_t bytes)
+    {
+        size_t o = align_up(size, 256);
+        size = o + bytes;
+        return o;
+    }
+};
+
+} // namespace

@@ -1,0 +1,458 @@
+// sdrx_delivery.hip -- how a frame's payloads reach the host and the caller: the egress copies, sdrx_wait / sdrx_fetch, the
+// publish callbacks, and the calls that read the delivered frame (output, meters, squelch, egress, pre-roll).
+// A fragment of sdrx.hip's translation unit.
+
+namespace {
+
+// Leaf `id`'s payload of the delivered frame in host slot `slot`.  Option squelch: through the delivered directory -- a closed
+// leaf has *len = 0 (the pointer is valid and not to be read).
+const unsigned char *leaf_payload(const sdrx_ctx *c, int id, int slot, uint32_t *len)
+{
+    const Node &n = c->nodes[(size_t)id];
+    *len = n.pay_len;
+    if (!c->opt_squelch)
+        return c->h_pay[slot] + n.pay_off;
+    const size_t k = (size_t)c->sq.index[(size_t)id];
+    const unsigned off = c->sq.offs[k];
+    if (off == kSqClosed) {
+        *len = 0;
+        return c->h_pay[slot];
+    }
+    if (c->opt_preroll && c->sq.pre[k]) // the pre-rolled payload lies in front
+        return c->h_pay[slot] + c->sq.hpack_off + 64 * ((size_t)off + c->sq.units[k]);
+    return c->h_pay[slot] + c->sq.hpack_off + 64 * (size_t)off;
+}
+// Option preroll: leaf `id`'s payload of the frame BEFORE the delivered one, if the delivered frame carries it (else *len = 0)
+const unsigned char *leaf_preroll(const sdrx_ctx *c, int id, int slot, uint32_t *len)
+{
+    *len = 0;
+    if (!c->opt_preroll)
+        return c->h_pay[slot];
+    const size_t k = (size_t)c->sq.index[(size_t)id];
+    if (c->sq.offs[k] == kSqClosed || !c->sq.pre[k])
+        return c->h_pay[slot];
+    *len = c->nodes[(size_t)id].pay_len;
+    return c->h_pay[slot] + c->sq.hpack_off + 64 * (size_t)c->sq.offs[k];
+}
+
+// vfo::transmitData for every leaf, in the reference's order (vfo.cpp:426-453, sdrj.cpp:288-294)
+void publish_all(sdrx_ctx *c, int slot)
+{
+    c->host_slot = slot;
+    if (!c->cb)
+        return;
+    for (int i : c->publish_order) {
+        const Node &n = c->nodes[(size_t)i];
+        // USB leaves always publish; an IQ leaf only with a topic; ZmqPublisher::publish sends
+        // nothing for len 0 (zmqpublisher.cpp:88) -- which is also what a leaf closed by option squelch has.
+        uint32_t len = 0;
+        const unsigned char *pay = leaf_payload(c, i, slot, &len);
+        if (len == 0)
+            continue;
+        if (!n.d.demod_usb && n.d.topic[0] == 0)
+            continue;
+        char topic[5] = {0, 0, 0, 0, 0};
+        for (int k = 0; k < 5 && n.d.topic[k]; ++k)
+            topic[k] = n.d.topic[k];
+        if (c->opt_preroll) { // a leaf that has just opened: the frame before, first
+            uint32_t plen = 0;
+            const unsigned char *pre = leaf_preroll(c, i, slot, &plen);
+            if (plen)
+                c->cb(c->cb_user, topic, n.rate, pre, plen);
+        }
+        c->cb(c->cb_user, topic, n.rate, pay, len);
+    }
+}
+
+// How the payloads of the frame of parity p leave the device: two steps, and these two functions ARE them -- enqueue_frame (a
+// frame that came through sdrx_submit*), start_owed_copy (sdrx_wait) and sdrx_fetch only choose the stream, what orders step 2
+// behind step 1 (an event or a stream synchronisation), and when copy_owed is cleared.
+//   1. queue_fixed_part (option squelch only): [meter_off, pay_bytes) of d_pay[p] -- meter records and directory -- which
+//      always travels, behind the gate of the frame;
+//   2. queue_payloads: with squelch the directory of step 1 must have ARRIVED in h_pay[p]: its packed_bytes says how much of
+//      d_pack[p] goes to h_pay[p] + hpack_off, in ONE copy (none if every leaf is closed); without squelch the whole of d_pay[p].
+// Both only read d_pay[p], d_pack[p] and the directory, whose next writer is frame f+2 (the safety argument above
+// enqueue_frame, sdrx_frame.hip).
+int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st)
+{
+    HIPCHK(c, hipMemcpyAsync(c->h_pay[p] + c->meter_off, c->d_pay[p] + c->meter_off, c->pay_bytes - c->meter_off, hipMemcpyDeviceToHost, st));
+    return SDRX_OK;
+}
+int queue_payloads(sdrx_ctx *c, int p, hipStream_t st)
+{
+    if (!c->opt_squelch) {
+        HIPCHK(c, hipMemcpyAsync(c->h_pay[p], c->d_pay[p], c->pay_bytes, hipMemcpyDeviceToHost, st));
+        return SDRX_OK;
+    }
+    SqHeader H;
+    memcpy(&H, c->h_pay[p] + c->sq.dir_off, sizeof H);
+    if (H.packed_bytes > c->sq.pack_bytes || H.packed_bytes % 64)
+        return fail(c, SDRX_EHIP, "squelch: the directory of frame %lld names %llu packed bytes, the buffer holds %zu", H.frame,
+                    H.packed_bytes, c->sq.pack_bytes);
+    if (H.packed_bytes)
+        HIPCHK(c, hipMemcpyAsync(c->h_pay[p] + c->sq.hpack_off, c->sq.d_pack[p], (size_t)H.packed_bytes, hipMemcpyDeviceToHost, st));
+    c->sq.copied_slot[p] = H.packed_bytes;
+    return SDRX_OK;
+}
+// Once the payloads are there too, the host's copy of the frame's directory: what sdrx_get_output, the callbacks,
+// sdrx_get_squelch and sdrx_get_egress serve until the next delivery
+void squelch_delivered(sdrx_ctx *c, int p)
+{
+    if (!c->opt_squelch)
+        return;
+    SqHeader H;
+    const unsigned char *dir = c->h_pay[p] + c->sq.dir_off;
+    memcpy(&H, dir, sizeof H);
+    const size_t n = c->sq.offs.size();
+    if (n) {
+        memcpy(c->sq.offs.data(), dir + sizeof H, 4 * n);
+        memcpy(c->sq.hang.data(), dir + sizeof H + 4 * n, 4 * n);
+    }
+    c->sq.n_open = H.n_open;
+    c->sq.copied = c->sq.copied_slot[p];
+    if (c->opt_preroll) {
+        if (n)
+            memcpy(c->sq.pre.data(), dir + sizeof H + 8 * n, 4 * n);
+        c->sq.n_pre = (unsigned)H.pad[0];
+        c->sq.pre_bytes = 0;
+        for (size_t k = 0; k < n; ++k)
+            if (c->sq.pre[k])
+                c->sq.pre_bytes += 64ull * c->sq.units[k];
+    }
+}
+
+// the oldest undelivered frame's payload copy, if sdrx_wait is the one to issue it (enqueue_frame: every frame under option
+// squelch -- its directory has arrived by now -- and frames that carry the DC recurrence: the host waits for the frame's last
+// kernel, then the copy goes out with nothing to wait for)
+int start_owed_copy(sdrx_ctx *c)
+{
+    if (c->in_flight <= 0)
+        return SDRX_OK;
+    const int p = (int)((c->frame_no - (unsigned long long)c->in_flight) & 1ull);
+    if (!c->copy_owed[p])
+        return SDRX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t cs = p ? c->st.copy_stream2 : c->st.copy_stream;
+    HIPCHK(c, hipEventSynchronize(c->opt_squelch ? c->sq.ev_dir[p] : c->st.ev_tail[p]));
+    if (int rc = queue_payloads(c, p, cs))
+        return rc;
+    HIPCHK(c, hipEventRecord(c->st.ev_copied[p], cs));
+    // only now: a wait retried after one of the calls above failed must find the copy still owed -- ev_copied[p] is still the
+    // event of frame f - 2, which completed long ago, and h_pay[p] still holds THAT frame's payloads
+    c->copy_owed[p] = false;
+    return SDRX_OK;
+}
+// Fault injection for the hosts' error paths (tests/test_dropin_qt.py): SDRX_FAULT_WAIT=k makes the k-th sdrx_wait of the PROCESS
+// fail like a HIP error does -- before the frame leaves the queue, and for good: every later frame call of that context fails
+// too (HIP errors are sticky).  One shot per process, so that a host which recovers by building a new context gets a sound one.
+bool injected_fault(sdrx_ctx *c, bool at_wait)
+{
+    static std::atomic<long> countdown{getenv("SDRX_FAULT_WAIT") ? atol(getenv("SDRX_FAULT_WAIT")) : 0};
+    if (c->broken)
+        return true;
+    if (at_wait && countdown.load() > 0 && countdown.fetch_sub(1) == 1)
+        c->broken = true;
+    return c->broken;
+}
+
+// the oldest undelivered frame's payloads are in host memory afterwards (slot returned); no callbacks
+int wait_frame(sdrx_ctx *c, int *slot)
+{
+    if (c->in_flight <= 0)
+        return fail(c, SDRX_ESTATE, "sdrx_wait: no submitted frame is in flight");
+    if (injected_fault(c, true))
+        return fail(c, SDRX_EHIP, "sdrx_wait: injected fault (SDRX_FAULT_WAIT): the context is unusable from here on");
+    int rc = start_owed_copy(c);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const unsigned long long f = c->frame_no - (unsigned long long)c->in_flight; // the oldest undelivered frame
+    const int p = (int)(f & 1ull);
+    HIPCHK(c, hipEventSynchronize(c->st.ev_copied[p]));
+    c->in_flight--;
+    c->host_slot = p;
+    c->host_frame = f;
+    squelch_delivered(c, p);
+    if (c->in_flight == 0)
+        drain_events(c);
+    *slot = p;
+    return SDRX_OK;
+}
+
+// The id list of a call that reads or sets per-leaf state: every id in range and a leaf, in list order; `once`: and listed once
+// (the setters).  The whole list is checked before the caller writes or changes anything.
+int check_leaf_ids(sdrx_ctx *c, const char *what, const int *ids, int n, bool once)
+{
+    std::vector<char> seen(once ? c->nodes.size() : 0, 0);
+    for (int k = 0; k < n; ++k) {
+        if (ids[k] < 0 || ids[k] >= (int)c->nodes.size())
+            return fail(c, SDRX_EINVAL, "%s: bad vfo id %d", what, ids[k]);
+        if (!c->nodes[(size_t)ids[k]].leaf)
+            return fail(c, SDRX_EINVAL, "%s: vfo %d has children and publishes nothing (vfo.cpp:253-266)", what, ids[k]);
+        if (once && seen[(size_t)ids[k]]++)
+            return fail(c, SDRX_EINVAL, "%s: vfo %d listed twice", what, ids[k]);
+    }
+    return SDRX_OK;
+}
+// A delivered frame is on the host (c->host_slot, c->host_frame) for the getter `what`: frames queued with sdrx_process_device are
+// brought over first (their payloads, records and directory).  `required` = false: a call that can answer without one.
+int need_delivered(sdrx_ctx *c, const char *what, bool required = true)
+{
+    if (c->in_flight > 0 && c->host_slot < 0)
+        return fail(c, SDRX_ESTATE, "%s: %d submitted frame(s), none delivered yet -- call sdrx_wait first", what, c->in_flight);
+    if (c->pending_fetch)
+        if (int rc = sdrx_fetch(c))
+            return rc;
+    if (required && c->host_slot < 0)
+        return fail(c, SDRX_ESTATE, "%s: no frame has been delivered yet", what);
+    return SDRX_OK;
+}
+} // namespace
+
+extern "C" {
+
+int sdrx_wait(sdrx_ctx *c)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    int p = 0;
+    const int rc = wait_frame(c, &p);
+    if (rc)
+        return rc;
+    publish_all(c, p);
+    return SDRX_OK;
+}
+
+int sdrx_fetch(sdrx_ctx *c)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_fetch before sdrx_finalize");
+    if (c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "sdrx_fetch: %d submitted frame(s) not yet delivered -- call sdrx_wait", c->in_flight);
+    if (c->frame_no == 0)
+        return fail(c, SDRX_ESTATE, "sdrx_fetch: no frame processed yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int p = (int)((c->frame_no - 1) & 1ull); // the last frame's payloads
+    hipStream_t ts = c->opt_pipeline ? c->st.tail_stream : c->st.stream;
+    if (int rc = pipeline_flush(c)) // frames still inside the software pipeline run to their end first
+        return rc;
+    if (c->pending_fetch && c->opt_squelch) { // the same two steps as sdrx_submit / sdrx_wait
+        if (int rc = queue_fixed_part(c, p, ts))
+            return rc;
+        HIPCHK(c, hipStreamSynchronize(ts));
+    }
+    if (c->pending_fetch)
+        if (int rc = queue_payloads(c, p, ts))
+            return rc;
+    int rc = drain(c);
+    if (rc)
+        return rc;
+    if (c->pending_fetch)
+        squelch_delivered(c, p);
+    c->pending_fetch = false;
+    c->host_frame = c->frame_no - 1;
+    publish_all(c, p);
+    return SDRX_OK;
+}
+
+int sdrx_get_output(sdrx_ctx *c, int id, const void **buf, uint32_t *len, uint32_t *rate)
+{
+    if (!c || id < 0 || id >= (int)c->nodes.size())
+        return fail(c, SDRX_EINVAL, "bad vfo id %d", id);
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_output before sdrx_finalize");
+    if (int rc = check_leaf_ids(c, "sdrx_get_output", &id, 1, false))
+        return rc;
+    if (int rc = need_delivered(c, "sdrx_get_output", buf != nullptr)) // (buf = NULL: a length query, good before any delivery)
+        return rc;
+    const Node &n = c->nodes[(size_t)id];
+    uint32_t pay_len = n.pay_len;
+    if (buf)
+        *buf = leaf_payload(c, id, c->host_slot, &pay_len);
+    else if (c->opt_squelch && c->host_slot >= 0)
+        (void)leaf_payload(c, id, c->host_slot, &pay_len);
+    if (len)
+        *len = pay_len;
+    if (rate)
+        *rate = n.rate;
+    return SDRX_OK;
+}
+
+int sdrx_get_meters(sdrx_ctx *c, const int *ids, int n, sdrx_meter *out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_meters before sdrx_finalize");
+    if (!c->opt_meter)
+        return fail(c, SDRX_ESTATE, "sdrx_get_meters: option \"meter\" is off");
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return fail(c, SDRX_EINVAL, "sdrx_get_meters: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
+    if (int rc = check_leaf_ids(c, "sdrx_get_meters", ids, n, false))
+        return rc;
+    if (n == 0)
+        return SDRX_OK;
+    if (int rc = need_delivered(c, "sdrx_get_meters"))
+        return rc;
+    const unsigned char *rec = c->h_pay[c->host_slot] + c->meter_off;
+    for (int k = 0; k < n; ++k) {
+        const Node &nd = c->nodes[(size_t)ids[k]];
+        sdrx_meter m;
+        memset(&m, 0, sizeof m);
+        m.frame = (int64_t)c->host_frame;
+        m.n_values = (uint32_t)(nd.d.demod_usb ? nd.n_out : 2 * nd.n_f);
+        uint32_t peak = 0;
+        for (int j = 0; j < nd.meter_n; ++j) { // {sum_sq u64, clipped u32, peak u32} per slot
+            const unsigned char *r = rec + 16 * (size_t)(nd.meter_first + j);
+            uint64_t sum;
+            uint32_t clipped, pk;
+            memcpy(&sum, r, 8);
+            memcpy(&clipped, r + 8, 4);
+            memcpy(&pk, r + 12, 4);
+            m.sum_sq += sum;
+            m.clipped += clipped;
+            peak = std::max(peak, pk); // magnitudes as bits: the max of the bits is the max, a NaN wins
+        }
+        memcpy(&m.peak, &peak, 4);
+        out[k] = m;
+    }
+    return SDRX_OK;
+}
+
+// The whole list is checked before anything changes; then the software pipeline runs out with the old values, one upload of
+// the job list, one k_squelch_set launch.
+int sdrx_set_squelch(sdrx_ctx *c, const int *ids, const uint64_t *thr, const uint32_t *hang_frames, int n)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_set_squelch before sdrx_finalize");
+    if (!c->opt_squelch)
+        return fail(c, SDRX_ESTATE, "sdrx_set_squelch: option \"squelch\" is off");
+    if (n < 0 || (n > 0 && (!ids || !thr || !hang_frames)))
+        return fail(c, SDRX_EINVAL, "sdrx_set_squelch: n = %d, ids %p, thresholds %p, hang times %p", n, (const void *)ids, (const void *)thr,
+                    (const void *)hang_frames);
+    if (int rc = check_leaf_ids(c, "sdrx_set_squelch", ids, n, true))
+        return rc;
+    if (c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "sdrx_set_squelch: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+    if (n == 0)
+        return SDRX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c))
+        return rc;
+    std::vector<SqJob> jobs((size_t)n);
+    for (int k = 0; k < n; ++k)
+        jobs[(size_t)k] = SqJob{thr[k], hang_frames[k], (unsigned)c->sq.index[(size_t)ids[k]]};
+    if (jobs.size() > c->sq.jobs_cap) {
+        if (c->sq.d_jobs)
+            (void)hipFree(c->sq.d_jobs);
+        c->sq.d_jobs = nullptr;
+        c->sq.jobs_cap = 0;
+        HIPCHK(c, hipMalloc(&c->sq.d_jobs, sizeof(SqJob) * jobs.size()));
+        c->sq.jobs_cap = jobs.size();
+    }
+    HIPCHK(c, hipMemcpyAsync(c->sq.d_jobs, jobs.data(), sizeof(SqJob) * jobs.size(), hipMemcpyHostToDevice, c->st.stream));
+    hipLaunchKernelGGL(k_squelch_set, dim3((n + 63) / 64), dim3(64), 0, c->st.stream, c->sq.d_jobs, n, c->sq.d_cfg, c->sq.d_hang);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->st.stream)); // (`jobs` lives on this stack)
+    for (const SqJob &J : jobs) {
+        c->sq.cfg[J.index] = SqCfg{J.thr, J.hang_frames, 0};
+        c->sq.hang[J.index] = 0;
+    }
+    return SDRX_OK;
+}
+
+int sdrx_get_squelch(sdrx_ctx *c, const int *ids, int n, sdrx_squelch_state *out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_squelch before sdrx_finalize");
+    if (!c->opt_squelch)
+        return fail(c, SDRX_ESTATE, "sdrx_get_squelch: option \"squelch\" is off");
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return fail(c, SDRX_EINVAL, "sdrx_get_squelch: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
+    if (int rc = check_leaf_ids(c, "sdrx_get_squelch", ids, n, false))
+        return rc;
+    if (n == 0)
+        return SDRX_OK;
+    if (int rc = need_delivered(c, "sdrx_get_squelch"))
+        return rc;
+    for (int k = 0; k < n; ++k) {
+        const size_t i = (size_t)c->sq.index[(size_t)ids[k]];
+        sdrx_squelch_state s;
+        memset(&s, 0, sizeof s);
+        s.frame = (int64_t)c->host_frame;
+        s.thr_sum_sq = c->sq.cfg[i].thr;
+        s.hang_frames = c->sq.cfg[i].hang_frames;
+        s.hang_left = c->sq.hang[i];
+        s.open = c->sq.offs[i] != kSqClosed;
+        out[k] = s;
+    }
+    return SDRX_OK;
+}
+
+int sdrx_get_egress(sdrx_ctx *c, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_egress before sdrx_finalize");
+    if (c->host_slot < 0 || c->pending_fetch)
+        return fail(c, SDRX_ESTATE, "sdrx_get_egress: no frame has been delivered yet (sdrx_wait / sdrx_fetch first)");
+    const uint32_t leaves = (uint32_t)c->publish_order.size();
+    if (frame)
+        *frame = (int64_t)c->host_frame;
+    if (n_leaves)
+        *n_leaves = leaves;
+    if (n_open)
+        *n_open = c->opt_squelch ? c->sq.n_open : leaves;
+    if (payload_bytes_copied)
+        *payload_bytes_copied = c->opt_squelch ? c->sq.copied : (uint64_t)(c->meter_off ? c->meter_off : c->pay_bytes);
+    return SDRX_OK;
+}
+
+int sdrx_get_preroll(sdrx_ctx *c, int id, const void **buf, uint32_t *len, int64_t *frame)
+{
+    if (!c || id < 0 || id >= (int)c->nodes.size())
+        return fail(c, SDRX_EINVAL, "bad vfo id %d", id);
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_preroll before sdrx_finalize");
+    if (!c->opt_preroll)
+        return fail(c, SDRX_ESTATE, "sdrx_get_preroll: option \"preroll\" is off");
+    if (int rc = check_leaf_ids(c, "sdrx_get_preroll", &id, 1, false))
+        return rc;
+    if (int rc = need_delivered(c, "sdrx_get_preroll"))
+        return rc;
+    uint32_t plen = 0;
+    const unsigned char *pre = leaf_preroll(c, id, c->host_slot, &plen);
+    if (buf)
+        *buf = pre;
+    if (len)
+        *len = plen;
+    if (frame)
+        *frame = (int64_t)c->host_frame - 1;
+    return SDRX_OK;
+}
+
+int sdrx_get_preroll_count(sdrx_ctx *c, uint32_t *n_preroll, uint64_t *preroll_bytes)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_preroll_count before sdrx_finalize");
+    if (!c->opt_preroll)
+        return fail(c, SDRX_ESTATE, "sdrx_get_preroll_count: option \"preroll\" is off");
+    if (c->host_slot < 0 || c->pending_fetch)
+        return fail(c, SDRX_ESTATE, "sdrx_get_preroll_count: no frame has been delivered yet (sdrx_wait / sdrx_fetch first)");
+    if (n_preroll)
+        *n_preroll = c->sq.n_pre;
+    if (preroll_bytes)
+        *preroll_bytes = c->sq.pre_bytes;
+    return SDRX_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,737 @@
+// sdrx_frame.hip -- the per-frame launch sequence: how a raw frame reaches the device (staging, DC-bias ingest), which kernels
+// run on it in which order on which stream (enqueue_frame, the software pipeline), and the ABI calls that start a frame.
+// How its payloads come back is sdrx_delivery.hip.  A fragment of sdrx.hip's translation unit.
+
+namespace {
+
+hipEvent_t get_event(sdrx_ctx *c)
+{
+    if (!c->tm.pool.empty()) {
+        hipEvent_t e = c->tm.pool.back();
+        c->tm.pool.pop_back();
+        return e;
+    }
+    hipEvent_t e = nullptr;
+    if (hipEventCreate(&e) != hipSuccess)
+        return nullptr; // the launch is then simply not timed
+    return e;
+}
+
+void drain_events(sdrx_ctx *c)
+{
+    for (auto &te : c->tm.pending) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, te.a, te.b) == hipSuccess) {
+            c->tm.ms[te.kind] += ms;
+            c->tm.n[te.kind] += 1;
+            c->tm.bytes[te.kind] += te.bytes;
+        }
+        c->tm.pool.push_back(te.a);
+        c->tm.pool.push_back(te.b);
+    }
+    c->tm.pending.clear();
+}
+
+struct Bracket { // RAII: event pair around one launch when timing is on, on the launch's stream
+    sdrx_ctx *c;
+    hipStream_t st;
+    TimedEvent te{};
+    bool on;
+    Bracket(sdrx_ctx *ctx, hipStream_t stream, int kind, int64_t bytes) : c(ctx), st(stream), on(ctx->tm.on)
+    {
+        if (!on)
+            return;
+        te.kind = kind;
+        te.bytes = bytes;
+        te.a = get_event(c);
+        te.b = get_event(c);
+        if (!te.a || !te.b) {
+            on = false;
+            return;
+        }
+        (void)hipEventRecord(te.a, st);
+    }
+    ~Bracket()
+    {
+        if (!on)
+            return;
+        (void)hipEventRecord(te.b, st);
+        c->tm.pending.push_back(te);
+    }
+};
+
+// The kernel variants this context runs, as compile-time constants: fn(EXACT, ROT, METER), each a std::bool_constant, from option
+// "exact" -- 1 the exact arithmetic, 0 the tolerance arithmetic (NCO as rotations), 2 the robust one (exact NCO, FMA mixer and
+// filters; kernels.hip, nco_mix) -- and option "meter".  Every launch of a kernel that has variants goes through here, so these six
+// combinations are all that is ever instantiated: there is no (EXACT, ROT) = (1, 1) kernel.
+template <class F>
+void with_variant(const sdrx_ctx *c, F fn)
+{
+    auto arith = [&](auto meter) {
+        if (c->opt_exact == 1)
+            fn(std::true_type(), std::false_type(), meter);
+        else if (c->opt_exact == 2)
+            fn(std::false_type(), std::false_type(), meter);
+        else
+            fn(std::false_type(), std::true_type(), meter);
+    };
+    if (c->opt_meter)
+        arith(std::true_type());
+    else
+        arith(std::false_type());
+}
+
+int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st); // (sdrx_delivery.hip)
+int queue_payloads(sdrx_ctx *c, int p, hipStream_t st);
+
+// The VFO spectra of tree levels lo..hi, whose streams hold frame frames[l] (frames == nullptr: all hold frame f): behind the
+// launch that wrote those streams, before anything can overwrite them (frame f + 2 -- the next writer of that parity -- is
+// queued behind this launch on the same stream, or waits for ev_tail).  Nothing enabled: nothing is launched.
+void spectrum_launch(sdrx_ctx *c, hipStream_t st, int lo, int hi, unsigned long long f, const unsigned long long *frames)
+{
+    if (c->spec.n_desc == 0)
+        return;
+    const int first = c->spec.level_begin[(size_t)lo], last = c->spec.level_begin[(size_t)hi + 1];
+    if (last <= first)
+        return;
+    SpecArgs A;
+    memset(&A, 0, sizeof A);
+    for (int l = 0; l < kMaxLevels; ++l)
+        A.frame_level[l] = frames ? frames[l] : f;
+    const float *hann = reinterpret_cast<const float *>(c->spec.d_tw + kSpecN);
+    hipLaunchKernelGGL(k_spectrum, dim3(last - first), dim3(kSpecThreads), 0, st, c->spec.d_desc + first, A, c->spec.d_tw, hann);
+}
+
+// The raw spectrum at sdrj's cadence: `if (count == 4) {emit fftData(samples); count = 0;} count++` once per frame, on the
+// frame as the parent-less VFOs get it -- queued first in the frame's own sequence, so that a caller's device frame or the
+// tile-layout copy of a DC-corrected one is read before anything else may overwrite it.
+void spectrum_raw_step(sdrx_ctx *c, const void *raw, int raw_mode)
+{
+    if (!c->spec.raw_on)
+        return;
+    const bool due = c->spec.raw_count == 4;
+    if (due)
+        c->spec.raw_count = 0;
+    c->spec.raw_count++;
+    if (!due)
+        return;
+    SpecArgs A;
+    memset(&A, 0, sizeof A);
+    A.raw = raw_mode == kRawTiled ? static_cast<const void *>(c->d_raw_tiled) : raw;
+    A.raw_mode = raw_mode;
+    const float *hann = reinterpret_cast<const float *>(c->spec.d_tw + kSpecN);
+    hipLaunchKernelGGL(k_spectrum, dim3(1), dim3(kSpecThreads), 0, c->st.stream, c->spec.d_desc + c->spec.n_desc, A, c->spec.d_tw, hann);
+}
+
+// Option squelch: the gate of frame `frame`, on the stream -- and behind the launch -- that completed its payloads and meter
+// records: decide + scan (one workgroup), then the gather of the open leaves into d_pack[p] (squelch.hip).  Not bracketed:
+// sdrx_get_kernel_times keeps its SDRX_NKERNELS kinds.
+void squelch_gate(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
+{
+    const int n = (int)c->publish_order.size();
+    if (!c->opt_squelch || n == 0)
+        return;
+    const int p = (int)(frame & 1ull);
+    unsigned char *dir = c->d_pay[p] + c->sq.dir_off;
+    if (c->opt_preroll) { // the same two launches in their second form: the gather also reads frame - 1's payloads in d_pay[p ^ 1]
+        const SqPre<true> X = {c->sq.d_prev, c->d_pay[p ^ 1]};
+        hipLaunchKernelGGL(k_squelch_scan<true>, dim3(1), dim3(kSqThreads), 0, ts, c->sq.d_leaves, c->sq.d_cfg, c->sq.d_hang, c->d_pay[p], dir, n,
+                           (long long)frame, X);
+        hipLaunchKernelGGL(k_squelch_gather<true>, dim3(n, c->sq.tiles, 2), dim3(256), 0, ts, c->sq.d_leaves, c->d_pay[p], dir, c->sq.d_pack[p], X);
+        return;
+    }
+    hipLaunchKernelGGL(k_squelch_scan<>, dim3(1), dim3(kSqThreads), 0, ts, c->sq.d_leaves, c->sq.d_cfg, c->sq.d_hang, c->d_pay[p], dir, n, (long long)frame,
+                       SqPre<false>());
+    hipLaunchKernelGGL(k_squelch_gather<>, dim3(n, c->sq.tiles), dim3(256), 0, ts, c->sq.d_leaves, c->d_pay[p], dir, c->sq.d_pack[p], SqPre<false>());
+}
+
+// One block-per-tile launch of the leaf tail (late decimation / demodulation / long audio low-pass / compress) for `frame`.
+void launch_block_kernel(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned long long frame)
+{
+    Bracket b(c, ts, L.kind, L.alg_bytes);
+    const dim3 grid(L.n_blocks);
+    const BlockWork *w = reinterpret_cast<const BlockWork *>(c->arena + L.off_work);
+    const int *mrel = c->opt_meter ? reinterpret_cast<const int *>(c->arena + L.off_mrel) : nullptr;
+    const unsigned char *desc = c->arena + L.off_desc;
+    with_variant(c, [&](auto EXACT, auto, auto METER) {
+        if (L.kind == KIND_LATE_DEC && c->late4)
+            hipLaunchKernelGGL(k_late_decimate4<EXACT()>, grid, dim3(64), L.lds_bytes, ts, reinterpret_cast<const K2aVfo *>(desc), w, frame);
+        else if (L.kind == KIND_LATE_DEC)
+            hipLaunchKernelGGL(k_late_decimate<EXACT()>, grid, dim3(256), L.lds_bytes, ts, reinterpret_cast<const K2aVfo *>(desc), w, frame);
+        else if (L.kind == KIND_DEMOD)
+            hipLaunchKernelGGL((k_usb_demod<EXACT(), METER()>), grid, dim3(256), 0, ts, reinterpret_cast<const K2Vfo *>(desc), w, frame);
+        else if (L.kind == KIND_LPF_LONG)
+            hipLaunchKernelGGL((k_lpf_long<EXACT(), METER()>), grid, dim3(256), L.lds_bytes, ts, reinterpret_cast<const K4Vfo *>(desc), w, frame, mrel);
+        else
+            hipLaunchKernelGGL(k_compress<METER()>, grid, dim3(256), 0, ts, reinterpret_cast<const K3Vfo *>(desc), w, frame);
+    });
+}
+
+// One step of the frame pipeline: every in-flight frame (and the new one, if `have_new`) moves through
+// the tree level it has reached -- ONE k_mix_levels launch over the contiguous range of those levels --
+// and the frame that thereby leaves the last level gets its leaf tail (late decimation, demodulation,
+// compress) right behind that launch.
+// With LevelPlan::tail the demodulation of that frame is one more stage instead: it runs inside the NEXT step's launch
+// (k_levels_tail), its long audio low-pass (k_lpf_long) right behind that launch; the late decimation and compress stay
+// behind the launch that finished the frame's levels.
+int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
+{
+    const LevelPlan &P = c->fp;
+    const int n_levels = (int)P.part_begin.size();
+    if (have_new)
+        c->pipe.push_back({c->frame_no, 0});
+    if (c->pipe.empty())
+        return SDRX_OK;
+    LevelArgs A;
+    memset(&A, 0, sizeof A);
+    A.raw = raw;
+    A.raw_mode = raw_mode;
+    int lo = n_levels, hi = -1;
+    bool dm = false;             // the oldest frame is due for its demodulation (P.tail only)
+    unsigned long long f_dm = 0;
+    for (const InFlight &q : c->pipe) {
+        if (q.next == n_levels) {
+            dm = true;
+            f_dm = q.f;
+            continue;
+        }
+        lo = std::min(lo, q.next);
+        hi = std::max(hi, q.next);
+        A.frame_level[q.next] = q.f;
+    }
+    const K1Vfo *k1 = reinterpret_cast<const K1Vfo *>(c->arena + c->off_k1vfo);
+    const K1Work *items = reinterpret_cast<const K1Work *>(c->arena + P.off_items);
+    const int *item_level = reinterpret_cast<const int *>(c->arena + P.off_item_level);
+    int64_t bytes = dm ? P.dm_bytes : 0;
+    for (int j = lo; j <= hi; ++j)
+        bytes += P.part_bytes[(size_t)j];
+    if (!P.tail) {
+        const int first = std::min(P.part_begin[(size_t)lo], P.part_begin[(size_t)hi]), last = std::max(P.part_end[(size_t)lo], P.part_end[(size_t)hi]);
+        Bracket b(c, c->st.stream, lo != hi ? KIND_LEVELS : lo == 0 ? KIND_MIX_ROOT : KIND_MIX_SUB, bytes);
+        const int *list = reinterpret_cast<const int *>(c->arena + P.off_list) + first;
+        const dim3 grid(last - first);
+        with_variant(c, [&](auto EXACT, auto ROT, auto METER) {
+            hipLaunchKernelGGL((k_mix_levels<EXACT(), ROT(), METER()>), grid, dim3(64), P.lds_bytes, c->st.stream, k1, items, item_level, list, A);
+        });
+    } else {
+        // the list is [level n-1 | ... | level 0 | demodulation]: the range runs from the deepest level with a frame to the
+        // demodulation (or to the shallowest level with a frame); levels inside it without a frame (the pipeline draining)
+        // are masked out by `active`
+        LevelTailArgs T;
+        memset(&T, 0, sizeof T);
+        T.L = A;
+        T.frame_tail = f_dm;
+        T.lds_wave = P.lds_wave;
+        T.active = dm ? 1 << kMaxLevels : 0;
+        for (int j = lo; j <= hi; ++j)
+            T.active |= 1 << j;
+        const int first = hi >= 0 ? P.wg_begin[(size_t)hi] : P.dm_begin, last = dm ? P.dm_end : P.wg_end[(size_t)lo];
+        Bracket b(c, c->st.stream, hi < 0 || lo != hi || dm ? KIND_LEVELS : lo == 0 ? KIND_MIX_ROOT : KIND_MIX_SUB, bytes);
+        const TailWg *wgs = reinterpret_cast<const TailWg *>(c->arena + P.off_wgs) + first;
+        const LaunchB &D = *std::find_if(c->lb.begin(), c->lb.end(), [](const LaunchB &L) { return L.kind == KIND_DEMOD; });
+        const K2Vfo *k2 = reinterpret_cast<const K2Vfo *>(c->arena + D.off_desc);
+        const BlockWork *dwork = reinterpret_cast<const BlockWork *>(c->arena + D.off_work);
+        const dim3 grid(last - first);
+        with_variant(c, [&](auto EXACT, auto ROT, auto METER) {
+            hipLaunchKernelGGL((k_levels_tail<EXACT(), ROT(), METER()>), grid, dim3(256), P.tail_lds, c->st.stream, k1, items, item_level, wgs, k2, dwork, T);
+        });
+    }
+    if (dm)
+        for (const LaunchB &L : c->lb)
+            if (L.kind == KIND_LPF_LONG)
+                launch_block_kernel(c, L, c->st.stream, f_dm);
+    if (dm) // that launch completed frame f_dm's payloads and records: its gate
+        squelch_gate(c, c->st.stream, f_dm);
+    if (hi >= 0)
+        spectrum_launch(c, c->st.stream, lo, hi, 0, A.frame_level);
+    if (dm)
+        c->pipe.erase(c->pipe.begin());
+    for (InFlight &q : c->pipe)
+        q.next++;
+    if (!c->pipe.empty() && c->pipe.front().next == n_levels) { // the oldest frame has passed its last level: its leaf tail, now
+        const unsigned long long f = c->pipe.front().f;
+        for (const LaunchB &L : c->lb)
+            if (!P.tail || (L.kind != KIND_DEMOD && L.kind != KIND_LPF_LONG))
+                launch_block_kernel(c, L, c->st.stream, f);
+        if (!P.tail) {
+            squelch_gate(c, c->st.stream, f);
+            c->pipe.erase(c->pipe.begin());
+        }
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return fail(c, SDRX_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return SDRX_OK;
+}
+
+// run every in-flight frame to its end
+int pipeline_flush(sdrx_ctx *c)
+{
+    while (!c->pipe.empty()) {
+        const int rc = pipeline_step(c, false, nullptr, kRawTiled);
+        if (rc)
+            return rc;
+    }
+    return SDRX_OK;
+}
+
+// One frame: [wait for the tail of frame f-2] -> ingest -> one k_mix_decimate launch per tree level on
+// `stream`; then the leaf tail (late decimation, demodulation, compress) -- on `tail_stream` behind an
+// event when the pipeline option is on, so that it runs beside the NEXT frame's levels -- and, for a
+// frame that came through sdrx_submit*, the payload copy on `copy_stream` behind the tail.
+//
+// What makes the two-stream form safe (frame f, parity p = f & 1):
+//   * the leaf streams of parity p are written by the levels of f and read by the tail of f: the tail
+//     waits for ev_levels[p]; their next writer is frame f+2, whose levels wait for ev_tail[p] first;
+//   * the history prefix of the parity-(p^1) leaf streams is written by the tail of f and read by the
+//     tail of f+1: same stream, in order (the levels of f+1 write only the data part behind it);
+//   * half-band state, NCO tables and the parents' streams are touched by the levels only;
+//   * d_pay[p] is written by the tail of f and read by the copy of f; its next writer is the tail of
+//     f+2, which the host does not submit before frame f was delivered (SDRX_MAX_IN_FLIGHT = 2).
+//   * option squelch: d_pack[p] and the directory (inside d_pay[p]) are written by the gate of f, behind its tail on the
+//     tail's stream, and read by the two copies of f -- queue_fixed_part at submit, queue_payloads from sdrx_wait
+//     (sdrx_delivery.hip) -- the same argument: their next writer is the gate of f+2.  hang_left is one array: gates run in
+//     frame order on one stream.
+//   * option preroll: the gate of f also READS the payloads of f-1 in d_pay[p ^ 1], whose next writer is frame f+1 -- every
+//     launch that writes a payload of f+1 must come behind the gate of f.  prev_open is one array, as hang_left.  Path by path:
+//       - one launch per level, one stream (below, !pipe): tail(f), gate(f), levels(f+1), tail(f+1) in order, whichever kernel
+//         writes the payloads (fuse_demod leaves write theirs in the levels);
+//       - two streams (pipe): the tails and gates of all frames are in order on tail_stream, and without fuse_demod only the
+//         tail writes d_pay.  With fuse_demod leaves the levels of f+1 on `stream` write it, and they wait only for ev_tail of
+//         f-1: with preroll they also wait for ev_tail[p ^ 1], recorded behind the gate of f (preroll_fused below) -- which
+//         takes the overlap away for exactly that combination;
+//       - pipeline_step with k_mix_levels: the launch of step k runs level l of frame k-l, then the block kernels and the gate
+//         of the frame g that left the last level.  Block kernels of g+1 come in step k+1: behind gate(g).  A fuse_demod leaf
+//         on level n-1 writes g's payload in step k and g+1's in step k+1: behind gate(g).  One on level n-2 writes g+1's payload
+//         in step k's launch, BEFORE gate(g): with preroll such a tree does not use the software pipeline (build_level_plan);
+//       - pipeline_step with k_levels_tail: the demodulation blocks of f ride in the launch of the step after f's last level,
+//         then k_lpf_long(f), gate(f), and only then the compress / late-decimation launches of f+1 in the same step; the
+//         demodulation of f+1 is in the next step's launch.  fuse_demod leaves of f+1 would write their payload inside the
+//         launch that carries f's demodulation, before gate(f): with preroll a tree with such leaves keeps k_mix_levels +
+//         k_usb_demod in every arithmetic (build_level_plan; the rule option meter has for the exact one);
+//       - paths mix only through pipeline_flush, which runs every gate still outstanding, in frame order, on `stream`; the
+//         two-stream form never enters pipeline_step.  sdrx_fetch, queue_fixed_part and queue_payloads read d_pack and the
+//         directory only.
+int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
+{
+    const K1Vfo *k1 = reinterpret_cast<const K1Vfo *>(c->arena + c->off_k1vfo);
+    const int p = (int)(c->frame_no & 1ull);
+    const bool pipe = c->opt_pipeline != 0;
+    if (pipe && c->st.tail_recorded[p])
+        HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.ev_tail[p], 0));
+    if (pipe && c->opt_preroll && c->sq.preroll_fused && c->st.tail_recorded[p ^ 1]) // the levels write d_pay[p], which the previous gate reads
+        HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.ev_tail[p ^ 1], 0));
+    spectrum_raw_step(c, raw, raw_mode);
+    // A few parent-less VFOs (the reference's 2-3 mains) read the caller's frame as it is; a wide
+    // level 0 (the flat workloads) is bandwidth bound and wants coalesced reads: one layout pass
+    // natural order -> tile layout first.
+    if (raw_mode != kRawTiled && !c->root_direct) {
+        Bracket b(c, c->st.stream, KIND_INGEST, 0);
+        const int n_pairs = c->root_frame / 2;
+        if (raw_mode == kRawF32)
+            hipLaunchKernelGGL(k_ingest_f32, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream,
+                               reinterpret_cast<const float4 *>(raw), reinterpret_cast<float4 *>(c->d_raw_tiled), n_pairs);
+        else
+            hipLaunchKernelGGL(k_ingest_u8, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream,
+                               reinterpret_cast<const unsigned *>(raw), reinterpret_cast<float4 *>(c->d_raw_tiled), n_pairs);
+        raw_mode = kRawTiled;
+    }
+    const bool shared_launches = c->fp.usable && c->opt_fuse && !pipe && !egress;
+    if (!shared_launches)
+        if (int rc = pipeline_flush(c))
+            return rc;
+    if (shared_launches) {
+        // Frames that stay on the device and are queued back to back share launches: level l of frame
+        // k - l runs in the launch that frame k enters with, and the frame that leaves the last level
+        // gets its leaf tail right behind it.  (A frame whose payloads must leave now -- sdrx_process*,
+        // sdrx_submit* -- runs through its own launches below: nothing to overlap it with.)
+        const int rc = pipeline_step(c, true, raw, raw_mode);
+        if (rc)
+            return rc;
+        if (!c->opt_frame_pipeline)
+            if (int rc2 = pipeline_flush(c))
+                return rc2;
+        c->frame_no++;
+        c->pending_fetch = true;
+        return SDRX_OK;
+    }
+    for (const Launch1 &L : c->l1) {
+        Bracket b(c, c->st.stream, L.kind, L.alg_bytes);
+        const K1Work *w = reinterpret_cast<const K1Work *>(c->arena + L.off_work);
+        const void *lraw = L.level == 0 ? raw : nullptr;
+        const int lmode = L.level == 0 ? raw_mode : kRawTiled;
+        with_variant(c, [&](auto EXACT, auto ROT, auto METER) {
+            if (L.level == 0)
+                hipLaunchKernelGGL((k_mix_decimate<EXACT(), 0, ROT(), METER()>), dim3(L.n_work), dim3(64), L.lds_bytes, c->st.stream, k1, w, c->frame_no, lraw, lmode);
+            else
+                hipLaunchKernelGGL((k_mix_decimate<EXACT(), 1, ROT(), METER()>), dim3(L.n_work), dim3(64), L.lds_bytes, c->st.stream, k1, w, c->frame_no, lraw, lmode);
+        });
+    }
+    hipStream_t ts = pipe ? c->st.tail_stream : c->st.stream;
+    if (pipe) {
+        HIPCHK(c, hipEventRecord(c->st.ev_levels[p], c->st.stream));
+        HIPCHK(c, hipStreamWaitEvent(ts, c->st.ev_levels[p], 0));
+    }
+    for (const LaunchB &L : c->lb)
+        launch_block_kernel(c, L, ts, c->frame_no);
+    squelch_gate(c, ts, c->frame_no);
+    spectrum_launch(c, ts, 0, c->n_levels - 1, c->frame_no, nullptr);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return fail(c, SDRX_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
+    if (pipe || egress) {
+        HIPCHK(c, hipEventRecord(c->st.ev_tail[p], ts));
+        c->st.tail_recorded[p] = pipe;
+    }
+    // How the payloads leave (measured, traced: profiles/README.md round 5; tools/copy_overlap_probe.hip).  Normally queued here,
+    // behind the frame's last kernel: hipMemcpyAsync on a copy stream, which the runtime hands to an SDMA engine -- the kernels of
+    // the next frame run beside it, config 3 from host floats goes at PCIe speed (0.30 ms per pipelined frame = the 15 MB copy).
+    // A frame that carries the DC-bias recurrence did not get to run beside a copy queued that way (0.59-0.82 ms per frame,
+    // about the SUM of its parts), nor beside a copy kernel of ours (a kernel cannot retire beside one): for those frames the copy
+    // is issued by sdrx_wait, when the host has seen the frame's last kernel end -- 0.34 ms per frame.  (The float path would lose
+    // by that, 0.38 vs 0.30: between two waits the copy engine idles.)
+    // Option squelch: how much leaves is a device result.  Here only the fixed-size part -- meter records and directory -- is
+    // queued behind the gate (queue_fixed_part); sdrx_wait reads packed_bytes from it and issues the one copy of the packed payloads
+    // (queue_payloads: the owed-copy form, whatever kind of frame this is).
+    hipStream_t cs = p ? c->st.copy_stream2 : c->st.copy_stream;
+    if (egress && c->opt_squelch) {
+        HIPCHK(c, hipStreamWaitEvent(cs, c->st.ev_tail[p], 0));
+        if (int rc = queue_fixed_part(c, p, cs))
+            return rc;
+        HIPCHK(c, hipEventRecord(c->sq.ev_dir[p], cs));
+        c->copy_owed[p] = true;
+    } else if (egress && c->long_frame) {
+        c->copy_owed[p] = true;
+    } else if (egress) {
+        HIPCHK(c, hipStreamWaitEvent(cs, c->st.ev_tail[p], 0));
+        if (int rc = queue_payloads(c, p, cs))
+            return rc;
+        HIPCHK(c, hipEventRecord(c->st.ev_copied[p], cs));
+    }
+    c->in_flight += egress;
+    c->frame_no++;
+    c->pending_fetch = !egress;
+    return SDRX_OK;
+}
+
+// every frame handed to the context is complete and every stream of the context idle afterwards
+int drain(sdrx_ctx *c)
+{
+    if (int rc = pipeline_flush(c))
+        return rc;
+    for (hipStream_t st : {c->st.stream, c->st.tail_stream, c->st.copy_stream, c->st.copy_stream2})
+        HIPCHK(c, hipStreamSynchronize(st));
+    drain_events(c);
+    return SDRX_OK;
+}
+
+
+int ensure_raw(sdrx_ctx *c, size_t n_complex)
+{
+    if (c->raw_cap >= n_complex)
+        return SDRX_OK;
+    for (int p = 0; p < 2; ++p) {
+        if (c->d_raw[p])
+            (void)hipFree(c->d_raw[p]);
+        if (c->d_raw_u8[p])
+            (void)hipFree(c->d_raw_u8[p]);
+        c->d_raw[p] = nullptr;
+        c->d_raw_u8[p] = nullptr;
+        HIPCHK(c, hipMalloc(&c->d_raw[p], n_complex * sizeof(float2)));
+        HIPCHK(c, hipMalloc(&c->d_raw_u8[p], n_complex * 2));
+    }
+    c->raw_cap = n_complex;
+    return SDRX_OK;
+}
+
+int check_frame_call(sdrx_ctx *c, const char *what, const void *ptr, int n_complex, bool sync_call)
+{
+    if (c && c->broken)
+        return fail(c, SDRX_EHIP, "%s: injected fault (SDRX_FAULT_WAIT): the context is unusable", what);
+    if (!c)
+        return SDRX_EINVAL;
+    if (!ptr)
+        return fail(c, SDRX_EINVAL, "%s: null frame pointer", what);
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "%s before sdrx_finalize", what);
+    if (n_complex != c->root_frame)
+        return fail(c, SDRX_EINVAL, "frame of %d samples, VFOs were initialised for %d (vfo::init samplesPerBuffer)", n_complex,
+                    c->root_frame);
+    if (sync_call && c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "%s: %d submitted frame(s) not yet delivered -- call sdrx_wait first", what, c->in_flight);
+    if (!sync_call && c->in_flight >= SDRX_MAX_IN_FLIGHT)
+        return fail(c, SDRX_ESTATE, "%s: %d frames in flight -- call sdrx_wait before submitting another", what, c->in_flight);
+    HIPCHK(c, hipSetDevice(c->device));
+    return SDRX_OK;
+}
+
+// host frame -> the library's pinned staging buffer of this frame parity -> device.  The pinned buffer's
+// previous user is frame f-2, which has been delivered (at most two frames are in flight), so its copy is
+// long done; the device buffer is written and read on `stream` only, in order.
+int stage_host_frame(sdrx_ctx *c, const void *src, size_t bytes, void *dst_dev)
+{
+    const int p = (int)(c->frame_no & 1ull);
+    if (c->h_in_bytes < (size_t)c->root_frame * sizeof(float2)) {
+        for (int q = 0; q < 2; ++q) {
+            if (c->h_in[q])
+                (void)hipHostFree(c->h_in[q]);
+            c->h_in[q] = nullptr;
+            HIPCHK(c, hipHostMalloc(&c->h_in[q], (size_t)c->root_frame * sizeof(float2), hipHostMallocDefault));
+        }
+        c->h_in_bytes = (size_t)c->root_frame * sizeof(float2);
+    }
+    memcpy(c->h_in[p], src, bytes);
+    for (auto &r : c->shared_readers[p]) // whoever shared frame f-2 of this buffer has read it before it is overwritten
+        if (r.pending) {
+            HIPCHK(c, hipStreamWaitEvent(c->st.stream, r.ev, 0));
+            r.pending = false;
+        }
+    // (the runtime moves host-to-device copies with the DMA engine: concurrent with kernels.  A copy kernel reading the pinned
+    // buffer over PCIe instead measured slower, 0.353 vs 0.302 ms per pipelined frame on config 3: it sits in the compute
+    // stream's way)
+    HIPCHK(c, hipMemcpyAsync(dst_dev, c->h_in[p], bytes, hipMemcpyHostToDevice, c->st.stream));
+    HIPCHK(c, hipEventRecord(c->st.ev_staged[p], c->st.stream)); // (for a context that shares this frame: sdrx_submit_shared)
+    return SDRX_OK;
+}
+
+int enqueue_f32(sdrx_ctx *c, const float *iq, int n_complex, bool egress)
+{
+    int rc = ensure_raw(c, (size_t)c->root_frame);
+    if (rc)
+        return rc;
+    float2 *dst = c->d_raw[c->frame_no & 1ull];
+    rc = stage_host_frame(c, iq, (size_t)n_complex * sizeof(float2), dst);
+    if (rc)
+        return rc;
+    rc = enqueue_frame(c, dst, kRawF32, egress);
+    if (rc == SDRX_OK)
+        c->last_raw = kRawF32;
+    return rc;
+}
+
+// `dev_bytes`: the frame's dongle bytes, already on this context's device and complete in the order of
+// c->st.stream.  LUT (+ the DC-bias IIR with this context's own accumulator) and the frame itself.
+int enqueue_u8_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, int correct_dc, bool egress)
+{
+    if (correct_dc && !c->dc.d_state) {
+        HIPCHK(c, hipMalloc(&c->dc.d_state, 4 * sizeof(float)));
+        HIPCHK(c, hipMemsetAsync(c->dc.d_state, 0, 4 * sizeof(float), c->st.stream)); // `static cpx_typef avept=0`, sdrj.cpp:279
+    }
+    int mode = kRawU8;
+    const int nchunks = (n_complex + kChunk - 1) / kChunk;
+    if (correct_dc && c->opt_dc_blocked && !c->dc.d_tab) {
+        // powers of the decay A = (float)(1 - 1e-6): [0..16] A^k, [32..95] A^(16 l), [96 + k] A^(1024 k)
+        const double A = (double)(1.0f - 0.000001f);
+        std::vector<double> tab(96 + (size_t)nchunks + 1 + 2 * (size_t)nchunks + 2, 0.0);
+        for (int k = 0; k <= 16; ++k)
+            tab[(size_t)k] = std::pow(A, k);
+        for (int l = 0; l < 64; ++l)
+            tab[32 + (size_t)l] = std::pow(A, 16.0 * l);
+        for (int k = 0; k <= nchunks; ++k)
+            tab[96 + (size_t)k] = std::pow(A, 1024.0 * k);
+        c->dc.tab_sums = (96 + (size_t)nchunks + 1 + 1) & ~(size_t)1; // 16-byte aligned double2[]
+        HIPCHK(c, hipMalloc(&c->dc.d_tab, tab.size() * sizeof(double)));
+        HIPCHK(c, hipMemcpy(c->dc.d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (correct_dc && !c->opt_dc_blocked) {
+        // products (parallel) -> the two recurrences (one wave each, nearly alone with their dependent chain) -> subtract (parallel)
+        const int stride = (int)align_up((size_t)n_complex + kDcPad, 64);
+        if (c->dc.work_stride < stride) {
+            if (c->dc.d_work)
+                (void)hipFree(c->dc.d_work);
+            c->dc.d_work = nullptr;
+            HIPCHK(c, hipMalloc(&c->dc.d_work, sizeof(float) * 4 * (size_t)stride)); // P[2][stride] | A[2][stride]
+            HIPCHK(c, hipMemsetAsync(c->dc.d_work, 0, sizeof(float) * 4 * (size_t)stride, c->st.stream));
+            c->dc.work_stride = stride;
+        }
+        float *Pp = c->dc.d_work, *Ap = c->dc.d_work + 2 * (size_t)c->dc.work_stride;
+        const int words = n_complex / 2;
+        Bracket b(c, c->st.stream, KIND_INGEST, 0);
+        hipLaunchKernelGGL(k_dc_products, dim3((words + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), Pp,
+                           n_complex, c->dc.work_stride);
+        if (c->opt_dc_speculative) {
+            if (!c->dc.d_counters) {
+                HIPCHK(c, hipMalloc(&c->dc.d_counters, 4 * sizeof(unsigned long long)));
+                HIPCHK(c, hipMemsetAsync(c->dc.d_counters, 0, 4 * sizeof(unsigned long long), c->st.stream));
+            }
+            // one workgroup per component, dc_waves consecutive 1024-sample blocks per step
+            auto chain = c->dc.waves >= 8 ? k_dc_chain_spec<8> : c->dc.waves >= 4 ? k_dc_chain_spec<4> : c->dc.waves >= 2 ? k_dc_chain_spec<2> : k_dc_chain_spec<1>;
+            const int waves = c->dc.waves >= 8 ? 8 : c->dc.waves >= 4 ? 4 : c->dc.waves >= 2 ? 2 : 1;
+            hipLaunchKernelGGL(chain, dim3(2), dim3(64 * waves), 0, c->st.stream, Pp, Ap, n_complex, c->dc.work_stride, c->dc.d_state, c->dc.d_counters,
+                               kDcMaxIter);
+        } else {
+            hipLaunchKernelGGL(k_dc_chain, dim3(2), dim3(64), 0, c->st.stream, Pp, Ap, n_complex, c->dc.work_stride, c->dc.d_state);
+        }
+        hipLaunchKernelGGL(k_dc_apply, dim3((words + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), Ap,
+                           reinterpret_cast<float4 *>(c->d_raw_tiled), n_complex, c->dc.work_stride);
+        mode = kRawTiled;
+    } else if (correct_dc) {
+        Bracket b(c, c->st.stream, KIND_INGEST, 0);
+        const int par = (int)(c->dc.frames++ & 1ull);
+        double2 *sums = reinterpret_cast<double2 *>(c->dc.d_tab + c->dc.tab_sums);
+        hipLaunchKernelGGL(k_dc_block_sums, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), n_complex,
+                           c->dc.d_tab, sums);
+        hipLaunchKernelGGL(k_ingest_u8_dc_fast, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
+                           reinterpret_cast<float4 *>(c->d_raw_tiled), n_complex, c->dc.d_state + 2 * par, c->dc.d_state + 2 * (par ^ 1),
+                           c->dc.d_tab, sums);
+        mode = kRawTiled;
+    }
+    c->long_frame = correct_dc && !c->opt_dc_blocked;
+    const int rc = enqueue_frame(c, dev_bytes, mode, egress);
+    c->long_frame = false;
+    if (rc == SDRX_OK)
+        c->last_raw = mode;
+    return rc;
+}
+
+int enqueue_u8(sdrx_ctx *c, const uint8_t *bytes, int n_complex, int correct_dc, bool egress)
+{
+    int rc = ensure_raw(c, (size_t)c->root_frame);
+    if (rc)
+        return rc;
+    unsigned char *dst = c->d_raw_u8[c->frame_no & 1ull];
+    rc = stage_host_frame(c, bytes, (size_t)n_complex * 2, dst);
+    return rc ? rc : enqueue_u8_device(c, dst, n_complex, correct_dc, egress);
+}
+
+} // namespace
+
+extern "C" {
+
+int sdrx_process_device(sdrx_ctx *c, const void *dev_iq, int n_complex)
+{
+    int rc = check_frame_call(c, "sdrx_process_device", dev_iq, n_complex, true);
+    if (rc)
+        return rc;
+    c->last_raw = -1;
+    return enqueue_frame(c, dev_iq, kRawF32, false);
+}
+
+int sdrx_submit_device(sdrx_ctx *c, const void *dev_iq, int n_complex)
+{
+    int rc = check_frame_call(c, "sdrx_submit_device", dev_iq, n_complex, false);
+    if (rc)
+        return rc;
+    c->last_raw = -1;
+    return enqueue_frame(c, dev_iq, kRawF32, true);
+}
+
+int sdrx_submit(sdrx_ctx *c, const float *iq, int n_complex)
+{
+    int rc = check_frame_call(c, "sdrx_submit", iq, n_complex, false);
+    return rc ? rc : enqueue_f32(c, iq, n_complex, true);
+}
+
+int sdrx_submit_u8(sdrx_ctx *c, const uint8_t *bytes, int n_complex, int correct_dc)
+{
+    int rc = check_frame_call(c, "sdrx_submit_u8", bytes, n_complex, false);
+    return rc ? rc : enqueue_u8(c, bytes, n_complex, correct_dc, true);
+}
+
+// The frame `src` staged LAST (host floats or dongle bytes handed to sdrx_process* / sdrx_submit* of `src`) once
+// more, through the tree of `c` -- two contexts on one device fed the same raw frame, as sdrj::demodData feeds
+// every main VFO the same `samples` (sdrj.cpp:288-294) -- without a second host-to-device copy: `c` waits for
+// src's upload event and reads src's device buffer.  That buffer is per frame parity: it stays untouched until
+// `src` stages the frame after next, by which time the caller must have waited for this one on `c`.
+// `same_as` (may be null): host cf32 the caller believes to BE that frame -- compared byte for byte with src's pinned staging
+// copy first; SDRX_DIFFERENT and nothing queued when it is not.
+static int submit_shared(sdrx_ctx *c, sdrx_ctx *src, const char *what, bool sync_call, const float *same_as = nullptr, int same_n = 0)
+{
+    if (!c || !src || c == src)
+        return c ? fail(c, SDRX_EINVAL, "%s: needs another context as the source", what) : SDRX_EINVAL;
+    if (!src->finalized || src->frame_no == 0 || (src->last_raw != kRawF32 && src->last_raw != kRawU8))
+        return fail(c, SDRX_ESTATE, "%s: the source context has staged no host frame (floats or bytes without DC removal) yet", what);
+    if (src->device != c->device)
+        return fail(c, SDRX_EINVAL, "%s: the source context lives on device %d, this one on %d", what, src->device, c->device);
+    const int p = (int)((src->frame_no - 1) & 1ull);
+    if (same_as) {
+        if (src->last_raw != kRawF32 || same_n != src->root_frame || !src->h_in[p] ||
+            memcmp(src->h_in[p], same_as, (size_t)same_n * sizeof(float2)) != 0)
+            return SDRX_DIFFERENT;
+    }
+    const void *frame = src->last_raw == kRawF32 ? (const void *)src->d_raw[p] : (const void *)src->d_raw_u8[p];
+    int rc = check_frame_call(c, what, frame, src->root_frame, sync_call);
+    if (rc)
+        return rc;
+    if (src->last_raw == kRawU8 && !c->root_direct)
+        return fail(c, SDRX_EUNSUPPORTED, "%s: a wide level 0 (more than 4 parent-less VFOs) shares float frames only", what);
+    // src's NEXT upload into this buffer (its frame after next) must not overtake this context's kernels: an event behind
+    // them, which src's staging waits for.  One event per (reader, parity), acquired BEFORE anything is queued -- a failure
+    // here leaves no frame in flight -- and re-recorded for every shared frame (a source that never restages, or a reader
+    // fed through sdrx_process_device, does not pile events up).
+    sdrx_ctx::SharedReader *slot = nullptr;
+    for (auto &r : src->shared_readers[p])
+        if (r.who == c)
+            slot = &r;
+    if (!slot) {
+        hipEvent_t e = nullptr;
+        HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        src->shared_readers[p].push_back({c, e, false});
+        slot = &src->shared_readers[p].back();
+    }
+    HIPCHK(c, hipStreamWaitEvent(c->st.stream, src->st.ev_staged[p], 0));
+    c->last_raw = -1; // (not this context's buffer: sdrx_get_raw is served by `src`)
+    const int src_raw = src->last_raw;
+    rc = enqueue_frame(c, frame, src_raw, true);
+    if (rc)
+        return rc;
+    if (hipEventRecord(slot->ev, c->st.stream) == hipSuccess)
+        slot->pending = true;
+    else
+        (void)hipStreamSynchronize(c->st.stream); // (the frame IS queued: order it the blunt way rather than report a failure)
+    return SDRX_OK;
+}
+
+int sdrx_submit_shared(sdrx_ctx *c, sdrx_ctx *src) { return submit_shared(c, src, "sdrx_submit_shared", false); }
+
+int sdrx_process_shared(sdrx_ctx *c, sdrx_ctx *src)
+{
+    const int rc = submit_shared(c, src, "sdrx_process_shared", true);
+    return rc ? rc : sdrx_wait(c);
+}
+
+int sdrx_submit_if_same(sdrx_ctx *c, sdrx_ctx *src, const float *iq, int n_complex)
+{
+    if (!iq)
+        return c ? fail(c, SDRX_EINVAL, "sdrx_submit_if_same: null frame pointer") : SDRX_EINVAL;
+    return submit_shared(c, src, "sdrx_submit_if_same", false, iq, n_complex);
+}
+
+int sdrx_process_if_same(sdrx_ctx *c, sdrx_ctx *src, const float *iq, int n_complex)
+{
+    if (!iq)
+        return c ? fail(c, SDRX_EINVAL, "sdrx_process_if_same: null frame pointer") : SDRX_EINVAL;
+    const int rc = submit_shared(c, src, "sdrx_process_if_same", true, iq, n_complex);
+    return rc ? rc : sdrx_wait(c);
+}
+
+int sdrx_in_flight(sdrx_ctx *c) { return c ? c->in_flight : SDRX_EINVAL; }
+
+
+int sdrx_sync(sdrx_ctx *c)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    return drain(c);
+}
+
+int sdrx_process(sdrx_ctx *c, const float *iq, int n_complex)
+{
+    int rc = check_frame_call(c, "sdrx_process", iq, n_complex, true);
+    if (rc)
+        return rc;
+    rc = enqueue_f32(c, iq, n_complex, true);
+    return rc ? rc : sdrx_wait(c);
+}
+
+int sdrx_process_u8(sdrx_ctx *c, const uint8_t *bytes, int n_complex, int correct_dc)
+{
+    int rc = check_frame_call(c, "sdrx_process_u8", bytes, n_complex, true);
+    if (rc)
+        return rc;
+    rc = enqueue_u8(c, bytes, n_complex, correct_dc, true);
+    return rc ? rc : sdrx_wait(c);
+}
+
+} // extern "C"

@@ -74,6 +74,15 @@ int member_fail(sdrx_group *g, int k, int rc)
     return gfail(g, rc, "device %d (member %d): %s", g->m[(size_t)k].device, k, sdrx_last_error(g->m[(size_t)k].c));
 }
 
+// The id list of a per-leaf group call `what`: every id one of sdrx_group_add_vfo and held by a member (g->where)
+int group_check_ids(sdrx_group *g, const char *what, const int *ids, int n)
+{
+    for (int k = 0; k < n; ++k)
+        if (ids[k] < 0 || ids[k] >= (int)g->descs.size() || g->where[(size_t)ids[k]].first < 0)
+            return gfail(g, SDRX_EINVAL, "%s: bad vfo id %d", what, ids[k]);
+    return SDRX_OK;
+}
+
 // frame (cf32 or bytes, `bytes` long) is complete on the first device at `src` once ev_ready[p] fires:
 // fan it out and enqueue frame processing on every member.
 int group_enqueue(sdrx_group *g, const void *src, size_t bytes, int raw_mode, bool egress, int correct_dc = 0)
@@ -85,12 +94,12 @@ int group_enqueue(sdrx_group *g, const void *src, size_t bytes, int raw_mode, bo
             continue;
         GHIP(g, hipSetDevice(M.device));
         const void *raw = src;
-        GHIP(g, hipStreamWaitEvent(M.c->stream, g->ev_ready[p], 0));
+        GHIP(g, hipStreamWaitEvent(M.c->st.stream, g->ev_ready[p], 0));
         if (k > 0) {
             if (M.device != g->m[0].device)
-                GHIP(g, hipMemcpyPeerAsync(M.d_frame[p], M.device, src, g->m[0].device, bytes, M.c->stream));
+                GHIP(g, hipMemcpyPeerAsync(M.d_frame[p], M.device, src, g->m[0].device, bytes, M.c->st.stream));
             else // two members on one device (tests on a 1-GPU box): the same transfer as a device copy
-                GHIP(g, hipMemcpyAsync(M.d_frame[p], src, bytes, hipMemcpyDeviceToDevice, M.c->stream));
+                GHIP(g, hipMemcpyAsync(M.d_frame[p], src, bytes, hipMemcpyDeviceToDevice, M.c->st.stream));
             raw = M.d_frame[p];
         }
         M.c->last_raw = -1;
@@ -575,9 +584,8 @@ int sdrx_group_get_meters(sdrx_group *g, const int *ids, int n, sdrx_meter *out)
         return gfail(g, SDRX_ESTATE, "sdrx_group_get_meters before sdrx_group_finalize");
     if (n < 0 || (n > 0 && (!ids || !out)))
         return gfail(g, SDRX_EINVAL, "sdrx_group_get_meters: n = %d", n);
-    for (int k = 0; k < n; ++k) // the whole list first: nothing is written for a bad one
-        if (ids[k] < 0 || ids[k] >= (int)g->descs.size() || g->where[(size_t)ids[k]].first < 0)
-            return gfail(g, SDRX_EINVAL, "bad vfo id %d", ids[k]);
+    if (int rc = group_check_ids(g, "sdrx_group_get_meters", ids, n)) // the whole list first: nothing is written for a bad one
+        return rc;
     for (int k = 0; k < n; ++k) {
         const auto w = g->where[(size_t)ids[k]];
         const int rc = sdrx_get_meters(g->m[(size_t)w.first].c, &w.second, 1, out + k);
@@ -600,8 +608,8 @@ int sdrx_group_set_squelch(sdrx_group *g, const int *ids, const uint64_t *thr, c
     const size_t W = g->m.size();
     std::vector<char> seen(g->descs.size(), 0);
     for (int k = 0; k < n; ++k) {
-        if (ids[k] < 0 || ids[k] >= (int)g->descs.size() || g->where[(size_t)ids[k]].first < 0)
-            return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch: bad vfo id %d", ids[k]);
+        if (int rc = group_check_ids(g, "sdrx_group_set_squelch", ids + k, 1))
+            return rc;
         const auto w = g->where[(size_t)ids[k]];
         if (!g->m[(size_t)w.first].c->nodes[(size_t)w.second].leaf)
             return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch: vfo %d has children and publishes nothing", ids[k]);
@@ -642,9 +650,8 @@ int sdrx_group_get_squelch(sdrx_group *g, const int *ids, int n, sdrx_squelch_st
         return gfail(g, SDRX_ESTATE, "sdrx_group_get_squelch before sdrx_group_finalize");
     if (n < 0 || (n > 0 && (!ids || !out)))
         return gfail(g, SDRX_EINVAL, "sdrx_group_get_squelch: n = %d", n);
-    for (int k = 0; k < n; ++k) // the whole list first: nothing is written for a bad one
-        if (ids[k] < 0 || ids[k] >= (int)g->descs.size() || g->where[(size_t)ids[k]].first < 0)
-            return gfail(g, SDRX_EINVAL, "bad vfo id %d", ids[k]);
+    if (int rc = group_check_ids(g, "sdrx_group_get_squelch", ids, n)) // the whole list first: nothing is written for a bad one
+        return rc;
     for (int k = 0; k < n; ++k) {
         const auto w = g->where[(size_t)ids[k]];
         const int rc = sdrx_get_squelch(g->m[(size_t)w.first].c, &w.second, 1, out + k);
@@ -692,8 +699,8 @@ int sdrx_group_get_preroll(sdrx_group *g, int id, const void **buf, uint32_t *le
         return SDRX_EINVAL;
     if (!g->finalized)
         return gfail(g, SDRX_ESTATE, "sdrx_group_get_preroll before sdrx_group_finalize");
-    if (id < 0 || id >= (int)g->descs.size() || g->where[(size_t)id].first < 0)
-        return gfail(g, SDRX_EINVAL, "bad vfo id %d", id);
+    if (int rc = group_check_ids(g, "sdrx_group_get_preroll", &id, 1))
+        return rc;
     const auto w = g->where[(size_t)id];
     const int rc = sdrx_get_preroll(g->m[(size_t)w.first].c, w.second, buf, len, frame);
     return rc ? member_fail(g, w.first, rc) : SDRX_OK;

@@ -224,7 +224,7 @@ def test_random_trees_bit_identical_to_two_launches():
 
 
 # (workload, arithmetic) -> does the planner fuse on a 256-CU MI355X: up to 64 demodulation blocks per CU in the exact arithmetic,
-# 16 in the others (sdrx.hip build_level_plan)
+# 16 in the others (sdrx_finalize.hip build_level_plan)
 FUSES = {("config3", "exact"): True, ("config3", "tolerance"): False, ("config3", "robust"): False, ("10k", "exact"): False,
          ("config4", "exact"): True, ("config4", "tolerance"): True, ("config4", "robust"): True}
 
