@@ -190,6 +190,18 @@ public:
         else
             check(sdrx_set_squelch(ctx_, ids.data(), thr_sum_sq.data(), hang_frames.data(), (int)ids.size()), "sdrx_set_squelch");
     }
+    // Auto-squelch (library option "squelch_auto" = 1): leaf ids[k]'s threshold becomes max(thr_sum_sq, floor * ratio_q8[k] / 256),
+    // the floor being the smallest sum_sq of its last window_frames[k] .. 2 * window_frames[k] - 1 frames; ratio_q8 0 = off for
+    // the leaf; between two frames.  Restarts the named leaves' floor.
+    void set_squelch_auto(const std::vector<int> &ids, const std::vector<uint32_t> &ratio_q8, const std::vector<uint32_t> &window_frames)
+    {
+        if (ids.size() != ratio_q8.size() || ids.size() != window_frames.size())
+            throw std::invalid_argument("set_squelch_auto: lists of different length");
+        if (grp_)
+            check(sdrx_group_set_squelch_auto(grp_, ids.data(), ratio_q8.data(), window_frames.data(), (int)ids.size()), "sdrx_group_set_squelch_auto");
+        else
+            check(sdrx_set_squelch_auto(ctx_, ids.data(), ratio_q8.data(), window_frames.data(), (int)ids.size()), "sdrx_set_squelch_auto");
+    }
 
 private:
     bool started() const { return ctx_ || grp_; }

@@ -156,6 +156,10 @@ int sdrx_add_vfo(sdrx_ctx *ctx, const sdrx_vfo_desc *desc, int *id_out);
  *            well, ahead of that of f: one frame, which is what the device still holds.  With "fuse_demod" leaves the tree
  *            keeps k_mix_levels + k_usb_demod in every arithmetic ("tail_in_levels" is not used), and "pipeline" = 1 loses its
  *            overlap.
+ *   "squelch_auto" 0 (default) | 1: the gate's threshold follows each leaf's own noise floor (sdrx_set_squelch_auto below); 1
+ *            implies "squelch".  0 changes nothing.  With 1 and every ratio_q8 0 (the start) the gate is that of "squelch" = 1.
+ *            Composes with "preroll", "fuse_demod", "tail_in_levels" and "pipeline" as "squelch" does: the gate keeps its
+ *            place in the launch sequence.
  *   "dc_blocked_scan" 0|1 (default 0): how sdrx_process_u8 removes the DC bias.  0 = the
  *                 reference's sequentially rounded fp32 recurrence, bit for bit (below).  1 = the same linear filter as a
  *                 blocked parallel scan (~15 us): the true IIR response.  The reference's recurrence
@@ -328,6 +332,37 @@ int sdrx_get_egress(sdrx_ctx *ctx, int64_t *frame, uint32_t *n_open, uint32_t *n
  * switched off and sdrx_finalize called again. */
 int sdrx_get_preroll(sdrx_ctx *ctx, int id, const void **buf, uint32_t *len_bytes, int64_t *frame);
 int sdrx_get_preroll_count(sdrx_ctx *ctx, uint32_t *n_preroll, uint64_t *preroll_bytes);
+/* Auto-squelch (option "squelch_auto" = 1): the gate's threshold as a RATIO over the leaf's own noise floor, the floor tracked
+ * on the device by minimum statistics over a sliding window of frames.  Per leaf two more settings -- ratio_q8 (a power ratio
+ * times 256; 0 = off for this leaf: the default) and window_frames (>= 1 wherever ratio_q8 > 0) -- and three more words of
+ * device state: cur_min, prev_min (uint64) and age (uint32); NONE = 2^64 - 1 is "no observation".  After sdrx_finalize, and
+ * after every sdrx_set_squelch_auto that names the leaf: cur_min = prev_min = NONE, age = 0.  For every frame the context
+ * processes, on whichever path, with s = the leaf's meter sum_sq of that frame, in integers:
+ *     floor   = min(cur_min, prev_min)                               (from the frames BEFORE this one)
+ *     auto    = 0 if ratio_q8 == 0 or floor == NONE, else min(2^64 - 1, (floor * ratio_q8) >> 8)     (the product in 128 bits)
+ *     thr_eff = max(thr_sum_sq, auto);   open / hang_left: the rule of sdrx_set_squelch with thr_eff in place of thr_sum_sq
+ *     cur_min = min(cur_min, s);  age += 1;  if age == window_frames: prev_min = cur_min, cur_min = NONE, age = 0
+ * What follows from it: the first frame after sdrx_finalize or a restart decides with thr_sum_sq alone (open, with the
+ * defaults); a frame of zeros makes the floor 0, so the gate fails open (thr_eff = thr_sum_sq) for at most 2 * window_frames
+ * - 1 frames; a burst never lifts its own threshold (the floor excludes the current frame), but a transmission longer than
+ * 2 * window_frames - 1 frames becomes the floor and, with ratio_q8 > 256, closes: choose window_frames above the longest
+ * transmission and keep ratio_q8 = 0 on continuous channels.  thr_sum_sq stays a lower bound.  sdrx_set_squelch does not touch
+ * the floor state; sdrx_set_squelch_auto does not touch thr_sum_sq, hang_frames, hang_left or prev_open; pre-roll follows
+ * `open` as before.  There is no default ratio or window: what a real front end needs has not been measured.
+ * sdrx_set_squelch_auto: batched and atomic, with the calling rules of sdrx_set_squelch; besides, window_frames[k] == 0 with
+ * ratio_q8[k] > 0 is SDRX_EINVAL with nothing changed.  One small upload and one small launch per call.
+ * sdrx_get_squelch_auto: for the last DELIVERED frame, the floor and the threshold that decided it; calling rules of
+ * sdrx_get_squelch.  ratio_q8 and window_frames are as set. */
+typedef struct sdrx_squelch_auto_state {
+    int64_t frame;           /* the frame these values decided */
+    uint64_t floor_sum_sq;   /* min(cur_min, prev_min) in front of that frame; 0 while floor_valid is 0 */
+    uint64_t thr_eff_sum_sq; /* max(thr_sum_sq, auto) */
+    uint32_t ratio_q8, window_frames;
+    uint32_t floor_valid;    /* 0: the leaf had no observation yet */
+    uint32_t reserved;
+} sdrx_squelch_auto_state;
+int sdrx_set_squelch_auto(sdrx_ctx *ctx, const int *ids, const uint32_t *ratio_q8, const uint32_t *window_frames, int n);
+int sdrx_get_squelch_auto(sdrx_ctx *ctx, const int *ids, int n, sdrx_squelch_auto_state *out);
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);
@@ -468,6 +503,11 @@ int sdrx_group_get_meters(sdrx_group *grp, const int *ids, int n, sdrx_meter *ou
 int sdrx_group_set_squelch(sdrx_group *grp, const int *ids, const uint64_t *thr_sum_sq, const uint32_t *hang_frames, int n);
 int sdrx_group_get_squelch(sdrx_group *grp, const int *ids, int n, sdrx_squelch_state *out);
 int sdrx_group_get_egress(sdrx_group *grp, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied);
+/* sdrx_set_squelch_auto / sdrx_get_squelch_auto with ids of the whole tree (group option "squelch_auto" = 1), each id routed
+ * to the member that owns the leaf. */
+int sdrx_group_set_squelch_auto(sdrx_group *grp, const int *ids, const uint32_t *ratio_q8, const uint32_t *window_frames, int n);
+int sdrx_group_get_squelch_auto(sdrx_group *grp, const int *ids, int n, sdrx_squelch_auto_state *out);
+
 /* sdrx_get_preroll routed to the member that owns the leaf; sdrx_get_preroll_count summed over the members (group option
  * "preroll" = 1). */
 int sdrx_group_get_preroll(sdrx_group *grp, int id, const void **buf, uint32_t *len_bytes, int64_t *frame);

@@ -62,6 +62,12 @@ class SquelchStateC(C.Structure):
                 ("open", C.c_int32), ("reserved", C.c_uint32)]
 
 
+class SquelchAutoStateC(C.Structure):
+    """struct sdrx_squelch_auto_state"""
+    _fields_ = [("frame", C.c_int64), ("floor_sum_sq", C.c_uint64), ("thr_eff_sum_sq", C.c_uint64), ("ratio_q8", C.c_uint32),
+                ("window_frames", C.c_uint32), ("floor_valid", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 PUBLISH_FN =C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
 
 # every symbol include/sdrx.h declares: (restype, argtypes)
@@ -109,6 +115,10 @@ SYMBOLS = {
     "sdrx_get_preroll_count": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "sdrx_group_get_preroll": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int64)]),
     "sdrx_group_get_preroll_count": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "sdrx_set_squelch_auto": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "sdrx_get_squelch_auto": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_group_set_squelch_auto": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "sdrx_group_get_squelch_auto": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

@@ -99,6 +99,7 @@ void free_device_state(sdrx_ctx *c)
     dfree(c->sq.d_cfg);
     dfree(c->sq.d_hang);
     dfree(c->sq.d_prev);
+    dfree(c->sq.d_auto);
     dfree(c->sq.d_jobs);
     c->sq.jobs_cap = 0;
     c->sq.bytes = c->sq.dir_off = c->sq.pack_bytes = c->sq.hpack_off = 0;
@@ -228,6 +229,8 @@ int sdrx_set_option(sdrx_ctx *c, const char *name, int value)
         c->opt_squelch = value != 0;
     else if (!strcmp(name, "preroll"))
         c->opt_preroll = value != 0;
+    else if (!strcmp(name, "squelch_auto"))
+        c->opt_squelch_auto = value != 0;
     else
         return fail(c, SDRX_EINVAL, "unknown option '%s'", name);
     return SDRX_OK;
@@ -322,7 +325,7 @@ int sdrx_finalize(sdrx_ctx *c)
         return fail(c, SDRX_ESTATE, "sdrx_finalize: no VFOs");
     HIPCHK(c, hipSetDevice(c->device));
     const int asked_squelch = c->opt_squelch, asked_meter = c->opt_meter;
-    if (c->opt_preroll) // the pre-roll is the gate's
+    if (c->opt_preroll || c->opt_squelch_auto) // the pre-roll and the floor tracking are the gate's
         c->opt_squelch = 1;
     if (c->opt_squelch) // the gate reads the meter records
         c->opt_meter = 1;

@@ -103,7 +103,7 @@ struct sdrx_ctx {
     int opt_exact = 1, opt_prequant = 0, opt_segments = 0, opt_dc_blocked = 0, opt_pipeline = 0, opt_dc_speculative = 1;
     int opt_fuse = 1, opt_frame_pipeline = 1, opt_fuse_late = 1, opt_keep_streams = 0, opt_fuse_demod = 0;
     int opt_tail_in_levels = 1;
-    int opt_meter = 0, opt_squelch = 0, opt_preroll = 0;
+    int opt_meter = 0, opt_squelch = 0, opt_preroll = 0, opt_squelch_auto = 0;
     // option meter: per frame parity, behind the payloads in d_pay / h_pay (at meter_off), one 16-byte MeterAcc record per work
     // unit that emits payload values (kernels.hip "output meters"); the records travel in the payload copy
     size_t meter_off = 0;
@@ -117,6 +117,8 @@ struct sdrx_ctx {
     // of f-1 in front of that of f.  prev_open per leaf on the device; the directory gains pre[n] behind hang[n]; d_pack[p] holds
     // the worst case (every leaf re-opens: twice the payload region), and so does its host side, which then lies BEHIND the
     // fixed part of h_pay[p] (at hpack_off; 0 with the option off: the start of h_pay[p], as before).
+    // Option squelch_auto: the threshold follows each leaf's noise floor.  One SqAuto record per leaf on the
+    // device (floor state and settings); the directory gains thr_eff[n] | floor[n] (u64) at aux_off, behind everything else.
     struct Squelch {
         size_t dir_off = 0, pack_bytes = 0, bytes = 0; // bytes: what the option allocates besides the directory
         unsigned char *d_pack[2] = {nullptr, nullptr};
@@ -124,7 +126,8 @@ struct sdrx_ctx {
         SqCfg *d_cfg = nullptr;
         unsigned *d_hang = nullptr; // hang_left per leaf: one array, every gate runs in frame order on one stream
         unsigned *d_prev = nullptr; // prev_open per leaf (preroll)
-        SqJob *d_jobs = nullptr;
+        SqAuto *d_auto = nullptr;   // floor state and settings per leaf (squelch_auto)
+        SqJob *d_jobs = nullptr;    // job list of sdrx_set_squelch and (SqAutoJob: the same size) sdrx_set_squelch_auto
         size_t jobs_cap = 0;
         int tiles = 1;                        // k_squelch_gather's grid.y: 16 KiB tiles of the longest payload
         std::vector<int> index;               // node -> its place in publish order (-1: not a leaf)
@@ -138,6 +141,9 @@ struct sdrx_ctx {
         std::vector<unsigned> pre, units;     // the delivered directory's pre-roll flags; 64-byte units of every leaf's payload
         unsigned n_pre = 0;                   // pre-rolled leaves of the delivered frame
         unsigned long long pre_bytes = 0;     //   ... and the packed bytes their pre-roll added to the copy
+        size_t aux_off = 0;                   // squelch_auto: thr_eff[n] | floor[n] inside the directory (sq_aux_off)
+        std::vector<SqAutoJob> acfg;          //   ... host copy of the settings (index = the leaf's place)
+        std::vector<unsigned long long> thr_eff, floor; // ... the delivered directory's values (floor: kSqNone = no observation)
         hipEvent_t ev_dir[2] = {nullptr, nullptr}; // the fixed-size part of frame f is in h_pay[f & 1]
     } sq;
 

@@ -119,6 +119,10 @@ void squelch_delivered(sdrx_ctx *c, int p)
             if (c->sq.pre[k])
                 c->sq.pre_bytes += 64ull * c->sq.units[k];
     }
+    if (c->opt_squelch_auto && n) { // the threshold and the floor that decided this frame
+        memcpy(c->sq.thr_eff.data(), dir + c->sq.aux_off, 8 * n);
+        memcpy(c->sq.floor.data(), dir + c->sq.aux_off + 8 * n, 8 * n);
+    }
 }
 
 // the oldest undelivered frame's payload copy, if sdrx_wait is the one to issue it (enqueue_frame: every frame under option
@@ -390,6 +394,83 @@ int sdrx_get_squelch(sdrx_ctx *c, const int *ids, int n, sdrx_squelch_state *out
         s.hang_frames = c->sq.cfg[i].hang_frames;
         s.hang_left = c->sq.hang[i];
         s.open = c->sq.offs[i] != kSqClosed;
+        out[k] = s;
+    }
+    return SDRX_OK;
+}
+
+// As sdrx_set_squelch: the whole list is checked before anything changes; then the software pipeline runs out with the old
+// values, one upload of the job list, one k_squelch_set_auto launch (which restarts the named leaves' floor state).
+int sdrx_set_squelch_auto(sdrx_ctx *c, const int *ids, const uint32_t *ratio_q8, const uint32_t *window_frames, int n)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_set_squelch_auto before sdrx_finalize");
+    if (!c->opt_squelch_auto)
+        return fail(c, SDRX_ESTATE, "sdrx_set_squelch_auto: option \"squelch_auto\" is off");
+    if (n < 0 || (n > 0 && (!ids || !ratio_q8 || !window_frames)))
+        return fail(c, SDRX_EINVAL, "sdrx_set_squelch_auto: n = %d, ids %p, ratios %p, windows %p", n, (const void *)ids, (const void *)ratio_q8,
+                    (const void *)window_frames);
+    if (int rc = check_leaf_ids(c, "sdrx_set_squelch_auto", ids, n, true))
+        return rc;
+    for (int k = 0; k < n; ++k)
+        if (ratio_q8[k] > 0 && window_frames[k] == 0)
+            return fail(c, SDRX_EINVAL, "sdrx_set_squelch_auto: vfo %d: window_frames 0 with ratio_q8 %u", ids[k], ratio_q8[k]);
+    if (c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "sdrx_set_squelch_auto: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+    if (n == 0)
+        return SDRX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c))
+        return rc;
+    std::vector<SqAutoJob> jobs((size_t)n);
+    for (int k = 0; k < n; ++k)
+        jobs[(size_t)k] = SqAutoJob{ratio_q8[k], window_frames[k], (unsigned)c->sq.index[(size_t)ids[k]], 0};
+    if (jobs.size() > c->sq.jobs_cap) { // (one buffer for both setters: SqAutoJob is as large as SqJob)
+        if (c->sq.d_jobs)
+            (void)hipFree(c->sq.d_jobs);
+        c->sq.d_jobs = nullptr;
+        c->sq.jobs_cap = 0;
+        HIPCHK(c, hipMalloc(&c->sq.d_jobs, sizeof(SqJob) * jobs.size()));
+        c->sq.jobs_cap = jobs.size();
+    }
+    HIPCHK(c, hipMemcpyAsync(c->sq.d_jobs, jobs.data(), sizeof(SqAutoJob) * jobs.size(), hipMemcpyHostToDevice, c->st.stream));
+    hipLaunchKernelGGL(k_squelch_set_auto, dim3((n + 63) / 64), dim3(64), 0, c->st.stream, reinterpret_cast<const SqAutoJob *>(c->sq.d_jobs), n,
+                       c->sq.d_auto);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->st.stream)); // (`jobs` lives on this stack)
+    for (const SqAutoJob &J : jobs)
+        c->sq.acfg[J.index] = J;
+    return SDRX_OK;
+}
+
+int sdrx_get_squelch_auto(sdrx_ctx *c, const int *ids, int n, sdrx_squelch_auto_state *out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_squelch_auto before sdrx_finalize");
+    if (!c->opt_squelch_auto)
+        return fail(c, SDRX_ESTATE, "sdrx_get_squelch_auto: option \"squelch_auto\" is off");
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return fail(c, SDRX_EINVAL, "sdrx_get_squelch_auto: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
+    if (int rc = check_leaf_ids(c, "sdrx_get_squelch_auto", ids, n, false))
+        return rc;
+    if (n == 0)
+        return SDRX_OK;
+    if (int rc = need_delivered(c, "sdrx_get_squelch_auto"))
+        return rc;
+    for (int k = 0; k < n; ++k) {
+        const size_t i = (size_t)c->sq.index[(size_t)ids[k]];
+        sdrx_squelch_auto_state s;
+        memset(&s, 0, sizeof s);
+        s.frame = (int64_t)c->host_frame;
+        s.floor_valid = c->sq.floor[i] != kSqNone;
+        s.floor_sum_sq = s.floor_valid ? c->sq.floor[i] : 0;
+        s.thr_eff_sum_sq = c->sq.thr_eff[i];
+        s.ratio_q8 = c->sq.acfg[i].ratio_q8;
+        s.window_frames = c->sq.acfg[i].window_frames;
         out[k] = s;
     }
     return SDRX_OK;

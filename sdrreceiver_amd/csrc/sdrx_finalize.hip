@@ -657,13 +657,17 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
     HIPCHK(c, hipMemsetAsync(c->arena, 0, c->arena_bytes, c->st.stream));
     // (the copy length stays a multiple of 64 bytes, as the packed payloads are)
     c->pay_bytes = std::max<size_t>(c->opt_meter ? align_up(c->meter_off + 16 * (size_t)c->meter_slots, 64) : B.pay, 64);
-    c->sq.dir_off = c->sq.pack_bytes = c->sq.hpack_off = 0; // (a finalize that was refused may have left another tree's values)
+    c->sq.dir_off = c->sq.pack_bytes = c->sq.hpack_off = c->sq.aux_off = 0; // (a finalize that was refused may have left another tree's values)
     if (c->opt_squelch) { // the directory behind the records: one fixed-size copy brings both
         size_t n_leaves = 0;
         for (const Node &n : c->nodes)
             n_leaves += n.leaf;
         c->sq.dir_off = c->pay_bytes;
         c->pay_bytes = align_up(c->sq.dir_off + sizeof(SqHeader) + (c->opt_preroll ? 12 : 8) * n_leaves, 64);
+        if (c->opt_squelch_auto) { // thr_eff[n] | floor[n] behind it
+            c->sq.aux_off = sq_aux_off(n_leaves, c->opt_preroll != 0);
+            c->pay_bytes = align_up(c->sq.dir_off + c->sq.aux_off + 16 * n_leaves, 64);
+        }
         c->sq.pack_bytes = std::max<size_t>(align_up(B.pay, 64), 64);
         if (c->opt_preroll) { // every leaf re-opens: two payloads each; on the host behind the fixed part, which they could overrun
             c->sq.pack_bytes *= 2;
@@ -883,6 +887,16 @@ int squelch_setup(sdrx_ctx *c)
         HIPCHK(c, hipMalloc(&c->sq.d_prev, sizeof(unsigned) * n1));
         HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->sq.d_prev), 1, n1, c->st.stream));
         c->sq.bytes += sizeof(unsigned) * n1;
+    }
+    std::vector<SqAuto> fresh; // (lives until the synchronisation below)
+    if (c->opt_squelch_auto) { // no observation, ratio 0: the plain gate until sdrx_set_squelch_auto
+        c->sq.acfg.assign(n, SqAutoJob{0, 0, 0, 0});
+        c->sq.thr_eff.assign(n, 0);
+        c->sq.floor.assign(n, kSqNone);
+        fresh.assign(n1, SqAuto{kSqNone, kSqNone, 0, 0, 0, 0});
+        HIPCHK(c, hipMalloc(&c->sq.d_auto, sizeof(SqAuto) * n1));
+        HIPCHK(c, hipMemcpyAsync(c->sq.d_auto, fresh.data(), sizeof(SqAuto) * n1, hipMemcpyHostToDevice, c->st.stream));
+        c->sq.bytes += sizeof(SqAuto) * n1;
     }
     HIPCHK(c, hipMemcpyAsync(c->sq.d_leaves, leaves.data(), sizeof(SqLeaf) * n, hipMemcpyHostToDevice, c->st.stream));
     HIPCHK(c, hipMemsetAsync(c->sq.d_cfg, 0, sizeof(SqCfg) * n1, c->st.stream));

@@ -125,24 +125,32 @@ void spectrum_raw_step(sdrx_ctx *c, const void *raw, int raw_mode)
 
 // Option squelch: the gate of frame `frame`, on the stream -- and behind the launch -- that completed its payloads and meter
 // records: decide + scan (one workgroup), then the gather of the open leaves into d_pack[p] (squelch.hip).  Not bracketed:
-// sdrx_get_kernel_times keeps its SDRX_NKERNELS kinds.
-void squelch_gate(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
+// sdrx_get_kernel_times keeps its SDRX_NKERNELS kinds.  PRE (option preroll): the two launches in their second form -- the gather
+// also reads frame - 1's payloads in d_pay[p ^ 1]; AUTO (option squelch_auto): the scan with the floor records, the gather as without.
+template <bool PRE, bool AUTO>
+void launch_gate(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
 {
     const int n = (int)c->publish_order.size();
-    if (!c->opt_squelch || n == 0)
-        return;
     const int p = (int)(frame & 1ull);
     unsigned char *dir = c->d_pay[p] + c->sq.dir_off;
-    if (c->opt_preroll) { // the same two launches in their second form: the gather also reads frame - 1's payloads in d_pay[p ^ 1]
-        const SqPre<true> X = {c->sq.d_prev, c->d_pay[p ^ 1]};
-        hipLaunchKernelGGL(k_squelch_scan<true>, dim3(1), dim3(kSqThreads), 0, ts, c->sq.d_leaves, c->sq.d_cfg, c->sq.d_hang, c->d_pay[p], dir, n,
-                           (long long)frame, X);
-        hipLaunchKernelGGL(k_squelch_gather<true>, dim3(n, c->sq.tiles, 2), dim3(256), 0, ts, c->sq.d_leaves, c->d_pay[p], dir, c->sq.d_pack[p], X);
+    SqPre<PRE> X;
+    SqAut<AUTO> A;
+    if constexpr (PRE)
+        X = {c->sq.d_prev, c->d_pay[p ^ 1]};
+    if constexpr (AUTO)
+        A = {c->sq.d_auto};
+    hipLaunchKernelGGL((k_squelch_scan<PRE, AUTO>), dim3(1), dim3(kSqThreads), 0, ts, c->sq.d_leaves, c->sq.d_cfg, c->sq.d_hang, c->d_pay[p], dir, n,
+                       (long long)frame, X, A);
+    hipLaunchKernelGGL(k_squelch_gather<PRE>, dim3(n, c->sq.tiles, PRE ? 2 : 1), dim3(256), 0, ts, c->sq.d_leaves, c->d_pay[p], dir, c->sq.d_pack[p], X);
+}
+void squelch_gate(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
+{
+    if (!c->opt_squelch || c->publish_order.empty())
         return;
-    }
-    hipLaunchKernelGGL(k_squelch_scan<>, dim3(1), dim3(kSqThreads), 0, ts, c->sq.d_leaves, c->sq.d_cfg, c->sq.d_hang, c->d_pay[p], dir, n, (long long)frame,
-                       SqPre<false>());
-    hipLaunchKernelGGL(k_squelch_gather<>, dim3(n, c->sq.tiles), dim3(256), 0, ts, c->sq.d_leaves, c->d_pay[p], dir, c->sq.d_pack[p], SqPre<false>());
+    if (c->opt_preroll)
+        c->opt_squelch_auto ? launch_gate<true, true>(c, ts, frame) : launch_gate<true, false>(c, ts, frame);
+    else
+        c->opt_squelch_auto ? launch_gate<false, true>(c, ts, frame) : launch_gate<false, false>(c, ts, frame);
 }
 
 // One block-per-tile launch of the leaf tail (late decimation / demodulation / long audio low-pass / compress) for `frame`.

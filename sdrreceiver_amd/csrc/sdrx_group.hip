@@ -661,6 +661,72 @@ int sdrx_group_get_squelch(sdrx_group *g, const int *ids, int n, sdrx_squelch_st
     return SDRX_OK;
 }
 
+// sdrx_set_squelch_auto over the whole tree, as sdrx_group_set_squelch: everything is checked before any member changes
+int sdrx_group_set_squelch_auto(sdrx_group *g, const int *ids, const uint32_t *ratio_q8, const uint32_t *window_frames, int n)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch_auto before sdrx_group_finalize");
+    if (n < 0 || (n > 0 && (!ids || !ratio_q8 || !window_frames)))
+        return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch_auto: n = %d", n);
+    const size_t W = g->m.size();
+    std::vector<char> seen(g->descs.size(), 0);
+    for (int k = 0; k < n; ++k) {
+        if (int rc = group_check_ids(g, "sdrx_group_set_squelch_auto", ids + k, 1))
+            return rc;
+        const auto w = g->where[(size_t)ids[k]];
+        if (!g->m[(size_t)w.first].c->nodes[(size_t)w.second].leaf)
+            return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch_auto: vfo %d has children and publishes nothing", ids[k]);
+        if (seen[(size_t)ids[k]]++)
+            return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch_auto: vfo %d listed twice", ids[k]);
+        if (ratio_q8[k] > 0 && window_frames[k] == 0)
+            return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch_auto: vfo %d: window_frames 0 with ratio_q8 %u", ids[k], ratio_q8[k]);
+    }
+    for (size_t k = 0; k < W; ++k)
+        if (g->m[k].c && !g->m[k].c->opt_squelch_auto)
+            return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch_auto: option \"squelch_auto\" is off");
+    if (g->broken)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch_auto: an earlier frame failed on one member");
+    if (g->in_flight > 0)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch_auto: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
+    std::vector<std::vector<int>> lids(W);
+    std::vector<std::vector<uint32_t>> rv(W), wv(W);
+    for (int k = 0; k < n; ++k) {
+        const auto w = g->where[(size_t)ids[k]];
+        lids[(size_t)w.first].push_back(w.second);
+        rv[(size_t)w.first].push_back(ratio_q8[k]);
+        wv[(size_t)w.first].push_back(window_frames[k]);
+    }
+    for (size_t k = 0; k < W; ++k) {
+        if (lids[k].empty())
+            continue;
+        const int rc = sdrx_set_squelch_auto(g->m[k].c, lids[k].data(), rv[k].data(), wv[k].data(), (int)lids[k].size());
+        if (rc)
+            return member_fail(g, (int)k, rc);
+    }
+    return SDRX_OK;
+}
+
+int sdrx_group_get_squelch_auto(sdrx_group *g, const int *ids, int n, sdrx_squelch_auto_state *out)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_squelch_auto before sdrx_group_finalize");
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return gfail(g, SDRX_EINVAL, "sdrx_group_get_squelch_auto: n = %d", n);
+    if (int rc = group_check_ids(g, "sdrx_group_get_squelch_auto", ids, n)) // the whole list first: nothing is written for a bad one
+        return rc;
+    for (int k = 0; k < n; ++k) {
+        const auto w = g->where[(size_t)ids[k]];
+        const int rc = sdrx_get_squelch_auto(g->m[(size_t)w.first].c, &w.second, 1, out + k);
+        if (rc)
+            return member_fail(g, w.first, rc);
+    }
+    return SDRX_OK;
+}
+
 int sdrx_group_get_egress(sdrx_group *g, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied)
 {
     if (!g)

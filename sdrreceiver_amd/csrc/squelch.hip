@@ -21,6 +21,16 @@
 // its offset, that of frame f directly behind -- and the directory gains pre[n] behind hang[n], the header the count of
 // pre-rolled leaves.  The gather's grid gets a third dimension: z = 0 copies from d_pay[p] as before, z = 1 from d_pay[p ^ 1]
 // and returns after one 4-byte load unless the leaf is pre-rolled.
+//
+// Option "squelch_auto"  launches k_squelch_scan with the template parameter AUTO (the gather is
+// unchanged): the threshold follows the leaf's own noise floor, tracked by minimum statistics over a sliding window of frames.
+// One 32-byte record per leaf (SqAuto: state and settings, two 16-byte loads issued with the pass's other loads, in front of
+// the meter records -- no dependent step more).  With s the frame's sum_sq and NONE = 2^64 - 1 "no observation":
+//     floor   = min(cur_min, prev_min)                                       (the frames BEFORE this one)
+//     auto    = ratio_q8 == 0 || floor == NONE ? 0 : min(NONE, (floor * ratio_q8) >> 8)      (the product in 128 bits)
+//     thr_eff = max(thr, auto);  the rule above with thr_eff in place of thr
+//     cur_min = min(cur_min, s);  age += 1;  if (age == window_frames) { prev_min = cur_min; cur_min = NONE; age = 0; }
+// and the directory gains thr_eff[n] and floor[n] (u64, 8-byte aligned) behind what it holds without: this frame's values.
 #pragma once
 
 namespace sdrx {
@@ -49,6 +59,18 @@ struct SqJob { // sdrx_set_squelch: leaf `index` (publish order) gets thr / hang
     unsigned hang_frames, index;
 };
 
+constexpr unsigned long long kSqNone = ~0ull; // option squelch_auto: no observation
+struct SqAuto { // option squelch_auto: a leaf's floor state and settings, 32 bytes = two 16-byte loads
+    unsigned long long cur_min, prev_min; // minimum of sum_sq in the running bucket / in the one before
+    unsigned age;                         // frames in the running bucket
+    unsigned ratio_q8, window_frames;     // sdrx_set_squelch_auto (ratio_q8 = 0: off for this leaf)
+    unsigned pad;
+};
+struct SqAutoJob { // sdrx_set_squelch_auto: leaf `index` gets ratio_q8 / window_frames, its floor state restarts
+    unsigned ratio_q8, window_frames, index, pad;
+};
+static_assert(sizeof(SqAuto) == 32 && sizeof(SqAutoJob) == sizeof(SqJob), "squelch_auto: record sizes");
+
 template <bool PRE>
 struct SqPre { // what the second form of the gate's kernels is given besides (option preroll); empty for the first
 };
@@ -56,6 +78,14 @@ template <>
 struct SqPre<true> {
     unsigned *prev_open;           // k_squelch_scan: per leaf, 1 = the previous gate left it open
     const unsigned char *pay_prev; // k_squelch_gather: d_pay[p ^ 1], the payloads of the frame before
+};
+
+template <bool AUTO>
+struct SqAut { // what k_squelch_scan<.., AUTO> is given besides (option squelch_auto); empty without
+};
+template <>
+struct SqAut<true> {
+    SqAuto *state; // per leaf
 };
 
 __global__ __launch_bounds__(64) void k_squelch_set(const SqJob *__restrict__ jobs, int n, SqCfg *__restrict__ cfg, unsigned *__restrict__ hang_left)
@@ -72,11 +102,30 @@ __global__ __launch_bounds__(64) void k_squelch_set(const SqJob *__restrict__ jo
     hang_left[J.index] = 0;
 }
 
-// dir: SqHeader | unsigned offs[n] | unsigned hang[n] | PRE: unsigned pre[n]
-template <bool PRE = false>
+__global__ __launch_bounds__(64) void k_squelch_set_auto(const SqAutoJob *__restrict__ jobs, int n, SqAuto *__restrict__ state)
+{
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= n)
+        return;
+    const SqAutoJob J = jobs[j];
+    SqAuto a;
+    a.cur_min = a.prev_min = kSqNone;
+    a.age = 0;
+    a.ratio_q8 = J.ratio_q8;
+    a.window_frames = J.window_frames;
+    a.pad = 0;
+    state[J.index] = a;
+}
+
+// where thr_eff[n] | floor[n] begin in the directory (AUTO): behind hang[n] / pre[n], on 8 bytes
+__host__ __device__ inline size_t sq_aux_off(size_t n, bool pre) { return (sizeof(SqHeader) + (pre ? 12 : 8) * n + 7) / 8 * 8; }
+
+// dir: SqHeader | unsigned offs[n] | unsigned hang[n] | PRE: unsigned pre[n] | AUTO: u64 thr_eff[n] | u64 floor[n]
+template <bool PRE = false, bool AUTO = false>
 __global__ __launch_bounds__(kSqThreads) void k_squelch_scan(const SqLeaf *__restrict__ leaves, const SqCfg *__restrict__ cfg,
                                                              unsigned *__restrict__ hang_left, const unsigned char *__restrict__ pay,
-                                                             unsigned char *__restrict__ dir, int n, long long frame, SqPre<PRE> X)
+                                                             unsigned char *__restrict__ dir, int n, long long frame, SqPre<PRE> X,
+                                                             SqAut<AUTO> A)
 {
     __shared__ unsigned s_units[kSqThreads / 64], s_open[kSqThreads / 64];
     __shared__ unsigned s_pre[PRE ? kSqThreads / 64 : 1]; // (PRE = false never touches it and the compiler drops it: 128 bytes
@@ -92,6 +141,12 @@ __global__ __launch_bounds__(kSqThreads) void k_squelch_scan(const SqLeaf *__res
         if (i < n) {
             const SqLeaf L = leaves[i];
             const SqCfg C = cfg[i];
+            uint4 a0 = make_uint4(0, 0, 0, 0), a1 = a0; // AUTO: the leaf's record, asked for HERE, with the loads above
+            if constexpr (AUTO) {
+                const uint4 *ap = reinterpret_cast<const uint4 *>(A.state + i);
+                a0 = ap[0];
+                a1 = ap[1];
+            }
             unsigned long long s = 0;
             const uint4 *rec = reinterpret_cast<const uint4 *>(pay + L.meter_off);
             for (unsigned j = 0; j < L.meter_n; ++j) { // {sum_sq u64, clipped u32, peak u32}
@@ -99,8 +154,31 @@ __global__ __launch_bounds__(kSqThreads) void k_squelch_scan(const SqLeaf *__res
                 s += ((unsigned long long)r.y << 32) | r.x;
             }
             unsigned h = hang_left[i];
+            unsigned long long thr = C.thr;
+            if constexpr (AUTO) {
+                unsigned long long cur = ((unsigned long long)a0.y << 32) | a0.x, prev = ((unsigned long long)a0.w << 32) | a0.z;
+                unsigned age = a1.x;
+                const unsigned long long ratio = a1.y, floor = min(cur, prev);
+                if (ratio != 0 && floor != kSqNone) { // (floor * ratio) >> 8 in 128 bits, saturating
+                    const unsigned long long lo = floor * ratio, hi = __umul64hi(floor, ratio);
+                    thr = max(thr, (hi >> 8) ? kSqNone : ((hi << 56) | (lo >> 8)));
+                }
+                unsigned long long *aux = reinterpret_cast<unsigned long long *>(dir + sq_aux_off((size_t)n, PRE));
+                aux[i] = thr;
+                aux[n + i] = floor;
+                cur = min(cur, s);
+                age += 1;
+                if (age == a1.z) {
+                    prev = cur;
+                    cur = kSqNone;
+                    age = 0;
+                }
+                uint4 *ap = reinterpret_cast<uint4 *>(A.state + i);
+                ap[0] = make_uint4((unsigned)cur, (unsigned)(cur >> 32), (unsigned)prev, (unsigned)(prev >> 32));
+                reinterpret_cast<unsigned *>(ap + 1)[0] = age;
+            }
             is_open = 1;
-            if (s >= C.thr)
+            if (s >= thr)
                 h = C.hang_frames;
             else if (h > 0)
                 h -= 1;

@@ -53,7 +53,8 @@ class Receiver:
                  dc_blocked_scan: bool = False, pipeline: bool = False, fuse: bool = True, frame_pipeline: bool = True,
                  fuse_late: bool = True, keep_streams: bool = False, dc_speculative: bool = True,
                  dc_blocks_per_step: int | None = None, fuse_demod: bool = False,
-                 tail_in_levels: bool = True, meter: bool = False, squelch: bool = False, preroll: bool = False):
+                 tail_in_levels: bool = True, meter: bool = False, squelch: bool = False, preroll: bool = False,
+                 squelch_auto: bool = False):
         self.L = _lib.lib()
         h = C.c_void_p()
         rc = self.L.sdrx_create(C.byref(h), int(device))
@@ -80,6 +81,8 @@ class Receiver:
             self._chk(self.L.sdrx_set_option(self.h, b"squelch", 1))
         if preroll:
             self._chk(self.L.sdrx_set_option(self.h, b"preroll", 1))
+        if squelch_auto:
+            self._chk(self.L.sdrx_set_option(self.h, b"squelch_auto", 1))
         self._chk(self.L.sdrx_set_option(self.h, b"dc_speculative", int(bool(dc_speculative))))
         if dc_blocks_per_step is not None:
             self._chk(self.L.sdrx_set_option(self.h, b"dc_blocks_per_step", int(dc_blocks_per_step)))
@@ -261,6 +264,23 @@ class Receiver:
         self._chk(self.L.sdrx_get_preroll_count(self.h, C.byref(n), C.byref(b)))
         return {"n_preroll": n.value, "preroll_bytes": b.value}
 
+    # -- auto-squelch (option ``squelch_auto``): the threshold as a ratio over the leaf's tracked noise floor -----------
+    def set_squelch_auto(self, vids, ratio_q8, window_frames) -> None:
+        """Leaf vids[k]'s threshold becomes ``max(thr, floor * ratio_q8[k] / 256)``, the floor being the minimum ``sum_sq``
+        of the last ``window_frames[k]`` .. ``2 * window_frames[k] - 1`` frames (:func:`sdrreceiver_amd.squelch.decide_auto`);
+        ``ratio_q8`` 0 switches it off for the leaf.  Restarts the named leaves' floor."""
+        ids, ratio = _value_list(vids, ratio_q8, np.uint32)
+        _, win = _value_list(vids, window_frames, np.uint32)
+        self._chk(self.L.sdrx_set_squelch_auto(self.h, ids.ctypes.data, ratio.ctypes.data, win.ctypes.data, ids.size))
+
+    def squelch_auto(self, vids) -> dict:
+        """What decided the last delivered frame for the leaves `vids`: ``frame``, ``floor_sum_sq``, ``thr_eff_sum_sq``,
+        ``ratio_q8``, ``window_frames``, ``floor_valid`` as arrays in the order of `vids`."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        out = (_lib.SquelchAutoStateC * max(1, ids.size))()
+        self._chk(self.L.sdrx_get_squelch_auto(self.h, ids.ctypes.data, ids.size, out))
+        return _squelch.squelch_auto_dict(out[:ids.size])
+
     def output_rate(self, vid: int) -> int:
         rate = C.c_uint32()
         self._chk(self.L.sdrx_get_output(self.h, vid, None, None, C.byref(rate)))
@@ -391,6 +411,7 @@ class Group:
     the whole tree; `published` holds the last delivered frame's messages in the reference's order."""
 
     def __init__(self, devices, exact: bool = True, **options):
+        # (`options`: the library's option names as keywords -- meter=1, squelch=1, preroll=1, squelch_auto=1, ...)
         self.L = _lib.lib()
         h = C.c_void_p()
         arr = (C.c_int * len(devices))(*[int(d) for d in devices])
@@ -529,6 +550,19 @@ class Group:
         n, b = C.c_uint32(), C.c_uint64()
         self._chk(self.L.sdrx_group_get_preroll_count(self.h, C.byref(n), C.byref(b)))
         return {"n_preroll": n.value, "preroll_bytes": b.value}
+
+    def set_squelch_auto(self, vids, ratio_q8, window_frames) -> None:
+        """:meth:`Receiver.set_squelch_auto` with ids of the whole tree (group option ``squelch_auto=1``)."""
+        ids, ratio = _value_list(vids, ratio_q8, np.uint32)
+        _, win = _value_list(vids, window_frames, np.uint32)
+        self._chk(self.L.sdrx_group_set_squelch_auto(self.h, ids.ctypes.data, ratio.ctypes.data, win.ctypes.data, ids.size))
+
+    def squelch_auto(self, vids) -> dict:
+        """:meth:`Receiver.squelch_auto` with ids of the whole tree."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        out = (_lib.SquelchAutoStateC * max(1, ids.size))()
+        self._chk(self.L.sdrx_group_get_squelch_auto(self.h, ids.ctypes.data, ids.size, out))
+        return _squelch.squelch_auto_dict(out[:ids.size])
 
     def locate(self, vid: int) -> tuple[int, int]:
         m, l = C.c_int(), C.c_int()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/squelch_time.py -- what squelch-gated egress costs and saves per streamed frame.
 
-    python3 tools/squelch_time.py [--steps K] [--warmup W] [--reps R] [--skip-10k] [--parent-lib FILE] [--out FILE]
+    python3 tools/squelch_time.py [--steps K] [--warmup W] [--reps R] [--skip-10k] [--parent-lib FILE] [--out FILE] [--auto]
 
 BASELINE config 3 (1 024 subs) and the north-star tree of 10 240 subs in the streaming host's form submit(f+1); wait() (kernels
 plus the payload copy), publish callback off.  Receivers, timed in turn (R rounds, the median per-frame time reported with
@@ -15,6 +15,12 @@ static open set -- no leaf ever re-opens, so the difference to `open_10pct` is t
 and `rot_preroll_10pct` rotate the open set EVERY frame (set_squelch; submit; wait -- a set needs an empty queue, so these two
 rows have no frame of look-ahead and compare with each other only): with preroll every open leaf is then pre-rolled and the
 copy doubles.
+
+--auto (option squelch_auto) times only the pair that isolates the scan's AUTO form: `squelch_10pct`, squelch=1
+with the static 10 % open set, and `auto_10pct`, squelch_auto=1 with the same thresholds and ratio_q8 = 256, window 8 on EVERY
+leaf.  The frame is the same each time, so every floor equals the leaf's sum_sq and a ratio of 1.0 gives thr_eff = max(thr, s):
+the same leaves are open and the same bytes copied, while every lane does the whole floor arithmetic.  Run it under
+`rocprofv3 --kernel-trace --stats` for the per-launch time of the two k_squelch_scan instantiations side by side.
 """
 import argparse
 import json
@@ -27,7 +33,8 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 NEW = ("sdrx_set_squelch", "sdrx_get_squelch", "sdrx_get_egress", "sdrx_group_set_squelch", "sdrx_group_get_squelch", "sdrx_group_get_egress",
-       "sdrx_get_preroll", "sdrx_get_preroll_count", "sdrx_group_get_preroll", "sdrx_group_get_preroll_count")
+       "sdrx_get_preroll", "sdrx_get_preroll_count", "sdrx_group_get_preroll", "sdrx_group_get_preroll_count",
+       "sdrx_set_squelch_auto", "sdrx_get_squelch_auto", "sdrx_group_set_squelch_auto", "sdrx_group_get_squelch_auto")
 FRACTIONS = (1.0, 0.5, 0.1, 0.01)
 
 
@@ -70,6 +77,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--skip-10k", action="store_true")
     ap.add_argument("--parent-lib", default="")
+    ap.add_argument("--auto", action="store_true", help="only squelch=1 against squelch_auto=1 at the same 10 %% open set")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)  # tree name: time the loaded library once, plain options
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -97,6 +105,29 @@ def main():
         topo = trees[name]()
         lv = topo.leaves_in_publish_order()
         host = synth.lcg_frame(topo.frame, synth.Lcg(1))
+        if a.auto:
+            is_open = np.zeros(len(lv), bool)
+            is_open[np.unique(np.linspace(0, len(lv) - 1, max(1, round(0.1 * len(lv)))).round().astype(int))] = True
+            thr = [0 if x else 1 << 63 for x in is_open]
+            pair = {"squelch_10pct": Receiver.from_topology(topo, device=0, squelch=True),
+                    "auto_10pct": Receiver.from_topology(topo, device=0, squelch_auto=True)}
+            for rx in pair.values():
+                rx.set_publish(False)
+                rx.set_squelch(lv, thr, [0] * len(lv))
+            pair["auto_10pct"].set_squelch_auto(lv, [256] * len(lv), [8] * len(lv))
+            times = {k: [] for k in pair}
+            for r in range(a.reps):
+                for k, rx in pair.items():
+                    times[k].append(timed(rx, host, a.steps, a.warmup))
+            for k, rx in pair.items():
+                eg = rx.egress()
+                result[f"{name}_{k}"] = dict(summary(times[k]), n_open=eg["n_open"], payload_bytes_copied=eg["payload_bytes_copied"],
+                                             device_bytes=rx.stats()["device_bytes"])
+            au = pair["auto_10pct"].squelch_auto(lv)
+            result[f"{name}_auto_10pct"].update(floor_valid=int(au["floor_valid"].sum()), lifted=int((au["thr_eff_sum_sq"] > 0).sum()))
+            for rx in pair.values():
+                rx.close()
+            continue
         rxs = {"meter1_squelch0": Receiver.from_topology(topo, device=0, meter=True)}
         for frac in FRACTIONS:
             rx = Receiver.from_topology(topo, device=0, squelch=True)
