@@ -202,6 +202,26 @@ public:
         else
             check(sdrx_set_squelch_auto(ctx_, ids.data(), ratio_q8.data(), window_frames.data(), (int)ids.size()), "sdrx_set_squelch_auto");
     }
+    // Parking (library option "park" = 1): leaf ids[k] is parked (active[k] 0: no arithmetic, delivered like a closed leaf) or
+    // unparked (1: a new vfo from the next frame on -- fresh oscillator, zero filter state); between two frames.
+    void set_active(const std::vector<int> &ids, const std::vector<int32_t> &active)
+    {
+        if (ids.size() != active.size())
+            throw std::invalid_argument("set_active: lists of different length");
+        if (grp_)
+            check(sdrx_group_set_active(grp_, ids.data(), active.data(), (int)ids.size()), "sdrx_group_set_active");
+        else
+            check(sdrx_set_active(ctx_, ids.data(), active.data(), (int)ids.size()), "sdrx_set_active");
+    }
+    std::vector<sdrx_active_state> active(const std::vector<int> &ids)
+    {
+        std::vector<sdrx_active_state> out(ids.size());
+        if (grp_)
+            check(sdrx_group_get_active(grp_, ids.data(), (int)ids.size(), out.data()), "sdrx_group_get_active");
+        else
+            check(sdrx_get_active(ctx_, ids.data(), (int)ids.size(), out.data()), "sdrx_get_active");
+        return out;
+    }
 
 private:
     bool started() const { return ctx_ || grp_; }

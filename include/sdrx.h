@@ -160,6 +160,10 @@ int sdrx_add_vfo(sdrx_ctx *ctx, const sdrx_vfo_desc *desc, int *id_out);
  *            implies "squelch".  0 changes nothing.  With 1 and every ratio_q8 0 (the start) the gate is that of "squelch" = 1.
  *            Composes with "preroll", "fuse_demod", "tail_in_levels" and "pipeline" as "squelch" does: the gate keeps its
  *            place in the launch sequence.
+ *   "park" 0 (default) | 1: leaves can be switched off and on between frames (sdrx_set_active below).  0 changes nothing:
+ *            the same kernels, launches, device_bytes and payloads, and sdrx_set_active returns SDRX_ESTATE.  With 1 and
+ *            nothing parked every payload, stream, meter, squelch decision and callback is bit for bit what it is with 0; the
+ *            kernels are then the forms that read one flag word per work item first.
  *   "dc_blocked_scan" 0|1 (default 0): how sdrx_process_u8 removes the DC bias.  0 = the
  *                 reference's sequentially rounded fp32 recurrence, bit for bit (below).  1 = the same linear filter as a
  *                 blocked parallel scan (~15 us): the true IIR response.  The reference's recurrence
@@ -363,6 +367,45 @@ typedef struct sdrx_squelch_auto_state {
 } sdrx_squelch_auto_state;
 int sdrx_set_squelch_auto(sdrx_ctx *ctx, const int *ids, const uint32_t *ratio_q8, const uint32_t *window_frames, int n);
 int sdrx_get_squelch_auto(sdrx_ctx *ctx, const int *ids, int n, sdrx_squelch_auto_state *out);
+
+/* Parking (option "park" = 1): a leaf VFO switched off costs no arithmetic on the device, and a leaf switched on again starts
+ * as a NEW vfo does -- together with sdrx_set_mixer_freqs the reference's `new vfo` + setters + vfo::init + setVFOs between two
+ * sdrj::demodData calls: finalize with spare leaves, park them, and retune and unpark one when a channel is assigned.
+ * Only leaves can be parked.  A VFO with children keeps running even when all its children are parked.
+ *
+ * A leaf that is PARKED in a frame does no mix, decimation, demodulation, compress, long low-pass or spectrum work in it, and
+ * is delivered as a leaf that option "squelch" closed: no publish callback; sdrx_get_output gives SDRX_OK, *len_bytes = 0,
+ * *rate as always and a non-NULL *buf that is not to be read; sdrx_get_preroll gives *len_bytes = 0; the other leaves'
+ * callbacks keep their order.  sdrx_get_stream and sdrx_get_prequant return SDRX_ENOSTREAM; an enabled spectrum's `updates`
+ * does not move (its display state is kept); a tap selection is kept and writes nothing; sdrx_get_meters gives the delivered
+ * `frame` and n_values = sum_sq = clipped = 0, peak = 0.  Under "squelch" / "preroll" / "squelch_auto" the gate gives open = 0
+ * and no pre-roll whatever the threshold is (threshold 0 = "always open" holds for active leaves only) and leaves hang_left,
+ * prev_open and the floor state untouched -- a parked frame is not an observation; sdrx_get_squelch and sdrx_get_squelch_auto
+ * report that frozen state with open = 0; sdrx_get_egress: n_leaves unchanged, n_open counts open active leaves, a parked leaf
+ * adds no packed bytes.  Without "squelch" the payload region is still copied whole and n_open is the number of active leaves.
+ * sdrx_set_mixer_freqs, sdrx_set_gains, sdrx_set_squelch and sdrx_set_squelch_auto accept a parked leaf and store the values.
+ *
+ * A leaf UNPARKED before frame K is, from K on, a new vfo with the leaf's descriptor as it stands (the mixer frequency and gain
+ * last set): its oscillator starts fresh (sample 0 of frame K takes the table's last entry, as after sdrx_set_mixer_freqs), every
+ * filter state is zero (half-band histories, late decimation, delay and Hilbert, audio low-pass), and its gate state is that of
+ * sdrx_finalize (hang_left = 0, prev_open = 1: no pre-roll of a stale payload; no floor observation) -- thresholds, hang time,
+ * ratio and window are kept, and so is the display state of an enabled spectrum.  Park followed by unpark with no frame
+ * between is allowed: it restarts the leaf.
+ *
+ * sdrx_set_active: batched and atomic, with the calling rules of sdrx_set_gains / sdrx_set_squelch -- the whole list is checked
+ * first: a bad or duplicate id, the id of a VFO with children, active[k] not 0 or 1 or n < 0 is SDRX_EINVAL with nothing
+ * changed; n == 0 does nothing; SDRX_ESTATE before sdrx_finalize, with the option off, and while submitted frames are
+ * undelivered.  Frames the software pipeline of sdrx_process_device still holds run to their end with the old values first.
+ * An entry that names the state the leaf is already in is ignored (no reset).  One upload and two small launches; the call
+ * returns when the device has applied it.  (A changed leaf with an enabled spectrum costs one more small upload.)
+ * sdrx_get_active: host bookkeeping, good from sdrx_finalize on and with the option off (every leaf active since frame 0). */
+typedef struct sdrx_active_state {
+    int64_t since_frame;  /* first frame index in the present state (0 after sdrx_finalize) */
+    int32_t active;       /* 1 after sdrx_finalize */
+    uint32_t reserved;
+} sdrx_active_state;
+int sdrx_set_active(sdrx_ctx *ctx, const int *ids, const int32_t *active, int n);
+int sdrx_get_active(sdrx_ctx *ctx, const int *ids, int n, sdrx_active_state *out);
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);
@@ -507,6 +550,10 @@ int sdrx_group_get_egress(sdrx_group *grp, int64_t *frame, uint32_t *n_open, uin
  * to the member that owns the leaf. */
 int sdrx_group_set_squelch_auto(sdrx_group *grp, const int *ids, const uint32_t *ratio_q8, const uint32_t *window_frames, int n);
 int sdrx_group_get_squelch_auto(sdrx_group *grp, const int *ids, int n, sdrx_squelch_auto_state *out);
+/* sdrx_set_active / sdrx_get_active with ids of the whole tree (group option "park" = 1), each id routed to the member that
+ * owns the leaf; `since_frame` counts the group's frames. */
+int sdrx_group_set_active(sdrx_group *grp, const int *ids, const int32_t *active, int n);
+int sdrx_group_get_active(sdrx_group *grp, const int *ids, int n, sdrx_active_state *out);
 
 /* sdrx_get_preroll routed to the member that owns the leaf; sdrx_get_preroll_count summed over the members (group option
  * "preroll" = 1). */

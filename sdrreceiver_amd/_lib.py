@@ -68,6 +68,11 @@ class SquelchAutoStateC(C.Structure):
                 ("window_frames", C.c_uint32), ("floor_valid", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ActiveStateC(C.Structure):
+    """struct sdrx_active_state"""
+    _fields_ = [("since_frame", C.c_int64), ("active", C.c_int32), ("reserved", C.c_uint32)]
+
+
 PUBLISH_FN =C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
 
 # every symbol include/sdrx.h declares: (restype, argtypes)
@@ -119,6 +124,10 @@ SYMBOLS = {
     "sdrx_get_squelch_auto": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_group_set_squelch_auto": (_i, [_vp, _vp, _vp, _vp, _i]),
     "sdrx_group_get_squelch_auto": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_set_active": (_i, [_vp, _vp, _vp, _i]),
+    "sdrx_get_active": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_group_set_active": (_i, [_vp, _vp, _vp, _i]),
+    "sdrx_group_get_active": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

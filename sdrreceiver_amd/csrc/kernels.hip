@@ -301,6 +301,15 @@ __global__ void k_vfo_retune(const RetuneJob *__restrict__ jobs, int n)
     v->origin = J.origin;
 }
 
+// sdrx_set_active between two frames: one workgroup per job (FillJob, sdrx_dev.h).  The host drained the context first: no
+// launch reads these words while this one runs.
+__global__ __launch_bounds__(256) void k_vfo_reset(const FillJob *__restrict__ jobs)
+{
+    const FillJob J = jobs[blockIdx.x];
+    for (unsigned i = threadIdx.x; i < J.words; i += 256)
+        J.ptr[i] = J.value;
+}
+
 // Debug/parity helper: regenerate table[first .. first+count) from the checkpoints.
 __global__ void k_nco_dump(const float2 *__restrict__ cp, float rc, float rs, long first, long count,
                            float2 *__restrict__ out)
@@ -2075,11 +2084,15 @@ __device__ __forceinline__ void run_item(const K1Vfo *__restrict__ vfos, const K
 // One wave per workgroup, one workgroup per K1Work.  LEVEL only gives the root launch and the sub
 // launches distinct kernel names in profiles.
 // METER: option "meter" (the fused-demodulation items write output meters).
-template <bool EXACT, int LEVEL, bool ROT = !EXACT, bool METER = false>
+// PARK: option "park" (the items of a parked leaf return at once; ParkArg, sdrx_dev.h).
+template <bool EXACT, int LEVEL, bool ROT = !EXACT, bool METER = false, bool PARK = false>
 __global__ __launch_bounds__(64, kK1MinWaves) void k_mix_decimate(const K1Vfo *__restrict__ vfos, const K1Work *__restrict__ work,
-                                                     unsigned long long frame_no, const void *__restrict__ raw, int raw_mode)
+                                                     unsigned long long frame_no, const void *__restrict__ raw, int raw_mode, ParkArg<PARK> P)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if constexpr (PARK)
+        if (ldc(P.act + ldc(&work[blockIdx.x].vfo)) == 0)
+            return;
     run_item<EXACT, ROT, METER>(vfos, work[blockIdx.x], frame_no, raw, raw_mode, LEVEL == 0, smem, (int)threadIdx.x);
 }
 
@@ -2088,13 +2101,16 @@ __global__ __launch_bounds__(64, kK1MinWaves) void k_mix_decimate(const K1Vfo *_
 // dsp.cpp:59-71,150-154): z'[k] = sum_i hd[i] * x[L k - Nd + i]  -- the newest sample x[L k] is
 // NOT part of the sum ((N+1)-slot ring).  The phase counter restarts every frame and frames are
 // multiples of L, so k is frame-local.  256 outputs per block; the input window sits in LDS.
-template <bool EXACT>
+template <bool EXACT, bool PARK = false>
 __global__ __launch_bounds__(256) void k_late_decimate(const K2aVfo *__restrict__ vfos, const BlockWork *__restrict__ work,
-                                                       unsigned long long frame_no)
+                                                       unsigned long long frame_no, ParkArg<PARK> P)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float2 *sx = reinterpret_cast<float2 *>(smem);
     const BlockWork bw = work[blockIdx.x];
+    if constexpr (PARK)
+        if (ldc(P.act + bw.vfo) == 0)
+            return;
     const K2aVfo *Dp = vfos + bw.vfo;
     const int blk = bw.blk;
     const int par = (int)(frame_no & 1ull);
@@ -2241,15 +2257,18 @@ __device__ __forceinline__ void late4_body(const float2 *__restrict__ x, float2 
 }
 
 constexpr int kLate4Waves = 6; // 76 VGPRs; measured 34.0 us vs 35.4 (5 waves) and 35.5 (8 waves) on config 4
-template <bool EXACT>
+template <bool EXACT, bool PARK = false>
 __global__ __launch_bounds__(64, kLate4Waves) void k_late_decimate4(const K2aVfo *__restrict__ vfos, const BlockWork *__restrict__ work,
-                                                       unsigned long long frame_no)
+                                                       unsigned long long frame_no, ParkArg<PARK> P)
 {
     constexpr int R = kLate4R;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *sh = reinterpret_cast<float *>(smem);
     v2f *sx = reinterpret_cast<v2f *>(smem + 4 * R * kLateTapRow);
     const BlockWork bw = work[blockIdx.x];
+    if constexpr (PARK)
+        if (ldc(P.act + bw.vfo) == 0)
+            return;
     const K2aVfo *Dp = vfos + bw.vfo;
     const int par = (int)(frame_no & 1ull);
     const int lane = threadIdx.x;
@@ -2565,11 +2584,14 @@ __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, cons
 
 // (no occupancy demand: __launch_bounds__(256, 8) -- at most 64 VGPRs, eight 256-thread blocks per CU -- measured 92 us
 // against 47 us; profiles/README.md)
-template <bool EXACT, bool METER = false>
+template <bool EXACT, bool METER = false, bool PARK = false>
 __global__ __launch_bounds__(256, 1) void k_usb_demod(const K2Vfo *__restrict__ vfos, const BlockWork *__restrict__ work,
-                                                   unsigned long long frame_no)
+                                                   unsigned long long frame_no, ParkArg<PARK> P)
 {
     __shared__ __attribute__((aligned(16))) DemodLds S;
+    if constexpr (PARK)
+        if (ldc(P.act + ldc(&work[blockIdx.x].vfo)) == 0)
+            return;
     demod_block<EXACT, METER>(vfos, work[blockIdx.x], frame_no, S, (int)threadIdx.x);
 }
 
@@ -2589,15 +2611,19 @@ struct LevelArgs {
     int raw_mode;                               // ... and its form (kRaw*)
     int pad_;
 };
-template <bool EXACT, bool ROT = !EXACT, bool METER = false>
+template <bool EXACT, bool ROT = !EXACT, bool METER = false, bool PARK = false>
 __global__ __launch_bounds__(64, kK1MinWaves) void k_mix_levels(const K1Vfo *__restrict__ k1, const K1Work *__restrict__ items,
-                                                   const int *__restrict__ item_level, const int *__restrict__ list, LevelArgs A)
+                                                   const int *__restrict__ item_level, const int *__restrict__ list, LevelArgs A,
+                                                   ParkArg<PARK> P)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int it = ldc(list + blockIdx.x);
     if (it < 0)
         return;
     const int lv = ldc(item_level + it);
+    if constexpr (PARK) // (the item's own level word carries the flag: kParkBit, sdrx_dev.h)
+        if (lv & kParkBit)
+            return;
     run_item<EXACT, ROT, METER>(k1, K1Work{ldc(&items[it].vfo), ldc(&items[it].s_begin), ldc(&items[it].s_first_out), ldc(&items[it].s_end)},
                     A.frame_level[lv], A.raw, A.raw_mode, lv == 0, smem, (int)threadIdx.x);
 }
@@ -2622,17 +2648,20 @@ struct LevelTailArgs {
     int active;                    // bit l: tree level l has a frame in this launch; bit kMaxLevels: the demodulation has one
     int lds_wave;                  // LDS bytes of one mix wave
 };
-template <bool EXACT, bool ROT = !EXACT, bool METER = false>
+template <bool EXACT, bool ROT = !EXACT, bool METER = false, bool PARK = false>
 __global__ __launch_bounds__(256, kK1MinWaves) void k_levels_tail(const K1Vfo *__restrict__ k1, const K1Work *__restrict__ items,
                                                                   const int *__restrict__ item_level, const TailWg *__restrict__ wgs,
                                                                   const K2Vfo *__restrict__ k2, const BlockWork *__restrict__ dwork,
-                                                                  LevelTailArgs A)
+                                                                  LevelTailArgs A, ParkArg<PARK> P)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int first = ldc(&wgs[blockIdx.x].item[0]);
     if (first <= -2) {
         if (A.active & (1 << kMaxLevels)) {
             const int b = -2 - first;
+            if constexpr (PARK)
+                if (ldc(P.act + ldc(&dwork[b].vfo)) == 0)
+                    return;
             demod_block<EXACT, METER>(k2, BlockWork{ldc(&dwork[b].vfo), ldc(&dwork[b].blk)}, A.frame_tail, *reinterpret_cast<DemodLds *>(smem),
                                       (int)threadIdx.x);
         }
@@ -2643,6 +2672,9 @@ __global__ __launch_bounds__(256, kK1MinWaves) void k_levels_tail(const K1Vfo *_
     if (it < 0)
         return;
     const int lv = ldc(item_level + it);
+    if constexpr (PARK)
+        if (lv & kParkBit)
+            return;
     if (!((A.active >> lv) & 1)) // (a level without a frame: only while the pipeline drains)
         return;
     // (METER && EXACT: the fused-demodulation items' meters would cost this kernel a spill -- 4 VGPRs of accumulators beside
@@ -2656,12 +2688,15 @@ __global__ __launch_bounds__(256, kK1MinWaves) void k_levels_tail(const K1Vfo *_
 // excluded (FIR::FIRUpdateAndProcess, dsp.cpp:59-71), one accumulator per output in tap order, then the
 // same quantisation as k_usb_demod.  256 outputs per block; the block's window of N + 256 usb values sits
 // in LDS, the taps are wave-uniform scalar loads.  A rare configuration: correctness first.
-template <bool EXACT, bool METER = false>
+template <bool EXACT, bool METER = false, bool PARK = false>
 __global__ __launch_bounds__(256) void k_lpf_long(const K4Vfo *__restrict__ vfos, const BlockWork *__restrict__ work, unsigned long long frame_no,
-                                                  const int *__restrict__ mrel)
+                                                  const int *__restrict__ mrel, ParkArg<PARK> P)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *sw = reinterpret_cast<float *>(smem);
+    if constexpr (PARK)
+        if (ldc(P.act + ldc(&work[blockIdx.x].vfo)) == 0)
+            return;
     const K4Vfo *Dp = vfos + ldc(&work[blockIdx.x].vfo);
     const int blk = ldc(&work[blockIdx.x].blk);
     const int par = (int)(frame_no & 1ull);
@@ -2726,11 +2761,14 @@ __device__ __forceinline__ void meter_iq(MeterAcc &m, float pre_re, float pre_im
     m.clipped += !(pre_re > -129.0f && pre_re < 128.0f && pre_im > -129.0f && pre_im < 128.0f);
     m.peak = max(m.peak, max(__float_as_uint(fabsf(pre_re)), __float_as_uint(fabsf(pre_im))));
 }
-template <bool METER = false>
+template <bool METER = false, bool PARK = false>
 __global__ __launch_bounds__(256) void k_compress(const K3Vfo *__restrict__ vfos, const BlockWork *__restrict__ work,
-                                                  unsigned long long frame_no)
+                                                  unsigned long long frame_no, ParkArg<PARK> P)
 {
     const BlockWork bw = work[blockIdx.x];
+    if constexpr (PARK)
+        if (ldc(P.act + bw.vfo) == 0)
+            return;
     const K3Vfo *Dp = vfos + bw.vfo;
     const int blk = bw.blk;
     const int par = (int)(frame_no & 1ull);

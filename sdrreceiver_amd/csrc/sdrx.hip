@@ -102,6 +102,9 @@ void free_device_state(sdrx_ctx *c)
     dfree(c->sq.d_auto);
     dfree(c->sq.d_jobs);
     c->sq.jobs_cap = 0;
+    dfree(c->park.d_act);
+    dfree(c->park.d_jobs);
+    c->park.jobs_cap = 0;
     c->sq.bytes = c->sq.dir_off = c->sq.pack_bytes = c->sq.hpack_off = 0;
 }
 
@@ -231,6 +234,8 @@ int sdrx_set_option(sdrx_ctx *c, const char *name, int value)
         c->opt_preroll = value != 0;
     else if (!strcmp(name, "squelch_auto"))
         c->opt_squelch_auto = value != 0;
+    else if (!strcmp(name, "park"))
+        c->opt_park = value != 0;
     else
         return fail(c, SDRX_EINVAL, "unknown option '%s'", name);
     return SDRX_OK;
@@ -360,6 +365,8 @@ int spectrum_rebuild(sdrx_ctx *c)
             const Node &n = c->nodes[(size_t)id];
             const auto tap = c->taps.find(id);
             if (n.level != lv || !c->spec.slots[(size_t)id].on || (!n.has_stream && tap == c->taps.end()))
+                continue;
+            if (c->park.parked_at(id, c->frame_no)) // a parked leaf writes no stream: no update (its display state stays)
                 continue;
             SpecDesc e;
             memset(&e, 0, sizeof e);
@@ -592,6 +599,170 @@ int sdrx_set_gains(sdrx_ctx *c, const int *ids, const float *gains, int n)
     return set_vfo_values(c, ids, nullptr, gains, n, "sdrx_set_gains");
 }
 
+} // extern "C"
+
+namespace {
+
+// sdrx_set_active on a checked list: the entries that change a leaf's state become fill jobs (FillJob: its flag words; for a
+// leaf that is unparked also zeros over every filter-state region of both frame parities and the gate state of sdrx_finalize)
+// and, for an unparked leaf, one retune job with the rotation it has (a fresh Oscillator from the next frame on).  The
+// software pipeline is drained first; one upload, k_vfo_reset and k_vfo_retune, one synchronisation.
+int apply_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c))
+        return rc;
+    sdrx_ctx::Park &K = c->park;
+    std::vector<FillJob> fills;
+    std::vector<RetuneJob> tunes;
+    auto fill = [&](void *ptr, size_t words, unsigned value) {
+        if (words)
+            fills.push_back(FillJob{static_cast<unsigned *>(ptr), (unsigned)words, value});
+    };
+    K1Vfo *k1 = reinterpret_cast<K1Vfo *>(c->arena + c->off_k1vfo);
+    bool any_spectrum = false;
+    for (int k = 0; k < n; ++k) {
+        const int id = ids[k];
+        const Node &nd = c->nodes[(size_t)id];
+        if (K.leaf[(size_t)id].active == active[k]) // already there: no reset
+            continue;
+        const unsigned v = (unsigned)active[k];
+        fill(K.d_act + id, 1, v);
+        for (int it : K.items[(size_t)id]) // (k_mix_levels / k_levels_tail: the flag rides in the item's level word)
+            fill(reinterpret_cast<int *>(c->arena + c->fp.off_item_level) + it, 1, (unsigned)nd.level | (v ? 0u : (unsigned)kParkBit));
+        if (nd.d2a_index >= 0)
+            fill(K.d_act + K.o_2a + nd.d2a_index, 1, v);
+        if (nd.d2_index >= 0)
+            fill(K.d_act + K.o_2 + nd.d2_index, 1, v);
+        if (nd.d3_index >= 0)
+            fill(K.d_act + K.o_3 + nd.d3_index, 1, v);
+        if (nd.d4_index >= 0)
+            fill(K.d_act + K.o_4 + nd.d4_index, 1, v);
+        const int sq = c->opt_squelch ? c->sq.index[(size_t)id] : -1; // (without the gate nothing reads its words)
+        if (sq >= 0)
+            fill(K.d_act + K.o_sq + sq, 1, v);
+        any_spectrum |= !c->spec.slots.empty() && c->spec.slots[(size_t)id].on;
+        if (!active[k])
+            continue;
+        // the leaf starts as vfo::init leaves a new vfo: every history zero, in both parities (whichever the next frame reads)
+        const bool late = nd.d.demod_usb && nd.d.late_decimate > 0;
+        const size_t hist = nd.fused_late == 5 ? (size_t)late_hist<5>() : nd.fused_late == 6 ? (size_t)late_hist<6>() : (size_t)std::max(1, nd.d.decimate_count * kHbHist);
+        for (int p = 0; p < 2; ++p) {
+            fill(c->arena + nd.off_hb[p], 2 * hist, 0);
+            if (nd.fused_demod)
+                fill(c->arena + nd.off_dstate[p], 256, 0);
+            if (nd.has_stream)
+                fill(c->arena + nd.off_stream[p], 2 * (size_t)nd.Hx, 0);
+            if (late)
+                fill(c->arena + nd.off_z[p], 2 * (size_t)nd.H, 0);
+            if (nd.long_lpf)
+                fill(c->arena + nd.off_u[p], (size_t)nd.Hu, 0);
+        }
+        if (sq >= 0) { // the gate state of sdrx_finalize; thresholds, hang time, ratio and window stay
+            fill(c->sq.d_hang + sq, 1, 0);
+            if (c->opt_preroll)
+                fill(c->sq.d_prev + sq, 1, 1);
+            if (c->opt_squelch_auto) {
+                fill(c->sq.d_auto + sq, 4, 0xffffffffu); // cur_min = prev_min = NONE
+                fill(reinterpret_cast<unsigned *>(c->sq.d_auto + sq) + 4, 1, 0); // age
+            }
+        }
+        RetuneJob J;
+        memset(&J, 0, sizeof J);
+        J.kind = kJobRetune;
+        J.vfo = k1 + id;
+        J.rot_re = nd.rot_re;
+        J.rot_im = nd.rot_im;
+        nco_powers(J.rot_re, J.rot_im, J.rk);
+        J.origin = c->frame_no;
+        tunes.push_back(J);
+    }
+    if (!fills.empty()) {
+        const size_t fb = sizeof(FillJob) * fills.size(), bytes = fb + sizeof(RetuneJob) * tunes.size();
+        if (bytes > K.jobs_cap) {
+            if (K.d_jobs)
+                (void)hipFree(K.d_jobs);
+            K.d_jobs = nullptr;
+            K.jobs_cap = 0;
+            HIPCHK(c, hipMalloc(&K.d_jobs, bytes));
+            K.jobs_cap = bytes;
+        }
+        std::vector<unsigned char> host(bytes);
+        memcpy(host.data(), fills.data(), fb);
+        if (!tunes.empty())
+            memcpy(host.data() + fb, tunes.data(), bytes - fb);
+        HIPCHK(c, hipMemcpyAsync(K.d_jobs, host.data(), bytes, hipMemcpyHostToDevice, c->st.stream));
+        hipLaunchKernelGGL(k_vfo_reset, dim3((unsigned)fills.size()), dim3(256), 0, c->st.stream, reinterpret_cast<const FillJob *>(K.d_jobs));
+        if (!tunes.empty()) {
+            const int nj = (int)tunes.size();
+            hipLaunchKernelGGL(k_vfo_retune, dim3((nj + 63) / 64), dim3(64), 0, c->st.stream, reinterpret_cast<const RetuneJob *>(K.d_jobs + fb), nj);
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->st.stream)); // (`host` lives on this stack)
+    }
+    for (int k = 0; k < n; ++k) {
+        sdrx_ctx::Park::Leaf &L = K.leaf[(size_t)ids[k]];
+        if (L.active == active[k])
+            continue;
+        if (L.since != c->frame_no) // (a second change before the same frame: the frames before it ran in the state they ran in)
+            L.was_active = L.active;
+        L.active = active[k];
+        L.since = c->frame_no;
+        if (active[k] && c->opt_squelch)
+            c->sq.hang[(size_t)c->sq.index[(size_t)ids[k]]] = 0;
+    }
+    return any_spectrum ? spectrum_rebuild(c) : SDRX_OK; // (an enabled spectrum of a parked leaf leaves the launch list)
+}
+
+} // namespace
+
+extern "C" {
+
+int sdrx_set_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_set_active before sdrx_finalize");
+    if (!c->opt_park)
+        return fail(c, SDRX_ESTATE, "sdrx_set_active: option \"park\" is off");
+    if (n < 0 || (n > 0 && (!ids || !active)))
+        return fail(c, SDRX_EINVAL, "sdrx_set_active: n = %d, ids %p, active %p", n, (const void *)ids, (const void *)active);
+    if (int rc = check_leaf_ids(c, "sdrx_set_active", ids, n, true))
+        return rc;
+    for (int k = 0; k < n; ++k)
+        if (active[k] != 0 && active[k] != 1)
+            return fail(c, SDRX_EINVAL, "sdrx_set_active: vfo %d: active = %d (0 or 1)", ids[k], active[k]);
+    if (c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "sdrx_set_active: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+    if (n == 0)
+        return SDRX_OK;
+    return apply_active(c, ids, active, n);
+}
+
+int sdrx_get_active(sdrx_ctx *c, const int *ids, int n, sdrx_active_state *out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_active before sdrx_finalize");
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return fail(c, SDRX_EINVAL, "sdrx_get_active: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
+    if (int rc = check_leaf_ids(c, "sdrx_get_active", ids, n, false))
+        return rc;
+    for (int k = 0; k < n; ++k) {
+        sdrx_active_state s;
+        memset(&s, 0, sizeof s);
+        s.active = 1;
+        if (!c->park.leaf.empty()) {
+            s.active = c->park.leaf[(size_t)ids[k]].active;
+            s.since_frame = (int64_t)c->park.leaf[(size_t)ids[k]].since;
+        }
+        out[k] = s;
+    }
+    return SDRX_OK;
+}
+
 int sdrx_set_stream(sdrx_ctx *c, void *s)
 {
     if (!c)
@@ -659,6 +830,8 @@ int sdrx_get_stream(sdrx_ctx *c, int id, float *out, int max_complex, int *n_ret
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = drain(c))
         return rc;
+    if (c->park.parked_at(id, c->frame_no - 1))
+        return fail(c, SDRX_ENOSTREAM, "sdrx_get_stream: vfo %d was parked in frame %llu (sdrx_set_active)", id, c->frame_no - 1);
     const auto tap = c->taps.find(id);
     if (!n.has_stream && !(tap != c->taps.end() && c->frame_no > tap->second.since))
         return fail(c, SDRX_ENOSTREAM,
@@ -824,6 +997,8 @@ int sdrx_get_prequant(sdrx_ctx *c, int id, float *out, int max, int *n_ret)
         return fail(c, SDRX_ESTATE, "sdrx_get_prequant: set option keep_prequant=1 before finalize; USB leaves only");
     if (c->in_flight > 0)
         return fail(c, SDRX_ESTATE, "sdrx_get_prequant: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+    if (c->frame_no > 0 && c->park.parked_at(id, c->frame_no - 1))
+        return fail(c, SDRX_ENOSTREAM, "sdrx_get_prequant: vfo %d was parked in frame %llu (sdrx_set_active)", id, c->frame_no - 1);
     const int cnt = std::min(max, n.n_out);
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = drain(c))
@@ -893,7 +1068,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->exact = c->opt_exact;
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq.bytes);
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq.bytes + sizeof(int) * c->park.words);
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

@@ -40,6 +40,7 @@ struct Node {
     size_t off_dstate[2] = {0, 0}; //   ... its demodulation history per frame parity (kDemodStateFloats floats)
     int d2_index = -1;      // its K2Vfo in the demodulation descriptor array
     int d4_index = -1;      // its K4Vfo (long_lpf): k_lpf_long applies the gain
+    int d2a_index = -1, d3_index = -1; // its K2aVfo (late decimation in a kernel of its own) / K3Vfo (compress): option park's flag words
     bool has_stream = true; // decimate[d] of every frame is kept in HBM (false: a fused late decimation writes only z', a fused demodulation only the payload)
     int meter_first = 0, meter_n = 0; // option meter: this leaf's records, slots [meter_first, meter_first + meter_n) behind the payloads
     int meter_shift = 0;              //   ... fuse_demod: the record of a mix item is s_first_out >> meter_shift
@@ -103,7 +104,7 @@ struct sdrx_ctx {
     int opt_exact = 1, opt_prequant = 0, opt_segments = 0, opt_dc_blocked = 0, opt_pipeline = 0, opt_dc_speculative = 1;
     int opt_fuse = 1, opt_frame_pipeline = 1, opt_fuse_late = 1, opt_keep_streams = 0, opt_fuse_demod = 0;
     int opt_tail_in_levels = 1;
-    int opt_meter = 0, opt_squelch = 0, opt_preroll = 0, opt_squelch_auto = 0;
+    int opt_meter = 0, opt_squelch = 0, opt_preroll = 0, opt_squelch_auto = 0, opt_park = 0;
     // option meter: per frame parity, behind the payloads in d_pay / h_pay (at meter_off), one 16-byte MeterAcc record per work
     // unit that emits payload values (kernels.hip "output meters"); the records travel in the payload copy
     size_t meter_off = 0;
@@ -146,6 +147,30 @@ struct sdrx_ctx {
         std::vector<unsigned long long> thr_eff, floor; // ... the delivered directory's values (floor: kSqNone = no observation)
         hipEvent_t ev_dir[2] = {nullptr, nullptr}; // the fixed-size part of frame f is in h_pay[f & 1]
     } sq;
+
+    // Option park (sdrx_set_active): one flag word per descriptor of every kernel that works on a leaf, in one
+    // device array -- [K1Vfo: per node | K2aVfo | K2Vfo | K3Vfo | K4Vfo | the gate: per leaf in publish order] -- 1 = active.
+    // The host's copy of a leaf's state is what the getters and the delivery serve: a frame f >= since ran in state `active`,
+    // the frames before it (the last one may not be fetched yet) in state `was_active`.
+    struct Park {
+        int *d_act = nullptr;
+        size_t o_2a = 0, o_2 = 0, o_3 = 0, o_4 = 0, o_sq = 0, words = 0;
+        struct Leaf {
+            int active = 1, was_active = 1;
+            unsigned long long since = 0;
+        };
+        std::vector<Leaf> leaf; // per node (leaves only are ever changed)
+        std::vector<std::vector<int>> items; // per node: its entries of LevelPlan's item_level[] (bit kParkBit; with a level plan)
+        unsigned char *d_jobs = nullptr; // job lists of sdrx_set_active: FillJob[] | RetuneJob[], grown on demand
+        size_t jobs_cap = 0;
+        bool parked_at(int id, unsigned long long frame) const
+        {
+            if (leaf.empty())
+                return false;
+            const Leaf &L = leaf[(size_t)id];
+            return !(frame >= L.since ? L.active : L.was_active);
+        }
+    } park;
 
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first

@@ -5,11 +5,15 @@
 namespace {
 
 // Leaf `id`'s payload of the delivered frame in host slot `slot`.  Option squelch: through the delivered directory -- a closed
-// leaf has *len = 0 (the pointer is valid and not to be read).
+// leaf has *len = 0 (the pointer is valid and not to be read).  Option park: so has a leaf that was parked in that frame.
 const unsigned char *leaf_payload(const sdrx_ctx *c, int id, int slot, uint32_t *len)
 {
     const Node &n = c->nodes[(size_t)id];
     *len = n.pay_len;
+    if (c->park.parked_at(id, c->host_frame)) {
+        *len = 0;
+        return c->h_pay[slot];
+    }
     if (!c->opt_squelch)
         return c->h_pay[slot] + n.pay_off;
     const size_t k = (size_t)c->sq.index[(size_t)id];
@@ -26,7 +30,7 @@ const unsigned char *leaf_payload(const sdrx_ctx *c, int id, int slot, uint32_t 
 const unsigned char *leaf_preroll(const sdrx_ctx *c, int id, int slot, uint32_t *len)
 {
     *len = 0;
-    if (!c->opt_preroll)
+    if (!c->opt_preroll || c->park.parked_at(id, c->host_frame))
         return c->h_pay[slot];
     const size_t k = (size_t)c->sq.index[(size_t)id];
     if (c->sq.offs[k] == kSqClosed || !c->sq.pre[k])
@@ -306,6 +310,10 @@ int sdrx_get_meters(sdrx_ctx *c, const int *ids, int n, sdrx_meter *out)
         sdrx_meter m;
         memset(&m, 0, sizeof m);
         m.frame = (int64_t)c->host_frame;
+        if (c->park.parked_at(ids[k], c->host_frame)) { // no value: nothing wrote the leaf's records in that frame
+            out[k] = m;
+            continue;
+        }
         m.n_values = (uint32_t)(nd.d.demod_usb ? nd.n_out : 2 * nd.n_f);
         uint32_t peak = 0;
         for (int j = 0; j < nd.meter_n; ++j) { // {sum_sq u64, clipped u32, peak u32} per slot
@@ -489,8 +497,11 @@ int sdrx_get_egress(sdrx_ctx *c, int64_t *frame, uint32_t *n_open, uint32_t *n_l
         *frame = (int64_t)c->host_frame;
     if (n_leaves)
         *n_leaves = leaves;
+    uint32_t n_active = leaves;
+    for (int i : c->publish_order)
+        n_active -= c->park.parked_at(i, c->host_frame);
     if (n_open)
-        *n_open = c->opt_squelch ? c->sq.n_open : leaves;
+        *n_open = c->opt_squelch ? c->sq.n_open : n_active;
     if (payload_bytes_copied)
         *payload_bytes_copied = c->opt_squelch ? c->sq.copied : (uint64_t)(c->meter_off ? c->meter_off : c->pay_bytes);
     return SDRX_OK;

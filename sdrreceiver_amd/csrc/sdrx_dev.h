@@ -180,4 +180,29 @@ struct RetuneJob {
 };
 static_assert(sizeof(RetuneJob) % 8 == 0, "RetuneJob array stride");
 
+// ---- option park (sdrx_set_active) ----------------------------------------------
+// What the park = 1 form of a kernel is given besides, in a trailing argument that is empty for the form without: the option
+// off runs the kernels as they were.  `act`: one word per descriptor of THAT kernel (K1Vfo: per node; K2aVfo / K2Vfo / K3Vfo /
+// K4Vfo: per entry of the array; the squelch gate: per leaf in publish order), 1 = active, 0 = parked.  A work unit reads its
+// word first -- wave-uniform, a scalar load -- and returns if it is 0.
+// The mix items of the one-launch levels (k_mix_levels, k_levels_tail) carry the flag in a word they read anyway: bit kParkBit
+// of their entry of item_level[] is set while the leaf is parked (the exact k_levels_tail has no register for another pointer;
+// its `act` names the K2Vfo words of its demodulation blocks).
+constexpr int kParkBit = 1 << 8;
+template <bool PARK>
+struct ParkArg {
+};
+template <>
+struct ParkArg<true> {
+    const int *act;
+};
+
+// One entry of k_vfo_reset's job list: `words` 32-bit words from `ptr` on become `value` -- a flag word (1 word), a state
+// region of a leaf that is unparked (zeros: the reference's zero-initialised filter state, dsp.cpp:40-49), its gate state.
+struct FillJob {
+    unsigned *ptr;
+    unsigned words, value;
+};
+static_assert(sizeof(FillJob) == 16, "FillJob array stride");
+
 } // namespace sdrx

@@ -394,6 +394,7 @@ void build_tail_work(sdrx_ctx *c, Built &B)
             if (two_kernel_late(n)) {
                 for (int b = 0; b < (n.n_out + late_tile - 1) / late_tile; ++b)
                     B.w2a.push_back({(int)B.d2a.size(), b});
+                n.d2a_index = (int)B.d2a.size();
                 B.n2a.push_back(i);
                 B.d2a.push_back(K2aVfo{});
                 lds2a = std::max(lds2a, (int)sizeof(float2) * (n.d.late_decimate * 255 + (int)n.dec.size()));
@@ -423,6 +424,7 @@ void build_tail_work(sdrx_ctx *c, Built &B)
         } else {
             for (int b = 0; b < (n.n_f + 4095) / 4096; ++b)
                 B.w3.push_back({(int)B.d3.size(), b});
+            n.d3_index = (int)B.d3.size();
             B.n3.push_back(i);
             B.d3.push_back(K3Vfo{});
             b3 += n.pay_len;
@@ -911,6 +913,30 @@ int squelch_setup(sdrx_ctx *c)
     return SDRX_OK;
 }
 
+// ---- option park: the flag words, all 1 (every leaf active, as the reference's VFOs are after vfo::init)
+int park_setup(sdrx_ctx *c, const Built &B)
+{
+    c->park = sdrx_ctx::Park();
+    if (!c->opt_park)
+        return SDRX_OK;
+    sdrx_ctx::Park &K = c->park;
+    K.o_2a = c->nodes.size();
+    K.o_2 = K.o_2a + B.d2a.size();
+    K.o_3 = K.o_2 + B.d2.size();
+    K.o_4 = K.o_3 + B.d3.size();
+    K.o_sq = K.o_4 + B.d4.size();
+    K.words = K.o_sq + c->publish_order.size();
+    K.leaf.assign(c->nodes.size(), sdrx_ctx::Park::Leaf());
+    K.items.assign(c->nodes.size(), {});
+    if (c->fp.usable)
+        for (size_t it = 0; it < B.all_items.size(); ++it)
+            K.items[(size_t)B.all_items[it].vfo].push_back((int)it);
+    HIPCHK(c, hipMalloc(&K.d_act, sizeof(int) * K.words));
+    HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(K.d_act), 1, K.words, c->st.stream));
+    HIPCHK(c, hipStreamSynchronize(c->st.stream));
+    return SDRX_OK;
+}
+
 int finalize_impl(sdrx_ctx *c)
 {
     if (int rc = derive_nodes(c))
@@ -926,6 +952,8 @@ int finalize_impl(sdrx_ctx *c)
         return rc;
     build_publish_order(c);
     if (int rc = squelch_setup(c))
+        return rc;
+    if (int rc = park_setup(c, B))
         return rc;
     c->sq.preroll_fused = false;
     for (const Node &n : c->nodes)

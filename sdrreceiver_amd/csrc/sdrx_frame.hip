@@ -60,25 +60,41 @@ struct Bracket { // RAII: event pair around one launch when timing is on, on the
     }
 };
 
-// The kernel variants this context runs, as compile-time constants: fn(EXACT, ROT, METER), each a std::bool_constant, from option
-// "exact" -- 1 the exact arithmetic, 0 the tolerance arithmetic (NCO as rotations), 2 the robust one (exact NCO, FMA mixer and
-// filters; kernels.hip, nco_mix) -- and option "meter".  Every launch of a kernel that has variants goes through here, so these six
-// combinations are all that is ever instantiated: there is no (EXACT, ROT) = (1, 1) kernel.
+// The kernel variants this context runs, as compile-time constants: fn(EXACT, ROT, METER, PARK), each a std::bool_constant, from
+// option "exact" -- 1 the exact arithmetic, 0 the tolerance arithmetic (NCO as rotations), 2 the robust one (exact NCO, FMA mixer
+// and filters; kernels.hip, nco_mix) --, option "meter" and option "park".  Every launch of a kernel that has variants goes through
+// here, so these twelve combinations are all that is ever instantiated: there is no (EXACT, ROT) = (1, 1) kernel.
 template <class F>
 void with_variant(const sdrx_ctx *c, F fn)
 {
-    auto arith = [&](auto meter) {
+    auto arith = [&](auto meter, auto park) {
         if (c->opt_exact == 1)
-            fn(std::true_type(), std::false_type(), meter);
+            fn(std::true_type(), std::false_type(), meter, park);
         else if (c->opt_exact == 2)
-            fn(std::false_type(), std::false_type(), meter);
+            fn(std::false_type(), std::false_type(), meter, park);
         else
-            fn(std::false_type(), std::true_type(), meter);
+            fn(std::false_type(), std::true_type(), meter, park);
     };
-    if (c->opt_meter)
-        arith(std::true_type());
+    auto meter = [&](auto park) {
+        if (c->opt_meter)
+            arith(std::true_type(), park);
+        else
+            arith(std::false_type(), park);
+    };
+    if (c->opt_park)
+        meter(std::true_type());
     else
-        arith(std::false_type());
+        meter(std::false_type());
+}
+// Option park: the flag words of one kernel's descriptors (sdrx_ctx::Park: `first` = where that kernel's words begin in d_act);
+// empty with the option off.
+template <bool PARK>
+ParkArg<PARK> park_arg(const sdrx_ctx *c, size_t first)
+{
+    ParkArg<PARK> P;
+    if constexpr (PARK)
+        P.act = c->park.d_act + first;
+    return P;
 }
 
 int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st); // (sdrx_delivery.hip)
@@ -127,7 +143,7 @@ void spectrum_raw_step(sdrx_ctx *c, const void *raw, int raw_mode)
 // records: decide + scan (one workgroup), then the gather of the open leaves into d_pack[p] (squelch.hip).  Not bracketed:
 // sdrx_get_kernel_times keeps its SDRX_NKERNELS kinds.  PRE (option preroll): the two launches in their second form -- the gather
 // also reads frame - 1's payloads in d_pay[p ^ 1]; AUTO (option squelch_auto): the scan with the floor records, the gather as without.
-template <bool PRE, bool AUTO>
+template <bool PRE, bool AUTO, bool PARK>
 void launch_gate(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
 {
     const int n = (int)c->publish_order.size();
@@ -139,18 +155,24 @@ void launch_gate(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
         X = {c->sq.d_prev, c->d_pay[p ^ 1]};
     if constexpr (AUTO)
         A = {c->sq.d_auto};
-    hipLaunchKernelGGL((k_squelch_scan<PRE, AUTO>), dim3(1), dim3(kSqThreads), 0, ts, c->sq.d_leaves, c->sq.d_cfg, c->sq.d_hang, c->d_pay[p], dir, n,
-                       (long long)frame, X, A);
+    hipLaunchKernelGGL((k_squelch_scan<PRE, AUTO, PARK>), dim3(1), dim3(kSqThreads), 0, ts, c->sq.d_leaves, c->sq.d_cfg, c->sq.d_hang, c->d_pay[p], dir, n,
+                       (long long)frame, X, A, park_arg<PARK>(c, c->park.o_sq));
     hipLaunchKernelGGL(k_squelch_gather<PRE>, dim3(n, c->sq.tiles, PRE ? 2 : 1), dim3(256), 0, ts, c->sq.d_leaves, c->d_pay[p], dir, c->sq.d_pack[p], X);
 }
 void squelch_gate(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
 {
     if (!c->opt_squelch || c->publish_order.empty())
         return;
-    if (c->opt_preroll)
-        c->opt_squelch_auto ? launch_gate<true, true>(c, ts, frame) : launch_gate<true, false>(c, ts, frame);
+    auto form = [&](auto PARK) {
+        if (c->opt_preroll)
+            c->opt_squelch_auto ? launch_gate<true, true, PARK()>(c, ts, frame) : launch_gate<true, false, PARK()>(c, ts, frame);
+        else
+            c->opt_squelch_auto ? launch_gate<false, true, PARK()>(c, ts, frame) : launch_gate<false, false, PARK()>(c, ts, frame);
+    };
+    if (c->opt_park)
+        form(std::true_type());
     else
-        c->opt_squelch_auto ? launch_gate<false, true>(c, ts, frame) : launch_gate<false, false>(c, ts, frame);
+        form(std::false_type());
 }
 
 // One block-per-tile launch of the leaf tail (late decimation / demodulation / long audio low-pass / compress) for `frame`.
@@ -161,17 +183,22 @@ void launch_block_kernel(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned
     const BlockWork *w = reinterpret_cast<const BlockWork *>(c->arena + L.off_work);
     const int *mrel = c->opt_meter ? reinterpret_cast<const int *>(c->arena + L.off_mrel) : nullptr;
     const unsigned char *desc = c->arena + L.off_desc;
-    with_variant(c, [&](auto EXACT, auto, auto METER) {
+    with_variant(c, [&](auto EXACT, auto, auto METER, auto PARK) {
         if (L.kind == KIND_LATE_DEC && c->late4)
-            hipLaunchKernelGGL(k_late_decimate4<EXACT()>, grid, dim3(64), L.lds_bytes, ts, reinterpret_cast<const K2aVfo *>(desc), w, frame);
+            hipLaunchKernelGGL((k_late_decimate4<EXACT(), PARK()>), grid, dim3(64), L.lds_bytes, ts, reinterpret_cast<const K2aVfo *>(desc), w, frame,
+                               park_arg<PARK()>(c, c->park.o_2a));
         else if (L.kind == KIND_LATE_DEC)
-            hipLaunchKernelGGL(k_late_decimate<EXACT()>, grid, dim3(256), L.lds_bytes, ts, reinterpret_cast<const K2aVfo *>(desc), w, frame);
+            hipLaunchKernelGGL((k_late_decimate<EXACT(), PARK()>), grid, dim3(256), L.lds_bytes, ts, reinterpret_cast<const K2aVfo *>(desc), w, frame,
+                               park_arg<PARK()>(c, c->park.o_2a));
         else if (L.kind == KIND_DEMOD)
-            hipLaunchKernelGGL((k_usb_demod<EXACT(), METER()>), grid, dim3(256), 0, ts, reinterpret_cast<const K2Vfo *>(desc), w, frame);
+            hipLaunchKernelGGL((k_usb_demod<EXACT(), METER(), PARK()>), grid, dim3(256), 0, ts, reinterpret_cast<const K2Vfo *>(desc), w, frame,
+                               park_arg<PARK()>(c, c->park.o_2));
         else if (L.kind == KIND_LPF_LONG)
-            hipLaunchKernelGGL((k_lpf_long<EXACT(), METER()>), grid, dim3(256), L.lds_bytes, ts, reinterpret_cast<const K4Vfo *>(desc), w, frame, mrel);
+            hipLaunchKernelGGL((k_lpf_long<EXACT(), METER(), PARK()>), grid, dim3(256), L.lds_bytes, ts, reinterpret_cast<const K4Vfo *>(desc), w, frame, mrel,
+                               park_arg<PARK()>(c, c->park.o_4));
         else
-            hipLaunchKernelGGL(k_compress<METER()>, grid, dim3(256), 0, ts, reinterpret_cast<const K3Vfo *>(desc), w, frame);
+            hipLaunchKernelGGL((k_compress<METER(), PARK()>), grid, dim3(256), 0, ts, reinterpret_cast<const K3Vfo *>(desc), w, frame,
+                               park_arg<PARK()>(c, c->park.o_3));
     });
 }
 
@@ -218,8 +245,9 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
         Bracket b(c, c->st.stream, lo != hi ? KIND_LEVELS : lo == 0 ? KIND_MIX_ROOT : KIND_MIX_SUB, bytes);
         const int *list = reinterpret_cast<const int *>(c->arena + P.off_list) + first;
         const dim3 grid(last - first);
-        with_variant(c, [&](auto EXACT, auto ROT, auto METER) {
-            hipLaunchKernelGGL((k_mix_levels<EXACT(), ROT(), METER()>), grid, dim3(64), P.lds_bytes, c->st.stream, k1, items, item_level, list, A);
+        with_variant(c, [&](auto EXACT, auto ROT, auto METER, auto PARK) {
+            hipLaunchKernelGGL((k_mix_levels<EXACT(), ROT(), METER(), PARK()>), grid, dim3(64), P.lds_bytes, c->st.stream, k1, items, item_level, list, A,
+                               park_arg<PARK()>(c, 0));
         });
     } else {
         // the list is [level n-1 | ... | level 0 | demodulation]: the range runs from the deepest level with a frame to the
@@ -240,8 +268,9 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
         const K2Vfo *k2 = reinterpret_cast<const K2Vfo *>(c->arena + D.off_desc);
         const BlockWork *dwork = reinterpret_cast<const BlockWork *>(c->arena + D.off_work);
         const dim3 grid(last - first);
-        with_variant(c, [&](auto EXACT, auto ROT, auto METER) {
-            hipLaunchKernelGGL((k_levels_tail<EXACT(), ROT(), METER()>), grid, dim3(256), P.tail_lds, c->st.stream, k1, items, item_level, wgs, k2, dwork, T);
+        with_variant(c, [&](auto EXACT, auto ROT, auto METER, auto PARK) {
+            hipLaunchKernelGGL((k_levels_tail<EXACT(), ROT(), METER(), PARK()>), grid, dim3(256), P.tail_lds, c->st.stream, k1, items, item_level, wgs, k2, dwork,
+                               T, park_arg<PARK()>(c, c->park.o_2));
         });
     }
     if (dm)
@@ -368,11 +397,13 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         const K1Work *w = reinterpret_cast<const K1Work *>(c->arena + L.off_work);
         const void *lraw = L.level == 0 ? raw : nullptr;
         const int lmode = L.level == 0 ? raw_mode : kRawTiled;
-        with_variant(c, [&](auto EXACT, auto ROT, auto METER) {
+        with_variant(c, [&](auto EXACT, auto ROT, auto METER, auto PARK) {
             if (L.level == 0)
-                hipLaunchKernelGGL((k_mix_decimate<EXACT(), 0, ROT(), METER()>), dim3(L.n_work), dim3(64), L.lds_bytes, c->st.stream, k1, w, c->frame_no, lraw, lmode);
+                hipLaunchKernelGGL((k_mix_decimate<EXACT(), 0, ROT(), METER(), PARK()>), dim3(L.n_work), dim3(64), L.lds_bytes, c->st.stream, k1, w, c->frame_no, lraw,
+                                   lmode, park_arg<PARK()>(c, 0));
             else
-                hipLaunchKernelGGL((k_mix_decimate<EXACT(), 1, ROT(), METER()>), dim3(L.n_work), dim3(64), L.lds_bytes, c->st.stream, k1, w, c->frame_no, lraw, lmode);
+                hipLaunchKernelGGL((k_mix_decimate<EXACT(), 1, ROT(), METER(), PARK()>), dim3(L.n_work), dim3(64), L.lds_bytes, c->st.stream, k1, w, c->frame_no, lraw,
+                                   lmode, park_arg<PARK()>(c, 0));
         });
     }
     hipStream_t ts = pipe ? c->st.tail_stream : c->st.stream;

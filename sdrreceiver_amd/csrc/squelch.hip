@@ -31,6 +31,11 @@
 //     thr_eff = max(thr, auto);  the rule above with thr_eff in place of thr
 //     cur_min = min(cur_min, s);  age += 1;  if (age == window_frames) { prev_min = cur_min; cur_min = NONE; age = 0; }
 // and the directory gains thr_eff[n] and floor[n] (u64, 8-byte aligned) behind what it holds without: this frame's values.
+//
+// Option "park"  launches k_squelch_scan with the template parameter PARK and one word per leaf (ParkArg,
+// sdrx_dev.h).  A parked leaf is closed whatever its threshold is (0 = "always open" holds for active leaves only), never
+// pre-rolled, and the frame is no observation: hang_left, prev_open and the floor state stay as they are.  Its meter records
+// are stale (nothing wrote them) and are not read into the decision.
 #pragma once
 
 namespace sdrx {
@@ -121,11 +126,11 @@ __global__ __launch_bounds__(64) void k_squelch_set_auto(const SqAutoJob *__rest
 __host__ __device__ inline size_t sq_aux_off(size_t n, bool pre) { return (sizeof(SqHeader) + (pre ? 12 : 8) * n + 7) / 8 * 8; }
 
 // dir: SqHeader | unsigned offs[n] | unsigned hang[n] | PRE: unsigned pre[n] | AUTO: u64 thr_eff[n] | u64 floor[n]
-template <bool PRE = false, bool AUTO = false>
+template <bool PRE = false, bool AUTO = false, bool PARK = false>
 __global__ __launch_bounds__(kSqThreads) void k_squelch_scan(const SqLeaf *__restrict__ leaves, const SqCfg *__restrict__ cfg,
                                                              unsigned *__restrict__ hang_left, const unsigned char *__restrict__ pay,
                                                              unsigned char *__restrict__ dir, int n, long long frame, SqPre<PRE> X,
-                                                             SqAut<AUTO> A)
+                                                             SqAut<AUTO> A, ParkArg<PARK> K)
 {
     __shared__ unsigned s_units[kSqThreads / 64], s_open[kSqThreads / 64];
     __shared__ unsigned s_pre[PRE ? kSqThreads / 64 : 1]; // (PRE = false never touches it and the compiler drops it: 128 bytes
@@ -141,6 +146,9 @@ __global__ __launch_bounds__(kSqThreads) void k_squelch_scan(const SqLeaf *__res
         if (i < n) {
             const SqLeaf L = leaves[i];
             const SqCfg C = cfg[i];
+            bool parked = false;
+            if constexpr (PARK)
+                parked = K.act[i] == 0;
             uint4 a0 = make_uint4(0, 0, 0, 0), a1 = a0; // AUTO: the leaf's record, asked for HERE, with the loads above
             if constexpr (AUTO) {
                 const uint4 *ap = reinterpret_cast<const uint4 *>(A.state + i);
@@ -173,10 +181,13 @@ __global__ __launch_bounds__(kSqThreads) void k_squelch_scan(const SqLeaf *__res
                     cur = kSqNone;
                     age = 0;
                 }
-                uint4 *ap = reinterpret_cast<uint4 *>(A.state + i);
-                ap[0] = make_uint4((unsigned)cur, (unsigned)(cur >> 32), (unsigned)prev, (unsigned)(prev >> 32));
-                reinterpret_cast<unsigned *>(ap + 1)[0] = age;
+                if (!parked) { // (a parked frame is not an observation of the floor)
+                    uint4 *ap = reinterpret_cast<uint4 *>(A.state + i);
+                    ap[0] = make_uint4((unsigned)cur, (unsigned)(cur >> 32), (unsigned)prev, (unsigned)(prev >> 32));
+                    reinterpret_cast<unsigned *>(ap + 1)[0] = age;
+                }
             }
+            const unsigned h_was = h;
             is_open = 1;
             if (s >= thr)
                 h = C.hang_frames;
@@ -184,12 +195,18 @@ __global__ __launch_bounds__(kSqThreads) void k_squelch_scan(const SqLeaf *__res
                 h -= 1;
             else
                 is_open = 0;
+            if (parked) { // closed, and the hang time does not run
+                is_open = 0;
+                h = h_was;
+            }
             hang_left[i] = h;
             hang[i] = h;
             units = is_open ? L.pay_units : 0u;
             if constexpr (PRE) {
-                pre = is_open & (X.prev_open[i] == 0u);
-                X.prev_open[i] = is_open;
+                if (!parked) {
+                    pre = is_open & (X.prev_open[i] == 0u);
+                    X.prev_open[i] = is_open;
+                }
                 hang[n + i] = pre; // (pre[] lies behind hang[])
                 units += pre ? L.pay_units : 0u; // frame f-1's payload in front of frame f's
             }

@@ -54,7 +54,7 @@ class Receiver:
                  fuse_late: bool = True, keep_streams: bool = False, dc_speculative: bool = True,
                  dc_blocks_per_step: int | None = None, fuse_demod: bool = False,
                  tail_in_levels: bool = True, meter: bool = False, squelch: bool = False, preroll: bool = False,
-                 squelch_auto: bool = False):
+                 squelch_auto: bool = False, park: bool = False):
         self.L = _lib.lib()
         h = C.c_void_p()
         rc = self.L.sdrx_create(C.byref(h), int(device))
@@ -83,6 +83,8 @@ class Receiver:
             self._chk(self.L.sdrx_set_option(self.h, b"preroll", 1))
         if squelch_auto:
             self._chk(self.L.sdrx_set_option(self.h, b"squelch_auto", 1))
+        if park:
+            self._chk(self.L.sdrx_set_option(self.h, b"park", 1))
         self._chk(self.L.sdrx_set_option(self.h, b"dc_speculative", int(bool(dc_speculative))))
         if dc_blocks_per_step is not None:
             self._chk(self.L.sdrx_set_option(self.h, b"dc_blocks_per_step", int(dc_blocks_per_step)))
@@ -280,6 +282,21 @@ class Receiver:
         out = (_lib.SquelchAutoStateC * max(1, ids.size))()
         self._chk(self.L.sdrx_get_squelch_auto(self.h, ids.ctypes.data, ids.size, out))
         return _squelch.squelch_auto_dict(out[:ids.size])
+
+    # -- parking (option ``park``): leaves switched off and on between frames --------------------------------------------
+    def set_active(self, vids, active) -> None:
+        """Park (``active[k]`` 0) or unpark (1) the leaves `vids` before the next frame.  A parked leaf costs no arithmetic and
+        is delivered like a closed one; an unparked leaf starts as a new VFO does (fresh oscillator, zero filter state)."""
+        ids, act = _value_list(vids, active, np.int32)
+        self._chk(self.L.sdrx_set_active(self.h, ids.ctypes.data, act.ctypes.data, ids.size))
+
+    def active(self, vids) -> dict:
+        """``active`` and ``since_frame`` (the first frame in the present state) of the leaves `vids`, as arrays."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        out = (_lib.ActiveStateC * max(1, ids.size))()
+        self._chk(self.L.sdrx_get_active(self.h, ids.ctypes.data, ids.size, out))
+        return {"active": np.array([o.active for o in out[:ids.size]], dtype=np.int32),
+                "since_frame": np.array([o.since_frame for o in out[:ids.size]], dtype=np.int64)}
 
     def output_rate(self, vid: int) -> int:
         rate = C.c_uint32()
@@ -563,6 +580,19 @@ class Group:
         out = (_lib.SquelchAutoStateC * max(1, ids.size))()
         self._chk(self.L.sdrx_group_get_squelch_auto(self.h, ids.ctypes.data, ids.size, out))
         return _squelch.squelch_auto_dict(out[:ids.size])
+
+    def set_active(self, vids, active) -> None:
+        """:meth:`Receiver.set_active` with ids of the whole tree (group option ``park=1``)."""
+        ids, act = _value_list(vids, active, np.int32)
+        self._chk(self.L.sdrx_group_set_active(self.h, ids.ctypes.data, act.ctypes.data, ids.size))
+
+    def active(self, vids) -> dict:
+        """:meth:`Receiver.active` with ids of the whole tree; ``since_frame`` counts the group's frames."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        out = (_lib.ActiveStateC * max(1, ids.size))()
+        self._chk(self.L.sdrx_group_get_active(self.h, ids.ctypes.data, ids.size, out))
+        return {"active": np.array([o.active for o in out[:ids.size]], dtype=np.int32),
+                "since_frame": np.array([o.since_frame for o in out[:ids.size]], dtype=np.int64)}
 
     def locate(self, vid: int) -> tuple[int, int]:
         m, l = C.c_int(), C.c_int()
