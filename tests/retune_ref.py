@@ -169,6 +169,7 @@ class Node:
         if self.lpf is not None:
             usb, self.lpf_hist = fir_excl(self.lpf, self.lpf_hist, usb)
         pre = (usb * self.gain).astype(np.float64) * 32768.0
+        self.pre = pre  # (float32 * 2^15: exact as float32 too -- what the meters' `clipped` and `peak` are defined on)
         return to_short(pre)
 
 
