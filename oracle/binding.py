@@ -103,6 +103,7 @@ class _Lib:
             s("double_to_short").argtypes = [_d]
             s("double_to_short").restype = C.c_short
             s("vfo_get_publish").argtypes = [_vp, _vp, _vp, _vp, _vp]
+            s("vfo_retune").argtypes = [_vp, _d]
         else:
             s("vfo_init").argtypes = [_vp, _i, _i, _i]
             s("vfo_set_zmq_topic").argtypes = [_vp, C.c_char_p]
@@ -216,6 +217,11 @@ class OracleVfo:
 
     def setGain(self, g):
         self.L.fn("vfo_set_gain")(self.h, float(g))
+
+    def retune(self, f):
+        """Between two frames: a fresh Oscillator(Fs, f), every filter state kept (port only: the reference has no such call)."""
+        assert self.kind == "port"
+        self.L.fn("vfo_retune")(self.h, float(f))
 
     def setCompressonStyle(self, st):  # sic, vfo.h:36
         self.L.fn("vfo_set_compression_style")(self.h, int(st))

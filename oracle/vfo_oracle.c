@@ -379,6 +379,17 @@ void orc_vfo_set_mixer_freq(orc_vfo *v, double f) { v->mixer_freq = f; }
 void orc_vfo_set_demod_usb(orc_vfo *v, int usb) { v->demod_usb = usb != 0; }
 void orc_vfo_set_filter_bandwidth(orc_vfo *v, double bw) { v->filterbw = (int)bw; } /* int member, vfo.h:104 */
 void orc_vfo_set_gain(orc_vfo *v, float g) { v->gain = g; }
+
+/* A retune of a running node: `delete osc_mix; osc_mix = new Oscillator(Fs, f)` between two vfo::process calls.  The
+ * oscillator starts again (its first tick takes entry L-1, oscillator.cpp:30,39-50); every filter keeps its state. */
+void orc_vfo_retune(orc_vfo *v, double f)
+{
+    v->mixer_freq = f;
+    if (v->osc_table) {
+        orc_osc_table((double)v->fs, f, v->osc_table);
+        v->sample_count = 0;
+    }
+}
 void orc_vfo_set_compression_style(orc_vfo *v, int st) { v->cstyle = st; }
 void orc_vfo_set_scale_comp(orc_vfo *v, int s) { v->scalecomp = s; }
 void orc_vfo_set_topic(orc_vfo *v, const char *t)

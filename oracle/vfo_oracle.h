@@ -27,6 +27,7 @@ void orc_vfo_set_mixer_freq(orc_vfo *v, double f);
 void orc_vfo_set_demod_usb(orc_vfo *v, int usb);
 void orc_vfo_set_filter_bandwidth(orc_vfo *v, double bw);
 void orc_vfo_set_gain(orc_vfo *v, float g);
+void orc_vfo_retune(orc_vfo *v, double f); /* after init: a fresh oscillator, the filters keep their state */
 void orc_vfo_set_compression_style(orc_vfo *v, int st);
 void orc_vfo_set_scale_comp(orc_vfo *v, int s);
 void orc_vfo_set_topic(orc_vfo *v, const char *topic);

@@ -327,7 +327,53 @@ def gen_dropin():
         print(f"dropin_{name}.json", len(lines), "lines")
 
 
+LATTICE_FRAMES = 4
+
+
+def gen_lattice():
+    """tests/golden/lattice.npz: the trees of tests/lattice.py (depths, positions, late decimations and scalecomp values no
+    other fixture holds) through the REAL reference build, -O2, on lattice.frames: per tree one uint8 array
+    [frame, node, (final stream | payload), 8] of the first 8 bytes of the sha256 (zeros where an inner node has no
+    payload) -- digests only, about 10 KB.  The provenance string records what the -O2 and the shipped -Ofast build differ
+    by on these inputs, per tree: max|a - b| / max|a| over every final stream, and the largest int16 difference."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import lattice as lt
+    d = {"frames": np.int64(LATTICE_FRAMES)}
+    lines = []
+    for name, topo in lt.trees().items():
+        ref = ob.build_tree("reference", topo)
+        fast = ob.build_tree("reference_ofast", topo) if ob.have_reference_ofast() else None
+        dig = np.zeros((LATTICE_FRAMES, len(topo.vfos), 2, 8), np.uint8)
+        worst, lsb = 0.0, 0
+        for f, iq in enumerate(lt.frames(name)[:LATTICE_FRAMES]):
+            ob.process_roots(ref[1], iq)
+            if fast:
+                ob.process_roots(fast[1], iq)
+            for i, v in enumerate(topo.vfos):
+                z = ref[0][i].stream()
+                dig[f, i, 0] = np.frombuffer(hashlib.sha256(z.tobytes()).digest()[:8], np.uint8)
+                pay = None
+                if not topo.children(i):
+                    pay = ref[0][i].usb() if v.demod_usb else ref[0][i].iq()
+                    dig[f, i, 1] = np.frombuffer(hashlib.sha256(pay.tobytes()).digest()[:8], np.uint8)
+                if fast:
+                    worst = max(worst, float(np.abs(z - fast[0][i].stream()).max() / np.abs(z).max()))
+                    if pay is not None and v.demod_usb:
+                        lsb = max(lsb, int(np.abs(pay.astype(np.int32) - fast[0][i].usb().astype(np.int32)).max()))
+        d[name] = dig
+        lines.append(f"{name}: {len(topo.vfos)} nodes" + (f", -O2 vs -Ofast {worst:.2e} of max|stream|, int16 within {lsb} LSB" if fast else ""))
+    d["provenance"] = np.array("real vfo tree (oracle/_ref/libsdrref.so, -O2) on tests/lattice.py frames; " + "; ".join(lines))
+    np.savez_compressed(os.path.join(OUT, "lattice.npz"), **d)
+    print("lattice.npz:", os.path.getsize(os.path.join(OUT, "lattice.npz")), "bytes")
+    print("\n".join(lines))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "lattice":
+        if not ob.have_reference():
+            sys.exit("oracle/_ref/libsdrref.so missing: run `make -C oracle/ref` first (needs /root/reference)")
+        gen_lattice()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "dropin":
         gen_dropin()
         sys.exit(0)
@@ -354,5 +400,6 @@ if __name__ == "__main__":
     gen_dc_reference()
     gen_zmq()
     gen_dropin()
+    gen_lattice()
     if ob.have_reference_ofast():
         gen_ofast()
