@@ -222,6 +222,34 @@ public:
             check(sdrx_get_active(ctx_, ids.data(), (int)ids.size(), out.data()), "sdrx_get_active");
         return out;
     }
+    // channel watch (option "watch"): band power of a leaf from its source's spectrum, active or parked
+    void set_watch(const std::vector<int> &ids, const std::vector<int32_t> &on)
+    {
+        if (ids.size() != on.size())
+            throw std::invalid_argument("set_watch: lists of different length");
+        if (grp_)
+            check(sdrx_group_set_watch(grp_, ids.data(), on.data(), (int)ids.size()), "sdrx_group_set_watch");
+        else
+            check(sdrx_set_watch(ctx_, ids.data(), on.data(), (int)ids.size()), "sdrx_set_watch");
+    }
+    std::vector<sdrx_watch_level> watch(const std::vector<int> &ids)
+    {
+        std::vector<sdrx_watch_level> out(ids.size());
+        if (grp_)
+            check(sdrx_group_get_watch(grp_, ids.data(), (int)ids.size(), out.data()), "sdrx_group_get_watch");
+        else
+            check(sdrx_get_watch(ctx_, ids.data(), (int)ids.size(), out.data()), "sdrx_get_watch");
+        return out;
+    }
+    std::vector<double> watch_psd(int leaf_id, int64_t *frame = nullptr)
+    {
+        std::vector<double> psd(SDRX_SPECTRUM_BINS);
+        if (grp_)
+            check(sdrx_group_get_watch_psd(grp_, leaf_id, psd.data(), frame), "sdrx_group_get_watch_psd");
+        else
+            check(sdrx_get_watch_psd(ctx_, leaf_id, psd.data(), frame), "sdrx_get_watch_psd");
+        return psd;
+    }
 
 private:
     bool started() const { return ctx_ || grp_; }

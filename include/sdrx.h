@@ -164,6 +164,11 @@ int sdrx_add_vfo(sdrx_ctx *ctx, const sdrx_vfo_desc *desc, int *id_out);
  *            the same kernels, launches, device_bytes and payloads, and sdrx_set_active returns SDRX_ESTATE.  With 1 and
  *            nothing parked every payload, stream, meter, squelch decision and callback is bit for bit what it is with 0; the
  *            kernels are then the forms that read one flag word per work item first.
+ *   "watch" 0 (default) | 1: channel watch (sdrx_set_watch below): the power inside any leaf's passband, measured on the stream
+ *            the leaf is fed, whether the leaf is active or parked.  0 changes nothing: the same kernels, launches,
+ *            device_bytes, payloads and callbacks, and the watch calls return SDRX_ESTATE.  1 is independent of "park", "meter"
+ *            and "squelch"; until the first sdrx_set_watch switches a leaf on, device_bytes and the launches are those of 0
+ *            (DESIGN.md section 4j).
  *   "dc_blocked_scan" 0|1 (default 0): how sdrx_process_u8 removes the DC bias.  0 = the
  *                 reference's sequentially rounded fp32 recurrence, bit for bit (below).  1 = the same linear filter as a
  *                 blocked parallel scan (~15 us): the true IIR response.  The reference's recurrence
@@ -406,6 +411,63 @@ typedef struct sdrx_active_state {
 } sdrx_active_state;
 int sdrx_set_active(sdrx_ctx *ctx, const int *ids, const int32_t *active, int n);
 int sdrx_get_active(sdrx_ctx *ctx, const int *ids, int n, sdrx_active_state *out);
+
+/* Channel watch (option "watch" = 1): what tells a host WHEN to unpark.  A parked leaf does no work and so has no meter, no
+ * squelch observation and no spectrum; the watch measures the stream the leaf CONSUMES instead -- one power spectrum per source
+ * stream, shared by all the leaves it feeds -- and gives each watched leaf one number: the power inside the band that would
+ * reach its output.  A leaf can be watched whether active or parked, and its figures do not depend on which.  The reference
+ * has no counterpart (it runs every VFO always): this text is the definition.
+ *
+ * Source of a leaf: decimate[decimate_count] of its parent; for parent_id == -1 the raw frame exactly as sdrx_get_raw /
+ * SDRX_SPECTRUM_RAW define it (after the byte LUT and the DC-bias removal on the device; for sdrx_process_device /
+ * sdrx_submit_device the caller's device frame, read inside that frame's own launch sequence).  A source is measured in a frame
+ * only while at least one of its leaves is watched.
+ *
+ * Per measured source and frame, n = the source's samples per frame, N = SDRX_SPECTRUM_BINS = 8192:
+ *   S = min(max(n / N, 1), SDRX_WATCH_MAX_SEGMENTS) segments (integer division); segment s starts at sample s * (n / S) and
+ *   takes min(N, n) samples, a stream shorter than N zero-padded as the spectrum display does;
+ *   each segment: Hann window (the display's table) -> kiss_fft of N points, bit-identical to the display's ->
+ *   P_s[i] = fl(fl(im*im) + fl(re*re)) in fp32, no contraction (the expression under the display's sqrtf);
+ *   PSD[i] = sum over s, ascending, of (double)P_s[i];  i in kiss_fft's natural output order (i >= N/2: negative frequencies).
+ * PSD is therefore bit-exact in every arithmetic, given the stream the device holds.
+ *
+ * Band of a leaf, computed on the host in IEEE double, recomputed when sdrx_set_mixer_freqs names the leaf.  The mixer
+ * multiplies by exp(+j 2 pi f t) (oscillator.cpp:9-11, vfo.cpp:241): a component at g in the source lands at g + f in the leaf.
+ * With f = mixer_freq_hz, fs = the leaf's fs, R = fs / 2^decimate_count:
+ *   USB leaf:      R_out = R / late_decimate when late_decimate is 5 or 6, else R;  B = filter_bw_hz if > 0, else R_out / 2,
+ *                  capped at R_out / 2;  [lo, hi] = [-f, -f + B]
+ *   compress leaf: [lo, hi] = [-f - R/2, -f + R/2]
+ *   k_lo = ceil(lo * 8192.0 / fs), k_hi = floor(hi * 8192.0 / fs), n_bins = clamp(k_hi - k_lo + 1, 1, 8192),
+ *   first_bin = k_lo mod 8192 in [0, 8192)  (a mixer beyond +-fs/2 aliases, as the oscillator table does).
+ *
+ * Per watched leaf and frame: band_pwr = sum over j < n_bins of PSD[(first_bin + j) mod 8192], total_pwr = sum of PSD: doubles,
+ * reduced in parallel -- every term is non-negative, so any order lies within n_terms * 2^-53 relative of the exact sum.
+ *
+ * sdrx_set_watch: batched and atomic, with the calling rules of sdrx_set_active -- the whole list is checked first: a bad or
+ * duplicate id, the id of a VFO with children, on[k] not 0 or 1 or n < 0 is SDRX_EINVAL with nothing changed; n == 0 does
+ * nothing; SDRX_ESTATE before sdrx_finalize, with the option off, and while submitted frames are undelivered.  Frames the
+ * software pipeline of sdrx_process_device still holds finish with the old selection first.  The buffers are allocated by the
+ * first call that switches a leaf on (as the spectrum's are); a leaf switched on is measured from the next frame on.
+ * sdrx_get_watch: the figures of the last DELIVERED frame, with the calling rules of sdrx_get_meters; the records travel with
+ * the frame's fixed-size part, so they can be read while the next frame is in flight.
+ * sdrx_get_watch_psd: PSD of the source of watched leaf `leaf_id` after the last frame, with sdrx_get_spectrum's rules:
+ * SDRX_ESTATE while frames are in flight (and before the first frame measured under the present selection of sources),
+ * SDRX_EINVAL if the leaf is not watched.
+ *
+ * Latency: a carrier first seen in the figures of frame f can be heard from frame f + 1 at the earliest -- sdrx_set_active
+ * needs every submitted frame delivered first, and the unparked leaf starts with empty filters. */
+#define SDRX_WATCH_MAX_SEGMENTS 16
+typedef struct sdrx_watch_level {
+    int64_t frame;        /* frame of the source stream these figures were taken from */
+    double band_pwr, total_pwr;
+    int32_t first_bin, n_bins;
+    int32_t segments;     /* S */
+    int32_t watched;      /* 0: not watched in that frame -> the other fields but `frame`, first_bin, n_bins are 0 */
+    int32_t reserved[2];  /* 0 (the record is 48 bytes) */
+} sdrx_watch_level;
+int sdrx_set_watch(sdrx_ctx *ctx, const int *ids, const int32_t *on, int n);
+int sdrx_get_watch(sdrx_ctx *ctx, const int *ids, int n, sdrx_watch_level *out);
+int sdrx_get_watch_psd(sdrx_ctx *ctx, int leaf_id, double *psd /* 8192, natural order */, int64_t *frame);
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);
@@ -554,6 +616,11 @@ int sdrx_group_get_squelch_auto(sdrx_group *grp, const int *ids, int n, sdrx_squ
  * owns the leaf; `since_frame` counts the group's frames. */
 int sdrx_group_set_active(sdrx_group *grp, const int *ids, const int32_t *active, int n);
 int sdrx_group_get_active(sdrx_group *grp, const int *ids, int n, sdrx_active_state *out);
+/* sdrx_set_watch / sdrx_get_watch / sdrx_get_watch_psd with ids of the whole tree (group option "watch" = 1), each id routed to
+ * the member that owns the leaf; each member measures the replicas of the source streams it holds. */
+int sdrx_group_set_watch(sdrx_group *grp, const int *ids, const int32_t *on, int n);
+int sdrx_group_get_watch(sdrx_group *grp, const int *ids, int n, sdrx_watch_level *out);
+int sdrx_group_get_watch_psd(sdrx_group *grp, int leaf_id, double *psd, int64_t *frame);
 
 /* sdrx_get_preroll routed to the member that owns the leaf; sdrx_get_preroll_count summed over the members (group option
  * "preroll" = 1). */

@@ -73,6 +73,12 @@ class ActiveStateC(C.Structure):
     _fields_ = [("since_frame", C.c_int64), ("active", C.c_int32), ("reserved", C.c_uint32)]
 
 
+class WatchLevelC(C.Structure):
+    """struct sdrx_watch_level"""
+    _fields_ = [("frame", C.c_int64), ("band_pwr", C.c_double), ("total_pwr", C.c_double), ("first_bin", C.c_int32),
+                ("n_bins", C.c_int32), ("segments", C.c_int32), ("watched", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 PUBLISH_FN =C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
 
 # every symbol include/sdrx.h declares: (restype, argtypes)
@@ -128,6 +134,12 @@ SYMBOLS = {
     "sdrx_get_active": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_group_set_active": (_i, [_vp, _vp, _vp, _i]),
     "sdrx_group_get_active": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_set_watch": (_i, [_vp, _vp, _vp, _i]),
+    "sdrx_get_watch": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_get_watch_psd": (_i, [_vp, _i, _vp, C.POINTER(C.c_int64)]),
+    "sdrx_group_set_watch": (_i, [_vp, _vp, _vp, _i]),
+    "sdrx_group_get_watch": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_group_get_watch_psd": (_i, [_vp, _i, _vp, C.POINTER(C.c_int64)]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

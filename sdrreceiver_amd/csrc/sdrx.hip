@@ -30,6 +30,7 @@
 #include "kernels.hip"
 #include "spectrum.hip"
 #include "squelch.hip"
+#include "watch.hip"
 #include "tapdesign.h"
 
 using namespace sdrx;
@@ -39,10 +40,33 @@ static_assert(sizeof(sdrx_stats) == 80, "sdrx_stats ABI layout");
 static_assert(sizeof(sdrx_spectrum_info) == sizeof(SpecRecord) && offsetof(sdrx_spectrum_info, maxval) == offsetof(SpecRecord, maxval) &&
                   SDRX_SPECTRUM_BINS == kSpecN,
               "sdrx_spectrum_info ABI layout");
+static_assert(sizeof(sdrx_watch_level) == 48 && sizeof(WatchRecord) == 48 && offsetof(sdrx_watch_level, total_pwr) == offsetof(WatchRecord, total_pwr) &&
+                  offsetof(sdrx_watch_level, watched) == offsetof(WatchRecord, watched) && SDRX_WATCH_MAX_SEGMENTS == kWatchMaxSeg,
+              "sdrx_watch_level ABI layout");
 
 #include "sdrx_ctx.h"
+
+namespace {
+// kiss_fft's twiddles for nfft = 8192, then the display's Hann window (kSpecN floats), from the reference's own double
+// expressions: what k_spectrum and k_watch_psd read.
+std::vector<float2> spectrum_tables()
+{
+    std::vector<float2> tab((size_t)kSpecN + kSpecN / 2);
+    const double pi = 3.141592653589793238462643383279502884197169399375105820974944; // kiss_fft.c:355-363
+    for (int i = 0; i < kSpecN; ++i) {
+        const double phase = -2 * pi * i / kSpecN;
+        tab[(size_t)i] = make_float2((float)cos(phase), (float)sin(phase));
+    }
+    float *hann = reinterpret_cast<float *>(tab.data() + kSpecN); // mainwindow.cpp:284-287
+    for (int i = 0; i < kSpecN; ++i)
+        hann[i] = (float)(0.5 * (1.0 - cos(2 * SDRX_PI * ((float)i) / (kSpecN - 1.0))));
+    return tab;
+}
+} // namespace
+
 #include "sdrx_frame.hip"
 #include "sdrx_delivery.hip"
+#include "sdrx_watch.hip"
 #include "sdrx_finalize.hip"
 
 namespace {
@@ -106,6 +130,16 @@ void free_device_state(sdrx_ctx *c)
     dfree(c->park.d_jobs);
     c->park.jobs_cap = 0;
     c->sq.bytes = c->sq.dir_off = c->sq.pack_bytes = c->sq.hpack_off = 0;
+    // channel watch: as before the first sdrx_set_watch
+    dfree(c->watch.d_desc);
+    dfree(c->watch.d_data);
+    dfree(c->watch.d_tw);
+    for (int p = 0; p < 2; ++p) {
+        dfree(c->watch.d_rec[p]);
+        if (c->watch.h_rec[p])
+            (void)hipHostFree(c->watch.h_rec[p]);
+    }
+    c->watch = sdrx_ctx::Watch();
 }
 
 } // namespace
@@ -236,6 +270,8 @@ int sdrx_set_option(sdrx_ctx *c, const char *name, int value)
         c->opt_squelch_auto = value != 0;
     else if (!strcmp(name, "park"))
         c->opt_park = value != 0;
+    else if (!strcmp(name, "watch"))
+        c->opt_watch = value != 0;
     else
         return fail(c, SDRX_EINVAL, "unknown option '%s'", name);
     return SDRX_OK;
@@ -566,7 +602,7 @@ int apply_vfo_jobs(sdrx_ctx *c, const int *ids, const double *freqs, const float
             nd.d.gain = gains[k];
         }
     }
-    return SDRX_OK;
+    return freqs ? watch_retuned(c, ids, n) : SDRX_OK; // (a watched leaf's band follows its mixer)
 }
 
 int set_vfo_values(sdrx_ctx *c, const int *ids, const double *freqs, const float *gains, int n, const char *what)
@@ -877,15 +913,7 @@ int sdrx_set_spectrum(sdrx_ctx *c, int id, int enable)
         return rc;
     const int slot = id < 0 ? N : id;
     if (c->spec.slots.empty()) { // the first spectrum: tables (the reference's own double expressions) and per-slot records
-        std::vector<float2> tab((size_t)kSpecN + kSpecN / 2);
-        const double pi = 3.141592653589793238462643383279502884197169399375105820974944; // kiss_fft.c:355-363
-        for (int i = 0; i < kSpecN; ++i) {
-            const double phase = -2 * pi * i / kSpecN;
-            tab[(size_t)i] = make_float2((float)cos(phase), (float)sin(phase));
-        }
-        float *hann = reinterpret_cast<float *>(tab.data() + kSpecN); // mainwindow.cpp:284-287
-        for (int i = 0; i < kSpecN; ++i)
-            hann[i] = (float)(0.5 * (1.0 - cos(2 * SDRX_PI * ((float)i) / (kSpecN - 1.0))));
+        const std::vector<float2> tab = spectrum_tables();
         HIPCHK(c, hipMalloc(&c->spec.d_tw, sizeof(float2) * tab.size()));
         HIPCHK(c, hipMemcpy(c->spec.d_tw, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
         HIPCHK(c, hipMalloc(&c->spec.d_rec, sizeof(SpecRecord) * (size_t)(N + 1)));
@@ -1068,7 +1096,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->exact = c->opt_exact;
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq.bytes + sizeof(int) * c->park.words);
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq.bytes + sizeof(int) * c->park.words + c->watch.bytes);
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

@@ -104,7 +104,7 @@ struct sdrx_ctx {
     int opt_exact = 1, opt_prequant = 0, opt_segments = 0, opt_dc_blocked = 0, opt_pipeline = 0, opt_dc_speculative = 1;
     int opt_fuse = 1, opt_frame_pipeline = 1, opt_fuse_late = 1, opt_keep_streams = 0, opt_fuse_demod = 0;
     int opt_tail_in_levels = 1;
-    int opt_meter = 0, opt_squelch = 0, opt_preroll = 0, opt_squelch_auto = 0, opt_park = 0;
+    int opt_meter = 0, opt_squelch = 0, opt_preroll = 0, opt_squelch_auto = 0, opt_park = 0, opt_watch = 0;
     // option meter: per frame parity, behind the payloads in d_pay / h_pay (at meter_off), one 16-byte MeterAcc record per work
     // unit that emits payload values (kernels.hip "output meters"); the records travel in the payload copy
     size_t meter_off = 0;
@@ -171,6 +171,43 @@ struct sdrx_ctx {
             return !(frame >= L.since ? L.active : L.was_active);
         }
     } park;
+
+    // Option watch (sdrx_set_watch, watch.hip).  Host bookkeeping per leaf as option park keeps it: a frame
+    // f >= since ran with the leaf in state `on`, the frames before it in state `was_on`.  Everything on the device is allocated
+    // by the first sdrx_set_watch that switches a leaf on; with no source measured the frame sequence launches nothing more.
+    // The records of frame f are written to d_rec[f & 1] -- one slot per leaf -- and travel to h_rec[f & 1] with the frame's
+    // fixed-size part (queue_watch, sdrx_delivery.hip).
+    struct Watch {
+        struct Leaf {
+            int on = 0, was_on = 0;
+            unsigned long long since = 0;
+            int first_bin = 0, n_bins = 1; // the band (watch_band), as the descriptor stands
+            int slot = -1;                 // its record (leaves in node order; -1: not a leaf)
+        };
+        std::vector<Leaf> leaf; // per node; sized by the first watch call
+        int n_slots = 0;
+        unsigned char *d_desc = nullptr; // WatchSrc[src_cap] | WatchSeg[kWatchMaxSeg src_cap] | WatchLeaf[n_slots]
+        int src_cap = 0;
+        unsigned char *d_data = nullptr; // per measured source: P[S][kSpecN] f32 | PSD[kSpecN] + total f64 | done u32
+        size_t data_cap = 0;
+        float2 *d_tw = nullptr;          // kiss_fft's twiddles, then the Hann window (as Spectrum::d_tw)
+        WatchRecord *d_rec[2] = {nullptr, nullptr}, *h_rec[2] = {nullptr, nullptr};
+        size_t bytes = 0;                // device memory the option holds
+        std::vector<int> src_ids;        // the measured sources in launch order: -1 the raw frame, else the parent's node id
+        std::vector<size_t> src_psd;     // ... where each one's PSD lies in d_data
+        std::vector<int> seg_begin, leaf_begin; // per source group (0: the raw frame, 1 + l: parents on tree level l), n_levels + 2 entries
+        unsigned long long psd_since = 0; // the PSD buffers hold a frame only once frame_no > psd_since
+        WatchSrc *d_src() const { return reinterpret_cast<WatchSrc *>(d_desc); }
+        WatchSeg *d_seg() const { return reinterpret_cast<WatchSeg *>(d_desc + sizeof(WatchSrc) * (size_t)src_cap); }
+        WatchLeaf *d_leaf() const { return reinterpret_cast<WatchLeaf *>(d_desc + (sizeof(WatchSrc) + sizeof(WatchSeg) * kWatchMaxSeg) * (size_t)src_cap); }
+        bool watched_at(int id, unsigned long long frame) const
+        {
+            if (leaf.empty())
+                return false;
+            const Leaf &L = leaf[(size_t)id];
+            return (frame >= L.since ? L.on : L.was_on) != 0;
+        }
+    } watch;
 
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first

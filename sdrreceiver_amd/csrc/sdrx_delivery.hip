@@ -77,14 +77,25 @@ void publish_all(sdrx_ctx *c, int slot)
 //      d_pack[p] goes to h_pay[p] + hpack_off, in ONE copy (none if every leaf is closed); without squelch the whole of d_pay[p].
 // Both only read d_pay[p], d_pack[p] and the directory, whose next writer is frame f+2 (the safety argument above
 // enqueue_frame, sdrx_frame.hip).
+// Option watch: the records of the frame of parity p, part of what always travels (nothing before the first sdrx_set_watch)
+int queue_watch(sdrx_ctx *c, int p, hipStream_t st)
+{
+    if (c->watch.d_rec[p])
+        HIPCHK(c, hipMemcpyAsync(c->watch.h_rec[p], c->watch.d_rec[p], sizeof(WatchRecord) * (size_t)c->watch.n_slots, hipMemcpyDeviceToHost, st));
+    return SDRX_OK;
+}
 int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st)
 {
+    if (int rc = queue_watch(c, p, st))
+        return rc;
     HIPCHK(c, hipMemcpyAsync(c->h_pay[p] + c->meter_off, c->d_pay[p] + c->meter_off, c->pay_bytes - c->meter_off, hipMemcpyDeviceToHost, st));
     return SDRX_OK;
 }
 int queue_payloads(sdrx_ctx *c, int p, hipStream_t st)
 {
     if (!c->opt_squelch) {
+        if (int rc = queue_watch(c, p, st))
+            return rc;
         HIPCHK(c, hipMemcpyAsync(c->h_pay[p], c->d_pay[p], c->pay_bytes, hipMemcpyDeviceToHost, st));
         return SDRX_OK;
     }

@@ -139,6 +139,46 @@ void spectrum_raw_step(sdrx_ctx *c, const void *raw, int raw_mode)
     hipLaunchKernelGGL(k_spectrum, dim3(1), dim3(kSpecThreads), 0, c->st.stream, c->spec.d_desc + c->spec.n_desc, A, c->spec.d_tw, hann);
 }
 
+// Option watch: the sources of groups g_lo..g_hi (0: the raw frame, 1 + l: the streams of tree level l) that have a watched
+// leaf -- one k_watch_psd workgroup per (source, segment), then one k_watch_bands wave per watched leaf of those sources.
+// Not bracketed: sdrx_get_kernel_times keeps its SDRX_NKERNELS kinds.  Nothing watched: nothing is launched.
+void watch_launch_groups(sdrx_ctx *c, hipStream_t st, int g_lo, int g_hi, const WatchArgs &A)
+{
+    const sdrx_ctx::Watch &W = c->watch;
+    const int s0 = W.seg_begin[(size_t)g_lo], s1 = W.seg_begin[(size_t)g_hi + 1];
+    const int l0 = W.leaf_begin[(size_t)g_lo], l1 = W.leaf_begin[(size_t)g_hi + 1];
+    if (s1 <= s0 || l1 <= l0)
+        return;
+    const float *hann = reinterpret_cast<const float *>(W.d_tw + kSpecN);
+    hipLaunchKernelGGL(k_watch_psd, dim3(s1 - s0), dim3(kSpecThreads), 0, st, W.d_src(), W.d_seg() + s0, A, W.d_tw, hann);
+    const int per = kWatchLeafThreads / 64;
+    hipLaunchKernelGGL(k_watch_bands, dim3((l1 - l0 + per - 1) / per), dim3(kWatchLeafThreads), 0, st, W.d_src(), W.d_leaf() + l0, l1 - l0, A, W.d_rec[0],
+                       W.d_rec[1]);
+}
+// ... of the VFO streams of tree levels lo..hi, where spectrum_launch reads them (the same frames per level)
+void watch_launch(sdrx_ctx *c, hipStream_t st, int lo, int hi, unsigned long long f, const unsigned long long *frames)
+{
+    if (c->watch.src_ids.empty())
+        return;
+    WatchArgs A;
+    memset(&A, 0, sizeof A);
+    for (int l = 0; l < kMaxLevels; ++l)
+        A.frame_level[l] = frames ? frames[l] : f;
+    watch_launch_groups(c, st, 1 + lo, 1 + hi, A);
+}
+// ... and of the raw frame, where spectrum_raw_step reads it: first in the frame's own sequence
+void watch_raw_step(sdrx_ctx *c, const void *raw, int raw_mode)
+{
+    if (c->watch.src_ids.empty())
+        return;
+    WatchArgs A;
+    memset(&A, 0, sizeof A);
+    A.raw = raw_mode == kRawTiled ? static_cast<const void *>(c->d_raw_tiled) : raw;
+    A.raw_mode = raw_mode;
+    A.frame_raw = c->frame_no;
+    watch_launch_groups(c, c->st.stream, 0, 0, A);
+}
+
 // Option squelch: the gate of frame `frame`, on the stream -- and behind the launch -- that completed its payloads and meter
 // records: decide + scan (one workgroup), then the gather of the open leaves into d_pack[p] (squelch.hip).  Not bracketed:
 // sdrx_get_kernel_times keeps its SDRX_NKERNELS kinds.  PRE (option preroll): the two launches in their second form -- the gather
@@ -279,8 +319,10 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
                 launch_block_kernel(c, L, c->st.stream, f_dm);
     if (dm) // that launch completed frame f_dm's payloads and records: its gate
         squelch_gate(c, c->st.stream, f_dm);
-    if (hi >= 0)
+    if (hi >= 0) {
         spectrum_launch(c, c->st.stream, lo, hi, 0, A.frame_level);
+        watch_launch(c, c->st.stream, lo, hi, 0, A.frame_level);
+    }
     if (dm)
         c->pipe.erase(c->pipe.begin());
     for (InFlight &q : c->pipe)
@@ -359,6 +401,7 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
     if (pipe && c->opt_preroll && c->sq.preroll_fused && c->st.tail_recorded[p ^ 1]) // the levels write d_pay[p], which the previous gate reads
         HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.ev_tail[p ^ 1], 0));
     spectrum_raw_step(c, raw, raw_mode);
+    watch_raw_step(c, raw, raw_mode);
     // A few parent-less VFOs (the reference's 2-3 mains) read the caller's frame as it is; a wide
     // level 0 (the flat workloads) is bandwidth bound and wants coalesced reads: one layout pass
     // natural order -> tile layout first.
@@ -415,6 +458,7 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         launch_block_kernel(c, L, ts, c->frame_no);
     squelch_gate(c, ts, c->frame_no);
     spectrum_launch(c, ts, 0, c->n_levels - 1, c->frame_no, nullptr);
+    watch_launch(c, ts, 0, c->n_levels - 1, c->frame_no, nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return fail(c, SDRX_EHIP, "kernel launch failed: %s", hipGetErrorString(e));

@@ -792,6 +792,86 @@ int sdrx_group_get_active(sdrx_group *g, const int *ids, int n, sdrx_active_stat
     return SDRX_OK;
 }
 
+// sdrx_set_watch over the whole tree, as sdrx_group_set_active: everything is checked before any member changes
+int sdrx_group_set_watch(sdrx_group *g, const int *ids, const int32_t *on, int n)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_set_watch before sdrx_group_finalize");
+    const size_t W = g->m.size();
+    for (size_t k = 0; k < W; ++k)
+        if (g->m[k].c && !g->m[k].c->opt_watch)
+            return gfail(g, SDRX_ESTATE, "sdrx_group_set_watch: option \"watch\" is off");
+    if (n < 0 || (n > 0 && (!ids || !on)))
+        return gfail(g, SDRX_EINVAL, "sdrx_group_set_watch: n = %d", n);
+    std::vector<char> seen(g->descs.size(), 0);
+    for (int k = 0; k < n; ++k) {
+        if (int rc = group_check_ids(g, "sdrx_group_set_watch", ids + k, 1))
+            return rc;
+        const auto w = g->where[(size_t)ids[k]];
+        if (!g->m[(size_t)w.first].c->nodes[(size_t)w.second].leaf)
+            return gfail(g, SDRX_EINVAL, "sdrx_group_set_watch: vfo %d has children and publishes nothing", ids[k]);
+        if (seen[(size_t)ids[k]]++)
+            return gfail(g, SDRX_EINVAL, "sdrx_group_set_watch: vfo %d listed twice", ids[k]);
+        if (on[k] != 0 && on[k] != 1)
+            return gfail(g, SDRX_EINVAL, "sdrx_group_set_watch: vfo %d: on = %d (0 or 1)", ids[k], on[k]);
+    }
+    if (g->broken)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_set_watch: an earlier frame failed on one member");
+    if (g->in_flight > 0)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_set_watch: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
+    std::vector<std::vector<int>> lids(W);
+    std::vector<std::vector<int32_t>> ov(W);
+    for (int k = 0; k < n; ++k) {
+        const auto w = g->where[(size_t)ids[k]];
+        lids[(size_t)w.first].push_back(w.second);
+        ov[(size_t)w.first].push_back(on[k]);
+    }
+    for (size_t k = 0; k < W; ++k) {
+        if (lids[k].empty())
+            continue;
+        const int rc = sdrx_set_watch(g->m[k].c, lids[k].data(), ov[k].data(), (int)lids[k].size());
+        if (rc)
+            return member_fail(g, (int)k, rc);
+    }
+    return SDRX_OK;
+}
+
+int sdrx_group_get_watch(sdrx_group *g, const int *ids, int n, sdrx_watch_level *out)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_watch before sdrx_group_finalize");
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return gfail(g, SDRX_EINVAL, "sdrx_group_get_watch: n = %d", n);
+    if (int rc = group_check_ids(g, "sdrx_group_get_watch", ids, n)) // the whole list first: nothing is written for a bad one
+        return rc;
+    for (int k = 0; k < n; ++k) {
+        const auto w = g->where[(size_t)ids[k]];
+        const int rc = sdrx_get_watch(g->m[(size_t)w.first].c, &w.second, 1, out + k);
+        if (rc)
+            return member_fail(g, w.first, rc);
+    }
+    return SDRX_OK;
+}
+
+int sdrx_group_get_watch_psd(sdrx_group *g, int leaf_id, double *psd, int64_t *frame)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_watch_psd before sdrx_group_finalize");
+    if (int rc = group_check_ids(g, "sdrx_group_get_watch_psd", &leaf_id, 1))
+        return rc;
+    if (g->in_flight > 0)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_watch_psd: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
+    const auto w = g->where[(size_t)leaf_id];
+    const int rc = sdrx_get_watch_psd(g->m[(size_t)w.first].c, w.second, psd, frame);
+    return rc ? member_fail(g, w.first, rc) : SDRX_OK;
+}
+
 int sdrx_group_get_egress(sdrx_group *g, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied)
 {
     if (!g)

@@ -1,0 +1,298 @@
+// sdrx_watch.hip -- host side of option "watch" (include/sdrx.h "Channel watch", watch.hip): a leaf's band, the
+// launch lists of the measured sources, and the ABI calls.  The launches themselves sit in the frame sequence
+// (watch_launch / watch_raw_step, sdrx_frame.hip), the records' way to the host in sdrx_delivery.hip (queue_watch).
+// A fragment of sdrx.hip's translation unit.
+
+namespace {
+
+// The band of a leaf in bins of its source's 8192-point spectrum: include/sdrx.h, in IEEE double.
+void watch_band(const sdrx_vfo_desc &d, int *first_bin, int *n_bins)
+{
+    const double f = d.mixer_freq_hz, fs = (double)d.fs;
+    const double R = fs / (double)(1 << d.decimate_count);
+    double lo, hi;
+    if (d.demod_usb) {
+        const double R_out = d.late_decimate == 5 || d.late_decimate == 6 ? R / (double)d.late_decimate : R;
+        double B = d.filter_bw_hz > 0 ? (double)d.filter_bw_hz : R_out / 2;
+        if (B > R_out / 2)
+            B = R_out / 2;
+        lo = -f;
+        hi = -f + B;
+    } else {
+        lo = -f - R / 2;
+        hi = -f + R / 2;
+    }
+    const long long k_lo = (long long)std::ceil(lo * 8192.0 / fs), k_hi = (long long)std::floor(hi * 8192.0 / fs);
+    const long long nb = std::min<long long>(std::max<long long>(k_hi - k_lo + 1, 1), kSpecN);
+    *n_bins = (int)nb;
+    *first_bin = (int)(((k_lo % kSpecN) + kSpecN) % kSpecN);
+}
+
+// host bookkeeping of every leaf (no device memory): by the first watch call of a finalized context
+void watch_host_init(sdrx_ctx *c)
+{
+    sdrx_ctx::Watch &W = c->watch;
+    if (!W.leaf.empty())
+        return;
+    W.leaf.assign(c->nodes.size(), sdrx_ctx::Watch::Leaf());
+    W.n_slots = 0;
+    for (size_t id = 0; id < c->nodes.size(); ++id) {
+        if (!c->nodes[id].leaf)
+            continue;
+        W.leaf[id].slot = W.n_slots++;
+        watch_band(c->nodes[id].d, &W.leaf[id].first_bin, &W.leaf[id].n_bins);
+    }
+    W.seg_begin.assign((size_t)c->n_levels + 2, 0);
+    W.leaf_begin.assign((size_t)c->n_levels + 2, 0);
+}
+
+int watch_segments(int n) { return std::min(std::max(n / kSpecN, 1), kWatchMaxSeg); }
+
+// The launch lists for the present selection, uploaded whenever it or a watched leaf's band changes.  Synchronous: never inside
+// a frame call, and the context is drained.  The sources in launch order: the raw frame, then the parents by tree level.
+int watch_rebuild(sdrx_ctx *c)
+{
+    sdrx_ctx::Watch &W = c->watch;
+    const int N = (int)c->nodes.size();
+    std::vector<char> measured((size_t)N + 1, 0); // [0]: the raw frame, [1 + id]: the stream of node id
+    bool any = false;
+    for (int id = 0; id < N; ++id)
+        if (W.leaf[(size_t)id].on) {
+            measured[(size_t)(1 + c->nodes[(size_t)id].d.parent_id)] = 1;
+            any = true;
+        }
+    if (!any && !W.d_desc) // nothing was ever switched on: nothing is allocated
+        return SDRX_OK;
+    if (!W.d_desc) {
+        int parents = 0;
+        for (const Node &n : c->nodes)
+            parents += !n.leaf;
+        W.src_cap = parents + 1;
+        const size_t desc_bytes = (sizeof(WatchSrc) + sizeof(WatchSeg) * kWatchMaxSeg) * (size_t)W.src_cap + sizeof(WatchLeaf) * (size_t)W.n_slots;
+        const size_t rec_bytes = sizeof(WatchRecord) * (size_t)W.n_slots;
+        const std::vector<float2> tab = spectrum_tables();
+        HIPCHK(c, hipMalloc(&W.d_desc, desc_bytes));
+        HIPCHK(c, hipMalloc(&W.d_tw, sizeof(float2) * tab.size()));
+        HIPCHK(c, hipMemcpy(W.d_tw, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
+        for (int p = 0; p < 2; ++p) {
+            HIPCHK(c, hipMalloc(&W.d_rec[p], rec_bytes));
+            HIPCHK(c, hipMemset(W.d_rec[p], 0, rec_bytes));
+            HIPCHK(c, hipHostMalloc(&W.h_rec[p], rec_bytes, hipHostMallocDefault));
+            memset(W.h_rec[p], 0, rec_bytes);
+        }
+        W.bytes = desc_bytes + sizeof(float2) * tab.size() + 2 * rec_bytes;
+    }
+    // the measured sources, by group, and where each one's buffers lie
+    std::vector<int> ids;
+    std::vector<WatchSrc> srcs;
+    std::vector<WatchSeg> segs;
+    std::vector<size_t> off_P, off_psd, off_done;
+    std::vector<int> src_index((size_t)N + 1, -1);
+    size_t need = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = align_up(need, 256);
+        need = o + bytes;
+        return o;
+    };
+    for (int g = 0; g <= c->n_levels; ++g) {
+        W.seg_begin[(size_t)g] = (int)segs.size();
+        for (int id = -1; id < N; ++id) {
+            if (!measured[(size_t)(1 + id)] || (id < 0 ? g != 0 : c->nodes[(size_t)id].level != g - 1))
+                continue;
+            WatchSrc e;
+            memset(&e, 0, sizeof e);
+            e.n = id < 0 ? c->root_frame : c->nodes[(size_t)id].n_f;
+            e.S = watch_segments(e.n);
+            e.level = id < 0 ? -1 : std::min(g - 1, kMaxLevels - 1); // (only the frame pipeline, at most kMaxLevels deep, has frames per level)
+            if (id >= 0)
+                for (int p = 0; p < 2; ++p)
+                    e.src[p] = reinterpret_cast<const float2 *>(c->arena + c->nodes[(size_t)id].off_stream[p]);
+            src_index[(size_t)(1 + id)] = (int)srcs.size();
+            for (int s = 0; s < e.S; ++s)
+                segs.push_back(WatchSeg{(int)srcs.size(), s});
+            off_P.push_back(take(sizeof(float) * (size_t)e.S * kSpecN));
+            off_psd.push_back(take(sizeof(double) * ((size_t)kSpecN + 1)));
+            off_done.push_back(take(sizeof(unsigned)));
+            ids.push_back(id);
+            srcs.push_back(e);
+        }
+    }
+    W.seg_begin[(size_t)c->n_levels + 1] = (int)segs.size();
+    if (ids != W.src_ids || need > W.data_cap) { // the buffers move: what they held is gone
+        if (need > W.data_cap) {
+            if (W.d_data)
+                (void)hipFree(W.d_data);
+            W.d_data = nullptr;
+            W.bytes -= W.data_cap;
+            W.data_cap = 0;
+            HIPCHK(c, hipMalloc(&W.d_data, need));
+            W.data_cap = need;
+            W.bytes += need;
+        }
+        if (W.d_data)
+            HIPCHK(c, hipMemset(W.d_data, 0, W.data_cap));
+        W.psd_since = c->frame_no;
+    }
+    W.src_psd = off_psd;
+    for (size_t k = 0; k < srcs.size(); ++k) {
+        srcs[k].P = reinterpret_cast<float *>(W.d_data + off_P[k]);
+        srcs[k].psd = reinterpret_cast<double *>(W.d_data + off_psd[k]);
+        srcs[k].done = reinterpret_cast<unsigned *>(W.d_data + off_done[k]);
+    }
+    // the watched leaves in the order of their sources
+    std::vector<WatchLeaf> leaves;
+    for (int g = 0; g <= c->n_levels; ++g) {
+        W.leaf_begin[(size_t)g] = (int)leaves.size();
+        for (int id = 0; id < N; ++id) {
+            const sdrx_ctx::Watch::Leaf &L = W.leaf[(size_t)id];
+            const int parent = c->nodes[(size_t)id].d.parent_id;
+            if (!L.on || (parent < 0 ? g != 0 : c->nodes[(size_t)parent].level != g - 1))
+                continue;
+            leaves.push_back(WatchLeaf{src_index[(size_t)(1 + parent)], L.first_bin, L.n_bins, L.slot});
+        }
+    }
+    W.leaf_begin[(size_t)c->n_levels + 1] = (int)leaves.size();
+    if (!srcs.empty()) {
+        HIPCHK(c, hipMemcpy(W.d_src(), srcs.data(), sizeof(WatchSrc) * srcs.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(W.d_seg(), segs.data(), sizeof(WatchSeg) * segs.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(W.d_leaf(), leaves.data(), sizeof(WatchLeaf) * leaves.size(), hipMemcpyHostToDevice));
+    }
+    W.src_ids = ids; // (last: the frame sequence launches from these lists only when everything above succeeded)
+    return SDRX_OK;
+}
+
+// sdrx_set_mixer_freqs has changed the descriptors of `ids` (the context is drained): the bands follow
+int watch_retuned(sdrx_ctx *c, const int *ids, int n)
+{
+    sdrx_ctx::Watch &W = c->watch;
+    if (!c->opt_watch || W.leaf.empty())
+        return SDRX_OK;
+    bool any = false;
+    for (int k = 0; k < n; ++k) {
+        sdrx_ctx::Watch::Leaf &L = W.leaf[(size_t)ids[k]];
+        if (L.slot < 0)
+            continue;
+        watch_band(c->nodes[(size_t)ids[k]].d, &L.first_bin, &L.n_bins);
+        any |= L.on != 0;
+    }
+    return any ? watch_rebuild(c) : SDRX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sdrx_set_watch(sdrx_ctx *c, const int *ids, const int32_t *on, int n)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_set_watch before sdrx_finalize");
+    if (!c->opt_watch)
+        return fail(c, SDRX_ESTATE, "sdrx_set_watch: option \"watch\" is off");
+    if (n < 0 || (n > 0 && (!ids || !on)))
+        return fail(c, SDRX_EINVAL, "sdrx_set_watch: n = %d, ids %p, on %p", n, (const void *)ids, (const void *)on);
+    if (int rc = check_leaf_ids(c, "sdrx_set_watch", ids, n, true))
+        return rc;
+    for (int k = 0; k < n; ++k)
+        if (on[k] != 0 && on[k] != 1)
+            return fail(c, SDRX_EINVAL, "sdrx_set_watch: vfo %d: on = %d (0 or 1)", ids[k], on[k]);
+    if (c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "sdrx_set_watch: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+    if (n == 0)
+        return SDRX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c)) // frames inside the software pipeline finish with the old selection
+        return rc;
+    watch_host_init(c);
+    sdrx_ctx::Watch &W = c->watch;
+    const std::vector<sdrx_ctx::Watch::Leaf> before = W.leaf;
+    bool changed = false;
+    for (int k = 0; k < n; ++k) {
+        sdrx_ctx::Watch::Leaf &L = W.leaf[(size_t)ids[k]];
+        if (L.on == on[k])
+            continue;
+        if (L.since != c->frame_no) // (a second change before the same frame: the frames before it ran in the state they ran in)
+            L.was_on = L.on;
+        L.on = on[k];
+        L.since = c->frame_no;
+        changed = true;
+    }
+    if (!changed)
+        return SDRX_OK;
+    const int rc = watch_rebuild(c);
+    if (rc) { // the lists on the device are the old ones (W.src_ids is set last): so is the selection
+        W.leaf = before;
+        return rc;
+    }
+    return SDRX_OK;
+}
+
+int sdrx_get_watch(sdrx_ctx *c, const int *ids, int n, sdrx_watch_level *out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_watch before sdrx_finalize");
+    if (!c->opt_watch)
+        return fail(c, SDRX_ESTATE, "sdrx_get_watch: option \"watch\" is off");
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return fail(c, SDRX_EINVAL, "sdrx_get_watch: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
+    if (int rc = check_leaf_ids(c, "sdrx_get_watch", ids, n, false))
+        return rc;
+    if (n == 0)
+        return SDRX_OK;
+    if (int rc = need_delivered(c, "sdrx_get_watch"))
+        return rc;
+    watch_host_init(c);
+    const sdrx_ctx::Watch &W = c->watch;
+    for (int k = 0; k < n; ++k) {
+        const sdrx_ctx::Watch::Leaf &L = W.leaf[(size_t)ids[k]];
+        sdrx_watch_level r;
+        memset(&r, 0, sizeof r);
+        if (W.h_rec[c->host_slot] && W.watched_at(ids[k], c->host_frame)) {
+            memcpy(&r, W.h_rec[c->host_slot] + L.slot, sizeof r);
+        } else {
+            r.first_bin = L.first_bin;
+            r.n_bins = L.n_bins;
+        }
+        r.frame = (int64_t)c->host_frame;
+        out[k] = r;
+    }
+    return SDRX_OK;
+}
+
+int sdrx_get_watch_psd(sdrx_ctx *c, int leaf_id, double *psd, int64_t *frame)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_watch_psd before sdrx_finalize");
+    if (!c->opt_watch)
+        return fail(c, SDRX_ESTATE, "sdrx_get_watch_psd: option \"watch\" is off");
+    if (int rc = check_leaf_ids(c, "sdrx_get_watch_psd", &leaf_id, 1, false))
+        return rc;
+    const sdrx_ctx::Watch &W = c->watch;
+    if (W.leaf.empty() || !W.leaf[(size_t)leaf_id].on)
+        return fail(c, SDRX_EINVAL, "sdrx_get_watch_psd: vfo %d is not watched (sdrx_set_watch)", leaf_id);
+    if (c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "sdrx_get_watch_psd: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c))
+        return rc;
+    if (c->frame_no <= std::max(W.psd_since, W.leaf[(size_t)leaf_id].since))
+        return fail(c, SDRX_ESTATE, "sdrx_get_watch_psd: no frame has been measured for vfo %d yet", leaf_id);
+    const int parent = c->nodes[(size_t)leaf_id].d.parent_id;
+    size_t k = 0;
+    while (k < W.src_ids.size() && W.src_ids[k] != parent)
+        ++k;
+    if (k == W.src_ids.size())
+        return fail(c, SDRX_EHIP, "sdrx_get_watch_psd: the source of vfo %d is not in the launch list", leaf_id);
+    if (psd)
+        HIPCHK(c, hipMemcpy(psd, W.d_data + W.src_psd[k], sizeof(double) * kSpecN, hipMemcpyDeviceToHost));
+    if (frame)
+        *frame = (int64_t)c->frame_no - 1;
+    return SDRX_OK;
+}
+
+} // extern "C"

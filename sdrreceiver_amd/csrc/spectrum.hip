@@ -69,41 +69,43 @@ __device__ __forceinline__ int spec_digit_rev(int n)
     return (r << 1) | n;
 }
 
-__global__ __launch_bounds__(kSpecThreads) void k_spectrum(const SpecDesc *__restrict__ descs, SpecArgs A,
-                                                           const float2 *__restrict__ tw, const float *__restrict__ hann)
-{
-    __shared__ float2 F[kSpecN];
-    __shared__ double red_max[kSpecThreads / 64], red_sum[kSpecThreads / 64];
-    const SpecDesc &D = descs[blockIdx.x]; // (read in place: a dynamically indexed private copy would live in scratch)
-    const int tid = threadIdx.x;
-    int kind = D.kind;
+// One stream as k_spectrum and k_watch_psd (watch.hip) read it: natural order or tile layout cf32, or dongle bytes.
+struct SpecSource {
     const float2 *src = nullptr;
     const unsigned char *bytes = nullptr;
-    if (kind == kSpecRaw) {
-        if (A.raw_mode == kRawU8)
-            bytes = static_cast<const unsigned char *>(A.raw);
-        else
-            src = static_cast<const float2 *>(A.raw);
-        kind = A.raw_mode == kRawTiled ? kSpecTiled : kSpecNatural;
-    } else {
-        unsigned long long f = A.frame_level[0]; // (a select chain, not a dynamic index into the kernel argument)
+    bool tiled = false;
+};
+__device__ __forceinline__ SpecSource spec_raw_source(const void *raw, int raw_mode)
+{
+    SpecSource S;
+    if (raw_mode == kRawU8)
+        S.bytes = static_cast<const unsigned char *>(raw);
+    else
+        S.src = static_cast<const float2 *>(raw);
+    S.tiled = raw_mode == kRawTiled;
+    return S;
+}
+// the frame that tree level `level` holds in this launch (a select chain, not a dynamic index into the kernel argument)
+__device__ __forceinline__ unsigned long long spec_level_frame(const unsigned long long (&frame_level)[kMaxLevels], int level)
+{
+    unsigned long long f = frame_level[0];
 #pragma unroll
-        for (int l = 1; l < kMaxLevels; ++l)
-            f = D.level == l ? A.frame_level[l] : f;
-        src = D.src[f & 1ull];
-    }
-    const int n_in = D.n_in;
-    auto input = [&](int a) -> float2 {
-        if (a >= n_in)
-            return make_float2(0.f, 0.f);
-        float2 x;
-        if (bytes) // floats[b] = b - 127, jonti/sdr.cpp:43-49
-            x = make_float2((float)((int)bytes[2 * a] - 127), (float)((int)bytes[2 * a + 1] - 127));
-        else
-            x = src[kind == kSpecTiled ? spec_tiled_index(a) : a];
-        const float h = hann[a];
-        return make_float2(x.x * h, x.y * h);
-    };
+    for (int l = 1; l < kMaxLevels; ++l)
+        f = level == l ? frame_level[l] : f;
+    return f;
+}
+__device__ __forceinline__ float2 spec_sample(const SpecSource &S, int g)
+{
+    if (S.bytes) // floats[b] = b - 127, jonti/sdr.cpp:43-49
+        return make_float2((float)((int)S.bytes[2 * g] - 127), (float)((int)S.bytes[2 * g + 1] - 127));
+    return S.src[S.tiled ? spec_tiled_index(g) : g];
+}
+
+// kiss_fft of the kSpecN windowed samples input(0..kSpecN-1) into F (LDS, natural output order), by one workgroup of
+// kSpecThreads threads; ends behind a barrier.
+template <class Input>
+__device__ __forceinline__ void spec_fft(float2 *F, Input input, const float2 *__restrict__ tw, int tid)
+{
     // window + digit-reversed store, with the innermost stage (kf_bfly2, m = 1: the pair n, n + N/2 lands side by side) done
     // in registers on the way
     const float2 w0 = tw[0];
@@ -139,6 +141,33 @@ __global__ __launch_bounds__(kSpecThreads) void k_spectrum(const SpecDesc *__res
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(kSpecThreads) void k_spectrum(const SpecDesc *__restrict__ descs, SpecArgs A,
+                                                           const float2 *__restrict__ tw, const float *__restrict__ hann)
+{
+    __shared__ float2 F[kSpecN];
+    __shared__ double red_max[kSpecThreads / 64], red_sum[kSpecThreads / 64];
+    const SpecDesc &D = descs[blockIdx.x]; // (read in place: a dynamically indexed private copy would live in scratch)
+    const int tid = threadIdx.x;
+    SpecSource S;
+    if (D.kind == kSpecRaw) {
+        S = spec_raw_source(A.raw, A.raw_mode);
+    } else {
+        S.src = D.src[spec_level_frame(A.frame_level, D.level) & 1ull];
+        S.tiled = D.kind == kSpecTiled;
+    }
+    const int n_in = D.n_in;
+    spec_fft(
+        F,
+        [&](int a) -> float2 {
+            if (a >= n_in)
+                return make_float2(0.f, 0.f);
+            const float2 x = spec_sample(S, a);
+            const float h = hann[a];
+            return make_float2(x.x * h, x.y * h);
+        },
+        tw, tid);
     // power, IIR, reductions (bin i feeds pwr[b], b = i + N/2 mod N: consecutive threads, consecutive doubles)
     double *pwr = D.pwr;
     float2 *bins = D.bins;

@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, meter, squelch as _squelch
+from . import _lib, meter, squelch as _squelch, watch as _watch
 from .topology import Topology, VfoDesc
 
 
@@ -54,7 +54,7 @@ class Receiver:
                  fuse_late: bool = True, keep_streams: bool = False, dc_speculative: bool = True,
                  dc_blocks_per_step: int | None = None, fuse_demod: bool = False,
                  tail_in_levels: bool = True, meter: bool = False, squelch: bool = False, preroll: bool = False,
-                 squelch_auto: bool = False, park: bool = False):
+                 squelch_auto: bool = False, park: bool = False, watch: bool = False):
         self.L = _lib.lib()
         h = C.c_void_p()
         rc = self.L.sdrx_create(C.byref(h), int(device))
@@ -85,6 +85,8 @@ class Receiver:
             self._chk(self.L.sdrx_set_option(self.h, b"squelch_auto", 1))
         if park:
             self._chk(self.L.sdrx_set_option(self.h, b"park", 1))
+        if watch:
+            self._chk(self.L.sdrx_set_option(self.h, b"watch", 1))
         self._chk(self.L.sdrx_set_option(self.h, b"dc_speculative", int(bool(dc_speculative))))
         if dc_blocks_per_step is not None:
             self._chk(self.L.sdrx_set_option(self.h, b"dc_blocks_per_step", int(dc_blocks_per_step)))
@@ -297,6 +299,29 @@ class Receiver:
         self._chk(self.L.sdrx_get_active(self.h, ids.ctypes.data, ids.size, out))
         return {"active": np.array([o.active for o in out[:ids.size]], dtype=np.int32),
                 "since_frame": np.array([o.since_frame for o in out[:ids.size]], dtype=np.int64)}
+
+    # -- channel watch (option ``watch``; sdrreceiver_amd.watch): band power of a leaf from its source's spectrum -------------
+    def set_watch(self, vids, on) -> None:
+        """Watch (``on[k]`` 1) or stop watching (0) the leaves `vids` from the next frame on, whether they are active or
+        parked."""
+        ids, val = _value_list(vids, on, np.int32)
+        self._chk(self.L.sdrx_set_watch(self.h, ids.ctypes.data, val.ctypes.data, ids.size))
+
+    def watch(self, vids) -> dict:
+        """Watch figures of the leaves `vids` for the last delivered frame: ``frame``, ``band_pwr``, ``total_pwr``,
+        ``first_bin``, ``n_bins``, ``segments``, ``watched`` as arrays in the order of `vids`."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        out = (_lib.WatchLevelC * max(1, ids.size))()
+        self._chk(self.L.sdrx_get_watch(self.h, ids.ctypes.data, ids.size, out))
+        return _watch.watch_dict(out[:ids.size])
+
+    def watch_psd(self, vid: int) -> tuple[np.ndarray, int]:
+        """``(PSD, frame)``: the power spectrum (8192 float64, kiss_fft's natural order) of the source of watched leaf `vid`
+        after the last frame."""
+        psd = np.zeros(_lib.SPECTRUM_BINS, np.float64)
+        f = C.c_int64()
+        self._chk(self.L.sdrx_get_watch_psd(self.h, int(vid), psd.ctypes.data, C.byref(f)))
+        return psd, f.value
 
     def output_rate(self, vid: int) -> int:
         rate = C.c_uint32()
@@ -593,6 +618,25 @@ class Group:
         self._chk(self.L.sdrx_group_get_active(self.h, ids.ctypes.data, ids.size, out))
         return {"active": np.array([o.active for o in out[:ids.size]], dtype=np.int32),
                 "since_frame": np.array([o.since_frame for o in out[:ids.size]], dtype=np.int64)}
+
+    def set_watch(self, vids, on) -> None:
+        """:meth:`Receiver.set_watch` with ids of the whole tree (group option ``watch=1``)."""
+        ids, val = _value_list(vids, on, np.int32)
+        self._chk(self.L.sdrx_group_set_watch(self.h, ids.ctypes.data, val.ctypes.data, ids.size))
+
+    def watch(self, vids) -> dict:
+        """:meth:`Receiver.watch` with ids of the whole tree."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        out = (_lib.WatchLevelC * max(1, ids.size))()
+        self._chk(self.L.sdrx_group_get_watch(self.h, ids.ctypes.data, ids.size, out))
+        return _watch.watch_dict(out[:ids.size])
+
+    def watch_psd(self, vid: int) -> tuple[np.ndarray, int]:
+        """:meth:`Receiver.watch_psd` with an id of the whole tree, from the member that owns the leaf."""
+        psd = np.zeros(_lib.SPECTRUM_BINS, np.float64)
+        f = C.c_int64()
+        self._chk(self.L.sdrx_group_get_watch_psd(self.h, int(vid), psd.ctypes.data, C.byref(f)))
+        return psd, f.value
 
     def locate(self, vid: int) -> tuple[int, int]:
         m, l = C.c_int(), C.c_int()
