@@ -169,6 +169,11 @@ int sdrx_add_vfo(sdrx_ctx *ctx, const sdrx_vfo_desc *desc, int *id_out);
  *            device_bytes, payloads and callbacks, and the watch calls return SDRX_ESTATE.  1 is independent of "park", "meter"
  *            and "squelch"; until the first sdrx_set_watch switches a leaf on, device_bytes and the launches are those of 0
  *            (DESIGN.md section 4j).
+ *   "catchup" 0 (default) | 1: a leaf unparked with sdrx_set_active starts one frame back, on the frame the device still holds
+ *            (sdrx_get_catchup below); 1 implies "park" and "preroll", hence "squelch" and "meter".  0 changes nothing: the
+ *            same kernels, launches, device_bytes, payloads and callbacks, and sdrx_get_catchup returns SDRX_ESTATE.  With 1
+ *            and nothing caught up every frame is what "park" = 1 with "preroll" = 1 gives.  A
+ *            sdrx_finalize that fails leaves the options as they were set, as with "preroll".
  *   "dc_blocked_scan" 0|1 (default 0): how sdrx_process_u8 removes the DC bias.  0 = the
  *                 reference's sequentially rounded fp32 recurrence, bit for bit (below).  1 = the same linear filter as a
  *                 blocked parallel scan (~15 us): the true IIR response.  The reference's recurrence
@@ -411,6 +416,44 @@ typedef struct sdrx_active_state {
 } sdrx_active_state;
 int sdrx_set_active(sdrx_ctx *ctx, const int *ids, const int32_t *active, int n);
 int sdrx_get_active(sdrx_ctx *ctx, const int *ids, int n, sdrx_active_state *out);
+/* Unpark with catch-up (option "catchup" = 1): a woken leaf starts one frame back.  A parent writes decimate[d] of every frame
+ * into the buffer of that frame's parity whether or not a child is active, and after frame K-1 that stream stays untouched until
+ * frame K+1: what an unparked leaf needs for K-1 is still on the device.  The reference has no counterpart: this text is the
+ * definition.
+ *
+ * Let K be the index of the next frame.  A leaf named by sdrx_set_active with active = 1 (and parked until then) is CAUGHT UP
+ * when it has a parent (parent_id >= 0), K >= 1, and it was parked in frame K-1.  A caught-up leaf
+ *   - is a new vfo, with the descriptor as it stands (mixer frequency and gain last set), from frame K-1 on: its oscillator
+ *     starts fresh at sample 0 of frame K-1, and every state region is zero, as for any unparked leaf;
+ *   - runs frame K-1 before sdrx_set_active returns: mix, half-bands, late decimation, demodulation, long low-pass or compress on
+ *     its parent's decimate[d] of K-1, read where it lies, into the leaf's own buffers of that frame's parity (stream, filter
+ *     state, meter records, payload); frame K then continues from that state like any second frame;
+ *   - has the gate state of sdrx_finalize EXCEPT prev_open = 0.  No gate runs on K-1, so in frame K pre(K) = open(K): if the
+ *     leaf is open in K (always, with threshold 0) the delivered frame K carries its payload of K-1 first -- the callback is
+ *     invoked twice, sdrx_get_preroll gives it with *frame = K-1, sdrx_get_preroll_count and sdrx_get_egress count it.  With
+ *     a threshold > 0 and the leaf closed in K the caught-up payload is dropped; hang_frames does not help, because no gate has
+ *     run on it.  Read sdrx_get_catchup to know what it held.
+ * Leaves that are not caught up start at K exactly as without the option, with prev_open = 1: a leaf without a parent (the raw
+ * frame of K-1 may be the caller's memory), a leaf unparked at K = 0, and a leaf parked and unparked with no frame between (it
+ * was active in K-1 and delivered then: the restart).  Parking a caught-up leaf again before frame K discards the catch-up.
+ *
+ * Everything the host reports for frame K-1 stays "parked" for that leaf: sdrx_get_output and sdrx_get_meters of a K-1 still to
+ * be fetched (frames queued with sdrx_process_device), n_open, and sdrx_get_active's since_frame = K.  A spectrum or a watch is
+ * not updated by the catch-up; sdrx_get_stream keeps its rules (SDRX_ENOSTREAM until frame K has run).
+ * The catch-up is this form whatever "fuse", "frame_pipeline", "tail_in_levels" or "pipeline" are: sub-lists of the leaf's own
+ * work items through one k_mix_decimate launch per tree level and one launch per block kernel, uploaded with the call's jobs.
+ * The call still returns when the device has applied it: it costs about one frame's work of the woken leaves more.
+ *
+ * One frame, no more: a host that pipelines `submit(f+1); wait() -> f` reads the figures of f only after f+1 is submitted, must
+ * wait for f+1 before it may call sdrx_set_active, and so catches up f+1, not f.  The synchronous loop
+ * process(f) -> sdrx_get_watch -> sdrx_set_mixer_freqs / sdrx_set_active -> process(f+1) loses nothing of f.
+ *
+ * sdrx_get_catchup: per leaf the meter of the caught-up frame -- frame = K-1 and sum_sq, n_values, clipped, peak by the
+ * definition of sdrx_get_meters -- or frame = -1 and zeros if the leaf's present active state did not begin with a catch-up.
+ * sdrx_set_active copies the few records back itself, so this is host bookkeeping that can be read as soon as that call has
+ * returned: the host knows whether the burst was there before it spends frame K.  Calling rules of sdrx_get_active, except
+ * SDRX_ESTATE with the option off: a bad id, the id of a VFO with children or n < 0 is SDRX_EINVAL; n == 0 does nothing. */
+int sdrx_get_catchup(sdrx_ctx *ctx, const int *ids, int n, sdrx_meter *out);
 
 /* Channel watch (option "watch" = 1): what tells a host WHEN to unpark.  A parked leaf does no work and so has no meter, no
  * squelch observation and no spectrum; the watch measures the stream the leaf CONSUMES instead -- one power spectrum per source
@@ -455,7 +498,9 @@ int sdrx_get_active(sdrx_ctx *ctx, const int *ids, int n, sdrx_active_state *out
  * SDRX_EINVAL if the leaf is not watched.
  *
  * Latency: a carrier first seen in the figures of frame f can be heard from frame f + 1 at the earliest -- sdrx_set_active
- * needs every submitted frame delivered first, and the unparked leaf starts with empty filters. */
+ * needs every submitted frame delivered first, and the unparked leaf starts with empty filters.  With option "catchup" = 1 a
+ * leaf with a parent, unparked before frame f + 1, starts on frame f itself: the stream the watch measured is still on the
+ * device, and its payload of f is delivered in front of that of f + 1 (sdrx_get_catchup above). */
 #define SDRX_WATCH_MAX_SEGMENTS 16
 typedef struct sdrx_watch_level {
     int64_t frame;        /* frame of the source stream these figures were taken from */
@@ -616,6 +661,9 @@ int sdrx_group_get_squelch_auto(sdrx_group *grp, const int *ids, int n, sdrx_squ
  * owns the leaf; `since_frame` counts the group's frames. */
 int sdrx_group_set_active(sdrx_group *grp, const int *ids, const int32_t *active, int n);
 int sdrx_group_get_active(sdrx_group *grp, const int *ids, int n, sdrx_active_state *out);
+/* sdrx_get_catchup with ids of the whole tree (group option "catchup" = 1; sdrx_group_set_active is unchanged in form), each id
+ * routed to the member that owns the leaf, as sdrx_group_get_meters. */
+int sdrx_group_get_catchup(sdrx_group *grp, const int *ids, int n, sdrx_meter *out);
 /* sdrx_set_watch / sdrx_get_watch / sdrx_get_watch_psd with ids of the whole tree (group option "watch" = 1), each id routed to
  * the member that owns the leaf; each member measures the replicas of the source streams it holds. */
 int sdrx_group_set_watch(sdrx_group *grp, const int *ids, const int32_t *on, int n);

@@ -134,6 +134,8 @@ SYMBOLS = {
     "sdrx_get_active": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_group_set_active": (_i, [_vp, _vp, _vp, _i]),
     "sdrx_group_get_active": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_get_catchup": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_group_get_catchup": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_set_watch": (_i, [_vp, _vp, _vp, _i]),
     "sdrx_get_watch": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_get_watch_psd": (_i, [_vp, _i, _vp, C.POINTER(C.c_int64)]),

@@ -272,6 +272,8 @@ int sdrx_set_option(sdrx_ctx *c, const char *name, int value)
         c->opt_park = value != 0;
     else if (!strcmp(name, "watch"))
         c->opt_watch = value != 0;
+    else if (!strcmp(name, "catchup"))
+        c->opt_catchup = value != 0;
     else
         return fail(c, SDRX_EINVAL, "unknown option '%s'", name);
     return SDRX_OK;
@@ -365,7 +367,9 @@ int sdrx_finalize(sdrx_ctx *c)
     if (c->nodes.empty())
         return fail(c, SDRX_ESTATE, "sdrx_finalize: no VFOs");
     HIPCHK(c, hipSetDevice(c->device));
-    const int asked_squelch = c->opt_squelch, asked_meter = c->opt_meter;
+    const int asked_squelch = c->opt_squelch, asked_meter = c->opt_meter, asked_preroll = c->opt_preroll, asked_park = c->opt_park;
+    if (c->opt_catchup) // the caught-up frame of an unparked leaf leaves through the pre-roll path
+        c->opt_park = c->opt_preroll = 1;
     if (c->opt_preroll || c->opt_squelch_auto) // the pre-roll and the floor tracking are the gate's
         c->opt_squelch = 1;
     if (c->opt_squelch) // the gate reads the meter records
@@ -380,6 +384,8 @@ int sdrx_finalize(sdrx_ctx *c)
         c->publish_order.clear();
         c->opt_squelch = asked_squelch;
         c->opt_meter = asked_meter;
+        c->opt_preroll = asked_preroll;
+        c->opt_park = asked_park;
     }
     return rc;
 }
@@ -643,6 +649,12 @@ namespace {
 // leaf that is unparked also zeros over every filter-state region of both frame parities and the gate state of sdrx_finalize)
 // and, for an unparked leaf, one retune job with the rotation it has (a fresh Oscillator from the next frame on).  The
 // software pipeline is drained first; one upload, k_vfo_reset and k_vfo_retune, one synchronisation.
+// Option catchup: a leaf with a parent that was parked in frame K-1 (K = the next frame, K >= 1) starts at K-1 instead -- its
+// oscillator's origin is K-1 and prev_open = 0 -- and runs that frame behind the two launches: its own mix items in one
+// k_mix_decimate launch per tree level, then its own blocks of every block kernel, the sub-lists uploaded with the jobs.  They
+// read the parent's decimate[d] of K-1 where it lies (parity (K-1) & 1: untouched until frame K+1) and write the leaf's
+// ordinary buffers of that parity; the gate of K then pre-rolls the payload (pre = open && !prev_open).  The leaf's meter
+// records of K-1 come back before the call returns (sdrx_get_catchup).
 int apply_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
 {
     HIPCHK(c, hipSetDevice(c->device));
@@ -657,11 +669,15 @@ int apply_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
     };
     K1Vfo *k1 = reinterpret_cast<K1Vfo *>(c->arena + c->off_k1vfo);
     bool any_spectrum = false;
+    std::vector<int> caught; // option catchup: the leaves that start one frame back
     for (int k = 0; k < n; ++k) {
         const int id = ids[k];
         const Node &nd = c->nodes[(size_t)id];
         if (K.leaf[(size_t)id].active == active[k]) // already there: no reset
             continue;
+        const bool catch_up = c->opt_catchup && active[k] && nd.d.parent_id >= 0 && c->frame_no >= 1 && K.parked_at(id, c->frame_no - 1);
+        if (catch_up)
+            caught.push_back(id);
         const unsigned v = (unsigned)active[k];
         fill(K.d_act + id, 1, v);
         for (int it : K.items[(size_t)id]) // (k_mix_levels / k_levels_tail: the flag rides in the item's level word)
@@ -696,8 +712,8 @@ int apply_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
         }
         if (sq >= 0) { // the gate state of sdrx_finalize; thresholds, hang time, ratio and window stay
             fill(c->sq.d_hang + sq, 1, 0);
-            if (c->opt_preroll)
-                fill(c->sq.d_prev + sq, 1, 1);
+            if (c->opt_preroll) // (caught up: no gate ran on K-1, and the gate of K finds the leaf "closed before")
+                fill(c->sq.d_prev + sq, 1, catch_up ? 0u : 1u);
             if (c->opt_squelch_auto) {
                 fill(c->sq.d_auto + sq, 4, 0xffffffffu); // cur_min = prev_min = NONE
                 fill(reinterpret_cast<unsigned *>(c->sq.d_auto + sq) + 4, 1, 0); // age
@@ -710,11 +726,52 @@ int apply_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
         J.rot_re = nd.rot_re;
         J.rot_im = nd.rot_im;
         nco_powers(J.rot_re, J.rot_im, J.rk);
-        J.origin = c->frame_no;
+        J.origin = catch_up ? c->frame_no - 1 : c->frame_no;
         tunes.push_back(J);
     }
+    // the sub-lists of the catch-up, behind the jobs: K1Work[] per tree level, then per block kernel BlockWork[] (k_lpf_long
+    // with option meter: and its blocks' record offsets)
+    struct Sub {
+        size_t off = 0, off_mrel = 0;
+        int n = 0;
+    };
+    std::vector<Sub> sub_mix((size_t)c->n_levels), sub_blk(c->lb.size());
+    std::vector<unsigned char> lists;
+    auto append = [&](const void *src, size_t bytes) {
+        const size_t o = align_up(lists.size(), 16);
+        lists.resize(o + bytes);
+        memcpy(lists.data() + o, src, bytes);
+        return o;
+    };
+    if (!caught.empty()) {
+        for (int lv = 1; lv < c->n_levels; ++lv) {
+            std::vector<K1Work> w;
+            for (int id : caught)
+                if (c->nodes[(size_t)id].level == lv)
+                    w.insert(w.end(), c->cu.leaf[(size_t)id].mix.begin(), c->cu.leaf[(size_t)id].mix.end());
+            sub_mix[(size_t)lv].n = (int)w.size();
+            if (!w.empty())
+                sub_mix[(size_t)lv].off = append(w.data(), sizeof(K1Work) * w.size());
+        }
+        for (size_t q = 0; q < c->lb.size(); ++q) {
+            const int slot = sdrx_ctx::Catchup::slot(c->lb[q].kind);
+            std::vector<BlockWork> w;
+            std::vector<int> mrel;
+            for (int id : caught) {
+                const sdrx_ctx::Catchup::Leaf &L = c->cu.leaf[(size_t)id];
+                w.insert(w.end(), L.blk[slot].begin(), L.blk[slot].end());
+                if (slot == 2)
+                    mrel.insert(mrel.end(), L.mrel.begin(), L.mrel.end());
+            }
+            sub_blk[q].n = (int)w.size();
+            if (!w.empty())
+                sub_blk[q].off = append(w.data(), sizeof(BlockWork) * w.size());
+            if (!mrel.empty())
+                sub_blk[q].off_mrel = append(mrel.data(), sizeof(int) * mrel.size());
+        }
+    }
     if (!fills.empty()) {
-        const size_t fb = sizeof(FillJob) * fills.size(), bytes = fb + sizeof(RetuneJob) * tunes.size();
+        const size_t fb = sizeof(FillJob) * fills.size(), jb = align_up(fb + sizeof(RetuneJob) * tunes.size(), 16), bytes = jb + lists.size();
         if (bytes > K.jobs_cap) {
             if (K.d_jobs)
                 (void)hipFree(K.d_jobs);
@@ -726,20 +783,62 @@ int apply_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
         std::vector<unsigned char> host(bytes);
         memcpy(host.data(), fills.data(), fb);
         if (!tunes.empty())
-            memcpy(host.data() + fb, tunes.data(), bytes - fb);
+            memcpy(host.data() + fb, tunes.data(), sizeof(RetuneJob) * tunes.size());
+        if (!lists.empty())
+            memcpy(host.data() + jb, lists.data(), lists.size());
         HIPCHK(c, hipMemcpyAsync(K.d_jobs, host.data(), bytes, hipMemcpyHostToDevice, c->st.stream));
         hipLaunchKernelGGL(k_vfo_reset, dim3((unsigned)fills.size()), dim3(256), 0, c->st.stream, reinterpret_cast<const FillJob *>(K.d_jobs));
         if (!tunes.empty()) {
             const int nj = (int)tunes.size();
             hipLaunchKernelGGL(k_vfo_retune, dim3((nj + 63) / 64), dim3(64), 0, c->st.stream, reinterpret_cast<const RetuneJob *>(K.d_jobs + fb), nj);
         }
+        if (!caught.empty()) { // frame K-1 of the caught-up leaves: the levels, then the leaf tail, as a frame's own sequence
+            const unsigned long long f = c->frame_no - 1;
+            for (const Launch1 &L : c->l1)
+                if (sub_mix[(size_t)L.level].n > 0)
+                    launch_mix_list(c, L, f, reinterpret_cast<const K1Work *>(K.d_jobs + jb + sub_mix[(size_t)L.level].off), sub_mix[(size_t)L.level].n, nullptr,
+                                    kRawTiled);
+            for (size_t q = 0; q < c->lb.size(); ++q)
+                if (sub_blk[q].n > 0)
+                    launch_block_list(c, c->lb[q], c->st.stream, f, reinterpret_cast<const BlockWork *>(K.d_jobs + jb + sub_blk[q].off),
+                                      c->opt_meter ? reinterpret_cast<const int *>(K.d_jobs + jb + sub_blk[q].off_mrel) : nullptr, sub_blk[q].n);
+        }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->st.stream)); // (`host` lives on this stack)
+    }
+    if (!caught.empty()) { // the caught-up frame's meter records: one copy of the span that holds them
+        int lo = c->meter_slots, hi = 0;
+        for (int id : caught) {
+            lo = std::min(lo, c->nodes[(size_t)id].meter_first);
+            hi = std::max(hi, c->nodes[(size_t)id].meter_first + c->nodes[(size_t)id].meter_n);
+        }
+        std::vector<unsigned char> rec(16 * (size_t)(hi - lo));
+        HIPCHK(c, hipMemcpy(rec.data(), c->d_pay[(c->frame_no - 1) & 1ull] + c->meter_off + 16 * (size_t)lo, rec.size(), hipMemcpyDeviceToHost));
+        for (int id : caught) {
+            const Node &nd = c->nodes[(size_t)id];
+            sdrx_ctx::Catchup::Leaf &U = c->cu.leaf[(size_t)id];
+            U.frame = (long long)c->frame_no - 1;
+            U.sum_sq = 0;
+            U.clipped = U.peak = 0;
+            for (int j = 0; j < nd.meter_n; ++j) { // {sum_sq u64, clipped u32, peak u32} per slot, as sdrx_get_meters folds them
+                const unsigned char *r = rec.data() + 16 * (size_t)(nd.meter_first - lo + j);
+                uint64_t sum;
+                uint32_t clipped, pk;
+                memcpy(&sum, r, 8);
+                memcpy(&clipped, r + 8, 4);
+                memcpy(&pk, r + 12, 4);
+                U.sum_sq += sum;
+                U.clipped += clipped;
+                U.peak = std::max(U.peak, pk);
+            }
+        }
     }
     for (int k = 0; k < n; ++k) {
         sdrx_ctx::Park::Leaf &L = K.leaf[(size_t)ids[k]];
         if (L.active == active[k])
             continue;
+        if (c->opt_catchup && std::find(caught.begin(), caught.end(), ids[k]) == caught.end())
+            c->cu.leaf[(size_t)ids[k]].frame = -1; // parked (a catch-up is discarded), or started at K as without the option
         if (L.since != c->frame_no) // (a second change before the same frame: the frames before it ran in the state they ran in)
             L.was_active = L.active;
         L.active = active[k];
@@ -795,6 +894,36 @@ int sdrx_get_active(sdrx_ctx *c, const int *ids, int n, sdrx_active_state *out)
             s.since_frame = (int64_t)c->park.leaf[(size_t)ids[k]].since;
         }
         out[k] = s;
+    }
+    return SDRX_OK;
+}
+
+int sdrx_get_catchup(sdrx_ctx *c, const int *ids, int n, sdrx_meter *out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_catchup before sdrx_finalize");
+    if (!c->opt_catchup)
+        return fail(c, SDRX_ESTATE, "sdrx_get_catchup: option \"catchup\" is off");
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return fail(c, SDRX_EINVAL, "sdrx_get_catchup: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
+    if (int rc = check_leaf_ids(c, "sdrx_get_catchup", ids, n, false))
+        return rc;
+    for (int k = 0; k < n; ++k) {
+        const Node &nd = c->nodes[(size_t)ids[k]];
+        const sdrx_ctx::Catchup::Leaf &U = c->cu.leaf[(size_t)ids[k]];
+        sdrx_meter m;
+        memset(&m, 0, sizeof m);
+        m.frame = -1;
+        if (U.frame >= 0) {
+            m.frame = (int64_t)U.frame;
+            m.sum_sq = U.sum_sq;
+            m.n_values = (uint32_t)(nd.d.demod_usb ? nd.n_out : 2 * nd.n_f);
+            m.clipped = U.clipped;
+            memcpy(&m.peak, &U.peak, 4);
+        }
+        out[k] = m;
     }
     return SDRX_OK;
 }

@@ -104,7 +104,7 @@ struct sdrx_ctx {
     int opt_exact = 1, opt_prequant = 0, opt_segments = 0, opt_dc_blocked = 0, opt_pipeline = 0, opt_dc_speculative = 1;
     int opt_fuse = 1, opt_frame_pipeline = 1, opt_fuse_late = 1, opt_keep_streams = 0, opt_fuse_demod = 0;
     int opt_tail_in_levels = 1;
-    int opt_meter = 0, opt_squelch = 0, opt_preroll = 0, opt_squelch_auto = 0, opt_park = 0, opt_watch = 0;
+    int opt_meter = 0, opt_squelch = 0, opt_preroll = 0, opt_squelch_auto = 0, opt_park = 0, opt_watch = 0, opt_catchup = 0;
     // option meter: per frame parity, behind the payloads in d_pay / h_pay (at meter_off), one 16-byte MeterAcc record per work
     // unit that emits payload values (kernels.hip "output meters"); the records travel in the payload copy
     size_t meter_off = 0;
@@ -171,6 +171,23 @@ struct sdrx_ctx {
             return !(frame >= L.since ? L.active : L.was_active);
         }
     } park;
+
+    // Option catchup (sdrx_set_active): a leaf unparked before frame K that was parked in K-1 runs K-1 on its
+    // parent's stream -- still in HBM -- before the call returns, through sub-list launches of the frame's own kernels.  Host
+    // memory only: every leaf's entries of the work lists finalize built (what the sub-lists are cut from), and per leaf the
+    // frame it was caught up in with that frame's meter (sdrx_get_catchup).  Empty with the option off.
+    struct Catchup {
+        struct Leaf {
+            std::vector<K1Work> mix;        // its items of its level's k_mix_decimate launch
+            std::vector<BlockWork> blk[4];  // its blocks per block kernel: 0 late decimation, 1 demodulation, 2 long low-pass, 3 compress
+            std::vector<int> mrel;          //   ... and the record offsets of blk[2] (option meter)
+            long long frame = -1;           // the frame its present active state began with a catch-up of; -1: it did not
+            unsigned long long sum_sq = 0;  // that frame's meter, folded as sdrx_get_meters folds it
+            uint32_t clipped = 0, peak = 0;
+        };
+        std::vector<Leaf> leaf; // per node
+        static int slot(int kind) { return kind == KIND_LATE_DEC ? 0 : kind == KIND_DEMOD ? 1 : kind == KIND_LPF_LONG ? 2 : 3; }
+    } cu;
 
     // Option watch (sdrx_set_watch, watch.hip).  Host bookkeeping per leaf as option park keeps it: a frame
     // f >= since ran with the leaf in state `on`, the frames before it in state `was_on`.  Everything on the device is allocated

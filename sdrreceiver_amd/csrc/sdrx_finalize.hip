@@ -937,6 +937,31 @@ int park_setup(sdrx_ctx *c, const Built &B)
     return SDRX_OK;
 }
 
+// ---- option catchup: every leaf's own entries of the work lists, kept on the host (sdrx_set_active cuts its sub-lists from them)
+void catchup_setup(sdrx_ctx *c, const Built &B)
+{
+    c->cu = sdrx_ctx::Catchup();
+    if (!c->opt_catchup)
+        return;
+    c->cu.leaf.assign(c->nodes.size(), sdrx_ctx::Catchup::Leaf());
+    for (const std::vector<K1Work> &level : B.works)
+        for (const K1Work &w : level)
+            if (c->nodes[(size_t)w.vfo].leaf)
+                c->cu.leaf[(size_t)w.vfo].mix.push_back(w);
+    for (const BlockWork &w : B.w2a)
+        c->cu.leaf[(size_t)B.n2a[(size_t)w.vfo]].blk[0].push_back(w);
+    for (const BlockWork &w : B.w2)
+        c->cu.leaf[(size_t)B.n2[(size_t)w.vfo]].blk[1].push_back(w);
+    for (size_t k = 0; k < B.w4.size(); ++k) {
+        sdrx_ctx::Catchup::Leaf &L = c->cu.leaf[(size_t)B.n4[(size_t)B.w4[k].vfo]];
+        L.blk[2].push_back(B.w4[k]);
+        if (c->opt_meter)
+            L.mrel.push_back(B.mrel4[k]);
+    }
+    for (const BlockWork &w : B.w3)
+        c->cu.leaf[(size_t)B.n3[(size_t)w.vfo]].blk[3].push_back(w);
+}
+
 int finalize_impl(sdrx_ctx *c)
 {
     if (int rc = derive_nodes(c))
@@ -955,6 +980,7 @@ int finalize_impl(sdrx_ctx *c)
         return rc;
     if (int rc = park_setup(c, B))
         return rc;
+    catchup_setup(c, B);
     c->sq.preroll_fused = false;
     for (const Node &n : c->nodes)
         c->sq.preroll_fused |= n.fused_demod;

@@ -215,13 +215,12 @@ void squelch_gate(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
         form(std::false_type());
 }
 
-// One block-per-tile launch of the leaf tail (late decimation / demodulation / long audio low-pass / compress) for `frame`.
-void launch_block_kernel(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned long long frame)
+// One block-per-tile launch of the leaf tail (late decimation / demodulation / long audio low-pass / compress) for `frame`:
+// `n_blocks` entries of the work list `w` (k_lpf_long with option meter: and of the record offsets `mrel`).
+void launch_block_list(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned long long frame, const BlockWork *w, const int *mrel, int n_blocks)
 {
     Bracket b(c, ts, L.kind, L.alg_bytes);
-    const dim3 grid(L.n_blocks);
-    const BlockWork *w = reinterpret_cast<const BlockWork *>(c->arena + L.off_work);
-    const int *mrel = c->opt_meter ? reinterpret_cast<const int *>(c->arena + L.off_mrel) : nullptr;
+    const dim3 grid(n_blocks);
     const unsigned char *desc = c->arena + L.off_desc;
     with_variant(c, [&](auto EXACT, auto, auto METER, auto PARK) {
         if (L.kind == KIND_LATE_DEC && c->late4)
@@ -239,6 +238,29 @@ void launch_block_kernel(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned
         else
             hipLaunchKernelGGL((k_compress<METER(), PARK()>), grid, dim3(256), 0, ts, reinterpret_cast<const K3Vfo *>(desc), w, frame,
                                park_arg<PARK()>(c, c->park.o_3));
+    });
+}
+// ... the whole list finalize built
+void launch_block_kernel(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned long long frame)
+{
+    launch_block_list(c, L, ts, frame, reinterpret_cast<const BlockWork *>(c->arena + L.off_work),
+                      c->opt_meter ? reinterpret_cast<const int *>(c->arena + L.off_mrel) : nullptr, L.n_blocks);
+}
+
+// One k_mix_decimate launch of a tree level for `frame`: `n_work` entries of the work list `w`.
+void launch_mix_list(sdrx_ctx *c, const Launch1 &L, unsigned long long frame, const K1Work *w, int n_work, const void *raw, int raw_mode)
+{
+    Bracket b(c, c->st.stream, L.kind, L.alg_bytes);
+    const K1Vfo *k1 = reinterpret_cast<const K1Vfo *>(c->arena + c->off_k1vfo);
+    const void *lraw = L.level == 0 ? raw : nullptr;
+    const int lmode = L.level == 0 ? raw_mode : kRawTiled;
+    with_variant(c, [&](auto EXACT, auto ROT, auto METER, auto PARK) {
+        if (L.level == 0)
+            hipLaunchKernelGGL((k_mix_decimate<EXACT(), 0, ROT(), METER(), PARK()>), dim3(n_work), dim3(64), L.lds_bytes, c->st.stream, k1, w, frame, lraw, lmode,
+                               park_arg<PARK()>(c, 0));
+        else
+            hipLaunchKernelGGL((k_mix_decimate<EXACT(), 1, ROT(), METER(), PARK()>), dim3(n_work), dim3(64), L.lds_bytes, c->st.stream, k1, w, frame, lraw, lmode,
+                               park_arg<PARK()>(c, 0));
     });
 }
 
@@ -393,7 +415,6 @@ int pipeline_flush(sdrx_ctx *c)
 //         directory only.
 int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
 {
-    const K1Vfo *k1 = reinterpret_cast<const K1Vfo *>(c->arena + c->off_k1vfo);
     const int p = (int)(c->frame_no & 1ull);
     const bool pipe = c->opt_pipeline != 0;
     if (pipe && c->st.tail_recorded[p])
@@ -435,20 +456,8 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         c->pending_fetch = true;
         return SDRX_OK;
     }
-    for (const Launch1 &L : c->l1) {
-        Bracket b(c, c->st.stream, L.kind, L.alg_bytes);
-        const K1Work *w = reinterpret_cast<const K1Work *>(c->arena + L.off_work);
-        const void *lraw = L.level == 0 ? raw : nullptr;
-        const int lmode = L.level == 0 ? raw_mode : kRawTiled;
-        with_variant(c, [&](auto EXACT, auto ROT, auto METER, auto PARK) {
-            if (L.level == 0)
-                hipLaunchKernelGGL((k_mix_decimate<EXACT(), 0, ROT(), METER(), PARK()>), dim3(L.n_work), dim3(64), L.lds_bytes, c->st.stream, k1, w, c->frame_no, lraw,
-                                   lmode, park_arg<PARK()>(c, 0));
-            else
-                hipLaunchKernelGGL((k_mix_decimate<EXACT(), 1, ROT(), METER(), PARK()>), dim3(L.n_work), dim3(64), L.lds_bytes, c->st.stream, k1, w, c->frame_no, lraw,
-                                   lmode, park_arg<PARK()>(c, 0));
-        });
-    }
+    for (const Launch1 &L : c->l1)
+        launch_mix_list(c, L, c->frame_no, reinterpret_cast<const K1Work *>(c->arena + L.off_work), L.n_work, raw, raw_mode);
     hipStream_t ts = pipe ? c->st.tail_stream : c->st.stream;
     if (pipe) {
         HIPCHK(c, hipEventRecord(c->st.ev_levels[p], c->st.stream));

@@ -792,6 +792,25 @@ int sdrx_group_get_active(sdrx_group *g, const int *ids, int n, sdrx_active_stat
     return SDRX_OK;
 }
 
+int sdrx_group_get_catchup(sdrx_group *g, const int *ids, int n, sdrx_meter *out)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_catchup before sdrx_group_finalize");
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return gfail(g, SDRX_EINVAL, "sdrx_group_get_catchup: n = %d", n);
+    if (int rc = group_check_ids(g, "sdrx_group_get_catchup", ids, n)) // the whole list first: nothing is written for a bad one
+        return rc;
+    for (int k = 0; k < n; ++k) {
+        const auto w = g->where[(size_t)ids[k]];
+        const int rc = sdrx_get_catchup(g->m[(size_t)w.first].c, &w.second, 1, out + k);
+        if (rc)
+            return member_fail(g, w.first, rc);
+    }
+    return SDRX_OK;
+}
+
 // sdrx_set_watch over the whole tree, as sdrx_group_set_active: everything is checked before any member changes
 int sdrx_group_set_watch(sdrx_group *g, const int *ids, const int32_t *on, int n)
 {

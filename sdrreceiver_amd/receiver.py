@@ -54,7 +54,7 @@ class Receiver:
                  fuse_late: bool = True, keep_streams: bool = False, dc_speculative: bool = True,
                  dc_blocks_per_step: int | None = None, fuse_demod: bool = False,
                  tail_in_levels: bool = True, meter: bool = False, squelch: bool = False, preroll: bool = False,
-                 squelch_auto: bool = False, park: bool = False, watch: bool = False):
+                 squelch_auto: bool = False, park: bool = False, watch: bool = False, catchup: bool = False):
         self.L = _lib.lib()
         h = C.c_void_p()
         rc = self.L.sdrx_create(C.byref(h), int(device))
@@ -87,6 +87,8 @@ class Receiver:
             self._chk(self.L.sdrx_set_option(self.h, b"park", 1))
         if watch:
             self._chk(self.L.sdrx_set_option(self.h, b"watch", 1))
+        if catchup:
+            self._chk(self.L.sdrx_set_option(self.h, b"catchup", 1))
         self._chk(self.L.sdrx_set_option(self.h, b"dc_speculative", int(bool(dc_speculative))))
         if dc_blocks_per_step is not None:
             self._chk(self.L.sdrx_set_option(self.h, b"dc_blocks_per_step", int(dc_blocks_per_step)))
@@ -299,6 +301,16 @@ class Receiver:
         self._chk(self.L.sdrx_get_active(self.h, ids.ctypes.data, ids.size, out))
         return {"active": np.array([o.active for o in out[:ids.size]], dtype=np.int32),
                 "since_frame": np.array([o.since_frame for o in out[:ids.size]], dtype=np.int64)}
+
+    def catchup(self, vids) -> dict:
+        """Option ``catchup``: the meter of the frame each of the leaves `vids` was caught up in -- the frame before the one
+        :meth:`set_active` unparked it for, run on the parent's stream the device still held -- as :meth:`meters` gives it;
+        ``frame`` is -1 (and the figures 0) for a leaf whose present active state did not begin with a catch-up.  Good as
+        soon as :meth:`set_active` has returned."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        out = (_lib.MeterC * max(1, ids.size))()
+        self._chk(self.L.sdrx_get_catchup(self.h, ids.ctypes.data, ids.size, out))
+        return meter.meters_dict(out[:ids.size], [self.descs[i].demod_usb for i in ids.tolist()])
 
     # -- channel watch (option ``watch``; sdrreceiver_amd.watch): band power of a leaf from its source's spectrum -------------
     def set_watch(self, vids, on) -> None:
@@ -618,6 +630,13 @@ class Group:
         self._chk(self.L.sdrx_group_get_active(self.h, ids.ctypes.data, ids.size, out))
         return {"active": np.array([o.active for o in out[:ids.size]], dtype=np.int32),
                 "since_frame": np.array([o.since_frame for o in out[:ids.size]], dtype=np.int64)}
+
+    def catchup(self, vids) -> dict:
+        """:meth:`Receiver.catchup` with ids of the whole tree (group option ``catchup=1``)."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        out = (_lib.MeterC * max(1, ids.size))()
+        self._chk(self.L.sdrx_group_get_catchup(self.h, ids.ctypes.data, ids.size, out))
+        return meter.meters_dict(out[:ids.size], [self.descs[i].demod_usb for i in ids.tolist()])
 
     def set_watch(self, vids, on) -> None:
         """:meth:`Receiver.set_watch` with ids of the whole tree (group option ``watch=1``)."""
