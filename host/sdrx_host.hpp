@@ -149,10 +149,7 @@ public:
             in = samples_.data();
         }
         select_tap();
-        if (grp_)
-            check(sdrx_group_process(grp_, in, len / 2), "sdrx_group_process");
-        else
-            check(sdrx_process(ctx_, in, len / 2), "sdrx_process");
+        call("process", sdrx_group_process, sdrx_process, in, len / 2);
         after_frame(len / 2);
     }
     // rtl_tcp / dongle bytes (sdrj.cpp:149-165): LUT and DC correction on the device.  On several devices
@@ -185,10 +182,7 @@ public:
     {
         if (ids.size() != thr_sum_sq.size() || ids.size() != hang_frames.size())
             throw std::invalid_argument("set_squelch: lists of different length");
-        if (grp_)
-            check(sdrx_group_set_squelch(grp_, ids.data(), thr_sum_sq.data(), hang_frames.data(), (int)ids.size()), "sdrx_group_set_squelch");
-        else
-            check(sdrx_set_squelch(ctx_, ids.data(), thr_sum_sq.data(), hang_frames.data(), (int)ids.size()), "sdrx_set_squelch");
+        call("set_squelch", sdrx_group_set_squelch, sdrx_set_squelch, ids.data(), thr_sum_sq.data(), hang_frames.data(), (int)ids.size());
     }
     // Auto-squelch (library option "squelch_auto" = 1): leaf ids[k]'s threshold becomes max(thr_sum_sq, floor * ratio_q8[k] / 256),
     // the floor being the smallest sum_sq of its last window_frames[k] .. 2 * window_frames[k] - 1 frames; ratio_q8 0 = off for
@@ -197,10 +191,7 @@ public:
     {
         if (ids.size() != ratio_q8.size() || ids.size() != window_frames.size())
             throw std::invalid_argument("set_squelch_auto: lists of different length");
-        if (grp_)
-            check(sdrx_group_set_squelch_auto(grp_, ids.data(), ratio_q8.data(), window_frames.data(), (int)ids.size()), "sdrx_group_set_squelch_auto");
-        else
-            check(sdrx_set_squelch_auto(ctx_, ids.data(), ratio_q8.data(), window_frames.data(), (int)ids.size()), "sdrx_set_squelch_auto");
+        call("set_squelch_auto", sdrx_group_set_squelch_auto, sdrx_set_squelch_auto, ids.data(), ratio_q8.data(), window_frames.data(), (int)ids.size());
     }
     // Parking (library option "park" = 1): leaf ids[k] is parked (active[k] 0: no arithmetic, delivered like a closed leaf) or
     // unparked (1: a new vfo from the next frame on -- fresh oscillator, zero filter state); between two frames.
@@ -208,18 +199,12 @@ public:
     {
         if (ids.size() != active.size())
             throw std::invalid_argument("set_active: lists of different length");
-        if (grp_)
-            check(sdrx_group_set_active(grp_, ids.data(), active.data(), (int)ids.size()), "sdrx_group_set_active");
-        else
-            check(sdrx_set_active(ctx_, ids.data(), active.data(), (int)ids.size()), "sdrx_set_active");
+        call("set_active", sdrx_group_set_active, sdrx_set_active, ids.data(), active.data(), (int)ids.size());
     }
     std::vector<sdrx_active_state> active(const std::vector<int> &ids)
     {
         std::vector<sdrx_active_state> out(ids.size());
-        if (grp_)
-            check(sdrx_group_get_active(grp_, ids.data(), (int)ids.size(), out.data()), "sdrx_group_get_active");
-        else
-            check(sdrx_get_active(ctx_, ids.data(), (int)ids.size(), out.data()), "sdrx_get_active");
+        call("get_active", sdrx_group_get_active, sdrx_get_active, ids.data(), (int)ids.size(), out.data());
         return out;
     }
     // channel watch (option "watch"): band power of a leaf from its source's spectrum, active or parked
@@ -227,27 +212,18 @@ public:
     {
         if (ids.size() != on.size())
             throw std::invalid_argument("set_watch: lists of different length");
-        if (grp_)
-            check(sdrx_group_set_watch(grp_, ids.data(), on.data(), (int)ids.size()), "sdrx_group_set_watch");
-        else
-            check(sdrx_set_watch(ctx_, ids.data(), on.data(), (int)ids.size()), "sdrx_set_watch");
+        call("set_watch", sdrx_group_set_watch, sdrx_set_watch, ids.data(), on.data(), (int)ids.size());
     }
     std::vector<sdrx_watch_level> watch(const std::vector<int> &ids)
     {
         std::vector<sdrx_watch_level> out(ids.size());
-        if (grp_)
-            check(sdrx_group_get_watch(grp_, ids.data(), (int)ids.size(), out.data()), "sdrx_group_get_watch");
-        else
-            check(sdrx_get_watch(ctx_, ids.data(), (int)ids.size(), out.data()), "sdrx_get_watch");
+        call("get_watch", sdrx_group_get_watch, sdrx_get_watch, ids.data(), (int)ids.size(), out.data());
         return out;
     }
     std::vector<double> watch_psd(int leaf_id, int64_t *frame = nullptr)
     {
         std::vector<double> psd(SDRX_SPECTRUM_BINS);
-        if (grp_)
-            check(sdrx_group_get_watch_psd(grp_, leaf_id, psd.data(), frame), "sdrx_group_get_watch_psd");
-        else
-            check(sdrx_get_watch_psd(ctx_, leaf_id, psd.data(), frame), "sdrx_get_watch_psd");
+        call("get_watch_psd", sdrx_group_get_watch_psd, sdrx_get_watch_psd, leaf_id, psd.data(), frame);
         return psd;
     }
 
@@ -345,13 +321,18 @@ private:
         if (!v->initialised)
             throw std::runtime_error("vfo::init was not called");
         v->d.parent_id = parent;
-        if (grp_)
-            check(sdrx_group_add_vfo(grp_, &v->d, &v->id), "sdrx_group_add_vfo");
-        else
-            check(sdrx_add_vfo(ctx_, &v->d, &v->id), "sdrx_add_vfo");
+        call("add_vfo", sdrx_group_add_vfo, sdrx_add_vfo, &v->d, &v->id);
         if (v->mpVFOs)
             for (vfo *c : *v->mpVFOs)
                 add(c, v->id);
+    }
+    // the call `name` of the ABI on whichever this host runs on: sdrx_group_<name>(grp_, ...) or sdrx_<name>(ctx_, ...)
+    template <class GroupFn, class CtxFn, class... Args>
+    void call(const char *name, GroupFn group_fn, CtxFn ctx_fn, Args... args)
+    {
+        const int rc = grp_ ? group_fn(grp_, args...) : ctx_fn(ctx_, args...);
+        if (rc != SDRX_OK)
+            check(rc, (std::string(grp_ ? "sdrx_group_" : "sdrx_") + name).c_str());
     }
     void check(int rc, const char *what)
     {

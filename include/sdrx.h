@@ -292,7 +292,9 @@ int sdrx_get_output(sdrx_ctx *ctx, int id, const void **buf, uint32_t *len_bytes
  *                          has !(pre > -129 && pre < 128).
  * sum_sq = sum of v * v (exact), peak = max |pre| in LSB of the payload type (NaN if any pre was NaN).
  * SDRX_ESTATE with the option off, before sdrx_finalize or before any frame was delivered; SDRX_EINVAL for a bad id, a
- * VFO with children (it publishes nothing) or n < 0; n == 0 does nothing. */
+ * VFO with children (it publishes nothing) or n < 0; n == 0 does nothing.
+ * This and every per-leaf list call below checks in one order, and the first thing wrong decides the code: handle, finalized,
+ * option, list shape, ids (range, leaf, listed once in a setter), values, broken (group), frames in flight or delivered. */
 typedef struct sdrx_meter {
     int64_t frame;     /* index of the frame these figures belong to (0 = first frame after finalize) */
     uint64_t sum_sq;   /* sum of v*v over the payload values v of that frame (exact integer) */

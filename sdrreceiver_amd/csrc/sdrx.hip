@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <type_traits>
@@ -521,7 +522,7 @@ int sdrx_add_tap(sdrx_ctx *c, int id) { return tap_change(c, id, false, "sdrx_ad
 
 namespace {
 
-// The checks of sdrx_set_mixer_freqs / sdrx_set_gains (and their group forms): the whole list before anything changes.
+// The checks of sdrx_set_mixer_freqs / sdrx_set_gains: the whole list before anything changes.
 // Returns SDRX_OK or SDRX_EINVAL with the reason in `msg`.
 int check_vfo_list(int n_nodes, const int *ids, const void *vals, bool dbl, int n, std::string &msg)
 {
@@ -585,15 +586,8 @@ int apply_vfo_jobs(sdrx_ctx *c, const int *ids, const double *freqs, const float
         }
     }
     if (!jobs.empty()) {
-        if (jobs.size() > c->jobs_cap) {
-            if (c->d_jobs)
-                (void)hipFree(c->d_jobs);
-            c->d_jobs = nullptr;
-            c->jobs_cap = 0;
-            HIPCHK(c, hipMalloc(&c->d_jobs, sizeof(RetuneJob) * jobs.size()));
-            c->jobs_cap = jobs.size();
-        }
-        HIPCHK(c, hipMemcpyAsync(c->d_jobs, jobs.data(), sizeof(RetuneJob) * jobs.size(), hipMemcpyHostToDevice, c->st.stream));
+        if (int rc = upload_jobs(c, c->d_jobs, c->jobs_cap, jobs.data(), sizeof(RetuneJob) * jobs.size()))
+            return rc;
         const int nj = (int)jobs.size();
         hipLaunchKernelGGL(k_vfo_retune, dim3((nj + 63) / 64), dim3(64), 0, c->st.stream, c->d_jobs, nj);
         HIPCHK(c, hipGetLastError());
@@ -772,21 +766,14 @@ int apply_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
     }
     if (!fills.empty()) {
         const size_t fb = sizeof(FillJob) * fills.size(), jb = align_up(fb + sizeof(RetuneJob) * tunes.size(), 16), bytes = jb + lists.size();
-        if (bytes > K.jobs_cap) {
-            if (K.d_jobs)
-                (void)hipFree(K.d_jobs);
-            K.d_jobs = nullptr;
-            K.jobs_cap = 0;
-            HIPCHK(c, hipMalloc(&K.d_jobs, bytes));
-            K.jobs_cap = bytes;
-        }
         std::vector<unsigned char> host(bytes);
         memcpy(host.data(), fills.data(), fb);
         if (!tunes.empty())
             memcpy(host.data() + fb, tunes.data(), sizeof(RetuneJob) * tunes.size());
         if (!lists.empty())
             memcpy(host.data() + jb, lists.data(), lists.size());
-        HIPCHK(c, hipMemcpyAsync(K.d_jobs, host.data(), bytes, hipMemcpyHostToDevice, c->st.stream));
+        if (int rc = upload_jobs(c, K.d_jobs, K.jobs_cap, host.data(), bytes))
+            return rc;
         hipLaunchKernelGGL(k_vfo_reset, dim3((unsigned)fills.size()), dim3(256), 0, c->st.stream, reinterpret_cast<const FillJob *>(K.d_jobs));
         if (!tunes.empty()) {
             const int nj = (int)tunes.size();
@@ -818,19 +805,10 @@ int apply_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
             const Node &nd = c->nodes[(size_t)id];
             sdrx_ctx::Catchup::Leaf &U = c->cu.leaf[(size_t)id];
             U.frame = (long long)c->frame_no - 1;
-            U.sum_sq = 0;
-            U.clipped = U.peak = 0;
-            for (int j = 0; j < nd.meter_n; ++j) { // {sum_sq u64, clipped u32, peak u32} per slot, as sdrx_get_meters folds them
-                const unsigned char *r = rec.data() + 16 * (size_t)(nd.meter_first - lo + j);
-                uint64_t sum;
-                uint32_t clipped, pk;
-                memcpy(&sum, r, 8);
-                memcpy(&clipped, r + 8, 4);
-                memcpy(&pk, r + 12, 4);
-                U.sum_sq += sum;
-                U.clipped += clipped;
-                U.peak = std::max(U.peak, pk);
-            }
+            const MeterFold F = fold_meter_records(rec.data(), nd.meter_first - lo, nd.meter_n); // (as sdrx_get_meters folds them)
+            U.sum_sq = F.sum_sq;
+            U.clipped = F.clipped;
+            U.peak = F.peak;
         }
     }
     for (int k = 0; k < n; ++k) {
@@ -855,35 +833,13 @@ extern "C" {
 
 int sdrx_set_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_set_active before sdrx_finalize");
-    if (!c->opt_park)
-        return fail(c, SDRX_ESTATE, "sdrx_set_active: option \"park\" is off");
-    if (n < 0 || (n > 0 && (!ids || !active)))
-        return fail(c, SDRX_EINVAL, "sdrx_set_active: n = %d, ids %p, active %p", n, (const void *)ids, (const void *)active);
-    if (int rc = check_leaf_ids(c, "sdrx_set_active", ids, n, true))
-        return rc;
-    for (int k = 0; k < n; ++k)
-        if (active[k] != 0 && active[k] != 1)
-            return fail(c, SDRX_EINVAL, "sdrx_set_active: vfo %d: active = %d (0 or 1)", ids[k], active[k]);
-    if (c->in_flight > 0)
-        return fail(c, SDRX_ESTATE, "sdrx_set_active: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
-    if (n == 0)
-        return SDRX_OK;
-    return apply_active(c, ids, active, n);
+    const int rc = leaf_call(c, "sdrx_set_active", &sdrx_ctx::opt_park, "park", ids, active != nullptr, n, kBetweenFrames, [&](int k) { return bad_switch(active[k]); });
+    return rc || n == 0 ? rc : apply_active(c, ids, active, n);
 }
 
 int sdrx_get_active(sdrx_ctx *c, const int *ids, int n, sdrx_active_state *out)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_get_active before sdrx_finalize");
-    if (n < 0 || (n > 0 && (!ids || !out)))
-        return fail(c, SDRX_EINVAL, "sdrx_get_active: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
-    if (int rc = check_leaf_ids(c, "sdrx_get_active", ids, n, false))
+    if (int rc = leaf_call(c, "sdrx_get_active", nullptr, nullptr, ids, out != nullptr, n, kAnyTime)) // (no option: every leaf is active without "park")
         return rc;
     for (int k = 0; k < n; ++k) {
         sdrx_active_state s;
@@ -900,15 +856,7 @@ int sdrx_get_active(sdrx_ctx *c, const int *ids, int n, sdrx_active_state *out)
 
 int sdrx_get_catchup(sdrx_ctx *c, const int *ids, int n, sdrx_meter *out)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_get_catchup before sdrx_finalize");
-    if (!c->opt_catchup)
-        return fail(c, SDRX_ESTATE, "sdrx_get_catchup: option \"catchup\" is off");
-    if (n < 0 || (n > 0 && (!ids || !out)))
-        return fail(c, SDRX_EINVAL, "sdrx_get_catchup: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
-    if (int rc = check_leaf_ids(c, "sdrx_get_catchup", ids, n, false))
+    if (int rc = leaf_call(c, "sdrx_get_catchup", &sdrx_ctx::opt_catchup, "catchup", ids, out != nullptr, n, kAnyTime))
         return rc;
     for (int k = 0; k < n; ++k) {
         const Node &nd = c->nodes[(size_t)ids[k]];

@@ -128,8 +128,8 @@ struct sdrx_ctx {
         unsigned *d_hang = nullptr; // hang_left per leaf: one array, every gate runs in frame order on one stream
         unsigned *d_prev = nullptr; // prev_open per leaf (preroll)
         SqAuto *d_auto = nullptr;   // floor state and settings per leaf (squelch_auto)
-        SqJob *d_jobs = nullptr;    // job list of sdrx_set_squelch and (SqAutoJob: the same size) sdrx_set_squelch_auto
-        size_t jobs_cap = 0;
+        SqJob *d_jobs = nullptr;    // job list of sdrx_set_squelch and (as SqAutoJob) of sdrx_set_squelch_auto
+        size_t jobs_cap = 0;        //   ... its size in bytes (upload_jobs)
         int tiles = 1;                        // k_squelch_gather's grid.y: 16 KiB tiles of the longest payload
         std::vector<int> index;               // node -> its place in publish order (-1: not a leaf)
         std::vector<SqCfg> cfg;               // host copy of the thresholds
@@ -299,7 +299,7 @@ struct sdrx_ctx {
     size_t off_k1vfo = 0;
     size_t off_k2 = 0, off_k4 = 0; // the K2Vfo / K4Vfo arrays (sdrx_set_gains patches their gain)
     RetuneJob *d_jobs = nullptr;   // k_vfo_retune's job list (sdrx_set_mixer_freqs, sdrx_set_gains), grown on demand
-    size_t jobs_cap = 0;
+    size_t jobs_cap = 0;           //   ... its size in bytes (upload_jobs)
     std::vector<Launch1> l1;
     std::vector<LaunchB> lb;
     std::vector<int> publish_order;

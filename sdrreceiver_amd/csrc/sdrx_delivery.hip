@@ -226,6 +226,78 @@ int need_delivered(sdrx_ctx *c, const char *what, bool required = true)
         return fail(c, SDRX_ESTATE, "%s: no frame has been delivered yet", what);
     return SDRX_OK;
 }
+
+// The checks every per-leaf call `what` shares, in the one order all of them keep (DESIGN.md "Per-leaf control calls"): handle,
+// finalized, option `opt` (none: nullptr), list shape (`arrays`: every array that goes with `ids` is there), ids (in range, a
+// leaf; listed once in a call that changes something), values (`bad(k)` says what is wrong with entry k), and what the call
+// waits for.  A list of 0 entries passes with SDRX_OK like any other: the caller returns then.
+enum LeafCall {
+    kBetweenFrames, // changes state, or reads the device: no frame in flight
+    kDelivered,     // reads the delivered frame: there is one (a list of 0 entries asks for none)
+    kAnyTime,
+};
+const char *bad_switch(int32_t v) { return v == 0 || v == 1 ? nullptr : "the value must be 0 or 1"; }
+const char *bad_auto(uint32_t ratio_q8, uint32_t window_frames) { return ratio_q8 > 0 && window_frames == 0 ? "window_frames 0 with a ratio" : nullptr; }
+int leaf_call(sdrx_ctx *c, const char *what, int sdrx_ctx::*opt, const char *opt_name, const int *ids, bool arrays, int n, LeafCall mode,
+              const std::function<const char *(int)> &bad = nullptr)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "%s before sdrx_finalize", what);
+    if (opt && !(c->*opt))
+        return fail(c, SDRX_ESTATE, "%s: option \"%s\" is off", what, opt_name);
+    if (n < 0 || (n > 0 && (!ids || !arrays)))
+        return fail(c, SDRX_EINVAL, "%s: n = %d, ids %p, or a null array beside them", what, n, (const void *)ids);
+    if (int rc = check_leaf_ids(c, what, ids, n, mode == kBetweenFrames))
+        return rc;
+    for (int k = 0; bad && k < n; ++k)
+        if (const char *why = bad(k))
+            return fail(c, SDRX_EINVAL, "%s: vfo %d (entry %d): %s", what, ids[k], k, why);
+    if (mode == kBetweenFrames && c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "%s: %d submitted frame(s) not yet delivered -- call sdrx_wait first", what, c->in_flight);
+    return mode == kDelivered && n > 0 ? need_delivered(c, what) : SDRX_OK;
+}
+
+// `bytes` of a job list into the device buffer `buf` (grown on demand, `cap` bytes), queued on the context's stream: the caller
+// launches behind it and synchronises before `data` goes away.
+template <class T>
+int upload_jobs(sdrx_ctx *c, T *&buf, size_t &cap, const void *data, size_t bytes)
+{
+    if (bytes > cap) {
+        if (buf)
+            (void)hipFree(buf);
+        buf = nullptr;
+        cap = 0;
+        HIPCHK(c, hipMalloc(&buf, bytes));
+        cap = bytes;
+    }
+    HIPCHK(c, hipMemcpyAsync(buf, data, bytes, hipMemcpyHostToDevice, c->st.stream));
+    return SDRX_OK;
+}
+
+// A leaf's meter of one frame: its `n` records {sum_sq u64, clipped u32, peak u32} from record `first` of `rec` on, folded.
+// (peak: magnitudes as bits -- the max of the bits is the max, a NaN wins)
+struct MeterFold {
+    uint64_t sum_sq = 0;
+    uint32_t clipped = 0, peak = 0;
+};
+MeterFold fold_meter_records(const unsigned char *rec, int first, int n)
+{
+    MeterFold F;
+    for (int j = 0; j < n; ++j) {
+        const unsigned char *r = rec + 16 * (size_t)(first + j);
+        uint64_t sum;
+        uint32_t clipped, pk;
+        memcpy(&sum, r, 8);
+        memcpy(&clipped, r + 8, 4);
+        memcpy(&pk, r + 12, 4);
+        F.sum_sq += sum;
+        F.clipped += clipped;
+        F.peak = std::max(F.peak, pk);
+    }
+    return F;
+}
 } // namespace
 
 extern "C" {
@@ -278,11 +350,9 @@ int sdrx_fetch(sdrx_ctx *c)
 
 int sdrx_get_output(sdrx_ctx *c, int id, const void **buf, uint32_t *len, uint32_t *rate)
 {
-    if (!c || id < 0 || id >= (int)c->nodes.size())
+    if (!c || id < 0 || id >= (int)c->nodes.size()) // (this call and sdrx_get_preroll: the id's range before anything else)
         return fail(c, SDRX_EINVAL, "bad vfo id %d", id);
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_get_output before sdrx_finalize");
-    if (int rc = check_leaf_ids(c, "sdrx_get_output", &id, 1, false))
+    if (int rc = leaf_call(c, "sdrx_get_output", nullptr, nullptr, &id, true, 1, kAnyTime))
         return rc;
     if (int rc = need_delivered(c, "sdrx_get_output", buf != nullptr)) // (buf = NULL: a length query, good before any delivery)
         return rc;
@@ -301,20 +371,10 @@ int sdrx_get_output(sdrx_ctx *c, int id, const void **buf, uint32_t *len, uint32
 
 int sdrx_get_meters(sdrx_ctx *c, const int *ids, int n, sdrx_meter *out)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_get_meters before sdrx_finalize");
-    if (!c->opt_meter)
-        return fail(c, SDRX_ESTATE, "sdrx_get_meters: option \"meter\" is off");
-    if (n < 0 || (n > 0 && (!ids || !out)))
-        return fail(c, SDRX_EINVAL, "sdrx_get_meters: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
-    if (int rc = check_leaf_ids(c, "sdrx_get_meters", ids, n, false))
+    if (int rc = leaf_call(c, "sdrx_get_meters", &sdrx_ctx::opt_meter, "meter", ids, out != nullptr, n, kDelivered))
         return rc;
     if (n == 0)
         return SDRX_OK;
-    if (int rc = need_delivered(c, "sdrx_get_meters"))
-        return rc;
     const unsigned char *rec = c->h_pay[c->host_slot] + c->meter_off;
     for (int k = 0; k < n; ++k) {
         const Node &nd = c->nodes[(size_t)ids[k]];
@@ -326,19 +386,10 @@ int sdrx_get_meters(sdrx_ctx *c, const int *ids, int n, sdrx_meter *out)
             continue;
         }
         m.n_values = (uint32_t)(nd.d.demod_usb ? nd.n_out : 2 * nd.n_f);
-        uint32_t peak = 0;
-        for (int j = 0; j < nd.meter_n; ++j) { // {sum_sq u64, clipped u32, peak u32} per slot
-            const unsigned char *r = rec + 16 * (size_t)(nd.meter_first + j);
-            uint64_t sum;
-            uint32_t clipped, pk;
-            memcpy(&sum, r, 8);
-            memcpy(&clipped, r + 8, 4);
-            memcpy(&pk, r + 12, 4);
-            m.sum_sq += sum;
-            m.clipped += clipped;
-            peak = std::max(peak, pk); // magnitudes as bits: the max of the bits is the max, a NaN wins
-        }
-        memcpy(&m.peak, &peak, 4);
+        const MeterFold F = fold_meter_records(rec, nd.meter_first, nd.meter_n);
+        m.sum_sq = F.sum_sq;
+        m.clipped = F.clipped;
+        memcpy(&m.peak, &F.peak, 4);
         out[k] = m;
     }
     return SDRX_OK;
@@ -348,19 +399,8 @@ int sdrx_get_meters(sdrx_ctx *c, const int *ids, int n, sdrx_meter *out)
 // the job list, one k_squelch_set launch.
 int sdrx_set_squelch(sdrx_ctx *c, const int *ids, const uint64_t *thr, const uint32_t *hang_frames, int n)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_set_squelch before sdrx_finalize");
-    if (!c->opt_squelch)
-        return fail(c, SDRX_ESTATE, "sdrx_set_squelch: option \"squelch\" is off");
-    if (n < 0 || (n > 0 && (!ids || !thr || !hang_frames)))
-        return fail(c, SDRX_EINVAL, "sdrx_set_squelch: n = %d, ids %p, thresholds %p, hang times %p", n, (const void *)ids, (const void *)thr,
-                    (const void *)hang_frames);
-    if (int rc = check_leaf_ids(c, "sdrx_set_squelch", ids, n, true))
+    if (int rc = leaf_call(c, "sdrx_set_squelch", &sdrx_ctx::opt_squelch, "squelch", ids, thr && hang_frames, n, kBetweenFrames))
         return rc;
-    if (c->in_flight > 0)
-        return fail(c, SDRX_ESTATE, "sdrx_set_squelch: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
     if (n == 0)
         return SDRX_OK;
     HIPCHK(c, hipSetDevice(c->device));
@@ -369,15 +409,8 @@ int sdrx_set_squelch(sdrx_ctx *c, const int *ids, const uint64_t *thr, const uin
     std::vector<SqJob> jobs((size_t)n);
     for (int k = 0; k < n; ++k)
         jobs[(size_t)k] = SqJob{thr[k], hang_frames[k], (unsigned)c->sq.index[(size_t)ids[k]]};
-    if (jobs.size() > c->sq.jobs_cap) {
-        if (c->sq.d_jobs)
-            (void)hipFree(c->sq.d_jobs);
-        c->sq.d_jobs = nullptr;
-        c->sq.jobs_cap = 0;
-        HIPCHK(c, hipMalloc(&c->sq.d_jobs, sizeof(SqJob) * jobs.size()));
-        c->sq.jobs_cap = jobs.size();
-    }
-    HIPCHK(c, hipMemcpyAsync(c->sq.d_jobs, jobs.data(), sizeof(SqJob) * jobs.size(), hipMemcpyHostToDevice, c->st.stream));
+    if (int rc = upload_jobs(c, c->sq.d_jobs, c->sq.jobs_cap, jobs.data(), sizeof(SqJob) * jobs.size()))
+        return rc;
     hipLaunchKernelGGL(k_squelch_set, dim3((n + 63) / 64), dim3(64), 0, c->st.stream, c->sq.d_jobs, n, c->sq.d_cfg, c->sq.d_hang);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->st.stream)); // (`jobs` lives on this stack)
@@ -390,19 +423,7 @@ int sdrx_set_squelch(sdrx_ctx *c, const int *ids, const uint64_t *thr, const uin
 
 int sdrx_get_squelch(sdrx_ctx *c, const int *ids, int n, sdrx_squelch_state *out)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_get_squelch before sdrx_finalize");
-    if (!c->opt_squelch)
-        return fail(c, SDRX_ESTATE, "sdrx_get_squelch: option \"squelch\" is off");
-    if (n < 0 || (n > 0 && (!ids || !out)))
-        return fail(c, SDRX_EINVAL, "sdrx_get_squelch: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
-    if (int rc = check_leaf_ids(c, "sdrx_get_squelch", ids, n, false))
-        return rc;
-    if (n == 0)
-        return SDRX_OK;
-    if (int rc = need_delivered(c, "sdrx_get_squelch"))
+    if (int rc = leaf_call(c, "sdrx_get_squelch", &sdrx_ctx::opt_squelch, "squelch", ids, out != nullptr, n, kDelivered))
         return rc;
     for (int k = 0; k < n; ++k) {
         const size_t i = (size_t)c->sq.index[(size_t)ids[k]];
@@ -422,22 +443,9 @@ int sdrx_get_squelch(sdrx_ctx *c, const int *ids, int n, sdrx_squelch_state *out
 // values, one upload of the job list, one k_squelch_set_auto launch (which restarts the named leaves' floor state).
 int sdrx_set_squelch_auto(sdrx_ctx *c, const int *ids, const uint32_t *ratio_q8, const uint32_t *window_frames, int n)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_set_squelch_auto before sdrx_finalize");
-    if (!c->opt_squelch_auto)
-        return fail(c, SDRX_ESTATE, "sdrx_set_squelch_auto: option \"squelch_auto\" is off");
-    if (n < 0 || (n > 0 && (!ids || !ratio_q8 || !window_frames)))
-        return fail(c, SDRX_EINVAL, "sdrx_set_squelch_auto: n = %d, ids %p, ratios %p, windows %p", n, (const void *)ids, (const void *)ratio_q8,
-                    (const void *)window_frames);
-    if (int rc = check_leaf_ids(c, "sdrx_set_squelch_auto", ids, n, true))
+    if (int rc = leaf_call(c, "sdrx_set_squelch_auto", &sdrx_ctx::opt_squelch_auto, "squelch_auto", ids, ratio_q8 && window_frames, n, kBetweenFrames,
+                           [&](int k) { return bad_auto(ratio_q8[k], window_frames[k]); }))
         return rc;
-    for (int k = 0; k < n; ++k)
-        if (ratio_q8[k] > 0 && window_frames[k] == 0)
-            return fail(c, SDRX_EINVAL, "sdrx_set_squelch_auto: vfo %d: window_frames 0 with ratio_q8 %u", ids[k], ratio_q8[k]);
-    if (c->in_flight > 0)
-        return fail(c, SDRX_ESTATE, "sdrx_set_squelch_auto: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
     if (n == 0)
         return SDRX_OK;
     HIPCHK(c, hipSetDevice(c->device));
@@ -446,15 +454,8 @@ int sdrx_set_squelch_auto(sdrx_ctx *c, const int *ids, const uint32_t *ratio_q8,
     std::vector<SqAutoJob> jobs((size_t)n);
     for (int k = 0; k < n; ++k)
         jobs[(size_t)k] = SqAutoJob{ratio_q8[k], window_frames[k], (unsigned)c->sq.index[(size_t)ids[k]], 0};
-    if (jobs.size() > c->sq.jobs_cap) { // (one buffer for both setters: SqAutoJob is as large as SqJob)
-        if (c->sq.d_jobs)
-            (void)hipFree(c->sq.d_jobs);
-        c->sq.d_jobs = nullptr;
-        c->sq.jobs_cap = 0;
-        HIPCHK(c, hipMalloc(&c->sq.d_jobs, sizeof(SqJob) * jobs.size()));
-        c->sq.jobs_cap = jobs.size();
-    }
-    HIPCHK(c, hipMemcpyAsync(c->sq.d_jobs, jobs.data(), sizeof(SqAutoJob) * jobs.size(), hipMemcpyHostToDevice, c->st.stream));
+    if (int rc = upload_jobs(c, c->sq.d_jobs, c->sq.jobs_cap, jobs.data(), sizeof(SqAutoJob) * jobs.size())) // (one buffer for both setters)
+        return rc;
     hipLaunchKernelGGL(k_squelch_set_auto, dim3((n + 63) / 64), dim3(64), 0, c->st.stream, reinterpret_cast<const SqAutoJob *>(c->sq.d_jobs), n,
                        c->sq.d_auto);
     HIPCHK(c, hipGetLastError());
@@ -466,19 +467,7 @@ int sdrx_set_squelch_auto(sdrx_ctx *c, const int *ids, const uint32_t *ratio_q8,
 
 int sdrx_get_squelch_auto(sdrx_ctx *c, const int *ids, int n, sdrx_squelch_auto_state *out)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_get_squelch_auto before sdrx_finalize");
-    if (!c->opt_squelch_auto)
-        return fail(c, SDRX_ESTATE, "sdrx_get_squelch_auto: option \"squelch_auto\" is off");
-    if (n < 0 || (n > 0 && (!ids || !out)))
-        return fail(c, SDRX_EINVAL, "sdrx_get_squelch_auto: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
-    if (int rc = check_leaf_ids(c, "sdrx_get_squelch_auto", ids, n, false))
-        return rc;
-    if (n == 0)
-        return SDRX_OK;
-    if (int rc = need_delivered(c, "sdrx_get_squelch_auto"))
+    if (int rc = leaf_call(c, "sdrx_get_squelch_auto", &sdrx_ctx::opt_squelch_auto, "squelch_auto", ids, out != nullptr, n, kDelivered))
         return rc;
     for (int k = 0; k < n; ++k) {
         const size_t i = (size_t)c->sq.index[(size_t)ids[k]];
@@ -522,13 +511,7 @@ int sdrx_get_preroll(sdrx_ctx *c, int id, const void **buf, uint32_t *len, int64
 {
     if (!c || id < 0 || id >= (int)c->nodes.size())
         return fail(c, SDRX_EINVAL, "bad vfo id %d", id);
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_get_preroll before sdrx_finalize");
-    if (!c->opt_preroll)
-        return fail(c, SDRX_ESTATE, "sdrx_get_preroll: option \"preroll\" is off");
-    if (int rc = check_leaf_ids(c, "sdrx_get_preroll", &id, 1, false))
-        return rc;
-    if (int rc = need_delivered(c, "sdrx_get_preroll"))
+    if (int rc = leaf_call(c, "sdrx_get_preroll", &sdrx_ctx::opt_preroll, "preroll", &id, true, 1, kDelivered))
         return rc;
     uint32_t plen = 0;
     const unsigned char *pre = leaf_preroll(c, id, c->host_slot, &plen);

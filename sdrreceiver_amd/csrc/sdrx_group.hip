@@ -560,335 +560,185 @@ int sdrx_group_sync(sdrx_group *g)
     return SDRX_OK;
 }
 
+} // extern "C"
+
+// ---- The per-leaf calls with ids of the whole tree (DESIGN.md "Per-leaf control calls"): three shapes ------------------------
+namespace {
+
+int member_rc(sdrx_group *g, int k, int rc) { return rc ? member_fail(g, k, rc) : SDRX_OK; }
+
+// Single id: the member that answers for VFO `id` in the call `what` and the id it has there
+int owner(sdrx_group *g, const char *what, int id, std::pair<int, int> *w)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "%s before sdrx_group_finalize", what);
+    if (int rc = group_check_ids(g, what, &id, 1))
+        return rc;
+    *w = g->where[(size_t)id];
+    return SDRX_OK;
+}
+
+// Gather: out[k] is what the owner of ids[k] says in the context's call `get`.  The whole list is checked first -- nothing is
+// written for a bad one; the option, that an id names a leaf and the delivered frame are the answering member's to check.
+template <class Out>
+int group_gather(sdrx_group *g, const char *what, const int *ids, int n, Out *out, int (*get)(sdrx_ctx *, const int *, int, Out *))
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "%s before sdrx_group_finalize", what);
+    if (n < 0 || (n > 0 && (!ids || !out)))
+        return gfail(g, SDRX_EINVAL, "%s: n = %d", what, n);
+    if (int rc = group_check_ids(g, what, ids, n))
+        return rc;
+    for (int k = 0; k < n; ++k) {
+        const auto w = g->where[(size_t)ids[k]];
+        if (int rc = get(g->m[(size_t)w.first].c, &w.second, 1, out + k))
+            return member_fail(g, w.first, rc);
+    }
+    return SDRX_OK;
+}
+
+// Scatter: one member's part of a list -- its own ids of the VFOs, and which entries of the caller's arrays they are
+struct Part {
+    std::vector<int> ids, at;
+    int n() const { return (int)ids.size(); }
+    template <class T>
+    std::vector<T> pick(const T *values) const
+    {
+        std::vector<T> v;
+        for (int k : at)
+            v.push_back(values[k]);
+        return v;
+    }
+};
+// The list is checked as a whole, in the order of the context's calls -- option `opt` on (none: nullptr), shape (`arrays`: every
+// array beside `ids` is there), every id held, a leaf (`leaves`; else any VFO) and listed once, its values good (`bad(k)` says
+// what is wrong with entry k) -- then the group's own state; only then `apply` runs on every member that holds a listed VFO
+// (a leaf has one owner; a VFO with children may be replicated on several), with its part.
+int group_scatter(sdrx_group *g, const char *what, int sdrx_ctx::*opt, const char *opt_name, bool leaves, const int *ids, bool arrays, int n,
+                  const std::function<const char *(int)> &bad, const std::function<int(sdrx_ctx *, const Part &)> &apply)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "%s before sdrx_group_finalize", what);
+    for (const GroupMember &M : g->m)
+        if (opt && M.c && !(M.c->*opt))
+            return gfail(g, SDRX_ESTATE, "%s: option \"%s\" is off", what, opt_name);
+    if (n < 0 || (n > 0 && (!ids || !arrays)))
+        return gfail(g, SDRX_EINVAL, "%s: n = %d", what, n);
+    std::vector<char> seen(g->descs.size(), 0);
+    for (int k = 0; k < n; ++k) {
+        if (int rc = group_check_ids(g, what, ids + k, 1))
+            return rc;
+        const auto w = g->where[(size_t)ids[k]];
+        if (leaves && !g->m[(size_t)w.first].c->nodes[(size_t)w.second].leaf)
+            return gfail(g, SDRX_EINVAL, "%s: vfo %d has children and publishes nothing", what, ids[k]);
+        if (seen[(size_t)ids[k]]++)
+            return gfail(g, SDRX_EINVAL, "%s: vfo %d listed twice", what, ids[k]);
+        if (const char *why = bad ? bad(k) : nullptr)
+            return gfail(g, SDRX_EINVAL, "%s: vfo %d (entry %d): %s", what, ids[k], k, why);
+    }
+    if (g->broken)
+        return gfail(g, SDRX_ESTATE, "%s: an earlier frame failed on one member", what);
+    if (g->in_flight > 0)
+        return gfail(g, SDRX_ESTATE, "%s: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", what, g->in_flight);
+    std::vector<Part> parts(g->m.size());
+    for (int k = 0; k < n; ++k)
+        for (const auto &r : g->replicas[(size_t)ids[k]]) {
+            parts[(size_t)r.first].ids.push_back(r.second);
+            parts[(size_t)r.first].at.push_back(k);
+        }
+    for (size_t k = 0; k < parts.size(); ++k)
+        if (parts[k].n() > 0)
+            if (int rc = apply(g->m[k].c, parts[k]))
+                return member_fail(g, (int)k, rc);
+    return SDRX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
 // Payload of leaf `id` (an id of sdrx_group_add_vfo) of the last delivered frame.
 int sdrx_group_get_output(sdrx_group *g, int id, const void **buf, uint32_t *len_bytes, uint32_t *rate)
 {
-    if (!g || id < 0 || id >= (int)g->descs.size())
+    if (!g || id < 0 || id >= (int)g->descs.size()) // (as sdrx_get_output: the id's range before anything else)
         return gfail(g, SDRX_EINVAL, "bad vfo id %d", id);
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_get_output before sdrx_group_finalize");
     // (with frames in flight this keeps serving the last DELIVERED frame, like sdrx_get_output: its payloads sit in
     // the host slot the frame in flight does not write; before the first delivery the member says SDRX_ESTATE)
-    const auto w = g->where[(size_t)id];
-    if (w.first < 0)
-        return gfail(g, SDRX_EINVAL, "vfo %d is held by no device", id);
-    const int rc = sdrx_get_output(g->m[(size_t)w.first].c, w.second, buf, len_bytes, rate);
-    return rc ? member_fail(g, w.first, rc) : SDRX_OK;
+    std::pair<int, int> w;
+    const int rc = owner(g, "sdrx_group_get_output", id, &w);
+    return rc ? rc : member_rc(g, w.first, sdrx_get_output(g->m[(size_t)w.first].c, w.second, buf, len_bytes, rate));
 }
 
 int sdrx_group_get_meters(sdrx_group *g, const int *ids, int n, sdrx_meter *out)
 {
-    if (!g)
-        return SDRX_EINVAL;
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_get_meters before sdrx_group_finalize");
-    if (n < 0 || (n > 0 && (!ids || !out)))
-        return gfail(g, SDRX_EINVAL, "sdrx_group_get_meters: n = %d", n);
-    if (int rc = group_check_ids(g, "sdrx_group_get_meters", ids, n)) // the whole list first: nothing is written for a bad one
-        return rc;
-    for (int k = 0; k < n; ++k) {
-        const auto w = g->where[(size_t)ids[k]];
-        const int rc = sdrx_get_meters(g->m[(size_t)w.first].c, &w.second, 1, out + k);
-        if (rc)
-            return member_fail(g, w.first, rc);
-    }
-    return SDRX_OK;
+    return group_gather(g, "sdrx_group_get_meters", ids, n, out, sdrx_get_meters);
 }
 
-// sdrx_set_squelch over the whole tree: the list is checked as a whole (a leaf has exactly one owner), then every member that
-// owns a listed leaf applies its part.
 int sdrx_group_set_squelch(sdrx_group *g, const int *ids, const uint64_t *thr, const uint32_t *hang_frames, int n)
 {
-    if (!g)
-        return SDRX_EINVAL;
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch before sdrx_group_finalize");
-    if (n < 0 || (n > 0 && (!ids || !thr || !hang_frames)))
-        return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch: n = %d", n);
-    const size_t W = g->m.size();
-    std::vector<char> seen(g->descs.size(), 0);
-    for (int k = 0; k < n; ++k) {
-        if (int rc = group_check_ids(g, "sdrx_group_set_squelch", ids + k, 1))
-            return rc;
-        const auto w = g->where[(size_t)ids[k]];
-        if (!g->m[(size_t)w.first].c->nodes[(size_t)w.second].leaf)
-            return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch: vfo %d has children and publishes nothing", ids[k]);
-        if (seen[(size_t)ids[k]]++)
-            return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch: vfo %d listed twice", ids[k]);
-    }
-    for (size_t k = 0; k < W; ++k)
-        if (g->m[k].c && !g->m[k].c->opt_squelch)
-            return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch: option \"squelch\" is off");
-    if (g->broken)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch: an earlier frame failed on one member");
-    if (g->in_flight > 0)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
-    std::vector<std::vector<int>> lids(W);
-    std::vector<std::vector<uint64_t>> tv(W);
-    std::vector<std::vector<uint32_t>> hv(W);
-    for (int k = 0; k < n; ++k) {
-        const auto w = g->where[(size_t)ids[k]];
-        lids[(size_t)w.first].push_back(w.second);
-        tv[(size_t)w.first].push_back(thr[k]);
-        hv[(size_t)w.first].push_back(hang_frames[k]);
-    }
-    for (size_t k = 0; k < W; ++k) {
-        if (lids[k].empty())
-            continue;
-        const int rc = sdrx_set_squelch(g->m[k].c, lids[k].data(), tv[k].data(), hv[k].data(), (int)lids[k].size());
-        if (rc)
-            return member_fail(g, (int)k, rc);
-    }
-    return SDRX_OK;
+    return group_scatter(g, "sdrx_group_set_squelch", &sdrx_ctx::opt_squelch, "squelch", true, ids, thr && hang_frames, n, nullptr,
+                         [&](sdrx_ctx *m, const Part &p) { return sdrx_set_squelch(m, p.ids.data(), p.pick(thr).data(), p.pick(hang_frames).data(), p.n()); });
 }
 
 int sdrx_group_get_squelch(sdrx_group *g, const int *ids, int n, sdrx_squelch_state *out)
 {
-    if (!g)
-        return SDRX_EINVAL;
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_get_squelch before sdrx_group_finalize");
-    if (n < 0 || (n > 0 && (!ids || !out)))
-        return gfail(g, SDRX_EINVAL, "sdrx_group_get_squelch: n = %d", n);
-    if (int rc = group_check_ids(g, "sdrx_group_get_squelch", ids, n)) // the whole list first: nothing is written for a bad one
-        return rc;
-    for (int k = 0; k < n; ++k) {
-        const auto w = g->where[(size_t)ids[k]];
-        const int rc = sdrx_get_squelch(g->m[(size_t)w.first].c, &w.second, 1, out + k);
-        if (rc)
-            return member_fail(g, w.first, rc);
-    }
-    return SDRX_OK;
+    return group_gather(g, "sdrx_group_get_squelch", ids, n, out, sdrx_get_squelch);
 }
 
-// sdrx_set_squelch_auto over the whole tree, as sdrx_group_set_squelch: everything is checked before any member changes
 int sdrx_group_set_squelch_auto(sdrx_group *g, const int *ids, const uint32_t *ratio_q8, const uint32_t *window_frames, int n)
 {
-    if (!g)
-        return SDRX_EINVAL;
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch_auto before sdrx_group_finalize");
-    if (n < 0 || (n > 0 && (!ids || !ratio_q8 || !window_frames)))
-        return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch_auto: n = %d", n);
-    const size_t W = g->m.size();
-    std::vector<char> seen(g->descs.size(), 0);
-    for (int k = 0; k < n; ++k) {
-        if (int rc = group_check_ids(g, "sdrx_group_set_squelch_auto", ids + k, 1))
-            return rc;
-        const auto w = g->where[(size_t)ids[k]];
-        if (!g->m[(size_t)w.first].c->nodes[(size_t)w.second].leaf)
-            return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch_auto: vfo %d has children and publishes nothing", ids[k]);
-        if (seen[(size_t)ids[k]]++)
-            return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch_auto: vfo %d listed twice", ids[k]);
-        if (ratio_q8[k] > 0 && window_frames[k] == 0)
-            return gfail(g, SDRX_EINVAL, "sdrx_group_set_squelch_auto: vfo %d: window_frames 0 with ratio_q8 %u", ids[k], ratio_q8[k]);
-    }
-    for (size_t k = 0; k < W; ++k)
-        if (g->m[k].c && !g->m[k].c->opt_squelch_auto)
-            return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch_auto: option \"squelch_auto\" is off");
-    if (g->broken)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch_auto: an earlier frame failed on one member");
-    if (g->in_flight > 0)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_squelch_auto: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
-    std::vector<std::vector<int>> lids(W);
-    std::vector<std::vector<uint32_t>> rv(W), wv(W);
-    for (int k = 0; k < n; ++k) {
-        const auto w = g->where[(size_t)ids[k]];
-        lids[(size_t)w.first].push_back(w.second);
-        rv[(size_t)w.first].push_back(ratio_q8[k]);
-        wv[(size_t)w.first].push_back(window_frames[k]);
-    }
-    for (size_t k = 0; k < W; ++k) {
-        if (lids[k].empty())
-            continue;
-        const int rc = sdrx_set_squelch_auto(g->m[k].c, lids[k].data(), rv[k].data(), wv[k].data(), (int)lids[k].size());
-        if (rc)
-            return member_fail(g, (int)k, rc);
-    }
-    return SDRX_OK;
+    return group_scatter(g, "sdrx_group_set_squelch_auto", &sdrx_ctx::opt_squelch_auto, "squelch_auto", true, ids, ratio_q8 && window_frames, n,
+                         [&](int k) { return bad_auto(ratio_q8[k], window_frames[k]); }, [&](sdrx_ctx *m, const Part &p) {
+                             return sdrx_set_squelch_auto(m, p.ids.data(), p.pick(ratio_q8).data(), p.pick(window_frames).data(), p.n());
+                         });
 }
 
 int sdrx_group_get_squelch_auto(sdrx_group *g, const int *ids, int n, sdrx_squelch_auto_state *out)
 {
-    if (!g)
-        return SDRX_EINVAL;
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_get_squelch_auto before sdrx_group_finalize");
-    if (n < 0 || (n > 0 && (!ids || !out)))
-        return gfail(g, SDRX_EINVAL, "sdrx_group_get_squelch_auto: n = %d", n);
-    if (int rc = group_check_ids(g, "sdrx_group_get_squelch_auto", ids, n)) // the whole list first: nothing is written for a bad one
-        return rc;
-    for (int k = 0; k < n; ++k) {
-        const auto w = g->where[(size_t)ids[k]];
-        const int rc = sdrx_get_squelch_auto(g->m[(size_t)w.first].c, &w.second, 1, out + k);
-        if (rc)
-            return member_fail(g, w.first, rc);
-    }
-    return SDRX_OK;
+    return group_gather(g, "sdrx_group_get_squelch_auto", ids, n, out, sdrx_get_squelch_auto);
 }
 
-// sdrx_set_active over the whole tree, as sdrx_group_set_squelch: everything is checked before any member changes
 int sdrx_group_set_active(sdrx_group *g, const int *ids, const int32_t *active, int n)
 {
-    if (!g)
-        return SDRX_EINVAL;
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_active before sdrx_group_finalize");
-    const size_t W = g->m.size();
-    for (size_t k = 0; k < W; ++k)
-        if (g->m[k].c && !g->m[k].c->opt_park)
-            return gfail(g, SDRX_ESTATE, "sdrx_group_set_active: option \"park\" is off");
-    if (n < 0 || (n > 0 && (!ids || !active)))
-        return gfail(g, SDRX_EINVAL, "sdrx_group_set_active: n = %d", n);
-    std::vector<char> seen(g->descs.size(), 0);
-    for (int k = 0; k < n; ++k) {
-        if (int rc = group_check_ids(g, "sdrx_group_set_active", ids + k, 1))
-            return rc;
-        const auto w = g->where[(size_t)ids[k]];
-        if (!g->m[(size_t)w.first].c->nodes[(size_t)w.second].leaf)
-            return gfail(g, SDRX_EINVAL, "sdrx_group_set_active: vfo %d has children and publishes nothing", ids[k]);
-        if (seen[(size_t)ids[k]]++)
-            return gfail(g, SDRX_EINVAL, "sdrx_group_set_active: vfo %d listed twice", ids[k]);
-        if (active[k] != 0 && active[k] != 1)
-            return gfail(g, SDRX_EINVAL, "sdrx_group_set_active: vfo %d: active = %d (0 or 1)", ids[k], active[k]);
-    }
-    if (g->broken)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_active: an earlier frame failed on one member");
-    if (g->in_flight > 0)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_active: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
-    std::vector<std::vector<int>> lids(W);
-    std::vector<std::vector<int32_t>> av(W);
-    for (int k = 0; k < n; ++k) {
-        const auto w = g->where[(size_t)ids[k]];
-        lids[(size_t)w.first].push_back(w.second);
-        av[(size_t)w.first].push_back(active[k]);
-    }
-    for (size_t k = 0; k < W; ++k) {
-        if (lids[k].empty())
-            continue;
-        const int rc = sdrx_set_active(g->m[k].c, lids[k].data(), av[k].data(), (int)lids[k].size());
-        if (rc)
-            return member_fail(g, (int)k, rc);
-    }
-    return SDRX_OK;
+    return group_scatter(g, "sdrx_group_set_active", &sdrx_ctx::opt_park, "park", true, ids, active != nullptr, n, [&](int k) { return bad_switch(active[k]); },
+                         [&](sdrx_ctx *m, const Part &p) { return sdrx_set_active(m, p.ids.data(), p.pick(active).data(), p.n()); });
 }
 
 int sdrx_group_get_active(sdrx_group *g, const int *ids, int n, sdrx_active_state *out)
 {
-    if (!g)
-        return SDRX_EINVAL;
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_get_active before sdrx_group_finalize");
-    if (n < 0 || (n > 0 && (!ids || !out)))
-        return gfail(g, SDRX_EINVAL, "sdrx_group_get_active: n = %d", n);
-    if (int rc = group_check_ids(g, "sdrx_group_get_active", ids, n)) // the whole list first: nothing is written for a bad one
-        return rc;
-    for (int k = 0; k < n; ++k) {
-        const auto w = g->where[(size_t)ids[k]];
-        const int rc = sdrx_get_active(g->m[(size_t)w.first].c, &w.second, 1, out + k);
-        if (rc)
-            return member_fail(g, w.first, rc);
-    }
-    return SDRX_OK;
+    return group_gather(g, "sdrx_group_get_active", ids, n, out, sdrx_get_active);
 }
 
 int sdrx_group_get_catchup(sdrx_group *g, const int *ids, int n, sdrx_meter *out)
 {
-    if (!g)
-        return SDRX_EINVAL;
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_get_catchup before sdrx_group_finalize");
-    if (n < 0 || (n > 0 && (!ids || !out)))
-        return gfail(g, SDRX_EINVAL, "sdrx_group_get_catchup: n = %d", n);
-    if (int rc = group_check_ids(g, "sdrx_group_get_catchup", ids, n)) // the whole list first: nothing is written for a bad one
-        return rc;
-    for (int k = 0; k < n; ++k) {
-        const auto w = g->where[(size_t)ids[k]];
-        const int rc = sdrx_get_catchup(g->m[(size_t)w.first].c, &w.second, 1, out + k);
-        if (rc)
-            return member_fail(g, w.first, rc);
-    }
-    return SDRX_OK;
+    return group_gather(g, "sdrx_group_get_catchup", ids, n, out, sdrx_get_catchup);
 }
 
-// sdrx_set_watch over the whole tree, as sdrx_group_set_active: everything is checked before any member changes
 int sdrx_group_set_watch(sdrx_group *g, const int *ids, const int32_t *on, int n)
 {
-    if (!g)
-        return SDRX_EINVAL;
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_watch before sdrx_group_finalize");
-    const size_t W = g->m.size();
-    for (size_t k = 0; k < W; ++k)
-        if (g->m[k].c && !g->m[k].c->opt_watch)
-            return gfail(g, SDRX_ESTATE, "sdrx_group_set_watch: option \"watch\" is off");
-    if (n < 0 || (n > 0 && (!ids || !on)))
-        return gfail(g, SDRX_EINVAL, "sdrx_group_set_watch: n = %d", n);
-    std::vector<char> seen(g->descs.size(), 0);
-    for (int k = 0; k < n; ++k) {
-        if (int rc = group_check_ids(g, "sdrx_group_set_watch", ids + k, 1))
-            return rc;
-        const auto w = g->where[(size_t)ids[k]];
-        if (!g->m[(size_t)w.first].c->nodes[(size_t)w.second].leaf)
-            return gfail(g, SDRX_EINVAL, "sdrx_group_set_watch: vfo %d has children and publishes nothing", ids[k]);
-        if (seen[(size_t)ids[k]]++)
-            return gfail(g, SDRX_EINVAL, "sdrx_group_set_watch: vfo %d listed twice", ids[k]);
-        if (on[k] != 0 && on[k] != 1)
-            return gfail(g, SDRX_EINVAL, "sdrx_group_set_watch: vfo %d: on = %d (0 or 1)", ids[k], on[k]);
-    }
-    if (g->broken)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_watch: an earlier frame failed on one member");
-    if (g->in_flight > 0)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_watch: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
-    std::vector<std::vector<int>> lids(W);
-    std::vector<std::vector<int32_t>> ov(W);
-    for (int k = 0; k < n; ++k) {
-        const auto w = g->where[(size_t)ids[k]];
-        lids[(size_t)w.first].push_back(w.second);
-        ov[(size_t)w.first].push_back(on[k]);
-    }
-    for (size_t k = 0; k < W; ++k) {
-        if (lids[k].empty())
-            continue;
-        const int rc = sdrx_set_watch(g->m[k].c, lids[k].data(), ov[k].data(), (int)lids[k].size());
-        if (rc)
-            return member_fail(g, (int)k, rc);
-    }
-    return SDRX_OK;
+    return group_scatter(g, "sdrx_group_set_watch", &sdrx_ctx::opt_watch, "watch", true, ids, on != nullptr, n, [&](int k) { return bad_switch(on[k]); },
+                         [&](sdrx_ctx *m, const Part &p) { return sdrx_set_watch(m, p.ids.data(), p.pick(on).data(), p.n()); });
 }
 
 int sdrx_group_get_watch(sdrx_group *g, const int *ids, int n, sdrx_watch_level *out)
 {
-    if (!g)
-        return SDRX_EINVAL;
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_get_watch before sdrx_group_finalize");
-    if (n < 0 || (n > 0 && (!ids || !out)))
-        return gfail(g, SDRX_EINVAL, "sdrx_group_get_watch: n = %d", n);
-    if (int rc = group_check_ids(g, "sdrx_group_get_watch", ids, n)) // the whole list first: nothing is written for a bad one
-        return rc;
-    for (int k = 0; k < n; ++k) {
-        const auto w = g->where[(size_t)ids[k]];
-        const int rc = sdrx_get_watch(g->m[(size_t)w.first].c, &w.second, 1, out + k);
-        if (rc)
-            return member_fail(g, w.first, rc);
-    }
-    return SDRX_OK;
+    return group_gather(g, "sdrx_group_get_watch", ids, n, out, sdrx_get_watch);
 }
 
 int sdrx_group_get_watch_psd(sdrx_group *g, int leaf_id, double *psd, int64_t *frame)
 {
-    if (!g)
-        return SDRX_EINVAL;
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_get_watch_psd before sdrx_group_finalize");
-    if (int rc = group_check_ids(g, "sdrx_group_get_watch_psd", &leaf_id, 1))
+    std::pair<int, int> w;
+    if (int rc = owner(g, "sdrx_group_get_watch_psd", leaf_id, &w))
         return rc;
-    if (g->in_flight > 0)
+    if (g->in_flight > 0) // (the member reads its device: it would say so too, but of ITS frames)
         return gfail(g, SDRX_ESTATE, "sdrx_group_get_watch_psd: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
-    const auto w = g->where[(size_t)leaf_id];
-    const int rc = sdrx_get_watch_psd(g->m[(size_t)w.first].c, w.second, psd, frame);
-    return rc ? member_fail(g, w.first, rc) : SDRX_OK;
+    return member_rc(g, w.first, sdrx_get_watch_psd(g->m[(size_t)w.first].c, w.second, psd, frame));
 }
 
 int sdrx_group_get_egress(sdrx_group *g, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied)
@@ -925,15 +775,9 @@ int sdrx_group_get_egress(sdrx_group *g, int64_t *frame, uint32_t *n_open, uint3
 
 int sdrx_group_get_preroll(sdrx_group *g, int id, const void **buf, uint32_t *len, int64_t *frame)
 {
-    if (!g)
-        return SDRX_EINVAL;
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_get_preroll before sdrx_group_finalize");
-    if (int rc = group_check_ids(g, "sdrx_group_get_preroll", &id, 1))
-        return rc;
-    const auto w = g->where[(size_t)id];
-    const int rc = sdrx_get_preroll(g->m[(size_t)w.first].c, w.second, buf, len, frame);
-    return rc ? member_fail(g, w.first, rc) : SDRX_OK;
+    std::pair<int, int> w;
+    const int rc = owner(g, "sdrx_group_get_preroll", id, &w);
+    return rc ? rc : member_rc(g, w.first, sdrx_get_preroll(g->m[(size_t)w.first].c, w.second, buf, len, frame));
 }
 
 int sdrx_group_get_preroll_count(sdrx_group *g, uint32_t *n_preroll, uint64_t *preroll_bytes)
@@ -981,38 +825,14 @@ int sdrx_group_locate(sdrx_group *g, int id, int *member, int *local_id)
 // others).
 static int group_set_values(sdrx_group *g, const int *ids, const double *freqs, const float *gains, int n, const char *what)
 {
-    if (!g)
-        return SDRX_EINVAL;
-    if (!g->finalized)
-        return gfail(g, SDRX_ESTATE, "%s before sdrx_group_finalize", what);
-    std::string msg;
-    if (check_vfo_list((int)g->descs.size(), ids, freqs ? (const void *)freqs : (const void *)gains, freqs != nullptr, n, msg))
-        return gfail(g, SDRX_EINVAL, "%s: %s", what, msg.c_str());
-    if (g->broken)
-        return gfail(g, SDRX_ESTATE, "%s: an earlier frame failed on one member", what);
-    if (g->in_flight > 0)
-        return gfail(g, SDRX_ESTATE, "%s: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", what, g->in_flight);
-    const size_t W = g->m.size();
-    std::vector<std::vector<int>> lids(W);
-    std::vector<std::vector<double>> fv(W);
-    std::vector<std::vector<float>> gv(W);
-    for (int k = 0; k < n; ++k)
-        for (const auto &r : g->replicas[(size_t)ids[k]]) {
-            lids[(size_t)r.first].push_back(r.second);
-            if (freqs)
-                fv[(size_t)r.first].push_back(freqs[k]);
-            else
-                gv[(size_t)r.first].push_back(gains[k]);
-        }
-    for (size_t k = 0; k < W; ++k) {
-        if (lids[k].empty())
-            continue;
-        const int cnt = (int)lids[k].size();
-        const int rc = freqs ? sdrx_set_mixer_freqs(g->m[k].c, lids[k].data(), fv[k].data(), cnt)
-                             : sdrx_set_gains(g->m[k].c, lids[k].data(), gv[k].data(), cnt);
-        if (rc)
-            return member_fail(g, (int)k, rc);
-    }
+    const int rc = group_scatter(
+        g, what, nullptr, nullptr, false, ids, freqs || gains, n,
+        [&](int k) { return std::isfinite(freqs ? freqs[k] : (double)gains[k]) ? nullptr : "value is not finite"; },
+        [&](sdrx_ctx *m, const Part &p) {
+            return freqs ? sdrx_set_mixer_freqs(m, p.ids.data(), p.pick(freqs).data(), p.n()) : sdrx_set_gains(m, p.ids.data(), p.pick(gains).data(), p.n());
+        });
+    if (rc)
+        return rc;
     for (int k = 0; k < n; ++k) {
         if (freqs)
             g->descs[(size_t)ids[k]].mixer_freq_hz = freqs[k];

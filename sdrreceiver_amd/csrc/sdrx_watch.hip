@@ -184,21 +184,8 @@ extern "C" {
 
 int sdrx_set_watch(sdrx_ctx *c, const int *ids, const int32_t *on, int n)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_set_watch before sdrx_finalize");
-    if (!c->opt_watch)
-        return fail(c, SDRX_ESTATE, "sdrx_set_watch: option \"watch\" is off");
-    if (n < 0 || (n > 0 && (!ids || !on)))
-        return fail(c, SDRX_EINVAL, "sdrx_set_watch: n = %d, ids %p, on %p", n, (const void *)ids, (const void *)on);
-    if (int rc = check_leaf_ids(c, "sdrx_set_watch", ids, n, true))
+    if (int rc = leaf_call(c, "sdrx_set_watch", &sdrx_ctx::opt_watch, "watch", ids, on != nullptr, n, kBetweenFrames, [&](int k) { return bad_switch(on[k]); }))
         return rc;
-    for (int k = 0; k < n; ++k)
-        if (on[k] != 0 && on[k] != 1)
-            return fail(c, SDRX_EINVAL, "sdrx_set_watch: vfo %d: on = %d (0 or 1)", ids[k], on[k]);
-    if (c->in_flight > 0)
-        return fail(c, SDRX_ESTATE, "sdrx_set_watch: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
     if (n == 0)
         return SDRX_OK;
     HIPCHK(c, hipSetDevice(c->device));
@@ -230,20 +217,10 @@ int sdrx_set_watch(sdrx_ctx *c, const int *ids, const int32_t *on, int n)
 
 int sdrx_get_watch(sdrx_ctx *c, const int *ids, int n, sdrx_watch_level *out)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_get_watch before sdrx_finalize");
-    if (!c->opt_watch)
-        return fail(c, SDRX_ESTATE, "sdrx_get_watch: option \"watch\" is off");
-    if (n < 0 || (n > 0 && (!ids || !out)))
-        return fail(c, SDRX_EINVAL, "sdrx_get_watch: n = %d, ids %p, out %p", n, (const void *)ids, (void *)out);
-    if (int rc = check_leaf_ids(c, "sdrx_get_watch", ids, n, false))
+    if (int rc = leaf_call(c, "sdrx_get_watch", &sdrx_ctx::opt_watch, "watch", ids, out != nullptr, n, kDelivered))
         return rc;
     if (n == 0)
         return SDRX_OK;
-    if (int rc = need_delivered(c, "sdrx_get_watch"))
-        return rc;
     watch_host_init(c);
     const sdrx_ctx::Watch &W = c->watch;
     for (int k = 0; k < n; ++k) {
@@ -264,19 +241,10 @@ int sdrx_get_watch(sdrx_ctx *c, const int *ids, int n, sdrx_watch_level *out)
 
 int sdrx_get_watch_psd(sdrx_ctx *c, int leaf_id, double *psd, int64_t *frame)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_get_watch_psd before sdrx_finalize");
-    if (!c->opt_watch)
-        return fail(c, SDRX_ESTATE, "sdrx_get_watch_psd: option \"watch\" is off");
-    if (int rc = check_leaf_ids(c, "sdrx_get_watch_psd", &leaf_id, 1, false))
+    auto unwatched = [&](int) { return c->watch.leaf.empty() || !c->watch.leaf[(size_t)leaf_id].on ? "is not watched (sdrx_set_watch)" : nullptr; };
+    if (int rc = leaf_call(c, "sdrx_get_watch_psd", &sdrx_ctx::opt_watch, "watch", &leaf_id, true, 1, kBetweenFrames, unwatched))
         return rc;
     const sdrx_ctx::Watch &W = c->watch;
-    if (W.leaf.empty() || !W.leaf[(size_t)leaf_id].on)
-        return fail(c, SDRX_EINVAL, "sdrx_get_watch_psd: vfo %d is not watched (sdrx_set_watch)", leaf_id);
-    if (c->in_flight > 0)
-        return fail(c, SDRX_ESTATE, "sdrx_get_watch_psd: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = drain(c))
         return rc;

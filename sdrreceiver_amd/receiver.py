@@ -46,7 +46,144 @@ def _value_list(vids, values, dtype) -> tuple[np.ndarray, np.ndarray]:
     return ids, vals
 
 
-class Receiver:
+class _LeafCalls:
+    """The per-leaf calls a :class:`Receiver` and a :class:`Group` share: ``sdrx_<name>`` on a context, ``sdrx_group_<name>`` --
+    with ids of the whole tree, answered by the member that holds the VFO, the counts summed over the members -- on a group."""
+
+    _prefix = "sdrx_"
+
+    def _call(self, name, *args) -> None:
+        self._chk(getattr(self.L, self._prefix + name)(self.h, *args))
+
+    def _get_list(self, symbol, vids, StructC):
+        """``(ids, records)`` of the batched getter `symbol` for the leaves `vids`."""
+        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        out = (StructC * max(1, ids.size))()
+        self._call(symbol, ids.ctypes.data, ids.size, out)
+        return ids, out[:ids.size]
+
+    def _set_list(self, symbol, vids, *columns) -> tuple[np.ndarray, np.ndarray]:
+        """The batched setter `symbol` with one ``(values, dtype)`` column per array of the call; ``(ids, last column)``."""
+        cols = [_value_list(vids, values, dtype) for values, dtype in columns]
+        ids = cols[0][0]
+        self._call(symbol, ids.ctypes.data, *[v.ctypes.data for _, v in cols], ids.size)
+        return ids, cols[-1][1]
+
+    def _payload(self, vid, buf, length) -> np.ndarray:
+        raw = C.string_at(buf.value, length.value) if length.value else b""
+        return np.frombuffer(raw, dtype=np.int16 if self.descs[vid].demod_usb else np.int8).copy()
+
+    def output(self, vid: int) -> np.ndarray:
+        """Leaf `vid`'s payload of the last delivered frame (int16 audio or int8 I/Q)."""
+        buf, ln, rate = C.c_void_p(), C.c_uint32(), C.c_uint32()
+        self._call("get_output", vid, C.byref(buf), C.byref(ln), C.byref(rate))
+        return self._payload(vid, buf, ln)
+
+    def meters(self, vids) -> dict:
+        """Output meters of the leaves `vids` for the last delivered frame (option ``meter``): arrays in the order of
+        `vids` -- see :func:`sdrreceiver_amd.meter.meters_dict`."""
+        ids, out = self._get_list("get_meters", vids, _lib.MeterC)
+        return meter.meters_dict(out, [self.descs[i].demod_usb for i in ids.tolist()])
+
+    # -- squelch-gated egress (option ``squelch``; sdrreceiver_amd.squelch has the definition) ---------------------
+    def set_squelch(self, vids, thr_sum_sq, hang_frames) -> None:
+        """Leaf vids[k] opens when its meter ``sum_sq`` reaches thr_sum_sq[k] and stays open hang_frames[k] frames
+        after it last did; from the next frame on.  Resets the named leaves' ``hang_left``."""
+        self._set_list("set_squelch", vids, (thr_sum_sq, np.uint64), (hang_frames, np.uint32))
+
+    def squelch(self, vids) -> dict:
+        """Squelch state of the leaves `vids` after the last delivered frame: ``frame``, ``thr_sum_sq``,
+        ``hang_frames``, ``hang_left``, ``open`` as arrays in the order of `vids`."""
+        return _squelch.squelch_dict(self._get_list("get_squelch", vids, _lib.SquelchStateC)[1])
+
+    def egress(self) -> dict:
+        """What the last delivered frame's payload copy moved: ``frame``, ``n_open``, ``n_leaves``,
+        ``payload_bytes_copied``."""
+        f, o, n, b = C.c_int64(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._call("get_egress", C.byref(f), C.byref(o), C.byref(n), C.byref(b))
+        return {"frame": f.value, "n_open": o.value, "n_leaves": n.value, "payload_bytes_copied": b.value}
+
+    def preroll(self, vid: int) -> np.ndarray:
+        """Option ``preroll``: leaf `vid`'s payload of the frame before the delivered one, if the leaf has just opened (what
+        the callback saw first); an empty array of the leaf's dtype otherwise."""
+        buf, ln, f = C.c_void_p(), C.c_uint32(), C.c_int64()
+        self._call("get_preroll", vid, C.byref(buf), C.byref(ln), C.byref(f))
+        return self._payload(vid, buf, ln)
+
+    def preroll_count(self) -> dict:
+        """Pre-rolled leaves of the last delivered frame and the bytes that added to its copy: ``n_preroll``,
+        ``preroll_bytes``."""
+        n, b = C.c_uint32(), C.c_uint64()
+        self._call("get_preroll_count", C.byref(n), C.byref(b))
+        return {"n_preroll": n.value, "preroll_bytes": b.value}
+
+    # -- auto-squelch (option ``squelch_auto``): the threshold as a ratio over the leaf's tracked noise floor -----------
+    def set_squelch_auto(self, vids, ratio_q8, window_frames) -> None:
+        """Leaf vids[k]'s threshold becomes ``max(thr, floor * ratio_q8[k] / 256)``, the floor being the minimum ``sum_sq``
+        of the last ``window_frames[k]`` .. ``2 * window_frames[k] - 1`` frames (:func:`sdrreceiver_amd.squelch.decide_auto`);
+        ``ratio_q8`` 0 switches it off for the leaf.  Restarts the named leaves' floor."""
+        self._set_list("set_squelch_auto", vids, (ratio_q8, np.uint32), (window_frames, np.uint32))
+
+    def squelch_auto(self, vids) -> dict:
+        """What decided the last delivered frame for the leaves `vids`: ``frame``, ``floor_sum_sq``, ``thr_eff_sum_sq``,
+        ``ratio_q8``, ``window_frames``, ``floor_valid`` as arrays in the order of `vids`."""
+        return _squelch.squelch_auto_dict(self._get_list("get_squelch_auto", vids, _lib.SquelchAutoStateC)[1])
+
+    # -- parking (option ``park``): leaves switched off and on between frames --------------------------------------------
+    def set_active(self, vids, active) -> None:
+        """Park (``active[k]`` 0) or unpark (1) the leaves `vids` before the next frame.  A parked leaf costs no arithmetic and
+        is delivered like a closed one; an unparked leaf starts as a new VFO does (fresh oscillator, zero filter state)."""
+        self._set_list("set_active", vids, (active, np.int32))
+
+    def active(self, vids) -> dict:
+        """``active`` and ``since_frame`` (the first frame in the present state; a group counts its own frames) of the leaves
+        `vids`, as arrays."""
+        _, out = self._get_list("get_active", vids, _lib.ActiveStateC)
+        return {"active": np.array([o.active for o in out], dtype=np.int32),
+                "since_frame": np.array([o.since_frame for o in out], dtype=np.int64)}
+
+    def catchup(self, vids) -> dict:
+        """Option ``catchup``: the meter of the frame each of the leaves `vids` was caught up in -- the frame before the one
+        :meth:`set_active` unparked it for, run on the parent's stream the device still held -- as :meth:`meters` gives it;
+        ``frame`` is -1 (and the figures 0) for a leaf whose present active state did not begin with a catch-up.  Good as
+        soon as :meth:`set_active` has returned."""
+        ids, out = self._get_list("get_catchup", vids, _lib.MeterC)
+        return meter.meters_dict(out, [self.descs[i].demod_usb for i in ids.tolist()])
+
+    # -- channel watch (option ``watch``; sdrreceiver_amd.watch): band power of a leaf from its source's spectrum -------------
+    def set_watch(self, vids, on) -> None:
+        """Watch (``on[k]`` 1) or stop watching (0) the leaves `vids` from the next frame on, whether they are active or
+        parked."""
+        self._set_list("set_watch", vids, (on, np.int32))
+
+    def watch(self, vids) -> dict:
+        """Watch figures of the leaves `vids` for the last delivered frame: ``frame``, ``band_pwr``, ``total_pwr``,
+        ``first_bin``, ``n_bins``, ``segments``, ``watched`` as arrays in the order of `vids`."""
+        return _watch.watch_dict(self._get_list("get_watch", vids, _lib.WatchLevelC)[1])
+
+    def watch_psd(self, vid: int) -> tuple[np.ndarray, int]:
+        """``(PSD, frame)``: the power spectrum (8192 float64, kiss_fft's natural order) of the source of watched leaf `vid`
+        after the last frame."""
+        psd = np.zeros(_lib.SPECTRUM_BINS, np.float64)
+        f = C.c_int64()
+        self._call("get_watch_psd", int(vid), psd.ctypes.data, C.byref(f))
+        return psd, f.value
+
+    # -- retuning between frames (on a group: on every member that holds the VFO) -------------------------------------------
+    def set_mixer_freqs(self, vids, freqs) -> None:
+        """VFO vids[k] mixes with a fresh oscillator at freqs[k] Hz from the next frame on; every filter state is kept."""
+        ids, vals = self._set_list("set_mixer_freqs", vids, (freqs, np.float64))
+        for i, f in zip(ids.tolist(), vals.tolist()):
+            self.descs[i] = dataclasses.replace(self.descs[i], mixer_freq=f)
+
+    def set_gains(self, vids, gains) -> None:
+        """vfo::setGain of VFO vids[k] between two frames: from the next frame on."""
+        ids, vals = self._set_list("set_gains", vids, (gains, np.float32))
+        for i, g in zip(ids.tolist(), vals.tolist()):
+            self.descs[i] = dataclasses.replace(self.descs[i], gain=g)
+
+
+class Receiver(_LeafCalls):
     """One libsdrx context: a VFO tree on one GPU."""
 
     def __init__(self, device: int = 0, exact: bool = True, keep_prequant: bool = False, segments: int = 0,
@@ -218,123 +355,6 @@ class Receiver:
         self._chk(self.L.sdrx_set_stream(self.h, C.c_void_p(hip_stream or 0)))
 
     # -- results ------------------------------------------------------------------------
-    def output(self, vid: int) -> np.ndarray:
-        buf, ln, rate = C.c_void_p(), C.c_uint32(), C.c_uint32()
-        self._chk(self.L.sdrx_get_output(self.h, vid, C.byref(buf), C.byref(ln), C.byref(rate)))
-        raw = C.string_at(buf.value, ln.value)
-        return np.frombuffer(raw, dtype=np.int16 if self.descs[vid].demod_usb else np.int8).copy()
-
-    def meters(self, vids) -> dict:
-        """Output meters of the leaves `vids` for the last delivered frame (option ``meter``): arrays in the order of
-        `vids` -- see :func:`sdrreceiver_amd.meter.meters_dict`."""
-        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
-        out = (_lib.MeterC * max(1, ids.size))()
-        self._chk(self.L.sdrx_get_meters(self.h, ids.ctypes.data, ids.size, out))
-        return meter.meters_dict(out[:ids.size], [self.descs[i].demod_usb for i in ids.tolist()])
-
-    # -- squelch-gated egress (option ``squelch``; sdrreceiver_amd.squelch has the definition) ---------------------
-    def set_squelch(self, vids, thr_sum_sq, hang_frames) -> None:
-        """Leaf vids[k] opens when its meter ``sum_sq`` reaches thr_sum_sq[k] and stays open hang_frames[k] frames
-        after it last did; from the next frame on.  Resets the named leaves' ``hang_left``."""
-        ids, thr = _value_list(vids, thr_sum_sq, np.uint64)
-        _, hang = _value_list(vids, hang_frames, np.uint32)
-        self._chk(self.L.sdrx_set_squelch(self.h, ids.ctypes.data, thr.ctypes.data, hang.ctypes.data, ids.size))
-
-    def squelch(self, vids) -> dict:
-        """Squelch state of the leaves `vids` after the last delivered frame: ``frame``, ``thr_sum_sq``,
-        ``hang_frames``, ``hang_left``, ``open`` as arrays in the order of `vids`."""
-        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
-        out = (_lib.SquelchStateC * max(1, ids.size))()
-        self._chk(self.L.sdrx_get_squelch(self.h, ids.ctypes.data, ids.size, out))
-        return _squelch.squelch_dict(out[:ids.size])
-
-    def egress(self) -> dict:
-        """What the last delivered frame's payload copy moved: ``frame``, ``n_open``, ``n_leaves``,
-        ``payload_bytes_copied``."""
-        f, o, n, b = C.c_int64(), C.c_uint32(), C.c_uint32(), C.c_uint64()
-        self._chk(self.L.sdrx_get_egress(self.h, C.byref(f), C.byref(o), C.byref(n), C.byref(b)))
-        return {"frame": f.value, "n_open": o.value, "n_leaves": n.value, "payload_bytes_copied": b.value}
-
-    def preroll(self, vid: int) -> np.ndarray:
-        """Option ``preroll``: leaf `vid`'s payload of the frame before the delivered one, if the leaf has just opened (what
-        the callback saw first); an empty array of the leaf's dtype otherwise."""
-        buf, ln, f = C.c_void_p(), C.c_uint32(), C.c_int64()
-        self._chk(self.L.sdrx_get_preroll(self.h, vid, C.byref(buf), C.byref(ln), C.byref(f)))
-        raw = C.string_at(buf.value, ln.value) if ln.value else b""
-        return np.frombuffer(raw, dtype=np.int16 if self.descs[vid].demod_usb else np.int8).copy()
-
-    def preroll_count(self) -> dict:
-        """Pre-rolled leaves of the last delivered frame and the bytes that added to its copy: ``n_preroll``,
-        ``preroll_bytes``."""
-        n, b = C.c_uint32(), C.c_uint64()
-        self._chk(self.L.sdrx_get_preroll_count(self.h, C.byref(n), C.byref(b)))
-        return {"n_preroll": n.value, "preroll_bytes": b.value}
-
-    # -- auto-squelch (option ``squelch_auto``): the threshold as a ratio over the leaf's tracked noise floor -----------
-    def set_squelch_auto(self, vids, ratio_q8, window_frames) -> None:
-        """Leaf vids[k]'s threshold becomes ``max(thr, floor * ratio_q8[k] / 256)``, the floor being the minimum ``sum_sq``
-        of the last ``window_frames[k]`` .. ``2 * window_frames[k] - 1`` frames (:func:`sdrreceiver_amd.squelch.decide_auto`);
-        ``ratio_q8`` 0 switches it off for the leaf.  Restarts the named leaves' floor."""
-        ids, ratio = _value_list(vids, ratio_q8, np.uint32)
-        _, win = _value_list(vids, window_frames, np.uint32)
-        self._chk(self.L.sdrx_set_squelch_auto(self.h, ids.ctypes.data, ratio.ctypes.data, win.ctypes.data, ids.size))
-
-    def squelch_auto(self, vids) -> dict:
-        """What decided the last delivered frame for the leaves `vids`: ``frame``, ``floor_sum_sq``, ``thr_eff_sum_sq``,
-        ``ratio_q8``, ``window_frames``, ``floor_valid`` as arrays in the order of `vids`."""
-        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
-        out = (_lib.SquelchAutoStateC * max(1, ids.size))()
-        self._chk(self.L.sdrx_get_squelch_auto(self.h, ids.ctypes.data, ids.size, out))
-        return _squelch.squelch_auto_dict(out[:ids.size])
-
-    # -- parking (option ``park``): leaves switched off and on between frames --------------------------------------------
-    def set_active(self, vids, active) -> None:
-        """Park (``active[k]`` 0) or unpark (1) the leaves `vids` before the next frame.  A parked leaf costs no arithmetic and
-        is delivered like a closed one; an unparked leaf starts as a new VFO does (fresh oscillator, zero filter state)."""
-        ids, act = _value_list(vids, active, np.int32)
-        self._chk(self.L.sdrx_set_active(self.h, ids.ctypes.data, act.ctypes.data, ids.size))
-
-    def active(self, vids) -> dict:
-        """``active`` and ``since_frame`` (the first frame in the present state) of the leaves `vids`, as arrays."""
-        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
-        out = (_lib.ActiveStateC * max(1, ids.size))()
-        self._chk(self.L.sdrx_get_active(self.h, ids.ctypes.data, ids.size, out))
-        return {"active": np.array([o.active for o in out[:ids.size]], dtype=np.int32),
-                "since_frame": np.array([o.since_frame for o in out[:ids.size]], dtype=np.int64)}
-
-    def catchup(self, vids) -> dict:
-        """Option ``catchup``: the meter of the frame each of the leaves `vids` was caught up in -- the frame before the one
-        :meth:`set_active` unparked it for, run on the parent's stream the device still held -- as :meth:`meters` gives it;
-        ``frame`` is -1 (and the figures 0) for a leaf whose present active state did not begin with a catch-up.  Good as
-        soon as :meth:`set_active` has returned."""
-        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
-        out = (_lib.MeterC * max(1, ids.size))()
-        self._chk(self.L.sdrx_get_catchup(self.h, ids.ctypes.data, ids.size, out))
-        return meter.meters_dict(out[:ids.size], [self.descs[i].demod_usb for i in ids.tolist()])
-
-    # -- channel watch (option ``watch``; sdrreceiver_amd.watch): band power of a leaf from its source's spectrum -------------
-    def set_watch(self, vids, on) -> None:
-        """Watch (``on[k]`` 1) or stop watching (0) the leaves `vids` from the next frame on, whether they are active or
-        parked."""
-        ids, val = _value_list(vids, on, np.int32)
-        self._chk(self.L.sdrx_set_watch(self.h, ids.ctypes.data, val.ctypes.data, ids.size))
-
-    def watch(self, vids) -> dict:
-        """Watch figures of the leaves `vids` for the last delivered frame: ``frame``, ``band_pwr``, ``total_pwr``,
-        ``first_bin``, ``n_bins``, ``segments``, ``watched`` as arrays in the order of `vids`."""
-        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
-        out = (_lib.WatchLevelC * max(1, ids.size))()
-        self._chk(self.L.sdrx_get_watch(self.h, ids.ctypes.data, ids.size, out))
-        return _watch.watch_dict(out[:ids.size])
-
-    def watch_psd(self, vid: int) -> tuple[np.ndarray, int]:
-        """``(PSD, frame)``: the power spectrum (8192 float64, kiss_fft's natural order) of the source of watched leaf `vid`
-        after the last frame."""
-        psd = np.zeros(_lib.SPECTRUM_BINS, np.float64)
-        f = C.c_int64()
-        self._chk(self.L.sdrx_get_watch_psd(self.h, int(vid), psd.ctypes.data, C.byref(f)))
-        return psd, f.value
-
     def output_rate(self, vid: int) -> int:
         rate = C.c_uint32()
         self._chk(self.L.sdrx_get_output(self.h, vid, None, None, C.byref(rate)))
@@ -398,21 +418,6 @@ class Receiver:
         self._chk(self.L.sdrx_get_nco(self.h, vid, first, count, out.ctypes.data))
         return out[: 2 * count].view(np.complex64).copy()
 
-    # -- retuning between frames (sdrx_set_mixer_freqs / sdrx_set_gains) ------------------------------------------
-    def set_mixer_freqs(self, vids, freqs) -> None:
-        """VFO vids[k] mixes with a fresh oscillator at freqs[k] Hz from the next frame on; every filter state is kept."""
-        ids, vals = _value_list(vids, freqs, np.float64)
-        self._chk(self.L.sdrx_set_mixer_freqs(self.h, ids.ctypes.data, vals.ctypes.data, ids.size))
-        for i, f in zip(ids.tolist(), vals.tolist()):
-            self.descs[i] = dataclasses.replace(self.descs[i], mixer_freq=f)
-
-    def set_gains(self, vids, gains) -> None:
-        """vfo::setGain of VFO vids[k] between two frames: from the next frame on."""
-        ids, vals = _value_list(vids, gains, np.float32)
-        self._chk(self.L.sdrx_set_gains(self.h, ids.ctypes.data, vals.ctypes.data, ids.size))
-        for i, g in zip(ids.tolist(), vals.tolist()):
-            self.descs[i] = dataclasses.replace(self.descs[i], gain=g)
-
     # -- spectrum display (MainWindow::fftHandlerSlot on the device) ---------------------------------------------
     def set_spectrum(self, vid: int, on: bool = True) -> None:
         """Enable (and zero: the GUI's combo-box reset) or release the spectrum of VFO `vid`, or of the raw frame with
@@ -458,11 +463,13 @@ class Receiver:
                 for k in range(_lib.NKERNELS) if n[k]}
 
 
-class Group:
+class Group(_LeafCalls):
     """One VFO tree on several GPUs from this one process (``sdrx_group_*``): one context per entry of
     `devices` (a device may be named twice: two shards on one GPU), sub VFOs block-partitioned per
     main VFO, the raw frame fanned out from the first device by peer-to-peer copies.  Ids are those of
     the whole tree; `published` holds the last delivered frame's messages in the reference's order."""
+
+    _prefix = "sdrx_group_"
 
     def __init__(self, devices, exact: bool = True, **options):
         # (`options`: the library's option names as keywords -- meter=1, squelch=1, preroll=1, squelch_auto=1, ...)
@@ -560,121 +567,10 @@ class Group:
     def in_flight(self) -> int:
         return int(self.L.sdrx_group_in_flight(self.h))
 
-    def output(self, vid: int) -> np.ndarray:
-        buf, ln, rate = C.c_void_p(), C.c_uint32(), C.c_uint32()
-        self._chk(self.L.sdrx_group_get_output(self.h, vid, C.byref(buf), C.byref(ln), C.byref(rate)))
-        raw = C.string_at(buf.value, ln.value)
-        return np.frombuffer(raw, dtype=np.int16 if self.descs[vid].demod_usb else np.int8).copy()
-
-    def meters(self, vids) -> dict:
-        """:meth:`Receiver.meters` with ids of the whole tree (group option ``meter=1``)."""
-        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
-        out = (_lib.MeterC * max(1, ids.size))()
-        self._chk(self.L.sdrx_group_get_meters(self.h, ids.ctypes.data, ids.size, out))
-        return meter.meters_dict(out[:ids.size], [self.descs[i].demod_usb for i in ids.tolist()])
-
-    def set_squelch(self, vids, thr_sum_sq, hang_frames) -> None:
-        """:meth:`Receiver.set_squelch` with ids of the whole tree (group option ``squelch=1``)."""
-        ids, thr = _value_list(vids, thr_sum_sq, np.uint64)
-        _, hang = _value_list(vids, hang_frames, np.uint32)
-        self._chk(self.L.sdrx_group_set_squelch(self.h, ids.ctypes.data, thr.ctypes.data, hang.ctypes.data, ids.size))
-
-    def squelch(self, vids) -> dict:
-        """:meth:`Receiver.squelch` with ids of the whole tree."""
-        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
-        out = (_lib.SquelchStateC * max(1, ids.size))()
-        self._chk(self.L.sdrx_group_get_squelch(self.h, ids.ctypes.data, ids.size, out))
-        return _squelch.squelch_dict(out[:ids.size])
-
-    def egress(self) -> dict:
-        """:meth:`Receiver.egress`, summed over the members."""
-        f, o, n, b = C.c_int64(), C.c_uint32(), C.c_uint32(), C.c_uint64()
-        self._chk(self.L.sdrx_group_get_egress(self.h, C.byref(f), C.byref(o), C.byref(n), C.byref(b)))
-        return {"frame": f.value, "n_open": o.value, "n_leaves": n.value, "payload_bytes_copied": b.value}
-
-    def preroll(self, vid: int) -> np.ndarray:
-        """:meth:`Receiver.preroll` with an id of the whole tree (group option ``preroll=1``)."""
-        buf, ln, f = C.c_void_p(), C.c_uint32(), C.c_int64()
-        self._chk(self.L.sdrx_group_get_preroll(self.h, vid, C.byref(buf), C.byref(ln), C.byref(f)))
-        raw = C.string_at(buf.value, ln.value) if ln.value else b""
-        return np.frombuffer(raw, dtype=np.int16 if self.descs[vid].demod_usb else np.int8).copy()
-
-    def preroll_count(self) -> dict:
-        """:meth:`Receiver.preroll_count`, summed over the members."""
-        n, b = C.c_uint32(), C.c_uint64()
-        self._chk(self.L.sdrx_group_get_preroll_count(self.h, C.byref(n), C.byref(b)))
-        return {"n_preroll": n.value, "preroll_bytes": b.value}
-
-    def set_squelch_auto(self, vids, ratio_q8, window_frames) -> None:
-        """:meth:`Receiver.set_squelch_auto` with ids of the whole tree (group option ``squelch_auto=1``)."""
-        ids, ratio = _value_list(vids, ratio_q8, np.uint32)
-        _, win = _value_list(vids, window_frames, np.uint32)
-        self._chk(self.L.sdrx_group_set_squelch_auto(self.h, ids.ctypes.data, ratio.ctypes.data, win.ctypes.data, ids.size))
-
-    def squelch_auto(self, vids) -> dict:
-        """:meth:`Receiver.squelch_auto` with ids of the whole tree."""
-        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
-        out = (_lib.SquelchAutoStateC * max(1, ids.size))()
-        self._chk(self.L.sdrx_group_get_squelch_auto(self.h, ids.ctypes.data, ids.size, out))
-        return _squelch.squelch_auto_dict(out[:ids.size])
-
-    def set_active(self, vids, active) -> None:
-        """:meth:`Receiver.set_active` with ids of the whole tree (group option ``park=1``)."""
-        ids, act = _value_list(vids, active, np.int32)
-        self._chk(self.L.sdrx_group_set_active(self.h, ids.ctypes.data, act.ctypes.data, ids.size))
-
-    def active(self, vids) -> dict:
-        """:meth:`Receiver.active` with ids of the whole tree; ``since_frame`` counts the group's frames."""
-        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
-        out = (_lib.ActiveStateC * max(1, ids.size))()
-        self._chk(self.L.sdrx_group_get_active(self.h, ids.ctypes.data, ids.size, out))
-        return {"active": np.array([o.active for o in out[:ids.size]], dtype=np.int32),
-                "since_frame": np.array([o.since_frame for o in out[:ids.size]], dtype=np.int64)}
-
-    def catchup(self, vids) -> dict:
-        """:meth:`Receiver.catchup` with ids of the whole tree (group option ``catchup=1``)."""
-        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
-        out = (_lib.MeterC * max(1, ids.size))()
-        self._chk(self.L.sdrx_group_get_catchup(self.h, ids.ctypes.data, ids.size, out))
-        return meter.meters_dict(out[:ids.size], [self.descs[i].demod_usb for i in ids.tolist()])
-
-    def set_watch(self, vids, on) -> None:
-        """:meth:`Receiver.set_watch` with ids of the whole tree (group option ``watch=1``)."""
-        ids, val = _value_list(vids, on, np.int32)
-        self._chk(self.L.sdrx_group_set_watch(self.h, ids.ctypes.data, val.ctypes.data, ids.size))
-
-    def watch(self, vids) -> dict:
-        """:meth:`Receiver.watch` with ids of the whole tree."""
-        ids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
-        out = (_lib.WatchLevelC * max(1, ids.size))()
-        self._chk(self.L.sdrx_group_get_watch(self.h, ids.ctypes.data, ids.size, out))
-        return _watch.watch_dict(out[:ids.size])
-
-    def watch_psd(self, vid: int) -> tuple[np.ndarray, int]:
-        """:meth:`Receiver.watch_psd` with an id of the whole tree, from the member that owns the leaf."""
-        psd = np.zeros(_lib.SPECTRUM_BINS, np.float64)
-        f = C.c_int64()
-        self._chk(self.L.sdrx_group_get_watch_psd(self.h, int(vid), psd.ctypes.data, C.byref(f)))
-        return psd, f.value
-
     def locate(self, vid: int) -> tuple[int, int]:
         m, l = C.c_int(), C.c_int()
         self._chk(self.L.sdrx_group_locate(self.h, vid, C.byref(m), C.byref(l)))
         return m.value, l.value
-
-    def set_mixer_freqs(self, vids, freqs) -> None:
-        """:meth:`Receiver.set_mixer_freqs` with ids of the whole tree, on every member that holds the VFO."""
-        ids, vals = _value_list(vids, freqs, np.float64)
-        self._chk(self.L.sdrx_group_set_mixer_freqs(self.h, ids.ctypes.data, vals.ctypes.data, ids.size))
-        for i, f in zip(ids.tolist(), vals.tolist()):
-            self.descs[i] = dataclasses.replace(self.descs[i], mixer_freq=f)
-
-    def set_gains(self, vids, gains) -> None:
-        """:meth:`Receiver.set_gains` with ids of the whole tree."""
-        ids, vals = _value_list(vids, gains, np.float32)
-        self._chk(self.L.sdrx_group_set_gains(self.h, ids.ctypes.data, vals.ctypes.data, ids.size))
-        for i, g in zip(ids.tolist(), vals.tolist()):
-            self.descs[i] = dataclasses.replace(self.descs[i], gain=g)
 
     def member_stats(self) -> list[dict | None]:
         out = []
