@@ -21,7 +21,8 @@ NONE = sq.NONE
 
 def gate_with_parking(sum_sq, events, thr, hang_frames, ratio_q8=0, window_frames=0):
     """One leaf over the frames of `sum_sq` (python ints; the value of a parked frame is never looked at).  `events[f]`: what
-    happens before frame f, a string of 'p' (park) and 'u' (unpark) applied in order -- "pu" restarts the leaf.  Returns one
+    happens before frame f, a string of 'p' (park), 'u' (unpark) and 'c' (an unpark that catches up, option "catchup": as 'u',
+    but prev_open = 0, so that an open frame K pre-rolls the caught-up frame) applied in order -- "pu" restarts the leaf.  Returns one
     dict per frame: active, open, pre, hang_left, prev_open, cur_min, prev_min, age (the state AFTER the frame), thr_eff and
     floor (what decided it; floor NONE = no observation).  `thr` may be a list: the threshold in force in each frame (with
     hang_frames 0, where sdrx_set_squelch's restart of hang_left changes nothing)."""
@@ -33,8 +34,8 @@ def gate_with_parking(sum_sq, events, thr, hang_frames, ratio_q8=0, window_frame
         for e in events.get(f, ""):
             if e == "p":
                 active = 0
-            elif e == "u" and not active:
-                active, left, prev_open, cur, prev, age = 1, 0, 1, NONE, NONE, 0
+            elif e in "uc" and not active:
+                active, left, prev_open, cur, prev, age = 1, 0, int(e == "u"), NONE, NONE, 0
         floor = min(cur, prev)
         auto = 0 if ratio == 0 or floor == NONE else min(NONE, (floor * ratio) >> 8)
         eff = max(thr_of(f), auto)
