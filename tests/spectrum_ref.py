@@ -44,6 +44,7 @@ def digit_reversed_positions(n: int = N) -> np.ndarray:
 
 _TW = None
 _POS = None
+_HANN = None
 
 
 def _cmul(ar, ai, br, bi):
@@ -100,8 +101,11 @@ def kiss_fft(x: np.ndarray) -> np.ndarray:
 def windowed(x: np.ndarray) -> np.ndarray:
     """inr: the first min(len, 8192) samples times the window (complex<float> * float), zero-padded."""
     x = np.asarray(x, np.complex64).reshape(-1)
+    global _HANN
+    if _HANN is None:
+        _HANN = hann()
     n = min(x.size, N)
-    h = hann()
+    h = _HANN
     out = np.zeros(N, np.complex64)
     out.real[:n] = x.real[:n] * h[:n]
     out.imag[:n] = x.imag[:n] * h[:n]
