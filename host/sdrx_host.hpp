@@ -193,6 +193,21 @@ public:
             throw std::invalid_argument("set_squelch_auto: lists of different length");
         call("set_squelch_auto", sdrx_group_set_squelch_auto, sdrx_set_squelch_auto, ids.data(), ratio_q8.data(), window_frames.data(), (int)ids.size());
     }
+    // Device-side AGC (library option "agc" = 1): USB leaf ids[k]'s gain follows its output meter between frames by the rule of
+    // sdrx.h (cfgs[k].hi_ms 0 = off for the leaf); between two frames.  Restarts the named leaves' quiet_run.  agc(): what the
+    // step did behind the last delivered frame -- and how a host reads a gain the device steps.
+    void set_agc(const std::vector<int> &ids, const std::vector<sdrx_agc_cfg> &cfgs)
+    {
+        if (ids.size() != cfgs.size())
+            throw std::invalid_argument("set_agc: lists of different length");
+        call("set_agc", sdrx_group_set_agc, sdrx_set_agc, ids.data(), cfgs.data(), (int)ids.size());
+    }
+    std::vector<sdrx_agc_state> agc(const std::vector<int> &ids)
+    {
+        std::vector<sdrx_agc_state> out(ids.size());
+        call("get_agc", sdrx_group_get_agc, sdrx_get_agc, ids.data(), (int)ids.size(), out.data());
+        return out;
+    }
     // Parking (library option "park" = 1): leaf ids[k] is parked (active[k] 0: no arithmetic, delivered like a closed leaf) or
     // unparked (1: a new vfo from the next frame on -- fresh oscillator, zero filter state); between two frames.
     void set_active(const std::vector<int> &ids, const std::vector<int32_t> &active)

@@ -174,6 +174,10 @@ int sdrx_add_vfo(sdrx_ctx *ctx, const sdrx_vfo_desc *desc, int *id_out);
  *            same kernels, launches, device_bytes, payloads and callbacks, and sdrx_get_catchup returns SDRX_ESTATE.  With 1
  *            and nothing caught up every frame is what "park" = 1 with "preroll" = 1 gives.  A
  *            sdrx_finalize that fails leaves the options as they were set, as with "preroll".
+ *   "agc" 0 (default) | 1: the gain of every USB leaf follows its output meter between frames, on the device (sdrx_set_agc
+ *            below); 1 implies "meter".  0 changes nothing: the same kernels, launches, device_bytes, payloads and callbacks,
+ *            and the AGC calls return SDRX_ESTATE.  With 1 and every hi_ms 0 (the start) every frame is what "meter" = 1 gives;
+ *            one more small launch per frame, and the planning rules of "preroll" on "fuse_demod" trees.
  *   "dc_blocked_scan" 0|1 (default 0): how sdrx_process_u8 removes the DC bias.  0 = the
  *                 reference's sequentially rounded fp32 recurrence, bit for bit (below).  1 = the same linear filter as a
  *                 blocked parallel scan (~15 us): the true IIR response.  The reference's recurrence
@@ -558,6 +562,69 @@ int sdrx_get_nco(sdrx_ctx *ctx, int id, long first, long count, float *out_iq);
 int sdrx_set_mixer_freqs(sdrx_ctx *ctx, const int *ids, const double *mixer_freq_hz, int n);
 int sdrx_set_gains(sdrx_ctx *ctx, const int *ids, const float *gains, int n);
 
+/* ---- device-side AGC (option "agc" = 1) ------------------------------------------------------------------------
+ * After every frame a small kernel steps the gain of each USB leaf from that frame's output meter, for the NEXT frame.  The
+ * reference has no AGC (its README tells the user to move the VFO gain until JAERO's volume light is green); a change of gain
+ * between two frames is the reference's own vfo::setGain between two vfo::process calls, so every frame stays bit for bit what
+ * the reference produces with the gain that frame had.  Settings per leaf (sdrx_agc_cfg, 32 bytes, all zero after
+ * sdrx_finalize: AGC off) and one word of device state, quiet_run (0 after sdrx_finalize and after every sdrx_set_agc that
+ * names the leaf).  The gain itself is the float the demodulation reads (what sdrx_set_gains sets).
+ * The step, for every frame f the context processes, on whichever path, once the leaf's meter records of f are complete; with
+ * s = the leaf's sum_sq, n = n_values, clipped as sdrx_get_meters defines them, g = the gain frame f was computed with, products
+ * in uint64 (< 2^62: no overflow):
+ *     parked in f, or n == 0, or hi_ms == 0:   g' = g, action 0, quiet_run unchanged
+ *     hot    = clipped > 0 || s > (u64)hi_ms * n
+ *     silent = !hot && s < (u64)silent_ms * n
+ *     cold   = !hot && !silent && s < (u64)lo_ms * n
+ *     hot:     g' = clamp(fl(g * down)); quiet_run = 0; action -1
+ *     silent:  g' = g; action 0; quiet_run unchanged
+ *     cold:    quiet_run = min(quiet_run + 1, 2^32 - 1);
+ *              if quiet_run > hold_frames: g' = clamp(fl(g * up)), action +1   else g' = g, action 0
+ *     else:    g' = g; quiet_run = 0; action 0
+ *     clamp(x) = fminf(fmaxf(x, gain_min), gain_max)    (one fp32 multiply, no contraction; an overflow to +inf clamps to gain_max)
+ * hot wins because a wrapped payload's sum_sq is that of the wrapped values.  The clamp acts only when the AGC moves the gain:
+ * a gain the host set outside [gain_min, gain_max] stays while the leaf is in its window.
+ * Choosing the window: the output scales with g, its mean square with g^2, so a steady input never alternates between the two
+ * steps when hi_ms >= lo_ms * max(up^2, 1 / down^2).  (Not validated: the comparison would mix integers and floats.)  No default
+ * window or step is offered: what JAERO's green light corresponds to has not been measured.
+ * sdrx_set_agc: batched and atomic, with the calling rules and check order of sdrx_set_squelch_auto; SDRX_ESTATE with the option
+ * off.  A setting with hi_ms == 0 is accepted as it is (the other fields are stored and ignored).  Otherwise SDRX_EINVAL with
+ * nothing changed unless silent_ms <= lo_ms <= hi_ms <= 2^30 (= 32768^2), up >= 1, 0 < down <= 1, 0 < gain_min <= gain_max, all
+ * four floats finite, and the leaf demodulates USB (the gain does not act on a compress() leaf).  One small upload and one
+ * small launch per call.
+ * sdrx_get_agc: for the last DELIVERED frame (calling rules of sdrx_get_meters), the gain it was computed with, the gain the
+ * step left for the next frame, what the step did and quiet_run behind it; the settings as set.  The step's record travels in
+ * the frame's fixed-size part beside the meter records, so it can be read while the next frame is in flight.  Leaves without
+ * AGC and compress() leaves report gain_used = gain_next = the stored gain and action 0.
+ * What goes with it:
+ *   sdrx_set_gains on an AGC leaf sets the value the AGC continues from (stream-ordered as before); quiet_run is not touched.
+ *     The host's copy of the descriptor gain is stale once the device has stepped: sdrx_get_agc is how a host reads the gain.
+ *   Parking: a parked frame is no observation; an unparked leaf continues from the gain the device holds, with quiet_run = 0;
+ *     a caught-up frame ("catchup") runs with that gain and gets no step (and no gate): sdrx_get_catchup tells what it held.
+ *   Squelch: the gate and the step both read the meter of f and are independent (the step runs behind the gate).  Fixed
+ *     thresholds (sdrx_set_squelch) are in output units and so move with the gain: use "squelch_auto", whose floor follows.
+ *   Planning: as with "preroll", a tree with a "fuse_demod" leaf off the last level does not use the software pipeline, a tree
+ *     with "fuse_demod" leaves does not use "tail_in_levels", and "pipeline" = 1 loses its overlap on such a tree.
+ * "agc" = 1 implies "meter".  0 changes nothing: the same kernels, launches, device_bytes, payloads and callbacks.  With 1 and
+ * every hi_ms 0 (the start) every payload, meter, stream and gate decision is bit for bit what "meter" = 1 gives. */
+typedef struct sdrx_agc_cfg {
+    uint32_t lo_ms, hi_ms; /* window on the payload's mean square, LSB^2; hi_ms = 0: AGC off for this leaf */
+    uint32_t silent_ms;    /* below this mean square the frame is no observation (dead channel, antenna off) */
+    uint32_t hold_frames;  /* consecutive cold frames to sit out before the gain is raised */
+    float up, down;        /* step factors */
+    float gain_min, gain_max;
+} sdrx_agc_cfg;
+typedef struct sdrx_agc_state {
+    int64_t frame;      /* the frame the step followed */
+    float gain_used;    /* the gain that frame was computed with */
+    float gain_next;    /* the gain the step left for the next frame */
+    int32_t action;     /* -1 lowered | 0 kept | +1 raised */
+    uint32_t quiet_run; /* behind the step */
+    sdrx_agc_cfg cfg;   /* as set */
+} sdrx_agc_state;
+int sdrx_set_agc(sdrx_ctx *ctx, const int *ids, const sdrx_agc_cfg *cfgs, int n);
+int sdrx_get_agc(sdrx_ctx *ctx, const int *ids, int n, sdrx_agc_state *out);
+
 /* ---- spectrum display ( = MainWindow::fftHandlerSlot, mainwindow.cpp:411-478, on the device) -------------------
  * One display state per enabled spectrum: VFO `id` (its decimate[decimateCount], what vfo.cpp:290-293 emits as fftData)
  * or SDRX_SPECTRUM_RAW (the raw frame exactly as sdrx_get_raw would return it -- for sdrx_process_device /
@@ -659,6 +726,10 @@ int sdrx_group_get_egress(sdrx_group *grp, int64_t *frame, uint32_t *n_open, uin
  * to the member that owns the leaf. */
 int sdrx_group_set_squelch_auto(sdrx_group *grp, const int *ids, const uint32_t *ratio_q8, const uint32_t *window_frames, int n);
 int sdrx_group_get_squelch_auto(sdrx_group *grp, const int *ids, int n, sdrx_squelch_auto_state *out);
+/* sdrx_set_agc / sdrx_get_agc with ids of the whole tree (group option "agc" = 1), each id routed to the member that owns the
+ * leaf; `frame` counts the group's frames. */
+int sdrx_group_set_agc(sdrx_group *grp, const int *ids, const sdrx_agc_cfg *cfgs, int n);
+int sdrx_group_get_agc(sdrx_group *grp, const int *ids, int n, sdrx_agc_state *out);
 /* sdrx_set_active / sdrx_get_active with ids of the whole tree (group option "park" = 1), each id routed to the member that
  * owns the leaf; `since_frame` counts the group's frames. */
 int sdrx_group_set_active(sdrx_group *grp, const int *ids, const int32_t *active, int n);

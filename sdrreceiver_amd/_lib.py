@@ -68,6 +68,18 @@ class SquelchAutoStateC(C.Structure):
                 ("window_frames", C.c_uint32), ("floor_valid", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class AgcCfgC(C.Structure):
+    """struct sdrx_agc_cfg"""
+    _fields_ = [("lo_ms", C.c_uint32), ("hi_ms", C.c_uint32), ("silent_ms", C.c_uint32), ("hold_frames", C.c_uint32),
+                ("up", C.c_float), ("down", C.c_float), ("gain_min", C.c_float), ("gain_max", C.c_float)]
+
+
+class AgcStateC(C.Structure):
+    """struct sdrx_agc_state"""
+    _fields_ = [("frame", C.c_int64), ("gain_used", C.c_float), ("gain_next", C.c_float), ("action", C.c_int32),
+                ("quiet_run", C.c_uint32), ("cfg", AgcCfgC)]
+
+
 class ActiveStateC(C.Structure):
     """struct sdrx_active_state"""
     _fields_ = [("since_frame", C.c_int64), ("active", C.c_int32), ("reserved", C.c_uint32)]
@@ -130,6 +142,10 @@ SYMBOLS = {
     "sdrx_get_squelch_auto": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_group_set_squelch_auto": (_i, [_vp, _vp, _vp, _vp, _i]),
     "sdrx_group_get_squelch_auto": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_set_agc": (_i, [_vp, _vp, _vp, _i]),
+    "sdrx_get_agc": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_group_set_agc": (_i, [_vp, _vp, _vp, _i]),
+    "sdrx_group_get_agc": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_set_active": (_i, [_vp, _vp, _vp, _i]),
     "sdrx_get_active": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_group_set_active": (_i, [_vp, _vp, _vp, _i]),

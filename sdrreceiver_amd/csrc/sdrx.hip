@@ -31,6 +31,7 @@
 #include "kernels.hip"
 #include "spectrum.hip"
 #include "squelch.hip"
+#include "agc.hip"
 #include "watch.hip"
 #include "tapdesign.h"
 
@@ -41,6 +42,9 @@ static_assert(sizeof(sdrx_stats) == 80, "sdrx_stats ABI layout");
 static_assert(sizeof(sdrx_spectrum_info) == sizeof(SpecRecord) && offsetof(sdrx_spectrum_info, maxval) == offsetof(SpecRecord, maxval) &&
                   SDRX_SPECTRUM_BINS == kSpecN,
               "sdrx_spectrum_info ABI layout");
+static_assert(sizeof(sdrx_agc_cfg) == 32 && sizeof(AgcCfg) == 32 && offsetof(sdrx_agc_cfg, up) == offsetof(AgcCfg, up) && sizeof(sdrx_agc_state) == 56 &&
+                  offsetof(sdrx_agc_state, cfg) == 24,
+              "sdrx_agc_cfg / sdrx_agc_state ABI layout");
 static_assert(sizeof(sdrx_watch_level) == 48 && sizeof(WatchRecord) == 48 && offsetof(sdrx_watch_level, total_pwr) == offsetof(WatchRecord, total_pwr) &&
                   offsetof(sdrx_watch_level, watched) == offsetof(WatchRecord, watched) && SDRX_WATCH_MAX_SEGMENTS == kWatchMaxSeg,
               "sdrx_watch_level ABI layout");
@@ -131,6 +135,11 @@ void free_device_state(sdrx_ctx *c)
     dfree(c->park.d_jobs);
     c->park.jobs_cap = 0;
     c->sq.bytes = c->sq.dir_off = c->sq.pack_bytes = c->sq.hpack_off = 0;
+    dfree(c->agc.d_leaves);
+    dfree(c->agc.d_cfg);
+    dfree(c->agc.d_quiet);
+    dfree(c->agc.d_jobs);
+    c->agc = sdrx_ctx::Agc();
     // channel watch: as before the first sdrx_set_watch
     dfree(c->watch.d_desc);
     dfree(c->watch.d_data);
@@ -275,6 +284,8 @@ int sdrx_set_option(sdrx_ctx *c, const char *name, int value)
         c->opt_watch = value != 0;
     else if (!strcmp(name, "catchup"))
         c->opt_catchup = value != 0;
+    else if (!strcmp(name, "agc"))
+        c->opt_agc = value != 0;
     else
         return fail(c, SDRX_EINVAL, "unknown option '%s'", name);
     return SDRX_OK;
@@ -373,7 +384,7 @@ int sdrx_finalize(sdrx_ctx *c)
         c->opt_park = c->opt_preroll = 1;
     if (c->opt_preroll || c->opt_squelch_auto) // the pre-roll and the floor tracking are the gate's
         c->opt_squelch = 1;
-    if (c->opt_squelch) // the gate reads the meter records
+    if (c->opt_squelch || c->opt_agc) // the gate and the gain step read the meter records
         c->opt_meter = 1;
     const int rc = finalize_impl(c);
     if (rc != SDRX_OK) { // nothing of a half-built tree stays behind: a later call starts clean -- with the options as they
@@ -713,6 +724,8 @@ int apply_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
                 fill(reinterpret_cast<unsigned *>(c->sq.d_auto + sq) + 4, 1, 0); // age
             }
         }
+        if (c->opt_agc && c->agc.slot[(size_t)id] >= 0) // the gain stays what the device holds; the cold run starts again
+            fill(c->agc.d_quiet + c->agc.slot[(size_t)id], 1, 0);
         RetuneJob J;
         memset(&J, 0, sizeof J);
         J.kind = kJobRetune;
@@ -1173,7 +1186,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->exact = c->opt_exact;
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq.bytes + sizeof(int) * c->park.words + c->watch.bytes);
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq.bytes + sizeof(int) * c->park.words + c->watch.bytes + c->agc.bytes);
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

@@ -104,7 +104,7 @@ struct sdrx_ctx {
     int opt_exact = 1, opt_prequant = 0, opt_segments = 0, opt_dc_blocked = 0, opt_pipeline = 0, opt_dc_speculative = 1;
     int opt_fuse = 1, opt_frame_pipeline = 1, opt_fuse_late = 1, opt_keep_streams = 0, opt_fuse_demod = 0;
     int opt_tail_in_levels = 1;
-    int opt_meter = 0, opt_squelch = 0, opt_preroll = 0, opt_squelch_auto = 0, opt_park = 0, opt_watch = 0, opt_catchup = 0;
+    int opt_meter = 0, opt_squelch = 0, opt_preroll = 0, opt_squelch_auto = 0, opt_park = 0, opt_watch = 0, opt_catchup = 0, opt_agc = 0;
     // option meter: per frame parity, behind the payloads in d_pay / h_pay (at meter_off), one 16-byte MeterAcc record per work
     // unit that emits payload values (kernels.hip "output meters"); the records travel in the payload copy
     size_t meter_off = 0;
@@ -147,6 +147,22 @@ struct sdrx_ctx {
         std::vector<unsigned long long> thr_eff, floor; // ... the delivered directory's values (floor: kSqNone = no observation)
         hipEvent_t ev_dir[2] = {nullptr, nullptr}; // the fixed-size part of frame f is in h_pay[f & 1]
     } sq;
+
+    // Option agc (agc.hip): one slot per USB leaf, in node order.  Per frame parity the step's records (AgcRecord per
+    // slot) sit behind the meter records in d_pay / h_pay, at rec_off -- in front of the gate's directory, inside the fixed-size
+    // part that always travels.  On the device the static table, the settings and quiet_run (one array: the steps run in frame
+    // order on one stream, as the gates do).
+    struct Agc {
+        size_t rec_off = 0, bytes = 0; // bytes: device memory the option holds besides the records
+        int n = 0;                     // slots
+        std::vector<int> slot;         // node -> its slot (-1: not a USB leaf)
+        AgcLeaf *d_leaves = nullptr;
+        AgcCfg *d_cfg = nullptr;
+        unsigned *d_quiet = nullptr;
+        AgcJob *d_jobs = nullptr; // job list of sdrx_set_agc
+        size_t jobs_cap = 0;      //   ... its size in bytes (upload_jobs)
+        std::vector<sdrx_agc_cfg> cfg; // host copy of the settings, per node (a compress() leaf's are stored too)
+    } agc;
 
     // Option park (sdrx_set_active): one flag word per descriptor of every kernel that works on a leaf, in one
     // device array -- [K1Vfo: per node | K2aVfo | K2Vfo | K3Vfo | K4Vfo | the gate: per leaf in publish order] -- 1 = active.

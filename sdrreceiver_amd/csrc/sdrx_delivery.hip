@@ -238,6 +238,23 @@ enum LeafCall {
 };
 const char *bad_switch(int32_t v) { return v == 0 || v == 1 ? nullptr : "the value must be 0 or 1"; }
 const char *bad_auto(uint32_t ratio_q8, uint32_t window_frames) { return ratio_q8 > 0 && window_frames == 0 ? "window_frames 0 with a ratio" : nullptr; }
+// sdrx_set_agc: what is wrong with a setting for a leaf that does (`usb`) or does not demodulate USB
+const char *bad_agc(const sdrx_agc_cfg &a, bool usb)
+{
+    if (a.hi_ms == 0) // off for this leaf: the other fields are stored and ignored
+        return nullptr;
+    if (!(a.silent_ms <= a.lo_ms && a.lo_ms <= a.hi_ms && a.hi_ms <= (1u << 30)))
+        return "the window needs silent_ms <= lo_ms <= hi_ms <= 2^30";
+    if (!std::isfinite(a.up) || !std::isfinite(a.down) || !std::isfinite(a.gain_min) || !std::isfinite(a.gain_max))
+        return "up, down, gain_min and gain_max must be finite";
+    if (!(a.up >= 1.0f) || !(a.down > 0.0f && a.down <= 1.0f))
+        return "the steps need up >= 1 and 0 < down <= 1";
+    if (!(a.gain_min > 0.0f && a.gain_min <= a.gain_max))
+        return "the limits need 0 < gain_min <= gain_max";
+    if (!usb)
+        return "the leaf does not demodulate USB: the gain does not act on a compress() leaf";
+    return nullptr;
+}
 int leaf_call(sdrx_ctx *c, const char *what, int sdrx_ctx::*opt, const char *opt_name, const int *ids, bool arrays, int n, LeafCall mode,
               const std::function<const char *(int)> &bad = nullptr)
 {
@@ -479,6 +496,71 @@ int sdrx_get_squelch_auto(sdrx_ctx *c, const int *ids, int n, sdrx_squelch_auto_
         s.thr_eff_sum_sq = c->sq.thr_eff[i];
         s.ratio_q8 = c->sq.acfg[i].ratio_q8;
         s.window_frames = c->sq.acfg[i].window_frames;
+        out[k] = s;
+    }
+    return SDRX_OK;
+}
+
+// As sdrx_set_squelch_auto: the whole list is checked before anything changes; then the software pipeline runs out with the old
+// settings, one upload of the job list, one k_agc_set launch (which restarts the named leaves' quiet_run).  A compress() leaf
+// (hi_ms == 0: nothing else passes the check) has no slot on the device: its setting is stored on the host alone.
+int sdrx_set_agc(sdrx_ctx *c, const int *ids, const sdrx_agc_cfg *cfgs, int n)
+{
+    if (int rc = leaf_call(c, "sdrx_set_agc", &sdrx_ctx::opt_agc, "agc", ids, cfgs != nullptr, n, kBetweenFrames,
+                           [&](int k) { return bad_agc(cfgs[k], c->nodes[(size_t)ids[k]].d.demod_usb != 0); }))
+        return rc;
+    if (n == 0)
+        return SDRX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c))
+        return rc;
+    std::vector<AgcJob> jobs;
+    for (int k = 0; k < n; ++k) {
+        const int slot = c->agc.slot[(size_t)ids[k]];
+        if (slot < 0)
+            continue;
+        AgcJob J;
+        memset(&J, 0, sizeof J);
+        memcpy(&J.cfg, &cfgs[k], sizeof J.cfg);
+        J.index = (unsigned)slot;
+        jobs.push_back(J);
+    }
+    if (!jobs.empty()) {
+        if (int rc = upload_jobs(c, c->agc.d_jobs, c->agc.jobs_cap, jobs.data(), sizeof(AgcJob) * jobs.size()))
+            return rc;
+        const int nj = (int)jobs.size();
+        hipLaunchKernelGGL(k_agc_set, dim3((nj + 63) / 64), dim3(64), 0, c->st.stream, c->agc.d_jobs, nj, c->agc.d_cfg, c->agc.d_quiet);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->st.stream)); // (`jobs` lives on this stack)
+    }
+    for (int k = 0; k < n; ++k)
+        c->agc.cfg[(size_t)ids[k]] = cfgs[k];
+    return SDRX_OK;
+}
+
+int sdrx_get_agc(sdrx_ctx *c, const int *ids, int n, sdrx_agc_state *out)
+{
+    if (int rc = leaf_call(c, "sdrx_get_agc", &sdrx_ctx::opt_agc, "agc", ids, out != nullptr, n, kDelivered))
+        return rc;
+    if (n == 0)
+        return SDRX_OK;
+    const unsigned char *rec = c->h_pay[c->host_slot] + c->agc.rec_off;
+    for (int k = 0; k < n; ++k) {
+        sdrx_agc_state s;
+        memset(&s, 0, sizeof s);
+        s.frame = (int64_t)c->host_frame;
+        s.cfg = c->agc.cfg[(size_t)ids[k]];
+        const int slot = c->agc.slot[(size_t)ids[k]];
+        if (slot < 0) { // a compress() leaf: the stored gain, which acts on nothing
+            s.gain_used = s.gain_next = c->nodes[(size_t)ids[k]].d.gain;
+        } else {
+            AgcRecord R;
+            memcpy(&R, rec + sizeof(AgcRecord) * (size_t)slot, sizeof R);
+            s.gain_used = R.gain_used;
+            s.gain_next = R.gain_next;
+            s.action = R.action;
+            s.quiet_run = R.quiet_run;
+        }
         out[k] = s;
     }
     return SDRX_OK;

@@ -488,8 +488,10 @@ void build_level_plan(sdrx_ctx *c, Built &B)
     // Option preroll: the gate of frame g, behind launch g + n_levels - 1, reads the payloads of g - 1 in the parity that g + 1
     // writes.  A leaf that demodulates in its mix wave on level n_levels - 2 writes g + 1's payload in that very launch: only
     // on the last level is its next write behind the gate (the argument above enqueue_frame_as).
+    // Option agc needs the same launch order for another reason: the step of frame g, behind the gate of g, writes the gain that
+    // g + 1 demodulates with, and such a leaf on level n_levels - 2 demodulates g + 1 in the launch in front of that step.
     for (const Node &n : c->nodes)
-        if (c->opt_preroll && n.fused_demod && n.level != c->n_levels - 1)
+        if ((c->opt_preroll || c->opt_agc) && n.fused_demod && n.level != c->n_levels - 1)
             P.usable = false;
     if (!P.usable)
         return;
@@ -531,8 +533,8 @@ void build_level_plan(sdrx_ctx *c, Built &B)
             tail = false;
         if (n.fused_demod && c->opt_meter && c->opt_exact == 1) // (k_levels_tail's exact form does not meter mix items: kernels.hip)
             tail = false;
-        if (n.fused_demod && c->opt_preroll) // (its payload of f+1 would be written in the launch in front of the gate of f)
-            tail = false;
+        if (n.fused_demod && (c->opt_preroll || c->opt_agc)) // (its payload of f+1 would be written in the launch in front of the gate
+            tail = false;                                    //   of f -- and computed with the gain of f: the step of f runs behind it)
     }
     // LDS: four mix waves or one demodulation block per workgroup.  Where four waves' LDS would fit fewer mix waves on a CU
     // than k_mix_levels does (the fused /5 and /6 leaves: 9 KB a wave), the two-launch form stays.
@@ -659,6 +661,14 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
     HIPCHK(c, hipMemsetAsync(c->arena, 0, c->arena_bytes, c->st.stream));
     // (the copy length stays a multiple of 64 bytes, as the packed payloads are)
     c->pay_bytes = std::max<size_t>(c->opt_meter ? align_up(c->meter_off + 16 * (size_t)c->meter_slots, 64) : B.pay, 64);
+    c->agc.rec_off = 0;
+    c->agc.n = 0;
+    if (c->opt_agc) { // the step's records behind the meter records, one per USB leaf
+        for (const Node &n : c->nodes)
+            c->agc.n += n.leaf && n.d.demod_usb;
+        c->agc.rec_off = align_up(c->meter_off + 16 * (size_t)c->meter_slots, 16);
+        c->pay_bytes = align_up(c->agc.rec_off + sizeof(AgcRecord) * (size_t)c->agc.n, 64);
+    }
     c->sq.dir_off = c->sq.pack_bytes = c->sq.hpack_off = c->sq.aux_off = 0; // (a finalize that was refused may have left another tree's values)
     if (c->opt_squelch) { // the directory behind the records: one fixed-size copy brings both
         size_t n_leaves = 0;
@@ -937,6 +947,49 @@ int park_setup(sdrx_ctx *c, const Built &B)
     return SDRX_OK;
 }
 
+// ---- option agc: the per-leaf table in node order, settings all zero (off), quiet_run 0
+int agc_setup(sdrx_ctx *c)
+{
+    const size_t rec_off = c->agc.rec_off;
+    const int n_slots = c->agc.n;
+    c->agc = sdrx_ctx::Agc();
+    if (!c->opt_agc)
+        return SDRX_OK;
+    sdrx_ctx::Agc &A = c->agc;
+    A.rec_off = rec_off;
+    A.n = n_slots;
+    A.slot.assign(c->nodes.size(), -1);
+    sdrx_agc_cfg off;
+    memset(&off, 0, sizeof off);
+    A.cfg.assign(c->nodes.size(), off);
+    std::vector<AgcLeaf> leaves;
+    for (size_t i = 0; i < c->nodes.size(); ++i) {
+        const Node &nd = c->nodes[i];
+        if (!nd.leaf || !nd.d.demod_usb)
+            continue;
+        A.slot[i] = (int)leaves.size();
+        AgcLeaf L;
+        memset(&L, 0, sizeof L);
+        L.gain = nd.d4_index >= 0 ? &(reinterpret_cast<K4Vfo *>(c->arena + c->off_k4) + nd.d4_index)->gain
+                                  : &(reinterpret_cast<K2Vfo *>(c->arena + c->off_k2) + nd.d2_index)->gain;
+        L.meter_off = (unsigned)(c->meter_off + 16 * (size_t)nd.meter_first);
+        L.meter_n = (unsigned)nd.meter_n;
+        L.n_values = (unsigned)nd.n_out;
+        L.act_word = c->opt_park ? (unsigned)(c->park.o_2 + (size_t)nd.d2_index) : 0u;
+        leaves.push_back(L);
+    }
+    const size_t n1 = std::max<size_t>(leaves.size(), 1);
+    HIPCHK(c, hipMalloc(&A.d_leaves, sizeof(AgcLeaf) * n1));
+    HIPCHK(c, hipMalloc(&A.d_cfg, sizeof(AgcCfg) * n1));
+    HIPCHK(c, hipMalloc(&A.d_quiet, sizeof(unsigned) * n1));
+    A.bytes = (sizeof(AgcLeaf) + sizeof(AgcCfg) + sizeof(unsigned)) * n1;
+    HIPCHK(c, hipMemcpyAsync(A.d_leaves, leaves.data(), sizeof(AgcLeaf) * leaves.size(), hipMemcpyHostToDevice, c->st.stream));
+    HIPCHK(c, hipMemsetAsync(A.d_cfg, 0, sizeof(AgcCfg) * n1, c->st.stream));
+    HIPCHK(c, hipMemsetAsync(A.d_quiet, 0, sizeof(unsigned) * n1, c->st.stream));
+    HIPCHK(c, hipStreamSynchronize(c->st.stream)); // (`leaves` lives on this stack)
+    return SDRX_OK;
+}
+
 // ---- option catchup: every leaf's own entries of the work lists, kept on the host (sdrx_set_active cuts its sub-lists from them)
 void catchup_setup(sdrx_ctx *c, const Built &B)
 {
@@ -979,6 +1032,8 @@ int finalize_impl(sdrx_ctx *c)
     if (int rc = squelch_setup(c))
         return rc;
     if (int rc = park_setup(c, B))
+        return rc;
+    if (int rc = agc_setup(c))
         return rc;
     catchup_setup(c, B);
     c->sq.preroll_fused = false;

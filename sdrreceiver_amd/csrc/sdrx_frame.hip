@@ -215,6 +215,24 @@ void squelch_gate(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
         form(std::false_type());
 }
 
+// Option agc: the gain step of frame `frame` (agc.hip), on the stream -- and behind the launch -- that completed its meter
+// records, directly behind its gate: wherever squelch_gate is called.  It writes the gains frame + 1 demodulates with: every
+// launch that reads a gain for frame + 1 comes behind it (the argument above enqueue_frame).  Not bracketed, like the gate.
+void agc_step(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
+{
+    if (!c->opt_agc || c->agc.n == 0)
+        return;
+    const int p = (int)(frame & 1ull);
+    AgcRecord *rec = reinterpret_cast<AgcRecord *>(c->d_pay[p] + c->agc.rec_off);
+    const dim3 grid((c->agc.n + kAgcThreads - 1) / kAgcThreads);
+    if (c->opt_park)
+        hipLaunchKernelGGL(k_agc_step<true>, grid, dim3(kAgcThreads), 0, ts, c->agc.d_leaves, c->agc.d_cfg, c->agc.d_quiet, c->d_pay[p], rec, c->agc.n,
+                           park_arg<true>(c, 0));
+    else
+        hipLaunchKernelGGL(k_agc_step<false>, grid, dim3(kAgcThreads), 0, ts, c->agc.d_leaves, c->agc.d_cfg, c->agc.d_quiet, c->d_pay[p], rec, c->agc.n,
+                           park_arg<false>(c, 0));
+}
+
 // One block-per-tile launch of the leaf tail (late decimation / demodulation / long audio low-pass / compress) for `frame`:
 // `n_blocks` entries of the work list `w` (k_lpf_long with option meter: and of the record offsets `mrel`).
 void launch_block_list(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned long long frame, const BlockWork *w, const int *mrel, int n_blocks)
@@ -339,8 +357,10 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
         for (const LaunchB &L : c->lb)
             if (L.kind == KIND_LPF_LONG)
                 launch_block_kernel(c, L, c->st.stream, f_dm);
-    if (dm) // that launch completed frame f_dm's payloads and records: its gate
+    if (dm) { // that launch completed frame f_dm's payloads and records: its gate, and its gain step
         squelch_gate(c, c->st.stream, f_dm);
+        agc_step(c, c->st.stream, f_dm);
+    }
     if (hi >= 0) {
         spectrum_launch(c, c->st.stream, lo, hi, 0, A.frame_level);
         watch_launch(c, c->st.stream, lo, hi, 0, A.frame_level);
@@ -356,6 +376,7 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
                 launch_block_kernel(c, L, c->st.stream, f);
         if (!P.tail) {
             squelch_gate(c, c->st.stream, f);
+            agc_step(c, c->st.stream, f);
             c->pipe.erase(c->pipe.begin());
         }
     }
@@ -413,13 +434,35 @@ int pipeline_flush(sdrx_ctx *c)
 //       - paths mix only through pipeline_flush, which runs every gate still outstanding, in frame order, on `stream`; the
 //         two-stream form never enters pipeline_step.  sdrx_fetch, queue_fixed_part and queue_payloads read d_pack and the
 //         directory only.
+//   * option agc: the step of f (agc_step, directly behind the gate of f wherever that is launched) reads the meter records of
+//     f and WRITES the gain floats in the K2Vfo / K4Vfo descriptors -- the value frame f+1 demodulates with.  It must come
+//     behind every launch that completes a meter record of f (the gate's own condition) and in front of every launch that reads
+//     a gain for f+1; no launch may still read a gain for f (all of them completed f's records, so they are in front).  quiet_run
+//     is one array, as hang_left.  The step's record goes to d_pay[p] beside the meter records: next writer the step of f+2.
+//     Who reads a gain: k_usb_demod / the demodulation blocks of k_levels_tail, k_lpf_long, and the mix waves of fuse_demod
+//     leaves.  Path by path, as for preroll:
+//       - one launch per level, one stream: tail(f), gate(f), step(f), levels(f+1), tail(f+1) in order;
+//       - two streams (pipe): tails, gates and steps of all frames are in order on tail_stream, and without fuse_demod only the
+//         tail reads gains.  With fuse_demod leaves the levels of f+1 on `stream` read them: they wait for ev_tail[p ^ 1],
+//         recorded behind the step of f (the wait preroll has) -- which takes the overlap away for that combination;
+//       - pipeline_step with k_mix_levels: the block kernels of g+1 come in step k+1, behind step(g).  A fuse_demod leaf on level
+//         n-1 demodulates g in step k's launch and g+1 in step k+1's: behind step(g).  One on level n-2 demodulates g+1 in step
+//         k's launch, in FRONT of step(g): with agc such a tree does not use the software pipeline (build_level_plan);
+//       - pipeline_step with k_levels_tail: the demodulation blocks of f ride in the launch of the step after f's last level,
+//         then k_lpf_long(f), gate(f), step(f); the demodulation of f+1 is in the next step's launch, k_lpf_long(f+1) behind
+//         that.  fuse_demod leaves of f+1 would demodulate inside the launch that carries f's demodulation, in front of
+//         step(f): with agc a tree with such leaves keeps k_mix_levels + k_usb_demod (build_level_plan);
+//       - pipeline_flush runs every step still outstanding behind its gate, in frame order; sdrx_set_gains, sdrx_set_agc and
+//         sdrx_set_active drain first, and their job kernels run on `stream` behind everything.  The catch-up of frame K-1
+//         (sdrx_set_active) launches no step: the leaf was parked in K-1, which is no observation.
 int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
 {
     const int p = (int)(c->frame_no & 1ull);
     const bool pipe = c->opt_pipeline != 0;
     if (pipe && c->st.tail_recorded[p])
         HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.ev_tail[p], 0));
-    if (pipe && c->opt_preroll && c->sq.preroll_fused && c->st.tail_recorded[p ^ 1]) // the levels write d_pay[p], which the previous gate reads
+    if (pipe && (c->opt_preroll || c->opt_agc) && c->sq.preroll_fused && c->st.tail_recorded[p ^ 1]) // the levels write d_pay[p], which the previous gate
+                                                                                                       // reads -- and read the gains its step writes
         HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.ev_tail[p ^ 1], 0));
     spectrum_raw_step(c, raw, raw_mode);
     watch_raw_step(c, raw, raw_mode);
@@ -466,6 +509,7 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
     for (const LaunchB &L : c->lb)
         launch_block_kernel(c, L, ts, c->frame_no);
     squelch_gate(c, ts, c->frame_no);
+    agc_step(c, ts, c->frame_no);
     spectrum_launch(c, ts, 0, c->n_levels - 1, c->frame_no, nullptr);
     watch_launch(c, ts, 0, c->n_levels - 1, c->frame_no, nullptr);
     hipError_t e = hipGetLastError();

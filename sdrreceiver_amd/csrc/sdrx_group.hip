@@ -704,6 +704,22 @@ int sdrx_group_get_squelch_auto(sdrx_group *g, const int *ids, int n, sdrx_squel
     return group_gather(g, "sdrx_group_get_squelch_auto", ids, n, out, sdrx_get_squelch_auto);
 }
 
+int sdrx_group_set_agc(sdrx_group *g, const int *ids, const sdrx_agc_cfg *cfgs, int n)
+{
+    return group_scatter(
+        g, "sdrx_group_set_agc", &sdrx_ctx::opt_agc, "agc", true, ids, cfgs != nullptr, n,
+        [&](int k) { // (the ids of entry k have passed the range check when this runs)
+            const auto w = g->where[(size_t)ids[k]];
+            return bad_agc(cfgs[k], g->m[(size_t)w.first].c->nodes[(size_t)w.second].d.demod_usb != 0);
+        },
+        [&](sdrx_ctx *m, const Part &p) { return sdrx_set_agc(m, p.ids.data(), p.pick(cfgs).data(), p.n()); });
+}
+
+int sdrx_group_get_agc(sdrx_group *g, const int *ids, int n, sdrx_agc_state *out)
+{
+    return group_gather(g, "sdrx_group_get_agc", ids, n, out, sdrx_get_agc);
+}
+
 int sdrx_group_set_active(sdrx_group *g, const int *ids, const int32_t *active, int n)
 {
     return group_scatter(g, "sdrx_group_set_active", &sdrx_ctx::opt_park, "park", true, ids, active != nullptr, n, [&](int k) { return bad_switch(active[k]); },

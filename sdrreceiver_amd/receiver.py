@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, meter, squelch as _squelch, watch as _watch
+from . import _lib, agc as _agc, meter, squelch as _squelch, watch as _watch
 from .topology import Topology, VfoDesc
 
 
@@ -129,6 +129,28 @@ class _LeafCalls:
         ``ratio_q8``, ``window_frames``, ``floor_valid`` as arrays in the order of `vids`."""
         return _squelch.squelch_auto_dict(self._get_list("get_squelch_auto", vids, _lib.SquelchAutoStateC)[1])
 
+    # -- device-side AGC (option ``agc``; sdrreceiver_amd.agc has the rule): the gain follows the meter between frames --------
+    def set_agc(self, vids, lo_ms, hi_ms, silent_ms, hold_frames, up, down, gain_min, gain_max) -> None:
+        """AGC settings of the USB leaves `vids` from the next frame on (``sdrx_agc_cfg``; every argument a scalar or one value
+        per leaf): the window ``lo_ms`` .. ``hi_ms`` on the payload's mean square in LSB^2 (``hi_ms`` 0: off for the leaf),
+        ``silent_ms`` below which a frame is no observation, ``hold_frames`` cold frames to sit out before a raise, the step
+        factors and the limits.  Restarts the named leaves' ``quiet_run``."""
+        ids = np.ascontiguousarray(np.atleast_1d(np.asarray(vids)), dtype=np.int32).reshape(-1)
+        cols = [np.broadcast_to(np.asarray(v, dt), ids.shape) for v, dt in
+                ((lo_ms, np.uint32), (hi_ms, np.uint32), (silent_ms, np.uint32), (hold_frames, np.uint32),
+                 (up, np.float32), (down, np.float32), (gain_min, np.float32), (gain_max, np.float32))]
+        cfgs = (_lib.AgcCfgC * max(1, ids.size))()
+        for k in range(ids.size):
+            cfgs[k] = _lib.AgcCfgC(int(cols[0][k]), int(cols[1][k]), int(cols[2][k]), int(cols[3][k]),
+                                   float(cols[4][k]), float(cols[5][k]), float(cols[6][k]), float(cols[7][k]))
+        self._call("set_agc", ids.ctypes.data, cfgs, ids.size)
+
+    def agc(self, vids) -> dict:
+        """What the gain step did behind the last delivered frame for the leaves `vids`: ``frame``, ``gain_used`` (the gain
+        that frame was computed with), ``gain_next``, ``action`` (-1 / 0 / +1), ``quiet_run`` and the settings as set, as
+        arrays in the order of `vids`.  This is how a host reads a gain the device steps."""
+        return _agc.agc_dict(self._get_list("get_agc", vids, _lib.AgcStateC)[1])
+
     # -- parking (option ``park``): leaves switched off and on between frames --------------------------------------------
     def set_active(self, vids, active) -> None:
         """Park (``active[k]`` 0) or unpark (1) the leaves `vids` before the next frame.  A parked leaf costs no arithmetic and
@@ -191,7 +213,8 @@ class Receiver(_LeafCalls):
                  fuse_late: bool = True, keep_streams: bool = False, dc_speculative: bool = True,
                  dc_blocks_per_step: int | None = None, fuse_demod: bool = False,
                  tail_in_levels: bool = True, meter: bool = False, squelch: bool = False, preroll: bool = False,
-                 squelch_auto: bool = False, park: bool = False, watch: bool = False, catchup: bool = False):
+                 squelch_auto: bool = False, park: bool = False, watch: bool = False, catchup: bool = False,
+                 agc: bool = False):
         self.L = _lib.lib()
         h = C.c_void_p()
         rc = self.L.sdrx_create(C.byref(h), int(device))
@@ -226,6 +249,8 @@ class Receiver(_LeafCalls):
             self._chk(self.L.sdrx_set_option(self.h, b"watch", 1))
         if catchup:
             self._chk(self.L.sdrx_set_option(self.h, b"catchup", 1))
+        if agc:
+            self._chk(self.L.sdrx_set_option(self.h, b"agc", 1))
         self._chk(self.L.sdrx_set_option(self.h, b"dc_speculative", int(bool(dc_speculative))))
         if dc_blocks_per_step is not None:
             self._chk(self.L.sdrx_set_option(self.h, b"dc_blocks_per_step", int(dc_blocks_per_step)))
