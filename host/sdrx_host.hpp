@@ -241,6 +241,34 @@ public:
         call("get_watch_psd", sdrx_group_get_watch_psd, sdrx_get_watch_psd, leaf_id, psd.data(), frame);
         return psd;
     }
+    // drift estimate (part of option "watch"): the spectrum of the source of watched leaf `leaf_id` registered against a
+    // template over the shifts -max_shift .. max_shift (0: off); templ == nullptr: the next measured frame's spectrum is
+    // captured on the device.  drift(): the record of the last delivered frame; drift_hz() turns it into Hz.
+    void set_drift(int leaf_id, const double *templ, int max_shift)
+    {
+        call("set_drift", sdrx_group_set_drift, sdrx_set_drift, leaf_id, templ, max_shift);
+    }
+    sdrx_drift_level drift(int leaf_id)
+    {
+        sdrx_drift_level out;
+        call("get_drift", sdrx_group_get_drift, sdrx_get_drift, leaf_id, &out);
+        return out;
+    }
+    std::vector<double> drift_profile(int leaf_id, int max_shift, int64_t *frame = nullptr)
+    {
+        std::vector<double> profile((size_t)(2 * max_shift + 1));
+        call("get_drift_profile", sdrx_group_get_drift_profile, sdrx_get_drift_profile, leaf_id, profile.data(), frame);
+        return profile;
+    }
+    // sdrx.h "Drift estimate": the parabola through the peak and its neighbours; plain shift at the window's edge
+    static double drift_bins(const sdrx_drift_level &r)
+    {
+        const double den = r.left - 2.0 * r.peak + r.right;
+        if (r.shift >= r.max_shift || r.shift <= -r.max_shift || den == 0.0)
+            return (double)r.shift;
+        return r.shift + 0.5 * (r.left - r.right) / den;
+    }
+    static double drift_hz(const sdrx_drift_level &r, double fs_source) { return drift_bins(r) * fs_source / SDRX_SPECTRUM_BINS; }
 
 private:
     bool started() const { return ctx_ || grp_; }

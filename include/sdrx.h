@@ -519,6 +519,68 @@ typedef struct sdrx_watch_level {
 int sdrx_set_watch(sdrx_ctx *ctx, const int *ids, const int32_t *on, int n);
 int sdrx_get_watch(sdrx_ctx *ctx, const int *ids, int n, sdrx_watch_level *out);
 int sdrx_get_watch_psd(sdrx_ctx *ctx, int leaf_id, double *psd /* 8192, natural order */, int64_t *frame);
+
+/* Drift estimate (part of option "watch" = 1; no option of its own): by how many Hz has the band moved?  The reference leaves
+ * this loop to its user ("When changing dongles there may be a slight frequency difference ... mix_offset"); the actuator is
+ * sdrx_set_mixer_freqs above, this is the sensor.  Per measured source and frame the PSD the watch has computed is registered
+ * against a template of that source on the device, and the answer travels with the frame.  The reference has no counterpart:
+ * this text is the definition.
+ *
+ * N = SDRX_SPECTRUM_BINS = 8192; PSD = the watch's PSD of the source for that frame; T = the source's template, N doubles, each
+ * finite and >= 0; K = max_shift, 1 <= K <= SDRX_DRIFT_MAX_SHIFT.
+ *   profile[s] = sum over i < N of T[i] * PSD[(i + s) mod N]      for s = -K .. K, in IEEE double
+ *   shift      = the first maximum of the device's own profile, the shifts taken in the order 0, -1, +1, -2, +2, ...
+ * Any summation order is allowed, with or without FMA.  The bound: every term is non-negative, so the exact sum E is the sum
+ * of the terms' magnitudes, and N - 1 additions of rounded products (or N fused steps) in any order give a value within
+ * ((1 + u)^N - 1) E <= (N + 1) u E of it, u = 2^-53 (Higham, Accuracy and Stability, 4.2, with the products' own rounding as
+ * the N-th factor; (1 + u)^N - 1 < (N + 1) u for N u < 2^-39).  A model that rounds each product once and adds them exactly
+ * (math.fsum) lies within 2 u E.  Device and model therefore differ by at most (N + 3) u E <= (N + 4) u * model, which is what
+ * the tests allow.  An all-zero T gives profile = 0 and shift = 0.
+ *
+ * The record, 64 bytes, per source and frame -- written by the device to the fixed-size part of the frame the source stream
+ * held, beside the watch records:
+ *   frame     the frame the source stream held
+ *   peak, left, right, zero      profile at shift, shift - 1, shift + 1 and 0; a neighbour outside [-K, K] is reported as 0
+ *   shift, max_shift, measured, captured
+ * A frame in which the source is not measured -- no leaf of it watched, or max_shift 0 -- has measured = 0, every other field
+ * but `frame` 0, and costs no launch.
+ *
+ * What a host does with it (sdrx_host.hpp drift_bins / drift_hz, sdrreceiver_amd/drift.py; not the device):
+ *   d_bins = shift + 0.5 * (left - right) / (left - 2 peak + right); plain shift when shift = +-K or the denominator is 0
+ *   d_Hz   = d_bins * fs_source / N      (fs_source: the leaf's fs)
+ * Sign: the mixer multiplies by exp(+j 2 pi f t); a band that appears D Hz higher in the source peaks at s = +D / binwidth, and
+ * the correction moves every sub's mixer by -D -- what a mix_offset raised by D does.  The estimate is absolute since the
+ * template was taken (a retune of the subs does not change the source's PSD): mix_offset = the offset at capture + D; there
+ * is no loop gain to choose.
+ *
+ * sdrx_set_drift: `leaf_id` names the source the way sdrx_get_watch_psd does -- the source of that watched leaf; calling rules
+ * and check order of sdrx_set_watch for a list of one.  SDRX_EINVAL with nothing changed for a leaf that is not watched, for
+ * max_shift outside 0 .. SDRX_DRIFT_MAX_SHIFT, and for a template entry that is negative, NaN or Inf.
+ *   max_shift == 0                  switches the source's drift off (templ is not read; the template stays)
+ *   templ != NULL, max_shift > 0    uploads N doubles
+ *   templ == NULL, max_shift > 0    capture: the PSD of the next frame in which the source is measured becomes the template,
+ *                                   copied on the device.  That frame's record has captured = 1 and the correlation runs as
+ *                                   always: shift = 0 and peak = sum of T^2
+ * The template belongs to the source, not to the leaf: it survives retunes, parking, changes of the watched set and the moves
+ * of the watch's buffers.  Nothing is allocated or launched until the first sdrx_set_drift that switches a source on: until
+ * then device_bytes, the launches and every payload are those of the watch alone.
+ * sdrx_get_drift: the record of the last DELIVERED frame for the source of leaf `leaf_id` (any leaf, watched or not), with the
+ * calling rules of sdrx_get_watch for a list of one: readable while the next frame is in flight.
+ * sdrx_get_drift_profile: the 2K + 1 values profile[-K .. K] after the last frame, with sdrx_get_watch_psd's rules: SDRX_ESTATE
+ * while frames are in flight and before the first frame measured under the present setting, SDRX_EINVAL if the leaf is not
+ * watched or its source's drift is off. */
+#define SDRX_DRIFT_MAX_SHIFT 1024
+typedef struct sdrx_drift_level {
+    int64_t frame;
+    double peak, left, right, zero;
+    int32_t shift, max_shift;
+    int32_t measured;     /* 0: not measured in that frame -> the other fields but `frame` are 0 */
+    int32_t captured;     /* 1: this frame's PSD became the template */
+    int32_t reserved[2];  /* 0 (the record is 64 bytes) */
+} sdrx_drift_level;
+int sdrx_set_drift(sdrx_ctx *ctx, int leaf_id, const double *templ /* 8192 or NULL */, int max_shift);
+int sdrx_get_drift(sdrx_ctx *ctx, int leaf_id, sdrx_drift_level *out);
+int sdrx_get_drift_profile(sdrx_ctx *ctx, int leaf_id, double *profile /* 2 max_shift + 1 */, int64_t *frame);
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);
@@ -742,6 +804,12 @@ int sdrx_group_get_catchup(sdrx_group *grp, const int *ids, int n, sdrx_meter *o
 int sdrx_group_set_watch(sdrx_group *grp, const int *ids, const int32_t *on, int n);
 int sdrx_group_get_watch(sdrx_group *grp, const int *ids, int n, sdrx_watch_level *out);
 int sdrx_group_get_watch_psd(sdrx_group *grp, int leaf_id, double *psd, int64_t *frame);
+/* sdrx_set_drift / sdrx_get_drift / sdrx_get_drift_profile with an id of the whole tree, routed to the member that holds the
+ * leaf.  A source replicated on several members has one template per member: set it through a leaf of each member that is to
+ * measure it. */
+int sdrx_group_set_drift(sdrx_group *grp, int leaf_id, const double *templ, int max_shift);
+int sdrx_group_get_drift(sdrx_group *grp, int leaf_id, sdrx_drift_level *out);
+int sdrx_group_get_drift_profile(sdrx_group *grp, int leaf_id, double *profile, int64_t *frame);
 
 /* sdrx_get_preroll routed to the member that owns the leaf; sdrx_get_preroll_count summed over the members (group option
  * "preroll" = 1). */

@@ -14,6 +14,7 @@ NKERNELS = 8
 SDRX_EINVAL, SDRX_ESTATE, SDRX_EFILTER, SDRX_EHIP, SDRX_EUNSUPPORTED, SDRX_ENOMEM, SDRX_ENOSTREAM = -1, -2, -3, -4, -5, -6, -7  # include/sdrx.h
 SDRX_DIFFERENT = 1  # sdrx_*_if_same: the frame is not the one the source context staged
 SPECTRUM_BINS, SPECTRUM_RAW = 8192, -2  # SDRX_SPECTRUM_BINS, SDRX_SPECTRUM_RAW
+DRIFT_MAX_SHIFT = 1024  # SDRX_DRIFT_MAX_SHIFT
 
 
 class VfoDescC(C.Structure):
@@ -83,6 +84,13 @@ class AgcStateC(C.Structure):
 class ActiveStateC(C.Structure):
     """struct sdrx_active_state"""
     _fields_ = [("since_frame", C.c_int64), ("active", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class DriftLevelC(C.Structure):
+    """struct sdrx_drift_level"""
+    _fields_ = [("frame", C.c_int64), ("peak", C.c_double), ("left", C.c_double), ("right", C.c_double), ("zero", C.c_double),
+                ("shift", C.c_int32), ("max_shift", C.c_int32), ("measured", C.c_int32), ("captured", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
 
 
 class WatchLevelC(C.Structure):
@@ -158,6 +166,12 @@ SYMBOLS = {
     "sdrx_group_set_watch": (_i, [_vp, _vp, _vp, _i]),
     "sdrx_group_get_watch": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_group_get_watch_psd": (_i, [_vp, _i, _vp, C.POINTER(C.c_int64)]),
+    "sdrx_set_drift": (_i, [_vp, _i, _vp, _i]),
+    "sdrx_get_drift": (_i, [_vp, _i, C.POINTER(DriftLevelC)]),
+    "sdrx_get_drift_profile": (_i, [_vp, _i, _vp, C.POINTER(C.c_int64)]),
+    "sdrx_group_set_drift": (_i, [_vp, _i, _vp, _i]),
+    "sdrx_group_get_drift": (_i, [_vp, _i, C.POINTER(DriftLevelC)]),
+    "sdrx_group_get_drift_profile": (_i, [_vp, _i, _vp, C.POINTER(C.c_int64)]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

@@ -33,6 +33,7 @@
 #include "squelch.hip"
 #include "agc.hip"
 #include "watch.hip"
+#include "drift.hip"
 #include "tapdesign.h"
 
 using namespace sdrx;
@@ -48,6 +49,9 @@ static_assert(sizeof(sdrx_agc_cfg) == 32 && sizeof(AgcCfg) == 32 && offsetof(sdr
 static_assert(sizeof(sdrx_watch_level) == 48 && sizeof(WatchRecord) == 48 && offsetof(sdrx_watch_level, total_pwr) == offsetof(WatchRecord, total_pwr) &&
                   offsetof(sdrx_watch_level, watched) == offsetof(WatchRecord, watched) && SDRX_WATCH_MAX_SEGMENTS == kWatchMaxSeg,
               "sdrx_watch_level ABI layout");
+static_assert(sizeof(sdrx_drift_level) == 64 && sizeof(DriftRecord) == 64 && offsetof(sdrx_drift_level, zero) == offsetof(DriftRecord, zero) &&
+                  offsetof(sdrx_drift_level, captured) == offsetof(DriftRecord, captured) && SDRX_DRIFT_MAX_SHIFT == kDriftMaxShift,
+              "sdrx_drift_level ABI layout");
 
 #include "sdrx_ctx.h"
 
@@ -150,6 +154,16 @@ void free_device_state(sdrx_ctx *c)
             (void)hipHostFree(c->watch.h_rec[p]);
     }
     c->watch = sdrx_ctx::Watch();
+    // drift estimate: as before the first sdrx_set_drift
+    for (auto &s : c->drift.src)
+        dfree(s.d_state);
+    dfree(c->drift.d_desc);
+    for (int p = 0; p < 2; ++p) {
+        dfree(c->drift.d_rec[p]);
+        if (c->drift.h_rec[p])
+            (void)hipHostFree(c->drift.h_rec[p]);
+    }
+    c->drift = sdrx_ctx::Drift();
 }
 
 } // namespace
@@ -1186,7 +1200,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->exact = c->opt_exact;
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq.bytes + sizeof(int) * c->park.words + c->watch.bytes + c->agc.bytes);
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq.bytes + sizeof(int) * c->park.words + c->watch.bytes + c->drift.bytes + c->agc.bytes);
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

@@ -242,6 +242,30 @@ struct sdrx_ctx {
         }
     } watch;
 
+    // Drift estimate (sdrx_set_drift, drift.hip), part of option watch.  A source -- index 0: the raw frame,
+    // 1 + id: the stream of node id -- keeps its template, its last profile and two words of launch state in one device
+    // allocation of its own from its first sdrx_set_drift on: nothing the watch moves or clears touches it.  Host bookkeeping
+    // as the watch keeps it: a frame f >= since ran with max_shift K, the frames before it with was_K.  The record of frame f
+    // goes to d_rec[f & 1] -- one slot per possible source -- and travels with the watch records (queue_watch).  Everything is
+    // allocated by the first sdrx_set_drift that switches a source on.
+    struct Drift {
+        struct Src {
+            int K = 0, was_K = 0;
+            unsigned long long since = 0;
+            unsigned long long set_at = 0; // frame_no of the last sdrx_set_drift: the profile is this setting's once frame_no > set_at
+            DriftState *d_state = nullptr;
+            int slot = -1; // its record (-1: a leaf's stream feeds nobody)
+        };
+        std::vector<Src> src; // sized by the first drift call
+        int n_slots = 0;
+        unsigned char *d_desc = nullptr; // DriftSrc[n_slots] | DriftBlk[kDriftMaxBlocks n_slots]
+        DriftRecord *d_rec[2] = {nullptr, nullptr}, *h_rec[2] = {nullptr, nullptr};
+        size_t bytes = 0;           // device memory it holds
+        std::vector<int> blk_begin; // per source group (as Watch::seg_begin), n_levels + 2 entries; empty: never switched on
+        DriftSrc *d_src() const { return reinterpret_cast<DriftSrc *>(d_desc); }
+        DriftBlk *d_blk() const { return reinterpret_cast<DriftBlk *>(d_desc + sizeof(DriftSrc) * (size_t)n_slots); }
+    } drift;
+
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first
     // frame that fills them.  The first such leaf uses the arena's buffer, further ones buffers of their own (hipMalloc).

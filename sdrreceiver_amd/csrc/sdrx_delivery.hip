@@ -82,6 +82,8 @@ int queue_watch(sdrx_ctx *c, int p, hipStream_t st)
 {
     if (c->watch.d_rec[p])
         HIPCHK(c, hipMemcpyAsync(c->watch.h_rec[p], c->watch.d_rec[p], sizeof(WatchRecord) * (size_t)c->watch.n_slots, hipMemcpyDeviceToHost, st));
+    if (c->drift.d_rec[p]) // ... and the drift records of its sources (nothing before the first sdrx_set_drift)
+        HIPCHK(c, hipMemcpyAsync(c->drift.h_rec[p], c->drift.d_rec[p], sizeof(DriftRecord) * (size_t)c->drift.n_slots, hipMemcpyDeviceToHost, st));
     return SDRX_OK;
 }
 int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st)

@@ -140,7 +140,8 @@ void spectrum_raw_step(sdrx_ctx *c, const void *raw, int raw_mode)
 }
 
 // Option watch: the sources of groups g_lo..g_hi (0: the raw frame, 1 + l: the streams of tree level l) that have a watched
-// leaf -- one k_watch_psd workgroup per (source, segment), then one k_watch_bands wave per watched leaf of those sources.
+// leaf -- one k_watch_psd workgroup per (source, segment), then one k_watch_bands wave per watched leaf of those sources, then
+// the drift estimate of those sources that have one (sdrx_set_drift).
 // Not bracketed: sdrx_get_kernel_times keeps its SDRX_NKERNELS kinds.  Nothing watched: nothing is launched.
 void watch_launch_groups(sdrx_ctx *c, hipStream_t st, int g_lo, int g_hi, const WatchArgs &A)
 {
@@ -154,6 +155,14 @@ void watch_launch_groups(sdrx_ctx *c, hipStream_t st, int g_lo, int g_hi, const 
     const int per = kWatchLeafThreads / 64;
     hipLaunchKernelGGL(k_watch_bands, dim3((l1 - l0 + per - 1) / per), dim3(kWatchLeafThreads), 0, st, W.d_src(), W.d_leaf() + l0, l1 - l0, A, W.d_rec[0],
                        W.d_rec[1]);
+    // drift estimate: one k_watch_drift workgroup per (source of those groups with a template, block of shifts), on the PSD
+    // k_watch_psd has just left.  Nothing before the first sdrx_set_drift; not bracketed either.
+    const sdrx_ctx::Drift &D = c->drift;
+    if (D.blk_begin.empty())
+        return;
+    const int b0 = D.blk_begin[(size_t)g_lo], b1 = D.blk_begin[(size_t)g_hi + 1];
+    if (b1 > b0)
+        hipLaunchKernelGGL(k_watch_drift, dim3(b1 - b0), dim3(kSpecThreads), 0, st, D.d_src(), D.d_blk() + b0, A, D.d_rec[0], D.d_rec[1]);
 }
 // ... of the VFO streams of tree levels lo..hi, where spectrum_launch reads them (the same frames per level)
 void watch_launch(sdrx_ctx *c, hipStream_t st, int lo, int hi, unsigned long long f, const unsigned long long *frames)

@@ -757,6 +757,35 @@ int sdrx_group_get_watch_psd(sdrx_group *g, int leaf_id, double *psd, int64_t *f
     return member_rc(g, w.first, sdrx_get_watch_psd(g->m[(size_t)w.first].c, w.second, psd, frame));
 }
 
+// The drift estimate of the source of leaf `leaf_id`, on the member that holds the leaf (its own copy of the source)
+int sdrx_group_set_drift(sdrx_group *g, int leaf_id, const double *templ, int max_shift)
+{
+    std::pair<int, int> w;
+    if (int rc = owner(g, "sdrx_group_set_drift", leaf_id, &w))
+        return rc;
+    if (g->in_flight > 0)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_set_drift: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
+    return member_rc(g, w.first, sdrx_set_drift(g->m[(size_t)w.first].c, w.second, templ, max_shift));
+}
+
+int sdrx_group_get_drift(sdrx_group *g, int leaf_id, sdrx_drift_level *out)
+{
+    std::pair<int, int> w;
+    if (int rc = owner(g, "sdrx_group_get_drift", leaf_id, &w))
+        return rc;
+    return member_rc(g, w.first, sdrx_get_drift(g->m[(size_t)w.first].c, w.second, out));
+}
+
+int sdrx_group_get_drift_profile(sdrx_group *g, int leaf_id, double *profile, int64_t *frame)
+{
+    std::pair<int, int> w;
+    if (int rc = owner(g, "sdrx_group_get_drift_profile", leaf_id, &w))
+        return rc;
+    if (g->in_flight > 0)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_drift_profile: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
+    return member_rc(g, w.first, sdrx_get_drift_profile(g->m[(size_t)w.first].c, w.second, profile, frame));
+}
+
 int sdrx_group_get_egress(sdrx_group *g, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied)
 {
     if (!g)

@@ -48,6 +48,75 @@ void watch_host_init(sdrx_ctx *c)
 
 int watch_segments(int n) { return std::min(std::max(n / kSpecN, 1), kWatchMaxSeg); }
 
+// ---- drift estimate: host bookkeeping of every possible source (no device memory), by the first drift call
+void drift_host_init(sdrx_ctx *c)
+{
+    sdrx_ctx::Drift &D = c->drift;
+    if (!D.src.empty())
+        return;
+    D.src.assign(c->nodes.size() + 1, sdrx_ctx::Drift::Src());
+    D.n_slots = 0;
+    D.src[0].slot = D.n_slots++;
+    for (size_t id = 0; id < c->nodes.size(); ++id)
+        if (!c->nodes[id].leaf)
+            D.src[1 + id].slot = D.n_slots++;
+}
+
+// The drift launch list for the measured sources `ids` (watch_rebuild's launch order: by source group) whose PSDs lie at
+// `off_psd` in the watch's data: the sources among them with max_shift > 0, one entry per block of shifts.  Synchronous, as
+// watch_rebuild is.  Nothing before the first sdrx_set_drift that switched a source on.
+int drift_rebuild(sdrx_ctx *c, const std::vector<int> &ids, const std::vector<size_t> &off_psd)
+{
+    sdrx_ctx::Drift &D = c->drift;
+    if (!D.d_desc)
+        return SDRX_OK;
+    std::vector<DriftSrc> srcs;
+    std::vector<DriftBlk> blks;
+    std::vector<int> begin((size_t)c->n_levels + 2, 0);
+    size_t k = 0;
+    for (int g = 0; g <= c->n_levels; ++g) {
+        begin[(size_t)g] = (int)blks.size();
+        for (; k < ids.size() && (ids[k] < 0 ? 0 : c->nodes[(size_t)ids[k]].level + 1) == g; ++k) {
+            const sdrx_ctx::Drift::Src &S = D.src[(size_t)(1 + ids[k])];
+            if (S.K == 0)
+                continue;
+            DriftSrc e;
+            e.psd = reinterpret_cast<const double *>(c->watch.d_data + off_psd[k]);
+            e.state = S.d_state;
+            e.K = S.K;
+            e.n_blocks = (2 * S.K + 1 + kDriftBlock - 1) / kDriftBlock;
+            e.level = ids[k] < 0 ? -1 : std::min(g - 1, kMaxLevels - 1);
+            e.slot = S.slot;
+            for (int b = 0; b < e.n_blocks; ++b)
+                blks.push_back(DriftBlk{(int)srcs.size(), b});
+            srcs.push_back(e);
+        }
+    }
+    begin[(size_t)c->n_levels + 1] = (int)blks.size();
+    if (!srcs.empty()) {
+        HIPCHK(c, hipMemcpy(D.d_src(), srcs.data(), sizeof(DriftSrc) * srcs.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(D.d_blk(), blks.data(), sizeof(DriftBlk) * blks.size(), hipMemcpyHostToDevice));
+    }
+    D.blk_begin = begin;
+    return SDRX_OK;
+}
+
+// was the source of `leaf_id` measured for its drift in frame `frame`: max_shift > 0 then, and a leaf of it watched
+bool drift_measured_at(const sdrx_ctx *c, int leaf_id, unsigned long long frame)
+{
+    const sdrx_ctx::Drift &D = c->drift;
+    if (D.src.empty())
+        return false;
+    const int parent = c->nodes[(size_t)leaf_id].d.parent_id;
+    const sdrx_ctx::Drift::Src &S = D.src[(size_t)(1 + parent)];
+    if ((frame >= S.since ? S.K : S.was_K) == 0)
+        return false;
+    for (size_t id = 0; id < c->nodes.size(); ++id)
+        if (c->nodes[id].leaf && c->nodes[id].d.parent_id == parent && c->watch.watched_at((int)id, frame))
+            return true;
+    return false;
+}
+
 // The launch lists for the present selection, uploaded whenever it or a watched leaf's band changes.  Synchronous: never inside
 // a frame call, and the context is drained.  The sources in launch order: the raw frame, then the parents by tree level.
 int watch_rebuild(sdrx_ctx *c)
@@ -157,6 +226,8 @@ int watch_rebuild(sdrx_ctx *c)
         HIPCHK(c, hipMemcpy(W.d_seg(), segs.data(), sizeof(WatchSeg) * segs.size(), hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(W.d_leaf(), leaves.data(), sizeof(WatchLeaf) * leaves.size(), hipMemcpyHostToDevice));
     }
+    if (int rc = drift_rebuild(c, ids, off_psd)) // (the templates stay where they are; their sources' PSDs may have moved)
+        return rc;
     W.src_ids = ids; // (last: the frame sequence launches from these lists only when everything above succeeded)
     return SDRX_OK;
 }
@@ -258,6 +329,106 @@ int sdrx_get_watch_psd(sdrx_ctx *c, int leaf_id, double *psd, int64_t *frame)
         return fail(c, SDRX_EHIP, "sdrx_get_watch_psd: the source of vfo %d is not in the launch list", leaf_id);
     if (psd)
         HIPCHK(c, hipMemcpy(psd, W.d_data + W.src_psd[k], sizeof(double) * kSpecN, hipMemcpyDeviceToHost));
+    if (frame)
+        *frame = (int64_t)c->frame_no - 1;
+    return SDRX_OK;
+}
+
+int sdrx_set_drift(sdrx_ctx *c, int leaf_id, const double *templ, int max_shift)
+{
+    auto bad = [&](int) -> const char * {
+        if (c->watch.leaf.empty() || !c->watch.leaf[(size_t)leaf_id].on)
+            return "is not watched (sdrx_set_watch)";
+        if (max_shift < 0 || max_shift > SDRX_DRIFT_MAX_SHIFT)
+            return "max_shift must lie in 0 .. SDRX_DRIFT_MAX_SHIFT";
+        for (int i = 0; templ && max_shift > 0 && i < kSpecN; ++i)
+            if (!(templ[i] >= 0.0) || !std::isfinite(templ[i]))
+                return "a template entry is negative or not finite";
+        return nullptr;
+    };
+    if (int rc = leaf_call(c, "sdrx_set_drift", &sdrx_ctx::opt_watch, "watch", &leaf_id, true, 1, kBetweenFrames, bad))
+        return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c)) // frames inside the software pipeline finish with the old setting
+        return rc;
+    drift_host_init(c);
+    sdrx_ctx::Drift &D = c->drift;
+    sdrx_ctx::Drift::Src &S = D.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)];
+    if (max_shift == 0 && S.K == 0)
+        return SDRX_OK;
+    if (!D.d_desc) {
+        const size_t desc_bytes = (sizeof(DriftSrc) + sizeof(DriftBlk) * kDriftMaxBlocks) * (size_t)D.n_slots;
+        const size_t rec_bytes = sizeof(DriftRecord) * (size_t)D.n_slots;
+        HIPCHK(c, hipMalloc(&D.d_desc, desc_bytes));
+        for (int p = 0; p < 2; ++p) {
+            HIPCHK(c, hipMalloc(&D.d_rec[p], rec_bytes));
+            HIPCHK(c, hipMemset(D.d_rec[p], 0, rec_bytes));
+            HIPCHK(c, hipHostMalloc(&D.h_rec[p], rec_bytes, hipHostMallocDefault));
+            memset(D.h_rec[p], 0, rec_bytes);
+        }
+        D.bytes += desc_bytes + 2 * rec_bytes;
+    }
+    if (max_shift > 0) {
+        if (!S.d_state) {
+            HIPCHK(c, hipMalloc(&S.d_state, sizeof(DriftState)));
+            HIPCHK(c, hipMemset(S.d_state, 0, sizeof(DriftState)));
+            D.bytes += sizeof(DriftState);
+        }
+        unsigned char *base = reinterpret_cast<unsigned char *>(S.d_state);
+        if (templ)
+            HIPCHK(c, hipMemcpy(base + offsetof(DriftState, templ), templ, sizeof(double) * kSpecN, hipMemcpyHostToDevice));
+        const unsigned capture = templ ? 0u : 1u; // (an upload also calls off a capture still waiting for its frame)
+        HIPCHK(c, hipMemcpy(base + offsetof(DriftState, capture), &capture, sizeof capture, hipMemcpyHostToDevice));
+    }
+    const sdrx_ctx::Drift::Src before = S;
+    if (S.K != max_shift) {
+        if (S.since != c->frame_no) // (as sdrx_set_watch: the frames before ran in the state they ran in)
+            S.was_K = S.K;
+        S.K = max_shift;
+        S.since = c->frame_no;
+    }
+    S.set_at = c->frame_no;
+    if (int rc = drift_rebuild(c, c->watch.src_ids, c->watch.src_psd)) {
+        S = before;
+        return rc;
+    }
+    return SDRX_OK;
+}
+
+int sdrx_get_drift(sdrx_ctx *c, int leaf_id, sdrx_drift_level *out)
+{
+    if (int rc = leaf_call(c, "sdrx_get_drift", &sdrx_ctx::opt_watch, "watch", &leaf_id, out != nullptr, 1, kDelivered))
+        return rc;
+    sdrx_drift_level r;
+    memset(&r, 0, sizeof r);
+    r.frame = (int64_t)c->host_frame;
+    const sdrx_ctx::Drift &D = c->drift;
+    if (D.h_rec[c->host_slot] && drift_measured_at(c, leaf_id, c->host_frame))
+        memcpy(&r, D.h_rec[c->host_slot] + D.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)].slot, sizeof r);
+    *out = r;
+    return SDRX_OK;
+}
+
+int sdrx_get_drift_profile(sdrx_ctx *c, int leaf_id, double *profile, int64_t *frame)
+{
+    auto bad = [&](int) -> const char * {
+        if (c->watch.leaf.empty() || !c->watch.leaf[(size_t)leaf_id].on)
+            return "is not watched (sdrx_set_watch)";
+        if (c->drift.src.empty() || c->drift.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)].K == 0)
+            return "its source has no drift estimate (sdrx_set_drift)";
+        return nullptr;
+    };
+    if (int rc = leaf_call(c, "sdrx_get_drift_profile", &sdrx_ctx::opt_watch, "watch", &leaf_id, true, 1, kBetweenFrames, bad))
+        return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c))
+        return rc;
+    const sdrx_ctx::Drift::Src &S = c->drift.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)];
+    if (c->frame_no <= std::max(std::max(S.set_at, S.since), c->watch.leaf[(size_t)leaf_id].since))
+        return fail(c, SDRX_ESTATE, "sdrx_get_drift_profile: no frame has been measured for the source of vfo %d yet", leaf_id);
+    if (profile)
+        HIPCHK(c, hipMemcpy(profile, reinterpret_cast<const unsigned char *>(S.d_state) + offsetof(DriftState, profile), sizeof(double) * (size_t)(2 * S.K + 1),
+                            hipMemcpyDeviceToHost));
     if (frame)
         *frame = (int64_t)c->frame_no - 1;
     return SDRX_OK;

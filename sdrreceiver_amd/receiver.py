@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, agc as _agc, meter, squelch as _squelch, watch as _watch
+from . import _lib, agc as _agc, drift as _drift, meter, squelch as _squelch, watch as _watch
 from .topology import Topology, VfoDesc
 
 
@@ -190,6 +190,31 @@ class _LeafCalls:
         f = C.c_int64()
         self._call("get_watch_psd", int(vid), psd.ctypes.data, C.byref(f))
         return psd, f.value
+
+    # -- drift estimate (part of option ``watch``; sdrreceiver_amd.drift): the source's spectrum registered against a template --
+    def set_drift(self, vid: int, template=None, max_shift: int = 0) -> None:
+        """The drift estimate of the source of watched leaf `vid` from the next frame on, over the shifts ``-max_shift ..
+        max_shift`` bins (0: off).  `template`: 8192 float64, each finite and >= 0; None: capture -- the source's spectrum of
+        the next measured frame becomes the template, on the device."""
+        t = None if template is None else np.ascontiguousarray(template, dtype=np.float64).reshape(-1)
+        if t is not None and t.size != _lib.SPECTRUM_BINS:
+            raise ValueError(f"a template has {_lib.SPECTRUM_BINS} entries, not {t.size}")
+        self._call("set_drift", int(vid), None if t is None else t.ctypes.data, int(max_shift))
+
+    def drift(self, vid: int) -> dict:
+        """The drift record of the source of leaf `vid` for the last delivered frame (:func:`sdrreceiver_amd.drift.drift_dict`;
+        :func:`sdrreceiver_amd.drift.estimate_hz` turns it into Hz)."""
+        out = _lib.DriftLevelC()
+        self._call("get_drift", int(vid), C.byref(out))
+        return _drift.drift_dict(out)
+
+    def drift_profile(self, vid: int) -> tuple[np.ndarray, int]:
+        """``(profile, frame)``: the correlation at the shifts ``-K .. K`` (2K + 1 float64) of the source of watched leaf `vid`
+        after the last frame."""
+        prof = np.zeros(2 * _lib.DRIFT_MAX_SHIFT + 1, np.float64)
+        f = C.c_int64()
+        self._call("get_drift_profile", int(vid), prof.ctypes.data, C.byref(f))
+        return prof[:2 * self.drift(vid)["max_shift"] + 1].copy(), f.value
 
     # -- retuning between frames (on a group: on every member that holds the VFO) -------------------------------------------
     def set_mixer_freqs(self, vids, freqs) -> None:
