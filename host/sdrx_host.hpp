@@ -269,6 +269,66 @@ public:
         return r.shift + 0.5 * (r.left - r.right) / den;
     }
     static double drift_hz(const sdrx_drift_level &r, double fs_source) { return drift_bins(r) * fs_source / SDRX_SPECTRUM_BINS; }
+    // band scan (part of option "watch"): the carriers in the integrated spectrum of the source of watched leaf `leaf_id`
+    // (cfg == nullptr or cell_bins 0: off).  scan(): the record of the last delivered frame; scan_hits() / scan_cells(): the
+    // last completed evaluation; scan_hit_hz / scan_mixer_for / scan_unassigned: what a host does with a hit (sdrx.h "Band scan").
+    void set_scan(int leaf_id, const sdrx_scan_cfg *cfg) { call("set_scan", sdrx_group_set_scan, sdrx_set_scan, leaf_id, cfg); }
+    sdrx_scan_level scan(int leaf_id)
+    {
+        sdrx_scan_level out;
+        call("get_scan", sdrx_group_get_scan, sdrx_get_scan, leaf_id, &out);
+        return out;
+    }
+    std::vector<sdrx_scan_hit> scan_hits(int leaf_id, int64_t *frame = nullptr)
+    {
+        std::vector<sdrx_scan_hit> hits(SDRX_SCAN_MAX_HITS);
+        int n = 0;
+        call("get_scan_hits", sdrx_group_get_scan_hits, sdrx_get_scan_hits, leaf_id, hits.data(), (int)hits.size(), &n, frame);
+        hits.resize((size_t)n);
+        return hits;
+    }
+    std::vector<double> scan_cells(int leaf_id, int cell_bins, int64_t *frame = nullptr)
+    {
+        std::vector<double> cells((size_t)(SDRX_SPECTRUM_BINS / cell_bins));
+        call("get_scan_cells", sdrx_group_get_scan_cells, sdrx_get_scan_cells, leaf_id, cells.data(), frame);
+        return cells;
+    }
+    struct scan_hz {
+        double lo, hi, peak;
+    };
+    static scan_hz scan_hit_hz(const sdrx_scan_hit &h, int cell_bins, double fs_source)
+    {
+        const double hz = fs_source / SDRX_SPECTRUM_BINS;
+        const int w = cell_bins, half = SDRX_SPECTRUM_BINS / 2;
+        return scan_hz{(h.first_cell * w - half) * hz, ((h.first_cell + h.n_cells) * w - 1 - half) * hz, (h.peak_cell * w + (w - 1) / 2.0 - half) * hz};
+    }
+    // the integer mixer frequency that puts `hz` (of the source) in the middle of the leaf's watch band
+    static long long scan_mixer_for(const sdrx_vfo_desc &d, double hz)
+    {
+        if (!d.demod_usb)
+            return std::llrint(-hz);
+        const double R = (double)d.fs / (double)(1 << d.decimate_count);
+        const double R_out = d.late_decimate == 5 || d.late_decimate == 6 ? R / (double)d.late_decimate : R;
+        double B = d.filter_bw_hz > 0 ? (double)d.filter_bw_hz : R_out / 2;
+        if (B > R_out / 2)
+            B = R_out / 2;
+        return std::llrint(B / 2 - hz);
+    }
+    // the hits whose [lo, hi] overlaps none of the leaf bands `bands` ([lo, hi] pairs in Hz of the source)
+    static std::vector<sdrx_scan_hit> scan_unassigned(const std::vector<sdrx_scan_hit> &hits, int cell_bins, double fs_source,
+                                                      const std::vector<std::pair<double, double>> &bands)
+    {
+        std::vector<sdrx_scan_hit> out;
+        for (const sdrx_scan_hit &h : hits) {
+            const scan_hz z = scan_hit_hz(h, cell_bins, fs_source);
+            bool taken = false;
+            for (const auto &b : bands)
+                taken = taken || (z.lo <= b.second && b.first <= z.hi);
+            if (!taken)
+                out.push_back(h);
+        }
+        return out;
+    }
 
 private:
     bool started() const { return ctx_ || grp_; }

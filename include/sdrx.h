@@ -581,6 +581,105 @@ typedef struct sdrx_drift_level {
 int sdrx_set_drift(sdrx_ctx *ctx, int leaf_id, const double *templ /* 8192 or NULL */, int max_shift);
 int sdrx_get_drift(sdrx_ctx *ctx, int leaf_id, sdrx_drift_level *out);
 int sdrx_get_drift_profile(sdrx_ctx *ctx, int leaf_id, double *profile /* 2 max_shift + 1 */, int64_t *frame);
+
+/* Band scan (part of option "watch" = 1; no option of its own, as the drift estimate): where are the carriers?  A watch band
+ * is derived from a leaf's mixer frequency, so a carrier no leaf is tuned to is invisible to the watch, and a tree finalized
+ * with spare parked leaves has nothing that tells it which frequency to assign.  (The reference leaves this to its user too:
+ * "the FFT is quite slow so it is probably a good idea to determine the exact frequencies to use via other means".)  The scan
+ * integrates a source's PSD over a few frames, folds it into cells, takes a noise floor as a rank statistic of the cells and
+ * reports every run of cells above a ratio over that floor.  The reference has no counterpart: this text is the definition,
+ * and the device's answer is bit for bit what it says on the PSD sdrx_get_watch_psd returns.
+ *
+ * N = SDRX_SPECTRUM_BINS = 8192; PSD = the watch's PSD of the source for that frame, natural order.
+ * Settings per source, sdrx_scan_cfg, 32 bytes:
+ *   cell_bins w       0 = scan off for this source; else a power of two 1 .. 256.  C = N / w cells, 32 .. 8192
+ *   frames M          frames integrated per evaluation, 1 .. 65 536
+ *   floor_permille q  0 .. 1000; the floor's rank is k = (q * (C - 1)) / 1000 (integer division)
+ *   ratio_q8          power ratio x 256, 1 .. 2^32 - 1
+ *   min_cells         shortest run reported, 1 .. C
+ *   reserved[3]       must be 0
+ * No default ratio_q8, floor_permille or cell width is offered: what a real front end needs has not been measured (as for
+ * the squelch and AGC windows).
+ *
+ * Device state per source, kept from the first sdrx_set_scan that switches the source on, in one allocation that never moves:
+ * ACC[N] doubles, count, and the cells, the hits and the record of the last completed evaluation.
+ *
+ * Per frame in which the source is measured and w > 0:
+ *   1. Integration, IEEE double, one addition per bin: ACC[i] = count == 0 ? PSD[i] : ACC[i] + PSD[i]; then count += 1.
+ *   2. count < M: the frame's record has complete = 0.  count == M: steps 3-7, then count = 0.
+ *   3. Cells in display order: display bin b is natural bin (b + N/2) mod N, so cell 0 begins at -fs/2.  Cell c covers display
+ *      bins c w .. c w + w - 1 (no cell straddles the wrap: w divides N/2).  cell[c] = the sum of its ACC values from left to
+ *      right, ((a0 + a1) + a2) + ...  -- only additions, so contraction cannot matter.
+ *   4. floor = the cell whose 64-bit pattern, read as an unsigned integer, is the k-th smallest of the C patterns (k 0-based,
+ *      equal values each count).  For finite non-negative doubles this is the k-th smallest value; the pattern order makes the
+ *      rule total for anything else.
+ *   5. thr = fl(floor * (ratio_q8 / 256.0)) -- the quotient is exact: one rounding.  hot[c] = cell[c] > thr by the IEEE
+ *      comparison: a NaN is not hot.
+ *   6. A run is a maximal sequence of consecutive hot cells inside 0 .. C - 1.  There is NO wrap: a run touching cell C - 1 and
+ *      one touching cell 0 are two runs.  A run of at least min_cells cells is a hit; hits are ordered by ascending first_cell.
+ *      n_hits counts all of them; the first n_stored = min(n_hits, SDRX_SCAN_MAX_HITS) are stored.
+ *   7. A hit, sdrx_scan_hit, 32 bytes: peak_cell = the lowest cell index among the run's largest cells, peak_pwr =
+ *      cell[peak_cell]; both reserved fields 0.
+ *
+ * The record, sdrx_scan_level, 64 bytes, per source and frame -- written by the device to the fixed-size part of the frame the
+ * source stream held, beside the watch and drift records.  `integrated` is the count behind step 1, `frames` is M, `n_hot` the
+ * number of hot cells.  A frame with complete = 0 has floor = thr = 0 and n_hits = n_stored = n_hot = 0.  A frame in which the
+ * source is not measured -- no leaf of it watched, or w = 0 -- has measured = 0 and every other field but `frame` 0; it costs
+ * no launch and is NO observation: count and ACC stay as they are.
+ *
+ * What a host does with a hit (sdrx_host.hpp scan_hit_hz / scan_mixer_for / scan_unassigned, sdrreceiver_amd/scan.py; not the
+ * device), fs = the source's rate (a leaf's fs), in IEEE double:
+ *   lo   = (first_cell * w - N/2) * fs / N
+ *   hi   = ((first_cell + n_cells) * w - 1 - N/2) * fs / N
+ *   peak = (peak_cell * w + (w - 1) / 2.0 - N/2) * fs / N
+ *   the integer mixer frequency that puts `hz` in the middle of a leaf's watch band: USB leaf rint(B/2 - hz), B as the watch
+ *   defines it; compress() leaf rint(-hz)
+ *   a hit is unassigned when [lo, hi] overlaps none of the given leaf bands [band_lo, band_hi] (closed intervals, Hz)
+ * The loop: scan -> unassigned -> mixer_for -> sdrx_set_mixer_freqs -> sdrx_set_active (with "catchup": the woken leaf hears
+ * the frame the scan completed on).
+ *
+ * sdrx_set_scan: `leaf_id` names the source the way sdrx_set_drift does; its calling rules and check order.  cfg == NULL or
+ * cell_bins == 0 switches the source's scan off (the state stays allocated).  SDRX_EINVAL with nothing changed for a leaf that
+ * is not watched, a field outside the table above, or a non-zero reserved field.  Every accepted call with w > 0 restarts the
+ * integration (count = 0).  A retune of the source's own VFO does not: the host calls sdrx_set_scan again if it wants that.
+ * Nothing is allocated or launched until the first sdrx_set_scan that switches a source on: until then device_bytes, the
+ * launches and every payload are those of the watch alone, or of the watch with drift.  A spectrum, a catch-up or the drift
+ * estimate neither reads nor changes the scan's state; scan and drift on one source each give what they give alone.
+ * sdrx_get_scan: the record of the last DELIVERED frame, with the rules of sdrx_get_drift: any leaf of the source, watched or
+ * not, readable while the next frame is in flight.
+ * sdrx_get_scan_hits: the stored hits of the last COMPLETED evaluation and the frame it completed on, with the rules of
+ * sdrx_get_drift_profile: SDRX_ESTATE while frames are in flight and before the first evaluation completed under the present
+ * setting, SDRX_EINVAL if the leaf is not watched or its source's scan is off.  *n = min(n_stored, max_hits).
+ * sdrx_get_scan_cells: cell[0 .. C - 1] of that evaluation, with the same rules. */
+#define SDRX_SCAN_MAX_HITS 512
+typedef struct sdrx_scan_cfg {
+    int32_t cell_bins;       /* w: 0 off, else a power of two 1 .. 256 */
+    int32_t frames;          /* M: 1 .. 65 536 */
+    int32_t floor_permille;  /* q: 0 .. 1000 */
+    uint32_t ratio_q8;       /* >= 1 */
+    int32_t min_cells;       /* 1 .. C */
+    int32_t reserved[3];     /* 0 */
+} sdrx_scan_cfg;
+typedef struct sdrx_scan_hit {
+    int32_t first_cell, n_cells, peak_cell, reserved;
+    double peak_pwr;
+    double reserved_d;
+} sdrx_scan_hit;
+typedef struct sdrx_scan_level {
+    int64_t frame;
+    double floor, thr;
+    int32_t n_hits, n_stored, n_hot;
+    int32_t integrated;      /* count behind step 1 */
+    int32_t frames;          /* M */
+    int32_t cell_bins;
+    int32_t measured;        /* 0: not measured in that frame -> the other fields but `frame` are 0 */
+    int32_t complete;        /* 1: this frame completed an evaluation */
+    int32_t reserved[2];     /* 0 (the record is 64 bytes) */
+} sdrx_scan_level;
+int sdrx_set_scan(sdrx_ctx *ctx, int leaf_id, const sdrx_scan_cfg *cfg);
+int sdrx_get_scan(sdrx_ctx *ctx, int leaf_id, sdrx_scan_level *out);
+int sdrx_get_scan_hits(sdrx_ctx *ctx, int leaf_id, sdrx_scan_hit *hits, int max_hits, int *n, int64_t *frame);
+int sdrx_get_scan_cells(sdrx_ctx *ctx, int leaf_id, double *cells /* C */, int64_t *frame);
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);
@@ -810,6 +909,12 @@ int sdrx_group_get_watch_psd(sdrx_group *grp, int leaf_id, double *psd, int64_t 
 int sdrx_group_set_drift(sdrx_group *grp, int leaf_id, const double *templ, int max_shift);
 int sdrx_group_get_drift(sdrx_group *grp, int leaf_id, sdrx_drift_level *out);
 int sdrx_group_get_drift_profile(sdrx_group *grp, int leaf_id, double *profile, int64_t *frame);
+/* sdrx_set_scan / sdrx_get_scan / sdrx_get_scan_hits / sdrx_get_scan_cells with an id of the whole tree, routed to the member
+ * that holds the leaf.  A source replicated on several members has one scan state per member, as it has one template. */
+int sdrx_group_set_scan(sdrx_group *grp, int leaf_id, const sdrx_scan_cfg *cfg);
+int sdrx_group_get_scan(sdrx_group *grp, int leaf_id, sdrx_scan_level *out);
+int sdrx_group_get_scan_hits(sdrx_group *grp, int leaf_id, sdrx_scan_hit *hits, int max_hits, int *n, int64_t *frame);
+int sdrx_group_get_scan_cells(sdrx_group *grp, int leaf_id, double *cells, int64_t *frame);
 
 /* sdrx_get_preroll routed to the member that owns the leaf; sdrx_get_preroll_count summed over the members (group option
  * "preroll" = 1). */

@@ -15,6 +15,7 @@ SDRX_EINVAL, SDRX_ESTATE, SDRX_EFILTER, SDRX_EHIP, SDRX_EUNSUPPORTED, SDRX_ENOME
 SDRX_DIFFERENT = 1  # sdrx_*_if_same: the frame is not the one the source context staged
 SPECTRUM_BINS, SPECTRUM_RAW = 8192, -2  # SDRX_SPECTRUM_BINS, SDRX_SPECTRUM_RAW
 DRIFT_MAX_SHIFT = 1024  # SDRX_DRIFT_MAX_SHIFT
+SCAN_MAX_HITS = 512  # SDRX_SCAN_MAX_HITS
 
 
 class VfoDescC(C.Structure):
@@ -91,6 +92,25 @@ class DriftLevelC(C.Structure):
     _fields_ = [("frame", C.c_int64), ("peak", C.c_double), ("left", C.c_double), ("right", C.c_double), ("zero", C.c_double),
                 ("shift", C.c_int32), ("max_shift", C.c_int32), ("measured", C.c_int32), ("captured", C.c_int32),
                 ("reserved", C.c_int32 * 2)]
+
+
+class ScanCfgC(C.Structure):
+    """struct sdrx_scan_cfg"""
+    _fields_ = [("cell_bins", C.c_int32), ("frames", C.c_int32), ("floor_permille", C.c_int32), ("ratio_q8", C.c_uint32),
+                ("min_cells", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class ScanHitC(C.Structure):
+    """struct sdrx_scan_hit"""
+    _fields_ = [("first_cell", C.c_int32), ("n_cells", C.c_int32), ("peak_cell", C.c_int32), ("reserved", C.c_int32),
+                ("peak_pwr", C.c_double), ("reserved_d", C.c_double)]
+
+
+class ScanLevelC(C.Structure):
+    """struct sdrx_scan_level"""
+    _fields_ = [("frame", C.c_int64), ("floor", C.c_double), ("thr", C.c_double), ("n_hits", C.c_int32), ("n_stored", C.c_int32),
+                ("n_hot", C.c_int32), ("integrated", C.c_int32), ("frames", C.c_int32), ("cell_bins", C.c_int32),
+                ("measured", C.c_int32), ("complete", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class WatchLevelC(C.Structure):
@@ -172,6 +192,14 @@ SYMBOLS = {
     "sdrx_group_set_drift": (_i, [_vp, _i, _vp, _i]),
     "sdrx_group_get_drift": (_i, [_vp, _i, C.POINTER(DriftLevelC)]),
     "sdrx_group_get_drift_profile": (_i, [_vp, _i, _vp, C.POINTER(C.c_int64)]),
+    "sdrx_set_scan": (_i, [_vp, _i, C.POINTER(ScanCfgC)]),
+    "sdrx_get_scan": (_i, [_vp, _i, C.POINTER(ScanLevelC)]),
+    "sdrx_get_scan_hits": (_i, [_vp, _i, _vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "sdrx_get_scan_cells": (_i, [_vp, _i, _vp, C.POINTER(C.c_int64)]),
+    "sdrx_group_set_scan": (_i, [_vp, _i, C.POINTER(ScanCfgC)]),
+    "sdrx_group_get_scan": (_i, [_vp, _i, C.POINTER(ScanLevelC)]),
+    "sdrx_group_get_scan_hits": (_i, [_vp, _i, _vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "sdrx_group_get_scan_cells": (_i, [_vp, _i, _vp, C.POINTER(C.c_int64)]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

@@ -34,6 +34,7 @@
 #include "agc.hip"
 #include "watch.hip"
 #include "drift.hip"
+#include "scan.hip"
 #include "tapdesign.h"
 
 using namespace sdrx;
@@ -52,6 +53,11 @@ static_assert(sizeof(sdrx_watch_level) == 48 && sizeof(WatchRecord) == 48 && off
 static_assert(sizeof(sdrx_drift_level) == 64 && sizeof(DriftRecord) == 64 && offsetof(sdrx_drift_level, zero) == offsetof(DriftRecord, zero) &&
                   offsetof(sdrx_drift_level, captured) == offsetof(DriftRecord, captured) && SDRX_DRIFT_MAX_SHIFT == kDriftMaxShift,
               "sdrx_drift_level ABI layout");
+static_assert(sizeof(sdrx_scan_cfg) == 32 && sizeof(ScanCfg) == 32 && offsetof(sdrx_scan_cfg, min_cells) == offsetof(ScanCfg, min_cells) &&
+                  sizeof(sdrx_scan_hit) == 32 && sizeof(ScanHit) == 32 && offsetof(sdrx_scan_hit, peak_pwr) == offsetof(ScanHit, peak_pwr) &&
+                  sizeof(sdrx_scan_level) == 64 && sizeof(ScanRecord) == 64 && offsetof(sdrx_scan_level, n_hits) == offsetof(ScanRecord, n_hits) &&
+                  offsetof(sdrx_scan_level, complete) == offsetof(ScanRecord, complete) && SDRX_SCAN_MAX_HITS == kScanMaxHits,
+              "band scan ABI layout");
 
 #include "sdrx_ctx.h"
 
@@ -164,6 +170,16 @@ void free_device_state(sdrx_ctx *c)
             (void)hipHostFree(c->drift.h_rec[p]);
     }
     c->drift = sdrx_ctx::Drift();
+    // band scan: as before the first sdrx_set_scan
+    for (auto &s : c->scan.src)
+        dfree(s.d_state);
+    dfree(c->scan.d_src);
+    for (int p = 0; p < 2; ++p) {
+        dfree(c->scan.d_rec[p]);
+        if (c->scan.h_rec[p])
+            (void)hipHostFree(c->scan.h_rec[p]);
+    }
+    c->scan = sdrx_ctx::Scan();
 }
 
 } // namespace
@@ -1200,7 +1216,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->exact = c->opt_exact;
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq.bytes + sizeof(int) * c->park.words + c->watch.bytes + c->drift.bytes + c->agc.bytes);
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq.bytes + sizeof(int) * c->park.words + c->watch.bytes + c->drift.bytes + c->scan.bytes + c->agc.bytes);
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

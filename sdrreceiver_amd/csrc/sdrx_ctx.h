@@ -266,6 +266,28 @@ struct sdrx_ctx {
         DriftBlk *d_blk() const { return reinterpret_cast<DriftBlk *>(d_desc + sizeof(DriftSrc) * (size_t)n_slots); }
     } drift;
 
+    // Band scan (sdrx_set_scan, scan.hip), part of option watch.  A source -- indexed as Drift's -- keeps its
+    // integrated spectrum, its count and the cells, hits and record of its last completed evaluation in one device allocation
+    // of its own from its first sdrx_set_scan on.  Host bookkeeping as the drift keeps it: a frame f >= since ran with cell
+    // width cfg.cell_bins, the frames before it with was_w.  The record of frame f goes to d_rec[f & 1] -- one slot per possible
+    // source -- and travels with the watch records (queue_watch).  Everything is allocated by the first sdrx_set_scan that
+    // switches a source on.
+    struct Scan {
+        struct Src {
+            ScanCfg cfg = {};  // cell_bins 0: off
+            int was_w = 0;
+            unsigned long long since = 0;
+            ScanState *d_state = nullptr;
+            int slot = -1;
+        };
+        std::vector<Src> src; // sized by the first scan call
+        int n_slots = 0;
+        ScanSrc *d_src = nullptr; // ScanSrc[n_slots]
+        ScanRecord *d_rec[2] = {nullptr, nullptr}, *h_rec[2] = {nullptr, nullptr};
+        size_t bytes = 0;           // device memory it holds
+        std::vector<int> src_begin; // per source group (as Watch::seg_begin), n_levels + 2 entries; empty: never switched on
+    } scan;
+
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first
     // frame that fills them.  The first such leaf uses the arena's buffer, further ones buffers of their own (hipMalloc).

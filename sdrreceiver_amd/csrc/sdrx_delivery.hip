@@ -84,6 +84,8 @@ int queue_watch(sdrx_ctx *c, int p, hipStream_t st)
         HIPCHK(c, hipMemcpyAsync(c->watch.h_rec[p], c->watch.d_rec[p], sizeof(WatchRecord) * (size_t)c->watch.n_slots, hipMemcpyDeviceToHost, st));
     if (c->drift.d_rec[p]) // ... and the drift records of its sources (nothing before the first sdrx_set_drift)
         HIPCHK(c, hipMemcpyAsync(c->drift.h_rec[p], c->drift.d_rec[p], sizeof(DriftRecord) * (size_t)c->drift.n_slots, hipMemcpyDeviceToHost, st));
+    if (c->scan.d_rec[p]) // ... and their band-scan records (nothing before the first sdrx_set_scan)
+        HIPCHK(c, hipMemcpyAsync(c->scan.h_rec[p], c->scan.d_rec[p], sizeof(ScanRecord) * (size_t)c->scan.n_slots, hipMemcpyDeviceToHost, st));
     return SDRX_OK;
 }
 int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st)

@@ -141,7 +141,7 @@ void spectrum_raw_step(sdrx_ctx *c, const void *raw, int raw_mode)
 
 // Option watch: the sources of groups g_lo..g_hi (0: the raw frame, 1 + l: the streams of tree level l) that have a watched
 // leaf -- one k_watch_psd workgroup per (source, segment), then one k_watch_bands wave per watched leaf of those sources, then
-// the drift estimate of those sources that have one (sdrx_set_drift).
+// the drift estimate (sdrx_set_drift) and the band scan (sdrx_set_scan) of those sources that have one.
 // Not bracketed: sdrx_get_kernel_times keeps its SDRX_NKERNELS kinds.  Nothing watched: nothing is launched.
 void watch_launch_groups(sdrx_ctx *c, hipStream_t st, int g_lo, int g_hi, const WatchArgs &A)
 {
@@ -158,11 +158,19 @@ void watch_launch_groups(sdrx_ctx *c, hipStream_t st, int g_lo, int g_hi, const 
     // drift estimate: one k_watch_drift workgroup per (source of those groups with a template, block of shifts), on the PSD
     // k_watch_psd has just left.  Nothing before the first sdrx_set_drift; not bracketed either.
     const sdrx_ctx::Drift &D = c->drift;
-    if (D.blk_begin.empty())
+    if (!D.blk_begin.empty()) {
+        const int b0 = D.blk_begin[(size_t)g_lo], b1 = D.blk_begin[(size_t)g_hi + 1];
+        if (b1 > b0)
+            hipLaunchKernelGGL(k_watch_drift, dim3(b1 - b0), dim3(kSpecThreads), 0, st, D.d_src(), D.d_blk() + b0, A, D.d_rec[0], D.d_rec[1]);
+    }
+    // band scan: one k_watch_scan workgroup per source of those groups with the scan on, on the same PSD.  Nothing before the
+    // first sdrx_set_scan; not bracketed either.
+    const sdrx_ctx::Scan &S = c->scan;
+    if (S.src_begin.empty())
         return;
-    const int b0 = D.blk_begin[(size_t)g_lo], b1 = D.blk_begin[(size_t)g_hi + 1];
-    if (b1 > b0)
-        hipLaunchKernelGGL(k_watch_drift, dim3(b1 - b0), dim3(kSpecThreads), 0, st, D.d_src(), D.d_blk() + b0, A, D.d_rec[0], D.d_rec[1]);
+    const int c0 = S.src_begin[(size_t)g_lo], c1 = S.src_begin[(size_t)g_hi + 1];
+    if (c1 > c0)
+        hipLaunchKernelGGL(k_watch_scan, dim3(c1 - c0), dim3(kSpecThreads), 0, st, S.d_src + c0, A, S.d_rec[0], S.d_rec[1]);
 }
 // ... of the VFO streams of tree levels lo..hi, where spectrum_launch reads them (the same frames per level)
 void watch_launch(sdrx_ctx *c, hipStream_t st, int lo, int hi, unsigned long long f, const unsigned long long *frames)

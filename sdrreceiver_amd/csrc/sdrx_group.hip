@@ -786,6 +786,45 @@ int sdrx_group_get_drift_profile(sdrx_group *g, int leaf_id, double *profile, in
     return member_rc(g, w.first, sdrx_get_drift_profile(g->m[(size_t)w.first].c, w.second, profile, frame));
 }
 
+// The band scan of the source of leaf `leaf_id`, on the member that holds the leaf (its own copy of the source)
+int sdrx_group_set_scan(sdrx_group *g, int leaf_id, const sdrx_scan_cfg *cfg)
+{
+    std::pair<int, int> w;
+    if (int rc = owner(g, "sdrx_group_set_scan", leaf_id, &w))
+        return rc;
+    if (g->in_flight > 0)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_set_scan: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
+    return member_rc(g, w.first, sdrx_set_scan(g->m[(size_t)w.first].c, w.second, cfg));
+}
+
+int sdrx_group_get_scan(sdrx_group *g, int leaf_id, sdrx_scan_level *out)
+{
+    std::pair<int, int> w;
+    if (int rc = owner(g, "sdrx_group_get_scan", leaf_id, &w))
+        return rc;
+    return member_rc(g, w.first, sdrx_get_scan(g->m[(size_t)w.first].c, w.second, out));
+}
+
+int sdrx_group_get_scan_hits(sdrx_group *g, int leaf_id, sdrx_scan_hit *hits, int max_hits, int *n, int64_t *frame)
+{
+    std::pair<int, int> w;
+    if (int rc = owner(g, "sdrx_group_get_scan_hits", leaf_id, &w))
+        return rc;
+    if (g->in_flight > 0)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_scan_hits: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
+    return member_rc(g, w.first, sdrx_get_scan_hits(g->m[(size_t)w.first].c, w.second, hits, max_hits, n, frame));
+}
+
+int sdrx_group_get_scan_cells(sdrx_group *g, int leaf_id, double *cells, int64_t *frame)
+{
+    std::pair<int, int> w;
+    if (int rc = owner(g, "sdrx_group_get_scan_cells", leaf_id, &w))
+        return rc;
+    if (g->in_flight > 0)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_scan_cells: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
+    return member_rc(g, w.first, sdrx_get_scan_cells(g->m[(size_t)w.first].c, w.second, cells, frame));
+}
+
 int sdrx_group_get_egress(sdrx_group *g, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied)
 {
     if (!g)

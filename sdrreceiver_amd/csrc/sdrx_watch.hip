@@ -117,6 +117,85 @@ bool drift_measured_at(const sdrx_ctx *c, int leaf_id, unsigned long long frame)
     return false;
 }
 
+// ---- band scan: host bookkeeping of every possible source (no device memory), by the first scan call; the slots are the drift's
+void scan_host_init(sdrx_ctx *c)
+{
+    sdrx_ctx::Scan &S = c->scan;
+    if (!S.src.empty())
+        return;
+    S.src.assign(c->nodes.size() + 1, sdrx_ctx::Scan::Src());
+    S.n_slots = 0;
+    S.src[0].slot = S.n_slots++;
+    for (size_t id = 0; id < c->nodes.size(); ++id)
+        if (!c->nodes[id].leaf)
+            S.src[1 + id].slot = S.n_slots++;
+}
+
+// The scan launch list for the measured sources `ids` whose PSDs lie at `off_psd` (as drift_rebuild): the sources among them
+// with cell_bins > 0, one workgroup each.  Nothing before the first sdrx_set_scan that switched a source on.
+int scan_rebuild(sdrx_ctx *c, const std::vector<int> &ids, const std::vector<size_t> &off_psd)
+{
+    sdrx_ctx::Scan &S = c->scan;
+    if (!S.d_src)
+        return SDRX_OK;
+    std::vector<ScanSrc> srcs;
+    std::vector<int> begin((size_t)c->n_levels + 2, 0);
+    size_t k = 0;
+    for (int g = 0; g <= c->n_levels; ++g) {
+        begin[(size_t)g] = (int)srcs.size();
+        for (; k < ids.size() && (ids[k] < 0 ? 0 : c->nodes[(size_t)ids[k]].level + 1) == g; ++k) {
+            const sdrx_ctx::Scan::Src &R = S.src[(size_t)(1 + ids[k])];
+            if (R.cfg.cell_bins == 0)
+                continue;
+            ScanSrc e;
+            e.psd = reinterpret_cast<const double *>(c->watch.d_data + off_psd[k]);
+            e.state = R.d_state;
+            e.cfg = R.cfg;
+            e.level = ids[k] < 0 ? -1 : std::min(g - 1, kMaxLevels - 1);
+            e.slot = R.slot;
+            srcs.push_back(e);
+        }
+    }
+    begin[(size_t)c->n_levels + 1] = (int)srcs.size();
+    if (!srcs.empty())
+        HIPCHK(c, hipMemcpy(S.d_src, srcs.data(), sizeof(ScanSrc) * srcs.size(), hipMemcpyHostToDevice));
+    S.src_begin = begin;
+    return SDRX_OK;
+}
+
+// was the source of `leaf_id` scanned in frame `frame`: cell_bins > 0 then, and a leaf of it watched
+bool scan_measured_at(const sdrx_ctx *c, int leaf_id, unsigned long long frame)
+{
+    const sdrx_ctx::Scan &S = c->scan;
+    if (S.src.empty())
+        return false;
+    const int parent = c->nodes[(size_t)leaf_id].d.parent_id;
+    const sdrx_ctx::Scan::Src &R = S.src[(size_t)(1 + parent)];
+    if ((frame >= R.since ? R.cfg.cell_bins : R.was_w) == 0)
+        return false;
+    for (size_t id = 0; id < c->nodes.size(); ++id)
+        if (c->nodes[id].leaf && c->nodes[id].d.parent_id == parent && c->watch.watched_at((int)id, frame))
+            return true;
+    return false;
+}
+
+// what is wrong with a setting that switches a scan on (include/sdrx.h "Band scan", the table)
+const char *bad_scan(const sdrx_scan_cfg &s)
+{
+    const int w = s.cell_bins;
+    if (w < 1 || w > kScanMaxCellBins || (w & (w - 1)) != 0)
+        return "cell_bins must be 0 or a power of two 1 .. 256";
+    if (s.frames < 1 || s.frames > 65536)
+        return "frames must lie in 1 .. 65536";
+    if (s.floor_permille < 0 || s.floor_permille > 1000)
+        return "floor_permille must lie in 0 .. 1000";
+    if (s.ratio_q8 == 0)
+        return "ratio_q8 must be at least 1";
+    if (s.min_cells < 1 || s.min_cells > kSpecN / w)
+        return "min_cells must lie in 1 .. 8192 / cell_bins";
+    return nullptr;
+}
+
 // The launch lists for the present selection, uploaded whenever it or a watched leaf's band changes.  Synchronous: never inside
 // a frame call, and the context is drained.  The sources in launch order: the raw frame, then the parents by tree level.
 int watch_rebuild(sdrx_ctx *c)
@@ -228,6 +307,8 @@ int watch_rebuild(sdrx_ctx *c)
     }
     if (int rc = drift_rebuild(c, ids, off_psd)) // (the templates stay where they are; their sources' PSDs may have moved)
         return rc;
+    if (int rc = scan_rebuild(c, ids, off_psd)) // (so do the scans' states)
+        return rc;
     W.src_ids = ids; // (last: the frame sequence launches from these lists only when everything above succeeded)
     return SDRX_OK;
 }
@@ -247,6 +328,35 @@ int watch_retuned(sdrx_ctx *c, const int *ids, int n)
         any |= L.on != 0;
     }
     return any ? watch_rebuild(c) : SDRX_OK;
+}
+
+// what sdrx_get_scan_hits and sdrx_get_scan_cells share: the checks, and the record of the last completed evaluation
+int scan_evaluation(sdrx_ctx *c, const char *what, int leaf_id, bool arrays, const ScanState **state, ScanRecord *head)
+{
+    auto bad = [&](int) -> const char * {
+        if (c->watch.leaf.empty() || !c->watch.leaf[(size_t)leaf_id].on)
+            return "is not watched (sdrx_set_watch)";
+        if (c->scan.src.empty() || c->scan.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)].cfg.cell_bins == 0)
+            return "its source has no band scan (sdrx_set_scan)";
+        return nullptr;
+    };
+    if (int rc = leaf_call(c, what, &sdrx_ctx::opt_watch, "watch", &leaf_id, arrays, 1, kBetweenFrames, bad))
+        return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c))
+        return rc;
+    const ScanState *st = c->scan.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)].d_state;
+    struct {
+        ScanRecord head;
+        unsigned count, valid;
+    } tail;
+    static_assert(offsetof(ScanState, count) == offsetof(ScanState, head) + sizeof(ScanRecord), "head, count and valid are read together");
+    HIPCHK(c, hipMemcpy(&tail, reinterpret_cast<const unsigned char *>(st) + offsetof(ScanState, head), sizeof tail, hipMemcpyDeviceToHost));
+    if (!tail.valid)
+        return fail(c, SDRX_ESTATE, "%s: no evaluation has completed for the source of vfo %d under the present setting yet", what, leaf_id);
+    *state = st;
+    *head = tail.head;
+    return SDRX_OK;
 }
 
 } // namespace
@@ -431,6 +541,109 @@ int sdrx_get_drift_profile(sdrx_ctx *c, int leaf_id, double *profile, int64_t *f
                             hipMemcpyDeviceToHost));
     if (frame)
         *frame = (int64_t)c->frame_no - 1;
+    return SDRX_OK;
+}
+
+int sdrx_set_scan(sdrx_ctx *c, int leaf_id, const sdrx_scan_cfg *cfg)
+{
+    const bool on = cfg && cfg->cell_bins != 0;
+    auto bad = [&](int) -> const char * {
+        if (c->watch.leaf.empty() || !c->watch.leaf[(size_t)leaf_id].on)
+            return "is not watched (sdrx_set_watch)";
+        if (cfg && (cfg->reserved[0] || cfg->reserved[1] || cfg->reserved[2]))
+            return "a reserved field is not 0";
+        return on ? bad_scan(*cfg) : nullptr;
+    };
+    if (int rc = leaf_call(c, "sdrx_set_scan", &sdrx_ctx::opt_watch, "watch", &leaf_id, true, 1, kBetweenFrames, bad))
+        return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c)) // frames inside the software pipeline finish with the old setting
+        return rc;
+    scan_host_init(c);
+    sdrx_ctx::Scan &S = c->scan;
+    sdrx_ctx::Scan::Src &R = S.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)];
+    if (!on && R.cfg.cell_bins == 0)
+        return SDRX_OK;
+    if (!S.d_src) {
+        const size_t src_bytes = sizeof(ScanSrc) * (size_t)S.n_slots, rec_bytes = sizeof(ScanRecord) * (size_t)S.n_slots;
+        HIPCHK(c, hipMalloc(&S.d_src, src_bytes));
+        for (int p = 0; p < 2; ++p) {
+            HIPCHK(c, hipMalloc(&S.d_rec[p], rec_bytes));
+            HIPCHK(c, hipMemset(S.d_rec[p], 0, rec_bytes));
+            HIPCHK(c, hipHostMalloc(&S.h_rec[p], rec_bytes, hipHostMallocDefault));
+            memset(S.h_rec[p], 0, rec_bytes);
+        }
+        S.bytes += src_bytes + 2 * rec_bytes;
+    }
+    if (on) {
+        if (!R.d_state) {
+            HIPCHK(c, hipMalloc(&R.d_state, sizeof(ScanState)));
+            HIPCHK(c, hipMemset(R.d_state, 0, sizeof(ScanState)));
+            S.bytes += sizeof(ScanState);
+        }
+        // every accepted setting restarts the integration, and the last evaluation is no longer this setting's
+        static_assert(offsetof(ScanState, valid) == offsetof(ScanState, count) + sizeof(unsigned), "count and valid are cleared together");
+        HIPCHK(c, hipMemset(reinterpret_cast<unsigned char *>(R.d_state) + offsetof(ScanState, count), 0, 2 * sizeof(unsigned)));
+    }
+    const sdrx_ctx::Scan::Src before = R;
+    const int w = on ? cfg->cell_bins : 0;
+    if (R.cfg.cell_bins != w) {
+        if (R.since != c->frame_no) // (as sdrx_set_watch: the frames before ran in the state they ran in)
+            R.was_w = R.cfg.cell_bins;
+        R.since = c->frame_no;
+    }
+    if (on)
+        memcpy(&R.cfg, cfg, sizeof R.cfg);
+    else
+        R.cfg.cell_bins = 0;
+    if (int rc = scan_rebuild(c, c->watch.src_ids, c->watch.src_psd)) {
+        R = before;
+        return rc;
+    }
+    return SDRX_OK;
+}
+
+int sdrx_get_scan(sdrx_ctx *c, int leaf_id, sdrx_scan_level *out)
+{
+    if (int rc = leaf_call(c, "sdrx_get_scan", &sdrx_ctx::opt_watch, "watch", &leaf_id, out != nullptr, 1, kDelivered))
+        return rc;
+    sdrx_scan_level r;
+    memset(&r, 0, sizeof r);
+    r.frame = (int64_t)c->host_frame;
+    const sdrx_ctx::Scan &S = c->scan;
+    if (S.h_rec[c->host_slot] && scan_measured_at(c, leaf_id, c->host_frame))
+        memcpy(&r, S.h_rec[c->host_slot] + S.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)].slot, sizeof r);
+    *out = r;
+    return SDRX_OK;
+}
+
+int sdrx_get_scan_hits(sdrx_ctx *c, int leaf_id, sdrx_scan_hit *hits, int max_hits, int *n, int64_t *frame)
+{
+    const ScanState *st = nullptr;
+    ScanRecord head;
+    if (int rc = scan_evaluation(c, "sdrx_get_scan_hits", leaf_id, max_hits >= 0 && (hits || max_hits == 0), &st, &head))
+        return rc;
+    const int take = std::min(head.n_stored, max_hits);
+    if (take > 0)
+        HIPCHK(c, hipMemcpy(hits, reinterpret_cast<const unsigned char *>(st) + offsetof(ScanState, hits), sizeof(ScanHit) * (size_t)take, hipMemcpyDeviceToHost));
+    if (n)
+        *n = take;
+    if (frame)
+        *frame = (int64_t)head.frame;
+    return SDRX_OK;
+}
+
+int sdrx_get_scan_cells(sdrx_ctx *c, int leaf_id, double *cells, int64_t *frame)
+{
+    const ScanState *st = nullptr;
+    ScanRecord head;
+    if (int rc = scan_evaluation(c, "sdrx_get_scan_cells", leaf_id, true, &st, &head))
+        return rc;
+    if (cells)
+        HIPCHK(c, hipMemcpy(cells, reinterpret_cast<const unsigned char *>(st) + offsetof(ScanState, cells), sizeof(double) * (size_t)(kSpecN / head.cell_bins),
+                            hipMemcpyDeviceToHost));
+    if (frame)
+        *frame = (int64_t)head.frame;
     return SDRX_OK;
 }
 

@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, agc as _agc, drift as _drift, meter, squelch as _squelch, watch as _watch
+from . import _lib, agc as _agc, drift as _drift, meter, scan as _scan, squelch as _squelch, watch as _watch
 from .topology import Topology, VfoDesc
 
 
@@ -215,6 +215,49 @@ class _LeafCalls:
         f = C.c_int64()
         self._call("get_drift_profile", int(vid), prof.ctypes.data, C.byref(f))
         return prof[:2 * self.drift(vid)["max_shift"] + 1].copy(), f.value
+
+    # -- band scan (part of option ``watch``; sdrreceiver_amd.scan): the carriers in the source's integrated spectrum -------------
+    def set_scan(self, vid: int, cell_bins: int = 0, frames: int = 1, floor_permille: int = 0, ratio_q8: int = 0,
+                 min_cells: int = 1) -> None:
+        """The band scan of the source of watched leaf `vid` from the next frame on: cells of `cell_bins` bins (a power of two 1 ..
+        256; 0: off), `frames` frames integrated per evaluation, the floor at rank ``floor_permille (C - 1) / 1000`` of the
+        cells, hot above ``ratio_q8 / 256`` times the floor, runs of at least `min_cells` cells reported.  Every call that
+        switches it on restarts the integration."""
+        if int(cell_bins) == 0:
+            self._call("set_scan", int(vid), None)
+            return
+        if not hasattr(self, "_scan_w"):
+            self._scan_w = {}
+        if not 0 <= int(ratio_q8) < 1 << 32:
+            raise ValueError(f"ratio_q8 {ratio_q8} is no uint32")
+        cfg = _lib.ScanCfgC(int(cell_bins), int(frames), int(floor_permille), int(ratio_q8), int(min_cells))
+        self._call("set_scan", int(vid), C.byref(cfg))
+        self._scan_w[self.descs[int(vid)].parent] = int(cell_bins)
+
+    def scan(self, vid: int) -> dict:
+        """The scan record of the source of leaf `vid` for the last delivered frame (:func:`sdrreceiver_amd.scan.scan_dict`)."""
+        out = _lib.ScanLevelC()
+        self._call("get_scan", int(vid), C.byref(out))
+        return _scan.scan_dict(out)
+
+    def scan_hits(self, vid: int, max_hits: int = _lib.SCAN_MAX_HITS) -> tuple[list, int]:
+        """``(hits, frame)``: the stored hits (dicts, :func:`sdrreceiver_amd.scan.hit_dict`) of the last completed evaluation of
+        the source of watched leaf `vid`, at most `max_hits`, and the frame it completed on."""
+        buf = (_lib.ScanHitC * max(int(max_hits), 1))()
+        n, f = C.c_int(), C.c_int64()
+        self._call("get_scan_hits", int(vid), C.cast(buf, C.c_void_p), int(max_hits), C.byref(n), C.byref(f))
+        return [_scan.hit_dict(buf[k]) for k in range(n.value)], f.value
+
+    def scan_cells(self, vid: int) -> tuple[np.ndarray, int]:
+        """``(cells, frame)``: the C = 8192 / cell_bins cell powers (float64, display order) of that evaluation."""
+        cells = np.zeros(_lib.SPECTRUM_BINS, np.float64)
+        f = C.c_int64()
+        self._call("get_scan_cells", int(vid), cells.ctypes.data, C.byref(f))
+        return cells[:_lib.SPECTRUM_BINS // self._scan_cell_bins(int(vid))].copy(), f.value
+
+    def _scan_cell_bins(self, vid: int) -> int:
+        # the width this wrapper last set for the leaf's source (the C call returns C doubles and leaves C to its caller)
+        return getattr(self, "_scan_w", {}).get(self.descs[vid].parent, 1)
 
     # -- retuning between frames (on a group: on every member that holds the VFO) -------------------------------------------
     def set_mixer_freqs(self, vids, freqs) -> None:
