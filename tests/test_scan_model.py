@@ -308,3 +308,110 @@ def test_the_edge_tone_gives_two_hits():
             fields, hits, cell = sc.evaluate(p, sc.cfg(w, floor_permille=500, ratio_q8=64 * 256))
             C_ = N // w
             assert fields["n_hits"] == 2 and hits[0]["first_cell"] == 0 and hits[1]["first_cell"] + hits[1]["n_cells"] == C_, (n_parent, w, hits)
+
+
+# ---- the crafted inputs of tests/test_gpu_scan_crafted.py: every condition that file relies on, on the model's own PSD ----------
+@functools.lru_cache(maxsize=None)
+def _crafted_psd(name, arg=None):
+    topo = sc.crafted_tree()
+    build = dict(comb=sc.comb_frame, all_hot=sc.all_hot_frame, spread=sc.spread_comb_frame, edge=sc.edge_noise_frame)
+    iq = sc.ruler_for(topo, arg) if name == "ruler" else sc.ruler2_frames(topo)[arg] if name == "ruler2" else build[name](topo)
+    assert iq.dtype == np.float32 and iq.shape == (2 * topo.frame,) and wr.segments(topo.frame)[0] == 8
+    return wr.psd(iq.view(np.complex64))
+
+
+def _patterns(a):
+    return np.unique(np.ascontiguousarray(a, np.float64).view(np.uint64))
+
+
+def test_crafted_segments_repeat_exactly():
+    """The same segment at each of the eight starts: the PSD is exactly 8 x one segment's fp32 power."""
+    topo = sc.crafted_tree()
+    iq = sc.edge_noise_frame(topo).view(np.complex64)
+    one = wr.segment_power(iq[:N]).astype(np.float64)
+    assert np.array_equal(_crafted_psd("edge"), 8.0 * one)
+
+
+def test_comb_ties():
+    p = _crafted_psd("comb")
+    assert _patterns(p).size == 2 and _patterns(p[0::2]).size == 1 and _patterns(p[1::2]).size == 1
+    low, high = float(p[1]), float(p[0])
+    assert 0.0 < low < 1e-2 and high > 3e4
+    assert sc.rank(500, N) == 4095 and sc.rank(501, N) == 4103  # the last low cell; a high cell
+    for q in sc.COMB_LOW_Q:
+        f, hits, _ = sc.evaluate(p, sc.cfg(1, floor_permille=q, ratio_q8=sc.COMB_RATIO_Q8))
+        assert (f["floor"], f["n_hits"], f["n_stored"], f["n_hot"]) == (low, 4096, 512, 4096)
+        assert all(h["n_cells"] == 1 and h["first_cell"] == 2 * i for i, h in enumerate(hits))
+    f, hits, _ = sc.evaluate(p, sc.cfg(1, floor_permille=sc.COMB_HIGH_Q, ratio_q8=sc.COMB_RATIO_Q8))
+    assert (f["floor"], f["n_hits"], f["n_hot"]) == (high, 0, 0)
+    for w in sc.WIDTHS[1:]:
+        C_ = N // w
+        f, hits, cell = sc.evaluate(p, sc.cfg(w, floor_permille=500, ratio_q8=256))
+        assert _patterns(cell).size == 1 and (f["n_hits"], f["n_hot"]) == (0, 0), w  # every cell ties: equal is not hot
+        f, hits, cell = sc.evaluate(p, sc.cfg(w, floor_permille=500, ratio_q8=255))
+        assert hits == [dict(first_cell=0, n_cells=C_, peak_cell=0, peak_pwr=float(cell[0]))] and f["n_hot"] == C_, w  # the first of C equal largest
+
+
+def test_all_hot_is_one_run_whose_peak_is_the_argmax():
+    p = _crafted_psd("all_hot")
+    assert p.min() > 0.0
+    for w in sc.WIDTHS:
+        C_ = N // w
+        for min_cells in (1, C_) + ((32,) if w == 256 else ()):
+            f, hits, cell = sc.evaluate(p, sc.all_hot_cfg(w, min_cells))
+            assert f["thr"] == cell.min() / 256.0 and f["n_hot"] == C_
+            assert hits == [dict(first_cell=0, n_cells=C_, peak_cell=int(np.argmax(cell)), peak_pwr=float(cell.max()))], (w, min_cells)
+            if w in sc.ALL_HOT_PEAKS:
+                assert hits[0]["peak_cell"] == sc.ALL_HOT_PEAKS[w]
+        if C_ >= sc.THREADS:  # the run ends in the last wave; its peak lies in an inner one and reaches the end through the waves' totals
+            assert 0 < hits[0]["peak_cell"] // (64 * sc.per_thread(w)) < 7, w
+
+
+def test_ruler_runs_land_on_the_thread_and_wave_grid():
+    for w in sc.WIDTHS:
+        p = _crafted_psd("ruler", w)
+        f, hits, cell = sc.evaluate(p, sc.ruler_cfg(w))
+        hot = cell > f["thr"]
+        print(w, f, "cold max", cell[~hot].max(), "hot min", cell[hot].min(), [(h["first_cell"], h["n_cells"], h["peak_cell"]) for h in hits])
+        assert cell[~hot].max() < 0.7 * f["thr"] and cell[hot].min() > 2.0 * f["thr"], w  # no cell near the threshold
+        cond = sc.ruler_conditions(hits, w) if w in sc.RULER_WIDTHS else sc.wide_conditions(hits, w)
+        assert all(cond.values()), (w, cond)
+        if w in sc.RULER_WIDTHS:
+            assert ("one_thread" in cond and "thread_straddle" in cond) == (w < 16)
+            want = sorted(sc.ruler_runs(w).values())  # the runs are where they were designed
+            assert [(h["first_cell"], h["first_cell"] + h["n_cells"] - 1) for h in hits] == want, w
+            long_run = max(hits, key=lambda h: h["n_cells"])
+            assert long_run["peak_cell"] == sc.ruler_boosted_cell(w)
+        f1, hits1, _ = sc.evaluate(p, sc.ruler_cfg(w, min_cells=sc.second_longest_plus_one(hits)))
+        assert f1["n_hits"] == 1 and hits1 == [max(hits, key=lambda h: h["n_cells"])] and f1["n_hot"] == f["n_hot"], w
+
+
+def test_ruler_over_two_frames_is_the_ruler_of_the_sum():
+    a, b = _crafted_psd("ruler2", 0), _crafted_psd("ruler2", 1)
+    c = sc.ruler_cfg(sc.RULER2_W, frames=2)
+    f, hits, cell = sc.evaluate(a + b, c)
+    assert all(sc.ruler_conditions(hits, sc.RULER2_W).values())
+    spans = [(h["first_cell"], h["n_cells"]) for h in hits]
+    for alone in (a, b):  # neither frame alone has these runs
+        assert [(h["first_cell"], h["n_cells"]) for h in sc.evaluate(alone, c)[1]] != spans
+    it = sc.Integrator(c)
+    assert it.step(a, 0)["complete"] == 0 and it.step(b, 1)["complete"] == 1 and it.hits == hits
+
+
+def test_spread_comb_fills_the_list_from_every_wave():
+    f, hits, cell = sc.evaluate(_crafted_psd("spread"), sc.SPREAD_CFG)
+    hot = cell > f["thr"]
+    assert cell[~hot].max() < 0.1 * f["thr"] and cell[hot].min() > 2.0 * f["thr"]
+    assert f["n_hits"] == f["n_stored"] == N // sc.SPREAD_L == 256 and f["n_hot"] == 3 * 256
+    assert np.bincount([h["first_cell"] // 1024 for h in hits], minlength=8).tolist() == [32] * 8  # every wave writes its 32
+    assert all(h["n_cells"] == 3 and h["peak_cell"] == h["first_cell"] + 1 and h["peak_cell"] % 16 == 0 for h in hits)  # each straddles two threads
+
+
+def test_exactly_512_and_513_hits():
+    p = _crafted_psd("edge")
+    f512, hits512, _ = sc.evaluate(p, sc.EDGE_512)
+    f513, hits513, _ = sc.evaluate(p, sc.EDGE_513)
+    assert (f512["n_hits"], f512["n_stored"]) == (512, 512) and (f513["n_hits"], f513["n_stored"]) == (513, 512)
+    few, hits_few, _ = sc.evaluate(p, sc.EDGE_FEW)
+    assert 0 < few["n_hits"] < 100
+    assert hits513[511]["first_cell"] < hits513[512]["first_cell"] and hits_few[0] != hits513[0]
