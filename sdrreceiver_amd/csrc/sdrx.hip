@@ -150,36 +150,14 @@ void free_device_state(sdrx_ctx *c)
     dfree(c->agc.d_quiet);
     dfree(c->agc.d_jobs);
     c->agc = sdrx_ctx::Agc();
-    // channel watch: as before the first sdrx_set_watch
+    // channel watch, drift estimate and band scan: as before the first sdrx_set_watch / sdrx_set_drift / sdrx_set_scan
     dfree(c->watch.d_desc);
     dfree(c->watch.d_data);
     dfree(c->watch.d_tw);
-    for (int p = 0; p < 2; ++p) {
-        dfree(c->watch.d_rec[p]);
-        if (c->watch.h_rec[p])
-            (void)hipHostFree(c->watch.h_rec[p]);
-    }
+    records_free(c->watch.rec);
     c->watch = sdrx_ctx::Watch();
-    // drift estimate: as before the first sdrx_set_drift
-    for (auto &s : c->drift.src)
-        dfree(s.d_state);
-    dfree(c->drift.d_desc);
-    for (int p = 0; p < 2; ++p) {
-        dfree(c->drift.d_rec[p]);
-        if (c->drift.h_rec[p])
-            (void)hipHostFree(c->drift.h_rec[p]);
-    }
-    c->drift = sdrx_ctx::Drift();
-    // band scan: as before the first sdrx_set_scan
-    for (auto &s : c->scan.src)
-        dfree(s.d_state);
-    dfree(c->scan.d_src);
-    for (int p = 0; p < 2; ++p) {
-        dfree(c->scan.d_rec[p]);
-        if (c->scan.h_rec[p])
-            (void)hipHostFree(c->scan.h_rec[p]);
-    }
-    c->scan = sdrx_ctx::Scan();
+    analysis_release(c->drift);
+    analysis_release(c->scan);
 }
 
 } // namespace

@@ -205,87 +205,84 @@ struct sdrx_ctx {
         static int slot(int kind) { return kind == KIND_LATE_DEC ? 0 : kind == KIND_DEMOD ? 1 : kind == KIND_LPF_LONG ? 2 : 3; }
     } cu;
 
-    // Option watch (sdrx_set_watch, watch.hip).  Host bookkeeping per leaf as option park keeps it: a frame
-    // f >= since ran with the leaf in state `on`, the frames before it in state `was_on`.  Everything on the device is allocated
-    // by the first sdrx_set_watch that switches a leaf on; with no source measured the frame sequence launches nothing more.
-    // The records of frame f are written to d_rec[f & 1] -- one slot per leaf -- and travel to h_rec[f & 1] with the frame's
-    // fixed-size part (queue_watch, sdrx_delivery.hip).
+    // A setting that changes between frames, as the host keeps it for what has not been delivered yet: a frame f >= since ran
+    // with `v`, the frames before it (the last one may not be fetched yet) with `was`.  Only switch_to (sdrx_watch.hip) writes one.
+    struct Switched {
+        int v = 0, was = 0;
+        unsigned long long since = 0;
+        int at(unsigned long long frame) const { return frame >= since ? v : was; }
+    };
+    // Records of frame f: written to d[f & 1] on the device, they travel to h[f & 1] (pinned) with the frame's fixed-size part
+    // (queue_watch, sdrx_delivery.hip).  records_alloc / records_free, sdrx_watch.hip.
+    struct Records {
+        void *d[2] = {nullptr, nullptr}, *h[2] = {nullptr, nullptr};
+        size_t bytes = 0; // of one buffer; 0: not allocated
+        template <class R>
+        R *dev(int p) const { return static_cast<R *>(d[p]); }
+        template <class R>
+        const R *host(int p) const { return static_cast<const R *>(h[p]); }
+    };
+
+    // Option watch (sdrx_set_watch, watch.hip).  Host bookkeeping per leaf: whether it is watched (`on`, a Switched).
+    // Everything on the device is allocated by the first sdrx_set_watch that switches a leaf on; with no source measured the frame
+    // sequence launches nothing more.  The records of frame f -- one slot per leaf -- are `rec`.
+    // A SOURCE is what a watched leaf's band is read from: index 0 the raw frame, 1 + id the stream of node id.  Every non-leaf
+    // has a slot (src_slot, in node order) for the records of the analyses below.
     struct Watch {
         struct Leaf {
-            int on = 0, was_on = 0;
-            unsigned long long since = 0;
+            Switched on;
             int first_bin = 0, n_bins = 1; // the band (watch_band), as the descriptor stands
             int slot = -1;                 // its record (leaves in node order; -1: not a leaf)
         };
-        std::vector<Leaf> leaf; // per node; sized by the first watch call
+        std::vector<Leaf> leaf; // per node; sized by the first watch call (watch_host_init), as src_slot is
         int n_slots = 0;
-        unsigned char *d_desc = nullptr; // WatchSrc[src_cap] | WatchSeg[kWatchMaxSeg src_cap] | WatchLeaf[n_slots]
-        int src_cap = 0;
+        std::vector<int> src_slot; // per source index: its slot (-1: a leaf's stream feeds nobody)
+        int n_src_slots = 0;
+        unsigned char *d_desc = nullptr; // WatchSrc[n_src_slots] | WatchSeg[kWatchMaxSeg n_src_slots] | WatchLeaf[n_slots]
         unsigned char *d_data = nullptr; // per measured source: P[S][kSpecN] f32 | PSD[kSpecN] + total f64 | done u32
         size_t data_cap = 0;
         float2 *d_tw = nullptr;          // kiss_fft's twiddles, then the Hann window (as Spectrum::d_tw)
-        WatchRecord *d_rec[2] = {nullptr, nullptr}, *h_rec[2] = {nullptr, nullptr};
+        Records rec;                     // WatchRecord[n_slots]
         size_t bytes = 0;                // device memory the option holds
         std::vector<int> src_ids;        // the measured sources in launch order: -1 the raw frame, else the parent's node id
         std::vector<size_t> src_psd;     // ... where each one's PSD lies in d_data
         std::vector<int> seg_begin, leaf_begin; // per source group (0: the raw frame, 1 + l: parents on tree level l), n_levels + 2 entries
         unsigned long long psd_since = 0; // the PSD buffers hold a frame only once frame_no > psd_since
         WatchSrc *d_src() const { return reinterpret_cast<WatchSrc *>(d_desc); }
-        WatchSeg *d_seg() const { return reinterpret_cast<WatchSeg *>(d_desc + sizeof(WatchSrc) * (size_t)src_cap); }
-        WatchLeaf *d_leaf() const { return reinterpret_cast<WatchLeaf *>(d_desc + (sizeof(WatchSrc) + sizeof(WatchSeg) * kWatchMaxSeg) * (size_t)src_cap); }
-        bool watched_at(int id, unsigned long long frame) const
-        {
-            if (leaf.empty())
-                return false;
-            const Leaf &L = leaf[(size_t)id];
-            return (frame >= L.since ? L.on : L.was_on) != 0;
-        }
+        WatchSeg *d_seg() const { return reinterpret_cast<WatchSeg *>(d_desc + sizeof(WatchSrc) * (size_t)n_src_slots); }
+        WatchLeaf *d_leaf() const { return reinterpret_cast<WatchLeaf *>(d_desc + (sizeof(WatchSrc) + sizeof(WatchSeg) * kWatchMaxSeg) * (size_t)n_src_slots); }
+        bool watched_at(int id, unsigned long long frame) const { return !leaf.empty() && leaf[(size_t)id].on.at(frame) != 0; }
     } watch;
 
-    // Drift estimate (sdrx_set_drift, drift.hip), part of option watch.  A source -- index 0: the raw frame,
-    // 1 + id: the stream of node id -- keeps its template, its last profile and two words of launch state in one device
-    // allocation of its own from its first sdrx_set_drift on: nothing the watch moves or clears touches it.  Host bookkeeping
-    // as the watch keeps it: a frame f >= since ran with max_shift K, the frames before it with was_K.  The record of frame f
-    // goes to d_rec[f & 1] -- one slot per possible source -- and travels with the watch records (queue_watch).  Everything is
-    // allocated by the first sdrx_set_drift that switches a source on.
-    struct Drift {
+    // An analysis of the watched PSD per source, part of option watch: one more kernel behind k_watch_bands on the sources that
+    // have it switched on.  A source keeps what the analysis carries from frame to frame in one device allocation of its own
+    // (d_state, state_bytes) from the first call that switches it on: nothing the watch moves or clears touches it.  The launch
+    // list in d_desc names the sources that have it among the measured ones, rebuilt with the watch's own (walk_sources); the
+    // record of frame f -- one slot per possible source, Watch::src_slot -- is in `rec`.  Everything is allocated by the first
+    // call that switches a source on (analysis_alloc), and released by analysis_release: sdrx_watch.hip has the shared steps.
+    struct SourceAnalysis {
         struct Src {
-            int K = 0, was_K = 0;
-            unsigned long long since = 0;
-            unsigned long long set_at = 0; // frame_no of the last sdrx_set_drift: the profile is this setting's once frame_no > set_at
-            DriftState *d_state = nullptr;
-            int slot = -1; // its record (-1: a leaf's stream feeds nobody)
+            Switched on; // the value that switches it (0: off)
+            void *d_state = nullptr;
         };
-        std::vector<Src> src; // sized by the first drift call
-        int n_slots = 0;
-        unsigned char *d_desc = nullptr; // DriftSrc[n_slots] | DriftBlk[kDriftMaxBlocks n_slots]
-        DriftRecord *d_rec[2] = {nullptr, nullptr}, *h_rec[2] = {nullptr, nullptr};
-        size_t bytes = 0;           // device memory it holds
-        std::vector<int> blk_begin; // per source group (as Watch::seg_begin), n_levels + 2 entries; empty: never switched on
+        std::vector<Src> src; // per source index; sized by the first call
+        unsigned char *d_desc = nullptr;
+        Records rec;
+        size_t bytes = 0;       // device memory it holds
+        std::vector<int> begin; // first launch entry per source group (as Watch::seg_begin), n_levels + 2 entries; empty: never switched on
+    };
+    // Drift estimate (sdrx_set_drift, drift.hip): switched by max_shift K.  d_state: a DriftState (template, last
+    // profile, two words of launch state); d_desc: DriftSrc[n_src_slots] | DriftBlk[kDriftMaxBlocks n_src_slots]; rec: DriftRecord.
+    struct Drift : SourceAnalysis {
+        std::vector<unsigned long long> set_at; // per source index: frame_no of the last sdrx_set_drift -- the profile is this setting's once frame_no > set_at
         DriftSrc *d_src() const { return reinterpret_cast<DriftSrc *>(d_desc); }
-        DriftBlk *d_blk() const { return reinterpret_cast<DriftBlk *>(d_desc + sizeof(DriftSrc) * (size_t)n_slots); }
+        DriftBlk *d_blk(int n_src_slots) const { return reinterpret_cast<DriftBlk *>(d_desc + sizeof(DriftSrc) * (size_t)n_src_slots); }
     } drift;
-
-    // Band scan (sdrx_set_scan, scan.hip), part of option watch.  A source -- indexed as Drift's -- keeps its
-    // integrated spectrum, its count and the cells, hits and record of its last completed evaluation in one device allocation
-    // of its own from its first sdrx_set_scan on.  Host bookkeeping as the drift keeps it: a frame f >= since ran with cell
-    // width cfg.cell_bins, the frames before it with was_w.  The record of frame f goes to d_rec[f & 1] -- one slot per possible
-    // source -- and travels with the watch records (queue_watch).  Everything is allocated by the first sdrx_set_scan that
-    // switches a source on.
-    struct Scan {
-        struct Src {
-            ScanCfg cfg = {};  // cell_bins 0: off
-            int was_w = 0;
-            unsigned long long since = 0;
-            ScanState *d_state = nullptr;
-            int slot = -1;
-        };
-        std::vector<Src> src; // sized by the first scan call
-        int n_slots = 0;
-        ScanSrc *d_src = nullptr; // ScanSrc[n_slots]
-        ScanRecord *d_rec[2] = {nullptr, nullptr}, *h_rec[2] = {nullptr, nullptr};
-        size_t bytes = 0;           // device memory it holds
-        std::vector<int> src_begin; // per source group (as Watch::seg_begin), n_levels + 2 entries; empty: never switched on
+    // Band scan (sdrx_set_scan, scan.hip): switched by the cell width cell_bins.  d_state: a ScanState (integrated
+    // spectrum, count, and the cells, hits and record of the last completed evaluation); d_desc: ScanSrc[n_src_slots]; rec: ScanRecord.
+    struct Scan : SourceAnalysis {
+        std::vector<ScanCfg> cfg; // per source index: the setting that last switched it on
+        ScanSrc *d_src() const { return reinterpret_cast<ScanSrc *>(d_desc); }
     } scan;
 
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot

@@ -77,15 +77,13 @@ void publish_all(sdrx_ctx *c, int slot)
 //      d_pack[p] goes to h_pay[p] + hpack_off, in ONE copy (none if every leaf is closed); without squelch the whole of d_pay[p].
 // Both only read d_pay[p], d_pack[p] and the directory, whose next writer is frame f+2 (the safety argument above
 // enqueue_frame, sdrx_frame.hip).
-// Option watch: the records of the frame of parity p, part of what always travels (nothing before the first sdrx_set_watch)
+// Option watch: the records of the frame of parity p, part of what always travels -- the watch's, then the drift's and the band
+// scan's of its sources (each: nothing before the first call that switched one on)
 int queue_watch(sdrx_ctx *c, int p, hipStream_t st)
 {
-    if (c->watch.d_rec[p])
-        HIPCHK(c, hipMemcpyAsync(c->watch.h_rec[p], c->watch.d_rec[p], sizeof(WatchRecord) * (size_t)c->watch.n_slots, hipMemcpyDeviceToHost, st));
-    if (c->drift.d_rec[p]) // ... and the drift records of its sources (nothing before the first sdrx_set_drift)
-        HIPCHK(c, hipMemcpyAsync(c->drift.h_rec[p], c->drift.d_rec[p], sizeof(DriftRecord) * (size_t)c->drift.n_slots, hipMemcpyDeviceToHost, st));
-    if (c->scan.d_rec[p]) // ... and their band-scan records (nothing before the first sdrx_set_scan)
-        HIPCHK(c, hipMemcpyAsync(c->scan.h_rec[p], c->scan.d_rec[p], sizeof(ScanRecord) * (size_t)c->scan.n_slots, hipMemcpyDeviceToHost, st));
+    for (const sdrx_ctx::Records *r : {&c->watch.rec, &c->drift.rec, &c->scan.rec})
+        if (r->d[p])
+            HIPCHK(c, hipMemcpyAsync(r->h[p], r->d[p], r->bytes, hipMemcpyDeviceToHost, st));
     return SDRX_OK;
 }
 int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st)

@@ -153,24 +153,25 @@ void watch_launch_groups(sdrx_ctx *c, hipStream_t st, int g_lo, int g_hi, const 
     const float *hann = reinterpret_cast<const float *>(W.d_tw + kSpecN);
     hipLaunchKernelGGL(k_watch_psd, dim3(s1 - s0), dim3(kSpecThreads), 0, st, W.d_src(), W.d_seg() + s0, A, W.d_tw, hann);
     const int per = kWatchLeafThreads / 64;
-    hipLaunchKernelGGL(k_watch_bands, dim3((l1 - l0 + per - 1) / per), dim3(kWatchLeafThreads), 0, st, W.d_src(), W.d_leaf() + l0, l1 - l0, A, W.d_rec[0],
-                       W.d_rec[1]);
+    hipLaunchKernelGGL(k_watch_bands, dim3((l1 - l0 + per - 1) / per), dim3(kWatchLeafThreads), 0, st, W.d_src(), W.d_leaf() + l0, l1 - l0, A,
+                       W.rec.dev<WatchRecord>(0), W.rec.dev<WatchRecord>(1));
     // drift estimate: one k_watch_drift workgroup per (source of those groups with a template, block of shifts), on the PSD
     // k_watch_psd has just left.  Nothing before the first sdrx_set_drift; not bracketed either.
     const sdrx_ctx::Drift &D = c->drift;
-    if (!D.blk_begin.empty()) {
-        const int b0 = D.blk_begin[(size_t)g_lo], b1 = D.blk_begin[(size_t)g_hi + 1];
+    if (!D.begin.empty()) {
+        const int b0 = D.begin[(size_t)g_lo], b1 = D.begin[(size_t)g_hi + 1];
         if (b1 > b0)
-            hipLaunchKernelGGL(k_watch_drift, dim3(b1 - b0), dim3(kSpecThreads), 0, st, D.d_src(), D.d_blk() + b0, A, D.d_rec[0], D.d_rec[1]);
+            hipLaunchKernelGGL(k_watch_drift, dim3(b1 - b0), dim3(kSpecThreads), 0, st, D.d_src(), D.d_blk(W.n_src_slots) + b0, A, D.rec.dev<DriftRecord>(0),
+                               D.rec.dev<DriftRecord>(1));
     }
     // band scan: one k_watch_scan workgroup per source of those groups with the scan on, on the same PSD.  Nothing before the
     // first sdrx_set_scan; not bracketed either.
     const sdrx_ctx::Scan &S = c->scan;
-    if (S.src_begin.empty())
+    if (S.begin.empty())
         return;
-    const int c0 = S.src_begin[(size_t)g_lo], c1 = S.src_begin[(size_t)g_hi + 1];
+    const int c0 = S.begin[(size_t)g_lo], c1 = S.begin[(size_t)g_hi + 1];
     if (c1 > c0)
-        hipLaunchKernelGGL(k_watch_scan, dim3(c1 - c0), dim3(kSpecThreads), 0, st, S.d_src + c0, A, S.d_rec[0], S.d_rec[1]);
+        hipLaunchKernelGGL(k_watch_scan, dim3(c1 - c0), dim3(kSpecThreads), 0, st, S.d_src() + c0, A, S.rec.dev<ScanRecord>(0), S.rec.dev<ScanRecord>(1));
 }
 // ... of the VFO streams of tree levels lo..hi, where spectrum_launch reads them (the same frames per level)
 void watch_launch(sdrx_ctx *c, hipStream_t st, int lo, int hi, unsigned long long f, const unsigned long long *frames)

@@ -579,6 +579,19 @@ int owner(sdrx_group *g, const char *what, int id, std::pair<int, int> *w)
     *w = g->where[(size_t)id];
     return SDRX_OK;
 }
+// ... and the call itself: `call(the member's context, its id there)` on that member.  `between_frames`: a call that changes what
+// the next frame does or reads the member's device -- the group has no frame in flight, looked at behind `owner` and in front of
+// everything the member checks (the member would say so too, but of ITS frames).  g->broken is not looked at.
+template <class Call>
+int on_owner(sdrx_group *g, const char *what, int id, bool between_frames, Call call)
+{
+    std::pair<int, int> w;
+    if (int rc = owner(g, what, id, &w))
+        return rc;
+    if (between_frames && g->in_flight > 0)
+        return gfail(g, SDRX_ESTATE, "%s: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", what, g->in_flight);
+    return member_rc(g, w.first, call(g->m[(size_t)w.first].c, w.second));
+}
 
 // Gather: out[k] is what the owner of ids[k] says in the context's call `get`.  The whole list is checked first -- nothing is
 // written for a bad one; the option, that an id names a leaf and the delivered frame are the answering member's to check.
@@ -670,9 +683,7 @@ int sdrx_group_get_output(sdrx_group *g, int id, const void **buf, uint32_t *len
         return gfail(g, SDRX_EINVAL, "bad vfo id %d", id);
     // (with frames in flight this keeps serving the last DELIVERED frame, like sdrx_get_output: its payloads sit in
     // the host slot the frame in flight does not write; before the first delivery the member says SDRX_ESTATE)
-    std::pair<int, int> w;
-    const int rc = owner(g, "sdrx_group_get_output", id, &w);
-    return rc ? rc : member_rc(g, w.first, sdrx_get_output(g->m[(size_t)w.first].c, w.second, buf, len_bytes, rate));
+    return on_owner(g, "sdrx_group_get_output", id, false, [&](sdrx_ctx *m, int local) { return sdrx_get_output(m, local, buf, len_bytes, rate); });
 }
 
 int sdrx_group_get_meters(sdrx_group *g, const int *ids, int n, sdrx_meter *out)
@@ -749,80 +760,44 @@ int sdrx_group_get_watch(sdrx_group *g, const int *ids, int n, sdrx_watch_level 
 
 int sdrx_group_get_watch_psd(sdrx_group *g, int leaf_id, double *psd, int64_t *frame)
 {
-    std::pair<int, int> w;
-    if (int rc = owner(g, "sdrx_group_get_watch_psd", leaf_id, &w))
-        return rc;
-    if (g->in_flight > 0) // (the member reads its device: it would say so too, but of ITS frames)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_get_watch_psd: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
-    return member_rc(g, w.first, sdrx_get_watch_psd(g->m[(size_t)w.first].c, w.second, psd, frame));
+    return on_owner(g, "sdrx_group_get_watch_psd", leaf_id, true, [&](sdrx_ctx *m, int id) { return sdrx_get_watch_psd(m, id, psd, frame); });
 }
 
 // The drift estimate of the source of leaf `leaf_id`, on the member that holds the leaf (its own copy of the source)
 int sdrx_group_set_drift(sdrx_group *g, int leaf_id, const double *templ, int max_shift)
 {
-    std::pair<int, int> w;
-    if (int rc = owner(g, "sdrx_group_set_drift", leaf_id, &w))
-        return rc;
-    if (g->in_flight > 0)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_drift: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
-    return member_rc(g, w.first, sdrx_set_drift(g->m[(size_t)w.first].c, w.second, templ, max_shift));
+    return on_owner(g, "sdrx_group_set_drift", leaf_id, true, [&](sdrx_ctx *m, int id) { return sdrx_set_drift(m, id, templ, max_shift); });
 }
 
 int sdrx_group_get_drift(sdrx_group *g, int leaf_id, sdrx_drift_level *out)
 {
-    std::pair<int, int> w;
-    if (int rc = owner(g, "sdrx_group_get_drift", leaf_id, &w))
-        return rc;
-    return member_rc(g, w.first, sdrx_get_drift(g->m[(size_t)w.first].c, w.second, out));
+    return on_owner(g, "sdrx_group_get_drift", leaf_id, false, [&](sdrx_ctx *m, int id) { return sdrx_get_drift(m, id, out); });
 }
 
 int sdrx_group_get_drift_profile(sdrx_group *g, int leaf_id, double *profile, int64_t *frame)
 {
-    std::pair<int, int> w;
-    if (int rc = owner(g, "sdrx_group_get_drift_profile", leaf_id, &w))
-        return rc;
-    if (g->in_flight > 0)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_get_drift_profile: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
-    return member_rc(g, w.first, sdrx_get_drift_profile(g->m[(size_t)w.first].c, w.second, profile, frame));
+    return on_owner(g, "sdrx_group_get_drift_profile", leaf_id, true, [&](sdrx_ctx *m, int id) { return sdrx_get_drift_profile(m, id, profile, frame); });
 }
 
 // The band scan of the source of leaf `leaf_id`, on the member that holds the leaf (its own copy of the source)
 int sdrx_group_set_scan(sdrx_group *g, int leaf_id, const sdrx_scan_cfg *cfg)
 {
-    std::pair<int, int> w;
-    if (int rc = owner(g, "sdrx_group_set_scan", leaf_id, &w))
-        return rc;
-    if (g->in_flight > 0)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_set_scan: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
-    return member_rc(g, w.first, sdrx_set_scan(g->m[(size_t)w.first].c, w.second, cfg));
+    return on_owner(g, "sdrx_group_set_scan", leaf_id, true, [&](sdrx_ctx *m, int id) { return sdrx_set_scan(m, id, cfg); });
 }
 
 int sdrx_group_get_scan(sdrx_group *g, int leaf_id, sdrx_scan_level *out)
 {
-    std::pair<int, int> w;
-    if (int rc = owner(g, "sdrx_group_get_scan", leaf_id, &w))
-        return rc;
-    return member_rc(g, w.first, sdrx_get_scan(g->m[(size_t)w.first].c, w.second, out));
+    return on_owner(g, "sdrx_group_get_scan", leaf_id, false, [&](sdrx_ctx *m, int id) { return sdrx_get_scan(m, id, out); });
 }
 
 int sdrx_group_get_scan_hits(sdrx_group *g, int leaf_id, sdrx_scan_hit *hits, int max_hits, int *n, int64_t *frame)
 {
-    std::pair<int, int> w;
-    if (int rc = owner(g, "sdrx_group_get_scan_hits", leaf_id, &w))
-        return rc;
-    if (g->in_flight > 0)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_get_scan_hits: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
-    return member_rc(g, w.first, sdrx_get_scan_hits(g->m[(size_t)w.first].c, w.second, hits, max_hits, n, frame));
+    return on_owner(g, "sdrx_group_get_scan_hits", leaf_id, true, [&](sdrx_ctx *m, int id) { return sdrx_get_scan_hits(m, id, hits, max_hits, n, frame); });
 }
 
 int sdrx_group_get_scan_cells(sdrx_group *g, int leaf_id, double *cells, int64_t *frame)
 {
-    std::pair<int, int> w;
-    if (int rc = owner(g, "sdrx_group_get_scan_cells", leaf_id, &w))
-        return rc;
-    if (g->in_flight > 0)
-        return gfail(g, SDRX_ESTATE, "sdrx_group_get_scan_cells: %d submitted frame(s) not yet delivered -- call sdrx_group_wait first", g->in_flight);
-    return member_rc(g, w.first, sdrx_get_scan_cells(g->m[(size_t)w.first].c, w.second, cells, frame));
+    return on_owner(g, "sdrx_group_get_scan_cells", leaf_id, true, [&](sdrx_ctx *m, int id) { return sdrx_get_scan_cells(m, id, cells, frame); });
 }
 
 int sdrx_group_get_egress(sdrx_group *g, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied)
@@ -859,9 +834,7 @@ int sdrx_group_get_egress(sdrx_group *g, int64_t *frame, uint32_t *n_open, uint3
 
 int sdrx_group_get_preroll(sdrx_group *g, int id, const void **buf, uint32_t *len, int64_t *frame)
 {
-    std::pair<int, int> w;
-    const int rc = owner(g, "sdrx_group_get_preroll", id, &w);
-    return rc ? rc : member_rc(g, w.first, sdrx_get_preroll(g->m[(size_t)w.first].c, w.second, buf, len, frame));
+    return on_owner(g, "sdrx_group_get_preroll", id, false, [&](sdrx_ctx *m, int local) { return sdrx_get_preroll(m, local, buf, len, frame); });
 }
 
 int sdrx_group_get_preroll_count(sdrx_group *g, uint32_t *n_preroll, uint64_t *preroll_bytes)

@@ -1,5 +1,6 @@
-// sdrx_watch.hip -- host side of option "watch" (include/sdrx.h "Channel watch", watch.hip): a leaf's band, the
-// launch lists of the measured sources, and the ABI calls.  The launches themselves sit in the frame sequence
+// sdrx_watch.hip -- host side of option "watch" (include/sdrx.h "Channel watch", watch.hip) and of the analyses on
+// a watched source's spectrum (drift estimate, 4n; band scan, 4o): a leaf's band, the launch lists of the measured sources, what
+// an analysis per source keeps (sdrx_ctx::SourceAnalysis), and the ABI calls.  The launches themselves sit in the frame sequence
 // (watch_launch / watch_raw_step, sdrx_frame.hip), the records' way to the host in sdrx_delivery.hip (queue_watch).
 // A fragment of sdrx.hip's translation unit.
 
@@ -28,17 +29,23 @@ void watch_band(const sdrx_vfo_desc &d, int *first_bin, int *n_bins)
     *first_bin = (int)(((k_lo % kSpecN) + kSpecN) % kSpecN);
 }
 
-// host bookkeeping of every leaf (no device memory): by the first watch call of a finalized context
+// host bookkeeping of every leaf and the slot of every possible source (no device memory): by the first watch call of a
+// finalized context
 void watch_host_init(sdrx_ctx *c)
 {
     sdrx_ctx::Watch &W = c->watch;
     if (!W.leaf.empty())
         return;
     W.leaf.assign(c->nodes.size(), sdrx_ctx::Watch::Leaf());
+    W.src_slot.assign(c->nodes.size() + 1, -1);
     W.n_slots = 0;
+    W.n_src_slots = 0;
+    W.src_slot[0] = W.n_src_slots++;
     for (size_t id = 0; id < c->nodes.size(); ++id) {
-        if (!c->nodes[id].leaf)
+        if (!c->nodes[id].leaf) {
+            W.src_slot[1 + id] = W.n_src_slots++;
             continue;
+        }
         W.leaf[id].slot = W.n_slots++;
         watch_band(c->nodes[id].d, &W.leaf[id].first_bin, &W.leaf[id].n_bins);
     }
@@ -48,23 +55,139 @@ void watch_host_init(sdrx_ctx *c)
 
 int watch_segments(int n) { return std::min(std::max(n / kSpecN, 1), kWatchMaxSeg); }
 
-// ---- drift estimate: host bookkeeping of every possible source (no device memory), by the first drift call
-void drift_host_init(sdrx_ctx *c)
+// A source is launched with its group: 0 the raw frame (id -1), 1 + l the streams of tree level l.  The frame a kernel finds
+// in a stream is its level's (only the frame pipeline, at most kMaxLevels deep, has frames per level); -1: the raw frame's.
+size_t source_of(const sdrx_ctx *c, int leaf_id) { return (size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id); }
+int source_group(const sdrx_ctx *c, int id) { return id < 0 ? 0 : c->nodes[(size_t)id].level + 1; }
+int source_level(int g) { return g == 0 ? -1 : std::min(g - 1, kMaxLevels - 1); }
+
+// The setting S becomes `to` before frame `now`; false: it is `to` already.  (A second change before the same frame: the frames
+// before it ran in the state they ran in.)
+bool switch_to(sdrx_ctx::Switched &S, int to, unsigned long long now)
 {
-    sdrx_ctx::Drift &D = c->drift;
-    if (!D.src.empty())
-        return;
-    D.src.assign(c->nodes.size() + 1, sdrx_ctx::Drift::Src());
-    D.n_slots = 0;
-    D.src[0].slot = D.n_slots++;
-    for (size_t id = 0; id < c->nodes.size(); ++id)
-        if (!c->nodes[id].leaf)
-            D.src[1 + id].slot = D.n_slots++;
+    if (S.v == to)
+        return false;
+    if (S.since != now)
+        S.was = S.v;
+    S.v = to;
+    S.since = now;
+    return true;
 }
 
-// The drift launch list for the measured sources `ids` (watch_rebuild's launch order: by source group) whose PSDs lie at
-// `off_psd` in the watch's data: the sources among them with max_shift > 0, one entry per block of shifts.  Synchronous, as
-// watch_rebuild is.  Nothing before the first sdrx_set_drift that switched a source on.
+// ---- what the watch, the drift estimate and the band scan share: records per frame parity, and an analysis per source
+int records_alloc(sdrx_ctx *c, sdrx_ctx::Records &r, size_t bytes)
+{
+    for (int p = 0; p < 2; ++p) {
+        HIPCHK(c, hipMalloc(&r.d[p], bytes));
+        HIPCHK(c, hipMemset(r.d[p], 0, bytes));
+        HIPCHK(c, hipHostMalloc(&r.h[p], bytes, hipHostMallocDefault));
+        memset(r.h[p], 0, bytes);
+    }
+    r.bytes = bytes;
+    return SDRX_OK;
+}
+void records_free(sdrx_ctx::Records &r)
+{
+    for (int p = 0; p < 2; ++p) {
+        if (r.d[p])
+            (void)hipFree(r.d[p]);
+        if (r.h[p])
+            (void)hipHostFree(r.h[p]);
+    }
+    r = sdrx_ctx::Records();
+}
+
+// the analysis's bookkeeping of the source of `leaf_id` (host memory: sized by the first call, whatever it sets)
+sdrx_ctx::SourceAnalysis::Src &analysis_source(sdrx_ctx *c, sdrx_ctx::SourceAnalysis &A, int leaf_id)
+{
+    if (A.src.empty())
+        A.src.assign(c->nodes.size() + 1, sdrx_ctx::SourceAnalysis::Src());
+    return A.src[source_of(c, leaf_id)];
+}
+// first use on the device: the launch list (`desc_bytes` per possible source) and the records (`rec_bytes` per possible source)
+int analysis_alloc(sdrx_ctx *c, sdrx_ctx::SourceAnalysis &A, size_t desc_bytes, size_t rec_bytes)
+{
+    if (A.d_desc)
+        return SDRX_OK;
+    HIPCHK(c, hipMalloc(&A.d_desc, desc_bytes * (size_t)c->watch.n_src_slots));
+    if (int rc = records_alloc(c, A.rec, rec_bytes * (size_t)c->watch.n_src_slots))
+        return rc;
+    A.bytes += desc_bytes * (size_t)c->watch.n_src_slots + 2 * A.rec.bytes;
+    return SDRX_OK;
+}
+// a source's state, cleared, by the first call that switches the analysis on for it
+int analysis_state(sdrx_ctx *c, sdrx_ctx::SourceAnalysis &A, sdrx_ctx::SourceAnalysis::Src &S, size_t state_bytes)
+{
+    if (S.d_state)
+        return SDRX_OK;
+    HIPCHK(c, hipMalloc(&S.d_state, state_bytes));
+    HIPCHK(c, hipMemset(S.d_state, 0, state_bytes));
+    A.bytes += state_bytes;
+    return SDRX_OK;
+}
+// as before the first call
+template <class Analysis>
+void analysis_release(Analysis &A)
+{
+    for (auto &s : A.src)
+        if (s.d_state)
+            (void)hipFree(s.d_state);
+    if (A.d_desc)
+        (void)hipFree(A.d_desc);
+    records_free(A.rec);
+    A = Analysis();
+}
+bool analysis_on(const sdrx_ctx::SourceAnalysis &A, size_t src) { return !A.src.empty() && A.src[src].on.v != 0; }
+
+// was the source of `leaf_id` measured by the analysis in frame `frame`: switched on then, and a leaf of it watched
+bool analysis_measured_at(const sdrx_ctx *c, const sdrx_ctx::SourceAnalysis &A, int leaf_id, unsigned long long frame)
+{
+    if (A.src.empty() || A.src[source_of(c, leaf_id)].on.at(frame) == 0)
+        return false;
+    const int parent = c->nodes[(size_t)leaf_id].d.parent_id;
+    for (size_t id = 0; id < c->nodes.size(); ++id)
+        if (c->nodes[id].leaf && c->nodes[id].d.parent_id == parent && c->watch.watched_at((int)id, frame))
+            return true;
+    return false;
+}
+
+// The record of the source of `leaf_id` for the delivered frame (sdrx_get_drift, sdrx_get_scan): zeros but for the frame where
+// the source was not measured.  Out is the ABI's name for the device's record (the static_asserts of sdrx.hip).
+template <class Out>
+int analysis_record(sdrx_ctx *c, const char *what, const sdrx_ctx::SourceAnalysis *which, int leaf_id, Out *out)
+{
+    if (int rc = leaf_call(c, what, &sdrx_ctx::opt_watch, "watch", &leaf_id, out != nullptr, 1, kDelivered))
+        return rc;
+    const sdrx_ctx::SourceAnalysis &A = *which; // (of `c`: null with a null handle, which leaf_call has refused)
+    Out r;
+    memset(&r, 0, sizeof r);
+    r.frame = (int64_t)c->host_frame;
+    if (A.rec.h[c->host_slot] && analysis_measured_at(c, A, leaf_id, c->host_frame))
+        memcpy(&r, A.rec.host<Out>(c->host_slot) + c->watch.src_slot[source_of(c, leaf_id)], sizeof r);
+    *out = r;
+    return SDRX_OK;
+}
+
+// The one walk over the measured sources `ids` (watch_rebuild's launch order: by source group) whose PSDs lie at `off_psd` in
+// the watch's data: add(source index, level, psd) says how many launch entries the source adds to an analysis's list.  Returns
+// the first entry of every source group.
+std::vector<int> walk_sources(const sdrx_ctx *c, const std::vector<int> &ids, const std::vector<size_t> &off_psd,
+                              const std::function<int(size_t, int, const double *)> &add)
+{
+    std::vector<int> begin((size_t)c->n_levels + 2, 0);
+    int n = 0;
+    size_t k = 0;
+    for (int g = 0; g <= c->n_levels; ++g) {
+        begin[(size_t)g] = n;
+        for (; k < ids.size() && source_group(c, ids[k]) == g; ++k)
+            n += add((size_t)(1 + ids[k]), source_level(g), reinterpret_cast<const double *>(c->watch.d_data + off_psd[k]));
+    }
+    begin[(size_t)c->n_levels + 1] = n;
+    return begin;
+}
+
+// The drift launch list: the sources among the measured ones with max_shift > 0, one entry per block of shifts.  Synchronous,
+// as watch_rebuild is.  Nothing before the first sdrx_set_drift that switched a source on.
 int drift_rebuild(sdrx_ctx *c, const std::vector<int> &ids, const std::vector<size_t> &off_psd)
 {
     sdrx_ctx::Drift &D = c->drift;
@@ -72,111 +195,42 @@ int drift_rebuild(sdrx_ctx *c, const std::vector<int> &ids, const std::vector<si
         return SDRX_OK;
     std::vector<DriftSrc> srcs;
     std::vector<DriftBlk> blks;
-    std::vector<int> begin((size_t)c->n_levels + 2, 0);
-    size_t k = 0;
-    for (int g = 0; g <= c->n_levels; ++g) {
-        begin[(size_t)g] = (int)blks.size();
-        for (; k < ids.size() && (ids[k] < 0 ? 0 : c->nodes[(size_t)ids[k]].level + 1) == g; ++k) {
-            const sdrx_ctx::Drift::Src &S = D.src[(size_t)(1 + ids[k])];
-            if (S.K == 0)
-                continue;
-            DriftSrc e;
-            e.psd = reinterpret_cast<const double *>(c->watch.d_data + off_psd[k]);
-            e.state = S.d_state;
-            e.K = S.K;
-            e.n_blocks = (2 * S.K + 1 + kDriftBlock - 1) / kDriftBlock;
-            e.level = ids[k] < 0 ? -1 : std::min(g - 1, kMaxLevels - 1);
-            e.slot = S.slot;
-            for (int b = 0; b < e.n_blocks; ++b)
-                blks.push_back(DriftBlk{(int)srcs.size(), b});
-            srcs.push_back(e);
-        }
-    }
-    begin[(size_t)c->n_levels + 1] = (int)blks.size();
+    const std::vector<int> begin = walk_sources(c, ids, off_psd, [&](size_t i, int level, const double *psd) {
+        const int K = D.src[i].on.v;
+        if (K == 0)
+            return 0;
+        const int n_blocks = (2 * K + 1 + kDriftBlock - 1) / kDriftBlock;
+        for (int b = 0; b < n_blocks; ++b)
+            blks.push_back(DriftBlk{(int)srcs.size(), b});
+        srcs.push_back(DriftSrc{psd, static_cast<DriftState *>(D.src[i].d_state), K, n_blocks, level, c->watch.src_slot[i]});
+        return n_blocks;
+    });
     if (!srcs.empty()) {
         HIPCHK(c, hipMemcpy(D.d_src(), srcs.data(), sizeof(DriftSrc) * srcs.size(), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(D.d_blk(), blks.data(), sizeof(DriftBlk) * blks.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(D.d_blk(c->watch.n_src_slots), blks.data(), sizeof(DriftBlk) * blks.size(), hipMemcpyHostToDevice));
     }
-    D.blk_begin = begin;
+    D.begin = begin;
     return SDRX_OK;
 }
 
-// was the source of `leaf_id` measured for its drift in frame `frame`: max_shift > 0 then, and a leaf of it watched
-bool drift_measured_at(const sdrx_ctx *c, int leaf_id, unsigned long long frame)
-{
-    const sdrx_ctx::Drift &D = c->drift;
-    if (D.src.empty())
-        return false;
-    const int parent = c->nodes[(size_t)leaf_id].d.parent_id;
-    const sdrx_ctx::Drift::Src &S = D.src[(size_t)(1 + parent)];
-    if ((frame >= S.since ? S.K : S.was_K) == 0)
-        return false;
-    for (size_t id = 0; id < c->nodes.size(); ++id)
-        if (c->nodes[id].leaf && c->nodes[id].d.parent_id == parent && c->watch.watched_at((int)id, frame))
-            return true;
-    return false;
-}
-
-// ---- band scan: host bookkeeping of every possible source (no device memory), by the first scan call; the slots are the drift's
-void scan_host_init(sdrx_ctx *c)
-{
-    sdrx_ctx::Scan &S = c->scan;
-    if (!S.src.empty())
-        return;
-    S.src.assign(c->nodes.size() + 1, sdrx_ctx::Scan::Src());
-    S.n_slots = 0;
-    S.src[0].slot = S.n_slots++;
-    for (size_t id = 0; id < c->nodes.size(); ++id)
-        if (!c->nodes[id].leaf)
-            S.src[1 + id].slot = S.n_slots++;
-}
-
-// The scan launch list for the measured sources `ids` whose PSDs lie at `off_psd` (as drift_rebuild): the sources among them
-// with cell_bins > 0, one workgroup each.  Nothing before the first sdrx_set_scan that switched a source on.
+// The scan launch list: the sources among the measured ones with cell_bins > 0, one workgroup each.  Nothing before the first
+// sdrx_set_scan that switched a source on.
 int scan_rebuild(sdrx_ctx *c, const std::vector<int> &ids, const std::vector<size_t> &off_psd)
 {
     sdrx_ctx::Scan &S = c->scan;
-    if (!S.d_src)
+    if (!S.d_desc)
         return SDRX_OK;
     std::vector<ScanSrc> srcs;
-    std::vector<int> begin((size_t)c->n_levels + 2, 0);
-    size_t k = 0;
-    for (int g = 0; g <= c->n_levels; ++g) {
-        begin[(size_t)g] = (int)srcs.size();
-        for (; k < ids.size() && (ids[k] < 0 ? 0 : c->nodes[(size_t)ids[k]].level + 1) == g; ++k) {
-            const sdrx_ctx::Scan::Src &R = S.src[(size_t)(1 + ids[k])];
-            if (R.cfg.cell_bins == 0)
-                continue;
-            ScanSrc e;
-            e.psd = reinterpret_cast<const double *>(c->watch.d_data + off_psd[k]);
-            e.state = R.d_state;
-            e.cfg = R.cfg;
-            e.level = ids[k] < 0 ? -1 : std::min(g - 1, kMaxLevels - 1);
-            e.slot = R.slot;
-            srcs.push_back(e);
-        }
-    }
-    begin[(size_t)c->n_levels + 1] = (int)srcs.size();
+    const std::vector<int> begin = walk_sources(c, ids, off_psd, [&](size_t i, int level, const double *psd) {
+        if (S.src[i].on.v == 0)
+            return 0;
+        srcs.push_back(ScanSrc{psd, static_cast<ScanState *>(S.src[i].d_state), S.cfg[i], level, c->watch.src_slot[i]});
+        return 1;
+    });
     if (!srcs.empty())
-        HIPCHK(c, hipMemcpy(S.d_src, srcs.data(), sizeof(ScanSrc) * srcs.size(), hipMemcpyHostToDevice));
-    S.src_begin = begin;
+        HIPCHK(c, hipMemcpy(S.d_src(), srcs.data(), sizeof(ScanSrc) * srcs.size(), hipMemcpyHostToDevice));
+    S.begin = begin;
     return SDRX_OK;
-}
-
-// was the source of `leaf_id` scanned in frame `frame`: cell_bins > 0 then, and a leaf of it watched
-bool scan_measured_at(const sdrx_ctx *c, int leaf_id, unsigned long long frame)
-{
-    const sdrx_ctx::Scan &S = c->scan;
-    if (S.src.empty())
-        return false;
-    const int parent = c->nodes[(size_t)leaf_id].d.parent_id;
-    const sdrx_ctx::Scan::Src &R = S.src[(size_t)(1 + parent)];
-    if ((frame >= R.since ? R.cfg.cell_bins : R.was_w) == 0)
-        return false;
-    for (size_t id = 0; id < c->nodes.size(); ++id)
-        if (c->nodes[id].leaf && c->nodes[id].d.parent_id == parent && c->watch.watched_at((int)id, frame))
-            return true;
-    return false;
 }
 
 // what is wrong with a setting that switches a scan on (include/sdrx.h "Band scan", the table)
@@ -205,29 +259,21 @@ int watch_rebuild(sdrx_ctx *c)
     std::vector<char> measured((size_t)N + 1, 0); // [0]: the raw frame, [1 + id]: the stream of node id
     bool any = false;
     for (int id = 0; id < N; ++id)
-        if (W.leaf[(size_t)id].on) {
-            measured[(size_t)(1 + c->nodes[(size_t)id].d.parent_id)] = 1;
+        if (W.leaf[(size_t)id].on.v) {
+            measured[source_of(c, id)] = 1;
             any = true;
         }
     if (!any && !W.d_desc) // nothing was ever switched on: nothing is allocated
         return SDRX_OK;
     if (!W.d_desc) {
-        int parents = 0;
-        for (const Node &n : c->nodes)
-            parents += !n.leaf;
-        W.src_cap = parents + 1;
-        const size_t desc_bytes = (sizeof(WatchSrc) + sizeof(WatchSeg) * kWatchMaxSeg) * (size_t)W.src_cap + sizeof(WatchLeaf) * (size_t)W.n_slots;
+        const size_t desc_bytes = (sizeof(WatchSrc) + sizeof(WatchSeg) * kWatchMaxSeg) * (size_t)W.n_src_slots + sizeof(WatchLeaf) * (size_t)W.n_slots;
         const size_t rec_bytes = sizeof(WatchRecord) * (size_t)W.n_slots;
         const std::vector<float2> tab = spectrum_tables();
         HIPCHK(c, hipMalloc(&W.d_desc, desc_bytes));
         HIPCHK(c, hipMalloc(&W.d_tw, sizeof(float2) * tab.size()));
         HIPCHK(c, hipMemcpy(W.d_tw, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
-        for (int p = 0; p < 2; ++p) {
-            HIPCHK(c, hipMalloc(&W.d_rec[p], rec_bytes));
-            HIPCHK(c, hipMemset(W.d_rec[p], 0, rec_bytes));
-            HIPCHK(c, hipHostMalloc(&W.h_rec[p], rec_bytes, hipHostMallocDefault));
-            memset(W.h_rec[p], 0, rec_bytes);
-        }
+        if (int rc = records_alloc(c, W.rec, rec_bytes))
+            return rc;
         W.bytes = desc_bytes + sizeof(float2) * tab.size() + 2 * rec_bytes;
     }
     // the measured sources, by group, and where each one's buffers lie
@@ -245,13 +291,13 @@ int watch_rebuild(sdrx_ctx *c)
     for (int g = 0; g <= c->n_levels; ++g) {
         W.seg_begin[(size_t)g] = (int)segs.size();
         for (int id = -1; id < N; ++id) {
-            if (!measured[(size_t)(1 + id)] || (id < 0 ? g != 0 : c->nodes[(size_t)id].level != g - 1))
+            if (!measured[(size_t)(1 + id)] || source_group(c, id) != g)
                 continue;
             WatchSrc e;
             memset(&e, 0, sizeof e);
             e.n = id < 0 ? c->root_frame : c->nodes[(size_t)id].n_f;
             e.S = watch_segments(e.n);
-            e.level = id < 0 ? -1 : std::min(g - 1, kMaxLevels - 1); // (only the frame pipeline, at most kMaxLevels deep, has frames per level)
+            e.level = source_level(g);
             if (id >= 0)
                 for (int p = 0; p < 2; ++p)
                     e.src[p] = reinterpret_cast<const float2 *>(c->arena + c->nodes[(size_t)id].off_stream[p]);
@@ -294,7 +340,7 @@ int watch_rebuild(sdrx_ctx *c)
         for (int id = 0; id < N; ++id) {
             const sdrx_ctx::Watch::Leaf &L = W.leaf[(size_t)id];
             const int parent = c->nodes[(size_t)id].d.parent_id;
-            if (!L.on || (parent < 0 ? g != 0 : c->nodes[(size_t)parent].level != g - 1))
+            if (!L.on.v || source_group(c, parent) != g)
                 continue;
             leaves.push_back(WatchLeaf{src_index[(size_t)(1 + parent)], L.first_bin, L.n_bins, L.slot});
         }
@@ -325,27 +371,34 @@ int watch_retuned(sdrx_ctx *c, const int *ids, int n)
         if (L.slot < 0)
             continue;
         watch_band(c->nodes[(size_t)ids[k]].d, &L.first_bin, &L.n_bins);
-        any |= L.on != 0;
+        any |= L.on.v != 0;
     }
     return any ? watch_rebuild(c) : SDRX_OK;
+}
+
+// A call `what` about the source of ONE watched leaf between frames -- it changes what the next frame measures, or reads the
+// device: leaf_call's checks with "the leaf is watched" in front of the caller's own `bad`, then the context's device, drained
+// (frames inside the software pipeline finish with the old setting).
+int watched_leaf_call(sdrx_ctx *c, const char *what, int leaf_id, bool arrays, const std::function<const char *()> &bad = nullptr)
+{
+    auto all = [&](int) -> const char * {
+        if (c->watch.leaf.empty() || !c->watch.leaf[(size_t)leaf_id].on.v)
+            return "is not watched (sdrx_set_watch)";
+        return bad ? bad() : nullptr;
+    };
+    if (int rc = leaf_call(c, what, &sdrx_ctx::opt_watch, "watch", &leaf_id, arrays, 1, kBetweenFrames, all))
+        return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return drain(c);
 }
 
 // what sdrx_get_scan_hits and sdrx_get_scan_cells share: the checks, and the record of the last completed evaluation
 int scan_evaluation(sdrx_ctx *c, const char *what, int leaf_id, bool arrays, const ScanState **state, ScanRecord *head)
 {
-    auto bad = [&](int) -> const char * {
-        if (c->watch.leaf.empty() || !c->watch.leaf[(size_t)leaf_id].on)
-            return "is not watched (sdrx_set_watch)";
-        if (c->scan.src.empty() || c->scan.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)].cfg.cell_bins == 0)
-            return "its source has no band scan (sdrx_set_scan)";
-        return nullptr;
-    };
-    if (int rc = leaf_call(c, what, &sdrx_ctx::opt_watch, "watch", &leaf_id, arrays, 1, kBetweenFrames, bad))
+    auto bad = [&] { return analysis_on(c->scan, source_of(c, leaf_id)) ? nullptr : "its source has no band scan (sdrx_set_scan)"; };
+    if (int rc = watched_leaf_call(c, what, leaf_id, arrays, bad))
         return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = drain(c))
-        return rc;
-    const ScanState *st = c->scan.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)].d_state;
+    const ScanState *st = static_cast<const ScanState *>(c->scan.src[source_of(c, leaf_id)].d_state);
     struct {
         ScanRecord head;
         unsigned count, valid;
@@ -376,16 +429,8 @@ int sdrx_set_watch(sdrx_ctx *c, const int *ids, const int32_t *on, int n)
     sdrx_ctx::Watch &W = c->watch;
     const std::vector<sdrx_ctx::Watch::Leaf> before = W.leaf;
     bool changed = false;
-    for (int k = 0; k < n; ++k) {
-        sdrx_ctx::Watch::Leaf &L = W.leaf[(size_t)ids[k]];
-        if (L.on == on[k])
-            continue;
-        if (L.since != c->frame_no) // (a second change before the same frame: the frames before it ran in the state they ran in)
-            L.was_on = L.on;
-        L.on = on[k];
-        L.since = c->frame_no;
-        changed = true;
-    }
+    for (int k = 0; k < n; ++k)
+        changed |= switch_to(W.leaf[(size_t)ids[k]].on, on[k], c->frame_no);
     if (!changed)
         return SDRX_OK;
     const int rc = watch_rebuild(c);
@@ -408,8 +453,8 @@ int sdrx_get_watch(sdrx_ctx *c, const int *ids, int n, sdrx_watch_level *out)
         const sdrx_ctx::Watch::Leaf &L = W.leaf[(size_t)ids[k]];
         sdrx_watch_level r;
         memset(&r, 0, sizeof r);
-        if (W.h_rec[c->host_slot] && W.watched_at(ids[k], c->host_frame)) {
-            memcpy(&r, W.h_rec[c->host_slot] + L.slot, sizeof r);
+        if (W.rec.h[c->host_slot] && W.watched_at(ids[k], c->host_frame)) {
+            memcpy(&r, W.rec.host<WatchRecord>(c->host_slot) + L.slot, sizeof r);
         } else {
             r.first_bin = L.first_bin;
             r.n_bins = L.n_bins;
@@ -422,14 +467,10 @@ int sdrx_get_watch(sdrx_ctx *c, const int *ids, int n, sdrx_watch_level *out)
 
 int sdrx_get_watch_psd(sdrx_ctx *c, int leaf_id, double *psd, int64_t *frame)
 {
-    auto unwatched = [&](int) { return c->watch.leaf.empty() || !c->watch.leaf[(size_t)leaf_id].on ? "is not watched (sdrx_set_watch)" : nullptr; };
-    if (int rc = leaf_call(c, "sdrx_get_watch_psd", &sdrx_ctx::opt_watch, "watch", &leaf_id, true, 1, kBetweenFrames, unwatched))
+    if (int rc = watched_leaf_call(c, "sdrx_get_watch_psd", leaf_id, true))
         return rc;
     const sdrx_ctx::Watch &W = c->watch;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = drain(c))
-        return rc;
-    if (c->frame_no <= std::max(W.psd_since, W.leaf[(size_t)leaf_id].since))
+    if (c->frame_no <= std::max(W.psd_since, W.leaf[(size_t)leaf_id].on.since))
         return fail(c, SDRX_ESTATE, "sdrx_get_watch_psd: no frame has been measured for vfo %d yet", leaf_id);
     const int parent = c->nodes[(size_t)leaf_id].d.parent_id;
     size_t k = 0;
@@ -446,9 +487,7 @@ int sdrx_get_watch_psd(sdrx_ctx *c, int leaf_id, double *psd, int64_t *frame)
 
 int sdrx_set_drift(sdrx_ctx *c, int leaf_id, const double *templ, int max_shift)
 {
-    auto bad = [&](int) -> const char * {
-        if (c->watch.leaf.empty() || !c->watch.leaf[(size_t)leaf_id].on)
-            return "is not watched (sdrx_set_watch)";
+    auto bad = [&]() -> const char * {
         if (max_shift < 0 || max_shift > SDRX_DRIFT_MAX_SHIFT)
             return "max_shift must lie in 0 .. SDRX_DRIFT_MAX_SHIFT";
         for (int i = 0; templ && max_shift > 0 && i < kSpecN; ++i)
@@ -456,88 +495,49 @@ int sdrx_set_drift(sdrx_ctx *c, int leaf_id, const double *templ, int max_shift)
                 return "a template entry is negative or not finite";
         return nullptr;
     };
-    if (int rc = leaf_call(c, "sdrx_set_drift", &sdrx_ctx::opt_watch, "watch", &leaf_id, true, 1, kBetweenFrames, bad))
+    if (int rc = watched_leaf_call(c, "sdrx_set_drift", leaf_id, true, bad))
         return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = drain(c)) // frames inside the software pipeline finish with the old setting
-        return rc;
-    drift_host_init(c);
     sdrx_ctx::Drift &D = c->drift;
-    sdrx_ctx::Drift::Src &S = D.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)];
-    if (max_shift == 0 && S.K == 0)
+    sdrx_ctx::SourceAnalysis::Src &S = analysis_source(c, D, leaf_id);
+    if (max_shift == 0 && S.on.v == 0)
         return SDRX_OK;
-    if (!D.d_desc) {
-        const size_t desc_bytes = (sizeof(DriftSrc) + sizeof(DriftBlk) * kDriftMaxBlocks) * (size_t)D.n_slots;
-        const size_t rec_bytes = sizeof(DriftRecord) * (size_t)D.n_slots;
-        HIPCHK(c, hipMalloc(&D.d_desc, desc_bytes));
-        for (int p = 0; p < 2; ++p) {
-            HIPCHK(c, hipMalloc(&D.d_rec[p], rec_bytes));
-            HIPCHK(c, hipMemset(D.d_rec[p], 0, rec_bytes));
-            HIPCHK(c, hipHostMalloc(&D.h_rec[p], rec_bytes, hipHostMallocDefault));
-            memset(D.h_rec[p], 0, rec_bytes);
-        }
-        D.bytes += desc_bytes + 2 * rec_bytes;
-    }
+    if (int rc = analysis_alloc(c, D, sizeof(DriftSrc) + sizeof(DriftBlk) * kDriftMaxBlocks, sizeof(DriftRecord)))
+        return rc;
+    D.set_at.resize(D.src.size(), 0);
     if (max_shift > 0) {
-        if (!S.d_state) {
-            HIPCHK(c, hipMalloc(&S.d_state, sizeof(DriftState)));
-            HIPCHK(c, hipMemset(S.d_state, 0, sizeof(DriftState)));
-            D.bytes += sizeof(DriftState);
-        }
-        unsigned char *base = reinterpret_cast<unsigned char *>(S.d_state);
+        if (int rc = analysis_state(c, D, S, sizeof(DriftState)))
+            return rc;
+        unsigned char *base = static_cast<unsigned char *>(S.d_state);
         if (templ)
             HIPCHK(c, hipMemcpy(base + offsetof(DriftState, templ), templ, sizeof(double) * kSpecN, hipMemcpyHostToDevice));
         const unsigned capture = templ ? 0u : 1u; // (an upload also calls off a capture still waiting for its frame)
         HIPCHK(c, hipMemcpy(base + offsetof(DriftState, capture), &capture, sizeof capture, hipMemcpyHostToDevice));
     }
-    const sdrx_ctx::Drift::Src before = S;
-    if (S.K != max_shift) {
-        if (S.since != c->frame_no) // (as sdrx_set_watch: the frames before ran in the state they ran in)
-            S.was_K = S.K;
-        S.K = max_shift;
-        S.since = c->frame_no;
-    }
-    S.set_at = c->frame_no;
+    unsigned long long &set_at = D.set_at[source_of(c, leaf_id)];
+    const sdrx_ctx::SourceAnalysis::Src before = S;
+    const unsigned long long set_before = set_at;
+    switch_to(S.on, max_shift, c->frame_no);
+    set_at = c->frame_no;
     if (int rc = drift_rebuild(c, c->watch.src_ids, c->watch.src_psd)) {
         S = before;
+        set_at = set_before;
         return rc;
     }
     return SDRX_OK;
 }
 
-int sdrx_get_drift(sdrx_ctx *c, int leaf_id, sdrx_drift_level *out)
-{
-    if (int rc = leaf_call(c, "sdrx_get_drift", &sdrx_ctx::opt_watch, "watch", &leaf_id, out != nullptr, 1, kDelivered))
-        return rc;
-    sdrx_drift_level r;
-    memset(&r, 0, sizeof r);
-    r.frame = (int64_t)c->host_frame;
-    const sdrx_ctx::Drift &D = c->drift;
-    if (D.h_rec[c->host_slot] && drift_measured_at(c, leaf_id, c->host_frame))
-        memcpy(&r, D.h_rec[c->host_slot] + D.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)].slot, sizeof r);
-    *out = r;
-    return SDRX_OK;
-}
+int sdrx_get_drift(sdrx_ctx *c, int leaf_id, sdrx_drift_level *out) { return analysis_record(c, "sdrx_get_drift", c ? &c->drift : nullptr, leaf_id, out); }
 
 int sdrx_get_drift_profile(sdrx_ctx *c, int leaf_id, double *profile, int64_t *frame)
 {
-    auto bad = [&](int) -> const char * {
-        if (c->watch.leaf.empty() || !c->watch.leaf[(size_t)leaf_id].on)
-            return "is not watched (sdrx_set_watch)";
-        if (c->drift.src.empty() || c->drift.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)].K == 0)
-            return "its source has no drift estimate (sdrx_set_drift)";
-        return nullptr;
-    };
-    if (int rc = leaf_call(c, "sdrx_get_drift_profile", &sdrx_ctx::opt_watch, "watch", &leaf_id, true, 1, kBetweenFrames, bad))
+    auto bad = [&] { return analysis_on(c->drift, source_of(c, leaf_id)) ? nullptr : "its source has no drift estimate (sdrx_set_drift)"; };
+    if (int rc = watched_leaf_call(c, "sdrx_get_drift_profile", leaf_id, true, bad))
         return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = drain(c))
-        return rc;
-    const sdrx_ctx::Drift::Src &S = c->drift.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)];
-    if (c->frame_no <= std::max(std::max(S.set_at, S.since), c->watch.leaf[(size_t)leaf_id].since))
+    const sdrx_ctx::SourceAnalysis::Src &S = c->drift.src[source_of(c, leaf_id)];
+    if (c->frame_no <= std::max(std::max(c->drift.set_at[source_of(c, leaf_id)], S.on.since), c->watch.leaf[(size_t)leaf_id].on.since))
         return fail(c, SDRX_ESTATE, "sdrx_get_drift_profile: no frame has been measured for the source of vfo %d yet", leaf_id);
     if (profile)
-        HIPCHK(c, hipMemcpy(profile, reinterpret_cast<const unsigned char *>(S.d_state) + offsetof(DriftState, profile), sizeof(double) * (size_t)(2 * S.K + 1),
+        HIPCHK(c, hipMemcpy(profile, static_cast<const unsigned char *>(S.d_state) + offsetof(DriftState, profile), sizeof(double) * (size_t)(2 * S.on.v + 1),
                             hipMemcpyDeviceToHost));
     if (frame)
         *frame = (int64_t)c->frame_no - 1;
@@ -547,75 +547,42 @@ int sdrx_get_drift_profile(sdrx_ctx *c, int leaf_id, double *profile, int64_t *f
 int sdrx_set_scan(sdrx_ctx *c, int leaf_id, const sdrx_scan_cfg *cfg)
 {
     const bool on = cfg && cfg->cell_bins != 0;
-    auto bad = [&](int) -> const char * {
-        if (c->watch.leaf.empty() || !c->watch.leaf[(size_t)leaf_id].on)
-            return "is not watched (sdrx_set_watch)";
+    auto bad = [&]() -> const char * {
         if (cfg && (cfg->reserved[0] || cfg->reserved[1] || cfg->reserved[2]))
             return "a reserved field is not 0";
         return on ? bad_scan(*cfg) : nullptr;
     };
-    if (int rc = leaf_call(c, "sdrx_set_scan", &sdrx_ctx::opt_watch, "watch", &leaf_id, true, 1, kBetweenFrames, bad))
+    if (int rc = watched_leaf_call(c, "sdrx_set_scan", leaf_id, true, bad))
         return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = drain(c)) // frames inside the software pipeline finish with the old setting
-        return rc;
-    scan_host_init(c);
     sdrx_ctx::Scan &S = c->scan;
-    sdrx_ctx::Scan::Src &R = S.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)];
-    if (!on && R.cfg.cell_bins == 0)
+    sdrx_ctx::SourceAnalysis::Src &R = analysis_source(c, S, leaf_id);
+    if (!on && R.on.v == 0)
         return SDRX_OK;
-    if (!S.d_src) {
-        const size_t src_bytes = sizeof(ScanSrc) * (size_t)S.n_slots, rec_bytes = sizeof(ScanRecord) * (size_t)S.n_slots;
-        HIPCHK(c, hipMalloc(&S.d_src, src_bytes));
-        for (int p = 0; p < 2; ++p) {
-            HIPCHK(c, hipMalloc(&S.d_rec[p], rec_bytes));
-            HIPCHK(c, hipMemset(S.d_rec[p], 0, rec_bytes));
-            HIPCHK(c, hipHostMalloc(&S.h_rec[p], rec_bytes, hipHostMallocDefault));
-            memset(S.h_rec[p], 0, rec_bytes);
-        }
-        S.bytes += src_bytes + 2 * rec_bytes;
-    }
+    if (int rc = analysis_alloc(c, S, sizeof(ScanSrc), sizeof(ScanRecord)))
+        return rc;
+    S.cfg.resize(S.src.size(), ScanCfg{});
     if (on) {
-        if (!R.d_state) {
-            HIPCHK(c, hipMalloc(&R.d_state, sizeof(ScanState)));
-            HIPCHK(c, hipMemset(R.d_state, 0, sizeof(ScanState)));
-            S.bytes += sizeof(ScanState);
-        }
+        if (int rc = analysis_state(c, S, R, sizeof(ScanState)))
+            return rc;
         // every accepted setting restarts the integration, and the last evaluation is no longer this setting's
         static_assert(offsetof(ScanState, valid) == offsetof(ScanState, count) + sizeof(unsigned), "count and valid are cleared together");
-        HIPCHK(c, hipMemset(reinterpret_cast<unsigned char *>(R.d_state) + offsetof(ScanState, count), 0, 2 * sizeof(unsigned)));
+        HIPCHK(c, hipMemset(static_cast<unsigned char *>(R.d_state) + offsetof(ScanState, count), 0, 2 * sizeof(unsigned)));
     }
-    const sdrx_ctx::Scan::Src before = R;
-    const int w = on ? cfg->cell_bins : 0;
-    if (R.cfg.cell_bins != w) {
-        if (R.since != c->frame_no) // (as sdrx_set_watch: the frames before ran in the state they ran in)
-            R.was_w = R.cfg.cell_bins;
-        R.since = c->frame_no;
-    }
+    ScanCfg &kept = S.cfg[source_of(c, leaf_id)];
+    const sdrx_ctx::SourceAnalysis::Src before = R;
+    const ScanCfg cfg_before = kept;
+    switch_to(R.on, on ? cfg->cell_bins : 0, c->frame_no);
     if (on)
-        memcpy(&R.cfg, cfg, sizeof R.cfg);
-    else
-        R.cfg.cell_bins = 0;
+        memcpy(&kept, cfg, sizeof kept);
     if (int rc = scan_rebuild(c, c->watch.src_ids, c->watch.src_psd)) {
         R = before;
+        kept = cfg_before;
         return rc;
     }
     return SDRX_OK;
 }
 
-int sdrx_get_scan(sdrx_ctx *c, int leaf_id, sdrx_scan_level *out)
-{
-    if (int rc = leaf_call(c, "sdrx_get_scan", &sdrx_ctx::opt_watch, "watch", &leaf_id, out != nullptr, 1, kDelivered))
-        return rc;
-    sdrx_scan_level r;
-    memset(&r, 0, sizeof r);
-    r.frame = (int64_t)c->host_frame;
-    const sdrx_ctx::Scan &S = c->scan;
-    if (S.h_rec[c->host_slot] && scan_measured_at(c, leaf_id, c->host_frame))
-        memcpy(&r, S.h_rec[c->host_slot] + S.src[(size_t)(1 + c->nodes[(size_t)leaf_id].d.parent_id)].slot, sizeof r);
-    *out = r;
-    return SDRX_OK;
-}
+int sdrx_get_scan(sdrx_ctx *c, int leaf_id, sdrx_scan_level *out) { return analysis_record(c, "sdrx_get_scan", c ? &c->scan : nullptr, leaf_id, out); }
 
 int sdrx_get_scan_hits(sdrx_ctx *c, int leaf_id, sdrx_scan_hit *hits, int max_hits, int *n, int64_t *frame)
 {

@@ -226,8 +226,6 @@ class _LeafCalls:
         if int(cell_bins) == 0:
             self._call("set_scan", int(vid), None)
             return
-        if not hasattr(self, "_scan_w"):
-            self._scan_w = {}
         if not 0 <= int(ratio_q8) < 1 << 32:
             raise ValueError(f"ratio_q8 {ratio_q8} is no uint32")
         cfg = _lib.ScanCfgC(int(cell_bins), int(frames), int(floor_permille), int(ratio_q8), int(min_cells))
@@ -257,7 +255,7 @@ class _LeafCalls:
 
     def _scan_cell_bins(self, vid: int) -> int:
         # the width this wrapper last set for the leaf's source (the C call returns C doubles and leaves C to its caller)
-        return getattr(self, "_scan_w", {}).get(self.descs[vid].parent, 1)
+        return self._scan_w.get(self.descs[vid].parent, 1)
 
     # -- retuning between frames (on a group: on every member that holds the VFO) -------------------------------------------
     def set_mixer_freqs(self, vids, freqs) -> None:
@@ -290,6 +288,7 @@ class Receiver(_LeafCalls):
             raise SdrxError(rc, self.L.sdrx_last_error(None).decode())
         self.h = h
         self.descs: list[VfoDesc] = []
+        self._scan_w: dict[int, int] = {}  # source -> the cell width last set through this object (scan_cells trims to it)
         self.published: list[tuple[bytes, int, bytes]] = []
         self._cb = _lib.PUBLISH_FN(self._on_publish)
         self._chk(self.L.sdrx_set_publish_callback(self.h, self._cb, None))
@@ -575,6 +574,7 @@ class Group(_LeafCalls):
         self.h = h
         self.devices = list(devices)
         self.descs: list[VfoDesc] = []
+        self._scan_w: dict[int, int] = {}  # source -> the cell width last set through this object (scan_cells trims to it)
         self.published: list[tuple[bytes, int, bytes]] = []
         self._cb = _lib.PUBLISH_FN(lambda user, topic, rate, buf, length: self.published.append(
             (C.string_at(topic, 5), int(rate), C.string_at(buf, length))))

@@ -1,9 +1,10 @@
 """The calling rules of the per-leaf control calls, one table for the context's calls and the group's.
 
-Every batched setter and getter (squelch, auto-squelch, parking, catch-up, watch, meters, retune, gain) and the single-id
-getters (output, pre-roll, watch PSD) are called with each kind of wrong input, alone and two at a time, and the code that
-comes back is compared with the order DESIGN.md states: handle, finalized, option, list shape, ids (range, leaf, once),
-values, frames in flight or delivered.  Then one frame runs and every pair is read back: what was set is what is got.
+Every batched setter and getter (squelch, auto-squelch, parking, catch-up, watch, meters, retune, gain), the single-id
+getters (output, pre-roll, watch PSD) and the single-leaf calls of the analyses on a watched source (drift estimate, band scan)
+are called with each kind of wrong input, alone and two at a time, and the code that comes back is compared with the order
+DESIGN.md states: handle, finalized, option, list shape, ids (range, leaf, once), values, frames in flight or delivered.  Then
+one frame runs and every pair is read back: what was set is what is got.
 
 The tree is helpers.tree_1536(): mains 0 and 1, leaves 2 3 (under 0) and 4 5 6 (under 1).  As a group on [0, 0] member 0
 holds {0, 1, 2, 4} and member 1 {0, 1, 3, 5, 6}.  The ABI has no getter for a gain: a leaf's gain is read off its payload
@@ -43,6 +44,20 @@ GETTERS = {
     "get_catchup": ("catchup", _lib.MeterC, False),
     "get_watch": ("watch", _lib.WatchLevelC, True),
 }
+# The single-leaf calls about the source of a watched leaf (besides get_watch_psd): True = needs no frame in flight -- there the
+# group looks at ITS frames in flight before the member looks at anything, so a group with a frame in flight answers ESTATE
+# where a context answers EINVAL; False = reads the delivered frame's record, and is the member's from the id's range on.
+SINGLE = {"set_drift": True, "get_drift": False, "get_drift_profile": True, "set_scan": True, "get_scan": False,
+          "get_scan_hits": True, "get_scan_cells": True}
+GOOD_SCAN = dict(cell_bins=4, frames=1, floor_permille=500, ratio_q8=512, min_cells=1)
+# what each setter refuses for its values: (call, arguments, what is wrong)
+BAD_VALUES = [("set_drift", dict(max_shift=-1), "max_shift -1"), ("set_drift", dict(max_shift=_lib.DRIFT_MAX_SHIFT + 1), "max_shift past the limit"),
+              ("set_drift", dict(templ=-1.0), "a negative template entry"), ("set_drift", dict(templ=NAN), "a template entry that is no number")]
+BAD_VALUES += [("set_scan", dict(cfg=dict(GOOD_SCAN, **{key: v})), f"{key} {v}") for key, v in
+               (("cell_bins", 3), ("cell_bins", -4), ("cell_bins", 512), ("frames", 0), ("frames", 65537), ("floor_permille", -1),
+                ("floor_permille", 1001), ("ratio_q8", 0), ("min_cells", 0), ("min_cells", _lib.SPECTRUM_BINS // 4 + 1))]
+BAD_VALUES += [("set_scan", dict(cfg=dict(GOOD_SCAN, reserved=(0, 0, 1))), "a reserved field"),
+               ("set_scan", dict(cfg=dict(GOOD_SCAN, cell_bins=0, reserved=(1, 0, 0))), "a reserved field of a switch-off")]
 
 
 class Api:
@@ -101,6 +116,32 @@ class Api:
         psd, f = np.zeros(_lib.SPECTRUM_BINS, np.float64), C.c_int64(-7)
         return self.call("get_watch_psd", vid, psd.ctypes.data, C.byref(f), handle=handle), psd, f.value
 
+    def single(self, name, vid, handle=True, out=True, **kw):
+        """(code, what it wrote) of the SINGLE call `name` about leaf `vid`, with good arguments but for `kw`: `templ` (a value
+        for template entry 5; default: capture), `max_shift`, `cfg` (a dict of sdrx_scan_cfg's fields or None), `max_hits`;
+        out = False: a null pointer for the result."""
+        f = C.c_int64(-7)
+        if name == "set_drift":
+            t = None
+            if "templ" in kw:
+                t = np.ones(_lib.SPECTRUM_BINS, np.float64)
+                t[5] = kw["templ"]
+            return self.call(name, vid, None if t is None else t.ctypes.data, kw.get("max_shift", 2), handle=handle), None
+        if name == "set_scan":
+            cfg = dict(kw.get("cfg", GOOD_SCAN) or {})
+            reserved = (C.c_int32 * 3)(*cfg.pop("reserved", (0, 0, 0)))
+            c = _lib.ScanCfgC(reserved=reserved, **cfg)
+            return self.call(name, vid, None if kw.get("cfg", GOOD_SCAN) is None else C.byref(c), handle=handle), None
+        if name in ("get_drift", "get_scan"):
+            rec = (_lib.DriftLevelC if name == "get_drift" else _lib.ScanLevelC)()
+            return self.call(name, vid, C.byref(rec) if out else None, handle=handle), rec
+        if name == "get_scan_hits":
+            hits, n = (_lib.ScanHitC * 4)(), C.c_int(-7)
+            rc = self.call(name, vid, C.cast(hits, C.c_void_p) if out else None, kw.get("max_hits", 4), C.byref(n), C.byref(f), handle=handle)
+            return rc, (n.value, f.value)
+        buf = np.zeros(max(_lib.SPECTRUM_BINS, 2 * _lib.DRIFT_MAX_SHIFT + 1), np.float64)  # get_drift_profile, get_scan_cells
+        return self.call(name, vid, buf.ctypes.data, C.byref(f), handle=handle), (buf, f.value)
+
     def contexts_of(self, vid):
         """(context, local id) of every holder of VFO `vid`"""
         if self.kind == "ctx":
@@ -125,9 +166,11 @@ class Api:
         """What the getters that answer at any time after a delivery say is set (the selection of the watch: through the PSD call,
         EINVAL for a leaf that is not watched)."""
         sq, au, ac = self.getter("get_squelch", LEAVES)[1], self.getter("get_squelch_auto", LEAVES)[1], self.getter("get_active", LEAVES)[1]
+        # (a drift setting that took effect makes the profile ESTATE until the next frame, a scan setting the hits and the cells)
+        reads = [(rc, out[0].tobytes()) for n in ("get_drift_profile", "get_scan_cells") for i in LEAVES for rc, out in [self.single(n, i)]]
         return ([(s.thr_sum_sq, s.hang_frames) for s in sq[:5]], [(s.ratio_q8, s.window_frames) for s in au[:5]],
                 [(s.active, s.since_frame) for s in ac[:5]], [self.watch_psd(i)[0] == EINVAL for i in LEAVES],
-                [t.tobytes() for i in range(7) for t in self.nco(i)])
+                [t.tobytes() for i in range(7) for t in self.nco(i)], reads, [self.single("get_scan_hits", i) for i in LEAVES])
 
     def close(self):
         self.obj.close()
@@ -169,6 +212,11 @@ def _unfinalized_and_null(api, r):
     r.code(api.output(2, handle=False)[0], EINVAL, k, "get_output, null handle")
     r.code(api.preroll(2, handle=False)[0], EINVAL, k, "get_preroll, null handle")
     r.code(api.watch_psd(2, handle=False)[0], EINVAL, k, "get_watch_psd, null handle")
+    for name in SINGLE:  # finalized before the id, the shape and the values, on a context and on a group
+        r.code(api.single(name, 2)[0], ESTATE, k, name, "before finalize")
+        r.code(api.single(name, 99)[0], ESTATE, k, name, "before finalize, id 99")
+        r.code(api.single(name, 2, out=False, max_hits=-1, max_shift=-1, cfg=dict(GOOD_SCAN, frames=0))[0], ESTATE, k, name, "before finalize, bad arguments")
+        r.code(api.single(name, 2, handle=False)[0], EINVAL, k, name, "null handle")
 
 
 def _options_off(api, r):
@@ -200,6 +248,11 @@ def _options_off(api, r):
     r.code(api.preroll(99)[0], EINVAL, k, "get_preroll, option off, id 99")  # (the id's range comes first in this call)
     r.code(api.watch_psd(2)[0], ESTATE, k, "get_watch_psd, option off")
     r.code(api.watch_psd(99)[0], EINVAL if grp else ESTATE, k, "get_watch_psd, option off, id 99")
+    for name in SINGLE:  # as get_watch_psd: the group has looked at the id's range when the member finds the option off
+        r.code(api.single(name, 2)[0], ESTATE, k, name, "option off")
+        r.code(api.single(name, 99)[0], EINVAL if grp else ESTATE, k, name, "option off, id 99")
+        r.code(api.single(name, PARENT)[0], ESTATE, k, name, "option off, a VFO with children")
+        r.code(api.single(name, 2, out=False, max_hits=-1, max_shift=-1, cfg=dict(GOOD_SCAN, frames=0))[0], ESTATE, k, name, "option off, bad arguments")
 
 
 def _wrong_lists(api, r, when, in_flight, delivered):
@@ -233,6 +286,25 @@ def _wrong_lists(api, r, when, in_flight, delivered):
         r.code(api.output(vid)[0], EINVAL, k, "get_output", when, "id", vid)
         r.code(api.preroll(vid)[0], EINVAL, k, "get_preroll", when, "id", vid)
         r.code(api.watch_psd(vid)[0], ESTATE if grp and in_flight and vid == PARENT else EINVAL, k, "get_watch_psd", when, "id", vid)
+    # The single-leaf calls of the drift and the scan.  Leaf 3 is never watched, leaf 5's source never has a drift or a scan; leaf 2
+    # is watched, and its source has both, from _round_trip on (before that, that it is not watched is what is wrong with it).
+    # On a group every call that needs no frame in flight is ESTATE while there is one, whatever else is wrong past the id's range.
+    early = ESTATE if grp and in_flight else EINVAL
+    for name, between in SINGLE.items():
+        for vid in (-1, 99):
+            r.code(api.single(name, vid)[0], EINVAL, k, name, when, "id", vid)
+        r.code(api.single(name, PARENT)[0], early if between else EINVAL, k, name, when, "id", PARENT)
+        if between:
+            r.code(api.single(name, 3)[0], early, k, name, when, "a leaf that is not watched")
+    for name in ("get_drift_profile", "get_scan_hits", "get_scan_cells"):
+        r.code(api.single(name, 5)[0], early, k, name, when, "a source without the analysis")
+    for name, kw, what in BAD_VALUES:
+        r.code(api.single(name, 2, **kw)[0], early, k, name, when, what)
+    r.code(api.single("get_drift", 2, out=False)[0], EINVAL, k, "get_drift", when, "null out")
+    r.code(api.single("get_scan", 2, out=False)[0], EINVAL, k, "get_scan", when, "null out")
+    r.code(api.single("get_scan_hits", 2, max_hits=-1)[0], early, k, "get_scan_hits", when, "max_hits -1")
+    r.code(api.single("get_scan_hits", 2, out=False)[0], early, k, "get_scan_hits", when, "null hits with room for 4")
+    r.code(api.single("get_scan_hits", 99, max_hits=-1)[0], EINVAL, k, "get_scan_hits", when, "max_hits -1, id 99")
 
 
 def _nothing_delivered(api, r, when, in_flight):
@@ -243,6 +315,8 @@ def _nothing_delivered(api, r, when, in_flight):
     r.code(api.output(2)[0], ESTATE, k, "get_output", when)
     r.code(api.output(2, buf=False)[0], ESTATE if in_flight else OK, k, "get_output as a length query", when)
     r.code(api.preroll(2)[0], ESTATE, k, "get_preroll", when)
+    r.code(api.single("get_drift", 2)[0], ESTATE, k, "get_drift", when)
+    r.code(api.single("get_scan", 2)[0], ESTATE, k, "get_scan", when)
 
 
 def _round_trip(api, r, iq):
@@ -255,10 +329,22 @@ def _round_trip(api, r, iq):
         r.code(api.setter(name, ids, *vals), OK, k, name, "valid", api.error())
     r.code(api.watch_psd(3)[0], EINVAL, k, "get_watch_psd of a leaf that is not watched")
     r.code(api.watch_psd(2)[0], ESTATE, k, "get_watch_psd before the first measured frame")
+    for name in ("get_drift_profile", "get_scan_hits", "get_scan_cells"):
+        r.code(api.single(name, 2)[0], EINVAL, k, name, "of a watched leaf whose source has no such analysis")
+    r.code(api.single("set_drift", 2, max_shift=0)[0], OK, k, "set_drift: off where it is off", api.error())
+    r.code(api.single("set_scan", 2, cfg=None)[0], OK, k, "set_scan: off where it is off", api.error())
+    r.code(api.single("set_drift", 2)[0], OK, k, "set_drift", "valid", api.error())  # captures frame 0 as the template
+    r.code(api.single("set_scan", 2)[0], OK, k, "set_scan", "valid", api.error())  # one frame per evaluation
+    r.code(api.single("get_drift_profile", 2)[0], ESTATE, k, "get_drift_profile before the first measured frame")
+    r.code(api.single("get_scan_hits", 2)[0], ESTATE, k, "get_scan_hits before the first evaluation")
+    r.code(api.single("get_scan_cells", 2)[0], ESTATE, k, "get_scan_cells before the first evaluation")
     api.obj.submit(iq)
     for name in SETTERS:  # a frame submitted and not waited for
         r.code(api.setter(name, [2], *api.good(name, [2])), ESTATE, k, name, "a frame in flight")
     r.code(api.watch_psd(2)[0], ESTATE, k, "get_watch_psd, a frame in flight")
+    for name, between in SINGLE.items():
+        if between:
+            r.code(api.single(name, 2)[0], ESTATE, k, name, "a frame in flight")
     _wrong_lists(api, r, "in flight", True, False)  # the list before the frames in flight
     _nothing_delivered(api, r, "in flight, nothing delivered", True)
     api.obj.wait()
@@ -276,6 +362,20 @@ def _round_trip(api, r, iq):
     r.true([(w.frame, w.watched) for w in wa[:3]] == [(0, 1), (0, 1), (0, 0)] and wa[0].band_pwr > 0 and wa[1].total_pwr > 0, k, "watch read back")
     rc, psd, frame = api.watch_psd(2)
     r.true(rc == OK and frame == 0 and float(psd.sum()) > 0, k, "get_watch_psd of a watched leaf", rc, frame)
+    rc, dl = api.single("get_drift", 2)
+    r.true(rc == OK and (dl.frame, dl.measured, dl.captured, dl.max_shift, dl.shift) == (0, 1, 1, 2, 0), k, "drift read back", rc, dl.frame, dl.measured, dl.captured)
+    rc, sl = api.single("get_scan", 2)
+    r.true(rc == OK and (sl.frame, sl.measured, sl.complete, sl.cell_bins, sl.frames, sl.integrated) == (0, 1, 1, 4, 1, 1), k, "scan read back", rc, sl.frame, sl.complete)
+    for name in ("get_drift", "get_scan"):  # a leaf whose source has no analysis: an empty record of the delivered frame
+        rc, rec = api.single(name, 5)
+        r.true(rc == OK and (rec.frame, rec.measured) == (0, 0), k, name, "of a source without the analysis", rc, rec.frame, rec.measured)
+    rc, (prof, frame) = api.single("get_drift_profile", 2)
+    r.true(rc == OK and frame == 0 and prof[2] > 0 and not prof[5:].any(), k, "get_drift_profile of a measured source", rc, frame)
+    rc, (n, frame) = api.single("get_scan_hits", 2)
+    r.true(rc == OK and frame == 0 and 0 <= n <= min(4, sl.n_stored), k, "get_scan_hits of a completed evaluation", rc, n, frame)
+    r.code(api.single("get_scan_hits", 2, out=False, max_hits=0)[0], OK, k, "get_scan_hits as a question without room")
+    rc, (cells, frame) = api.single("get_scan_cells", 2)
+    r.true(rc == OK and frame == 0 and float(cells[:2048].sum()) > 0 and not cells[2048:].any(), k, "get_scan_cells of a completed evaluation", rc, frame)
     me = api.getter("get_meters", LEAVES)[1]
     for j, i in enumerate(LEAVES):
         rc, pay = api.output(i)
@@ -301,6 +401,19 @@ def _round_trip(api, r, iq):
     r.true(cu[0].frame == 0 and cu[0].n_values == 96000 >> 5 and cu[0].sum_sq > 0 and cu[1].frame == -1, k, "catch-up read back", cu[0].frame, cu[1].frame)
     ac = api.getter("get_active", [3])[1]
     r.true((ac[0].active, ac[0].since_frame) == (1, 1), k, "active after the unpark")
+    # a new setting: the profile and the evaluation are no longer this setting's; switched off: the source has no analysis
+    r.code(api.single("set_drift", 2, templ=1.0, max_shift=3)[0], OK, k, "set_drift with a template", api.error())
+    r.code(api.single("get_drift_profile", 2)[0], ESTATE, k, "get_drift_profile after a new setting")
+    r.code(api.single("set_scan", 2)[0], OK, k, "set_scan again", api.error())
+    r.code(api.single("get_scan_cells", 2)[0], ESTATE, k, "get_scan_cells after a new setting")
+    r.code(api.single("set_drift", 2, max_shift=0)[0], OK, k, "set_drift: off", api.error())
+    r.code(api.single("set_scan", 2, cfg=None)[0], OK, k, "set_scan: off", api.error())
+    for name in ("get_drift_profile", "get_scan_hits", "get_scan_cells"):
+        r.code(api.single(name, 2)[0], EINVAL, k, name, "after the switch-off")
+    rc, dl = api.single("get_drift", 2)  # the delivered frame ran with the analyses on
+    r.true(rc == OK and (dl.frame, dl.measured) == (0, 1), k, "get_drift of frame 0 after the switch-off", rc, dl.frame, dl.measured)
+    rc, sl = api.single("get_scan", 2)
+    r.true(rc == OK and (sl.frame, sl.measured) == (0, 1), k, "get_scan of frame 0 after the switch-off", rc, sl.frame, sl.measured)
 
 
 @pytest.mark.parametrize("kind", ["ctx", "group"])
