@@ -1,5 +1,5 @@
 // sdrx.hip -- host side of libsdrx.so: the C ABI of include/sdrx.h, VFO-tree bookkeeping,
-// HBM layout, and the per-frame launch sequence.  The arithmetic lives in kernels.hip.
+// HBM layout, and the per-frame launch sequence.  The arithmetic lives in the files kernels.hip includes.
 //
 // Data layout in HBM (all in one arena, zeroed at finalize == the reference's zero start state):
 //   per VFO   NCO checkpoints  (L/16+1) cf32           cp[j] = table[16j-1]
@@ -934,16 +934,11 @@ int sdrx_get_raw(sdrx_ctx *c, float *out, int max_complex, int *n_ret)
         HIPCHK(c, hipMemcpy(b.data(), c->d_raw_u8[(c->frame_no - 1) & 1ull], b.size(), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < b.size(); ++i)
             out[i] = (float)((int)b[i] - 127);
-    } else { // tile layout (the DC-bias kernels wrote it): unit (chunk, i2, lane) = samples 16 lane + 2 i2, +1
+    } else { // tile layout (the DC-bias kernels wrote it)
         const size_t total = align_up((size_t)c->root_frame, kChunk);
         std::vector<float2> t(total);
         HIPCHK(c, hipMemcpy(t.data(), c->d_raw_tiled, total * sizeof(float2), hipMemcpyDeviceToHost));
-        for (int g = 0; g < n; ++g) {
-            const int ch = g >> 10, r = g & 1023, ln = r >> 4, i = r & 15;
-            const float2 v = t[(size_t)ch * 1024 + (size_t)(i >> 1) * 128 + (size_t)ln * 2 + (size_t)(i & 1)];
-            out[2 * g] = v.x;
-            out[2 * g + 1] = v.y;
-        }
+        untile(t.data(), out, n);
     }
     if (n_ret)
         *n_ret = n;
@@ -983,11 +978,7 @@ int sdrx_get_stream(sdrx_ctx *c, int id, float *out, int max_complex, int *n_ret
             const size_t total = align_up((size_t)n.n_f, kChunk);
             std::vector<float2> tmp(total);
             HIPCHK(c, hipMemcpy(tmp.data(), c->arena + n.off_stream[par], sizeof(float2) * total, hipMemcpyDeviceToHost));
-            float2 *o = reinterpret_cast<float2 *>(out);
-            for (int g = 0; g < cnt; ++g) {
-                const int ch = g >> 10, r = g & 1023, ln = r >> 4, i = r & 15;
-                o[g] = tmp[(size_t)ch * 1024 + (size_t)(i >> 1) * 128 + (size_t)ln * 2 + (size_t)(i & 1)];
-            }
+            untile(tmp.data(), out, cnt);
         }
     }
     if (n_ret)

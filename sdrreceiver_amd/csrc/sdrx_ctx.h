@@ -73,7 +73,7 @@ struct LevelPlan {
     std::vector<int64_t> part_bytes;                         // SURVEY 8d share of every level
     int lds_bytes = 0;
     // Option tail_in_levels: k_levels_tail's workgroup list [level n-1 | ... | level 0 | demodulation blocks], each part from a
-    // multiple of 8 workgroups (TailWg, kernels.hip); the demodulation of a frame then rides in the launch after the one that
+    // multiple of 8 workgroups (TailWg, levels.hip); the demodulation of a frame then rides in the launch after the one that
     // finished its last level.  tail = false: k_mix_levels, and k_usb_demod behind the launch that finished the frame.
     bool tail = false;
     size_t off_wgs = 0;
@@ -106,7 +106,7 @@ struct sdrx_ctx {
     int opt_tail_in_levels = 1;
     int opt_meter = 0, opt_squelch = 0, opt_preroll = 0, opt_squelch_auto = 0, opt_park = 0, opt_watch = 0, opt_catchup = 0, opt_agc = 0;
     // option meter: per frame parity, behind the payloads in d_pay / h_pay (at meter_off), one 16-byte MeterAcc record per work
-    // unit that emits payload values (kernels.hip "output meters"); the records travel in the payload copy
+    // unit that emits payload values (meter.hip "output meters"); the records travel in the payload copy
     size_t meter_off = 0;
     int meter_slots = 0;
 

@@ -21,10 +21,35 @@ constexpr int kRawTiled = 0;        // the context's tile-layout copy (an ingest
 constexpr int kRawF32 = 1;          // the caller's cf32 frame, natural order
 constexpr int kRawU8 = 2;           // the dongle's interleaved bytes, natural order
 
+// TILE LAYOUT.  Every cf32 stream that feeds k_mix_decimate is stored in tiles of 1024 samples:
+// tile c is 512 float4 units [i2 = 0..7][lane = 0..63]; unit (i2, lane) holds samples
+// c*1024 + lane*16 + 2*i2 and +1.  A wave then loads its chunk as 8 fully coalesced 1 KiB
+// instructions and every lane ends up with 16 CONSECUTIVE samples in registers -- the shape both
+// the NCO replay and the register-resident half-band stages want -- with no LDS transpose.
+__device__ __forceinline__ size_t tile_unit(int chunk, int i2, int lane) { return (size_t)chunk * 512 + i2 * 64 + lane; }
+// float2 index of natural sample g inside a tile-layout stream; T: the index type the caller computes in (the kernels of
+// mix.hip address with size_t, k_spectrum's and the watch's sample fetch with int)
+template <typename T>
+__host__ __device__ constexpr T tile_index(int g)
+{
+    const int c = g >> 10, r = g & 1023, ln = r >> 4, i = r & 15;
+    return (T)c * 1024 + (i >> 1) * 128 + ln * 2 + (i & 1);
+}
+// host: the first n samples of a tile-layout stream (whole tiles, copied from the device) in natural order, as the getters of
+// include/sdrx.h hand them out: interleaved floats, no alignment asked of `out` beyond a float's
+inline void untile(const float2 *tiled, float *out, int n)
+{
+    for (int g = 0; g < n; ++g) {
+        const float2 v = tiled[tile_index<size_t>(g)];
+        out[2 * g] = v.x;
+        out[2 * g + 1] = v.y;
+    }
+}
+
 struct K2Vfo;
 // ---- mix + half-band cascade (one per VFO) ---------------------------------------------------
 struct K1Vfo {
-    const float2 *in[2];   // input stream in TILE LAYOUT (see kernels.hip) per frame parity
+    const float2 *in[2];   // input stream in TILE LAYOUT (above) per frame parity
     float2 *out[2];        // decimate[d] of this frame, per frame parity (tile layout iff out_tiled)
     const float2 *cp;      // NCO checkpoints: cp[j] = table[16 j - 1], cp[0] = (1,0), cp[L/16] = table[L-1]
     float2 *hb[2];         // half-band history per frame parity: [d][10], entry k-1 = x[-k]
@@ -33,18 +58,18 @@ struct K1Vfo {
     int d;                 // half-band stages
     int L;                 // NCO table length = (int)fs
     int out_tiled;         // 1: children consume the output (tile layout); 0: natural order for the demod
-    // A leaf whose /5 or /6 low-pass (vfo::usb_decimdemod, vfo.cpp:334-387) runs in the mix wave itself (late_item, kernels.hip):
+    // A leaf whose /5 or /6 low-pass (vfo::usb_decimdemod, vfo.cpp:334-387) runs in the mix wave itself (late_item, mix.hip):
     // d == 0, `out` = the DECIMATED stream z' (behind its demodulation history), hb[] = the last kLateHist mixed samples of
     // the previous frame, and the mixed 240 kS/s stream decimate[0] is never written to HBM -- unless it is wanted:
     int late_L;            // 0: not such a leaf; 5 | 6
     int pad_;
     const float *late_taps; // the Nd = LateGeom<L>::kTaps taps of the decimating low-pass
     float2 *tap[2];        // non-null: also keep decimate[0] of this frame here, natural order (sdrx_set_tap, option keep_streams)
-    // Tolerance arithmetic only (option exact = 0; kernels.hip "NCO in the tolerance arithmetic"): rk[j] = u^(j+1), u = the
+    // Tolerance arithmetic only (option exact = 0; nco.hip "NCO in the tolerance arithmetic"): rk[j] = u^(j+1), u = the
     // rotation by the angle of (rot_re, rot_im) at unit modulus, computed in double and stored as floats -- 1 .. 4 steps of
     // the table's recurrence as one rotation, once its amplitude has settled (entries >= kNcoSettle).
     float2 rk[4];
-    // A USB leaf that demodulates in the mix wave itself (demod_chunk, kernels.hip; option fuse_demod): its demodulation
+    // A USB leaf that demodulates in the mix wave itself (demod_chunk, demod.hip; option fuse_demod): its demodulation
     // descriptor.  `out` is then unused -- decimate[d] of such a leaf goes to HBM only through `tap`.
     const K2Vfo *dm;
     // The frame at which this VFO's oscillator started: 0 at finalize, the next frame after sdrx_set_mixer_freqs.  The table

@@ -67,7 +67,7 @@ int fused_late_of(const sdrx_ctx *c, const Node &n)
     return 0;
 }
 
-// Does this leaf demodulate inside its mix wave (demod_chunk, kernels.hip)?  The reference's 48 kS/s sub VFO: two half-band
+// Does this leaf demodulate inside its mix wave (demod_chunk, demod.hip)?  The reference's 48 kS/s sub VFO: two half-band
 // stages below a parent (a tile-layout input, 256 stream samples per 1024-sample chunk), no late decimation, an audio low-pass of
 // at most kDmMaxLpf taps (the 10 kHz filter at 48 kS/s has 47).  Everything else keeps k_usb_demod.
 bool fused_demod_of(const sdrx_ctx *c, const Node &n)
@@ -531,7 +531,7 @@ void build_level_plan(sdrx_ctx *c, Built &B)
     for (const Node &n : c->nodes) {
         if (n.leaf && n.d.demod_usb && !n.fused_demod && n.level != c->n_levels - 1)
             tail = false;
-        if (n.fused_demod && c->opt_meter && c->opt_exact == 1) // (k_levels_tail's exact form does not meter mix items: kernels.hip)
+        if (n.fused_demod && c->opt_meter && c->opt_exact == 1) // (k_levels_tail's exact form does not meter mix items: levels.hip)
             tail = false;
         if (n.fused_demod && (c->opt_preroll || c->opt_agc)) // (its payload of f+1 would be written in the launch in front of the gate
             tail = false;                                    //   of f -- and computed with the gain of f: the step of f runs behind it)

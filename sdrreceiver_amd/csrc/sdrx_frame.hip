@@ -62,7 +62,7 @@ struct Bracket { // RAII: event pair around one launch when timing is on, on the
 
 // The kernel variants this context runs, as compile-time constants: fn(EXACT, ROT, METER, PARK), each a std::bool_constant, from
 // option "exact" -- 1 the exact arithmetic, 0 the tolerance arithmetic (NCO as rotations), 2 the robust one (exact NCO, FMA mixer
-// and filters; kernels.hip, nco_mix) --, option "meter" and option "park".  Every launch of a kernel that has variants goes through
+// and filters; mix.hip, nco_mix) --, option "meter" and option "park".  Every launch of a kernel that has variants goes through
 // here, so these twelve combinations are all that is ever instantiated: there is no (EXACT, ROT) = (1, 1) kernel.
 template <class F>
 void with_variant(const sdrx_ctx *c, F fn)

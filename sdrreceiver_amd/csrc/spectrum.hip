@@ -49,13 +49,6 @@ __device__ __forceinline__ float2 spec_cmul(float2 a, float2 b) // C_MUL, _kiss_
 __device__ __forceinline__ float2 spec_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 spec_sub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
 
-// sample g of a stream in tile layout: unit (chunk, i2, lane) = samples 16 lane + 2 i2, +1
-__device__ __forceinline__ int spec_tiled_index(int g)
-{
-    const int ch = g >> 10, r = g & 1023, ln = r >> 4, i = r & 15;
-    return ch * 1024 + (i >> 1) * 128 + ln * 2 + (i & 1);
-}
-
 // where kf_work's recursion puts input n (factors 4,4,4,4,4,4,2): its base-4 digits d0..d5 (lowest first) reversed, times 2,
 // plus the last radix-2 digit
 __device__ __forceinline__ int spec_digit_rev(int n)
@@ -98,7 +91,7 @@ __device__ __forceinline__ float2 spec_sample(const SpecSource &S, int g)
 {
     if (S.bytes) // floats[b] = b - 127, jonti/sdr.cpp:43-49
         return make_float2((float)((int)S.bytes[2 * g] - 127), (float)((int)S.bytes[2 * g + 1] - 127));
-    return S.src[S.tiled ? spec_tiled_index(g) : g];
+    return S.src[S.tiled ? tile_index<int>(g) : g]; // (tile layout: sdrx_dev.h)
 }
 
 // kiss_fft of the kSpecN windowed samples input(0..kSpecN-1) into F (LDS, natural output order), by one workgroup of

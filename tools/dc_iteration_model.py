@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/dc_iteration_model.py [trials] -- numpy model of how k_dc_chain_spec finds its start values (kernels.hip, dc_spec_blocks;
+"""tools/dc_iteration_model.py [trials] -- numpy model of how k_dc_chain_spec finds its start values (ingest.hip, dc_spec_blocks;
 DESIGN.md section 9.1), used to choose the iteration before it was written as a kernel.
 
 The integer form of the reference's DC recurrence (sdrj.cpp:277-283) around a rounding threshold T is  z' = z + e + [z < 0]

@@ -18,7 +18,7 @@ The register-resident part is straight-line code, so the STATIC counts of a mix/
                  finished alone, first and second chunk of a pair -- with 2 dot products each, the single-chunk tail 1 + 1, the
                  two-chunk tail 2 + 1) = 192 + 4 / 168 + 7 (its frame-end chunks still take the generic stage) / 32 / 32
   d = 2 body:    64 + 32 + 32 + 16 = 144 / 84 / 32 / 32 (no LDS stage)
-Since round 5 mix_item is compiled in those three bodies (kernels.hip, run_item), and the compiler unswitches the any-VFO body's
+Since round 5 mix_item is compiled in those three bodies (mix.hip, run_item), and the compiler unswitches the any-VFO body's
 chunk loop on its loop-invariant output form (tile layout / natural order): it is in the code twice.
 The same kernels also hold the two fused late decimations (late_item<5>, <6>: NCO + mix as above, and 3 x Nd products and
 sums of the decimating low-pass in inline asm):

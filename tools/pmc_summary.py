@@ -44,7 +44,7 @@ PROBE_NAMES = ["fma32", "mul32", "add32", "mul32_sgpr", "pk_mul", "pk_add", "pk_
                "add32_vv"]
 
 # VALU wave-instructions k_mix_decimate issues per 1024-sample chunk of a d = 5 sub VFO, counted in the
-# source (sdrreceiver_amd/csrc/kernels.hip; a packed v_pk_*_f32 on a (re, im) pair counts as ONE):
+# source (sdrreceiver_amd/csrc/mix.hip and nco.hip; a packed v_pk_*_f32 on a (re, im) pair counts as ONE):
 INST_MIX_D5 = {
     "nco_replay": 16 * 7,      # cmul 3 + n*n 1 + (x+y) 1 + (1.95-s) 1 + n*norm 1, per table entry
     "mix": 16 * 3,             # cmul per sample
