@@ -241,6 +241,21 @@ public:
         call("get_watch_psd", sdrx_group_get_watch_psd, sdrx_get_watch_psd, leaf_id, psd.data(), frame);
         return psd;
     }
+    // device-side wake (library option "wake" = 1): watched leaf ids[k] is parked and unparked by the device itself, inside the
+    // frame, by the rule of sdrx.h on its watch figures (cfgs[k].on 0 releases it); between two frames.  Resets the named
+    // leaves' hold_left.  wake(): the decision of the last delivered frame.
+    void set_wake(const std::vector<int> &ids, const std::vector<sdrx_wake_cfg> &cfgs)
+    {
+        if (ids.size() != cfgs.size())
+            throw std::invalid_argument("set_wake: lists of different length");
+        call("set_wake", sdrx_group_set_wake, sdrx_set_wake, ids.data(), cfgs.data(), (int)ids.size());
+    }
+    std::vector<sdrx_wake_state> wake(const std::vector<int> &ids)
+    {
+        std::vector<sdrx_wake_state> out(ids.size());
+        call("get_wake", sdrx_group_get_wake, sdrx_get_wake, ids.data(), (int)ids.size(), out.data());
+        return out;
+    }
     // drift estimate (part of option "watch"): the spectrum of the source of watched leaf `leaf_id` registered against a
     // template over the shifts -max_shift .. max_shift (0: off); templ == nullptr: the next measured frame's spectrum is
     // captured on the device.  drift(): the record of the last delivered frame; drift_hz() turns it into Hz.

@@ -178,6 +178,13 @@ int sdrx_add_vfo(sdrx_ctx *ctx, const sdrx_vfo_desc *desc, int *id_out);
  *            below); 1 implies "meter".  0 changes nothing: the same kernels, launches, device_bytes, payloads and callbacks,
  *            and the AGC calls return SDRX_ESTATE.  With 1 and every hi_ms 0 (the start) every frame is what "meter" = 1 gives;
  *            one more small launch per frame, and the planning rules of "preroll" on "fuse_demod" trees.
+ *   "wake" 0 (default) | 1: the watch unparks and parks leaves itself, inside the frame, on the device (sdrx_set_wake below);
+ *            1 implies "park" and "watch".  0 changes nothing: the same kernels, launches, device_bytes, payloads and
+ *            callbacks, and the wake calls return SDRX_ESTATE.  With 1 and no leaf under control every frame and record is bit
+ *            for bit what "park" = 1 with "watch" = 1 gives, and nothing is allocated and no launch added until the first
+ *            sdrx_set_wake that switches a leaf on.  What 1 costs in the launch plan: with "pipeline" = 1 the levels of a frame
+ *            wait for the tail of the frame before (the two-stream overlap is lost); "tail_in_levels" is not used; a tree with
+ *            a leaf off its last level runs one launch per level instead of the software pipeline.
  *   "dc_blocked_scan" 0|1 (default 0): how sdrx_process_u8 removes the DC bias.  0 = the
  *                 reference's sequentially rounded fp32 recurrence, bit for bit (below).  1 = the same linear filter as a
  *                 blocked parallel scan (~15 us): the true IIR response.  The reference's recurrence
@@ -680,6 +687,62 @@ int sdrx_set_scan(sdrx_ctx *ctx, int leaf_id, const sdrx_scan_cfg *cfg);
 int sdrx_get_scan(sdrx_ctx *ctx, int leaf_id, sdrx_scan_level *out);
 int sdrx_get_scan_hits(sdrx_ctx *ctx, int leaf_id, sdrx_scan_hit *hits, int max_hits, int *n, int64_t *frame);
 int sdrx_get_scan_cells(sdrx_ctx *ctx, int leaf_id, double *cells /* C */, int64_t *frame);
+
+/* Device-side wake (option "wake" = 1): the watch decides on the device, for frame f from the source's spectrum of frame f,
+ * whether a leaf runs in frame f -- no host between two frames, in every launch form (sdrx_process*, frames in flight through
+ * sdrx_submit*, frames queued with sdrx_process_device), parent-less leaves included.  The reference has no counterpart: this
+ * text is the definition.  No default threshold, contrast or hold time is offered (the stance of the squelch, the AGC and the
+ * scan).
+ *
+ * Per controlled leaf the device keeps hold_left, 0 after every sdrx_set_wake that names the leaf.  THE RULE runs for every frame
+ * f the context processes, for every controlled leaf, on the leaf's own watch record of frame f -- b = band_pwr, t = total_pwr,
+ * n = n_bins, N = 8192 -- in IEEE double, one rounding per operation, no contraction:
+ *     c_ok = contrast_q8 == 0
+ *            || (n < N && fl(b * (double)(256 * (N - n))) >= fl(fl(t - b) * (double)((uint64)contrast_q8 * n)))
+ *     hot  = b >= min_band_pwr && c_ok               (a NaN is not hot; both integer factors are exact in double)
+ *     hot:                 hold_left = hold_frames;  active(f) = 1
+ *     else if hold_left>0: hold_left -= 1;           active(f) = 1
+ *     else:                                          active(f) = 0
+ * c_ok is `contrast >= contrast_q8 / 256` (contrast: the band's power density over the density outside it) without the
+ * division.  The decision is bit for bit this rule applied to the figures sdrx_get_watch reports for that leaf and frame;
+ * band_pwr itself keeps its summation bound ("Channel watch" above).
+ *
+ * A leaf with active(f) = 1 that was parked in f-1 is a new vfo from frame f on, as an unparked leaf in "Parking" without
+ * catch-up: the oscillator starts fresh at sample 0 of frame f, every state region is zero, the gate state is that of
+ * sdrx_finalize (hang_left 0, prev_open 1, no floor observation), the AGC's quiet_run is 0; the gain and the mixer are what the
+ * device holds.  No oscillator replay: a wake does not change the frequency, the checkpoints stand.  A leaf with active(f) = 0
+ * is parked in f exactly as "Parking" defines a parked frame; a leaf that stays active continues.  Control starts with the
+ * next frame: an active leaf with a cold band is parked by it.
+ *
+ * Whether a controlled leaf ran in a frame is a device result: sdrx_get_output / sdrx_get_preroll length 0 and no callback,
+ * SDRX_ENOSTREAM from sdrx_get_stream / sdrx_get_prequant, the zero meter, n_open without "squelch" and sdrx_get_active answer
+ * from the wake record of that frame.  The record travels with the fixed-size part of the frame, beside the watch records.
+ *
+ * sdrx_set_wake is batched and atomic, with the calling rules and check order of sdrx_set_agc (between frames; the software
+ * pipeline drains first).  SDRX_EINVAL with nothing changed: a leaf that is not watched; a leaf with an enabled spectrum; `on`
+ * not 0 or 1; a non-finite or negative min_band_pwr; a non-zero reserved word.  on = 0 releases the leaf: it stays in the state
+ * its last frame ran in, and sdrx_set_active works on it again.  While a leaf is controlled, sdrx_set_active,
+ * sdrx_set_watch(.., 0) and sdrx_set_spectrum(id, 1) on it are SDRX_EINVAL with nothing changed; sdrx_set_mixer_freqs (the watch
+ * band follows), sdrx_set_gains, sdrx_set_squelch*, sdrx_set_agc and the taps keep working.  "catchup" composes: it concerns
+ * only leaves the host unparks.  sdrx_get_wake has the calling rules of sdrx_get_watch. */
+typedef struct sdrx_wake_cfg {   /* 32 bytes */
+    double   min_band_pwr;       /* finite, >= 0: units of sdrx_watch_level.band_pwr */
+    uint32_t contrast_q8;        /* 0: no contrast condition; else density ratio x 256 */
+    uint32_t hold_frames;        /* frames a leaf stays active after the last hot one */
+    uint32_t on;                 /* 0 | 1: 1 puts the leaf under the device's control */
+    uint32_t reserved[3];        /* must be 0 */
+} sdrx_wake_cfg;
+typedef struct sdrx_wake_state { /* 32 bytes */
+    int64_t  frame;
+    int64_t  since_frame;        /* first frame of the present state */
+    int32_t  active;             /* the state frame `frame` ran in */
+    int32_t  hot;
+    uint32_t hold_left;          /* behind the rule */
+    int32_t  controlled;         /* 0: not under control in that frame -> active / since_frame from the host's bookkeeping, the rest 0 */
+} sdrx_wake_state;
+int sdrx_set_wake(sdrx_ctx *ctx, const int *ids, const sdrx_wake_cfg *cfgs, int n);
+int sdrx_get_wake(sdrx_ctx *ctx, const int *ids, int n, sdrx_wake_state *out);
+
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);
@@ -915,6 +978,10 @@ int sdrx_group_set_scan(sdrx_group *grp, int leaf_id, const sdrx_scan_cfg *cfg);
 int sdrx_group_get_scan(sdrx_group *grp, int leaf_id, sdrx_scan_level *out);
 int sdrx_group_get_scan_hits(sdrx_group *grp, int leaf_id, sdrx_scan_hit *hits, int max_hits, int *n, int64_t *frame);
 int sdrx_group_get_scan_cells(sdrx_group *grp, int leaf_id, double *cells, int64_t *frame);
+/* sdrx_set_wake / sdrx_get_wake with ids of the whole tree (group option "wake" = 1), each id routed to the member that owns
+ * the leaf; `frame` and `since_frame` count the group's frames. */
+int sdrx_group_set_wake(sdrx_group *grp, const int *ids, const sdrx_wake_cfg *cfgs, int n);
+int sdrx_group_get_wake(sdrx_group *grp, const int *ids, int n, sdrx_wake_state *out);
 
 /* sdrx_get_preroll routed to the member that owns the leaf; sdrx_get_preroll_count summed over the members (group option
  * "preroll" = 1). */

@@ -119,6 +119,18 @@ class WatchLevelC(C.Structure):
                 ("n_bins", C.c_int32), ("segments", C.c_int32), ("watched", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class WakeCfgC(C.Structure):
+    """struct sdrx_wake_cfg"""
+    _fields_ = [("min_band_pwr", C.c_double), ("contrast_q8", C.c_uint32), ("hold_frames", C.c_uint32), ("on", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+class WakeStateC(C.Structure):
+    """struct sdrx_wake_state"""
+    _fields_ = [("frame", C.c_int64), ("since_frame", C.c_int64), ("active", C.c_int32), ("hot", C.c_int32),
+                ("hold_left", C.c_uint32), ("controlled", C.c_int32)]
+
+
 PUBLISH_FN =C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
 
 # every symbol include/sdrx.h declares: (restype, argtypes)
@@ -200,6 +212,10 @@ SYMBOLS = {
     "sdrx_group_get_scan": (_i, [_vp, _i, C.POINTER(ScanLevelC)]),
     "sdrx_group_get_scan_hits": (_i, [_vp, _i, _vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "sdrx_group_get_scan_cells": (_i, [_vp, _i, _vp, C.POINTER(C.c_int64)]),
+    "sdrx_set_wake": (_i, [_vp, _vp, _vp, _i]),
+    "sdrx_get_wake": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_group_set_wake": (_i, [_vp, _vp, _vp, _i]),
+    "sdrx_group_get_wake": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

@@ -30,7 +30,7 @@
 //   k_mix_levels          levels.hip    k_mix_decimate's items of every tree level in one launch (run_item, mix.hip)
 //   k_levels_tail         levels.hip    the same plus k_usb_demod's blocks of the frame that left the last level (option tail_in_levels)
 //   k_compress            compress.hip  vfo::compress, vfo.cpp:389-424
-// (The kernels beside the chain have files of their own, included by sdrx.hip: spectrum.hip, squelch.hip, agc.hip, watch.hip,
+// (The kernels beside the chain have files of their own, included by sdrx.hip: spectrum.hip, squelch.hip, agc.hip, watch.hip, wake.hip,
 // drift.hip, scan.hip.)
 //
 // Execution model: 64-wide wavefronts.  k_mix_decimate runs ONE wave per workgroup and one

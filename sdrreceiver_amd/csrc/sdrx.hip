@@ -33,6 +33,7 @@
 #include "squelch.hip"
 #include "agc.hip"
 #include "watch.hip"
+#include "wake.hip"
 #include "drift.hip"
 #include "scan.hip"
 #include "tapdesign.h"
@@ -58,6 +59,10 @@ static_assert(sizeof(sdrx_scan_cfg) == 32 && sizeof(ScanCfg) == 32 && offsetof(s
                   sizeof(sdrx_scan_level) == 64 && sizeof(ScanRecord) == 64 && offsetof(sdrx_scan_level, n_hits) == offsetof(ScanRecord, n_hits) &&
                   offsetof(sdrx_scan_level, complete) == offsetof(ScanRecord, complete) && SDRX_SCAN_MAX_HITS == kScanMaxHits,
               "band scan ABI layout");
+static_assert(sizeof(sdrx_wake_cfg) == 32 && sizeof(WakeCfg) == 32 && offsetof(sdrx_wake_cfg, on) == offsetof(WakeCfg, on) && sizeof(sdrx_wake_state) == 32 &&
+                  sizeof(WakeRecord) == 32 && offsetof(sdrx_wake_state, hold_left) == offsetof(WakeRecord, hold_left) &&
+                  offsetof(sdrx_wake_state, controlled) == offsetof(WakeRecord, controlled),
+              "sdrx_wake_cfg / sdrx_wake_state ABI layout");
 
 #include "sdrx_ctx.h"
 
@@ -83,6 +88,7 @@ std::vector<float2> spectrum_tables()
 #include "sdrx_delivery.hip"
 #include "sdrx_watch.hip"
 #include "sdrx_finalize.hip"
+#include "sdrx_wake.hip"
 
 namespace {
 
@@ -158,6 +164,13 @@ void free_device_state(sdrx_ctx *c)
     c->watch = sdrx_ctx::Watch();
     analysis_release(c->drift);
     analysis_release(c->scan);
+    // device-side wake: as before the first sdrx_set_wake
+    dfree(c->wake.d_leaf);
+    dfree(c->wake.d_state);
+    dfree(c->wake.d_list);
+    dfree(c->wake.d_fill);
+    records_free(c->wake.rec);
+    c->wake = sdrx_ctx::Wake();
 }
 
 } // namespace
@@ -294,6 +307,8 @@ int sdrx_set_option(sdrx_ctx *c, const char *name, int value)
         c->opt_catchup = value != 0;
     else if (!strcmp(name, "agc"))
         c->opt_agc = value != 0;
+    else if (!strcmp(name, "wake"))
+        c->opt_wake = value != 0;
     else
         return fail(c, SDRX_EINVAL, "unknown option '%s'", name);
     return SDRX_OK;
@@ -388,6 +403,9 @@ int sdrx_finalize(sdrx_ctx *c)
         return fail(c, SDRX_ESTATE, "sdrx_finalize: no VFOs");
     HIPCHK(c, hipSetDevice(c->device));
     const int asked_squelch = c->opt_squelch, asked_meter = c->opt_meter, asked_preroll = c->opt_preroll, asked_park = c->opt_park;
+    const int asked_watch = c->opt_watch;
+    if (c->opt_wake) // the device parks and unparks the leaves the watch measures
+        c->opt_park = c->opt_watch = 1;
     if (c->opt_catchup) // the caught-up frame of an unparked leaf leaves through the pre-roll path
         c->opt_park = c->opt_preroll = 1;
     if (c->opt_preroll || c->opt_squelch_auto) // the pre-roll and the floor tracking are the gate's
@@ -406,6 +424,7 @@ int sdrx_finalize(sdrx_ctx *c)
         c->opt_meter = asked_meter;
         c->opt_preroll = asked_preroll;
         c->opt_park = asked_park;
+        c->opt_watch = asked_watch;
     }
     return rc;
 }
@@ -428,7 +447,7 @@ int spectrum_rebuild(sdrx_ctx *c)
             const auto tap = c->taps.find(id);
             if (n.level != lv || !c->spec.slots[(size_t)id].on || (!n.has_stream && tap == c->taps.end()))
                 continue;
-            if (c->park.parked_at(id, c->frame_no)) // a parked leaf writes no stream: no update (its display state stays)
+            if (leaf_parked_at(c, id, c->frame_no)) // a parked leaf writes no stream: no update (its display state stays)
                 continue;
             SpecDesc e;
             memset(&e, 0, sizeof e);
@@ -691,49 +710,17 @@ int apply_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
         const bool catch_up = c->opt_catchup && active[k] && nd.d.parent_id >= 0 && c->frame_no >= 1 && K.parked_at(id, c->frame_no - 1);
         if (catch_up)
             caught.push_back(id);
-        const unsigned v = (unsigned)active[k];
-        fill(K.d_act + id, 1, v);
-        for (int it : K.items[(size_t)id]) // (k_mix_levels / k_levels_tail: the flag rides in the item's level word)
-            fill(reinterpret_cast<int *>(c->arena + c->fp.off_item_level) + it, 1, (unsigned)nd.level | (v ? 0u : (unsigned)kParkBit));
-        if (nd.d2a_index >= 0)
-            fill(K.d_act + K.o_2a + nd.d2a_index, 1, v);
-        if (nd.d2_index >= 0)
-            fill(K.d_act + K.o_2 + nd.d2_index, 1, v);
-        if (nd.d3_index >= 0)
-            fill(K.d_act + K.o_3 + nd.d3_index, 1, v);
-        if (nd.d4_index >= 0)
-            fill(K.d_act + K.o_4 + nd.d4_index, 1, v);
-        const int sq = c->opt_squelch ? c->sq.index[(size_t)id] : -1; // (without the gate nothing reads its words)
-        if (sq >= 0)
-            fill(K.d_act + K.o_sq + sq, 1, v);
+        // the leaf's flag words; for a leaf that is unparked also what makes it a new vfo (caught up: no gate ran on K-1, and
+        // the gate of K finds the leaf "closed before")
+        leaf_regions(c, id, catch_up ? 0u : 1u, [&](void *ptr, size_t words, unsigned v_on, unsigned v_off, bool wake_only) {
+            if (active[k])
+                fill(ptr, words, v_on);
+            else if (!wake_only)
+                fill(ptr, words, v_off);
+        });
         any_spectrum |= !c->spec.slots.empty() && c->spec.slots[(size_t)id].on;
         if (!active[k])
             continue;
-        // the leaf starts as vfo::init leaves a new vfo: every history zero, in both parities (whichever the next frame reads)
-        const bool late = nd.d.demod_usb && nd.d.late_decimate > 0;
-        const size_t hist = nd.fused_late == 5 ? (size_t)late_hist<5>() : nd.fused_late == 6 ? (size_t)late_hist<6>() : (size_t)std::max(1, nd.d.decimate_count * kHbHist);
-        for (int p = 0; p < 2; ++p) {
-            fill(c->arena + nd.off_hb[p], 2 * hist, 0);
-            if (nd.fused_demod)
-                fill(c->arena + nd.off_dstate[p], 256, 0);
-            if (nd.has_stream)
-                fill(c->arena + nd.off_stream[p], 2 * (size_t)nd.Hx, 0);
-            if (late)
-                fill(c->arena + nd.off_z[p], 2 * (size_t)nd.H, 0);
-            if (nd.long_lpf)
-                fill(c->arena + nd.off_u[p], (size_t)nd.Hu, 0);
-        }
-        if (sq >= 0) { // the gate state of sdrx_finalize; thresholds, hang time, ratio and window stay
-            fill(c->sq.d_hang + sq, 1, 0);
-            if (c->opt_preroll) // (caught up: no gate ran on K-1, and the gate of K finds the leaf "closed before")
-                fill(c->sq.d_prev + sq, 1, catch_up ? 0u : 1u);
-            if (c->opt_squelch_auto) {
-                fill(c->sq.d_auto + sq, 4, 0xffffffffu); // cur_min = prev_min = NONE
-                fill(reinterpret_cast<unsigned *>(c->sq.d_auto + sq) + 4, 1, 0); // age
-            }
-        }
-        if (c->opt_agc && c->agc.slot[(size_t)id] >= 0) // the gain stays what the device holds; the cold run starts again
-            fill(c->agc.d_quiet + c->agc.slot[(size_t)id], 1, 0);
         RetuneJob J;
         memset(&J, 0, sizeof J);
         J.kind = kJobRetune;
@@ -854,7 +841,10 @@ extern "C" {
 
 int sdrx_set_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
 {
-    const int rc = leaf_call(c, "sdrx_set_active", &sdrx_ctx::opt_park, "park", ids, active != nullptr, n, kBetweenFrames, [&](int k) { return bad_switch(active[k]); });
+    const int rc = leaf_call(c, "sdrx_set_active", &sdrx_ctx::opt_park, "park", ids, active != nullptr, n, kBetweenFrames, [&](int k) {
+        const char *why = bad_if_controlled(c, ids[k]);
+        return why ? why : bad_switch(active[k]);
+    });
     return rc || n == 0 ? rc : apply_active(c, ids, active, n);
 }
 
@@ -869,6 +859,20 @@ int sdrx_get_active(sdrx_ctx *c, const int *ids, int n, sdrx_active_state *out)
         if (!c->park.leaf.empty()) {
             s.active = c->park.leaf[(size_t)ids[k]].active;
             s.since_frame = (int64_t)c->park.leaf[(size_t)ids[k]].since;
+        }
+        // a leaf under wake control: the state its newest frame ran in is a device result -- of the last frame, or with frames
+        // in flight of the delivered one
+        WakeRecord r;
+        if (c->wake.controlled(ids[k]) && c->frame_no > 0) {
+            bool have = false;
+            if (c->in_flight > 0)
+                have = c->host_slot >= 0 && wake_record(c, ids[k], c->host_frame, &r);
+            else if (hipSetDevice(c->device) == hipSuccess && drain(c) == SDRX_OK)
+                have = wake_record(c, ids[k], c->frame_no - 1, &r);
+            if (have) {
+                s.active = r.active;
+                s.since_frame = r.since_frame;
+            }
         }
         out[k] = s;
     }
@@ -959,7 +963,7 @@ int sdrx_get_stream(sdrx_ctx *c, int id, float *out, int max_complex, int *n_ret
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = drain(c))
         return rc;
-    if (c->park.parked_at(id, c->frame_no - 1))
+    if (leaf_parked_at(c, id, c->frame_no - 1))
         return fail(c, SDRX_ENOSTREAM, "sdrx_get_stream: vfo %d was parked in frame %llu (sdrx_set_active)", id, c->frame_no - 1);
     const auto tap = c->taps.find(id);
     if (!n.has_stream && !(tap != c->taps.end() && c->frame_no > tap->second.since))
@@ -1000,6 +1004,8 @@ int sdrx_set_spectrum(sdrx_ctx *c, int id, int enable)
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = drain(c)) // frames inside the software pipeline finish under the spectra they were queued with
         return rc;
+    if (enable && id >= 0 && c->wake.controlled(id))
+        return fail(c, SDRX_EINVAL, "sdrx_set_spectrum: vfo %d is under the device's wake control (sdrx_set_wake)", id);
     const int slot = id < 0 ? N : id;
     if (c->spec.slots.empty()) { // the first spectrum: tables (the reference's own double expressions) and per-slot records
         const std::vector<float2> tab = spectrum_tables();
@@ -1114,12 +1120,12 @@ int sdrx_get_prequant(sdrx_ctx *c, int id, float *out, int max, int *n_ret)
         return fail(c, SDRX_ESTATE, "sdrx_get_prequant: set option keep_prequant=1 before finalize; USB leaves only");
     if (c->in_flight > 0)
         return fail(c, SDRX_ESTATE, "sdrx_get_prequant: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
-    if (c->frame_no > 0 && c->park.parked_at(id, c->frame_no - 1))
-        return fail(c, SDRX_ENOSTREAM, "sdrx_get_prequant: vfo %d was parked in frame %llu (sdrx_set_active)", id, c->frame_no - 1);
     const int cnt = std::min(max, n.n_out);
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = drain(c))
         return rc;
+    if (c->frame_no > 0 && leaf_parked_at(c, id, c->frame_no - 1))
+        return fail(c, SDRX_ENOSTREAM, "sdrx_get_prequant: vfo %d was parked in frame %llu (sdrx_set_active)", id, c->frame_no - 1);
     if (out && cnt > 0)
         HIPCHK(c, hipMemcpy(out, c->arena + n.off_preq, sizeof(float) * (size_t)cnt, hipMemcpyDeviceToHost));
     if (n_ret)
@@ -1185,7 +1191,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->exact = c->opt_exact;
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq.bytes + sizeof(int) * c->park.words + c->watch.bytes + c->drift.bytes + c->scan.bytes + c->agc.bytes);
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq.bytes + sizeof(int) * c->park.words + c->watch.bytes + c->drift.bytes + c->scan.bytes + c->agc.bytes + c->wake.bytes);
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

@@ -104,7 +104,7 @@ struct sdrx_ctx {
     int opt_exact = 1, opt_prequant = 0, opt_segments = 0, opt_dc_blocked = 0, opt_pipeline = 0, opt_dc_speculative = 1;
     int opt_fuse = 1, opt_frame_pipeline = 1, opt_fuse_late = 1, opt_keep_streams = 0, opt_fuse_demod = 0;
     int opt_tail_in_levels = 1;
-    int opt_meter = 0, opt_squelch = 0, opt_preroll = 0, opt_squelch_auto = 0, opt_park = 0, opt_watch = 0, opt_catchup = 0, opt_agc = 0;
+    int opt_meter = 0, opt_squelch = 0, opt_preroll = 0, opt_squelch_auto = 0, opt_park = 0, opt_watch = 0, opt_catchup = 0, opt_agc = 0, opt_wake = 0;
     // option meter: per frame parity, behind the payloads in d_pay / h_pay (at meter_off), one 16-byte MeterAcc record per work
     // unit that emits payload values (meter.hip "output meters"); the records travel in the payload copy
     size_t meter_off = 0;
@@ -167,7 +167,8 @@ struct sdrx_ctx {
     // Option park (sdrx_set_active): one flag word per descriptor of every kernel that works on a leaf, in one
     // device array -- [K1Vfo: per node | K2aVfo | K2Vfo | K3Vfo | K4Vfo | the gate: per leaf in publish order] -- 1 = active.
     // The host's copy of a leaf's state is what the getters and the delivery serve: a frame f >= since ran in state `active`,
-    // the frames before it (the last one may not be fetched yet) in state `was_active`.
+    // the frames before it (the last one may not be fetched yet) in state `was_active`.  (A leaf under option wake's control is the
+    // exception: the device decides, and the answers come from the frame's wake record -- leaf_parked_at, sdrx_delivery.hip.)
     struct Park {
         int *d_act = nullptr;
         size_t o_2a = 0, o_2 = 0, o_3 = 0, o_4 = 0, o_sq = 0, words = 0;
@@ -247,6 +248,7 @@ struct sdrx_ctx {
         std::vector<int> src_ids;        // the measured sources in launch order: -1 the raw frame, else the parent's node id
         std::vector<size_t> src_psd;     // ... where each one's PSD lies in d_data
         std::vector<int> seg_begin, leaf_begin; // per source group (0: the raw frame, 1 + l: parents on tree level l), n_levels + 2 entries
+        std::vector<WatchLeaf> launch_leaves;   // the host's copy of the WatchLeaf list (what option wake's launch list is cut from)
         unsigned long long psd_since = 0; // the PSD buffers hold a frame only once frame_no > psd_since
         WatchSrc *d_src() const { return reinterpret_cast<WatchSrc *>(d_desc); }
         WatchSeg *d_seg() const { return reinterpret_cast<WatchSeg *>(d_desc + sizeof(WatchSrc) * (size_t)n_src_slots); }
@@ -284,6 +286,29 @@ struct sdrx_ctx {
         std::vector<ScanCfg> cfg; // per source index: the setting that last switched it on
         ScanSrc *d_src() const { return reinterpret_cast<ScanSrc *>(d_desc); }
     } scan;
+
+    // Option wake (sdrx_set_wake, wake.hip): the leaves the device parks and unparks itself.  `ctl` says per leaf
+    // whether it is under control (a Switched); for a frame it is, whether the leaf ran is a device result -- the wake record of
+    // that frame (`rec`, one slot per leaf: the watch's slots), not Park::leaf (leaf_parked_at, sdrx_delivery.hip).  Everything on
+    // the device is allocated by the first sdrx_set_wake that switches a leaf on: the static table and the state per watch slot,
+    // the launch list (the controlled leaves in the order of the watch's own list, `begin` per source group as
+    // Watch::leaf_begin) and the fill lists of the controlled leaves (leaf_regions, sdrx_wake.hip).
+    struct Wake {
+        std::vector<Switched> ctl;      // per node; sized by the first sdrx_set_wake
+        std::vector<sdrx_wake_cfg> cfg; // per node: the settings as set
+        int n_ctl = 0;                  // leaves under control
+        WakeLeaf *d_leaf = nullptr;
+        WakeState *d_state = nullptr;
+        int *d_list = nullptr;
+        WakeFill *d_fill = nullptr;
+        size_t fill_cap = 0;            // entries d_fill holds
+        std::vector<WakeLeaf> h_leaf;   // host copy of d_leaf
+        Records rec;                    // WakeRecord per watch slot
+        size_t bytes = 0;               // device memory the option holds
+        std::vector<int> begin;         // first launch entry per source group, n_levels + 2 entries
+        bool controlled(int id) const { return !ctl.empty() && ctl[(size_t)id].v != 0; }
+        bool controlled_at(int id, unsigned long long frame) const { return !ctl.empty() && ctl[(size_t)id].at(frame) != 0; }
+    } wake;
 
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first

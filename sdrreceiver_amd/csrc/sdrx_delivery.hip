@@ -4,13 +4,41 @@
 
 namespace {
 
+// Option wake: the wake record of leaf `id` for frame `frame`, if the leaf was under the device's control in that frame -- from
+// the pinned copy that travelled with the delivered frame, else one small device read (the caller has seen that frame's
+// kernels end: a delivered frame, or a drained context).  false: not controlled then, or the record is no longer that frame's.
+bool wake_record(const sdrx_ctx *c, int id, unsigned long long frame, WakeRecord *out)
+{
+    const sdrx_ctx::Wake &K = c->wake;
+    if (!K.controlled_at(id, frame) || !K.rec.d[0])
+        return false;
+    const int slot = c->watch.leaf[(size_t)id].slot, p = (int)(frame & 1ull);
+    if (c->host_slot == p && c->host_frame == frame) {
+        *out = K.rec.host<WakeRecord>(p)[slot];
+        if (out->controlled && out->frame == (long long)frame)
+            return true;
+    }
+    if (hipMemcpy(out, K.rec.dev<WakeRecord>(p) + slot, sizeof *out, hipMemcpyDeviceToHost) != hipSuccess)
+        return false;
+    return out->controlled && out->frame == (long long)frame;
+}
+// Was leaf `id` parked in frame `frame`: a device result for a leaf under wake control, else the host's bookkeeping of
+// sdrx_set_active.  Every answer the host gives about a parked frame comes through here.
+bool leaf_parked_at(const sdrx_ctx *c, int id, unsigned long long frame)
+{
+    WakeRecord r;
+    if (wake_record(c, id, frame, &r))
+        return !r.active;
+    return c->park.parked_at(id, frame);
+}
+
 // Leaf `id`'s payload of the delivered frame in host slot `slot`.  Option squelch: through the delivered directory -- a closed
 // leaf has *len = 0 (the pointer is valid and not to be read).  Option park: so has a leaf that was parked in that frame.
 const unsigned char *leaf_payload(const sdrx_ctx *c, int id, int slot, uint32_t *len)
 {
     const Node &n = c->nodes[(size_t)id];
     *len = n.pay_len;
-    if (c->park.parked_at(id, c->host_frame)) {
+    if (leaf_parked_at(c, id, c->host_frame)) {
         *len = 0;
         return c->h_pay[slot];
     }
@@ -30,7 +58,7 @@ const unsigned char *leaf_payload(const sdrx_ctx *c, int id, int slot, uint32_t 
 const unsigned char *leaf_preroll(const sdrx_ctx *c, int id, int slot, uint32_t *len)
 {
     *len = 0;
-    if (!c->opt_preroll || c->park.parked_at(id, c->host_frame))
+    if (!c->opt_preroll || leaf_parked_at(c, id, c->host_frame))
         return c->h_pay[slot];
     const size_t k = (size_t)c->sq.index[(size_t)id];
     if (c->sq.offs[k] == kSqClosed || !c->sq.pre[k])
@@ -78,10 +106,10 @@ void publish_all(sdrx_ctx *c, int slot)
 // Both only read d_pay[p], d_pack[p] and the directory, whose next writer is frame f+2 (the safety argument above
 // enqueue_frame, sdrx_frame.hip).
 // Option watch: the records of the frame of parity p, part of what always travels -- the watch's, then the drift's and the band
-// scan's of its sources (each: nothing before the first call that switched one on)
+// scan's of its sources, and option wake's of the controlled leaves (each: nothing before the first call that switched one on)
 int queue_watch(sdrx_ctx *c, int p, hipStream_t st)
 {
-    for (const sdrx_ctx::Records *r : {&c->watch.rec, &c->drift.rec, &c->scan.rec})
+    for (const sdrx_ctx::Records *r : {&c->watch.rec, &c->drift.rec, &c->scan.rec, &c->wake.rec})
         if (r->d[p])
             HIPCHK(c, hipMemcpyAsync(r->h[p], r->d[p], r->bytes, hipMemcpyDeviceToHost, st));
     return SDRX_OK;
@@ -400,7 +428,7 @@ int sdrx_get_meters(sdrx_ctx *c, const int *ids, int n, sdrx_meter *out)
         sdrx_meter m;
         memset(&m, 0, sizeof m);
         m.frame = (int64_t)c->host_frame;
-        if (c->park.parked_at(ids[k], c->host_frame)) { // no value: nothing wrote the leaf's records in that frame
+        if (leaf_parked_at(c, ids[k], c->host_frame)) { // no value: nothing wrote the leaf's records in that frame
             out[k] = m;
             continue;
         }
@@ -583,7 +611,7 @@ int sdrx_get_egress(sdrx_ctx *c, int64_t *frame, uint32_t *n_open, uint32_t *n_l
         *n_leaves = leaves;
     uint32_t n_active = leaves;
     for (int i : c->publish_order)
-        n_active -= c->park.parked_at(i, c->host_frame);
+        n_active -= leaf_parked_at(c, i, c->host_frame);
     if (n_open)
         *n_open = c->opt_squelch ? c->sq.n_open : n_active;
     if (payload_bytes_copied)

@@ -493,6 +493,12 @@ void build_level_plan(sdrx_ctx *c, Built &B)
     for (const Node &n : c->nodes)
         if ((c->opt_preroll || c->opt_agc) && n.fused_demod && n.level != c->n_levels - 1)
             P.usable = false;
+    // Option wake: the wake step of a frame, behind the watch of the leaf's source, must sit behind the leaf tail of the frame
+    // before and in front of the leaf's own items.  In a step of the software pipeline that order exists only for leaves on the
+    // last level (the argument above enqueue_frame): any other tree runs one launch per level.
+    for (const Node &n : c->nodes)
+        if (c->opt_wake && n.leaf && n.level != c->n_levels - 1)
+            P.usable = false;
     if (!P.usable)
         return;
     // deepest level first: in the steady state of the reference's two-level trees the long sub-VFO
@@ -527,7 +533,7 @@ void build_level_plan(sdrx_ctx *c, Built &B)
     // f + n_levels + 1); compress reads its streams there too, as without the option.  Leaves that demodulate in their mix
     // wave (fuse_demod) have no blocks here.  One-level trees have no k_mix_levels launch to ride in (see above).
     const auto dm_launch = std::find_if(c->lb.begin(), c->lb.end(), [](const LaunchB &L) { return L.kind == KIND_DEMOD; });
-    bool tail = c->opt_tail_in_levels && dm_launch != c->lb.end();
+    bool tail = c->opt_tail_in_levels && !c->opt_wake && dm_launch != c->lb.end(); // (wake: the demodulation must not ride in the next launch)
     for (const Node &n : c->nodes) {
         if (n.leaf && n.d.demod_usb && !n.fused_demod && n.level != c->n_levels - 1)
             tail = false;

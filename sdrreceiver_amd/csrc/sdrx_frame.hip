@@ -155,6 +155,17 @@ void watch_launch_groups(sdrx_ctx *c, hipStream_t st, int g_lo, int g_hi, const 
     const int per = kWatchLeafThreads / 64;
     hipLaunchKernelGGL(k_watch_bands, dim3((l1 - l0 + per - 1) / per), dim3(kWatchLeafThreads), 0, st, W.d_src(), W.d_leaf() + l0, l1 - l0, A,
                        W.rec.dev<WatchRecord>(0), W.rec.dev<WatchRecord>(1));
+    // option wake: one k_watch_wake workgroup per leaf of those sources that is under the device's control, on the records
+    // k_watch_bands has just left -- the decision for the frame those sources hold, and on a change of state the leaf's flag
+    // words and state regions (where this call sits in the frame: the argument above enqueue_frame).  Nothing before the first
+    // sdrx_set_wake that switched a leaf on; not bracketed either.
+    const sdrx_ctx::Wake &K = c->wake;
+    if (K.n_ctl > 0) {
+        const int w0 = K.begin[(size_t)g_lo], w1 = K.begin[(size_t)g_hi + 1];
+        if (w1 > w0)
+            hipLaunchKernelGGL(k_watch_wake, dim3(w1 - w0), dim3(kWakeThreads), 0, st, W.d_src(), K.d_leaf, K.d_state, K.d_list + w0, K.d_fill, A,
+                               W.rec.dev<WatchRecord>(0), W.rec.dev<WatchRecord>(1), K.rec.dev<WakeRecord>(0), K.rec.dev<WakeRecord>(1));
+    }
     // drift estimate: one k_watch_drift workgroup per (source of those groups with a template, block of shifts), on the PSD
     // k_watch_psd has just left.  Nothing before the first sdrx_set_drift; not bracketed either.
     const sdrx_ctx::Drift &D = c->drift;
@@ -381,7 +392,8 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
     }
     if (hi >= 0) {
         spectrum_launch(c, c->st.stream, lo, hi, 0, A.frame_level);
-        watch_launch(c, c->st.stream, lo, hi, 0, A.frame_level);
+        if (!c->opt_wake) // (option wake: behind the leaf tail below -- the argument above enqueue_frame)
+            watch_launch(c, c->st.stream, lo, hi, 0, A.frame_level);
     }
     if (dm)
         c->pipe.erase(c->pipe.begin());
@@ -398,6 +410,9 @@ int pipeline_step(sdrx_ctx *c, bool have_new, const void *raw, int raw_mode)
             c->pipe.erase(c->pipe.begin());
         }
     }
+    if (hi >= 0 && c->opt_wake) // the watch of the streams this step wrote, with its wake: behind the tail, gate and step of the
+                                // frame that has just left the last level, in front of the next step's launch
+        watch_launch(c, c->st.stream, lo, hi, 0, A.frame_level);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return fail(c, SDRX_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
@@ -473,14 +488,42 @@ int pipeline_flush(sdrx_ctx *c)
 //       - pipeline_flush runs every step still outstanding behind its gate, in frame order; sdrx_set_gains, sdrx_set_agc and
 //         sdrx_set_active drain first, and their job kernels run on `stream` behind everything.  The catch-up of frame K-1
 //         (sdrx_set_active) launches no step: the leaf was parked in K-1, which is no observation.
+//   * option wake: the wake step of frame f for a leaf (k_watch_wake, behind k_watch_bands on the leaf's source: wherever
+//     watch_launch_groups is called) WRITES the leaf's flag words (Park::d_act, item_level[]), and when the leaf wakes its state
+//     regions of both parities, its gate words (hang_left, prev_open, the floor record), quiet_run and K1Vfo::origin.  The source
+//     of frame f is complete before the leaf's own mix items of f run, so the step can sit -- and must sit -- in two places at
+//     once: BEHIND every launch that reads one of those words for frame f-1 (the leaf's mix items, block kernels, gate and AGC
+//     step) and IN FRONT of every launch that reads one for frame f.  Flags and origin reach the later launches through the
+//     constant path, as the gains of the AGC step and the jobs of k_vfo_retune do: a kernel boundary on one stream, or an
+//     event between two.  The step's record goes to a buffer of the frame's parity: next writer the step of f+2.  Path by path:
+//       - one launch per level, one stream: the raw watch with its wake stays in front of level 0 (watch_raw_step: the
+//         parent-less leaves run in level 0), and the watch of level l's streams, with its wake, comes directly behind level l's
+//         launch -- in front of level l+1, where the children of those streams run.  Everything of f-1 (levels, tail, gate,
+//         step) is in front of all of it, the tail, gate and step of f behind all of it.  The watch_launch at the end has nothing
+//         left; records and PSDs are what they were (the same streams, complete, read by the same kernels);
+//       - two streams (pipe): the tail, gate and step of f-1 on tail_stream read words the wake steps of f write on `stream`:
+//         the levels of f also wait for ev_tail[p ^ 1] (the wait preroll_fused has), for every tree.  The overlap of the tail
+//         with the next frame's levels is lost for this option.  The tail of f waits for ev_levels[p], recorded behind the
+//         last wake step of f;
+//       - pipeline_step with k_mix_levels: step k's launch runs level l of frame k-l; the leaves all sit on the last level
+//         n-1 (build_level_plan: any other tree runs one launch per level under this option), so their sources are the level
+//         n-2 streams, which hold frame k-n+2 behind step k's launch, and their items of that frame run in step k+1's launch.
+//         The watch with its wake therefore goes to the END of the step: behind the block kernels, gate and step of the
+//         frame k-n+1 that has just left the last level (they read the words as the wake of that frame left them), in front of
+//         step k+1's launch.  A one-level tree does not use pipeline_step;
+//       - pipeline_step with k_levels_tail: not used under this option (build_level_plan) -- the demodulation of frame g rides in
+//         the launch that also runs the last level of g+1, one flag word cannot serve both;
+//       - pipeline_flush steps levels that hold a frame; a leaf's source level holds none once its frame has passed, so no
+//         wake step runs twice for a frame.  sdrx_set_wake, sdrx_set_active and the other setters drain first.
 int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
 {
     const int p = (int)(c->frame_no & 1ull);
     const bool pipe = c->opt_pipeline != 0;
     if (pipe && c->st.tail_recorded[p])
         HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.ev_tail[p], 0));
-    if (pipe && (c->opt_preroll || c->opt_agc) && c->sq.preroll_fused && c->st.tail_recorded[p ^ 1]) // the levels write d_pay[p], which the previous gate
-                                                                                                       // reads -- and read the gains its step writes
+    if (pipe && (((c->opt_preroll || c->opt_agc) && c->sq.preroll_fused) || c->opt_wake) && c->st.tail_recorded[p ^ 1])
+        // the levels write d_pay[p], which the previous gate reads -- and read the gains its step writes; option wake: the wake
+        // steps of this frame write the flag words and state regions the previous tail, gate and step read
         HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.ev_tail[p ^ 1], 0));
     spectrum_raw_step(c, raw, raw_mode);
     watch_raw_step(c, raw, raw_mode);
@@ -517,8 +560,11 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         c->pending_fetch = true;
         return SDRX_OK;
     }
-    for (const Launch1 &L : c->l1)
+    for (const Launch1 &L : c->l1) {
         launch_mix_list(c, L, c->frame_no, reinterpret_cast<const K1Work *>(c->arena + L.off_work), L.n_work, raw, raw_mode);
+        if (c->opt_wake) // the watch of the streams this level wrote, with its wake: in front of the level their children run in
+            watch_launch(c, c->st.stream, L.level, L.level, c->frame_no, nullptr);
+    }
     hipStream_t ts = pipe ? c->st.tail_stream : c->st.stream;
     if (pipe) {
         HIPCHK(c, hipEventRecord(c->st.ev_levels[p], c->st.stream));
@@ -529,7 +575,8 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
     squelch_gate(c, ts, c->frame_no);
     agc_step(c, ts, c->frame_no);
     spectrum_launch(c, ts, 0, c->n_levels - 1, c->frame_no, nullptr);
-    watch_launch(c, ts, 0, c->n_levels - 1, c->frame_no, nullptr);
+    if (!c->opt_wake) // (option wake: every level's watch is behind its own launch above)
+        watch_launch(c, ts, 0, c->n_levels - 1, c->frame_no, nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return fail(c, SDRX_EHIP, "kernel launch failed: %s", hipGetErrorString(e));

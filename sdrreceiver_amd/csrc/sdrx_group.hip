@@ -733,7 +733,12 @@ int sdrx_group_get_agc(sdrx_group *g, const int *ids, int n, sdrx_agc_state *out
 
 int sdrx_group_set_active(sdrx_group *g, const int *ids, const int32_t *active, int n)
 {
-    return group_scatter(g, "sdrx_group_set_active", &sdrx_ctx::opt_park, "park", true, ids, active != nullptr, n, [&](int k) { return bad_switch(active[k]); },
+    return group_scatter(g, "sdrx_group_set_active", &sdrx_ctx::opt_park, "park", true, ids, active != nullptr, n,
+                         [&](int k) { // (a leaf under wake control refuses the call: checked for the whole list before any member changes)
+                             const auto w = g->where[(size_t)ids[k]];
+                             const char *why = bad_if_controlled(g->m[(size_t)w.first].c, w.second);
+                             return why ? why : bad_switch(active[k]);
+                         },
                          [&](sdrx_ctx *m, const Part &p) { return sdrx_set_active(m, p.ids.data(), p.pick(active).data(), p.n()); });
 }
 
@@ -749,7 +754,12 @@ int sdrx_group_get_catchup(sdrx_group *g, const int *ids, int n, sdrx_meter *out
 
 int sdrx_group_set_watch(sdrx_group *g, const int *ids, const int32_t *on, int n)
 {
-    return group_scatter(g, "sdrx_group_set_watch", &sdrx_ctx::opt_watch, "watch", true, ids, on != nullptr, n, [&](int k) { return bad_switch(on[k]); },
+    return group_scatter(g, "sdrx_group_set_watch", &sdrx_ctx::opt_watch, "watch", true, ids, on != nullptr, n,
+                         [&](int k) {
+                             const auto w = g->where[(size_t)ids[k]];
+                             const char *why = on[k] ? nullptr : bad_if_controlled(g->m[(size_t)w.first].c, w.second);
+                             return why ? why : bad_switch(on[k]);
+                         },
                          [&](sdrx_ctx *m, const Part &p) { return sdrx_set_watch(m, p.ids.data(), p.pick(on).data(), p.n()); });
 }
 
@@ -798,6 +808,23 @@ int sdrx_group_get_scan_hits(sdrx_group *g, int leaf_id, sdrx_scan_hit *hits, in
 int sdrx_group_get_scan_cells(sdrx_group *g, int leaf_id, double *cells, int64_t *frame)
 {
     return on_owner(g, "sdrx_group_get_scan_cells", leaf_id, true, [&](sdrx_ctx *m, int id) { return sdrx_get_scan_cells(m, id, cells, frame); });
+}
+
+// sdrx_set_wake over the whole tree: every entry is checked against the member that owns its leaf before any member changes
+int sdrx_group_set_wake(sdrx_group *g, const int *ids, const sdrx_wake_cfg *cfgs, int n)
+{
+    return group_scatter(
+        g, "sdrx_group_set_wake", &sdrx_ctx::opt_wake, "wake", true, ids, cfgs != nullptr, n,
+        [&](int k) { // (the ids of entry k have passed the range check when this runs)
+            const auto w = g->where[(size_t)ids[k]];
+            return bad_wake(g->m[(size_t)w.first].c, w.second, cfgs[k]);
+        },
+        [&](sdrx_ctx *m, const Part &p) { return sdrx_set_wake(m, p.ids.data(), p.pick(cfgs).data(), p.n()); });
+}
+
+int sdrx_group_get_wake(sdrx_group *g, const int *ids, int n, sdrx_wake_state *out)
+{
+    return group_gather(g, "sdrx_group_get_wake", ids, n, out, sdrx_get_wake);
 }
 
 int sdrx_group_get_egress(sdrx_group *g, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied)

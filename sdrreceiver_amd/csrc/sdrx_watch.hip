@@ -6,6 +6,8 @@
 
 namespace {
 
+int wake_rebuild(sdrx_ctx *c); // (sdrx_wake.hip: option wake's launch list follows the watch's)
+
 // The band of a leaf in bins of its source's 8192-point spectrum: include/sdrx.h, in IEEE double.
 void watch_band(const sdrx_vfo_desc &d, int *first_bin, int *n_bins)
 {
@@ -355,6 +357,12 @@ int watch_rebuild(sdrx_ctx *c)
         return rc;
     if (int rc = scan_rebuild(c, ids, off_psd)) // (so do the scans' states)
         return rc;
+    const std::vector<WatchLeaf> leaves_before = W.launch_leaves;
+    W.launch_leaves = leaves;
+    if (int rc = wake_rebuild(c)) { // (the controlled leaves' sources and bands)
+        W.launch_leaves = leaves_before;
+        return rc;
+    }
     W.src_ids = ids; // (last: the frame sequence launches from these lists only when everything above succeeded)
     return SDRX_OK;
 }
@@ -418,7 +426,9 @@ extern "C" {
 
 int sdrx_set_watch(sdrx_ctx *c, const int *ids, const int32_t *on, int n)
 {
-    if (int rc = leaf_call(c, "sdrx_set_watch", &sdrx_ctx::opt_watch, "watch", ids, on != nullptr, n, kBetweenFrames, [&](int k) { return bad_switch(on[k]); }))
+    if (int rc = leaf_call(c, "sdrx_set_watch", &sdrx_ctx::opt_watch, "watch", ids, on != nullptr, n, kBetweenFrames, [&](int k) {
+            return !on[k] && c->wake.controlled(ids[k]) ? "is under the device's wake control (sdrx_set_wake)" : bad_switch(on[k]);
+        }))
         return rc;
     if (n == 0)
         return SDRX_OK;

@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, agc as _agc, drift as _drift, meter, scan as _scan, squelch as _squelch, watch as _watch
+from . import _lib, agc as _agc, drift as _drift, meter, scan as _scan, squelch as _squelch, wake as _wake, watch as _watch
 from .topology import Topology, VfoDesc
 
 
@@ -191,6 +191,27 @@ class _LeafCalls:
         self._call("get_watch_psd", int(vid), psd.ctypes.data, C.byref(f))
         return psd, f.value
 
+    # -- device-side wake (option ``wake``; sdrreceiver_amd.wake has the rule): the watch parks and unparks leaves in the frame ----
+    def set_wake(self, vids, min_band_pwr, contrast_q8=0, hold_frames=0, on=1) -> None:
+        """Wake settings of the watched leaves `vids` from the next frame on (``sdrx_wake_cfg``; every argument a scalar or one
+        value per leaf): a leaf is hot when its ``band_pwr`` reaches ``min_band_pwr`` and -- ``contrast_q8`` > 0 -- its contrast
+        reaches ``contrast_q8 / 256``; it runs in hot frames and ``hold_frames`` frames after the last one, and is parked in
+        the others, decided on the device for the very frame that was measured.  ``on`` 0 releases the leaf in the state its
+        last frame ran in.  Restarts the named leaves' ``hold_left``."""
+        ids = np.ascontiguousarray(np.atleast_1d(np.asarray(vids)), dtype=np.int32).reshape(-1)
+        cols = [np.broadcast_to(np.asarray(v, dt), ids.shape) for v, dt in
+                ((min_band_pwr, np.float64), (contrast_q8, np.uint32), (hold_frames, np.uint32), (on, np.uint32))]
+        cfgs = (_lib.WakeCfgC * max(1, ids.size))()
+        for k in range(ids.size):
+            cfgs[k] = _lib.WakeCfgC(float(cols[0][k]), int(cols[1][k]), int(cols[2][k]), int(cols[3][k]))
+        self._call("set_wake", ids.ctypes.data, cfgs, ids.size)
+
+    def wake(self, vids) -> dict:
+        """What the wake step decided for the leaves `vids` in the last delivered frame: ``frame``, ``since_frame``, ``active``,
+        ``hot``, ``hold_left``, ``controlled`` as arrays in the order of `vids` (``controlled`` 0: the leaf was not under the
+        device's control in that frame; ``active`` and ``since_frame`` are then the host's bookkeeping)."""
+        return _wake.wake_dict(self._get_list("get_wake", vids, _lib.WakeStateC)[1])
+
     # -- drift estimate (part of option ``watch``; sdrreceiver_amd.drift): the source's spectrum registered against a template --
     def set_drift(self, vid: int, template=None, max_shift: int = 0) -> None:
         """The drift estimate of the source of watched leaf `vid` from the next frame on, over the shifts ``-max_shift ..
@@ -280,7 +301,7 @@ class Receiver(_LeafCalls):
                  dc_blocks_per_step: int | None = None, fuse_demod: bool = False,
                  tail_in_levels: bool = True, meter: bool = False, squelch: bool = False, preroll: bool = False,
                  squelch_auto: bool = False, park: bool = False, watch: bool = False, catchup: bool = False,
-                 agc: bool = False):
+                 agc: bool = False, wake: bool = False):
         self.L = _lib.lib()
         h = C.c_void_p()
         rc = self.L.sdrx_create(C.byref(h), int(device))
@@ -318,6 +339,8 @@ class Receiver(_LeafCalls):
             self._chk(self.L.sdrx_set_option(self.h, b"catchup", 1))
         if agc:
             self._chk(self.L.sdrx_set_option(self.h, b"agc", 1))
+        if wake:
+            self._chk(self.L.sdrx_set_option(self.h, b"wake", 1))
         self._chk(self.L.sdrx_set_option(self.h, b"dc_speculative", int(bool(dc_speculative))))
         if dc_blocks_per_step is not None:
             self._chk(self.L.sdrx_set_option(self.h, b"dc_blocks_per_step", int(dc_blocks_per_step)))
