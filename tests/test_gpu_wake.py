@@ -120,17 +120,28 @@ def check_frame(rx, scn, w, f, tag, exact=True, keep_streams=True, meter=True, s
                 assert float(np.abs(got - z).max()) <= REL_TOL * float(np.abs(z).max()), (tag, f, i, "stream")
 
 
-def drive(rx, scn, mode, check):
+def drive(rx, scn, mode, check, before=None, fetch_at=None):
     """No control call between the frames.  "process": sdrx_process; "submit": sdrx_submit with two frames in flight; "device":
-    sdrx_process_device queued back to back, fetched only at FETCH_AT."""
+    sdrx_process_device queued back to back, fetched only at `fetch_at` (FETCH_AT).  `before`: frame -> a control call made
+    before that frame, once every frame before it is delivered (a queued run fetches the frame before it)."""
     frames, seen = scn.frames, []
+    before = before or {}
+    fetch_at = FETCH_AT[scn.name] if fetch_at is None else fetch_at
     if mode == "process":
         for f, iq in enumerate(frames):
+            if f in before:
+                before[f]()
             rx.process(iq)
             check(f)
             seen.append(f)
     elif mode == "submit":
         for f, iq in enumerate(frames):
+            if f in before:
+                while rx.in_flight():
+                    rx.wait()
+                    check(len(seen))
+                    seen.append(len(seen))
+                before[f]()
             rx.submit(iq)
             if rx.in_flight() == 2:
                 rx.wait()
@@ -145,8 +156,11 @@ def drive(rx, scn, mode, check):
         dev = [torch.from_numpy(np.array(iq)).cuda() for iq in frames]
         torch.cuda.synchronize()
         for f in range(len(frames)):
+            if f in before:
+                assert seen and seen[-1] == f - 1, (f, "a control call behind an unfetched frame")
+                before[f]()
             rx.process_device(dev[f].data_ptr(), scn.topo.frame)
-            if f in FETCH_AT[scn.name]:
+            if f in fetch_at:
                 rx.fetch()
                 check(f)
                 seen.append(f)

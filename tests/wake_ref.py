@@ -123,6 +123,13 @@ FLAT_MIN = 3e7
 _BUILD = {"watch": _watch_scenario, "deep": _deep_scenario, "flat": _flat_scenario}
 
 
+def register(name: str, build) -> None:
+    """Another scenario under `name` (tests/wake_edges_ref.py's): :func:`scenario`, :func:`sources` and :func:`figures` then
+    serve it as they serve the three above, which stay what they are."""
+    assert _BUILD.get(name, build) is build, name
+    _BUILD[name] = build
+
+
 @functools.lru_cache(maxsize=None)
 def scenario(name: str) -> Scenario:
     return _BUILD[name]()
@@ -174,9 +181,10 @@ def step_hold_decremented_when_hot(cfg, hold_left, band_pwr, total_pwr, n_bins):
     return (active, hot, max(left - 1, 0)) if hot else (active, hot, left)
 
 
-def decide(scn: Scenario, figs, stepper=wake.step, cfgs=None, start=None) -> list:
+def decide(scn: Scenario, figs, stepper=wake.step, cfgs=None, start=None, reset_hold=True) -> list:
     """Per frame: controlled leaf -> dict(frame, since_frame, active, hot, hold_left, controlled) -- the wake records.
-    `cfgs`: frame -> {leaf: Cfg} set before that frame (default: scn.cfgs before frame 0); `start`: leaf -> (active, since)."""
+    `cfgs`: frame -> {leaf: Cfg} set before that frame (default: scn.cfgs before frame 0); `start`: leaf -> (active, since);
+    `reset_hold` False: a wrong device whose sdrx_set_wake leaves hold_left standing."""
     cfgs = {0: scn.cfgs} if cfgs is None else cfgs
     cur: dict = {}
     state = {i: [0 if i in scn.parked0 else 1, 0, 0] for i in scn.topo.leaves_in_publish_order()}  # active, since, hold_left
@@ -186,7 +194,8 @@ def decide(scn: Scenario, figs, stepper=wake.step, cfgs=None, start=None) -> lis
     out = []
     for f, row in enumerate(figs):
         for i, c in cfgs.get(f, {}).items():
-            state[i][2] = 0
+            if reset_hold:
+                state[i][2] = 0
             if c.on:
                 cur[i] = c
             else:
@@ -240,14 +249,18 @@ class Tree(live_ref.ModelTree):
                 self.nodes[i].k = self.frame_no * self.descs[i].samples_per_buffer
 
 
-def run(scn: Scenario, wrong: str | None = None, figs=None, cfgs=None, ops=None, start=None, tree_cls=None) -> list:
+def run(scn: Scenario, wrong: str | None = None, figs=None, cfgs=None, ops=None, start=None, tree_cls=None, stepper=None,
+        reset_hold=True) -> list:
     """The frames of `scn` under the device-side wake: per frame live_ref.ModelTree.process's result plus "wake" (the records
     of :func:`decide`), "events" (leaf -> 'u' | 'p' of this frame: test_park_model.gate_with_parking's; the wrong device
     "prev_open" says 'c') and "descs".  `ops`: frame -> host calls before it (ModelTree.apply: retunes, gains); `tree_cls`:
-    another model tree on top of :class:`Tree` (agc_ref.agc_tree(Tree): the AGC loop, whose "agc" calls `ops` may then hold)."""
+    another model tree on top of :class:`Tree` (agc_ref.agc_tree(Tree): the AGC loop, whose "agc" calls `ops` may then hold);
+    `stepper`, `reset_hold`: another rule in place of wake.step, :func:`decide`'s wrong sdrx_set_wake."""
     assert wrong is None or wrong in WRONG, wrong
     figs = figures(scn.name) if figs is None else figs
-    recs = decide(scn, figs, step_hold_decremented_when_hot if wrong == "hold_dec" else wake.step, cfgs, start)
+    if stepper is None:
+        stepper = step_hold_decremented_when_hot if wrong == "hold_dec" else wake.step
+    recs = decide(scn, figs, stepper, cfgs, start, reset_hold)
     model = Tree(scn.topo, wrong) if tree_cls is None else tree_cls(scn.topo)
     model.park([i for i in scn.parked0])
     if start:
