@@ -3,9 +3,11 @@
 // frames to sdrj::demodData, receive every leaf's payload through the publish hook.
 //
 //   sdrx_demo <profile.ini> --dump              descriptors as JSON lines (no GPU needed)
-//   sdrx_demo <profile.ini> --frames N [--u8] [--fft TOPIC] [--devices 0,1,...]
+//   sdrx_demo <profile.ini> --frames N [--u8] [--format cu8|cs8|cs16] [--fft TOPIC] [--devices 0,1,...]
 //                                               N synthetic LCG frames; one line per published
 //                                               message: frame topic rate bytes fnv1a64(payload)
+//                                               --u8 feeds them as dongle bytes, --format as integer samples of that
+//                                               format (the same sample values in each: the same messages); neither: floats
 #include <cinttypes>
 #include <cstdio>
 #include <iostream>
@@ -28,7 +30,7 @@ static uint64_t fnv1a(const void *p, size_t n)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
         return 2;
     }
     try {
@@ -57,12 +59,19 @@ int main(int argc, char **argv)
             throw std::runtime_error("bad arguments");
         const int frames = std::atoi(argv[3]);
         bool u8 = false;
+        int fmt = SDRX_FMT_CU8;
         std::string fft_topic;
         std::vector<int> devices;
         for (int a = 4; a < argc; ++a) {
             if (std::string(argv[a]) == "--u8")
                 u8 = true;
-            else if (std::string(argv[a]) == "--fft" && a + 1 < argc)
+            else if (std::string(argv[a]) == "--format" && a + 1 < argc) {
+                const std::string f = argv[++a];
+                if (f != "cu8" && f != "cs8" && f != "cs16")
+                    throw std::runtime_error("--format takes cu8, cs8 or cs16");
+                fmt = f == "cu8" ? SDRX_FMT_CU8 : f == "cs8" ? SDRX_FMT_CS8 : SDRX_FMT_CS16;
+                u8 = true;
+            } else if (std::string(argv[a]) == "--fft" && a + 1 < argc)
                 fft_topic = argv[++a];
             else if (std::string(argv[a]) == "--devices" && a + 1 < argc) { // one tree sharded over several GPUs
                 std::stringstream ss(argv[++a]);
@@ -101,14 +110,24 @@ int main(int argc, char **argv)
         uint32_t x = 1;
         std::vector<float> iq((size_t)2 * P->frame);
         std::vector<uint8_t> bytes((size_t)2 * P->frame);
+        std::vector<int8_t> s8(fmt == SDRX_FMT_CS8 ? bytes.size() : 0);
+        std::vector<int16_t> s16(fmt == SDRX_FMT_CS16 ? bytes.size() : 0);
         for (frame_no = 0; frame_no < frames; ++frame_no) {
             for (size_t i = 0; i < iq.size(); ++i) {
                 x = x * 1664525u + 1013904223u;
                 const int c = (int)((x >> 24) % 17u) - 8;
                 iq[i] = (float)c;
                 bytes[i] = (uint8_t)(c + 127);
+                if (fmt == SDRX_FMT_CS8)
+                    s8[i] = (int8_t)c;
+                else if (fmt == SDRX_FMT_CS16)
+                    s16[i] = (int16_t)(256 * c); // c * 2^8: the same sample value
             }
-            if (u8)
+            if (fmt == SDRX_FMT_CS8)
+                radio.demodSamples(s8.data(), P->frame, fmt);
+            else if (fmt == SDRX_FMT_CS16)
+                radio.demodSamples(s16.data(), P->frame, fmt);
+            else if (u8)
                 radio.demodBytes(bytes.data(), P->frame);
             else
                 radio.demodData(iq.data(), (int)iq.size());

@@ -174,6 +174,24 @@ public:
         }
         after_frame(n_complex);
     }
+    // Integer samples of a front end in format `fmt` (SDRX_FMT_CU8 / CS8 / CS16, include/sdrx.h): conversion to the reference's
+    // units and DC correction on the device.  SDRX_FMT_CU8 is demodBytes.  On several devices the integers themselves are
+    // fanned out; the raw spectrum tap of a group is then served by the first member that holds VFOs, which keeps the
+    // converted frame with or without DC removal.
+    void demodSamples(const void *samples, int n_complex, int fmt)
+    {
+        if (fmt == SDRX_FMT_CU8)
+            return demodBytes(static_cast<const uint8_t *>(samples), n_complex);
+        if (!started())
+            start();
+        select_tap();
+        samples_.clear();
+        if (!grp_)
+            check(sdrx_process_fmt(ctx_, samples, n_complex, fmt, correctDC ? 1 : 0), "sdrx_process_fmt");
+        else
+            check(sdrx_group_process_fmt(grp_, samples, n_complex, fmt, correctDC ? 1 : 0), "sdrx_group_process_fmt");
+        after_frame(n_complex);
+    }
     sdrx_ctx *context() { return ctx_; }
     sdrx_group *group() { return grp_; }
     // Squelch-gated egress (library option "squelch" = 1, no counterpart in the reference): leaf ids[k] -- vfo::id after

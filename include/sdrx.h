@@ -230,6 +230,29 @@ int sdrx_process(sdrx_ctx *ctx, const float *iq, int n_complex);
  * (sdrj.cpp:271-286) done on the device.  Otherwise like sdrx_process. */
 int sdrx_process_u8(sdrx_ctx *ctx, const uint8_t *iq_bytes, int n_complex, int correct_dc);
 
+/* ---- integer sample formats: one front door for dongle bytes and wideband front ends ---------
+ * `fmt` of the *_fmt calls.  Every format maps to the SAME units, the reference's "dongle LSB, |x| <= 128": the shipped INI
+ * gains and every squelch, AGC and watch threshold live in those units, and the device's DC-bias removal is proved bit-exact
+ * for exactly that bound.  The scale is therefore FIXED: there is no per-call scale or shift, and cf32 frames are not offered
+ * with DC removal on the device (unbounded floats break the bound).
+ *
+ *   constant           memory                      sample value x (fp32, exact)       range
+ *   SDRX_FMT_CU8  = 0  uint8 I,Q                   b - 127                            [-127, 128]   (RTL dongles; = sdrx_*_u8)
+ *   SDRX_FMT_CS8  = 1  int8 I,Q                    (float)v                           [-128, 127]   (HackRF)
+ *   SDRX_FMT_CS16 = 2  native-endian int16 I,Q     (float)v * 2^-8                    [-128, 128)   (Airspy, SDRplay, USRP sc16, LimeSDR)
+ *
+ * correct_dc != 0: avept = fl(fl(avept * (1 - 1e-6f)) + fl(1e-6f * x)), x - avept (sdrj.cpp:277-283) on x as defined above, with
+ * the context's ONE accumulator -- the format may change from frame to frame.  Options "dc_blocked_scan", "dc_speculative" and
+ * "dc_blocks_per_step" apply as for bytes.  SDRX_FMT_CU8 is the sdrx_*_u8 path itself: the same launches, the same bits.  The
+ * signed formats always enter through one conversion pass into the tile layout (2-4 bytes read, 8 written per sample).
+ * An unknown fmt is SDRX_EINVAL; pointer, n_complex and in-flight rules as for the calls they are named after.
+ * Afterwards sdrx_get_raw serves the float frame (DC-corrected if it was); sdrx_submit_shared and its siblings refuse a source
+ * whose last frame was SDRX_FMT_CS8 / SDRX_FMT_CS16 (SDRX_ESTATE, as after a DC-corrected frame). */
+#define SDRX_FMT_CU8 0
+#define SDRX_FMT_CS8 1
+#define SDRX_FMT_CS16 2
+int sdrx_process_fmt(sdrx_ctx *ctx, const void *iq, int n_complex, int fmt, int correct_dc);
+
 /* Device-resident variant for pipelines that already hold the frame in HBM (bench.py, the
  * multi-GPU path where the frame arrives by RCCL broadcast): `dev_iq` is a DEVICE pointer to
  * n_complex cf32.  Asynchronous on the context's stream; sdrx_fetch() waits, copies the payloads
@@ -268,6 +291,15 @@ int sdrx_submit_u8(sdrx_ctx *ctx, const uint8_t *iq_bytes, int n_complex, int co
  * stream by default: then complete already at the time of the call) and stay untouched until sdrx_wait has delivered
  * this frame.  sdrx_get_raw returns SDRX_ESTATE after such a frame (caller-owned device memory). */
 int sdrx_submit_device(sdrx_ctx *ctx, const void *dev_iq, int n_complex);
+/* The *_fmt forms (formats above).  sdrx_submit_fmt: like sdrx_submit_u8.  The two device forms take integer samples that
+ * already lie in this context's device memory -- rtl_tcp or front-end samples landed by another kernel or a peer copy --
+ * 16-byte aligned (SDRX_EINVAL otherwise, nothing queued) and complete in the order of the context's stream:
+ * sdrx_process_device_fmt queues the frame like sdrx_process_device (sdrx_fetch / sdrx_sync afterwards), sdrx_submit_device_fmt
+ * like sdrx_submit_device (sdrx_wait afterwards).  The samples must stay untouched until the frame's conversion has run:
+ * until sdrx_sync, sdrx_fetch or sdrx_wait returns. */
+int sdrx_submit_fmt(sdrx_ctx *ctx, const void *iq, int n_complex, int fmt, int correct_dc);
+int sdrx_process_device_fmt(sdrx_ctx *ctx, const void *dev_iq, int n_complex, int fmt, int correct_dc);
+int sdrx_submit_device_fmt(sdrx_ctx *ctx, const void *dev_iq, int n_complex, int fmt, int correct_dc);
 /* Two contexts on ONE device fed the same raw frame -- sdrj::demodData hands every main VFO the same `samples`
  * (sdrj.cpp:288-294), and a binding that keeps one context per main VFO (host/qt/vfo_adapter.cpp) would otherwise
  * upload the frame once per main: run through `ctx` the frame `src` staged LAST (host floats or dongle bytes given
@@ -757,9 +789,9 @@ int sdrx_set_tap(sdrx_ctx *ctx, int id);
 int sdrx_add_tap(sdrx_ctx *ctx, int id);
 /* The raw frame exactly as the parent-less VFOs consumed it -- `samples` of sdrj::demodData
  * (sdrj.cpp:266-305) after the byte LUT and the DC-bias removal, what sdrj's own fftData signal
- * carries (sdrj.cpp:296-303) -- natural order, cf32.  Available after sdrx_process and
- * sdrx_process_u8; after sdrx_process_device the frame was the caller's own device memory and
- * the call returns SDRX_ESTATE. */
+ * carries (sdrj.cpp:296-303) -- natural order, cf32.  Available after sdrx_process,
+ * sdrx_process_u8 and the *_fmt calls (after SDRX_FMT_CS8 / SDRX_FMT_CS16 frames, device ones included: the converted floats);
+ * after sdrx_process_device the frame was the caller's own device memory and the call returns SDRX_ESTATE. */
 int sdrx_get_raw(sdrx_ctx *ctx, float *out_iq, int max_complex, int *n);
 int sdrx_get_prequant(sdrx_ctx *ctx, int id, float *out, int max, int *n);
 /* Designed tap sets, for parity checks: which = 0 audio low-pass, 1 late-decimation low-pass,
@@ -921,6 +953,11 @@ int sdrx_group_submit(sdrx_group *grp, const float *iq, int n_complex);
  * identical, so only the bytes travel.  What the shipped sdr_25E.ini (correct_dc_bias=1) needs. */
 int sdrx_group_submit_u8(sdrx_group *grp, const uint8_t *iq_bytes, int n_complex, int correct_dc);
 int sdrx_group_process_u8(sdrx_group *grp, const uint8_t *iq_bytes, int n_complex, int correct_dc);
+/* Integer samples of any format (SDRX_FMT_*, above): the raw integers are fanned out -- 2 or 4 bytes a sample, a quarter or
+ * half of a cf32 frame's traffic -- and every member converts them and, if correct_dc != 0, removes the DC bias with an
+ * accumulator of its own, as for bytes.  (No device-frame forms of these for groups.) */
+int sdrx_group_submit_fmt(sdrx_group *grp, const void *iq, int n_complex, int fmt, int correct_dc);
+int sdrx_group_process_fmt(sdrx_group *grp, const void *iq, int n_complex, int fmt, int correct_dc);
 int sdrx_group_submit_device(sdrx_group *grp, const void *dev_iq_on_first_device, int n_complex, void *producer_stream);
 /* like sdrx_process_device: kernels only, asynchronous; the frame must stay untouched until sdrx_group_sync */
 int sdrx_group_process_device(sdrx_group *grp, const void *dev_iq_on_first_device, int n_complex, void *producer_stream);

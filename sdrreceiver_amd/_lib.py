@@ -148,10 +148,14 @@ SYMBOLS = {
     "sdrx_check_vfo": (_i, [C.POINTER(VfoDescC), C.c_char_p, C.c_size_t]),
     "sdrx_process": (_i, [_vp, _vp, _i]),
     "sdrx_process_u8": (_i, [_vp, _vp, _i, _i]),
+    "sdrx_process_fmt": (_i, [_vp, _vp, _i, _i, _i]),
     "sdrx_process_device": (_i, [_vp, _vp, _i]),
     "sdrx_submit": (_i, [_vp, _vp, _i]),
     "sdrx_submit_u8": (_i, [_vp, _vp, _i, _i]),
     "sdrx_submit_device": (_i, [_vp, _vp, _i]),
+    "sdrx_submit_fmt": (_i, [_vp, _vp, _i, _i, _i]),
+    "sdrx_process_device_fmt": (_i, [_vp, _vp, _i, _i, _i]),
+    "sdrx_submit_device_fmt": (_i, [_vp, _vp, _i, _i, _i]),
     "sdrx_wait": (_i, [_vp]),
     "sdrx_in_flight": (_i, [_vp]),
     "sdrx_fetch": (_i, [_vp]),
@@ -235,6 +239,8 @@ SYMBOLS = {
     "sdrx_group_submit": (_i, [_vp, _vp, _i]),
     "sdrx_group_submit_u8": (_i, [_vp, _vp, _i, _i]),
     "sdrx_group_process_u8": (_i, [_vp, _vp, _i, _i]),
+    "sdrx_group_submit_fmt": (_i, [_vp, _vp, _i, _i, _i]),
+    "sdrx_group_process_fmt": (_i, [_vp, _vp, _i, _i, _i]),
     "sdrx_group_peer_access": (_i, [_vp]),
     "sdrx_group_submit_device": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_group_process_device": (_i, [_vp, _vp, _i, _vp]),

@@ -19,6 +19,9 @@
 //   k_dc_apply            ingest.hip    /
 //   k_dc_block_sums       ingest.hip    \ the same in the tolerance arithmetic: a blocked scan of the linear recurrence
 //   k_ingest_u8_dc_fast   ingest.hip    /
+//   k_ingest_s8, _s16     ingest.hip    (none: int8 / int16 samples of a wideband front end in the reference's units, SDRX_FMT_CS8 / CS16)
+//   k_dc_products_signed, k_dc_apply_signed, k_dc_block_sums_signed, k_ingest_signed_dc_fast
+//                         ingest.hip    the four DC kernels that read samples, for those formats (the chain kernels serve every format)
 //   k_mix_decimate        mix.hip       vfo::process mix loop, vfo.cpp:237-245; HalfBandDecimator::decimate, halfbanddecimator.cpp:43-72,
 //                                       with FIR::...HalfBandQueue, dsp.cpp:96-173 (mix_item); option fuse_late: the FIR part of
 //                                       vfo::usb_decimdemod, vfo.cpp:334-356, inside a d = 0 leaf's wave (late_item); option fuse_demod:

@@ -710,10 +710,34 @@ int enqueue_f32(sdrx_ctx *c, const float *iq, int n_complex, bool egress)
     return rc;
 }
 
-// `dev_bytes`: the frame's dongle bytes, already on this context's device and complete in the order of
-// c->st.stream.  LUT (+ the DC-bias IIR with this context's own accumulator) and the frame itself.
-int enqueue_u8_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, int correct_dc, bool egress)
+// The kernels that read a frame of integer samples, by format (include/sdrx.h SDRX_FMT_*): for CU8 the dongle-byte kernels
+// as they always were, for CS8 / CS16 their signed siblings (ingest.hip).
+struct SampleKernels {
+    void (*ingest)(const unsigned *, float4 *, int);
+    void (*products)(const unsigned *, float *, int, int);
+    void (*apply)(const unsigned *, const float *, float4 *, int, int);
+    void (*block_sums)(const unsigned *, int, const double *, double2 *);
+    void (*dc_fast)(const unsigned *, float4 *, int, const float *, float *, const double *, const double2 *);
+};
+const SampleKernels &sample_kernels(int fmt)
 {
+    static const SampleKernels K[3] = {
+        {k_ingest_u8, k_dc_products, k_dc_apply, k_dc_block_sums, k_ingest_u8_dc_fast},
+        {k_ingest_s8, k_dc_products_signed<1>, k_dc_apply_signed<1>, k_dc_block_sums_signed<1>, k_ingest_signed_dc_fast<1>},
+        {k_ingest_s16, k_dc_products_signed<2>, k_dc_apply_signed<2>, k_dc_block_sums_signed<2>, k_ingest_signed_dc_fast<2>},
+    };
+    return K[fmt];
+}
+bool known_format(int fmt) { return fmt == SDRX_FMT_CU8 || fmt == SDRX_FMT_CS8 || fmt == SDRX_FMT_CS16; }
+size_t sample_bytes(int fmt, int n_complex) { return (size_t)n_complex * (fmt == SDRX_FMT_CS16 ? 4 : 2); }
+
+// `dev_bytes`: the frame's integer samples in format `fmt` (dongle bytes, int8 or int16), already on this context's device and
+// complete in the order of c->st.stream.  Sample conversion (+ the DC-bias IIR with this context's own accumulator, the one
+// accumulator whatever the format) and the frame itself.  Dongle bytes without DC removal go to level 0 as they are (kRawU8);
+// the signed formats always enter through an ingest pass into the tile layout, as every DC-corrected frame does.
+int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, int fmt, int correct_dc, bool egress)
+{
+    const SampleKernels &K = sample_kernels(fmt);
     if (correct_dc && !c->dc.d_state) {
         HIPCHK(c, hipMalloc(&c->dc.d_state, 4 * sizeof(float)));
         HIPCHK(c, hipMemsetAsync(c->dc.d_state, 0, 4 * sizeof(float), c->st.stream)); // `static cpx_typef avept=0`, sdrj.cpp:279
@@ -748,7 +772,7 @@ int enqueue_u8_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, int cor
         float *Pp = c->dc.d_work, *Ap = c->dc.d_work + 2 * (size_t)c->dc.work_stride;
         const int words = n_complex / 2;
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
-        hipLaunchKernelGGL(k_dc_products, dim3((words + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), Pp,
+        hipLaunchKernelGGL(K.products, dim3((words + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), Pp,
                            n_complex, c->dc.work_stride);
         if (c->opt_dc_speculative) {
             if (!c->dc.d_counters) {
@@ -763,18 +787,24 @@ int enqueue_u8_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, int cor
         } else {
             hipLaunchKernelGGL(k_dc_chain, dim3(2), dim3(64), 0, c->st.stream, Pp, Ap, n_complex, c->dc.work_stride, c->dc.d_state);
         }
-        hipLaunchKernelGGL(k_dc_apply, dim3((words + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), Ap,
+        hipLaunchKernelGGL(K.apply, dim3((words + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), Ap,
                            reinterpret_cast<float4 *>(c->d_raw_tiled), n_complex, c->dc.work_stride);
         mode = kRawTiled;
     } else if (correct_dc) {
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
         const int par = (int)(c->dc.frames++ & 1ull);
         double2 *sums = reinterpret_cast<double2 *>(c->dc.d_tab + c->dc.tab_sums);
-        hipLaunchKernelGGL(k_dc_block_sums, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), n_complex,
+        hipLaunchKernelGGL(K.block_sums, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), n_complex,
                            c->dc.d_tab, sums);
-        hipLaunchKernelGGL(k_ingest_u8_dc_fast, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
+        hipLaunchKernelGGL(K.dc_fast, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
                            reinterpret_cast<float4 *>(c->d_raw_tiled), n_complex, c->dc.d_state + 2 * par, c->dc.d_state + 2 * (par ^ 1),
                            c->dc.d_tab, sums);
+        mode = kRawTiled;
+    } else if (fmt != SDRX_FMT_CU8) {
+        Bracket b(c, c->st.stream, KIND_INGEST, 0);
+        const int n_pairs = n_complex / 2;
+        hipLaunchKernelGGL(K.ingest, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
+                           reinterpret_cast<float4 *>(c->d_raw_tiled), n_pairs);
         mode = kRawTiled;
     }
     c->long_frame = correct_dc && !c->opt_dc_blocked;
@@ -785,14 +815,29 @@ int enqueue_u8_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, int cor
     return rc;
 }
 
-int enqueue_u8(sdrx_ctx *c, const uint8_t *bytes, int n_complex, int correct_dc, bool egress)
+// host samples -> this frame parity's device buffer -> enqueue_samples_device.  Dongle bytes land in d_raw_u8 (which
+// sdrx_get_raw and sdrx_submit_shared read after a frame without DC removal); the signed formats, up to 4 bytes a sample, in
+// the cf32 buffer of that parity, which is twice as large as they need and has no other use in such a frame.
+int enqueue_samples(sdrx_ctx *c, const void *samples, int n_complex, int fmt, int correct_dc, bool egress)
 {
     int rc = ensure_raw(c, (size_t)c->root_frame);
     if (rc)
         return rc;
-    unsigned char *dst = c->d_raw_u8[c->frame_no & 1ull];
-    rc = stage_host_frame(c, bytes, (size_t)n_complex * 2, dst);
-    return rc ? rc : enqueue_u8_device(c, dst, n_complex, correct_dc, egress);
+    const int p = (int)(c->frame_no & 1ull);
+    void *dst = fmt == SDRX_FMT_CU8 ? static_cast<void *>(c->d_raw_u8[p]) : static_cast<void *>(c->d_raw[p]);
+    rc = stage_host_frame(c, samples, sample_bytes(fmt, n_complex), dst);
+    return rc ? rc : enqueue_samples_device(c, dst, n_complex, fmt, correct_dc, egress);
+}
+
+// What the *_fmt calls check on top of check_frame_call / group_check: the format, and for device frames the alignment the
+// 16-byte loads of the DC kernels ask for.  nullptr: fine.
+const char *bad_samples(int fmt, const void *dev_ptr)
+{
+    if (!known_format(fmt))
+        return "fmt must be SDRX_FMT_CU8 (0), SDRX_FMT_CS8 (1) or SDRX_FMT_CS16 (2)";
+    if (dev_ptr && (reinterpret_cast<uintptr_t>(dev_ptr) & 15u))
+        return "device samples must be 16-byte aligned";
+    return nullptr;
 }
 
 } // namespace
@@ -826,7 +871,7 @@ int sdrx_submit(sdrx_ctx *c, const float *iq, int n_complex)
 int sdrx_submit_u8(sdrx_ctx *c, const uint8_t *bytes, int n_complex, int correct_dc)
 {
     int rc = check_frame_call(c, "sdrx_submit_u8", bytes, n_complex, false);
-    return rc ? rc : enqueue_u8(c, bytes, n_complex, correct_dc, true);
+    return rc ? rc : enqueue_samples(c, bytes, n_complex, SDRX_FMT_CU8, correct_dc, true);
 }
 
 // The frame `src` staged LAST (host floats or dongle bytes handed to sdrx_process* / sdrx_submit* of `src`) once
@@ -931,8 +976,56 @@ int sdrx_process_u8(sdrx_ctx *c, const uint8_t *bytes, int n_complex, int correc
     int rc = check_frame_call(c, "sdrx_process_u8", bytes, n_complex, true);
     if (rc)
         return rc;
-    rc = enqueue_u8(c, bytes, n_complex, correct_dc, true);
+    rc = enqueue_samples(c, bytes, n_complex, SDRX_FMT_CU8, correct_dc, true);
     return rc ? rc : sdrx_wait(c);
+}
+
+// ---- one front door for integer samples (SDRX_FMT_*): host frames, and frames already on the device ------------------------
+static int frame_call_fmt(sdrx_ctx *c, const char *what, const void *ptr, int n_complex, int fmt, const void *dev_ptr, bool sync_call)
+{
+    const int rc = check_frame_call(c, what, ptr, n_complex, sync_call);
+    if (rc)
+        return rc;
+    if (const char *why = bad_samples(fmt, dev_ptr))
+        return fail(c, SDRX_EINVAL, "%s: %s", what, why);
+    return SDRX_OK;
+}
+
+int sdrx_submit_fmt(sdrx_ctx *c, const void *iq, int n_complex, int fmt, int correct_dc)
+{
+    const int rc = frame_call_fmt(c, "sdrx_submit_fmt", iq, n_complex, fmt, nullptr, false);
+    return rc ? rc : enqueue_samples(c, iq, n_complex, fmt, correct_dc, true);
+}
+
+int sdrx_process_fmt(sdrx_ctx *c, const void *iq, int n_complex, int fmt, int correct_dc)
+{
+    int rc = frame_call_fmt(c, "sdrx_process_fmt", iq, n_complex, fmt, nullptr, true);
+    if (rc)
+        return rc;
+    rc = enqueue_samples(c, iq, n_complex, fmt, correct_dc, true);
+    return rc ? rc : sdrx_wait(c);
+}
+
+// (the samples are the caller's: where the frame went to level 0 as it lies -- dongle bytes without DC removal -- sdrx_get_raw
+// and sdrx_submit_shared have no buffer of this context to serve; every other frame left its floats in the tile layout)
+static int device_frame_fmt(sdrx_ctx *c, const void *dev_iq, int n_complex, int fmt, int correct_dc, bool egress)
+{
+    const int rc = enqueue_samples_device(c, dev_iq, n_complex, fmt, correct_dc, egress);
+    if (rc == SDRX_OK && c->last_raw == kRawU8)
+        c->last_raw = -1;
+    return rc;
+}
+
+int sdrx_process_device_fmt(sdrx_ctx *c, const void *dev_iq, int n_complex, int fmt, int correct_dc)
+{
+    const int rc = frame_call_fmt(c, "sdrx_process_device_fmt", dev_iq, n_complex, fmt, dev_iq, true);
+    return rc ? rc : device_frame_fmt(c, dev_iq, n_complex, fmt, correct_dc, false);
+}
+
+int sdrx_submit_device_fmt(sdrx_ctx *c, const void *dev_iq, int n_complex, int fmt, int correct_dc)
+{
+    const int rc = frame_call_fmt(c, "sdrx_submit_device_fmt", dev_iq, n_complex, fmt, dev_iq, false);
+    return rc ? rc : device_frame_fmt(c, dev_iq, n_complex, fmt, correct_dc, true);
 }
 
 } // extern "C"

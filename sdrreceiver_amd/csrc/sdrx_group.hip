@@ -85,7 +85,7 @@ int group_check_ids(sdrx_group *g, const char *what, const int *ids, int n)
 
 // frame (cf32 or bytes, `bytes` long) is complete on the first device at `src` once ev_ready[p] fires:
 // fan it out and enqueue frame processing on every member.
-int group_enqueue(sdrx_group *g, const void *src, size_t bytes, int raw_mode, bool egress, int correct_dc = 0)
+int group_enqueue(sdrx_group *g, const void *src, size_t bytes, int raw_mode, bool egress, int correct_dc = 0, int fmt = SDRX_FMT_CU8)
 {
     const int p = (int)(g->frame_no & 1ull);
     for (size_t k = 0; k < g->m.size(); ++k) {
@@ -104,10 +104,11 @@ int group_enqueue(sdrx_group *g, const void *src, size_t bytes, int raw_mode, bo
         }
         M.c->last_raw = -1;
         int rc;
-        if (raw_mode == kRawU8 && correct_dc) {
+        if (raw_mode == kRawU8 && (correct_dc || fmt != SDRX_FMT_CU8)) {
             // sdrj.cpp:271-286 on every member: identical bytes and identical (zero-started) accumulators keep the
-            // members' DC estimates identical, so no state ever has to travel between devices
-            rc = enqueue_u8_device(M.c, raw, g->root_frame, 1, egress); // (leaves last_raw = tile layout: sdrx_get_raw serves it)
+            // members' DC estimates identical, so no state ever has to travel between devices.  The signed formats (`fmt`)
+            // take this way with or without DC removal: every member converts the integer samples it was sent itself
+            rc = enqueue_samples_device(M.c, raw, g->root_frame, fmt, correct_dc, egress); // (leaves last_raw = tile layout: sdrx_get_raw serves it)
         } else {
             rc = enqueue_frame(M.c, raw, raw_mode, egress);
         }
@@ -475,6 +476,29 @@ int sdrx_group_process_u8(sdrx_group *g, const uint8_t *bytes, int n_complex, in
     if (rc)
         return rc;
     rc = sdrx_group_submit_u8(g, bytes, n_complex, correct_dc);
+    return rc ? rc : sdrx_group_wait(g);
+}
+
+// Integer samples of any format (SDRX_FMT_*): the raw integers are what is fanned out -- 2 or 4 bytes a sample where a
+// float frame takes 8 --, and every member converts them and, with correct_dc, runs the DC-bias IIR with its own accumulator.
+int sdrx_group_submit_fmt(sdrx_group *g, const void *iq, int n_complex, int fmt, int correct_dc)
+{
+    int rc = group_check(g, "sdrx_group_submit_fmt", iq, n_complex, false);
+    if (rc)
+        return rc;
+    if (const char *why = bad_samples(fmt, nullptr))
+        return gfail(g, SDRX_EINVAL, "sdrx_group_submit_fmt: %s", why);
+    const size_t nb = sample_bytes(fmt, n_complex);
+    rc = group_stage(g, iq, nb);
+    return rc ? rc : group_enqueue(g, g->d_stage[g->frame_no & 1ull], nb, kRawU8, true, correct_dc, fmt);
+}
+
+int sdrx_group_process_fmt(sdrx_group *g, const void *iq, int n_complex, int fmt, int correct_dc)
+{
+    int rc = group_check(g, "sdrx_group_process_fmt", iq, n_complex, true);
+    if (rc)
+        return rc;
+    rc = sdrx_group_submit_fmt(g, iq, n_complex, fmt, correct_dc);
     return rc ? rc : sdrx_group_wait(g);
 }
 

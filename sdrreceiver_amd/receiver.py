@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, agc as _agc, drift as _drift, meter, scan as _scan, squelch as _squelch, wake as _wake, watch as _watch
+from . import _lib, agc as _agc, drift as _drift, ingest, meter, scan as _scan, squelch as _squelch, wake as _wake, watch as _watch
 from .topology import Topology, VfoDesc
 
 
@@ -404,9 +404,22 @@ class Receiver(_LeafCalls):
         self.published.clear()
         self._chk(self.L.sdrx_process_u8(self.h, b.ctypes.data, b.size // 2, int(bool(correct_dc))))
 
+    def process_fmt(self, iq, correct_dc: bool = False, fmt=None) -> None:
+        """One frame of integer samples on the host in one of the formats of :mod:`sdrreceiver_amd.ingest` (dongle bytes,
+        int8, int16; `fmt` None: the one the array's dtype stands for): conversion + optional DC-bias IIR on the device."""
+        a, fmt = ingest.as_samples(iq, fmt)
+        self.published.clear()
+        self._chk(self.L.sdrx_process_fmt(self.h, a.ctypes.data, a.size // 2, fmt, int(bool(correct_dc))))
+
     def process_device(self, dev_ptr: int, n_complex: int) -> None:
         self.published.clear()  # the payloads of this frame arrive with the next (explicit or implicit) fetch
         self._chk(self.L.sdrx_process_device(self.h, C.c_void_p(dev_ptr), int(n_complex)))
+
+    def process_device_fmt(self, dev_ptr: int, n_complex: int, fmt: int, correct_dc: bool = False) -> None:
+        """One frame of integer samples of format `fmt` already in this context's device memory (16-byte aligned), queued
+        like :meth:`process_device`."""
+        self.published.clear()
+        self._chk(self.L.sdrx_process_device_fmt(self.h, C.c_void_p(dev_ptr), int(n_complex), int(fmt), int(bool(correct_dc))))
 
     def fetch(self) -> None:
         self.published.clear()
@@ -426,6 +439,15 @@ class Receiver(_LeafCalls):
         complete in the order of the context's stream (:meth:`set_stream`; by default: complete already) and stay untouched
         until :meth:`wait` has delivered it."""
         self._chk(self.L.sdrx_submit_device(self.h, C.c_void_p(dev_ptr), int(n_complex)))
+
+    def submit_fmt(self, iq, correct_dc: bool = False, fmt=None) -> None:
+        """:meth:`process_fmt`'s frame, pipelined like :meth:`submit_u8`."""
+        a, fmt = ingest.as_samples(iq, fmt)
+        self._chk(self.L.sdrx_submit_fmt(self.h, a.ctypes.data, a.size // 2, fmt, int(bool(correct_dc))))
+
+    def submit_device_fmt(self, dev_ptr: int, n_complex: int, fmt: int, correct_dc: bool = False) -> None:
+        """:meth:`process_device_fmt`'s frame, pipelined like :meth:`submit_device`."""
+        self._chk(self.L.sdrx_submit_device_fmt(self.h, C.c_void_p(dev_ptr), int(n_complex), int(fmt), int(bool(correct_dc))))
 
     def process_shared(self, src: "Receiver") -> None:
         """The frame `src` staged last (same device), once more through THIS tree, without a second upload."""
@@ -638,6 +660,16 @@ class Group(_LeafCalls):
         b = np.ascontiguousarray(iq_bytes, dtype=np.uint8).reshape(-1)
         self.published.clear()
         self._chk(self.L.sdrx_group_process_u8(self.h, b.ctypes.data, b.size // 2, int(bool(correct_dc))))
+
+    def submit_fmt(self, iq, correct_dc: bool = False, fmt=None) -> None:
+        """Integer samples of any format of :mod:`sdrreceiver_amd.ingest`: the integers are fanned out, every member converts."""
+        a, fmt = ingest.as_samples(iq, fmt)
+        self._chk(self.L.sdrx_group_submit_fmt(self.h, a.ctypes.data, a.size // 2, fmt, int(bool(correct_dc))))
+
+    def process_fmt(self, iq, correct_dc: bool = False, fmt=None) -> None:
+        a, fmt = ingest.as_samples(iq, fmt)
+        self.published.clear()
+        self._chk(self.L.sdrx_group_process_fmt(self.h, a.ctypes.data, a.size // 2, fmt, int(bool(correct_dc))))
 
     def peer_access(self) -> bool:
         """True: every member reaches the first device's frame directly (same device or xGMI peer access)."""
@@ -855,10 +887,14 @@ class sdrj:  # noqa: N801  (the reference's class name, sdrj.h)
 
     def demodBytes(self, data):
         """The rtl_tcp byte stream (sdrj.cpp:155-160 feeds it through the LUT into demodData):
-        LUT and DC-bias removal run on the device."""
+        LUT and DC-bias removal run on the device.  An int8 or int16 array is a wideband front end's samples instead
+        (:mod:`sdrreceiver_amd.ingest`); anything else is taken as bytes, as before."""
         if self.rx is None:
             self.start()
-        self.rx.process_u8(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), correct_dc=self.correctDC)
+        if isinstance(data, np.ndarray) and data.dtype in (np.int8, np.int16):
+            self.rx.process_fmt(data, correct_dc=self.correctDC)
+        else:
+            self.rx.process_u8(np.ascontiguousarray(data, dtype=np.uint8).reshape(-1), correct_dc=self.correctDC)
         self._after_frame()
 
     @property
