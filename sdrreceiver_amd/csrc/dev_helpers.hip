@@ -137,6 +137,13 @@ __device__ __forceinline__ v2f gldv2(const float2 *p) { return *(const SDRX_AS1 
 __device__ __forceinline__ v4f gldv4(const float4 *p) { return *(const SDRX_AS1 v4f *)p; }
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ v4u gldv4u(const v4u *p) { return *(const SDRX_AS1 v4u *)p; }
+// Four dongle bytes of one word -> two complex samples: floats[b] = b - 127 (jonti/sdr.cpp:43-49,122-129; sdrj.cpp:155-160).
+// The one place the table is spelled out on the device, for ingest.hip (sample_pair) and mix.hip (load_run_raw).
+__device__ __forceinline__ float4 cu8_pair(unsigned w)
+{
+    return make_float4((float)((int)(w & 255u) - 127), (float)((int)((w >> 8) & 255u) - 127), (float)((int)((w >> 16) & 255u) - 127),
+                       (float)((int)(w >> 24) - 127));
+}
 __device__ __forceinline__ void gstv2(float2 *p, v2f v) { *(SDRX_AS1 v2f *)p = v; }
 __device__ __forceinline__ void gstv4(float4 *p, v4f v) { *(SDRX_AS1 v4f *)p = v; }
 // Stores that are ALWAYS issued, lanes that have nothing to store included: a buffer store whose offset lies beyond the

@@ -1,10 +1,11 @@
-// ingest.hip -- the raw frame's way into the tile layout (sdrx_dev.h): k_ingest_f32 and k_ingest_u8 (floats[b] = b - 127:
-// jonti/sdr.cpp:43-49,122-129; sdrj.cpp:155-160), and the DC-bias removal of sdrj::demodData (sdrj.cpp:271-286) -- bit-exact
-// as k_dc_products -> k_dc_chain | k_dc_chain_spec -> k_dc_apply, in the tolerance arithmetic as k_dc_block_sums ->
-// k_ingest_u8_dc_fast -- with the DPP scans that only these kernels use.  The signed formats of a wideband front end
-// (SDRX_FMT_CS8 / SDRX_FMT_CS16: signed_pair, k_ingest_s8 / k_ingest_s16) have siblings of the four DC kernels that read
-// samples; the byte kernels are what they were, and the chain kernels, which only ever see products, serve every format.
-// Relies on dev_helpers.hip (gldv4, gldv4u, gst2, v16f) and on tile_unit (sdrx_dev.h).
+// ingest.hip -- the raw frame's way into the tile layout (sdrx_dev.h): k_ingest_f32, and for frames of integer samples one
+// family of kernels templated on the format (include/sdrx.h: SDRX_FMT_CU8, floats[b] = b - 127 of jonti/sdr.cpp:43-49,122-129 and
+// sdrj.cpp:155-160; SDRX_FMT_CS8 / SDRX_FMT_CS16, a wideband front end's signed samples) -- k_ingest_samples, and the DC-bias
+// removal of sdrj::demodData (sdrj.cpp:271-286): bit-exact as k_dc_products -> k_dc_chain | k_dc_chain_spec -> k_dc_apply, in the
+// tolerance arithmetic as k_dc_block_sums -> k_ingest_dc_fast -- with the DPP scans that only these kernels use.  What differs
+// between the formats is how four floats are made out of one or two 32-bit words (sample_pair); the chain kernels, which only
+// ever see products, are no templates.
+// Relies on dev_helpers.hip (cu8_pair, gldv4, gldv4u, gst2, v16f) and on tile_unit (sdrx_dev.h).
 
 // ------------------------------------------------------------------------------------ ingest
 // natural cf32 frame -> tile layout (host-fed / broadcast raw frames enter the pipeline here)
@@ -17,70 +18,54 @@ __global__ __launch_bounds__(256) void k_ingest_f32(const float4 *__restrict__ n
     tiled[tile_unit(c, r & 7, r >> 3)] = nat[p];
 }
 
-// Dongle bytes -> cf32 in tile layout: floats[b] = b - 127 (jonti/sdr.cpp:43-49,122-129;
-// sdrj.cpp:155-160).  One thread = one complex pair (4 bytes).
-__global__ __launch_bounds__(256) void k_ingest_u8(const unsigned *__restrict__ bytes4, float4 *__restrict__ tiled, int n_pairs)
-{
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= n_pairs)
-        return;
-    const unsigned w = bytes4[p];
-    const float4 v = make_float4((float)((int)(w & 255u) - 127), (float)((int)((w >> 8) & 255u) - 127),
-                                 (float)((int)((w >> 16) & 255u) - 127), (float)((int)(w >> 24) - 127));
-    const int c = p >> 9, r = p & 511;
-    tiled[tile_unit(c, r & 7, r >> 3)] = v;
-}
-
-// Signed integer samples of a wideband front end (include/sdrx.h, SDRX_FMT_CS8 / SDRX_FMT_CS16) -> cf32 in the reference's
-// units, "dongle LSB, |x| <= 128": int8 as it is, int16 times 2^-8 (an exact scaling: 16 significant bits, no rounding).
-// One definition of a pair of complex samples for every kernel that reads such a frame; FMT is the header's constant.
-// The sample is computed FIRST and everything else from it -- fl(1e-6f * x) below is a product of x, never of v.
+// Integer samples (include/sdrx.h, SDRX_FMT_*) -> cf32 in the reference's units, "dongle LSB, |x| <= 128": dongle bytes b - 127
+// (cu8_pair), int8 of a wideband front end as it is, int16 times 2^-8 (an exact scaling: 16 significant bits, no rounding).
+// One definition of a pair of complex samples for every kernel that reads such a frame; FMT is the header's constant.  A pair
+// is one 32-bit word of the 8-bit formats and two of int16 (pair_words: .y unused for the former).
+// The sample is computed FIRST and everything else from it -- fl(1e-6f * x) below is a product of x, never of b or v.
 template <int FMT>
-__device__ __forceinline__ float4 signed_pair(const unsigned *__restrict__ words, int p) // complex samples 2 p and 2 p + 1
+__device__ __forceinline__ float4 decode_pair(uint2 w)
 {
-    static_assert(FMT == 1 || FMT == 2, "SDRX_FMT_CS8 | SDRX_FMT_CS16");
-    if constexpr (FMT == 1) {
-        const unsigned w = words[p];
-        return make_float4((float)(signed char)(w & 255u), (float)(signed char)((w >> 8) & 255u), (float)(signed char)((w >> 16) & 255u),
-                           (float)((int)w >> 24));
+    static_assert(FMT == SDRX_FMT_CU8 || FMT == SDRX_FMT_CS8 || FMT == SDRX_FMT_CS16, "a format of include/sdrx.h");
+    if constexpr (FMT == SDRX_FMT_CU8) {
+        return cu8_pair(w.x);
+    } else if constexpr (FMT == SDRX_FMT_CS8) {
+        return make_float4((float)(signed char)(w.x & 255u), (float)(signed char)((w.x >> 8) & 255u), (float)(signed char)((w.x >> 16) & 255u),
+                           (float)((int)w.x >> 24));
     } else {
         const float s = 0.00390625f; // 2^-8
-        const uint2 w = reinterpret_cast<const uint2 *>(words)[p];
         return make_float4((float)(short)(w.x & 0xffffu) * s, (float)((int)w.x >> 16) * s, (float)(short)(w.y & 0xffffu) * s,
                            (float)((int)w.y >> 16) * s);
     }
 }
-// ... and out of 16-byte units a thread has loaded itself: pair e of unit q (4 pairs of int8, 2 of int16)
 template <int FMT>
-__device__ __forceinline__ float4 signed_pair_of(const v4u q, int e)
+__device__ __forceinline__ uint2 pair_words(const unsigned *__restrict__ words, int p) // the words of complex samples 2 p and 2 p + 1
 {
-    if constexpr (FMT == 1) {
-        const unsigned w = q[e];
-        return make_float4((float)(signed char)(w & 255u), (float)(signed char)((w >> 8) & 255u), (float)(signed char)((w >> 16) & 255u),
-                           (float)((int)w >> 24));
-    } else {
-        const float s = 0.00390625f;
-        const unsigned a = q[2 * e], b = q[2 * e + 1];
-        return make_float4((float)(short)(a & 0xffffu) * s, (float)((int)a >> 16) * s, (float)(short)(b & 0xffffu) * s, (float)((int)b >> 16) * s);
-    }
+    if constexpr (FMT == SDRX_FMT_CS16)
+        return reinterpret_cast<const uint2 *>(words)[p];
+    else
+        return make_uint2(words[p], 0u);
 }
-// natural order -> tile layout, like k_ingest_u8: one thread = one float4 = 2 complex samples (4 bytes of int8, 8 of int16)
 template <int FMT>
-__device__ __forceinline__ void ingest_signed(const unsigned *__restrict__ words, float4 *__restrict__ tiled, int n_pairs)
+__device__ __forceinline__ float4 sample_pair(const unsigned *__restrict__ words, int p) // complex samples 2 p and 2 p + 1
+{
+    return decode_pair<FMT>(pair_words<FMT>(words, p));
+}
+// ... and out of 16-byte units a thread has loaded itself: pair e of unit q (4 pairs of the 8-bit formats, 2 of int16)
+template <int FMT>
+__device__ __forceinline__ float4 sample_pair_of(const v4u q, int e)
+{
+    return decode_pair<FMT>(FMT == SDRX_FMT_CS16 ? make_uint2(q[2 * e], q[2 * e + 1]) : make_uint2(q[e], 0u));
+}
+// natural order -> tile layout: one thread = one float4 = 2 complex samples (4 bytes of the 8-bit formats, 8 of int16)
+template <int FMT>
+__global__ __launch_bounds__(256) void k_ingest_samples(const unsigned *__restrict__ words, float4 *__restrict__ tiled, int n_pairs)
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= n_pairs)
         return;
     const int c = p >> 9, r = p & 511;
-    tiled[tile_unit(c, r & 7, r >> 3)] = signed_pair<FMT>(words, p);
-}
-__global__ __launch_bounds__(256) void k_ingest_s8(const unsigned *__restrict__ words, float4 *__restrict__ tiled, int n_pairs)
-{
-    ingest_signed<1>(words, tiled, n_pairs);
-}
-__global__ __launch_bounds__(256) void k_ingest_s16(const unsigned *__restrict__ words, float4 *__restrict__ tiled, int n_pairs)
-{
-    ingest_signed<2>(words, tiled, n_pairs);
+    tiled[tile_unit(c, r & 7, r >> 3)] = sample_pair<FMT>(words, p);
 }
 
 // ------------------------------------------------------------------------------------ DC-bias removal, exact: products, the sequential chain
@@ -103,28 +88,15 @@ __global__ __launch_bounds__(256) void k_ingest_s16(const unsigned *__restrict__
 // Measured: 2.03 ms per 384 000-sample frame (4.5 ms for the one-workgroup pipeline of round 3, 9.3 ms for the one-wave
 // version of rounds 1-2); the floor of the recurrence itself is 384 000 x 12.25 cycles = 1.96 ms at 2.4 GHz.
 constexpr int kDcPad = 32 * 16 + 128; // floats behind the last sample of P / A: the chain's scalar prefetch runs two groups ahead, its line prefetch kDcAhead
-__global__ __launch_bounds__(256) void k_dc_products(const unsigned *__restrict__ bytes4, float *__restrict__ P, int n_complex, int stride)
-{
-    const int w = blockIdx.x * 256 + threadIdx.x; // one word = 2 complex samples
-    if (2 * w >= n_complex)
-        return;
-    const float k = 0.000001f;
-    const unsigned u = bytes4[w];
-    const v2f pi = {k * (float)((int)(u & 255u) - 127), k * (float)((int)((u >> 16) & 255u) - 127)};
-    const v2f pq = {k * (float)((int)((u >> 8) & 255u) - 127), k * (float)((int)(u >> 24) - 127)};
-    *(SDRX_AS1 v2f *)(P + 2 * w) = pi;
-    *(SDRX_AS1 v2f *)(P + stride + 2 * w) = pq;
-}
-// ... of a signed frame (signed_pair above): the same products of the same kind of value -- |x| <= 128 is what the chain kernels
-// below are proved for, and all they ever see is P.
+// (all the chain kernels below ever see is P, products of samples with |x| <= 128 whatever the format: what they are proved for)
 template <int FMT>
-__global__ __launch_bounds__(256) void k_dc_products_signed(const unsigned *__restrict__ words, float *__restrict__ P, int n_complex, int stride)
+__global__ __launch_bounds__(256) void k_dc_products(const unsigned *__restrict__ words, float *__restrict__ P, int n_complex, int stride)
 {
     const int w = blockIdx.x * 256 + threadIdx.x; // one pair = 2 complex samples
     if (2 * w >= n_complex)
         return;
     const float k = 0.000001f;
-    const float4 x = signed_pair<FMT>(words, w);
+    const float4 x = sample_pair<FMT>(words, w);
     const v2f pi = {k * x.x, k * x.z};
     const v2f pq = {k * x.y, k * x.w};
     *(SDRX_AS1 v2f *)(P + 2 * w) = pi;
@@ -545,46 +517,17 @@ __global__ __launch_bounds__(64 * NW) void k_dc_chain_spec(const float *__restri
 }
 
 // ------------------------------------------------------------------------------------ DC-bias removal, exact: apply
-// curr - avept in tile layout: one thread = the 16 samples behind one stored estimate = one lane's run of a tile
-__global__ __launch_bounds__(256) void k_dc_apply(const unsigned *__restrict__ bytes4, const float *__restrict__ A, float4 *__restrict__ tiled,
+// curr - avept in tile layout: one thread = the 16 samples behind one stored estimate = one lane's run of a tile.  They are
+// 32 bytes of an 8-bit format (two 16-byte loads of 4 pairs) or 64 bytes of int16 (four loads of 2 pairs), all inside the
+// frame: 16 j < n_complex and frames are multiples of 16
+template <int FMT>
+__global__ __launch_bounds__(256) void k_dc_apply(const unsigned *__restrict__ words, const float *__restrict__ A, float4 *__restrict__ tiled,
                                                   int n_complex, int stride)
 {
     const int j = blockIdx.x * 256 + threadIdx.x; // block of 16 samples
     if (16 * j >= n_complex)
         return;
-    const float keep = 1.0f - 0.000001f, k = 0.000001f;
-    float ai = A[j], aq = A[(stride >> 4) + j];
-    const v4u *src = reinterpret_cast<const v4u *>(bytes4) + 2 * j; // 32 bytes
-    const int ch = j >> 6, lane = j & 63;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const v4u q = gldv4u(src + h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const unsigned u = q[e];
-            const float x0 = (float)((int)(u & 255u) - 127), y0 = (float)((int)((u >> 8) & 255u) - 127);
-            const float x1 = (float)((int)((u >> 16) & 255u) - 127), y1 = (float)((int)(u >> 24) - 127);
-            ai = ai * keep + k * x0;
-            aq = aq * keep + k * y0;
-            float4 v;
-            v.x = x0 - ai, v.y = y0 - aq;
-            ai = ai * keep + k * x1;
-            aq = aq * keep + k * y1;
-            v.z = x1 - ai, v.w = y1 - aq;
-            tiled[tile_unit(ch, 4 * h + e, lane)] = v;
-        }
-    }
-}
-// ... of a signed frame: the thread's 16 samples are 32 bytes of int8 (two 16-byte loads of 4 pairs) or 64 bytes of int16 (four
-// loads of 2 pairs), all inside the frame: 16 j < n_complex and frames are multiples of 16
-template <int FMT>
-__global__ __launch_bounds__(256) void k_dc_apply_signed(const unsigned *__restrict__ words, const float *__restrict__ A, float4 *__restrict__ tiled,
-                                                         int n_complex, int stride)
-{
-    const int j = blockIdx.x * 256 + threadIdx.x; // block of 16 samples
-    if (16 * j >= n_complex)
-        return;
-    constexpr int kLoads = 2 * FMT, kPairs = 4 / FMT; // 16-byte loads per thread, pairs in each
+    constexpr int kLoads = FMT == SDRX_FMT_CS16 ? 4 : 2, kPairs = FMT == SDRX_FMT_CS16 ? 2 : 4; // 16-byte loads per thread, pairs in each
     const float keep = 1.0f - 0.000001f, k = 0.000001f;
     float ai = A[j], aq = A[(stride >> 4) + j];
     const v4u *src = reinterpret_cast<const v4u *>(words) + kLoads * j;
@@ -594,7 +537,7 @@ __global__ __launch_bounds__(256) void k_dc_apply_signed(const unsigned *__restr
         const v4u q = gldv4u(src + h);
 #pragma unroll
         for (int e = 0; e < kPairs; ++e) {
-            const float4 x = signed_pair_of<FMT>(q, e);
+            const float4 x = sample_pair_of<FMT>(q, e);
             ai = ai * keep + k * x.x;
             aq = aq * keep + k * x.y;
             float4 v;
@@ -612,7 +555,7 @@ __global__ __launch_bounds__(256) void k_dc_apply_signed(const unsigned *__restr
 // linear, a_t = A a_{t-1} + B x_t, so it is evaluated as a blocked scan -- per 1024-sample chunk
 // one wave runs 16 sequential steps per lane from zero, combines the 64 lane totals with a
 // log-step scan of affine maps, and adds the carry-in  A^(16 l + i + 1) * (state before the chunk).
-// k_dc_block_sums leaves each chunk's zero-state response; k_ingest_u8_dc_fast folds the responses
+// k_dc_block_sums leaves each chunk's zero-state response; k_ingest_dc_fast folds the responses
 // of all earlier chunks into its own carry-in (<= 375 terms, powers of A^1024 from a host table)
 // and writes the corrected chunk in tile layout.  Chunk-level sums are kept in double; against the
 // reference's sequentially ROUNDED fp32 recurrence the estimate differs by ~1e-5 of the DC offset
@@ -622,16 +565,20 @@ struct DcLocal {
     float ai[kRun], aq[kRun]; // zero-state response at each of the lane's 16 samples
     float xi[kRun], xq[kRun];
 };
-__device__ __forceinline__ void dc_local(const unsigned *__restrict__ bytes4, int base, int valid, int lane, DcLocal &L)
+// Behind a short last chunk the lanes go on with the format's neutral WORD -- the one whose samples are 0: 0x7f bytes, the
+// integer 0 of the signed formats -- decoded like a loaded one (a select between words, in front of the decode, not between
+// float4s behind it): nothing is read past the frame's n_complex samples.
+template <int FMT>
+__device__ __forceinline__ void dc_local(const unsigned *__restrict__ words, int base, int valid, int lane, DcLocal &L)
 {
+    constexpr unsigned kNeutral = FMT == SDRX_FMT_CU8 ? 0x7f7f7f7fu : 0u;
     const float keep = 1.0f - 0.000001f, k = 0.000001f;
     float ai = 0.f, aq = 0.f;
 #pragma unroll
     for (int i2 = 0; i2 < 8; ++i2) {
         const int s0 = lane * kRun + 2 * i2;
-        const unsigned w = s0 < valid ? bytes4[((base + s0) >> 1)] : 0x7f7f7f7fu;
-        const float x[4] = {(float)((int)(w & 255u) - 127), (float)((int)((w >> 8) & 255u) - 127), (float)((int)((w >> 16) & 255u) - 127),
-                            (float)((int)(w >> 24) - 127)};
+        const float4 v = decode_pair<FMT>(s0 < valid ? pair_words<FMT>(words, (base + s0) >> 1) : make_uint2(kNeutral, kNeutral));
+        const float x[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             ai = fmaf(ai, keep, k * x[2 * h]);
@@ -654,20 +601,22 @@ __device__ __forceinline__ void dc_wave_scan(double &si, double &sq, const doubl
         }
     }
 }
-__global__ __launch_bounds__(64) void k_dc_block_sums(const unsigned *__restrict__ bytes4, int n_complex, const double *__restrict__ dctab,
+template <int FMT>
+__global__ __launch_bounds__(64) void k_dc_block_sums(const unsigned *__restrict__ words, int n_complex, const double *__restrict__ dctab,
                                                       double2 *__restrict__ sums)
 {
     const int c = blockIdx.x, lane = threadIdx.x, base = c * kChunk;
     DcLocal L;
-    dc_local(bytes4, base, min(kChunk, n_complex - base), lane, L);
+    dc_local<FMT>(words, base, min(kChunk, n_complex - base), lane, L);
     double si = L.ai[kRun - 1], sq = L.aq[kRun - 1];
     dc_wave_scan(si, sq, dctab, lane);
     if (lane == 63)
         sums[c] = make_double2(si, sq);
 }
-__global__ __launch_bounds__(64) void k_ingest_u8_dc_fast(const unsigned *__restrict__ bytes4, float4 *__restrict__ tiled, int n_complex,
-                                                          const float *__restrict__ state_in, float *__restrict__ state_out,
-                                                          const double *__restrict__ dctab, const double2 *__restrict__ sums)
+template <int FMT>
+__global__ __launch_bounds__(64) void k_ingest_dc_fast(const unsigned *__restrict__ words, float4 *__restrict__ tiled, int n_complex,
+                                                       const float *__restrict__ state_in, float *__restrict__ state_out,
+                                                       const double *__restrict__ dctab, const double2 *__restrict__ sums)
 {
     const int c = blockIdx.x, lane = threadIdx.x, base = c * kChunk;
     const int valid = min(kChunk, n_complex - base);
@@ -687,92 +636,7 @@ __global__ __launch_bounds__(64) void k_ingest_u8_dc_fast(const unsigned *__rest
     ci = fma(dctab[96 + c], (double)state_in[0], ci);
     cq = fma(dctab[96 + c], (double)state_in[1], cq);
     DcLocal L;
-    dc_local(bytes4, base, valid, lane, L);
-    double si = L.ai[kRun - 1], sq = L.aq[kRun - 1];
-    dc_wave_scan(si, sq, dctab, lane);
-    double pi = __shfl_up(si, 1), pq = __shfl_up(sq, 1); // S_{l-1}
-    if (lane == 0)
-        pi = 0.0, pq = 0.0;
-    const double inc_i = fma(dctab[32 + lane], ci, pi), inc_q = fma(dctab[32 + lane], cq, pq); // state before this lane's run
-    float ai_last = 0.f, aq_last = 0.f;
-#pragma unroll
-    for (int i2 = 0; i2 < 8; ++i2) {
-        float y[4];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int i = 2 * i2 + h;
-            const float ai = (float)fma(dctab[i + 1], inc_i, (double)L.ai[i]);
-            const float aq = (float)fma(dctab[i + 1], inc_q, (double)L.aq[i]);
-            y[2 * h] = L.xi[i] - ai;
-            y[2 * h + 1] = L.xq[i] - aq;
-            ai_last = ai, aq_last = aq;
-        }
-        if (lane * kRun + 2 * i2 < valid)
-            tiled[tile_unit(c, i2, lane)] = make_float4(y[0], y[1], y[2], y[3]);
-    }
-    if (base + valid == n_complex && lane == (valid >> 4) - 1) { // the frame's last sample (frames are multiples of 16)
-        state_out[0] = ai_last;
-        state_out[1] = aq_last;
-    }
-}
-
-// ... of a signed frame: the same two kernels on signed_pair's samples.  The neutral word behind a short last chunk is the
-// sample 0 itself here (bytes: 0x7f, the byte whose sample is 0): nothing is read past the frame's n_complex samples.
-template <int FMT>
-__device__ __forceinline__ void dc_local_signed(const unsigned *__restrict__ words, int base, int valid, int lane, DcLocal &L)
-{
-    const float keep = 1.0f - 0.000001f, k = 0.000001f;
-    float ai = 0.f, aq = 0.f;
-#pragma unroll
-    for (int i2 = 0; i2 < 8; ++i2) {
-        const int s0 = lane * kRun + 2 * i2;
-        const float4 v = s0 < valid ? signed_pair<FMT>(words, (base + s0) >> 1) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            ai = fmaf(ai, keep, k * x[2 * h]);
-            aq = fmaf(aq, keep, k * x[2 * h + 1]);
-            L.ai[2 * i2 + h] = ai, L.aq[2 * i2 + h] = aq;
-            L.xi[2 * i2 + h] = x[2 * h], L.xq[2 * i2 + h] = x[2 * h + 1];
-        }
-    }
-}
-template <int FMT>
-__global__ __launch_bounds__(64) void k_dc_block_sums_signed(const unsigned *__restrict__ words, int n_complex, const double *__restrict__ dctab,
-                                                             double2 *__restrict__ sums)
-{
-    const int c = blockIdx.x, lane = threadIdx.x, base = c * kChunk;
-    DcLocal L;
-    dc_local_signed<FMT>(words, base, min(kChunk, n_complex - base), lane, L);
-    double si = L.ai[kRun - 1], sq = L.aq[kRun - 1];
-    dc_wave_scan(si, sq, dctab, lane);
-    if (lane == 63)
-        sums[c] = make_double2(si, sq);
-}
-template <int FMT>
-__global__ __launch_bounds__(64) void k_ingest_signed_dc_fast(const unsigned *__restrict__ words, float4 *__restrict__ tiled, int n_complex,
-                                                              const float *__restrict__ state_in, float *__restrict__ state_out,
-                                                              const double *__restrict__ dctab, const double2 *__restrict__ sums)
-{
-    const int c = blockIdx.x, lane = threadIdx.x, base = c * kChunk;
-    const int valid = min(kChunk, n_complex - base);
-    // carry-in of the chunk: the state before the frame and every earlier chunk's response
-    double ci = 0.0, cq = 0.0;
-    for (int j = lane; j < c; j += 64) {
-        const double m = dctab[96 + (c - 1 - j)];
-        const double2 b = sums[j];
-        ci = fma(m, b.x, ci);
-        cq = fma(m, b.y, cq);
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        ci += __shfl_xor(ci, d);
-        cq += __shfl_xor(cq, d);
-    }
-    ci = fma(dctab[96 + c], (double)state_in[0], ci);
-    cq = fma(dctab[96 + c], (double)state_in[1], cq);
-    DcLocal L;
-    dc_local_signed<FMT>(words, base, valid, lane, L);
+    dc_local<FMT>(words, base, valid, lane, L);
     double si = L.ai[kRun - 1], sq = L.aq[kRun - 1];
     dc_wave_scan(si, sq, dctab, lane);
     double pi = __shfl_up(si, 1), pq = __shfl_up(sq, 1); // S_{l-1}

@@ -12,16 +12,14 @@
 //   k_vfo_reset           nco.hip       (none: sdrx_set_active fills a leaf's state words between two frames, FillJob in sdrx_dev.h)
 //   k_nco_dump            nco.hip       (none: table entries regenerated from the checkpoints, for the parity tests)
 //   k_ingest_f32          ingest.hip    (none: a natural-order cf32 frame into the tile layout, sdrx_dev.h)
-//   k_ingest_u8           ingest.hip    floats[b] = b - 127, jonti/sdr.cpp:43-49,122-129 and sdrj.cpp:155-160, into the tile layout
-//   k_dc_products         ingest.hip    \
+//   k_ingest_samples<FMT> ingest.hip    floats[b] = b - 127, jonti/sdr.cpp:43-49,122-129 and sdrj.cpp:155-160, into the tile layout (FMT =
+//                                       SDRX_FMT_CU8; CS8 / CS16: none -- a wideband front end's int8 / int16 in the reference's units)
+//   k_dc_products<FMT>    ingest.hip    \
 //   k_dc_chain            ingest.hip     | sdrj::demodData's DC-bias removal, sdrj.cpp:271-286, bit for bit: k * curr of every sample; avept
 //   k_dc_chain_spec       ingest.hip     | sample by sample, or a verified block of 1024 at a time; curr -= avept into the tile layout
-//   k_dc_apply            ingest.hip    /
-//   k_dc_block_sums       ingest.hip    \ the same in the tolerance arithmetic: a blocked scan of the linear recurrence
-//   k_ingest_u8_dc_fast   ingest.hip    /
-//   k_ingest_s8, _s16     ingest.hip    (none: int8 / int16 samples of a wideband front end in the reference's units, SDRX_FMT_CS8 / CS16)
-//   k_dc_products_signed, k_dc_apply_signed, k_dc_block_sums_signed, k_ingest_signed_dc_fast
-//                         ingest.hip    the four DC kernels that read samples, for those formats (the chain kernels serve every format)
+//   k_dc_apply<FMT>       ingest.hip    /  (the kernels that read samples are templates on the format; the chain kernels serve every format)
+//   k_dc_block_sums<FMT>  ingest.hip    \ the same in the tolerance arithmetic: a blocked scan of the linear recurrence
+//   k_ingest_dc_fast<FMT> ingest.hip    /
 //   k_mix_decimate        mix.hip       vfo::process mix loop, vfo.cpp:237-245; HalfBandDecimator::decimate, halfbanddecimator.cpp:43-72,
 //                                       with FIR::...HalfBandQueue, dsp.cpp:96-173 (mix_item); option fuse_late: the FIR part of
 //                                       vfo::usb_decimdemod, vfo.cpp:334-356, inside a d = 0 leaf's wave (late_item); option fuse_demod:

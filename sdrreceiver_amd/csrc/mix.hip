@@ -214,9 +214,8 @@ __device__ __forceinline__ void load_run_raw(const void *__restrict__ raw, int r
             const v4u q = active ? gldv4u(nat + h) : z4;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const unsigned w = q[k];
-                const v2f a = {(float)((int)(w & 255u) - 127), (float)((int)((w >> 8) & 255u) - 127)};
-                const v2f b = {(float)((int)((w >> 16) & 255u) - 127), (float)((int)(w >> 24) - 127)};
+                const float4 s = cu8_pair(q[k]);
+                const v2f a = {s.x, s.y}, b = {s.z, s.w};
                 x[8 * h + 2 * k] = a;
                 x[8 * h + 2 * k + 1] = b;
             }

@@ -537,7 +537,7 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
             hipLaunchKernelGGL(k_ingest_f32, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream,
                                reinterpret_cast<const float4 *>(raw), reinterpret_cast<float4 *>(c->d_raw_tiled), n_pairs);
         else
-            hipLaunchKernelGGL(k_ingest_u8, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream,
+            hipLaunchKernelGGL(k_ingest_samples<SDRX_FMT_CU8>, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream,
                                reinterpret_cast<const unsigned *>(raw), reinterpret_cast<float4 *>(c->d_raw_tiled), n_pairs);
         raw_mode = kRawTiled;
     }
@@ -710,8 +710,7 @@ int enqueue_f32(sdrx_ctx *c, const float *iq, int n_complex, bool egress)
     return rc;
 }
 
-// The kernels that read a frame of integer samples, by format (include/sdrx.h SDRX_FMT_*): for CU8 the dongle-byte kernels
-// as they always were, for CS8 / CS16 their signed siblings (ingest.hip).
+// The kernels that read a frame of integer samples (ingest.hip), by format (include/sdrx.h SDRX_FMT_*): one template's instances.
 struct SampleKernels {
     void (*ingest)(const unsigned *, float4 *, int);
     void (*products)(const unsigned *, float *, int, int);
@@ -719,13 +718,14 @@ struct SampleKernels {
     void (*block_sums)(const unsigned *, int, const double *, double2 *);
     void (*dc_fast)(const unsigned *, float4 *, int, const float *, float *, const double *, const double2 *);
 };
+template <int FMT>
+SampleKernels sample_kernels_of()
+{
+    return {k_ingest_samples<FMT>, k_dc_products<FMT>, k_dc_apply<FMT>, k_dc_block_sums<FMT>, k_ingest_dc_fast<FMT>};
+}
 const SampleKernels &sample_kernels(int fmt)
 {
-    static const SampleKernels K[3] = {
-        {k_ingest_u8, k_dc_products, k_dc_apply, k_dc_block_sums, k_ingest_u8_dc_fast},
-        {k_ingest_s8, k_dc_products_signed<1>, k_dc_apply_signed<1>, k_dc_block_sums_signed<1>, k_ingest_signed_dc_fast<1>},
-        {k_ingest_s16, k_dc_products_signed<2>, k_dc_apply_signed<2>, k_dc_block_sums_signed<2>, k_ingest_signed_dc_fast<2>},
-    };
+    static const SampleKernels K[3] = {sample_kernels_of<SDRX_FMT_CU8>(), sample_kernels_of<SDRX_FMT_CS8>(), sample_kernels_of<SDRX_FMT_CS16>()};
     return K[fmt];
 }
 bool known_format(int fmt) { return fmt == SDRX_FMT_CU8 || fmt == SDRX_FMT_CS8 || fmt == SDRX_FMT_CS16; }
@@ -868,12 +868,6 @@ int sdrx_submit(sdrx_ctx *c, const float *iq, int n_complex)
     return rc ? rc : enqueue_f32(c, iq, n_complex, true);
 }
 
-int sdrx_submit_u8(sdrx_ctx *c, const uint8_t *bytes, int n_complex, int correct_dc)
-{
-    int rc = check_frame_call(c, "sdrx_submit_u8", bytes, n_complex, false);
-    return rc ? rc : enqueue_samples(c, bytes, n_complex, SDRX_FMT_CU8, correct_dc, true);
-}
-
 // The frame `src` staged LAST (host floats or dongle bytes handed to sdrx_process* / sdrx_submit* of `src`) once
 // more, through the tree of `c` -- two contexts on one device fed the same raw frame, as sdrj::demodData feeds
 // every main VFO the same `samples` (sdrj.cpp:288-294) -- without a second host-to-device copy: `c` waits for
@@ -971,15 +965,6 @@ int sdrx_process(sdrx_ctx *c, const float *iq, int n_complex)
     return rc ? rc : sdrx_wait(c);
 }
 
-int sdrx_process_u8(sdrx_ctx *c, const uint8_t *bytes, int n_complex, int correct_dc)
-{
-    int rc = check_frame_call(c, "sdrx_process_u8", bytes, n_complex, true);
-    if (rc)
-        return rc;
-    rc = enqueue_samples(c, bytes, n_complex, SDRX_FMT_CU8, correct_dc, true);
-    return rc ? rc : sdrx_wait(c);
-}
-
 // ---- one front door for integer samples (SDRX_FMT_*): host frames, and frames already on the device ------------------------
 static int frame_call_fmt(sdrx_ctx *c, const char *what, const void *ptr, int n_complex, int fmt, const void *dev_ptr, bool sync_call)
 {
@@ -991,19 +976,35 @@ static int frame_call_fmt(sdrx_ctx *c, const char *what, const void *ptr, int n_
     return SDRX_OK;
 }
 
+// A host frame through the call `what`: the four entry points below.  The *_u8 calls are the format SDRX_FMT_CU8 under their
+// own name: that format passes bad_samples, and a host frame has no alignment to test, so their checks are check_frame_call's.
+static int host_samples_call(sdrx_ctx *c, const char *what, const void *ptr, int n_complex, int fmt, int correct_dc, bool sync_call)
+{
+    int rc = frame_call_fmt(c, what, ptr, n_complex, fmt, nullptr, sync_call);
+    if (rc)
+        return rc;
+    rc = enqueue_samples(c, ptr, n_complex, fmt, correct_dc, true);
+    return rc || !sync_call ? rc : sdrx_wait(c);
+}
+
+int sdrx_submit_u8(sdrx_ctx *c, const uint8_t *bytes, int n_complex, int correct_dc)
+{
+    return host_samples_call(c, "sdrx_submit_u8", bytes, n_complex, SDRX_FMT_CU8, correct_dc, false);
+}
+
+int sdrx_process_u8(sdrx_ctx *c, const uint8_t *bytes, int n_complex, int correct_dc)
+{
+    return host_samples_call(c, "sdrx_process_u8", bytes, n_complex, SDRX_FMT_CU8, correct_dc, true);
+}
+
 int sdrx_submit_fmt(sdrx_ctx *c, const void *iq, int n_complex, int fmt, int correct_dc)
 {
-    const int rc = frame_call_fmt(c, "sdrx_submit_fmt", iq, n_complex, fmt, nullptr, false);
-    return rc ? rc : enqueue_samples(c, iq, n_complex, fmt, correct_dc, true);
+    return host_samples_call(c, "sdrx_submit_fmt", iq, n_complex, fmt, correct_dc, false);
 }
 
 int sdrx_process_fmt(sdrx_ctx *c, const void *iq, int n_complex, int fmt, int correct_dc)
 {
-    int rc = frame_call_fmt(c, "sdrx_process_fmt", iq, n_complex, fmt, nullptr, true);
-    if (rc)
-        return rc;
-    rc = enqueue_samples(c, iq, n_complex, fmt, correct_dc, true);
-    return rc ? rc : sdrx_wait(c);
+    return host_samples_call(c, "sdrx_process_fmt", iq, n_complex, fmt, correct_dc, true);
 }
 
 // (the samples are the caller's: where the frame went to level 0 as it lies -- dongle bytes without DC removal -- sdrx_get_raw

@@ -84,8 +84,9 @@ int group_check_ids(sdrx_group *g, const char *what, const int *ids, int n)
 }
 
 // frame (cf32 or bytes, `bytes` long) is complete on the first device at `src` once ev_ready[p] fires:
-// fan it out and enqueue frame processing on every member.
-int group_enqueue(sdrx_group *g, const void *src, size_t bytes, int raw_mode, bool egress, int correct_dc = 0, int fmt = SDRX_FMT_CU8)
+// fan it out and enqueue frame processing on every member.  `correct_dc` and `fmt` say what a kRawU8 frame holds (a cf32 frame:
+// 0 and SDRX_FMT_CU8).
+int group_enqueue(sdrx_group *g, const void *src, size_t bytes, int raw_mode, bool egress, int correct_dc, int fmt)
 {
     const int p = (int)(g->frame_no & 1ull);
     for (size_t k = 0; k < g->m.size(); ++k) {
@@ -453,53 +454,47 @@ int sdrx_group_submit(sdrx_group *g, const float *iq, int n_complex)
         return rc;
     const size_t bytes = (size_t)n_complex * sizeof(float2);
     rc = group_stage(g, iq, bytes);
-    return rc ? rc : group_enqueue(g, g->d_stage[g->frame_no & 1ull], bytes, kRawF32, true);
+    return rc ? rc : group_enqueue(g, g->d_stage[g->frame_no & 1ull], bytes, kRawF32, true, 0, SDRX_FMT_CU8);
 }
 
-// dongle bytes (jonti/sdr.cpp:43-49): a quarter of the bytes cross PCIe and xGMI; every device applies
-// the b - 127 LUT itself and, with correct_dc, the DC-bias IIR of sdrj.cpp:271-286 with an accumulator of
-// its own (the recurrence is sequential over the raw stream, so each member runs it on the whole frame: same
-// bytes, same start state, same result on every device -- nothing but the bytes is exchanged).
-int sdrx_group_submit_u8(sdrx_group *g, const uint8_t *bytes, int n_complex, int correct_dc)
+// Integer samples of any format (SDRX_FMT_*; dongle bytes, jonti/sdr.cpp:43-49, through the *_u8 calls: SDRX_FMT_CU8 under
+// their own name, a format that passes bad_samples, so their checks are group_check's).  The raw integers are what crosses
+// PCIe and xGMI -- 2 or 4 bytes a sample where a float frame takes 8 --; every device converts them itself and, with
+// correct_dc, runs the DC-bias IIR of sdrj.cpp:271-286 with an accumulator of its own (the recurrence is sequential over the
+// raw stream, so each member runs it on the whole frame: same samples, same start state, same result on every device --
+// nothing but the samples is exchanged).
+static int group_samples_call(sdrx_group *g, const char *what, const void *ptr, int n_complex, int fmt, int correct_dc, bool sync_call)
 {
-    int rc = group_check(g, "sdrx_group_submit_u8", bytes, n_complex, false);
+    int rc = group_check(g, what, ptr, n_complex, sync_call);
     if (rc)
         return rc;
-    const size_t nb = (size_t)n_complex * 2;
-    rc = group_stage(g, bytes, nb);
-    return rc ? rc : group_enqueue(g, g->d_stage[g->frame_no & 1ull], nb, kRawU8, true, correct_dc);
+    if (const char *why = bad_samples(fmt, nullptr))
+        return gfail(g, SDRX_EINVAL, "%s: %s", what, why);
+    const size_t nb = sample_bytes(fmt, n_complex);
+    rc = group_stage(g, ptr, nb);
+    if (!rc)
+        rc = group_enqueue(g, g->d_stage[g->frame_no & 1ull], nb, kRawU8, true, correct_dc, fmt);
+    return rc || !sync_call ? rc : sdrx_group_wait(g);
+}
+
+int sdrx_group_submit_u8(sdrx_group *g, const uint8_t *bytes, int n_complex, int correct_dc)
+{
+    return group_samples_call(g, "sdrx_group_submit_u8", bytes, n_complex, SDRX_FMT_CU8, correct_dc, false);
 }
 
 int sdrx_group_process_u8(sdrx_group *g, const uint8_t *bytes, int n_complex, int correct_dc)
 {
-    int rc = group_check(g, "sdrx_group_process_u8", bytes, n_complex, true);
-    if (rc)
-        return rc;
-    rc = sdrx_group_submit_u8(g, bytes, n_complex, correct_dc);
-    return rc ? rc : sdrx_group_wait(g);
+    return group_samples_call(g, "sdrx_group_process_u8", bytes, n_complex, SDRX_FMT_CU8, correct_dc, true);
 }
 
-// Integer samples of any format (SDRX_FMT_*): the raw integers are what is fanned out -- 2 or 4 bytes a sample where a
-// float frame takes 8 --, and every member converts them and, with correct_dc, runs the DC-bias IIR with its own accumulator.
 int sdrx_group_submit_fmt(sdrx_group *g, const void *iq, int n_complex, int fmt, int correct_dc)
 {
-    int rc = group_check(g, "sdrx_group_submit_fmt", iq, n_complex, false);
-    if (rc)
-        return rc;
-    if (const char *why = bad_samples(fmt, nullptr))
-        return gfail(g, SDRX_EINVAL, "sdrx_group_submit_fmt: %s", why);
-    const size_t nb = sample_bytes(fmt, n_complex);
-    rc = group_stage(g, iq, nb);
-    return rc ? rc : group_enqueue(g, g->d_stage[g->frame_no & 1ull], nb, kRawU8, true, correct_dc, fmt);
+    return group_samples_call(g, "sdrx_group_submit_fmt", iq, n_complex, fmt, correct_dc, false);
 }
 
 int sdrx_group_process_fmt(sdrx_group *g, const void *iq, int n_complex, int fmt, int correct_dc)
 {
-    int rc = group_check(g, "sdrx_group_process_fmt", iq, n_complex, true);
-    if (rc)
-        return rc;
-    rc = sdrx_group_submit_fmt(g, iq, n_complex, fmt, correct_dc);
-    return rc ? rc : sdrx_group_wait(g);
+    return group_samples_call(g, "sdrx_group_process_fmt", iq, n_complex, fmt, correct_dc, true);
 }
 
 // 1: every member reaches the first device's frame directly (same device, or peer access enabled: one xGMI
@@ -516,7 +511,7 @@ int sdrx_group_submit_device(sdrx_group *g, const void *dev_iq, int n_complex, v
         return rc;
     GHIP(g, hipSetDevice(g->m[0].device));
     GHIP(g, hipEventRecord(g->ev_ready[g->frame_no & 1ull], producer_stream ? reinterpret_cast<hipStream_t>(producer_stream) : g->stage_stream));
-    return group_enqueue(g, dev_iq, (size_t)n_complex * sizeof(float2), kRawF32, true);
+    return group_enqueue(g, dev_iq, (size_t)n_complex * sizeof(float2), kRawF32, true, 0, SDRX_FMT_CU8);
 }
 
 // The device-resident frame without the payload copies (cf. sdrx_process_device): every member queues its
@@ -528,7 +523,7 @@ int sdrx_group_process_device(sdrx_group *g, const void *dev_iq, int n_complex, 
         return rc;
     GHIP(g, hipSetDevice(g->m[0].device));
     GHIP(g, hipEventRecord(g->ev_ready[g->frame_no & 1ull], producer_stream ? reinterpret_cast<hipStream_t>(producer_stream) : g->stage_stream));
-    return group_enqueue(g, dev_iq, (size_t)n_complex * sizeof(float2), kRawF32, false);
+    return group_enqueue(g, dev_iq, (size_t)n_complex * sizeof(float2), kRawF32, false, 0, SDRX_FMT_CU8);
 }
 
 int sdrx_group_wait(sdrx_group *g)

@@ -305,6 +305,42 @@ def test_cs16_dc_bias_blocked_scan_option(Receiver):
     assert kt["k_ingest"]["ms"] / kt["k_ingest"]["launches"] < 0.1, kt["k_ingest"]
 
 
+@pytest.mark.parametrize("n", [1296, 69968])
+def test_blocked_scan_with_a_short_last_chunk(Receiver, n):
+    """Option dc_blocked_scan on frames that are no multiple of 1024: the padding behind the last chunk's samples, the guards on
+    its stores and the lane that leaves the state.  1296 = one chunk + 272 samples (17 lanes), the smallest frame with a short
+    last chunk and a carry-in; 69968 = 68 chunks + 336, where the carry-in loop runs more than one round per lane.  The same
+    bytes as dongle bytes, int8 and int16: one result bit for bit, within the usual tolerance of the float64 IIR response."""
+    import scipy.signal as sg
+    topo = _shape_tree(n, wide=False)
+    fmts = (ingest.CU8, ingest.CS8, ingest.CS16)
+    rxs = {fmt: Receiver.from_topology(topo, exact=True, keep_streams=True, dc_blocked_scan=True) for fmt in fmts}
+    rng = np.random.default_rng(n)
+    A = float(np.float32(1.0) - np.float32(0.000001))
+    B = float(np.float32(0.000001))
+    z = [np.zeros(1), np.zeros(1)]
+    for f in range(3):
+        b = rng.integers(0, 256, 2 * n, dtype=np.uint8)
+        b[0::2] = np.clip(b[0::2].astype(int) + 3, 0, 254)
+        b[1::2] = np.clip(b[1::2].astype(int) - 2, 0, 254)
+        rxs[ingest.CU8].process_u8(b, correct_dc=True)
+        rxs[ingest.CS8].process_fmt(embed_s8(b), correct_dc=True)
+        rxs[ingest.CS16].process_fmt(embed_s16(b), correct_dc=True)
+        for fmt in (ingest.CS8, ingest.CS16):
+            _check_twin(rxs[fmt], rxs[ingest.CU8], topo, (n, NAME[fmt], f))
+        x = ob.u8_to_float(b)
+        iq = x.copy()
+        for comp in (0, 1):
+            a, z[comp] = sg.lfilter([B], [1.0, -A], x[comp::2].astype(np.float64), zi=z[comp])
+            iq[comp::2] = x[comp::2] - a.astype(np.float32)
+        got = rxs[ingest.CU8].raw()
+        err = float(np.abs(got - iq.view(np.complex64)).max())
+        print(f"n {n} frame {f}: max |raw - model| {err:.3g}, bound {REL_TOL * float(np.abs(x).max()):.3g}")
+        assert got.size == n and err <= REL_TOL * float(np.abs(x).max()), (n, f, err)
+    for rx in rxs.values():
+        rx.close()
+
+
 # ------------------------------------------------------------------------------------------- 9. launch forms
 def _forms_tree(n=20480):
     t = tp.Topology(fs=4 * n, frame=n, name="fmtforms")

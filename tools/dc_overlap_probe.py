@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/dc_overlap_probe.py [sync|pipelined|both] [frames] -- dongle bytes with the exact DC-bias removal (sdrj.cpp:271-286)
-through config 3, frame after frame: ms per frame, and the event-timed ingest group (k_dc_products + k_dc_chain +
-k_dc_apply) per frame, synchronous (sdrx_process_u8) and pipelined (sdrx_submit_u8 / sdrx_wait).  Run it under
+through config 3, frame after frame: ms per frame, and the event-timed ingest group (k_dc_products<CU8> + k_dc_chain +
+k_dc_apply<CU8>) per frame, synchronous (sdrx_process_u8) and pipelined (sdrx_submit_u8 / sdrx_wait).  Run it under
 `rocprofv3 --kernel-trace --stats` for k_dc_chain's own duration in each mode."""
 import json
 import os

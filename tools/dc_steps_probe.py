@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/dc_steps_probe.py [frames] -- the exact DC-bias removal (k_dc_products + k_dc_chain_spec + k_dc_apply, event-timed as
+"""tools/dc_steps_probe.py [frames] -- the exact DC-bias removal (k_dc_products<CU8> + k_dc_chain_spec + k_dc_apply<CU8>, event-timed as
 one group) for every value of option dc_blocks_per_step, on the capture-like stream, a quiet front end and the zero-offset LCG
 frames; with the counters: blocks walked / taken again on their own / redone with the sequential operations."""
 import json

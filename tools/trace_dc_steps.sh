@@ -1,6 +1,7 @@
 #!/bin/bash
-# tools/trace_dc_steps.sh -- per-kernel durations (rocprofv3 --kernel-trace --stats) of tools/dc_steps_probe.py: k_dc_products,
-# k_dc_chain_spec<NW>, k_dc_apply on its four byte streams.  PER_STEP as for the probe.
+# tools/trace_dc_steps.sh -- per-kernel durations (rocprofv3 --kernel-trace --stats) of tools/dc_steps_probe.py: k_dc_products<0>,
+# k_dc_chain_spec<NW>, k_dc_apply<0> on its four byte streams (the sample kernels are templates on the format, 0 = SDRX_FMT_CU8; a
+# key below is the name with its template arguments, one per kernel).  PER_STEP as for the probe.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/trace_dc_steps; rm -rf $OUT; mkdir -p $OUT
 rocprofv3 --kernel-trace --stats -d $OUT -o t --output-format csv -- python3 tools/dc_steps_probe.py 16 > $OUT/probe.txt 2> $OUT/err.txt
