@@ -38,6 +38,8 @@
 #include "scan.hip"
 #include "tapdesign.h"
 
+#include "sdrx_mem.h"
+
 using namespace sdrx;
 
 static_assert(sizeof(sdrx_vfo_desc) == 56 && offsetof(sdrx_vfo_desc, topic) == 48, "sdrx_vfo_desc ABI layout");
@@ -92,84 +94,21 @@ std::vector<float2> spectrum_tables()
 
 namespace {
 
+// Everything a context holds on the device and in pinned memory, released with the context's device current; the context is as
+// before sdrx_finalize and its first uses.  What stays is host-side: the option dc.waves, the gate's events (sq.ev_dir) and its
+// host copies, which squelch_setup sizes again, and the host's view of option park.
 void free_device_state(sdrx_ctx *c)
 {
-    auto dfree = [](auto *&p) {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-    };
-    auto hfree = [](unsigned char *&p) {
-        if (p)
-            (void)hipHostFree(p);
-        p = nullptr;
-    };
-    for (auto &kv : c->taps)
-        if (kv.second.own)
-            for (int p = 0; p < 2; ++p)
-                (void)hipFree(kv.second.buf[p]);
     c->taps.clear();
-    dfree(c->arena);
-    for (int p = 0; p < 2; ++p) {
-        dfree(c->d_pay[p]);
-        hfree(c->h_pay[p]);
-        hfree(c->h_in[p]);
-    }
-    c->h_in_bytes = 0;
-    for (int p = 0; p < 2; ++p) {
-        dfree(c->d_raw[p]);
-        dfree(c->d_raw_u8[p]);
-    }
-    dfree(c->d_raw_tiled);
-    c->raw_cap = 0;
-    dfree(c->d_jobs);
-    c->jobs_cap = 0;
-    // DC-bias removal (the option dc.waves stays)
-    dfree(c->dc.d_state);
-    dfree(c->dc.d_work);
-    dfree(c->dc.d_counters);
-    dfree(c->dc.d_tab);
-    c->dc.work_stride = 0;
-    // spectrum display: as before the first sdrx_set_spectrum
-    for (auto &s : c->spec.slots)
-        dfree(s.pwr);
-    dfree(c->spec.d_rec);
-    dfree(c->spec.d_tw);
-    dfree(c->spec.d_desc);
-    c->spec = sdrx_ctx::Spectrum();
-    // squelch and pre-roll: the buffers and what describes them (the host copies are sized again by squelch_setup; ev_dir stays)
-    for (int p = 0; p < 2; ++p)
-        dfree(c->sq.d_pack[p]);
-    dfree(c->sq.d_leaves);
-    dfree(c->sq.d_cfg);
-    dfree(c->sq.d_hang);
-    dfree(c->sq.d_prev);
-    dfree(c->sq.d_auto);
-    dfree(c->sq.d_jobs);
-    c->sq.jobs_cap = 0;
-    dfree(c->park.d_act);
-    dfree(c->park.d_jobs);
-    c->park.jobs_cap = 0;
-    c->sq.bytes = c->sq.dir_off = c->sq.pack_bytes = c->sq.hpack_off = 0;
-    dfree(c->agc.d_leaves);
-    dfree(c->agc.d_cfg);
-    dfree(c->agc.d_quiet);
-    dfree(c->agc.d_jobs);
+    static_cast<CtxBuffers &>(*c) = CtxBuffers();
+    static_cast<sdrx_ctx::DcDevice &>(c->dc) = sdrx_ctx::DcDevice();
+    static_cast<sdrx_ctx::SquelchDevice &>(c->sq) = sdrx_ctx::SquelchDevice();
+    static_cast<sdrx_ctx::ParkDevice &>(c->park) = sdrx_ctx::ParkDevice();
     c->agc = sdrx_ctx::Agc();
-    // channel watch, drift estimate and band scan: as before the first sdrx_set_watch / sdrx_set_drift / sdrx_set_scan
-    dfree(c->watch.d_desc);
-    dfree(c->watch.d_data);
-    dfree(c->watch.d_tw);
-    records_free(c->watch.rec);
+    c->spec = sdrx_ctx::Spectrum();
     c->watch = sdrx_ctx::Watch();
-    analysis_release(c->drift);
-    analysis_release(c->scan);
-    // device-side wake: as before the first sdrx_set_wake
-    dfree(c->wake.d_leaf);
-    dfree(c->wake.d_state);
-    dfree(c->wake.d_list);
-    dfree(c->wake.d_fill);
-    records_free(c->wake.rec);
+    c->drift = sdrx_ctx::Drift();
+    c->scan = sdrx_ctx::Scan();
     c->wake = sdrx_ctx::Wake();
 }
 
@@ -523,9 +462,6 @@ static int tap_change_impl(sdrx_ctx *c, int id, bool replace, const char *what)
                 continue;
             }
             HIPCHK(c, point(it->first, nullptr, nullptr));
-            if (it->second.own)
-                for (int p = 0; p < 2; ++p)
-                    (void)hipFree(it->second.buf[p]);
             it = c->taps.erase(it);
         }
     }
@@ -535,21 +471,19 @@ static int tap_change_impl(sdrx_ctx *c, int id, bool replace, const char *what)
     t.since = c->frame_no;
     bool arena_free = c->tap_len > 0;
     for (const auto &kv : c->taps)
-        arena_free = arena_free && kv.second.own;
+        arena_free = arena_free && kv.second.own[0];
     if (arena_free) {
         for (int p = 0; p < 2; ++p)
             t.buf[p] = reinterpret_cast<float2 *>(c->arena + c->off_tapbuf[p]);
     } else {
-        t.own = true;
-        for (int p = 0; p < 2; ++p)
-            if (hipMalloc(&t.buf[p], sizeof(float2) * (size_t)c->nodes[(size_t)id].n_f) != hipSuccess) {
-                if (t.buf[0])
-                    (void)hipFree(t.buf[0]);
+        for (int p = 0; p < 2; ++p) {
+            if (t.own[p].alloc((size_t)c->nodes[(size_t)id].n_f) != hipSuccess)
                 return fail(c, SDRX_ENOMEM, "%s: no device memory for another tap buffer", what);
-            }
+            t.buf[p] = t.own[p];
+        }
     }
     HIPCHK(c, point(id, t.buf[0], t.buf[1]));
-    c->taps.emplace(id, t);
+    c->taps.emplace(id, std::move(t));
     return SDRX_OK;
 }
 
@@ -624,7 +558,7 @@ int apply_vfo_jobs(sdrx_ctx *c, const int *ids, const double *freqs, const float
         }
     }
     if (!jobs.empty()) {
-        if (int rc = upload_jobs(c, c->d_jobs, c->jobs_cap, jobs.data(), sizeof(RetuneJob) * jobs.size()))
+        if (int rc = upload_jobs(c, c->d_jobs, jobs.data(), jobs.size()))
             return rc;
         const int nj = (int)jobs.size();
         hipLaunchKernelGGL(k_vfo_retune, dim3((nj + 63) / 64), dim3(64), 0, c->st.stream, c->d_jobs, nj);
@@ -780,9 +714,9 @@ int apply_active(sdrx_ctx *c, const int *ids, const int32_t *active, int n)
             memcpy(host.data() + fb, tunes.data(), sizeof(RetuneJob) * tunes.size());
         if (!lists.empty())
             memcpy(host.data() + jb, lists.data(), lists.size());
-        if (int rc = upload_jobs(c, K.d_jobs, K.jobs_cap, host.data(), bytes))
+        if (int rc = upload_jobs(c, K.d_jobs, host.data(), bytes))
             return rc;
-        hipLaunchKernelGGL(k_vfo_reset, dim3((unsigned)fills.size()), dim3(256), 0, c->st.stream, reinterpret_cast<const FillJob *>(K.d_jobs));
+        hipLaunchKernelGGL(k_vfo_reset, dim3((unsigned)fills.size()), dim3(256), 0, c->st.stream, reinterpret_cast<const FillJob *>(K.d_jobs.get()));
         if (!tunes.empty()) {
             const int nj = (int)tunes.size();
             hipLaunchKernelGGL(k_vfo_retune, dim3((nj + 63) / 64), dim3(64), 0, c->st.stream, reinterpret_cast<const RetuneJob *>(K.d_jobs + fb), nj);
@@ -990,6 +924,20 @@ int sdrx_get_stream(sdrx_ctx *c, int id, float *out, int max_complex, int *n_ret
     return SDRX_OK;
 }
 
+// the first spectrum: tables (the reference's own double expressions) and per-slot records
+static int spectrum_first_use(sdrx_ctx *c)
+{
+    const size_t slots = c->nodes.size() + 1;
+    const std::vector<float2> tab = spectrum_tables();
+    HIPCHK(c, c->spec.d_tw.alloc(tab.size()));
+    HIPCHK(c, hipMemcpy(c->spec.d_tw, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, c->spec.d_rec.alloc(slots));
+    HIPCHK(c, hipMemsetAsync(c->spec.d_rec, 0, sizeof(SpecRecord) * slots, c->st.stream));
+    HIPCHK(c, c->spec.d_desc.alloc(slots));
+    c->spec.slots.resize(slots);
+    return SDRX_OK;
+}
+
 int sdrx_set_spectrum(sdrx_ctx *c, int id, int enable)
 {
     if (!c)
@@ -1007,23 +955,18 @@ int sdrx_set_spectrum(sdrx_ctx *c, int id, int enable)
     if (enable && id >= 0 && c->wake.controlled(id))
         return fail(c, SDRX_EINVAL, "sdrx_set_spectrum: vfo %d is under the device's wake control (sdrx_set_wake)", id);
     const int slot = id < 0 ? N : id;
-    if (c->spec.slots.empty()) { // the first spectrum: tables (the reference's own double expressions) and per-slot records
-        const std::vector<float2> tab = spectrum_tables();
-        HIPCHK(c, hipMalloc(&c->spec.d_tw, sizeof(float2) * tab.size()));
-        HIPCHK(c, hipMemcpy(c->spec.d_tw, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMalloc(&c->spec.d_rec, sizeof(SpecRecord) * (size_t)(N + 1)));
-        HIPCHK(c, hipMemsetAsync(c->spec.d_rec, 0, sizeof(SpecRecord) * (size_t)(N + 1), c->st.stream));
-        HIPCHK(c, hipMalloc(&c->spec.d_desc, sizeof(SpecDesc) * (size_t)(N + 1)));
-        c->spec.slots.assign((size_t)N + 1, sdrx_ctx::SpecState());
+    if (c->spec.slots.empty()) {
+        if (int rc = spectrum_first_use(c)) {
+            c->spec = sdrx_ctx::Spectrum();
+            return rc;
+        }
     }
     sdrx_ctx::SpecState &S = c->spec.slots[(size_t)slot];
     if (enable) {
-        if (!S.pwr && hipMalloc(&S.pwr, (sizeof(double) + sizeof(float2)) * kSpecN) != hipSuccess) {
-            S.pwr = nullptr;
+        if (!S.pwr && S.pwr.alloc(2 * (size_t)kSpecN) != hipSuccess)
             return fail(c, SDRX_ENOMEM, "sdrx_set_spectrum: no device memory for the spectrum of vfo %d", id);
-        }
         // the combo-box reset (mainwindow.cpp:539-549): pwr and the window input zeroed, sdrj's count = 0
-        HIPCHK(c, hipMemsetAsync(S.pwr, 0, (sizeof(double) + sizeof(float2)) * kSpecN, c->st.stream));
+        HIPCHK(c, hipMemsetAsync(S.pwr, 0, S.pwr.bytes(), c->st.stream));
         HIPCHK(c, hipStreamSynchronize(c->st.stream)); // (the context's streams do not synchronise with the null stream)
         SpecRecord r;
         memset(&r, 0, sizeof r);
@@ -1033,9 +976,7 @@ int sdrx_set_spectrum(sdrx_ctx *c, int id, int enable)
         if (id < 0)
             c->spec.raw_count = 0;
     } else {
-        if (S.pwr)
-            (void)hipFree(S.pwr);
-        S.pwr = nullptr;
+        S.pwr.reset();
         S.on = false;
     }
     return spectrum_rebuild(c);
@@ -1166,14 +1107,14 @@ int sdrx_get_nco(sdrx_ctx *c, int id, long first, long count, float *out)
     if (count == 0)
         return SDRX_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    float2 *tmp = nullptr;
-    HIPCHK(c, hipMalloc(&tmp, sizeof(float2) * (size_t)count));
+    DevBuf<float2> tmp;
+    HIPCHK(c, tmp.alloc((size_t)count));
     hipLaunchKernelGGL(k_nco_dump, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->st.stream,
                        reinterpret_cast<const float2 *>(c->arena + n.off_cp), n.rot_re, n.rot_im, first, count, tmp);
     hipError_t e = hipStreamSynchronize(c->st.stream);
     if (e == hipSuccess)
         e = hipMemcpy(out, tmp, sizeof(float2) * (size_t)count, hipMemcpyDeviceToHost);
-    (void)hipFree(tmp);
+    tmp.reset();
     if (e != hipSuccess)
         return fail(c, SDRX_EHIP, "sdrx_get_nco: %s", hipGetErrorString(e));
     return SDRX_OK;
@@ -1191,7 +1132,8 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->exact = c->opt_exact;
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + c->raw_cap * 10 + c->sq.bytes + sizeof(int) * c->park.words + c->watch.bytes + c->drift.bytes + c->scan.bytes + c->agc.bytes + c->wake.bytes);
+    const size_t raw_bytes = c->d_raw[0].bytes() + c->d_raw_u8[0].bytes(); // (ONE parity of the host-fed frames' buffers: kept for compatibility)
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes());
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

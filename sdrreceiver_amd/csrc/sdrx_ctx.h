@@ -94,9 +94,24 @@ struct TimedEvent {
     int64_t bytes;
 };
 
+// The buffers of a context that belong to no option (free_device_state releases them as one).
+struct CtxBuffers {
+    DevBuf<unsigned char> arena;
+    DevBuf<unsigned char> d_pay[2]; // per frame parity
+    PinBuf<unsigned char> h_pay[2];
+    PinBuf<unsigned char> h_in[2];  // pinned staging of host-fed frames, per frame parity
+    // host-fed frames on the device (natural order), per frame parity: frame f's buffer stays untouched until f+2 is staged
+    // (another context on this device may be working on it: sdrx_submit_shared); and the same for dongle bytes.  All four or
+    // none (ensure_raw).
+    DevBuf<float2> d_raw[2];
+    DevBuf<unsigned char> d_raw_u8[2];
+    DevBuf<float2> d_raw_tiled; // the raw frame in tile layout: input of the parent-less VFOs
+    DevBuf<RetuneJob> d_jobs;   // k_vfo_retune's job list (sdrx_set_mixer_freqs, sdrx_set_gains), grown on demand
+};
+
 } // namespace
 
-struct sdrx_ctx {
+struct sdrx_ctx : CtxBuffers {
     int device = 0;
     std::string err;
     std::vector<Node> nodes;
@@ -120,16 +135,19 @@ struct sdrx_ctx {
     // fixed part of h_pay[p] (at hpack_off; 0 with the option off: the start of h_pay[p], as before).
     // Option squelch_auto: the threshold follows each leaf's noise floor.  One SqAuto record per leaf on the
     // device (floor state and settings); the directory gains thr_eff[n] | floor[n] (u64) at aux_off, behind everything else.
-    struct Squelch {
-        size_t dir_off = 0, pack_bytes = 0, bytes = 0; // bytes: what the option allocates besides the directory
-        unsigned char *d_pack[2] = {nullptr, nullptr};
-        SqLeaf *d_leaves = nullptr;
-        SqCfg *d_cfg = nullptr;
-        unsigned *d_hang = nullptr; // hang_left per leaf: one array, every gate runs in frame order on one stream
-        unsigned *d_prev = nullptr; // prev_open per leaf (preroll)
-        SqAuto *d_auto = nullptr;   // floor state and settings per leaf (squelch_auto)
-        SqJob *d_jobs = nullptr;    // job list of sdrx_set_squelch and (as SqAutoJob) of sdrx_set_squelch_auto
-        size_t jobs_cap = 0;        //   ... its size in bytes (upload_jobs)
+    struct SquelchDevice { // the buffers and what describes them: what free_device_state puts back
+        size_t dir_off = 0, pack_bytes = 0, hpack_off = 0;
+        DevBuf<unsigned char> d_pack[2];
+        DevBuf<SqLeaf> d_leaves;
+        DevBuf<SqCfg> d_cfg;
+        DevBuf<unsigned> d_hang; // hang_left per leaf: one array, every gate runs in frame order on one stream
+        DevBuf<unsigned> d_prev; // prev_open per leaf (preroll)
+        DevBuf<SqAuto> d_auto;   // floor state and settings per leaf (squelch_auto)
+        DevBuf<unsigned char> d_jobs; // job list of sdrx_set_squelch (SqJob) and of sdrx_set_squelch_auto (SqAutoJob), grown on demand
+        // what the option holds besides the directory (the job list is not counted)
+        size_t bytes() const { return d_leaves.bytes() + d_cfg.bytes() + d_hang.bytes() + d_prev.bytes() + d_auto.bytes() + d_pack[0].bytes() + d_pack[1].bytes(); }
+    };
+    struct Squelch : SquelchDevice {
         int tiles = 1;                        // k_squelch_gather's grid.y: 16 KiB tiles of the longest payload
         std::vector<int> index;               // node -> its place in publish order (-1: not a leaf)
         std::vector<SqCfg> cfg;               // host copy of the thresholds
@@ -137,7 +155,6 @@ struct sdrx_ctx {
         unsigned n_open = 0;                  //   ... its header
         unsigned long long copied = 0;        //   ... and the payload bytes its copy moved
         unsigned long long copied_slot[2] = {0, 0};
-        size_t hpack_off = 0;
         bool preroll_fused = false;           // a leaf demodulates in its mix wave: the levels write d_pay (enqueue_frame)
         std::vector<unsigned> pre, units;     // the delivered directory's pre-roll flags; 64-byte units of every leaf's payload
         unsigned n_pre = 0;                   // pre-rolled leaves of the delivered frame
@@ -153,14 +170,14 @@ struct sdrx_ctx {
     // part that always travels.  On the device the static table, the settings and quiet_run (one array: the steps run in frame
     // order on one stream, as the gates do).
     struct Agc {
-        size_t rec_off = 0, bytes = 0; // bytes: device memory the option holds besides the records
+        size_t rec_off = 0;
         int n = 0;                     // slots
         std::vector<int> slot;         // node -> its slot (-1: not a USB leaf)
-        AgcLeaf *d_leaves = nullptr;
-        AgcCfg *d_cfg = nullptr;
-        unsigned *d_quiet = nullptr;
-        AgcJob *d_jobs = nullptr; // job list of sdrx_set_agc
-        size_t jobs_cap = 0;      //   ... its size in bytes (upload_jobs)
+        DevBuf<AgcLeaf> d_leaves;
+        DevBuf<AgcCfg> d_cfg;
+        DevBuf<unsigned> d_quiet;
+        DevBuf<AgcJob> d_jobs; // job list of sdrx_set_agc, grown on demand
+        size_t bytes() const { return d_leaves.bytes() + d_cfg.bytes() + d_quiet.bytes(); } // device memory the option holds besides the records and the job list
         std::vector<sdrx_agc_cfg> cfg; // host copy of the settings, per node (a compress() leaf's are stored too)
     } agc;
 
@@ -169,8 +186,11 @@ struct sdrx_ctx {
     // The host's copy of a leaf's state is what the getters and the delivery serve: a frame f >= since ran in state `active`,
     // the frames before it (the last one may not be fetched yet) in state `was_active`.  (A leaf under option wake's control is the
     // exception: the device decides, and the answers come from the frame's wake record -- leaf_parked_at, sdrx_delivery.hip.)
-    struct Park {
-        int *d_act = nullptr;
+    struct ParkDevice { // what free_device_state releases
+        DevBuf<int> d_act;
+        DevBuf<unsigned char> d_jobs; // job lists of sdrx_set_active: FillJob[] | RetuneJob[], grown on demand
+    };
+    struct Park : ParkDevice {
         size_t o_2a = 0, o_2 = 0, o_3 = 0, o_4 = 0, o_sq = 0, words = 0;
         struct Leaf {
             int active = 1, was_active = 1;
@@ -178,8 +198,6 @@ struct sdrx_ctx {
         };
         std::vector<Leaf> leaf; // per node (leaves only are ever changed)
         std::vector<std::vector<int>> items; // per node: its entries of LevelPlan's item_level[] (bit kParkBit; with a level plan)
-        unsigned char *d_jobs = nullptr; // job lists of sdrx_set_active: FillJob[] | RetuneJob[], grown on demand
-        size_t jobs_cap = 0;
         bool parked_at(int id, unsigned long long frame) const
         {
             if (leaf.empty())
@@ -214,14 +232,25 @@ struct sdrx_ctx {
         int at(unsigned long long frame) const { return frame >= since ? v : was; }
     };
     // Records of frame f: written to d[f & 1] on the device, they travel to h[f & 1] (pinned) with the frame's fixed-size part
-    // (queue_watch, sdrx_delivery.hip).  records_alloc / records_free, sdrx_watch.hip.
+    // (queue_watch, sdrx_delivery.hip).
     struct Records {
-        void *d[2] = {nullptr, nullptr}, *h[2] = {nullptr, nullptr};
-        size_t bytes = 0; // of one buffer; 0: not allocated
+        DevBuf<unsigned char> d[2];
+        PinBuf<unsigned char> h[2];
+        size_t bytes() const { return d[0].bytes(); } // of one buffer; 0: not allocated
+        hipError_t alloc(size_t n) // all four, zeroed, or none
+        {
+            hipError_t e = hipSuccess;
+            for (int p = 0; p < 2 && e == hipSuccess; ++p)
+                if ((e = d[p].alloc(n, true)) == hipSuccess)
+                    e = h[p].alloc(n, true);
+            if (e != hipSuccess)
+                *this = Records();
+            return e;
+        }
         template <class R>
-        R *dev(int p) const { return static_cast<R *>(d[p]); }
+        R *dev(int p) const { return reinterpret_cast<R *>(d[p].get()); }
         template <class R>
-        const R *host(int p) const { return static_cast<const R *>(h[p]); }
+        const R *host(int p) const { return reinterpret_cast<const R *>(h[p].get()); }
     };
 
     // Option watch (sdrx_set_watch, watch.hip).  Host bookkeeping per leaf: whether it is watched (`on`, a Switched).
@@ -229,7 +258,14 @@ struct sdrx_ctx {
     // sequence launches nothing more.  The records of frame f -- one slot per leaf -- are `rec`.
     // A SOURCE is what a watched leaf's band is read from: index 0 the raw frame, 1 + id the stream of node id.  Every non-leaf
     // has a slot (src_slot, in node order) for the records of the analyses below.
-    struct Watch {
+    struct WatchDevice { // what the first sdrx_set_watch allocates, all of it or none
+        DevBuf<unsigned char> d_desc; // WatchSrc[n_src_slots] | WatchSeg[kWatchMaxSeg n_src_slots] | WatchLeaf[n_slots]
+        DevBuf<unsigned char> d_data; // per measured source: P[S][kSpecN] f32 | PSD[kSpecN] + total f64 | done u32; grown on demand
+        DevBuf<float2> d_tw;          // kiss_fft's twiddles, then the Hann window (as Spectrum::d_tw)
+        Records rec;                  // WatchRecord[n_slots]
+        size_t bytes() const { return d_desc.bytes() + d_tw.bytes() + 2 * rec.bytes() + d_data.bytes(); } // device memory the option holds
+    };
+    struct Watch : WatchDevice {
         struct Leaf {
             Switched on;
             int first_bin = 0, n_bins = 1; // the band (watch_band), as the descriptor stands
@@ -239,18 +275,12 @@ struct sdrx_ctx {
         int n_slots = 0;
         std::vector<int> src_slot; // per source index: its slot (-1: a leaf's stream feeds nobody)
         int n_src_slots = 0;
-        unsigned char *d_desc = nullptr; // WatchSrc[n_src_slots] | WatchSeg[kWatchMaxSeg n_src_slots] | WatchLeaf[n_slots]
-        unsigned char *d_data = nullptr; // per measured source: P[S][kSpecN] f32 | PSD[kSpecN] + total f64 | done u32
-        size_t data_cap = 0;
-        float2 *d_tw = nullptr;          // kiss_fft's twiddles, then the Hann window (as Spectrum::d_tw)
-        Records rec;                     // WatchRecord[n_slots]
-        size_t bytes = 0;                // device memory the option holds
         std::vector<int> src_ids;        // the measured sources in launch order: -1 the raw frame, else the parent's node id
         std::vector<size_t> src_psd;     // ... where each one's PSD lies in d_data
         std::vector<int> seg_begin, leaf_begin; // per source group (0: the raw frame, 1 + l: parents on tree level l), n_levels + 2 entries
         std::vector<WatchLeaf> launch_leaves;   // the host's copy of the WatchLeaf list (what option wake's launch list is cut from)
         unsigned long long psd_since = 0; // the PSD buffers hold a frame only once frame_no > psd_since
-        WatchSrc *d_src() const { return reinterpret_cast<WatchSrc *>(d_desc); }
+        WatchSrc *d_src() const { return reinterpret_cast<WatchSrc *>(d_desc.get()); }
         WatchSeg *d_seg() const { return reinterpret_cast<WatchSeg *>(d_desc + sizeof(WatchSrc) * (size_t)n_src_slots); }
         WatchLeaf *d_leaf() const { return reinterpret_cast<WatchLeaf *>(d_desc + (sizeof(WatchSrc) + sizeof(WatchSeg) * kWatchMaxSeg) * (size_t)n_src_slots); }
         bool watched_at(int id, unsigned long long frame) const { return !leaf.empty() && leaf[(size_t)id].on.at(frame) != 0; }
@@ -261,30 +291,36 @@ struct sdrx_ctx {
     // (d_state, state_bytes) from the first call that switches it on: nothing the watch moves or clears touches it.  The launch
     // list in d_desc names the sources that have it among the measured ones, rebuilt with the watch's own (walk_sources); the
     // record of frame f -- one slot per possible source, Watch::src_slot -- is in `rec`.  Everything is allocated by the first
-    // call that switches a source on (analysis_alloc), and released by analysis_release: sdrx_watch.hip has the shared steps.
+    // call that switches a source on (analysis_alloc): sdrx_watch.hip has the shared steps.
     struct SourceAnalysis {
         struct Src {
             Switched on; // the value that switches it (0: off)
-            void *d_state = nullptr;
+            DevBuf<unsigned char> d_state;
         };
         std::vector<Src> src; // per source index; sized by the first call
-        unsigned char *d_desc = nullptr;
+        DevBuf<unsigned char> d_desc;
         Records rec;
-        size_t bytes = 0;       // device memory it holds
+        size_t bytes() const // device memory it holds
+        {
+            size_t b = d_desc.bytes() + 2 * rec.bytes();
+            for (const Src &s : src)
+                b += s.d_state.bytes();
+            return b;
+        }
         std::vector<int> begin; // first launch entry per source group (as Watch::seg_begin), n_levels + 2 entries; empty: never switched on
     };
     // Drift estimate (sdrx_set_drift, drift.hip): switched by max_shift K.  d_state: a DriftState (template, last
     // profile, two words of launch state); d_desc: DriftSrc[n_src_slots] | DriftBlk[kDriftMaxBlocks n_src_slots]; rec: DriftRecord.
     struct Drift : SourceAnalysis {
         std::vector<unsigned long long> set_at; // per source index: frame_no of the last sdrx_set_drift -- the profile is this setting's once frame_no > set_at
-        DriftSrc *d_src() const { return reinterpret_cast<DriftSrc *>(d_desc); }
+        DriftSrc *d_src() const { return reinterpret_cast<DriftSrc *>(d_desc.get()); }
         DriftBlk *d_blk(int n_src_slots) const { return reinterpret_cast<DriftBlk *>(d_desc + sizeof(DriftSrc) * (size_t)n_src_slots); }
     } drift;
     // Band scan (sdrx_set_scan, scan.hip): switched by the cell width cell_bins.  d_state: a ScanState (integrated
     // spectrum, count, and the cells, hits and record of the last completed evaluation); d_desc: ScanSrc[n_src_slots]; rec: ScanRecord.
     struct Scan : SourceAnalysis {
         std::vector<ScanCfg> cfg; // per source index: the setting that last switched it on
-        ScanSrc *d_src() const { return reinterpret_cast<ScanSrc *>(d_desc); }
+        ScanSrc *d_src() const { return reinterpret_cast<ScanSrc *>(d_desc.get()); }
     } scan;
 
     // Option wake (sdrx_set_wake, wake.hip): the leaves the device parks and unparks itself.  `ctl` says per leaf
@@ -293,18 +329,19 @@ struct sdrx_ctx {
     // the device is allocated by the first sdrx_set_wake that switches a leaf on: the static table and the state per watch slot,
     // the launch list (the controlled leaves in the order of the watch's own list, `begin` per source group as
     // Watch::leaf_begin) and the fill lists of the controlled leaves (leaf_regions, sdrx_wake.hip).
-    struct Wake {
+    struct WakeDevice { // what the first sdrx_set_wake that switches a leaf on allocates, all of it or none
+        DevBuf<WakeLeaf> d_leaf;
+        DevBuf<WakeState> d_state;
+        DevBuf<int> d_list;
+        DevBuf<WakeFill> d_fill; // grown on demand
+        Records rec;             // WakeRecord per watch slot
+        size_t bytes() const { return d_state.bytes() + d_list.bytes() + d_leaf.bytes() + 2 * rec.bytes() + d_fill.bytes(); } // device memory the option holds
+    };
+    struct Wake : WakeDevice {
         std::vector<Switched> ctl;      // per node; sized by the first sdrx_set_wake
         std::vector<sdrx_wake_cfg> cfg; // per node: the settings as set
         int n_ctl = 0;                  // leaves under control
-        WakeLeaf *d_leaf = nullptr;
-        WakeState *d_state = nullptr;
-        int *d_list = nullptr;
-        WakeFill *d_fill = nullptr;
-        size_t fill_cap = 0;            // entries d_fill holds
         std::vector<WakeLeaf> h_leaf;   // host copy of d_leaf
-        Records rec;                    // WakeRecord per watch slot
-        size_t bytes = 0;               // device memory the option holds
         std::vector<int> begin;         // first launch entry per source group, n_levels + 2 entries
         bool controlled(int id) const { return !ctl.empty() && ctl[(size_t)id].v != 0; }
         bool controlled_at(int id, unsigned long long frame) const { return !ctl.empty() && ctl[(size_t)id].at(frame) != 0; }
@@ -312,11 +349,11 @@ struct sdrx_ctx {
 
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first
-    // frame that fills them.  The first such leaf uses the arena's buffer, further ones buffers of their own (hipMalloc).
+    // frame that fills them.  The first such leaf uses the arena's buffer, further ones buffers of their own (`own`).
     struct TapBuf {
         float2 *buf[2] = {nullptr, nullptr};
         unsigned long long since = 0;
-        bool own = false;
+        DevBuf<float2> own[2]; // what buf[] points at, unless it is the arena's
     };
     std::map<int, TapBuf> taps;
     size_t tap_len = 0, off_tapbuf[2] = {0, 0}; // the arena's tap buffer (sized for the longest fused leaf), per frame parity
@@ -341,19 +378,12 @@ struct sdrx_ctx {
     } st;
     bool long_frame = false;             // the frame's kernels outlast its payload copy (the DC-bias recurrence): the copy is issued by sdrx_wait
     bool copy_owed[2] = {false, false};  //   ... and not issued yet
-    unsigned char *arena = nullptr;
     size_t arena_bytes = 0;
-    unsigned char *d_pay[2] = {nullptr, nullptr}, *h_pay[2] = {nullptr, nullptr}; // per frame parity
     size_t pay_bytes = 0;
-    unsigned char *h_in[2] = {nullptr, nullptr}; // pinned staging of host-fed frames, per frame parity
-    size_t h_in_bytes = 0;
     int in_flight = 0;               // frames submitted (sdrx_submit*) and not yet delivered (sdrx_wait)
     bool broken = false;             // fault injection (SDRX_FAULT_WAIT): every frame call fails from here on, like after a HIP error
     int host_slot = -1;              // which h_pay holds the payloads sdrx_get_output serves
     unsigned long long host_frame = 0; // ... and which frame they are
-    float2 *d_raw[2] = {nullptr, nullptr}; // host-fed frames on the device (natural order), per frame parity: frame f's
-                                           //   buffer stays untouched until f+2 is staged (another context on this device may
-                                           //   be working on it: sdrx_submit_shared)
     // other contexts that ran on this context's uploaded frame of parity p (sdrx_submit_shared): each left an event behind its
     // kernels, and this context's next upload into that buffer waits for them (events owned, and reused, by this context).
     // No lock: `ctx` and `src` of a sharing call must be driven from ONE thread (sdrx.h).
@@ -363,27 +393,24 @@ struct sdrx_ctx {
         bool pending;        // recorded since this context last waited for it
     };
     std::vector<SharedReader> shared_readers[2]; // at most one entry per (reader, parity): re-recorded, never piled up
-    float2 *d_raw_tiled = nullptr; // the raw frame in tile layout: input of the parent-less VFOs
     int last_raw = -1;             // how the last frame reached level 0 (kRaw*; -1: caller-owned device memory)
     bool late4 = false;            // k_late_decimate4 serves the late-decimation launch
     bool root_direct = false;      // level 0 reads the caller's natural-order frame itself (few VFOs)
-    unsigned char *d_raw_u8[2] = {nullptr, nullptr}; // the same for dongle bytes
-    struct DcBias { // DC-bias removal of dongle bytes (sdrx_*_u8 with correct_dc), allocated by the first such frame
-        float *d_state = nullptr;   // accumulator (exact: [2]; fast: [parity][2])
-        float *d_work = nullptr;    // exact removal: products P[2][stride] and estimates A[2][stride] of one frame
-        unsigned long long *d_counters = nullptr; // k_dc_chain_spec: [0] blocks walked, [1] blocks redone with the sequential operations, [2] blocks taken again on their own
-        int waves = 8;              // k_dc_chain_spec: blocks per step = waves per workgroup (option dc_blocks_per_step: 1, 2, 4, 8)
+    struct DcDevice { // DC-bias removal of dongle bytes (sdrx_*_u8 with correct_dc), allocated by the first such frame (dc_first_use)
+        DevBuf<float> d_state;      // accumulator (exact: [2]; fast: [parity][2])
+        DevBuf<float> d_work;       // exact removal: products P[2][stride] and estimates A[2][stride] of one frame
+        DevBuf<unsigned long long> d_counters; // k_dc_chain_spec: [0] blocks walked, [1] blocks redone with the sequential operations, [2] blocks taken again on their own
         int work_stride = 0;
-        double *d_tab = nullptr;    // fast scan: powers of the decay + per-chunk sums behind them
+        DevBuf<double> d_tab;       // fast scan: powers of the decay + per-chunk sums behind them
         unsigned long long frames = 0; // frames the fast scan has run on (its state ping-pongs)
         size_t tab_sums = 0;        // offset (in doubles) of the double2 sums[] inside d_tab
+    };
+    struct DcBias : DcDevice {
+        int waves = 8;              // k_dc_chain_spec: blocks per step = waves per workgroup (option dc_blocks_per_step: 1, 2, 4, 8)
     } dc;
-    size_t raw_cap = 0;
     int root_frame = 0; // samples_per_buffer of the parent-less VFOs
     size_t off_k1vfo = 0;
     size_t off_k2 = 0, off_k4 = 0; // the K2Vfo / K4Vfo arrays (sdrx_set_gains patches their gain)
-    RetuneJob *d_jobs = nullptr;   // k_vfo_retune's job list (sdrx_set_mixer_freqs, sdrx_set_gains), grown on demand
-    size_t jobs_cap = 0;           //   ... its size in bytes (upload_jobs)
     std::vector<Launch1> l1;
     std::vector<LaunchB> lb;
     std::vector<int> publish_order;
@@ -404,14 +431,14 @@ struct sdrx_ctx {
     // spectrum display (sdrx_set_spectrum): state slot id of a VFO, nodes.size() of the raw frame.  All of it is allocated by
     // sdrx_set_spectrum; with nothing enabled the frame sequence launches nothing more.
     struct SpecState {
-        double *pwr = nullptr; // kSpecN doubles, then kSpecN cf32 bins (one allocation)
+        DevBuf<double> pwr; // kSpecN doubles, then kSpecN cf32 bins (one allocation, counted in doubles)
         bool on = false;
     };
     struct Spectrum {
         std::vector<SpecState> slots;  // per slot
-        SpecRecord *d_rec = nullptr;   // per slot (one array: sdrx_get_spectrum_levels is one copy)
-        float2 *d_tw = nullptr;        // kiss_fft's twiddles, then the Hann window (kSpecN floats)
-        SpecDesc *d_desc = nullptr;    // the VFO spectra that have a stream, by tree level; then the raw one
+        DevBuf<SpecRecord> d_rec;      // per slot (one array: sdrx_get_spectrum_levels is one copy)
+        DevBuf<float2> d_tw;           // kiss_fft's twiddles, then the Hann window (kSpecN floats)
+        DevBuf<SpecDesc> d_desc;       // the VFO spectra that have a stream, by tree level; then the raw one
         int n_desc = 0;                // VFO descriptors in d_desc
         std::vector<int> level_begin;  // first descriptor of every level (n_levels + 1 entries)
         bool raw_on = false;

@@ -111,7 +111,7 @@ int queue_watch(sdrx_ctx *c, int p, hipStream_t st)
 {
     for (const sdrx_ctx::Records *r : {&c->watch.rec, &c->drift.rec, &c->scan.rec, &c->wake.rec})
         if (r->d[p])
-            HIPCHK(c, hipMemcpyAsync(r->h[p], r->d[p], r->bytes, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipMemcpyAsync(r->h[p], r->d[p], r->bytes(), hipMemcpyDeviceToHost, st));
     return SDRX_OK;
 }
 int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st)
@@ -306,20 +306,13 @@ int leaf_call(sdrx_ctx *c, const char *what, int sdrx_ctx::*opt, const char *opt
     return mode == kDelivered && n > 0 ? need_delivered(c, what) : SDRX_OK;
 }
 
-// `bytes` of a job list into the device buffer `buf` (grown on demand, `cap` bytes), queued on the context's stream: the caller
+// `count` entries of a job list into the device buffer `buf` (grown on demand), queued on the context's stream: the caller
 // launches behind it and synchronises before `data` goes away.
 template <class T>
-int upload_jobs(sdrx_ctx *c, T *&buf, size_t &cap, const void *data, size_t bytes)
+int upload_jobs(sdrx_ctx *c, DevBuf<T> &buf, const void *data, size_t count)
 {
-    if (bytes > cap) {
-        if (buf)
-            (void)hipFree(buf);
-        buf = nullptr;
-        cap = 0;
-        HIPCHK(c, hipMalloc(&buf, bytes));
-        cap = bytes;
-    }
-    HIPCHK(c, hipMemcpyAsync(buf, data, bytes, hipMemcpyHostToDevice, c->st.stream));
+    HIPCHK(c, buf.reserve(count));
+    HIPCHK(c, hipMemcpyAsync(buf, data, sizeof(T) * count, hipMemcpyHostToDevice, c->st.stream));
     return SDRX_OK;
 }
 
@@ -456,9 +449,9 @@ int sdrx_set_squelch(sdrx_ctx *c, const int *ids, const uint64_t *thr, const uin
     std::vector<SqJob> jobs((size_t)n);
     for (int k = 0; k < n; ++k)
         jobs[(size_t)k] = SqJob{thr[k], hang_frames[k], (unsigned)c->sq.index[(size_t)ids[k]]};
-    if (int rc = upload_jobs(c, c->sq.d_jobs, c->sq.jobs_cap, jobs.data(), sizeof(SqJob) * jobs.size()))
+    if (int rc = upload_jobs(c, c->sq.d_jobs, jobs.data(), sizeof(SqJob) * jobs.size()))
         return rc;
-    hipLaunchKernelGGL(k_squelch_set, dim3((n + 63) / 64), dim3(64), 0, c->st.stream, c->sq.d_jobs, n, c->sq.d_cfg, c->sq.d_hang);
+    hipLaunchKernelGGL(k_squelch_set, dim3((n + 63) / 64), dim3(64), 0, c->st.stream, reinterpret_cast<const SqJob *>(c->sq.d_jobs.get()), n, c->sq.d_cfg, c->sq.d_hang);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->st.stream)); // (`jobs` lives on this stack)
     for (const SqJob &J : jobs) {
@@ -501,9 +494,9 @@ int sdrx_set_squelch_auto(sdrx_ctx *c, const int *ids, const uint32_t *ratio_q8,
     std::vector<SqAutoJob> jobs((size_t)n);
     for (int k = 0; k < n; ++k)
         jobs[(size_t)k] = SqAutoJob{ratio_q8[k], window_frames[k], (unsigned)c->sq.index[(size_t)ids[k]], 0};
-    if (int rc = upload_jobs(c, c->sq.d_jobs, c->sq.jobs_cap, jobs.data(), sizeof(SqAutoJob) * jobs.size())) // (one buffer for both setters)
+    if (int rc = upload_jobs(c, c->sq.d_jobs, jobs.data(), sizeof(SqAutoJob) * jobs.size())) // (one buffer for both setters)
         return rc;
-    hipLaunchKernelGGL(k_squelch_set_auto, dim3((n + 63) / 64), dim3(64), 0, c->st.stream, reinterpret_cast<const SqAutoJob *>(c->sq.d_jobs), n,
+    hipLaunchKernelGGL(k_squelch_set_auto, dim3((n + 63) / 64), dim3(64), 0, c->st.stream, reinterpret_cast<const SqAutoJob *>(c->sq.d_jobs.get()), n,
                        c->sq.d_auto);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->st.stream)); // (`jobs` lives on this stack)
@@ -556,7 +549,7 @@ int sdrx_set_agc(sdrx_ctx *c, const int *ids, const sdrx_agc_cfg *cfgs, int n)
         jobs.push_back(J);
     }
     if (!jobs.empty()) {
-        if (int rc = upload_jobs(c, c->agc.d_jobs, c->agc.jobs_cap, jobs.data(), sizeof(AgcJob) * jobs.size()))
+        if (int rc = upload_jobs(c, c->agc.d_jobs, jobs.data(), jobs.size()))
             return rc;
         const int nj = (int)jobs.size();
         hipLaunchKernelGGL(k_agc_set, dim3((nj + 63) / 64), dim3(64), 0, c->st.stream, c->agc.d_jobs, nj, c->agc.d_cfg, c->agc.d_quiet);

@@ -663,7 +663,7 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
     const int N = (int)c->nodes.size();
     B.off_nco_jobs = B.plan.take(sizeof(NcoInit) * (size_t)N);
     c->arena_bytes = align_up(B.plan.size, 256);
-    HIPCHK(c, hipMalloc(&c->arena, c->arena_bytes));
+    HIPCHK(c, c->arena.alloc(c->arena_bytes));
     HIPCHK(c, hipMemsetAsync(c->arena, 0, c->arena_bytes, c->st.stream));
     // (the copy length stays a multiple of 64 bytes, as the packed payloads are)
     c->pay_bytes = std::max<size_t>(c->opt_meter ? align_up(c->meter_off + 16 * (size_t)c->meter_slots, 64) : B.pay, 64);
@@ -694,14 +694,13 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
     }
     const size_t h_bytes = align_up(c->pay_bytes, 16) + (c->opt_preroll ? c->sq.pack_bytes : 0);
     for (int p = 0; p < 2; ++p) {
-        HIPCHK(c, hipMalloc(&c->d_pay[p], align_up(c->pay_bytes, 16))); // (whole 16-byte units)
+        HIPCHK(c, c->d_pay[p].alloc(align_up(c->pay_bytes, 16))); // (whole 16-byte units)
         HIPCHK(c, hipMemsetAsync(c->d_pay[p], 0, c->pay_bytes, c->st.stream));
-        HIPCHK(c, hipHostMalloc(&c->h_pay[p], h_bytes, hipHostMallocDefault));
-        memset(c->h_pay[p], 0, h_bytes);
+        HIPCHK(c, c->h_pay[p].alloc(h_bytes, true));
     }
     {
         const size_t raw_tiles = align_up((size_t)c->root_frame, kChunk) + kChunk; // (+1 tile, as for the parents' streams)
-        HIPCHK(c, hipMalloc(&c->d_raw_tiled, raw_tiles * sizeof(float2)));
+        HIPCHK(c, c->d_raw_tiled.alloc(raw_tiles));
         HIPCHK(c, hipMemsetAsync(c->d_raw_tiled, 0, raw_tiles * sizeof(float2), c->st.stream));
         c->root_direct = B.level_count[0] <= 4; // the reference allows 3 mains (mainwindow.h:82)
     }
@@ -897,14 +896,12 @@ int squelch_setup(sdrx_ctx *c)
     for (size_t k = 0; k < n; ++k)
         c->sq.units[k] = leaves[k].pay_units;
     const size_t n1 = std::max<size_t>(n, 1);
-    HIPCHK(c, hipMalloc(&c->sq.d_leaves, sizeof(SqLeaf) * n1));
-    HIPCHK(c, hipMalloc(&c->sq.d_cfg, sizeof(SqCfg) * n1));
-    HIPCHK(c, hipMalloc(&c->sq.d_hang, sizeof(unsigned) * n1));
-    c->sq.bytes = (sizeof(SqLeaf) + sizeof(SqCfg) + sizeof(unsigned)) * n1 + 2 * c->sq.pack_bytes;
+    HIPCHK(c, c->sq.d_leaves.alloc(n1));
+    HIPCHK(c, c->sq.d_cfg.alloc(n1));
+    HIPCHK(c, c->sq.d_hang.alloc(n1));
     if (c->opt_preroll) { // prev_open = 1: frame 0 has no predecessor
-        HIPCHK(c, hipMalloc(&c->sq.d_prev, sizeof(unsigned) * n1));
-        HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->sq.d_prev), 1, n1, c->st.stream));
-        c->sq.bytes += sizeof(unsigned) * n1;
+        HIPCHK(c, c->sq.d_prev.alloc(n1));
+        HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->sq.d_prev.get()), 1, n1, c->st.stream));
     }
     std::vector<SqAuto> fresh; // (lives until the synchronisation below)
     if (c->opt_squelch_auto) { // no observation, ratio 0: the plain gate until sdrx_set_squelch_auto
@@ -912,15 +909,14 @@ int squelch_setup(sdrx_ctx *c)
         c->sq.thr_eff.assign(n, 0);
         c->sq.floor.assign(n, kSqNone);
         fresh.assign(n1, SqAuto{kSqNone, kSqNone, 0, 0, 0, 0});
-        HIPCHK(c, hipMalloc(&c->sq.d_auto, sizeof(SqAuto) * n1));
+        HIPCHK(c, c->sq.d_auto.alloc(n1));
         HIPCHK(c, hipMemcpyAsync(c->sq.d_auto, fresh.data(), sizeof(SqAuto) * n1, hipMemcpyHostToDevice, c->st.stream));
-        c->sq.bytes += sizeof(SqAuto) * n1;
     }
     HIPCHK(c, hipMemcpyAsync(c->sq.d_leaves, leaves.data(), sizeof(SqLeaf) * n, hipMemcpyHostToDevice, c->st.stream));
     HIPCHK(c, hipMemsetAsync(c->sq.d_cfg, 0, sizeof(SqCfg) * n1, c->st.stream));
     HIPCHK(c, hipMemsetAsync(c->sq.d_hang, 0, sizeof(unsigned) * n1, c->st.stream));
     for (int p = 0; p < 2; ++p) {
-        HIPCHK(c, hipMalloc(&c->sq.d_pack[p], c->sq.pack_bytes));
+        HIPCHK(c, c->sq.d_pack[p].alloc(c->sq.pack_bytes));
         HIPCHK(c, hipMemsetAsync(c->sq.d_pack[p], 0, c->sq.pack_bytes, c->st.stream));
         if (!c->sq.ev_dir[p])
             HIPCHK(c, hipEventCreateWithFlags(&c->sq.ev_dir[p], hipEventDisableTiming));
@@ -947,8 +943,8 @@ int park_setup(sdrx_ctx *c, const Built &B)
     if (c->fp.usable)
         for (size_t it = 0; it < B.all_items.size(); ++it)
             K.items[(size_t)B.all_items[it].vfo].push_back((int)it);
-    HIPCHK(c, hipMalloc(&K.d_act, sizeof(int) * K.words));
-    HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(K.d_act), 1, K.words, c->st.stream));
+    HIPCHK(c, K.d_act.alloc(K.words));
+    HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(K.d_act.get()), 1, K.words, c->st.stream));
     HIPCHK(c, hipStreamSynchronize(c->st.stream));
     return SDRX_OK;
 }
@@ -985,10 +981,9 @@ int agc_setup(sdrx_ctx *c)
         leaves.push_back(L);
     }
     const size_t n1 = std::max<size_t>(leaves.size(), 1);
-    HIPCHK(c, hipMalloc(&A.d_leaves, sizeof(AgcLeaf) * n1));
-    HIPCHK(c, hipMalloc(&A.d_cfg, sizeof(AgcCfg) * n1));
-    HIPCHK(c, hipMalloc(&A.d_quiet, sizeof(unsigned) * n1));
-    A.bytes = (sizeof(AgcLeaf) + sizeof(AgcCfg) + sizeof(unsigned)) * n1;
+    HIPCHK(c, A.d_leaves.alloc(n1));
+    HIPCHK(c, A.d_cfg.alloc(n1));
+    HIPCHK(c, A.d_quiet.alloc(n1));
     HIPCHK(c, hipMemcpyAsync(A.d_leaves, leaves.data(), sizeof(AgcLeaf) * leaves.size(), hipMemcpyHostToDevice, c->st.stream));
     HIPCHK(c, hipMemsetAsync(A.d_cfg, 0, sizeof(AgcCfg) * n1, c->st.stream));
     HIPCHK(c, hipMemsetAsync(A.d_quiet, 0, sizeof(unsigned) * n1, c->st.stream));

@@ -535,10 +535,10 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         const int n_pairs = c->root_frame / 2;
         if (raw_mode == kRawF32)
             hipLaunchKernelGGL(k_ingest_f32, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream,
-                               reinterpret_cast<const float4 *>(raw), reinterpret_cast<float4 *>(c->d_raw_tiled), n_pairs);
+                               reinterpret_cast<const float4 *>(raw), reinterpret_cast<float4 *>(c->d_raw_tiled.get()), n_pairs);
         else
             hipLaunchKernelGGL(k_ingest_samples<SDRX_FMT_CU8>, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream,
-                               reinterpret_cast<const unsigned *>(raw), reinterpret_cast<float4 *>(c->d_raw_tiled), n_pairs);
+                               reinterpret_cast<const unsigned *>(raw), reinterpret_cast<float4 *>(c->d_raw_tiled.get()), n_pairs);
         raw_mode = kRawTiled;
     }
     const bool shared_launches = c->fp.usable && c->opt_fuse && !pipe && !egress;
@@ -627,22 +627,20 @@ int drain(sdrx_ctx *c)
 }
 
 
+// the device buffers of host-fed frames, both parities: all four hold `n_complex` samples, or (an allocation failed) none exists
 int ensure_raw(sdrx_ctx *c, size_t n_complex)
 {
-    if (c->raw_cap >= n_complex)
+    hipError_t e = hipSuccess;
+    for (int p = 0; p < 2 && e == hipSuccess; ++p)
+        if ((e = c->d_raw[p].reserve(n_complex)) == hipSuccess)
+            e = c->d_raw_u8[p].reserve(n_complex * 2);
+    if (e == hipSuccess)
         return SDRX_OK;
     for (int p = 0; p < 2; ++p) {
-        if (c->d_raw[p])
-            (void)hipFree(c->d_raw[p]);
-        if (c->d_raw_u8[p])
-            (void)hipFree(c->d_raw_u8[p]);
-        c->d_raw[p] = nullptr;
-        c->d_raw_u8[p] = nullptr;
-        HIPCHK(c, hipMalloc(&c->d_raw[p], n_complex * sizeof(float2)));
-        HIPCHK(c, hipMalloc(&c->d_raw_u8[p], n_complex * 2));
+        c->d_raw[p].reset();
+        c->d_raw_u8[p].reset();
     }
-    c->raw_cap = n_complex;
-    return SDRX_OK;
+    return fail(c, SDRX_EHIP, "no device memory for the frame buffers: %s", hipGetErrorString(e));
 }
 
 int check_frame_call(sdrx_ctx *c, const char *what, const void *ptr, int n_complex, bool sync_call)
@@ -672,14 +670,13 @@ int check_frame_call(sdrx_ctx *c, const char *what, const void *ptr, int n_compl
 int stage_host_frame(sdrx_ctx *c, const void *src, size_t bytes, void *dst_dev)
 {
     const int p = (int)(c->frame_no & 1ull);
-    if (c->h_in_bytes < (size_t)c->root_frame * sizeof(float2)) {
-        for (int q = 0; q < 2; ++q) {
-            if (c->h_in[q])
-                (void)hipHostFree(c->h_in[q]);
-            c->h_in[q] = nullptr;
-            HIPCHK(c, hipHostMalloc(&c->h_in[q], (size_t)c->root_frame * sizeof(float2), hipHostMallocDefault));
-        }
-        c->h_in_bytes = (size_t)c->root_frame * sizeof(float2);
+    hipError_t e = c->h_in[0].reserve((size_t)c->root_frame * sizeof(float2)); // both pinned buffers, or none
+    if (e == hipSuccess)
+        e = c->h_in[1].reserve((size_t)c->root_frame * sizeof(float2));
+    if (e != hipSuccess) {
+        c->h_in[0].reset();
+        c->h_in[1].reset();
+        return fail(c, SDRX_EHIP, "no pinned memory for the frame staging: %s", hipGetErrorString(e));
     }
     memcpy(c->h_in[p], src, bytes);
     for (auto &r : c->shared_readers[p]) // whoever shared frame f-2 of this buffer has read it before it is overwritten
@@ -731,20 +728,16 @@ const SampleKernels &sample_kernels(int fmt)
 bool known_format(int fmt) { return fmt == SDRX_FMT_CU8 || fmt == SDRX_FMT_CS8 || fmt == SDRX_FMT_CS16; }
 size_t sample_bytes(int fmt, int n_complex) { return (size_t)n_complex * (fmt == SDRX_FMT_CS16 ? 4 : 2); }
 
-// `dev_bytes`: the frame's integer samples in format `fmt` (dongle bytes, int8 or int16), already on this context's device and
-// complete in the order of c->st.stream.  Sample conversion (+ the DC-bias IIR with this context's own accumulator, the one
-// accumulator whatever the format) and the frame itself.  Dongle bytes without DC removal go to level 0 as they are (kRawU8);
-// the signed formats always enter through an ingest pass into the tile layout, as every DC-corrected frame does.
-int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, int fmt, int correct_dc, bool egress)
+// What the DC-bias removal of this context's frames holds on the device, by the first frame that asks for it (nothing once it
+// exists: the options and the frame length are fixed): the accumulator, and the fast scan's table or the exact removal's work
+// buffer and counters.  All of it or -- the caller resets dc's device part on an error -- none.
+int dc_first_use(sdrx_ctx *c, int n_complex, int nchunks)
 {
-    const SampleKernels &K = sample_kernels(fmt);
-    if (correct_dc && !c->dc.d_state) {
-        HIPCHK(c, hipMalloc(&c->dc.d_state, 4 * sizeof(float)));
+    if (!c->dc.d_state) {
+        HIPCHK(c, c->dc.d_state.alloc(4));
         HIPCHK(c, hipMemsetAsync(c->dc.d_state, 0, 4 * sizeof(float), c->st.stream)); // `static cpx_typef avept=0`, sdrj.cpp:279
     }
-    int mode = kRawU8;
-    const int nchunks = (n_complex + kChunk - 1) / kChunk;
-    if (correct_dc && c->opt_dc_blocked && !c->dc.d_tab) {
+    if (c->opt_dc_blocked && !c->dc.d_tab) {
         // powers of the decay A = (float)(1 - 1e-6): [0..16] A^k, [32..95] A^(16 l), [96 + k] A^(1024 k)
         const double A = (double)(1.0f - 0.000001f);
         std::vector<double> tab(96 + (size_t)nchunks + 1 + 2 * (size_t)nchunks + 2, 0.0);
@@ -755,30 +748,46 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         for (int k = 0; k <= nchunks; ++k)
             tab[96 + (size_t)k] = std::pow(A, 1024.0 * k);
         c->dc.tab_sums = (96 + (size_t)nchunks + 1 + 1) & ~(size_t)1; // 16-byte aligned double2[]
-        HIPCHK(c, hipMalloc(&c->dc.d_tab, tab.size() * sizeof(double)));
+        HIPCHK(c, c->dc.d_tab.alloc(tab.size()));
         HIPCHK(c, hipMemcpy(c->dc.d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (correct_dc && !c->opt_dc_blocked) {
-        // products (parallel) -> the two recurrences (one wave each, nearly alone with their dependent chain) -> subtract (parallel)
+    if (!c->opt_dc_blocked) {
         const int stride = (int)align_up((size_t)n_complex + kDcPad, 64);
         if (c->dc.work_stride < stride) {
-            if (c->dc.d_work)
-                (void)hipFree(c->dc.d_work);
-            c->dc.d_work = nullptr;
-            HIPCHK(c, hipMalloc(&c->dc.d_work, sizeof(float) * 4 * (size_t)stride)); // P[2][stride] | A[2][stride]
+            HIPCHK(c, c->dc.d_work.reserve(4 * (size_t)stride)); // P[2][stride] | A[2][stride]
             HIPCHK(c, hipMemsetAsync(c->dc.d_work, 0, sizeof(float) * 4 * (size_t)stride, c->st.stream));
             c->dc.work_stride = stride;
         }
+        if (c->opt_dc_speculative && !c->dc.d_counters) {
+            HIPCHK(c, c->dc.d_counters.alloc(4));
+            HIPCHK(c, hipMemsetAsync(c->dc.d_counters, 0, 4 * sizeof(unsigned long long), c->st.stream));
+        }
+    }
+    return SDRX_OK;
+}
+
+// `dev_bytes`: the frame's integer samples in format `fmt` (dongle bytes, int8 or int16), already on this context's device and
+// complete in the order of c->st.stream.  Sample conversion (+ the DC-bias IIR with this context's own accumulator, the one
+// accumulator whatever the format) and the frame itself.  Dongle bytes without DC removal go to level 0 as they are (kRawU8);
+// the signed formats always enter through an ingest pass into the tile layout, as every DC-corrected frame does.
+int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, int fmt, int correct_dc, bool egress)
+{
+    const SampleKernels &K = sample_kernels(fmt);
+    int mode = kRawU8;
+    const int nchunks = (n_complex + kChunk - 1) / kChunk;
+    if (correct_dc)
+        if (int rc = dc_first_use(c, n_complex, nchunks)) {
+            static_cast<sdrx_ctx::DcDevice &>(c->dc) = sdrx_ctx::DcDevice();
+            return rc;
+        }
+    if (correct_dc && !c->opt_dc_blocked) {
+        // products (parallel) -> the two recurrences (one wave each, nearly alone with their dependent chain) -> subtract (parallel)
         float *Pp = c->dc.d_work, *Ap = c->dc.d_work + 2 * (size_t)c->dc.work_stride;
         const int words = n_complex / 2;
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
         hipLaunchKernelGGL(K.products, dim3((words + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), Pp,
                            n_complex, c->dc.work_stride);
         if (c->opt_dc_speculative) {
-            if (!c->dc.d_counters) {
-                HIPCHK(c, hipMalloc(&c->dc.d_counters, 4 * sizeof(unsigned long long)));
-                HIPCHK(c, hipMemsetAsync(c->dc.d_counters, 0, 4 * sizeof(unsigned long long), c->st.stream));
-            }
             // one workgroup per component, dc_waves consecutive 1024-sample blocks per step
             auto chain = c->dc.waves >= 8 ? k_dc_chain_spec<8> : c->dc.waves >= 4 ? k_dc_chain_spec<4> : c->dc.waves >= 2 ? k_dc_chain_spec<2> : k_dc_chain_spec<1>;
             const int waves = c->dc.waves >= 8 ? 8 : c->dc.waves >= 4 ? 4 : c->dc.waves >= 2 ? 2 : 1;
@@ -788,7 +797,7 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
             hipLaunchKernelGGL(k_dc_chain, dim3(2), dim3(64), 0, c->st.stream, Pp, Ap, n_complex, c->dc.work_stride, c->dc.d_state);
         }
         hipLaunchKernelGGL(K.apply, dim3((words + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), Ap,
-                           reinterpret_cast<float4 *>(c->d_raw_tiled), n_complex, c->dc.work_stride);
+                           reinterpret_cast<float4 *>(c->d_raw_tiled.get()), n_complex, c->dc.work_stride);
         mode = kRawTiled;
     } else if (correct_dc) {
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
@@ -797,14 +806,14 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         hipLaunchKernelGGL(K.block_sums, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), n_complex,
                            c->dc.d_tab, sums);
         hipLaunchKernelGGL(K.dc_fast, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
-                           reinterpret_cast<float4 *>(c->d_raw_tiled), n_complex, c->dc.d_state + 2 * par, c->dc.d_state + 2 * (par ^ 1),
+                           reinterpret_cast<float4 *>(c->d_raw_tiled.get()), n_complex, c->dc.d_state + 2 * par, c->dc.d_state + 2 * (par ^ 1),
                            c->dc.d_tab, sums);
         mode = kRawTiled;
     } else if (fmt != SDRX_FMT_CU8) {
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
         const int n_pairs = n_complex / 2;
         hipLaunchKernelGGL(K.ingest, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
-                           reinterpret_cast<float4 *>(c->d_raw_tiled), n_pairs);
+                           reinterpret_cast<float4 *>(c->d_raw_tiled.get()), n_pairs);
         mode = kRawTiled;
     }
     c->long_frame = correct_dc && !c->opt_dc_blocked;

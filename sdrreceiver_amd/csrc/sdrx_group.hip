@@ -18,7 +18,7 @@ struct GroupMember {
     sdrx_ctx *c = nullptr;
     int device = 0;
     std::vector<int> global_of; // local id -> global id
-    unsigned char *d_frame[2] = {nullptr, nullptr}; // peers: the raw frame of parity p (cf32 or bytes)
+    DevBuf<unsigned char> d_frame[2]; // peers: the raw frame of parity p (cf32 or bytes); on `device`
 };
 
 } // namespace
@@ -39,8 +39,10 @@ struct sdrx_group {
     int in_flight = 0;
     unsigned long long frame_no = 0;
     // staging of host-fed frames on the first device, per frame parity
-    unsigned char *h_stage[2] = {nullptr, nullptr};
-    unsigned char *d_stage[2] = {nullptr, nullptr};
+    struct Stage {
+        PinBuf<unsigned char> h[2];
+        DevBuf<unsigned char> d[2];
+    } stage;
     hipEvent_t ev_ready[2] = {nullptr, nullptr}; // frame of parity p is complete on the first device
     hipStream_t stage_stream = nullptr;          // first device: host -> device copies of the raw frames
     bool peer_ok = true;
@@ -147,8 +149,8 @@ int group_stage(sdrx_group *g, const void *host, size_t bytes)
 {
     const int p = (int)(g->frame_no & 1ull);
     GHIP(g, hipSetDevice(g->m[0].device));
-    memcpy(g->h_stage[p], host, bytes);
-    GHIP(g, hipMemcpyAsync(g->d_stage[p], g->h_stage[p], bytes, hipMemcpyHostToDevice, g->stage_stream));
+    memcpy(g->stage.h[p], host, bytes);
+    GHIP(g, hipMemcpyAsync(g->stage.d[p], g->stage.h[p], bytes, hipMemcpyHostToDevice, g->stage_stream));
     GHIP(g, hipEventRecord(g->ev_ready[p], g->stage_stream));
     return SDRX_OK;
 }
@@ -160,24 +162,16 @@ void group_drop_members(sdrx_group *g)
         (void)hipSetDevice(M.device);
         if (M.c)
             sdrx_destroy(M.c);
-        M.c = nullptr;
-        M.global_of.clear();
-        for (int p = 0; p < 2; ++p) {
-            if (M.d_frame[p])
-                (void)hipFree(M.d_frame[p]);
-            M.d_frame[p] = nullptr;
-        }
+        const int device = M.device;
+        M = GroupMember(); // (its frame buffers go with their device current)
+        M.device = device;
     }
     if (!g->m.empty())
         (void)hipSetDevice(g->m[0].device);
+    g->stage = sdrx_group::Stage();
     for (int p = 0; p < 2; ++p) {
-        if (g->h_stage[p])
-            (void)hipHostFree(g->h_stage[p]);
-        if (g->d_stage[p])
-            (void)hipFree(g->d_stage[p]);
         if (g->ev_ready[p])
             (void)hipEventDestroy(g->ev_ready[p]);
-        g->h_stage[p] = g->d_stage[p] = nullptr;
         g->ev_ready[p] = nullptr;
     }
     if (g->stage_stream)
@@ -421,7 +415,7 @@ static int group_finalize_impl(sdrx_group *g)
             return gfail(g, SDRX_EINVAL, "member %d was initialised for frames of %d samples, the group for %d", k, M.c->root_frame, g->root_frame);
         if (k > 0)
             for (int p = 0; p < 2; ++p)
-                GHIP(g, hipMalloc(&M.d_frame[p], (size_t)g->root_frame * sizeof(float2)));
+                GHIP(g, M.d_frame[p].alloc((size_t)g->root_frame * sizeof(float2)));
     }
     // reference publish order over the WHOLE tree: main order x sub order (sdrj.cpp:288-294, vfo.cpp:257-263)
     std::vector<int> stack;
@@ -439,8 +433,8 @@ static int group_finalize_impl(sdrx_group *g)
     GHIP(g, hipSetDevice(g->m[0].device));
     GHIP(g, hipStreamCreateWithFlags(&g->stage_stream, hipStreamNonBlocking));
     for (int p = 0; p < 2; ++p) {
-        GHIP(g, hipHostMalloc(&g->h_stage[p], (size_t)g->root_frame * sizeof(float2), hipHostMallocDefault));
-        GHIP(g, hipMalloc(&g->d_stage[p], (size_t)g->root_frame * sizeof(float2)));
+        GHIP(g, g->stage.h[p].alloc((size_t)g->root_frame * sizeof(float2)));
+        GHIP(g, g->stage.d[p].alloc((size_t)g->root_frame * sizeof(float2)));
         GHIP(g, hipEventCreateWithFlags(&g->ev_ready[p], hipEventDisableTiming));
     }
     g->finalized = true;
@@ -454,7 +448,7 @@ int sdrx_group_submit(sdrx_group *g, const float *iq, int n_complex)
         return rc;
     const size_t bytes = (size_t)n_complex * sizeof(float2);
     rc = group_stage(g, iq, bytes);
-    return rc ? rc : group_enqueue(g, g->d_stage[g->frame_no & 1ull], bytes, kRawF32, true, 0, SDRX_FMT_CU8);
+    return rc ? rc : group_enqueue(g, g->stage.d[g->frame_no & 1ull], bytes, kRawF32, true, 0, SDRX_FMT_CU8);
 }
 
 // Integer samples of any format (SDRX_FMT_*; dongle bytes, jonti/sdr.cpp:43-49, through the *_u8 calls: SDRX_FMT_CU8 under
@@ -473,7 +467,7 @@ static int group_samples_call(sdrx_group *g, const char *what, const void *ptr, 
     const size_t nb = sample_bytes(fmt, n_complex);
     rc = group_stage(g, ptr, nb);
     if (!rc)
-        rc = group_enqueue(g, g->d_stage[g->frame_no & 1ull], nb, kRawU8, true, correct_dc, fmt);
+        rc = group_enqueue(g, g->stage.d[g->frame_no & 1ull], nb, kRawU8, true, correct_dc, fmt);
     return rc || !sync_call ? rc : sdrx_group_wait(g);
 }
 

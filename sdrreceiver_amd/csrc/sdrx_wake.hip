@@ -101,16 +101,7 @@ int wake_rebuild(sdrx_ctx *c)
         }
     }
     begin[(size_t)c->n_levels + 1] = (int)list.size();
-    if (fills.size() > K.fill_cap) {
-        if (K.d_fill)
-            (void)hipFree(K.d_fill);
-        K.d_fill = nullptr;
-        K.bytes -= sizeof(WakeFill) * K.fill_cap;
-        K.fill_cap = 0;
-        HIPCHK(c, hipMalloc(&K.d_fill, sizeof(WakeFill) * fills.size()));
-        K.fill_cap = fills.size();
-        K.bytes += sizeof(WakeFill) * K.fill_cap;
-    }
+    HIPCHK(c, K.d_fill.reserve(fills.size()));
     if (!list.empty()) {
         HIPCHK(c, hipMemcpy(K.d_leaf, K.h_leaf.data(), sizeof(WakeLeaf) * K.h_leaf.size(), hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(K.d_fill, fills.data(), sizeof(WakeFill) * fills.size(), hipMemcpyHostToDevice));
@@ -118,6 +109,18 @@ int wake_rebuild(sdrx_ctx *c)
     }
     K.begin = begin;
     K.n_ctl = (int)list.size(); // (last: the frame sequence launches from these lists only when everything above succeeded)
+    return SDRX_OK;
+}
+
+// first use on the device: the static table, the state and the records per watch slot, and the launch list
+int wake_first_use(sdrx_ctx *c)
+{
+    sdrx_ctx::Wake &K = c->wake;
+    const size_t slots = (size_t)c->watch.n_slots;
+    HIPCHK(c, K.d_state.alloc(slots, true));
+    HIPCHK(c, K.d_list.alloc(slots));
+    HIPCHK(c, K.rec.alloc(sizeof(WakeRecord) * slots));
+    HIPCHK(c, K.d_leaf.alloc(slots, true));
     return SDRX_OK;
 }
 
@@ -167,16 +170,11 @@ int sdrx_set_wake(sdrx_ctx *c, const int *ids, const sdrx_wake_cfg *cfgs, int n)
         return SDRX_OK;
     }
     if (!K.d_leaf) {
-        const size_t slots = (size_t)W.n_slots;
-        HIPCHK(c, hipMalloc(&K.d_state, sizeof(WakeState) * slots));
-        HIPCHK(c, hipMemset(K.d_state, 0, sizeof(WakeState) * slots));
-        HIPCHK(c, hipMalloc(&K.d_list, sizeof(int) * slots));
-        if (int rc = records_alloc(c, K.rec, sizeof(WakeRecord) * slots))
+        if (int rc = wake_first_use(c)) { // all of it or none: the next call starts here again
+            static_cast<sdrx_ctx::WakeDevice &>(K) = sdrx_ctx::WakeDevice();
             return rc;
-        HIPCHK(c, hipMalloc(&K.d_leaf, sizeof(WakeLeaf) * slots)); // (last: wake_rebuild takes it for "allocated")
-        HIPCHK(c, hipMemset(K.d_leaf, 0, sizeof(WakeLeaf) * slots));
-        K.h_leaf.assign(slots, WakeLeaf{});
-        K.bytes += (sizeof(WakeState) + sizeof(int) + sizeof(WakeLeaf)) * slots + 2 * K.rec.bytes;
+        }
+        K.h_leaf.assign((size_t)W.n_slots, WakeLeaf{});
     }
     // what the device holds for the leaves that are controlled already; then the named ones
     std::vector<WakeState> state((size_t)W.n_slots);

@@ -76,68 +76,33 @@ bool switch_to(sdrx_ctx::Switched &S, int to, unsigned long long now)
     return true;
 }
 
-// ---- what the watch, the drift estimate and the band scan share: records per frame parity, and an analysis per source
-int records_alloc(sdrx_ctx *c, sdrx_ctx::Records &r, size_t bytes)
-{
-    for (int p = 0; p < 2; ++p) {
-        HIPCHK(c, hipMalloc(&r.d[p], bytes));
-        HIPCHK(c, hipMemset(r.d[p], 0, bytes));
-        HIPCHK(c, hipHostMalloc(&r.h[p], bytes, hipHostMallocDefault));
-        memset(r.h[p], 0, bytes);
-    }
-    r.bytes = bytes;
-    return SDRX_OK;
-}
-void records_free(sdrx_ctx::Records &r)
-{
-    for (int p = 0; p < 2; ++p) {
-        if (r.d[p])
-            (void)hipFree(r.d[p]);
-        if (r.h[p])
-            (void)hipHostFree(r.h[p]);
-    }
-    r = sdrx_ctx::Records();
-}
-
+// ---- what the drift estimate and the band scan share: an analysis per source
 // the analysis's bookkeeping of the source of `leaf_id` (host memory: sized by the first call, whatever it sets)
 sdrx_ctx::SourceAnalysis::Src &analysis_source(sdrx_ctx *c, sdrx_ctx::SourceAnalysis &A, int leaf_id)
 {
     if (A.src.empty())
-        A.src.assign(c->nodes.size() + 1, sdrx_ctx::SourceAnalysis::Src());
+        A.src.resize(c->nodes.size() + 1);
     return A.src[source_of(c, leaf_id)];
 }
-// first use on the device: the launch list (`desc_bytes` per possible source) and the records (`rec_bytes` per possible source)
+// first use on the device: the launch list (`desc_bytes` per possible source) and the records (`rec_bytes` per possible source),
+// both or neither
 int analysis_alloc(sdrx_ctx *c, sdrx_ctx::SourceAnalysis &A, size_t desc_bytes, size_t rec_bytes)
 {
     if (A.d_desc)
         return SDRX_OK;
-    HIPCHK(c, hipMalloc(&A.d_desc, desc_bytes * (size_t)c->watch.n_src_slots));
-    if (int rc = records_alloc(c, A.rec, rec_bytes * (size_t)c->watch.n_src_slots))
-        return rc;
-    A.bytes += desc_bytes * (size_t)c->watch.n_src_slots + 2 * A.rec.bytes;
-    return SDRX_OK;
+    HIPCHK(c, A.d_desc.alloc(desc_bytes * (size_t)c->watch.n_src_slots));
+    const hipError_t e = A.rec.alloc(rec_bytes * (size_t)c->watch.n_src_slots);
+    if (e == hipSuccess)
+        return SDRX_OK;
+    A.d_desc.reset();
+    return fail(c, SDRX_EHIP, "no memory for the analysis's records: %s", hipGetErrorString(e));
 }
 // a source's state, cleared, by the first call that switches the analysis on for it
-int analysis_state(sdrx_ctx *c, sdrx_ctx::SourceAnalysis &A, sdrx_ctx::SourceAnalysis::Src &S, size_t state_bytes)
+int analysis_state(sdrx_ctx *c, sdrx_ctx::SourceAnalysis::Src &S, size_t state_bytes)
 {
-    if (S.d_state)
-        return SDRX_OK;
-    HIPCHK(c, hipMalloc(&S.d_state, state_bytes));
-    HIPCHK(c, hipMemset(S.d_state, 0, state_bytes));
-    A.bytes += state_bytes;
+    if (!S.d_state)
+        HIPCHK(c, S.d_state.alloc(state_bytes, true));
     return SDRX_OK;
-}
-// as before the first call
-template <class Analysis>
-void analysis_release(Analysis &A)
-{
-    for (auto &s : A.src)
-        if (s.d_state)
-            (void)hipFree(s.d_state);
-    if (A.d_desc)
-        (void)hipFree(A.d_desc);
-    records_free(A.rec);
-    A = Analysis();
 }
 bool analysis_on(const sdrx_ctx::SourceAnalysis &A, size_t src) { return !A.src.empty() && A.src[src].on.v != 0; }
 
@@ -204,7 +169,7 @@ int drift_rebuild(sdrx_ctx *c, const std::vector<int> &ids, const std::vector<si
         const int n_blocks = (2 * K + 1 + kDriftBlock - 1) / kDriftBlock;
         for (int b = 0; b < n_blocks; ++b)
             blks.push_back(DriftBlk{(int)srcs.size(), b});
-        srcs.push_back(DriftSrc{psd, static_cast<DriftState *>(D.src[i].d_state), K, n_blocks, level, c->watch.src_slot[i]});
+        srcs.push_back(DriftSrc{psd, reinterpret_cast<DriftState *>(D.src[i].d_state.get()), K, n_blocks, level, c->watch.src_slot[i]});
         return n_blocks;
     });
     if (!srcs.empty()) {
@@ -226,7 +191,7 @@ int scan_rebuild(sdrx_ctx *c, const std::vector<int> &ids, const std::vector<siz
     const std::vector<int> begin = walk_sources(c, ids, off_psd, [&](size_t i, int level, const double *psd) {
         if (S.src[i].on.v == 0)
             return 0;
-        srcs.push_back(ScanSrc{psd, static_cast<ScanState *>(S.src[i].d_state), S.cfg[i], level, c->watch.src_slot[i]});
+        srcs.push_back(ScanSrc{psd, reinterpret_cast<ScanState *>(S.src[i].d_state.get()), S.cfg[i], level, c->watch.src_slot[i]});
         return 1;
     });
     if (!srcs.empty())
@@ -252,6 +217,18 @@ const char *bad_scan(const sdrx_scan_cfg &s)
     return nullptr;
 }
 
+// first use on the device: the launch lists, the tables and the records
+int watch_first_use(sdrx_ctx *c)
+{
+    sdrx_ctx::Watch &W = c->watch;
+    const std::vector<float2> tab = spectrum_tables();
+    HIPCHK(c, W.d_desc.alloc((sizeof(WatchSrc) + sizeof(WatchSeg) * kWatchMaxSeg) * (size_t)W.n_src_slots + sizeof(WatchLeaf) * (size_t)W.n_slots));
+    HIPCHK(c, W.d_tw.alloc(tab.size()));
+    HIPCHK(c, hipMemcpy(W.d_tw, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, W.rec.alloc(sizeof(WatchRecord) * (size_t)W.n_slots));
+    return SDRX_OK;
+}
+
 // The launch lists for the present selection, uploaded whenever it or a watched leaf's band changes.  Synchronous: never inside
 // a frame call, and the context is drained.  The sources in launch order: the raw frame, then the parents by tree level.
 int watch_rebuild(sdrx_ctx *c)
@@ -267,17 +244,11 @@ int watch_rebuild(sdrx_ctx *c)
         }
     if (!any && !W.d_desc) // nothing was ever switched on: nothing is allocated
         return SDRX_OK;
-    if (!W.d_desc) {
-        const size_t desc_bytes = (sizeof(WatchSrc) + sizeof(WatchSeg) * kWatchMaxSeg) * (size_t)W.n_src_slots + sizeof(WatchLeaf) * (size_t)W.n_slots;
-        const size_t rec_bytes = sizeof(WatchRecord) * (size_t)W.n_slots;
-        const std::vector<float2> tab = spectrum_tables();
-        HIPCHK(c, hipMalloc(&W.d_desc, desc_bytes));
-        HIPCHK(c, hipMalloc(&W.d_tw, sizeof(float2) * tab.size()));
-        HIPCHK(c, hipMemcpy(W.d_tw, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
-        if (int rc = records_alloc(c, W.rec, rec_bytes))
+    if (!W.d_desc)
+        if (int rc = watch_first_use(c)) { // all of it or none: the next call starts here again
+            static_cast<sdrx_ctx::WatchDevice &>(W) = sdrx_ctx::WatchDevice();
             return rc;
-        W.bytes = desc_bytes + sizeof(float2) * tab.size() + 2 * rec_bytes;
-    }
+        }
     // the measured sources, by group, and where each one's buffers lie
     std::vector<int> ids;
     std::vector<WatchSrc> srcs;
@@ -314,19 +285,10 @@ int watch_rebuild(sdrx_ctx *c)
         }
     }
     W.seg_begin[(size_t)c->n_levels + 1] = (int)segs.size();
-    if (ids != W.src_ids || need > W.data_cap) { // the buffers move: what they held is gone
-        if (need > W.data_cap) {
-            if (W.d_data)
-                (void)hipFree(W.d_data);
-            W.d_data = nullptr;
-            W.bytes -= W.data_cap;
-            W.data_cap = 0;
-            HIPCHK(c, hipMalloc(&W.d_data, need));
-            W.data_cap = need;
-            W.bytes += need;
-        }
+    if (ids != W.src_ids || need > W.d_data.bytes()) { // the buffers move: what they held is gone
+        HIPCHK(c, W.d_data.reserve(need));
         if (W.d_data)
-            HIPCHK(c, hipMemset(W.d_data, 0, W.data_cap));
+            HIPCHK(c, hipMemset(W.d_data, 0, W.d_data.bytes()));
         W.psd_since = c->frame_no;
     }
     W.src_psd = off_psd;
@@ -406,7 +368,7 @@ int scan_evaluation(sdrx_ctx *c, const char *what, int leaf_id, bool arrays, con
     auto bad = [&] { return analysis_on(c->scan, source_of(c, leaf_id)) ? nullptr : "its source has no band scan (sdrx_set_scan)"; };
     if (int rc = watched_leaf_call(c, what, leaf_id, arrays, bad))
         return rc;
-    const ScanState *st = static_cast<const ScanState *>(c->scan.src[source_of(c, leaf_id)].d_state);
+    const ScanState *st = reinterpret_cast<const ScanState *>(c->scan.src[source_of(c, leaf_id)].d_state.get());
     struct {
         ScanRecord head;
         unsigned count, valid;
@@ -515,21 +477,21 @@ int sdrx_set_drift(sdrx_ctx *c, int leaf_id, const double *templ, int max_shift)
         return rc;
     D.set_at.resize(D.src.size(), 0);
     if (max_shift > 0) {
-        if (int rc = analysis_state(c, D, S, sizeof(DriftState)))
+        if (int rc = analysis_state(c, S, sizeof(DriftState)))
             return rc;
-        unsigned char *base = static_cast<unsigned char *>(S.d_state);
+        unsigned char *base = S.d_state;
         if (templ)
             HIPCHK(c, hipMemcpy(base + offsetof(DriftState, templ), templ, sizeof(double) * kSpecN, hipMemcpyHostToDevice));
         const unsigned capture = templ ? 0u : 1u; // (an upload also calls off a capture still waiting for its frame)
         HIPCHK(c, hipMemcpy(base + offsetof(DriftState, capture), &capture, sizeof capture, hipMemcpyHostToDevice));
     }
     unsigned long long &set_at = D.set_at[source_of(c, leaf_id)];
-    const sdrx_ctx::SourceAnalysis::Src before = S;
+    const sdrx_ctx::Switched before = S.on;
     const unsigned long long set_before = set_at;
     switch_to(S.on, max_shift, c->frame_no);
     set_at = c->frame_no;
     if (int rc = drift_rebuild(c, c->watch.src_ids, c->watch.src_psd)) {
-        S = before;
+        S.on = before;
         set_at = set_before;
         return rc;
     }
@@ -547,7 +509,7 @@ int sdrx_get_drift_profile(sdrx_ctx *c, int leaf_id, double *profile, int64_t *f
     if (c->frame_no <= std::max(std::max(c->drift.set_at[source_of(c, leaf_id)], S.on.since), c->watch.leaf[(size_t)leaf_id].on.since))
         return fail(c, SDRX_ESTATE, "sdrx_get_drift_profile: no frame has been measured for the source of vfo %d yet", leaf_id);
     if (profile)
-        HIPCHK(c, hipMemcpy(profile, static_cast<const unsigned char *>(S.d_state) + offsetof(DriftState, profile), sizeof(double) * (size_t)(2 * S.on.v + 1),
+        HIPCHK(c, hipMemcpy(profile, S.d_state + offsetof(DriftState, profile), sizeof(double) * (size_t)(2 * S.on.v + 1),
                             hipMemcpyDeviceToHost));
     if (frame)
         *frame = (int64_t)c->frame_no - 1;
@@ -572,20 +534,20 @@ int sdrx_set_scan(sdrx_ctx *c, int leaf_id, const sdrx_scan_cfg *cfg)
         return rc;
     S.cfg.resize(S.src.size(), ScanCfg{});
     if (on) {
-        if (int rc = analysis_state(c, S, R, sizeof(ScanState)))
+        if (int rc = analysis_state(c, R, sizeof(ScanState)))
             return rc;
         // every accepted setting restarts the integration, and the last evaluation is no longer this setting's
         static_assert(offsetof(ScanState, valid) == offsetof(ScanState, count) + sizeof(unsigned), "count and valid are cleared together");
-        HIPCHK(c, hipMemset(static_cast<unsigned char *>(R.d_state) + offsetof(ScanState, count), 0, 2 * sizeof(unsigned)));
+        HIPCHK(c, hipMemset(R.d_state + offsetof(ScanState, count), 0, 2 * sizeof(unsigned)));
     }
     ScanCfg &kept = S.cfg[source_of(c, leaf_id)];
-    const sdrx_ctx::SourceAnalysis::Src before = R;
+    const sdrx_ctx::Switched before = R.on;
     const ScanCfg cfg_before = kept;
     switch_to(R.on, on ? cfg->cell_bins : 0, c->frame_no);
     if (on)
         memcpy(&kept, cfg, sizeof kept);
     if (int rc = scan_rebuild(c, c->watch.src_ids, c->watch.src_psd)) {
-        R = before;
+        R.on = before;
         kept = cfg_before;
         return rc;
     }
