@@ -3,11 +3,15 @@
 // frames to sdrj::demodData, receive every leaf's payload through the publish hook.
 //
 //   sdrx_demo <profile.ini> --dump              descriptors as JSON lines (no GPU needed)
-//   sdrx_demo <profile.ini> --frames N [--u8] [--format cu8|cs8|cs16] [--fft TOPIC] [--devices 0,1,...]
+//   sdrx_demo <profile.ini> --frames N [--u8] [--format cu8|cs8|cs16] [--adc] [--fft TOPIC] [--devices 0,1,...]
 //                                               N synthetic LCG frames; one line per published
 //                                               message: frame topic rate bytes fnv1a64(payload)
 //                                               --u8 feeds them as dongle bytes, --format as integer samples of that
 //                                               format (the same sample values in each: the same messages); neither: floats
+//                                               --adc (library option adc_meter): one more line per frame behind its messages,
+//                                               adc frame fmt n sum_i sum_q sum_sq_i sum_sq_q sum_iq min_i max_i min_q max_q
+//                                               at_rail longest_rail_run bits_used | peak headroom_db dc_i dc_q rms
+//                                               (adc frame unmeasured for a frame of floats)
 #include <cinttypes>
 #include <cstdio>
 #include <iostream>
@@ -30,7 +34,7 @@ static uint64_t fnv1a(const void *p, size_t n)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16] [--adc] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
         return 2;
     }
     try {
@@ -58,7 +62,7 @@ int main(int argc, char **argv)
         if (mode != "--frames" || argc < 4)
             throw std::runtime_error("bad arguments");
         const int frames = std::atoi(argv[3]);
-        bool u8 = false;
+        bool u8 = false, adc = false;
         int fmt = SDRX_FMT_CU8;
         std::string fft_topic;
         std::vector<int> devices;
@@ -71,7 +75,9 @@ int main(int argc, char **argv)
                     throw std::runtime_error("--format takes cu8, cs8 or cs16");
                 fmt = f == "cu8" ? SDRX_FMT_CU8 : f == "cs8" ? SDRX_FMT_CS8 : SDRX_FMT_CS16;
                 u8 = true;
-            } else if (std::string(argv[a]) == "--fft" && a + 1 < argc)
+            } else if (std::string(argv[a]) == "--adc")
+                adc = true;
+            else if (std::string(argv[a]) == "--fft" && a + 1 < argc)
                 fft_topic = argv[++a];
             else if (std::string(argv[a]) == "--devices" && a + 1 < argc) { // one tree sharded over several GPUs
                 std::stringstream ss(argv[++a]);
@@ -85,6 +91,8 @@ int main(int argc, char **argv)
         sdrj radio(devices);
         radio.setVFOs(&P->mains);
         radio.setDCCorrection(P->correct_dc);
+        if (adc)
+            radio.setOption("adc_meter", 1);
         int frame_no = 0;
         radio.setPublisher([&](const char topic[5], uint32_t rate, const void *buf, uint32_t len) {
             char t[6] = {0, 0, 0, 0, 0, 0};
@@ -131,6 +139,18 @@ int main(int argc, char **argv)
                 radio.demodBytes(bytes.data(), P->frame);
             else
                 radio.demodData(iq.data(), (int)iq.size());
+            if (adc) {
+                const sdrx_adc_meter r = radio.adcMeter();
+                if (!r.measured) {
+                    std::printf("adc %d unmeasured\n", frame_no);
+                    continue;
+                }
+                const adc_levels_t L = adc_levels(r);
+                std::printf("adc %d %s %u %" PRId64 " %" PRId64 " %" PRIu64 " %" PRIu64 " %" PRId64 " %d %d %d %d %u %u %d | %.6g %.3f %.6g %.6g %.6g\n", frame_no,
+                            r.fmt == SDRX_FMT_CU8 ? "cu8" : r.fmt == SDRX_FMT_CS8 ? "cs8" : "cs16", r.n_complex, r.i.sum, r.q.sum, r.i.sum_sq, r.q.sum_sq,
+                            r.sum_iq, r.i.min, r.i.max, r.q.min, r.q.max, r.i.at_lo + r.i.at_hi + r.q.at_lo + r.q.at_hi, L.longest_rail_run,
+                            L.bits_used, L.peak, L.headroom_db, L.dc_i, L.dc_q, L.rms);
+            }
         }
         return 0;
     } catch (const std::exception &e) {

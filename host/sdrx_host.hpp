@@ -79,6 +79,50 @@ public:
 // publish(topic5, rate, payload, len): what vfo::transmitData hands to ZmqPublisher::publish.
 using publish_fn = std::function<void(const char topic[5], uint32_t rate, const void *buf, uint32_t len)>;
 
+// ------------------------------------------------------------------------------------------ ADC meter
+// What an sdrx_adc_meter record (library option "adc_meter" = 1, sdrj::adcMeter below) says about the front end, in the chain's
+// units -- CS16 codes times 2^-8, the 8-bit codes as they are; full scale is 128 for every format.  The arithmetic of
+// sdrreceiver_amd.ingest.adc_levels, operation for operation: the variances and the covariance from exact integers,
+// var_i = (n sum_sq_i - sum_i^2) / n^2, cov = (n sum_iq - sum_i sum_q) / n^2, each numerator converted to double once.
+struct adc_levels_t {
+    double dc_i = 0, dc_q = 0;  // means
+    double rms = 0;             // of the components, I and Q together, DC included
+    double peak = 0;            // largest |code|
+    double headroom_db = 0;     // 20 log10(128 / peak); +inf for an all-zero frame
+    double clip_share = 0;      // components at a rail / 2 n
+    uint32_t longest_rail_run = 0;
+    int bits_used = 0;          // the highest non-empty bin of bits[]
+    double gain_imbalance = 0;  // sqrt(var_i / var_q); NaN when an arm is constant
+    double phase_error = 0;     // asin(cov / sqrt(var_i var_q)), radians; NaN likewise
+};
+inline adc_levels_t adc_levels(const sdrx_adc_meter &r)
+{
+    if (!r.measured)
+        throw std::invalid_argument("adc_levels: the frame was not measured (it did not arrive as integer samples)");
+    typedef __int128 wide;
+    const double s = r.fmt == SDRX_FMT_CS16 ? 0.00390625 : 1.0, n = (double)r.n_complex, nn = n * n;
+    const wide N = (wide)r.n_complex;
+    const double var_i = (double)(N * (wide)r.i.sum_sq - (wide)r.i.sum * (wide)r.i.sum) / nn * s * s;
+    const double var_q = (double)(N * (wide)r.q.sum_sq - (wide)r.q.sum * (wide)r.q.sum) / nn * s * s;
+    const double cov = (double)(N * (wide)r.sum_iq - (wide)r.i.sum * (wide)r.q.sum) / nn * s * s;
+    auto mag = [](int32_t v) { return v < 0 ? -(int64_t)v : (int64_t)v; };
+    adc_levels_t L;
+    L.dc_i = (double)r.i.sum / n * s;
+    L.dc_q = (double)r.q.sum / n * s;
+    L.rms = std::sqrt((double)(r.i.sum_sq + r.q.sum_sq) / (2.0 * n)) * s;
+    L.peak = (double)std::max(std::max(mag(r.i.min), mag(r.i.max)), std::max(mag(r.q.min), mag(r.q.max))) * s;
+    L.headroom_db = L.peak > 0.0 ? 20.0 * std::log10(128.0 / L.peak) : HUGE_VAL;
+    L.clip_share = (double)((uint64_t)r.i.at_lo + r.i.at_hi + r.q.at_lo + r.q.at_hi) / (2.0 * n);
+    L.longest_rail_run = std::max(r.i.longest_rail_run, r.q.longest_rail_run);
+    for (int k = 0; k < 17; ++k)
+        if (r.bits[k])
+            L.bits_used = k;
+    const bool ok = var_i > 0.0 && var_q > 0.0;
+    L.gain_imbalance = ok ? std::sqrt(var_i / var_q) : NAN;
+    L.phase_error = ok ? std::asin(std::min(1.0, std::max(-1.0, cov / std::sqrt(var_i * var_q)))) : NAN;
+    return L;
+}
+
 class sdrj {
 public:
     explicit sdrj(int device = 0) : devices_(1, device) {}
@@ -194,6 +238,15 @@ public:
     }
     sdrx_ctx *context() { return ctx_; }
     sdrx_group *group() { return grp_; }
+    // ADC meter (library option "adc_meter" = 1, setOption before the first frame; no counterpart in the reference): the exact
+    // integer statistics of the last delivered frame's integer samples as they arrived -- demodBytes / demodSamples frames;
+    // measured = 0 after demodData.  adc_levels() above turns the record into levels, headroom and IQ balance.
+    sdrx_adc_meter adcMeter()
+    {
+        sdrx_adc_meter r;
+        call("get_adc_meter", sdrx_group_get_adc_meter, sdrx_get_adc_meter, &r);
+        return r;
+    }
     // Squelch-gated egress (library option "squelch" = 1, no counterpart in the reference): leaf ids[k] -- vfo::id after
     // start() -- opens when its meter sum_sq reaches thr_sum_sq[k] and stays open hang_frames[k] frames; between two frames.
     void set_squelch(const std::vector<int> &ids, const std::vector<uint64_t> &thr_sum_sq, const std::vector<uint32_t> &hang_frames)

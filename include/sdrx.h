@@ -775,6 +775,52 @@ typedef struct sdrx_wake_state { /* 32 bytes */
 int sdrx_set_wake(sdrx_ctx *ctx, const int *ids, const sdrx_wake_cfg *cfgs, int n);
 int sdrx_get_wake(sdrx_ctx *ctx, const int *ids, int n, sdrx_wake_state *out);
 
+/* ---- ADC meter (option "adc_meter" = 1, set before sdrx_finalize) ---------------------------------------------
+ * Every meter above sits behind the chain, on leaf payloads.  This one looks at what the front end delivers: with the option on,
+ * every frame that reaches the context AS INTEGER SAMPLES -- sdrx_process_u8 / sdrx_submit_u8, the *_fmt calls for host and for
+ * device frames, and the group's *_u8 / *_fmt calls -- gets one record of exact integer statistics of those samples as they
+ * arrived: before the conversion to float and before the DC-bias removal (correct_dc changes nothing in it).  The record is
+ * computed on the device (one launch per frame, in front of the conversion) and travels with the frame's fixed-size part.
+ *
+ * The integer code v of a component:
+ *   SDRX_FMT_CU8   b - 127, in [-127, 128]; the rails are the bytes 0 and 255
+ *   SDRX_FMT_CS8   the int8, in [-128, 127]
+ *   SDRX_FMT_CS16  the int16 ITSELF -- not scaled by 2^-8 --, in [-32768, 32767]
+ * "At a rail": equal to the format's lowest or highest code.  Multiply CS16 figures by 2^-8 (sums) or 2^-16 (sums of squares and
+ * of products) for the chain's units, "dongle LSB"; the 8-bit formats are in those units already.
+ *
+ * Everything is an exact integer and fits its type: a frame is at most one second long and n_complex < 2^31, so
+ * sum_sq <= n_complex * 2^30 < 2^61, |sum| and |sum_iq| likewise, and every count is at most 2 n_complex < 2^32.  The device's
+ * answer is therefore bit for bit a plain integer model of the definitions below; there is no tolerance.
+ *
+ * sdrx_get_adc_meter answers for the last DELIVERED frame, the one sdrx_get_output serves, and is readable while the next frame
+ * is in flight; frames queued with sdrx_process_device_fmt are brought over first (as for sdrx_get_meters).  A cf32 frame
+ * (sdrx_process, sdrx_submit, sdrx_process_device, sdrx_submit_device) and a shared frame (sdrx_*_shared, sdrx_*_if_same) did
+ * not arrive here as ADC samples: the record then has that frame's `frame`, measured = 0, fmt = -1 and zeros elsewhere, and
+ * nothing was launched for it.  SDRX_ESTATE with the option off, before sdrx_finalize or before any frame was delivered;
+ * SDRX_EINVAL for a NULL `out` (checked in this order, as the per-leaf calls do).  With the option off nothing changes at all:
+ * the same kernels, launches, device_bytes, payloads and callbacks.  The launch is not one of sdrx_get_kernel_times' kinds. */
+typedef struct sdrx_adc_arm {    /* 40 bytes: one component (I or Q) of the frame */
+    int64_t  sum;                /* sum of v */
+    uint64_t sum_sq;             /* sum of v*v */
+    int32_t  min, max;           /* smallest / largest v */
+    uint32_t at_lo, at_hi;       /* components equal to the lowest / highest code */
+    uint32_t longest_rail_run;   /* longest run of CONSECUTIVE samples of this arm that are each at a rail (either one) */
+    uint32_t reserved;
+} sdrx_adc_arm;
+typedef struct sdrx_adc_meter {  /* 184 bytes */
+    int64_t  frame;              /* as sdrx_meter.frame */
+    uint32_t n_complex;
+    int32_t  fmt;                /* SDRX_FMT_* of that frame; -1 if not measured */
+    uint32_t measured;           /* 0: the frame did not arrive here as integer samples; everything below is 0 */
+    uint32_t reserved;
+    sdrx_adc_arm i, q;
+    int64_t  sum_iq;             /* sum of vI * vQ */
+    uint32_t bits[17];           /* bits[k]: components, I and Q together, with bit_length(|v|) == k (0 for v = 0, 16 for -32768); sums to 2 n_complex */
+    uint32_t reserved2;
+} sdrx_adc_meter;
+int sdrx_get_adc_meter(sdrx_ctx *ctx, sdrx_adc_meter *out);
+
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);
@@ -1019,6 +1065,9 @@ int sdrx_group_get_scan_cells(sdrx_group *grp, int leaf_id, double *cells, int64
  * the leaf; `frame` and `since_frame` count the group's frames. */
 int sdrx_group_set_wake(sdrx_group *grp, const int *ids, const sdrx_wake_cfg *cfgs, int n);
 int sdrx_group_get_wake(sdrx_group *grp, const int *ids, int n, sdrx_wake_state *out);
+/* sdrx_get_adc_meter for the group (group option "adc_meter" = 1, applied to every member): every member that is sent the
+ * integers measures them, the records are identical, and the first member answers. */
+int sdrx_group_get_adc_meter(sdrx_group *grp, sdrx_adc_meter *out);
 
 /* sdrx_get_preroll routed to the member that owns the leaf; sdrx_get_preroll_count summed over the members (group option
  * "preroll" = 1). */

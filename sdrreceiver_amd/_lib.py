@@ -131,6 +131,19 @@ class WakeStateC(C.Structure):
                 ("hold_left", C.c_uint32), ("controlled", C.c_int32)]
 
 
+class AdcArmC(C.Structure):
+    """struct sdrx_adc_arm"""
+    _fields_ = [("sum", C.c_int64), ("sum_sq", C.c_uint64), ("min", C.c_int32), ("max", C.c_int32), ("at_lo", C.c_uint32),
+                ("at_hi", C.c_uint32), ("longest_rail_run", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AdcMeterC(C.Structure):
+    """struct sdrx_adc_meter"""
+    _fields_ = [("frame", C.c_int64), ("n_complex", C.c_uint32), ("fmt", C.c_int32), ("measured", C.c_uint32),
+                ("reserved", C.c_uint32), ("i", AdcArmC), ("q", AdcArmC), ("sum_iq", C.c_int64), ("bits", C.c_uint32 * 17),
+                ("reserved2", C.c_uint32)]
+
+
 PUBLISH_FN =C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
 
 # every symbol include/sdrx.h declares: (restype, argtypes)
@@ -220,6 +233,8 @@ SYMBOLS = {
     "sdrx_get_wake": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_group_set_wake": (_i, [_vp, _vp, _vp, _i]),
     "sdrx_group_get_wake": (_i, [_vp, _vp, _i, _vp]),
+    "sdrx_get_adc_meter": (_i, [_vp, C.POINTER(AdcMeterC)]),
+    "sdrx_group_get_adc_meter": (_i, [_vp, C.POINTER(AdcMeterC)]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

@@ -20,6 +20,8 @@
 //   k_dc_apply<FMT>       ingest.hip    /  (the kernels that read samples are templates on the format; the chain kernels serve every format)
 //   k_dc_block_sums<FMT>  ingest.hip    \ the same in the tolerance arithmetic: a blocked scan of the linear recurrence
 //   k_ingest_dc_fast<FMT> ingest.hip    /
+//   k_adc_meter<FMT>      adcmeter.hip  (none: option adc_meter -- exact integer statistics of an integer frame as it arrived: sums, min / max,
+//                                       rail counts, the longest rail run, a bit-length histogram; include/sdrx.h sdrx_adc_meter)
 //   k_mix_decimate        mix.hip       vfo::process mix loop, vfo.cpp:237-245; HalfBandDecimator::decimate, halfbanddecimator.cpp:43-72,
 //                                       with FIR::...HalfBandQueue, dsp.cpp:96-173 (mix_item); option fuse_late: the FIR part of
 //                                       vfo::usb_decimdemod, vfo.cpp:334-356, inside a d = 0 leaf's wave (late_item); option fuse_demod:
@@ -48,6 +50,7 @@ namespace sdrx {
 #include "dev_helpers.hip"
 #include "nco.hip"
 #include "ingest.hip"
+#include "adcmeter.hip"
 #include "meter.hip"
 #include "demod.hip"
 #include "mix.hip"

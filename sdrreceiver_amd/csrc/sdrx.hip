@@ -65,6 +65,10 @@ static_assert(sizeof(sdrx_wake_cfg) == 32 && sizeof(WakeCfg) == 32 && offsetof(s
                   sizeof(WakeRecord) == 32 && offsetof(sdrx_wake_state, hold_left) == offsetof(WakeRecord, hold_left) &&
                   offsetof(sdrx_wake_state, controlled) == offsetof(WakeRecord, controlled),
               "sdrx_wake_cfg / sdrx_wake_state ABI layout");
+static_assert(sizeof(sdrx_adc_arm) == 40 && sizeof(AdcArm) == 40 && offsetof(sdrx_adc_arm, longest_rail_run) == offsetof(AdcArm, longest_rail_run) &&
+                  sizeof(sdrx_adc_meter) == 184 && sizeof(AdcRecord) == 184 && offsetof(sdrx_adc_meter, q) == offsetof(AdcRecord, q) &&
+                  offsetof(sdrx_adc_meter, sum_iq) == offsetof(AdcRecord, sum_iq) && offsetof(sdrx_adc_meter, bits) == offsetof(AdcRecord, bits),
+              "sdrx_adc_arm / sdrx_adc_meter ABI layout");
 
 #include "sdrx_ctx.h"
 
@@ -110,6 +114,7 @@ void free_device_state(sdrx_ctx *c)
     c->drift = sdrx_ctx::Drift();
     c->scan = sdrx_ctx::Scan();
     c->wake = sdrx_ctx::Wake();
+    c->adc = sdrx_ctx::Adc();
 }
 
 } // namespace
@@ -248,6 +253,8 @@ int sdrx_set_option(sdrx_ctx *c, const char *name, int value)
         c->opt_agc = value != 0;
     else if (!strcmp(name, "wake"))
         c->opt_wake = value != 0;
+    else if (!strcmp(name, "adc_meter"))
+        c->opt_adc_meter = value != 0;
     else
         return fail(c, SDRX_EINVAL, "unknown option '%s'", name);
     return SDRX_OK;
@@ -1133,7 +1140,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
     const size_t raw_bytes = c->d_raw[0].bytes() + c->d_raw_u8[0].bytes(); // (ONE parity of the host-fed frames' buffers: kept for compatibility)
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes());
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes() + c->adc.bytes());
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

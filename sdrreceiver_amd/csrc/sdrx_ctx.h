@@ -120,6 +120,7 @@ struct sdrx_ctx : CtxBuffers {
     int opt_fuse = 1, opt_frame_pipeline = 1, opt_fuse_late = 1, opt_keep_streams = 0, opt_fuse_demod = 0;
     int opt_tail_in_levels = 1;
     int opt_meter = 0, opt_squelch = 0, opt_preroll = 0, opt_squelch_auto = 0, opt_park = 0, opt_watch = 0, opt_catchup = 0, opt_agc = 0, opt_wake = 0;
+    int opt_adc_meter = 0;
     // option meter: per frame parity, behind the payloads in d_pay / h_pay (at meter_off), one 16-byte MeterAcc record per work
     // unit that emits payload values (meter.hip "output meters"); the records travel in the payload copy
     size_t meter_off = 0;
@@ -346,6 +347,24 @@ struct sdrx_ctx : CtxBuffers {
         bool controlled(int id) const { return !ctl.empty() && ctl[(size_t)id].v != 0; }
         bool controlled_at(int id, unsigned long long frame) const { return !ctl.empty() && ctl[(size_t)id].at(frame) != 0; }
     } wake;
+
+    // Option adc_meter (adcmeter.hip): exact integer statistics of every frame that reaches the context as integer
+    // samples.  Allocated at sdrx_finalize with the option on: one AdcPartial per workgroup of the longest frame, the launch's
+    // counter, and the record of frame f (`rec`, one AdcRecord).  A frame that is not measured launches nothing, so its slot
+    // holds stale bytes: `note` says per frame parity which frame the slot was last written for and in which format, and the
+    // getter answers from it.
+    struct AdcDevice { // what free_device_state releases
+        DevBuf<AdcPartial> d_part;
+        DevBuf<unsigned> d_count;
+        Records rec;
+        size_t bytes() const { return d_part.bytes() + d_count.bytes() + 2 * rec.bytes(); } // device memory the option holds
+    };
+    struct Adc : AdcDevice {
+        struct Note {
+            unsigned long long frame = 0;
+            int fmt = -1; // -1: nothing measured yet
+        } note[2];
+    } adc;
 
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first

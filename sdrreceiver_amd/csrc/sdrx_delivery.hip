@@ -106,10 +106,11 @@ void publish_all(sdrx_ctx *c, int slot)
 // Both only read d_pay[p], d_pack[p] and the directory, whose next writer is frame f+2 (the safety argument above
 // enqueue_frame, sdrx_frame.hip).
 // Option watch: the records of the frame of parity p, part of what always travels -- the watch's, then the drift's and the band
-// scan's of its sources, and option wake's of the controlled leaves (each: nothing before the first call that switched one on)
+// scan's of its sources, and option wake's of the controlled leaves (each: nothing before the first call that switched one on);
+// and option adc_meter's record of the frame's integer samples (nothing with the option off)
 int queue_watch(sdrx_ctx *c, int p, hipStream_t st)
 {
-    for (const sdrx_ctx::Records *r : {&c->watch.rec, &c->drift.rec, &c->scan.rec, &c->wake.rec})
+    for (const sdrx_ctx::Records *r : {&c->watch.rec, &c->drift.rec, &c->scan.rec, &c->wake.rec, &c->adc.rec})
         if (r->d[p])
             HIPCHK(c, hipMemcpyAsync(r->h[p], r->d[p], r->bytes(), hipMemcpyDeviceToHost, st));
     return SDRX_OK;
@@ -626,6 +627,33 @@ int sdrx_get_preroll(sdrx_ctx *c, int id, const void **buf, uint32_t *len, int64
         *len = plen;
     if (frame)
         *frame = (int64_t)c->host_frame - 1;
+    return SDRX_OK;
+}
+
+// Option adc_meter: the record of the delivered frame.  Whether that frame was measured is the host's note of the frame's
+// parity (the slot of a frame that launched nothing holds an older frame's bytes).
+int sdrx_get_adc_meter(sdrx_ctx *c, sdrx_adc_meter *out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_adc_meter before sdrx_finalize");
+    if (!c->opt_adc_meter)
+        return fail(c, SDRX_ESTATE, "sdrx_get_adc_meter: option \"adc_meter\" is off");
+    if (!out)
+        return fail(c, SDRX_EINVAL, "sdrx_get_adc_meter: null output pointer");
+    if (int rc = need_delivered(c, "sdrx_get_adc_meter"))
+        return rc;
+    const int p = c->host_slot;
+    const sdrx_ctx::Adc::Note &N = c->adc.note[p];
+    memset(out, 0, sizeof *out);
+    out->frame = (int64_t)c->host_frame;
+    out->fmt = -1;
+    if (N.fmt < 0 || N.frame != c->host_frame)
+        return SDRX_OK;
+    memcpy(out, c->adc.rec.host<AdcRecord>(p), sizeof *out);
+    if (!out->measured || out->frame != (int64_t)c->host_frame || out->fmt != N.fmt)
+        return fail(c, SDRX_EHIP, "sdrx_get_adc_meter: the record of frame %llu did not arrive (it names frame %lld)", c->host_frame, (long long)out->frame);
     return SDRX_OK;
 }
 

@@ -1016,6 +1016,18 @@ void catchup_setup(sdrx_ctx *c, const Built &B)
         c->cu.leaf[(size_t)B.n3[(size_t)w.vfo]].blk[3].push_back(w);
 }
 
+// Option adc_meter: what k_adc_meter needs for this context's frames -- one partial per workgroup of a frame, the launch's
+// counter, and the record buffers of both frame parities with their pinned copies.  All of it or (the caller releases) none.
+int adc_setup(sdrx_ctx *c)
+{
+    if (!c->opt_adc_meter)
+        return SDRX_OK;
+    const size_t nb = ((size_t)c->root_frame + kAdcWg - 1) / kAdcWg;
+    if (c->adc.d_part.alloc(nb) != hipSuccess || c->adc.d_count.alloc(1, true) != hipSuccess || c->adc.rec.alloc(sizeof(AdcRecord)) != hipSuccess)
+        return fail(c, SDRX_ENOMEM, "sdrx_finalize: no memory for the ADC meter (option \"adc_meter\")");
+    return SDRX_OK;
+}
+
 int finalize_impl(sdrx_ctx *c)
 {
     if (int rc = derive_nodes(c))
@@ -1035,6 +1047,8 @@ int finalize_impl(sdrx_ctx *c)
     if (int rc = park_setup(c, B))
         return rc;
     if (int rc = agc_setup(c))
+        return rc;
+    if (int rc = adc_setup(c))
         return rc;
     catchup_setup(c, B);
     c->sq.preroll_fused = false;

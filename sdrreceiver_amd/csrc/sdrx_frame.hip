@@ -728,6 +728,28 @@ const SampleKernels &sample_kernels(int fmt)
 bool known_format(int fmt) { return fmt == SDRX_FMT_CU8 || fmt == SDRX_FMT_CS8 || fmt == SDRX_FMT_CS16; }
 size_t sample_bytes(int fmt, int n_complex) { return (size_t)n_complex * (fmt == SDRX_FMT_CS16 ? 4 : 2); }
 
+// Option adc_meter: the statistics of the next frame's integer samples as they lie at `dev_samples` (format `fmt`), on the
+// context's stream in front of everything that converts them -- one k_adc_meter launch, its record into the frame parity's
+// slot, and the host's note that this slot now belongs to that frame.  Called wherever a frame of integer samples enters a
+// context: enqueue_samples_device, and the group's dongle bytes without DC removal (group_enqueue).  Not bracketed:
+// sdrx_get_kernel_times keeps its SDRX_NKERNELS kinds, and k_ingest stays the conversion.  Option off: nothing.
+void adc_meter_launch(sdrx_ctx *c, const void *dev_samples, int n_complex, int fmt)
+{
+    if (!c->opt_adc_meter)
+        return;
+    static void (*const K[3])(const unsigned *, int, long long, AdcPartial *, unsigned *, AdcRecord *, int, int) = {
+        k_adc_meter<SDRX_FMT_CU8>, k_adc_meter<SDRX_FMT_CS8>, k_adc_meter<SDRX_FMT_CS16>};
+    const int p = (int)(c->frame_no & 1ull);
+    const int nb = (n_complex + kAdcWg - 1) / kAdcWg; // workgroups = partials
+    if ((size_t)nb > c->adc.d_part.count()) // (never: every frame has root_frame samples, what adc_setup sized for)
+        return;
+    const int per = (nb + kAdcThreads - 1) / kAdcThreads, cnt = (nb + per - 1) / per; // the last workgroup's merge: partials per thread, threads
+    hipLaunchKernelGGL(K[fmt], dim3(nb), dim3(kAdcThreads), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_samples), n_complex,
+                       (long long)c->frame_no, c->adc.d_part.get(), c->adc.d_count.get(), c->adc.rec.dev<AdcRecord>(p), per, cnt);
+    c->adc.note[p].frame = c->frame_no;
+    c->adc.note[p].fmt = fmt;
+}
+
 // What the DC-bias removal of this context's frames holds on the device, by the first frame that asks for it (nothing once it
 // exists: the options and the frame length are fixed): the accumulator, and the fast scan's table or the exact removal's work
 // buffer and counters.  All of it or -- the caller resets dc's device part on an error -- none.
@@ -773,6 +795,7 @@ int dc_first_use(sdrx_ctx *c, int n_complex, int nchunks)
 int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, int fmt, int correct_dc, bool egress)
 {
     const SampleKernels &K = sample_kernels(fmt);
+    adc_meter_launch(c, dev_bytes, n_complex, fmt); // (option adc_meter: the samples as they arrived, in front of everything)
     int mode = kRawU8;
     const int nchunks = (n_complex + kChunk - 1) / kChunk;
     if (correct_dc)

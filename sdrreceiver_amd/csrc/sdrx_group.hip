@@ -113,6 +113,8 @@ int group_enqueue(sdrx_group *g, const void *src, size_t bytes, int raw_mode, bo
             // take this way with or without DC removal: every member converts the integer samples it was sent itself
             rc = enqueue_samples_device(M.c, raw, g->root_frame, fmt, correct_dc, egress); // (leaves last_raw = tile layout: sdrx_get_raw serves it)
         } else {
+            if (raw_mode == kRawU8) // dongle bytes without DC removal: the one integer frame that does not pass enqueue_samples_device
+                adc_meter_launch(M.c, raw, g->root_frame, SDRX_FMT_CU8);
             rc = enqueue_frame(M.c, raw, raw_mode, egress);
         }
         if (rc) {
@@ -838,6 +840,19 @@ int sdrx_group_set_wake(sdrx_group *g, const int *ids, const sdrx_wake_cfg *cfgs
 int sdrx_group_get_wake(sdrx_group *g, const int *ids, int n, sdrx_wake_state *out)
 {
     return group_gather(g, "sdrx_group_get_wake", ids, n, out, sdrx_get_wake);
+}
+
+// Every member that is sent the integers measures them, and the records are identical: the first member answers.
+int sdrx_group_get_adc_meter(sdrx_group *g, sdrx_adc_meter *out)
+{
+    if (!g)
+        return SDRX_EINVAL;
+    if (!g->finalized)
+        return gfail(g, SDRX_ESTATE, "sdrx_group_get_adc_meter before sdrx_group_finalize");
+    for (size_t k = 0; k < g->m.size(); ++k)
+        if (g->m[k].c)
+            return member_rc(g, (int)k, sdrx_get_adc_meter(g->m[k].c, out));
+    return gfail(g, SDRX_ESTATE, "sdrx_group_get_adc_meter: no member holds a VFO");
 }
 
 int sdrx_group_get_egress(sdrx_group *g, int64_t *frame, uint32_t *n_open, uint32_t *n_leaves, uint64_t *payload_bytes_copied)

@@ -46,3 +46,96 @@ def to_float(a, fmt=None) -> np.ndarray:
     if fmt == CS8:
         return a.astype(np.float32)
     return a.astype(np.float32) * np.float32(2.0 ** -8)
+
+
+# ---- ADC meter (option ``adc_meter``; include/sdrx.h sdrx_adc_meter): the record, and the figures a front-end loop wants --------
+# The integer code v of a component: CU8 b - 127, CS8 the int8, CS16 the int16 itself.  LOWEST / HIGHEST: the rails per format.
+LOWEST = {CU8: -127, CS8: -128, CS16: -32768}
+HIGHEST = {CU8: 128, CS8: 127, CS16: 32767}
+FULL_SCALE = 128.0  # the largest |code| of every format in the chain's units, "dongle LSB" (CS16 codes times 2**-8)
+ADC_BINS = 17
+
+
+def codes(a, fmt=None) -> np.ndarray:
+    """The integer codes (int64, interleaved I,Q) the ADC meter counts: the table above."""
+    a, fmt = as_samples(a, fmt)
+    return a.astype(np.int64) - 127 if fmt == CU8 else a.astype(np.int64)
+
+
+def _arm_dict(a) -> dict:
+    return {"sum": int(a.sum), "sum_sq": int(a.sum_sq), "min": int(a.min), "max": int(a.max), "at_lo": int(a.at_lo),
+            "at_hi": int(a.at_hi), "longest_rail_run": int(a.longest_rail_run)}
+
+
+def adc_dict(r) -> dict:
+    """One ``sdrx_adc_meter`` record as a dict of Python ints: ``frame``, ``n_complex``, ``fmt``, ``measured``, the arms ``i`` and
+    ``q`` (dicts: ``sum``, ``sum_sq``, ``min``, ``max``, ``at_lo``, ``at_hi``, ``longest_rail_run``), ``sum_iq`` and ``bits``
+    (a list of 17 counts)."""
+    return {"frame": int(r.frame), "n_complex": int(r.n_complex), "fmt": int(r.fmt), "measured": int(r.measured),
+            "i": _arm_dict(r.i), "q": _arm_dict(r.q), "sum_iq": int(r.sum_iq), "bits": [int(b) for b in r.bits]}
+
+
+def adc_levels(rec: dict) -> dict:
+    """What the record says about the front end, in the chain's units (CS16 codes times 2**-8, the 8-bit codes as they are):
+
+    ``dc_i``, ``dc_q`` (means), ``rms`` (of the components, I and Q together, DC included), ``peak`` (largest ``|code|``),
+    ``headroom_db = 20 log10(FULL_SCALE / peak)`` (inf for an all-zero frame), ``clip_share`` (components at a rail / 2n),
+    ``longest_rail_run`` (the longer of the arms'), ``bits_used`` (the highest non-empty bin of ``bits``),
+    ``gain_imbalance = sqrt(var_i / var_q)`` and ``phase_error = asin(cov_iq / sqrt(var_i var_q))`` in radians (nan when an
+    arm is constant).  Variances and the covariance come from exact integers: ``var_i = (n sum_sq_i - sum_i**2) / n**2`` and
+    ``cov_iq = (n sum_iq - sum_i sum_q) / n**2``, each numerator converted to float64 once.  ValueError for a record that was
+    not measured."""
+    if not rec["measured"]:
+        raise ValueError("the frame was not measured: it did not arrive as integer samples")
+    n = int(rec["n_complex"])
+    s = 2.0 ** -8 if rec["fmt"] == CS16 else 1.0
+    i, q = rec["i"], rec["q"]
+    nn = float(n) * float(n)
+    var_i = float(n * i["sum_sq"] - i["sum"] ** 2) / nn * s * s
+    var_q = float(n * q["sum_sq"] - q["sum"] ** 2) / nn * s * s
+    cov = float(n * rec["sum_iq"] - i["sum"] * q["sum"]) / nn * s * s
+    peak = float(max(abs(i["min"]), abs(i["max"]), abs(q["min"]), abs(q["max"]))) * s
+    used = [k for k, b in enumerate(rec["bits"]) if b]
+    ok = var_i > 0.0 and var_q > 0.0
+    return {
+        "dc_i": float(i["sum"]) / float(n) * s,
+        "dc_q": float(q["sum"]) / float(n) * s,
+        "rms": float(np.sqrt(float(i["sum_sq"] + q["sum_sq"]) / (2.0 * float(n)))) * s,
+        "peak": peak,
+        "headroom_db": float(20.0 * np.log10(FULL_SCALE / peak)) if peak > 0.0 else float("inf"),
+        "clip_share": float(i["at_lo"] + i["at_hi"] + q["at_lo"] + q["at_hi"]) / (2.0 * float(n)),
+        "longest_rail_run": max(i["longest_rail_run"], q["longest_rail_run"]),
+        "bits_used": used[-1] if used else 0,
+        "gain_imbalance": float(np.sqrt(var_i / var_q)) if ok else float("nan"),
+        "phase_error": float(np.arcsin(min(1.0, max(-1.0, cov / float(np.sqrt(var_i * var_q)))))) if ok else float("nan"),
+    }
+
+
+def suggest_tuner_gain(rec: dict, gains, current, headroom_db: float, unit_db: float = 0.1):
+    """The entry of the front end's gain list to set next, from one ADC record: the counterpart of
+    :func:`sdrreceiver_amd.meter.suggest_gains` for the gain in FRONT of the ADC.
+
+    `gains` is the caller's list of tuner gains, sorted ascending, in steps of `unit_db` dB (librtlsdr's lists are tenths of a
+    dB: 496 is 49.6 dB); `current` is the entry the frame was received with.  A change of g units moves the peak by
+    ``g * unit_db`` dB, so the answer is the largest entry whose predicted headroom ``headroom_now - (entry - current) *
+    unit_db`` still reaches `headroom_db` -- the peak closest to the asked headroom without going under it -- or the lowest
+    entry if none does.  A record whose ``longest_rail_run`` is 2 or more saw the converter saturate: its peak is a lower bound
+    only, and the answer is at most the entry below `current` (a step down at once, whatever the headroom says).  A frame
+    that was not measured or is all zeros says nothing: `current` comes back.
+
+    There is deliberately no default headroom, as there is none for squelch, AGC or scan: how far below full scale the
+    strongest signal of YOUR band may come is the caller's to choose."""
+    g = sorted(gains)
+    if not g:
+        raise ValueError("an empty gain list")
+    if not rec["measured"]:
+        return current
+    lv = adc_levels(rec)
+    if lv["peak"] <= 0.0:
+        return current
+    fits = [x for x in g if lv["headroom_db"] - (x - current) * float(unit_db) >= float(headroom_db)]
+    pick = fits[-1] if fits else g[0]
+    if lv["longest_rail_run"] >= 2:
+        lower = [x for x in g if x < current]
+        pick = min(pick, lower[-1] if lower else g[0])
+    return pick

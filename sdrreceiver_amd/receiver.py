@@ -212,6 +212,16 @@ class _LeafCalls:
         device's control in that frame; ``active`` and ``since_frame`` are then the host's bookkeeping)."""
         return _wake.wake_dict(self._get_list("get_wake", vids, _lib.WakeStateC)[1])
 
+    # -- ADC meter (option ``adc_meter``; sdrreceiver_amd.ingest has the derived figures): the integer samples as they arrived ---
+    def adc_meter(self) -> dict:
+        """The ADC record of the last delivered frame (:func:`sdrreceiver_amd.ingest.adc_dict`): exact integer statistics of the
+        frame's integer samples before conversion and DC removal; ``measured`` 0 (and ``fmt`` -1) for a frame that did not
+        arrive as integer samples.  On a group: the first member's record (every member's is the same).
+        :func:`sdrreceiver_amd.ingest.adc_levels` turns it into levels, headroom and IQ balance."""
+        out = _lib.AdcMeterC()
+        self._call("get_adc_meter", C.byref(out))
+        return ingest.adc_dict(out)
+
     # -- drift estimate (part of option ``watch``; sdrreceiver_amd.drift): the source's spectrum registered against a template --
     def set_drift(self, vid: int, template=None, max_shift: int = 0) -> None:
         """The drift estimate of the source of watched leaf `vid` from the next frame on, over the shifts ``-max_shift ..
@@ -301,7 +311,7 @@ class Receiver(_LeafCalls):
                  dc_blocks_per_step: int | None = None, fuse_demod: bool = False,
                  tail_in_levels: bool = True, meter: bool = False, squelch: bool = False, preroll: bool = False,
                  squelch_auto: bool = False, park: bool = False, watch: bool = False, catchup: bool = False,
-                 agc: bool = False, wake: bool = False):
+                 agc: bool = False, wake: bool = False, adc_meter: bool = False):
         self.L = _lib.lib()
         h = C.c_void_p()
         rc = self.L.sdrx_create(C.byref(h), int(device))
@@ -341,6 +351,8 @@ class Receiver(_LeafCalls):
             self._chk(self.L.sdrx_set_option(self.h, b"agc", 1))
         if wake:
             self._chk(self.L.sdrx_set_option(self.h, b"wake", 1))
+        if adc_meter:
+            self._chk(self.L.sdrx_set_option(self.h, b"adc_meter", 1))
         self._chk(self.L.sdrx_set_option(self.h, b"dc_speculative", int(bool(dc_speculative))))
         if dc_blocks_per_step is not None:
             self._chk(self.L.sdrx_set_option(self.h, b"dc_blocks_per_step", int(dc_blocks_per_step)))
