@@ -3,7 +3,7 @@
 // frames to sdrj::demodData, receive every leaf's payload through the publish hook.
 //
 //   sdrx_demo <profile.ini> --dump              descriptors as JSON lines (no GPU needed)
-//   sdrx_demo <profile.ini> --frames N [--u8] [--format cu8|cs8|cs16] [--adc] [--fft TOPIC] [--devices 0,1,...]
+//   sdrx_demo <profile.ini> --frames N [--u8] [--format cu8|cs8|cs16] [--adc] [--input-rate HZ] [--fft TOPIC] [--devices 0,1,...]
 //                                               N synthetic LCG frames; one line per published
 //                                               message: frame topic rate bytes fnv1a64(payload)
 //                                               --u8 feeds them as dongle bytes, --format as integer samples of that
@@ -12,6 +12,9 @@
 //                                               adc frame fmt n sum_i sum_q sum_sq_i sum_sq_q sum_iq min_i max_i min_q max_q
 //                                               at_rail longest_rail_run bits_used | peak headroom_db dc_i dc_q rms
 //                                               (adc frame unmeasured for a frame of floats)
+//                                               --input-rate HZ: the frames are at HZ, not at the profile's sample rate, and
+//                                               the library's resampler makes the tree's frames from them; first line
+//                                               resampler fs_in fs_out L M taps_per_phase in_frame out_frame delay passband_hz
 #include <cinttypes>
 #include <cstdio>
 #include <iostream>
@@ -34,7 +37,7 @@ static uint64_t fnv1a(const void *p, size_t n)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16] [--adc] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16] [--adc] [--input-rate HZ] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
         return 2;
     }
     try {
@@ -63,7 +66,7 @@ int main(int argc, char **argv)
             throw std::runtime_error("bad arguments");
         const int frames = std::atoi(argv[3]);
         bool u8 = false, adc = false;
-        int fmt = SDRX_FMT_CU8;
+        int fmt = SDRX_FMT_CU8, input_rate = 0;
         std::string fft_topic;
         std::vector<int> devices;
         for (int a = 4; a < argc; ++a) {
@@ -77,6 +80,8 @@ int main(int argc, char **argv)
                 u8 = true;
             } else if (std::string(argv[a]) == "--adc")
                 adc = true;
+            else if (std::string(argv[a]) == "--input-rate" && a + 1 < argc)
+                input_rate = std::atoi(argv[++a]);
             else if (std::string(argv[a]) == "--fft" && a + 1 < argc)
                 fft_topic = argv[++a];
             else if (std::string(argv[a]) == "--devices" && a + 1 < argc) { // one tree sharded over several GPUs
@@ -114,10 +119,19 @@ int main(int argc, char **argv)
             radio.fftData = tap("Main");
             radio.fftVFOSlot(fft_topic);
         }
+        int n_frame = P->frame; // samples of a frame as it is handed over
+        if (input_rate > 0) {
+            radio.setInputRate(input_rate);
+            radio.start();
+            const sdrx_resampler_info R = radio.resampler();
+            n_frame = R.in_frame;
+            std::printf("resampler %d %d %d %d %d %d %d %.6f %.3f\n", R.fs_in, R.fs_out, R.L, R.M, R.taps_per_phase, R.in_frame, R.out_frame,
+                        R.delay_out_samples, R.passband_hz);
+        }
         // synthetic IQ of BASELINE.md: LCG x <- x*1664525 + 1013904223, component ((x >> 24) % 17) - 8
         uint32_t x = 1;
-        std::vector<float> iq((size_t)2 * P->frame);
-        std::vector<uint8_t> bytes((size_t)2 * P->frame);
+        std::vector<float> iq((size_t)2 * n_frame);
+        std::vector<uint8_t> bytes((size_t)2 * n_frame);
         std::vector<int8_t> s8(fmt == SDRX_FMT_CS8 ? bytes.size() : 0);
         std::vector<int16_t> s16(fmt == SDRX_FMT_CS16 ? bytes.size() : 0);
         for (frame_no = 0; frame_no < frames; ++frame_no) {
@@ -132,11 +146,11 @@ int main(int argc, char **argv)
                     s16[i] = (int16_t)(256 * c); // c * 2^8: the same sample value
             }
             if (fmt == SDRX_FMT_CS8)
-                radio.demodSamples(s8.data(), P->frame, fmt);
+                radio.demodSamples(s8.data(), n_frame, fmt);
             else if (fmt == SDRX_FMT_CS16)
-                radio.demodSamples(s16.data(), P->frame, fmt);
+                radio.demodSamples(s16.data(), n_frame, fmt);
             else if (u8)
-                radio.demodBytes(bytes.data(), P->frame);
+                radio.demodBytes(bytes.data(), n_frame);
             else
                 radio.demodData(iq.data(), (int)iq.size());
             if (adc) {

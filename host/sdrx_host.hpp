@@ -147,6 +147,27 @@ public:
     void setDCCorrection(bool dc) { correctDC = dc; }
     void setPublisher(publish_fn f) { publish_ = std::move(f); }
     void setOption(const std::string &name, int value) { options_[name] = value; }
+    // The front end's sample rate where it is not the main VFOs' Fs (Airspy at 10, 6, 3 or 2.5 MS/s, an RTL dongle at 2.4 or
+    // 2.048 MS/s; no counterpart in the reference): before the first frame.  Every frame handed to demodData / demodBytes /
+    // demodSamples then has resampler().in_frame samples at that rate, and a rational resampler on the device -- the library's
+    // own Kaiser design with `taps_per_phase` taps per phase and `atten_db` of stop band -- makes the tree's frame from it
+    // (include/sdrx.h "Resampler").  0: off.  One device only.
+    void setInputRate(int fs_in, int taps_per_phase = 32, double atten_db = 80.0)
+    {
+        if (started())
+            throw std::runtime_error("sdrj::setInputRate after the first frame");
+        input_rate_ = fs_in, rs_taps_ = taps_per_phase, rs_atten_ = atten_db;
+    }
+    // ... and what it is once the tree is committed (start()): ratio, frame lengths, delay and pass band
+    sdrx_resampler_info resampler()
+    {
+        if (!ctx_ || !input_rate_)
+            throw std::runtime_error("sdrj::resampler: no input rate set, or not started");
+        sdrx_resampler_info info;
+        check(sdrx_get_resampler(ctx_, &info, nullptr, 0), "sdrx_get_resampler");
+        info.passband_hz = rs_passband_;
+        return info;
+    }
     // sdrj.cpp:84-101: the raw spectrum is selected by the topic "Main"; any selection restarts
     // the every-4th-call counter of demodData (sdrj.cpp:296-303)
     void fftVFOSlot(const std::string &topic)
@@ -161,6 +182,8 @@ public:
     {
         if (!mpVFOs || mpVFOs->empty())
             throw std::runtime_error("sdrj: no main VFOs");
+        if (devices_.size() > 1 && input_rate_)
+            throw std::runtime_error("sdrj: the resampler (setInputRate) is not offered on several devices");
         if (devices_.size() > 1) {
             check(sdrx_group_create(&grp_, devices_.data(), (int)devices_.size()), "sdrx_group_create");
             for (auto &kv : options_)
@@ -176,6 +199,14 @@ public:
             check(sdrx_set_option(ctx_, kv.first.c_str(), kv.second), "sdrx_set_option");
         for (vfo *m : *mpVFOs)
             add(m, -1); // parents first: ids are creation order = the reference's publish order
+        if (input_rate_) { // (behind the VFOs: the first main's Fs is the output rate)
+            std::vector<float> taps(32768);
+            sdrx_resampler_info info;
+            if (sdrx_resampler_design(input_rate_, (*mpVFOs)[0]->d.fs, rs_taps_, rs_atten_, taps.data(), (int)taps.size(), &info) != SDRX_OK)
+                throw std::runtime_error(std::string("sdrx_resampler_design: ") + sdrx_last_error(nullptr));
+            rs_passband_ = info.passband_hz;
+            check(sdrx_set_resampler(ctx_, input_rate_, taps.data(), rs_taps_), "sdrx_set_resampler");
+        }
         check(sdrx_set_publish_callback(ctx_, &sdrj::trampoline, this), "sdrx_set_publish_callback");
         check(sdrx_finalize(ctx_), "sdrx_finalize");
     }
@@ -554,6 +585,8 @@ private:
     std::vector<float> samples_;
     publish_fn publish_;
     std::map<std::string, int> options_;
+    int input_rate_ = 0, rs_taps_ = 32; // setInputRate
+    double rs_atten_ = 80.0, rs_passband_ = 0;
 };
 
 // ------------------------------------------------------------------------------------------ INI

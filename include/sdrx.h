@@ -821,6 +821,61 @@ typedef struct sdrx_adc_meter {  /* 184 bytes */
 } sdrx_adc_meter;
 int sdrx_get_adc_meter(sdrx_ctx *ctx, sdrx_adc_meter *out);
 
+/* ---- Resampler (sdrx_set_resampler before sdrx_finalize) ---------------------------------------------------------
+ * A tree can only halve, and end in /5 or /6: its root rate is 48 kHz or 12 kHz times a power of two, times 1, 5 or 6.  A front
+ * end with a fixed master clock -- Airspy R2 at 10 and 2.5 MS/s, Airspy Mini at 6 and 3 MS/s, an RTL dongle at 2.4 or 2.048 MS/s
+ * -- delivers another rate.  With a resampler set, the frames handed to the context are at the front end's rate fs_in, and one
+ * more kernel, a polyphase rational resampler L/M behind the ingest kernels, makes the tree's raw frame from them.  The
+ * reference has no counterpart: this text is the definition.  Off (the default) nothing changes at all: the same kernels,
+ * launches, device_bytes, payloads and callbacks.
+ *
+ * Ratio and frame lengths.  fs_out is the fs of the parent-less VFOs and n their samples_per_buffer.  With g = gcd(fs_in, fs_out):
+ * L = fs_out / g, M = fs_in / g, and the incoming frame has n_in = n M / L samples.  Required, else SDRX_EUNSUPPORTED at
+ * sdrx_finalize with the reason in sdrx_last_error:
+ *   n M % L == 0, so that every frame starts at phase 0;   n_in % 16 == 0 (the DC and ADC-meter kernels);   n_in >= taps_per_phase;
+ *   L <= 1024;   1/2 <= M / L <= 4;   taps_per_phase T a multiple of 4 in 8 .. 64;   L T <= 32768;
+ *   all parent-less VFOs have one fs and one frame length.
+ *
+ * Filter arithmetic.  The prototype is h[k], k < L T, fp32.  x_f[j] is frame f's cf32 input at the input rate: after the format
+ * conversion and, if asked for, after the DC-bias removal (in that order: the removal keeps the |x| <= 128 bound it is proved
+ * for).  For j < 0, x_f[j] := x_{f-1}[n_in + j], zero for the first frame after sdrx_finalize.  For output m in [0, n):
+ *   p = m M in 64 bits, i = p div L, ph = p mod L, and separately for re and im
+ *   acc_0 = +0.0f;  acc_{t+1} = fl(acc_t + fl(h[ph + t L] * x[i - t])), t = 0 .. T-1 ascending;  y[m] = acc_T
+ * -- two roundings per tap, no FMA, the same in all three settings of option "exact".  y is the tree's raw frame.  The group
+ * delay is (L T - 1) / (2 M) output samples.
+ *
+ * The built-in design (sdrx_resampler_design; host only, IEEE double, rounded once to fp32).  With N = L T and A = atten_db,
+ * 50 < A <= 120 (SDRX_EINVAL otherwise):
+ *   beta = 0.1102 (A - 8.7);   tw = (A - 7.95) / (2.285 (N - 1) 2 pi);   fn = 0.5 / max(L, M);   fc = fn - tw / 2
+ *   h[k] = L * 2 fc * sinc(2 fc (k - (N-1)/2)) * I0(beta sqrt(1 - (2k/(N-1) - 1)^2)) / I0(beta),   sinc(x) = sin(pi x) / (pi x)
+ * SDRX_EFILTER if fn - tw <= 0: the transition is wider than the band (5/3 with T = 8).  The stop band starts at the lower
+ * Nyquist rate, so nothing aliases into the pass band, which is (fn - tw) L fs_in Hz wide.
+ *
+ * sdrx_resampler_design needs no context and no device: the ratio rules above (SDRX_EUNSUPPORTED), then the design into `taps`
+ * (L T floats, prototype order; NULL: only `info`; SDRX_EINVAL if cap < L T).  in_frame and out_frame of `info` are 0.
+ * sdrx_set_resampler: before sdrx_finalize (SDRX_ESTATE after it) and after the first parent-less VFO was added (SDRX_ESTATE
+ * before: its fs is fs_out, which says how many taps L T the call copies from `taps` -- the caller's own, so a test can craft
+ * them; passband_hz of the info is then 0).  fs_in = 0 switches the resampler off again.
+ * sdrx_get_resampler: the info (in_frame and out_frame once finalized) and up to `cap` taps in prototype order (`taps` may be
+ * NULL); SDRX_ESTATE without a resampler.
+ * sdrx_get_resampler_input: the staged input-rate frame x_f of the last frame in natural order, under sdrx_get_raw's rules
+ * (and after caller-owned device frames too: the staging buffer is the context's).
+ *
+ * With a resampler set every frame call of the context -- sdrx_process, _u8, _fmt, _device*, their submit forms, cf32 and integer
+ * frames alike -- takes n_complex == in_frame; a frame of out_frame samples is SDRX_EINVAL.  sdrx_get_raw, the raw spectrum and
+ * the raw watch see the resampled frame (sdrx_get_raw also after sdrx_process_device); the ADC meter sees the in_frame samples
+ * as they arrived.  Dongle bytes without DC removal take the conversion pass too.  sdrx_*_shared and sdrx_*_if_same return
+ * SDRX_ESTATE if either context resamples.  Groups do not offer it. */
+typedef struct sdrx_resampler_info { /* 48 bytes */
+    int32_t fs_in, fs_out, L, M, taps_per_phase, in_frame, out_frame, reserved;
+    double delay_out_samples, passband_hz;
+} sdrx_resampler_info;
+int sdrx_resampler_design(int32_t fs_in, int32_t fs_out, int32_t taps_per_phase, double atten_db, float *taps, int32_t cap,
+                          sdrx_resampler_info *info);
+int sdrx_set_resampler(sdrx_ctx *ctx, int32_t fs_in, const float *taps, int32_t taps_per_phase);
+int sdrx_get_resampler(sdrx_ctx *ctx, sdrx_resampler_info *info, float *taps, int32_t cap);
+int sdrx_get_resampler_input(sdrx_ctx *ctx, float *out_iq, int32_t cap_complex);
+
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);

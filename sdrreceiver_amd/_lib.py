@@ -144,6 +144,13 @@ class AdcMeterC(C.Structure):
                 ("reserved2", C.c_uint32)]
 
 
+class ResamplerInfoC(C.Structure):
+    """struct sdrx_resampler_info"""
+    _fields_ = [("fs_in", C.c_int32), ("fs_out", C.c_int32), ("L", C.c_int32), ("M", C.c_int32), ("taps_per_phase", C.c_int32),
+                ("in_frame", C.c_int32), ("out_frame", C.c_int32), ("reserved", C.c_int32), ("delay_out_samples", C.c_double),
+                ("passband_hz", C.c_double)]
+
+
 PUBLISH_FN =C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
 
 # every symbol include/sdrx.h declares: (restype, argtypes)
@@ -235,6 +242,10 @@ SYMBOLS = {
     "sdrx_group_get_wake": (_i, [_vp, _vp, _i, _vp]),
     "sdrx_get_adc_meter": (_i, [_vp, C.POINTER(AdcMeterC)]),
     "sdrx_group_get_adc_meter": (_i, [_vp, C.POINTER(AdcMeterC)]),
+    "sdrx_resampler_design": (_i, [C.c_int32, C.c_int32, C.c_int32, C.c_double, _vp, C.c_int32, C.POINTER(ResamplerInfoC)]),
+    "sdrx_set_resampler": (_i, [_vp, C.c_int32, _vp, C.c_int32]),
+    "sdrx_get_resampler": (_i, [_vp, C.POINTER(ResamplerInfoC), _vp, C.c_int32]),
+    "sdrx_get_resampler_input": (_i, [_vp, _vp, C.c_int32]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

@@ -22,6 +22,8 @@
 //   k_ingest_dc_fast<FMT> ingest.hip    /
 //   k_adc_meter<FMT>      adcmeter.hip  (none: option adc_meter -- exact integer statistics of an integer frame as it arrived: sums, min / max,
 //                                       rail counts, the longest rail run, a bit-length histogram; include/sdrx.h sdrx_adc_meter)
+//   k_resample            resample.hip  (none: sdrx_set_resampler -- the polyphase rational resampler L/M between the ingest kernels and level 0, for
+//                                       front ends whose rate no chain of half-bands reaches; include/sdrx.h "Resampler")
 //   k_mix_decimate        mix.hip       vfo::process mix loop, vfo.cpp:237-245; HalfBandDecimator::decimate, halfbanddecimator.cpp:43-72,
 //                                       with FIR::...HalfBandQueue, dsp.cpp:96-173 (mix_item); option fuse_late: the FIR part of
 //                                       vfo::usb_decimdemod, vfo.cpp:334-356, inside a d = 0 leaf's wave (late_item); option fuse_demod:
@@ -41,6 +43,7 @@
 // __syncthreads() are wave-local (no cross-wave barrier traffic) and the segment walks the
 // frame chunk by chunk with the filter state resident in LDS.
 #include "sdrx_dev.h"
+#include "sdrx_resample.h"
 
 #include <type_traits>
 #include <utility>
@@ -51,6 +54,7 @@ namespace sdrx {
 #include "nco.hip"
 #include "ingest.hip"
 #include "adcmeter.hip"
+#include "resample.hip"
 #include "meter.hip"
 #include "demod.hip"
 #include "mix.hip"

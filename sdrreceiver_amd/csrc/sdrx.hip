@@ -65,6 +65,7 @@ static_assert(sizeof(sdrx_wake_cfg) == 32 && sizeof(WakeCfg) == 32 && offsetof(s
                   sizeof(WakeRecord) == 32 && offsetof(sdrx_wake_state, hold_left) == offsetof(WakeRecord, hold_left) &&
                   offsetof(sdrx_wake_state, controlled) == offsetof(WakeRecord, controlled),
               "sdrx_wake_cfg / sdrx_wake_state ABI layout");
+static_assert(sizeof(sdrx_resampler_info) == 48 && offsetof(sdrx_resampler_info, delay_out_samples) == 32, "sdrx_resampler_info ABI layout");
 static_assert(sizeof(sdrx_adc_arm) == 40 && sizeof(AdcArm) == 40 && offsetof(sdrx_adc_arm, longest_rail_run) == offsetof(AdcArm, longest_rail_run) &&
                   sizeof(sdrx_adc_meter) == 184 && sizeof(AdcRecord) == 184 && offsetof(sdrx_adc_meter, q) == offsetof(AdcRecord, q) &&
                   offsetof(sdrx_adc_meter, sum_iq) == offsetof(AdcRecord, sum_iq) && offsetof(sdrx_adc_meter, bits) == offsetof(AdcRecord, bits),
@@ -115,6 +116,7 @@ void free_device_state(sdrx_ctx *c)
     c->scan = sdrx_ctx::Scan();
     c->wake = sdrx_ctx::Wake();
     c->adc = sdrx_ctx::Adc();
+    static_cast<sdrx_ctx::ResamplerDevice &>(c->rs) = sdrx_ctx::ResamplerDevice();
 }
 
 } // namespace
@@ -890,6 +892,103 @@ int sdrx_get_raw(sdrx_ctx *c, float *out, int max_complex, int *n_ret)
     return SDRX_OK;
 }
 
+// ---- Resampler (include/sdrx.h; sdrx_resample.h has the ratio, the frame lengths and the design) ------------------------------
+static void resampler_info(const ResamplePlan &P, double passband_hz, sdrx_resampler_info *info)
+{
+    memset(info, 0, sizeof *info);
+    info->fs_in = P.fs_in, info->fs_out = P.fs_out;
+    info->L = P.L, info->M = P.M, info->taps_per_phase = P.T;
+    info->in_frame = P.n_in, info->out_frame = P.n_out;
+    info->delay_out_samples = resample_delay(P);
+    info->passband_hz = passband_hz;
+}
+
+int sdrx_resampler_design(int32_t fs_in, int32_t fs_out, int32_t taps_per_phase, double atten_db, float *taps, int32_t cap, sdrx_resampler_info *info)
+{
+    ResamplePlan P;
+    if (fs_in <= 0 || fs_out <= 0)
+        return fail(nullptr, SDRX_EINVAL, "sdrx_resampler_design: sample rates must be positive");
+    if (const char *why = resample_ratio(fs_in, fs_out, taps_per_phase, P))
+        return fail(nullptr, SDRX_EUNSUPPORTED, "sdrx_resampler_design %d -> %d S/s: %s", fs_in, fs_out, why);
+    if (taps && cap < P.L * P.T)
+        return fail(nullptr, SDRX_EINVAL, "sdrx_resampler_design: room for %d taps, the prototype has L * T = %d", cap, P.L * P.T);
+    double pass = 0;
+    const int rc = resample_design(P, atten_db, taps, &pass);
+    if (rc == 1)
+        return fail(nullptr, SDRX_EINVAL, "sdrx_resampler_design: atten_db must be above 50 and at most 120");
+    if (rc == 2)
+        return fail(nullptr, SDRX_EFILTER, "sdrx_resampler_design %d -> %d S/s: with %d taps per phase the transition is wider than the band", fs_in, fs_out,
+                    taps_per_phase);
+    if (info)
+        resampler_info(P, pass, info);
+    return SDRX_OK;
+}
+
+int sdrx_set_resampler(sdrx_ctx *c, int32_t fs_in, const float *taps, int32_t taps_per_phase)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_set_resampler after sdrx_finalize");
+    if (fs_in == 0) {
+        static_cast<sdrx_ctx::Resampler &>(c->rs) = sdrx_ctx::Resampler();
+        return SDRX_OK;
+    }
+    if (fs_in < 0 || !taps || taps_per_phase <= 0)
+        return fail(c, SDRX_EINVAL, "sdrx_set_resampler: fs_in and taps_per_phase must be positive and taps not null");
+    int fs_out = 0;
+    for (const Node &n : c->nodes)
+        if (n.d.parent_id < 0 && !fs_out)
+            fs_out = n.d.fs;
+    if (!fs_out)
+        return fail(c, SDRX_ESTATE, "sdrx_set_resampler before the first parent-less VFO was added: its fs is the output rate");
+    sdrx_ctx::Resampler R;
+    R.on = true;
+    if (const char *why = resample_ratio(fs_in, fs_out, taps_per_phase, R.plan))
+        R.refused = why; // (sdrx_finalize says so: SDRX_EUNSUPPORTED)
+    else
+        R.taps.assign(taps, taps + (size_t)R.plan.L * R.plan.T);
+    static_cast<sdrx_ctx::Resampler &>(c->rs) = std::move(R);
+    return SDRX_OK;
+}
+
+int sdrx_get_resampler(sdrx_ctx *c, sdrx_resampler_info *info, float *taps, int32_t cap)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->rs.on)
+        return fail(c, SDRX_ESTATE, "sdrx_get_resampler: no resampler set (sdrx_set_resampler)");
+    if (!info || (taps && cap < 0))
+        return fail(c, SDRX_EINVAL, "sdrx_get_resampler: null info or negative cap");
+    resampler_info(c->rs.plan, c->rs.passband_hz, info);
+    if (!c->finalized)
+        info->in_frame = info->out_frame = 0;
+    if (taps)
+        std::copy(c->rs.taps.begin(), c->rs.taps.begin() + std::min((size_t)cap, c->rs.taps.size()), taps);
+    return SDRX_OK;
+}
+
+int sdrx_get_resampler_input(sdrx_ctx *c, float *out, int32_t cap_complex)
+{
+    if (!c || !out)
+        return SDRX_EINVAL;
+    if (!c->rs.on)
+        return fail(c, SDRX_ESTATE, "sdrx_get_resampler_input: no resampler set (sdrx_set_resampler)");
+    if (!c->finalized || c->frame_no == 0)
+        return fail(c, SDRX_ESTATE, "sdrx_get_resampler_input: no frame processed yet");
+    if (c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "sdrx_get_resampler_input: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c))
+        return rc;
+    const int n = std::min((int)cap_complex, c->in_frame);
+    const size_t total = align_up((size_t)c->in_frame, kChunk);
+    std::vector<float2> t(total);
+    HIPCHK(c, hipMemcpy(t.data(), c->rs.d_stage, total * sizeof(float2), hipMemcpyDeviceToHost));
+    untile(t.data(), out, std::max(n, 0));
+    return SDRX_OK;
+}
+
 int sdrx_get_stream(sdrx_ctx *c, int id, float *out, int max_complex, int *n_ret)
 {
     if (!c || id < 0 || id >= (int)c->nodes.size())
@@ -1140,7 +1239,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
     const size_t raw_bytes = c->d_raw[0].bytes() + c->d_raw_u8[0].bytes(); // (ONE parity of the host-fed frames' buffers: kept for compatibility)
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes() + c->adc.bytes());
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes() + c->adc.bytes() + c->rs.bytes());
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

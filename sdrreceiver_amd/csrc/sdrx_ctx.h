@@ -366,6 +366,27 @@ struct sdrx_ctx : CtxBuffers {
         } note[2];
     } adc;
 
+    // Resampler (sdrx_set_resampler, resample.hip): frames arrive at the rate fs_in, in_frame samples each, and
+    // k_resample makes the tree's raw frame (root_frame samples in d_raw_tiled) from them.  The setting -- the rate and the
+    // caller's taps in prototype order, or why that ratio is not offered -- is the host's and stays; what finalize allocates
+    // with it: the input-rate frame in tile layout (where the ingest kernels then write), the history of both frame parities
+    // (kRsHist cf32 each, zeroed), and the taps phase-major.
+    struct ResamplerDevice { // what free_device_state releases
+        DevBuf<float2> d_stage;
+        DevBuf<float2> d_hist;
+        DevBuf<float> d_taps;
+        size_t bytes() const { return d_stage.bytes() + d_hist.bytes() + d_taps.bytes(); } // device memory it holds
+    };
+    struct Resampler : ResamplerDevice {
+        bool on = false;          // set (sdrx_set_resampler with fs_in > 0)
+        ResamplePlan plan;        // the ratio from the setting, the frame lengths from finalize
+        std::string refused;      // not empty: why finalize will refuse the ratio (no taps were copied)
+        std::vector<float> taps;  // L T floats, prototype order
+        double passband_hz = 0;
+        int lds_bytes = 0;        // k_resample's dynamic LDS: the output tile and the longest window
+    } rs;
+    int in_frame = 0; // samples of an incoming frame: root_frame, or with a resampler rs.plan.n_in
+
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first
     // frame that fills them.  The first such leaf uses the arena's buffer, further ones buffers of their own (`own`).

@@ -1022,15 +1022,59 @@ int adc_setup(sdrx_ctx *c)
 {
     if (!c->opt_adc_meter)
         return SDRX_OK;
-    const size_t nb = ((size_t)c->root_frame + kAdcWg - 1) / kAdcWg;
+    const size_t nb = ((size_t)c->in_frame + kAdcWg - 1) / kAdcWg; // (the frame as it arrives: at the input rate with a resampler)
     if (c->adc.d_part.alloc(nb) != hipSuccess || c->adc.d_count.alloc(1, true) != hipSuccess || c->adc.rec.alloc(sizeof(AdcRecord)) != hipSuccess)
         return fail(c, SDRX_ENOMEM, "sdrx_finalize: no memory for the ADC meter (option \"adc_meter\")");
+    return SDRX_OK;
+}
+
+// Resampler: the frame lengths of the ratio sdrx_set_resampler fixed, for the tree as it now stands (c->in_frame: what a frame
+// call takes), or why this tree cannot have it.  Off: in_frame = root_frame.
+int resample_plan_frames(sdrx_ctx *c)
+{
+    c->in_frame = c->root_frame;
+    if (!c->rs.on)
+        return SDRX_OK;
+    if (!c->rs.refused.empty())
+        return fail(c, SDRX_EUNSUPPORTED, "resampler %d -> %d S/s: %s", c->rs.plan.fs_in, c->rs.plan.fs_out, c->rs.refused.c_str());
+    for (const Node &n : c->nodes)
+        if (n.d.parent_id < 0 && n.d.fs != c->rs.plan.fs_out)
+            return fail(c, SDRX_EUNSUPPORTED, "resampler: the parent-less VFOs must share one fs (%d and %d; sdrx_set_resampler took the first)",
+                        c->rs.plan.fs_out, n.d.fs);
+    if (const char *why = resample_frames(c->rs.plan, c->root_frame))
+        return fail(c, SDRX_EUNSUPPORTED, "resampler %d -> %d S/s (L = %d, M = %d) with frames of %d: %s", c->rs.plan.fs_in, c->rs.plan.fs_out,
+                    c->rs.plan.L, c->rs.plan.M, c->root_frame, why);
+    c->in_frame = c->rs.plan.n_in;
+    return SDRX_OK;
+}
+
+// ... and what k_resample needs on the device: the staging frame, the zeroed history, the taps phase-major g[ph][t] = h[ph + t L].
+// All of it or (the caller releases) none.
+int resample_setup(sdrx_ctx *c)
+{
+    if (!c->rs.on)
+        return SDRX_OK;
+    const ResamplePlan &P = c->rs.plan;
+    const size_t stage = align_up((size_t)P.n_in, kChunk) + kChunk;
+    if (c->rs.d_stage.alloc(stage) != hipSuccess || c->rs.d_hist.alloc(2 * (size_t)kRsHist) != hipSuccess ||
+        c->rs.d_taps.alloc((size_t)P.L * P.T) != hipSuccess)
+        return fail(c, SDRX_ENOMEM, "sdrx_finalize: no device memory for the resampler");
+    HIPCHK(c, hipMemsetAsync(c->rs.d_stage, 0, stage * sizeof(float2), c->st.stream));
+    HIPCHK(c, hipMemsetAsync(c->rs.d_hist, 0, 2 * (size_t)kRsHist * sizeof(float2), c->st.stream));
+    std::vector<float> g((size_t)P.L * P.T);
+    for (int ph = 0; ph < P.L; ++ph)
+        for (int t = 0; t < P.T; ++t)
+            g[(size_t)ph * P.T + t] = c->rs.taps[(size_t)ph + (size_t)t * P.L];
+    HIPCHK(c, hipMemcpy(c->rs.d_taps, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->rs.lds_bytes = resample_lds_bytes(resample_max_window(P));
     return SDRX_OK;
 }
 
 int finalize_impl(sdrx_ctx *c)
 {
     if (int rc = derive_nodes(c))
+        return rc;
+    if (int rc = resample_plan_frames(c))
         return rc;
     Built B;
     plan_buffers(c, B);
@@ -1049,6 +1093,8 @@ int finalize_impl(sdrx_ctx *c)
     if (int rc = agc_setup(c))
         return rc;
     if (int rc = adc_setup(c))
+        return rc;
+    if (int rc = resample_setup(c))
         return rc;
     catchup_setup(c, B);
     c->sq.preroll_fused = false;

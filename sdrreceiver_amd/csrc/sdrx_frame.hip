@@ -97,6 +97,30 @@ ParkArg<PARK> park_arg(const sdrx_ctx *c, size_t first)
     return P;
 }
 
+// Where the ingest kernels leave a frame in tile layout: the tree's raw frame, or with a resampler the input-rate staging
+// buffer in front of it.
+float4 *ingest_dest(sdrx_ctx *c) { return reinterpret_cast<float4 *>(c->rs.on ? c->rs.d_stage.get() : c->d_raw_tiled.get()); }
+
+// Resampler: the staged input-rate frame of the next frame (c->frame_no) -> the tree's raw frame, on the context's stream
+// behind the ingest kernel that staged it, inside that kernel's KIND_INGEST bracket.  The history slot of the previous frame's
+// parity is read, this frame's written (resample.hip).  Off: nothing.
+void resample_launch(sdrx_ctx *c)
+{
+    if (!c->rs.on)
+        return;
+    const ResamplePlan &P = c->rs.plan;
+    const int p = (int)(c->frame_no & 1ull);
+    ResampleArgs A;
+    A.stage = c->rs.d_stage;
+    A.hist_prev = c->rs.d_hist + (size_t)(p ^ 1) * kRsHist;
+    A.hist_next = c->rs.d_hist + (size_t)p * kRsHist;
+    A.taps = reinterpret_cast<const float4 *>(c->rs.d_taps.get());
+    A.out = reinterpret_cast<float4 *>(c->d_raw_tiled.get());
+    A.n_in = P.n_in, A.n_out = P.n_out;
+    A.L = P.L, A.M = P.M, A.T = P.T;
+    hipLaunchKernelGGL(k_resample, dim3((P.n_out + kRsChunk - 1) / kRsChunk), dim3(256), c->rs.lds_bytes, c->st.stream, A);
+}
+
 int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st); // (sdrx_delivery.hip)
 int queue_payloads(sdrx_ctx *c, int p, hipStream_t st);
 
@@ -525,6 +549,21 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         // the levels write d_pay[p], which the previous gate reads -- and read the gains its step writes; option wake: the wake
         // steps of this frame write the flag words and state regions the previous tail, gate and step read
         HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.ev_tail[p ^ 1], 0));
+    if (c->rs.on && raw_mode != kRawTiled) {
+        // Resampler: a natural-order frame (cf32, or a shared context's bytes) is at the input rate -- one layout pass into the
+        // staging buffer, then k_resample, in front of everything that reads the tree's raw frame.  (A frame of integer samples
+        // came through enqueue_samples_device, which did both: kRawTiled.)
+        Bracket b(c, c->st.stream, KIND_INGEST, 0);
+        const int n_pairs = c->in_frame / 2;
+        if (raw_mode == kRawF32)
+            hipLaunchKernelGGL(k_ingest_f32, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const float4 *>(raw), ingest_dest(c),
+                               n_pairs);
+        else
+            hipLaunchKernelGGL(k_ingest_samples<SDRX_FMT_CU8>, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream,
+                               reinterpret_cast<const unsigned *>(raw), ingest_dest(c), n_pairs);
+        resample_launch(c);
+        raw_mode = kRawTiled;
+    }
     spectrum_raw_step(c, raw, raw_mode);
     watch_raw_step(c, raw, raw_mode);
     // A few parent-less VFOs (the reference's 2-3 mains) read the caller's frame as it is; a wide
@@ -653,7 +692,10 @@ int check_frame_call(sdrx_ctx *c, const char *what, const void *ptr, int n_compl
         return fail(c, SDRX_EINVAL, "%s: null frame pointer", what);
     if (!c->finalized)
         return fail(c, SDRX_ESTATE, "%s before sdrx_finalize", what);
-    if (n_complex != c->root_frame)
+    if (n_complex != c->in_frame && c->rs.on)
+        return fail(c, SDRX_EINVAL, "frame of %d samples: with the resampler %d -> %d S/s a frame has %d (for the VFOs' %d)", n_complex, c->rs.plan.fs_in,
+                    c->rs.plan.fs_out, c->in_frame, c->root_frame);
+    if (n_complex != c->root_frame && !c->rs.on)
         return fail(c, SDRX_EINVAL, "frame of %d samples, VFOs were initialised for %d (vfo::init samplesPerBuffer)", n_complex,
                     c->root_frame);
     if (sync_call && c->in_flight > 0)
@@ -670,9 +712,9 @@ int check_frame_call(sdrx_ctx *c, const char *what, const void *ptr, int n_compl
 int stage_host_frame(sdrx_ctx *c, const void *src, size_t bytes, void *dst_dev)
 {
     const int p = (int)(c->frame_no & 1ull);
-    hipError_t e = c->h_in[0].reserve((size_t)c->root_frame * sizeof(float2)); // both pinned buffers, or none
+    hipError_t e = c->h_in[0].reserve((size_t)c->in_frame * sizeof(float2)); // both pinned buffers, or none
     if (e == hipSuccess)
-        e = c->h_in[1].reserve((size_t)c->root_frame * sizeof(float2));
+        e = c->h_in[1].reserve((size_t)c->in_frame * sizeof(float2));
     if (e != hipSuccess) {
         c->h_in[0].reset();
         c->h_in[1].reset();
@@ -694,7 +736,7 @@ int stage_host_frame(sdrx_ctx *c, const void *src, size_t bytes, void *dst_dev)
 
 int enqueue_f32(sdrx_ctx *c, const float *iq, int n_complex, bool egress)
 {
-    int rc = ensure_raw(c, (size_t)c->root_frame);
+    int rc = ensure_raw(c, (size_t)c->in_frame);
     if (rc)
         return rc;
     float2 *dst = c->d_raw[c->frame_no & 1ull];
@@ -703,7 +745,7 @@ int enqueue_f32(sdrx_ctx *c, const float *iq, int n_complex, bool egress)
         return rc;
     rc = enqueue_frame(c, dst, kRawF32, egress);
     if (rc == SDRX_OK)
-        c->last_raw = kRawF32;
+        c->last_raw = c->rs.on ? kRawTiled : kRawF32; // (resampler: the tree's frame is k_resample's, in the tile layout)
     return rc;
 }
 
@@ -741,7 +783,7 @@ void adc_meter_launch(sdrx_ctx *c, const void *dev_samples, int n_complex, int f
         k_adc_meter<SDRX_FMT_CU8>, k_adc_meter<SDRX_FMT_CS8>, k_adc_meter<SDRX_FMT_CS16>};
     const int p = (int)(c->frame_no & 1ull);
     const int nb = (n_complex + kAdcWg - 1) / kAdcWg; // workgroups = partials
-    if ((size_t)nb > c->adc.d_part.count()) // (never: every frame has root_frame samples, what adc_setup sized for)
+    if ((size_t)nb > c->adc.d_part.count()) // (never: every frame has in_frame samples, what adc_setup sized for)
         return;
     const int per = (nb + kAdcThreads - 1) / kAdcThreads, cnt = (nb + per - 1) / per; // the last workgroup's merge: partials per thread, threads
     hipLaunchKernelGGL(K[fmt], dim3(nb), dim3(kAdcThreads), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_samples), n_complex,
@@ -820,7 +862,8 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
             hipLaunchKernelGGL(k_dc_chain, dim3(2), dim3(64), 0, c->st.stream, Pp, Ap, n_complex, c->dc.work_stride, c->dc.d_state);
         }
         hipLaunchKernelGGL(K.apply, dim3((words + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), Ap,
-                           reinterpret_cast<float4 *>(c->d_raw_tiled.get()), n_complex, c->dc.work_stride);
+                           ingest_dest(c), n_complex, c->dc.work_stride);
+        resample_launch(c);
         mode = kRawTiled;
     } else if (correct_dc) {
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
@@ -829,14 +872,15 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         hipLaunchKernelGGL(K.block_sums, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), n_complex,
                            c->dc.d_tab, sums);
         hipLaunchKernelGGL(K.dc_fast, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
-                           reinterpret_cast<float4 *>(c->d_raw_tiled.get()), n_complex, c->dc.d_state + 2 * par, c->dc.d_state + 2 * (par ^ 1),
-                           c->dc.d_tab, sums);
+                           ingest_dest(c), n_complex, c->dc.d_state + 2 * par, c->dc.d_state + 2 * (par ^ 1), c->dc.d_tab, sums);
+        resample_launch(c);
         mode = kRawTiled;
-    } else if (fmt != SDRX_FMT_CU8) {
+    } else if (fmt != SDRX_FMT_CU8 || c->rs.on) { // (resampler: k_resample reads the tile layout, so bytes take the pass too)
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
         const int n_pairs = n_complex / 2;
         hipLaunchKernelGGL(K.ingest, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
-                           reinterpret_cast<float4 *>(c->d_raw_tiled.get()), n_pairs);
+                           ingest_dest(c), n_pairs);
+        resample_launch(c);
         mode = kRawTiled;
     }
     c->long_frame = correct_dc && !c->opt_dc_blocked;
@@ -852,7 +896,7 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
 // the cf32 buffer of that parity, which is twice as large as they need and has no other use in such a frame.
 int enqueue_samples(sdrx_ctx *c, const void *samples, int n_complex, int fmt, int correct_dc, bool egress)
 {
-    int rc = ensure_raw(c, (size_t)c->root_frame);
+    int rc = ensure_raw(c, (size_t)c->in_frame);
     if (rc)
         return rc;
     const int p = (int)(c->frame_no & 1ull);
@@ -881,7 +925,7 @@ int sdrx_process_device(sdrx_ctx *c, const void *dev_iq, int n_complex)
     int rc = check_frame_call(c, "sdrx_process_device", dev_iq, n_complex, true);
     if (rc)
         return rc;
-    c->last_raw = -1;
+    c->last_raw = c->rs.on ? kRawTiled : -1; // (resampler: the tree's frame is the context's own, k_resample wrote it)
     return enqueue_frame(c, dev_iq, kRawF32, false);
 }
 
@@ -890,7 +934,7 @@ int sdrx_submit_device(sdrx_ctx *c, const void *dev_iq, int n_complex)
     int rc = check_frame_call(c, "sdrx_submit_device", dev_iq, n_complex, false);
     if (rc)
         return rc;
-    c->last_raw = -1;
+    c->last_raw = c->rs.on ? kRawTiled : -1;
     return enqueue_frame(c, dev_iq, kRawF32, true);
 }
 
@@ -911,6 +955,8 @@ static int submit_shared(sdrx_ctx *c, sdrx_ctx *src, const char *what, bool sync
 {
     if (!c || !src || c == src)
         return c ? fail(c, SDRX_EINVAL, "%s: needs another context as the source", what) : SDRX_EINVAL;
+    if (c->rs.on || src->rs.on)
+        return fail(c, SDRX_ESTATE, "%s: a context with a resampler (sdrx_set_resampler) shares no frames", what);
     if (!src->finalized || src->frame_no == 0 || (src->last_raw != kRawF32 && src->last_raw != kRawU8))
         return fail(c, SDRX_ESTATE, "%s: the source context has staged no host frame (floats or bytes without DC removal) yet", what);
     if (src->device != c->device)

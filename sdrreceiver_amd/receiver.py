@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, agc as _agc, drift as _drift, ingest, meter, scan as _scan, squelch as _squelch, wake as _wake, watch as _watch
+from . import _lib, agc as _agc, drift as _drift, ingest, meter, resample as _resample, scan as _scan, squelch as _squelch, wake as _wake, watch as _watch
 from .topology import Topology, VfoDesc
 
 
@@ -311,7 +311,13 @@ class Receiver(_LeafCalls):
                  dc_blocks_per_step: int | None = None, fuse_demod: bool = False,
                  tail_in_levels: bool = True, meter: bool = False, squelch: bool = False, preroll: bool = False,
                  squelch_auto: bool = False, park: bool = False, watch: bool = False, catchup: bool = False,
-                 agc: bool = False, wake: bool = False, adc_meter: bool = False):
+                 agc: bool = False, wake: bool = False, adc_meter: bool = False, input_rate: int | None = None,
+                 resample_taps=32, resample_atten_db: float = 80.0):
+        # input_rate: the front end's sample rate where it is not the parent-less VFOs' fs -- frames then have
+        # resampler["in_frame"] samples and a rational resampler on the device makes the tree's frame (sdrreceiver_amd.resample).
+        # resample_taps: the taps per phase of the built-in design with resample_atten_db, or the caller's own L * T prototype.
+        self._input_rate, self._resample_taps, self._resample_atten = input_rate, resample_taps, float(resample_atten_db)
+        self._passband_hz = 0.0
         self.L = _lib.lib()
         h = C.c_void_p()
         rc = self.L.sdrx_create(C.byref(h), int(device))
@@ -391,8 +397,49 @@ class Receiver(_LeafCalls):
         return out.value
 
     def finalize(self):
+        if self._input_rate:
+            self._set_resampler()
         self._chk(self.L.sdrx_finalize(self.h))
         self.finalized = True
+
+    def _set_resampler(self) -> None:
+        fs_in, fs_out = int(self._input_rate), next(d.fs for d in self.descs if d.parent < 0)
+        if np.ndim(self._resample_taps) == 0:  # taps per phase: the library's own design
+            T = int(self._resample_taps)
+            info = _lib.ResamplerInfoC()
+            taps = np.zeros(max(1, _resample.MAX_TAPS), np.float32)
+            rc = self.L.sdrx_resampler_design(fs_in, fs_out, T, self._resample_atten, taps.ctypes.data, taps.size, C.byref(info))
+            if rc != 0:
+                raise SdrxError(rc, self.L.sdrx_last_error(None).decode())
+            self._passband_hz = info.passband_hz
+        else:
+            taps = np.ascontiguousarray(self._resample_taps, dtype=np.float32).reshape(-1)
+            L, _ = _resample.ratio(fs_in, fs_out)
+            if taps.size % L:
+                raise ValueError(f"resample_taps holds {taps.size} floats, no multiple of L = {L}")
+            T = taps.size // L
+        self._chk(self.L.sdrx_set_resampler(self.h, fs_in, taps.ctypes.data, T))
+
+    @property
+    def resampler(self) -> dict | None:
+        """The resampler's ``sdrx_resampler_info`` as a dict (``passband_hz`` of the built-in design; 0 for the caller's own
+        taps) with ``taps``, the prototype as the library holds it; None without ``input_rate``."""
+        if not self._input_rate:
+            return None
+        info = _lib.ResamplerInfoC()
+        taps = np.zeros(_resample.MAX_TAPS, np.float32)
+        self._chk(self.L.sdrx_get_resampler(self.h, C.byref(info), taps.ctypes.data, taps.size))
+        d = _resample.info_dict(info)
+        d["passband_hz"] = self._passband_hz
+        d["taps"] = taps[: d["L"] * d["taps_per_phase"]].copy()
+        return d
+
+    def resampler_input(self) -> np.ndarray:
+        """The last frame at the input rate as the resampler read it: after the format conversion and the DC-bias removal."""
+        n = self.resampler["in_frame"]
+        out = np.zeros(2 * max(n, 1), np.float32)
+        self._chk(self.L.sdrx_get_resampler_input(self.h, out.ctypes.data, n))
+        return out[: 2 * n].view(np.complex64).copy()
 
     @classmethod
     def from_topology(cls, topo: Topology, **kw) -> "Receiver":
