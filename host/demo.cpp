@@ -3,7 +3,8 @@
 // frames to sdrj::demodData, receive every leaf's payload through the publish hook.
 //
 //   sdrx_demo <profile.ini> --dump              descriptors as JSON lines (no GPU needed)
-//   sdrx_demo <profile.ini> --frames N [--u8] [--format cu8|cs8|cs16] [--adc] [--input-rate HZ] [--fft TOPIC] [--devices 0,1,...]
+//   sdrx_demo <profile.ini> --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ]
+//                                   [--front-stages N [--front-real] [--front-taps K]] [--fft TOPIC] [--devices 0,1,...]
 //                                               N synthetic LCG frames; one line per published
 //                                               message: frame topic rate bytes fnv1a64(payload)
 //                                               --u8 feeds them as dongle bytes, --format as integer samples of that
@@ -15,6 +16,11 @@
 //                                               --input-rate HZ: the frames are at HZ, not at the profile's sample rate, and
 //                                               the library's resampler makes the tree's frames from them; first line
 //                                               resampler fs_in fs_out L M taps_per_phase in_frame out_frame delay passband_hz
+//                                               --front-stages N: N half-band decimations by 2 on the device in front of that (or
+//                                               of the tree), the library's design with 4 K + 3 taps (--front-taps K, default 15);
+//                                               the frames have 2^N times the samples.  --front-real: they are REAL samples,
+//                                               --format rs16 (int16) or ru12 (12-bit offset codes in uint16).  Next line
+//                                               front real_input stages K N in_frame out_frame tw alias_free
 #include <cinttypes>
 #include <cstdio>
 #include <iostream>
@@ -37,7 +43,7 @@ static uint64_t fnv1a(const void *p, size_t n)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16] [--adc] [--input-rate HZ] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ] [--front-stages N [--front-real] [--front-taps K]] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
         return 2;
     }
     try {
@@ -66,7 +72,8 @@ int main(int argc, char **argv)
             throw std::runtime_error("bad arguments");
         const int frames = std::atoi(argv[3]);
         bool u8 = false, adc = false;
-        int fmt = SDRX_FMT_CU8, input_rate = 0;
+        int fmt = SDRX_FMT_CU8, input_rate = 0, front_stages = 0, front_K = 15;
+        bool front_real = false;
         std::string fft_topic;
         std::vector<int> devices;
         for (int a = 4; a < argc; ++a) {
@@ -74,14 +81,20 @@ int main(int argc, char **argv)
                 u8 = true;
             else if (std::string(argv[a]) == "--format" && a + 1 < argc) {
                 const std::string f = argv[++a];
-                if (f != "cu8" && f != "cs8" && f != "cs16")
-                    throw std::runtime_error("--format takes cu8, cs8 or cs16");
-                fmt = f == "cu8" ? SDRX_FMT_CU8 : f == "cs8" ? SDRX_FMT_CS8 : SDRX_FMT_CS16;
+                if (f != "cu8" && f != "cs8" && f != "cs16" && f != "rs16" && f != "ru12")
+                    throw std::runtime_error("--format takes cu8, cs8 or cs16, or with --front-real rs16 or ru12");
+                fmt = f == "cu8" ? SDRX_FMT_CU8 : f == "cs8" ? SDRX_FMT_CS8 : f == "cs16" ? SDRX_FMT_CS16 : f == "rs16" ? SDRX_FMT_RS16 : SDRX_FMT_RU12;
                 u8 = true;
             } else if (std::string(argv[a]) == "--adc")
                 adc = true;
             else if (std::string(argv[a]) == "--input-rate" && a + 1 < argc)
                 input_rate = std::atoi(argv[++a]);
+            else if (std::string(argv[a]) == "--front-stages" && a + 1 < argc)
+                front_stages = std::atoi(argv[++a]);
+            else if (std::string(argv[a]) == "--front-taps" && a + 1 < argc)
+                front_K = std::atoi(argv[++a]);
+            else if (std::string(argv[a]) == "--front-real")
+                front_real = true;
             else if (std::string(argv[a]) == "--fft" && a + 1 < argc)
                 fft_topic = argv[++a];
             else if (std::string(argv[a]) == "--devices" && a + 1 < argc) { // one tree sharded over several GPUs
@@ -119,14 +132,28 @@ int main(int argc, char **argv)
             radio.fftData = tap("Main");
             radio.fftVFOSlot(fft_topic);
         }
+        const bool real_fmt = fmt == SDRX_FMT_RS16 || fmt == SDRX_FMT_RU12;
+        if (real_fmt != front_real)
+            throw std::runtime_error("--format rs16 / ru12 and --front-real (with --front-stages) go together");
+        if (real_fmt)
+            radio.setDCCorrection(false); // (the library removes no DC from real samples: it lands at the band's edge)
         int n_frame = P->frame; // samples of a frame as it is handed over
-        if (input_rate > 0) {
+        if (input_rate > 0)
             radio.setInputRate(input_rate);
+        if (front_stages > 0)
+            radio.setFront(front_stages, front_real, front_K);
+        if (input_rate > 0 || front_stages > 0)
             radio.start();
+        if (input_rate > 0) {
             const sdrx_resampler_info R = radio.resampler();
             n_frame = R.in_frame;
             std::printf("resampler %d %d %d %d %d %d %d %.6f %.3f\n", R.fs_in, R.fs_out, R.L, R.M, R.taps_per_phase, R.in_frame, R.out_frame,
                         R.delay_out_samples, R.passband_hz);
+        }
+        if (front_stages > 0) {
+            const sdrx_front_info F = radio.front();
+            n_frame = F.in_frame;
+            std::printf("front %d %d %d %d %d %d %.9f %.9f\n", F.real_input, F.stages, F.K, F.N, F.in_frame, F.out_frame, F.tw, F.alias_free);
         }
         // synthetic IQ of BASELINE.md: LCG x <- x*1664525 + 1013904223, component ((x >> 24) % 17) - 8
         uint32_t x = 1;
@@ -134,6 +161,7 @@ int main(int argc, char **argv)
         std::vector<uint8_t> bytes((size_t)2 * n_frame);
         std::vector<int8_t> s8(fmt == SDRX_FMT_CS8 ? bytes.size() : 0);
         std::vector<int16_t> s16(fmt == SDRX_FMT_CS16 ? bytes.size() : 0);
+        std::vector<uint16_t> r16(real_fmt ? (size_t)n_frame : 0); // real samples: one component a sample
         for (frame_no = 0; frame_no < frames; ++frame_no) {
             for (size_t i = 0; i < iq.size(); ++i) {
                 x = x * 1664525u + 1013904223u;
@@ -144,8 +172,12 @@ int main(int argc, char **argv)
                     s8[i] = (int8_t)c;
                 else if (fmt == SDRX_FMT_CS16)
                     s16[i] = (int16_t)(256 * c); // c * 2^8: the same sample value
+                else if (real_fmt && i < r16.size())
+                    r16[i] = fmt == SDRX_FMT_RS16 ? (uint16_t)(int16_t)(256 * c) : (uint16_t)(16 * c + 2048); // the same value in both
             }
-            if (fmt == SDRX_FMT_CS8)
+            if (real_fmt)
+                radio.demodSamples(r16.data(), n_frame, fmt);
+            else if (fmt == SDRX_FMT_CS8)
                 radio.demodSamples(s8.data(), n_frame, fmt);
             else if (fmt == SDRX_FMT_CS16)
                 radio.demodSamples(s16.data(), n_frame, fmt);
@@ -161,7 +193,7 @@ int main(int argc, char **argv)
                 }
                 const adc_levels_t L = adc_levels(r);
                 std::printf("adc %d %s %u %" PRId64 " %" PRId64 " %" PRIu64 " %" PRIu64 " %" PRId64 " %d %d %d %d %u %u %d | %.6g %.3f %.6g %.6g %.6g\n", frame_no,
-                            r.fmt == SDRX_FMT_CU8 ? "cu8" : r.fmt == SDRX_FMT_CS8 ? "cs8" : "cs16", r.n_complex, r.i.sum, r.q.sum, r.i.sum_sq, r.q.sum_sq,
+                            r.fmt == SDRX_FMT_CU8 ? "cu8" : r.fmt == SDRX_FMT_CS8 ? "cs8" : r.fmt == SDRX_FMT_CS16 ? "cs16" : r.fmt == SDRX_FMT_RS16 ? "rs16" : "ru12", r.n_complex, r.i.sum, r.q.sum, r.i.sum_sq, r.q.sum_sq,
                             r.sum_iq, r.i.min, r.i.max, r.q.min, r.q.max, r.i.at_lo + r.i.at_hi + r.q.at_lo + r.q.at_hi, L.longest_rail_run,
                             L.bits_used, L.peak, L.headroom_db, L.dc_i, L.dc_q, L.rms);
             }

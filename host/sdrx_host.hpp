@@ -100,7 +100,9 @@ inline adc_levels_t adc_levels(const sdrx_adc_meter &r)
     if (!r.measured)
         throw std::invalid_argument("adc_levels: the frame was not measured (it did not arrive as integer samples)");
     typedef __int128 wide;
-    const double s = r.fmt == SDRX_FMT_CS16 ? 0.00390625 : 1.0, n = (double)r.n_complex, nn = n * n;
+    // (a record of real samples, SDRX_FMT_RS16 / RU12, holds the even samples in arm i and the odd ones in arm q: the levels are per
+    // arm as for I/Q; sdrreceiver_amd.ingest.adc_levels merges them)
+    const double s = r.fmt == SDRX_FMT_CS16 || r.fmt == SDRX_FMT_RS16 ? 0.00390625 : r.fmt == SDRX_FMT_RU12 ? 0.0625 : 1.0, n = (double)r.n_complex, nn = n * n;
     const wide N = (wide)r.n_complex;
     const double var_i = (double)(N * (wide)r.i.sum_sq - (wide)r.i.sum * (wide)r.i.sum) / nn * s * s;
     const double var_q = (double)(N * (wide)r.q.sum_sq - (wide)r.q.sum * (wide)r.q.sum) / nn * s * s;
@@ -168,6 +170,26 @@ public:
         info.passband_hz = rs_passband_;
         return info;
     }
+    // A half-band front stage on the device in front of the resampler or of the main VFOs (include/sdrx.h "Front stage"; no
+    // counterpart in the reference): before the first frame.  `stages` (1 .. 3) decimations by 2 with the library's own Kaiser
+    // half-band of N = 4 K + 3 taps and `atten_db` of stop band; every frame then has front().in_frame samples.  real_input: the
+    // front end delivers REAL samples of an IF (Airspy R2 / Mini) -- demodSamples with SDRX_FMT_RS16 or SDRX_FMT_RU12, the count
+    // in real samples -- and the first stage makes I/Q of them (tuned centre fs_r / 4).  stages = 0: off.  One device only.
+    void setFront(int stages, bool real_input = false, int K = 15, double atten_db = 80.0)
+    {
+        if (started())
+            throw std::runtime_error("sdrj::setFront after the first frame");
+        fr_stages_ = stages, fr_real_ = real_input, fr_K_ = K, fr_atten_ = atten_db;
+    }
+    // ... and what it is once the tree is committed (start()): stages, taps, frame lengths, transition width
+    sdrx_front_info front()
+    {
+        if (!ctx_ || !fr_stages_)
+            throw std::runtime_error("sdrj::front: no front stage set, or not started");
+        sdrx_front_info info;
+        check(sdrx_get_front(ctx_, &info, nullptr, 0), "sdrx_get_front");
+        return info;
+    }
     // sdrj.cpp:84-101: the raw spectrum is selected by the topic "Main"; any selection restarts
     // the every-4th-call counter of demodData (sdrj.cpp:296-303)
     void fftVFOSlot(const std::string &topic)
@@ -184,6 +206,8 @@ public:
             throw std::runtime_error("sdrj: no main VFOs");
         if (devices_.size() > 1 && input_rate_)
             throw std::runtime_error("sdrj: the resampler (setInputRate) is not offered on several devices");
+        if (devices_.size() > 1 && fr_stages_)
+            throw std::runtime_error("sdrj: the front stage (setFront) is not offered on several devices");
         if (devices_.size() > 1) {
             check(sdrx_group_create(&grp_, devices_.data(), (int)devices_.size()), "sdrx_group_create");
             for (auto &kv : options_)
@@ -207,6 +231,8 @@ public:
             rs_passband_ = info.passband_hz;
             check(sdrx_set_resampler(ctx_, input_rate_, taps.data(), rs_taps_), "sdrx_set_resampler");
         }
+        if (fr_stages_)
+            check(sdrx_set_front(ctx_, fr_real_ ? 1 : 0, fr_stages_, nullptr, fr_K_, fr_atten_), "sdrx_set_front");
         check(sdrx_set_publish_callback(ctx_, &sdrj::trampoline, this), "sdrx_set_publish_callback");
         check(sdrx_finalize(ctx_), "sdrx_finalize");
     }
@@ -249,7 +275,8 @@ public:
         }
         after_frame(n_complex);
     }
-    // Integer samples of a front end in format `fmt` (SDRX_FMT_CU8 / CS8 / CS16, include/sdrx.h): conversion to the reference's
+    // Integer samples of a front end in format `fmt` (SDRX_FMT_CU8 / CS8 / CS16, include/sdrx.h; with setFront(.., true) the real
+    // formats SDRX_FMT_RS16 / RU12, n_complex then counting real samples): conversion to the reference's
     // units and DC correction on the device.  SDRX_FMT_CU8 is demodBytes.  On several devices the integers themselves are
     // fanned out; the raw spectrum tap of a group is then served by the first member that holds VFOs, which keeps the
     // converted frame with or without DC removal.
@@ -587,6 +614,9 @@ private:
     std::map<std::string, int> options_;
     int input_rate_ = 0, rs_taps_ = 32; // setInputRate
     double rs_atten_ = 80.0, rs_passband_ = 0;
+    int fr_stages_ = 0, fr_K_ = 15; // setFront
+    bool fr_real_ = false;
+    double fr_atten_ = 80.0;
 };
 
 // ------------------------------------------------------------------------------------------ INI

@@ -876,6 +876,71 @@ int sdrx_set_resampler(sdrx_ctx *ctx, int32_t fs_in, const float *taps, int32_t 
 int sdrx_get_resampler(sdrx_ctx *ctx, sdrx_resampler_info *info, float *taps, int32_t cap);
 int sdrx_get_resampler_input(sdrx_ctx *ctx, float *out_iq, int32_t cap_complex);
 
+/* ---- Front stage (sdrx_set_front before sdrx_finalize) -----------------------------------------------------------
+ * 1 .. 3 half-band decimations by 2 between the ingest kernels and the resampler -- or level 0 where no resampler is set.  Two
+ * kinds of front end need it: one that delivers REAL samples of an IF (Airspy R2 / Mini: 20, 12, 10, 6 MS/s real), which the
+ * first stage turns into I/Q on the device (fs/4 translation, half-band, decimation by 2) from 2 bytes a sample, and one whose
+ * rate is more than 4 times the tree's, which a stage in front brings into the resampler's 1/2 <= M/L <= 4.  The reference has
+ * no counterpart: this text is the definition.  Off (the default) nothing changes at all: the same kernels, launches,
+ * device_bytes, payloads and callbacks.
+ *
+ * sdrx_set_front(ctx, real_input, stages, taps, K, atten_db): before sdrx_finalize (SDRX_ESTATE after it) and after the first
+ * parent-less VFO was added (SDRX_ESTATE before), before or after sdrx_set_resampler.  stages in 1 .. 3, real_input 0 or 1,
+ * 2 <= K <= 31, else SDRX_EINVAL.  One prototype h[0 .. N-1], N = 4 K + 3, centre C = 2 K + 1, serves every stage; h[k] must
+ * be +0.0f (that bit pattern) for every odd k != C, else SDRX_EINVAL; symmetry is not required.  taps == NULL: the built-in
+ * design below at `atten_db`, which is not read otherwise.  stages == 0 switches the stage off again.
+ *
+ * Frame lengths.  n0 is the frame the stage feeds: the resampler's in_frame if one is set, else the parent-less VFOs' frame.
+ * Stage s (s = stages .. 1; stage 1 reads the caller's samples) has n0 2^(stages - s) outputs and twice as many inputs.  Every
+ * frame call of the context -- *_fmt, cf32, host and device frames -- takes in_frame = n0 2^stages samples; for the real formats
+ * the count argument counts REAL samples.  Any other count is SDRX_EINVAL.  SDRX_EUNSUPPORTED at sdrx_finalize, with the reason
+ * in sdrx_last_error, if the parent-less VFOs do not share one fs and one frame.  With a resampler, fs_in of
+ * sdrx_set_resampler stays the rate at the RESAMPLER's input: the front end's rate over 2^stages.
+ *
+ * A stage with input z and output y.
+ *   Complex stage: z[n] is the stage's cf32 input; in stage 1 the format conversion, after the DC-bias removal if asked for.
+ *   Real stage (stage 1 with real_input = 1 only): r[n] is the converted real sample, n counted from the start of the frame,
+ *     and z[n] = r[n] (-j)^n: Re z = +r, 0, -r, 0 and Im z = 0, -r, 0, +r for n mod 4 = 0, 1, 2, 3 (-r is the negation: -0.0f
+ *     for r = +0.0f).  in_frame is a multiple of 4, so the pattern runs on across frames.  The band [0, fs_r / 2] comes out as
+ *     [-fs_r / 4, +fs_r / 4]: the tuned centre is fs_r / 4.
+ *   History: z[n] := z_prev_frame[n_in_stage + n] for n < 0, zero before the first frame.  Every stage keeps its own.
+ *   Output y[m], separately for re and im: acc = +0.0f; acc = fl(acc + fl(h[k] z[2m - k])) over the structurally non-zero k in
+ *     ascending order, k = 0, 2, .. 2K, 2K+1, 2K+2, .. 4K+2 -- two roundings per tap, no FMA, the same in all three settings of
+ *     option "exact".  Real stage: the products whose z component is structurally zero are not formed -- I sums the even k only
+ *     (2K + 2 products), Q is the single product fl(h[C] Im z[2m - C]).
+ *
+ * Real formats, valid only on a context whose front stage has real_input = 1; on such a context the complex formats and cf32
+ * frames are SDRX_EINVAL, and correct_dc != 0 is SDRX_EINVAL (DC lands at the edge of the output band, where the stages behind
+ * discard it):
+ *   SDRX_FMT_RS16 = 3   native-endian int16, real                    x = (float)v * 2^-8                      [-128, 128)
+ *   SDRX_FMT_RU12 = 4   uint16 holding a 12-bit offset code, real    x = (float)((v & 4095) - 2048) * 2^-4    [-128, 128)
+ * One fixed scale, as for the complex formats.  The half-band has unit DC gain, so a real sine of amplitude a arrives as a
+ * complex tone of magnitude a / 2; a caller who wants a passes the doubled taps, which is exact in fp32.
+ * The ADC meter records a real frame as the same memory read as pairs -- even samples in arm I, odd samples in arm Q,
+ * n_complex = in_frame / 2 -- with fmt the real format; the integer code is the int16 itself (RS16) or (v & 4095) - 2048 (RU12,
+ * rails -2048 and 2047).
+ *
+ * The built-in design (sdrx_front_design; host only, IEEE double rounded once to fp32).  With A = atten_db, 50 < A <= 120
+ * (SDRX_EINVAL otherwise):
+ *   beta = 0.1102 (A - 8.7);   tw = (A - 7.95) / (2.285 (N - 1) 2 pi), a fraction of the stage's input rate
+ *   h[k] = 0.5 sinc(0.5 (k - C)) I0(beta sqrt(1 - (2k/(N-1) - 1)^2)) / I0(beta),   sinc(x) = sin(pi x) / (pi x)
+ * with the odd k != C set to +0.0 exactly.  SDRX_EFILTER if 0.25 - tw / 2 <= 0 (K = 2 at A = 80).  `taps`: N floats (NULL: only
+ * `info`; SDRX_EINVAL if cap < N).  `info` carries N, tw and the alias-free share of the output band, 1 - 2 tw.
+ *
+ * sdrx_get_front: the info (in_frame and out_frame once finalized; tw and alias_free 0 for the caller's own taps) and up to `cap`
+ * taps (`taps` may be NULL); SDRX_ESTATE without a front stage.  With no resampler the last stage's output is the raw frame
+ * (sdrx_get_raw, raw spectrum, raw watch); with one it is what sdrx_get_resampler_input serves.  sdrx_*_shared and sdrx_*_if_same
+ * return SDRX_ESTATE if either context has a front stage.  Groups do not offer it. */
+#define SDRX_FMT_RS16 3
+#define SDRX_FMT_RU12 4
+typedef struct sdrx_front_info { /* 48 bytes */
+    int32_t real_input, stages, K, N, in_frame, out_frame, reserved[2];
+    double tw, alias_free;
+} sdrx_front_info;
+int sdrx_front_design(int32_t K, double atten_db, float *taps, int32_t cap, sdrx_front_info *info);
+int sdrx_set_front(sdrx_ctx *ctx, int32_t real_input, int32_t stages, const float *taps, int32_t K, double atten_db);
+int sdrx_get_front(sdrx_ctx *ctx, sdrx_front_info *info, float *taps, int32_t cap);
+
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);

@@ -151,6 +151,12 @@ class ResamplerInfoC(C.Structure):
                 ("passband_hz", C.c_double)]
 
 
+class FrontInfoC(C.Structure):
+    """struct sdrx_front_info"""
+    _fields_ = [("real_input", C.c_int32), ("stages", C.c_int32), ("K", C.c_int32), ("N", C.c_int32), ("in_frame", C.c_int32),
+                ("out_frame", C.c_int32), ("reserved", C.c_int32 * 2), ("tw", C.c_double), ("alias_free", C.c_double)]
+
+
 PUBLISH_FN =C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
 
 # every symbol include/sdrx.h declares: (restype, argtypes)
@@ -246,6 +252,9 @@ SYMBOLS = {
     "sdrx_set_resampler": (_i, [_vp, C.c_int32, _vp, C.c_int32]),
     "sdrx_get_resampler": (_i, [_vp, C.POINTER(ResamplerInfoC), _vp, C.c_int32]),
     "sdrx_get_resampler_input": (_i, [_vp, _vp, C.c_int32]),
+    "sdrx_front_design": (_i, [C.c_int32, C.c_double, _vp, C.c_int32, C.POINTER(FrontInfoC)]),
+    "sdrx_set_front": (_i, [_vp, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_double]),
+    "sdrx_get_front": (_i, [_vp, C.POINTER(FrontInfoC), _vp, C.c_int32]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

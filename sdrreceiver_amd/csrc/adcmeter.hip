@@ -74,12 +74,21 @@ __device__ __forceinline__ void adc_merge(AdcElem &a, const AdcElem &b)
     a.len += b.len;
 }
 
-// The integer code of component `comp` (0 = I, 1 = Q) of sample s of a 16-byte unit: CU8 b - 127, CS8 / CS16 the integer itself.
+// The formats of 16-bit components: CS16, and the real formats RS16 and RU12, whose frame is read as pairs (even samples in arm
+// I, odd samples in arm Q: include/sdrx.h "Front stage").
+template <int FMT>
+constexpr bool kAdcWide = FMT == SDRX_FMT_CS16 || FMT == SDRX_FMT_RS16 || FMT == SDRX_FMT_RU12;
+
+// The integer code of component `comp` (0 = I, 1 = Q) of sample s of a 16-byte unit: CU8 b - 127, CS8 / CS16 / RS16 the integer
+// itself, RU12 the 12-bit offset code (v & 4095) - 2048.
 template <int FMT>
 __device__ __forceinline__ int adc_code(const v4u q, int s, int comp)
 {
-    static_assert(FMT == SDRX_FMT_CU8 || FMT == SDRX_FMT_CS8 || FMT == SDRX_FMT_CS16, "a format of include/sdrx.h");
-    if constexpr (FMT == SDRX_FMT_CS16) {
+    static_assert(FMT == SDRX_FMT_CU8 || FMT == SDRX_FMT_CS8 || kAdcWide<FMT>, "a format of include/sdrx.h");
+    if constexpr (FMT == SDRX_FMT_RU12) {
+        const unsigned w = q[s];
+        return (int)((comp ? w >> 16 : w) & 4095u) - 2048;
+    } else if constexpr (kAdcWide<FMT>) {
         const unsigned w = q[s];
         return comp ? (int)w >> 16 : (int)(short)(w & 0xffffu);
     } else {
@@ -93,8 +102,8 @@ __device__ __forceinline__ int adc_code(const v4u q, int s, int comp)
 }
 template <int FMT>
 struct AdcRails {
-    static constexpr int lo = FMT == SDRX_FMT_CU8 ? -127 : FMT == SDRX_FMT_CS8 ? -128 : -32768;
-    static constexpr int hi = FMT == SDRX_FMT_CU8 ? 128 : FMT == SDRX_FMT_CS8 ? 127 : 32767;
+    static constexpr int lo = FMT == SDRX_FMT_CU8 ? -127 : FMT == SDRX_FMT_CS8 ? -128 : FMT == SDRX_FMT_RU12 ? -2048 : -32768;
+    static constexpr int hi = FMT == SDRX_FMT_CU8 ? 128 : FMT == SDRX_FMT_CS8 ? 127 : FMT == SDRX_FMT_RU12 ? 2047 : 32767;
 };
 
 // A 64-bit value of at most 35 significant bits (signed: arithmetic shift) as two parts whose sums over a wave fit 32 bits:
@@ -112,7 +121,7 @@ __global__ __launch_bounds__(kAdcThreads) void k_adc_meter(const unsigned *__res
                                                            AdcPartial *__restrict__ part, unsigned *__restrict__ counter,
                                                            AdcRecord *__restrict__ rec, int per, int cnt)
 {
-    constexpr int kLoads = FMT == SDRX_FMT_CS16 ? 4 : 2, kPer = kAdcThread / kLoads; // 16-byte loads per thread, samples in each
+    constexpr int kLoads = kAdcWide<FMT> ? 4 : 2, kPer = kAdcThread / kLoads; // 16-byte loads per thread, samples in each
     constexpr int LO = AdcRails<FMT>::lo, HI = AdcRails<FMT>::hi;
     __shared__ AdcElem sh_e[kAdcThreads]; // [0..3]: the waves' partials; the last workgroup: one element per thread
     __shared__ unsigned sh_bits[kAdcThreads / 64][kAdcBins];
@@ -155,7 +164,7 @@ __global__ __launch_bounds__(kAdcThreads) void k_adc_meter(const unsigned *__res
                     all[c] &= rail;
                     pre[c] += all[c];
                     const unsigned k = 32u - (unsigned)__clz((int)a); // bit_length(|v|): 0 for 0, 16 for 32768
-                    if constexpr (FMT == SDRX_FMT_CS16) {
+                    if constexpr (kAdcWide<FMT>) {
                         hb0 += (unsigned long long)(k < 10u) << ((6u * k) & 63u);
                         hb1 += (unsigned long long)(k >= 10u) << ((6u * k - 60u) & 63u);
                     } else {
@@ -216,11 +225,11 @@ __global__ __launch_bounds__(kAdcThreads) void k_adc_meter(const unsigned *__res
     for (int j = 0; j < (kAdcBins + 1) / 2; ++j) {
         const int k0 = 2 * j, k1 = 2 * j + 1;
         auto field = [&](int k) -> unsigned {
-            if (k >= kAdcBins || (FMT != SDRX_FMT_CS16 && k > 8))
+            if (k >= kAdcBins || (!kAdcWide<FMT> && k > 8))
                 return 0u;
             return k < 10 ? (unsigned)(hb0 >> (6 * k)) & 63u : (unsigned)(hb1 >> (6 * (k - 10))) & 63u;
         };
-        if (FMT != SDRX_FMT_CS16 && k0 > 8) {
+        if (!kAdcWide<FMT> && k0 > 8) {
             wb[k0] = 0u;
             if (k1 < kAdcBins)
                 wb[k1] = 0u;

@@ -24,6 +24,8 @@
 //                                       rail counts, the longest rail run, a bit-length histogram; include/sdrx.h sdrx_adc_meter)
 //   k_resample            resample.hip  (none: sdrx_set_resampler -- the polyphase rational resampler L/M between the ingest kernels and level 0, for
 //                                       front ends whose rate no chain of half-bands reaches; include/sdrx.h "Resampler")
+//   k_front_halfband<MODE> front.hip    (none: sdrx_set_front -- 1 .. 3 half-band decimations by 2 in front of k_resample or level 0; stage 1 may read
+//                                       real int16 / 12-bit samples with the fs/4 translation built in; include/sdrx.h "Front stage")
 //   k_mix_decimate        mix.hip       vfo::process mix loop, vfo.cpp:237-245; HalfBandDecimator::decimate, halfbanddecimator.cpp:43-72,
 //                                       with FIR::...HalfBandQueue, dsp.cpp:96-173 (mix_item); option fuse_late: the FIR part of
 //                                       vfo::usb_decimdemod, vfo.cpp:334-356, inside a d = 0 leaf's wave (late_item); option fuse_demod:
@@ -44,6 +46,7 @@
 // frame chunk by chunk with the filter state resident in LDS.
 #include "sdrx_dev.h"
 #include "sdrx_resample.h"
+#include "sdrx_front.h"
 
 #include <type_traits>
 #include <utility>
@@ -55,6 +58,7 @@ namespace sdrx {
 #include "ingest.hip"
 #include "adcmeter.hip"
 #include "resample.hip"
+#include "front.hip"
 #include "meter.hip"
 #include "demod.hip"
 #include "mix.hip"

@@ -66,6 +66,7 @@ static_assert(sizeof(sdrx_wake_cfg) == 32 && sizeof(WakeCfg) == 32 && offsetof(s
                   offsetof(sdrx_wake_state, controlled) == offsetof(WakeRecord, controlled),
               "sdrx_wake_cfg / sdrx_wake_state ABI layout");
 static_assert(sizeof(sdrx_resampler_info) == 48 && offsetof(sdrx_resampler_info, delay_out_samples) == 32, "sdrx_resampler_info ABI layout");
+static_assert(sizeof(sdrx_front_info) == 48 && offsetof(sdrx_front_info, tw) == 32, "sdrx_front_info ABI layout");
 static_assert(sizeof(sdrx_adc_arm) == 40 && sizeof(AdcArm) == 40 && offsetof(sdrx_adc_arm, longest_rail_run) == offsetof(AdcArm, longest_rail_run) &&
                   sizeof(sdrx_adc_meter) == 184 && sizeof(AdcRecord) == 184 && offsetof(sdrx_adc_meter, q) == offsetof(AdcRecord, q) &&
                   offsetof(sdrx_adc_meter, sum_iq) == offsetof(AdcRecord, sum_iq) && offsetof(sdrx_adc_meter, bits) == offsetof(AdcRecord, bits),
@@ -117,6 +118,7 @@ void free_device_state(sdrx_ctx *c)
     c->wake = sdrx_ctx::Wake();
     c->adc = sdrx_ctx::Adc();
     static_cast<sdrx_ctx::ResamplerDevice &>(c->rs) = sdrx_ctx::ResamplerDevice();
+    static_cast<sdrx_ctx::FrontDevice &>(c->fr) = sdrx_ctx::FrontDevice();
 }
 
 } // namespace
@@ -981,11 +983,98 @@ int sdrx_get_resampler_input(sdrx_ctx *c, float *out, int32_t cap_complex)
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = drain(c))
         return rc;
-    const int n = std::min((int)cap_complex, c->in_frame);
-    const size_t total = align_up((size_t)c->in_frame, kChunk);
+    const int n_in = c->rs.plan.n_in; // (not c->in_frame: a front stage in front of the resampler takes a longer frame)
+    const int n = std::min((int)cap_complex, n_in);
+    const size_t total = align_up((size_t)n_in, kChunk);
     std::vector<float2> t(total);
     HIPCHK(c, hipMemcpy(t.data(), c->rs.d_stage, total * sizeof(float2), hipMemcpyDeviceToHost));
     untile(t.data(), out, std::max(n, 0));
+    return SDRX_OK;
+}
+
+// ---- Front stage (include/sdrx.h; sdrx_front.h has the frame lengths, the windows and the design) ------------------------------
+static void front_info(const FrontPlan &P, double tw, sdrx_front_info *info)
+{
+    memset(info, 0, sizeof *info);
+    info->real_input = P.real, info->stages = P.stages, info->K = P.K, info->N = front_taps(P.K);
+    info->in_frame = P.in_frame, info->out_frame = P.n0;
+    info->tw = tw;
+    info->alias_free = tw > 0 ? 1.0 - 2.0 * tw : 0.0;
+}
+
+static int front_design_checked(sdrx_ctx *c, const char *what, int K, double atten_db, float *taps, double *tw)
+{
+    const int rc = front_design(K, atten_db, taps, tw);
+    if (rc == 1)
+        return fail(c, SDRX_EINVAL, "%s: atten_db must be above 50 and at most 120", what);
+    if (rc == 2)
+        return fail(c, SDRX_EFILTER, "%s: with K = %d (N = %d taps) at %g dB the transition is wider than the band", what, K, front_taps(K), atten_db);
+    return SDRX_OK;
+}
+
+int sdrx_front_design(int32_t K, double atten_db, float *taps, int32_t cap, sdrx_front_info *info)
+{
+    if (K < kFrMinK || K > kFrMaxK)
+        return fail(nullptr, SDRX_EINVAL, "sdrx_front_design: K must be in 2 .. 31 (N = 4 K + 3 taps)");
+    if (taps && cap < front_taps(K))
+        return fail(nullptr, SDRX_EINVAL, "sdrx_front_design: room for %d taps, the prototype has N = %d", cap, front_taps(K));
+    double tw = 0;
+    if (int rc = front_design_checked(nullptr, "sdrx_front_design", K, atten_db, taps, &tw))
+        return rc;
+    if (info) {
+        FrontPlan P;
+        P.K = K;
+        front_info(P, tw, info);
+    }
+    return SDRX_OK;
+}
+
+int sdrx_set_front(sdrx_ctx *c, int32_t real_input, int32_t stages, const float *taps, int32_t K, double atten_db)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_set_front after sdrx_finalize");
+    if (stages == 0) {
+        static_cast<sdrx_ctx::Front &>(c->fr) = sdrx_ctx::Front();
+        return SDRX_OK;
+    }
+    bool root = false;
+    for (const Node &n : c->nodes)
+        root = root || n.d.parent_id < 0;
+    if (!root)
+        return fail(c, SDRX_ESTATE, "sdrx_set_front before the first parent-less VFO was added");
+    if (const char *why = front_args(real_input, stages, K))
+        return fail(c, SDRX_EINVAL, "sdrx_set_front: %s", why);
+    sdrx_ctx::Front F;
+    F.on = true;
+    F.plan.real = real_input, F.plan.stages = stages, F.plan.K = K;
+    F.taps.resize((size_t)front_taps(K));
+    if (taps) {
+        const int bad = front_bad_tap(taps, K);
+        if (bad >= 0)
+            return fail(c, SDRX_EINVAL, "sdrx_set_front: h[%d] must be +0.0f (every odd k but the centre %d is a zero of the half-band)", bad, front_centre(K));
+        std::copy(taps, taps + F.taps.size(), F.taps.begin());
+    } else if (int rc = front_design_checked(c, "sdrx_set_front", K, atten_db, F.taps.data(), &F.tw)) {
+        return rc;
+    }
+    static_cast<sdrx_ctx::Front &>(c->fr) = std::move(F);
+    return SDRX_OK;
+}
+
+int sdrx_get_front(sdrx_ctx *c, sdrx_front_info *info, float *taps, int32_t cap)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->fr.on)
+        return fail(c, SDRX_ESTATE, "sdrx_get_front: no front stage set (sdrx_set_front)");
+    if (!info || (taps && cap < 0))
+        return fail(c, SDRX_EINVAL, "sdrx_get_front: null info or negative cap");
+    front_info(c->fr.plan, c->fr.tw, info);
+    if (!c->finalized)
+        info->in_frame = info->out_frame = 0;
+    if (taps)
+        std::copy(c->fr.taps.begin(), c->fr.taps.begin() + std::min((size_t)cap, c->fr.taps.size()), taps);
     return SDRX_OK;
 }
 
@@ -1239,7 +1328,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
     const size_t raw_bytes = c->d_raw[0].bytes() + c->d_raw_u8[0].bytes(); // (ONE parity of the host-fed frames' buffers: kept for compatibility)
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes() + c->adc.bytes() + c->rs.bytes());
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes() + c->adc.bytes() + c->rs.bytes() + c->fr.bytes());
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

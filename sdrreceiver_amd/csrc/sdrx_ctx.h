@@ -385,7 +385,25 @@ struct sdrx_ctx : CtxBuffers {
         double passband_hz = 0;
         int lds_bytes = 0;        // k_resample's dynamic LDS: the output tile and the longest window
     } rs;
-    int in_frame = 0; // samples of an incoming frame: root_frame, or with a resampler rs.plan.n_in
+    // Front stage (sdrx_set_front, front.hip): 1 .. 3 half-band decimations by 2 in front of the resampler, or of
+    // level 0 where none is set; stage 1 may read real samples.  The setting is the host's and stays; what finalize allocates
+    // with it: the cf32 input frame of every complex stage in tile layout (d_in[s - 1] for stage s; stage 1 of a real front end
+    // reads the caller's words and has none), every stage's history of both frame parities (kFrHist cf32 each, zeroed) and the
+    // non-zero taps.  The last stage writes the resampler's staging buffer or the tree's raw frame.
+    struct FrontDevice { // what free_device_state releases
+        DevBuf<float2> d_in[kFrMaxStages];
+        DevBuf<float2> d_hist;
+        DevBuf<float> d_taps;
+        size_t bytes() const { return d_in[0].bytes() + d_in[1].bytes() + d_in[2].bytes() + d_hist.bytes() + d_taps.bytes(); }
+    };
+    struct Front : FrontDevice {
+        bool on = false;         // set (sdrx_set_front)
+        FrontPlan plan;          // the setting, the frame lengths from finalize
+        std::vector<float> taps; // N floats, prototype order
+        double tw = 0;           // the built-in design's transition width (0 for the caller's own taps)
+    } fr;
+    bool staged() const { return rs.on || fr.on; } // the ingest kernels write a staging buffer, not the tree's raw frame
+    int in_frame = 0; // samples of an incoming frame: root_frame, or with a resampler rs.plan.n_in; times 2^stages with a front stage
 
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first

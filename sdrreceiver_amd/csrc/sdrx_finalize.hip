@@ -1070,11 +1070,61 @@ int resample_setup(sdrx_ctx *c)
     return SDRX_OK;
 }
 
+// Front stage: the frame lengths of the stages sdrx_set_front fixed in front of what the tree (or the resampler) takes -- c->in_frame
+// grows by 2^stages --, or why this tree cannot have it.  Off: nothing.
+int front_plan_frames(sdrx_ctx *c)
+{
+    if (!c->fr.on)
+        return SDRX_OK;
+    const Node *first = nullptr;
+    for (const Node &n : c->nodes) {
+        if (n.d.parent_id >= 0)
+            continue;
+        if (!first)
+            first = &n;
+        else if (n.d.fs != first->d.fs || n.d.samples_per_buffer != first->d.samples_per_buffer)
+            return fail(c, SDRX_EUNSUPPORTED, "front stage: the parent-less VFOs must share one fs and one frame (%d S/s with %d samples, and %d S/s with %d)",
+                        first->d.fs, first->d.samples_per_buffer, n.d.fs, n.d.samples_per_buffer);
+    }
+    if (const char *why = front_frames(c->fr.plan, c->in_frame))
+        return fail(c, SDRX_EUNSUPPORTED, "front stage of %d half-band(s) in front of frames of %d: %s", c->fr.plan.stages, c->in_frame, why);
+    c->in_frame = c->fr.plan.in_frame;
+    return SDRX_OK;
+}
+
+// ... and what k_front_halfband needs on the device: the cf32 input frame of every complex stage (whole tiles plus one), the
+// zeroed histories, the non-zero taps as the kernel reads them: h[0], h[2], .. h[4K+2], then h[C].  All of it or (the caller
+// releases) none.
+int front_setup(sdrx_ctx *c)
+{
+    if (!c->fr.on)
+        return SDRX_OK;
+    const FrontPlan &P = c->fr.plan;
+    for (int s = P.real ? 2 : 1; s <= P.stages; ++s) {
+        const size_t n = align_up((size_t)front_stage_in(P, s), kChunk) + kChunk;
+        if (c->fr.d_in[s - 1].alloc(n) != hipSuccess)
+            return fail(c, SDRX_ENOMEM, "sdrx_finalize: no device memory for the front stage");
+        HIPCHK(c, hipMemsetAsync(c->fr.d_in[s - 1], 0, n * sizeof(float2), c->st.stream));
+    }
+    const size_t hist = 2 * (size_t)kFrHist * P.stages;
+    if (c->fr.d_hist.alloc(hist) != hipSuccess || c->fr.d_taps.alloc(2 * (size_t)P.K + 3) != hipSuccess)
+        return fail(c, SDRX_ENOMEM, "sdrx_finalize: no device memory for the front stage");
+    HIPCHK(c, hipMemsetAsync(c->fr.d_hist, 0, hist * sizeof(float2), c->st.stream));
+    std::vector<float> g(2 * (size_t)P.K + 3);
+    for (int i = 0; i <= 2 * P.K + 1; ++i)
+        g[(size_t)i] = c->fr.taps[2 * (size_t)i];
+    g[2 * (size_t)P.K + 2] = c->fr.taps[(size_t)front_centre(P.K)];
+    HIPCHK(c, hipMemcpy(c->fr.d_taps, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
+    return SDRX_OK;
+}
+
 int finalize_impl(sdrx_ctx *c)
 {
     if (int rc = derive_nodes(c))
         return rc;
     if (int rc = resample_plan_frames(c))
+        return rc;
+    if (int rc = front_plan_frames(c))
         return rc;
     Built B;
     plan_buffers(c, B);
@@ -1095,6 +1145,8 @@ int finalize_impl(sdrx_ctx *c)
     if (int rc = adc_setup(c))
         return rc;
     if (int rc = resample_setup(c))
+        return rc;
+    if (int rc = front_setup(c))
         return rc;
     catchup_setup(c, B);
     c->sq.preroll_fused = false;

@@ -99,7 +99,12 @@ ParkArg<PARK> park_arg(const sdrx_ctx *c, size_t first)
 
 // Where the ingest kernels leave a frame in tile layout: the tree's raw frame, or with a resampler the input-rate staging
 // buffer in front of it.
-float4 *ingest_dest(sdrx_ctx *c) { return reinterpret_cast<float4 *>(c->rs.on ? c->rs.d_stage.get() : c->d_raw_tiled.get()); }
+float4 *ingest_dest(sdrx_ctx *c)
+{
+    if (c->fr.on) // (complex front stage: its first stage's input frame; a real one converts the caller's words itself)
+        return reinterpret_cast<float4 *>(c->fr.d_in[0].get());
+    return reinterpret_cast<float4 *>(c->rs.on ? c->rs.d_stage.get() : c->d_raw_tiled.get());
+}
 
 // Resampler: the staged input-rate frame of the next frame (c->frame_no) -> the tree's raw frame, on the context's stream
 // behind the ingest kernel that staged it, inside that kernel's KIND_INGEST bracket.  The history slot of the previous frame's
@@ -119,6 +124,33 @@ void resample_launch(sdrx_ctx *c)
     A.n_in = P.n_in, A.n_out = P.n_out;
     A.L = P.L, A.M = P.M, A.T = P.T;
     hipLaunchKernelGGL(k_resample, dim3((P.n_out + kRsChunk - 1) / kRsChunk), dim3(256), c->rs.lds_bytes, c->st.stream, A);
+}
+
+// Front stage: one k_front_halfband launch per stage for the next frame (c->frame_no), on the context's stream behind the ingest
+// kernel that staged its input, inside that kernel's KIND_INGEST bracket and in front of resample_launch.  `real_words`: the
+// frame's 16-bit words on the device where stage 1 is the real one (format `fmt`), else null.  Every stage reads the history
+// slot of the previous frame's parity and writes this frame's (front.hip).  Off: nothing.
+void front_launch(sdrx_ctx *c, const void *real_words = nullptr, int fmt = -1)
+{
+    if (!c->fr.on)
+        return;
+    const FrontPlan &P = c->fr.plan;
+    const int p = (int)(c->frame_no & 1ull);
+    for (int s = 1; s <= P.stages; ++s) {
+        FrontArgs A;
+        const bool real = s == 1 && P.real;
+        A.in = real ? real_words : static_cast<const void *>(c->fr.d_in[s - 1].get());
+        float2 *hist = c->fr.d_hist + (size_t)(s - 1) * 2 * kFrHist;
+        A.hist_prev = hist + (size_t)(p ^ 1) * kFrHist;
+        A.hist_next = hist + (size_t)p * kFrHist;
+        A.taps = c->fr.d_taps;
+        float2 *out = s < P.stages ? c->fr.d_in[s].get() : c->rs.on ? c->rs.d_stage.get() : c->d_raw_tiled.get();
+        A.out = reinterpret_cast<float4 *>(out);
+        A.n_out = (int)front_stage_out(P, s), A.n_in = 2 * A.n_out;
+        A.K = P.K;
+        auto k = !real ? k_front_halfband<kFrontComplex> : fmt == SDRX_FMT_RS16 ? k_front_halfband<kFrontRS16> : k_front_halfband<kFrontRU12>;
+        hipLaunchKernelGGL(k, dim3((A.n_out + kFrTile - 1) / kFrTile), dim3(256), 0, c->st.stream, A);
+    }
 }
 
 int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st); // (sdrx_delivery.hip)
@@ -549,8 +581,8 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         // the levels write d_pay[p], which the previous gate reads -- and read the gains its step writes; option wake: the wake
         // steps of this frame write the flag words and state regions the previous tail, gate and step read
         HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.ev_tail[p ^ 1], 0));
-    if (c->rs.on && raw_mode != kRawTiled) {
-        // Resampler: a natural-order frame (cf32, or a shared context's bytes) is at the input rate -- one layout pass into the
+    if (c->staged() && raw_mode != kRawTiled) {
+        // Resampler / front stage: a natural-order frame (cf32, or a shared context's bytes) is at the input rate -- one layout pass into the
         // staging buffer, then k_resample, in front of everything that reads the tree's raw frame.  (A frame of integer samples
         // came through enqueue_samples_device, which did both: kRawTiled.)
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
@@ -561,6 +593,7 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         else
             hipLaunchKernelGGL(k_ingest_samples<SDRX_FMT_CU8>, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream,
                                reinterpret_cast<const unsigned *>(raw), ingest_dest(c), n_pairs);
+        front_launch(c);
         resample_launch(c);
         raw_mode = kRawTiled;
     }
@@ -682,7 +715,10 @@ int ensure_raw(sdrx_ctx *c, size_t n_complex)
     return fail(c, SDRX_EHIP, "no device memory for the frame buffers: %s", hipGetErrorString(e));
 }
 
-int check_frame_call(sdrx_ctx *c, const char *what, const void *ptr, int n_complex, bool sync_call)
+bool real_format(int fmt) { return fmt == SDRX_FMT_RS16 || fmt == SDRX_FMT_RU12; }
+
+// `fmt`: the format of the frame's samples, -1 for cf32
+int check_frame_call(sdrx_ctx *c, const char *what, const void *ptr, int n_complex, bool sync_call, int fmt = -1)
 {
     if (c && c->broken)
         return fail(c, SDRX_EHIP, "%s: injected fault (SDRX_FAULT_WAIT): the context is unusable", what);
@@ -692,10 +728,19 @@ int check_frame_call(sdrx_ctx *c, const char *what, const void *ptr, int n_compl
         return fail(c, SDRX_EINVAL, "%s: null frame pointer", what);
     if (!c->finalized)
         return fail(c, SDRX_ESTATE, "%s before sdrx_finalize", what);
+    if (real_format(fmt) != (c->fr.on && c->fr.plan.real != 0))
+        return fail(c, SDRX_EINVAL,
+                    real_format(fmt) ? "%s: fmt must be SDRX_FMT_CU8 (0), SDRX_FMT_CS8 (1) or SDRX_FMT_CS16 (2) here: the real formats SDRX_FMT_RS16 (3) "
+                                       "and SDRX_FMT_RU12 (4) need a front stage with real_input = 1 (sdrx_set_front)"
+                                     : "%s: this context's front stage takes real samples (SDRX_FMT_RS16, SDRX_FMT_RU12) only",
+                    what);
+    if (n_complex != c->in_frame && c->fr.on)
+        return fail(c, SDRX_EINVAL, "frame of %d samples: with a front stage of %d half-band(s) a frame has %d (%d behind it)", n_complex, c->fr.plan.stages,
+                    c->in_frame, c->fr.plan.n0);
     if (n_complex != c->in_frame && c->rs.on)
         return fail(c, SDRX_EINVAL, "frame of %d samples: with the resampler %d -> %d S/s a frame has %d (for the VFOs' %d)", n_complex, c->rs.plan.fs_in,
                     c->rs.plan.fs_out, c->in_frame, c->root_frame);
-    if (n_complex != c->root_frame && !c->rs.on)
+    if (n_complex != c->root_frame && !c->staged())
         return fail(c, SDRX_EINVAL, "frame of %d samples, VFOs were initialised for %d (vfo::init samplesPerBuffer)", n_complex,
                     c->root_frame);
     if (sync_call && c->in_flight > 0)
@@ -745,7 +790,7 @@ int enqueue_f32(sdrx_ctx *c, const float *iq, int n_complex, bool egress)
         return rc;
     rc = enqueue_frame(c, dst, kRawF32, egress);
     if (rc == SDRX_OK)
-        c->last_raw = c->rs.on ? kRawTiled : kRawF32; // (resampler: the tree's frame is k_resample's, in the tile layout)
+        c->last_raw = c->staged() ? kRawTiled : kRawF32; // (resampler, front stage: the tree's frame is their output, in the tile layout)
     return rc;
 }
 
@@ -767,8 +812,8 @@ const SampleKernels &sample_kernels(int fmt)
     static const SampleKernels K[3] = {sample_kernels_of<SDRX_FMT_CU8>(), sample_kernels_of<SDRX_FMT_CS8>(), sample_kernels_of<SDRX_FMT_CS16>()};
     return K[fmt];
 }
-bool known_format(int fmt) { return fmt == SDRX_FMT_CU8 || fmt == SDRX_FMT_CS8 || fmt == SDRX_FMT_CS16; }
-size_t sample_bytes(int fmt, int n_complex) { return (size_t)n_complex * (fmt == SDRX_FMT_CS16 ? 4 : 2); }
+bool known_format(int fmt) { return fmt == SDRX_FMT_CU8 || fmt == SDRX_FMT_CS8 || fmt == SDRX_FMT_CS16 || real_format(fmt); }
+size_t sample_bytes(int fmt, int n_complex) { return (size_t)n_complex * (fmt == SDRX_FMT_CS16 ? 4 : 2); } // (real formats: 2 bytes a real sample)
 
 // Option adc_meter: the statistics of the next frame's integer samples as they lie at `dev_samples` (format `fmt`), on the
 // context's stream in front of everything that converts them -- one k_adc_meter launch, its record into the frame parity's
@@ -779,8 +824,8 @@ void adc_meter_launch(sdrx_ctx *c, const void *dev_samples, int n_complex, int f
 {
     if (!c->opt_adc_meter)
         return;
-    static void (*const K[3])(const unsigned *, int, long long, AdcPartial *, unsigned *, AdcRecord *, int, int) = {
-        k_adc_meter<SDRX_FMT_CU8>, k_adc_meter<SDRX_FMT_CS8>, k_adc_meter<SDRX_FMT_CS16>};
+    static void (*const K[5])(const unsigned *, int, long long, AdcPartial *, unsigned *, AdcRecord *, int, int) = {
+        k_adc_meter<SDRX_FMT_CU8>, k_adc_meter<SDRX_FMT_CS8>, k_adc_meter<SDRX_FMT_CS16>, k_adc_meter<SDRX_FMT_RS16>, k_adc_meter<SDRX_FMT_RU12>};
     const int p = (int)(c->frame_no & 1ull);
     const int nb = (n_complex + kAdcWg - 1) / kAdcWg; // workgroups = partials
     if ((size_t)nb > c->adc.d_part.count()) // (never: every frame has in_frame samples, what adc_setup sized for)
@@ -836,6 +881,20 @@ int dc_first_use(sdrx_ctx *c, int n_complex, int nchunks)
 // the signed formats always enter through an ingest pass into the tile layout, as every DC-corrected frame does.
 int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, int fmt, int correct_dc, bool egress)
 {
+    if (real_format(fmt)) {
+        // Real samples: the ADC meter reads the same memory as pairs (even samples arm I, odd samples arm Q); stage 1 of the
+        // front stage converts the words itself -- no conversion kernel, no DC removal (frame_call_fmt refused it).
+        adc_meter_launch(c, dev_bytes, n_complex / 2, fmt);
+        {
+            Bracket b(c, c->st.stream, KIND_INGEST, 0);
+            front_launch(c, dev_bytes, fmt);
+            resample_launch(c);
+        }
+        const int rc = enqueue_frame(c, dev_bytes, kRawTiled, egress);
+        if (rc == SDRX_OK)
+            c->last_raw = kRawTiled;
+        return rc;
+    }
     const SampleKernels &K = sample_kernels(fmt);
     adc_meter_launch(c, dev_bytes, n_complex, fmt); // (option adc_meter: the samples as they arrived, in front of everything)
     int mode = kRawU8;
@@ -863,6 +922,7 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         }
         hipLaunchKernelGGL(K.apply, dim3((words + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), Ap,
                            ingest_dest(c), n_complex, c->dc.work_stride);
+        front_launch(c);
         resample_launch(c);
         mode = kRawTiled;
     } else if (correct_dc) {
@@ -873,13 +933,15 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
                            c->dc.d_tab, sums);
         hipLaunchKernelGGL(K.dc_fast, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
                            ingest_dest(c), n_complex, c->dc.d_state + 2 * par, c->dc.d_state + 2 * (par ^ 1), c->dc.d_tab, sums);
+        front_launch(c);
         resample_launch(c);
         mode = kRawTiled;
-    } else if (fmt != SDRX_FMT_CU8 || c->rs.on) { // (resampler: k_resample reads the tile layout, so bytes take the pass too)
+    } else if (fmt != SDRX_FMT_CU8 || c->staged()) { // (resampler, front stage: they read the tile layout, so bytes take the pass too)
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
         const int n_pairs = n_complex / 2;
         hipLaunchKernelGGL(K.ingest, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
                            ingest_dest(c), n_pairs);
+        front_launch(c);
         resample_launch(c);
         mode = kRawTiled;
     }
@@ -910,7 +972,7 @@ int enqueue_samples(sdrx_ctx *c, const void *samples, int n_complex, int fmt, in
 const char *bad_samples(int fmt, const void *dev_ptr)
 {
     if (!known_format(fmt))
-        return "fmt must be SDRX_FMT_CU8 (0), SDRX_FMT_CS8 (1) or SDRX_FMT_CS16 (2)";
+        return "fmt must be SDRX_FMT_CU8 (0), SDRX_FMT_CS8 (1), SDRX_FMT_CS16 (2), or with a real front stage SDRX_FMT_RS16 (3) or SDRX_FMT_RU12 (4)";
     if (dev_ptr && (reinterpret_cast<uintptr_t>(dev_ptr) & 15u))
         return "device samples must be 16-byte aligned";
     return nullptr;
@@ -925,7 +987,7 @@ int sdrx_process_device(sdrx_ctx *c, const void *dev_iq, int n_complex)
     int rc = check_frame_call(c, "sdrx_process_device", dev_iq, n_complex, true);
     if (rc)
         return rc;
-    c->last_raw = c->rs.on ? kRawTiled : -1; // (resampler: the tree's frame is the context's own, k_resample wrote it)
+    c->last_raw = c->staged() ? kRawTiled : -1; // (resampler, front stage: the tree's frame is the context's own, they wrote it)
     return enqueue_frame(c, dev_iq, kRawF32, false);
 }
 
@@ -934,7 +996,7 @@ int sdrx_submit_device(sdrx_ctx *c, const void *dev_iq, int n_complex)
     int rc = check_frame_call(c, "sdrx_submit_device", dev_iq, n_complex, false);
     if (rc)
         return rc;
-    c->last_raw = c->rs.on ? kRawTiled : -1;
+    c->last_raw = c->staged() ? kRawTiled : -1;
     return enqueue_frame(c, dev_iq, kRawF32, true);
 }
 
@@ -955,8 +1017,8 @@ static int submit_shared(sdrx_ctx *c, sdrx_ctx *src, const char *what, bool sync
 {
     if (!c || !src || c == src)
         return c ? fail(c, SDRX_EINVAL, "%s: needs another context as the source", what) : SDRX_EINVAL;
-    if (c->rs.on || src->rs.on)
-        return fail(c, SDRX_ESTATE, "%s: a context with a resampler (sdrx_set_resampler) shares no frames", what);
+    if (c->staged() || src->staged())
+        return fail(c, SDRX_ESTATE, "%s: a context with a resampler or a front stage (sdrx_set_resampler, sdrx_set_front) shares no frames", what);
     if (!src->finalized || src->frame_no == 0 || (src->last_raw != kRawF32 && src->last_raw != kRawU8))
         return fail(c, SDRX_ESTATE, "%s: the source context has staged no host frame (floats or bytes without DC removal) yet", what);
     if (src->device != c->device)
@@ -1044,13 +1106,15 @@ int sdrx_process(sdrx_ctx *c, const float *iq, int n_complex)
 }
 
 // ---- one front door for integer samples (SDRX_FMT_*): host frames, and frames already on the device ------------------------
-static int frame_call_fmt(sdrx_ctx *c, const char *what, const void *ptr, int n_complex, int fmt, const void *dev_ptr, bool sync_call)
+static int frame_call_fmt(sdrx_ctx *c, const char *what, const void *ptr, int n_complex, int fmt, const void *dev_ptr, bool sync_call, int correct_dc)
 {
-    const int rc = check_frame_call(c, what, ptr, n_complex, sync_call);
+    const int rc = check_frame_call(c, what, ptr, n_complex, sync_call, known_format(fmt) ? fmt : -1);
     if (rc)
         return rc;
     if (const char *why = bad_samples(fmt, dev_ptr))
         return fail(c, SDRX_EINVAL, "%s: %s", what, why);
+    if (real_format(fmt) && correct_dc)
+        return fail(c, SDRX_EINVAL, "%s: no DC removal for real samples (DC lands at the edge of the output band, where the stages behind discard it)", what);
     return SDRX_OK;
 }
 
@@ -1058,7 +1122,7 @@ static int frame_call_fmt(sdrx_ctx *c, const char *what, const void *ptr, int n_
 // own name: that format passes bad_samples, and a host frame has no alignment to test, so their checks are check_frame_call's.
 static int host_samples_call(sdrx_ctx *c, const char *what, const void *ptr, int n_complex, int fmt, int correct_dc, bool sync_call)
 {
-    int rc = frame_call_fmt(c, what, ptr, n_complex, fmt, nullptr, sync_call);
+    int rc = frame_call_fmt(c, what, ptr, n_complex, fmt, nullptr, sync_call, correct_dc);
     if (rc)
         return rc;
     rc = enqueue_samples(c, ptr, n_complex, fmt, correct_dc, true);
@@ -1097,13 +1161,13 @@ static int device_frame_fmt(sdrx_ctx *c, const void *dev_iq, int n_complex, int 
 
 int sdrx_process_device_fmt(sdrx_ctx *c, const void *dev_iq, int n_complex, int fmt, int correct_dc)
 {
-    const int rc = frame_call_fmt(c, "sdrx_process_device_fmt", dev_iq, n_complex, fmt, dev_iq, true);
+    const int rc = frame_call_fmt(c, "sdrx_process_device_fmt", dev_iq, n_complex, fmt, dev_iq, true, correct_dc);
     return rc ? rc : device_frame_fmt(c, dev_iq, n_complex, fmt, correct_dc, false);
 }
 
 int sdrx_submit_device_fmt(sdrx_ctx *c, const void *dev_iq, int n_complex, int fmt, int correct_dc)
 {
-    const int rc = frame_call_fmt(c, "sdrx_submit_device_fmt", dev_iq, n_complex, fmt, dev_iq, false);
+    const int rc = frame_call_fmt(c, "sdrx_submit_device_fmt", dev_iq, n_complex, fmt, dev_iq, false, correct_dc);
     return rc ? rc : device_frame_fmt(c, dev_iq, n_complex, fmt, correct_dc, true);
 }
 

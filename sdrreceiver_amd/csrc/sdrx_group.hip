@@ -466,6 +466,8 @@ static int group_samples_call(sdrx_group *g, const char *what, const void *ptr, 
         return rc;
     if (const char *why = bad_samples(fmt, nullptr))
         return gfail(g, SDRX_EINVAL, "%s: %s", what, why);
+    if (real_format(fmt)) // (a group has no front stage: sdrx_set_front is a context's)
+        return gfail(g, SDRX_EINVAL, "%s: fmt must be SDRX_FMT_CU8 (0), SDRX_FMT_CS8 (1) or SDRX_FMT_CS16 (2) on a group (the real formats need a front stage)", what);
     const size_t nb = sample_bytes(fmt, n_complex);
     rc = group_stage(g, ptr, nb);
     if (!rc)

@@ -7,14 +7,28 @@ AGC and watch threshold live in, and the bound the device's DC-bias removal is p
     CU8 = 0    uint8 I,Q                 b - 127                           [-127, 128]
     CS8 = 1    int8 I,Q                  float(v)                          [-128, 127]
     CS16 = 2   native-endian int16 I,Q   float(v) * 2**-8                  [-128, 128)
+
+Two formats of REAL samples, taken only by a receiver whose front stage has ``front_real`` (sdrreceiver_amd.front; include/sdrx.h
+"Front stage"), whose first half-band turns them into I/Q on the device:
+
+    RS16 = 3   native-endian int16       float(v) * 2**-8                  [-128, 128)
+    RU12 = 4   uint16, 12-bit offset     float((v & 4095) - 2048) * 2**-4  [-128, 128)
+
+An array's dtype never stands for a real format: int16 is CS16 to :func:`infer_format` and uint16 nothing, so `fmt` must be told.
 """
 from __future__ import annotations
 
 import numpy as np
 
 CU8, CS8, CS16 = 0, 1, 2  # SDRX_FMT_CU8, SDRX_FMT_CS8, SDRX_FMT_CS16
+RS16, RU12 = 3, 4  # SDRX_FMT_RS16, SDRX_FMT_RU12: real samples
 FORMATS = {CU8: np.dtype(np.uint8), CS8: np.dtype(np.int8), CS16: np.dtype(np.int16)}
-NAMES = {"cu8": CU8, "cs8": CS8, "cs16": CS16}
+REAL_FORMATS = {RS16: np.dtype(np.int16), RU12: np.dtype(np.uint16)}
+NAMES = {"cu8": CU8, "cs8": CS8, "cs16": CS16, "rs16": RS16, "ru12": RU12}
+
+
+def is_real(fmt) -> bool:
+    return fmt in REAL_FORMATS
 
 
 def infer_format(a) -> int:
@@ -30,10 +44,12 @@ def as_samples(a, fmt=None) -> tuple[np.ndarray, int]:
     """`a` as the flat contiguous array of format `fmt` (None: the one its dtype stands for), and that format."""
     if fmt is None:
         fmt = infer_format(a)
-    if fmt not in FORMATS:
-        raise ValueError(f"fmt {fmt!r}: CU8 (0), CS8 (1) or CS16 (2)")
+    if fmt not in FORMATS and fmt not in REAL_FORMATS:
+        raise ValueError(f"fmt {fmt!r}: CU8 (0), CS8 (1), CS16 (2), or the real RS16 (3) or RU12 (4)")
     a = np.asarray(a)
-    if a.dtype != FORMATS[fmt]:
+    if fmt in REAL_FORMATS and a.dtype != REAL_FORMATS[fmt]:  # (a value problem: the real formats are named, never inferred)
+        raise ValueError(f"the real format {fmt} takes {REAL_FORMATS[fmt]} samples, not {a.dtype}")
+    if fmt in FORMATS and a.dtype != FORMATS[fmt]:
         raise TypeError(f"format {fmt} takes {FORMATS[fmt]}, not {a.dtype}")
     return np.ascontiguousarray(a).reshape(-1), int(fmt)
 
@@ -45,13 +61,24 @@ def to_float(a, fmt=None) -> np.ndarray:
         return (a.astype(np.int32) - 127).astype(np.float32)
     if fmt == CS8:
         return a.astype(np.float32)
+    if fmt == RU12:
+        return ((a.astype(np.int32) & 4095) - 2048).astype(np.float32) * np.float32(2.0 ** -4)
     return a.astype(np.float32) * np.float32(2.0 ** -8)
 
 
 # ---- ADC meter (option ``adc_meter``; include/sdrx.h sdrx_adc_meter): the record, and the figures a front-end loop wants --------
 # The integer code v of a component: CU8 b - 127, CS8 the int8, CS16 the int16 itself.  LOWEST / HIGHEST: the rails per format.
+# A real frame is recorded as the same memory read as pairs -- even samples in arm I, odd samples in arm Q --: RS16 the int16,
+# RU12 (v & 4095) - 2048.
 LOWEST = {CU8: -127, CS8: -128, CS16: -32768}
 HIGHEST = {CU8: 128, CS8: 127, CS16: 32767}
+REAL_LOWEST = {RS16: -32768, RU12: -2048}
+REAL_HIGHEST = {RS16: 32767, RU12: 2047}
+
+
+def rails(fmt) -> tuple[int, int]:
+    """(lowest, highest) code of a format, complex or real"""
+    return (REAL_LOWEST[fmt], REAL_HIGHEST[fmt]) if fmt in REAL_FORMATS else (LOWEST[fmt], HIGHEST[fmt])
 FULL_SCALE = 128.0  # the largest |code| of every format in the chain's units, "dongle LSB" (CS16 codes times 2**-8)
 ADC_BINS = 17
 
@@ -59,6 +86,8 @@ ADC_BINS = 17
 def codes(a, fmt=None) -> np.ndarray:
     """The integer codes (int64, interleaved I,Q) the ADC meter counts: the table above."""
     a, fmt = as_samples(a, fmt)
+    if fmt == RU12:
+        return (a.astype(np.int64) & 4095) - 2048
     return a.astype(np.int64) - 127 if fmt == CU8 else a.astype(np.int64)
 
 
@@ -84,12 +113,35 @@ def adc_levels(rec: dict) -> dict:
     ``gain_imbalance = sqrt(var_i / var_q)`` and ``phase_error = asin(cov_iq / sqrt(var_i var_q))`` in radians (nan when an
     arm is constant).  Variances and the covariance come from exact integers: ``var_i = (n sum_sq_i - sum_i**2) / n**2`` and
     ``cov_iq = (n sum_iq - sum_i sum_q) / n**2``, each numerator converted to float64 once.  ValueError for a record that was
-    not measured."""
+    not measured.
+
+    A record of REAL samples (``fmt`` RS16 or RU12: the arms are the even and the odd samples) is merged into one arm first:
+    sums, sums of squares and rail counts add up, min / max are taken over both; ``dc`` (the mean), ``rms``, ``peak``,
+    ``headroom_db``, ``clip_share`` (of 2 n real samples), ``bits_used`` and ``longest_rail_run`` -- the larger of the two arms',
+    a LOWER BOUND: a run of consecutive real samples alternates between the arms, so it is up to twice that plus one.  No IQ
+    balance: ``dc_i`` = ``dc_q`` = ``dc`` and ``gain_imbalance`` and ``phase_error`` are nan."""
     if not rec["measured"]:
         raise ValueError("the frame was not measured: it did not arrive as integer samples")
     n = int(rec["n_complex"])
-    s = 2.0 ** -8 if rec["fmt"] == CS16 else 1.0
+    s = 2.0 ** -8 if rec["fmt"] in (CS16, RS16) else 2.0 ** -4 if rec["fmt"] == RU12 else 1.0
     i, q = rec["i"], rec["q"]
+    if is_real(rec["fmt"]):
+        total, total_sq = i["sum"] + q["sum"], i["sum_sq"] + q["sum_sq"]
+        peak = float(max(abs(min(i["min"], q["min"])), abs(max(i["max"], q["max"])))) * s
+        used = [k for k, b in enumerate(rec["bits"]) if b]
+        dc = float(total) / (2.0 * float(n)) * s
+        return {
+            "dc": dc, "dc_i": dc, "dc_q": dc,
+            "rms": float(np.sqrt(float(total_sq) / (2.0 * float(n)))) * s,
+            "peak": peak,
+            "headroom_db": float(20.0 * np.log10(FULL_SCALE / peak)) if peak > 0.0 else float("inf"),
+            "clip_share": float(i["at_lo"] + i["at_hi"] + q["at_lo"] + q["at_hi"]) / (2.0 * float(n)),
+            "longest_rail_run": max(i["longest_rail_run"], q["longest_rail_run"]),
+            "longest_rail_run_is_lower_bound": True,
+            "bits_used": used[-1] if used else 0,
+            "gain_imbalance": float("nan"),
+            "phase_error": float("nan"),
+        }
     nn = float(n) * float(n)
     var_i = float(n * i["sum_sq"] - i["sum"] ** 2) / nn * s * s
     var_q = float(n * q["sum_sq"] - q["sum"] ** 2) / nn * s * s

@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, agc as _agc, drift as _drift, ingest, meter, resample as _resample, scan as _scan, squelch as _squelch, wake as _wake, watch as _watch
+from . import _lib, agc as _agc, drift as _drift, front as _front, ingest, meter, resample as _resample, scan as _scan, squelch as _squelch, wake as _wake, watch as _watch
 from .topology import Topology, VfoDesc
 
 
@@ -312,7 +312,14 @@ class Receiver(_LeafCalls):
                  tail_in_levels: bool = True, meter: bool = False, squelch: bool = False, preroll: bool = False,
                  squelch_auto: bool = False, park: bool = False, watch: bool = False, catchup: bool = False,
                  agc: bool = False, wake: bool = False, adc_meter: bool = False, input_rate: int | None = None,
-                 resample_taps=32, resample_atten_db: float = 80.0):
+                 resample_taps=32, resample_atten_db: float = 80.0, front_stages: int = 0, front_real: bool = False,
+                 front_taps=15, front_atten_db: float = 80.0):
+        # front_stages: 1 .. 3 half-band decimations by 2 in front of the resampler (or of level 0) -- frames then have
+        # front["in_frame"] samples (sdrreceiver_amd.front).  front_real: the first stage reads REAL samples (process_fmt with
+        # fmt=ingest.RS16 or ingest.RU12).  front_taps: K of the built-in design (N = 4 K + 3 taps) with front_atten_db, or the
+        # caller's own prototype.  With both, input_rate stays the rate at the resampler's input: behind the front stage.
+        self._front_stages, self._front_real = int(front_stages), bool(front_real)
+        self._front_taps, self._front_atten = front_taps, float(front_atten_db)
         # input_rate: the front end's sample rate where it is not the parent-less VFOs' fs -- frames then have
         # resampler["in_frame"] samples and a rational resampler on the device makes the tree's frame (sdrreceiver_amd.resample).
         # resample_taps: the taps per phase of the built-in design with resample_atten_db, or the caller's own L * T prototype.
@@ -399,6 +406,8 @@ class Receiver(_LeafCalls):
     def finalize(self):
         if self._input_rate:
             self._set_resampler()
+        if self._front_stages:
+            self._set_front()
         self._chk(self.L.sdrx_finalize(self.h))
         self.finalized = True
 
@@ -419,6 +428,26 @@ class Receiver(_LeafCalls):
                 raise ValueError(f"resample_taps holds {taps.size} floats, no multiple of L = {L}")
             T = taps.size // L
         self._chk(self.L.sdrx_set_resampler(self.h, fs_in, taps.ctypes.data, T))
+
+    def _set_front(self) -> None:
+        if np.ndim(self._front_taps) == 0:  # K: the library's own design
+            self._chk(self.L.sdrx_set_front(self.h, int(self._front_real), self._front_stages, None, int(self._front_taps), self._front_atten))
+        else:
+            taps = np.ascontiguousarray(self._front_taps, dtype=np.float32).reshape(-1)
+            self._chk(self.L.sdrx_set_front(self.h, int(self._front_real), self._front_stages, taps.ctypes.data, _front.k_of(taps), 0.0))
+
+    @property
+    def front(self) -> dict | None:
+        """The front stage's ``sdrx_front_info`` as a dict (``tw`` and ``alias_free`` of the built-in design; 0 for the caller's
+        own taps) with ``taps``, the prototype as the library holds it; None without ``front_stages``."""
+        if not self._front_stages:
+            return None
+        info = _lib.FrontInfoC()
+        taps = np.zeros(_front.MAX_N, np.float32)
+        self._chk(self.L.sdrx_get_front(self.h, C.byref(info), taps.ctypes.data, taps.size))
+        d = _front.info_dict(info)
+        d["taps"] = taps[: d["N"]].copy()
+        return d
 
     @property
     def resampler(self) -> dict | None:
@@ -468,7 +497,7 @@ class Receiver(_LeafCalls):
         int8, int16; `fmt` None: the one the array's dtype stands for): conversion + optional DC-bias IIR on the device."""
         a, fmt = ingest.as_samples(iq, fmt)
         self.published.clear()
-        self._chk(self.L.sdrx_process_fmt(self.h, a.ctypes.data, a.size // 2, fmt, int(bool(correct_dc))))
+        self._chk(self.L.sdrx_process_fmt(self.h, a.ctypes.data, a.size if ingest.is_real(fmt) else a.size // 2, fmt, int(bool(correct_dc))))
 
     def process_device(self, dev_ptr: int, n_complex: int) -> None:
         self.published.clear()  # the payloads of this frame arrive with the next (explicit or implicit) fetch
@@ -502,7 +531,7 @@ class Receiver(_LeafCalls):
     def submit_fmt(self, iq, correct_dc: bool = False, fmt=None) -> None:
         """:meth:`process_fmt`'s frame, pipelined like :meth:`submit_u8`."""
         a, fmt = ingest.as_samples(iq, fmt)
-        self._chk(self.L.sdrx_submit_fmt(self.h, a.ctypes.data, a.size // 2, fmt, int(bool(correct_dc))))
+        self._chk(self.L.sdrx_submit_fmt(self.h, a.ctypes.data, a.size if ingest.is_real(fmt) else a.size // 2, fmt, int(bool(correct_dc))))
 
     def submit_device_fmt(self, dev_ptr: int, n_complex: int, fmt: int, correct_dc: bool = False) -> None:
         """:meth:`process_device_fmt`'s frame, pipelined like :meth:`submit_device`."""
