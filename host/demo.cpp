@@ -4,7 +4,8 @@
 //
 //   sdrx_demo <profile.ini> --dump              descriptors as JSON lines (no GPU needed)
 //   sdrx_demo <profile.ini> --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ]
-//                                   [--front-stages N [--front-real] [--front-taps K]] [--fft TOPIC] [--devices 0,1,...]
+//                                   [--front-stages N [--front-real] [--front-taps K]] [--blanker RATIO,GUARD[,FLOOR[,RANK]]]
+//                                   [--fft TOPIC] [--devices 0,1,...]
 //                                               N synthetic LCG frames; one line per published
 //                                               message: frame topic rate bytes fnv1a64(payload)
 //                                               --u8 feeds them as dongle bytes, --format as integer samples of that
@@ -21,6 +22,10 @@
 //                                               the frames have 2^N times the samples.  --front-real: they are REAL samples,
 //                                               --format rs16 (int16) or ru12 (12-bit offset codes in uint16).  Next line
 //                                               front real_input stages K N in_frame out_frame tw alias_free
+//                                               --blanker RATIO,GUARD[,FLOOR[,RANK]]: the impulse blanker on the device (FLOOR 0,
+//                                               RANK 32768 -- the median -- unless given); one more line per frame behind its
+//                                               messages (in front of the adc line),
+//                                               blanker frame thr_bits ref_bin next_ref_bin hits blanked runs carry_in
 #include <cinttypes>
 #include <cstdio>
 #include <iostream>
@@ -43,7 +48,7 @@ static uint64_t fnv1a(const void *p, size_t n)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ] [--front-stages N [--front-real] [--front-taps K]] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ] [--front-stages N [--front-real] [--front-taps K]] [--blanker RATIO,GUARD[,FLOOR[,RANK]]] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
         return 2;
     }
     try {
@@ -73,7 +78,9 @@ int main(int argc, char **argv)
         const int frames = std::atoi(argv[3]);
         bool u8 = false, adc = false;
         int fmt = SDRX_FMT_CU8, input_rate = 0, front_stages = 0, front_K = 15;
-        bool front_real = false;
+        bool front_real = false, blanker = false;
+        float bl_ratio = 0, bl_floor = 0;
+        int bl_guard = 0, bl_rank = 32768;
         std::string fft_topic;
         std::vector<int> devices;
         for (int a = 4; a < argc; ++a) {
@@ -95,7 +102,12 @@ int main(int argc, char **argv)
                 front_K = std::atoi(argv[++a]);
             else if (std::string(argv[a]) == "--front-real")
                 front_real = true;
-            else if (std::string(argv[a]) == "--fft" && a + 1 < argc)
+            else if (std::string(argv[a]) == "--blanker" && a + 1 < argc) {
+                const int got = std::sscanf(argv[++a], "%f,%d,%f,%d", &bl_ratio, &bl_guard, &bl_floor, &bl_rank);
+                if (got < 2)
+                    throw std::runtime_error("--blanker takes RATIO,GUARD[,FLOOR[,RANK]]");
+                blanker = true;
+            } else if (std::string(argv[a]) == "--fft" && a + 1 < argc)
                 fft_topic = argv[++a];
             else if (std::string(argv[a]) == "--devices" && a + 1 < argc) { // one tree sharded over several GPUs
                 std::stringstream ss(argv[++a]);
@@ -142,6 +154,8 @@ int main(int argc, char **argv)
             radio.setInputRate(input_rate);
         if (front_stages > 0)
             radio.setFront(front_stages, front_real, front_K);
+        if (blanker)
+            radio.setBlanker(bl_ratio, bl_guard, bl_floor, bl_rank);
         if (input_rate > 0 || front_stages > 0)
             radio.start();
         if (input_rate > 0) {
@@ -185,6 +199,10 @@ int main(int argc, char **argv)
                 radio.demodBytes(bytes.data(), n_frame);
             else
                 radio.demodData(iq.data(), (int)iq.size());
+            if (blanker) {
+                const sdrx_blanker_record b = radio.blanker();
+                std::printf("blanker %d %08x %d %d %u %u %u %u\n", frame_no, b.thr_bits, b.ref_bin, b.next_ref_bin, b.hits, b.blanked, b.runs, b.carry_in);
+            }
             if (adc) {
                 const sdrx_adc_meter r = radio.adcMeter();
                 if (!r.measured) {

@@ -190,6 +190,28 @@ public:
         check(sdrx_get_front(ctx_, &info, nullptr, 0), "sdrx_get_front");
         return info;
     }
+    // The impulse blanker on the device (include/sdrx.h "Impulse blanker"; no counterpart in the reference): samples whose power
+    // exceeds `ratio` times the rank `rank_q16` (32768: the median) of the previous frame's powers, and `floor`, become zero with
+    // `guard` samples on either side, behind the format conversion and the DC removal and in front of everything else.  Before
+    // the first frame it switches the stage on; afterwards it changes the four settings between two frames.  One device only.
+    void setBlanker(float ratio, int guard, float floor = 0.0f, int rank_q16 = 32768)
+    {
+        if (grp_)
+            throw std::runtime_error("sdrj: the blanker (setBlanker) is not offered on several devices");
+        bl_cfg_ = sdrx_blanker_cfg{ratio, floor, rank_q16, guard, {0, 0, 0, 0}};
+        if (ctx_)
+            check(sdrx_set_blanker(ctx_, &bl_cfg_), "sdrx_set_blanker");
+        bl_on_ = true;
+    }
+    // ... and its record of the last delivered frame: threshold, reference bins, hits / blanked / runs / carry_in
+    sdrx_blanker_record blanker()
+    {
+        if (!ctx_ || !bl_on_)
+            throw std::runtime_error("sdrj::blanker: no blanker set, or not started");
+        sdrx_blanker_record r;
+        check(sdrx_get_blanker(ctx_, nullptr, &r), "sdrx_get_blanker");
+        return r;
+    }
     // sdrj.cpp:84-101: the raw spectrum is selected by the topic "Main"; any selection restarts
     // the every-4th-call counter of demodData (sdrj.cpp:296-303)
     void fftVFOSlot(const std::string &topic)
@@ -208,6 +230,8 @@ public:
             throw std::runtime_error("sdrj: the resampler (setInputRate) is not offered on several devices");
         if (devices_.size() > 1 && fr_stages_)
             throw std::runtime_error("sdrj: the front stage (setFront) is not offered on several devices");
+        if (devices_.size() > 1 && bl_on_)
+            throw std::runtime_error("sdrj: the blanker (setBlanker) is not offered on several devices");
         if (devices_.size() > 1) {
             check(sdrx_group_create(&grp_, devices_.data(), (int)devices_.size()), "sdrx_group_create");
             for (auto &kv : options_)
@@ -233,6 +257,8 @@ public:
         }
         if (fr_stages_)
             check(sdrx_set_front(ctx_, fr_real_ ? 1 : 0, fr_stages_, nullptr, fr_K_, fr_atten_), "sdrx_set_front");
+        if (bl_on_)
+            check(sdrx_set_blanker(ctx_, &bl_cfg_), "sdrx_set_blanker");
         check(sdrx_set_publish_callback(ctx_, &sdrj::trampoline, this), "sdrx_set_publish_callback");
         check(sdrx_finalize(ctx_), "sdrx_finalize");
     }
@@ -617,6 +643,8 @@ private:
     int fr_stages_ = 0, fr_K_ = 15; // setFront
     bool fr_real_ = false;
     double fr_atten_ = 80.0;
+    bool bl_on_ = false; // setBlanker
+    sdrx_blanker_cfg bl_cfg_{};
 };
 
 // ------------------------------------------------------------------------------------------ INI

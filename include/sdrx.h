@@ -941,6 +941,62 @@ int sdrx_front_design(int32_t K, double atten_db, float *taps, int32_t cap, sdrx
 int sdrx_set_front(sdrx_ctx *ctx, int32_t real_input, int32_t stages, const float *taps, int32_t K, double atten_db);
 int sdrx_get_front(sdrx_ctx *ctx, sdrx_front_info *info, float *taps, int32_t cap);
 
+/* ---- Impulse blanker (sdrx_set_blanker before sdrx_finalize) -----------------------------------------------------
+ * Zeroes short, strong pulses (radar, ignition, a switching supply, a USB dropout) in the wideband frame, behind the format
+ * conversion and the DC-bias removal and in front of the front stage, the resampler or level 0: one pass over the frame instead
+ * of a pulse ringing in every channel.  The reference has no counterpart: this text is the definition, sdrreceiver_amd/blank.py
+ * restates it in numpy, and the device is held to that bit for bit.  Off (the default) nothing changes at all: the same kernels,
+ * launches, device_bytes, payloads and callbacks.
+ *
+ * Settings (sdrx_blanker_cfg; anything else is SDRX_EINVAL, there are no defaults):
+ *   ratio      fp32, finite, >= 1: a hit is a power above ratio times the reference
+ *   floor      fp32, finite, >= 0: ... and above this, in chain units squared
+ *   rank_q16   1 .. 65536: the reference is this rank of the previous frame's powers (32768: the median)
+ *   guard      G in 0 .. 64: samples blanked on either side of a hit
+ *
+ * Frame f, x its n cf32 samples as they reach the stage.  State: ref_bin (-1 after sdrx_finalize), tail_gap (G_max + 1 = 65 after
+ * sdrx_finalize: no carry), last_blank (0).
+ *   1. p[j] = fl(fl(re re) + fl(im im)): three roundings, no FMA, in every setting of option "exact".
+ *   2. bin(p) = (bits(p) & 0x7fffffff) >> 20, 0 .. 2047: an eighth of an octave of power; +inf is bin 2040.  edge(b) is the float
+ *      whose bits are b << 20.
+ *   3. thr = +inf if ref_bin < 0, else max(fl(ratio edge(ref_bin)), floor) -- from the settings current at this frame.
+ *   4. hit[j] = p[j] > thr (IEEE: a NaN power is no hit).
+ *   5. blank[j] = some hit[m] of this frame with |m - j| <= G, or j <= G - 1 - tail_gap.  Lookahead stops at the frame's end.  A
+ *      blanked sample becomes (+0.0f, +0.0f); every other keeps its bits.
+ *   6. h[bin(p[j])] over all n samples as they arrived; next_ref_bin = min(2040, the smallest b with 65536 (h[0] + .. + h[b]) >=
+ *      rank_q16 n), in 64-bit unsigned; it is ref_bin of frame f + 1.
+ *   7. tail_gap of frame f + 1 = min(65, n - 1 - the last hit's index), 65 without a hit; last_blank = blank[n - 1].
+ * The record of frame f: thr_bits, ref_bin (the one used), next_ref_bin; hits, blanked = the j with hit, with blank; runs = the j
+ * with blank[j] and not blank[j - 1], blank[-1] being last_blank; carry_in = the j with j <= G - 1 - tail_gap.
+ *
+ * sdrx_set_blanker(ctx, cfg): before sdrx_finalize it switches the stage on (cfg == NULL: off again).  After sdrx_finalize it
+ * changes the four settings between two frames (SDRX_ESTATE with submitted frames not yet delivered; the calls in flight are
+ * drained first); SDRX_ESTATE if the stage was not on at sdrx_finalize, or for cfg == NULL.  The state stays: the next frame uses
+ * the old ref_bin and tail_gap under the new settings.
+ * sdrx_get_blanker(ctx, cfg_out, record_out): the settings the last delivered frame ran with and its record (either may be NULL),
+ * under sdrx_get_adc_meter's rules.  sdrx_get_blanker_input(ctx, out_iq, cap): the last frame handed over as it reached the
+ * stage, natural order, up to cap samples, under sdrx_get_resampler_input's rules.
+ * in_frame is unchanged.  sdrx_get_raw, the raw spectrum and the raw watch see the blanked frame (behind a resampler or a front
+ * stage: what those make of it); the ADC meter sees the samples as they arrived.  SDRX_EUNSUPPORTED at sdrx_finalize with a real
+ * first front stage (it reads the caller's words itself: there is no complex frame in front of it).  sdrx_*_shared and
+ * sdrx_*_if_same return SDRX_ESTATE if either context blanks.  Groups do not offer it. */
+typedef struct sdrx_blanker_cfg { /* 32 bytes */
+    float ratio, floor;
+    int32_t rank_q16, guard;
+    int32_t reserved[4];
+} sdrx_blanker_cfg;
+typedef struct sdrx_blanker_record { /* 64 bytes */
+    int64_t frame;
+    uint32_t n_complex, measured;
+    uint32_t thr_bits;
+    int32_t ref_bin, next_ref_bin;
+    uint32_t hits, blanked, runs, carry_in;
+    uint32_t reserved[5];
+} sdrx_blanker_record;
+int sdrx_set_blanker(sdrx_ctx *ctx, const sdrx_blanker_cfg *cfg);
+int sdrx_get_blanker(sdrx_ctx *ctx, sdrx_blanker_cfg *cfg_out, sdrx_blanker_record *record_out);
+int sdrx_get_blanker_input(sdrx_ctx *ctx, float *out_iq, int32_t cap_complex);
+
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);

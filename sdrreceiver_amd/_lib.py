@@ -157,6 +157,18 @@ class FrontInfoC(C.Structure):
                 ("out_frame", C.c_int32), ("reserved", C.c_int32 * 2), ("tw", C.c_double), ("alias_free", C.c_double)]
 
 
+class BlankerCfgC(C.Structure):
+    """struct sdrx_blanker_cfg"""
+    _fields_ = [("ratio", C.c_float), ("floor", C.c_float), ("rank_q16", C.c_int32), ("guard", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class BlankerRecordC(C.Structure):
+    """struct sdrx_blanker_record"""
+    _fields_ = [("frame", C.c_int64), ("n_complex", C.c_uint32), ("measured", C.c_uint32), ("thr_bits", C.c_uint32), ("ref_bin", C.c_int32),
+                ("next_ref_bin", C.c_int32), ("hits", C.c_uint32), ("blanked", C.c_uint32), ("runs", C.c_uint32), ("carry_in", C.c_uint32),
+                ("reserved", C.c_uint32 * 5)]
+
+
 PUBLISH_FN =C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
 
 # every symbol include/sdrx.h declares: (restype, argtypes)
@@ -255,6 +267,9 @@ SYMBOLS = {
     "sdrx_front_design": (_i, [C.c_int32, C.c_double, _vp, C.c_int32, C.POINTER(FrontInfoC)]),
     "sdrx_set_front": (_i, [_vp, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_double]),
     "sdrx_get_front": (_i, [_vp, C.POINTER(FrontInfoC), _vp, C.c_int32]),
+    "sdrx_set_blanker": (_i, [_vp, C.POINTER(BlankerCfgC)]),
+    "sdrx_get_blanker": (_i, [_vp, C.POINTER(BlankerCfgC), C.POINTER(BlankerRecordC)]),
+    "sdrx_get_blanker_input": (_i, [_vp, _vp, C.c_int32]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

@@ -26,6 +26,9 @@
 //                                       front ends whose rate no chain of half-bands reaches; include/sdrx.h "Resampler")
 //   k_front_halfband<MODE> front.hip    (none: sdrx_set_front -- 1 .. 3 half-band decimations by 2 in front of k_resample or level 0; stage 1 may read
 //                                       real int16 / 12-bit samples with the fs/4 translation built in; include/sdrx.h "Front stage")
+//   k_blank, k_blank_step blank.hip     (none: sdrx_set_blanker -- the impulse blanker behind the format conversion and in front of the front stage, the
+//                                       resampler or level 0: samples above ratio x a rank of the previous frame's power histogram, and a guard on
+//                                       either side, become zero; include/sdrx.h "Impulse blanker")
 //   k_mix_decimate        mix.hip       vfo::process mix loop, vfo.cpp:237-245; HalfBandDecimator::decimate, halfbanddecimator.cpp:43-72,
 //                                       with FIR::...HalfBandQueue, dsp.cpp:96-173 (mix_item); option fuse_late: the FIR part of
 //                                       vfo::usb_decimdemod, vfo.cpp:334-356, inside a d = 0 leaf's wave (late_item); option fuse_demod:
@@ -47,6 +50,7 @@
 #include "sdrx_dev.h"
 #include "sdrx_resample.h"
 #include "sdrx_front.h"
+#include "sdrx_blank.h"
 
 #include <type_traits>
 #include <utility>
@@ -59,6 +63,7 @@ namespace sdrx {
 #include "adcmeter.hip"
 #include "resample.hip"
 #include "front.hip"
+#include "blank.hip"
 #include "meter.hip"
 #include "demod.hip"
 #include "mix.hip"

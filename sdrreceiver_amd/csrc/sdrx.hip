@@ -67,6 +67,12 @@ static_assert(sizeof(sdrx_wake_cfg) == 32 && sizeof(WakeCfg) == 32 && offsetof(s
               "sdrx_wake_cfg / sdrx_wake_state ABI layout");
 static_assert(sizeof(sdrx_resampler_info) == 48 && offsetof(sdrx_resampler_info, delay_out_samples) == 32, "sdrx_resampler_info ABI layout");
 static_assert(sizeof(sdrx_front_info) == 48 && offsetof(sdrx_front_info, tw) == 32, "sdrx_front_info ABI layout");
+static_assert(sizeof(sdrx_blanker_cfg) == 32 && sizeof(BlankCfg) == 32 && offsetof(sdrx_blanker_cfg, rank_q16) == offsetof(BlankCfg, rank_q16) &&
+                  offsetof(sdrx_blanker_cfg, guard) == offsetof(BlankCfg, guard) && sizeof(sdrx_blanker_record) == 64 && sizeof(BlankRecord) == 64 &&
+                  offsetof(sdrx_blanker_record, thr_bits) == offsetof(BlankRecord, thr_bits) &&
+                  offsetof(sdrx_blanker_record, next_ref_bin) == offsetof(BlankRecord, next_ref_bin) &&
+                  offsetof(sdrx_blanker_record, carry_in) == offsetof(BlankRecord, carry_in),
+              "sdrx_blanker_cfg / sdrx_blanker_record ABI layout");
 static_assert(sizeof(sdrx_adc_arm) == 40 && sizeof(AdcArm) == 40 && offsetof(sdrx_adc_arm, longest_rail_run) == offsetof(AdcArm, longest_rail_run) &&
                   sizeof(sdrx_adc_meter) == 184 && sizeof(AdcRecord) == 184 && offsetof(sdrx_adc_meter, q) == offsetof(AdcRecord, q) &&
                   offsetof(sdrx_adc_meter, sum_iq) == offsetof(AdcRecord, sum_iq) && offsetof(sdrx_adc_meter, bits) == offsetof(AdcRecord, bits),
@@ -119,6 +125,7 @@ void free_device_state(sdrx_ctx *c)
     c->adc = sdrx_ctx::Adc();
     static_cast<sdrx_ctx::ResamplerDevice &>(c->rs) = sdrx_ctx::ResamplerDevice();
     static_cast<sdrx_ctx::FrontDevice &>(c->fr) = sdrx_ctx::FrontDevice();
+    static_cast<sdrx_ctx::BlankerDevice &>(c->bl) = sdrx_ctx::BlankerDevice();
 }
 
 } // namespace
@@ -1078,6 +1085,80 @@ int sdrx_get_front(sdrx_ctx *c, sdrx_front_info *info, float *taps, int32_t cap)
     return SDRX_OK;
 }
 
+// ---- Impulse blanker (include/sdrx.h; sdrx_blank.h has the rules) ----------------------------------------------------------------
+int sdrx_set_blanker(sdrx_ctx *c, const sdrx_blanker_cfg *cfg)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (c->finalized && !c->bl.on)
+        return fail(c, SDRX_ESTATE, "sdrx_set_blanker: the blanker was not switched on before sdrx_finalize");
+    if (!cfg) {
+        if (c->finalized)
+            return fail(c, SDRX_ESTATE, "sdrx_set_blanker: the blanker is switched off before sdrx_finalize only");
+        c->bl.on = false;
+        return SDRX_OK;
+    }
+    if (const char *why = blank_args(cfg->ratio, cfg->floor, cfg->rank_q16, cfg->guard))
+        return fail(c, SDRX_EINVAL, "sdrx_set_blanker: %s", why);
+    if (c->finalized) { // between two frames: every frame handed over ran with the settings it was launched with
+        if (c->in_flight > 0)
+            return fail(c, SDRX_ESTATE, "sdrx_set_blanker: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+        HIPCHK(c, hipSetDevice(c->device));
+        if (int rc = drain(c))
+            return rc;
+    }
+    c->bl.on = true;
+    c->bl.cfg = BlankCfg{cfg->ratio, cfg->floor, cfg->rank_q16, cfg->guard, {0, 0, 0, 0}};
+    return SDRX_OK;
+}
+
+int sdrx_get_blanker(sdrx_ctx *c, sdrx_blanker_cfg *cfg_out, sdrx_blanker_record *out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_blanker before sdrx_finalize");
+    if (!c->bl.on)
+        return fail(c, SDRX_ESTATE, "sdrx_get_blanker: no blanker set (sdrx_set_blanker before sdrx_finalize)");
+    if (!cfg_out && !out)
+        return fail(c, SDRX_EINVAL, "sdrx_get_blanker: null output pointers");
+    if (int rc = need_delivered(c, "sdrx_get_blanker"))
+        return rc;
+    const int p = c->host_slot;
+    const sdrx_ctx::Blanker::Used &U = c->bl.used[p];
+    if (!U.any || U.frame != c->host_frame)
+        return fail(c, SDRX_EHIP, "sdrx_get_blanker: frame %llu did not pass the blanker", c->host_frame);
+    if (cfg_out)
+        memcpy(cfg_out, &U.cfg, sizeof *cfg_out);
+    if (out) {
+        memcpy(out, c->bl.rec.host<BlankRecord>(p), sizeof *out);
+        if (!out->measured || out->frame != (int64_t)c->host_frame)
+            return fail(c, SDRX_EHIP, "sdrx_get_blanker: the record of frame %llu did not arrive (it names frame %lld)", c->host_frame, (long long)out->frame);
+    }
+    return SDRX_OK;
+}
+
+int sdrx_get_blanker_input(sdrx_ctx *c, float *out, int32_t cap_complex)
+{
+    if (!c || !out)
+        return SDRX_EINVAL;
+    if (!c->bl.on)
+        return fail(c, SDRX_ESTATE, "sdrx_get_blanker_input: no blanker set (sdrx_set_blanker)");
+    if (!c->finalized || c->frame_no == 0)
+        return fail(c, SDRX_ESTATE, "sdrx_get_blanker_input: no frame processed yet");
+    if (c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "sdrx_get_blanker_input: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = drain(c))
+        return rc;
+    const int n = std::min((int)cap_complex, c->in_frame);
+    const size_t total = align_up((size_t)c->in_frame, kChunk);
+    std::vector<float2> t(total);
+    HIPCHK(c, hipMemcpy(t.data(), c->bl.d_stage, total * sizeof(float2), hipMemcpyDeviceToHost));
+    untile(t.data(), out, std::max(n, 0));
+    return SDRX_OK;
+}
+
 int sdrx_get_stream(sdrx_ctx *c, int id, float *out, int max_complex, int *n_ret)
 {
     if (!c || id < 0 || id >= (int)c->nodes.size())
@@ -1328,7 +1409,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
     const size_t raw_bytes = c->d_raw[0].bytes() + c->d_raw_u8[0].bytes(); // (ONE parity of the host-fed frames' buffers: kept for compatibility)
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes() + c->adc.bytes() + c->rs.bytes() + c->fr.bytes());
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes() + c->adc.bytes() + c->rs.bytes() + c->fr.bytes() + c->bl.bytes());
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

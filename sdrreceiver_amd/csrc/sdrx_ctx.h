@@ -402,7 +402,26 @@ struct sdrx_ctx : CtxBuffers {
         std::vector<float> taps; // N floats, prototype order
         double tw = 0;           // the built-in design's transition width (0 for the caller's own taps)
     } fr;
-    bool staged() const { return rs.on || fr.on; } // the ingest kernels write a staging buffer, not the tree's raw frame
+    // Impulse blanker (sdrx_set_blanker, blank.hip): k_blank between the ingest kernels and what they wrote before.
+    // The setting is the host's; what finalize allocates with it: the staging frame the ingest kernels then write (tile layout),
+    // the device state (reference bin, carry, the frame's histogram and counters) and the record of frame f (`rec`).  `used`
+    // says per frame parity which frame the slot was written for and under which settings.
+    struct BlankerDevice { // what free_device_state releases
+        DevBuf<float2> d_stage;
+        DevBuf<BlankState> d_state;
+        Records rec;
+        size_t bytes() const { return d_stage.bytes() + d_state.bytes() + 2 * rec.bytes(); } // device memory it holds
+    };
+    struct Blanker : BlankerDevice {
+        bool on = false; // set before sdrx_finalize
+        BlankCfg cfg{};  // the settings of the next frame
+        struct Used {
+            unsigned long long frame = 0;
+            bool any = false;
+            BlankCfg cfg{};
+        } used[2];
+    } bl;
+    bool staged() const { return rs.on || fr.on || bl.on; } // the ingest kernels write a staging buffer, not the tree's raw frame
     int in_frame = 0; // samples of an incoming frame: root_frame, or with a resampler rs.plan.n_in; times 2^stages with a front stage
 
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot

@@ -1118,6 +1118,35 @@ int front_setup(sdrx_ctx *c)
     return SDRX_OK;
 }
 
+// Impulse blanker: why this context cannot have it, or nothing ...
+int blank_plan(sdrx_ctx *c)
+{
+    if (c->bl.on && c->fr.on && c->fr.plan.real)
+        return fail(c, SDRX_EUNSUPPORTED, "blanker: a real first front stage (sdrx_set_front with real_input = 1) reads the caller's words itself -- there is "
+                                          "no complex frame in front of it to blank");
+    return SDRX_OK;
+}
+
+// ... and what k_blank needs on the device: the staging frame the ingest kernels write (whole tiles plus one, zeroed), the state
+// (no reference yet, no carry, an empty histogram) and the record buffers of both frame parities.  All of it or (the caller
+// releases) none.
+int blank_setup(sdrx_ctx *c)
+{
+    for (sdrx_ctx::Blanker::Used &u : c->bl.used)
+        u = sdrx_ctx::Blanker::Used();
+    if (!c->bl.on)
+        return SDRX_OK;
+    const size_t stage = align_up((size_t)c->in_frame, kChunk) + kChunk;
+    if (c->bl.d_stage.alloc(stage) != hipSuccess || c->bl.d_state.alloc(1) != hipSuccess || c->bl.rec.alloc(sizeof(BlankRecord)) != hipSuccess)
+        return fail(c, SDRX_ENOMEM, "sdrx_finalize: no device memory for the blanker");
+    HIPCHK(c, hipMemsetAsync(c->bl.d_stage, 0, stage * sizeof(float2), c->st.stream));
+    std::vector<BlankState> st(1);
+    memset(st.data(), 0, sizeof(BlankState));
+    st[0].ref_bin = -1, st[0].tail_gap = kBlankNoHit, st[0].last_hit = -1;
+    HIPCHK(c, hipMemcpy(c->bl.d_state, st.data(), sizeof(BlankState), hipMemcpyHostToDevice));
+    return SDRX_OK;
+}
+
 int finalize_impl(sdrx_ctx *c)
 {
     if (int rc = derive_nodes(c))
@@ -1125,6 +1154,8 @@ int finalize_impl(sdrx_ctx *c)
     if (int rc = resample_plan_frames(c))
         return rc;
     if (int rc = front_plan_frames(c))
+        return rc;
+    if (int rc = blank_plan(c))
         return rc;
     Built B;
     plan_buffers(c, B);
@@ -1147,6 +1178,8 @@ int finalize_impl(sdrx_ctx *c)
     if (int rc = resample_setup(c))
         return rc;
     if (int rc = front_setup(c))
+        return rc;
+    if (int rc = blank_setup(c))
         return rc;
     catchup_setup(c, B);
     c->sq.preroll_fused = false;

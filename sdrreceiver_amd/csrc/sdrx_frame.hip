@@ -101,6 +101,8 @@ ParkArg<PARK> park_arg(const sdrx_ctx *c, size_t first)
 // buffer in front of it.
 float4 *ingest_dest(sdrx_ctx *c)
 {
+    if (c->bl.on) // (the blanker's staging frame: k_blank writes what this returned without it, blank_launch)
+        return reinterpret_cast<float4 *>(c->bl.d_stage.get());
     if (c->fr.on) // (complex front stage: its first stage's input frame; a real one converts the caller's words itself)
         return reinterpret_cast<float4 *>(c->fr.d_in[0].get());
     return reinterpret_cast<float4 *>(c->rs.on ? c->rs.d_stage.get() : c->d_raw_tiled.get());
@@ -151,6 +153,25 @@ void front_launch(sdrx_ctx *c, const void *real_words = nullptr, int fmt = -1)
         auto k = !real ? k_front_halfband<kFrontComplex> : fmt == SDRX_FMT_RS16 ? k_front_halfband<kFrontRS16> : k_front_halfband<kFrontRU12>;
         hipLaunchKernelGGL(k, dim3((A.n_out + kFrTile - 1) / kFrTile), dim3(256), 0, c->st.stream, A);
     }
+}
+
+// Impulse blanker: k_blank and k_blank_step for the next frame (c->frame_no), on the context's stream behind the ingest kernel that
+// staged it, inside that kernel's KIND_INGEST bracket and in front of front_launch.  Out of place: from the blanker's staging
+// frame to what ingest_dest returned without it.  The state chains on the device in stream order.  Off: nothing.
+void blank_launch(sdrx_ctx *c)
+{
+    if (!c->bl.on)
+        return;
+    const int p = (int)(c->frame_no & 1ull);
+    const BlankCfg &B = c->bl.cfg;
+    float2 *out = c->fr.on ? c->fr.d_in[0].get() : c->rs.on ? c->rs.d_stage.get() : c->d_raw_tiled.get();
+    hipLaunchKernelGGL(k_blank, dim3(blank_workgroups(c->in_frame)), dim3(kBlankThreads), 0, c->st.stream, reinterpret_cast<const float4 *>(c->bl.d_stage.get()),
+                       reinterpret_cast<float4 *>(out), c->in_frame, B.ratio, B.floor, B.guard, c->bl.d_state.get());
+    hipLaunchKernelGGL(k_blank_step, dim3(1), dim3(kBlankThreads), 0, c->st.stream, c->bl.d_state.get(), c->bl.rec.dev<BlankRecord>(p), (long long)c->frame_no,
+                       c->in_frame, B.rank_q16, B.guard, B.ratio, B.floor);
+    c->bl.used[p].frame = c->frame_no;
+    c->bl.used[p].any = true;
+    c->bl.used[p].cfg = B;
 }
 
 int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st); // (sdrx_delivery.hip)
@@ -593,6 +614,7 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         else
             hipLaunchKernelGGL(k_ingest_samples<SDRX_FMT_CU8>, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream,
                                reinterpret_cast<const unsigned *>(raw), ingest_dest(c), n_pairs);
+        blank_launch(c);
         front_launch(c);
         resample_launch(c);
         raw_mode = kRawTiled;
@@ -740,7 +762,7 @@ int check_frame_call(sdrx_ctx *c, const char *what, const void *ptr, int n_compl
     if (n_complex != c->in_frame && c->rs.on)
         return fail(c, SDRX_EINVAL, "frame of %d samples: with the resampler %d -> %d S/s a frame has %d (for the VFOs' %d)", n_complex, c->rs.plan.fs_in,
                     c->rs.plan.fs_out, c->in_frame, c->root_frame);
-    if (n_complex != c->root_frame && !c->staged())
+    if (n_complex != c->root_frame && !c->rs.on && !c->fr.on)
         return fail(c, SDRX_EINVAL, "frame of %d samples, VFOs were initialised for %d (vfo::init samplesPerBuffer)", n_complex,
                     c->root_frame);
     if (sync_call && c->in_flight > 0)
@@ -922,6 +944,7 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         }
         hipLaunchKernelGGL(K.apply, dim3((words + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), Ap,
                            ingest_dest(c), n_complex, c->dc.work_stride);
+        blank_launch(c);
         front_launch(c);
         resample_launch(c);
         mode = kRawTiled;
@@ -933,14 +956,16 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
                            c->dc.d_tab, sums);
         hipLaunchKernelGGL(K.dc_fast, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
                            ingest_dest(c), n_complex, c->dc.d_state + 2 * par, c->dc.d_state + 2 * (par ^ 1), c->dc.d_tab, sums);
+        blank_launch(c);
         front_launch(c);
         resample_launch(c);
         mode = kRawTiled;
-    } else if (fmt != SDRX_FMT_CU8 || c->staged()) { // (resampler, front stage: they read the tile layout, so bytes take the pass too)
+    } else if (fmt != SDRX_FMT_CU8 || c->staged()) { // (resampler, front stage, blanker: they read the tile layout, so bytes take the pass too)
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
         const int n_pairs = n_complex / 2;
         hipLaunchKernelGGL(K.ingest, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
                            ingest_dest(c), n_pairs);
+        blank_launch(c);
         front_launch(c);
         resample_launch(c);
         mode = kRawTiled;
@@ -1018,7 +1043,7 @@ static int submit_shared(sdrx_ctx *c, sdrx_ctx *src, const char *what, bool sync
     if (!c || !src || c == src)
         return c ? fail(c, SDRX_EINVAL, "%s: needs another context as the source", what) : SDRX_EINVAL;
     if (c->staged() || src->staged())
-        return fail(c, SDRX_ESTATE, "%s: a context with a resampler or a front stage (sdrx_set_resampler, sdrx_set_front) shares no frames", what);
+        return fail(c, SDRX_ESTATE, "%s: a context with a resampler, a front stage or a blanker (sdrx_set_resampler, sdrx_set_front, sdrx_set_blanker) shares no frames", what);
     if (!src->finalized || src->frame_no == 0 || (src->last_raw != kRawF32 && src->last_raw != kRawU8))
         return fail(c, SDRX_ESTATE, "%s: the source context has staged no host frame (floats or bytes without DC removal) yet", what);
     if (src->device != c->device)

@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, agc as _agc, drift as _drift, front as _front, ingest, meter, resample as _resample, scan as _scan, squelch as _squelch, wake as _wake, watch as _watch
+from . import _lib, agc as _agc, blank as _blank, drift as _drift, front as _front, ingest, meter, resample as _resample, scan as _scan, squelch as _squelch, wake as _wake, watch as _watch
 from .topology import Topology, VfoDesc
 
 
@@ -313,7 +313,10 @@ class Receiver(_LeafCalls):
                  squelch_auto: bool = False, park: bool = False, watch: bool = False, catchup: bool = False,
                  agc: bool = False, wake: bool = False, adc_meter: bool = False, input_rate: int | None = None,
                  resample_taps=32, resample_atten_db: float = 80.0, front_stages: int = 0, front_real: bool = False,
-                 front_taps=15, front_atten_db: float = 80.0):
+                 front_taps=15, front_atten_db: float = 80.0, blanker=None):
+        # blanker: the impulse blanker's settings (sdrreceiver_amd.blank.Cfg, or a (ratio, floor, rank_q16, guard) tuple) -- the
+        # stage zeroes pulses in the frame behind the format conversion and in front of everything else; None: off.
+        self._blanker = None if blanker is None else _blank.Cfg(*blanker) if isinstance(blanker, (tuple, list)) else blanker
         # front_stages: 1 .. 3 half-band decimations by 2 in front of the resampler (or of level 0) -- frames then have
         # front["in_frame"] samples (sdrreceiver_amd.front).  front_real: the first stage reads REAL samples (process_fmt with
         # fmt=ingest.RS16 or ingest.RU12).  front_taps: K of the built-in design (N = 4 K + 3 taps) with front_atten_db, or the
@@ -408,6 +411,8 @@ class Receiver(_LeafCalls):
             self._set_resampler()
         if self._front_stages:
             self._set_front()
+        if self._blanker is not None:
+            self.set_blanker(self._blanker)
         self._chk(self.L.sdrx_finalize(self.h))
         self.finalized = True
 
@@ -448,6 +453,39 @@ class Receiver(_LeafCalls):
         d = _front.info_dict(info)
         d["taps"] = taps[: d["N"]].copy()
         return d
+
+    def set_blanker(self, cfg) -> None:
+        """The impulse blanker's settings (``sdrx_set_blanker``): before :meth:`finalize` this switches the stage on (None: off
+        again); afterwards it changes ratio, floor, rank_q16 and guard between two frames."""
+        if cfg is None:
+            self._chk(self.L.sdrx_set_blanker(self.h, None))
+            self._blanker = None
+            return
+        cfg = _blank.Cfg(*cfg) if isinstance(cfg, (tuple, list)) else cfg
+        c = _lib.BlankerCfgC(float(cfg.ratio), float(cfg.floor), int(cfg.rank_q16), int(cfg.guard))
+        self._chk(self.L.sdrx_set_blanker(self.h, C.byref(c)))
+        self._blanker = cfg
+
+    @property
+    def blanker(self) -> dict | None:
+        """The blanker's record of the last delivered frame (``sdrx_blanker_record`` as a dict: ``thr_bits``, ``ref_bin``,
+        ``next_ref_bin``, ``hits``, ``blanked``, ``runs``, ``carry_in``) with ``cfg``, the settings that frame ran with; None
+        without ``blanker``."""
+        if self._blanker is None:
+            return None
+        cfg, rec = _lib.BlankerCfgC(), _lib.BlankerRecordC()
+        self._chk(self.L.sdrx_get_blanker(self.h, C.byref(cfg), C.byref(rec)))
+        d = _blank.record_dict(rec)
+        d["cfg"] = _blank.cfg_of(cfg)
+        return d
+
+    def blanker_input(self) -> np.ndarray:
+        """The last frame as it reached the blanker: after the format conversion and the DC-bias removal, natural order."""
+        n = self.front["in_frame"] if self._front_stages else self.resampler["in_frame"] if self._input_rate else \
+            next(d.samples_per_buffer for d in self.descs if d.parent < 0)
+        out = np.zeros(2 * max(n, 1), np.float32)
+        self._chk(self.L.sdrx_get_blanker_input(self.h, out.ctypes.data, n))
+        return out[: 2 * n].view(np.complex64).copy()
 
     @property
     def resampler(self) -> dict | None:
