@@ -5,7 +5,7 @@
 //   sdrx_demo <profile.ini> --dump              descriptors as JSON lines (no GPU needed)
 //   sdrx_demo <profile.ini> --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ]
 //                                   [--front-stages N [--front-real] [--front-taps K]] [--blanker RATIO,GUARD[,FLOOR[,RANK]]]
-//                                   [--fft TOPIC] [--devices 0,1,...]
+//                                   [--iq-balance MU,MINPOWER[,C0,D0]] [--fft TOPIC] [--devices 0,1,...]
 //                                               N synthetic LCG frames; one line per published
 //                                               message: frame topic rate bytes fnv1a64(payload)
 //                                               --u8 feeds them as dongle bytes, --format as integer samples of that
@@ -26,6 +26,11 @@
 //                                               RANK 32768 -- the median -- unless given); one more line per frame behind its
 //                                               messages (in front of the adc line),
 //                                               blanker frame thr_bits ref_bin next_ref_bin hits blanked runs carry_in
+//                                               --iq-balance MU,MINPOWER[,C0,D0]: the IQ balance correction on the device (C0 0,
+//                                               D0 1 unless given); one more line per frame behind its messages (in front of
+//                                               the blanker line),
+//                                               iq frame measured adapted rejected c_bits d_bits next_c_bits next_d_bits
+//                                                  sum_i sum_q sum_iq sum_ii sum_qq
 #include <cinttypes>
 #include <cstdio>
 #include <iostream>
@@ -48,7 +53,7 @@ static uint64_t fnv1a(const void *p, size_t n)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ] [--front-stages N [--front-real] [--front-taps K]] [--blanker RATIO,GUARD[,FLOOR[,RANK]]] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ] [--front-stages N [--front-real] [--front-taps K]] [--blanker RATIO,GUARD[,FLOOR[,RANK]]] [--iq-balance MU,MINPOWER[,C0,D0]] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
         return 2;
     }
     try {
@@ -81,6 +86,8 @@ int main(int argc, char **argv)
         bool front_real = false, blanker = false;
         float bl_ratio = 0, bl_floor = 0;
         int bl_guard = 0, bl_rank = 32768;
+        bool iq_balance = false;
+        float iq_mu = 0, iq_min_power = 0, iq_c0 = 0, iq_d0 = 1;
         std::string fft_topic;
         std::vector<int> devices;
         for (int a = 4; a < argc; ++a) {
@@ -107,6 +114,11 @@ int main(int argc, char **argv)
                 if (got < 2)
                     throw std::runtime_error("--blanker takes RATIO,GUARD[,FLOOR[,RANK]]");
                 blanker = true;
+            } else if (std::string(argv[a]) == "--iq-balance" && a + 1 < argc) {
+                const int got = std::sscanf(argv[++a], "%f,%f,%f,%f", &iq_mu, &iq_min_power, &iq_c0, &iq_d0);
+                if (got != 2 && got != 4)
+                    throw std::runtime_error("--iq-balance takes MU,MINPOWER[,C0,D0]");
+                iq_balance = true;
             } else if (std::string(argv[a]) == "--fft" && a + 1 < argc)
                 fft_topic = argv[++a];
             else if (std::string(argv[a]) == "--devices" && a + 1 < argc) { // one tree sharded over several GPUs
@@ -156,6 +168,8 @@ int main(int argc, char **argv)
             radio.setFront(front_stages, front_real, front_K);
         if (blanker)
             radio.setBlanker(bl_ratio, bl_guard, bl_floor, bl_rank);
+        if (iq_balance)
+            radio.setIqBalance(iq_mu, iq_min_power, iq_c0, iq_d0);
         if (input_rate > 0 || front_stages > 0)
             radio.start();
         if (input_rate > 0) {
@@ -199,6 +213,11 @@ int main(int argc, char **argv)
                 radio.demodBytes(bytes.data(), n_frame);
             else
                 radio.demodData(iq.data(), (int)iq.size());
+            if (iq_balance) {
+                const sdrx_iq_record q = radio.iqBalance();
+                std::printf("iq %d %u %u %u %08x %08x %08x %08x %" PRId64 " %" PRId64 " %" PRId64 " %" PRIu64 " %" PRIu64 "\n", frame_no, q.measured, q.adapted,
+                            q.rejected, q.c_bits, q.d_bits, q.next_c_bits, q.next_d_bits, q.sum_i, q.sum_q, q.sum_iq, q.sum_ii, q.sum_qq);
+            }
             if (blanker) {
                 const sdrx_blanker_record b = radio.blanker();
                 std::printf("blanker %d %08x %d %d %u %u %u %u\n", frame_no, b.thr_bits, b.ref_bin, b.next_ref_bin, b.hits, b.blanked, b.runs, b.carry_in);

@@ -212,6 +212,28 @@ public:
         check(sdrx_get_blanker(ctx_, nullptr, &r), "sdrx_get_blanker");
         return r;
     }
+    // The IQ balance correction on the device (include/sdrx.h "IQ balance"; no counterpart in the reference): Q' = c I + d Q behind
+    // the format conversion and the DC removal, the pair moved by `mu` times a Newton step once per frame that holds at least
+    // `min_power` (mu = 0: held).  Before the first frame it switches the stage on, starting from (c0, d0); afterwards it changes
+    // mu and min_power between two frames, and with load = true writes (c0, d0) as the pair of the next frame.  One device only.
+    void setIqBalance(float mu, float min_power, float c0 = 0.0f, float d0 = 1.0f, bool load = false)
+    {
+        if (grp_)
+            throw std::runtime_error("sdrj: the IQ balance correction (setIqBalance) is not offered on several devices");
+        iq_cfg_ = sdrx_iq_cfg{mu, min_power, c0, d0, load ? SDRX_IQ_LOAD : 0u, {0, 0, 0}};
+        if (ctx_)
+            check(sdrx_set_iq_balance(ctx_, &iq_cfg_), "sdrx_set_iq_balance");
+        iq_on_ = true;
+    }
+    // ... and its record of the last delivered frame: measured / adapted / rejected, the pair used, the next one, the five sums
+    sdrx_iq_record iqBalance()
+    {
+        if (!ctx_ || !iq_on_)
+            throw std::runtime_error("sdrj::iqBalance: no IQ balance correction set, or not started");
+        sdrx_iq_record r;
+        check(sdrx_get_iq_balance(ctx_, nullptr, &r), "sdrx_get_iq_balance");
+        return r;
+    }
     // sdrj.cpp:84-101: the raw spectrum is selected by the topic "Main"; any selection restarts
     // the every-4th-call counter of demodData (sdrj.cpp:296-303)
     void fftVFOSlot(const std::string &topic)
@@ -232,6 +254,8 @@ public:
             throw std::runtime_error("sdrj: the front stage (setFront) is not offered on several devices");
         if (devices_.size() > 1 && bl_on_)
             throw std::runtime_error("sdrj: the blanker (setBlanker) is not offered on several devices");
+        if (devices_.size() > 1 && iq_on_)
+            throw std::runtime_error("sdrj: the IQ balance correction (setIqBalance) is not offered on several devices");
         if (devices_.size() > 1) {
             check(sdrx_group_create(&grp_, devices_.data(), (int)devices_.size()), "sdrx_group_create");
             for (auto &kv : options_)
@@ -259,6 +283,8 @@ public:
             check(sdrx_set_front(ctx_, fr_real_ ? 1 : 0, fr_stages_, nullptr, fr_K_, fr_atten_), "sdrx_set_front");
         if (bl_on_)
             check(sdrx_set_blanker(ctx_, &bl_cfg_), "sdrx_set_blanker");
+        if (iq_on_)
+            check(sdrx_set_iq_balance(ctx_, &iq_cfg_), "sdrx_set_iq_balance");
         check(sdrx_set_publish_callback(ctx_, &sdrj::trampoline, this), "sdrx_set_publish_callback");
         check(sdrx_finalize(ctx_), "sdrx_finalize");
     }
@@ -645,6 +671,8 @@ private:
     double fr_atten_ = 80.0;
     bool bl_on_ = false; // setBlanker
     sdrx_blanker_cfg bl_cfg_{};
+    bool iq_on_ = false; // setIqBalance
+    sdrx_iq_cfg iq_cfg_{};
 };
 
 // ------------------------------------------------------------------------------------------ INI

@@ -169,6 +169,18 @@ class BlankerRecordC(C.Structure):
                 ("reserved", C.c_uint32 * 5)]
 
 
+class IqCfgC(C.Structure):
+    """struct sdrx_iq_cfg"""
+    _fields_ = [("mu", C.c_float), ("min_power", C.c_float), ("c0", C.c_float), ("d0", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class IqRecordC(C.Structure):
+    """struct sdrx_iq_record"""
+    _fields_ = [("frame", C.c_int64), ("n_complex", C.c_uint32), ("measured", C.c_uint32), ("adapted", C.c_uint32), ("rejected", C.c_uint32),
+                ("c_bits", C.c_uint32), ("d_bits", C.c_uint32), ("next_c_bits", C.c_uint32), ("next_d_bits", C.c_uint32), ("sum_i", C.c_int64),
+                ("sum_q", C.c_int64), ("sum_iq", C.c_int64), ("sum_ii", C.c_uint64), ("sum_qq", C.c_uint64), ("reserved", C.c_uint32 * 4)]
+
+
 PUBLISH_FN =C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
 
 # every symbol include/sdrx.h declares: (restype, argtypes)
@@ -270,6 +282,8 @@ SYMBOLS = {
     "sdrx_set_blanker": (_i, [_vp, C.POINTER(BlankerCfgC)]),
     "sdrx_get_blanker": (_i, [_vp, C.POINTER(BlankerCfgC), C.POINTER(BlankerRecordC)]),
     "sdrx_get_blanker_input": (_i, [_vp, _vp, C.c_int32]),
+    "sdrx_set_iq_balance": (_i, [_vp, C.POINTER(IqCfgC)]),
+    "sdrx_get_iq_balance": (_i, [_vp, C.POINTER(IqCfgC), C.POINTER(IqRecordC)]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

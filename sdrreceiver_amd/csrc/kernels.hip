@@ -29,6 +29,9 @@
 //   k_blank, k_blank_step blank.hip     (none: sdrx_set_blanker -- the impulse blanker behind the format conversion and in front of the front stage, the
 //                                       resampler or level 0: samples above ratio x a rank of the previous frame's power histogram, and a guard on
 //                                       either side, become zero; include/sdrx.h "Impulse blanker")
+//   k_iqbal, k_iqbal_step iqbal.hip     (none: sdrx_set_iq_balance -- the IQ balance correction behind the format conversion and the DC removal, in front
+//                                       of the blanker: Q' = c I + d Q in place, and the pair (c, d) moved from exact integer statistics of each
+//                                       frame's output; include/sdrx.h "IQ balance")
 //   k_mix_decimate        mix.hip       vfo::process mix loop, vfo.cpp:237-245; HalfBandDecimator::decimate, halfbanddecimator.cpp:43-72,
 //                                       with FIR::...HalfBandQueue, dsp.cpp:96-173 (mix_item); option fuse_late: the FIR part of
 //                                       vfo::usb_decimdemod, vfo.cpp:334-356, inside a d = 0 leaf's wave (late_item); option fuse_demod:
@@ -51,6 +54,7 @@
 #include "sdrx_resample.h"
 #include "sdrx_front.h"
 #include "sdrx_blank.h"
+#include "sdrx_iqbal.h"
 
 #include <type_traits>
 #include <utility>
@@ -64,6 +68,7 @@ namespace sdrx {
 #include "resample.hip"
 #include "front.hip"
 #include "blank.hip"
+#include "iqbal.hip"
 #include "meter.hip"
 #include "demod.hip"
 #include "mix.hip"

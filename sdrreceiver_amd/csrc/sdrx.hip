@@ -73,6 +73,11 @@ static_assert(sizeof(sdrx_blanker_cfg) == 32 && sizeof(BlankCfg) == 32 && offset
                   offsetof(sdrx_blanker_record, next_ref_bin) == offsetof(BlankRecord, next_ref_bin) &&
                   offsetof(sdrx_blanker_record, carry_in) == offsetof(BlankRecord, carry_in),
               "sdrx_blanker_cfg / sdrx_blanker_record ABI layout");
+static_assert(sizeof(sdrx_iq_cfg) == 32 && sizeof(IqCfg) == 32 && offsetof(sdrx_iq_cfg, d0) == offsetof(IqCfg, d0) && offsetof(sdrx_iq_cfg, flags) == offsetof(IqCfg, flags) &&
+                  sizeof(sdrx_iq_record) == 96 && sizeof(IqRecord) == 96 && offsetof(sdrx_iq_record, rejected) == offsetof(IqRecord, rejected) &&
+                  offsetof(sdrx_iq_record, next_d_bits) == offsetof(IqRecord, next_d_bits) && offsetof(sdrx_iq_record, sum_i) == offsetof(IqRecord, sum_i) &&
+                  offsetof(sdrx_iq_record, sum_qq) == offsetof(IqRecord, sum_qq) && sizeof(IqState) == 64 && SDRX_IQ_LOAD == kIqLoad,
+              "sdrx_iq_cfg / sdrx_iq_record ABI layout");
 static_assert(sizeof(sdrx_adc_arm) == 40 && sizeof(AdcArm) == 40 && offsetof(sdrx_adc_arm, longest_rail_run) == offsetof(AdcArm, longest_rail_run) &&
                   sizeof(sdrx_adc_meter) == 184 && sizeof(AdcRecord) == 184 && offsetof(sdrx_adc_meter, q) == offsetof(AdcRecord, q) &&
                   offsetof(sdrx_adc_meter, sum_iq) == offsetof(AdcRecord, sum_iq) && offsetof(sdrx_adc_meter, bits) == offsetof(AdcRecord, bits),
@@ -126,6 +131,7 @@ void free_device_state(sdrx_ctx *c)
     static_cast<sdrx_ctx::ResamplerDevice &>(c->rs) = sdrx_ctx::ResamplerDevice();
     static_cast<sdrx_ctx::FrontDevice &>(c->fr) = sdrx_ctx::FrontDevice();
     static_cast<sdrx_ctx::BlankerDevice &>(c->bl) = sdrx_ctx::BlankerDevice();
+    static_cast<sdrx_ctx::IqDevice &>(c->iq) = sdrx_ctx::IqDevice();
 }
 
 } // namespace
@@ -1159,6 +1165,62 @@ int sdrx_get_blanker_input(sdrx_ctx *c, float *out, int32_t cap_complex)
     return SDRX_OK;
 }
 
+// ---- IQ balance correction (include/sdrx.h; sdrx_iqbal.h has the rules) ---------------------------------------------------------
+int sdrx_set_iq_balance(sdrx_ctx *c, const sdrx_iq_cfg *cfg)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (c->finalized && !c->iq.on)
+        return fail(c, SDRX_ESTATE, "sdrx_set_iq_balance: the IQ balance correction was not switched on before sdrx_finalize");
+    if (!cfg) {
+        if (c->finalized)
+            return fail(c, SDRX_ESTATE, "sdrx_set_iq_balance: the IQ balance correction is switched off before sdrx_finalize only");
+        c->iq.on = false;
+        return SDRX_OK;
+    }
+    if (const char *why = iq_args(cfg->mu, cfg->min_power, cfg->c0, cfg->d0, cfg->flags, cfg->reserved))
+        return fail(c, SDRX_EINVAL, "sdrx_set_iq_balance: %s", why);
+    if (c->finalized) { // between two frames: every frame handed over ran with the settings it was launched with
+        if (c->in_flight > 0)
+            return fail(c, SDRX_ESTATE, "sdrx_set_iq_balance: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+        HIPCHK(c, hipSetDevice(c->device));
+        if (int rc = drain(c))
+            return rc;
+        if (cfg->flags & SDRX_IQ_LOAD) // the pair of the next frame, in stream order
+            hipLaunchKernelGGL(k_iqbal_load, dim3(1), dim3(64), 0, c->st.stream, c->iq.d_state.get(), cfg->c0, cfg->d0);
+    }
+    const bool keep = c->finalized && !(cfg->flags & SDRX_IQ_LOAD); // (c0, d0 stay what was last written into the state)
+    c->iq.cfg = IqCfg{cfg->mu, cfg->min_power, keep ? c->iq.cfg.c0 : cfg->c0, keep ? c->iq.cfg.d0 : cfg->d0, cfg->flags, {0, 0, 0}};
+    c->iq.on = true;
+    return SDRX_OK;
+}
+
+int sdrx_get_iq_balance(sdrx_ctx *c, sdrx_iq_cfg *cfg_out, sdrx_iq_record *out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_iq_balance before sdrx_finalize");
+    if (!c->iq.on)
+        return fail(c, SDRX_ESTATE, "sdrx_get_iq_balance: no IQ balance correction set (sdrx_set_iq_balance before sdrx_finalize)");
+    if (!cfg_out && !out)
+        return fail(c, SDRX_EINVAL, "sdrx_get_iq_balance: null output pointers");
+    if (int rc = need_delivered(c, "sdrx_get_iq_balance"))
+        return rc;
+    const int p = c->host_slot;
+    const sdrx_ctx::Iq::Used &U = c->iq.used[p];
+    if (!U.any || U.frame != c->host_frame)
+        return fail(c, SDRX_EHIP, "sdrx_get_iq_balance: frame %llu did not pass the IQ balance correction", c->host_frame);
+    if (cfg_out)
+        memcpy(cfg_out, &U.cfg, sizeof *cfg_out);
+    if (out) {
+        memcpy(out, c->iq.rec.host<IqRecord>(p), sizeof *out);
+        if (!out->n_complex || out->frame != (int64_t)c->host_frame) // (a slot never written holds zeros)
+            return fail(c, SDRX_EHIP, "sdrx_get_iq_balance: the record of frame %llu did not arrive (it names frame %lld)", c->host_frame, (long long)out->frame);
+    }
+    return SDRX_OK;
+}
+
 int sdrx_get_stream(sdrx_ctx *c, int id, float *out, int max_complex, int *n_ret)
 {
     if (!c || id < 0 || id >= (int)c->nodes.size())
@@ -1409,7 +1471,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
     const size_t raw_bytes = c->d_raw[0].bytes() + c->d_raw_u8[0].bytes(); // (ONE parity of the host-fed frames' buffers: kept for compatibility)
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes() + c->adc.bytes() + c->rs.bytes() + c->fr.bytes() + c->bl.bytes());
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes() + c->adc.bytes() + c->rs.bytes() + c->fr.bytes() + c->bl.bytes() + c->iq.bytes());
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

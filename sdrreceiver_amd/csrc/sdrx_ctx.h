@@ -422,6 +422,26 @@ struct sdrx_ctx : CtxBuffers {
         } used[2];
     } bl;
     bool staged() const { return rs.on || fr.on || bl.on; } // the ingest kernels write a staging buffer, not the tree's raw frame
+    // IQ balance correction (sdrx_set_iq_balance, iqbal.hip): k_iqbal in place on what the ingest kernels wrote, in
+    // front of the blanker.  The setting is the host's; what finalize allocates with it: the device state (the pair and the five
+    // accumulators of the frame in flight) and the record of frame f (`rec`).  No staging frame: staged() is not its business,
+    // but every frame, cf32 ones included, then takes the ingest pass into the tile layout (tiled_ingest).  `used` says per frame
+    // parity which frame the slot was written for and under which settings.
+    struct IqDevice { // what free_device_state releases
+        DevBuf<IqState> d_state;
+        Records rec;
+        size_t bytes() const { return d_state.bytes() + 2 * rec.bytes(); } // device memory it holds
+    };
+    struct Iq : IqDevice {
+        bool on = false; // set before sdrx_finalize
+        IqCfg cfg{};     // the settings of the next frame (c0, d0: what sdrx_finalize or the last SDRX_IQ_LOAD wrote)
+        struct Used {
+            unsigned long long frame = 0;
+            bool any = false;
+            IqCfg cfg{};
+        } used[2];
+    } iq;
+    bool tiled_ingest() const { return staged() || iq.on; } // every frame goes through an ingest kernel into the tile layout
     int in_frame = 0; // samples of an incoming frame: root_frame, or with a resampler rs.plan.n_in; times 2^stages with a front stage
 
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot

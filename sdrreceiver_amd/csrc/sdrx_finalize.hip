@@ -1147,6 +1147,32 @@ int blank_setup(sdrx_ctx *c)
     return SDRX_OK;
 }
 
+// IQ balance correction: why this context cannot have it, or nothing ...
+int iqbal_plan(sdrx_ctx *c)
+{
+    if (c->iq.on && c->fr.on && c->fr.plan.real)
+        return fail(c, SDRX_EUNSUPPORTED, "IQ balance: a real first front stage (sdrx_set_front with real_input = 1) reads the caller's words itself -- there "
+                                          "is no complex frame in front of it, and I/Q made digitally has no imbalance");
+    return SDRX_OK;
+}
+
+// ... and what k_iqbal needs on the device: the state (the pair c0, d0 and empty accumulators) and the record buffers of both
+// frame parities.  All of it or (the caller releases) none.
+int iqbal_setup(sdrx_ctx *c)
+{
+    for (sdrx_ctx::Iq::Used &u : c->iq.used)
+        u = sdrx_ctx::Iq::Used();
+    if (!c->iq.on)
+        return SDRX_OK;
+    if (c->iq.d_state.alloc(1) != hipSuccess || c->iq.rec.alloc(sizeof(IqRecord)) != hipSuccess)
+        return fail(c, SDRX_ENOMEM, "sdrx_finalize: no device memory for the IQ balance correction");
+    IqState st;
+    memset(&st, 0, sizeof st);
+    st.c = c->iq.cfg.c0, st.d = c->iq.cfg.d0;
+    HIPCHK(c, hipMemcpy(c->iq.d_state, &st, sizeof st, hipMemcpyHostToDevice));
+    return SDRX_OK;
+}
+
 int finalize_impl(sdrx_ctx *c)
 {
     if (int rc = derive_nodes(c))
@@ -1156,6 +1182,8 @@ int finalize_impl(sdrx_ctx *c)
     if (int rc = front_plan_frames(c))
         return rc;
     if (int rc = blank_plan(c))
+        return rc;
+    if (int rc = iqbal_plan(c))
         return rc;
     Built B;
     plan_buffers(c, B);
@@ -1180,6 +1208,8 @@ int finalize_impl(sdrx_ctx *c)
     if (int rc = front_setup(c))
         return rc;
     if (int rc = blank_setup(c))
+        return rc;
+    if (int rc = iqbal_setup(c))
         return rc;
     catchup_setup(c, B);
     c->sq.preroll_fused = false;

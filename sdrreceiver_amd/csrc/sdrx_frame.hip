@@ -174,6 +174,23 @@ void blank_launch(sdrx_ctx *c)
     c->bl.used[p].cfg = B;
 }
 
+// IQ balance correction: k_iqbal and k_iqbal_step for the next frame (c->frame_no), on the context's stream behind the ingest
+// kernel that staged it, inside that kernel's KIND_INGEST bracket and in front of blank_launch.  In place, on whatever
+// ingest_dest returned.  The pair chains on the device in stream order.  Off: nothing.
+void iqbal_launch(sdrx_ctx *c)
+{
+    if (!c->iq.on)
+        return;
+    const int p = (int)(c->frame_no & 1ull);
+    const IqCfg &Q = c->iq.cfg;
+    hipLaunchKernelGGL(k_iqbal, dim3(iq_workgroups(c->in_frame)), dim3(kIqThreads), 0, c->st.stream, ingest_dest(c), c->in_frame, c->iq.d_state.get());
+    hipLaunchKernelGGL(k_iqbal_step, dim3(1), dim3(64), 0, c->st.stream, c->iq.d_state.get(), c->iq.rec.dev<IqRecord>(p), (long long)c->frame_no, c->in_frame,
+                       Q.mu, Q.min_power);
+    c->iq.used[p].frame = c->frame_no;
+    c->iq.used[p].any = true;
+    c->iq.used[p].cfg = Q;
+}
+
 int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st); // (sdrx_delivery.hip)
 int queue_payloads(sdrx_ctx *c, int p, hipStream_t st);
 
@@ -602,8 +619,8 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         // the levels write d_pay[p], which the previous gate reads -- and read the gains its step writes; option wake: the wake
         // steps of this frame write the flag words and state regions the previous tail, gate and step read
         HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.ev_tail[p ^ 1], 0));
-    if (c->staged() && raw_mode != kRawTiled) {
-        // Resampler / front stage: a natural-order frame (cf32, or a shared context's bytes) is at the input rate -- one layout pass into the
+    if (c->tiled_ingest() && raw_mode != kRawTiled) {
+        // Resampler / front stage / blanker / IQ balance: a natural-order frame (cf32, or a shared context's bytes) is at the input rate -- one layout pass into the
         // staging buffer, then k_resample, in front of everything that reads the tree's raw frame.  (A frame of integer samples
         // came through enqueue_samples_device, which did both: kRawTiled.)
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
@@ -614,6 +631,7 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         else
             hipLaunchKernelGGL(k_ingest_samples<SDRX_FMT_CU8>, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream,
                                reinterpret_cast<const unsigned *>(raw), ingest_dest(c), n_pairs);
+        iqbal_launch(c);
         blank_launch(c);
         front_launch(c);
         resample_launch(c);
@@ -812,7 +830,7 @@ int enqueue_f32(sdrx_ctx *c, const float *iq, int n_complex, bool egress)
         return rc;
     rc = enqueue_frame(c, dst, kRawF32, egress);
     if (rc == SDRX_OK)
-        c->last_raw = c->staged() ? kRawTiled : kRawF32; // (resampler, front stage: the tree's frame is their output, in the tile layout)
+        c->last_raw = c->tiled_ingest() ? kRawTiled : kRawF32; // (resampler, front stage: the tree's frame is their output, in the tile layout)
     return rc;
 }
 
@@ -944,6 +962,7 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         }
         hipLaunchKernelGGL(K.apply, dim3((words + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), Ap,
                            ingest_dest(c), n_complex, c->dc.work_stride);
+        iqbal_launch(c);
         blank_launch(c);
         front_launch(c);
         resample_launch(c);
@@ -956,15 +975,17 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
                            c->dc.d_tab, sums);
         hipLaunchKernelGGL(K.dc_fast, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
                            ingest_dest(c), n_complex, c->dc.d_state + 2 * par, c->dc.d_state + 2 * (par ^ 1), c->dc.d_tab, sums);
+        iqbal_launch(c);
         blank_launch(c);
         front_launch(c);
         resample_launch(c);
         mode = kRawTiled;
-    } else if (fmt != SDRX_FMT_CU8 || c->staged()) { // (resampler, front stage, blanker: they read the tile layout, so bytes take the pass too)
+    } else if (fmt != SDRX_FMT_CU8 || c->tiled_ingest()) { // (resampler, front stage, blanker, IQ balance: they read the tile layout, so bytes take the pass too)
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
         const int n_pairs = n_complex / 2;
         hipLaunchKernelGGL(K.ingest, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
                            ingest_dest(c), n_pairs);
+        iqbal_launch(c);
         blank_launch(c);
         front_launch(c);
         resample_launch(c);
@@ -1012,7 +1033,7 @@ int sdrx_process_device(sdrx_ctx *c, const void *dev_iq, int n_complex)
     int rc = check_frame_call(c, "sdrx_process_device", dev_iq, n_complex, true);
     if (rc)
         return rc;
-    c->last_raw = c->staged() ? kRawTiled : -1; // (resampler, front stage: the tree's frame is the context's own, they wrote it)
+    c->last_raw = c->tiled_ingest() ? kRawTiled : -1; // (resampler, front stage: the tree's frame is the context's own, they wrote it)
     return enqueue_frame(c, dev_iq, kRawF32, false);
 }
 
@@ -1021,7 +1042,7 @@ int sdrx_submit_device(sdrx_ctx *c, const void *dev_iq, int n_complex)
     int rc = check_frame_call(c, "sdrx_submit_device", dev_iq, n_complex, false);
     if (rc)
         return rc;
-    c->last_raw = c->staged() ? kRawTiled : -1;
+    c->last_raw = c->tiled_ingest() ? kRawTiled : -1;
     return enqueue_frame(c, dev_iq, kRawF32, true);
 }
 
@@ -1042,8 +1063,9 @@ static int submit_shared(sdrx_ctx *c, sdrx_ctx *src, const char *what, bool sync
 {
     if (!c || !src || c == src)
         return c ? fail(c, SDRX_EINVAL, "%s: needs another context as the source", what) : SDRX_EINVAL;
-    if (c->staged() || src->staged())
-        return fail(c, SDRX_ESTATE, "%s: a context with a resampler, a front stage or a blanker (sdrx_set_resampler, sdrx_set_front, sdrx_set_blanker) shares no frames", what);
+    if (c->tiled_ingest() || src->tiled_ingest())
+        return fail(c, SDRX_ESTATE, "%s: a context with a resampler, a front stage, a blanker or an IQ balance correction (sdrx_set_resampler, sdrx_set_front, sdrx_set_blanker, "
+                                    "sdrx_set_iq_balance) shares no frames", what);
     if (!src->finalized || src->frame_no == 0 || (src->last_raw != kRawF32 && src->last_raw != kRawU8))
         return fail(c, SDRX_ESTATE, "%s: the source context has staged no host frame (floats or bytes without DC removal) yet", what);
     if (src->device != c->device)

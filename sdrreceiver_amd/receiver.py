@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, agc as _agc, blank as _blank, drift as _drift, front as _front, ingest, meter, resample as _resample, scan as _scan, squelch as _squelch, wake as _wake, watch as _watch
+from . import _lib, agc as _agc, blank as _blank, iqbal as _iqbal, drift as _drift, front as _front, ingest, meter, resample as _resample, scan as _scan, squelch as _squelch, wake as _wake, watch as _watch
 from .topology import Topology, VfoDesc
 
 
@@ -313,7 +313,11 @@ class Receiver(_LeafCalls):
                  squelch_auto: bool = False, park: bool = False, watch: bool = False, catchup: bool = False,
                  agc: bool = False, wake: bool = False, adc_meter: bool = False, input_rate: int | None = None,
                  resample_taps=32, resample_atten_db: float = 80.0, front_stages: int = 0, front_real: bool = False,
-                 front_taps=15, front_atten_db: float = 80.0, blanker=None):
+                 front_taps=15, front_atten_db: float = 80.0, blanker=None, iq_balance=None):
+        # iq_balance: the IQ balance correction's settings (sdrreceiver_amd.iqbal.Cfg, or a (mu, min_power[, c0, d0]) tuple) -- the
+        # stage cancels a direct-conversion front end's image in the frame behind the format conversion and the DC removal, in
+        # front of the blanker; None: off.
+        self._iq_balance = None if iq_balance is None else _iqbal.Cfg(*iq_balance) if isinstance(iq_balance, (tuple, list)) else iq_balance
         # blanker: the impulse blanker's settings (sdrreceiver_amd.blank.Cfg, or a (ratio, floor, rank_q16, guard) tuple) -- the
         # stage zeroes pulses in the frame behind the format conversion and in front of everything else; None: off.
         self._blanker = None if blanker is None else _blank.Cfg(*blanker) if isinstance(blanker, (tuple, list)) else blanker
@@ -413,6 +417,8 @@ class Receiver(_LeafCalls):
             self._set_front()
         if self._blanker is not None:
             self.set_blanker(self._blanker)
+        if self._iq_balance is not None:
+            self.set_iq_balance(self._iq_balance)
         self._chk(self.L.sdrx_finalize(self.h))
         self.finalized = True
 
@@ -477,6 +483,32 @@ class Receiver(_LeafCalls):
         self._chk(self.L.sdrx_get_blanker(self.h, C.byref(cfg), C.byref(rec)))
         d = _blank.record_dict(rec)
         d["cfg"] = _blank.cfg_of(cfg)
+        return d
+
+    def set_iq_balance(self, cfg) -> None:
+        """The IQ balance correction's settings (``sdrx_set_iq_balance``): before :meth:`finalize` this switches the stage on
+        (None: off again) and sets the pair it starts from; afterwards it changes mu and min_power between two frames, and with
+        ``iqbal.IQ_LOAD`` in ``flags`` loads ``c0``, ``d0`` as the pair of the next frame."""
+        if cfg is None:
+            self._chk(self.L.sdrx_set_iq_balance(self.h, None))
+            self._iq_balance = None
+            return
+        cfg = _iqbal.Cfg(*cfg) if isinstance(cfg, (tuple, list)) else cfg
+        c = _lib.IqCfgC(float(cfg.mu), float(cfg.min_power), float(cfg.c0), float(cfg.d0), int(cfg.flags))
+        self._chk(self.L.sdrx_set_iq_balance(self.h, C.byref(c)))
+        self._iq_balance = cfg
+
+    @property
+    def iq_balance(self) -> dict | None:
+        """The IQ balance correction's record of the last delivered frame (``sdrx_iq_record`` as a dict: ``measured``,
+        ``adapted``, ``rejected``, the pair used and the next one as fp32 bits, the five sums) with ``cfg``, the settings that frame
+        ran with; None without ``iq_balance``.  ``iqbal.levels`` turns it into the residual imbalance."""
+        if self._iq_balance is None:
+            return None
+        cfg, rec = _lib.IqCfgC(), _lib.IqRecordC()
+        self._chk(self.L.sdrx_get_iq_balance(self.h, C.byref(cfg), C.byref(rec)))
+        d = _iqbal.record_dict(rec)
+        d["cfg"] = _iqbal.cfg_of(cfg)
         return d
 
     def blanker_input(self) -> np.ndarray:
