@@ -5,7 +5,7 @@
 //   sdrx_demo <profile.ini> --dump              descriptors as JSON lines (no GPU needed)
 //   sdrx_demo <profile.ini> --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ]
 //                                   [--front-stages N [--front-real] [--front-taps K]] [--blanker RATIO,GUARD[,FLOOR[,RANK]]]
-//                                   [--iq-balance MU,MINPOWER[,C0,D0]] [--fft TOPIC] [--devices 0,1,...]
+//                                   [--iq-balance MU,MINPOWER[,C0,D0]] [--shift HZ] [--fft TOPIC] [--devices 0,1,...]
 //                                               N synthetic LCG frames; one line per published
 //                                               message: frame topic rate bytes fnv1a64(payload)
 //                                               --u8 feeds them as dongle bytes, --format as integer samples of that
@@ -31,6 +31,9 @@
 //                                               the blanker line),
 //                                               iq frame measured adapted rejected c_bits d_bits next_c_bits next_d_bits
 //                                                  sum_i sum_q sum_iq sum_ii sum_qq
+//                                               --shift HZ: the frequency shift on the device, HZ at the main VFOs' rate; one
+//                                               more line per frame behind its messages (in front of the iq line),
+//                                               shift frame phase inc next_phase next_inc      (8 hex digits each)
 #include <cinttypes>
 #include <cstdio>
 #include <iostream>
@@ -53,7 +56,7 @@ static uint64_t fnv1a(const void *p, size_t n)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ] [--front-stages N [--front-real] [--front-taps K]] [--blanker RATIO,GUARD[,FLOOR[,RANK]]] [--iq-balance MU,MINPOWER[,C0,D0]] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ] [--front-stages N [--front-real] [--front-taps K]] [--blanker RATIO,GUARD[,FLOOR[,RANK]]] [--iq-balance MU,MINPOWER[,C0,D0]] [--shift HZ] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
         return 2;
     }
     try {
@@ -88,6 +91,8 @@ int main(int argc, char **argv)
         int bl_guard = 0, bl_rank = 32768;
         bool iq_balance = false;
         float iq_mu = 0, iq_min_power = 0, iq_c0 = 0, iq_d0 = 1;
+        bool shift = false;
+        double shift_hz = 0;
         std::string fft_topic;
         std::vector<int> devices;
         for (int a = 4; a < argc; ++a) {
@@ -119,6 +124,10 @@ int main(int argc, char **argv)
                 if (got != 2 && got != 4)
                     throw std::runtime_error("--iq-balance takes MU,MINPOWER[,C0,D0]");
                 iq_balance = true;
+            } else if (std::string(argv[a]) == "--shift" && a + 1 < argc) {
+                if (std::sscanf(argv[++a], "%lf", &shift_hz) != 1)
+                    throw std::runtime_error("--shift takes HZ");
+                shift = true;
             } else if (std::string(argv[a]) == "--fft" && a + 1 < argc)
                 fft_topic = argv[++a];
             else if (std::string(argv[a]) == "--devices" && a + 1 < argc) { // one tree sharded over several GPUs
@@ -170,6 +179,8 @@ int main(int argc, char **argv)
             radio.setBlanker(bl_ratio, bl_guard, bl_floor, bl_rank);
         if (iq_balance)
             radio.setIqBalance(iq_mu, iq_min_power, iq_c0, iq_d0);
+        if (shift)
+            radio.setShift(shift_hz);
         if (input_rate > 0 || front_stages > 0)
             radio.start();
         if (input_rate > 0) {
@@ -213,6 +224,10 @@ int main(int argc, char **argv)
                 radio.demodBytes(bytes.data(), n_frame);
             else
                 radio.demodData(iq.data(), (int)iq.size());
+            if (shift) {
+                const sdrx_shift_record s = radio.shift();
+                std::printf("shift %d %08x %08x %08x %08x\n", frame_no, s.phase, s.inc, s.next_phase, s.next_inc);
+            }
             if (iq_balance) {
                 const sdrx_iq_record q = radio.iqBalance();
                 std::printf("iq %d %u %u %u %08x %08x %08x %08x %" PRId64 " %" PRId64 " %" PRId64 " %" PRIu64 " %" PRIu64 "\n", frame_no, q.measured, q.adapted,

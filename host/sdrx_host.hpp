@@ -234,6 +234,37 @@ public:
         check(sdrx_get_iq_balance(ctx_, nullptr, &r), "sdrx_get_iq_balance");
         return r;
     }
+    // The frequency shift on the device (include/sdrx.h "Frequency shift"; the reference's mix_offset, README "tune ALL VFO's up or
+    // down by a number of Hz", as one stage): the tree's raw frame times exp(+j 2 pi hz t), `hz` at the parent-less VFOs' rate.
+    // Before the first frame it switches the stage on; afterwards it changes the shift between two frames, phase-continuous in
+    // every channel.  One device only.
+    void setShift(double hz)
+    {
+        if (grp_)
+            throw std::runtime_error("sdrj: the frequency shift (setShift) is not offered on several devices");
+        shift_hz_ = hz;
+        if (ctx_) {
+            const sdrx_shift_cfg cfg = shift_cfg();
+            check(sdrx_set_shift(ctx_, &cfg), "sdrx_set_shift");
+        }
+        sh_on_ = true;
+    }
+    // ... and its record of the last delivered frame: the phase and the increment it used, and what it left behind
+    sdrx_shift_record shift()
+    {
+        if (!ctx_ || !sh_on_)
+            throw std::runtime_error("sdrj::shift: no frequency shift set, or not started");
+        sdrx_shift_record r;
+        check(sdrx_get_shift(ctx_, nullptr, &r), "sdrx_get_shift");
+        return r;
+    }
+    // Closing the loop on the host: the shift that follows a drift estimate (drift_hz of the raw frame's source: a band that sits D
+    // Hz high peaks at +D and is corrected by a shift of -D), clamped to +-fs_tree / 2
+    static double shift_follow(double hz_now, double drift_hz, double fs_tree, double gain = 1.0)
+    {
+        const double hz = hz_now - gain * drift_hz;
+        return hz > fs_tree / 2 ? fs_tree / 2 : hz < -fs_tree / 2 ? -fs_tree / 2 : hz;
+    }
     // sdrj.cpp:84-101: the raw spectrum is selected by the topic "Main"; any selection restarts
     // the every-4th-call counter of demodData (sdrj.cpp:296-303)
     void fftVFOSlot(const std::string &topic)
@@ -256,6 +287,8 @@ public:
             throw std::runtime_error("sdrj: the blanker (setBlanker) is not offered on several devices");
         if (devices_.size() > 1 && iq_on_)
             throw std::runtime_error("sdrj: the IQ balance correction (setIqBalance) is not offered on several devices");
+        if (devices_.size() > 1 && sh_on_)
+            throw std::runtime_error("sdrj: the frequency shift (setShift) is not offered on several devices");
         if (devices_.size() > 1) {
             check(sdrx_group_create(&grp_, devices_.data(), (int)devices_.size()), "sdrx_group_create");
             for (auto &kv : options_)
@@ -285,6 +318,10 @@ public:
             check(sdrx_set_blanker(ctx_, &bl_cfg_), "sdrx_set_blanker");
         if (iq_on_)
             check(sdrx_set_iq_balance(ctx_, &iq_cfg_), "sdrx_set_iq_balance");
+        if (sh_on_) {
+            const sdrx_shift_cfg cfg = shift_cfg();
+            check(sdrx_set_shift(ctx_, &cfg), "sdrx_set_shift");
+        }
         check(sdrx_set_publish_callback(ctx_, &sdrj::trampoline, this), "sdrx_set_publish_callback");
         check(sdrx_finalize(ctx_), "sdrx_finalize");
     }
@@ -673,6 +710,15 @@ private:
     sdrx_blanker_cfg bl_cfg_{};
     bool iq_on_ = false; // setIqBalance
     sdrx_iq_cfg iq_cfg_{};
+    bool sh_on_ = false; // setShift
+    double shift_hz_ = 0.0;
+    sdrx_shift_cfg shift_cfg() const // shift_hz_ at the first main's rate
+    {
+        sdrx_shift_cfg cfg{};
+        if (sdrx_shift_inc((double)(*mpVFOs)[0]->d.fs, shift_hz_, &cfg.inc) != SDRX_OK)
+            throw std::runtime_error("sdrj::setShift: the shift must be finite and at most half the main VFOs' sample rate");
+        return cfg;
+    }
 };
 
 // ------------------------------------------------------------------------------------------ INI

@@ -1065,6 +1065,64 @@ typedef struct sdrx_iq_record { /* 96 bytes */
 int sdrx_set_iq_balance(sdrx_ctx *ctx, const sdrx_iq_cfg *cfg);
 int sdrx_get_iq_balance(sdrx_ctx *ctx, sdrx_iq_cfg *cfg_out, sdrx_iq_record *record_out);
 
+/* ---- Frequency shift (sdrx_set_shift before sdrx_finalize) -----------------------------------------------------------
+ * The reference's mix_offset ("tune ALL VFO's up or down by a number of Hz", after a dongle change or while the dongle warms up)
+ * as one stage: one elementwise complex mix over the wideband frame, once instead of once per VFO, phase-continuous across frames
+ * and across changes of the shift.  It is the last stage of the ingest chain: in place on the tree's raw frame, behind the
+ * resampler or whatever comes last, in front of the raw-frame spectrum, the watch and level 0, at the tree's rate -- its Hz are
+ * mix_offset's Hz.  This text is the definition, sdrreceiver_amd/shift.py restates it in numpy, and the device is held to that bit
+ * for bit.  No FMA anywhere; the same in every setting of option "exact".  Off (the default) nothing changes at all: the same
+ * kernels, launches, device_bytes, payloads and callbacks.
+ *
+ * State: phase and inc, uint32.  One unit of phase is 2^-32 turn, so inc is the shift in units of fs_tree / 2^32 per sample.  A
+ * positive inc moves the spectrum up: the mixer's own sign convention, multiplication by exp(+j 2 pi f t).  After sdrx_finalize
+ * they are phase0 and inc of the settings.
+ * Tables: three of 256 cf32 entries, built on the host in double with the C library's cos / sin and rounded once to float:
+ *   A[k] = (cos, sin)(2 pi k / 2^8),  B[k] = (cos, sin)(2 pi k / 2^16),  C[k] = (cos, sin)(2 pi k / 2^24)
+ * sdrx_shift_tables(out) hands them out: A | B | C, (re, im) interleaved, 3 * 256 * 2 floats.
+ * Frame f of n samples (n: the tree's raw frame).  Sample j has phase p = (phase + j inc) mod 2^32, and
+ *   h = p >> 24,  m = (p >> 16) & 255,  l = (p >> 8) & 255          (the low 8 bits are dropped: truncated, not rounded)
+ *   r1 = A[h] (x) B[m],  rot = r1 (x) C[l],  y = x (x) rot
+ *   a (x) b = ( fl(fl(ar br) - fl(ai bi)), fl(fl(ar bi) + fl(ai br)) )
+ * three fp32 roundings per component, in this association and operand order.  A component of y that is a NaN is the quiet NaN
+ * 0x7fc00000, whatever produced it.  At phase = 0, inc = 0 the output has the input's bits for finite samples other than -0.
+ * Behind the frame: phase <- (phase + n inc) mod 2^32.
+ * The record of frame f (sdrx_shift_record): phase, inc -- what the frame used; next_phase, next_inc -- what it left behind.
+ *
+ * Settings (sdrx_shift_cfg): inc, phase0; flags: bit 0 SDRX_SHIFT_LOAD_PHASE, the other bits 0 (else SDRX_EINVAL); reserved zeros.
+ * sdrx_shift_inc(fs_tree, hz, &inc): rint(hz / fs_tree 2^32) in double, ties to even, mod 2^32; SDRX_EINVAL for non-finite input,
+ * fs_tree <= 0 or |hz| > fs_tree / 2.  sdrx_shift_hz(fs_tree, inc): the signed inverse.
+ *
+ * sdrx_set_shift(ctx, cfg): before sdrx_finalize it switches the stage on (cfg == NULL: off again).  After sdrx_finalize it
+ * changes inc between two frames with a one-thread launch in stream order -- the phase carries on, every channel stays
+ * phase-continuous -- and with SDRX_SHIFT_LOAD_PHASE also sets the phase to phase0 (SDRX_ESTATE with submitted frames not yet
+ * delivered; the calls in flight are drained first); SDRX_ESTATE if the stage was not on at sdrx_finalize, or for cfg == NULL.
+ * sdrx_get_shift(ctx, cfg_out, record_out): the settings the last delivered frame ran with (phase0: what sdrx_finalize or the last
+ * SDRX_SHIFT_LOAD_PHASE wrote) and its record (either may be NULL), under sdrx_get_blanker's rules.
+ * in_frame is unchanged.  sdrx_get_raw, the raw-frame spectrum, the watch, the drift estimate and the band scan see the shifted
+ * frame (so the drift estimate reads the residual); sdrx_get_resampler_input, sdrx_get_blanker_input and the ADC meter see what
+ * they saw.  A cf32 host frame or a caller's device frame is copied into the context's own buffer first: the caller's buffer is
+ * never written.  Offered behind every ingest chain, a real first front stage included.  sdrx_*_shared and sdrx_*_if_same return
+ * SDRX_ESTATE if either context has the stage.  Groups do not offer it. */
+#define SDRX_SHIFT_LOAD_PHASE 1u
+typedef struct sdrx_shift_cfg { /* 32 bytes */
+    uint32_t inc, phase0;
+    uint32_t flags;
+    uint32_t reserved[5];
+} sdrx_shift_cfg;
+typedef struct sdrx_shift_record { /* 64 bytes */
+    int64_t frame;
+    uint32_t n_complex, applied;
+    uint32_t phase, inc;
+    uint32_t next_phase, next_inc;
+    uint32_t reserved[8];
+} sdrx_shift_record;
+int sdrx_set_shift(sdrx_ctx *ctx, const sdrx_shift_cfg *cfg);
+int sdrx_get_shift(sdrx_ctx *ctx, sdrx_shift_cfg *cfg_out, sdrx_shift_record *record_out);
+void sdrx_shift_tables(float *out);
+int sdrx_shift_inc(double fs_tree, double hz, uint32_t *inc);
+double sdrx_shift_hz(double fs_tree, uint32_t inc);
+
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);

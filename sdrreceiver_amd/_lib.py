@@ -181,6 +181,17 @@ class IqRecordC(C.Structure):
                 ("sum_q", C.c_int64), ("sum_iq", C.c_int64), ("sum_ii", C.c_uint64), ("sum_qq", C.c_uint64), ("reserved", C.c_uint32 * 4)]
 
 
+class ShiftCfgC(C.Structure):
+    """struct sdrx_shift_cfg"""
+    _fields_ = [("inc", C.c_uint32), ("phase0", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class ShiftRecordC(C.Structure):
+    """struct sdrx_shift_record"""
+    _fields_ = [("frame", C.c_int64), ("n_complex", C.c_uint32), ("applied", C.c_uint32), ("phase", C.c_uint32), ("inc", C.c_uint32),
+                ("next_phase", C.c_uint32), ("next_inc", C.c_uint32), ("reserved", C.c_uint32 * 8)]
+
+
 PUBLISH_FN =C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
 
 # every symbol include/sdrx.h declares: (restype, argtypes)
@@ -284,6 +295,11 @@ SYMBOLS = {
     "sdrx_get_blanker_input": (_i, [_vp, _vp, C.c_int32]),
     "sdrx_set_iq_balance": (_i, [_vp, C.POINTER(IqCfgC)]),
     "sdrx_get_iq_balance": (_i, [_vp, C.POINTER(IqCfgC), C.POINTER(IqRecordC)]),
+    "sdrx_set_shift": (_i, [_vp, C.POINTER(ShiftCfgC)]),
+    "sdrx_get_shift": (_i, [_vp, C.POINTER(ShiftCfgC), C.POINTER(ShiftRecordC)]),
+    "sdrx_shift_tables": (None, [_vp]),
+    "sdrx_shift_inc": (_i, [C.c_double, C.c_double, C.POINTER(C.c_uint32)]),
+    "sdrx_shift_hz": (C.c_double, [C.c_double, C.c_uint32]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

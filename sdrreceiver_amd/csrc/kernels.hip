@@ -32,6 +32,9 @@
 //   k_iqbal, k_iqbal_step iqbal.hip     (none: sdrx_set_iq_balance -- the IQ balance correction behind the format conversion and the DC removal, in front
 //                                       of the blanker: Q' = c I + d Q in place, and the pair (c, d) moved from exact integer statistics of each
 //                                       frame's output; include/sdrx.h "IQ balance")
+//   k_shift, k_shift_step shift.hip     mix_offset (README "tune ALL VFO's up or down"), as one stage: sdrx_set_shift -- the frequency shift at the end
+//                                       of the ingest chain, in place on the tree's raw frame: y = x exp(+j 2 pi p / 2^32) from three 256-entry
+//                                       tables, the 32-bit phase carried on the device from frame to frame; include/sdrx.h "Frequency shift")
 //   k_mix_decimate        mix.hip       vfo::process mix loop, vfo.cpp:237-245; HalfBandDecimator::decimate, halfbanddecimator.cpp:43-72,
 //                                       with FIR::...HalfBandQueue, dsp.cpp:96-173 (mix_item); option fuse_late: the FIR part of
 //                                       vfo::usb_decimdemod, vfo.cpp:334-356, inside a d = 0 leaf's wave (late_item); option fuse_demod:
@@ -55,6 +58,7 @@
 #include "sdrx_front.h"
 #include "sdrx_blank.h"
 #include "sdrx_iqbal.h"
+#include "sdrx_shift.h"
 
 #include <type_traits>
 #include <utility>
@@ -69,6 +73,7 @@ namespace sdrx {
 #include "front.hip"
 #include "blank.hip"
 #include "iqbal.hip"
+#include "shift.hip"
 #include "meter.hip"
 #include "demod.hip"
 #include "mix.hip"

@@ -78,6 +78,12 @@ static_assert(sizeof(sdrx_iq_cfg) == 32 && sizeof(IqCfg) == 32 && offsetof(sdrx_
                   offsetof(sdrx_iq_record, next_d_bits) == offsetof(IqRecord, next_d_bits) && offsetof(sdrx_iq_record, sum_i) == offsetof(IqRecord, sum_i) &&
                   offsetof(sdrx_iq_record, sum_qq) == offsetof(IqRecord, sum_qq) && sizeof(IqState) == 64 && SDRX_IQ_LOAD == kIqLoad,
               "sdrx_iq_cfg / sdrx_iq_record ABI layout");
+static_assert(sizeof(sdrx_shift_cfg) == 32 && sizeof(ShiftCfg) == 32 && offsetof(sdrx_shift_cfg, phase0) == offsetof(ShiftCfg, phase0) &&
+                  offsetof(sdrx_shift_cfg, flags) == offsetof(ShiftCfg, flags) && sizeof(sdrx_shift_record) == 64 && sizeof(ShiftRecord) == 64 &&
+                  offsetof(sdrx_shift_record, applied) == offsetof(ShiftRecord, applied) && offsetof(sdrx_shift_record, phase) == offsetof(ShiftRecord, phase) &&
+                  offsetof(sdrx_shift_record, next_inc) == offsetof(ShiftRecord, next_inc) && offsetof(sdrx_shift_record, reserved) == offsetof(ShiftRecord, reserved) &&
+                  sizeof(ShiftState) == 16 && SDRX_SHIFT_LOAD_PHASE == kShLoadPhase,
+              "sdrx_shift_cfg / sdrx_shift_record ABI layout");
 static_assert(sizeof(sdrx_adc_arm) == 40 && sizeof(AdcArm) == 40 && offsetof(sdrx_adc_arm, longest_rail_run) == offsetof(AdcArm, longest_rail_run) &&
                   sizeof(sdrx_adc_meter) == 184 && sizeof(AdcRecord) == 184 && offsetof(sdrx_adc_meter, q) == offsetof(AdcRecord, q) &&
                   offsetof(sdrx_adc_meter, sum_iq) == offsetof(AdcRecord, sum_iq) && offsetof(sdrx_adc_meter, bits) == offsetof(AdcRecord, bits),
@@ -132,6 +138,7 @@ void free_device_state(sdrx_ctx *c)
     static_cast<sdrx_ctx::FrontDevice &>(c->fr) = sdrx_ctx::FrontDevice();
     static_cast<sdrx_ctx::BlankerDevice &>(c->bl) = sdrx_ctx::BlankerDevice();
     static_cast<sdrx_ctx::IqDevice &>(c->iq) = sdrx_ctx::IqDevice();
+    static_cast<sdrx_ctx::ShiftDevice &>(c->sh) = sdrx_ctx::ShiftDevice();
 }
 
 } // namespace
@@ -1221,6 +1228,80 @@ int sdrx_get_iq_balance(sdrx_ctx *c, sdrx_iq_cfg *cfg_out, sdrx_iq_record *out)
     return SDRX_OK;
 }
 
+// ---- Frequency shift (include/sdrx.h; sdrx_shift.h has the rules) ------------------------------------------------------------------
+int sdrx_set_shift(sdrx_ctx *c, const sdrx_shift_cfg *cfg)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (c->finalized && !c->sh.on)
+        return fail(c, SDRX_ESTATE, "sdrx_set_shift: the frequency shift was not switched on before sdrx_finalize");
+    if (!cfg) {
+        if (c->finalized)
+            return fail(c, SDRX_ESTATE, "sdrx_set_shift: the frequency shift is switched off before sdrx_finalize only");
+        c->sh.on = false;
+        return SDRX_OK;
+    }
+    if (const char *why = shift_args(cfg->flags, cfg->reserved))
+        return fail(c, SDRX_EINVAL, "sdrx_set_shift: %s", why);
+    const bool load = (cfg->flags & SDRX_SHIFT_LOAD_PHASE) != 0;
+    if (c->finalized) { // between two frames: every frame handed over ran with the increment it was launched with
+        if (c->in_flight > 0)
+            return fail(c, SDRX_ESTATE, "sdrx_set_shift: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+        HIPCHK(c, hipSetDevice(c->device));
+        if (int rc = drain(c))
+            return rc;
+        // the increment of the next frame, in stream order; the phase carries on unless the caller loads one
+        hipLaunchKernelGGL(k_shift_load, dim3(1), dim3(64), 0, c->st.stream, c->sh.d_state.get(), cfg->inc, cfg->phase0, load ? 1 : 0);
+    }
+    const bool keep = c->finalized && !load; // (phase0 stays what was last written into the state)
+    c->sh.cfg = ShiftCfg{cfg->inc, keep ? c->sh.cfg.phase0 : cfg->phase0, cfg->flags, {0, 0, 0, 0, 0}};
+    c->sh.on = true;
+    return SDRX_OK;
+}
+
+int sdrx_get_shift(sdrx_ctx *c, sdrx_shift_cfg *cfg_out, sdrx_shift_record *out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_shift before sdrx_finalize");
+    if (!c->sh.on)
+        return fail(c, SDRX_ESTATE, "sdrx_get_shift: no frequency shift set (sdrx_set_shift before sdrx_finalize)");
+    if (!cfg_out && !out)
+        return fail(c, SDRX_EINVAL, "sdrx_get_shift: null output pointers");
+    if (int rc = need_delivered(c, "sdrx_get_shift"))
+        return rc;
+    const int p = c->host_slot;
+    const sdrx_ctx::Shift::Used &U = c->sh.used[p];
+    if (!U.any || U.frame != c->host_frame)
+        return fail(c, SDRX_EHIP, "sdrx_get_shift: frame %llu did not pass the frequency shift", c->host_frame);
+    if (cfg_out)
+        memcpy(cfg_out, &U.cfg, sizeof *cfg_out);
+    if (out) {
+        memcpy(out, c->sh.rec.host<ShiftRecord>(p), sizeof *out);
+        if (!out->n_complex || out->frame != (int64_t)c->host_frame) // (a slot never written holds zeros)
+            return fail(c, SDRX_EHIP, "sdrx_get_shift: the record of frame %llu did not arrive (it names frame %lld)", c->host_frame, (long long)out->frame);
+    }
+    return SDRX_OK;
+}
+
+void sdrx_shift_tables(float *out)
+{
+    if (out)
+        shift_tables(out);
+}
+
+int sdrx_shift_inc(double fs_tree, double hz, uint32_t *inc)
+{
+    uint32_t v = 0;
+    if (!inc || !shift_inc(fs_tree, hz, &v))
+        return SDRX_EINVAL;
+    *inc = v;
+    return SDRX_OK;
+}
+
+double sdrx_shift_hz(double fs_tree, uint32_t inc) { return shift_hz(fs_tree, inc); }
+
 int sdrx_get_stream(sdrx_ctx *c, int id, float *out, int max_complex, int *n_ret)
 {
     if (!c || id < 0 || id >= (int)c->nodes.size())
@@ -1471,7 +1552,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
     const size_t raw_bytes = c->d_raw[0].bytes() + c->d_raw_u8[0].bytes(); // (ONE parity of the host-fed frames' buffers: kept for compatibility)
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes() + c->adc.bytes() + c->rs.bytes() + c->fr.bytes() + c->bl.bytes() + c->iq.bytes());
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes() + c->adc.bytes() + c->rs.bytes() + c->fr.bytes() + c->bl.bytes() + c->iq.bytes() + c->sh.bytes());
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

@@ -441,7 +441,26 @@ struct sdrx_ctx : CtxBuffers {
             IqCfg cfg{};
         } used[2];
     } iq;
-    bool tiled_ingest() const { return staged() || iq.on; } // every frame goes through an ingest kernel into the tile layout
+    // Frequency shift (sdrx_set_shift, shift.hip): k_shift in place on the tree's raw frame, behind the resampler or
+    // whatever comes last in the ingest chain.  The setting is the host's; what finalize allocates with it: the device state (phase
+    // and increment of the next frame), the one device copy of the three tables and the record of frame f (`rec`).  No staging
+    // frame, but every frame takes the ingest pass into the tile layout (tiled_ingest).  `used` as for the IQ balance.
+    struct ShiftDevice { // what free_device_state releases
+        DevBuf<ShiftState> d_state;
+        DevBuf<float2> d_tab; // A | B | C, 3 * kShTab entries
+        Records rec;
+        size_t bytes() const { return d_state.bytes() + d_tab.bytes() + 2 * rec.bytes(); } // device memory it holds
+    };
+    struct Shift : ShiftDevice {
+        bool on = false; // set before sdrx_finalize
+        ShiftCfg cfg{};  // inc: of the next frame; phase0: what sdrx_finalize or the last SDRX_SHIFT_LOAD_PHASE wrote
+        struct Used {
+            unsigned long long frame = 0;
+            bool any = false;
+            ShiftCfg cfg{};
+        } used[2];
+    } sh;
+    bool tiled_ingest() const { return staged() || iq.on || sh.on; } // every frame goes through an ingest kernel into the tile layout
     int in_frame = 0; // samples of an incoming frame: root_frame, or with a resampler rs.plan.n_in; times 2^stages with a front stage
 
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot

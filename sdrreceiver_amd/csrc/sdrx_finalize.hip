@@ -1173,6 +1173,27 @@ int iqbal_setup(sdrx_ctx *c)
     return SDRX_OK;
 }
 
+// Frequency shift: what k_shift needs on the device -- the state (phase0, inc), the three tables and the record buffers of both
+// frame parities.  All of it or (the caller releases) none.  It is offered behind every ingest chain, a real first front stage
+// included: it works on the tree's raw frame.
+int shift_setup(sdrx_ctx *c)
+{
+    for (sdrx_ctx::Shift::Used &u : c->sh.used)
+        u = sdrx_ctx::Shift::Used();
+    if (!c->sh.on)
+        return SDRX_OK;
+    if (c->sh.d_state.alloc(1) != hipSuccess || c->sh.d_tab.alloc(3 * kShTab) != hipSuccess || c->sh.rec.alloc(sizeof(ShiftRecord)) != hipSuccess)
+        return fail(c, SDRX_ENOMEM, "sdrx_finalize: no device memory for the frequency shift");
+    ShiftState st;
+    memset(&st, 0, sizeof st);
+    st.phase = c->sh.cfg.phase0, st.inc = c->sh.cfg.inc;
+    HIPCHK(c, hipMemcpy(c->sh.d_state, &st, sizeof st, hipMemcpyHostToDevice));
+    std::vector<float> tab(3 * kShTab * 2);
+    shift_tables(tab.data());
+    HIPCHK(c, hipMemcpy(c->sh.d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    return SDRX_OK;
+}
+
 int finalize_impl(sdrx_ctx *c)
 {
     if (int rc = derive_nodes(c))
@@ -1210,6 +1231,8 @@ int finalize_impl(sdrx_ctx *c)
     if (int rc = blank_setup(c))
         return rc;
     if (int rc = iqbal_setup(c))
+        return rc;
+    if (int rc = shift_setup(c))
         return rc;
     catchup_setup(c, B);
     c->sq.preroll_fused = false;

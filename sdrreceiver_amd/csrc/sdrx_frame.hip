@@ -191,6 +191,22 @@ void iqbal_launch(sdrx_ctx *c)
     c->iq.used[p].cfg = Q;
 }
 
+// Frequency shift: k_shift and k_shift_step for the next frame (c->frame_no), on the context's stream behind the last kernel of
+// the ingest chain, inside its KIND_INGEST bracket.  In place on the tree's raw frame (root_frame samples), in front of
+// everything that reads it.  Phase and increment chain on the device in stream order.  Off: nothing.
+void shift_launch(sdrx_ctx *c)
+{
+    if (!c->sh.on)
+        return;
+    const int p = (int)(c->frame_no & 1ull);
+    hipLaunchKernelGGL(k_shift, dim3(shift_workgroups(c->root_frame)), dim3(kShThreads), 0, c->st.stream, reinterpret_cast<float4 *>(c->d_raw_tiled.get()),
+                       c->root_frame, c->sh.d_state.get(), c->sh.d_tab.get());
+    hipLaunchKernelGGL(k_shift_step, dim3(1), dim3(64), 0, c->st.stream, c->sh.d_state.get(), c->sh.rec.dev<ShiftRecord>(p), (long long)c->frame_no, c->root_frame);
+    c->sh.used[p].frame = c->frame_no;
+    c->sh.used[p].any = true;
+    c->sh.used[p].cfg = c->sh.cfg;
+}
+
 int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st); // (sdrx_delivery.hip)
 int queue_payloads(sdrx_ctx *c, int p, hipStream_t st);
 
@@ -620,7 +636,7 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         // steps of this frame write the flag words and state regions the previous tail, gate and step read
         HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.ev_tail[p ^ 1], 0));
     if (c->tiled_ingest() && raw_mode != kRawTiled) {
-        // Resampler / front stage / blanker / IQ balance: a natural-order frame (cf32, or a shared context's bytes) is at the input rate -- one layout pass into the
+        // Resampler / front stage / blanker / IQ balance / shift: a natural-order frame (cf32, or a shared context's bytes) is at the input rate -- one layout pass into the
         // staging buffer, then k_resample, in front of everything that reads the tree's raw frame.  (A frame of integer samples
         // came through enqueue_samples_device, which did both: kRawTiled.)
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
@@ -635,6 +651,7 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         blank_launch(c);
         front_launch(c);
         resample_launch(c);
+        shift_launch(c);
         raw_mode = kRawTiled;
     }
     spectrum_raw_step(c, raw, raw_mode);
@@ -929,6 +946,7 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
             Bracket b(c, c->st.stream, KIND_INGEST, 0);
             front_launch(c, dev_bytes, fmt);
             resample_launch(c);
+            shift_launch(c);
         }
         const int rc = enqueue_frame(c, dev_bytes, kRawTiled, egress);
         if (rc == SDRX_OK)
@@ -966,6 +984,7 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         blank_launch(c);
         front_launch(c);
         resample_launch(c);
+        shift_launch(c);
         mode = kRawTiled;
     } else if (correct_dc) {
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
@@ -979,8 +998,9 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         blank_launch(c);
         front_launch(c);
         resample_launch(c);
+        shift_launch(c);
         mode = kRawTiled;
-    } else if (fmt != SDRX_FMT_CU8 || c->tiled_ingest()) { // (resampler, front stage, blanker, IQ balance: they read the tile layout, so bytes take the pass too)
+    } else if (fmt != SDRX_FMT_CU8 || c->tiled_ingest()) { // (resampler, front stage, blanker, IQ balance, shift: they read the tile layout, so bytes take the pass too)
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
         const int n_pairs = n_complex / 2;
         hipLaunchKernelGGL(K.ingest, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
@@ -989,6 +1009,7 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         blank_launch(c);
         front_launch(c);
         resample_launch(c);
+        shift_launch(c);
         mode = kRawTiled;
     }
     c->long_frame = correct_dc && !c->opt_dc_blocked;
@@ -1064,8 +1085,8 @@ static int submit_shared(sdrx_ctx *c, sdrx_ctx *src, const char *what, bool sync
     if (!c || !src || c == src)
         return c ? fail(c, SDRX_EINVAL, "%s: needs another context as the source", what) : SDRX_EINVAL;
     if (c->tiled_ingest() || src->tiled_ingest())
-        return fail(c, SDRX_ESTATE, "%s: a context with a resampler, a front stage, a blanker or an IQ balance correction (sdrx_set_resampler, sdrx_set_front, sdrx_set_blanker, "
-                                    "sdrx_set_iq_balance) shares no frames", what);
+        return fail(c, SDRX_ESTATE, "%s: a context with a resampler, a front stage, a blanker, an IQ balance correction or a frequency shift (sdrx_set_resampler, sdrx_set_front, "
+                                    "sdrx_set_blanker, sdrx_set_iq_balance, sdrx_set_shift) shares no frames", what);
     if (!src->finalized || src->frame_no == 0 || (src->last_raw != kRawF32 && src->last_raw != kRawU8))
         return fail(c, SDRX_ESTATE, "%s: the source context has staged no host frame (floats or bytes without DC removal) yet", what);
     if (src->device != c->device)

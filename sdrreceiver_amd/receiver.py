@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, agc as _agc, blank as _blank, iqbal as _iqbal, drift as _drift, front as _front, ingest, meter, resample as _resample, scan as _scan, squelch as _squelch, wake as _wake, watch as _watch
+from . import _lib, agc as _agc, blank as _blank, iqbal as _iqbal, drift as _drift, front as _front, ingest, meter, resample as _resample, scan as _scan, shift as _shift, squelch as _squelch, wake as _wake, watch as _watch
 from .topology import Topology, VfoDesc
 
 
@@ -313,7 +313,10 @@ class Receiver(_LeafCalls):
                  squelch_auto: bool = False, park: bool = False, watch: bool = False, catchup: bool = False,
                  agc: bool = False, wake: bool = False, adc_meter: bool = False, input_rate: int | None = None,
                  resample_taps=32, resample_atten_db: float = 80.0, front_stages: int = 0, front_real: bool = False,
-                 front_taps=15, front_atten_db: float = 80.0, blanker=None, iq_balance=None):
+                 front_taps=15, front_atten_db: float = 80.0, blanker=None, iq_balance=None, shift=None):
+        # shift: the frequency shift at the end of the ingest chain (sdrreceiver_amd.shift) -- a number is Hz at the tree's rate
+        # (mix_offset's Hz; converted at finalize), a shift.Cfg or an (inc[, phase0]) tuple the 32-bit words themselves; None: off.
+        self._shift = None if shift is None else _shift.Cfg(*shift) if isinstance(shift, (tuple, list)) else shift
         # iq_balance: the IQ balance correction's settings (sdrreceiver_amd.iqbal.Cfg, or a (mu, min_power[, c0, d0]) tuple) -- the
         # stage cancels a direct-conversion front end's image in the frame behind the format conversion and the DC removal, in
         # front of the blanker; None: off.
@@ -419,6 +422,11 @@ class Receiver(_LeafCalls):
             self.set_blanker(self._blanker)
         if self._iq_balance is not None:
             self.set_iq_balance(self._iq_balance)
+        if self._shift is not None:
+            if isinstance(self._shift, _shift.Cfg):
+                self.set_shift(inc=self._shift.inc, phase=self._shift.phase0)
+            else:
+                self.set_shift(hz=float(self._shift))
         self._chk(self.L.sdrx_finalize(self.h))
         self.finalized = True
 
@@ -509,6 +517,42 @@ class Receiver(_LeafCalls):
         self._chk(self.L.sdrx_get_iq_balance(self.h, C.byref(cfg), C.byref(rec)))
         d = _iqbal.record_dict(rec)
         d["cfg"] = _iqbal.cfg_of(cfg)
+        return d
+
+    @property
+    def tree_rate(self) -> float:
+        """The parent-less VFOs' sample rate: the rate the frequency shift runs at"""
+        return float(next(d.fs for d in self.descs if d.parent < 0))
+
+    def set_shift(self, hz: float | None = None, inc: int | None = None, phase: int | None = None, off: bool = False) -> None:
+        """The frequency shift's settings (``sdrx_set_shift``): ``hz`` at the tree's rate (``shift.inc_of``) or ``inc``, the
+        32-bit increment itself.  Before :meth:`finalize` this switches the stage on (``off=True``: off again) and ``phase`` is
+        the phase it starts from (default 0); afterwards it changes the increment between two frames -- the phase carries on --
+        and a ``phase`` that is not None is loaded as the phase of the next frame (``SDRX_SHIFT_LOAD_PHASE``)."""
+        if off:
+            self._chk(self.L.sdrx_set_shift(self.h, None))
+            self._shift = None
+            return
+        if (hz is None) == (inc is None):
+            raise ValueError("set_shift takes hz or inc")
+        word = _shift.inc_of(self.tree_rate, hz) if inc is None else int(inc) & _shift.M32
+        flags = _shift.LOAD_PHASE if phase is not None and self.finalized else 0
+        c = _lib.ShiftCfgC(word, int(phase or 0) & _shift.M32, flags)
+        self._chk(self.L.sdrx_set_shift(self.h, C.byref(c)))
+        self._shift = _shift.Cfg(word, int(phase or 0) & _shift.M32, flags)
+
+    @property
+    def shift(self) -> dict | None:
+        """The frequency shift's record of the last delivered frame (``sdrx_shift_record`` as a dict: the phase and increment the
+        frame used, and what it left behind) with ``cfg``, the settings that frame ran with, and ``hz``, its increment in Hz at
+        the tree's rate; None without ``shift``."""
+        if self._shift is None:
+            return None
+        cfg, rec = _lib.ShiftCfgC(), _lib.ShiftRecordC()
+        self._chk(self.L.sdrx_get_shift(self.h, C.byref(cfg), C.byref(rec)))
+        d = _shift.record_dict(rec)
+        d["cfg"] = _shift.cfg_of(cfg)
+        d["hz"] = _shift.hz_of(self.tree_rate, d["inc"])
         return d
 
     def blanker_input(self) -> np.ndarray:
