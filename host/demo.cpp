@@ -5,7 +5,8 @@
 //   sdrx_demo <profile.ini> --dump              descriptors as JSON lines (no GPU needed)
 //   sdrx_demo <profile.ini> --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ]
 //                                   [--front-stages N [--front-real] [--front-taps K]] [--blanker RATIO,GUARD[,FLOOR[,RANK]]]
-//                                   [--iq-balance MU,MINPOWER[,C0,D0]] [--shift HZ] [--fft TOPIC] [--devices 0,1,...]
+//                                   [--iq-balance MU,MINPOWER[,C0,D0]] [--shift HZ] [--notch HZ[,HZ...]:MU[,AFC,COH,PULLHZ]]
+//                                   [--fft TOPIC] [--devices 0,1,...]
 //                                               N synthetic LCG frames; one line per published
 //                                               message: frame topic rate bytes fnv1a64(payload)
 //                                               --u8 feeds them as dongle bytes, --format as integer samples of that
@@ -34,9 +35,15 @@
 //                                               --shift HZ: the frequency shift on the device, HZ at the main VFOs' rate; one
 //                                               more line per frame behind its messages (in front of the iq line),
 //                                               shift frame phase inc next_phase next_inc      (8 hex digits each)
+//                                               --notch HZ[,HZ...]:MU[,AFC,COH,PULLHZ]: the spur canceller on the device, up to eight
+//                                               tones in HZ at the main VFOs' rate (AFC 1, COH 0.5, PULLHZ 100 unless given); one
+//                                               more line per frame behind its messages (in front of the shift line),
+//                                               notch frame blocks then per tone: tracked_hz inc inc_next a_re_bits a_im_bits
+//                                                  coherent adapted clamped rejected
 #include <cinttypes>
 #include <cstdio>
 #include <iostream>
+#include <sstream>
 
 #include "sdrx_host.hpp"
 
@@ -56,7 +63,7 @@ static uint64_t fnv1a(const void *p, size_t n)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ] [--front-stages N [--front-real] [--front-taps K]] [--blanker RATIO,GUARD[,FLOOR[,RANK]]] [--iq-balance MU,MINPOWER[,C0,D0]] [--shift HZ] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s profile.ini --dump | --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ] [--front-stages N [--front-real] [--front-taps K]] [--blanker RATIO,GUARD[,FLOOR[,RANK]]] [--iq-balance MU,MINPOWER[,C0,D0]] [--shift HZ] [--notch HZ[,HZ...]:MU[,AFC,COH,PULLHZ]] [--fft TOPIC] [--devices 0,1,...]\n", argv[0]);
         return 2;
     }
     try {
@@ -93,6 +100,10 @@ int main(int argc, char **argv)
         float iq_mu = 0, iq_min_power = 0, iq_c0 = 0, iq_d0 = 1;
         bool shift = false;
         double shift_hz = 0;
+        bool notch = false;
+        std::vector<double> notch_hz;
+        float notch_mu = 0, notch_afc = 1.0f, notch_coh = 0.5f;
+        double notch_pull = 100.0;
         std::string fft_topic;
         std::vector<int> devices;
         for (int a = 4; a < argc; ++a) {
@@ -128,6 +139,22 @@ int main(int argc, char **argv)
                 if (std::sscanf(argv[++a], "%lf", &shift_hz) != 1)
                     throw std::runtime_error("--shift takes HZ");
                 shift = true;
+            } else if (std::string(argv[a]) == "--notch" && a + 1 < argc) {
+                const std::string spec = argv[++a];
+                const size_t colon = spec.find(':');
+                if (colon == std::string::npos)
+                    throw std::runtime_error("--notch takes HZ[,HZ...]:MU[,AFC,COH,PULLHZ]");
+                std::stringstream tones(spec.substr(0, colon));
+                for (std::string item; std::getline(tones, item, ',');) {
+                    double v = 0;
+                    if (std::sscanf(item.c_str(), "%lf", &v) != 1)
+                        throw std::runtime_error("--notch: a tone is a number of Hz");
+                    notch_hz.push_back(v);
+                }
+                const int got = std::sscanf(spec.c_str() + colon + 1, "%f,%f,%f,%lf", &notch_mu, &notch_afc, &notch_coh, &notch_pull);
+                if ((got != 1 && got != 4) || notch_hz.empty())
+                    throw std::runtime_error("--notch takes HZ[,HZ...]:MU[,AFC,COH,PULLHZ]");
+                notch = true;
             } else if (std::string(argv[a]) == "--fft" && a + 1 < argc)
                 fft_topic = argv[++a];
             else if (std::string(argv[a]) == "--devices" && a + 1 < argc) { // one tree sharded over several GPUs
@@ -181,6 +208,8 @@ int main(int argc, char **argv)
             radio.setIqBalance(iq_mu, iq_min_power, iq_c0, iq_d0);
         if (shift)
             radio.setShift(shift_hz);
+        if (notch)
+            radio.setNotch(notch_hz, notch_mu, notch_afc, notch_coh, notch_pull);
         if (input_rate > 0 || front_stages > 0)
             radio.start();
         if (input_rate > 0) {
@@ -224,6 +253,14 @@ int main(int argc, char **argv)
                 radio.demodBytes(bytes.data(), n_frame);
             else
                 radio.demodData(iq.data(), (int)iq.size());
+            if (notch) {
+                const sdrx_notch_record r = radio.notch();
+                std::printf("notch %d %u", frame_no, r.blocks);
+                for (uint32_t k = 0; k < r.n_tones; ++k)
+                    std::printf(" %.3f %08x %08x %08x %08x %u %u %u %u", radio.notchHz(r, (int)k), r.tone[k].inc, r.tone[k].inc_next, r.tone[k].a_re_bits,
+                                r.tone[k].a_im_bits, r.tone[k].coherent, r.tone[k].adapted, r.tone[k].clamped, r.tone[k].rejected);
+                std::printf("\n");
+            }
             if (shift) {
                 const sdrx_shift_record s = radio.shift();
                 std::printf("shift %d %08x %08x %08x %08x\n", frame_no, s.phase, s.inc, s.next_phase, s.next_inc);

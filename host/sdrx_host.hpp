@@ -265,6 +265,35 @@ public:
         const double hz = hz_now - gain * drift_hz;
         return hz > fs_tree / 2 ? fs_tree / 2 : hz < -fs_tree / 2 ? -fs_tree / 2 : hz;
     }
+    // The spur canceller on the device (include/sdrx.h "Spur canceller"): up to SDRX_NOTCH_MAX steady carriers that are not signals,
+    // given in Hz at the parent-less VFOs' rate to within tens of Hz, tracked and subtracted from the tree's raw frame in front of
+    // the shift.  mu: the amplitude loop's gain; afc_gain: the frequency loop's (0 holds the frequencies); min_coherence: its gate;
+    // max_pull_hz: how far a tone may move from where it was given.  Before the first frame it switches the stage on; afterwards
+    // it changes the settings between two frames (a tone whose frequency is unchanged keeps its state).  One device only.
+    void setNotch(const std::vector<double> &hz, float mu, float afc_gain, float min_coherence, double max_pull_hz)
+    {
+        if (grp_)
+            throw std::runtime_error("sdrj: the spur canceller (setNotch) is not offered on several devices");
+        if (hz.size() > SDRX_NOTCH_MAX)
+            throw std::runtime_error("sdrj::setNotch: at most SDRX_NOTCH_MAX tones");
+        nt_hz_ = hz, nt_mu_ = mu, nt_afc_ = afc_gain, nt_coh_ = min_coherence, nt_pull_hz_ = max_pull_hz;
+        if (ctx_) {
+            const sdrx_notch_cfg cfg = notch_cfg();
+            check(sdrx_set_notch(ctx_, &cfg), "sdrx_set_notch");
+        }
+        nt_on_ = true;
+    }
+    // ... and its record of the last delivered frame: per tone the increment used and the next one, the amplitude, the flags, S, P, E
+    sdrx_notch_record notch()
+    {
+        if (!ctx_ || !nt_on_)
+            throw std::runtime_error("sdrj::notch: no spur canceller set, or not started");
+        sdrx_notch_record r;
+        check(sdrx_get_notch(ctx_, nullptr, &r), "sdrx_get_notch");
+        return r;
+    }
+    // the frequency a tone of that record is tracked at, in Hz at the parent-less VFOs' rate
+    double notchHz(const sdrx_notch_record &r, int k) const { return sdrx_shift_hz((double)(*mpVFOs)[0]->d.fs, r.tone[k].inc_next); }
     // sdrj.cpp:84-101: the raw spectrum is selected by the topic "Main"; any selection restarts
     // the every-4th-call counter of demodData (sdrj.cpp:296-303)
     void fftVFOSlot(const std::string &topic)
@@ -289,6 +318,8 @@ public:
             throw std::runtime_error("sdrj: the IQ balance correction (setIqBalance) is not offered on several devices");
         if (devices_.size() > 1 && sh_on_)
             throw std::runtime_error("sdrj: the frequency shift (setShift) is not offered on several devices");
+        if (devices_.size() > 1 && nt_on_)
+            throw std::runtime_error("sdrj: the spur canceller (setNotch) is not offered on several devices");
         if (devices_.size() > 1) {
             check(sdrx_group_create(&grp_, devices_.data(), (int)devices_.size()), "sdrx_group_create");
             for (auto &kv : options_)
@@ -321,6 +352,10 @@ public:
         if (sh_on_) {
             const sdrx_shift_cfg cfg = shift_cfg();
             check(sdrx_set_shift(ctx_, &cfg), "sdrx_set_shift");
+        }
+        if (nt_on_) {
+            const sdrx_notch_cfg cfg = notch_cfg();
+            check(sdrx_set_notch(ctx_, &cfg), "sdrx_set_notch");
         }
         check(sdrx_set_publish_callback(ctx_, &sdrj::trampoline, this), "sdrx_set_publish_callback");
         check(sdrx_finalize(ctx_), "sdrx_finalize");
@@ -717,6 +752,23 @@ private:
         sdrx_shift_cfg cfg{};
         if (sdrx_shift_inc((double)(*mpVFOs)[0]->d.fs, shift_hz_, &cfg.inc) != SDRX_OK)
             throw std::runtime_error("sdrj::setShift: the shift must be finite and at most half the main VFOs' sample rate");
+        return cfg;
+    }
+    bool nt_on_ = false; // setNotch
+    std::vector<double> nt_hz_;
+    float nt_mu_ = 0, nt_afc_ = 0, nt_coh_ = 0;
+    double nt_pull_hz_ = 0.0;
+    sdrx_notch_cfg notch_cfg() const // the tones and the pull at the first main's rate
+    {
+        sdrx_notch_cfg cfg{};
+        const double fs = (double)(*mpVFOs)[0]->d.fs;
+        cfg.n_tones = (uint32_t)nt_hz_.size();
+        cfg.mu = nt_mu_, cfg.afc_gain = nt_afc_, cfg.min_coherence = nt_coh_;
+        bool ok = nt_pull_hz_ >= 0 && sdrx_shift_inc(fs, nt_pull_hz_, &cfg.max_pull) == SDRX_OK;
+        for (size_t k = 0; ok && k < nt_hz_.size(); ++k)
+            ok = sdrx_shift_inc(fs, nt_hz_[k], &cfg.inc0[k]) == SDRX_OK;
+        if (!ok)
+            throw std::runtime_error("sdrj::setNotch: the tones and the pull must be finite and at most half the main VFOs' sample rate");
         return cfg;
     }
 };

@@ -1123,6 +1123,98 @@ void sdrx_shift_tables(float *out);
 int sdrx_shift_inc(double fs_tree, double hz, uint32_t *inc);
 double sdrx_shift_hz(double fs_tree, uint32_t inc);
 
+/* ---- Spur canceller (sdrx_set_notch before sdrx_finalize) ------------------------------------------------------------
+ * Narrow steady carriers that are not signals -- a dongle's clock spurs, a switching regulator's harmonics, a neighbour's birdie --
+ * removed from the wideband frame in one pass before the tree fans out: up to SDRX_NOTCH_MAX tones, each a complex amplitude times
+ * a table oscillator, the amplitude estimated in blocks of L = 4096 samples, smoothed by a one-pole loop and subtracted one block
+ * late, the frequency of each tone re-estimated once a frame from how the block estimates rotate.  A tone given to within tens of Hz
+ * is locked and removed, and the record tells where it really is.  The stage sits behind the resampler or whatever comes last in the
+ * ingest chain and directly in front of the frequency shift: in place on the tree's raw frame, at the tree's rate, so a tone's
+ * frequency is the front end's and does not move when the shift does.  The reference has no counterpart (its DC removal is a notch
+ * at 0 Hz only).  This text is the definition, sdrreceiver_amd/notch.py restates it in numpy, and the device is held to that bit for
+ * bit.  No FMA anywhere; the same in every setting of option "exact".  Off (the default) nothing changes at all: the same kernels,
+ * launches, device_bytes, payloads and callbacks.
+ *
+ * Settings (sdrx_notch_cfg): n_tones (0 .. 8; 0 = off), inc0[k] (uint32, units of 2^-32 turn a sample, made by sdrx_shift_inc), mu
+ * (fp32, 0 < mu <= 1), afc_gain (fp32, 0 .. 1; 0 holds the frequencies), min_coherence (fp32, 0 < c <= 1), max_pull (uint32, inc
+ * units: how far a tone may move from its inc0), flags (bit 0 SDRX_NOTCH_LOAD), reserved words and unused tone slots 0.  Anything
+ * else is SDRX_EINVAL; no defaults are offered.  Two tones whose inc0 are closer than 8 2^32 / L = 2^23 (circular distance) are
+ * refused: a block correlation sees another tone D bins away at 1 / (pi D) of its amplitude, and that leakage is never cancelled
+ * because the measurement is on the input -- at 8 bins it is 4 % of the other tone's amplitude.
+ * State, per tone: phase, inc (uint32), a (two fp32).  After sdrx_finalize: 0, inc0, 0.
+ *
+ * A frame of n samples is cut into blocks b = 0 .. of L samples; the last has L_b = n - b L samples, which may be fewer than L.
+ * 1. Oscillator.  rot_k[j] is the frequency shift's rotation for p = phase_k + j inc_k (mod 2^32): the same three tables
+ *    (sdrx_shift_tables), the same index split, the same (x) of three fp32 roundings a component in the same operand order.
+ * 2. Block correlation.  t = x[j] (x) conj(rot_k[j]), the conjugate exact.  A lane sums its 16 consecutive samples in ascending
+ *    order from +0, one fp32 addition a step and a component.  The 64 lanes of a wave (1024 samples) combine in the fixed tree "at
+ *    distance s = 1, 2, 4, .., 32, lane l with l mod 2s = 0 takes fl(v[l] + v[l + s])"; the four waves of the block combine as
+ *    fl(fl(w0 + w1) + fl(w2 + w3)).  Lanes behind the frame's end carry +0.  The result is c[b][k].  The order does not depend on
+ *    the frame.
+ * 3. Loop.  One sequence per tone, b ascending, every operation a single IEEE double operation in the written order:
+ *      m_b = c[b][k] / L_b                       per component
+ *      used[b][k] = a                            as fp32: the value in front of the update -- the estimate of block b comes from the
+ *                                                blocks before it, for block 0 from the frame before
+ *      a <- (float)(a + mu (m_b - a))            per component
+ *    and if either component of the new a is not finite: a <- 0 (both), rejected += 1, and the sequence goes on.
+ * 4. Subtraction.  y[j] = x[j]; then for k ascending y <- fl(y - (used[b][k] (x) rot_k[j])) per component.  A component that is a
+ *    NaN is the quiet NaN 0x7fc00000.
+ * 5. Frequency.  Over the FULL blocks only, b = 1 .. nfull - 1 (nfull = floor(n / L)); nothing is done with fewer than two full
+ *    blocks.  Accumulated in double, b ascending (each term fl(fl(.) +- fl(.)), then one addition to the sum):
+ *      S_re = sum (mr_b mr_{b-1} + mi_b mi_{b-1})     S_im = sum (mi_b mr_{b-1} - mr_b mi_{b-1})     P = sum (mr_b^2 + mi_b^2)
+ *      E    = sum ((mr_b - used_re)^2 + (mi_b - used_im)^2)      with used[b][k]: what the estimate missed
+ *      coherent = S_re > 0 && S_re >= min_coherence P
+ *    If coherent and afc_gain > 0 (adapted = 1):
+ *      r = S_im / S_re;  r = r > 1 ? 1 : r;  r = r >= -1 ? r : -1          (a NaN is -1)
+ *      d = rint((afc_gain r) 166886.05360752725)                          (2^20 / (2 pi) = 2^32 / (2 pi L): one block's rotation
+ *                                                                          in inc units; ties to even)
+ *      inc_next = inc + d, then clamped so that the signed wrapped difference inc_next - inc0 stays within +-max_pull (clamped = 1
+ *      if that changed it)
+ *    else inc_next = inc.  Without the gate a tone that is not there lets inc walk on noise.  Only division, multiplication,
+ *    addition, comparison and rint occur.
+ * 6. Frame end.  phase_k += n inc_k with the inc that was USED; then inc_k = inc_next: the tone is phase-continuous across frames
+ *    and across frequency steps.
+ * The record of frame f (sdrx_notch_record): frame, n_complex, n_tones, blocks; per tone the inc used, inc_next, the bits of a at the
+ * end, coherent, adapted, clamped, rejected, and the doubles S_re, S_im, P, E (slots from n_tones on: zeros).
+ *
+ * sdrx_set_notch(ctx, cfg): before sdrx_finalize it switches the stage on (cfg == NULL or n_tones == 0: off again).  After
+ * sdrx_finalize it changes mu, afc_gain, min_coherence, max_pull and the tone list between two frames (n_tones may be 0 then: the
+ * frame passes unchanged); the list is held within the eight slots allocated at sdrx_finalize.  A slot whose inc0 is unchanged
+ * keeps phase, inc and a; a changed or new slot starts at (0, inc0, 0); SDRX_NOTCH_LOAD restarts every slot.  The write is a
+ * one-thread launch in stream order.  SDRX_ESTATE with submitted frames not yet delivered (the calls in flight are drained first),
+ * if the stage was not on at sdrx_finalize, or for cfg == NULL.
+ * sdrx_get_notch(ctx, cfg_out, record_out): the settings as last written, and the record of the last delivered frame under
+ * sdrx_get_blanker's rules (either may be NULL).
+ * in_frame is unchanged.  sdrx_get_raw, the raw-frame spectrum, the watch, the drift estimate, the band scan and the frequency shift
+ * see the notched frame; sdrx_get_resampler_input, sdrx_get_blanker_input and the ADC meter see what they saw.  A cf32 host frame
+ * or a caller's device frame is copied into the context's own buffer first: the caller's buffer is never written.  Offered behind
+ * every ingest chain, a real first front stage included.  sdrx_*_shared and sdrx_*_if_same return SDRX_ESTATE if either context has
+ * the stage.  Groups do not offer it. */
+#define SDRX_NOTCH_MAX 8
+#define SDRX_NOTCH_LOAD 1u
+typedef struct sdrx_notch_cfg { /* 96 bytes */
+    uint32_t n_tones, flags;
+    uint32_t max_pull, reserved0;
+    float mu, afc_gain, min_coherence;
+    uint32_t reserved1;
+    uint32_t inc0[SDRX_NOTCH_MAX];
+    uint32_t reserved[8];
+} sdrx_notch_cfg;
+typedef struct sdrx_notch_tone { /* 64 bytes */
+    uint32_t inc, inc_next;
+    uint32_t a_re_bits, a_im_bits;
+    uint32_t coherent, adapted, clamped, rejected;
+    double s_re, s_im, p, e;
+} sdrx_notch_tone;
+typedef struct sdrx_notch_record { /* 544 bytes */
+    int64_t frame;
+    uint32_t n_complex, n_tones, blocks;
+    uint32_t reserved[3];
+    sdrx_notch_tone tone[SDRX_NOTCH_MAX];
+} sdrx_notch_record;
+int sdrx_set_notch(sdrx_ctx *ctx, const sdrx_notch_cfg *cfg);
+int sdrx_get_notch(sdrx_ctx *ctx, sdrx_notch_cfg *cfg_out, sdrx_notch_record *record_out);
+
 /* decimate[decimateCount] of node `id` (public member vfo.h:39 -- what the fftData signal
  * carries, vfo.cpp:290-293): copies up to max_complex cf32 to `out`, returns the count in *n. */
 int sdrx_get_stream(sdrx_ctx *ctx, int id, float *out_iq, int max_complex, int *n);

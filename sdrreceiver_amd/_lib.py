@@ -192,6 +192,25 @@ class ShiftRecordC(C.Structure):
                 ("next_phase", C.c_uint32), ("next_inc", C.c_uint32), ("reserved", C.c_uint32 * 8)]
 
 
+class NotchCfgC(C.Structure):
+    """struct sdrx_notch_cfg"""
+    _fields_ = [("n_tones", C.c_uint32), ("flags", C.c_uint32), ("max_pull", C.c_uint32), ("reserved0", C.c_uint32), ("mu", C.c_float),
+                ("afc_gain", C.c_float), ("min_coherence", C.c_float), ("reserved1", C.c_uint32), ("inc0", C.c_uint32 * 8), ("reserved", C.c_uint32 * 8)]
+
+
+class NotchToneC(C.Structure):
+    """struct sdrx_notch_tone"""
+    _fields_ = [("inc", C.c_uint32), ("inc_next", C.c_uint32), ("a_re_bits", C.c_uint32), ("a_im_bits", C.c_uint32), ("coherent", C.c_uint32),
+                ("adapted", C.c_uint32), ("clamped", C.c_uint32), ("rejected", C.c_uint32), ("s_re", C.c_double), ("s_im", C.c_double),
+                ("p", C.c_double), ("e", C.c_double)]
+
+
+class NotchRecordC(C.Structure):
+    """struct sdrx_notch_record"""
+    _fields_ = [("frame", C.c_int64), ("n_complex", C.c_uint32), ("n_tones", C.c_uint32), ("blocks", C.c_uint32), ("reserved", C.c_uint32 * 3),
+                ("tone", NotchToneC * 8)]
+
+
 PUBLISH_FN =C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_char), C.c_uint32, C.c_void_p, C.c_uint32)
 
 # every symbol include/sdrx.h declares: (restype, argtypes)
@@ -300,6 +319,8 @@ SYMBOLS = {
     "sdrx_shift_tables": (None, [_vp]),
     "sdrx_shift_inc": (_i, [C.c_double, C.c_double, C.POINTER(C.c_uint32)]),
     "sdrx_shift_hz": (C.c_double, [C.c_double, C.c_uint32]),
+    "sdrx_set_notch": (_i, [_vp, C.POINTER(NotchCfgC)]),
+    "sdrx_get_notch": (_i, [_vp, C.POINTER(NotchCfgC), C.POINTER(NotchRecordC)]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

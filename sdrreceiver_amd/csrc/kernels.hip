@@ -35,6 +35,9 @@
 //   k_shift, k_shift_step shift.hip     mix_offset (README "tune ALL VFO's up or down"), as one stage: sdrx_set_shift -- the frequency shift at the end
 //                                       of the ingest chain, in place on the tree's raw frame: y = x exp(+j 2 pi p / 2^32) from three 256-entry
 //                                       tables, the 32-bit phase carried on the device from frame to frame; include/sdrx.h "Frequency shift")
+//   k_notch_corr, k_notch_step, k_notch_apply notch.hip (none: sdrx_set_notch -- the spur canceller in front of the frequency shift, in place on the
+//                                       tree's raw frame: up to eight tones, each a tracked complex amplitude times the shift's table oscillator,
+//                                       estimated per block of 4096 samples and subtracted one block late; include/sdrx.h "Spur canceller")
 //   k_mix_decimate        mix.hip       vfo::process mix loop, vfo.cpp:237-245; HalfBandDecimator::decimate, halfbanddecimator.cpp:43-72,
 //                                       with FIR::...HalfBandQueue, dsp.cpp:96-173 (mix_item); option fuse_late: the FIR part of
 //                                       vfo::usb_decimdemod, vfo.cpp:334-356, inside a d = 0 leaf's wave (late_item); option fuse_demod:
@@ -59,6 +62,7 @@
 #include "sdrx_blank.h"
 #include "sdrx_iqbal.h"
 #include "sdrx_shift.h"
+#include "sdrx_notch.h"
 
 #include <type_traits>
 #include <utility>
@@ -74,6 +78,7 @@ namespace sdrx {
 #include "blank.hip"
 #include "iqbal.hip"
 #include "shift.hip"
+#include "notch.hip"
 #include "meter.hip"
 #include "demod.hip"
 #include "mix.hip"

@@ -84,6 +84,15 @@ static_assert(sizeof(sdrx_shift_cfg) == 32 && sizeof(ShiftCfg) == 32 && offsetof
                   offsetof(sdrx_shift_record, next_inc) == offsetof(ShiftRecord, next_inc) && offsetof(sdrx_shift_record, reserved) == offsetof(ShiftRecord, reserved) &&
                   sizeof(ShiftState) == 16 && SDRX_SHIFT_LOAD_PHASE == kShLoadPhase,
               "sdrx_shift_cfg / sdrx_shift_record ABI layout");
+static_assert(sizeof(sdrx_notch_cfg) == 96 && sizeof(NotchCfg) == 96 && offsetof(sdrx_notch_cfg, max_pull) == offsetof(NotchCfg, max_pull) &&
+                  offsetof(sdrx_notch_cfg, mu) == offsetof(NotchCfg, mu) && offsetof(sdrx_notch_cfg, min_coherence) == offsetof(NotchCfg, min_coherence) &&
+                  offsetof(sdrx_notch_cfg, inc0) == offsetof(NotchCfg, inc0) && offsetof(sdrx_notch_cfg, reserved) == offsetof(NotchCfg, reserved) &&
+                  sizeof(sdrx_notch_tone) == 64 && sizeof(NotchToneRecord) == 64 && offsetof(sdrx_notch_tone, a_re_bits) == offsetof(NotchToneRecord, a_re_bits) &&
+                  offsetof(sdrx_notch_tone, rejected) == offsetof(NotchToneRecord, rejected) && offsetof(sdrx_notch_tone, s_re) == offsetof(NotchToneRecord, s_re) &&
+                  offsetof(sdrx_notch_tone, e) == offsetof(NotchToneRecord, e) && sizeof(sdrx_notch_record) == 544 && sizeof(NotchRecord) == 544 &&
+                  offsetof(sdrx_notch_record, blocks) == offsetof(NotchRecord, blocks) && offsetof(sdrx_notch_record, tone) == offsetof(NotchRecord, tone) &&
+                  sizeof(NotchTone) == 32 && SDRX_NOTCH_LOAD == kNtLoad && SDRX_NOTCH_MAX == kNtMax,
+              "sdrx_notch_cfg / sdrx_notch_record ABI layout");
 static_assert(sizeof(sdrx_adc_arm) == 40 && sizeof(AdcArm) == 40 && offsetof(sdrx_adc_arm, longest_rail_run) == offsetof(AdcArm, longest_rail_run) &&
                   sizeof(sdrx_adc_meter) == 184 && sizeof(AdcRecord) == 184 && offsetof(sdrx_adc_meter, q) == offsetof(AdcRecord, q) &&
                   offsetof(sdrx_adc_meter, sum_iq) == offsetof(AdcRecord, sum_iq) && offsetof(sdrx_adc_meter, bits) == offsetof(AdcRecord, bits),
@@ -139,6 +148,7 @@ void free_device_state(sdrx_ctx *c)
     static_cast<sdrx_ctx::BlankerDevice &>(c->bl) = sdrx_ctx::BlankerDevice();
     static_cast<sdrx_ctx::IqDevice &>(c->iq) = sdrx_ctx::IqDevice();
     static_cast<sdrx_ctx::ShiftDevice &>(c->sh) = sdrx_ctx::ShiftDevice();
+    static_cast<sdrx_ctx::NotchDevice &>(c->nt) = sdrx_ctx::NotchDevice();
 }
 
 } // namespace
@@ -1302,6 +1312,70 @@ int sdrx_shift_inc(double fs_tree, double hz, uint32_t *inc)
 
 double sdrx_shift_hz(double fs_tree, uint32_t inc) { return shift_hz(fs_tree, inc); }
 
+// ---- Spur canceller (include/sdrx.h; sdrx_notch.h has the rules) -------------------------------------------------------------------
+int sdrx_set_notch(sdrx_ctx *c, const sdrx_notch_cfg *cfg)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (c->finalized && !c->nt.on)
+        return fail(c, SDRX_ESTATE, "sdrx_set_notch: the spur canceller was not switched on before sdrx_finalize");
+    if (!cfg) {
+        if (c->finalized)
+            return fail(c, SDRX_ESTATE, "sdrx_set_notch: the spur canceller is switched off before sdrx_finalize only");
+        c->nt.on = false;
+        return SDRX_OK;
+    }
+    NotchCfg N;
+    memcpy(&N, cfg, sizeof N);
+    if (const char *why = notch_args(N))
+        return fail(c, SDRX_EINVAL, "sdrx_set_notch: %s", why);
+    if (c->finalized) { // between two frames: every frame handed over ran with the settings it was launched with
+        if (c->in_flight > 0)
+            return fail(c, SDRX_ESTATE, "sdrx_set_notch: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
+        HIPCHK(c, hipSetDevice(c->device));
+        if (int rc = drain(c))
+            return rc;
+        // the tone list of the next frame, in stream order: a slot whose inc0 stays keeps phase, increment and amplitude
+        NotchLoad a;
+        memcpy(a.inc0, N.inc0, sizeof a.inc0);
+        a.restart = notch_restart_mask(c->nt.cfg, N);
+        if (a.restart)
+            hipLaunchKernelGGL(k_notch_load, dim3(1), dim3(64), 0, c->st.stream, c->nt.d_state.get(), a);
+    } else if (N.n_tones == 0) { // no tones before sdrx_finalize: off
+        c->nt.on = false;
+        return SDRX_OK;
+    }
+    c->nt.cfg = N;
+    c->nt.on = true;
+    return SDRX_OK;
+}
+
+int sdrx_get_notch(sdrx_ctx *c, sdrx_notch_cfg *cfg_out, sdrx_notch_record *out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_get_notch before sdrx_finalize");
+    if (!c->nt.on)
+        return fail(c, SDRX_ESTATE, "sdrx_get_notch: no spur canceller set (sdrx_set_notch before sdrx_finalize)");
+    if (!cfg_out && !out)
+        return fail(c, SDRX_EINVAL, "sdrx_get_notch: null output pointers");
+    if (cfg_out) // the settings as last written
+        memcpy(cfg_out, &c->nt.cfg, sizeof *cfg_out);
+    if (out) {
+        if (int rc = need_delivered(c, "sdrx_get_notch"))
+            return rc;
+        const int p = c->host_slot;
+        const sdrx_ctx::Notch::Used &U = c->nt.used[p];
+        if (!U.any || U.frame != c->host_frame)
+            return fail(c, SDRX_EHIP, "sdrx_get_notch: frame %llu did not pass the spur canceller", c->host_frame);
+        memcpy(out, c->nt.rec.host<NotchRecord>(p), sizeof *out);
+        if (!out->n_complex || out->frame != (int64_t)c->host_frame) // (a slot never written holds zeros)
+            return fail(c, SDRX_EHIP, "sdrx_get_notch: the record of frame %llu did not arrive (it names frame %lld)", c->host_frame, (long long)out->frame);
+    }
+    return SDRX_OK;
+}
+
 int sdrx_get_stream(sdrx_ctx *c, int id, float *out, int max_complex, int *n_ret)
 {
     if (!c || id < 0 || id >= (int)c->nodes.size())
@@ -1552,7 +1626,7 @@ int sdrx_get_stats(sdrx_ctx *c, sdrx_stats *s)
     s->algorithmic_bytes_per_frame = c->alg_bytes;
     s->vfo_samples_per_frame = c->vfo_samples;
     const size_t raw_bytes = c->d_raw[0].bytes() + c->d_raw_u8[0].bytes(); // (ONE parity of the host-fed frames' buffers: kept for compatibility)
-    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes() + c->adc.bytes() + c->rs.bytes() + c->fr.bytes() + c->bl.bytes() + c->iq.bytes() + c->sh.bytes());
+    s->device_bytes = (int64_t)(c->arena_bytes + 2 * c->pay_bytes + raw_bytes + c->sq.bytes() + c->park.d_act.bytes() + c->watch.bytes() + c->drift.bytes() + c->scan.bytes() + c->agc.bytes() + c->wake.bytes() + c->adc.bytes() + c->rs.bytes() + c->fr.bytes() + c->bl.bytes() + c->iq.bytes() + c->sh.bytes() + c->nt.bytes());
     s->frames = (int64_t)c->frame_no;
     s->mix_chunks_per_frame = c->mix_chunks;
     if (c->dc.d_counters) { // (waits for what is queued: a measurement call)

@@ -460,7 +460,26 @@ struct sdrx_ctx : CtxBuffers {
             ShiftCfg cfg{};
         } used[2];
     } sh;
-    bool tiled_ingest() const { return staged() || iq.on || sh.on; } // every frame goes through an ingest kernel into the tile layout
+    // Spur canceller (sdrx_set_notch, notch.hip): k_notch_corr / _step / _apply in place on the tree's raw frame, in
+    // front of k_shift.  What finalize allocates with it: the eight tone slots, c[b][k] and used[b][k] of one frame's blocks, the
+    // record of frame f (`rec`) and -- unless the shift is on, whose copy then serves both -- the three tables.  `used` as for the
+    // shift; cfg.flags: of the last call.
+    struct NotchDevice { // what free_device_state releases
+        DevBuf<NotchTone> d_state;  // kNtMax slots
+        DevBuf<ShiftC> d_c, d_used; // blocks * kNtMax each
+        DevBuf<float2> d_tab;       // A | B | C; empty with the shift on
+        Records rec;
+        size_t bytes() const { return d_state.bytes() + d_c.bytes() + d_used.bytes() + d_tab.bytes() + 2 * rec.bytes(); }
+    };
+    struct Notch : NotchDevice {
+        bool on = false; // set before sdrx_finalize
+        NotchCfg cfg{};  // of the next frame: as last written
+        struct Used {
+            unsigned long long frame = 0;
+            bool any = false;
+        } used[2];
+    } nt;
+    bool tiled_ingest() const { return staged() || iq.on || sh.on || nt.on; } // every frame goes through an ingest kernel into the tile layout
     int in_frame = 0; // samples of an incoming frame: root_frame, or with a resampler rs.plan.n_in; times 2^stages with a front stage
 
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot

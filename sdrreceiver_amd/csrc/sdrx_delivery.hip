@@ -107,10 +107,10 @@ void publish_all(sdrx_ctx *c, int slot)
 // enqueue_frame, sdrx_frame.hip).
 // Option watch: the records of the frame of parity p, part of what always travels -- the watch's, then the drift's and the band
 // scan's of its sources, and option wake's of the controlled leaves (each: nothing before the first call that switched one on);
-// option adc_meter's record of the frame's integer samples, the blanker's, the IQ balance's and the frequency shift's record (each: nothing with it off)
+// option adc_meter's record of the frame's integer samples, the blanker's, the IQ balance's, the frequency shift's and the spur canceller's record (each: nothing with it off)
 int queue_watch(sdrx_ctx *c, int p, hipStream_t st)
 {
-    for (const sdrx_ctx::Records *r : {&c->watch.rec, &c->drift.rec, &c->scan.rec, &c->wake.rec, &c->adc.rec, &c->bl.rec, &c->iq.rec, &c->sh.rec})
+    for (const sdrx_ctx::Records *r : {&c->watch.rec, &c->drift.rec, &c->scan.rec, &c->wake.rec, &c->adc.rec, &c->bl.rec, &c->iq.rec, &c->sh.rec, &c->nt.rec})
         if (r->d[p])
             HIPCHK(c, hipMemcpyAsync(r->h[p], r->d[p], r->bytes(), hipMemcpyDeviceToHost, st));
     return SDRX_OK;

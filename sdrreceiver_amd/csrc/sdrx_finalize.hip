@@ -1194,6 +1194,31 @@ int shift_setup(sdrx_ctx *c)
     return SDRX_OK;
 }
 
+// Spur canceller: the eight tone slots at (0, inc0, 0), c[b][k] and used[b][k] of one frame's blocks, the record buffers of both
+// frame parities, and the three tables unless the shift's copy serves.  All of it or (the caller releases) none.
+int notch_setup(sdrx_ctx *c)
+{
+    for (sdrx_ctx::Notch::Used &u : c->nt.used)
+        u = sdrx_ctx::Notch::Used();
+    if (!c->nt.on)
+        return SDRX_OK;
+    const size_t per_frame = (size_t)notch_blocks(c->root_frame) * kNtMax;
+    if (c->nt.d_state.alloc(kNtMax) != hipSuccess || c->nt.d_c.alloc(per_frame, true) != hipSuccess || c->nt.d_used.alloc(per_frame, true) != hipSuccess ||
+        c->nt.rec.alloc(sizeof(NotchRecord)) != hipSuccess || (!c->sh.on && c->nt.d_tab.alloc(3 * kShTab) != hipSuccess))
+        return fail(c, SDRX_ENOMEM, "sdrx_finalize: no device memory for the spur canceller");
+    NotchTone st[kNtMax];
+    memset(st, 0, sizeof st);
+    for (int k = 0; k < (int)c->nt.cfg.n_tones; ++k)
+        st[k].inc = st[k].inc0 = st[k].inc_used = c->nt.cfg.inc0[k];
+    HIPCHK(c, hipMemcpy(c->nt.d_state, st, sizeof st, hipMemcpyHostToDevice));
+    if (!c->sh.on) {
+        std::vector<float> tab(3 * kShTab * 2);
+        shift_tables(tab.data());
+        HIPCHK(c, hipMemcpy(c->nt.d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return SDRX_OK;
+}
+
 int finalize_impl(sdrx_ctx *c)
 {
     if (int rc = derive_nodes(c))
@@ -1233,6 +1258,8 @@ int finalize_impl(sdrx_ctx *c)
     if (int rc = iqbal_setup(c))
         return rc;
     if (int rc = shift_setup(c))
+        return rc;
+    if (int rc = notch_setup(c))
         return rc;
     catchup_setup(c, B);
     c->sq.preroll_fused = false;

@@ -191,6 +191,27 @@ void iqbal_launch(sdrx_ctx *c)
     c->iq.used[p].cfg = Q;
 }
 
+// Spur canceller: k_notch_corr, k_notch_step and k_notch_apply for the next frame (c->frame_no), on the context's stream behind the
+// last kernel of the ingest chain and in front of the shift's, inside the same KIND_INGEST bracket.  In place on the tree's raw
+// frame.  Phase, increment and amplitude of every tone chain on the device in stream order.  Off: nothing.
+void notch_launch(sdrx_ctx *c)
+{
+    if (!c->nt.on)
+        return;
+    const NotchCfg &N = c->nt.cfg;
+    const int p = (int)(c->frame_no & 1ull), n = c->root_frame, K = (int)N.n_tones;
+    const float2 *tab = c->sh.on ? c->sh.d_tab.get() : c->nt.d_tab.get(); // (one device copy of the tables serves both)
+    float4 *buf = reinterpret_cast<float4 *>(c->d_raw_tiled.get());
+    if (K > 0)
+        hipLaunchKernelGGL(k_notch_corr, dim3(notch_workgroups(n)), dim3(kNtThreads), 0, c->st.stream, buf, n, K, c->nt.d_state.get(), tab, c->nt.d_c.get());
+    hipLaunchKernelGGL(k_notch_step, dim3(1), dim3(64), 0, c->st.stream, c->nt.d_state.get(), c->nt.d_c.get(), c->nt.d_used.get(), c->nt.rec.dev<NotchRecord>(p),
+                       (long long)c->frame_no, n, K, N.mu, N.afc_gain, N.min_coherence, N.max_pull);
+    if (K > 0)
+        hipLaunchKernelGGL(k_notch_apply, dim3(notch_workgroups(n)), dim3(kNtThreads), 0, c->st.stream, buf, n, K, c->nt.d_state.get(), tab, c->nt.d_used.get());
+    c->nt.used[p].frame = c->frame_no;
+    c->nt.used[p].any = true;
+}
+
 // Frequency shift: k_shift and k_shift_step for the next frame (c->frame_no), on the context's stream behind the last kernel of
 // the ingest chain, inside its KIND_INGEST bracket.  In place on the tree's raw frame (root_frame samples), in front of
 // everything that reads it.  Phase and increment chain on the device in stream order.  Off: nothing.
@@ -636,7 +657,7 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         // steps of this frame write the flag words and state regions the previous tail, gate and step read
         HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.ev_tail[p ^ 1], 0));
     if (c->tiled_ingest() && raw_mode != kRawTiled) {
-        // Resampler / front stage / blanker / IQ balance / shift: a natural-order frame (cf32, or a shared context's bytes) is at the input rate -- one layout pass into the
+        // Resampler / front stage / blanker / IQ balance / notch / shift: a natural-order frame (cf32, or a shared context's bytes) is at the input rate -- one layout pass into the
         // staging buffer, then k_resample, in front of everything that reads the tree's raw frame.  (A frame of integer samples
         // came through enqueue_samples_device, which did both: kRawTiled.)
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
@@ -651,6 +672,7 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         blank_launch(c);
         front_launch(c);
         resample_launch(c);
+        notch_launch(c);
         shift_launch(c);
         raw_mode = kRawTiled;
     }
@@ -946,6 +968,7 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
             Bracket b(c, c->st.stream, KIND_INGEST, 0);
             front_launch(c, dev_bytes, fmt);
             resample_launch(c);
+            notch_launch(c);
             shift_launch(c);
         }
         const int rc = enqueue_frame(c, dev_bytes, kRawTiled, egress);
@@ -984,6 +1007,7 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         blank_launch(c);
         front_launch(c);
         resample_launch(c);
+        notch_launch(c);
         shift_launch(c);
         mode = kRawTiled;
     } else if (correct_dc) {
@@ -998,9 +1022,10 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         blank_launch(c);
         front_launch(c);
         resample_launch(c);
+        notch_launch(c);
         shift_launch(c);
         mode = kRawTiled;
-    } else if (fmt != SDRX_FMT_CU8 || c->tiled_ingest()) { // (resampler, front stage, blanker, IQ balance, shift: they read the tile layout, so bytes take the pass too)
+    } else if (fmt != SDRX_FMT_CU8 || c->tiled_ingest()) { // (resampler, front stage, blanker, IQ balance, notch, shift: they read the tile layout, so bytes take the pass too)
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
         const int n_pairs = n_complex / 2;
         hipLaunchKernelGGL(K.ingest, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
@@ -1009,6 +1034,7 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         blank_launch(c);
         front_launch(c);
         resample_launch(c);
+        notch_launch(c);
         shift_launch(c);
         mode = kRawTiled;
     }
@@ -1085,8 +1111,8 @@ static int submit_shared(sdrx_ctx *c, sdrx_ctx *src, const char *what, bool sync
     if (!c || !src || c == src)
         return c ? fail(c, SDRX_EINVAL, "%s: needs another context as the source", what) : SDRX_EINVAL;
     if (c->tiled_ingest() || src->tiled_ingest())
-        return fail(c, SDRX_ESTATE, "%s: a context with a resampler, a front stage, a blanker, an IQ balance correction or a frequency shift (sdrx_set_resampler, sdrx_set_front, "
-                                    "sdrx_set_blanker, sdrx_set_iq_balance, sdrx_set_shift) shares no frames", what);
+        return fail(c, SDRX_ESTATE, "%s: a context with a resampler, a front stage, a blanker, an IQ balance correction, a spur canceller or a frequency shift (sdrx_set_resampler, "
+                                    "sdrx_set_front, sdrx_set_blanker, sdrx_set_iq_balance, sdrx_set_notch, sdrx_set_shift) shares no frames", what);
     if (!src->finalized || src->frame_no == 0 || (src->last_raw != kRawF32 && src->last_raw != kRawU8))
         return fail(c, SDRX_ESTATE, "%s: the source context has staged no host frame (floats or bytes without DC removal) yet", what);
     if (src->device != c->device)

@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, agc as _agc, blank as _blank, iqbal as _iqbal, drift as _drift, front as _front, ingest, meter, resample as _resample, scan as _scan, shift as _shift, squelch as _squelch, wake as _wake, watch as _watch
+from . import _lib, agc as _agc, blank as _blank, iqbal as _iqbal, drift as _drift, front as _front, ingest, meter, notch as _notch, resample as _resample, scan as _scan, shift as _shift, squelch as _squelch, wake as _wake, watch as _watch
 from .topology import Topology, VfoDesc
 
 
@@ -313,7 +313,10 @@ class Receiver(_LeafCalls):
                  squelch_auto: bool = False, park: bool = False, watch: bool = False, catchup: bool = False,
                  agc: bool = False, wake: bool = False, adc_meter: bool = False, input_rate: int | None = None,
                  resample_taps=32, resample_atten_db: float = 80.0, front_stages: int = 0, front_real: bool = False,
-                 front_taps=15, front_atten_db: float = 80.0, blanker=None, iq_balance=None, shift=None):
+                 front_taps=15, front_atten_db: float = 80.0, blanker=None, iq_balance=None, shift=None, notch=None):
+        # notch: the spur canceller in front of the shift (sdrreceiver_amd.notch) -- a notch.Cfg (increments and max_pull in inc
+        # units), or a dict of set_notch's keywords (hz=[...], max_pull_hz=..: converted at finalize); None: off.
+        self._notch = notch
         # shift: the frequency shift at the end of the ingest chain (sdrreceiver_amd.shift) -- a number is Hz at the tree's rate
         # (mix_offset's Hz; converted at finalize), a shift.Cfg or an (inc[, phase0]) tuple the 32-bit words themselves; None: off.
         self._shift = None if shift is None else _shift.Cfg(*shift) if isinstance(shift, (tuple, list)) else shift
@@ -427,6 +430,11 @@ class Receiver(_LeafCalls):
                 self.set_shift(inc=self._shift.inc, phase=self._shift.phase0)
             else:
                 self.set_shift(hz=float(self._shift))
+        if self._notch is not None:
+            if isinstance(self._notch, _notch.Cfg):
+                self._set_notch_cfg(self._notch)
+            else:
+                self.set_notch(**self._notch)
         self._chk(self.L.sdrx_finalize(self.h))
         self.finalized = True
 
@@ -553,6 +561,59 @@ class Receiver(_LeafCalls):
         d = _shift.record_dict(rec)
         d["cfg"] = _shift.cfg_of(cfg)
         d["hz"] = _shift.hz_of(self.tree_rate, d["inc"])
+        return d
+
+    def _set_notch_cfg(self, cfg) -> None:
+        c = _lib.NotchCfgC(n_tones=cfg.n_tones, flags=int(cfg.flags), max_pull=int(cfg.max_pull), mu=float(cfg.mu), afc_gain=float(cfg.afc_gain),
+                           min_coherence=float(cfg.min_coherence))
+        for k, v in enumerate(cfg.inc0):
+            c.inc0[k] = int(v)
+        self._chk(self.L.sdrx_set_notch(self.h, C.byref(c)))
+        self._notch = cfg if cfg.n_tones or self.finalized else None
+
+    def set_notch(self, hz=None, inc=None, mu: float | None = None, afc_gain: float | None = None, min_coherence: float | None = None,
+                  max_pull_hz: float | None = None, max_pull: int | None = None, load: bool = False, off: bool = False) -> None:
+        """The spur canceller's settings (``sdrx_set_notch``): the tones as ``hz`` at the tree's rate (``shift.inc_of``) or as
+        ``inc``, the 32-bit increments themselves; the loop gain ``mu``, the frequency loop's ``afc_gain`` (0 holds the
+        frequencies) and its gate ``min_coherence``; how far a tone may move from where it was given, ``max_pull_hz`` (or
+        ``max_pull`` in increment units).  No defaults: the first call names them all; a later call keeps what it does not name.
+        Before :meth:`finalize` this switches the stage on (``off=True``: off again); afterwards it changes the settings between
+        two frames -- a tone whose increment is unchanged keeps its state, a new or moved one starts afresh, ``load=True``
+        restarts all."""
+        if off:
+            self._chk(self.L.sdrx_set_notch(self.h, None))
+            self._notch = None
+            return
+        old = self._notch if isinstance(self._notch, _notch.Cfg) else None
+        if hz is not None and inc is not None:
+            raise ValueError("set_notch takes hz or inc")
+        if len(hz if hz is not None else inc if inc is not None else ()) > _notch.MAX:
+            raise ValueError("set_notch: at most 8 tones")
+        words = tuple(_shift.inc_of(self.tree_rate, v) for v in hz) if hz is not None else tuple(int(v) & _shift.M32 for v in inc) if inc is not None else \
+            old.inc0 if old else None
+        if max_pull_hz is not None:
+            if not 0 <= float(max_pull_hz) <= self.tree_rate / 2:
+                raise ValueError("set_notch: max_pull_hz lies in 0 .. half the tree's rate")
+            max_pull = _shift.inc_of(self.tree_rate, float(max_pull_hz))
+        vals = [words, mu, afc_gain, min_coherence, max_pull]
+        if old:
+            vals = [v if v is not None else o for v, o in zip(vals, (old.inc0, old.mu, old.afc_gain, old.min_coherence, old.max_pull))]
+        if any(v is None for v in vals):
+            raise ValueError("set_notch: the first call names the tones, mu, afc_gain, min_coherence and max_pull_hz (no defaults)")
+        self._set_notch_cfg(_notch.Cfg(vals[0], float(vals[1]), float(vals[2]), float(vals[3]), int(vals[4]), _notch.LOAD if load else 0))
+
+    @property
+    def notch(self) -> dict | None:
+        """The spur canceller's record of the last delivered frame (``sdrx_notch_record`` as a dict, ``tones`` a list of eight) with
+        ``cfg``, the settings as last written, and ``levels`` (``notch.levels``: per tone the tracked Hz, the amplitude, the
+        coherence, the depth figure and the lock flags); None without ``notch``."""
+        if self._notch is None:
+            return None
+        cfg, rec = _lib.NotchCfgC(), _lib.NotchRecordC()
+        self._chk(self.L.sdrx_get_notch(self.h, C.byref(cfg), C.byref(rec)))
+        d = _notch.record_dict(rec)
+        d["cfg"] = _notch.cfg_of(cfg)
+        d["levels"] = _notch.levels(d, self.tree_rate)
         return d
 
     def blanker_input(self) -> np.ndarray:
