@@ -227,7 +227,6 @@ __device__ __forceinline__ void demod_chunk(float *dm, const DemodCtx &C, const 
 // thread from the usb values parked in LDS, taps broadcast from LDS.  EXACT keeps one accumulator
 // per output and the reference's summation order (4 independent chains per thread give the ILP).
 constexpr int kDemodTile = 1024;
-constexpr int kPlaneLen = (kDemodTile + kMaxFir + kHilbert + 1) / 2 + 8;
 
 // ---- the non-exact arithmetics' MACs, two outputs per instruction ----------------------------------------------------------
 // Four outputs r = 0..3 of a thread share a window: at window entry k output r takes tap h[k - r] (the Hilbert sum: outputs
@@ -305,14 +304,23 @@ __device__ __forceinline__ void hilbert4_packed(const float *plane, const float 
     acc[0] = A.x, acc[1] = A.y, acc[2] = B.x, acc[3] = B.y;
 }
 
+// The block's window is staged in 16-byte UNITS: unit j = the sample pair at offsets r = 2 j, 2 j + 1 from `lo`, one per thread
+// and iteration, kStageUnits in all.  Every unit has a home in LDS whether the block wants it or not (no test per sample):
+//   sP0[j + 3] = Q(2 j)   sP1[j] = Q(2 j + 1)   sI[2 j - 62], sI[2 j - 61] = I(2 j), I(2 j + 1)   (sI[t] = I of usb value t)
+// which takes kDelay floats of slack in FRONT of sI for the units j < 31.
+constexpr int kStageIters = 3, kStageUnits = 256 * kStageIters;
+constexpr int kWindowUnits = (kDemodTile + kHilbert - 1) / 2; // units a block can want: nr <= 1148 (demod_block)
+constexpr int kSiFront = 64;                                  // >= kDelay, a multiple of 4
+static_assert(kWindowUnits > 256 * (kStageIters - 1) && kWindowUnits <= kStageUnits && kSiFront >= kDelay, "staging covers the window");
 struct DemodLds { // LDS of one 256-thread demodulation block
-    alignas(16) float sP0[kPlaneLen + 4]; // even offsets from `lo`, stored shifted by +3
-    alignas(16) float sP1[kPlaneLen + 4]; // odd offsets
-    alignas(16) float sI[kDemodTile + kMaxFir + 8];
+    alignas(16) float sP0[kStageUnits + 4]; // even offsets from `lo`, stored shifted by +3
+    alignas(16) float sP1[kStageUnits];     // odd offsets
+    alignas(16) float sIf[kSiFront + 2 * kStageUnits - kDelay + 2]; // sI = sIf + kSiFront
     alignas(16) float sU[kDemodTile + kMaxFir + 16];
     alignas(16) float sH[kMaxFir + 16];  // sH[m] = hu[m - 3]
 };
 static_assert(sizeof(DemodLds) % 16 == 0, "DemodLds is a whole number of 16-byte units");
+static_assert(7 * sizeof(DemodLds) <= 160 * 1024, "seven blocks of k_usb_demod per CU (its 7 waves per SIMD)");
 
 // METER: the block's output meter goes to the leaf's record blk (K2Vfo::meter_rel; not for a leaf with a long low-pass:
 // k_lpf_long meters that one).
@@ -320,7 +328,7 @@ template <bool EXACT, bool METER>
 __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, const BlockWork bw, unsigned long long frame_no, DemodLds &S,
                                             int tid)
 {
-    float *sP0 = S.sP0, *sP1 = S.sP1, *sI = S.sI, *sU = S.sU, *sH = S.sH;
+    float *sP0 = S.sP0, *sP1 = S.sP1, *sI = S.sIf + kSiFront, *sU = S.sU, *sH = S.sH;
     const K2Vfo *Dp = vfos + bw.vfo;
     const int blk = bw.blk;
     const int par = (int)(frame_no & 1ull);
@@ -359,33 +367,36 @@ __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, cons
     if (blk == 0) // history for the next frame: the last H entries of [hist | data]
         for (int j = tid; j < D.H; j += 256)
             gst2(snext + j, gld2(sbase + D.n + j));
-    const float2 *z = sbase + D.H; // sample 0 of this frame
     const int N = D.nlpf;
     const int E = N + (N & 1);                  // usb values m0-E .. m0+1023 are computed (t = 0 .. ntv-1)
-    const int ntv = D.tile + E;                 // <= 1024 when the host shortens the tile of a low-pass VFO by E: one usb pass
+    const int ntv = D.tile + E;                 // <= 1024: the host shortens the tile of a low-pass VFO by E (one usb pass)
     const int lo = m0 - E - (kHilbert - 1);     // first stream index touched (>= -H)
-    const int nr = ntv + (kHilbert - 1);        // offsets r = idx - lo in [0, nr)
-    // all of this thread's loads are issued before the first LDS write (a rolled load -> wait ->
-    // write loop would pay the memory latency once per iteration)
-    constexpr int kStageIters = (kDemodTile + kMaxFir + kHilbert + 255) / 256;
-    float2 stage[kStageIters];
+    // Offsets r = idx - lo in [0, nr), nr = ntv + 124 <= 1148, are what the block wants: kWindowUnits units at most.  H + lo is
+    // even and the stream starts on a 16-byte boundary (sdrx_finalize checks both: demod_window_rule), so unit j -- samples
+    // lo + 2 j and lo + 2 j + 1 -- is ONE aligned 16-byte load through a resource that ends at sample n: what lies beyond
+    // reads 0, dword by dword.  All of this thread's loads are issued before the first LDS write (a rolled load -> wait ->
+    // write loop would pay the memory latency once per iteration); the last iteration asks only for units the largest
+    // window has (the others would be bytes fetched for nothing) and gets zeros for the rest.
+    // Units past nr are written but feed no output that is kept: usb value t reads Q at r = t + 1 + 2 s <= t + 123 and I at
+    // sI[t], and only t < ntv is stored to sU below (r <= ntv + 122 < nr, sI[t] from r = t + 62 < nr); the threads
+    // whose t runs past ntv compute on them and drop the result.
+    const __amdgpu_buffer_rsrc_t win = window_rsrc(sbase, D.H + D.n);
+    const unsigned voff = 8u * (unsigned)(D.H + lo) + 16u * (unsigned)tid;
+    v4f stage[kStageIters];
 #pragma unroll
     for (int it = 0; it < kStageIters; ++it) {
-        const int r = tid + 256 * it, idx = lo + r;
-        stage[it] = (r < nr && idx < D.n) ? gld2(z + idx) : make_float2(0.f, 0.f);
+        unsigned off = voff + 4096u * it;
+        if (it == kStageIters - 1)
+            off = tid < kWindowUnits - 256 * it ? off : kNoLoad;
+        stage[it] = bld4(win, off);
     }
 #pragma unroll
     for (int it = 0; it < kStageIters; ++it) {
-        const int r = tid + 256 * it;
-        if (r < nr) {
-            if (r & 1)
-                sP1[r >> 1] = stage[it].y;
-            else
-                sP0[(r >> 1) + 3] = stage[it].y;
-            const int t = r - kDelay;           // I[u-62] for u = m0 - E + t
-            if (t >= 0 && t < ntv)
-                sI[t] = stage[it].x;
-        }
+        const int j = tid + 256 * it;
+        sP0[j + 3] = stage[it].y;
+        sP1[j] = stage[it].w;
+        sI[2 * j - kDelay] = stage[it].x; // I[u-62] for u = m0 - E + t, t = 2 j - 62 and the next
+        sI[2 * j - kDelay + 1] = stage[it].z;
     }
     __syncthreads();
 
@@ -427,6 +438,7 @@ __device__ __forceinline__ void demod_block(const K2Vfo *__restrict__ vfos, cons
     __syncthreads();
 
     // ---- audio low-pass (newest sample excluded) on 4 consecutive outputs, then int16
+    asm volatile("" : "+v"(tid)); // (multiples of tid are formed again here, not carried through the Hilbert sum in registers of their own)
     const int j0 = 4 * tid;
     const int m = m0 + j0;
     const bool emits = j0 < D.tile && m < D.n;

@@ -166,6 +166,20 @@ __device__ __forceinline__ void bst4(__amdgpu_buffer_rsrc_t r, unsigned byte_off
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v), r, (int)byte_off, 0, 0);
 }
 
+// Loads through a resource that ends where the data does: a dword whose offset lies at or beyond num_records reads 0.0f, so
+// "is this sample inside the frame" is the descriptor's business, not a compare and a branch per load.  The lane's whole
+// byte offset goes into the VGPR operand -- the range check looks at that operand (and the instruction's 12-bit offset) only,
+// never at a scalar offset.
+constexpr unsigned kNoLoad = kNoStore; // a byte offset beyond every stream: the lane reads zeros
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t window_rsrc(const float2 *base, int samples)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(base), 0, 8 * samples, 0x00020000);
+}
+__device__ __forceinline__ v4f bld4(__amdgpu_buffer_rsrc_t r, unsigned byte_off)
+{
+    return __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0));
+}
+
 // ---- lane helpers -----------------------------------------------------------------------------------------------------------
 // Whole-wave DPP shift by one lane (GFX9 `wave_shr:1`): lane l receives src of lane l-1,
 // lane 0 keeps `old`.  Lane semantics verified on gfx950 by tools/dpp_probe.hip.

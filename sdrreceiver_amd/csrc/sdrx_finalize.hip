@@ -405,6 +405,10 @@ void build_tail_work(sdrx_ctx *c, Built &B)
                 // keep two of the four waves busy for a whole Hilbert loop on ~50 values)
                 const int nl = n.long_lpf ? 0 : (int)n.lpf.size();
                 n.demod_tile = nl > 0 ? ((kDemodTile - (nl + (nl & 1))) & ~3) : kDemodTile;
+                // demod_window_rule: a block stages its window [hist | data] entries H + blk tile - E - 124 ... in 16-byte
+                // units, sample PAIRS (demod_block).  That entry is even for every blk because the history H and the tile are
+                // multiples of 4 and E is even; the stream's base must be a multiple of 16 bytes, and its 8 (H + n) bytes a
+                // 32-bit offset.  allocate_and_upload checks all of it on the descriptor it writes.
             }
             // (a leaf that demodulates in its mix wave has a descriptor -- the wave reads it -- but no blocks in this launch)
             for (int b = 0; !n.fused_demod && b < (n.n_out + n.demod_tile - 1) / n.demod_tile; ++b)
@@ -781,6 +785,15 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
         k.n = n.n_out;
         k.nlpf = n.long_lpf ? 0 : (int)n.lpf.size();
         k.tile = n.demod_tile;
+        if (!n.fused_demod) { // demod_window_rule (build_tail_work)
+            if ((k.H | k.tile) & 1)
+                return fail(c, SDRX_EUNSUPPORTED, "vfo %d: demodulation history %d or tile %d is odd", B.n2[q], k.H, k.tile);
+            for (int p = 0; p < 2; ++p)
+                if (reinterpret_cast<uintptr_t>(k.s[p]) % 16)
+                    return fail(c, SDRX_EUNSUPPORTED, "vfo %d: demodulation stream %d is not 16-byte aligned", B.n2[q], p);
+            if ((long long)k.H + k.n >= (1ll << 28))
+                return fail(c, SDRX_EUNSUPPORTED, "vfo %d: demodulation stream of %d samples exceeds a 32-bit byte offset", B.n2[q], k.n);
+        }
         k.meter_rel = c->opt_meter ? meter_rel(c, n) | n.meter_shift : 0;
     }
     for (size_t q = 0; q < B.d4.size(); ++q) {
