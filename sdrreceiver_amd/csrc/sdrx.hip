@@ -149,6 +149,73 @@ void free_device_state(sdrx_ctx *c)
     static_cast<sdrx_ctx::IqDevice &>(c->iq) = sdrx_ctx::IqDevice();
     static_cast<sdrx_ctx::ShiftDevice &>(c->sh) = sdrx_ctx::ShiftDevice();
     static_cast<sdrx_ctx::NotchDevice &>(c->nt) = sdrx_ctx::NotchDevice();
+    c->route = sdrx_ctx::IngestRoute();
+}
+
+// ---- What the setters and getters of the ingest stages with settings and a record share (sdrx_ctx::CfgStage) -------------------------
+// `what`: the call's name; `noun`: the stage's, as the messages say it -- "blanker", "IQ balance correction", "frequency shift",
+// "spur canceller".  The order of the checks decides which code a call that is wrong twice gets.
+constexpr int kStageOff = 1; // stage_set_entry: the call switched the stage off and is finished
+
+// Entry of a setter: an error code, kStageOff (`cfg` null before sdrx_finalize), or SDRX_OK: go on to the stage's argument check
+template <class S>
+int stage_set_entry(sdrx_ctx *c, S sdrx_ctx::*stage, const void *cfg, const char *what, const char *noun)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (c->finalized && !(c->*stage).on)
+        return fail(c, SDRX_ESTATE, "%s: the %s was not switched on before sdrx_finalize", what, noun);
+    if (!cfg) {
+        if (c->finalized)
+            return fail(c, SDRX_ESTATE, "%s: the %s is switched off before sdrx_finalize only", what, noun);
+        (c->*stage).on = false;
+        return kStageOff;
+    }
+    return SDRX_OK;
+}
+
+// A setter on a finalized context works between two frames: every frame handed over ran with the settings it was launched with
+int stage_set_between_frames(sdrx_ctx *c, const char *what)
+{
+    if (c->in_flight > 0)
+        return fail(c, SDRX_ESTATE, "%s: %d submitted frame(s) not yet delivered -- call sdrx_wait first", what, c->in_flight);
+    HIPCHK(c, hipSetDevice(c->device));
+    return drain(c);
+}
+
+// A getter: the settings the delivered frame ran with -- `cfg_as_written`: the settings as last written, which need no delivered
+// frame -- and its record of type Rec; `arrived`: whether the record's slot was ever written (a slot never written holds zeros).
+// `what` is "sdrx_get_<stage>": the setter's name is made from it.
+template <class Rec, class S, class CfgOut, class RecOut, class Arrived>
+int stage_get(sdrx_ctx *c, S sdrx_ctx::*stage, CfgOut *cfg_out, RecOut *out, const char *what, const char *noun, bool cfg_as_written, Arrived arrived)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!c->finalized)
+        return fail(c, SDRX_ESTATE, "%s before sdrx_finalize", what);
+    const S &st = c->*stage;
+    if (!st.on)
+        return fail(c, SDRX_ESTATE, "%s: no %s set (sdrx_set_%s before sdrx_finalize)", what, noun, what + strlen("sdrx_get_"));
+    if (!cfg_out && !out)
+        return fail(c, SDRX_EINVAL, "%s: null output pointers", what);
+    if (cfg_as_written && cfg_out) {
+        memcpy(cfg_out, &st.cfg, sizeof *cfg_out);
+        if (!out)
+            return SDRX_OK;
+    }
+    if (int rc = need_delivered(c, what))
+        return rc;
+    const int p = c->host_slot;
+    if (!st.used[p].any || st.used[p].frame != c->host_frame)
+        return fail(c, SDRX_EHIP, "%s: frame %llu did not pass the %s", what, c->host_frame, noun);
+    if (cfg_out && !cfg_as_written)
+        memcpy(cfg_out, &st.used[p].cfg, sizeof *cfg_out);
+    if (out) {
+        memcpy(out, st.rec.template host<Rec>(p), sizeof *out);
+        if (!arrived(*out) || out->frame != (int64_t)c->host_frame)
+            return fail(c, SDRX_EHIP, "%s: the record of frame %llu did not arrive (it names frame %lld)", what, c->host_frame, (long long)out->frame);
+    }
+    return SDRX_OK;
 }
 
 } // namespace
@@ -1111,25 +1178,13 @@ int sdrx_get_front(sdrx_ctx *c, sdrx_front_info *info, float *taps, int32_t cap)
 // ---- Impulse blanker (include/sdrx.h; sdrx_blank.h has the rules) ----------------------------------------------------------------
 int sdrx_set_blanker(sdrx_ctx *c, const sdrx_blanker_cfg *cfg)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (c->finalized && !c->bl.on)
-        return fail(c, SDRX_ESTATE, "sdrx_set_blanker: the blanker was not switched on before sdrx_finalize");
-    if (!cfg) {
-        if (c->finalized)
-            return fail(c, SDRX_ESTATE, "sdrx_set_blanker: the blanker is switched off before sdrx_finalize only");
-        c->bl.on = false;
-        return SDRX_OK;
-    }
+    if (int rc = stage_set_entry(c, &sdrx_ctx::bl, cfg, "sdrx_set_blanker", "blanker"))
+        return rc == kStageOff ? SDRX_OK : rc;
     if (const char *why = blank_args(cfg->ratio, cfg->floor, cfg->rank_q16, cfg->guard))
         return fail(c, SDRX_EINVAL, "sdrx_set_blanker: %s", why);
-    if (c->finalized) { // between two frames: every frame handed over ran with the settings it was launched with
-        if (c->in_flight > 0)
-            return fail(c, SDRX_ESTATE, "sdrx_set_blanker: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
-        HIPCHK(c, hipSetDevice(c->device));
-        if (int rc = drain(c))
+    if (c->finalized)
+        if (int rc = stage_set_between_frames(c, "sdrx_set_blanker"))
             return rc;
-    }
     c->bl.on = true;
     c->bl.cfg = BlankCfg{cfg->ratio, cfg->floor, cfg->rank_q16, cfg->guard, {0, 0, 0, 0}};
     return SDRX_OK;
@@ -1137,28 +1192,8 @@ int sdrx_set_blanker(sdrx_ctx *c, const sdrx_blanker_cfg *cfg)
 
 int sdrx_get_blanker(sdrx_ctx *c, sdrx_blanker_cfg *cfg_out, sdrx_blanker_record *out)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_get_blanker before sdrx_finalize");
-    if (!c->bl.on)
-        return fail(c, SDRX_ESTATE, "sdrx_get_blanker: no blanker set (sdrx_set_blanker before sdrx_finalize)");
-    if (!cfg_out && !out)
-        return fail(c, SDRX_EINVAL, "sdrx_get_blanker: null output pointers");
-    if (int rc = need_delivered(c, "sdrx_get_blanker"))
-        return rc;
-    const int p = c->host_slot;
-    const sdrx_ctx::Blanker::Used &U = c->bl.used[p];
-    if (!U.any || U.frame != c->host_frame)
-        return fail(c, SDRX_EHIP, "sdrx_get_blanker: frame %llu did not pass the blanker", c->host_frame);
-    if (cfg_out)
-        memcpy(cfg_out, &U.cfg, sizeof *cfg_out);
-    if (out) {
-        memcpy(out, c->bl.rec.host<BlankRecord>(p), sizeof *out);
-        if (!out->measured || out->frame != (int64_t)c->host_frame)
-            return fail(c, SDRX_EHIP, "sdrx_get_blanker: the record of frame %llu did not arrive (it names frame %lld)", c->host_frame, (long long)out->frame);
-    }
-    return SDRX_OK;
+    return stage_get<BlankRecord>(c, &sdrx_ctx::bl, cfg_out, out, "sdrx_get_blanker", "blanker", false,
+                                  [](const sdrx_blanker_record &r) { return r.measured != 0; });
 }
 
 int sdrx_get_blanker_input(sdrx_ctx *c, float *out, int32_t cap_complex)
@@ -1185,23 +1220,12 @@ int sdrx_get_blanker_input(sdrx_ctx *c, float *out, int32_t cap_complex)
 // ---- IQ balance correction (include/sdrx.h; sdrx_iqbal.h has the rules) ---------------------------------------------------------
 int sdrx_set_iq_balance(sdrx_ctx *c, const sdrx_iq_cfg *cfg)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (c->finalized && !c->iq.on)
-        return fail(c, SDRX_ESTATE, "sdrx_set_iq_balance: the IQ balance correction was not switched on before sdrx_finalize");
-    if (!cfg) {
-        if (c->finalized)
-            return fail(c, SDRX_ESTATE, "sdrx_set_iq_balance: the IQ balance correction is switched off before sdrx_finalize only");
-        c->iq.on = false;
-        return SDRX_OK;
-    }
+    if (int rc = stage_set_entry(c, &sdrx_ctx::iq, cfg, "sdrx_set_iq_balance", "IQ balance correction"))
+        return rc == kStageOff ? SDRX_OK : rc;
     if (const char *why = iq_args(cfg->mu, cfg->min_power, cfg->c0, cfg->d0, cfg->flags, cfg->reserved))
         return fail(c, SDRX_EINVAL, "sdrx_set_iq_balance: %s", why);
-    if (c->finalized) { // between two frames: every frame handed over ran with the settings it was launched with
-        if (c->in_flight > 0)
-            return fail(c, SDRX_ESTATE, "sdrx_set_iq_balance: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
-        HIPCHK(c, hipSetDevice(c->device));
-        if (int rc = drain(c))
+    if (c->finalized) {
+        if (int rc = stage_set_between_frames(c, "sdrx_set_iq_balance"))
             return rc;
         if (cfg->flags & SDRX_IQ_LOAD) // the pair of the next frame, in stream order
             hipLaunchKernelGGL(k_iqbal_load, dim3(1), dim3(64), 0, c->st.stream, c->iq.d_state.get(), cfg->c0, cfg->d0);
@@ -1214,51 +1238,20 @@ int sdrx_set_iq_balance(sdrx_ctx *c, const sdrx_iq_cfg *cfg)
 
 int sdrx_get_iq_balance(sdrx_ctx *c, sdrx_iq_cfg *cfg_out, sdrx_iq_record *out)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_get_iq_balance before sdrx_finalize");
-    if (!c->iq.on)
-        return fail(c, SDRX_ESTATE, "sdrx_get_iq_balance: no IQ balance correction set (sdrx_set_iq_balance before sdrx_finalize)");
-    if (!cfg_out && !out)
-        return fail(c, SDRX_EINVAL, "sdrx_get_iq_balance: null output pointers");
-    if (int rc = need_delivered(c, "sdrx_get_iq_balance"))
-        return rc;
-    const int p = c->host_slot;
-    const sdrx_ctx::Iq::Used &U = c->iq.used[p];
-    if (!U.any || U.frame != c->host_frame)
-        return fail(c, SDRX_EHIP, "sdrx_get_iq_balance: frame %llu did not pass the IQ balance correction", c->host_frame);
-    if (cfg_out)
-        memcpy(cfg_out, &U.cfg, sizeof *cfg_out);
-    if (out) {
-        memcpy(out, c->iq.rec.host<IqRecord>(p), sizeof *out);
-        if (!out->n_complex || out->frame != (int64_t)c->host_frame) // (a slot never written holds zeros)
-            return fail(c, SDRX_EHIP, "sdrx_get_iq_balance: the record of frame %llu did not arrive (it names frame %lld)", c->host_frame, (long long)out->frame);
-    }
-    return SDRX_OK;
+    return stage_get<IqRecord>(c, &sdrx_ctx::iq, cfg_out, out, "sdrx_get_iq_balance", "IQ balance correction", false,
+                               [](const sdrx_iq_record &r) { return r.n_complex != 0; });
 }
 
 // ---- Frequency shift (include/sdrx.h; sdrx_shift.h has the rules) ------------------------------------------------------------------
 int sdrx_set_shift(sdrx_ctx *c, const sdrx_shift_cfg *cfg)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (c->finalized && !c->sh.on)
-        return fail(c, SDRX_ESTATE, "sdrx_set_shift: the frequency shift was not switched on before sdrx_finalize");
-    if (!cfg) {
-        if (c->finalized)
-            return fail(c, SDRX_ESTATE, "sdrx_set_shift: the frequency shift is switched off before sdrx_finalize only");
-        c->sh.on = false;
-        return SDRX_OK;
-    }
+    if (int rc = stage_set_entry(c, &sdrx_ctx::sh, cfg, "sdrx_set_shift", "frequency shift"))
+        return rc == kStageOff ? SDRX_OK : rc;
     if (const char *why = shift_args(cfg->flags, cfg->reserved))
         return fail(c, SDRX_EINVAL, "sdrx_set_shift: %s", why);
     const bool load = (cfg->flags & SDRX_SHIFT_LOAD_PHASE) != 0;
-    if (c->finalized) { // between two frames: every frame handed over ran with the increment it was launched with
-        if (c->in_flight > 0)
-            return fail(c, SDRX_ESTATE, "sdrx_set_shift: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
-        HIPCHK(c, hipSetDevice(c->device));
-        if (int rc = drain(c))
+    if (c->finalized) {
+        if (int rc = stage_set_between_frames(c, "sdrx_set_shift"))
             return rc;
         // the increment of the next frame, in stream order; the phase carries on unless the caller loads one
         hipLaunchKernelGGL(k_shift_load, dim3(1), dim3(64), 0, c->st.stream, c->sh.d_state.get(), cfg->inc, cfg->phase0, load ? 1 : 0);
@@ -1271,28 +1264,8 @@ int sdrx_set_shift(sdrx_ctx *c, const sdrx_shift_cfg *cfg)
 
 int sdrx_get_shift(sdrx_ctx *c, sdrx_shift_cfg *cfg_out, sdrx_shift_record *out)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_get_shift before sdrx_finalize");
-    if (!c->sh.on)
-        return fail(c, SDRX_ESTATE, "sdrx_get_shift: no frequency shift set (sdrx_set_shift before sdrx_finalize)");
-    if (!cfg_out && !out)
-        return fail(c, SDRX_EINVAL, "sdrx_get_shift: null output pointers");
-    if (int rc = need_delivered(c, "sdrx_get_shift"))
-        return rc;
-    const int p = c->host_slot;
-    const sdrx_ctx::Shift::Used &U = c->sh.used[p];
-    if (!U.any || U.frame != c->host_frame)
-        return fail(c, SDRX_EHIP, "sdrx_get_shift: frame %llu did not pass the frequency shift", c->host_frame);
-    if (cfg_out)
-        memcpy(cfg_out, &U.cfg, sizeof *cfg_out);
-    if (out) {
-        memcpy(out, c->sh.rec.host<ShiftRecord>(p), sizeof *out);
-        if (!out->n_complex || out->frame != (int64_t)c->host_frame) // (a slot never written holds zeros)
-            return fail(c, SDRX_EHIP, "sdrx_get_shift: the record of frame %llu did not arrive (it names frame %lld)", c->host_frame, (long long)out->frame);
-    }
-    return SDRX_OK;
+    return stage_get<ShiftRecord>(c, &sdrx_ctx::sh, cfg_out, out, "sdrx_get_shift", "frequency shift", false,
+                                  [](const sdrx_shift_record &r) { return r.n_complex != 0; });
 }
 
 void sdrx_shift_tables(float *out)
@@ -1315,25 +1288,14 @@ double sdrx_shift_hz(double fs_tree, uint32_t inc) { return shift_hz(fs_tree, in
 // ---- Spur canceller (include/sdrx.h; sdrx_notch.h has the rules) -------------------------------------------------------------------
 int sdrx_set_notch(sdrx_ctx *c, const sdrx_notch_cfg *cfg)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (c->finalized && !c->nt.on)
-        return fail(c, SDRX_ESTATE, "sdrx_set_notch: the spur canceller was not switched on before sdrx_finalize");
-    if (!cfg) {
-        if (c->finalized)
-            return fail(c, SDRX_ESTATE, "sdrx_set_notch: the spur canceller is switched off before sdrx_finalize only");
-        c->nt.on = false;
-        return SDRX_OK;
-    }
+    if (int rc = stage_set_entry(c, &sdrx_ctx::nt, cfg, "sdrx_set_notch", "spur canceller"))
+        return rc == kStageOff ? SDRX_OK : rc;
     NotchCfg N;
     memcpy(&N, cfg, sizeof N);
     if (const char *why = notch_args(N))
         return fail(c, SDRX_EINVAL, "sdrx_set_notch: %s", why);
-    if (c->finalized) { // between two frames: every frame handed over ran with the settings it was launched with
-        if (c->in_flight > 0)
-            return fail(c, SDRX_ESTATE, "sdrx_set_notch: %d submitted frame(s) not yet delivered -- call sdrx_wait first", c->in_flight);
-        HIPCHK(c, hipSetDevice(c->device));
-        if (int rc = drain(c))
+    if (c->finalized) {
+        if (int rc = stage_set_between_frames(c, "sdrx_set_notch"))
             return rc;
         // the tone list of the next frame, in stream order: a slot whose inc0 stays keeps phase, increment and amplitude
         NotchLoad a;
@@ -1352,28 +1314,8 @@ int sdrx_set_notch(sdrx_ctx *c, const sdrx_notch_cfg *cfg)
 
 int sdrx_get_notch(sdrx_ctx *c, sdrx_notch_cfg *cfg_out, sdrx_notch_record *out)
 {
-    if (!c)
-        return SDRX_EINVAL;
-    if (!c->finalized)
-        return fail(c, SDRX_ESTATE, "sdrx_get_notch before sdrx_finalize");
-    if (!c->nt.on)
-        return fail(c, SDRX_ESTATE, "sdrx_get_notch: no spur canceller set (sdrx_set_notch before sdrx_finalize)");
-    if (!cfg_out && !out)
-        return fail(c, SDRX_EINVAL, "sdrx_get_notch: null output pointers");
-    if (cfg_out) // the settings as last written
-        memcpy(cfg_out, &c->nt.cfg, sizeof *cfg_out);
-    if (out) {
-        if (int rc = need_delivered(c, "sdrx_get_notch"))
-            return rc;
-        const int p = c->host_slot;
-        const sdrx_ctx::Notch::Used &U = c->nt.used[p];
-        if (!U.any || U.frame != c->host_frame)
-            return fail(c, SDRX_EHIP, "sdrx_get_notch: frame %llu did not pass the spur canceller", c->host_frame);
-        memcpy(out, c->nt.rec.host<NotchRecord>(p), sizeof *out);
-        if (!out->n_complex || out->frame != (int64_t)c->host_frame) // (a slot never written holds zeros)
-            return fail(c, SDRX_EHIP, "sdrx_get_notch: the record of frame %llu did not arrive (it names frame %lld)", c->host_frame, (long long)out->frame);
-    }
-    return SDRX_OK;
+    return stage_get<NotchRecord>(c, &sdrx_ctx::nt, cfg_out, out, "sdrx_get_notch", "spur canceller", true, // (the settings as last written)
+                                  [](const sdrx_notch_record &r) { return r.n_complex != 0; });
 }
 
 int sdrx_get_stream(sdrx_ctx *c, int id, float *out, int max_complex, int *n_ret)

@@ -366,6 +366,22 @@ struct sdrx_ctx : CtxBuffers {
         } note[2];
     } adc;
 
+    // An ingest stage with settings and a record of every frame (blanker, IQ balance, shift, spur canceller): `Device` is what
+    // finalize allocates with it and free_device_state releases, its `rec` the record of frame f.  `used` says per frame parity
+    // which frame the slot was written for and under which settings: what the stage's getter answers from.
+    template <class Cfg, class Device>
+    struct CfgStage : Device {
+        bool on = false; // set before sdrx_finalize
+        Cfg cfg{};       // the settings of the next frame
+        struct Used {
+            unsigned long long frame = 0;
+            bool any = false;
+            Cfg cfg{};
+        } used[2];
+        void ran(int p, unsigned long long frame) { used[p] = Used{frame, true, cfg}; } // the stage's launch: frame `frame` passed it
+        void reset_used() { used[0] = used[1] = Used(); }
+    };
+
     // Resampler (sdrx_set_resampler, resample.hip): frames arrive at the rate fs_in, in_frame samples each, and
     // k_resample makes the tree's raw frame (root_frame samples in d_raw_tiled) from them.  The setting -- the rate and the
     // caller's taps in prototype order, or why that ratio is not offered -- is the host's and stays; what finalize allocates
@@ -404,66 +420,42 @@ struct sdrx_ctx : CtxBuffers {
     } fr;
     // Impulse blanker (sdrx_set_blanker, blank.hip): k_blank between the ingest kernels and what they wrote before.
     // The setting is the host's; what finalize allocates with it: the staging frame the ingest kernels then write (tile layout),
-    // the device state (reference bin, carry, the frame's histogram and counters) and the record of frame f (`rec`).  `used`
-    // says per frame parity which frame the slot was written for and under which settings.
+    // the device state (reference bin, carry, the frame's histogram and counters) and the record of frame f (`rec`).
     struct BlankerDevice { // what free_device_state releases
         DevBuf<float2> d_stage;
         DevBuf<BlankState> d_state;
         Records rec;
         size_t bytes() const { return d_stage.bytes() + d_state.bytes() + 2 * rec.bytes(); } // device memory it holds
     };
-    struct Blanker : BlankerDevice {
-        bool on = false; // set before sdrx_finalize
-        BlankCfg cfg{};  // the settings of the next frame
-        struct Used {
-            unsigned long long frame = 0;
-            bool any = false;
-            BlankCfg cfg{};
-        } used[2];
-    } bl;
+    CfgStage<BlankCfg, BlankerDevice> bl;
     bool staged() const { return rs.on || fr.on || bl.on; } // the ingest kernels write a staging buffer, not the tree's raw frame
     // IQ balance correction (sdrx_set_iq_balance, iqbal.hip): k_iqbal in place on what the ingest kernels wrote, in
     // front of the blanker.  The setting is the host's; what finalize allocates with it: the device state (the pair and the five
     // accumulators of the frame in flight) and the record of frame f (`rec`).  No staging frame: staged() is not its business,
-    // but every frame, cf32 ones included, then takes the ingest pass into the tile layout (tiled_ingest).  `used` says per frame
-    // parity which frame the slot was written for and under which settings.
+    // but every frame, cf32 ones included, then takes the ingest pass into the tile layout (tiled_ingest).  cfg.c0, cfg.d0: what
+    // sdrx_finalize or the last SDRX_IQ_LOAD wrote.
     struct IqDevice { // what free_device_state releases
         DevBuf<IqState> d_state;
         Records rec;
         size_t bytes() const { return d_state.bytes() + 2 * rec.bytes(); } // device memory it holds
     };
-    struct Iq : IqDevice {
-        bool on = false; // set before sdrx_finalize
-        IqCfg cfg{};     // the settings of the next frame (c0, d0: what sdrx_finalize or the last SDRX_IQ_LOAD wrote)
-        struct Used {
-            unsigned long long frame = 0;
-            bool any = false;
-            IqCfg cfg{};
-        } used[2];
-    } iq;
+    CfgStage<IqCfg, IqDevice> iq;
     // Frequency shift (sdrx_set_shift, shift.hip): k_shift in place on the tree's raw frame, behind the resampler or
     // whatever comes last in the ingest chain.  The setting is the host's; what finalize allocates with it: the device state (phase
     // and increment of the next frame), the one device copy of the three tables and the record of frame f (`rec`).  No staging
-    // frame, but every frame takes the ingest pass into the tile layout (tiled_ingest).  `used` as for the IQ balance.
+    // frame, but every frame takes the ingest pass into the tile layout (tiled_ingest).  cfg.inc: of the next frame; cfg.phase0:
+    // what sdrx_finalize or the last SDRX_SHIFT_LOAD_PHASE wrote.
     struct ShiftDevice { // what free_device_state releases
         DevBuf<ShiftState> d_state;
         DevBuf<float2> d_tab; // A | B | C, 3 * kShTab entries
         Records rec;
         size_t bytes() const { return d_state.bytes() + d_tab.bytes() + 2 * rec.bytes(); } // device memory it holds
     };
-    struct Shift : ShiftDevice {
-        bool on = false; // set before sdrx_finalize
-        ShiftCfg cfg{};  // inc: of the next frame; phase0: what sdrx_finalize or the last SDRX_SHIFT_LOAD_PHASE wrote
-        struct Used {
-            unsigned long long frame = 0;
-            bool any = false;
-            ShiftCfg cfg{};
-        } used[2];
-    } sh;
+    CfgStage<ShiftCfg, ShiftDevice> sh;
     // Spur canceller (sdrx_set_notch, notch.hip): k_notch_corr / _step / _apply in place on the tree's raw frame, in
     // front of k_shift.  What finalize allocates with it: the eight tone slots, c[b][k] and used[b][k] of one frame's blocks, the
-    // record of frame f (`rec`) and -- unless the shift is on, whose copy then serves both -- the three tables.  `used` as for the
-    // shift; cfg.flags: of the last call.
+    // record of frame f (`rec`) and -- unless the shift is on, whose copy then serves both (shift_tables_dev) -- the three tables.
+    // cfg: as last written (flags: of the last call), and what the getter answers with -- used[].cfg goes unread.
     struct NotchDevice { // what free_device_state releases
         DevBuf<NotchTone> d_state;  // kNtMax slots
         DevBuf<ShiftC> d_c, d_used; // blocks * kNtMax each
@@ -471,16 +463,17 @@ struct sdrx_ctx : CtxBuffers {
         Records rec;
         size_t bytes() const { return d_state.bytes() + d_c.bytes() + d_used.bytes() + d_tab.bytes() + 2 * rec.bytes(); }
     };
-    struct Notch : NotchDevice {
-        bool on = false; // set before sdrx_finalize
-        NotchCfg cfg{};  // of the next frame: as last written
-        struct Used {
-            unsigned long long frame = 0;
-            bool any = false;
-        } used[2];
-    } nt;
+    CfgStage<NotchCfg, NotchDevice> nt;
+    const float2 *shift_tables_dev() const { return sh.on ? sh.d_tab.get() : nt.d_tab.get(); } // the one device copy of A | B | C
     bool tiled_ingest() const { return staged() || iq.on || sh.on || nt.on; } // every frame goes through an ingest kernel into the tile layout
     int in_frame = 0; // samples of an incoming frame: root_frame, or with a resampler rs.plan.n_in; times 2^stages with a front stage
+    // Where the out-of-place kernels of the ingest chain write, in tile layout: planned once by sdrx_finalize (plan_ingest_route,
+    // sdrx_finalize.hip, which states the whole routing), cleared by free_device_state with the buffers it points into.
+    struct IngestRoute {
+        float2 *ingest_out = nullptr; // the format conversion (and the DC forms); the IQ balance works in place on it
+        float2 *blank_out = nullptr;  // k_blank, reading its staging frame
+        float2 *front_out = nullptr;  // the last front stage
+    } route;
 
     // sdrx_set_tap / sdrx_add_tap: the fused late-decimation leaves that keep decimate[0] because they are taps (vfo::fftVFOSlot
     // sets emitFFT on EVERY VFO whose topic matches, vfo.cpp:492-509): node -> its buffers per frame parity and the first

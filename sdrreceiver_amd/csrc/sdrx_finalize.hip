@@ -1145,8 +1145,7 @@ int blank_plan(sdrx_ctx *c)
 // releases) none.
 int blank_setup(sdrx_ctx *c)
 {
-    for (sdrx_ctx::Blanker::Used &u : c->bl.used)
-        u = sdrx_ctx::Blanker::Used();
+    c->bl.reset_used();
     if (!c->bl.on)
         return SDRX_OK;
     const size_t stage = align_up((size_t)c->in_frame, kChunk) + kChunk;
@@ -1173,8 +1172,7 @@ int iqbal_plan(sdrx_ctx *c)
 // frame parities.  All of it or (the caller releases) none.
 int iqbal_setup(sdrx_ctx *c)
 {
-    for (sdrx_ctx::Iq::Used &u : c->iq.used)
-        u = sdrx_ctx::Iq::Used();
+    c->iq.reset_used();
     if (!c->iq.on)
         return SDRX_OK;
     if (c->iq.d_state.alloc(1) != hipSuccess || c->iq.rec.alloc(sizeof(IqRecord)) != hipSuccess)
@@ -1186,13 +1184,21 @@ int iqbal_setup(sdrx_ctx *c)
     return SDRX_OK;
 }
 
+// The shift's three tables A | B | C into a buffer of 3 * kShTab entries its owner allocated: the shift's, or the spur canceller's
+// where the shift is off (sdrx_ctx::shift_tables_dev hands out the one there is).
+hipError_t fill_shift_tables(DevBuf<float2> &d_tab)
+{
+    std::vector<float> tab(3 * kShTab * 2);
+    shift_tables(tab.data());
+    return hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
+}
+
 // Frequency shift: what k_shift needs on the device -- the state (phase0, inc), the three tables and the record buffers of both
 // frame parities.  All of it or (the caller releases) none.  It is offered behind every ingest chain, a real first front stage
 // included: it works on the tree's raw frame.
 int shift_setup(sdrx_ctx *c)
 {
-    for (sdrx_ctx::Shift::Used &u : c->sh.used)
-        u = sdrx_ctx::Shift::Used();
+    c->sh.reset_used();
     if (!c->sh.on)
         return SDRX_OK;
     if (c->sh.d_state.alloc(1) != hipSuccess || c->sh.d_tab.alloc(3 * kShTab) != hipSuccess || c->sh.rec.alloc(sizeof(ShiftRecord)) != hipSuccess)
@@ -1201,9 +1207,7 @@ int shift_setup(sdrx_ctx *c)
     memset(&st, 0, sizeof st);
     st.phase = c->sh.cfg.phase0, st.inc = c->sh.cfg.inc;
     HIPCHK(c, hipMemcpy(c->sh.d_state, &st, sizeof st, hipMemcpyHostToDevice));
-    std::vector<float> tab(3 * kShTab * 2);
-    shift_tables(tab.data());
-    HIPCHK(c, hipMemcpy(c->sh.d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(c, fill_shift_tables(c->sh.d_tab));
     return SDRX_OK;
 }
 
@@ -1211,8 +1215,7 @@ int shift_setup(sdrx_ctx *c)
 // frame parities, and the three tables unless the shift's copy serves.  All of it or (the caller releases) none.
 int notch_setup(sdrx_ctx *c)
 {
-    for (sdrx_ctx::Notch::Used &u : c->nt.used)
-        u = sdrx_ctx::Notch::Used();
+    c->nt.reset_used();
     if (!c->nt.on)
         return SDRX_OK;
     const size_t per_frame = (size_t)notch_blocks(c->root_frame) * kNtMax;
@@ -1224,18 +1227,37 @@ int notch_setup(sdrx_ctx *c)
     for (int k = 0; k < (int)c->nt.cfg.n_tones; ++k)
         st[k].inc = st[k].inc0 = st[k].inc_used = c->nt.cfg.inc0[k];
     HIPCHK(c, hipMemcpy(c->nt.d_state, st, sizeof st, hipMemcpyHostToDevice));
-    if (!c->sh.on) {
-        std::vector<float> tab(3 * kShTab * 2);
-        shift_tables(tab.data());
-        HIPCHK(c, hipMemcpy(c->nt.d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
+    if (!c->sh.on)
+        HIPCHK(c, fill_shift_tables(c->nt.d_tab));
     return SDRX_OK;
+}
+
+// The route of a frame through the ingest chain, planned once: every buffer exists by now and stays until free_device_state.
+//   - the format conversion (or the DC form's last kernel) writes ingest_out: the blanker's staging frame if it is on, else what
+//     the blanker would have written;
+//   - k_iqbal works in place on ingest_out (so in front of the blanker, on what the blanker reads);
+//   - k_blank reads its staging frame and writes blank_out: the first front stage's input frame, else what the front stage
+//     would have written;
+//   - front stage s reads fr.d_in[s - 1] and writes fr.d_in[s]; the last one writes front_out: the resampler's staging frame,
+//     else the tree's raw frame.  (A real first stage reads the caller's words; nothing is staged in front of it, fr.d_in[0] is
+//     empty and ingest_out is never written: blank_plan and iqbal_plan refused the two stages that would.)
+//   - k_resample reads its staging frame and writes the tree's raw frame, d_raw_tiled;
+//   - the spur canceller, then the shift, work in place on d_raw_tiled.
+// Whatever is on, the last destination is the tree's raw frame.  The order is ingest_chain_launch's (sdrx_frame.hip).
+void plan_ingest_route(sdrx_ctx *c)
+{
+    sdrx_ctx::IngestRoute &R = c->route;
+    R.front_out = c->rs.on ? c->rs.d_stage.get() : c->d_raw_tiled.get();
+    R.blank_out = c->fr.on ? c->fr.d_in[0].get() : R.front_out;
+    R.ingest_out = c->bl.on ? c->bl.d_stage.get() : R.blank_out;
 }
 
 int finalize_impl(sdrx_ctx *c)
 {
     if (int rc = derive_nodes(c))
         return rc;
+    // the ingest stages' plans: the frame lengths from the tree outwards (each stage in front multiplies what is behind it), then
+    // the two stages a real first front stage rules out (the blanker first: its message is what a context with both gets)
     if (int rc = resample_plan_frames(c))
         return rc;
     if (int rc = front_plan_frames(c))
@@ -1262,18 +1284,20 @@ int finalize_impl(sdrx_ctx *c)
         return rc;
     if (int rc = adc_setup(c))
         return rc;
-    if (int rc = resample_setup(c))
-        return rc;
-    if (int rc = front_setup(c))
+    // the ingest stages' device state, in chain order, and the route between their buffers
+    if (int rc = iqbal_setup(c))
         return rc;
     if (int rc = blank_setup(c))
         return rc;
-    if (int rc = iqbal_setup(c))
+    if (int rc = front_setup(c))
         return rc;
-    if (int rc = shift_setup(c))
+    if (int rc = resample_setup(c))
         return rc;
     if (int rc = notch_setup(c))
         return rc;
+    if (int rc = shift_setup(c))
+        return rc;
+    plan_ingest_route(c);
     catchup_setup(c, B);
     c->sq.preroll_fused = false;
     for (const Node &n : c->nodes)

@@ -97,16 +97,8 @@ ParkArg<PARK> park_arg(const sdrx_ctx *c, size_t first)
     return P;
 }
 
-// Where the ingest kernels leave a frame in tile layout: the tree's raw frame, or with a resampler the input-rate staging
-// buffer in front of it.
-float4 *ingest_dest(sdrx_ctx *c)
-{
-    if (c->bl.on) // (the blanker's staging frame: k_blank writes what this returned without it, blank_launch)
-        return reinterpret_cast<float4 *>(c->bl.d_stage.get());
-    if (c->fr.on) // (complex front stage: its first stage's input frame; a real one converts the caller's words itself)
-        return reinterpret_cast<float4 *>(c->fr.d_in[0].get());
-    return reinterpret_cast<float4 *>(c->rs.on ? c->rs.d_stage.get() : c->d_raw_tiled.get());
-}
+// Where the ingest kernels leave a frame in tile layout: the first buffer of the route sdrx_finalize planned (plan_ingest_route).
+float4 *ingest_dest(sdrx_ctx *c) { return reinterpret_cast<float4 *>(c->route.ingest_out); }
 
 // Resampler: the staged input-rate frame of the next frame (c->frame_no) -> the tree's raw frame, on the context's stream
 // behind the ingest kernel that staged it, inside that kernel's KIND_INGEST bracket.  The history slot of the previous frame's
@@ -146,8 +138,7 @@ void front_launch(sdrx_ctx *c, const void *real_words = nullptr, int fmt = -1)
         A.hist_prev = hist + (size_t)(p ^ 1) * kFrHist;
         A.hist_next = hist + (size_t)p * kFrHist;
         A.taps = c->fr.d_taps;
-        float2 *out = s < P.stages ? c->fr.d_in[s].get() : c->rs.on ? c->rs.d_stage.get() : c->d_raw_tiled.get();
-        A.out = reinterpret_cast<float4 *>(out);
+        A.out = reinterpret_cast<float4 *>(s < P.stages ? c->fr.d_in[s].get() : c->route.front_out);
         A.n_out = (int)front_stage_out(P, s), A.n_in = 2 * A.n_out;
         A.K = P.K;
         auto k = !real ? k_front_halfband<kFrontComplex> : fmt == SDRX_FMT_RS16 ? k_front_halfband<kFrontRS16> : k_front_halfband<kFrontRU12>;
@@ -157,26 +148,23 @@ void front_launch(sdrx_ctx *c, const void *real_words = nullptr, int fmt = -1)
 
 // Impulse blanker: k_blank and k_blank_step for the next frame (c->frame_no), on the context's stream behind the ingest kernel that
 // staged it, inside that kernel's KIND_INGEST bracket and in front of front_launch.  Out of place: from the blanker's staging
-// frame to what ingest_dest returned without it.  The state chains on the device in stream order.  Off: nothing.
+// frame to the route's blank_out.  The state chains on the device in stream order.  Off: nothing.
 void blank_launch(sdrx_ctx *c)
 {
     if (!c->bl.on)
         return;
     const int p = (int)(c->frame_no & 1ull);
     const BlankCfg &B = c->bl.cfg;
-    float2 *out = c->fr.on ? c->fr.d_in[0].get() : c->rs.on ? c->rs.d_stage.get() : c->d_raw_tiled.get();
     hipLaunchKernelGGL(k_blank, dim3(blank_workgroups(c->in_frame)), dim3(kBlankThreads), 0, c->st.stream, reinterpret_cast<const float4 *>(c->bl.d_stage.get()),
-                       reinterpret_cast<float4 *>(out), c->in_frame, B.ratio, B.floor, B.guard, c->bl.d_state.get());
+                       reinterpret_cast<float4 *>(c->route.blank_out), c->in_frame, B.ratio, B.floor, B.guard, c->bl.d_state.get());
     hipLaunchKernelGGL(k_blank_step, dim3(1), dim3(kBlankThreads), 0, c->st.stream, c->bl.d_state.get(), c->bl.rec.dev<BlankRecord>(p), (long long)c->frame_no,
                        c->in_frame, B.rank_q16, B.guard, B.ratio, B.floor);
-    c->bl.used[p].frame = c->frame_no;
-    c->bl.used[p].any = true;
-    c->bl.used[p].cfg = B;
+    c->bl.ran(p, c->frame_no);
 }
 
 // IQ balance correction: k_iqbal and k_iqbal_step for the next frame (c->frame_no), on the context's stream behind the ingest
-// kernel that staged it, inside that kernel's KIND_INGEST bracket and in front of blank_launch.  In place, on whatever
-// ingest_dest returned.  The pair chains on the device in stream order.  Off: nothing.
+// kernel that staged it, inside that kernel's KIND_INGEST bracket and in front of blank_launch.  In place, on what the ingest
+// kernel wrote (ingest_dest).  The pair chains on the device in stream order.  Off: nothing.
 void iqbal_launch(sdrx_ctx *c)
 {
     if (!c->iq.on)
@@ -186,9 +174,7 @@ void iqbal_launch(sdrx_ctx *c)
     hipLaunchKernelGGL(k_iqbal, dim3(iq_workgroups(c->in_frame)), dim3(kIqThreads), 0, c->st.stream, ingest_dest(c), c->in_frame, c->iq.d_state.get());
     hipLaunchKernelGGL(k_iqbal_step, dim3(1), dim3(64), 0, c->st.stream, c->iq.d_state.get(), c->iq.rec.dev<IqRecord>(p), (long long)c->frame_no, c->in_frame,
                        Q.mu, Q.min_power);
-    c->iq.used[p].frame = c->frame_no;
-    c->iq.used[p].any = true;
-    c->iq.used[p].cfg = Q;
+    c->iq.ran(p, c->frame_no);
 }
 
 // Spur canceller: k_notch_corr, k_notch_step and k_notch_apply for the next frame (c->frame_no), on the context's stream behind the
@@ -200,7 +186,7 @@ void notch_launch(sdrx_ctx *c)
         return;
     const NotchCfg &N = c->nt.cfg;
     const int p = (int)(c->frame_no & 1ull), n = c->root_frame, K = (int)N.n_tones;
-    const float2 *tab = c->sh.on ? c->sh.d_tab.get() : c->nt.d_tab.get(); // (one device copy of the tables serves both)
+    const float2 *tab = c->shift_tables_dev();
     float4 *buf = reinterpret_cast<float4 *>(c->d_raw_tiled.get());
     if (K > 0)
         hipLaunchKernelGGL(k_notch_corr, dim3(notch_workgroups(n)), dim3(kNtThreads), 0, c->st.stream, buf, n, K, c->nt.d_state.get(), tab, c->nt.d_c.get());
@@ -208,8 +194,7 @@ void notch_launch(sdrx_ctx *c)
                        (long long)c->frame_no, n, K, N.mu, N.afc_gain, N.min_coherence, N.max_pull);
     if (K > 0)
         hipLaunchKernelGGL(k_notch_apply, dim3(notch_workgroups(n)), dim3(kNtThreads), 0, c->st.stream, buf, n, K, c->nt.d_state.get(), tab, c->nt.d_used.get());
-    c->nt.used[p].frame = c->frame_no;
-    c->nt.used[p].any = true;
+    c->nt.ran(p, c->frame_no);
 }
 
 // Frequency shift: k_shift and k_shift_step for the next frame (c->frame_no), on the context's stream behind the last kernel of
@@ -221,11 +206,23 @@ void shift_launch(sdrx_ctx *c)
         return;
     const int p = (int)(c->frame_no & 1ull);
     hipLaunchKernelGGL(k_shift, dim3(shift_workgroups(c->root_frame)), dim3(kShThreads), 0, c->st.stream, reinterpret_cast<float4 *>(c->d_raw_tiled.get()),
-                       c->root_frame, c->sh.d_state.get(), c->sh.d_tab.get());
+                       c->root_frame, c->sh.d_state.get(), c->shift_tables_dev());
     hipLaunchKernelGGL(k_shift_step, dim3(1), dim3(64), 0, c->st.stream, c->sh.d_state.get(), c->sh.rec.dev<ShiftRecord>(p), (long long)c->frame_no, c->root_frame);
-    c->sh.used[p].frame = c->frame_no;
-    c->sh.used[p].any = true;
-    c->sh.used[p].cfg = c->sh.cfg;
+    c->sh.ran(p, c->frame_no);
+}
+
+// The ingest chain of the next frame (c->frame_no) behind the kernel that staged it, inside that kernel's KIND_INGEST bracket: the
+// one place that says in which order the stages run.  Every stage that is off launches nothing.  `real_words`, `fmt`: the frame's
+// 16-bit words where the first front stage is the real one (front_launch) -- nothing staged a complex frame then, and the IQ
+// balance and the blanker launch nothing: blank_plan and iqbal_plan refuse them in front of a real first stage.
+void ingest_chain_launch(sdrx_ctx *c, const void *real_words = nullptr, int fmt = -1)
+{
+    iqbal_launch(c);
+    blank_launch(c);
+    front_launch(c, real_words, fmt);
+    resample_launch(c);
+    notch_launch(c);
+    shift_launch(c);
 }
 
 int queue_fixed_part(sdrx_ctx *c, int p, hipStream_t st); // (sdrx_delivery.hip)
@@ -657,9 +654,9 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         // steps of this frame write the flag words and state regions the previous tail, gate and step read
         HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.ev_tail[p ^ 1], 0));
     if (c->tiled_ingest() && raw_mode != kRawTiled) {
-        // Resampler / front stage / blanker / IQ balance / notch / shift: a natural-order frame (cf32, or a shared context's bytes) is at the input rate -- one layout pass into the
-        // staging buffer, then k_resample, in front of everything that reads the tree's raw frame.  (A frame of integer samples
-        // came through enqueue_samples_device, which did both: kRawTiled.)
+        // With any stage of the ingest chain on, a natural-order frame (cf32, or a shared context's bytes) is at the input rate:
+        // one layout pass into the route's first buffer, then the chain (ingest_chain_launch), in front of everything that reads
+        // the tree's raw frame.  (A frame of integer samples came through enqueue_samples_device, which did both: kRawTiled.)
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
         const int n_pairs = c->in_frame / 2;
         if (raw_mode == kRawF32)
@@ -668,12 +665,7 @@ int enqueue_frame(sdrx_ctx *c, const void *raw, int raw_mode, bool egress)
         else
             hipLaunchKernelGGL(k_ingest_samples<SDRX_FMT_CU8>, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream,
                                reinterpret_cast<const unsigned *>(raw), ingest_dest(c), n_pairs);
-        iqbal_launch(c);
-        blank_launch(c);
-        front_launch(c);
-        resample_launch(c);
-        notch_launch(c);
-        shift_launch(c);
+        ingest_chain_launch(c);
         raw_mode = kRawTiled;
     }
     spectrum_raw_step(c, raw, raw_mode);
@@ -966,10 +958,7 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         adc_meter_launch(c, dev_bytes, n_complex / 2, fmt);
         {
             Bracket b(c, c->st.stream, KIND_INGEST, 0);
-            front_launch(c, dev_bytes, fmt);
-            resample_launch(c);
-            notch_launch(c);
-            shift_launch(c);
+            ingest_chain_launch(c, dev_bytes, fmt);
         }
         const int rc = enqueue_frame(c, dev_bytes, kRawTiled, egress);
         if (rc == SDRX_OK)
@@ -1003,12 +992,7 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
         }
         hipLaunchKernelGGL(K.apply, dim3((words + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes), Ap,
                            ingest_dest(c), n_complex, c->dc.work_stride);
-        iqbal_launch(c);
-        blank_launch(c);
-        front_launch(c);
-        resample_launch(c);
-        notch_launch(c);
-        shift_launch(c);
+        ingest_chain_launch(c);
         mode = kRawTiled;
     } else if (correct_dc) {
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
@@ -1018,24 +1002,14 @@ int enqueue_samples_device(sdrx_ctx *c, const void *dev_bytes, int n_complex, in
                            c->dc.d_tab, sums);
         hipLaunchKernelGGL(K.dc_fast, dim3(nchunks), dim3(64), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
                            ingest_dest(c), n_complex, c->dc.d_state + 2 * par, c->dc.d_state + 2 * (par ^ 1), c->dc.d_tab, sums);
-        iqbal_launch(c);
-        blank_launch(c);
-        front_launch(c);
-        resample_launch(c);
-        notch_launch(c);
-        shift_launch(c);
+        ingest_chain_launch(c);
         mode = kRawTiled;
     } else if (fmt != SDRX_FMT_CU8 || c->tiled_ingest()) { // (resampler, front stage, blanker, IQ balance, notch, shift: they read the tile layout, so bytes take the pass too)
         Bracket b(c, c->st.stream, KIND_INGEST, 0);
         const int n_pairs = n_complex / 2;
         hipLaunchKernelGGL(K.ingest, dim3((n_pairs + 255) / 256), dim3(256), 0, c->st.stream, reinterpret_cast<const unsigned *>(dev_bytes),
                            ingest_dest(c), n_pairs);
-        iqbal_launch(c);
-        blank_launch(c);
-        front_launch(c);
-        resample_launch(c);
-        notch_launch(c);
-        shift_launch(c);
+        ingest_chain_launch(c);
         mode = kRawTiled;
     }
     c->long_frame = correct_dc && !c->opt_dc_blocked;
