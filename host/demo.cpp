@@ -3,6 +3,7 @@
 // frames to sdrj::demodData, receive every leaf's payload through the publish hook.
 //
 //   sdrx_demo <profile.ini> --dump              descriptors as JSON lines (no GPU needed)
+//                                               (a [vfos] entry with detector=am|fm is a detector leaf: int16 messages at 48 kS/s)
 //   sdrx_demo <profile.ini> --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ]
 //                                   [--front-stages N [--front-real] [--front-taps K]] [--blanker RATIO,GUARD[,FLOOR[,RANK]]]
 //                                   [--iq-balance MU,MINPOWER[,C0,D0]] [--shift HZ] [--notch HZ[,HZ...]:MU[,AFC,COH,PULLHZ]]
@@ -82,9 +83,9 @@ int main(int argc, char **argv)
                 for (vfo *v : P->subs[m]) {
                     const sdrx_vfo_desc &d = v->d;
                     std::printf("{\"sub_of\": %zu, \"topic\": \"%s\", \"fs\": %d, \"d\": %d, \"late\": %d, \"mixer\": %.1f, \"bw\": %d, "
-                                "\"gain\": %.9g, \"spb\": %d}\n",
+                                "\"gain\": %.9g, \"spb\": %d, \"usb\": %d, \"detector\": %d}\n",
                                 m, v->topic.c_str(), d.fs, d.decimate_count, d.late_decimate, d.mixer_freq_hz, d.filter_bw_hz, (double)d.gain,
-                                d.samples_per_buffer);
+                                d.samples_per_buffer, d.demod_usb, v->getDetector());
                 }
             return 0;
         }

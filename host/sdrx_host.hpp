@@ -8,6 +8,7 @@
 // A Qt front-end wraps these; tests drive them through host/demo.cpp.
 #pragma once
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <complex>
 #include <cstdint>
@@ -47,6 +48,10 @@ public:
     void setDemodUSB(bool usb) { d.demod_usb = usb ? 1 : 0; }
     bool getDemodUSB() const { return d.demod_usb != 0; }
     void setCompressonStyle(int st) { d.cstyle = st; } // sic, vfo.h:36
+    // no counterpart in vfo.h: a leaf with setDemodUSB(false) leaves as an AM envelope (SDRX_DETECT_AM) or an FM discriminator
+    // (SDRX_DETECT_FM) in int16 instead of compress()'s bytes (include/sdrx.h "Detector leaves"); a single context only
+    void setDetector(int kind) { detector = kind; }
+    int getDetector() const { return detector; }
     void setScaleComp(int scale) { d.scalecomp = scale; }
     void setZmqTopic(const std::string &t)
     {
@@ -72,6 +77,7 @@ public:
     std::string topic, zmqAddress;
     std::vector<vfo *> *mpVFOs = nullptr;
     int id = -1;
+    int detector = SDRX_DETECT_NONE;
     bool initialised = false;
 };
 
@@ -693,6 +699,14 @@ private:
             throw std::runtime_error("vfo::init was not called");
         v->d.parent_id = parent;
         call("add_vfo", sdrx_group_add_vfo, sdrx_add_vfo, &v->d, &v->id);
+        if (v->detector != SDRX_DETECT_NONE) {
+            if (grp_)
+                throw std::runtime_error("vfo::setDetector: groups do not offer detector leaves (include/sdrx.h \"Detector leaves\")");
+            sdrx_detect_cfg cfg;
+            std::memset(&cfg, 0, sizeof cfg);
+            cfg.kind = v->detector;
+            check(sdrx_set_detector(ctx_, v->id, &cfg), "sdrx_set_detector");
+        }
         if (v->mpVFOs)
             for (vfo *c : *v->mpVFOs)
                 add(c, v->id);
@@ -955,6 +969,15 @@ inline std::unique_ptr<Profile> load_profile(std::istream &in)
             if (data_rate > 0)
                 out_rate = data_rate == 600 ? 12000 : data_rate == 1200 ? 24000 : 48000;
         }
+        // `detector=am|fm` (no key of the reference, which ignores keys it does not know): the entry leaves as an AM envelope or an
+        // FM discriminator in int16 and is placed as a 48 kS/s sub is
+        std::string det = ini.text(key("detector"));
+        for (char &ch : det)
+            ch = (char)std::tolower((unsigned char)ch);
+        if (!det.empty() && det != "am" && det != "fm")
+            throw std::runtime_error(ini.item("vfos", i, "") + ": detector=" + det + ": only am and fm are offered");
+        if (!det.empty() && out_rate == 0)
+            out_rate = 48000;
         if (out_rate <= 0)
             throw std::runtime_error(ini.item("vfos", i, "") + ": neither out_rate nor data_rate given");
         if (P.mains.empty())
@@ -971,6 +994,17 @@ inline std::unique_ptr<Profile> load_profile(std::istream &in)
         v.setMixerFreq((P.center_frequency - pl.parent_mixer) - channel);
         v.setFs(pl.input_rate);
         v.setCompressonStyle(1);
+        if (!det.empty()) {
+            if (pl.late_decimate)
+                throw std::runtime_error(ini.item("vfos", i, "") + ": detector=" + det + " below a main VFO of " + std::to_string(pl.input_rate) +
+                                         " S/s would need the late decimation by " + std::to_string(pl.late_decimate) +
+                                         ", which runs in front of the USB demodulation only: give the entry a main VFO whose out_rate is a "
+                                         "power of two times its own");
+            v.setDemodUSB(false);
+            v.setFilterBandwidth(0);
+            v.setCompressonStyle(0);
+            v.setDetector(det == "am" ? SDRX_DETECT_AM : SDRX_DETECT_FM);
+        }
         v.init(pl.input_rate / P.bufsplit, true, pl.late_decimate);
         P.subs[(size_t)pl.main_index].push_back(&v);
     }

@@ -1355,6 +1355,55 @@ int sdrx_get_spectrum(sdrx_ctx *ctx, int id, sdrx_spectrum_info *info, double *p
  * output array may be NULL). */
 int sdrx_get_spectrum_levels(sdrx_ctx *ctx, const int *ids, int n, double *maxval, double *aveval, int64_t *updates);
 
+/* ---- Detector leaves: an AM envelope or an FM discriminator in place of compress() -------------------------------------------
+ * No counterpart in the reference.  A leaf with demod_usb = 0 can be given a detector before sdrx_finalize.  Its payload is then n
+ * int16 per frame -- n = fs-side samples_per_buffer / 2^decimate_count, the leaf's stream length -- in place of compress()'s bytes
+ * (the same byte count as cstyle 0).  sdrx_vfo_desc is unchanged: any non-zero demod_usb means USB, every cstyle is taken.
+ *
+ * This text is the definition; csrc/sdrx_detect.h spells it per sample and sdrreceiver_amd/detect.py is the model the tests hold the
+ * device to, bit for bit.  Every operation is ONE fp32 operation, separately rounded, no FMA -- the same in all three settings of
+ * option "exact", given the stream the device holds (as the watch's PSD is).  z[i] = (re, im) is sample i of the leaf's stream.
+ *
+ * SDRX_DETECT_AM
+ *   1. e[i] = sqrt(fl(fl(re re) + fl(im im))), the correctly rounded fp32 square root;
+ *   2. the frame's carrier: S = sum of q[i] over the frame's n samples, q[i] = min(e[i], 2^15) 2^8 rounded to nearest even as an
+ *      unsigned integer (a NaN counts as 2^15), summed in 64-bit integers: independent of order and geometry;
+ *   3. c = (float)((double)S / (double)(256 n));
+ *   4. pre[i] = fl(fl(e[i] - c) gain), then the USB leaves' conversion: pre 32768 in double, truncated to int32 as the x86-64
+ *      build does (INT32_MIN outside it), the low 16 bits kept.
+ *   The carrier is the frame's own: an AM leaf carries nothing from frame to frame, and a frame of zeros gives zeros.
+ * SDRX_DETECT_FM
+ *   1. with z[i] = (a, b) and z[i-1] = (p, q): d_re = fl(fl(a p) + fl(b q)), d_im = fl(fl(b p) - fl(a q));
+ *   2. x = ANG(d_im, d_re), the angle in half-turns, in [-1, 1]: t = min(|y|, |x|) / max(|y|, |x|) (one correctly rounded division;
+ *      0 where both are 0), atan(t) / pi = t P(t t) with P of degree 5 in separately rounded Horner steps (the coefficients are in
+ *      sdrx_detect.h), 1/2 - r where |y| > |x|, 1 - r where x < 0, negated where y < 0; ANG(0, 0) = 0.  Its error against atan2 is
+ *      below 1e-5 rad: at gain = 1 -- full scale = a deviation of fs / 2 -- a third of one LSB;
+ *   3. pre[i] = fl(x gain), then the same conversion.
+ *   z[-1] of a frame is the last stream sample of the leaf's frame before; 0 + 0j for a leaf that sdrx_finalize, sdrx_set_active,
+ *   the catch-up or the wake starts as a new vfo.
+ *
+ * `gain` acts as on a USB leaf (sdrx_set_gains included); cstyle, scalecomp and filter_bw_hz are ignored -- there is no
+ * post-detection filter.  The leaf publishes by the IQ leaf's rule (only with a topic; rate = fs / 2^decimate_count, len = 2 n), its
+ * watch band is the IQ leaf's, and its output meter is the USB leaves' (n_values = n, int16 full scale).  The squelch gate, the
+ * auto-squelch, the pre-roll, parking, the catch-up, the watch and the wake serve it as they serve any leaf; sdrx_set_agc answers
+ * what it answers for an IQ leaf; fuse_demod and keep_prequant do not apply.  sdrx_get_kernel_times books its launches with
+ * k_compress.  With no detector set anywhere the library launches, allocates and delivers exactly what it did without this section.
+ *
+ * sdrx_set_detector: before sdrx_finalize (SDRX_ESTATE after it); SDRX_EINVAL for a bad id, a node with demod_usb != 0, an unknown
+ * kind or a non-zero reserved word.  SDRX_DETECT_NONE takes the detector away again.  sdrx_finalize returns SDRX_EINVAL for a node
+ * with children that carries a detector.  sdrx_get_detector: the setting of any node, at any time.
+ * Groups do not offer it: a group's members are made by sdrx_group_finalize, and on a member handed out by sdrx_group_member the
+ * call returns SDRX_ESTATE as on every finalized context. */
+#define SDRX_DETECT_NONE 0
+#define SDRX_DETECT_AM 1
+#define SDRX_DETECT_FM 2
+typedef struct sdrx_detect_cfg { /* 16 bytes */
+    int32_t kind;
+    int32_t reserved[3];
+} sdrx_detect_cfg;
+int sdrx_set_detector(sdrx_ctx *ctx, int id, const sdrx_detect_cfg *cfg);
+int sdrx_get_detector(sdrx_ctx *ctx, int id, sdrx_detect_cfg *cfg_out);
+
 /* ---- one tree on several GPUs, one host process ---------------------------------------------------
  * The fan-out the reference does on one thread -- sdrj::demodData over the main VFOs (sdrj.cpp:288-294),
  * each main over its sub VFOs (vfo.cpp:253-264) -- sharded over the devices of one node:

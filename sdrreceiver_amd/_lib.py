@@ -198,6 +198,11 @@ class NotchCfgC(C.Structure):
                 ("afc_gain", C.c_float), ("min_coherence", C.c_float), ("reserved1", C.c_uint32), ("inc0", C.c_uint32 * 8), ("reserved", C.c_uint32 * 8)]
 
 
+class DetectCfgC(C.Structure):
+    """struct sdrx_detect_cfg"""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class NotchToneC(C.Structure):
     """struct sdrx_notch_tone"""
     _fields_ = [("inc", C.c_uint32), ("inc_next", C.c_uint32), ("a_re_bits", C.c_uint32), ("a_im_bits", C.c_uint32), ("coherent", C.c_uint32),
@@ -321,6 +326,8 @@ SYMBOLS = {
     "sdrx_shift_hz": (C.c_double, [C.c_double, C.c_uint32]),
     "sdrx_set_notch": (_i, [_vp, C.POINTER(NotchCfgC)]),
     "sdrx_get_notch": (_i, [_vp, C.POINTER(NotchCfgC), C.POINTER(NotchRecordC)]),
+    "sdrx_set_detector": (_i, [_vp, _i, C.POINTER(DetectCfgC)]),
+    "sdrx_get_detector": (_i, [_vp, _i, C.POINTER(DetectCfgC)]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

@@ -49,6 +49,8 @@
 //   k_mix_levels          levels.hip    k_mix_decimate's items of every tree level in one launch (run_item, mix.hip)
 //   k_levels_tail         levels.hip    the same plus k_usb_demod's blocks of the frame that left the last level (option tail_in_levels)
 //   k_compress            compress.hip  vfo::compress, vfo.cpp:389-424
+//   k_env_sum, k_detect<KIND> detect.hip (none: sdrx_set_detector -- the int16 payload of a non-USB leaf as an AM envelope (carrier = the frame's
+//                                       own mean, summed in exact integers by k_env_sum) or an FM discriminator; include/sdrx.h "Detector leaves")
 // (The kernels beside the chain have files of their own, included by sdrx.hip: spectrum.hip, squelch.hip, agc.hip, watch.hip, wake.hip,
 // drift.hip, scan.hip.)
 //
@@ -63,6 +65,7 @@
 #include "sdrx_iqbal.h"
 #include "sdrx_shift.h"
 #include "sdrx_notch.h"
+#include "sdrx_detect.h"
 
 #include <type_traits>
 #include <utility>
@@ -85,5 +88,6 @@ namespace sdrx {
 #include "late.hip"
 #include "levels.hip"
 #include "compress.hip"
+#include "detect.hip"
 
 } // namespace sdrx

@@ -93,6 +93,9 @@ static_assert(sizeof(sdrx_notch_cfg) == 96 && sizeof(NotchCfg) == 96 && offsetof
                   offsetof(sdrx_notch_record, blocks) == offsetof(NotchRecord, blocks) && offsetof(sdrx_notch_record, tone) == offsetof(NotchRecord, tone) &&
                   sizeof(NotchTone) == 32 && SDRX_NOTCH_LOAD == kNtLoad && SDRX_NOTCH_MAX == kNtMax,
               "sdrx_notch_cfg / sdrx_notch_record ABI layout");
+static_assert(sizeof(sdrx_detect_cfg) == 16 && sizeof(DetectCfg) == 16 && offsetof(sdrx_detect_cfg, reserved) == offsetof(DetectCfg, reserved) &&
+                  SDRX_DETECT_NONE == kDetNone && SDRX_DETECT_AM == kDetAm && SDRX_DETECT_FM == kDetFm,
+              "sdrx_detect_cfg ABI layout");
 static_assert(sizeof(sdrx_adc_arm) == 40 && sizeof(AdcArm) == 40 && offsetof(sdrx_adc_arm, longest_rail_run) == offsetof(AdcArm, longest_rail_run) &&
                   sizeof(sdrx_adc_meter) == 184 && sizeof(AdcRecord) == 184 && offsetof(sdrx_adc_meter, q) == offsetof(AdcRecord, q) &&
                   offsetof(sdrx_adc_meter, sum_iq) == offsetof(AdcRecord, sum_iq) && offsetof(sdrx_adc_meter, bits) == offsetof(AdcRecord, bits),
@@ -664,6 +667,10 @@ int apply_vfo_jobs(sdrx_ctx *c, const int *ids, const double *freqs, const float
             J.gain = &(reinterpret_cast<K4Vfo *>(c->arena + c->off_k4) + nd.d4_index)->gain;
             jobs.push_back(J);
         }
+        if (nd.d5_index >= 0) {
+            J.gain = &(reinterpret_cast<K5Vfo *>(c->arena + c->off_k5) + nd.d5_index)->gain;
+            jobs.push_back(J);
+        }
     }
     if (!jobs.empty()) {
         if (int rc = upload_jobs(c, c->d_jobs, jobs.data(), jobs.size()))
@@ -934,7 +941,7 @@ int sdrx_get_catchup(sdrx_ctx *c, const int *ids, int n, sdrx_meter *out)
         if (U.frame >= 0) {
             m.frame = (int64_t)U.frame;
             m.sum_sq = U.sum_sq;
-            m.n_values = (uint32_t)(nd.d.demod_usb ? nd.n_out : 2 * nd.n_f);
+            m.n_values = meter_n_values(nd);
             m.clipped = U.clipped;
             memcpy(&m.peak, &U.peak, 4);
         }
@@ -1284,6 +1291,37 @@ int sdrx_shift_inc(double fs_tree, double hz, uint32_t *inc)
 }
 
 double sdrx_shift_hz(double fs_tree, uint32_t inc) { return shift_hz(fs_tree, inc); }
+
+// ---- Detector leaves (include/sdrx.h; sdrx_detect.h has the rules) -----------------------------------------------------------------
+int sdrx_set_detector(sdrx_ctx *c, int id, const sdrx_detect_cfg *cfg)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_set_detector after sdrx_finalize");
+    if (!cfg || id < 0 || id >= (int)c->nodes.size())
+        return fail(c, SDRX_EINVAL, "sdrx_set_detector: bad vfo id %d or null settings", id);
+    DetectCfg d;
+    memcpy(&d, cfg, sizeof d);
+    if (const char *why = detect_args(d))
+        return fail(c, SDRX_EINVAL, "sdrx_set_detector: vfo %d: %s", id, why);
+    Node &n = c->nodes[(size_t)id];
+    if (n.d.demod_usb)
+        return fail(c, SDRX_EINVAL, "sdrx_set_detector: vfo %d has demod_usb set: a USB leaf has its detector", id);
+    n.detector = d.kind;
+    return SDRX_OK;
+}
+
+int sdrx_get_detector(sdrx_ctx *c, int id, sdrx_detect_cfg *cfg_out)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!cfg_out || id < 0 || id >= (int)c->nodes.size())
+        return fail(c, SDRX_EINVAL, "sdrx_get_detector: bad vfo id %d or null output", id);
+    memset(cfg_out, 0, sizeof *cfg_out);
+    cfg_out->kind = c->nodes[(size_t)id].detector;
+    return SDRX_OK;
+}
 
 // ---- Spur canceller (include/sdrx.h; sdrx_notch.h has the rules) -------------------------------------------------------------------
 int sdrx_set_notch(sdrx_ctx *c, const sdrx_notch_cfg *cfg)

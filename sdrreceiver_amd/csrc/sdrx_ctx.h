@@ -8,6 +8,10 @@ namespace {
 thread_local std::string g_create_error;
 
 enum Kind { KIND_MIX_ROOT = 0, KIND_MIX_SUB = 1, KIND_LATE_DEC = 2, KIND_DEMOD = 3, KIND_COMPRESS = 4, KIND_INGEST = 5, KIND_LEVELS = 6, KIND_LPF_LONG = 7 };
+// The detector leaves' two block launches (detect.hip) are kinds of the leaf tail's plan only: sdrx_get_kernel_times keeps its
+// SDRX_NKERNELS kinds and books them with k_compress, the payload kernel of the other non-USB leaves (bracket_kind).
+constexpr int KIND_DETECT_AM = SDRX_NKERNELS, KIND_DETECT_FM = SDRX_NKERNELS + 1;
+inline int bracket_kind(int kind) { return kind >= SDRX_NKERNELS ? (int)KIND_COMPRESS : kind; }
 const char *kKindNames[SDRX_NKERNELS] = {"k_mix_decimate(level0)", "k_mix_decimate(sub)", "k_late_decimate", "k_usb_demod",
                                          "k_compress",             "k_ingest",            "k_mix_levels",    "k_lpf_long"};
 
@@ -41,10 +45,17 @@ struct Node {
     int d2_index = -1;      // its K2Vfo in the demodulation descriptor array
     int d4_index = -1;      // its K4Vfo (long_lpf): k_lpf_long applies the gain
     int d2a_index = -1, d3_index = -1; // its K2aVfo (late decimation in a kernel of its own) / K3Vfo (compress): option park's flag words
+    int detector = 0;       // sdrx_set_detector: kDetNone | kDetAm | kDetFm (a leaf with demod_usb = 0 only)
+    int d5_index = -1;      // its K5Vfo (a detector leaf: in place of d3_index)
+    size_t off_part[2] = {0, 0};  //   ... AM: the carrier's block partials per frame parity
+    size_t off_zprev[2] = {0, 0}; //   ... FM: z[-1] per frame parity
     bool has_stream = true; // decimate[d] of every frame is kept in HBM (false: a fused late decimation writes only z', a fused demodulation only the payload)
     int meter_first = 0, meter_n = 0; // option meter: this leaf's records, slots [meter_first, meter_first + meter_n) behind the payloads
     int meter_shift = 0;              //   ... fuse_demod: the record of a mix item is s_first_out >> meter_shift
 };
+
+// sdrx_meter::n_values of a leaf: the int16 of a USB or a detector leaf, the two int8 a sample of an IQ leaf
+inline uint32_t meter_n_values(const Node &n) { return (uint32_t)(n.d.demod_usb ? n.n_out : n.detector ? n.n_f : 2 * n.n_f); }
 
 struct Launch1 { // one k_mix_decimate launch (a tree level)
     int kind;
@@ -183,7 +194,7 @@ struct sdrx_ctx : CtxBuffers {
     } agc;
 
     // Option park (sdrx_set_active): one flag word per descriptor of every kernel that works on a leaf, in one
-    // device array -- [K1Vfo: per node | K2aVfo | K2Vfo | K3Vfo | K4Vfo | the gate: per leaf in publish order] -- 1 = active.
+    // device array -- [K1Vfo: per node | K2aVfo | K2Vfo | K3Vfo | K4Vfo | K5Vfo | the gate: per leaf in publish order] -- 1 = active.
     // The host's copy of a leaf's state is what the getters and the delivery serve: a frame f >= since ran in state `active`,
     // the frames before it (the last one may not be fetched yet) in state `was_active`.  (A leaf under option wake's control is the
     // exception: the device decides, and the answers come from the frame's wake record -- leaf_parked_at, sdrx_delivery.hip.)
@@ -192,7 +203,7 @@ struct sdrx_ctx : CtxBuffers {
         DevBuf<unsigned char> d_jobs; // job lists of sdrx_set_active: FillJob[] | RetuneJob[], grown on demand
     };
     struct Park : ParkDevice {
-        size_t o_2a = 0, o_2 = 0, o_3 = 0, o_4 = 0, o_sq = 0, words = 0;
+        size_t o_2a = 0, o_2 = 0, o_3 = 0, o_4 = 0, o_5 = 0, o_sq = 0, words = 0;
         struct Leaf {
             int active = 1, was_active = 1;
             unsigned long long since = 0;
@@ -215,14 +226,14 @@ struct sdrx_ctx : CtxBuffers {
     struct Catchup {
         struct Leaf {
             std::vector<K1Work> mix;        // its items of its level's k_mix_decimate launch
-            std::vector<BlockWork> blk[4];  // its blocks per block kernel: 0 late decimation, 1 demodulation, 2 long low-pass, 3 compress
+            std::vector<BlockWork> blk[6];  // its blocks per block kernel: 0 late decimation, 1 demodulation, 2 long low-pass, 3 compress, 4 AM detector, 5 FM detector
             std::vector<int> mrel;          //   ... and the record offsets of blk[2] (option meter)
             long long frame = -1;           // the frame its present active state began with a catch-up of; -1: it did not
             unsigned long long sum_sq = 0;  // that frame's meter, folded as sdrx_get_meters folds it
             uint32_t clipped = 0, peak = 0;
         };
         std::vector<Leaf> leaf; // per node
-        static int slot(int kind) { return kind == KIND_LATE_DEC ? 0 : kind == KIND_DEMOD ? 1 : kind == KIND_LPF_LONG ? 2 : 3; }
+        static int slot(int kind) { return kind == KIND_LATE_DEC ? 0 : kind == KIND_DEMOD ? 1 : kind == KIND_LPF_LONG ? 2 : kind == KIND_DETECT_AM ? 4 : kind == KIND_DETECT_FM ? 5 : 3; }
     } cu;
 
     // A setting that changes between frames, as the host keeps it for what has not been delivered yet: a frame f >= since ran
@@ -538,7 +549,7 @@ struct sdrx_ctx : CtxBuffers {
     } dc;
     int root_frame = 0; // samples_per_buffer of the parent-less VFOs
     size_t off_k1vfo = 0;
-    size_t off_k2 = 0, off_k4 = 0; // the K2Vfo / K4Vfo arrays (sdrx_set_gains patches their gain)
+    size_t off_k2 = 0, off_k4 = 0, off_k5 = 0; // the K2Vfo / K4Vfo / K5Vfo arrays (sdrx_set_gains patches their gain)
     std::vector<Launch1> l1;
     std::vector<LaunchB> lb;
     std::vector<int> publish_order;

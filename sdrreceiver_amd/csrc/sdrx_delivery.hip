@@ -426,7 +426,7 @@ int sdrx_get_meters(sdrx_ctx *c, const int *ids, int n, sdrx_meter *out)
             out[k] = m;
             continue;
         }
-        m.n_values = (uint32_t)(nd.d.demod_usb ? nd.n_out : 2 * nd.n_f);
+        m.n_values = meter_n_values(nd);
         const MeterFold F = fold_meter_records(rec, nd.meter_first, nd.meter_n);
         m.sum_sq = F.sum_sq;
         m.clipped = F.clipped;

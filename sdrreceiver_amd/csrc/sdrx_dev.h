@@ -184,6 +184,19 @@ struct K4Vfo {
     int Hu, n, nlpf;
 };
 
+// ---- detector leaves: AM envelope / FM discriminator of a childless non-USB VFO's stream (detect.hip, sdrx_detect.h) ----------
+struct K5Vfo {
+    const float2 *s[2];          // the leaf's stream per frame parity (no history in front: 16-byte aligned)
+    short *pay[2];               // n int16, per frame parity
+    unsigned long long *part[2]; // AM: one partial of the carrier sum per block and frame parity (k_env_sum writes, k_detect<AM> adds)
+    float2 *zprev[2];            // FM: z[-1] of the frame of this parity (the tail of the frame before wrote it; zero for a new vfo)
+    float gain;
+    int n;                       // stream samples per frame
+    int kind;                    // kDetAm | kDetFm (sdrx_detect.h)
+    int meter_rel;               // option meter: byte offset from pay[par] to this leaf's first output-meter record (one per block)
+};
+static_assert(sizeof(K5Vfo) % 8 == 0, "K5Vfo array stride");
+
 struct NcoInit {
     float2 *cp;
     float rot_re, rot_im;
@@ -193,7 +206,7 @@ struct NcoInit {
 
 // One entry of k_vfo_retune's job list (sdrx_set_mixer_freqs, sdrx_set_gains).
 constexpr int kJobRetune = 0; // a new oscillator: regenerate vfo->cp, then write rot, rk and origin into *vfo
-constexpr int kJobGain = 1;   // *gain = value (K2Vfo::gain or K4Vfo::gain)
+constexpr int kJobGain = 1;   // *gain = value (K2Vfo::gain, K4Vfo::gain or K5Vfo::gain)
 struct RetuneJob {
     K1Vfo *vfo;
     float *gain;
@@ -208,7 +221,7 @@ static_assert(sizeof(RetuneJob) % 8 == 0, "RetuneJob array stride");
 // ---- option park (sdrx_set_active) ----------------------------------------------
 // What the park = 1 form of a kernel is given besides, in a trailing argument that is empty for the form without: the option
 // off runs the kernels as they were.  `act`: one word per descriptor of THAT kernel (K1Vfo: per node; K2aVfo / K2Vfo / K3Vfo /
-// K4Vfo: per entry of the array; the squelch gate: per leaf in publish order), 1 = active, 0 = parked.  A work unit reads its
+// K4Vfo / K5Vfo: per entry of the array; the squelch gate: per leaf in publish order), 1 = active, 0 = parked.  A work unit reads its
 // word first -- wave-uniform, a scalar load -- and returns if it is 0.
 // The mix items of the one-launch levels (k_mix_levels, k_levels_tail) carry the flag in a word they read anyway: bit kParkBit
 // of their entry of item_level[] is set while the leaf is parked (the exact k_levels_tail has no register for another pointer;

@@ -34,9 +34,10 @@ struct Built { // host copies of what goes to the arena, and where
     std::vector<K2Vfo> d2;
     std::vector<K3Vfo> d3;
     std::vector<K4Vfo> d4;
-    std::vector<BlockWork> w2a, w2, w3, w4;
-    std::vector<int> n2a, n2, n3, n4; // node index of each descriptor
-    size_t o2a = 0, o2 = 0, o3 = 0, o4 = 0, ow2a = 0, ow2 = 0, ow3 = 0, ow4 = 0;
+    std::vector<K5Vfo> d5;
+    std::vector<BlockWork> w2a, w2, w3, w4, w5am, w5fm; // (the detector leaves' blocks: one list per kind, one descriptor array)
+    std::vector<int> n2a, n2, n3, n4, n5; // node index of each descriptor
+    size_t o2a = 0, o2 = 0, o3 = 0, o4 = 0, o5 = 0, ow2a = 0, ow2 = 0, ow3 = 0, ow4 = 0, ow5am = 0, ow5fm = 0;
     std::vector<K1Work> all_items; // k_mix_levels: every level's items in one array ...
     std::vector<int> all_item_level, llist; // ... their levels, and the launch list over them
     std::vector<TailWg> tail_wgs;           // k_levels_tail's workgroup list (LevelPlan::tail)
@@ -157,6 +158,8 @@ int derive_nodes(sdrx_ctx *c)
         }
         if (!n.leaf && d.demod_usb)
             return fail(c, SDRX_EINVAL, "vfo %d has children but demod_usb set", i);
+        if (!n.leaf && n.detector)
+            return fail(c, SDRX_EINVAL, "vfo %d has children but a detector set (sdrx_set_detector)", i);
         max_level = std::max(max_level, n.level);
     }
     c->n_levels = max_level + 1;
@@ -228,11 +231,19 @@ void plan_buffers(sdrx_ctx *c, Built &B)
             n.pay_off = B.pay;
             if (d.demod_usb)
                 n.pay_len = (uint32_t)(n.n_out * 2);
+            else if (n.detector)
+                n.pay_len = (uint32_t)(2 * n.n_f); // n int16: exactly the bytes of the IQ leaf's int8 pairs
             else
                 n.pay_len = (uint32_t)(d.cstyle == 1 ? n.n_f : 2 * n.n_f); // vfo.cpp:143-150
             B.pay = align_up(B.pay + n.pay_len, 64);
             if (c->opt_prequant && d.demod_usb)
                 n.off_preq = plan.take(sizeof(float) * (size_t)n.n_out);
+            for (int p = 0; p < 2; ++p) { // a detector leaf's state: per frame parity the AM carrier's block partials, the FM z[-1]
+                if (n.detector == kDetAm)
+                    n.off_part[p] = plan.take(sizeof(unsigned long long) * (size_t)detect_blocks(n.n_f));
+                if (n.detector == kDetFm)
+                    n.off_zprev[p] = plan.take(sizeof(float2));
+            }
         }
         // SURVEY.md 8d algorithmic bytes: cf32 consumed + what this VFO hands on
         c->alg_bytes += 8ll * d.samples_per_buffer + (n.leaf ? (int64_t)n.pay_len : 8ll * n.n_f);
@@ -371,7 +382,7 @@ int build_mix_work(sdrx_ctx *c, Built &B)
 void build_tail_work(sdrx_ctx *c, Built &B)
 {
     const int N = (int)c->nodes.size();
-    int64_t b2 = 0, b3 = 0;
+    int64_t b2 = 0, b3 = 0, b5am = 0, b5fm = 0;
     int lds2a = 0;
     auto two_kernel_late = [](const Node &n) { return n.leaf && n.d.demod_usb && n.d.late_decimate > 0 && !n.fused_late; };
     // every late-decimating VFO left to a kernel of its own has L in {5,6} and <= 96 taps: one-wave tiles of k_late_decimate4,
@@ -425,6 +436,14 @@ void build_tail_work(sdrx_ctx *c, Built &B)
                 B.n4.push_back(i);
                 B.d4.push_back(K4Vfo{});
             }
+        } else if (n.detector) {
+            std::vector<BlockWork> &w = n.detector == kDetAm ? B.w5am : B.w5fm;
+            for (int b = 0; b < detect_blocks(n.n_f); ++b)
+                w.push_back({(int)B.d5.size(), b});
+            n.d5_index = (int)B.d5.size();
+            B.n5.push_back(i);
+            B.d5.push_back(K5Vfo{});
+            (n.detector == kDetAm ? b5am : b5fm) += n.pay_len;
         } else {
             for (int b = 0; b < (n.n_f + 4095) / 4096; ++b)
                 B.w3.push_back({(int)B.d3.size(), b});
@@ -472,6 +491,18 @@ void build_tail_work(sdrx_ctx *c, Built &B)
         B.o3 = plan.take(sizeof(K3Vfo) * B.d3.size());
         B.ow3 = plan.take(sizeof(BlockWork) * B.w3.size());
         c->lb.push_back({KIND_COMPRESS, (int)B.w3.size(), B.o3, B.ow3, 0, b3});
+    }
+    if (!B.d5.empty()) { // the detector leaves, where k_compress's launch sits: the AM leaves' two passes, then the FM leaves
+        B.o5 = plan.take(sizeof(K5Vfo) * B.d5.size());
+        c->off_k5 = B.o5;
+        if (!B.w5am.empty()) {
+            B.ow5am = plan.take(sizeof(BlockWork) * B.w5am.size());
+            c->lb.push_back({KIND_DETECT_AM, (int)B.w5am.size(), B.o5, B.ow5am, 0, b5am});
+        }
+        if (!B.w5fm.empty()) {
+            B.ow5fm = plan.take(sizeof(BlockWork) * B.w5fm.size());
+            c->lb.push_back({KIND_DETECT_FM, (int)B.w5fm.size(), B.o5, B.ow5fm, 0, b5fm});
+        }
     }
 }
 
@@ -634,7 +665,7 @@ void build_meter_plan(sdrx_ctx *c, Built &B)
             while (n.meter_shift < 15 && (2 << n.meter_shift) <= gap) // (15: what K2Vfo::meter_rel has room for)
                 n.meter_shift++;
             n.meter_n = (fo.back() >> n.meter_shift) + 1;
-        } else if (!n.d.demod_usb) {
+        } else if (!n.d.demod_usb) { // (k_compress's blocks or a detector's: the same geometry)
             n.meter_n = (n.n_f + 4095) / 4096;
         } else if (n.long_lpf) {
             n.meter_n = (n.n_out + 255) / 256;
@@ -823,6 +854,23 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
         k.scalecomp = n.d.scalecomp;
         k.meter_rel = c->opt_meter ? meter_rel(c, n) : 0;
     }
+    for (size_t q = 0; q < B.d5.size(); ++q) {
+        Node &n = c->nodes[(size_t)B.n5[q]];
+        K5Vfo &k = B.d5[q];
+        memset(&k, 0, sizeof k);
+        for (int p = 0; p < 2; ++p) {
+            k.s[p] = reinterpret_cast<const float2 *>(P(n.off_stream[p])) + n.Hx;
+            k.pay[p] = reinterpret_cast<short *>(c->d_pay[p] + n.pay_off);
+            k.part[p] = n.detector == kDetAm ? reinterpret_cast<unsigned long long *>(P(n.off_part[p])) : nullptr;
+            k.zprev[p] = n.detector == kDetFm ? reinterpret_cast<float2 *>(P(n.off_zprev[p])) : nullptr;
+            if (reinterpret_cast<uintptr_t>(k.s[p]) % 16) // (k_detect loads sample pairs)
+                return fail(c, SDRX_EUNSUPPORTED, "vfo %d: detector stream %d is not 16-byte aligned", B.n5[q], p);
+        }
+        k.gain = n.d.gain;
+        k.n = n.n_f;
+        k.kind = n.detector;
+        k.meter_rel = c->opt_meter ? meter_rel(c, n) : 0;
+    }
     auto up = [&](size_t off, const void *src, size_t bytes) -> hipError_t {
         return bytes ? hipMemcpyAsync(P(off), src, bytes, hipMemcpyHostToDevice, c->st.stream) : hipSuccess;
     };
@@ -838,6 +886,9 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
     HIPCHK(c, up(B.ow4, B.w4.data(), sizeof(BlockWork) * B.w4.size()));
     HIPCHK(c, up(B.o3, B.d3.data(), sizeof(K3Vfo) * B.d3.size()));
     HIPCHK(c, up(B.ow3, B.w3.data(), sizeof(BlockWork) * B.w3.size()));
+    HIPCHK(c, up(B.o5, B.d5.data(), sizeof(K5Vfo) * B.d5.size()));
+    HIPCHK(c, up(B.ow5am, B.w5am.data(), sizeof(BlockWork) * B.w5am.size()));
+    HIPCHK(c, up(B.ow5fm, B.w5fm.data(), sizeof(BlockWork) * B.w5fm.size()));
     if (c->fp.usable) {
         HIPCHK(c, up(c->fp.off_items, B.all_items.data(), sizeof(K1Work) * B.all_items.size()));
         HIPCHK(c, up(c->fp.off_item_level, B.all_item_level.data(), sizeof(int) * B.all_item_level.size()));
@@ -949,7 +1000,8 @@ int park_setup(sdrx_ctx *c, const Built &B)
     K.o_2 = K.o_2a + B.d2a.size();
     K.o_3 = K.o_2 + B.d2.size();
     K.o_4 = K.o_3 + B.d3.size();
-    K.o_sq = K.o_4 + B.d4.size();
+    K.o_5 = K.o_4 + B.d4.size();
+    K.o_sq = K.o_5 + B.d5.size();
     K.words = K.o_sq + c->publish_order.size();
     K.leaf.assign(c->nodes.size(), sdrx_ctx::Park::Leaf());
     K.items.assign(c->nodes.size(), {});
@@ -1027,6 +1079,10 @@ void catchup_setup(sdrx_ctx *c, const Built &B)
     }
     for (const BlockWork &w : B.w3)
         c->cu.leaf[(size_t)B.n3[(size_t)w.vfo]].blk[3].push_back(w);
+    for (const BlockWork &w : B.w5am)
+        c->cu.leaf[(size_t)B.n5[(size_t)w.vfo]].blk[4].push_back(w);
+    for (const BlockWork &w : B.w5fm)
+        c->cu.leaf[(size_t)B.n5[(size_t)w.vfo]].blk[5].push_back(w);
 }
 
 // Option adc_meter: what k_adc_meter needs for this context's frames -- one partial per workgroup of a frame, the launch's

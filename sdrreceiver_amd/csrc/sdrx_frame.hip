@@ -394,7 +394,7 @@ void agc_step(sdrx_ctx *c, hipStream_t ts, unsigned long long frame)
 // `n_blocks` entries of the work list `w` (k_lpf_long with option meter: and of the record offsets `mrel`).
 void launch_block_list(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned long long frame, const BlockWork *w, const int *mrel, int n_blocks)
 {
-    Bracket b(c, ts, L.kind, L.alg_bytes);
+    Bracket b(c, ts, bracket_kind(L.kind), L.alg_bytes);
     const dim3 grid(n_blocks);
     const unsigned char *desc = c->arena + L.off_desc;
     with_variant(c, [&](auto EXACT, auto, auto METER, auto PARK) {
@@ -410,6 +410,13 @@ void launch_block_list(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned l
         else if (L.kind == KIND_LPF_LONG)
             hipLaunchKernelGGL((k_lpf_long<EXACT(), METER(), PARK()>), grid, dim3(256), L.lds_bytes, ts, reinterpret_cast<const K4Vfo *>(desc), w, frame, mrel,
                                park_arg<PARK()>(c, c->park.o_4));
+        else if (L.kind == KIND_DETECT_AM) { // the carrier's partials of every block, then the blocks themselves
+            hipLaunchKernelGGL((k_env_sum<PARK()>), grid, dim3(kDetThreads), 0, ts, reinterpret_cast<const K5Vfo *>(desc), w, frame, park_arg<PARK()>(c, c->park.o_5));
+            hipLaunchKernelGGL((k_detect<kDetAm, METER(), PARK()>), grid, dim3(kDetThreads), 0, ts, reinterpret_cast<const K5Vfo *>(desc), w, frame,
+                               park_arg<PARK()>(c, c->park.o_5));
+        } else if (L.kind == KIND_DETECT_FM)
+            hipLaunchKernelGGL((k_detect<kDetFm, METER(), PARK()>), grid, dim3(kDetThreads), 0, ts, reinterpret_cast<const K5Vfo *>(desc), w, frame,
+                               park_arg<PARK()>(c, c->park.o_5));
         else
             hipLaunchKernelGGL((k_compress<METER(), PARK()>), grid, dim3(256), 0, ts, reinterpret_cast<const K3Vfo *>(desc), w, frame,
                                park_arg<PARK()>(c, c->park.o_3));

@@ -9,7 +9,7 @@ namespace {
 // Every word that says whether leaf `id` runs, and every word that makes it a new vfo when it starts to:
 //   emit(ptr, words, v_on, v_off, wake_only) -- `words` 32-bit words from `ptr` on become v_on when the leaf is unparked and,
 //   unless wake_only, v_off when it is parked.
-// The flag words in Park::d_act (K1, 2a, 2, 3, 4, the gate) and the item_level[] words with kParkBit; then, wake_only, zeros over
+// The flag words in Park::d_act (K1, 2a, 2, 3, 4, 5, the gate) and the item_level[] words with kParkBit; then, wake_only, zeros over
 // every filter-state region of both frame parities (whichever the next frame reads: the reference's zero-initialised filter
 // state, dsp.cpp:40-49), the gate state of sdrx_finalize -- prev_open = `prev_open`: 1, or 0 for a leaf that is caught up -- and
 // the AGC's quiet_run.  The oscillator's origin is not a fill: the caller writes K1Vfo::origin.
@@ -32,6 +32,8 @@ void leaf_regions(sdrx_ctx *c, int id, unsigned prev_open, const std::function<v
         put(K.d_act + K.o_3 + nd.d3_index, 1, 1, 0, false);
     if (nd.d4_index >= 0)
         put(K.d_act + K.o_4 + nd.d4_index, 1, 1, 0, false);
+    if (nd.d5_index >= 0)
+        put(K.d_act + K.o_5 + nd.d5_index, 1, 1, 0, false);
     const int sq = c->opt_squelch ? c->sq.index[(size_t)id] : -1; // (without the gate nothing reads its words)
     if (sq >= 0)
         put(K.d_act + K.o_sq + sq, 1, 1, 0, false);
@@ -48,6 +50,8 @@ void leaf_regions(sdrx_ctx *c, int id, unsigned prev_open, const std::function<v
             put(c->arena + nd.off_z[p], 2 * (size_t)nd.H, 0, 0, true);
         if (nd.long_lpf)
             put(c->arena + nd.off_u[p], (size_t)nd.Hu, 0, 0, true);
+        if (nd.detector == kDetFm) // z[-1] = 0 + 0j: the one place a detector leaf's start as a new vfo is defined (AM carries nothing)
+            put(c->arena + nd.off_zprev[p], 2, 0, 0, true);
     }
     if (sq >= 0) { // the gate state of sdrx_finalize; thresholds, hang time, ratio and window stay
         put(c->sq.d_hang + sq, 1, 0, 0, true);

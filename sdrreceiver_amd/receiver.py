@@ -71,10 +71,14 @@ class _LeafCalls:
 
     def _payload(self, vid, buf, length) -> np.ndarray:
         raw = C.string_at(buf.value, length.value) if length.value else b""
-        return np.frombuffer(raw, dtype=np.int16 if self.descs[vid].demod_usb else np.int8).copy()
+        return np.frombuffer(raw, dtype=np.int16 if self._int16(vid) else np.int8).copy()
+
+    def _int16(self, vid) -> bool:
+        """int16 payload values: a USB leaf or a detector leaf; int8 otherwise (compress())"""
+        return bool(self.descs[vid].demod_usb or self.descs[vid].detector)
 
     def output(self, vid: int) -> np.ndarray:
-        """Leaf `vid`'s payload of the last delivered frame (int16 audio or int8 I/Q)."""
+        """Leaf `vid`'s payload of the last delivered frame (int16 audio -- USB or a detector's -- or int8 I/Q)."""
         buf, ln, rate = C.c_void_p(), C.c_uint32(), C.c_uint32()
         self._call("get_output", vid, C.byref(buf), C.byref(ln), C.byref(rate))
         return self._payload(vid, buf, ln)
@@ -83,7 +87,7 @@ class _LeafCalls:
         """Output meters of the leaves `vids` for the last delivered frame (option ``meter``): arrays in the order of
         `vids` -- see :func:`sdrreceiver_amd.meter.meters_dict`."""
         ids, out = self._get_list("get_meters", vids, _lib.MeterC)
-        return meter.meters_dict(out, [self.descs[i].demod_usb for i in ids.tolist()])
+        return meter.meters_dict(out, [self._int16(i) for i in ids.tolist()])
 
     # -- squelch-gated egress (option ``squelch``; sdrreceiver_amd.squelch has the definition) ---------------------
     def set_squelch(self, vids, thr_sum_sq, hang_frames) -> None:
@@ -170,7 +174,7 @@ class _LeafCalls:
         ``frame`` is -1 (and the figures 0) for a leaf whose present active state did not begin with a catch-up.  Good as
         soon as :meth:`set_active` has returned."""
         ids, out = self._get_list("get_catchup", vids, _lib.MeterC)
-        return meter.meters_dict(out, [self.descs[i].demod_usb for i in ids.tolist()])
+        return meter.meters_dict(out, [self._int16(i) for i in ids.tolist()])
 
     # -- channel watch (option ``watch``; sdrreceiver_amd.watch): band power of a leaf from its source's spectrum -------------
     def set_watch(self, vids, on) -> None:
@@ -414,7 +418,23 @@ class Receiver(_LeafCalls):
         out = C.c_int(-1)
         self._chk(self.L.sdrx_add_vfo(self.h, C.byref(c), C.byref(out)))
         self.descs.append(d)
+        if d.detector:
+            self.set_detector(out.value, d.detector)
         return out.value
+
+    def set_detector(self, vid: int, kind: int) -> None:
+        """Before finalize: leaf `vid` (``demod_usb`` False) leaves as an AM envelope (1) or an FM discriminator (2) in int16
+        instead of compress()'s bytes (sdrreceiver_amd.detect); 0 takes the detector away."""
+        cfg = _lib.DetectCfgC(kind=int(kind))
+        self._chk(self.L.sdrx_set_detector(self.h, int(vid), C.byref(cfg)))
+        if 0 <= vid < len(self.descs):
+            self.descs[vid] = dataclasses.replace(self.descs[vid], detector=int(kind))
+
+    def detector(self, vid: int) -> int:
+        """The detector kind of VFO `vid` (0 none, 1 AM, 2 FM)."""
+        cfg = _lib.DetectCfgC()
+        self._chk(self.L.sdrx_get_detector(self.h, int(vid), C.byref(cfg)))
+        return int(cfg.kind)
 
     def finalize(self):
         if self._input_rate:
@@ -899,6 +919,8 @@ class Group(_LeafCalls):
     def from_topology(cls, topo: Topology, devices, **kw) -> "Group":
         g = cls(devices, **kw)
         for d in topo.vfos:
+            if d.detector:
+                raise ValueError("groups do not offer detector leaves (include/sdrx.h \"Detector leaves\")")
             c = _lib.desc_to_c(d)
             out = C.c_int(-1)
             g._chk(g.L.sdrx_group_add_vfo(g.h, C.byref(c), C.byref(out)))
@@ -1034,6 +1056,7 @@ class vfo:  # noqa: N801  (the reference's class name, vfo.h:11)
     def setGain(self, g): self.desc.gain = float(np.float32(g))
     def setDemodUSB(self, usb): self.desc.demod_usb = bool(usb)
     def getDemodUSB(self): return self.desc.demod_usb
+    def setDetector(self, kind): self.desc.detector = int(kind)  # (no counterpart in vfo.h: sdrx_set_detector, 0 none / 1 AM / 2 FM)
     def setCompressonStyle(self, st): self.desc.cstyle = int(st)  # sic
     def setScaleComp(self, scale): self.desc.scalecomp = int(scale)
     def setZmqTopic(self, topic): self.desc.topic = str(topic)

@@ -25,6 +25,8 @@ SUPPORTED_RATES = (288000, 1536000, 1920000)  # mainwindow.h:29
 class VfoDesc:
     """One VFO node.  Field <-> reference setter (vfo.h:21-38):
 
+    (``detector`` has no reference setter: include/sdrx.h "Detector leaves", sdrreceiver_amd.detect.)
+
     fs <-> setFs, decimate_count <-> setDecimationCount, mixer_freq <-> setMixerFreq,
     demod_usb <-> setDemodUSB, filter_bw <-> setFilterBandwidth, gain <-> setGain,
     cstyle <-> setCompressonStyle, scalecomp <-> setScaleComp, topic <-> setZmqTopic,
@@ -44,6 +46,7 @@ class VfoDesc:
     cstyle: int = 0
     scalecomp: int = 1
     samples_per_buffer: int = 0
+    detector: int = 0  # sdrx_set_detector (no counterpart in the reference): 0 none, 1 AM, 2 FM -- a leaf with demod_usb False only
 
     @property
     def out_rate_stage(self) -> int:
@@ -242,6 +245,14 @@ def topology_from_ini(text: str, name: str = "", mix_offset: int | None = None) 
         out_rate = _to_int(kv.get(p + "out_rate"))
         if out_rate == 0 and data_rate > 0:
             out_rate = {600: 12000, 1200: 24000}.get(data_rate, 48000)
+        # `detector=am|fm` (no key of the reference, which ignores keys it does not know): the entry leaves as an AM envelope or an
+        # FM discriminator in int16 (sdrreceiver_amd.detect) and is placed as a 48 kS/s sub is
+        det_key = kv.get(p + "detector", "").strip().lower()
+        if det_key not in ("", "am", "fm"):
+            raise ValueError(f"vfos/{i}: detector={det_key!r}: only am and fm are offered")
+        detector = {"": 0, "am": 1, "fm": 2}[det_key]
+        if detector and out_rate == 0:
+            out_rate = 48000
         if out_rate <= 0:
             raise ValueError(f"vfos/{i}: neither out_rate nor data_rate given")
         filterbw = _to_int(kv.get(p + "filter_bandwidth"))
@@ -262,6 +273,16 @@ def topology_from_ini(text: str, name: str = "", mix_offset: int | None = None) 
         gain = float(_to_float32(kv.get(p + "gain")) / np.float32(100))
         if not mains:
             raise ValueError("profile has sub VFOs but no main VFO")
+        if detector and late:
+            raise ValueError(f"vfos/{i}: detector={det_key} below a main VFO of {main_out} S/s would need the late decimation by {late}, "
+                             "which runs in front of the USB demodulation only: give the entry a main VFO whose out_rate is a power of two "
+                             "times its own")
+        if detector:
+            topo.vfos.append(VfoDesc(
+                topic=kv.get(p + "topic", ""), parent=mains[main_idx], fs=main_out, decimate_count=d,
+                mixer_freq=float((center - main_vfo_freq) - vfo_freq), demod_usb=False, gain=gain, cstyle=0,
+                samples_per_buffer=main_out // bufsplit, detector=detector))
+            continue
         topo.vfos.append(VfoDesc(
             topic=kv.get(p + "topic", ""), parent=mains[main_idx], fs=main_out, decimate_count=d,
             mixer_freq=float((center - main_vfo_freq) - vfo_freq), demod_usb=True, late_decimate=late,
