@@ -3,7 +3,8 @@
 // frames to sdrj::demodData, receive every leaf's payload through the publish hook.
 //
 //   sdrx_demo <profile.ini> --dump              descriptors as JSON lines (no GPU needed)
-//                                               (a [vfos] entry with detector=am|fm is a detector leaf: int16 messages at 48 kS/s)
+//                                               (a [vfos] entry with detector=am|fm is a detector leaf: int16 messages at 48 kS/s,
+//                                               or at 48 kS/s / post_decim behind post_decim, post_taps, post_cutoff_hz, post_atten_db)
 //   sdrx_demo <profile.ini> --frames N [--u8] [--format cu8|cs8|cs16|rs16|ru12] [--adc] [--input-rate HZ]
 //                                   [--front-stages N [--front-real] [--front-taps K]] [--blanker RATIO,GUARD[,FLOOR[,RANK]]]
 //                                   [--iq-balance MU,MINPOWER[,C0,D0]] [--shift HZ] [--notch HZ[,HZ...]:MU[,AFC,COH,PULLHZ]]
@@ -83,9 +84,12 @@ int main(int argc, char **argv)
                 for (vfo *v : P->subs[m]) {
                     const sdrx_vfo_desc &d = v->d;
                     std::printf("{\"sub_of\": %zu, \"topic\": \"%s\", \"fs\": %d, \"d\": %d, \"late\": %d, \"mixer\": %.1f, \"bw\": %d, "
-                                "\"gain\": %.9g, \"spb\": %d, \"usb\": %d, \"detector\": %d}\n",
+                                "\"gain\": %.9g, \"spb\": %d, \"usb\": %d, \"detector\": %d, \"post_decim\": %d, \"post_taps\": [",
                                 m, v->topic.c_str(), d.fs, d.decimate_count, d.late_decimate, d.mixer_freq_hz, d.filter_bw_hz, (double)d.gain,
-                                d.samples_per_buffer, d.demod_usb, v->getDetector());
+                                d.samples_per_buffer, d.demod_usb, v->getDetector(), v->getPostDecim());
+                    for (size_t t = 0; t < v->getPostTaps().size(); ++t)
+                        std::printf("%s%.9g", t ? ", " : "", (double)v->getPostTaps()[t]);
+                    std::printf("]}\n");
                 }
             return 0;
         }

@@ -52,6 +52,15 @@ public:
     // (SDRX_DETECT_FM) in int16 instead of compress()'s bytes (include/sdrx.h "Detector leaves"); a single context only
     void setDetector(int kind) { detector = kind; }
     int getDetector() const { return detector; }
+    // no counterpart in vfo.h either: a detector leaf leaves through a FIR of `taps` over the detector's floats, decimated by
+    // `decim` (include/sdrx.h "Post-detection filter"); no taps take it away; a single context only
+    void setPostFilter(const std::vector<float> &taps, int decim)
+    {
+        postTaps = taps;
+        postDecim = taps.empty() ? 1 : decim;
+    }
+    const std::vector<float> &getPostTaps() const { return postTaps; }
+    int getPostDecim() const { return postDecim; }
     void setScaleComp(int scale) { d.scalecomp = scale; }
     void setZmqTopic(const std::string &t)
     {
@@ -78,6 +87,8 @@ public:
     std::vector<vfo *> *mpVFOs = nullptr;
     int id = -1;
     int detector = SDRX_DETECT_NONE;
+    std::vector<float> postTaps;
+    int postDecim = 1;
     bool initialised = false;
 };
 
@@ -707,6 +718,15 @@ private:
             cfg.kind = v->detector;
             check(sdrx_set_detector(ctx_, v->id, &cfg), "sdrx_set_detector");
         }
+        if (!v->postTaps.empty()) {
+            if (grp_)
+                throw std::runtime_error("vfo::setPostFilter: groups do not offer the post-detection filter (include/sdrx.h \"Post-detection filter\")");
+            sdrx_postfilter_cfg cfg;
+            std::memset(&cfg, 0, sizeof cfg);
+            cfg.decim = v->postDecim;
+            cfg.ntaps = (int32_t)v->postTaps.size();
+            check(sdrx_set_postfilter(ctx_, v->id, &cfg, v->postTaps.data()), "sdrx_set_postfilter");
+        }
         if (v->mpVFOs)
             for (vfo *c : *v->mpVFOs)
                 add(c, v->id);
@@ -976,6 +996,20 @@ inline std::unique_ptr<Profile> load_profile(std::istream &in)
             ch = (char)std::tolower((unsigned char)ch);
         if (!det.empty() && det != "am" && det != "fm")
             throw std::runtime_error(ini.item("vfos", i, "") + ": detector=" + det + ": only am and fm are offered");
+        // `post_decim`, `post_taps`, `post_cutoff_hz`, `post_atten_db` (no keys of the reference): all four or none, on an entry with
+        // `detector=` -- its post-detection filter, designed at the leaf's rate
+        const char *post_keys[4] = {"post_decim", "post_taps", "post_cutoff_hz", "post_atten_db"};
+        std::string post_val[4];
+        int post_given = 0;
+        for (int k = 0; k < 4; ++k) {
+            post_val[k] = ini.text(key(post_keys[k]));
+            post_given += !post_val[k].empty();
+        }
+        if (post_given != 0 && post_given != 4)
+            throw std::runtime_error(ini.item("vfos", i, "") + ": the post-detection filter takes all four keys or none (post_decim, post_taps, "
+                                                              "post_cutoff_hz, post_atten_db)");
+        if (post_given && det.empty())
+            throw std::runtime_error(ini.item("vfos", i, "") + ": post_decim, post_taps, post_cutoff_hz and post_atten_db belong to an entry with detector=am|fm");
         if (!det.empty() && out_rate == 0)
             out_rate = 48000;
         if (out_rate <= 0)
@@ -1004,6 +1038,23 @@ inline std::unique_ptr<Profile> load_profile(std::istream &in)
             v.setFilterBandwidth(0);
             v.setCompressonStyle(0);
             v.setDetector(det == "am" ? SDRX_DETECT_AM : SDRX_DETECT_FM);
+            if (post_given) {
+                const int R = std::atoi(post_val[0].c_str()), T = std::atoi(post_val[1].c_str());
+                const int n = (pl.input_rate / P.bufsplit) >> v.d.decimate_count;
+                const double rate = (double)(pl.input_rate >> v.d.decimate_count);
+                const std::string where = ini.item("vfos", i, "") + ": post-detection filter: ";
+                if (T < 1 || T > SDRX_POSTFILTER_MAX_TAPS)
+                    throw std::runtime_error(where + "ntaps must be 1 .. 256");
+                if (R < 1 || R > SDRX_POSTFILTER_MAX_DECIM)
+                    throw std::runtime_error(where + "decim must be 1 .. 16");
+                if (n % R)
+                    throw std::runtime_error(where + "the leaf's samples per frame are not a multiple of decim");
+                std::vector<float> taps((size_t)T);
+                const int rc = sdrx_postfilter_design(rate, std::atof(post_val[2].c_str()), T, std::atof(post_val[3].c_str()), taps.data(), T, nullptr);
+                if (rc != SDRX_OK)
+                    throw std::runtime_error(where + sdrx_last_error(nullptr));
+                v.setPostFilter(taps, R);
+            }
         }
         v.init(pl.input_rate / P.bufsplit, true, pl.late_decimate);
         P.subs[(size_t)pl.main_index].push_back(&v);

@@ -1382,8 +1382,8 @@ int sdrx_get_spectrum_levels(sdrx_ctx *ctx, const int *ids, int n, double *maxva
  *   z[-1] of a frame is the last stream sample of the leaf's frame before; 0 + 0j for a leaf that sdrx_finalize, sdrx_set_active,
  *   the catch-up or the wake starts as a new vfo.
  *
- * `gain` acts as on a USB leaf (sdrx_set_gains included); cstyle, scalecomp and filter_bw_hz are ignored -- there is no
- * post-detection filter.  The leaf publishes by the IQ leaf's rule (only with a topic; rate = fs / 2^decimate_count, len = 2 n), its
+ * `gain` acts as on a USB leaf (sdrx_set_gains included); cstyle, scalecomp and filter_bw_hz are ignored -- the post-detection
+ * filter is a setting of its own ("Post-detection filter", below).  The leaf publishes by the IQ leaf's rule (only with a topic; rate = fs / 2^decimate_count, len = 2 n), its
  * watch band is the IQ leaf's, and its output meter is the USB leaves' (n_values = n, int16 full scale).  The squelch gate, the
  * auto-squelch, the pre-roll, parking, the catch-up, the watch and the wake serve it as they serve any leaf; sdrx_set_agc answers
  * what it answers for an IQ leaf; fuse_demod and keep_prequant do not apply.  sdrx_get_kernel_times books its launches with
@@ -1403,6 +1403,68 @@ typedef struct sdrx_detect_cfg { /* 16 bytes */
 } sdrx_detect_cfg;
 int sdrx_set_detector(sdrx_ctx *ctx, int id, const sdrx_detect_cfg *cfg);
 int sdrx_get_detector(sdrx_ctx *ctx, int id, sdrx_detect_cfg *cfg_out);
+
+/* ---- Post-detection filter: a FIR low-pass and a decimation on a detector leaf ---------------------------------------------------
+ * No counterpart in the reference.  A detector leaf can be given a real FIR of the caller's taps h[t], t < T, over the detector's
+ * pre-quantisation floats, decimated by an integer R, before sdrx_finalize.  It carries its state from frame to frame.  This text
+ * is the definition; csrc/sdrx_postdet.h spells it per output and sdrreceiver_amd/postdet.py is the model the tests hold the device
+ * to, bit for bit, in every setting of option "exact".
+ *
+ * pre_f[i], 0 <= i < n, is frame f's value of step 4 (AM) or step 3 (FM) of "Detector leaves", before the conversion.
+ *   - The carrier and gain are those frame f had.
+ *   - For j < 0, pre_f[j] := pre_{f-1}[n + j].
+ *     - This applies recursively when n < T - 1.
+ *     - It is +0.0f for a leaf that sdrx_finalize, sdrx_set_active, the catch-up or the wake starts as a new vfo.
+ *     - An FM leaf started that way still has z[-1] = 0 as well.
+ *   - A gain change or a new AM carrier does not rewrite history: the filter sees what a host filter behind the channel would have
+ *     seen.
+ *
+ * With taps h[t], t < T, and decimation R, for output m in [0, n / R):
+ *
+ *   acc_0 = +0.0f;   acc_{t+1} = fl(acc_t + fl(h[t] * pre[m R - t])),  t = 0 .. T-1 ascending;   y[m] = acc_T
+ *
+ *   - Two roundings per tap, no FMA, the same in all three settings of exact.  This is the idiom of the resampler and the front
+ *     stage.
+ *   - The payload is the USB leaves' conversion of y[m]: n / R int16.
+ *   - The output meter is meter_usb over those n / R values (n_values = n / R).
+ *   - The leaf publishes by the IQ leaf's rule with rate = fs / 2^decimate_count / R and len = 2 n / R.
+ *   - The group delay is (T - 1) / 2 stream samples.
+ *   - T = 1, h = {1.0f}, R = 1 is the identity.  Payload and meter records are bit for bit those of the same leaf without the
+ *     stage.
+ *   - Behaviour on non-finite pre is whatever IEEE gives.
+ *
+ * Limits: 1 <= T <= 256; 1 <= R <= 16; n % R == 0, else SDRX_EUNSUPPORTED at sdrx_finalize with the reason in sdrx_last_error.
+ *
+ * The squelch gate, the pre-roll, parking, the catch-up and the wake serve the shorter payload as they serve any leaf's; the
+ * launches are booked with k_compress.  With no post filter anywhere the library launches, allocates and delivers exactly what it
+ * did without this section.  Not offered: IIR de-emphasis, a DC block for FM, changing taps on a running tree, groups, the AGC.
+ *
+ * sdrx_set_postfilter: before sdrx_finalize (SDRX_ESTATE after it, and so on a group's members); SDRX_EINVAL for a bad id, limits
+ * exceeded, null taps or a non-zero reserved word; ntaps = 0 takes the filter away (decim and taps are not looked at).  The taps
+ * are copied.  sdrx_finalize returns SDRX_EINVAL for a node that carries a post filter without a detector.
+ * sdrx_get_postfilter: at any time; SDRX_ESTATE for a node without one.  `taps` may be NULL; otherwise min(ntaps, cap) floats are
+ * written.  out_len = n / R once the tree is finalized (0 before), delay_samples = (T - 1) / 2; pass_hz = stop_hz = 0: the
+ * library does not know how the caller's taps were made.
+ * sdrx_postfilter_design needs no context and no device: a Kaiser low-pass in IEEE double, rounded once to fp32.  With
+ * N = ntaps and A = atten_db: beta = 0.1102 (A - 8.7) and tw = (A - 7.95) / (2.285 (N - 1) 2 pi) -- sdrx_resampler_design's --,
+ * fc = cutoff_hz / fs, h[k] = 2 fc sinc(2 fc (k - (N-1)/2)) I0(beta sqrt(1 - (2k/(N-1) - 1)^2)) / I0(beta), divided by the double
+ * sum of the h[k] taken with k ascending: unit DC gain.  SDRX_EINVAL unless 50 < A <= 120, 1 <= N <= 256, fs > 0, cutoff_hz > 0
+ * and (with taps given) cap >= N; SDRX_EFILTER if fc - tw/2 <= 0 or fc + tw/2 > 0.5 (N = 1 always).  `taps` and `info` may be
+ * NULL.  info: decim = 0, out_len = 0, ntaps = N, delay_samples = (N - 1) / 2, pass_hz = (fc - tw/2) fs, stop_hz = (fc + tw/2) fs.
+ * Whether stop_hz <= fs / (2 R) is the caller's decision; no default is offered. */
+#define SDRX_POSTFILTER_MAX_TAPS 256
+#define SDRX_POSTFILTER_MAX_DECIM 16
+typedef struct sdrx_postfilter_cfg { /* 16 bytes */
+    int32_t decim, ntaps;
+    int32_t reserved[2];
+} sdrx_postfilter_cfg;
+typedef struct sdrx_postfilter_info { /* 40 bytes */
+    int32_t decim, ntaps, out_len, reserved;
+    double delay_samples, pass_hz, stop_hz;
+} sdrx_postfilter_info;
+int sdrx_set_postfilter(sdrx_ctx *ctx, int id, const sdrx_postfilter_cfg *cfg, const float *taps);
+int sdrx_get_postfilter(sdrx_ctx *ctx, int id, sdrx_postfilter_info *info, float *taps, int32_t cap);
+int sdrx_postfilter_design(double fs, double cutoff_hz, int32_t ntaps, double atten_db, float *taps, int32_t cap, sdrx_postfilter_info *info);
 
 /* ---- one tree on several GPUs, one host process ---------------------------------------------------
  * The fan-out the reference does on one thread -- sdrj::demodData over the main VFOs (sdrj.cpp:288-294),

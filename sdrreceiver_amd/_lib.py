@@ -203,6 +203,17 @@ class DetectCfgC(C.Structure):
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class PostfilterCfgC(C.Structure):
+    """struct sdrx_postfilter_cfg"""
+    _fields_ = [("decim", C.c_int32), ("ntaps", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class PostfilterInfoC(C.Structure):
+    """struct sdrx_postfilter_info"""
+    _fields_ = [("decim", C.c_int32), ("ntaps", C.c_int32), ("out_len", C.c_int32), ("reserved", C.c_int32),
+                ("delay_samples", C.c_double), ("pass_hz", C.c_double), ("stop_hz", C.c_double)]
+
+
 class NotchToneC(C.Structure):
     """struct sdrx_notch_tone"""
     _fields_ = [("inc", C.c_uint32), ("inc_next", C.c_uint32), ("a_re_bits", C.c_uint32), ("a_im_bits", C.c_uint32), ("coherent", C.c_uint32),
@@ -328,6 +339,9 @@ SYMBOLS = {
     "sdrx_get_notch": (_i, [_vp, C.POINTER(NotchCfgC), C.POINTER(NotchRecordC)]),
     "sdrx_set_detector": (_i, [_vp, _i, C.POINTER(DetectCfgC)]),
     "sdrx_get_detector": (_i, [_vp, _i, C.POINTER(DetectCfgC)]),
+    "sdrx_set_postfilter": (_i, [_vp, _i, C.POINTER(PostfilterCfgC), _vp]),
+    "sdrx_get_postfilter": (_i, [_vp, _i, C.POINTER(PostfilterInfoC), _vp, C.c_int32]),
+    "sdrx_postfilter_design": (_i, [C.c_double, C.c_double, C.c_int32, C.c_double, _vp, C.c_int32, C.POINTER(PostfilterInfoC)]),
     "sdrx_set_spectrum": (_i, [_vp, _i, _i]),
     "sdrx_get_spectrum": (_i, [_vp, _i, C.POINTER(SpectrumInfoC), _vp, _vp, _vp]),
     "sdrx_get_spectrum_levels": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

@@ -51,6 +51,8 @@
 //   k_compress            compress.hip  vfo::compress, vfo.cpp:389-424
 //   k_env_sum, k_detect<KIND> detect.hip (none: sdrx_set_detector -- the int16 payload of a non-USB leaf as an AM envelope (carrier = the frame's
 //                                       own mean, summed in exact integers by k_env_sum) or an FM discriminator; include/sdrx.h "Detector leaves")
+//   k_detect_post<KIND>   postdet.hip   (none: sdrx_set_postfilter -- the same leaf through a real FIR of the caller's taps over the detector's floats,
+//                                       decimated by R, history carried per frame parity; include/sdrx.h "Post-detection filter")
 // (The kernels beside the chain have files of their own, included by sdrx.hip: spectrum.hip, squelch.hip, agc.hip, watch.hip, wake.hip,
 // drift.hip, scan.hip.)
 //
@@ -66,6 +68,7 @@
 #include "sdrx_shift.h"
 #include "sdrx_notch.h"
 #include "sdrx_detect.h"
+#include "sdrx_postdet.h"
 
 #include <type_traits>
 #include <utility>
@@ -89,5 +92,6 @@ namespace sdrx {
 #include "levels.hip"
 #include "compress.hip"
 #include "detect.hip"
+#include "postdet.hip"
 
 } // namespace sdrx

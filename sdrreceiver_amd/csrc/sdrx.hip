@@ -96,6 +96,10 @@ static_assert(sizeof(sdrx_notch_cfg) == 96 && sizeof(NotchCfg) == 96 && offsetof
 static_assert(sizeof(sdrx_detect_cfg) == 16 && sizeof(DetectCfg) == 16 && offsetof(sdrx_detect_cfg, reserved) == offsetof(DetectCfg, reserved) &&
                   SDRX_DETECT_NONE == kDetNone && SDRX_DETECT_AM == kDetAm && SDRX_DETECT_FM == kDetFm,
               "sdrx_detect_cfg ABI layout");
+static_assert(sizeof(sdrx_postfilter_cfg) == 16 && sizeof(PostCfg) == 16 && offsetof(sdrx_postfilter_cfg, reserved) == offsetof(PostCfg, reserved) &&
+                  sizeof(sdrx_postfilter_info) == 40 && offsetof(sdrx_postfilter_info, delay_samples) == 16 && SDRX_POSTFILTER_MAX_TAPS == kPdMaxTaps &&
+                  SDRX_POSTFILTER_MAX_DECIM == kPdMaxDecim,
+              "sdrx_postfilter_cfg / sdrx_postfilter_info ABI layout");
 static_assert(sizeof(sdrx_adc_arm) == 40 && sizeof(AdcArm) == 40 && offsetof(sdrx_adc_arm, longest_rail_run) == offsetof(AdcArm, longest_rail_run) &&
                   sizeof(sdrx_adc_meter) == 184 && sizeof(AdcRecord) == 184 && offsetof(sdrx_adc_meter, q) == offsetof(AdcRecord, q) &&
                   offsetof(sdrx_adc_meter, sum_iq) == offsetof(AdcRecord, sum_iq) && offsetof(sdrx_adc_meter, bits) == offsetof(AdcRecord, bits),
@@ -1320,6 +1324,71 @@ int sdrx_get_detector(sdrx_ctx *c, int id, sdrx_detect_cfg *cfg_out)
         return fail(c, SDRX_EINVAL, "sdrx_get_detector: bad vfo id %d or null output", id);
     memset(cfg_out, 0, sizeof *cfg_out);
     cfg_out->kind = c->nodes[(size_t)id].detector;
+    return SDRX_OK;
+}
+
+// ---- Post-detection filter (include/sdrx.h; sdrx_postdet.h has the rules and the design) -------------------------------------------
+int sdrx_set_postfilter(sdrx_ctx *c, int id, const sdrx_postfilter_cfg *cfg, const float *taps)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (c->finalized)
+        return fail(c, SDRX_ESTATE, "sdrx_set_postfilter after sdrx_finalize");
+    if (!cfg || id < 0 || id >= (int)c->nodes.size())
+        return fail(c, SDRX_EINVAL, "sdrx_set_postfilter: bad vfo id %d or null settings", id);
+    PostCfg p;
+    memcpy(&p, cfg, sizeof p);
+    if (const char *why = postdet_args(p))
+        return fail(c, SDRX_EINVAL, "sdrx_set_postfilter: vfo %d: %s", id, why);
+    if (p.ntaps > 0 && !taps)
+        return fail(c, SDRX_EINVAL, "sdrx_set_postfilter: vfo %d: null taps", id);
+    Node &n = c->nodes[(size_t)id];
+    if (p.ntaps == 0) {
+        n.post_taps.clear();
+        n.post_decim = 1;
+    } else {
+        n.post_taps.assign(taps, taps + p.ntaps);
+        n.post_decim = p.decim;
+    }
+    return SDRX_OK;
+}
+
+int sdrx_get_postfilter(sdrx_ctx *c, int id, sdrx_postfilter_info *info, float *taps, int32_t cap)
+{
+    if (!c)
+        return SDRX_EINVAL;
+    if (!info || id < 0 || id >= (int)c->nodes.size())
+        return fail(c, SDRX_EINVAL, "sdrx_get_postfilter: bad vfo id %d or null output", id);
+    const Node &n = c->nodes[(size_t)id];
+    if (n.post_taps.empty())
+        return fail(c, SDRX_ESTATE, "sdrx_get_postfilter: vfo %d has no post-detection filter", id);
+    memset(info, 0, sizeof *info);
+    info->decim = n.post_decim;
+    info->ntaps = (int32_t)n.post_taps.size();
+    info->out_len = c->finalized ? detect_out(n) : 0;
+    info->delay_samples = ((double)n.post_taps.size() - 1) / 2.0;
+    if (taps && cap > 0)
+        memcpy(taps, n.post_taps.data(), sizeof(float) * std::min((size_t)cap, n.post_taps.size()));
+    return SDRX_OK;
+}
+
+int sdrx_postfilter_design(double fs, double cutoff_hz, int32_t ntaps, double atten_db, float *taps, int32_t cap, sdrx_postfilter_info *info)
+{
+    if (taps && cap < ntaps)
+        return fail(nullptr, SDRX_EINVAL, "sdrx_postfilter_design: room for %d taps, %d asked for", cap, ntaps);
+    double pass = 0, stop = 0;
+    const int rc = postdet_design(fs, cutoff_hz, ntaps, atten_db, taps, &pass, &stop);
+    if (rc == 1)
+        return fail(nullptr, SDRX_EINVAL, "sdrx_postfilter_design: atten_db must be above 50 and at most 120, ntaps in 1 .. 256, fs and cutoff_hz positive");
+    if (rc == 2)
+        return fail(nullptr, SDRX_EFILTER, "sdrx_postfilter_design: %d taps at %g dB: the transition around %g Hz does not fit into 0 .. %g Hz", ntaps, atten_db,
+                    cutoff_hz, fs / 2);
+    if (info) {
+        memset(info, 0, sizeof *info);
+        info->ntaps = ntaps;
+        info->delay_samples = ((double)ntaps - 1) / 2.0;
+        info->pass_hz = pass, info->stop_hz = stop;
+    }
     return SDRX_OK;
 }
 

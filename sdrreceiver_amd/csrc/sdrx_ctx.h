@@ -11,6 +11,8 @@ enum Kind { KIND_MIX_ROOT = 0, KIND_MIX_SUB = 1, KIND_LATE_DEC = 2, KIND_DEMOD =
 // The detector leaves' two block launches (detect.hip) are kinds of the leaf tail's plan only: sdrx_get_kernel_times keeps its
 // SDRX_NKERNELS kinds and books them with k_compress, the payload kernel of the other non-USB leaves (bracket_kind).
 constexpr int KIND_DETECT_AM = SDRX_NKERNELS, KIND_DETECT_FM = SDRX_NKERNELS + 1;
+// ... and the same two for the leaves with a post-detection filter (postdet.hip): work lists of their own
+constexpr int KIND_DETECT_AM_POST = SDRX_NKERNELS + 2, KIND_DETECT_FM_POST = SDRX_NKERNELS + 3;
 inline int bracket_kind(int kind) { return kind >= SDRX_NKERNELS ? (int)KIND_COMPRESS : kind; }
 const char *kKindNames[SDRX_NKERNELS] = {"k_mix_decimate(level0)", "k_mix_decimate(sub)", "k_late_decimate", "k_usb_demod",
                                          "k_compress",             "k_ingest",            "k_mix_levels",    "k_lpf_long"};
@@ -49,13 +51,17 @@ struct Node {
     int d5_index = -1;      // its K5Vfo (a detector leaf: in place of d3_index)
     size_t off_part[2] = {0, 0};  //   ... AM: the carrier's block partials per frame parity
     size_t off_zprev[2] = {0, 0}; //   ... FM: z[-1] per frame parity
+    std::vector<float> post_taps; // sdrx_set_postfilter: h[0 .. T) (empty: no post-detection filter)
+    int post_decim = 1;           //   ... R; the leaf leaves as n_f / R int16
+    size_t off_post_taps = 0, off_post_hist[2] = {0, 0}; //   ... the taps, and pre[-(T-1) .. -1] per frame parity
     bool has_stream = true; // decimate[d] of every frame is kept in HBM (false: a fused late decimation writes only z', a fused demodulation only the payload)
     int meter_first = 0, meter_n = 0; // option meter: this leaf's records, slots [meter_first, meter_first + meter_n) behind the payloads
     int meter_shift = 0;              //   ... fuse_demod: the record of a mix item is s_first_out >> meter_shift
 };
 
 // sdrx_meter::n_values of a leaf: the int16 of a USB or a detector leaf, the two int8 a sample of an IQ leaf
-inline uint32_t meter_n_values(const Node &n) { return (uint32_t)(n.d.demod_usb ? n.n_out : n.detector ? n.n_f : 2 * n.n_f); }
+inline int detect_out(const Node &n) { return n.post_taps.empty() ? n.n_f : n.n_f / n.post_decim; } // a detector leaf's int16 per frame
+inline uint32_t meter_n_values(const Node &n) { return (uint32_t)(n.d.demod_usb ? n.n_out : n.detector ? detect_out(n) : 2 * n.n_f); }
 
 struct Launch1 { // one k_mix_decimate launch (a tree level)
     int kind;
@@ -226,14 +232,14 @@ struct sdrx_ctx : CtxBuffers {
     struct Catchup {
         struct Leaf {
             std::vector<K1Work> mix;        // its items of its level's k_mix_decimate launch
-            std::vector<BlockWork> blk[6];  // its blocks per block kernel: 0 late decimation, 1 demodulation, 2 long low-pass, 3 compress, 4 AM detector, 5 FM detector
+            std::vector<BlockWork> blk[8];  // its blocks per block kernel: 0 late decimation, 1 demodulation, 2 long low-pass, 3 compress, 4 AM detector, 5 FM detector, 6 / 7 the same with a post-detection filter
             std::vector<int> mrel;          //   ... and the record offsets of blk[2] (option meter)
             long long frame = -1;           // the frame its present active state began with a catch-up of; -1: it did not
             unsigned long long sum_sq = 0;  // that frame's meter, folded as sdrx_get_meters folds it
             uint32_t clipped = 0, peak = 0;
         };
         std::vector<Leaf> leaf; // per node
-        static int slot(int kind) { return kind == KIND_LATE_DEC ? 0 : kind == KIND_DEMOD ? 1 : kind == KIND_LPF_LONG ? 2 : kind == KIND_DETECT_AM ? 4 : kind == KIND_DETECT_FM ? 5 : 3; }
+        static int slot(int kind) { return kind == KIND_LATE_DEC ? 0 : kind == KIND_DEMOD ? 1 : kind == KIND_LPF_LONG ? 2 : kind == KIND_DETECT_AM ? 4 : kind == KIND_DETECT_FM ? 5 : kind == KIND_DETECT_AM_POST ? 6 : kind == KIND_DETECT_FM_POST ? 7 : 3; }
     } cu;
 
     // A setting that changes between frames, as the host keeps it for what has not been delivered yet: a frame f >= since ran
@@ -550,6 +556,7 @@ struct sdrx_ctx : CtxBuffers {
     int root_frame = 0; // samples_per_buffer of the parent-less VFOs
     size_t off_k1vfo = 0;
     size_t off_k2 = 0, off_k4 = 0, off_k5 = 0; // the K2Vfo / K4Vfo / K5Vfo arrays (sdrx_set_gains patches their gain)
+    size_t off_k5post = 0;                     // the K5Post array beside K5Vfo's (only with a post-detection filter somewhere)
     std::vector<Launch1> l1;
     std::vector<LaunchB> lb;
     std::vector<int> publish_order;

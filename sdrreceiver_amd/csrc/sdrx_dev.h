@@ -197,6 +197,15 @@ struct K5Vfo {
 };
 static_assert(sizeof(K5Vfo) % 8 == 0, "K5Vfo array stride");
 
+// ---- the post-detection filter of a detector leaf (postdet.hip, sdrx_postdet.h): an array beside K5Vfo's, entry for entry, that
+// exists only where some leaf has the filter (K5Vfo and what a tree without one allocates stay what they were)
+struct K5Post {
+    const float *taps; // h[0 .. ntaps)
+    float *hist[2];    // pre[-(ntaps-1) .. -1] of the frame of this parity (the tail of the frame before wrote it; zero for a new vfo)
+    int ntaps, decim;  // 0, 0: this leaf has no filter (it is on k_detect's lists)
+};
+static_assert(sizeof(K5Post) % 8 == 0, "K5Post array stride");
+
 struct NcoInit {
     float2 *cp;
     float rot_re, rot_im;

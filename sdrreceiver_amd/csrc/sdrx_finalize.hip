@@ -35,7 +35,10 @@ struct Built { // host copies of what goes to the arena, and where
     std::vector<K3Vfo> d3;
     std::vector<K4Vfo> d4;
     std::vector<K5Vfo> d5;
+    std::vector<K5Post> d5p; // (empty unless some detector leaf has a post-detection filter; then one entry per K5Vfo)
     std::vector<BlockWork> w2a, w2, w3, w4, w5am, w5fm; // (the detector leaves' blocks: one list per kind, one descriptor array)
+    std::vector<BlockWork> w5amp, w5fmp;                // (... and of the leaves with a post-detection filter)
+    size_t o5p = 0, ow5amp = 0, ow5fmp = 0;
     std::vector<int> n2a, n2, n3, n4, n5; // node index of each descriptor
     size_t o2a = 0, o2 = 0, o3 = 0, o4 = 0, o5 = 0, ow2a = 0, ow2 = 0, ow3 = 0, ow4 = 0, ow5am = 0, ow5fm = 0;
     std::vector<K1Work> all_items; // k_mix_levels: every level's items in one array ...
@@ -160,6 +163,14 @@ int derive_nodes(sdrx_ctx *c)
             return fail(c, SDRX_EINVAL, "vfo %d has children but demod_usb set", i);
         if (!n.leaf && n.detector)
             return fail(c, SDRX_EINVAL, "vfo %d has children but a detector set (sdrx_set_detector)", i);
+        if (!n.post_taps.empty()) {
+            if (!n.detector)
+                return fail(c, SDRX_EINVAL, "vfo %d carries a post-detection filter (sdrx_set_postfilter) but no detector", i);
+            if (n.n_f % n.post_decim)
+                return fail(c, SDRX_EUNSUPPORTED, "vfo %d: %d samples per frame is not a multiple of the post-detection decimation %d", i, n.n_f,
+                            n.post_decim);
+            n.rate = (unsigned)target / (unsigned)n.post_decim;
+        }
         max_level = std::max(max_level, n.level);
     }
     c->n_levels = max_level + 1;
@@ -232,7 +243,7 @@ void plan_buffers(sdrx_ctx *c, Built &B)
             if (d.demod_usb)
                 n.pay_len = (uint32_t)(n.n_out * 2);
             else if (n.detector)
-                n.pay_len = (uint32_t)(2 * n.n_f); // n int16: exactly the bytes of the IQ leaf's int8 pairs
+                n.pay_len = (uint32_t)(2 * detect_out(n)); // n int16: exactly the bytes of the IQ leaf's int8 pairs (n / R with a post-detection filter)
             else
                 n.pay_len = (uint32_t)(d.cstyle == 1 ? n.n_f : 2 * n.n_f); // vfo.cpp:143-150
             B.pay = align_up(B.pay + n.pay_len, 64);
@@ -243,7 +254,11 @@ void plan_buffers(sdrx_ctx *c, Built &B)
                     n.off_part[p] = plan.take(sizeof(unsigned long long) * (size_t)detect_blocks(n.n_f));
                 if (n.detector == kDetFm)
                     n.off_zprev[p] = plan.take(sizeof(float2));
+                if (!n.post_taps.empty()) // the post-detection filter's history: T - 1 floats (a slot of its own even for T = 1)
+                    n.off_post_hist[p] = plan.take(sizeof(float) * std::max<size_t>(n.post_taps.size() - 1, 1));
             }
+            if (!n.post_taps.empty())
+                n.off_post_taps = B.place_taps(n.post_taps);
         }
         // SURVEY.md 8d algorithmic bytes: cf32 consumed + what this VFO hands on
         c->alg_bytes += 8ll * d.samples_per_buffer + (n.leaf ? (int64_t)n.pay_len : 8ll * n.n_f);
@@ -382,7 +397,7 @@ int build_mix_work(sdrx_ctx *c, Built &B)
 void build_tail_work(sdrx_ctx *c, Built &B)
 {
     const int N = (int)c->nodes.size();
-    int64_t b2 = 0, b3 = 0, b5am = 0, b5fm = 0;
+    int64_t b2 = 0, b3 = 0, b5am = 0, b5fm = 0, b5amp = 0, b5fmp = 0;
     int lds2a = 0;
     auto two_kernel_late = [](const Node &n) { return n.leaf && n.d.demod_usb && n.d.late_decimate > 0 && !n.fused_late; };
     // every late-decimating VFO left to a kernel of its own has L in {5,6} and <= 96 taps: one-wave tiles of k_late_decimate4,
@@ -437,13 +452,14 @@ void build_tail_work(sdrx_ctx *c, Built &B)
                 B.d4.push_back(K4Vfo{});
             }
         } else if (n.detector) {
-            std::vector<BlockWork> &w = n.detector == kDetAm ? B.w5am : B.w5fm;
+            const bool post = !n.post_taps.empty();
+            std::vector<BlockWork> &w = n.detector == kDetAm ? (post ? B.w5amp : B.w5am) : (post ? B.w5fmp : B.w5fm);
             for (int b = 0; b < detect_blocks(n.n_f); ++b)
                 w.push_back({(int)B.d5.size(), b});
             n.d5_index = (int)B.d5.size();
             B.n5.push_back(i);
             B.d5.push_back(K5Vfo{});
-            (n.detector == kDetAm ? b5am : b5fm) += n.pay_len;
+            (n.detector == kDetAm ? (post ? b5amp : b5am) : (post ? b5fmp : b5fm)) += n.pay_len;
         } else {
             for (int b = 0; b < (n.n_f + 4095) / 4096; ++b)
                 B.w3.push_back({(int)B.d3.size(), b});
@@ -502,6 +518,20 @@ void build_tail_work(sdrx_ctx *c, Built &B)
         if (!B.w5fm.empty()) {
             B.ow5fm = plan.take(sizeof(BlockWork) * B.w5fm.size());
             c->lb.push_back({KIND_DETECT_FM, (int)B.w5fm.size(), B.o5, B.ow5fm, 0, b5fm});
+        }
+        c->off_k5post = 0;
+        if (!B.w5amp.empty() || !B.w5fmp.empty()) { // the leaves with a post-detection filter: K5Post beside K5Vfo, lists of their own
+            B.d5p.assign(B.d5.size(), K5Post{});
+            B.o5p = plan.take(sizeof(K5Post) * B.d5p.size());
+            c->off_k5post = B.o5p;
+        }
+        if (!B.w5amp.empty()) {
+            B.ow5amp = plan.take(sizeof(BlockWork) * B.w5amp.size());
+            c->lb.push_back({KIND_DETECT_AM_POST, (int)B.w5amp.size(), B.o5, B.ow5amp, 0, b5amp});
+        }
+        if (!B.w5fmp.empty()) {
+            B.ow5fmp = plan.take(sizeof(BlockWork) * B.w5fmp.size());
+            c->lb.push_back({KIND_DETECT_FM_POST, (int)B.w5fmp.size(), B.o5, B.ow5fmp, 0, b5fmp});
         }
     }
 }
@@ -870,6 +900,14 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
         k.n = n.n_f;
         k.kind = n.detector;
         k.meter_rel = c->opt_meter ? meter_rel(c, n) : 0;
+        if (!n.post_taps.empty()) {
+            K5Post &kp = B.d5p[q];
+            kp.taps = reinterpret_cast<const float *>(P(n.off_post_taps));
+            for (int p = 0; p < 2; ++p)
+                kp.hist[p] = reinterpret_cast<float *>(P(n.off_post_hist[p]));
+            kp.ntaps = (int)n.post_taps.size();
+            kp.decim = n.post_decim;
+        }
     }
     auto up = [&](size_t off, const void *src, size_t bytes) -> hipError_t {
         return bytes ? hipMemcpyAsync(P(off), src, bytes, hipMemcpyHostToDevice, c->st.stream) : hipSuccess;
@@ -889,6 +927,9 @@ int allocate_and_upload(sdrx_ctx *c, Built &B)
     HIPCHK(c, up(B.o5, B.d5.data(), sizeof(K5Vfo) * B.d5.size()));
     HIPCHK(c, up(B.ow5am, B.w5am.data(), sizeof(BlockWork) * B.w5am.size()));
     HIPCHK(c, up(B.ow5fm, B.w5fm.data(), sizeof(BlockWork) * B.w5fm.size()));
+    HIPCHK(c, up(B.o5p, B.d5p.data(), sizeof(K5Post) * B.d5p.size()));
+    HIPCHK(c, up(B.ow5amp, B.w5amp.data(), sizeof(BlockWork) * B.w5amp.size()));
+    HIPCHK(c, up(B.ow5fmp, B.w5fmp.data(), sizeof(BlockWork) * B.w5fmp.size()));
     if (c->fp.usable) {
         HIPCHK(c, up(c->fp.off_items, B.all_items.data(), sizeof(K1Work) * B.all_items.size()));
         HIPCHK(c, up(c->fp.off_item_level, B.all_item_level.data(), sizeof(int) * B.all_item_level.size()));
@@ -1083,6 +1124,10 @@ void catchup_setup(sdrx_ctx *c, const Built &B)
         c->cu.leaf[(size_t)B.n5[(size_t)w.vfo]].blk[4].push_back(w);
     for (const BlockWork &w : B.w5fm)
         c->cu.leaf[(size_t)B.n5[(size_t)w.vfo]].blk[5].push_back(w);
+    for (const BlockWork &w : B.w5amp)
+        c->cu.leaf[(size_t)B.n5[(size_t)w.vfo]].blk[6].push_back(w);
+    for (const BlockWork &w : B.w5fmp)
+        c->cu.leaf[(size_t)B.n5[(size_t)w.vfo]].blk[7].push_back(w);
 }
 
 // Option adc_meter: what k_adc_meter needs for this context's frames -- one partial per workgroup of a frame, the launch's

@@ -417,6 +417,13 @@ void launch_block_list(sdrx_ctx *c, const LaunchB &L, hipStream_t ts, unsigned l
         } else if (L.kind == KIND_DETECT_FM)
             hipLaunchKernelGGL((k_detect<kDetFm, METER(), PARK()>), grid, dim3(kDetThreads), 0, ts, reinterpret_cast<const K5Vfo *>(desc), w, frame,
                                park_arg<PARK()>(c, c->park.o_5));
+        else if (L.kind == KIND_DETECT_AM_POST) { // the same two passes, the second one through the post-detection filter
+            hipLaunchKernelGGL((k_env_sum<PARK()>), grid, dim3(kDetThreads), 0, ts, reinterpret_cast<const K5Vfo *>(desc), w, frame, park_arg<PARK()>(c, c->park.o_5));
+            hipLaunchKernelGGL((k_detect_post<kDetAm, METER(), PARK()>), grid, dim3(kDetThreads), 0, ts, reinterpret_cast<const K5Vfo *>(desc),
+                               reinterpret_cast<const K5Post *>(c->arena + c->off_k5post), w, frame, park_arg<PARK()>(c, c->park.o_5));
+        } else if (L.kind == KIND_DETECT_FM_POST)
+            hipLaunchKernelGGL((k_detect_post<kDetFm, METER(), PARK()>), grid, dim3(kDetThreads), 0, ts, reinterpret_cast<const K5Vfo *>(desc),
+                               reinterpret_cast<const K5Post *>(c->arena + c->off_k5post), w, frame, park_arg<PARK()>(c, c->park.o_5));
         else
             hipLaunchKernelGGL((k_compress<METER(), PARK()>), grid, dim3(256), 0, ts, reinterpret_cast<const K3Vfo *>(desc), w, frame,
                                park_arg<PARK()>(c, c->park.o_3));

@@ -52,6 +52,8 @@ void leaf_regions(sdrx_ctx *c, int id, unsigned prev_open, const std::function<v
             put(c->arena + nd.off_u[p], (size_t)nd.Hu, 0, 0, true);
         if (nd.detector == kDetFm) // z[-1] = 0 + 0j: the one place a detector leaf's start as a new vfo is defined (AM carries nothing)
             put(c->arena + nd.off_zprev[p], 2, 0, 0, true);
+        if (nd.post_taps.size() > 1) // the post-detection filter's history = +0.0f: a new vfo's, defined here alone
+            put(c->arena + nd.off_post_hist[p], nd.post_taps.size() - 1, 0, 0, true);
     }
     if (sq >= 0) { // the gate state of sdrx_finalize; thresholds, hang time, ratio and window stay
         put(c->sq.d_hang + sq, 1, 0, 0, true);

@@ -17,7 +17,7 @@ import dataclasses
 
 import numpy as np
 
-from . import _lib, agc as _agc, blank as _blank, iqbal as _iqbal, drift as _drift, front as _front, ingest, meter, notch as _notch, resample as _resample, scan as _scan, shift as _shift, squelch as _squelch, wake as _wake, watch as _watch
+from . import _lib, agc as _agc, blank as _blank, postdet, iqbal as _iqbal, drift as _drift, front as _front, ingest, meter, notch as _notch, resample as _resample, scan as _scan, shift as _shift, squelch as _squelch, wake as _wake, watch as _watch
 from .topology import Topology, VfoDesc
 
 
@@ -420,6 +420,8 @@ class Receiver(_LeafCalls):
         self.descs.append(d)
         if d.detector:
             self.set_detector(out.value, d.detector)
+        if len(d.post_taps):
+            self.set_postfilter(out.value, d.post_taps, d.post_decim)
         return out.value
 
     def set_detector(self, vid: int, kind: int) -> None:
@@ -435,6 +437,26 @@ class Receiver(_LeafCalls):
         cfg = _lib.DetectCfgC()
         self._chk(self.L.sdrx_get_detector(self.h, int(vid), C.byref(cfg)))
         return int(cfg.kind)
+
+    def set_postfilter(self, vid: int, taps, decim: int = 1) -> None:
+        """Before finalize: detector leaf `vid` leaves through a FIR of `taps` (float32, 1 .. 256) over the detector's floats,
+        decimated by `decim` (1 .. 16): n / decim int16 per frame (sdrreceiver_amd.postdet).  No taps (None or empty) take the
+        filter away."""
+        h = np.ascontiguousarray(() if taps is None else taps, dtype=np.float32).reshape(-1)
+        cfg = _lib.PostfilterCfgC(decim=int(decim) if h.size else 0, ntaps=int(h.size))
+        self._chk(self.L.sdrx_set_postfilter(self.h, int(vid), C.byref(cfg), h.ctypes.data if h.size else None))
+        if 0 <= vid < len(self.descs):
+            self.descs[vid] = dataclasses.replace(self.descs[vid], post_taps=tuple(h.tolist()), post_decim=int(decim) if h.size else 1)
+
+    def postfilter(self, vid: int) -> dict:
+        """The post-detection filter of VFO `vid`: :func:`sdrreceiver_amd.postdet.info_dict` plus ``taps`` (float32).  SdrxError
+        (SDRX_ESTATE) for a node without one."""
+        info = _lib.PostfilterInfoC()
+        h = np.zeros(postdet.MAX_TAPS, np.float32)
+        self._chk(self.L.sdrx_get_postfilter(self.h, int(vid), C.byref(info), h.ctypes.data, h.size))
+        out = postdet.info_dict(info)
+        out["taps"] = h[:info.ntaps].copy()
+        return out
 
     def finalize(self):
         if self._input_rate:
@@ -919,7 +941,7 @@ class Group(_LeafCalls):
     def from_topology(cls, topo: Topology, devices, **kw) -> "Group":
         g = cls(devices, **kw)
         for d in topo.vfos:
-            if d.detector:
+            if d.detector or len(d.post_taps):
                 raise ValueError("groups do not offer detector leaves (include/sdrx.h \"Detector leaves\")")
             c = _lib.desc_to_c(d)
             out = C.c_int(-1)
@@ -1057,6 +1079,10 @@ class vfo:  # noqa: N801  (the reference's class name, vfo.h:11)
     def setDemodUSB(self, usb): self.desc.demod_usb = bool(usb)
     def getDemodUSB(self): return self.desc.demod_usb
     def setDetector(self, kind): self.desc.detector = int(kind)  # (no counterpart in vfo.h: sdrx_set_detector, 0 none / 1 AM / 2 FM)
+
+    def setPostFilter(self, taps, decim=1):  # (no counterpart in vfo.h: sdrx_set_postfilter on a detector leaf)
+        self.desc.post_taps = tuple(np.asarray(() if taps is None else taps, np.float32).reshape(-1).tolist())
+        self.desc.post_decim = int(decim) if self.desc.post_taps else 1
     def setCompressonStyle(self, st): self.desc.cstyle = int(st)  # sic
     def setScaleComp(self, scale): self.desc.scalecomp = int(scale)
     def setZmqTopic(self, topic): self.desc.topic = str(topic)

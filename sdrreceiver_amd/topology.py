@@ -25,7 +25,8 @@ SUPPORTED_RATES = (288000, 1536000, 1920000)  # mainwindow.h:29
 class VfoDesc:
     """One VFO node.  Field <-> reference setter (vfo.h:21-38):
 
-    (``detector`` has no reference setter: include/sdrx.h "Detector leaves", sdrreceiver_amd.detect.)
+    (``detector`` has no reference setter: include/sdrx.h "Detector leaves", sdrreceiver_amd.detect; nor have ``post_taps`` and
+    ``post_decim``: include/sdrx.h "Post-detection filter", sdrreceiver_amd.postdet.)
 
     fs <-> setFs, decimate_count <-> setDecimationCount, mixer_freq <-> setMixerFreq,
     demod_usb <-> setDemodUSB, filter_bw <-> setFilterBandwidth, gain <-> setGain,
@@ -47,6 +48,8 @@ class VfoDesc:
     scalecomp: int = 1
     samples_per_buffer: int = 0
     detector: int = 0  # sdrx_set_detector (no counterpart in the reference): 0 none, 1 AM, 2 FM -- a leaf with demod_usb False only
+    post_taps: tuple = ()  # sdrx_set_postfilter (no counterpart in the reference): the FIR's float32 taps -- a detector leaf only; () none
+    post_decim: int = 1    #   ... and its decimation R: the leaf leaves as n / R int16 at rate / R
 
     @property
     def out_rate_stage(self) -> int:
@@ -71,6 +74,16 @@ class VfoDesc:
         if self.demod_usb and self.late_decimate > 0:
             n //= self.late_decimate
         return n
+
+    @property
+    def n_detect_out(self) -> int:
+        """int16 values per frame of a detector leaf: n, or n / R behind a post-detection filter"""
+        return self.n_stage_out // self.post_decim if len(self.post_taps) else self.n_stage_out
+
+    @property
+    def detect_rate(self) -> int:
+        """the rate a detector leaf publishes at: fs / 2^decimate_count, or that / R behind a post-detection filter"""
+        return self.out_rate_stage // self.post_decim if len(self.post_taps) else self.out_rate_stage
 
 
 @dataclass
@@ -251,6 +264,15 @@ def topology_from_ini(text: str, name: str = "", mix_offset: int | None = None) 
         if det_key not in ("", "am", "fm"):
             raise ValueError(f"vfos/{i}: detector={det_key!r}: only am and fm are offered")
         detector = {"": 0, "am": 1, "fm": 2}[det_key]
+        # `post_decim`, `post_taps`, `post_cutoff_hz`, `post_atten_db` (no keys of the reference): all four or none, on an entry
+        # with `detector=` -- its post-detection filter (sdrreceiver_amd.postdet), designed at the leaf's rate
+        post_keys = ("post_decim", "post_taps", "post_cutoff_hz", "post_atten_db")
+        post_given = [k for k in post_keys if kv.get(p + k, "").strip() != ""]
+        if post_given and len(post_given) != len(post_keys):
+            raise ValueError(f"vfos/{i}: {', '.join(post_given)} given without {', '.join(k for k in post_keys if k not in post_given)}: "
+                             "the post-detection filter takes all four keys or none")
+        if post_given and not detector:
+            raise ValueError(f"vfos/{i}: post_decim, post_taps, post_cutoff_hz and post_atten_db belong to an entry with detector=am|fm")
         if detector and out_rate == 0:
             out_rate = 48000
         if out_rate <= 0:
@@ -278,10 +300,22 @@ def topology_from_ini(text: str, name: str = "", mix_offset: int | None = None) 
                              "which runs in front of the USB demodulation only: give the entry a main VFO whose out_rate is a power of two "
                              "times its own")
         if detector:
-            topo.vfos.append(VfoDesc(
+            desc = VfoDesc(
                 topic=kv.get(p + "topic", ""), parent=mains[main_idx], fs=main_out, decimate_count=d,
                 mixer_freq=float((center - main_vfo_freq) - vfo_freq), demod_usb=False, gain=gain, cstyle=0,
-                samples_per_buffer=main_out // bufsplit, detector=detector))
+                samples_per_buffer=main_out // bufsplit, detector=detector)
+            if post_given:
+                from . import postdet
+                try:
+                    R, T = int(kv[p + "post_decim"]), int(kv[p + "post_taps"])
+                    why = postdet.refusal(T, R, desc.n_stage_out)
+                    if why:
+                        raise ValueError(why)
+                    taps, _ = postdet.design(desc.out_rate_stage, float(kv[p + "post_cutoff_hz"]), T, float(kv[p + "post_atten_db"]))
+                except ValueError as e:
+                    raise ValueError(f"vfos/{i}: post-detection filter: {e}") from None
+                desc = replace(desc, post_taps=tuple(taps.tolist()), post_decim=R)
+            topo.vfos.append(desc)
             continue
         topo.vfos.append(VfoDesc(
             topic=kv.get(p + "topic", ""), parent=mains[main_idx], fs=main_out, decimate_count=d,
